@@ -8,17 +8,21 @@
 
 One "step" = one pass of the hot path over one batch of synthetic input: all reads of the workload
 searched (both strands) against the resident synthetic 3 Gbp genome - search kernel, bin sort of the
-hits, record assembly - and, for N > 1, ONE exchange of 8-byte hit records over RCCL plus the merge:
+hits, record assembly - and, for N > 1, ONE exchange of 8-byte hit records over RCCL plus the merge; with --full
 both shapes are timed and reported (`exchanges`): "root" = the single gather to rank 0 (north star; the headline `value`),
 "reads" = every rank gathers and merges its read range (result stays distributed).  Inputs (packed genome planes) are
 resident in HBM before the timed region starts; results stay in HBM.  The genome is sharded by position range across ranks
 (total work fixed => strong scaling).  Rank 0 prints ONE JSON line.
 
+A plain run does what its headline needs: set up, W warm-up steps, K timed steps, the outputs (--dump-outputs DIR), the
+line.  --full adds everything else the benchmark measures: the CPU baseline (one GPU), both exchange shapes and the C-ABI
+driver's line (N > 1).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64).
+
 Two multi-GPU drivers share the kernels and the exchange record:
   --multi torch   one process per GPU over torch.distributed / RCCL (varscot_amd/dist.py) - what the launcher contract starts
   --multi abi     ONE process over the N devices behind the C ABI (vsc_multi_*: what `bidir_mapping -D 0,..,N-1` executes)
-  --multi both    (default for N > 1) the torch path is the headline; rank 0 first runs the abi path as a child process - before
-                  it touches a GPU itself - and embeds that line as `multi_abi`
+  --multi both    (default for N > 1 with --full) the torch path is the headline; rank 0 first runs the abi path as a child
+                  process - before it touches a GPU itself - and embeds that line as `multi_abi`
 """
 import argparse
 import json
@@ -54,6 +58,10 @@ KERNEL_SOURCES = ("vsc_seed.hip", "vsc_kernels.hip", "vsc_sort.hip", "vsc_device
 
 # pair-node forest walk: 15.2 vector instructions per step (2 levels), ~40 SIMD-cycles at the costs of tools/micro/valu_kinds.hip
 FOREST_CYCLES_PER_INSTRUCTION = 2.6
+
+# --dump-outputs: the sampled arrays (float64) take at most this much; the counts beside them are a few bytes
+DUMP_SAMPLE_BYTES = 48 << 20
+DUMP_SEED = 0x5EED0D00
 
 
 def kernel_sources_sha():
@@ -96,11 +104,11 @@ def parse():
     ap.add_argument("--exchange", default="root", choices=["reads", "root"],
                     help="multi-rank exchange of the hit records that `value` reports: 'root' = everything to rank 0 (the north "
                          "star's single gather), 'reads' = every rank gathers and merges its read range (all-to-all, result stays "
-                         "distributed); both are timed and reported")
+                         "distributed); with --full both are timed and reported")
     ap.add_argument("--multi", default=None, choices=["torch", "abi", "both"],
                     help="multi-GPU driver: torch = one process per GPU (torch.distributed / RCCL), abi = ONE process over the "
                          "devices behind the C ABI (vsc_multi_*), both = torch as the headline + the abi line embedded (default "
-                         "for N > 1)")
+                         "for N > 1 with --full)")
     ap.add_argument("--abi-devices", default=None,
                     help="--multi abi: the device list, e.g. 0,0,0,0 (ids may repeat: a rehearsal of N shards on one GPU); "
                          "default 0..gpus-1")
@@ -119,7 +127,17 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check without a GPU: the ranks form the process group (gloo with --rehearse), all-reduce "
                          "once, rank 0 prints a JSON line saying what the communicator reported")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the CPU baseline (one GPU; --no-cpu-baseline still leaves "
+                         "it out), both exchange shapes and, with --multi both (then the default), the C-ABI driver's line (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one process on one GPU: after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float64): the hit records (a fixed, seeded sample of at most %d MB) with their indices and count, "
+                         "and the feature rows of c5's fused route (taken inside that step's batch callbacks)" % (DUMP_SAMPLE_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(args):
@@ -229,6 +247,51 @@ def sort_roofline(timing_sums, steps):
             "achieved": timing_sums["sort_bytes"] / steps / (max(ms, 1e-9) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "launch_ms": ms, "partition_levels": timing_sums["sort_levels"], "first_level_bin_bits": timing_sums["sort_bin_bits"],
             "bytes": timing_sums["sort_bytes"] / steps}
+
+
+class _DeviceWords:
+    """n_words 32-bit words of the library's device memory as torch sees them, without a copy (__cuda_array_interface__)."""
+
+    def __init__(self, address, n_words):
+        self.__cuda_array_interface__ = {"shape": (n_words,), "typestr": "<i4", "data": (int(address), False), "version": 2}
+
+
+def sample_device_rows(address, n_rows, row_words, k, seed):
+    """A fixed, seeded choice of at most k of the n_rows rows (row_words uint32 each) of a device array, in ascending order:
+    (row indices int64, uint32[len(indices), row_words]).  Only the chosen rows leave the device."""
+    import torch
+    if n_rows <= k:
+        idx = np.arange(n_rows, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(seed).integers(0, n_rows, size=k, dtype=np.int64))
+    if len(idx) == 0:
+        return idx, np.zeros((0, row_words), dtype=np.uint32)
+    torch.cuda.synchronize()  # (the library writes on its own stream)
+    rows = torch.as_tensor(_DeviceWords(address, n_rows * row_words)).view(n_rows, row_words)
+    got = rows.index_select(0, torch.from_numpy(idx).to(rows.device)).cpu().numpy()
+    return idx, got.view(np.uint32)
+
+
+def hit_samples(prefix, parts):
+    """parts: [(n_records, record indices, uint32[k, 4] records, uint32[k, 16] feature rows or None)], one per hit set that
+    follows the previous one in the result (c5's batches) -> {name: float64 array}: <prefix>_count, <prefix>_index (global),
+    <prefix> (columns guide, contig, pos, info of vsc_hit) and feature_rows where the route hands rows to its caller."""
+    offsets = np.cumsum([0] + [p[0] for p in parts])
+    out = {prefix + "_count": np.array([offsets[-1]], dtype=np.float64),
+           prefix + "_index": np.concatenate([p[1] + o for p, o in zip(parts, offsets)]).astype(np.float64),
+           prefix: np.concatenate([p[2] for p in parts]).reshape(-1, 4).astype(np.float64)}
+    if parts and parts[0][3] is not None:
+        out["feature_rows"] = np.concatenate([p[3] for p in parts]).reshape(-1, 16).astype(np.float64)
+    return out
+
+
+def write_outputs(directory, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, "bench.py --dump-outputs: %d bytes" % total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    print("bench.py: %d arrays (%.1f MB) written to %s" % (len(arrays), total / 1e6, directory), file=sys.stderr)
 
 
 def run_abi_child(args):
@@ -351,7 +414,9 @@ def main_abi(args, json_fd):
 def main():
     args = parse()
     under_launcher = "WORLD_SIZE" in os.environ
-    multi = args.multi or ("both" if args.gpus > 1 else "torch")
+    multi = args.multi or ("both" if args.gpus > 1 and args.full else "torch")
+    if args.dump_outputs and (args.gpus > 1 or multi != "torch" or args.force_dist or args.dry_run):
+        raise SystemExit("bench.py --dump-outputs: one process on one GPU only (no --gpus N > 1, --multi, --force-dist or --dry-run)")
     if multi == "abi":
         # one process does everything: under a launcher that is rank 0, the others have nothing to do
         if under_launcher and int(os.environ.get("RANK", "0")) != 0:
@@ -476,6 +541,16 @@ def main():
         # guideseqOntargetActivity.txt: 0.2 .. 1.8), one per read, seeded
         guide_activity = np.random.default_rng(0x5EED0004).uniform(0.2, 1.8, size=n_guides)
 
+    # --dump-outputs on c5: the batches' results live only inside the callbacks, so the last timed step samples them there
+    capture = {"on": False, "parts": []}
+
+    def capture_batch(h, rows_dev=None):
+        n = len(h)
+        k = DUMP_SAMPLE_BYTES // (8 * (5 + (16 if rows_fused else 0))) // -(-n_guides // (args.batch or 16384))
+        idx, recs = sample_device_rows(h.device_ptr, n, 4, k, DUMP_SEED + len(capture["parts"]))
+        rows = sample_device_rows(rows_dev, n, 16, k, DUMP_SEED + len(capture["parts"]))[1] if rows_fused else None
+        capture["parts"].append((n, idx, recs, rows))
+
     def score_batch(h, first, count):
         if forest is not None:
             # (a streamed batch numbers its reads globally; a per-batch search of the multi-rank path from 0)
@@ -483,6 +558,12 @@ def main():
             forest.classify_hits(h, act, to_host=False)
         else:
             h.packed_features(to_host=False, mit=False)
+        if capture["on"]:
+            capture_batch(h)
+
+    def rows_batch(h, first, count, rows_dev):
+        if capture["on"]:
+            capture_batch(h, rows_dev)
 
     # more pieces = more of the exchange hidden, but every piece visits all site chunks again (c3 on one GPU:
     # 102 ms in one piece, 116 ms in four): 4 pieces at 2 ranks (13 GB over one link), 2 at 4, 1 at 8
@@ -565,7 +646,7 @@ def main():
         acc = new_acc()
         if not use_dist:
             if rows_fused:
-                genome.search_streamed_rows(codes, max_mm, lambda h, first, count, rows_dev: None, batch=args.batch, algorithm=algorithm)
+                genome.search_streamed_rows(codes, max_mm, rows_batch, batch=args.batch, algorithm=algorithm)
             else:
                 genome.search_streamed(codes, max_mm, score_batch, batch=args.batch, algorithm=algorithm)
             add_timing(acc, ctx.timing(), score=True)
@@ -605,7 +686,8 @@ def main():
         return [x for x in (h, m) if x is not None], len(m) if m is not None else len(h), acc
 
     def timed_run():
-        """W untimed steps, then exactly K steps between barriers; max over ranks."""
+        """W untimed steps, then exactly K steps between barriers; max over ranks.  The last step's objects are returned
+        open (what --dump-outputs reads): the caller closes them."""
         for i in range(args.warmup):
             objs, _, _ = step()
             for o in objs:
@@ -613,15 +695,17 @@ def main():
         barrier()
         for k in X_KEYS:
             xacc[k] = 0.0
-        sums, total_hits = new_acc(), 0
+        sums, total_hits, objs = new_acc(), 0, []
         t0 = time.perf_counter()
         for i in range(args.steps):
-            objs, total_hits, acc = step()
-            add_timing(sums, acc, score=True)
             for o in objs:
                 o.close()
+            capture["on"] = bool(args.dump_outputs) and i == args.steps - 1
+            objs, total_hits, acc = step()
+            add_timing(sums, acc, score=True)
         barrier()
         dt = time.perf_counter() - t0
+        capture["on"] = False
         x = dict(xacc)
         if use_dist:
             tt = torch.tensor([dt] + [x[k] for k in X_KEYS[:4]], dtype=torch.float64, device=xdev)
@@ -632,16 +716,18 @@ def main():
             for i, k in enumerate(X_KEYS[:4]):
                 x[k] = float(tt[1 + i].item())
             x["sent_bytes"], x["received_bytes"] = float(bb[0].item()), float(bb[1].item())
-        return dt, sums, total_hits, x
+        return dt, sums, total_hits, x, objs
 
     exchanges = None
-    if use_dist:
+    if use_dist and args.full:
         # both shapes of the one exchange, K steps each (plain: search, pack, exchange, merge, one after the other)
         exchanges = {}
         # (the streamed, scored workload always gathers to rank 0: one run)
         for ex in (("root",) if streamed else ("root", "reads") if args.exchange == "reads" else ("reads", "root")):
             mode.update(exchange=ex, pipelined=False)
-            dt_x, sums_x, hits_x, x = timed_run()
+            dt_x, sums_x, hits_x, x, objs = timed_run()
+            for o in objs:
+                o.close()
             exchanges[ex] = {
                 "value": n_guides * args.steps / dt_x, "unit": "guides/s", "ms_per_step": dt_x / args.steps * 1e3,
                 "search_wall_ms": x["search_ms"] / args.steps, "pack_ms": x["pack_ms"] / args.steps,
@@ -651,13 +737,25 @@ def main():
                 "result": "all records on rank 0" if ex == "root" else "every rank holds the merged records of its read range",
                 "note": "host wall times per step, max over ranks; exchanged_bytes = bytes that left a rank, summed over ranks"}
             keep = (dt_x, sums_x, hits_x)
-        mode.update(exchange=args.exchange, pipelined=True)
-        if pipelined:
-            dt, sums, total_hits, _ = timed_run()   # the headline: --exchange's gather with the exchange of one piece
-        else:                                       # hidden behind the search of the next
-            dt, sums, total_hits = keep             # (the last plain run was --exchange's)
-    else:
-        dt, sums, total_hits, _ = timed_run()
+    mode.update(exchange=args.exchange, pipelined=True)
+    if exchanges is not None and not pipelined:
+        dt, sums, total_hits = keep                 # (the last plain run was --exchange's)
+        objs = []
+    else:                                           # one GPU, or the headline alone (pipelined: --exchange's gather with the
+        dt, sums, total_hits, _, objs = timed_run()  # exchange of one piece hidden behind the search of the next)
+    if args.dump_outputs:
+        if streamed:
+            arrays = hit_samples("hits", capture["parts"])
+        else:
+            sets = list(zip(("hits_ref", "hits_snp"), objs)) if args.workload == "c4" else [("hits", objs[0])]
+            arrays = {}
+            for i, (name, h) in enumerate(sets):
+                n = len(h)
+                idx, recs = sample_device_rows(h.device_ptr, n, 4, DUMP_SAMPLE_BYTES // (8 * 5) // len(sets), DUMP_SEED + i)
+                arrays.update(hit_samples(name, [(n, idx, recs, None)]))
+        write_outputs(args.dump_outputs, arrays)
+    for o in objs:
+        o.close()
     hits_local, sites_local, passes = sums["hits"] // args.steps, sums["sites"], sums["passes"]
     pairs_local, stream_bytes = sums["pairs"] // args.steps, sums["genome_bytes"] // args.steps
     if use_dist:
@@ -818,7 +916,7 @@ def main():
             # the same workload through the product's own multi-device driver (one process over the devices, vsc_multi_*)
             out["multi_abi"] = abi_line if "error" in abi_line else {
                 k: abi_line.get(k) for k in ("value", "unit", "ms_per_step", "n_gpus", "steps", "config", "vsc_multi_timing", "n_gt_1_rccl_executed")}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(total_bases, max_mm, args.cpu_sample_bases)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
 

@@ -73,7 +73,7 @@ timeout -k 10 500 python3 $ROOT/bench.py --workload c5 --steps 1 --warmup 1 --no
 timeout -k 10 400 python3 $ROOT/bench.py --multi abi --gpus 1 --workload c3 --steps 5 --warmup 2 > "$OUT/bench_abi_c3_x1.json" 2> "$OUT/bench_abi_c3_x1.err" || true
 timeout -k 10 400 python3 $ROOT/bench.py --multi abi --gpus 4 --abi-devices 0,0,0,0 --workload c3 --steps 5 --warmup 2 > "$OUT/bench_abi_c3_x4_one_gpu.json" 2> "$OUT/bench_abi_c3_x4_one_gpu.err" || true
 timeout -k 10 400 python3 $ROOT/bench.py --multi abi --gpus 2 --abi-devices 0,0 --workload c5 --guides 40000 --batch 5000 --steps 1 --warmup 1 > "$OUT/bench_abi_c5_x2_one_gpu.json" 2> "$OUT/bench_abi_c5_x2_one_gpu.err" || true
-timeout -k 10 500 python3 $ROOT/bench.py --workload c3 --steps 3 --warmup 1 > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || true
+timeout -k 10 500 python3 $ROOT/bench.py --workload c3 --steps 3 --warmup 1 --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || true
 fi
 find "$OUT" -name '*kernel_trace.csv' -delete
 du -sh "$OUT"

@@ -71,11 +71,11 @@ PY
 collect)
     bash tools/collect_profiles.sh "${1:-r03}";;
 final)
-    # what the driver runs at the end of a round, in one go: smoke, the GPU suite, the default bench line
+    # smoke, the GPU suite and the default bench line in one go (--full: with the CPU baseline)
     python3 -c "import __graft_entry__ as g; g.smoke()" || exit 1
     timeout -k 10 1000 python3 -m pytest tests -m gpu -x -q > "$OUT/pytest.log" 2>&1 || { tail -5 "$OUT/pytest.log"; exit 1; }
     tail -2 "$OUT/pytest.log"
-    timeout -k 10 300 python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
+    timeout -k 10 300 python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
     line "$OUT/bench_default.json";;
 bw)
     timeout -k 10 300 python3 - <<'PY'
