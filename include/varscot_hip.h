@@ -227,6 +227,44 @@ int vsc_search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *gu
 typedef int (*vsc_rows_batch_fn)(void *user, vsc_hits *batch, uint32_t first_guide, uint32_t n_guides, const void *rows_dev);
 int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                            const vsc_search_params *params, uint32_t batch_reads, vsc_rows_batch_fn on_batch, void *user);
+/*
+ * Per-guide off-target summary: what a guide-library screen asks of the search (how specific is each guide?) without
+ * the records.  The counted hits of guide i are exactly the hits vsc_search returns for the same genome, guides and
+ * params, minus the one at exclude[i] if that locus is a hit.  Over them:
+ *   nm[k]      hits with NM = k (popcount of the mismatch mask, as VSC_HIT_NM)
+ *   mit_sum    sum of rint(MIT * 2^24) (MIT = vsc_score_hits' score of the hit, rint = round half to even): a fixed-point
+ *              sum, independent of the order of the hits and exact when passes or shards are added
+ *   mit_ub     counted hits whose MIT score raised the reference-UB flag (vsc_score_hits' mit_flags)
+ *   on_target  1 if exclude[i] was a hit (and was left out), else 0
+ * exclude: NULL (nothing excluded) or n_guides loci in vsc_hit coordinates - 0-based leftmost window position on the
+ * forward genome, strand 1 = '-' (BED6: chr, start, strand); contig == UINT32_MAX: none.  A contig >= the genome's
+ * contig count (and not UINT32_MAX) or a strand > 1 is VSC_ERR_INVALID.  A genome loaded as one shard counts its own
+ * windows only.  The search kernel's records are summarised where they lie: no sort, no result buffer, no record
+ * leaves the device.  vsc_ctx_timing afterwards fills the fields vsc_search fills, with sort_ms = 0 and finalize_ms =
+ * the summary kernel.  out: host memory, n_guides entries.
+ * Replaces, for a screen: bidir_mapping (read_mapping/bidir_mapping.cpp:285-295) + the per-hit MIT scores of the
+ * mergers (variant_processing/mit_score.h:12-68) + the guide-level aggregation CRISPOR reports as mitSpecScore.
+ */
+typedef struct {
+    uint32_t contig, pos, strand, reserved; /* contig == UINT32_MAX: none */
+} vsc_locus;
+typedef struct {
+    uint64_t mit_sum; /* sum of rint(MIT * 2^24) */
+    uint64_t nm[9];
+    uint64_t mit_ub;
+    uint32_t on_target;
+    uint32_t reserved;
+} vsc_guide_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_guide_summary) == 96, "vsc_guide_summary layout");
+#else
+_Static_assert(sizeof(vsc_guide_summary) == 96, "vsc_guide_summary layout");
+#endif
+int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                       const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out);
+/* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
+ * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
+double vsc_mit_specificity(uint64_t mit_sum);
 uint64_t vsc_hits_count(const vsc_hits *hits);
 /* Device pointer to vsc_hits_count() records of type vsc_hit (valid until vsc_hits_free). */
 const void *vsc_hits_data_dev(const vsc_hits *hits);
@@ -372,6 +410,11 @@ int vsc_multi_genome_build_index(vsc_multi *m, vsc_multi_genome *g, const vsc_se
  * the first device as soon as THAT shard is done (they do not wait for the slowest one). */
 int vsc_multi_search(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                      const vsc_search_params *params, vsc_hits **out);
+/* vsc_search_summary over the device set: every shard summarises its own windows on its own context (from its own host
+ * thread, as vsc_multi_search), and the rows are added on the host (on_target: OR over the shards).  No record moves
+ * between devices. */
+int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                             const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out);
 /* (vsc_multi_search_stream, which scores on the owning shard, is declared behind the classifier below.) */
 
 /* ---- variant windows (row R8) ------------------------------------------------------------------- */

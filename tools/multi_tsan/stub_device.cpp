@@ -183,6 +183,19 @@ int vsc_search(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32
     return VSC_OK;
 }
 
+// (vsc_multi_search_summary: the stub's shard result, counted as NM 0 hits)
+int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                       const vsc_locus *, vsc_guide_summary *out)
+{
+    vsc_hits *h = nullptr;
+    const int rc = vsc_search(ctx, g, guides, n_guides, p, &h);
+    if (rc != VSC_OK) return rc;
+    for (uint32_t i = 0; i < n_guides; ++i) out[i] = vsc_guide_summary{};
+    for (const vsc_hit &r : h->host) out[r.guide].nm[0]++;
+    vsc_hits_free(h);
+    return VSC_OK;
+}
+
 int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p, uint32_t,
                            vsc_rows_batch_fn on_batch, void *user)
 {

@@ -19,6 +19,12 @@ ERRORS = {-22: "VSC_ERR_INVALID", -12: "VSC_ERR_NOMEM", -5: "VSC_ERR_DEVICE", -3
 HIT_DTYPE = np.dtype([("guide", "<u4"), ("contig", "<u4"), ("pos", "<u4"), ("info", "<u4")])
 CONTIG_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u4"), ("reserved", "<u4")])
 N_FEATURES = 442
+# vsc_guide_summary (vsc_search_summary): 96 bytes per guide
+SUMMARY_DTYPE = np.dtype([("mit_sum", "<u8"), ("nm", "<u8", (9,)), ("mit_ub", "<u8"), ("on_target", "<u4"),
+                          ("reserved", "<u4")])
+assert SUMMARY_DTYPE.itemsize == 96
+# vsc_locus: an excluded locus (contig == 0xFFFFFFFF: none)
+LOCUS_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
 
 
 class SearchParams(C.Structure):
@@ -118,6 +124,8 @@ SYMBOLS = [
     ("vsc_search", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(_vp)]),
     ("vsc_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, BATCH_FN, _vp]),
     ("vsc_search_stream_rows", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, ROWS_BATCH_FN, _vp]),
+    ("vsc_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
+    ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),
     ("vsc_hits_data", C.c_int, [_vp, C.POINTER(_vp)]),
@@ -144,6 +152,7 @@ SYMBOLS = [
     ("vsc_multi_genome_free", C.c_int, [_vp]),
     ("vsc_multi_genome_build_index", C.c_int, [_vp, _vp, C.POINTER(SearchParams)]),
     ("vsc_multi_search", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(_vp)]),
+    ("vsc_multi_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
     ("vsc_multi_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, C.POINTER(MultiScore), MULTI_BATCH_FN, _vp]),
     ("vsc_windows_build", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                     C.POINTER(_vp), C.c_char_p, C.c_size_t]),

@@ -27,6 +27,26 @@ def pack_guides(guides):
     return out
 
 
+def _loci(exclude, n):
+    """(contig, pos, strand) per guide -> vsc_locus array (None stays None)."""
+    if exclude is None:
+        return None
+    if isinstance(exclude, np.ndarray) and exclude.dtype == _lib.LOCUS_DTYPE:
+        ex = np.ascontiguousarray(exclude)
+    else:
+        a = np.asarray(exclude, dtype=np.int64).reshape(-1, 3)
+        ex = np.zeros(len(a), dtype=_lib.LOCUS_DTYPE)
+        ex["contig"], ex["pos"], ex["strand"] = (a[:, 0] & 0xFFFFFFFF), a[:, 1], a[:, 2]
+    if len(ex) != n:
+        raise ValueError("exclude holds %d loci for %d guides" % (len(ex), n))
+    return ex
+
+
+def mit_specificity(mit_sum):
+    """CRISPOR's guide specificity (mitSpecScore before rounding) from a summary's mit_sum (vsc_mit_specificity)."""
+    return lib().vsc_mit_specificity(int(mit_sum))
+
+
 class PackedGenome:
     """The host-side packed planes of a genome (0.375 byte per base) plus its contig table.
 
@@ -252,6 +272,18 @@ class Genome:
         h = C.c_void_p()
         check(lib().vsc_search(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(h)), self.ctx._h)
         return Hits(self, h, codes)
+
+    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None):
+        """vsc_search_summary: per guide, the NM counts, the fixed-point MIT sum (units of 2^-24), the reference-UB count
+        and whether the excluded locus was a hit - over the hits search() would return, without the records.
+        exclude: None or one (contig, pos, strand) per guide (contig 0xFFFFFFFF: none).  Returns SUMMARY_DTYPE rows."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        check(lib().vsc_search_summary(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), ptr(out)), self.ctx._h)
+        return out
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)
@@ -533,6 +565,17 @@ class MultiGenome:
         res = MergedHits(_BorrowedContext(C.c_void_p(lib().vsc_multi_result_ctx(self.multi._h))), h)
         self.multi._results.add(res)
         return res
+
+    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None):
+        """vsc_multi_search_summary: Genome.summarize over the shards, rows added on the host."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = Genome._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        self.multi._check(lib().vsc_multi_search_summary(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
+                                                         ptr(out)))
+        return out
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

@@ -1,0 +1,198 @@
+// guide_summary - per-guide off-target summary of a guide library (vsc_search_summary): for every guide the number of
+// off-targets at each mismatch count and CRISPOR's MIT specificity score, without writing a single hit record.
+// Flags, validation, exit codes and genome loading follow bidir_mapping (read_mapping/bidir_mapping.cpp:190-280).
+// Guides come from exactly one of
+//   -R reads.fa       23-mers (non-ACGT letters become A); nothing is excluded
+//   -B ontargets.bed  BED6 on-targets, the 23-mer extracted as fasta_writer does (extract_fasta_ontargets.h:92-139); the
+//                     on-target locus itself (chr, start, strand) is left out of the counts and reported as onTargetFound
+// Output (-O, default stdout): one line per guide in input order under the header
+//   #guideId guideSeq mitSpecScore offtargetCount onTargetFound mm0 .. mm<M> mitHitSum
+// mitSpecScore = floor(100 / (100 + mitHitSum) * 100 + 0.5) (CRISPOR's guide score and Python 2 round()),
+// mitHitSum = the sum of the counted hits' MIT scores (fixed point, 2^-24 units, printed with %.6f).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+#include <fstream>
+#include <sstream>
+
+#include "merge_host.hpp"
+
+using namespace vsc_host;
+
+int main(int argc, char **argv)
+{
+    std::vector<Option> opts = {
+        {'G', "genome", "Path to genome fasta file", true},
+        {'I', "index", "Path to the indexed genome", true},
+        {'R', "reads", "Path to the guides as 23-mers (.fa/.fasta; everything else than ACGT is converted to A)", false},
+        {'B', "bed", "Path to BED6 on-targets (.bed): the 23-mer is extracted from the genome, the locus is excluded", false},
+        {'M', "mismatches", "Number of allowed mismatches", true},
+        {'O', "output", "Path to output TSV file (default: standard output)", false},
+        {'P', "pam", "Additional non-canonical PAM that should be allowed for off-target search besides (N)GG and (N)GA (default).", false},
+        {'D', "device", "HIP device index (default 0), or a comma-separated list (0,1,2,...): the genome is sharded over these "
+                        "devices, each summarises its own windows, the counts are added on the host", false},
+    };
+    const int pr = parse_args(argc, argv, opts, "Guide summary",
+                              "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
+                              "mitSpecScore) over the same hits as the read mapper, without writing them.");
+    if (pr) return pr == 1;
+    const std::string genome_path = opts[0].value, index_prefix = opts[1].value, reads_path = opts[2].value, bed_path = opts[3].value;
+    const std::string out_path = opts[5].value, pam = opts[6].value;
+    if (opts[2].set == opts[3].set) {
+        std::fprintf(stderr, "%s: give the guides with exactly one of -R (reads) and -B (on-targets)\n", argv[0]);
+        return 1;
+    }
+    if (!has_extension(genome_path, {"fa", "fasta"}) || (opts[2].set && !has_extension(reads_path, {"fa", "fasta"})) ||
+        (opts[3].set && !has_extension(bed_path, {"bed"})) || (opts[5].set && !has_extension(out_path, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: genome and reads must be .fa/.fasta files, on-targets a .bed file, the output a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
+    char *end = nullptr;
+    const long mm = std::strtol(opts[4].value.c_str(), &end, 10);
+    if (end == opts[4].value.c_str() || *end) {
+        std::fprintf(stderr, "%s: the given value '%s' cannot be casted to integer\n", argv[0], opts[4].value.c_str());
+        return 1;
+    }
+    if (mm < 0 || mm > 8) {  // bidir_mapping.cpp:234-238
+        std::fprintf(stderr, "Error: Maximum number of mismatches must lie between 0 and 8.\n");
+        return 1;
+    }
+    std::vector<int> devices;  // -D 0 | -D 0,1,2,3 (an id may repeat: several shards on one device)
+    {
+        const std::string d = opts[7].set ? opts[7].value : "0";
+        size_t b = 0;
+        for (;;) {
+            const size_t e = d.find(',', b);
+            const std::string item = d.substr(b, e == std::string::npos ? std::string::npos : e - b);
+            char *iend = nullptr;
+            const long v = std::strtol(item.c_str(), &iend, 10);
+            if (item.empty() || *iend || v < 0) {
+                std::fprintf(stderr, "%s: bad device list '%s'\n", argv[0], d.c_str());
+                return 1;
+            }
+            devices.push_back((int)v);
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+    }
+
+    vsc_ctx *ctx = nullptr;
+    vsc_genome *genome = nullptr;
+    vsc_multi *multi = nullptr;
+    vsc_multi_genome *mgenome = nullptr;
+    int rc = 1;
+    try {
+        const PackedIndex ix = read_index(index_prefix);
+        uint64_t size = 0;
+        int64_t mtime = 0;
+        if (ix.src_size && (!file_stamp(genome_path, &size, &mtime) || size != ix.src_size || mtime != ix.src_mtime))
+            throw std::runtime_error("index " + index_path(index_prefix) + " was not packed from " + genome_path);
+        // the guides (+ their excluded loci)
+        std::vector<std::string> ids, seqs;
+        std::vector<vsc_locus> loci;
+        if (opts[2].set) {
+            for (auto &r : read_fasta(reads_path)) {
+                ids.push_back(r.id);
+                seqs.push_back(r.seq);
+            }
+        } else {
+            const vsc_merge::Genome text(genome_path);
+            std::ifstream bed(bed_path);
+            if (!bed) throw std::runtime_error("Could not open BED file.");
+            std::string line;
+            while (std::getline(bed, line)) {  // as fasta_writer reads it
+                if (line.empty() || line[0] == '#') continue;
+                std::istringstream is(line);
+                std::string chr, name, score, strand;
+                unsigned long start = 0, stop = 0;
+                if (!(is >> chr >> start >> stop >> name >> score >> strand)) continue;
+                const char s = strand.empty() ? '+' : strand[0];
+                auto it = text.by_name.find(chr);
+                if (it == text.by_name.end()) throw std::runtime_error("on-target '" + name + "': no sequence '" + chr + "' in the genome");
+                ids.push_back(name);
+                seqs.push_back(text.region_at(it->second, (uint32_t)start, (uint32_t)stop, s));
+                loci.push_back(vsc_locus{(uint32_t)it->second, (uint32_t)start, s == '-' ? 1u : 0u, 0u});
+            }
+        }
+        std::vector<uint64_t> codes(seqs.size());
+        for (size_t i = 0; i < seqs.size(); ++i) {
+            if (seqs[i].size() != VSC_READ_LEN)
+                throw std::runtime_error("guide '" + ids[i] + "' is not 23 nt long (VARSCOT searches 20 nt + PAM)");
+            codes[i] = vsc_pack_guide(seqs[i].c_str());
+        }
+        std::fprintf(stderr, "Guides loaded (total: %zu).\n", seqs.size());
+        int st;
+        if (devices.size() == 1) {
+            st = vsc_ctx_create(devices[0], &ctx);
+            if (st != VSC_OK) throw std::runtime_error(st == VSC_ERR_NODEVICE ? "no HIP device available (there is no CPU fallback)" : "could not create the device context");
+            st = vsc_genome_load(ctx, ix.hi.data(), ix.lo.data(), ix.nm.data(), 0, ix.hi.size(), ix.hi.size(), ix.contigs.data(),
+                                 (uint32_t)ix.contigs.size(), &genome);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            if (pam.size() != 2 && std::ifstream(seed_index_path(index_prefix)).good() &&
+                vsc_genome_index_load(ctx, genome, seed_index_path(index_prefix).c_str()) != VSC_OK)
+                std::fprintf(stderr, "%s: %s - building the seed index instead\n", argv[0], vsc_last_error(ctx));
+        } else {
+            st = vsc_multi_create(devices.data(), (int)devices.size(), &multi);
+            if (st != VSC_OK) throw std::runtime_error(st == VSC_ERR_NODEVICE ? "no HIP device available (there is no CPU fallback)" : "could not create the device contexts");
+            st = vsc_multi_genome_load(multi, ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.hi.size(), ix.contigs.data(),
+                                       (uint32_t)ix.contigs.size(), &mgenome);
+            if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
+        }
+        std::fprintf(stderr, "Index loaded.\n");
+
+        vsc_search_params p{};
+        p.max_mismatches = (uint32_t)mm;
+        if (pam.size() == 2) {  // a PAM of any other length can never equal a 2-base window slice (:71-76)
+            p.has_extra_pam = 1;
+            p.extra_pam[0] = pam[0];
+            p.extra_pam[1] = pam[1];
+        }
+        std::vector<vsc_guide_summary> sum(codes.size());
+        const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
+        if (multi) {
+            st = vsc_multi_search_summary(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
+        } else {
+            st = vsc_search_summary(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+
+        std::string text = "#guideId\tguideSeq\tmitSpecScore\tofftargetCount\tonTargetFound";
+        for (long k = 0; k <= mm; ++k) text += "\tmm" + std::to_string(k);
+        text += "\tmitHitSum\n";
+        char buf[64];
+        for (size_t i = 0; i < sum.size(); ++i) {
+            const vsc_guide_summary &s = sum[i];
+            uint64_t total = 0;
+            for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) total += s.nm[k];
+            text += ids[i] + '\t' + dna4(seqs[i]) + '\t';
+            std::snprintf(buf, sizeof buf, "%.0f", std::floor(vsc_mit_specificity(s.mit_sum) + 0.5));
+            text += std::string(buf) + '\t' + std::to_string(total) + '\t' + std::to_string(s.on_target);
+            for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(s.nm[k]);
+            std::snprintf(buf, sizeof buf, "%.6f", (double)s.mit_sum * 0x1p-24);
+            text += '\t' + std::string(buf) + '\n';
+        }
+        if (opts[5].set) {
+            std::ofstream out(out_path);
+            if (!out.is_open()) throw std::runtime_error("Could not open output path.");
+            out << text;
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the output.");
+        } else {
+            std::fwrite(text.data(), 1, text.size(), stdout);
+        }
+        rc = 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "ERROR: %s\n", e.what());
+        rc = 1;
+    }
+    if (multi) {
+        vsc_multi_genome_free(mgenome);
+        vsc_multi_destroy(multi);
+    } else {
+        vsc_genome_free(genome);
+        vsc_ctx_destroy(ctx);
+    }
+    return rc;
+}

@@ -210,7 +210,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     for (DeviceBuf *b : {&ctx->counters, &ctx->guides, &ctx->score_guides, &ctx->keys_a, &ctx->keys_b, &ctx->vals_a, &ctx->vals_b,
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
-                         &ctx->seed_poff, &ctx->seed_lrest})
+                         &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl})
         b->release();
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
@@ -1239,13 +1239,21 @@ struct PassResult {
     uint64_t n = 0;  // records this pass appended to the result
 };
 
+// Summary mode of a search pass (vsc_search_summary): the records are added into per-read rows instead of being sorted
+struct SumTarget {
+    unsigned long long *out;  // kSumWords per read of the pass (the pass's slice of the call's zeroed rows)
+    const uint64_t *excl;     // per read of the pass: strand << 32 | global position, ~0 = none; null: nothing excluded
+};
+
 // One search pass: reads guides[0 .. n_guides) (n_guides <= kMaxPassReads), reported as read indices
 // guide_base + i, appended to `hits` behind the `used` records it already holds.  Timings are ADDED to t.
 // want_rows (SEED only): the search keeps the sites' bases beside the records and the sort's last stage writes every hit's
 // packed feature row into ctx->score_feat (row i of the pass at byte 64 i).
+// sum (summary mode): once the search kernel's records are final (no overflow), summary_kernel adds them into sum->out where
+// they lie - no sort, no result buffer (`hits` is not touched); finalize_ms times that kernel, sort_ms stays 0.
 int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, uint32_t guide_base,
                 const vsc_search_params *params, int algo, vsc_hits *hits, uint64_t used, uint64_t projected, vsc_timing &t,
-                PassResult *res, bool want_rows = false)
+                PassResult *res, bool want_rows = false, const SumTarget *sum = nullptr)
 {
 #define VSC_HIP_H(call)                                                                                  \
     do {                                                                                                 \
@@ -1502,7 +1510,7 @@ int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, 
         n = cnt[kCntHits];
         const_cast<vsc_genome *>(genome)->seen_rate[params->max_mismatches] = (double)n / n_guides;
         if (n >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in one scan pass (split the read set)");
-        if (n > 0) {
+        if (n > 0 && !sum) {
             // level 0: (key, value) pairs -> packed records, partitioned by region
             VSC_HIP_H(ctx->keys_b.ensure(cap * sizeof(uint64_t)));
             const unsigned bits0 = ceil_log2((uint64_t)n_parts);
@@ -1559,6 +1567,47 @@ int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, 
         // (the sort's second buffer, ctx->keys_b, is sized by bin_sort for the layout its first level uses)
     }
     t.hits += n;
+    if (sum) {
+        // ---- summary: the regions (SEED) or the pairs (SCAN) as they are, into the per-read rows ----------------------
+        std::vector<SumSeg> ss;
+        std::vector<uint32_t> tile0(1, 0);
+        if (algo == VSC_ALGO_SCAN) {
+            if (n) ss.push_back(SumSeg{0, (uint32_t)n, 0});
+        } else {
+            for (const SortSeg &sg : segs) ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - guide_base});
+        }
+        for (const SumSeg &sg : ss) tile0.push_back(tile0.back() + (sg.n + kSumTile - 1) / kSumTile);
+        SummaryArgs sa_sum{};
+        if (!ss.empty()) {
+            const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
+            VSC_HIP_H(ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
+            VSC_HIP_H(hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP_H(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t),
+                                     hipMemcpyHostToDevice, ctx->stream));
+            sa_sum.recs = (const uint64_t *)ctx->keys_a.p;
+            sa_sum.vals = algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
+            sa_sum.segs = (const SumSeg *)ctx->sort_segs.p;
+            sa_sum.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
+            sa_sum.n_segs = (uint32_t)ss.size();
+            sa_sum.n_tiles = tile0.back();
+            sa_sum.pos_pad = pos_pad;
+            sa_sum.pos_base = pos_base;
+            sa_sum.excl = sum->excl;
+            sa_sum.out = sum->out;
+        }
+        VSC_HIP_H(hipEventRecord(ctx->ev[3], ctx->stream));
+        VSC_HIP_H(launch_summary(sa_sum, ctx->stream));
+        VSC_HIP_H(hipEventRecord(ctx->ev[4], ctx->stream));
+        VSC_HIP_H(hipStreamSynchronize(ctx->stream));
+        ht.lap("summary + sync");
+        VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+        t.finalize_ms += ms;
+        VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
+        t.total_ms += ms;
+        t.read_passes++;
+        res->n = n;
+        return VSC_OK;
+    }
     if (n > 0) {
         ht.lap("sort buffers");
         VSC_HIP_H(result_room(ctx, hits, used, n, projected));
@@ -1685,6 +1734,67 @@ int vsc_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     *out = hits;
     return VSC_OK;
     });
+}
+
+int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                       const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary: null argument");
+    vsc_timing t{};
+    int algo = 0;
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_summary", &algo, &t);
+    if (rc != VSC_OK) return rc;
+    // the excluded loci as the records carry them: strand << 32 | global position
+    std::vector<uint64_t> excl;
+    if (exclude && n_guides) {
+        std::vector<uint32_t> off(genome->n_contigs), end(genome->n_contigs);
+        if (genome->n_contigs) {
+            VSC_HIP(ctx, hipMemcpy(off.data(), genome->d_contig_off, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            VSC_HIP(ctx, hipMemcpy(end.data(), genome->d_contig_end, end.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        }
+        excl.assign(n_guides, ~0ull);
+        for (uint32_t i = 0; i < n_guides; ++i) {
+            const vsc_locus &l = exclude[i];
+            if (l.contig == UINT32_MAX) continue;
+            if (l.contig >= genome->n_contigs || l.strand > 1)
+                return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary: excluded locus outside the genome's contigs or strands");
+            if (l.pos >= end[l.contig] - off[l.contig]) continue;  // no window starts there: nothing to exclude
+            excl[i] = (uint64_t)l.strand << 32 | (off[l.contig] + l.pos);
+        }
+    }
+    if (n_guides) {
+        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+        VSC_HIP(ctx, ctx->sum_rows.ensure(row_bytes));
+        VSC_HIP(ctx, hipMemsetAsync(ctx->sum_rows.p, 0, row_bytes, ctx->stream));
+        if (!excl.empty()) {
+            VSC_HIP(ctx, ctx->sum_excl.ensure(excl.size() * sizeof(uint64_t)));
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->sum_excl.p, excl.data(), excl.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
+    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
+        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
+        SumTarget st{(unsigned long long *)ctx->sum_rows.p + (size_t)first * kSumWords,
+                     excl.empty() ? nullptr : (const uint64_t *)ctx->sum_excl.p + first};
+        PassResult r;
+        const int prc = search_pass(ctx, genome, guides + first, count, first, params, algo, nullptr, 0, 0, t, &r, false, &st);
+        if (prc != VSC_OK) return prc;
+    }
+    if (n_guides) {
+        VSC_HIP(ctx, hipMemcpyAsync(out, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+double vsc_mit_specificity(uint64_t mit_sum)
+{
+    // CRISPOR's mitSpecScore before its round(): 100 / (100 + Σ mitOfftargetScore) * 100, the sum in units of 2^-24
+    return (100.0 / (100.0 + (double)mit_sum * 0x1p-24)) * 100.0;
 }
 
 int vsc_search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,

@@ -314,8 +314,38 @@ struct RfArgs {
     ScoreArgs score;            // fused path: hits, planes, reads (+ optional MIT output)
 };
 
+// ---- per-guide summary (vsc_search_summary; summary_kernel in vsc_kernels.hip) ----------------------------------------------
+// The kernel reads the search kernel's records where they lie - the packed records of every region (SEED) or the (key, value)
+// pairs (SCAN) - and adds them into one row of kSumWords 64-bit words per read of the pass, the layout of vsc_guide_summary:
+// mit_sum, nm[0..8], mit_ub, on_target (low half of the last word).
+constexpr int kSumWords = 12;
+constexpr int kSumCounts = 11;    // LDS counters per read of the region: nm[0..8], mit_ub, on_target
+constexpr int kSumThreads = 256;
+constexpr int kSumItems = 8;      // consecutive records a lane takes (one running accumulator per lane)
+constexpr int kSumTile = kSumThreads * kSumItems;
+constexpr int kSumTilesPerBlock = 8;
+constexpr int kSumCountBits = 7;  // nm counters of a lane packed into one 64-bit word (9 x 7 bits; a lane adds <= kSumItems)
+
+struct SumSeg {
+    uint64_t in_off;      // first record of the region (SEED) / of the pairs (SCAN)
+    uint32_t n;           // records in the span (SEED: sentinels included)
+    uint32_t first_read;  // pass-local index of the region's first read (SCAN: 0, the key holds the pass-local read)
+};
+
+struct SummaryArgs {
+    const uint64_t *recs;       // SEED: packed records; SCAN: keys (read << 33 | strand << 32 | global position)
+    const uint32_t *vals;       // SCAN: NM << 23 | mask; SEED: null
+    const SumSeg *segs;
+    const uint32_t *seg_tile0;  // [n_segs + 1]: first tile (kSumTile records) of every segment
+    uint32_t n_segs, n_tiles;
+    uint32_t pos_pad, pos_base; // SEED: the pass's position encoding (vsc_sort.hip pack_pair)
+    const uint64_t *excl;       // per pass-local read: strand << 32 | global position of the excluded locus, ~0: none (null: none)
+    unsigned long long *out;    // kSumWords per pass-local read, zeroed once per call
+};
+
 // Launch wrappers implemented in vsc_kernels.hip.  They only enqueue work on `stream`.
 hipError_t launch_scan(const ScanArgs &args, int n_groups, bool extract, hipStream_t stream);
+hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream);
 // vsc_sort.hip
 hipError_t launch_bin_hist(const SortArgs &args, hipStream_t stream);
 hipError_t launch_bin_scan(const SortArgs &args, hipStream_t stream);

@@ -6,6 +6,8 @@
 //                 (the hits are ordered and turned into vsc_hit records by vsc_sort.hip)
 // score_kernel    rows R5/R6: calcMitScore (variant_processing/mit_score.h:12-68) and
 //                 featureMatrixRecord (variant_processing/feature_matrix.h:25-126) per hit.
+// summary_kernel  per-guide NM counts and fixed-point MIT sums over the search kernel's records, unsorted
+//                 (vsc_search_summary): the same mit_score as score_kernel.
 //
 // Integer / bitwise work on the VALU (v_alignbit, v_xor, v_or, v_bcnt, v_min3, ballot / mbcnt);
 // no MFMA: the comparison is not a dense contraction.
@@ -833,6 +835,158 @@ hipError_t launch_score(const ScoreArgs &args, hipStream_t stream)
     if (args.n == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((args.n + 255) / 256);
     hipLaunchKernelGGL(score_kernel, dim3(blocks), dim3(256), 0, stream, args);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// per-guide summary: NM counts, Σ rint(MIT · 2^24), reference-UB flags, on-target found
+// ------------------------------------------------------------------------------------------------
+// The records are read where the search kernel left them; they are unique, so no order is needed.  A region's
+// records come in runs of one read, so one LDS atomic per record would serialise on one address.
+// Instead every lane takes kSumItems CONSECUTIVE records (staged through LDS so that the global loads stay
+// coalesced) and keeps one running accumulator for the read it is on, flushed when the read changes and at the end
+// of the tile: into the region's LDS table (SEED: a workgroup's tiles lie in one region at a time, 64 reads), or
+// straight into the result (SCAN: the pairs of all reads of the pass arrive mixed).  The LDS table goes out with one
+// agent-scope atomic per nonzero (read, field).
+template <bool kSeed>
+__global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs a)
+{
+    constexpr int kStride = kSumItems + 1;  // a lane's records in LDS, padded against bank conflicts
+    __shared__ uint64_t s_rec[kWavesPerGroup][kWave * kStride];
+    __shared__ uint32_t s_val[kSeed ? 1 : kWavesPerGroup][kSeed ? 1 : kWave * kStride];
+    __shared__ unsigned long long s_mit[kSeed ? kRegionReads : 1];
+    __shared__ uint32_t s_cnt[kSeed ? kRegionReads * kSumCounts : 1];
+    const uint32_t t = threadIdx.x, lane = t % kWave, wave = t / kWave;
+    if (kSeed) {
+        for (uint32_t i = t; i < (uint32_t)kRegionReads * kSumCounts; i += kSumThreads) s_cnt[i] = 0;
+        for (uint32_t i = t; i < (uint32_t)kRegionReads; i += kSumThreads) s_mit[i] = 0;
+        block_sync();
+    }
+    const uint32_t tile_begin = blockIdx.x * kSumTilesPerBlock, tile_end = min(tile_begin + (uint32_t)kSumTilesPerBlock, a.n_tiles);
+    uint32_t seg = 0;
+    {
+        uint32_t lo = 0, hi = a.n_segs;  // last s with seg_tile0[s] <= tile_begin
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.seg_tile0[mid] <= tile_begin) lo = mid; else hi = mid;
+        }
+        seg = lo;
+    }
+    // the region's LDS table -> the result rows of its reads
+    auto flush_table = [&](const SumSeg &sg) {
+        block_sync();
+        for (uint32_t i = t; i < (uint32_t)kRegionReads * kSumWords; i += kSumThreads) {
+            const uint32_t r = i / kSumWords, f = i % kSumWords;
+            unsigned long long v;
+            if (f == 0) {
+                v = s_mit[r];
+                s_mit[r] = 0;
+            } else {
+                v = s_cnt[r * kSumCounts + f - 1];
+                s_cnt[r * kSumCounts + f - 1] = 0;
+            }
+            if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
+        }
+        block_sync();
+    };
+    for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
+        if (tile >= a.seg_tile0[seg + 1]) {
+            if (kSeed) flush_table(a.segs[seg]);
+            while (tile >= a.seg_tile0[seg + 1]) ++seg;
+        }
+        const SumSeg sg = a.segs[seg];
+        const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile + wave * (uint32_t)(kWave * kSumItems);
+        const uint32_t n = first < sg.n ? min(sg.n - first, (uint32_t)(kWave * kSumItems)) : 0u;  // this wave's records
+        wave_sync();
+#pragma unroll
+        for (int k = 0; k < kSumItems; ++k) {
+            const uint32_t i = (uint32_t)k * kWave + lane;
+            const uint64_t at = sg.in_off + first + (i < n ? i : 0u);
+            uint64_t r = kRecSentinel;
+            uint32_t v = 0;
+            if (i < n) {
+                r = a.recs[at];
+                if (!kSeed) v = a.vals[at];
+            }
+            s_rec[wave][(i / kSumItems) * kStride + i % kSumItems] = r;
+            if (!kSeed) s_val[wave][(i / kSumItems) * kStride + i % kSumItems] = v;
+        }
+        wave_sync();
+        uint32_t cur = ~0u;  // pass-local read the accumulator belongs to
+        uint64_t cur_ex = ~0ull, cnt = 0;
+        unsigned long long mit = 0;
+        uint32_t ub = 0, on = 0;
+        auto flush = [&]() {
+            if (cur == ~0u) return;
+            if (kSeed) {
+                const uint32_t r = cur - sg.first_read;
+                if (mit) atomicAdd(&s_mit[r], mit);
+#pragma unroll
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+                    const uint32_t c = (uint32_t)(cnt >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    if (c) atomicAdd(&s_cnt[r * kSumCounts + k], c);
+                }
+                if (ub) atomicAdd(&s_cnt[r * kSumCounts + 9], ub);
+                if (on) atomicAdd(&s_cnt[r * kSumCounts + 10], on);
+            } else {
+                unsigned long long *o = a.out + (size_t)cur * kSumWords;
+                if (mit) atomicAdd(&o[0], mit);
+#pragma unroll
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+                    const uint32_t c = (uint32_t)(cnt >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    if (c) atomicAdd(&o[1 + k], (unsigned long long)c);
+                }
+                if (ub) atomicAdd(&o[10], (unsigned long long)ub);
+                if (on) atomicAdd(&o[11], (unsigned long long)on);
+            }
+            cnt = 0;
+            mit = 0;
+            ub = on = 0;
+        };
+        for (int k = 0; k < kSumItems; ++k) {
+            if (lane * kSumItems + (uint32_t)k >= n) break;
+            const uint64_t r = s_rec[wave][lane * kStride + k];
+            uint32_t read, strand, pos, mask;
+            if (kSeed) {
+                if (r >> 63) continue;  // sentinel: a reserved slot nobody wrote
+                read = sg.first_read + (uint32_t)((r >> kRecReadShift) & (kRegionReads - 1));
+                strand = (uint32_t)(r >> kRecStrandShift) & 1u;
+                pos = ((uint32_t)(r >> kRecPosShift) >> a.pos_pad) + a.pos_base;
+                mask = (uint32_t)r & kMask23;
+            } else {
+                read = (uint32_t)(r >> 33);
+                strand = (uint32_t)(r >> 32) & 1u;
+                pos = (uint32_t)r;
+                mask = s_val[wave][lane * kStride + k] & kMask23;
+            }
+            if (read != cur) {
+                flush();
+                cur = read;
+                cur_ex = a.excl ? a.excl[read] : ~0ull;
+            }
+            if ((((uint64_t)strand << 32) | pos) == cur_ex) {  // the guide's own locus: reported, not counted
+                on = 1;
+                continue;
+            }
+            int f;
+            const double s = mit_score(mask, &f);
+            mit += (uint32_t)__builtin_rint(s * 0x1p24);  // <= 100 * 2^24 < 2^32; exact: a power-of-two scale
+            ub += (uint32_t)f;
+            cnt += 1ull << (kSumCountBits * __popc(mask));
+        }
+        flush();
+    }
+    if (kSeed && tile_begin < tile_end) flush_table(a.segs[seg]);
+}
+
+hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
+    if (args.vals)
+        hipLaunchKernelGGL(summary_kernel<false>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL(summary_kernel<true>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
     return hipGetLastError();
 }
 

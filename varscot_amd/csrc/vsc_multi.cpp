@@ -703,6 +703,58 @@ int vsc_multi_search(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *gu
     });
 }
 
+int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                             const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
+{
+    return mguarded(m, [&]() -> int {
+    if (!m) return VSC_ERR_INVALID;
+    m->err.clear();
+    if (!g || g->multi != m || !params || (n_guides && (!guides || !out)))
+        return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_summary: null argument");
+    if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
+        for (uint32_t i = 0; i < n_guides; ++i)
+            if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
+                return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_summary: excluded locus outside the genome's contigs or strands");
+    const auto t0 = clk::now();
+    const size_t n = m->ctx.size();
+    std::vector<int> rc(n, VSC_OK);
+    std::vector<std::vector<vsc_guide_summary>> part(n);
+    on_all(n, [&](size_t r) {
+        if (!g->shard[r]) return;
+        part[r].resize(n_guides);
+        rc[r] = vsc_search_summary(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, part[r].data());
+    });
+    for (size_t r = 0; r < n; ++r)
+        if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
+    const double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    // the rows add exactly (fixed-point MIT sums, counts); a locus lies in one shard only
+    std::fill(out, out + n_guides, vsc_guide_summary{});
+    vsc_multi_timing mt{};
+    for (size_t r = 0; r < n; ++r) {
+        if (!g->shard[r]) continue;
+        for (uint32_t i = 0; i < n_guides; ++i) {
+            const vsc_guide_summary &p = part[r][i];
+            vsc_guide_summary &o = out[i];
+            o.mit_sum += p.mit_sum;
+            for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.nm[k] += p.nm[k];
+            o.mit_ub += p.mit_ub;
+            o.on_target |= p.on_target;
+        }
+        vsc_timing t{};
+        (void)vsc_ctx_timing(m->ctx[r], &t);
+        mt.search_ms_max = std::max(mt.search_ms_max, t.total_ms);
+        mt.hits += t.hits;
+    }
+    mt.search_wall_ms = wall;
+    mt.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    mt.n_devices = (uint32_t)n;
+    mt.used_rccl = m->use_rccl ? 1u : 0u;
+    mt.batches = 1;
+    m->timing = mt;
+    return VSC_OK;
+    });
+}
+
 int vsc_multi_search_stream(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                             const vsc_search_params *params, uint32_t batch_reads, const vsc_multi_score *score,
                             vsc_multi_batch_fn on_batch, void *user)

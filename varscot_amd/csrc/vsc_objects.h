@@ -78,6 +78,7 @@ struct vsc_ctx {
     std::vector<vsc::SortSeg> host_segs;
     std::vector<uint32_t> host_tile0;  // bin sort: segment table + tile starts, per-bin tables, oversize list + counter
     vsc::DeviceBuf seed_off, seed_poff, seed_lrest;  // per-search read lists: bucket counts, padded list starts, entries
+    vsc::DeviceBuf sum_rows, sum_excl;  // vsc_search_summary: the per-read rows it adds into, the excluded loci
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
