@@ -906,7 +906,7 @@ def test_output_regions_of_128_reads(ctx, oracle, algo):
 
 
 def test_more_reads_than_one_pass_takes(ctx, oracle):
-    """16 384 reads fill the 128 output regions of a pass: vsc_search runs larger read sets pass by pass and
+    """16 384 reads fill the 256 output regions of a pass: vsc_search runs larger read sets pass by pass and
     the passes' results follow each other (read index = major sort key).  Reads on either side of the pass
     boundary get planted sites; the second pass has an odd read count."""
     rng = np.random.default_rng(4242)

@@ -1235,57 +1235,211 @@ hipError_t result_room(vsc_ctx *ctx, vsc_hits *hits, uint64_t used, uint64_t n, 
     return hipSuccess;
 }
 
-struct PassResult {
-    uint64_t n = 0;  // records this pass appended to the result
+// What a pass's search found, its records final: a sink's input.  The records lie in ctx->keys_a (SCAN: values in ctx->vals_a).
+struct PassFound {
+    HostTimer ht;  // laps from the start of the pass; the sink goes on with them
+    int algo = 0, n_parts = 0;             // n_parts: output regions of kRegionReads reads
+    uint32_t max_mm = 0, guide_base = 0;  // guide_base: read index of the pass's first read
+    uint64_t cap = 0, n = 0;               // records the search's buffers hold; hits
+    // SEED: one segment per region that holds records (sentinels included); SCAN: the one segment of (key, value) pairs,
+    // before the level-0 partition by region.  final_off counts from the pass's first hit.
+    std::vector<SortSeg> segs;
+    unsigned key_bits = 0, pos_pad = 0;  // bin_sort's key bits; the records' position encoding (with pos_base)
+    uint32_t pos_base = 0;
+    bool bases = false;  // SEED: every record's site lo plane lies beside it in ctx->vals_a (feature rows wanted)
 };
 
-// Summary mode of a search pass (vsc_search_summary): the records are added into per-read rows instead of being sorted
-struct SumTarget {
-    unsigned long long *out;  // kSumWords per read of the pass (the pass's slice of the call's zeroed rows)
-    const uint64_t *excl;     // per read of the pass: strand << 32 | global position, ~0 = none; null: nothing excluded
-};
+// words within k substitutions of a 7-base segment (k < 0: none)
+uint32_t neighbours(int k) { return k < 0 ? 0u : (k == 0 ? 1u : (k == 1 ? 22u : 211u)); }
 
-// One search pass: reads guides[0 .. n_guides) (n_guides <= kMaxPassReads), reported as read indices
-// guide_base + i, appended to `hits` behind the `used` records it already holds.  Timings are ADDED to t.
-// want_rows (SEED only): the search keeps the sites' bases beside the records and the sort's last stage writes every hit's
-// packed feature row into ctx->score_feat (row i of the pass at byte 64 i).
-// sum (summary mode): once the search kernel's records are final (no overflow), summary_kernel adds them into sum->out where
-// they lie - no sort, no result buffer (`hits` is not touched); finalize_ms times that kernel, sort_ms stays 0.
-int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, uint32_t guide_base,
-                const vsc_search_params *params, int algo, vsc_hits *hits, uint64_t used, uint64_t projected, vsc_timing &t,
-                PassResult *res, bool want_rows = false, const SumTarget *sum = nullptr)
+// The cut of the pigeonhole (SeedPlan, vsc_internal.h): segment 0 within k0 substitutions, segment 1 within k1, segment 2
+// within what the site's PAM class leaves of the limit - k0 - k1 - 2.  Hook seed_tight = 0: floor(m / 3) everywhere (the
+// round-3 cut); 1 + k0 + 3 k1: that cut, if it is a valid one.  Host arithmetic only.  *k2_max: segment 2's largest threshold.
+SeedPlan seed_cut(const vsc_genome *genome, const uint32_t *gp, uint32_t n_guides, uint32_t m, int n_cus, const vsc_debug_params &dbg,
+                  int *k2_max)
 {
-#define VSC_HIP_H(call)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) return fail(ctx, e_ == hipErrorOutOfMemory ? VSC_ERR_NOMEM : VSC_ERR_DEVICE, #call, e_); \
-    } while (0)
-    HostTimer ht;
+    SeedPlan plan{};
+    plan.max_mm = m;
+    ScanArgs pa{};
+    vsc_search_params ip{};
+    ip.has_extra_pam = genome->index_has_extra_pam;
+    ip.extra_pam[0] = genome->index_extra_pam[0];
+    ip.extra_pam[1] = genome->index_extra_pam[1];
+    fill_pam(pa, &ip);  // the classes of the index, in the order build_index gave them
+    plan.n_pam = pa.n_pam;
+    plan.pam_codes = pam_code_set(pa);
+    plan.tight = dbg.seed_tight != 0;
+    if (!plan.tight) {
+        plan.k0 = plan.k1 = m / kSegments;
+        *k2_max = (int)plan.k0;
+    } else {
+        // reads per (class, what the class leaves them for positions 0..20)
+        uint32_t left_reads[kSeedClasses][VSC_MAX_MISMATCHES + 1] = {};
+        int left_max = -1;
+        for (uint32_t i = 0; i < n_guides; ++i) {
+            const uint32_t x = gp[2 * (size_t)i], l = gp[2 * (size_t)i + 1];
+            const uint32_t mine = (((x >> 21) & 1u) << 3) | (((l >> 21) & 1u) << 2) | (((x >> 22) & 1u) << 1) | ((l >> 22) & 1u);
+            for (uint32_t c = 0; c < plan.n_pam; ++c) {
+                const uint32_t diff = mine ^ ((plan.pam_codes >> (4 * c)) & 15u);
+                const uint32_t spent = ((diff & 12u) ? 1u : 0u) + ((diff & 3u) ? 1u : 0u);
+                if (spent > m) continue;
+                left_reads[c][m - spent]++;
+                left_max = std::max(left_max, (int)(m - spent));
+            }
+        }
+        // Every (k0, k1) in 0..2 that keeps the third threshold within two substitutions is a valid cut; they differ in what
+        // they cost.  Fewer buckets per read = fewer comparisons (what a dense search is bound by: c3), but a table whose
+        // lists are short still has nearly all of its chunks loaded for a read or two each (what a sparse search is bound by:
+        // at 1 000 reads and m = 6 the cut (2, 2, 0) compares 2.6 x the pairs of (1, 1, 2) and loads 14 % fewer blocks).
+        // cost = max(block bytes at 4.2 TB/s, chunk visits x 215 SIMD-cycles over all SIMDs at 2 GHz)
+        double cost[9];  // [k0 + 3 k1]; < 0: not a valid cut
+        double chunks_all = 0, sites_all = 0;
+        uint64_t reads_any = 0;
+        for (uint32_t c = 0; c < plan.n_pam; ++c) {
+            chunks_all += (double)genome->ix_class_chunks[c] / kSegments;
+            sites_all += (double)genome->ix_class_sites[c];
+            uint64_t reads_c = 0;
+            for (int left = 0; left <= (int)m; ++left) reads_c += left_reads[c][left];
+            reads_any = std::max(reads_any, reads_c);
+        }
+        const double block_bytes = (double)kVertWords * 4 / kSlicedSites;  // per site
+        for (int cut = 0; cut < 9; ++cut) {
+            const int k0 = cut % 3, k1 = cut / 3;
+            cost[cut] = -1;
+            if (left_max - k0 - k1 - 2 > 2) continue;
+            double bytes = 0, visits = 0;
+            for (uint32_t c = 0; c < plan.n_pam; ++c) {
+                double e2 = 0;  // entries of class c's lists of segment 2
+                for (int left = 0; left <= (int)m; ++left) e2 += (double)left_reads[c][left] * neighbours(left - k0 - k1 - 2);
+                const double per_list = e2 / kBucketsPerSeg;
+                bytes += (1.0 - std::exp(-per_list)) * (double)genome->ix_class_sites[c] * block_bytes;
+                visits += per_list * (double)genome->ix_class_chunks[c] / kSegments;
+            }
+            for (int k : {k0, k1}) {  // segments 0 and 1: one list per bucket for all classes
+                const double per_list = (double)reads_any * neighbours(k) / kBucketsPerSeg;
+                bytes += (1.0 - std::exp(-per_list)) * sites_all * block_bytes;
+                visits += per_list * chunks_all;
+            }
+            cost[cut] = std::max(bytes / 4.2e12, visits * 215.0 / ((double)n_cus * 4 * 2.0e9));
+        }
+        int best = -1;
+        for (int cut = 0; cut < 9; ++cut)
+            if (cost[cut] >= 0 && (best < 0 || cost[cut] < cost[best])) best = cut;
+        const int forced = dbg.seed_tight >= 1 ? dbg.seed_tight - 1 : -1;  // hook: 1 + k0 + 3 k1
+        if (forced >= 0 && forced < 9 && cost[forced] >= 0) best = forced;
+        if (best < 0) best = 4 * (int)(m ? (m - 1) / kSegments : 0u);  // (no read can reach any class: nothing to search)
+        plan.k0 = (uint32_t)(best % 3);
+        plan.k1 = (uint32_t)(best / 3);
+        *k2_max = std::min<int>(2, (int)m - (int)plan.k0 - (int)plan.k1 - 2);
+    }
+    plan.n_nbr = neighbours(std::max<int>(std::max<int>((int)plan.k0, (int)plan.k1), *k2_max));
+    return plan;
+}
+
+// The seed search's plan of a pass: the cut, the per-bucket read lists (a counting sort of the reads' segment neighbourhoods
+// over the buckets, enqueued here) and the sliced kernel's launch, which fills sa but for its record buffers.
+hipError_t seed_plan(vsc_ctx *ctx, const vsc_genome *genome, const uint32_t *gp, uint32_t n_guides, const PassFound &f, SeedArgs &sa,
+                     int *n_groups, bool *shared)
+{
+    int k2_max = 0;
+    const SeedPlan plan = seed_cut(genome, gp, n_guides, f.max_mm, ctx->n_cus, ctx->dbg, &k2_max);
+    // entries: one per (read, neighbour within the threshold) of segments 0 and 1, one per class and neighbour of segment 2
+    const uint64_t n_pairs = (uint64_t)n_guides * (neighbours((int)plan.k0) + neighbours((int)plan.k1) + plan.n_pam * neighbours(k2_max));
+    const uint64_t list_cap = n_pairs + (uint64_t)kLists * (kGuideUnroll - 1) + 2 * kGuideUnroll;
+    VSC_TRY(ctx->seed_off.ensure((kLists + 1) * sizeof(uint32_t)));
+    VSC_TRY(ctx->seed_poff.ensure((kLists + 1) * sizeof(uint32_t)));
+    VSC_TRY(ctx->seed_lrest.ensure(list_cap * sizeof(uint2)));
+    VSC_TRY(hipMemsetAsync(ctx->seed_lrest.p, 0xFF, list_cap * sizeof(uint2), ctx->stream));  // padding: y = ~0, skipped
+    VSC_TRY(launch_seed_lists((const uint2 *)ctx->guides.p, n_guides, plan, (uint32_t *)ctx->seed_off.p, (uint32_t *)ctx->seed_poff.p,
+                              (uint2 *)ctx->seed_lrest.p, ctx->stream));
+    VSC_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
+    sa.chunk_tab = genome->d_ix_chunk_tab;
+    sa.n_chunks = genome->ix_chunks;
+    sa.vert = genome->d_ix_vert;
+    sa.list_rest = (const uint2 *)ctx->seed_lrest.p;
+    sa.sites = genome->d_ix_sites;
+    sa.edge_bits = genome->d_ix_edge;
+    sa.guides = (const uint2 *)ctx->guides.p;
+    sa.poff = (const uint32_t *)ctx->seed_poff.p;
+    sa.max_mm = f.max_mm;
+    sa.k_half = f.max_mm / 2;
+    sa.k_seg0 = plan.k0;
+    sa.k_seg1 = plan.k1;
+    sa.contig_end = genome->d_contig_end;
+    sa.n_contigs = genome->n_contigs;
+    sa.counters = (unsigned long long *)ctx->counters.p;
+    sa.n_parts = (uint32_t)f.n_parts;
+    uint32_t groups_per_cu = kSlicedWavesPerSimd;  // resident groups (of four waves) per CU: registers / LDS of the kernel
+    if (ctx->dbg.seed_groups_per_cu) groups_per_cu = ctx->dbg.seed_groups_per_cu;
+    // dense searches (c3: 129 reads per bucket) share a chunk between the four waves of a workgroup, sparse ones
+    // (c2: 13) keep a chunk per wave - see seed_sliced_kernel.  Measured at <= 8 mismatches (tools/
+    // experiments.sh shared-threshold): 51 reads per bucket 12.1 vs 11.4 ms, 77: 15.9 vs 16.0, 103: 19.9 vs 20.7
+    // (reads per list of segments 0 and 1 - and of segment 2 wherever it is searched as widely)
+    *shared = (uint64_t)n_guides * neighbours((int)std::max(plan.k0, plan.k1)) / kBucketsPerSeg >= 72;
+    if (ctx->dbg.seed_shared >= 0) *shared = ctx->dbg.seed_shared == 1;
+    const uint32_t n_grabs = (sa.n_chunks + kSlicedGrab - 1) / kSlicedGrab;
+    const uint32_t n_waves_max = (uint32_t)ctx->n_cus * groups_per_cu * kWavesPerGroup;
+    const uint32_t n_waves = std::max<uint32_t>(1, std::min<uint32_t>(n_waves_max, *shared ? n_grabs * kWavesPerGroup : n_grabs));
+    *n_groups = (int)((n_waves + kWavesPerGroup - 1) / kWavesPerGroup);
+    // block of records a wave reserves per atomic and region (a power of two, 64 .. 1024): large when many hits
+    // are expected, small otherwise (the unused tail of every wave's last block is written as sentinels
+    // and read by the sort)
+    // with chunk sharing the four waves of a workgroup also share their open output blocks: a quarter of the open
+    // lines and of the padding, so the blocks can be eight times as large (c3: per-wave blocks of 128 records 40.6 ms
+    // per step, group blocks of 512 39.3, of 1 024 39.0 - tools/experiments.sh group-out; hook seed_group_out = 0 switches it off)
+    sa.group_out = *shared && ctx->dbg.seed_group_out != 0 ? 1u : 0u;
+    const uint32_t owners = sa.group_out ? (uint32_t)*n_groups : (uint32_t)*n_groups * kWavesPerGroup;  // open blocks per region
+    const uint64_t per_wave = f.cap / ((uint64_t)owners * 8 * f.n_parts);
+    uint32_t want_reserve = (uint32_t)std::min<uint64_t>(f.n_parts > 8 ? (sa.group_out ? 1024 : 128) : 1024, std::max<uint64_t>(kWave, per_wave));
+    if (ctx->dbg.seed_reserve) want_reserve = std::min<uint32_t>(1024, std::max<uint32_t>(kWave, ctx->dbg.seed_reserve));
+    sa.reserve_log2 = 6;
+    while ((2u << sa.reserve_log2) <= want_reserve) ++sa.reserve_log2;
+    sa.reserve = 1u << sa.reserve_log2;
+    sa.pos_pad = f.pos_pad;
+    sa.pos_base = f.pos_base;
+    // a region gets its share of the expected hits + 15 % (read ranges differ) + the open blocks
+    uint64_t part_cap = f.cap / f.n_parts + f.cap / f.n_parts / 7 + 4096;
+    part_cap = std::max<uint64_t>(part_cap, (uint64_t)(1.2 * genome->seen_rate[f.max_mm] * std::min<uint32_t>(n_guides, kRegionReads)) + 4096);
+    sa.part_cap = part_cap + (uint64_t)owners * sa.reserve;
+    return hipSuccess;
+}
+
+// The search of a pass over guides[0 .. n_guides) (<= kMaxPassReads; read indices guide_base + i) up to final records, with
+// the genome's sizing hints it learns.  keep_bases (SEED): every hit's site lo plane beside its record.  Timings ADD to t.
+int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, uint32_t guide_base,
+              const vsc_search_params *params, bool keep_bases, vsc_timing &t, PassFound &f)
+{
+    const int algo = (int)t.algorithm;  // search_setup's choice
+    const uint32_t m = params->max_mismatches;
+    f.algo = algo;
+    f.max_mm = m;
+    f.guide_base = guide_base;
+    f.bases = keep_bases;
     // reads as (hi, lo) plane pairs, padded to the unroll factor with reads that can never match
     const uint32_t n_pad = (n_guides + kGuideUnroll - 1) / kGuideUnroll * kGuideUnroll;
     std::vector<uint32_t> gp((size_t)(n_pad + kGuideUnroll) * 2, 0xFFFFFFFFu);  // + one prefetch group
     for (uint32_t i = 0; i < n_guides; ++i) guide_planes(guides[i], &gp[2 * (size_t)i], &gp[2 * (size_t)i + 1]);
-    VSC_HIP_H(ctx->guides.ensure(gp.size() * sizeof(uint32_t)));
-    VSC_HIP_H(ctx->counters.ensure(kCounterWords * sizeof(unsigned long long)));
-    VSC_HIP_H(hipEventRecord(ctx->ev[0], ctx->stream));
-    VSC_HIP_H(hipMemcpyAsync(ctx->guides.p, gp.data(), gp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, ctx->guides.ensure(gp.size() * sizeof(uint32_t)));
+    VSC_HIP(ctx, ctx->counters.ensure(kCounterWords * sizeof(unsigned long long)));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->guides.p, gp.data(), gp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 
     const double own_bases = (double)genome->n_tiles * kTileBases;
     const double sites_est = genome->sites ? (double)genome->sites : own_bases / 4;
-    uint64_t cap = (uint64_t)(1.5 * sites_est * n_guides * hit_probability(params->max_mismatches)) + (1u << 20);
-    const double seen_rate = genome->seen_rate[params->max_mismatches];  // 0: no search with this budget yet
-    if (algo == VSC_ALGO_SCAN) cap = std::max<uint64_t>(cap, (uint64_t)(1.2 * seen_rate * n_guides) + 4096);
+    f.cap = (uint64_t)(1.5 * sites_est * n_guides * hit_probability(m)) + (1u << 20);
+    const double seen_rate = genome->seen_rate[m];  // 0: no search with this budget yet
+    if (algo == VSC_ALGO_SCAN) f.cap = std::max<uint64_t>(f.cap, (uint64_t)(1.2 * seen_rate * n_guides) + 4096);
     unsigned long long cnt[kCntPart + 4 * kParts] = {};
-    const int n_parts = (int)((n_guides + kRegionReads - 1) / kRegionReads);  // output regions of 64 reads
+    f.n_parts = (int)((n_guides + kRegionReads - 1) / kRegionReads);  // output regions of 64 reads
     // bits the positions of this shard need, counted from the shard's first position (a shard of the upper part of a
     // genome must not leave the top key bits constant); the records keep them at the top of their 32-bit position field
-    const uint32_t pos_base = (uint32_t)(genome->first_word * 32);
+    f.pos_base = (uint32_t)(genome->first_word * 32);
     const unsigned pos_bits = std::max(1u, ceil_log2((uint64_t)genome->dev_words * 32));
-    const unsigned pos_pad = pos_bits < 32 ? 32 - pos_bits : 0;
+    f.pos_pad = pos_bits < 32 ? 32 - pos_bits : 0;
+    f.key_bits = pos_bits + 1 + ceil_log2(std::min<uint32_t>(n_guides, kRegionReads));
 
     ScanArgs a{};
     SeedArgs sa{};
-    uint64_t part_cap = 0;
     int n_groups = 1;
     bool seed_shared = false;
     if (algo == VSC_ALGO_SCAN) {
@@ -1293,234 +1447,126 @@ int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, 
         fill_genome(a, ctx, genome);
         a.guides = (const uint4 *)ctx->guides.p;
         a.n_guides_padded = n_pad;
-        a.max_mm = params->max_mismatches;
-        a.k_half = params->max_mismatches / 2;  // bidir_mapping.cpp:129-146
+        a.max_mm = m;
+        a.k_half = m / 2;  // bidir_mapping.cpp:129-146
         n_groups = scan_groups(ctx, a.n_tiles);
         t.genome_bytes += (uint64_t)genome->n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        VSC_HIP_H(hipEventRecord(ctx->ev[7], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
     } else {
-        // ---- per-bucket read lists: a counting sort of the reads' segment neighbourhoods over the buckets ------
-        // The cut of the pigeonhole (SeedPlan, vsc_internal.h): segment 0 within k0 substitutions, segment 1 within k1, segment 2
-        // within what the site's PAM class leaves of the limit - k0 - k1 - 2.  Hook seed_tight = 0: floor(m / 3) everywhere (the
-        // round-3 cut); 1 + k0 + 3 k1: that cut, if it is a valid one.
-        const uint32_t m = params->max_mismatches;
-        auto nbr = [](int k) { return k < 0 ? 0u : (k == 0 ? 1u : (k == 1 ? 22u : 211u)); };
-        SeedPlan plan{};
-        plan.max_mm = m;
-        {
-            ScanArgs pa{};
-            vsc_search_params ip{};
-            ip.has_extra_pam = genome->index_has_extra_pam;
-            ip.extra_pam[0] = genome->index_extra_pam[0];
-            ip.extra_pam[1] = genome->index_extra_pam[1];
-            fill_pam(pa, &ip);  // the classes of the index, in the order build_index gave them
-            plan.n_pam = pa.n_pam;
-            plan.pam_codes = pam_code_set(pa);
-        }
-        plan.tight = ctx->dbg.seed_tight != 0;
-        int k2_max = 0;
-        if (!plan.tight) {
-            plan.k0 = plan.k1 = m / kSegments;
-            k2_max = (int)plan.k0;
-        } else {
-            // reads per (class, what the class leaves them for positions 0..20)
-            uint32_t left_reads[kSeedClasses][VSC_MAX_MISMATCHES + 1] = {};
-            int left_max = -1;
-            for (uint32_t i = 0; i < n_guides; ++i) {
-                const uint32_t x = gp[2 * (size_t)i], l = gp[2 * (size_t)i + 1];
-                const uint32_t mine = (((x >> 21) & 1u) << 3) | (((l >> 21) & 1u) << 2) | (((x >> 22) & 1u) << 1) | ((l >> 22) & 1u);
-                for (uint32_t c = 0; c < plan.n_pam; ++c) {
-                    const uint32_t diff = mine ^ ((plan.pam_codes >> (4 * c)) & 15u);
-                    const uint32_t spent = ((diff & 12u) ? 1u : 0u) + ((diff & 3u) ? 1u : 0u);
-                    if (spent > m) continue;
-                    left_reads[c][m - spent]++;
-                    left_max = std::max(left_max, (int)(m - spent));
-                }
-            }
-            // Every (k0, k1) in 0..2 that keeps the third threshold within two substitutions is a valid cut; they differ in what
-            // they cost.  Fewer buckets per read = fewer comparisons (what a dense search is bound by: c3), but a table whose
-            // lists are short still has nearly all of its chunks loaded for a read or two each (what a sparse search is bound by:
-            // at 1 000 reads and m = 6 the cut (2, 2, 0) compares 2.6 x the pairs of (1, 1, 2) and loads 14 % fewer blocks).
-            // cost = max(block bytes at 4.2 TB/s, chunk visits x 215 SIMD-cycles over all SIMDs at 2 GHz)
-            double cost[9];  // [k0 + 3 k1]; < 0: not a valid cut
-            double chunks_all = 0, sites_all = 0;
-            uint64_t reads_any = 0;
-            for (uint32_t c = 0; c < plan.n_pam; ++c) {
-                chunks_all += (double)genome->ix_class_chunks[c] / kSegments;
-                sites_all += (double)genome->ix_class_sites[c];
-                uint64_t reads_c = 0;
-                for (int left = 0; left <= (int)m; ++left) reads_c += left_reads[c][left];
-                reads_any = std::max(reads_any, reads_c);
-            }
-            const double block_bytes = (double)kVertWords * 4 / kSlicedSites;  // per site
-            for (int cut = 0; cut < 9; ++cut) {
-                const int k0 = cut % 3, k1 = cut / 3;
-                cost[cut] = -1;
-                if (left_max - k0 - k1 - 2 > 2) continue;
-                double bytes = 0, visits = 0;
-                for (uint32_t c = 0; c < plan.n_pam; ++c) {
-                    double e2 = 0;  // entries of class c's lists of segment 2
-                    for (int left = 0; left <= (int)m; ++left) e2 += (double)left_reads[c][left] * nbr(left - k0 - k1 - 2);
-                    const double per_list = e2 / kBucketsPerSeg;
-                    bytes += (1.0 - std::exp(-per_list)) * (double)genome->ix_class_sites[c] * block_bytes;
-                    visits += per_list * (double)genome->ix_class_chunks[c] / kSegments;
-                }
-                for (int k : {k0, k1}) {  // segments 0 and 1: one list per bucket for all classes
-                    const double per_list = (double)reads_any * nbr(k) / kBucketsPerSeg;
-                    bytes += (1.0 - std::exp(-per_list)) * sites_all * block_bytes;
-                    visits += per_list * chunks_all;
-                }
-                cost[cut] = std::max(bytes / 4.2e12, visits * 215.0 / ((double)ctx->n_cus * 4 * 2.0e9));
-            }
-            int best = -1;
-            for (int cut = 0; cut < 9; ++cut)
-                if (cost[cut] >= 0 && (best < 0 || cost[cut] < cost[best])) best = cut;
-            const int forced = ctx->dbg.seed_tight >= 1 ? ctx->dbg.seed_tight - 1 : -1;  // hook: 1 + k0 + 3 k1
-            if (forced >= 0 && forced < 9 && cost[forced] >= 0) best = forced;
-            if (best < 0) best = 4 * (int)(m ? (m - 1) / kSegments : 0u);  // (no read can reach any class: nothing to search)
-            plan.k0 = (uint32_t)(best % 3);
-            plan.k1 = (uint32_t)(best / 3);
-            k2_max = std::min<int>(2, (int)m - (int)plan.k0 - (int)plan.k1 - 2);
-        }
-        plan.n_nbr = nbr(std::max<int>(std::max<int>((int)plan.k0, (int)plan.k1), k2_max));
-        // entries: one per (read, neighbour within the threshold) of segments 0 and 1, one per class and neighbour of segment 2
-        const uint64_t n_pairs = (uint64_t)n_guides * (nbr((int)plan.k0) + nbr((int)plan.k1) + plan.n_pam * nbr(k2_max));
-        const uint64_t list_cap = n_pairs + (uint64_t)kLists * (kGuideUnroll - 1) + 2 * kGuideUnroll;
-        VSC_HIP_H(ctx->seed_off.ensure((kLists + 1) * sizeof(uint32_t)));
-        VSC_HIP_H(ctx->seed_poff.ensure((kLists + 1) * sizeof(uint32_t)));
-        VSC_HIP_H(ctx->seed_lrest.ensure(list_cap * sizeof(uint2)));
-        VSC_HIP_H(hipMemsetAsync(ctx->seed_lrest.p, 0xFF, list_cap * sizeof(uint2), ctx->stream));  // padding: y = ~0, skipped
-        VSC_HIP_H(launch_seed_lists((const uint2 *)ctx->guides.p, n_guides, plan, (uint32_t *)ctx->seed_off.p, (uint32_t *)ctx->seed_poff.p,
-                                    (uint2 *)ctx->seed_lrest.p, ctx->stream));
-        VSC_HIP_H(hipEventRecord(ctx->ev[7], ctx->stream));
-        sa.chunk_tab = genome->d_ix_chunk_tab;
-        sa.n_chunks = genome->ix_chunks;
-        sa.vert = genome->d_ix_vert;
-        sa.list_rest = (const uint2 *)ctx->seed_lrest.p;
-        sa.sites = genome->d_ix_sites;
-        sa.edge_bits = genome->d_ix_edge;
-        sa.guides = (const uint2 *)ctx->guides.p;
-        sa.poff = (const uint32_t *)ctx->seed_poff.p;
-        sa.max_mm = params->max_mismatches;
-        sa.k_half = params->max_mismatches / 2;
-        sa.k_seg0 = plan.k0;
-        sa.k_seg1 = plan.k1;
-        sa.contig_end = genome->d_contig_end;
-        sa.n_contigs = genome->n_contigs;
-        sa.counters = (unsigned long long *)ctx->counters.p;
-        uint32_t groups_per_cu = kSlicedWavesPerSimd;  // resident groups (of four waves) per CU: registers / LDS of the kernel
-        if (ctx->dbg.seed_groups_per_cu) groups_per_cu = ctx->dbg.seed_groups_per_cu;
-        // dense searches (c3: 129 reads per bucket) share a chunk between the four waves of a workgroup, sparse ones
-        // (c2: 13) keep a chunk per wave - see seed_sliced_kernel.  Measured at <= 8 mismatches (tools/
-        // experiments.sh shared-threshold): 51 reads per bucket 12.1 vs 11.4 ms, 77: 15.9 vs 16.0, 103: 19.9 vs 20.7
-        // (reads per list of segments 0 and 1 - and of segment 2 wherever it is searched as widely)
-        seed_shared = (uint64_t)n_guides * nbr((int)std::max(plan.k0, plan.k1)) / kBucketsPerSeg >= 72;
-        if (ctx->dbg.seed_shared >= 0) seed_shared = ctx->dbg.seed_shared == 1;
-        const uint32_t n_grabs = (sa.n_chunks + kSlicedGrab - 1) / kSlicedGrab;
-        const uint32_t n_waves_max = (uint32_t)ctx->n_cus * groups_per_cu * kWavesPerGroup;
-        const uint32_t n_waves = std::max<uint32_t>(1, std::min<uint32_t>(n_waves_max, seed_shared ? n_grabs * kWavesPerGroup : n_grabs));
-        n_groups = (int)((n_waves + kWavesPerGroup - 1) / kWavesPerGroup);
-        // block of records a wave reserves per atomic and region (a power of two, 64 .. 1024): large when many hits
-        // are expected, small otherwise (the unused tail of every wave's last block is written as sentinels
-        // and read by the sort)
-        // with chunk sharing the four waves of a workgroup also share their open output blocks: a quarter of the open
-        // lines and of the padding, so the blocks can be eight times as large (c3: per-wave blocks of 128 records 40.6 ms
-        // per step, group blocks of 512 39.3, of 1 024 39.0 - tools/experiments.sh group-out; hook seed_group_out = 0 switches it off)
-        sa.group_out = seed_shared && ctx->dbg.seed_group_out != 0 ? 1u : 0u;
-        const uint32_t owners = sa.group_out ? (uint32_t)n_groups : (uint32_t)n_groups * kWavesPerGroup;  // open blocks per region
-        const uint64_t per_wave = cap / ((uint64_t)owners * 8 * n_parts);
-        uint32_t want_reserve = (uint32_t)std::min<uint64_t>(n_parts > 8 ? (sa.group_out ? 1024 : 128) : 1024, std::max<uint64_t>(kWave, per_wave));
-        if (ctx->dbg.seed_reserve) want_reserve = std::min<uint32_t>(1024, std::max<uint32_t>(kWave, ctx->dbg.seed_reserve));
-        sa.reserve_log2 = 6;
-        while ((2u << sa.reserve_log2) <= want_reserve) ++sa.reserve_log2;
-        sa.reserve = 1u << sa.reserve_log2;
-        sa.n_parts = (uint32_t)n_parts;
-        sa.pos_pad = pos_pad;
-        sa.pos_base = pos_base;
-        // a region gets its share of the expected hits + 15 % (read ranges differ) + the open blocks
-        part_cap = cap / n_parts + cap / n_parts / 7 + 4096;
-        part_cap = std::max<uint64_t>(part_cap, (uint64_t)(1.2 * seen_rate * std::min<uint32_t>(n_guides, kRegionReads)) + 4096);
-        part_cap += (uint64_t)owners * sa.reserve;
-        cap = part_cap * n_parts;
+        VSC_HIP(ctx, seed_plan(ctx, genome, gp.data(), n_guides, f, sa, &n_groups, &seed_shared));
+        f.cap = sa.part_cap * f.n_parts;
     }
 
-    ht.lap("prep enqueue");
+    f.ht.lap("prep enqueue");
+    uint32_t list_total = 0;
     for (unsigned tries = 0;; ++tries) {
         // (the kernel keeps a block number in 20 bits, all ones meaning "full": part_cap / reserve < 2^20 - 1)
-        if (algo == VSC_ALGO_SEED && (part_cap >= (1ull << 32) - (1u << 20) || part_cap >= ((uint64_t)sa.reserve << 20) - sa.reserve))
+        if (algo == VSC_ALGO_SEED && (sa.part_cap >= (1ull << 32) - (1u << 20) || sa.part_cap >= ((uint64_t)sa.reserve << 20) - sa.reserve))
             return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in a block of 64 reads");
-        VSC_HIP_H(ctx->keys_a.ensure(cap * sizeof(uint64_t)));
-        VSC_HIP_H(hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
-        VSC_HIP_H(hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, ctx->keys_a.ensure(f.cap * sizeof(uint64_t)));
+        VSC_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
         if (algo == VSC_ALGO_SCAN) {
-            VSC_HIP_H(ctx->vals_a.ensure(cap * sizeof(uint32_t)));
+            VSC_HIP(ctx, ctx->vals_a.ensure(f.cap * sizeof(uint32_t)));
             a.hit_keys = (uint64_t *)ctx->keys_a.p;
             a.hit_vals = (uint32_t *)ctx->vals_a.p;
-            a.hit_cap = cap;
-            VSC_HIP_H(launch_scan(a, n_groups, false, ctx->stream));
+            a.hit_cap = f.cap;
+            VSC_HIP(ctx, launch_scan(a, n_groups, false, ctx->stream));
         } else {
             sa.hit_recs = (uint64_t *)ctx->keys_a.p;
-            sa.hit_side = nullptr;
-            if (want_rows) {
-                VSC_HIP_H(ctx->vals_a.ensure(cap * sizeof(uint32_t)));
+            if (keep_bases) {
+                VSC_HIP(ctx, ctx->vals_a.ensure(f.cap * sizeof(uint32_t)));
                 sa.hit_side = (uint32_t *)ctx->vals_a.p;
             }
-            sa.part_cap = part_cap;
-            VSC_HIP_H(launch_seed_sliced(sa, n_groups, seed_shared, ctx->stream));
+            VSC_HIP(ctx, launch_seed_sliced(sa, n_groups, seed_shared, ctx->stream));
         }
-        VSC_HIP_H(hipEventRecord(ctx->ev[2], ctx->stream));
-        VSC_HIP_H(hipMemcpyAsync(cnt, ctx->counters.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
-        uint32_t list_total = 0;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
         if (algo == VSC_ALGO_SEED)
-            VSC_HIP_H(hipMemcpyAsync(&list_total, (const uint32_t *)ctx->seed_poff.p + kLists, sizeof list_total, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP_H(hipStreamSynchronize(ctx->stream));
-        ht.lap("search kernel + sync");
+            VSC_HIP(ctx, hipMemcpyAsync(&list_total, (const uint32_t *)ctx->seed_poff.p + kLists, sizeof list_total, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        f.ht.lap("search kernel + sync");
         t.passes++;
-        if (algo == VSC_ALGO_SEED) {
-            t.list_entries = list_total;
-            t.seed_cut = sa.k_seg0 | (sa.k_seg1 << 4);
-        }
         if (!cnt[kCntOverflow]) break;
         if (tries >= 2) return fail(ctx, VSC_ERR_DEVICE, "vsc_search: hit buffer overflowed repeatedly");
         // the counters hold the true totals (SEED: records placed + records lost per region, + one block per wave)
         if (algo == VSC_ALGO_SEED) {
             uint64_t need = 0;
-            for (int q = 0; q < n_parts; ++q) need = std::max<uint64_t>(need, cnt[kCntPart + 4 * q] + cnt[kCntPart + 4 * q + 2]);
-            part_cap = need + (need >> 6) + 4096 + (uint64_t)(sa.group_out ? n_groups : n_groups * kWavesPerGroup) * sa.reserve;
-            cap = part_cap * n_parts;
+            for (int q = 0; q < f.n_parts; ++q) need = std::max<uint64_t>(need, cnt[kCntPart + 4 * q] + cnt[kCntPart + 4 * q + 2]);
+            sa.part_cap = need + (need >> 6) + 4096 + (uint64_t)(sa.group_out ? n_groups : n_groups * kWavesPerGroup) * sa.reserve;
+            f.cap = sa.part_cap * f.n_parts;
         } else {
-            cap = cnt[kCntHits] + (cnt[kCntHits] >> 6) + 4096;
+            f.cap = cnt[kCntHits] + (cnt[kCntHits] >> 6) + 4096;
         }
     }
     float ms = 0;
-    VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[7]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[7]));
     t.prep_ms += ms;
-    VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
     t.scan_ms += ms;
 
-    // ---- the segments of the sort: one per region ----------------------------------------------------
-    std::vector<SortSeg> segs;
-    uint64_t n = 0;
-    uint64_t *src = (uint64_t *)ctx->keys_a.p, *other = nullptr;
-    SortInfo info;
+    // ---- the records: one segment of pairs (SCAN) or one per region (SEED) ----------------------------------------
     if (algo == VSC_ALGO_SCAN) {
-        const_cast<vsc_genome *>(genome)->sites = cnt[kCntSites];
+        genome->sites = cnt[kCntSites];
         t.sites = cnt[kCntSites];
         t.pairs += cnt[kCntSites] * n_guides;
-        n = cnt[kCntHits];
-        const_cast<vsc_genome *>(genome)->seen_rate[params->max_mismatches] = (double)n / n_guides;
-        if (n >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in one scan pass (split the read set)");
-        if (n > 0 && !sum) {
+        f.n = cnt[kCntHits];
+        genome->seen_rate[m] = (double)f.n / n_guides;
+        if (f.n >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in one scan pass (split the read set)");
+        if (f.n > 0) f.segs.push_back(SortSeg{0, 0, 0, (uint32_t)f.n, guide_base});
+    } else {
+        t.list_entries = list_total;
+        t.seed_cut = sa.k_seg0 | (sa.k_seg1 << 4);
+        t.sites = genome->index_sites;
+        t.pairs += cnt[kCntSites];
+        t.genome_bytes += cnt[kCntVisited] * kVertWords * sizeof(uint32_t) / kSlicedSites;  // sites visited, 3.5 bytes each bit-sliced
+        double fullest = 0;
+        for (int q = 0; q < f.n_parts; ++q) {
+            const uint64_t placed = cnt[kCntPart + 4 * q], real = placed - cnt[kCntPart + 4 * q + 1];
+            fullest = std::max(fullest, (double)placed / std::min<uint32_t>(kRegionReads, n_guides - (uint32_t)q * kRegionReads));
+            if (placed) f.segs.push_back(SortSeg{(uint64_t)q * sa.part_cap, (uint64_t)q * sa.part_cap, f.n, (uint32_t)placed,
+                                                 guide_base + (uint32_t)q * kRegionReads});
+            f.n += real;
+        }
+        genome->seen_rate[m] = fullest;
+        // (the sort's second buffer, ctx->keys_b, is sized by bin_sort for the layout its first level uses)
+    }
+    t.hits += f.n;
+    return VSC_OK;
+}
+
+// The end of a sink: waits for the pass; the sink's own stage (ev[3] -> ev[4]) is finalize_ms, the whole pass total_ms.
+hipError_t end_pass(vsc_ctx *ctx, PassFound &f, const char *lap, vsc_timing &t)
+{
+    VSC_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    VSC_TRY(hipStreamSynchronize(ctx->stream));
+    f.ht.lap(lap);
+    float ms = 0;
+    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+    t.finalize_ms += ms;
+    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
+    t.total_ms += ms;
+    t.read_passes++;
+    return hipSuccess;
+}
+
+// Record sink (vsc_search, the stream calls): sorts the records into `hits` behind its `used` ones (`projected`: its expected
+// final size).  With f.bases the last stage also writes every hit's feature row into ctx->score_feat (pass row i at 64 i).
+int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hits, uint64_t used, uint64_t projected, vsc_timing &t)
+{
+    SortInfo info;
+    if (f.n > 0) {
+        uint64_t *src = (uint64_t *)ctx->keys_a.p, *other = nullptr;
+        if (f.algo == VSC_ALGO_SCAN) {
             // level 0: (key, value) pairs -> packed records, partitioned by region
-            VSC_HIP_H(ctx->keys_b.ensure(cap * sizeof(uint64_t)));
-            const unsigned bits0 = ceil_log2((uint64_t)n_parts);
+            VSC_HIP(ctx, ctx->keys_b.ensure(f.cap * sizeof(uint64_t)));
+            const unsigned bits0 = ceil_log2((uint64_t)f.n_parts);
             const size_t n_bins = (size_t)1 << bits0;
-            VSC_HIP_H(ctx->sort_segs.ensure(512));
-            VSC_HIP_H(ctx->sort_tabs.ensure(3 * n_bins * sizeof(uint32_t)));
-            SortSeg s0{0, 0, 0, (uint32_t)n, guide_base};
-            const uint32_t tile0[2] = {0u, (uint32_t)((n + kSortTile - 1) / kSortTile)};
-            VSC_HIP_H(hipMemcpyAsync(ctx->sort_segs.p, &s0, sizeof s0, hipMemcpyHostToDevice, ctx->stream));
-            VSC_HIP_H(hipMemcpyAsync((char *)ctx->sort_segs.p + 256, tile0, sizeof tile0, hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, ctx->sort_segs.ensure(512));
+            VSC_HIP(ctx, ctx->sort_tabs.ensure(3 * n_bins * sizeof(uint32_t)));
+            const uint32_t tile0[2] = {0u, (uint32_t)((f.n + kSortTile - 1) / kSortTile)};
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->sort_segs.p, f.segs.data(), sizeof(SortSeg), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->sort_segs.p + 256, tile0, sizeof tile0, hipMemcpyHostToDevice, ctx->stream));
             SortArgs l0{};
             l0.segs = (const SortSeg *)ctx->sort_segs.p;
             l0.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + 256);
@@ -1534,133 +1580,102 @@ int search_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, 
             l0.bin_start = l0.cursor + n_bins;
             l0.bin_bits = bits0;
             l0.bin_shift = kRecKeyBits;  // key >> 39 = read index >> 6 = region
-            l0.pos_pad = pos_pad;
-            l0.pos_base = pos_base;
-            VSC_HIP_H(hipMemsetAsync(l0.hist, 0, n_bins * sizeof(uint32_t), ctx->stream));
-            VSC_HIP_H(launch_bin_hist(l0, ctx->stream));
-            VSC_HIP_H(launch_bin_scan(l0, ctx->stream));
-            VSC_HIP_H(launch_bin_partition(l0, ctx->stream));
+            l0.pos_pad = f.pos_pad;
+            l0.pos_base = f.pos_base;
+            VSC_HIP(ctx, hipMemsetAsync(l0.hist, 0, n_bins * sizeof(uint32_t), ctx->stream));
+            VSC_HIP(ctx, launch_bin_hist(l0, ctx->stream));
+            VSC_HIP(ctx, launch_bin_scan(l0, ctx->stream));
+            VSC_HIP(ctx, launch_bin_partition(l0, ctx->stream));
             std::vector<uint32_t> tabs(3 * n_bins);
-            VSC_HIP_H(hipMemcpyAsync(tabs.data(), l0.hist, tabs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VSC_HIP_H(hipStreamSynchronize(ctx->stream));
-            for (int q = 0; q < n_parts; ++q) {
+            VSC_HIP(ctx, hipMemcpyAsync(tabs.data(), l0.hist, tabs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            f.segs.clear();
+            for (int q = 0; q < f.n_parts; ++q) {
                 const uint32_t count = tabs[q], start = tabs[2 * n_bins + q];
-                if (count) segs.push_back(SortSeg{start, start, used + start, count, guide_base + (uint32_t)q * kRegionReads});
+                if (count) f.segs.push_back(SortSeg{start, start, start, count, f.guide_base + (uint32_t)q * kRegionReads});
             }
             src = (uint64_t *)ctx->keys_b.p;
             other = (uint64_t *)ctx->keys_a.p;
-            info.bytes += 12 * n + 20 * n;  // histogram read; partition read 12, write 8
+            info.bytes += 12 * f.n + 20 * f.n;  // histogram read; partition read 12, write 8
         }
-    } else {
-        t.sites = genome->index_sites;
-        t.pairs += cnt[kCntSites];
-        t.genome_bytes += cnt[kCntVisited] * kVertWords * sizeof(uint32_t) / kSlicedSites;  // sites visited, 3.5 bytes each bit-sliced
-        double fullest = 0;
-        for (int q = 0; q < n_parts; ++q) {
-            const uint64_t placed = cnt[kCntPart + 4 * q], real = placed - cnt[kCntPart + 4 * q + 1];
-            fullest = std::max(fullest, (double)placed / std::min<uint32_t>(kRegionReads, n_guides - (uint32_t)q * kRegionReads));
-            if (placed) segs.push_back(SortSeg{(uint64_t)q * part_cap, (uint64_t)q * part_cap, used + n, (uint32_t)placed,
-                                               guide_base + (uint32_t)q * kRegionReads});
-            n += real;
-        }
-        const_cast<vsc_genome *>(genome)->seen_rate[params->max_mismatches] = fullest;
-        // (the sort's second buffer, ctx->keys_b, is sized by bin_sort for the layout its first level uses)
-    }
-    t.hits += n;
-    if (sum) {
-        // ---- summary: the regions (SEED) or the pairs (SCAN) as they are, into the per-read rows ----------------------
-        std::vector<SumSeg> ss;
-        std::vector<uint32_t> tile0(1, 0);
-        if (algo == VSC_ALGO_SCAN) {
-            if (n) ss.push_back(SumSeg{0, (uint32_t)n, 0});
-        } else {
-            for (const SortSeg &sg : segs) ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - guide_base});
-        }
-        for (const SumSeg &sg : ss) tile0.push_back(tile0.back() + (sg.n + kSumTile - 1) / kSumTile);
-        SummaryArgs sa_sum{};
-        if (!ss.empty()) {
-            const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
-            VSC_HIP_H(ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
-            VSC_HIP_H(hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, ctx->stream));
-            VSC_HIP_H(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t),
-                                     hipMemcpyHostToDevice, ctx->stream));
-            sa_sum.recs = (const uint64_t *)ctx->keys_a.p;
-            sa_sum.vals = algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
-            sa_sum.segs = (const SumSeg *)ctx->sort_segs.p;
-            sa_sum.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
-            sa_sum.n_segs = (uint32_t)ss.size();
-            sa_sum.n_tiles = tile0.back();
-            sa_sum.pos_pad = pos_pad;
-            sa_sum.pos_base = pos_base;
-            sa_sum.excl = sum->excl;
-            sa_sum.out = sum->out;
-        }
-        VSC_HIP_H(hipEventRecord(ctx->ev[3], ctx->stream));
-        VSC_HIP_H(launch_summary(sa_sum, ctx->stream));
-        VSC_HIP_H(hipEventRecord(ctx->ev[4], ctx->stream));
-        VSC_HIP_H(hipStreamSynchronize(ctx->stream));
-        ht.lap("summary + sync");
-        VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-        t.finalize_ms += ms;
-        VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-        t.total_ms += ms;
-        t.read_passes++;
-        res->n = n;
-        return VSC_OK;
-    }
-    if (n > 0) {
-        ht.lap("sort buffers");
-        VSC_HIP_H(result_room(ctx, hits, used, n, projected));
-        ht.lap("record storage");
-        const unsigned key_bits = pos_bits + 1 + ceil_log2(std::min<uint32_t>(n_guides, kRegionReads));
+        for (SortSeg &s : f.segs) s.final_off += used;
+        f.ht.lap("sort buffers");
+        VSC_HIP(ctx, result_room(ctx, hits, used, f.n, projected));
+        f.ht.lap("record storage");
         // the seed search's regions go through the slot partition (no histogram pass) unless this genome has shown
         // bins that outgrow their slots at this budget
-        bool *slots = algo == VSC_ALGO_SEED ? &const_cast<vsc_genome *>(genome)->sort_slots_ok[params->max_mismatches] : nullptr;
+        bool *slots = f.algo == VSC_ALGO_SEED ? &genome->sort_slots_ok[f.max_mm] : nullptr;
         SortRows rows;
-        if (want_rows) {
+        if (f.bases) {
             // the batch's rows, all at once (the caller reads them in its callback): 64 bytes per hit - 104 GB for 10 000 reads at
             // 8 mismatches on 3 Gbp.  If that does not fit beside the pooled buffers, those go back first.
-            if (ctx->score_feat.ensure(n * VSC_PACKED_FEATURE_BYTES) != hipSuccess) {
+            if (ctx->score_feat.ensure(f.n * VSC_PACKED_FEATURE_BYTES) != hipSuccess) {
                 (void)hipGetLastError();
                 for (auto &b : ctx->spare_records) b.release();
                 ctx->spare_records.clear();
                 for (DeviceBuf *b : {&ctx->score_mit, &ctx->score_flags, &ctx->score_sched, &ctx->keys_b, &ctx->vals_b}) b->release();
-                VSC_HIP_H(ctx->score_feat.ensure(n * VSC_PACKED_FEATURE_BYTES));
+                VSC_HIP(ctx, ctx->score_feat.ensure(f.n * VSC_PACKED_FEATURE_BYTES));
             }
             rows.side_src = (uint32_t *)ctx->vals_a.p;
             rows.side_other = &ctx->vals_b;
             rows.guides = (const uint2 *)ctx->guides.p;
-            rows.guide_first = guide_base;
+            rows.guide_first = f.guide_base;
             rows.rows = (uint4 *)ctx->score_feat.p;
             rows.rows_first = used;
         }
-        VSC_HIP_H(bin_sort(ctx, genome, std::move(segs), src, other, key_bits, pos_pad, pos_base, hits->d_records, ctx->ev[3], &info,
-                           algo == VSC_ALGO_SEED ? &ctx->keys_b : nullptr, slots, want_rows ? &rows : nullptr));
+        VSC_HIP(ctx, bin_sort(ctx, genome, std::move(f.segs), src, other, f.key_bits, f.pos_pad, f.pos_base, hits->d_records, ctx->ev[3],
+                              &info, f.algo == VSC_ALGO_SEED ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr));
     } else {
-        VSC_HIP_H(hipEventRecord(ctx->ev[3], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     }
-    VSC_HIP_H(hipEventRecord(ctx->ev[4], ctx->stream));
-    VSC_HIP_H(hipStreamSynchronize(ctx->stream));
-    ht.lap("sort + finalize + sync");
-    VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+    VSC_HIP(ctx, end_pass(ctx, f, "sort + finalize + sync", t));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
     t.sort_ms += ms;
-    VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
-    t.finalize_ms += ms;
-    VSC_HIP_H(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
-    t.total_ms += ms;
     t.sort_levels = std::max(t.sort_levels, info.levels);
     t.sort_bin_bits = std::max(t.sort_bin_bits, info.bin_bits);
     t.sort_bytes += info.bytes;
     t.sort_fallbacks += info.slot_fallbacks;
-    t.read_passes++;
-    res->n = n;
     return VSC_OK;
-#undef VSC_HIP_H
 }
 
-// common front end of vsc_search / vsc_search_stream: argument checks, choice of the algorithm, index
+// Summary sink (vsc_search_summary): summary_kernel adds the records where they lie into the pass's rows of ctx->sum_rows,
+// minus its loci in ctx->sum_excl if `excluded`.  No sort, no result buffer: finalize_ms times that kernel, sort_ms stays 0.
+int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t)
+{
+    std::vector<SumSeg> ss;
+    std::vector<uint32_t> tile0(1, 0);
+    for (const SortSeg &sg : f.segs) {
+        ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
+        tile0.push_back(tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
+    }
+    SummaryArgs a{};
+    if (!ss.empty()) {
+        const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
+        VSC_HIP(ctx, ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t),
+                                    hipMemcpyHostToDevice, ctx->stream));
+        a.recs = (const uint64_t *)ctx->keys_a.p;
+        a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
+        a.segs = (const SumSeg *)ctx->sort_segs.p;
+        a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
+        a.n_segs = (uint32_t)ss.size();
+        a.n_tiles = tile0.back();
+        a.pos_pad = f.pos_pad;
+        a.pos_base = f.pos_base;
+        a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+        a.out = (unsigned long long *)ctx->sum_rows.p + (size_t)f.guide_base * kSumWords;
+    }
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    VSC_HIP(ctx, launch_summary(a, ctx->stream));
+    VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
+    return VSC_OK;
+}
+
+// common front end of vsc_search / vsc_search_stream: argument checks, choice of the algorithm (t->algorithm), index
 int search_setup(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
-                 const vsc_search_params *params, const char *who, int *algo_out, vsc_timing *t)
+                 const vsc_search_params *params, const char *who, vsc_timing *t)
 {
     ctx->err.clear();
     if (!genome || !params || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
@@ -1693,8 +1708,44 @@ int search_setup(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides,
         }
     }
     t->algorithm = (uint32_t)algo;
-    *algo_out = algo;
     return VSC_OK;
+}
+
+// The batch loop of vsc_search_stream / vsc_search_stream_rows (`who`): one pass per batch into a result of its own, which
+// deliver(hits, first, count, t) hands on.  rows: the seed search writes the hits' feature rows with the records.
+template <class Deliver>
+int stream_batches(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                   uint32_t batch_reads, bool rows, const char *who, bool have_callback, Deliver &&deliver)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    vsc_timing t{};
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
+    if (rc != VSC_OK) return rc;
+    if (!have_callback) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null callback").c_str());
+    if (batch_reads == 0 || batch_reads > (uint32_t)kMaxPassReads) batch_reads = kMaxPassReads;
+    for (uint32_t first = 0; first < n_guides; first += batch_reads) {
+        const uint32_t count = std::min<uint32_t>(batch_reads, n_guides - first);
+        vsc_hits *hits = new (std::nothrow) vsc_hits();
+        if (!hits) return fail(ctx, VSC_ERR_NOMEM, (std::string(who) + ": out of host memory").c_str());
+        hits->ctx = ctx;
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, rows && t.algorithm == VSC_ALGO_SEED, t, f);
+        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, 0, 0, t);
+        if (prc == VSC_OK) {
+            hits->n = f.n;
+            if (f.n == 0) hits->host_valid = true;
+            ctx->timing = t;
+            ctx->timing.score_ms = 0;
+            prc = deliver(hits, first, count, t);
+            if (prc != VSC_OK && ctx->err.empty()) ctx->err = std::string(who) + ": the batch callback failed";
+        }
+        vsc_hits_free(hits);
+        if (prc != VSC_OK) return prc;
+    }
+    ctx->timing = t;
+    return VSC_OK;
+    });
 }
 
 }  // namespace
@@ -1708,25 +1759,25 @@ int vsc_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     if (!ctx || !out) return VSC_ERR_INVALID;
     *out = nullptr;
     vsc_timing t{};
-    int algo = 0;
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search", &algo, &t);
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search", &t);
     if (rc != VSC_OK) return rc;
     vsc_hits *hits = new (std::nothrow) vsc_hits();
     if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search: out of host memory");
     hits->ctx = ctx;
-    // a pass takes at most kMaxPassReads reads (128 output regions of 64 reads); larger sets are searched
+    // a pass takes at most kMaxPassReads reads (256 output regions of 64 reads); larger sets are searched
     // pass by pass - the read index is the major sort key, so the passes' results simply follow each other
     uint64_t used = 0;
     for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
         const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
         const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
-        PassResult r;
-        const int prc = search_pass(ctx, genome, guides + first, count, first, params, algo, hits, used, projected, t, &r);
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
+        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
         if (prc != VSC_OK) {
             vsc_hits_free(hits);
             return prc;
         }
-        used += r.n;
+        used += f.n;
     }
     hits->n = used;
     if (used == 0) hits->host_valid = true;
@@ -1743,8 +1794,7 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *g
     if (!ctx) return VSC_ERR_INVALID;
     if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary: null argument");
     vsc_timing t{};
-    int algo = 0;
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_summary", &algo, &t);
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_summary", &t);
     if (rc != VSC_OK) return rc;
     // the excluded loci as the records carry them: strand << 32 | global position
     std::vector<uint64_t> excl;
@@ -1776,10 +1826,9 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *g
     // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
     for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
         const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        SumTarget st{(unsigned long long *)ctx->sum_rows.p + (size_t)first * kSumWords,
-                     excl.empty() ? nullptr : (const uint64_t *)ctx->sum_excl.p + first};
-        PassResult r;
-        const int prc = search_pass(ctx, genome, guides + first, count, first, params, algo, nullptr, 0, 0, t, &r, false, &st);
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
+        if (prc == VSC_OK) prc = summarize_pass(ctx, f, !excl.empty(), t);
         if (prc != VSC_OK) return prc;
     }
     if (n_guides) {
@@ -1800,82 +1849,30 @@ double vsc_mit_specificity(uint64_t mit_sum)
 int vsc_search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                       const vsc_search_params *params, uint32_t batch_reads, vsc_batch_fn on_batch, void *user)
 {
-    return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
-    vsc_timing t{};
-    int algo = 0;
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_stream", &algo, &t);
-    if (rc != VSC_OK) return rc;
-    if (!on_batch) return fail(ctx, VSC_ERR_INVALID, "vsc_search_stream: null callback");
-    if (batch_reads == 0 || batch_reads > (uint32_t)kMaxPassReads) batch_reads = kMaxPassReads;
-    for (uint32_t first = 0; first < n_guides; first += batch_reads) {
-        const uint32_t count = std::min<uint32_t>(batch_reads, n_guides - first);
-        vsc_hits *hits = new (std::nothrow) vsc_hits();
-        if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_stream: out of host memory");
-        hits->ctx = ctx;
-        PassResult r;
-        int prc = search_pass(ctx, genome, guides + first, count, first, params, algo, hits, 0, 0, t, &r);
-        if (prc == VSC_OK) {
-            hits->n = r.n;
-            if (r.n == 0) hits->host_valid = true;
-            ctx->timing = t;
-            ctx->timing.score_ms = 0;
-            prc = on_batch(user, hits, first, count);
-            t.score_ms += ctx->timing.score_ms;  // what the callback's scoring calls measured
-            if (prc != VSC_OK && ctx->err.empty()) ctx->err = "vsc_search_stream: the batch callback failed";
-        }
-        vsc_hits_free(hits);
-        if (prc != VSC_OK) return prc;
-    }
-    ctx->timing = t;
-    return VSC_OK;
-    });
+    return stream_batches(ctx, genome, guides, n_guides, params, batch_reads, false, "vsc_search_stream", on_batch != nullptr,
+                          [&](vsc_hits *hits, uint32_t first, uint32_t count, vsc_timing &t) {
+                              const int prc = on_batch(user, hits, first, count);
+                              t.score_ms += ctx->timing.score_ms;  // what the callback's scoring calls measured
+                              return prc;
+                          });
 }
 
 int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                            const vsc_search_params *params, uint32_t batch_reads, vsc_rows_batch_fn on_batch, void *user)
 {
-    return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
-    vsc_timing t{};
-    int algo = 0;
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_stream_rows", &algo, &t);
-    if (rc != VSC_OK) return rc;
-    if (!on_batch) return fail(ctx, VSC_ERR_INVALID, "vsc_search_stream_rows: null callback");
-    if (batch_reads == 0 || batch_reads > (uint32_t)kMaxPassReads) batch_reads = kMaxPassReads;
-    for (uint32_t first = 0; first < n_guides; first += batch_reads) {
-        const uint32_t count = std::min<uint32_t>(batch_reads, n_guides - first);
-        vsc_hits *hits = new (std::nothrow) vsc_hits();
-        if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_stream_rows: out of host memory");
-        hits->ctx = ctx;
-        PassResult r;
-        // the seed search hands the sites' bases to the record assembly, which writes the rows; the streaming scan's hits
-        // (small searches on a genome without an index) are scored the usual way afterwards
-        int prc = search_pass(ctx, genome, guides + first, count, first, params, algo, hits, 0, 0, t, &r, algo == VSC_ALGO_SEED);
-        if (prc == VSC_OK) {
-            hits->n = r.n;
-            if (r.n == 0) hits->host_valid = true;
-            ctx->timing = t;
-            ctx->timing.score_ms = 0;
-            const void *rows = nullptr;
-            if (r.n && algo != VSC_ALGO_SEED) {
-                prc = vsc_score_hits_packed(ctx, genome, hits, guides, n_guides, 0, r.n, nullptr, nullptr, nullptr);
-                if (prc == VSC_OK && ctx->score_feat.cap < r.n * VSC_PACKED_FEATURE_BYTES)
-                    prc = fail(ctx, VSC_ERR_NOMEM, "vsc_search_stream_rows: the batch's rows do not fit the device at once (smaller batches)");
-                t.score_ms += ctx->timing.score_ms;
-            }
-            if (prc == VSC_OK) {
-                if (r.n) rows = ctx->score_feat.p;
-                prc = on_batch(user, hits, first, count, rows);
-                if (prc != VSC_OK && ctx->err.empty()) ctx->err = "vsc_search_stream_rows: the batch callback failed";
-            }
-        }
-        vsc_hits_free(hits);
-        if (prc != VSC_OK) return prc;
-    }
-    ctx->timing = t;
-    return VSC_OK;
-    });
+    return stream_batches(ctx, genome, guides, n_guides, params, batch_reads, true, "vsc_search_stream_rows", on_batch != nullptr,
+                          [&](vsc_hits *hits, uint32_t first, uint32_t count, vsc_timing &t) {
+                              // the seed search wrote the rows with the records; the streaming scan's hits (small searches on a
+                              // genome without an index) are scored the usual way
+                              if (hits->n && t.algorithm != VSC_ALGO_SEED) {
+                                  int prc = vsc_score_hits_packed(ctx, genome, hits, guides, n_guides, 0, hits->n, nullptr, nullptr, nullptr);
+                                  if (prc == VSC_OK && ctx->score_feat.cap < hits->n * VSC_PACKED_FEATURE_BYTES)
+                                      prc = fail(ctx, VSC_ERR_NOMEM, "vsc_search_stream_rows: the batch's rows do not fit the device at once (smaller batches)");
+                                  t.score_ms += ctx->timing.score_ms;
+                                  if (prc != VSC_OK) return prc;
+                              }
+                              return on_batch(user, hits, first, count, hits->n ? ctx->score_feat.p : nullptr);
+                          });
 }
 
 uint64_t vsc_hits_count(const vsc_hits *hits) { return hits ? hits->n : 0; }

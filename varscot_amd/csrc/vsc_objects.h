@@ -104,13 +104,14 @@ struct vsc_genome {
     uint64_t first_word = 0, own_words = 0, dev_words = 0;
     uint32_t n_tiles = 0, n_contigs = 0;
     uint64_t device_bytes = 0;
-    uint64_t sites = 0;  // PAM-valid windows seen by the last scan (sizes the next hit buffer)
+    // sites, seen_rate, sort_slots_ok: sizing hints that searches learn (mutable: a search takes the genome as const)
+    mutable uint64_t sites = 0;  // PAM-valid windows seen by the last scan (sizes the next hit buffer)
     // hits per read the last search with mismatch budget m produced (scan: all reads; seed: the fullest output
     // region) - real genomes are not the uniform model the first buffer size comes from
-    double seen_rate[VSC_MAX_MISMATCHES + 1] = {};
+    mutable double seen_rate[VSC_MAX_MISMATCHES + 1] = {};
     // the sort's first level may skip its histogram pass (slot partition) until a search with this budget has
     // produced a bin that outgrew its slot (repeats)
-    bool sort_slots_ok[VSC_MAX_MISMATCHES + 1] = {true, true, true, true, true, true, true, true, true};
+    mutable bool sort_slots_ok[VSC_MAX_MISMATCHES + 1] = {true, true, true, true, true, true, true, true, true};
     // seed index (vsc_seed.hip): the PAM-valid sites filed once per segment, sorted by bucket
     bool has_index = false;
     uint8_t index_has_extra_pam = 0;
