@@ -262,6 +262,41 @@ _Static_assert(sizeof(vsc_guide_summary) == 96, "vsc_guide_summary layout");
 #endif
 int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                        const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out);
+/*
+ * Per-guide selection: the specificity number AND the handful of off-targets that matter, from one search.  For every guide,
+ * of the hits vsc_search would return for the same genome, guides and params - minus the one at exclude[i] if that locus is
+ * a hit - with  score = rint(MIT * 2^24)  (MIT as vsc_score_hits computes it, round half to even: the summary's unit):
+ *   min_score  keeps the hits with score >= min_score (0: no floor);
+ *   top_k      keeps, of those, the first top_k in the total order (score descending, strand '+' before '-', global position
+ *              ascending) - ties in the score are broken by the order of vsc_search's result (0: no limit).  Records are
+ *              unique per guide, so the selected set is fully determined.
+ * The result is an ordinary vsc_hits SORTED AS vsc_search SORTS IT (guide, strand, contig, pos) that holds the selected records
+ * only: every vsc_hits_* / vsc_score_hits* / vsc_score_classify_hits / vsc_sam_order call works on it unchanged; the rank order
+ * is the caller's to restore (<= top_k records per guide).  top_k = 0, min_score = 0, exclude = NULL returns vsc_search's bytes.
+ * Selection composes over genome shards (the tie-break uses the global position): the selection of the union of the
+ * shards' selections is the selection on the whole genome.  Any n_guides (passes of <= 16 384 reads as vsc_search, every
+ * pass's survivors appended to the one result).
+ * The decision is made on the device over the search kernel's records where they lie (an exact radix select per guide): the
+ * sort, the result buffer and everything downstream see the survivors only - 100 000 guides at 8 mismatches on 3 Gbp with
+ * top_k = 100 return 160 MB instead of 260 GB.
+ * summary (optional, n_guides rows, host memory): the rows vsc_search_summary writes for the same arguments - over ALL hits -
+ * from the same search.  exclude: as vsc_search_summary (same validation); the excluded locus is neither selected nor counted.
+ * select == NULL or a non-zero reserved field: VSC_ERR_INVALID; the rest as vsc_search.
+ * vsc_ctx_timing afterwards: hits = all hits found (before the selection), scan_ms / prep_ms as after vsc_search, sort_ms =
+ * the selection kernels (+ the summary kernel if asked for) + the partition levels of the survivors' sort, finalize_ms as after
+ * vsc_search; sort_bytes counts what the bin sort moved: survivors only.
+ * Replaces, for a screen: bidir_mapping (read_mapping/bidir_mapping.cpp:285-295) + the per-hit MIT scores of the mergers
+ * (variant_processing/mit_score.h:12-68) + the cut by score the evaluation applies to the output afterwards
+ * (workflow/siteseqPipelineComparison.R:41-49, subset(..., Score > x)) or the top of CRISPOR's off-target list.
+ */
+typedef struct {
+    uint32_t top_k;      /* hits kept per guide, best first by (score desc, strand, position); 0 = no limit */
+    uint32_t min_score;  /* keep hits with rint(MIT * 2^24) >= min_score; 0 = no floor */
+    uint32_t reserved[2];
+} vsc_select;
+int vsc_search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                      const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                      vsc_guide_summary *summary, vsc_hits **out);
 /* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
  * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
 double vsc_mit_specificity(uint64_t mit_sum);
@@ -415,6 +450,15 @@ int vsc_multi_search(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *gu
  * between devices. */
 int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                              const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out);
+/* vsc_search_select over the device set: every shard selects among its own windows on its own context (from its own host
+ * thread); selection composes over shards, so with top_k > 0 the <= shards x top_k survivors per guide and their scores
+ * (vsc_score_hits on the shard's result) go to the host, are cut per guide to top_k in the same order, and the surviving
+ * records go in shard order through vsc_hits_merge on vsc_multi_result_ctx(m) - no RCCL leg; with top_k = 0 there is
+ * nothing to cut and the survivors can be many: they take vsc_multi_search's packed exchange and merge.  summary rows are
+ * added over the shards as vsc_multi_search_summary adds them. */
+int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                            vsc_guide_summary *summary, vsc_hits **out);
 /* (vsc_multi_search_stream, which scores on the owning shard, is declared behind the classifier below.) */
 
 /* ---- variant windows (row R8) ------------------------------------------------------------------- */

@@ -126,6 +126,28 @@ int main()
                 CHECK(same(all, expected(codes, 0, (uint32_t)codes.size(), fw)), "vsc_multi_search over %d shards", n);
                 vsc_hits_free(all);
             }
+            // selection: no cut = the search's records through the exchange; a cut = the first top_k of every read, cut on the host
+            for (uint32_t top_k : {0u, 3u}) {
+                vsc_select sel{};
+                sel.top_k = top_k;
+                std::vector<vsc_guide_summary> rows(codes.size());
+                vsc_hits *some = nullptr;
+                CHECK(vsc_multi_search_select(m, g, codes.data(), (uint32_t)codes.size(), &params, &sel, nullptr, rows.data(), &some) == VSC_OK && some,
+                      "select: %s", vsc_multi_last_error(m));
+                Expect all_of = expected(codes, 0, (uint32_t)codes.size(), fw), want;
+                std::vector<uint64_t> per_read(codes.size(), 0);
+                for (const vsc_hit &r : all_of.hits)
+                    if (per_read[r.guide]++ < top_k || !top_k) want.hits.push_back(r);
+                if (some) {
+                    CHECK(same(some, want), "vsc_multi_search_select (top_k %u) over %d shards", top_k, n);
+                    vsc_hits_free(some);
+                }
+                for (size_t i = 0; i < codes.size(); ++i)
+                    if (rows[i].nm[0] != per_read[i]) {
+                        CHECK(false, "summary row %zu of the selection (top_k %u)", i, top_k);
+                        break;
+                    }
+            }
             // streams: batch sizes that give 1, 2, 3, many batches (a ragged last one), every scoring mode
             for (uint32_t batch : {173u, 100u, 64u, 7u, 1u})
                 for (uint32_t mode : {(uint32_t)VSC_MULTI_SCORE_NONE, (uint32_t)VSC_MULTI_SCORE_ROWS, (uint32_t)VSC_MULTI_SCORE_VOTES}) {

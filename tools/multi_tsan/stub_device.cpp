@@ -196,6 +196,66 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides
     return VSC_OK;
 }
 
+// (vsc_multi_search_select: every stub hit has the same score, so a guide's top_k are its first top_k in result order)
+int vsc_search_select(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                      const vsc_select *sel, const vsc_locus *, vsc_guide_summary *summary, vsc_hits **out)
+{
+    const int rc = vsc_search(ctx, g, guides, n_guides, p, out);
+    if (rc != VSC_OK) return rc;
+    vsc_hits *h = *out;
+    if (summary) {
+        for (uint32_t i = 0; i < n_guides; ++i) summary[i] = vsc_guide_summary{};
+        for (const vsc_hit &r : h->host) summary[r.guide].nm[0]++;
+    }
+    if (sel->top_k) {
+        std::vector<vsc_hit> kept;
+        uint32_t run = 0;
+        for (size_t i = 0; i < h->host.size(); ++i) {
+            run = i && h->host[i - 1].guide == h->host[i].guide ? run + 1 : 0;
+            if (run < sel->top_k) kept.push_back(h->host[i]);
+        }
+        h->host.swap(kept);
+        h->n = h->host.size();
+    }
+    return VSC_OK;
+}
+
+int vsc_hits_copy(vsc_hits *h, void *dst, int)
+{
+    std::memcpy(dst, h->host.data(), h->host.size() * sizeof(vsc_hit));
+    return VSC_OK;
+}
+
+int vsc_score_hits(vsc_ctx *, const vsc_genome *, const vsc_hits *, const uint64_t *, uint32_t, uint64_t, uint64_t count, double *mit, uint8_t *,
+                   uint8_t *)
+{
+    for (uint64_t i = 0; i < count; ++i) mit[i] = 1.0;
+    return VSC_OK;
+}
+
+// (records of shard 0, shard 1, ... each sorted by key: per key the shards in order)
+int vsc_hits_merge(vsc_ctx *ctx, const void *records, int, const uint64_t *shard_counts, uint32_t n_shards, uint32_t n_guides, vsc_hits **out)
+{
+    vsc_hits *h = new vsc_hits();
+    h->ctx = ctx;
+    const vsc_hit *rec = (const vsc_hit *)records;
+    std::vector<uint64_t> at(n_shards, 0), end(n_shards, 0);
+    uint64_t off = 0;
+    for (uint32_t s = 0; s < n_shards; ++s) {
+        at[s] = off;
+        off += shard_counts[s];
+        end[s] = off;
+    }
+    for (uint32_t key = 0; key < 2 * n_guides; ++key)
+        for (uint32_t s = 0; s < n_shards; ++s)
+            for (; at[s] < end[s] && (rec[at[s]].guide << 1 | VSC_HIT_STRAND(rec[at[s]].info)) == key; ++at[s]) h->host.push_back(rec[at[s]]);
+    h->n = h->host.size();
+    h->host_valid = true;
+    stub::merges++;
+    *out = h;
+    return VSC_OK;
+}
+
 int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p, uint32_t,
                            vsc_rows_batch_fn on_batch, void *user)
 {

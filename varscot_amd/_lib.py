@@ -35,6 +35,15 @@ class SearchParams(C.Structure):
 ALGO_AUTO, ALGO_SCAN, ALGO_SEED = 0, 1, 2
 
 
+class Select(C.Structure):
+    """vsc_select: per guide, the top_k hits by rint(MIT * 2^24) among those >= min_score (0 = no limit / no floor)."""
+    _fields_ = [("top_k", C.c_uint32), ("min_score", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SELECT = Select
+assert C.sizeof(Select) == 16
+
+
 class RfModel(C.Structure):
     _fields_ = [("n_trees", C.c_uint32), ("n_nodes", C.c_uint32), ("node_status", C.c_void_p), ("feature", C.c_void_p),
                 ("left", C.c_void_p), ("right", C.c_void_p), ("split", C.c_void_p), ("node_class", C.c_void_p)]
@@ -125,6 +134,7 @@ SYMBOLS = [
     ("vsc_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, BATCH_FN, _vp]),
     ("vsc_search_stream_rows", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, ROWS_BATCH_FN, _vp]),
     ("vsc_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
+    ("vsc_search_select", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, C.POINTER(_vp)]),
     ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),
@@ -153,6 +163,7 @@ SYMBOLS = [
     ("vsc_multi_genome_build_index", C.c_int, [_vp, _vp, C.POINTER(SearchParams)]),
     ("vsc_multi_search", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(_vp)]),
     ("vsc_multi_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
+    ("vsc_multi_search_select", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, C.POINTER(_vp)]),
     ("vsc_multi_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, C.POINTER(MultiScore), MULTI_BATCH_FN, _vp]),
     ("vsc_windows_build", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                     C.POINTER(_vp), C.c_char_p, C.c_size_t]),

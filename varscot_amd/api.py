@@ -47,6 +47,19 @@ def mit_specificity(mit_sum):
     return lib().vsc_mit_specificity(int(mit_sum))
 
 
+def mit_fixed(mit):
+    """An MIT score as a floor for search_select: the smallest fixed-point score (units of 2^-24) that is >= mit."""
+    return int(np.ceil(float(mit) * 2.0 ** 24))
+
+
+def _select(top_k, min_score):
+    if not (0 <= int(top_k) < 2 ** 32 and 0 <= int(min_score) < 2 ** 32):
+        raise ValueError("top_k and min_score must fit 32 unsigned bits")
+    s = _lib.Select()
+    s.top_k, s.min_score = int(top_k), int(min_score)
+    return s
+
+
 class PackedGenome:
     """The host-side packed planes of a genome (0.375 byte per base) plus its contig table.
 
@@ -284,6 +297,24 @@ class Genome:
         out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
         check(lib().vsc_search_summary(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), ptr(out)), self.ctx._h)
         return out
+
+    def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
+                      summary=False):
+        """vsc_search_select: per guide, of the hits search() would return (minus the excluded locus), those with
+        rint(MIT * 2^24) >= min_score (mit_fixed() turns an MIT value into one) and of them the top_k best by (score
+        descending, strand, position); 0 = no floor / no limit.  Returns Hits sorted as search() sorts them - or, with
+        summary=True, (Hits, the SUMMARY_DTYPE rows of summarize() for the same arguments) from the one search."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        sel = _select(top_k, min_score)
+        ex = _loci(exclude, len(codes))
+        rows = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
+        h = C.c_void_p()
+        check(lib().vsc_search_select(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), ptr(ex), ptr(rows),
+                                      C.byref(h)), self.ctx._h)
+        hits = Hits(self, h, codes)
+        return (hits, rows) if summary else hits
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)
@@ -576,6 +607,22 @@ class MultiGenome:
         self.multi._check(lib().vsc_multi_search_summary(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
                                                          ptr(out)))
         return out
+
+    def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
+                      summary=False):
+        """vsc_multi_search_select: Genome.search_select over the shards; the merged records on the first context."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = Genome._params(max_mismatches, extra_pam, algorithm)
+        sel = _select(top_k, min_score)
+        ex = _loci(exclude, len(codes))
+        rows = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
+        h = C.c_void_p()
+        self.multi._check(lib().vsc_multi_search_select(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel),
+                                                        ptr(ex), ptr(rows), C.byref(h)))
+        res = MergedHits(_BorrowedContext(C.c_void_p(lib().vsc_multi_result_ctx(self.multi._h))), h)
+        self.multi._results.add(res)
+        return (res, rows) if summary else res
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

@@ -9,6 +9,13 @@
 //   #guideId guideSeq mitSpecScore offtargetCount onTargetFound mm0 .. mm<M> mitHitSum
 // mitSpecScore = floor(100 / (100 + mitHitSum) * 100 + 0.5) (CRISPOR's guide score and Python 2 round()),
 // mitHitSum = the sum of the counted hits' MIT scores (fixed point, 2^-24 units, printed with %.6f).
+// With -T hits.tsv the same search also lists every guide's off-targets that matter (vsc_search_select): the -K best by MIT
+// score and / or those with an MIT score >= -S, per guide in rank order (score descending, '+' before '-', position) under
+//   #guideId rank chrom start end strand mismatches mismatchPositions mitScore sequence
+// chrom = first word of the contig name, start / end 0-based half-open on the forward genome, mismatchPositions = 0-based
+// window positions on the forward genome (ascending, comma-separated, - if none), sequence = the window's forward-genome
+// bases.  The summary TSV is the same with and without these options.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +39,9 @@ int main(int argc, char **argv)
         {'P', "pam", "Additional non-canonical PAM that should be allowed for off-target search besides (N)GG and (N)GA (default).", false},
         {'D', "device", "HIP device index (default 0), or a comma-separated list (0,1,2,...): the genome is sharded over these "
                         "devices, each summarises its own windows, the counts are added on the host", false},
+        {'K', "top", "List the K best off-targets of every guide by MIT score in the -T file (default: no limit)", false},
+        {'S', "min-score", "List only off-targets with an MIT score >= this value, 0 .. 100, in the -T file (default: no floor)", false},
+        {'T', "hits", "Path to the TSV file of the listed off-targets (.tsv/.txt); required with -K / -S", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -58,6 +68,37 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "Error: Maximum number of mismatches must lie between 0 and 8.\n");
         return 1;
     }
+    vsc_select sel{};
+    const bool listing = opts[10].set;
+    const std::string hits_path = opts[10].value;
+    if (opts[8].set) {
+        const std::string &v = opts[8].value;
+        char *kend = nullptr;
+        const long long k = std::strtoll(v.c_str(), &kend, 10);
+        if (v.empty() || *kend || k < 0 || k > 0xFFFFFFFFll) {
+            std::fprintf(stderr, "%s: -K takes a number of hits, 0 (no limit) .. 4294967295, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        sel.top_k = (uint32_t)k;
+    }
+    if (opts[9].set) {
+        const std::string &v = opts[9].value;
+        char *send = nullptr;
+        const double x = std::strtod(v.c_str(), &send);
+        if (v.empty() || *send || !(x >= 0.0 && x <= 100.0)) {
+            std::fprintf(stderr, "%s: -S takes an MIT score, 0 .. 100, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        sel.min_score = (uint32_t)std::ceil(x * 0x1p24);  // the smallest fixed-point score that is >= x
+    }
+    if ((opts[8].set || opts[9].set) && !listing) {
+        std::fprintf(stderr, "%s: -K / -S select the off-targets listed in the -T file: give -T\n", argv[0]);
+        return 1;
+    }
+    if (listing && !has_extension(hits_path, {"tsv", "txt"})) {
+        std::fprintf(stderr, "%s: the -T file must be a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
     std::vector<int> devices;  // -D 0 | -D 0,1,2,3 (an id may repeat: several shards on one device)
     {
         const std::string d = opts[7].set ? opts[7].value : "0";
@@ -81,6 +122,7 @@ int main(int argc, char **argv)
     vsc_genome *genome = nullptr;
     vsc_multi *multi = nullptr;
     vsc_multi_genome *mgenome = nullptr;
+    vsc_hits *hits = nullptr;
     int rc = 1;
     try {
         const PackedIndex ix = read_index(index_prefix);
@@ -150,7 +192,13 @@ int main(int argc, char **argv)
         }
         std::vector<vsc_guide_summary> sum(codes.size());
         const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
-        if (multi) {
+        if (listing && multi) {
+            st = vsc_multi_search_select(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, &sel, ex, sum.data(), &hits);
+            if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
+        } else if (listing) {
+            st = vsc_search_select(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, &sel, ex, sum.data(), &hits);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        } else if (multi) {
             st = vsc_multi_search_summary(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
         } else {
@@ -182,11 +230,58 @@ int main(int argc, char **argv)
         } else {
             std::fwrite(text.data(), 1, text.size(), stdout);
         }
+        if (listing) {
+            // the selected records (sorted by guide, strand, contig, pos) and their scores, per guide into rank order
+            vsc_ctx *hctx = multi ? vsc_multi_result_ctx(multi) : ctx;
+            const uint64_t n = vsc_hits_count(hits);
+            std::vector<vsc_hit> rec(n);
+            std::vector<uint64_t> on(n);
+            std::vector<uint32_t> masks(n), score(n);
+            std::vector<double> mit(n);
+            if (n && vsc_hits_copy(hits, rec.data(), 0) != VSC_OK) throw std::runtime_error(vsc_last_error(hctx));
+            for (uint64_t i = 0; i < n; ++i) {
+                on[i] = codes[rec[i].guide];
+                masks[i] = VSC_HIT_MASK(rec[i].info);
+            }
+            if (vsc_score_pairs(hctx, on.data(), on.data(), masks.data(), n, mit.data(), nullptr, nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(hctx));
+            std::vector<uint64_t> order(n);
+            for (uint64_t i = 0; i < n; ++i) {
+                score[i] = (uint32_t)std::nearbyint(mit[i] * 0x1p24);
+                order[i] = i;
+            }
+            std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {  // (stable: ties keep the result order)
+                if (rec[a].guide != rec[b].guide) return rec[a].guide < rec[b].guide;
+                return score[a] > score[b];
+            });
+            std::string list = "#guideId\trank\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tmitScore\tsequence\n";
+            std::string window(VSC_READ_LEN, 'N');
+            uint32_t rank = 0;
+            for (uint64_t j = 0; j < n; ++j) {
+                const vsc_hit &h = rec[order[j]];
+                rank = j && rec[order[j - 1]].guide == h.guide ? rank + 1 : 1;
+                const std::string &name = ix.names[h.contig];
+                std::string positions;
+                for (int b = 0; b < VSC_READ_LEN; ++b)
+                    if ((VSC_HIT_MASK(h.info) >> b) & 1u) positions += (positions.empty() ? "" : ",") + std::to_string(b);
+                vsc_unpack_bases(ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs[h.contig].offset + h.pos, VSC_READ_LEN, &window[0]);
+                std::snprintf(buf, sizeof buf, "%.6f", (double)score[order[j]] * 0x1p-24);
+                list += ids[h.guide] + '\t' + std::to_string(rank) + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' +
+                        std::to_string(h.pos) + '\t' + std::to_string(h.pos + VSC_READ_LEN) + '\t' + (VSC_HIT_STRAND(h.info) ? '-' : '+') + '\t' +
+                        std::to_string(VSC_HIT_NM(h.info)) + '\t' + (positions.empty() ? "-" : positions) + '\t' + buf + '\t' + window + '\n';
+            }
+            std::ofstream out(hits_path);
+            if (!out.is_open()) throw std::runtime_error("Could not open the -T path.");
+            out << list;
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the -T file.");
+        }
         rc = 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "ERROR: %s\n", e.what());
         rc = 1;
     }
+    if (hits) vsc_hits_free(hits);
     if (multi) {
         vsc_multi_genome_free(mgenome);
         vsc_multi_destroy(multi);

@@ -210,7 +210,8 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     for (DeviceBuf *b : {&ctx->counters, &ctx->guides, &ctx->score_guides, &ctx->keys_a, &ctx->keys_b, &ctx->vals_a, &ctx->vals_b,
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
-                         &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl})
+                         &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
+                         &ctx->sel_masks})
         b->release();
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
@@ -1247,6 +1248,8 @@ struct PassFound {
     unsigned key_bits = 0, pos_pad = 0;  // bin_sort's key bits; the records' position encoding (with pos_base)
     uint32_t pos_base = 0;
     bool bases = false;  // SEED: every record's site lo plane lies beside it in ctx->vals_a (feature rows wanted)
+    bool selected = false;  // select_pass has run: n, segs, cap describe the survivors, packed records at the start of ctx->keys_a
+    std::vector<uint64_t> sel_off;  // select_pass's host staging (uploaded with hipMemcpyAsync: it must outlive the pass)
 };
 
 // words within k substitutions of a 7-base segment (k < 0: none)
@@ -1557,7 +1560,7 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
     SortInfo info;
     if (f.n > 0) {
         uint64_t *src = (uint64_t *)ctx->keys_a.p, *other = nullptr;
-        if (f.algo == VSC_ALGO_SCAN) {
+        if (f.algo == VSC_ALGO_SCAN && !f.selected) {
             // level 0: (key, value) pairs -> packed records, partitioned by region
             VSC_HIP(ctx, ctx->keys_b.ensure(f.cap * sizeof(uint64_t)));
             const unsigned bits0 = ceil_log2((uint64_t)f.n_parts);
@@ -1604,7 +1607,8 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
         f.ht.lap("record storage");
         // the seed search's regions go through the slot partition (no histogram pass) unless this genome has shown
         // bins that outgrow their slots at this budget
-        bool *slots = f.algo == VSC_ALGO_SEED ? &genome->sort_slots_ok[f.max_mm] : nullptr;
+        // (survivors of a selection say nothing about the genome's bins: they neither use nor change what it remembers)
+        bool *slots = f.algo == VSC_ALGO_SEED && !f.selected ? &genome->sort_slots_ok[f.max_mm] : nullptr;
         SortRows rows;
         if (f.bases) {
             // the batch's rows, all at once (the caller reads them in its callback): 64 bytes per hit - 104 GB for 10 000 reads at
@@ -1624,7 +1628,7 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
             rows.rows_first = used;
         }
         VSC_HIP(ctx, bin_sort(ctx, genome, std::move(f.segs), src, other, f.key_bits, f.pos_pad, f.pos_base, hits->d_records, ctx->ev[3],
-                              &info, f.algo == VSC_ALGO_SEED ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr));
+                              &info, f.algo == VSC_ALGO_SEED || f.selected ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr));
     } else {
         VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     }
@@ -1641,7 +1645,8 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
 
 // Summary sink (vsc_search_summary): summary_kernel adds the records where they lie into the pass's rows of ctx->sum_rows,
 // minus its loci in ctx->sum_excl if `excluded`.  No sort, no result buffer: finalize_ms times that kernel, sort_ms stays 0.
-int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t)
+// last = false (vsc_search_select with a summary): another sink follows and ends the pass; the kernel has run on return.
+int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, bool last = true)
 {
     std::vector<SumSeg> ss;
     std::vector<uint32_t> tile0(1, 0);
@@ -1669,7 +1674,137 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t)
     }
     VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     VSC_HIP(ctx, launch_summary(a, ctx->stream));
-    VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
+    if (last) VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
+    else VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the uploads above read this call's vectors)
+    return VSC_OK;
+}
+
+// Selection stage (vsc_search_select), between find_pass and sort_pass: decides on the device, over the records where the
+// search kernel left them, which survive - per read the sel.top_k best by rint(MIT * 2^24) among those >= sel.min_score that
+// are not the read's excluded locus (SelectArgs, vsc_internal.h) - and leaves the survivors as packed records, region after
+// region, at the start of ctx->keys_a: f.n, f.segs, f.cap describe them from here on, whichever algorithm found them, so the
+// bin sort, the result buffer and everything downstream see survivors only.  Beyond the search's own buffers: 4 bytes per
+// placed record (ctx->vals_b: the scores), 512 bytes per read of the pass (histograms) and 12 bytes per candidate.  One read-back
+// (the reads' candidate counts), as find_pass has one for its counters.
+int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &sel, bool excluded)
+{
+    f.selected = true;
+    if (f.n == 0) return VSC_OK;
+    hipStream_t st = ctx->stream;
+    std::vector<SumSeg> ss;
+    std::vector<uint32_t> tile0(1, 0);
+    for (const SortSeg &sg : f.segs) {
+        ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
+        tile0.push_back(tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
+    }
+    const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
+    VSC_HIP(ctx, ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, st));
+    VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    // per-read tables: thr, count, cursor, the regions' smallest thresholds (32-bit), then the lists' and the survivors' starts (64-bit)
+    const size_t words = ((size_t)n_reads + 63) / 64 * 64;
+    VSC_HIP(ctx, ctx->sel_tabs.ensure(4 * words * sizeof(uint32_t) + 2 * words * sizeof(uint64_t)));
+    VSC_HIP(ctx, ctx->sel_hist.ensure((size_t)n_reads * kSelBins * sizeof(uint32_t)));
+    VSC_HIP(ctx, ctx->vals_b.ensure((size_t)tile0.back() * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
+    SelectArgs a{};
+    a.recs = (const uint64_t *)ctx->keys_a.p;
+    a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
+    a.segs = (const SumSeg *)ctx->sort_segs.p;
+    a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
+    a.n_segs = (uint32_t)ss.size();
+    a.n_tiles = tile0.back();
+    a.pos_pad = f.pos_pad;
+    a.pos_base = f.pos_base;
+    a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+    a.min_score = sel.min_score;
+    a.top_k = sel.top_k;
+    a.n_reads = n_reads;
+    // enough workgroups for every CU, few table flushes per region
+    a.tiles_per_block = std::min<uint32_t>(kSelMaxTilesPerBlock, std::max<uint32_t>(kSelMinTilesPerBlock, a.n_tiles / (16u * (uint32_t)ctx->n_cus)));
+    a.score = (uint32_t *)ctx->vals_b.p;
+    a.hist = (uint32_t *)ctx->sel_hist.p;
+    a.thr = (uint32_t *)ctx->sel_tabs.p;
+    a.count = a.thr + words;
+    a.cursor = a.count + words;
+    a.thr_region = a.cursor + words;
+    uint64_t *d_off = (uint64_t *)(a.thr_region + words);
+    a.cand_off = d_off;
+    a.surv_off = d_off + words;
+    VSC_HIP(ctx, hipMemsetAsync(a.hist, 0, (size_t)n_reads * kSelBins * sizeof(uint32_t), st));
+    VSC_HIP(ctx, hipMemsetAsync(a.cursor, 0, words * sizeof(uint32_t), st));
+    VSC_HIP(ctx, hipMemsetAsync(a.thr_region, 0xFF, words * sizeof(uint32_t), st));
+    VSC_HIP(ctx, launch_select_score(a, st));
+    VSC_HIP(ctx, launch_select_threshold(a, st));
+    std::vector<uint32_t> count(n_reads);
+    VSC_HIP(ctx, hipMemcpyAsync(count.data(), a.count, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VSC_HIP(ctx, hipStreamSynchronize(st));
+    f.ht.lap("select: scores + thresholds + sync");
+    // the lists' and the survivors' starts; the survivors' regions are the segments of the sort
+    f.sel_off.assign(2 * words, 0);
+    uint64_t n_cand = 0, n_surv = 0;
+    for (uint32_t i = 0; i < n_reads; ++i) {
+        f.sel_off[i] = n_cand;
+        f.sel_off[words + i] = n_surv;
+        n_cand += count[i];
+        n_surv += sel.top_k ? std::min<uint32_t>(count[i], sel.top_k) : count[i];
+    }
+    f.segs.clear();
+    for (uint32_t q = 0; q * (uint32_t)kRegionReads < n_reads; ++q) {
+        const uint64_t begin = f.sel_off[words + (size_t)q * kRegionReads];
+        const uint32_t next = (q + 1) * (uint32_t)kRegionReads;
+        const uint64_t end = next < n_reads ? f.sel_off[words + next] : n_surv;
+        if (end - begin >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_select: more than 2^32 selected hits in a block of 64 reads");
+        if (end > begin) f.segs.push_back(SortSeg{begin, begin, begin, (uint32_t)(end - begin), f.guide_base + q * (uint32_t)kRegionReads});
+    }
+    f.n = n_surv;
+    f.cap = n_surv;
+    if (n_surv == 0) return VSC_OK;
+    VSC_HIP(ctx, ctx->sel_keys.ensure(n_cand * sizeof(uint64_t)));
+    VSC_HIP(ctx, ctx->sel_masks.ensure(n_cand * sizeof(uint32_t)));
+    a.cand_key = (uint64_t *)ctx->sel_keys.p;
+    a.cand_mask = (uint32_t *)ctx->sel_masks.p;
+    a.out = (uint64_t *)ctx->keys_a.p;  // (read for the last time by the compaction, which the stream runs first)
+    VSC_HIP(ctx, hipMemcpyAsync(d_off, f.sel_off.data(), f.sel_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VSC_HIP(ctx, launch_select_compact(a, st));
+    VSC_HIP(ctx, launch_select_resolve(a, st));
+    return VSC_OK;
+}
+
+// The excluded loci of vsc_search_summary / vsc_search_select (`who`) as the records carry them - strand << 32 | global
+// position, ~0: none - in excl (left empty without loci or reads).
+int excluded_loci(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *exclude, uint32_t n_guides, const char *who, std::vector<uint64_t> &excl)
+{
+    if (!exclude || !n_guides) return VSC_OK;
+    std::vector<uint32_t> off(genome->n_contigs), end(genome->n_contigs);
+    if (genome->n_contigs) {
+        VSC_HIP(ctx, hipMemcpy(off.data(), genome->d_contig_off, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        VSC_HIP(ctx, hipMemcpy(end.data(), genome->d_contig_end, end.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    excl.assign(n_guides, ~0ull);
+    for (uint32_t i = 0; i < n_guides; ++i) {
+        const vsc_locus &l = exclude[i];
+        if (l.contig == UINT32_MAX) continue;
+        if (l.contig >= genome->n_contigs || l.strand > 1)
+            return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": excluded locus outside the genome's contigs or strands").c_str());
+        if (l.pos >= end[l.contig] - off[l.contig]) continue;  // no window starts there: nothing to exclude
+        excl[i] = (uint64_t)l.strand << 32 | (off[l.contig] + l.pos);
+    }
+    return VSC_OK;
+}
+
+// the zeroed rows (if wanted) and the excluded loci of a call on the device
+int upload_summary_state(vsc_ctx *ctx, uint32_t n_guides, bool rows, const std::vector<uint64_t> &excl)
+{
+    if (!n_guides) return VSC_OK;
+    if (rows) {
+        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+        VSC_HIP(ctx, ctx->sum_rows.ensure(row_bytes));
+        VSC_HIP(ctx, hipMemsetAsync(ctx->sum_rows.p, 0, row_bytes, ctx->stream));
+    }
+    if (!excl.empty()) {
+        VSC_HIP(ctx, ctx->sum_excl.ensure(excl.size() * sizeof(uint64_t)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->sum_excl.p, excl.data(), excl.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    }
     return VSC_OK;
 }
 
@@ -1796,33 +1931,11 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *g
     vsc_timing t{};
     const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_summary", &t);
     if (rc != VSC_OK) return rc;
-    // the excluded loci as the records carry them: strand << 32 | global position
     std::vector<uint64_t> excl;
-    if (exclude && n_guides) {
-        std::vector<uint32_t> off(genome->n_contigs), end(genome->n_contigs);
-        if (genome->n_contigs) {
-            VSC_HIP(ctx, hipMemcpy(off.data(), genome->d_contig_off, off.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            VSC_HIP(ctx, hipMemcpy(end.data(), genome->d_contig_end, end.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        }
-        excl.assign(n_guides, ~0ull);
-        for (uint32_t i = 0; i < n_guides; ++i) {
-            const vsc_locus &l = exclude[i];
-            if (l.contig == UINT32_MAX) continue;
-            if (l.contig >= genome->n_contigs || l.strand > 1)
-                return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary: excluded locus outside the genome's contigs or strands");
-            if (l.pos >= end[l.contig] - off[l.contig]) continue;  // no window starts there: nothing to exclude
-            excl[i] = (uint64_t)l.strand << 32 | (off[l.contig] + l.pos);
-        }
-    }
-    if (n_guides) {
-        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
-        VSC_HIP(ctx, ctx->sum_rows.ensure(row_bytes));
-        VSC_HIP(ctx, hipMemsetAsync(ctx->sum_rows.p, 0, row_bytes, ctx->stream));
-        if (!excl.empty()) {
-            VSC_HIP(ctx, ctx->sum_excl.ensure(excl.size() * sizeof(uint64_t)));
-            VSC_HIP(ctx, hipMemcpyAsync(ctx->sum_excl.p, excl.data(), excl.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
+    const int erc = excluded_loci(ctx, genome, exclude, n_guides, "vsc_search_summary", excl);
+    if (erc != VSC_OK) return erc;
+    const int urc = upload_summary_state(ctx, n_guides, true, excl);
+    if (urc != VSC_OK) return urc;
     // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
     for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
         const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
@@ -1836,6 +1949,59 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *g
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+int vsc_search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                      const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                      vsc_guide_summary *summary, vsc_hits **out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    vsc_timing t{};
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_select", &t);
+    if (rc != VSC_OK) return rc;
+    if (!select) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select: null argument");
+    if (select->reserved[0] || select->reserved[1]) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select: reserved fields must be 0");
+    std::vector<uint64_t> excl;
+    const int erc = excluded_loci(ctx, genome, exclude, n_guides, "vsc_search_select", excl);
+    if (erc != VSC_OK) return erc;
+    const int urc = upload_summary_state(ctx, n_guides, summary != nullptr, excl);
+    if (urc != VSC_OK) return urc;
+    // nothing to decide: the records go to the sort as vsc_search hands them over
+    const bool selecting = select->top_k || select->min_score || !excl.empty();
+    vsc_hits *hits = new (std::nothrow) vsc_hits();
+    if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_select: out of host memory");
+    hits->ctx = ctx;
+    uint64_t used = 0;
+    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
+        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
+        const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
+        if (prc == VSC_OK && summary) prc = summarize_pass(ctx, f, !excl.empty(), t, false);
+        if (prc == VSC_OK && selecting) prc = select_pass(ctx, f, count, *select, !excl.empty());
+        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
+        if (prc != VSC_OK) {
+            vsc_hits_free(hits);
+            return prc;
+        }
+        used += f.n;
+    }
+    if (summary && n_guides) {
+        hipError_t e = hipMemcpyAsync(summary, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            vsc_hits_free(hits);
+            VSC_HIP(ctx, e);
+        }
+    }
+    hits->n = used;
+    if (used == 0) hits->host_valid = true;
+    ctx->timing = t;
+    *out = hits;
     return VSC_OK;
     });
 }

@@ -343,9 +343,52 @@ struct SummaryArgs {
     unsigned long long *out;    // kSumWords per pass-local read, zeroed once per call
 };
 
+// ---- per-guide selection (vsc_search_select; select_*_kernel in vsc_kernels.hip) -------------------------------------------
+// An exact per-read radix select on the composite key  score (31 bits) << 33 | ~(strand << 32 | global position) (33 bits):
+// the larger key is the better hit (score descending, '+' before '-', position ascending), and keys are unique per read.
+// Round 1 runs over the records where the search kernel left them (the two forms SummaryArgs describes): every record's
+// score goes into a word beside it and into its read's histogram over kSelBins monotone coarse bins of the score.  From the
+// histogram every read gets its threshold bin (the bin the K-th best lies in); round 2 copies the records of the bins >=
+// the threshold - the candidates - into per-read lists; the later rounds (select_resolve_kernel) run over a read's list only.
+constexpr int kSelBins = 128;            // score bin: 0 for score 0, else 1 + 4 * (31 - clz) + the next 2 bits (<= 124)
+constexpr int kSelThreads = 256;
+constexpr int kSelMaxTilesPerBlock = 128;  // tiles of kSumTile records a workgroup of round 1 / 2 walks through: as many as leave
+constexpr int kSelMinTilesPerBlock = 8;    // every CU a few workgroups (one LDS table flush of 8 192 cells per region a workgroup meets)
+constexpr uint32_t kSelDropped = ~0u;    // score word of a record that is no candidate (sentinel, excluded locus, below the floor)
+constexpr int kSelKeyPosBits = 33;
+
+struct SelectArgs {
+    const uint64_t *recs;       // as SummaryArgs
+    const uint32_t *vals;
+    const SumSeg *segs;
+    const uint32_t *seg_tile0;
+    uint32_t n_segs, n_tiles;
+    uint32_t pos_pad, pos_base;
+    const uint64_t *excl;       // per pass-local read, as SummaryArgs (null: none)
+    uint32_t min_score;         // records below it are dropped
+    uint32_t top_k;             // 0: no limit
+    uint32_t n_reads;           // reads of the pass
+    uint32_t tiles_per_block;   // kSelMinTilesPerBlock .. kSelMaxTilesPerBlock
+    uint32_t *score;            // one word per record of every tile (record k of tile i: i * kSumTile + k): round 1 writes, round 2 reads
+    uint32_t *hist;             // [n_reads * kSelBins], zeroed: records per (read, score bin)
+    uint32_t *thr;              // [n_reads] threshold bin
+    uint32_t *thr_region;       // [regions of kRegionReads reads], all ones before: the smallest threshold bin of the region's reads
+    uint32_t *count;            // [n_reads] candidates = records in the bins >= thr
+    uint32_t *cursor;           // [n_reads], zeroed: next free entry of the read's candidate list
+    const uint64_t *cand_off;   // [n_reads] first entry of the read's list in cand_key / cand_mask
+    const uint64_t *surv_off;   // [n_reads] first record of the read's survivors in `out`
+    uint64_t *cand_key;         // composite keys
+    uint32_t *cand_mask;        // mismatch masks beside them
+    uint64_t *out;              // survivors as packed records (layout above), reads in order, unsorted inside a read
+};
+
 // Launch wrappers implemented in vsc_kernels.hip.  They only enqueue work on `stream`.
 hipError_t launch_scan(const ScanArgs &args, int n_groups, bool extract, hipStream_t stream);
 hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream);
+hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream);      // round 1: scores + histograms
+hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream);  // histograms -> thr, count
+hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream);    // round 2: candidates into their reads' lists
+hipError_t launch_select_resolve(const SelectArgs &args, hipStream_t stream);    // later rounds + cut: survivors as packed records
 // vsc_sort.hip
 hipError_t launch_bin_hist(const SortArgs &args, hipStream_t stream);
 hipError_t launch_bin_scan(const SortArgs &args, hipStream_t stream);

@@ -991,6 +991,254 @@ hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream)
 }
 
 // ------------------------------------------------------------------------------------------------
+// per-guide selection: the top_k hits of every read by rint(MIT * 2^24), ties by (strand, global position); SelectArgs
+// ------------------------------------------------------------------------------------------------
+// Monotone coarse bin of a score: its exponent and the two bits below the leading one.  The scores of a read's hits
+// pile up near 0 (most hits have many mismatches) while the best reach 100 * 2^24: bins by the TOP bits of the score would put
+// every small-K threshold into one bin.
+__device__ __forceinline__ uint32_t select_bin(uint32_t score)
+{
+    if (score == 0) return 0;
+    const uint32_t e = 31u - (uint32_t)__clz(score);
+    const uint32_t mant = e >= 2u ? (score >> (e - 2u)) & 3u : (score << (2u - e)) & 3u;
+    return 1u + 4u * e + mant;
+}
+
+// record `at` of segment sg: pass-local read, strand << 32 | global position, mismatch mask; false: a sentinel
+template <bool kSeed>
+__device__ __forceinline__ bool select_decode(const SelectArgs &a, const SumSeg &sg, uint64_t at, uint32_t &read, uint64_t &locus, uint32_t &mask)
+{
+    const uint64_t r = a.recs[at];
+    if (kSeed) {
+        if (r >> 63) return false;
+        read = sg.first_read + (uint32_t)((r >> kRecReadShift) & (kRegionReads - 1));
+        const uint32_t pos = ((uint32_t)(r >> kRecPosShift) >> a.pos_pad) + a.pos_base;
+        locus = ((r >> kRecStrandShift) & 1ull) << 32 | pos;
+        mask = (uint32_t)r & kMask23;
+    } else {
+        read = (uint32_t)(r >> 33);
+        locus = r & ((1ull << kSelKeyPosBits) - 1ull);
+        mask = a.vals[at] & kMask23;
+    }
+    return true;
+}
+
+// the segment that holds tile `tile`: last s with seg_tile0[s] <= tile
+__device__ __forceinline__ uint32_t select_find_seg(const SelectArgs &a, uint32_t tile)
+{
+    uint32_t lo = 0, hi = a.n_segs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.seg_tile0[mid] <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Round 1, over the records where the search kernel left them (tiled as summary_kernel tiles them): every record's score
+// into the word beside it (kSelDropped: sentinel, excluded locus, below the floor) and into its read's histogram.  SEED: a
+// workgroup's tiles lie in one region at a time, whose 64 reads x 128 bins are an LDS table (32 KB, five workgroups per CU)
+// that goes out with one agent-scope atomic per nonzero cell; SCAN: the pairs of all reads arrive mixed, global atomics.
+// Neighbouring records belong to one read but to different bins, so the LDS atomics of a wave spread over a row of the table.
+template <bool kSeed>
+__global__ __launch_bounds__(kSelThreads) void select_score_kernel(const SelectArgs a)
+{
+    __shared__ uint32_t s_hist[kSeed ? kRegionReads * kSelBins : 1];
+    const uint32_t t = threadIdx.x;
+    if (kSeed) {
+        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSelBins); i += kSelThreads) s_hist[i] = 0;
+        block_sync();
+    }
+    const uint32_t tile_begin = blockIdx.x * a.tiles_per_block, tile_end = min(tile_begin + a.tiles_per_block, a.n_tiles);
+    uint32_t seg = select_find_seg(a, tile_begin);
+    auto flush_table = [&](const SumSeg &sg) {
+        block_sync();
+        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSelBins); i += kSelThreads) {
+            const uint32_t v = s_hist[i];
+            if (v) {
+                s_hist[i] = 0;
+                atomicAdd(&a.hist[(size_t)(sg.first_read + i / kSelBins) * kSelBins + i % kSelBins], v);
+            }
+        }
+        block_sync();
+    };
+    for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
+        if (tile >= a.seg_tile0[seg + 1]) {
+            if (kSeed) flush_table(a.segs[seg]);
+            while (tile >= a.seg_tile0[seg + 1]) ++seg;
+        }
+        const SumSeg sg = a.segs[seg];
+        const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile;
+#pragma unroll 2
+        for (int k = 0; k < kSumItems; ++k) {
+            const uint32_t i = first + (uint32_t)k * kSelThreads + t;
+            if (i >= sg.n) break;
+            const uint64_t at = sg.in_off + i;
+            uint32_t read, mask, score = kSelDropped;
+            uint64_t locus;
+            if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus)) {
+                int ub;
+                const uint32_t sc = (uint32_t)__builtin_rint(mit_score(mask, &ub) * 0x1p24);  // <= 100 * 2^24 < 2^31; as summary_kernel
+                if (sc >= a.min_score) {
+                    score = sc;
+                    if (kSeed) atomicAdd(&s_hist[(read - sg.first_read) * kSelBins + select_bin(sc)], 1u);
+                    else atomicAdd(&a.hist[(size_t)read * kSelBins + select_bin(sc)], 1u);
+                }
+            }
+            a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t] = score;
+        }
+    }
+    if (kSeed && tile_begin < tile_end) flush_table(a.segs[seg]);
+}
+
+// A read's histogram -> its threshold bin (the bin the top_k-th best score lies in; 0 when fewer pass or top_k = 0) and the
+// number of records in the bins from there up: the candidates.  One thread per read.
+__global__ __launch_bounds__(kSelThreads) void select_threshold_kernel(const SelectArgs a)
+{
+    const uint32_t read = blockIdx.x * kSelThreads + threadIdx.x;
+    if (read >= a.n_reads) return;
+    const uint32_t *h = a.hist + (size_t)read * kSelBins;
+    uint32_t sum = 0, thr = 0;
+    for (int b = kSelBins - 1; b >= 0; --b) {
+        sum += h[b];
+        if (a.top_k && sum >= a.top_k) {
+            thr = (uint32_t)b;
+            break;
+        }
+    }
+    a.thr[read] = thr;
+    a.count[read] = sum;
+    if (sum) atomicMin(&a.thr_region[read / kRegionReads], thr);  // (a read without candidates holds nothing back)
+}
+
+// Round 2, over the scores round 1 left: the records of the bins >= their read's threshold go, as composite key + mask, into
+// the read's candidate list (the lists' starts: prefix sums of the counts).  SEED: a score below every threshold of its
+// region - nearly all of them - is done with its 4 bytes; the record is read for the others only.
+template <bool kSeed>
+__global__ __launch_bounds__(kSelThreads) void select_compact_kernel(const SelectArgs a)
+{
+    const uint32_t t = threadIdx.x;
+    const uint32_t tile_begin = blockIdx.x * a.tiles_per_block, tile_end = min(tile_begin + a.tiles_per_block, a.n_tiles);
+    uint32_t seg = select_find_seg(a, tile_begin);
+    for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
+        while (tile >= a.seg_tile0[seg + 1]) ++seg;
+        const SumSeg sg = a.segs[seg];
+        const uint32_t region_thr = kSeed ? a.thr_region[sg.first_read / kRegionReads] : 0u;
+        const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile;
+#pragma unroll 2
+        for (int k = 0; k < kSumItems; ++k) {
+            const uint32_t i = first + (uint32_t)k * kSelThreads + t;
+            if (i >= sg.n) break;
+            const uint32_t sc = a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t];
+            if (sc == kSelDropped) continue;
+            const uint32_t bin = select_bin(sc);
+            if (kSeed && bin < region_thr) continue;  // (most records: below every threshold of the region, the record is not read)
+            uint32_t read, mask;
+            uint64_t locus;
+            if (!select_decode<kSeed>(a, sg, sg.in_off + i, read, locus, mask)) continue;
+            if (bin < a.thr[read]) continue;
+            const uint32_t slot = atomicAdd(&a.cursor[read], 1u);
+            if (slot >= a.count[read]) continue;  // (cannot happen: the histogram counted these very records)
+            const uint64_t p = a.cand_off[read] + slot;
+            a.cand_key[p] = (uint64_t)sc << kSelKeyPosBits | (~locus & ((1ull << kSelKeyPosBits) - 1ull));
+            a.cand_mask[p] = mask;
+        }
+    }
+}
+
+// The later rounds and the cut, one workgroup per read over the read's candidate list: if it holds more than top_k, the key of
+// the top_k-th best is found digit by digit (8 bits per round from the top; a round counts the keys that share the digits
+// found so far - only the boundary class goes on), then the keys >= it - exactly top_k, keys are unique - leave as packed
+// records (the form the bin sort takes) for the read's span of `out`.
+__global__ __launch_bounds__(kSelThreads) void select_resolve_kernel(const SelectArgs a)
+{
+    __shared__ uint32_t s_h[256];
+    __shared__ uint64_t s_prefix;
+    __shared__ uint32_t s_k, s_out;
+    const uint32_t t = threadIdx.x, read = blockIdx.x;
+    const uint32_t n = a.count[read];
+    if (n == 0) return;
+    const uint64_t *keys = a.cand_key + a.cand_off[read];
+    const uint32_t *masks = a.cand_mask + a.cand_off[read];
+    const uint32_t keep = a.top_k && n > a.top_k ? a.top_k : n;
+    uint64_t bound = 0;  // the smallest key that survives
+    if (keep < n) {
+        uint64_t prefix = 0;
+        uint32_t k = keep;
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            s_h[t] = 0;
+            block_sync();
+            for (uint32_t i = t; i < n; i += kSelThreads) {
+                const uint64_t key = keys[i];
+                if (shift == 56 || (key >> (shift + 8)) == prefix) atomicAdd(&s_h[(uint32_t)(key >> shift) & 255u], 1u);
+            }
+            block_sync();
+            if (t == 0) {
+                int d = 255;
+                for (; d > 0; --d) {  // the digit in which the k-th best of the class lies
+                    const uint32_t c = s_h[d];
+                    if (c >= k) break;
+                    k -= c;
+                }
+                s_k = k;
+                s_prefix = prefix << 8 | (uint64_t)d;
+            }
+            block_sync();
+            prefix = s_prefix;
+            k = s_k;
+        }
+        bound = prefix;
+    }
+    if (t == 0) s_out = 0;
+    block_sync();
+    const uint64_t out0 = a.surv_off[read];
+    for (uint32_t i = t; i < n; i += kSelThreads) {
+        const uint64_t key = keys[i];
+        if (key < bound) continue;
+        const uint32_t slot = atomicAdd(&s_out, 1u);
+        if (slot >= keep) continue;  // (cannot happen: exactly `keep` keys are >= bound)
+        const uint64_t locus = ~key & ((1ull << kSelKeyPosBits) - 1ull);
+        const uint64_t high = (uint64_t)((read & (kRegionReads - 1)) << 1) | (locus >> 32);  // read inside its region, strand
+        a.out[out0 + slot] = (((high << 32) | (uint32_t)(((uint32_t)locus - a.pos_base) << a.pos_pad)) << kRecPosShift) | masks[i];
+    }
+}
+
+hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
+    if (args.vals)
+        hipLaunchKernelGGL(select_score_kernel<false>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL(select_score_kernel<true>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream)
+{
+    if (args.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(select_threshold_kernel, dim3((args.n_reads + kSelThreads - 1) / kSelThreads), dim3(kSelThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
+    if (args.vals)
+        hipLaunchKernelGGL(select_compact_kernel<false>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL(select_compact_kernel<true>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_resolve(const SelectArgs &args, hipStream_t stream)
+{
+    if (args.n_reads == 0) return hipSuccess;
+    hipLaunchKernelGGL(select_resolve_kernel, dim3(args.n_reads), dim3(kSelThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // random-forest inference (classification/classificationPipeline.R:27-34, randomForest's classForest):
 // x[var] <= split ? left : right from the root until a terminal node, for every tree; votes for class "1".
 //

@@ -22,6 +22,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -362,10 +363,12 @@ double ms_between(clk::time_point a, clk::time_point b) { return std::chrono::du
 
 // on_batch(hits, first read, reads, votes on the first device or null) -> status; *keep = true: the callback took the hits over
 typedef std::function<int(vsc_hits *, uint32_t, uint32_t, const uint16_t *, bool *)> BatchSink;
+// what shard r runs in place of vsc_search on its context (vsc_multi_search_select without a cut: one batch, all reads)
+typedef std::function<int(size_t, vsc_hits **)> ShardSearch;
 
 // The engine behind vsc_multi_search and vsc_multi_search_stream (see the head of this file).
 int run_batches(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
-                uint32_t batch, const vsc_multi_score *score, const BatchSink &sink)
+                uint32_t batch, const vsc_multi_score *score, const BatchSink &sink, const ShardSearch &shard_search = nullptr)
 {
     const size_t n = m->ctx.size();
     const uint32_t mode = score ? score->mode : VSC_MULTI_SCORE_NONE;
@@ -474,7 +477,7 @@ int run_batches(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides,
                     }
                 } else {
                     vsc_hits *part = nullptr;
-                    rc = vsc_search(ctx, g->shard[r], guides + first, cnt, params, &part);
+                    rc = shard_search ? shard_search(r, &part) : vsc_search(ctx, g->shard[r], guides + first, cnt, params, &part);
                     if (rc == VSC_OK) {
                         rc = pack(part, false);
                         vsc_hits_free(part);  // the 8-byte records carry everything the merge needs
@@ -747,6 +750,137 @@ int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint
     }
     mt.search_wall_ms = wall;
     mt.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    mt.n_devices = (uint32_t)n;
+    mt.used_rccl = m->use_rccl ? 1u : 0u;
+    mt.batches = 1;
+    m->timing = mt;
+    return VSC_OK;
+    });
+}
+
+int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                            vsc_guide_summary *summary, vsc_hits **out)
+{
+    return mguarded(m, [&]() -> int {
+    if (!m || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    m->err.clear();
+    if (!g || g->multi != m || !params || !select || (n_guides && !guides))
+        return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: null argument");
+    if (select->reserved[0] || select->reserved[1]) return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: reserved fields must be 0");
+    if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
+        for (uint32_t i = 0; i < n_guides; ++i)
+            if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
+                return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: excluded locus outside the genome's contigs or strands");
+    const size_t n = m->ctx.size();
+    std::vector<std::vector<vsc_guide_summary>> part(summary ? n : 0);
+    for (size_t r = 0; r < part.size(); ++r)
+        if (g->shard[r]) part[r].resize(n_guides);
+    auto select_on = [&](size_t r, vsc_hits **h) {
+        return vsc_search_select(m->ctx[r], g->shard[r], guides, n_guides, params, select, exclude, summary ? part[r].data() : nullptr, h);
+    };
+    // the rows add exactly, as in vsc_multi_search_summary
+    auto add_rows = [&]() {
+        if (!summary) return;
+        std::fill(summary, summary + n_guides, vsc_guide_summary{});
+        for (size_t r = 0; r < n; ++r) {
+            if (!g->shard[r]) continue;
+            for (uint32_t i = 0; i < n_guides; ++i) {
+                const vsc_guide_summary &p = part[r][i];
+                vsc_guide_summary &o = summary[i];
+                o.mit_sum += p.mit_sum;
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.nm[k] += p.nm[k];
+                o.mit_ub += p.mit_ub;
+                o.on_target |= p.on_target;
+            }
+        }
+    };
+    if (select->top_k == 0) {
+        // nothing to cut: the shards' survivors are the result - through the packed exchange, they can be many
+        const int rc = run_batches(m, g, guides, n_guides, params, 0, nullptr, [&](vsc_hits *h, uint32_t, uint32_t, const uint16_t *, bool *keep) {
+            *out = h;
+            *keep = true;
+            return VSC_OK;
+        }, select_on);
+        if (rc == VSC_OK) add_rows();
+        return rc;
+    }
+    const auto t0 = clk::now();
+    // every shard: select, score the survivors, records and scores to the host
+    struct Cand {
+        uint32_t score, strand, contig, pos, shard;
+        uint64_t index;  // in the shard's records
+    };
+    std::vector<int> rc(n, VSC_OK);
+    std::vector<std::vector<vsc_hit>> rec(n);
+    std::vector<std::vector<double>> mit(n);
+    std::vector<vsc_timing> tm(n);
+    on_all(n, [&](size_t r) {
+        if (!g->shard[r]) return;
+        vsc_hits *h = nullptr;
+        rc[r] = select_on(r, &h);
+        if (rc[r] != VSC_OK) return;
+        (void)vsc_ctx_timing(m->ctx[r], &tm[r]);
+        const uint64_t c = vsc_hits_count(h);
+        try {
+            rec[r].resize(c);
+            mit[r].resize(c);
+        } catch (...) {
+            m->ctx[r]->err = "out of host memory";
+            rc[r] = VSC_ERR_NOMEM;
+        }
+        if (rc[r] == VSC_OK && c) rc[r] = vsc_hits_copy(h, rec[r].data(), 0);
+        if (rc[r] == VSC_OK && c) rc[r] = vsc_score_hits(m->ctx[r], g->shard[r], h, guides, n_guides, 0, c, mit[r].data(), nullptr, nullptr);
+        vsc_hits_free(h);
+    });
+    for (size_t r = 0; r < n; ++r)
+        if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
+    const double wall = ms_between(t0, clk::now());
+    // the cut: per guide the top_k of the shards' survivors by (score desc, strand, contig, pos) - (contig, pos) orders as the
+    // global position does.  A shard's records are sorted by guide: one cursor per shard walks them guide by guide.
+    std::vector<std::vector<char>> keep(n);
+    for (size_t r = 0; r < n; ++r) keep[r].assign(rec[r].size(), 0);
+    std::vector<uint64_t> at(n, 0);
+    std::vector<Cand> cand;
+    for (uint32_t gi = 0; gi < n_guides; ++gi) {
+        cand.clear();
+        for (size_t r = 0; r < n; ++r)
+            for (; at[r] < rec[r].size() && rec[r][at[r]].guide == gi; ++at[r]) {
+                const vsc_hit &h = rec[r][at[r]];
+                cand.push_back(Cand{(uint32_t)std::nearbyint(mit[r][at[r]] * 0x1p24), VSC_HIT_STRAND(h.info), h.contig, h.pos, (uint32_t)r, at[r]});
+            }
+        if (cand.size() > select->top_k) {
+            std::nth_element(cand.begin(), cand.begin() + select->top_k, cand.end(), [](const Cand &a, const Cand &b) {
+                if (a.score != b.score) return a.score > b.score;
+                if (a.strand != b.strand) return a.strand < b.strand;
+                if (a.contig != b.contig) return a.contig < b.contig;
+                return a.pos < b.pos;
+            });
+            cand.resize(select->top_k);
+        }
+        for (const Cand &c : cand) keep[c.shard][c.index] = 1;
+    }
+    std::vector<vsc_hit> all;
+    std::vector<uint64_t> counts(n, 0);
+    for (size_t r = 0; r < n; ++r)
+        for (size_t i = 0; i < rec[r].size(); ++i)
+            if (keep[r][i]) {
+                all.push_back(rec[r][i]);
+                counts[r]++;
+            }
+    const auto t_cut = clk::now();
+    const int mrc = vsc_hits_merge(m->merge_ctx, all.data(), 0, counts.data(), (uint32_t)n, n_guides, out);
+    if (mrc != VSC_OK) return mfail(m, mrc, std::string("merge: ") + vsc_last_error(m->merge_ctx));
+    add_rows();
+    vsc_multi_timing mt{};
+    for (size_t r = 0; r < n; ++r) {
+        mt.search_ms_max = std::max(mt.search_ms_max, tm[r].total_ms);
+        mt.hits += tm[r].hits;
+    }
+    mt.search_wall_ms = wall;
+    mt.merge_ms = ms_between(t_cut, clk::now());
+    mt.total_ms = ms_between(t0, clk::now());
     mt.n_devices = (uint32_t)n;
     mt.used_rccl = m->use_rccl ? 1u : 0u;
     mt.batches = 1;

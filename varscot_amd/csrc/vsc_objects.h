@@ -79,6 +79,8 @@ struct vsc_ctx {
     std::vector<uint32_t> host_tile0;  // bin sort: segment table + tile starts, per-bin tables, oversize list + counter
     vsc::DeviceBuf seed_off, seed_poff, seed_lrest;  // per-search read lists: bucket counts, padded list starts, entries
     vsc::DeviceBuf sum_rows, sum_excl;  // vsc_search_summary: the per-read rows it adds into, the excluded loci
+    // vsc_search_select: per-read tables of a pass (score histograms, thresholds, counts, cursors, list starts), the candidates' keys and masks
+    vsc::DeviceBuf sel_hist, sel_tabs, sel_keys, sel_masks;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
