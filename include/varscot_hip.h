@@ -297,6 +297,73 @@ typedef struct {
 int vsc_search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                       const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
                       vsc_guide_summary *summary, vsc_hits **out);
+/*
+ * Region-aware summary and selection: where do a guide's off-targets fall?  An annotation (exons, a gene of interest, regions
+ * the experiment does not care about, variant windows) is a set of intervals on the forward genome; a hit is IN THE REGIONS
+ * when its 23-base window [pos, pos + 23) meets the set under the set's rule:
+ *   VSC_REGION_OVERLAP  the window shares at least one base with some interval
+ *   VSC_REGION_INSIDE   the window lies fully inside ONE interval - the test filterRefAlignment applies to a reference hit
+ *                       and a variant window (variant_processing/filter_output_bam.h:70-124); two abutting intervals do not
+ *                       contain a window that spans their seam
+ * vsc_regions_build (host only, no device needed): iv = n intervals, 0-based half-open per contig as in BED, in any order,
+ * overlapping and nested as they come; `end` is clipped to the contig's length, empty intervals are dropped, n = 0 is valid
+ * (nothing is in the regions).  contig >= n_contigs, start > end, a non-zero reserved field or an unknown rule:
+ * VSC_ERR_INVALID.  contigs / n_contigs: the WHOLE genome's table, as for vsc_genome_load.  The object is immutable, owns no
+ * device memory and may be used with any context and any shard of that genome, from several threads at once; a context keeps
+ * the device copy of the regions it used last (uploaded on first use, given back by vsc_ctx_release_scratch).
+ * Inside: the intervals in global coordinates sorted by start, the running maximum of their ends (one binary search answers
+ * either rule), and two bits per block of block_bases window starts - no start of the block is in the regions / every start
+ * is / look it up - so that most hits are decided by one read of a table that stays in the L2 cache.
+ */
+typedef struct {
+    uint32_t contig, start, end, reserved; /* 0-based, half-open, forward genome (BED) */
+} vsc_interval;
+#define VSC_REGION_OVERLAP 0
+#define VSC_REGION_INSIDE 1
+typedef struct vsc_regions vsc_regions;
+typedef struct {
+    uint64_t intervals;    /* intervals kept (non-empty after clipping) */
+    uint32_t rule;         /* VSC_REGION_* */
+    uint32_t block_bases;  /* window starts per block of the class table: a power of two */
+    uint64_t blocks_out;   /* blocks none of whose starts is in the regions */
+    uint64_t blocks_in;    /* blocks all of whose starts are in the regions */
+    uint64_t blocks_mixed; /* blocks that need the interval search */
+} vsc_regions_stats;
+int vsc_regions_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_interval *iv, uint64_t n, uint32_t rule,
+                      vsc_regions **out);
+void vsc_regions_free(vsc_regions *r);
+/* 1 if the window that starts at (contig, pos) is in the regions, else 0 (also for a contig or position outside the genome). */
+int vsc_regions_contains(const vsc_regions *r, uint32_t contig, uint32_t pos);
+int vsc_regions_info(const vsc_regions *r, vsc_regions_stats *out);
+/*
+ * vsc_search_summary with a second set of rows: out_all = exactly what vsc_search_summary writes for the same arguments,
+ * out_in = the same fields over the counted hits that are in the regions (on_target as in out_all: the excluded locus is
+ * counted in neither).  One search, one pass of the summary kernel over the records where they lie; positions are global, so
+ * the rows of genome shards add up as the plain ones do.  regions == NULL or built for another contig table: VSC_ERR_INVALID.
+ */
+int vsc_search_summary_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                               const vsc_search_params *params, const vsc_locus *exclude, const vsc_regions *regions,
+                               vsc_guide_summary *out_all, vsc_guide_summary *out_in);
+/*
+ * vsc_search_select among the hits on one side of the regions: scope VSC_REGION_KEEP selects among the hits in the regions,
+ * VSC_REGION_DROP among those that are not; the floor and top_k then apply to what is left.  With a filter the stage runs
+ * also for top_k = 0, min_score = 0 and then returns exactly the filtered records in vsc_search's order: INSIDE + DROP is
+ * the reference-side shadow filter of the mergers (variant_processing/filter_output_bam.h:70-124) on the device.
+ * summary_all / summary_in (optional): the rows of vsc_search_summary_regions for the same arguments from the same search,
+ * whatever the scope.  filter == NULL: vsc_search_select (summary_in must then be NULL).  A non-zero reserved field, a scope
+ * > 1 or regions == NULL inside a filter: VSC_ERR_INVALID.
+ */
+#define VSC_REGION_KEEP 0
+#define VSC_REGION_DROP 1
+typedef struct {
+    const vsc_regions *regions;
+    uint32_t scope; /* VSC_REGION_KEEP / VSC_REGION_DROP */
+    uint32_t reserved;
+} vsc_region_filter;
+int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                              const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
+                              const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
+                              vsc_hits **out);
 /* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
  * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
 double vsc_mit_specificity(uint64_t mit_sum);
@@ -459,6 +526,16 @@ int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint
 int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                             const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
                             vsc_guide_summary *summary, vsc_hits **out);
+/* vsc_search_summary_regions / vsc_search_select_regions over the device set: the two calls above with the extra arguments
+ * handed to every shard (the regions are global, every context uploads its own copy on first use); out_in / summary_in are
+ * added on the host as the other rows are. */
+int vsc_multi_search_summary_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                     const vsc_search_params *params, const vsc_locus *exclude, const vsc_regions *regions,
+                                     vsc_guide_summary *out_all, vsc_guide_summary *out_in);
+int vsc_multi_search_select_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                    const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
+                                    const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
+                                    vsc_hits **out);
 /* (vsc_multi_search_stream, which scores on the owning shard, is declared behind the classifier below.) */
 
 /* ---- variant windows (row R8) ------------------------------------------------------------------- */

@@ -148,6 +148,36 @@ int main()
                         break;
                     }
             }
+            // the region-aware forms: the same two paths with the extra arguments and the second set of rows (a real vsc_regions
+            // object, empty; the stand-in does not consult it and counts every hit as inside)
+            const vsc_regions regions{};
+            for (uint32_t top_k : {0u, 3u}) {
+                vsc_select sel{};
+                sel.top_k = top_k;
+                vsc_region_filter flt{&regions, VSC_REGION_KEEP, 0};
+                std::vector<vsc_guide_summary> rows(codes.size()), rows_in(codes.size()), sum(codes.size()), sum_in(codes.size());
+                vsc_hits *some = nullptr;
+                CHECK(vsc_multi_search_select_regions(m, g, codes.data(), (uint32_t)codes.size(), &params, &sel, &flt, nullptr, rows.data(),
+                                                      rows_in.data(), &some) == VSC_OK && some, "select_regions: %s", vsc_multi_last_error(m));
+                CHECK(vsc_multi_search_summary_regions(m, g, codes.data(), (uint32_t)codes.size(), &params, nullptr, flt.regions, sum.data(),
+                                                       sum_in.data()) == VSC_OK, "summary_regions: %s", vsc_multi_last_error(m));
+                Expect all_of = expected(codes, 0, (uint32_t)codes.size(), fw), want;
+                std::vector<uint64_t> per_read(codes.size(), 0);
+                for (const vsc_hit &r : all_of.hits)
+                    if (per_read[r.guide]++ < top_k || !top_k) want.hits.push_back(r);
+                if (some) {
+                    CHECK(same(some, want), "vsc_multi_search_select_regions (top_k %u) over %d shards", top_k, n);
+                    vsc_hits_free(some);
+                }
+                for (size_t i = 0; i < codes.size(); ++i)
+                    if (rows[i].nm[0] != per_read[i] || rows_in[i].nm[0] != per_read[i] || sum[i].nm[0] != per_read[i] || sum_in[i].nm[0] != per_read[i]) {
+                        CHECK(false, "rows %zu of the region-aware calls (top_k %u)", i, top_k);
+                        break;
+                    }
+                flt.scope = 2;
+                CHECK(vsc_multi_search_select_regions(m, g, codes.data(), (uint32_t)codes.size(), &params, &sel, &flt, nullptr, nullptr, nullptr,
+                                                      &some) == VSC_ERR_INVALID && !some, "a bad filter is refused");
+            }
             // streams: batch sizes that give 1, 2, 3, many batches (a ragged last one), every scoring mode
             for (uint32_t batch : {173u, 100u, 64u, 7u, 1u})
                 for (uint32_t mode : {(uint32_t)VSC_MULTI_SCORE_NONE, (uint32_t)VSC_MULTI_SCORE_ROWS, (uint32_t)VSC_MULTI_SCORE_VOTES}) {

@@ -196,6 +196,26 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides
     return VSC_OK;
 }
 
+// (the region-aware sinks: the stand-in has no regions - its hits count as inside)
+int vsc_search_summary_regions(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                               const vsc_locus *ex, const vsc_regions *, vsc_guide_summary *out_all, vsc_guide_summary *out_in)
+{
+    const int rc = vsc_search_summary(ctx, g, guides, n_guides, p, ex, out_all);
+    for (uint32_t i = 0; rc == VSC_OK && i < n_guides; ++i) out_in[i] = out_all[i];
+    return rc;
+}
+
+int vsc_search_select(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                      const vsc_select *sel, const vsc_locus *, vsc_guide_summary *summary, vsc_hits **out);
+int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                              const vsc_select *sel, const vsc_region_filter *, const vsc_locus *ex, vsc_guide_summary *summary_all,
+                              vsc_guide_summary *summary_in, vsc_hits **out)
+{
+    const int rc = vsc_search_select(ctx, g, guides, n_guides, p, sel, ex, summary_all ? summary_all : summary_in, out);
+    for (uint32_t i = 0; rc == VSC_OK && summary_all && summary_in && i < n_guides; ++i) summary_in[i] = summary_all[i];
+    return rc;
+}
+
 // (vsc_multi_search_select: every stub hit has the same score, so a guide's top_k are its first top_k in result order)
 int vsc_search_select(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
                       const vsc_select *sel, const vsc_locus *, vsc_guide_summary *summary, vsc_hits **out)

@@ -12,6 +12,9 @@ wall time per step (mean, and the fastest and slowest step).
 Before each path the context's pooled scratch is given back; the device memory the path then takes (free memory before
 minus after its steps, results freed: the pooled buffers) is reported as pooled_bytes - the record path's includes the
 sort's slot layout and the result's room, the selection's does not.
+--regions N,FRACTION adds, for every K, the selection among the hits in a synthetic annotation (vsc_search_select_regions,
+scope keep; N random intervals covering FRACTION of the genome as tools/summary_bench.py makes them) and its ratio to the
+plain selection of the same process.
 """
 import argparse
 import json
@@ -60,6 +63,10 @@ def main():
     ap.add_argument("--top-k", type=int, nargs="+", default=[20, 100])
     ap.add_argument("--batch", type=int, default=10_000, help="c5 record path: reads per streamed batch (bench.py --batch)")
     ap.add_argument("--select-only", action="store_true", help="time the selection only")
+    ap.add_argument("--regions", type=lambda t: (int(t.split(",")[0]), float(t.split(",")[1])), metavar="N,FRACTION",
+                    help="also time the selection among the hits in N random intervals covering FRACTION of the genome")
+    ap.add_argument("--rule", default="overlap", choices=["overlap", "inside"], help="--regions: the membership rule")
+    ap.add_argument("--scope", default="keep", choices=["keep", "drop"], help="--regions: the side the selection is made on")
     args = ap.parse_args()
     names = ["c3", "c5"] if args.workload == "both" else [args.workload]
     total_bases = WORKLOADS[names[0]][1]
@@ -72,6 +79,9 @@ def main():
     genome = va.Genome.from_shard(ctx, hi, lo, nm, wb, we - wb, table)
     del hi, lo, nm
     genome.build_index()
+    regions = None
+    if args.regions:
+        regions = va.Regions(va.PackedGenome(None, None, None, table), synth.synthetic_regions(table, *args.regions), rule=args.rule)
     for name in names:
         n_guides, _, max_mm = WORKLOADS[name]
         _, seqs = synth.synthetic_guides(n_guides)
@@ -88,6 +98,18 @@ def main():
             t = ctx.timing()
             res["select"][str(k)] = {"ms_per_step": ms, "selected": kept, "result_bytes": 16 * kept, "pooled_bytes": held,
                                      "timing": {f: t[f] for f in SPLIT}}
+            if regions is not None:
+                def step_regions():
+                    h = genome.search_select(codes, max_mm, top_k=k, algorithm="seed", regions=regions, region_scope=args.scope)
+                    n = len(h)
+                    h.close()
+                    return n
+                ms_r, kept_r, held_r = pooled(ctx, step_regions, args.steps, args.warmup)
+                t = ctx.timing()
+                res.setdefault("select_regions", {"intervals": args.regions[0], "fraction": args.regions[1], "rule": args.rule,
+                                                  "scope": args.scope, "info": regions.info()})[str(k)] = {
+                    "ms_per_step": ms_r, "selected": kept_r, "pooled_bytes": held_r, "timing": {f: t[f] for f in SPLIT},
+                    "regions_vs_plain": ms_r["mean"] / ms["mean"]}
         if not args.select_only:
             if name == "c5":
                 got = [0]
@@ -113,6 +135,8 @@ def main():
             res["same_hits"] = all(v["timing"]["hits"] == n_rec for v in res["select"].values())
             res["select_vs_records"] = {k: v["ms_per_step"]["mean"] / ms["mean"] for k, v in res["select"].items()}
         print(json.dumps(res), flush=True)
+    if regions is not None:
+        regions.close()
     genome.close()
     ctx.close()
 

@@ -44,6 +44,26 @@ SELECT = Select
 assert C.sizeof(Select) == 16
 
 
+# vsc_interval: one interval of an annotation (vsc_regions_build), 0-based half-open on the forward genome
+INTERVAL_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4")])
+REGION_OVERLAP, REGION_INSIDE = 0, 1
+REGION_KEEP, REGION_DROP = 0, 1
+
+
+class RegionFilter(C.Structure):
+    """vsc_region_filter: select among the hits in the regions (scope REGION_KEEP) or among those outside (REGION_DROP)."""
+    _fields_ = [("regions", C.c_void_p), ("scope", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RegionsStats(C.Structure):
+    """vsc_regions_stats (vsc_regions_info)."""
+    _fields_ = [("intervals", C.c_uint64), ("rule", C.c_uint32), ("block_bases", C.c_uint32), ("blocks_out", C.c_uint64),
+                ("blocks_in", C.c_uint64), ("blocks_mixed", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class RfModel(C.Structure):
     _fields_ = [("n_trees", C.c_uint32), ("n_nodes", C.c_uint32), ("node_status", C.c_void_p), ("feature", C.c_void_p),
                 ("left", C.c_void_p), ("right", C.c_void_p), ("split", C.c_void_p), ("node_class", C.c_void_p)]
@@ -135,6 +155,13 @@ SYMBOLS = [
     ("vsc_search_stream_rows", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, ROWS_BATCH_FN, _vp]),
     ("vsc_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
     ("vsc_search_select", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_regions_build", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_regions_free", None, [_vp]),
+    ("vsc_regions_contains", C.c_int, [_vp, C.c_uint32, C.c_uint32]),
+    ("vsc_regions_info", C.c_int, [_vp, C.POINTER(RegionsStats)]),
+    ("vsc_search_summary_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
+    ("vsc_search_select_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), C.POINTER(RegionFilter),
+                                            _vp, _vp, _vp, C.POINTER(_vp)]),
     ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),
@@ -164,6 +191,9 @@ SYMBOLS = [
     ("vsc_multi_search", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(_vp)]),
     ("vsc_multi_search_summary", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp]),
     ("vsc_multi_search_select", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_multi_search_summary_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
+    ("vsc_multi_search_select_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select),
+                                                  C.POINTER(RegionFilter), _vp, _vp, _vp, C.POINTER(_vp)]),
     ("vsc_multi_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, C.POINTER(MultiScore), MULTI_BATCH_FN, _vp]),
     ("vsc_windows_build", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                     C.POINTER(_vp), C.c_char_p, C.c_size_t]),

@@ -60,6 +60,61 @@ def _select(top_k, min_score):
     return s
 
 
+def _region_filter(regions, scope):
+    """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
+    if regions is None:
+        return None
+    if scope not in ("keep", "drop"):
+        raise ValueError("region_scope must be 'keep' or 'drop'")
+    return _lib.RegionFilter(regions._h, _lib.REGION_DROP if scope == "drop" else _lib.REGION_KEEP, 0)
+
+
+class Regions:
+    """An annotation to test hits against (vsc_regions): `intervals` = (contig, start, end) triples - 0-based, half-open, on
+    the forward genome as in BED; unsorted, overlapping, nested as they come - or an INTERVAL_DTYPE array.  A hit is in the
+    regions when its 23-base window shares a base with some interval (rule="overlap") or lies fully inside one interval
+    (rule="inside", the reference's filterRefAlignment test).  Host-side and immutable; every context that uses it keeps a
+    device copy while it is the last one it used."""
+
+    def __init__(self, packed_genome, intervals, rule="overlap"):
+        if rule not in ("overlap", "inside"):
+            raise ValueError("rule must be 'overlap' or 'inside'")
+        if isinstance(intervals, np.ndarray) and intervals.dtype == _lib.INTERVAL_DTYPE:
+            iv = np.ascontiguousarray(intervals)
+        else:
+            a = np.asarray(intervals, dtype=np.int64).reshape(-1, 3)
+            if len(a) and (a.min() < 0 or a.max() >= 2 ** 32):
+                raise ValueError("interval fields must fit 32 unsigned bits")
+            iv = np.zeros(len(a), dtype=_lib.INTERVAL_DTYPE)
+            iv["contig"], iv["start"], iv["end"] = a[:, 0], a[:, 1], a[:, 2]
+        contigs = np.ascontiguousarray(packed_genome.contigs, dtype=CONTIG_DTYPE)
+        self.rule = rule
+        self._h = C.c_void_p()
+        check(lib().vsc_regions_build(ptr(contigs), len(contigs), ptr(iv), len(iv),
+                                      _lib.REGION_INSIDE if rule == "inside" else _lib.REGION_OVERLAP, C.byref(self._h)))
+
+    def contains(self, contig, pos):
+        """Is the window that starts at (contig, pos) in the regions?  (vsc_regions_contains, on the host)"""
+        return bool(lib().vsc_regions_contains(self._h, int(contig), int(pos)))
+
+    def info(self):
+        """vsc_regions_info: intervals kept, rule, block_bases and the class table's blocks_out / blocks_in / blocks_mixed."""
+        st = _lib.RegionsStats()
+        check(lib().vsc_regions_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if self._h:
+            lib().vsc_regions_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PackedGenome:
     """The host-side packed planes of a genome (0.375 byte per base) plus its contig table.
 
@@ -286,35 +341,51 @@ class Genome:
         check(lib().vsc_search(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(h)), self.ctx._h)
         return Hits(self, h, codes)
 
-    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None):
+    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):
         """vsc_search_summary: per guide, the NM counts, the fixed-point MIT sum (units of 2^-24), the reference-UB count
         and whether the excluded locus was a hit - over the hits search() would return, without the records.
-        exclude: None or one (contig, pos, strand) per guide (contig 0xFFFFFFFF: none).  Returns SUMMARY_DTYPE rows."""
+        exclude: None or one (contig, pos, strand) per guide (contig 0xFFFFFFFF: none).  Returns SUMMARY_DTYPE rows - or,
+        with regions (a Regions; vsc_search_summary_regions), the pair (those rows, the same over the hits in the regions)."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = self._params(max_mismatches, extra_pam, algorithm)
         ex = _loci(exclude, len(codes))
         out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
-        check(lib().vsc_search_summary(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), ptr(out)), self.ctx._h)
-        return out
+        if regions is None:
+            check(lib().vsc_search_summary(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), ptr(out)), self.ctx._h)
+            return out
+        inside = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        check(lib().vsc_search_summary_regions(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), regions._h, ptr(out),
+                                               ptr(inside)), self.ctx._h)
+        return out, inside
 
     def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
-                      summary=False):
+                      summary=False, regions=None, region_scope="keep"):
         """vsc_search_select: per guide, of the hits search() would return (minus the excluded locus), those with
         rint(MIT * 2^24) >= min_score (mit_fixed() turns an MIT value into one) and of them the top_k best by (score
         descending, strand, position); 0 = no floor / no limit.  Returns Hits sorted as search() sorts them - or, with
-        summary=True, (Hits, the SUMMARY_DTYPE rows of summarize() for the same arguments) from the one search."""
+        summary=True, (Hits, the SUMMARY_DTYPE rows of summarize() for the same arguments) from the one search.
+        regions (a Regions; vsc_search_select_regions): the selection is made among the hits in the regions
+        (region_scope="keep") or among those outside (region_scope="drop"); with summary=True the result is then (Hits, rows,
+        rows over the hits in the regions), the two row sets of summarize(..., regions=regions) whatever the scope."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = self._params(max_mismatches, extra_pam, algorithm)
         sel = _select(top_k, min_score)
         ex = _loci(exclude, len(codes))
+        flt = _region_filter(regions, region_scope)
         rows = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
         h = C.c_void_p()
-        check(lib().vsc_search_select(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), ptr(ex), ptr(rows),
-                                      C.byref(h)), self.ctx._h)
+        if flt is None:
+            check(lib().vsc_search_select(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), ptr(ex), ptr(rows),
+                                          C.byref(h)), self.ctx._h)
+            hits = Hits(self, h, codes)
+            return (hits, rows) if summary else hits
+        inside = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
+        check(lib().vsc_search_select_regions(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), C.byref(flt),
+                                              ptr(ex), ptr(rows), ptr(inside), C.byref(h)), self.ctx._h)
         hits = Hits(self, h, codes)
-        return (hits, rows) if summary else hits
+        return (hits, rows, inside) if summary else hits
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)
@@ -597,32 +668,47 @@ class MultiGenome:
         self.multi._results.add(res)
         return res
 
-    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None):
-        """vsc_multi_search_summary: Genome.summarize over the shards, rows added on the host."""
+    def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):
+        """vsc_multi_search_summary: Genome.summarize over the shards, rows added on the host (with regions: both row sets,
+        vsc_multi_search_summary_regions)."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = Genome._params(max_mismatches, extra_pam, algorithm)
         ex = _loci(exclude, len(codes))
         out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
-        self.multi._check(lib().vsc_multi_search_summary(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
-                                                         ptr(out)))
-        return out
+        if regions is None:
+            self.multi._check(lib().vsc_multi_search_summary(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
+                                                             ptr(out)))
+            return out
+        inside = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        self.multi._check(lib().vsc_multi_search_summary_regions(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
+                                                                 regions._h, ptr(out), ptr(inside)))
+        return out, inside
 
     def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
-                      summary=False):
-        """vsc_multi_search_select: Genome.search_select over the shards; the merged records on the first context."""
+                      summary=False, regions=None, region_scope="keep"):
+        """vsc_multi_search_select: Genome.search_select over the shards; the merged records on the first context (with
+        regions: vsc_multi_search_select_regions, results as Genome.search_select returns them)."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = Genome._params(max_mismatches, extra_pam, algorithm)
         sel = _select(top_k, min_score)
         ex = _loci(exclude, len(codes))
+        flt = _region_filter(regions, region_scope)
         rows = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
+        inside = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary and flt is not None else None
         h = C.c_void_p()
-        self.multi._check(lib().vsc_multi_search_select(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel),
-                                                        ptr(ex), ptr(rows), C.byref(h)))
+        if flt is None:
+            self.multi._check(lib().vsc_multi_search_select(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel),
+                                                            ptr(ex), ptr(rows), C.byref(h)))
+        else:
+            self.multi._check(lib().vsc_multi_search_select_regions(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p),
+                                                                    C.byref(sel), C.byref(flt), ptr(ex), ptr(rows), ptr(inside), C.byref(h)))
         res = MergedHits(_BorrowedContext(C.c_void_p(lib().vsc_multi_result_ctx(self.multi._h))), h)
         self.multi._results.add(res)
-        return (res, rows) if summary else res
+        if not summary:
+            return res
+        return (res, rows) if flt is None else (res, rows, inside)
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

@@ -15,12 +15,21 @@
 // chrom = first word of the contig name, start / end 0-based half-open on the forward genome, mismatchPositions = 0-based
 // window positions on the forward genome (ascending, comma-separated, - if none), sequence = the window's forward-genome
 // bases.  The summary TSV is the same with and without these options.
+// With -A regions.bed (BED3+: chrom start end ..., chrom = first word of a contig name; an unknown chrom is an error) every
+// guide's hits are also summarised over those IN THE REGIONS (vsc_search_summary_regions) - a hit is in when its window shares a
+// base with an interval (-a overlap, the default) or lies fully inside one (-a inside) - and every line gains the columns
+//   regionMitSpecScore regionCount rmm0 .. rmm<M> regionMitHitSum
+// -X keep|drop (needs -A and -T) lists in the -T file only hits in the regions / only hits outside them: -K and -S then apply
+// to that side.  With -A and -T but no -X the genome is searched twice: the unfiltered listing (vsc_search_select_regions
+// takes region rows only beside a filter) and then the region rows (vsc_search_summary_regions); with -X one search gives
+// both.  Without -A the output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <fstream>
+#include <map>
 #include <sstream>
 
 #include "merge_host.hpp"
@@ -42,6 +51,10 @@ int main(int argc, char **argv)
         {'K', "top", "List the K best off-targets of every guide by MIT score in the -T file (default: no limit)", false},
         {'S', "min-score", "List only off-targets with an MIT score >= this value, 0 .. 100, in the -T file (default: no floor)", false},
         {'T', "hits", "Path to the TSV file of the listed off-targets (.tsv/.txt); required with -K / -S", false},
+        {'A', "regions", "Path to an annotation (.bed, BED3+): adds the summary columns over the hits in these regions", false},
+        {'a', "region-rule", "overlap (default): a hit is in the regions when its window shares a base with an interval; "
+                             "inside: when it lies fully inside one interval", false},
+        {'X', "region-scope", "keep | drop: list in the -T file only hits in the regions / outside them (needs -A and -T)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -99,6 +112,36 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: the -T file must be a .tsv/.txt file\n", argv[0]);
         return 1;
     }
+    const bool annotated = opts[11].set;
+    const std::string regions_path = opts[11].value;
+    uint32_t region_rule = VSC_REGION_OVERLAP;
+    vsc_region_filter filter{};
+    if (annotated && !has_extension(regions_path, {"bed"})) {
+        std::fprintf(stderr, "%s: the -A annotation must be a .bed file\n", argv[0]);
+        return 1;
+    }
+    if (opts[12].set) {
+        if (opts[12].value != "overlap" && opts[12].value != "inside") {
+            std::fprintf(stderr, "%s: -a takes overlap or inside, not '%s'\n", argv[0], opts[12].value.c_str());
+            return 1;
+        }
+        region_rule = opts[12].value == "inside" ? VSC_REGION_INSIDE : VSC_REGION_OVERLAP;
+    }
+    if (opts[13].set) {
+        if (opts[13].value != "keep" && opts[13].value != "drop") {
+            std::fprintf(stderr, "%s: -X takes keep or drop, not '%s'\n", argv[0], opts[13].value.c_str());
+            return 1;
+        }
+        if (!annotated || !listing) {
+            std::fprintf(stderr, "%s: -X restricts the -T listing to one side of the -A regions: give both\n", argv[0]);
+            return 1;
+        }
+        filter.scope = opts[13].value == "drop" ? VSC_REGION_DROP : VSC_REGION_KEEP;
+    }
+    if (opts[12].set && !annotated) {
+        std::fprintf(stderr, "%s: -a chooses the rule of the -A regions: give -A\n", argv[0]);
+        return 1;
+    }
     std::vector<int> devices;  // -D 0 | -D 0,1,2,3 (an id may repeat: several shards on one device)
     {
         const std::string d = opts[7].set ? opts[7].value : "0";
@@ -123,6 +166,7 @@ int main(int argc, char **argv)
     vsc_multi *multi = nullptr;
     vsc_multi_genome *mgenome = nullptr;
     vsc_hits *hits = nullptr;
+    vsc_regions *regions = nullptr;
     int rc = 1;
     try {
         const PackedIndex ix = read_index(index_prefix);
@@ -164,6 +208,29 @@ int main(int argc, char **argv)
             codes[i] = vsc_pack_guide(seqs[i].c_str());
         }
         std::fprintf(stderr, "Guides loaded (total: %zu).\n", seqs.size());
+        if (annotated) {
+            std::map<std::string, uint32_t> by_chrom;  // first word of the contig name, as the -T file prints it
+            for (size_t c = ix.names.size(); c-- > 0;) by_chrom[ix.names[c].substr(0, ix.names[c].find_first_of(" \t"))] = (uint32_t)c;
+            std::ifstream bed(regions_path);
+            if (!bed) throw std::runtime_error("Could not open the -A file.");
+            std::vector<vsc_interval> iv;
+            std::string line;
+            while (std::getline(bed, line)) {
+                if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+                std::istringstream is(line);
+                std::string chr;
+                unsigned long long start = 0, stop = 0;
+                if (!(is >> chr >> start >> stop)) throw std::runtime_error("-A: not a BED line: '" + line + "'");
+                auto it = by_chrom.find(chr);
+                if (it == by_chrom.end()) throw std::runtime_error("-A: no sequence '" + chr + "' in the genome");
+                if (start > stop || stop > 0xFFFFFFFFull) throw std::runtime_error("-A: bad interval in '" + line + "'");
+                iv.push_back(vsc_interval{it->second, (uint32_t)start, (uint32_t)stop, 0u});
+            }
+            if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), region_rule, &regions) != VSC_OK)
+                throw std::runtime_error("could not build the regions of the -A file");
+            filter.regions = regions;
+            std::fprintf(stderr, "Regions loaded (total: %zu).\n", iv.size());
+        }
         int st;
         if (devices.size() == 1) {
             st = vsc_ctx_create(devices[0], &ctx);
@@ -190,9 +257,23 @@ int main(int argc, char **argv)
             p.extra_pam[0] = pam[0];
             p.extra_pam[1] = pam[1];
         }
-        std::vector<vsc_guide_summary> sum(codes.size());
+        std::vector<vsc_guide_summary> sum(codes.size()), sum_in(annotated ? codes.size() : 0);
         const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
-        if (listing && multi) {
+        const uint32_t n_codes = (uint32_t)codes.size();
+        if (annotated && listing) {  // without -X the listing is not filtered: the rows then come from a second search, a summary call
+            const vsc_region_filter *flt = opts[13].set ? &filter : nullptr;
+            vsc_guide_summary *rows_in = flt ? sum_in.data() : nullptr;
+            st = multi ? vsc_multi_search_select_regions(multi, mgenome, codes.data(), n_codes, &p, &sel, flt, ex, sum.data(), rows_in, &hits)
+                       : vsc_search_select_regions(ctx, genome, codes.data(), n_codes, &p, &sel, flt, ex, sum.data(), rows_in, &hits);
+            if (st == VSC_OK && !flt)
+                st = multi ? vsc_multi_search_summary_regions(multi, mgenome, codes.data(), n_codes, &p, ex, regions, sum.data(), sum_in.data())
+                           : vsc_search_summary_regions(ctx, genome, codes.data(), n_codes, &p, ex, regions, sum.data(), sum_in.data());
+            if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+        } else if (annotated) {
+            st = multi ? vsc_multi_search_summary_regions(multi, mgenome, codes.data(), n_codes, &p, ex, regions, sum.data(), sum_in.data())
+                       : vsc_search_summary_regions(ctx, genome, codes.data(), n_codes, &p, ex, regions, sum.data(), sum_in.data());
+            if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+        } else if (listing && multi) {
             st = vsc_multi_search_select(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, &sel, ex, sum.data(), &hits);
             if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
         } else if (listing) {
@@ -208,7 +289,13 @@ int main(int argc, char **argv)
 
         std::string text = "#guideId\tguideSeq\tmitSpecScore\tofftargetCount\tonTargetFound";
         for (long k = 0; k <= mm; ++k) text += "\tmm" + std::to_string(k);
-        text += "\tmitHitSum\n";
+        text += "\tmitHitSum";
+        if (annotated) {
+            text += "\tregionMitSpecScore\tregionCount";
+            for (long k = 0; k <= mm; ++k) text += "\trmm" + std::to_string(k);
+            text += "\tregionMitHitSum";
+        }
+        text += '\n';
         char buf[64];
         for (size_t i = 0; i < sum.size(); ++i) {
             const vsc_guide_summary &s = sum[i];
@@ -219,7 +306,18 @@ int main(int argc, char **argv)
             text += std::string(buf) + '\t' + std::to_string(total) + '\t' + std::to_string(s.on_target);
             for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(s.nm[k]);
             std::snprintf(buf, sizeof buf, "%.6f", (double)s.mit_sum * 0x1p-24);
-            text += '\t' + std::string(buf) + '\n';
+            text += '\t' + std::string(buf);
+            if (annotated) {
+                const vsc_guide_summary &r = sum_in[i];
+                uint64_t inside = 0;
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) inside += r.nm[k];
+                std::snprintf(buf, sizeof buf, "%.0f", std::floor(vsc_mit_specificity(r.mit_sum) + 0.5));
+                text += '\t' + std::string(buf) + '\t' + std::to_string(inside);
+                for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(r.nm[k]);
+                std::snprintf(buf, sizeof buf, "%.6f", (double)r.mit_sum * 0x1p-24);
+                text += '\t' + std::string(buf);
+            }
+            text += '\n';
         }
         if (opts[5].set) {
             std::ofstream out(out_path);
@@ -282,6 +380,7 @@ int main(int argc, char **argv)
         rc = 1;
     }
     if (hits) vsc_hits_free(hits);
+    vsc_regions_free(regions);
     if (multi) {
         vsc_multi_genome_free(mgenome);
         vsc_multi_destroy(multi);

@@ -211,8 +211,9 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
-                         &ctx->sel_masks})
+                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf})
         b->release();
+    ctx->regions_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
     ctx->forest.nodes.release();
@@ -304,6 +305,8 @@ int vsc_genome_load(vsc_ctx *ctx, const uint32_t *hi, const uint32_t *lo, const 
     g->dev_words = dev_words;
     g->n_tiles = (uint32_t)n_tiles;
     g->n_contigs = n_contigs;
+    g->h_contig_off = off;
+    g->h_contig_end = end;
     const size_t pb = dev_words * sizeof(uint32_t), cb = (size_t)n_contigs * sizeof(uint32_t);
     hipError_t e = hipSuccess;
     auto step = [&](hipError_t r) {
@@ -351,6 +354,8 @@ int vsc::genome_table_only(vsc_ctx *ctx, const vsc_contig *contigs, uint32_t n_c
     if (!g) return fail(ctx, VSC_ERR_NOMEM, "out of host memory");
     g->ctx = ctx;
     g->n_contigs = n_contigs;
+    g->h_contig_off = off;
+    g->h_contig_end = end;
     const size_t cb = (size_t)n_contigs * sizeof(uint32_t);
     hipError_t e = hipMalloc((void **)&g->d_contig_off, cb);
     if (e == hipSuccess) e = hipMalloc((void **)&g->d_contig_end, cb);
@@ -1646,7 +1651,8 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
 // Summary sink (vsc_search_summary): summary_kernel adds the records where they lie into the pass's rows of ctx->sum_rows,
 // minus its loci in ctx->sum_excl if `excluded`.  No sort, no result buffer: finalize_ms times that kernel, sort_ms stays 0.
 // last = false (vsc_search_select with a summary): another sink follows and ends the pass; the kernel has run on return.
-int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, bool last = true)
+// reg: the device copy of the regions (resident_regions) - the rows over the hits inside go to ctx->sum_rows_in as well.
+int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, bool last = true, const RegionsView *reg = nullptr)
 {
     std::vector<SumSeg> ss;
     std::vector<uint32_t> tile0(1, 0);
@@ -1654,7 +1660,7 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
         ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
         tile0.push_back(tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
     }
-    SummaryArgs a{};
+    SummaryRegionArgs a{};
     if (!ss.empty()) {
         const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
         VSC_HIP(ctx, ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
@@ -1671,9 +1677,13 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
         a.pos_base = f.pos_base;
         a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
         a.out = (unsigned long long *)ctx->sum_rows.p + (size_t)f.guide_base * kSumWords;
+        if (reg) {
+            a.reg = *reg;
+            a.out_in = (unsigned long long *)ctx->sum_rows_in.p + (size_t)f.guide_base * kSumWords;
+        }
     }
     VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    VSC_HIP(ctx, launch_summary(a, ctx->stream));
+    VSC_HIP(ctx, reg ? launch_summary_regions(a, ctx->stream) : launch_summary(a, ctx->stream));
     if (last) VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
     else VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the uploads above read this call's vectors)
     return VSC_OK;
@@ -1686,7 +1696,9 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
 // bin sort, the result buffer and everything downstream see survivors only.  Beyond the search's own buffers: 4 bytes per
 // placed record (ctx->vals_b: the scores), 512 bytes per read of the pass (histograms) and 12 bytes per candidate.  One read-back
 // (the reads' candidate counts), as find_pass has one for its counters.
-int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &sel, bool excluded)
+// reg / drop: the selection is made among the records on one side of the regions (SelectRegionArgs).
+int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &sel, bool excluded, const RegionsView *reg = nullptr,
+                uint32_t drop = 0)
 {
     f.selected = true;
     if (f.n == 0) return VSC_OK;
@@ -1706,7 +1718,11 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     VSC_HIP(ctx, ctx->sel_tabs.ensure(4 * words * sizeof(uint32_t) + 2 * words * sizeof(uint64_t)));
     VSC_HIP(ctx, ctx->sel_hist.ensure((size_t)n_reads * kSelBins * sizeof(uint32_t)));
     VSC_HIP(ctx, ctx->vals_b.ensure((size_t)tile0.back() * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
-    SelectArgs a{};
+    SelectRegionArgs a{};
+    if (reg) {
+        a.reg = *reg;
+        a.drop = drop;
+    }
     a.recs = (const uint64_t *)ctx->keys_a.p;
     a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
     a.segs = (const SumSeg *)ctx->sort_segs.p;
@@ -1733,7 +1749,7 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     VSC_HIP(ctx, hipMemsetAsync(a.hist, 0, (size_t)n_reads * kSelBins * sizeof(uint32_t), st));
     VSC_HIP(ctx, hipMemsetAsync(a.cursor, 0, words * sizeof(uint32_t), st));
     VSC_HIP(ctx, hipMemsetAsync(a.thr_region, 0xFF, words * sizeof(uint32_t), st));
-    VSC_HIP(ctx, launch_select_score(a, st));
+    VSC_HIP(ctx, reg ? launch_select_score_regions(a, st) : launch_select_score(a, st));
     VSC_HIP(ctx, launch_select_threshold(a, st));
     std::vector<uint32_t> count(n_reads);
     VSC_HIP(ctx, hipMemcpyAsync(count.data(), a.count, (size_t)n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1793,18 +1809,52 @@ int excluded_loci(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *exclu
 }
 
 // the zeroed rows (if wanted) and the excluded loci of a call on the device
-int upload_summary_state(vsc_ctx *ctx, uint32_t n_guides, bool rows, const std::vector<uint64_t> &excl)
+int upload_summary_state(vsc_ctx *ctx, uint32_t n_guides, bool rows, const std::vector<uint64_t> &excl, bool rows_in = false)
 {
     if (!n_guides) return VSC_OK;
     if (rows) {
         const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
         VSC_HIP(ctx, ctx->sum_rows.ensure(row_bytes));
         VSC_HIP(ctx, hipMemsetAsync(ctx->sum_rows.p, 0, row_bytes, ctx->stream));
+        if (rows_in) {
+            VSC_HIP(ctx, ctx->sum_rows_in.ensure(row_bytes));
+            VSC_HIP(ctx, hipMemsetAsync(ctx->sum_rows_in.p, 0, row_bytes, ctx->stream));
+        }
     }
     if (!excl.empty()) {
         VSC_HIP(ctx, ctx->sum_excl.ensure(excl.size() * sizeof(uint64_t)));
         VSC_HIP(ctx, hipMemcpyAsync(ctx->sum_excl.p, excl.data(), excl.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     }
+    return VSC_OK;
+}
+
+// The device copy of `regions` on this context (`who`: the caller, for error texts): the context keeps the copy of the regions
+// it used last, keyed by their serial number; another set is uploaded over it on the context's stream.  The regions must
+// have been built for the genome's contig table.
+int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const char *who, RegionsView &dev)
+{
+    bool same = regions->contig_off.size() == genome->n_contigs;
+    for (uint32_t c = 0; same && c < genome->n_contigs; ++c)  // (the genome's host copy of its table: no device read per call)
+        same = genome->h_contig_off[c] == regions->contig_off[c] && genome->h_contig_end[c] - genome->h_contig_off[c] == regions->contig_len[c];
+    if (!same) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": the regions were built for another contig table").c_str());
+    const size_t n = regions->start.size(), cls_at = (2 * n * sizeof(uint32_t) + 255) / 256 * 256;
+    if (ctx->regions_serial != regions->serial) {
+        ctx->regions_serial = 0;
+        VSC_HIP(ctx, ctx->regions_buf.ensure(cls_at + regions->cls.size() * sizeof(uint32_t)));
+        char *p = (char *)ctx->regions_buf.p;
+        if (n) {
+            VSC_HIP(ctx, hipMemcpyAsync(p, regions->start.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(p + n * sizeof(uint32_t), regions->end_max.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+        VSC_HIP(ctx, hipMemcpyAsync(p + cls_at, regions->cls.data(), regions->cls.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the regions as soon as its call returns)
+        ctx->regions_serial = regions->serial;
+    }
+    const char *p = (const char *)ctx->regions_buf.p;
+    dev = regions->view();
+    dev.start = (const uint32_t *)p;
+    dev.end_max = (const uint32_t *)p + n;
+    dev.cls = (const uint32_t *)(p + cls_at);
     return VSC_OK;
 }
 
@@ -1883,6 +1933,109 @@ int stream_batches(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guide
     });
 }
 
+// vsc_search_summary (regions == null) and vsc_search_summary_regions (`who`)
+int search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                   const vsc_locus *exclude, const vsc_regions *regions, vsc_guide_summary *out, vsc_guide_summary *out_in, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
+    vsc_timing t{};
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
+    if (rc != VSC_OK) return rc;
+    std::vector<uint64_t> excl;
+    const int erc = excluded_loci(ctx, genome, exclude, n_guides, who, excl);
+    if (erc != VSC_OK) return erc;
+    RegionsView reg{};
+    if (regions) {
+        const int rrc = resident_regions(ctx, genome, regions, who, reg);
+        if (rrc != VSC_OK) return rrc;
+    }
+    const int urc = upload_summary_state(ctx, n_guides, true, excl, regions != nullptr);
+    if (urc != VSC_OK) return urc;
+    // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
+    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
+        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
+        if (prc == VSC_OK) prc = summarize_pass(ctx, f, !excl.empty(), t, true, regions ? &reg : nullptr);
+        if (prc != VSC_OK) return prc;
+    }
+    if (n_guides) {
+        VSC_HIP(ctx, hipMemcpyAsync(out, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
+        if (regions)
+            VSC_HIP(ctx, hipMemcpyAsync(out_in, ctx->sum_rows_in.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+// vsc_search_select (filter == null) and vsc_search_select_regions (`who`; the filter's fields have been checked)
+int search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                  const vsc_select *select, const vsc_region_filter *filter, const vsc_locus *exclude, vsc_guide_summary *summary,
+                  vsc_guide_summary *summary_in, vsc_hits **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    vsc_timing t{};
+    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
+    if (rc != VSC_OK) return rc;
+    if (!select) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
+    if (select->reserved[0] || select->reserved[1]) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": reserved fields must be 0").c_str());
+    std::vector<uint64_t> excl;
+    const int erc = excluded_loci(ctx, genome, exclude, n_guides, who, excl);
+    if (erc != VSC_OK) return erc;
+    RegionsView reg{};
+    if (filter) {
+        const int rrc = resident_regions(ctx, genome, filter->regions, who, reg);
+        if (rrc != VSC_OK) return rrc;
+    }
+    // the summary kernel writes both sets of rows or the plain one: summary_in alone takes the plain rows along
+    const bool rows = summary != nullptr || summary_in != nullptr;
+    const int urc = upload_summary_state(ctx, n_guides, rows, excl, summary_in != nullptr);
+    if (urc != VSC_OK) return urc;
+    // nothing to decide: the records go to the sort as vsc_search hands them over
+    const bool selecting = select->top_k || select->min_score || !excl.empty() || filter;
+    vsc_hits *hits = new (std::nothrow) vsc_hits();
+    if (!hits) return fail(ctx, VSC_ERR_NOMEM, (std::string(who) + ": out of host memory").c_str());
+    hits->ctx = ctx;
+    uint64_t used = 0;
+    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
+        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
+        const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
+        PassFound f;
+        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
+        if (prc == VSC_OK && rows) prc = summarize_pass(ctx, f, !excl.empty(), t, false, summary_in ? &reg : nullptr);
+        if (prc == VSC_OK && selecting) prc = select_pass(ctx, f, count, *select, !excl.empty(), filter ? &reg : nullptr, filter ? filter->scope : 0u);
+        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
+        if (prc != VSC_OK) {
+            vsc_hits_free(hits);
+            return prc;
+        }
+        used += f.n;
+    }
+    if (rows && n_guides) {
+        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+        hipError_t e = hipSuccess;
+        if (summary) e = hipMemcpyAsync(summary, ctx->sum_rows.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && summary_in) e = hipMemcpyAsync(summary_in, ctx->sum_rows_in.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            vsc_hits_free(hits);
+            VSC_HIP(ctx, e);
+        }
+    }
+    hits->n = used;
+    if (used == 0) hits->host_valid = true;
+    ctx->timing = t;
+    *out = hits;
+    return VSC_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1925,85 +2078,37 @@ int vsc_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
 int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                        const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
 {
-    return guarded(ctx, [&]() -> int {
+    return search_summary(ctx, genome, guides, n_guides, params, exclude, nullptr, out, nullptr, "vsc_search_summary");
+}
+
+int vsc_search_summary_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                               const vsc_search_params *params, const vsc_locus *exclude, const vsc_regions *regions,
+                               vsc_guide_summary *out_all, vsc_guide_summary *out_in)
+{
     if (!ctx) return VSC_ERR_INVALID;
-    if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary: null argument");
-    vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_summary", &t);
-    if (rc != VSC_OK) return rc;
-    std::vector<uint64_t> excl;
-    const int erc = excluded_loci(ctx, genome, exclude, n_guides, "vsc_search_summary", excl);
-    if (erc != VSC_OK) return erc;
-    const int urc = upload_summary_state(ctx, n_guides, true, excl);
-    if (urc != VSC_OK) return urc;
-    // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
-    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
-        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
-        if (prc == VSC_OK) prc = summarize_pass(ctx, f, !excl.empty(), t);
-        if (prc != VSC_OK) return prc;
-    }
-    if (n_guides) {
-        VSC_HIP(ctx, hipMemcpyAsync(out, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->timing = t;
-    return VSC_OK;
-    });
+    if (!regions || (n_guides && !out_in)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary_regions: null argument");
+    return search_summary(ctx, genome, guides, n_guides, params, exclude, regions, out_all, out_in, "vsc_search_summary_regions");
 }
 
 int vsc_search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                       const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
                       vsc_guide_summary *summary, vsc_hits **out)
 {
-    return guarded(ctx, [&]() -> int {
+    return search_select(ctx, genome, guides, n_guides, params, select, nullptr, exclude, summary, nullptr, out, "vsc_search_select");
+}
+
+int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                              const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
+                              const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
+                              vsc_hits **out)
+{
     if (!ctx || !out) return VSC_ERR_INVALID;
     *out = nullptr;
-    vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search_select", &t);
-    if (rc != VSC_OK) return rc;
-    if (!select) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select: null argument");
-    if (select->reserved[0] || select->reserved[1]) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select: reserved fields must be 0");
-    std::vector<uint64_t> excl;
-    const int erc = excluded_loci(ctx, genome, exclude, n_guides, "vsc_search_select", excl);
-    if (erc != VSC_OK) return erc;
-    const int urc = upload_summary_state(ctx, n_guides, summary != nullptr, excl);
-    if (urc != VSC_OK) return urc;
-    // nothing to decide: the records go to the sort as vsc_search hands them over
-    const bool selecting = select->top_k || select->min_score || !excl.empty();
-    vsc_hits *hits = new (std::nothrow) vsc_hits();
-    if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_select: out of host memory");
-    hits->ctx = ctx;
-    uint64_t used = 0;
-    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
-        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
-        PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
-        if (prc == VSC_OK && summary) prc = summarize_pass(ctx, f, !excl.empty(), t, false);
-        if (prc == VSC_OK && selecting) prc = select_pass(ctx, f, count, *select, !excl.empty());
-        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
-        if (prc != VSC_OK) {
-            vsc_hits_free(hits);
-            return prc;
-        }
-        used += f.n;
-    }
-    if (summary && n_guides) {
-        hipError_t e = hipMemcpyAsync(summary, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            vsc_hits_free(hits);
-            VSC_HIP(ctx, e);
-        }
-    }
-    hits->n = used;
-    if (used == 0) hits->host_valid = true;
-    ctx->timing = t;
-    *out = hits;
-    return VSC_OK;
-    });
+    if (filter && (!filter->regions || filter->scope > VSC_REGION_DROP || filter->reserved))
+        return fail(ctx, VSC_ERR_INVALID, "vsc_search_select_regions: a filter needs regions, a scope of 0 or 1 and a reserved field of 0");
+    if (!filter && summary_in) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select_regions: summary_in without a filter");
+    return search_select(ctx, genome, guides, n_guides, params, select, filter, exclude, summary_all, summary_in, out,
+                         "vsc_search_select_regions");
 }
 
 double vsc_mit_specificity(uint64_t mit_sum)

@@ -382,10 +382,71 @@ struct SelectArgs {
     uint64_t *out;              // survivors as packed records (layout above), reads in order, unsorted inside a read
 };
 
+// ---- regions (vsc_regions; vsc_regions.cpp builds them, the two sinks above test their records against them) ---------------
+// The intervals in global coordinates, sorted by start: start[] and end_max[] = the running maximum of their ends (no
+// interval reaches across a contig boundary, so the maximum over earlier contigs stays below every later position), and
+// two bits per block of 2^block_shift window starts: kRegOut - no start of the block is in the regions, kRegIn - every one
+// is, kRegMixed - one binary search over start[] answers either rule (18 dependent loads for 250 000 intervals).
+// The same arrays on the host (vsc_regions) and on the device (the context's copy).
+constexpr uint32_t kRegOut = 0, kRegIn = 1, kRegMixed = 2;
+constexpr uint32_t kRegMinBlockShift = 5;    // blocks of at least 32 starts ...
+constexpr uint32_t kRegMaxBlocks = 1u << 23; // ... and as small as keeps the table within 2 MB (2 bits per block): 512 at 3 Gbp
+
+struct RegionsView {
+    const uint32_t *start;    // [n] ascending
+    const uint32_t *end_max;  // [n]
+    const uint32_t *cls;      // 16 blocks per word, block b in bits 2 (b & 15) .. of word b >> 4
+    uint32_t n;
+    uint32_t n_blocks;        // blocks the table covers (the genome's positions); a start beyond them is out
+    uint32_t block_shift;
+    uint32_t rule;            // VSC_REGION_OVERLAP / VSC_REGION_INSIDE
+};
+
+// The interval search, for the window of `len` bases that starts at global position pos (len < VSC_READ_LEN: a window cut off
+// by its contig's end - the host's vsc_regions_contains only; it overlaps with what is left of it and lies inside nothing).
+//   OVERLAP  n = #{start < pos + len}: in iff n > 0 and end_max[n - 1] > pos
+//   INSIDE   n = #{start <= pos}:      in iff n > 0 and end_max[n - 1] >= pos + VSC_READ_LEN
+__host__ __device__ inline bool regions_search(const RegionsView &v, uint32_t pos, uint32_t len)
+{
+    const bool inside = v.rule == VSC_REGION_INSIDE;
+    const uint32_t bound = inside ? pos + 1u : pos + len;
+    uint32_t lo = 0, hi = v.n;  // -> #{start < bound}
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (v.start[mid] < bound) lo = mid + 1; else hi = mid;
+    }
+    if (lo == 0) return false;
+    const uint32_t e = v.end_max[lo - 1];
+    return inside ? e >= pos + (uint32_t)VSC_READ_LEN : e > pos;
+}
+
+// Is the window that starts at global position pos in the regions?  One read of the class table, the search for mixed blocks.
+__host__ __device__ inline bool regions_contains(const RegionsView &v, uint32_t pos, uint32_t len = VSC_READ_LEN)
+{
+    if (len != (uint32_t)VSC_READ_LEN) return len != 0 && regions_search(v, pos, len);  // (the table describes whole windows)
+    const uint32_t b = pos >> v.block_shift;
+    if (b >= v.n_blocks) return false;
+    const uint32_t c = (v.cls[b >> 4] >> (2u * (b & 15u))) & 3u;
+    return c == kRegMixed ? regions_search(v, pos, len) : c == kRegIn;
+}
+
+// the sinks' arguments with regions: the plain kernels keep the plain structs (and compile to what they were)
+struct SummaryRegionArgs : SummaryArgs {
+    RegionsView reg;
+    unsigned long long *out_in;  // the rows over the hits in the regions, laid out and zeroed as `out`
+};
+
+struct SelectRegionArgs : SelectArgs {
+    RegionsView reg;
+    uint32_t drop;               // 0: records outside the regions are dropped (VSC_REGION_KEEP), 1: those inside
+};
+
 // Launch wrappers implemented in vsc_kernels.hip.  They only enqueue work on `stream`.
 hipError_t launch_scan(const ScanArgs &args, int n_groups, bool extract, hipStream_t stream);
 hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream);
+hipError_t launch_summary_regions(const SummaryRegionArgs &args, hipStream_t stream);
 hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream);      // round 1: scores + histograms
+hipError_t launch_select_score_regions(const SelectRegionArgs &args, hipStream_t stream);  // ... on one side of the regions only
 hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream);  // histograms -> thr, count
 hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream);    // round 2: candidates into their reads' lists
 hipError_t launch_select_resolve(const SelectArgs &args, hipStream_t stream);    // later rounds + cut: survivors as packed records

@@ -15,6 +15,7 @@
 #include "vsc_device.h"
 
 #include <cstring>
+#include <type_traits>
 
 
 namespace vsc {
@@ -848,18 +849,22 @@ hipError_t launch_score(const ScoreArgs &args, hipStream_t stream)
 // of the tile: into the region's LDS table (SEED: a workgroup's tiles lie in one region at a time, 64 reads), or
 // straight into the result (SCAN: the pairs of all reads of the pass arrive mixed).  The LDS table goes out with one
 // agent-scope atomic per nonzero (read, field).
-template <bool kSeed>
-__global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs a)
+// kRegions (vsc_search_summary_regions): every counted record is also tested against the regions (regions_contains: one read
+// of the L2-resident class table, an interval search for mixed blocks) and those inside go into a second accumulator set, a
+// second half of the LDS table and the second result array a.out_in in the same way.
+template <bool kSeed, bool kRegions>
+__global__ __launch_bounds__(kSumThreads) void summary_kernel(const std::conditional_t<kRegions, SummaryRegionArgs, SummaryArgs> a)
 {
+    constexpr uint32_t kTabReads = kRegions ? 2 * kRegionReads : kRegionReads;  // LDS rows: the region's reads (+ the same again, inside)
     constexpr int kStride = kSumItems + 1;  // a lane's records in LDS, padded against bank conflicts
     __shared__ uint64_t s_rec[kWavesPerGroup][kWave * kStride];
     __shared__ uint32_t s_val[kSeed ? 1 : kWavesPerGroup][kSeed ? 1 : kWave * kStride];
-    __shared__ unsigned long long s_mit[kSeed ? kRegionReads : 1];
-    __shared__ uint32_t s_cnt[kSeed ? kRegionReads * kSumCounts : 1];
+    __shared__ unsigned long long s_mit[kSeed ? kTabReads : 1];
+    __shared__ uint32_t s_cnt[kSeed ? kTabReads * kSumCounts : 1];
     const uint32_t t = threadIdx.x, lane = t % kWave, wave = t / kWave;
     if (kSeed) {
-        for (uint32_t i = t; i < (uint32_t)kRegionReads * kSumCounts; i += kSumThreads) s_cnt[i] = 0;
-        for (uint32_t i = t; i < (uint32_t)kRegionReads; i += kSumThreads) s_mit[i] = 0;
+        for (uint32_t i = t; i < kTabReads * kSumCounts; i += kSumThreads) s_cnt[i] = 0;
+        for (uint32_t i = t; i < kTabReads; i += kSumThreads) s_mit[i] = 0;
         block_sync();
     }
     const uint32_t tile_begin = blockIdx.x * kSumTilesPerBlock, tile_end = min(tile_begin + (uint32_t)kSumTilesPerBlock, a.n_tiles);
@@ -875,7 +880,7 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs 
     // the region's LDS table -> the result rows of its reads
     auto flush_table = [&](const SumSeg &sg) {
         block_sync();
-        for (uint32_t i = t; i < (uint32_t)kRegionReads * kSumWords; i += kSumThreads) {
+        for (uint32_t i = t; i < kTabReads * kSumWords; i += kSumThreads) {
             const uint32_t r = i / kSumWords, f = i % kSumWords;
             unsigned long long v;
             if (f == 0) {
@@ -885,7 +890,11 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs 
                 v = s_cnt[r * kSumCounts + f - 1];
                 s_cnt[r * kSumCounts + f - 1] = 0;
             }
-            if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
+            if constexpr (kRegions) {
+                if (v) atomicAdd(&(r < (uint32_t)kRegionReads ? a.out : a.out_in)[(size_t)(sg.first_read + (r & (kRegionReads - 1))) * kSumWords + f], v);
+            } else {
+                if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
+            }
         }
         block_sync();
     };
@@ -916,28 +925,40 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs 
         uint64_t cur_ex = ~0ull, cnt = 0;
         unsigned long long mit = 0;
         uint32_t ub = 0, on = 0;
-        auto flush = [&]() {
-            if (cur == ~0u) return;
+        uint64_t cnt_in = 0;  // (kRegions) the same over the records in the regions
+        unsigned long long mit_in = 0;
+        uint32_t ub_in = 0;
+        // one accumulator set into one LDS row (SEED) / one result row (SCAN)
+        auto flush_row = [&](uint32_t row, unsigned long long *o, unsigned long long m, uint64_t c9, uint32_t u) {
             if (kSeed) {
-                const uint32_t r = cur - sg.first_read;
-                if (mit) atomicAdd(&s_mit[r], mit);
+                if (m) atomicAdd(&s_mit[row], m);
 #pragma unroll
                 for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(cnt >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
-                    if (c) atomicAdd(&s_cnt[r * kSumCounts + k], c);
+                    const uint32_t c = (uint32_t)(c9 >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    if (c) atomicAdd(&s_cnt[row * kSumCounts + k], c);
                 }
-                if (ub) atomicAdd(&s_cnt[r * kSumCounts + 9], ub);
-                if (on) atomicAdd(&s_cnt[r * kSumCounts + 10], on);
+                if (u) atomicAdd(&s_cnt[row * kSumCounts + 9], u);
+                if (on) atomicAdd(&s_cnt[row * kSumCounts + 10], on);
             } else {
-                unsigned long long *o = a.out + (size_t)cur * kSumWords;
-                if (mit) atomicAdd(&o[0], mit);
+                if (m) atomicAdd(&o[0], m);
 #pragma unroll
                 for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(cnt >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    const uint32_t c = (uint32_t)(c9 >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
                     if (c) atomicAdd(&o[1 + k], (unsigned long long)c);
                 }
-                if (ub) atomicAdd(&o[10], (unsigned long long)ub);
+                if (u) atomicAdd(&o[10], (unsigned long long)u);
                 if (on) atomicAdd(&o[11], (unsigned long long)on);
+            }
+        };
+        auto flush = [&]() {
+            if (cur == ~0u) return;
+            const uint32_t r = kSeed ? cur - sg.first_read : 0u;
+            flush_row(r, a.out + (size_t)cur * kSumWords, mit, cnt, ub);
+            if constexpr (kRegions) {
+                flush_row(kRegionReads + r, a.out_in + (size_t)cur * kSumWords, mit_in, cnt_in, ub_in);
+                cnt_in = 0;
+                mit_in = 0;
+                ub_in = 0;
             }
             cnt = 0;
             mit = 0;
@@ -973,6 +994,13 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const SummaryArgs 
             mit += (uint32_t)__builtin_rint(s * 0x1p24);  // <= 100 * 2^24 < 2^32; exact: a power-of-two scale
             ub += (uint32_t)f;
             cnt += 1ull << (kSumCountBits * __popc(mask));
+            if constexpr (kRegions) {
+                if (regions_contains(a.reg, pos)) {
+                    mit_in += (uint32_t)__builtin_rint(s * 0x1p24);
+                    ub_in += (uint32_t)f;
+                    cnt_in += 1ull << (kSumCountBits * __popc(mask));
+                }
+            }
         }
         flush();
     }
@@ -984,9 +1012,20 @@ hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream)
     if (args.n_tiles == 0) return hipSuccess;
     const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
     if (args.vals)
-        hipLaunchKernelGGL(summary_kernel<false>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
+        hipLaunchKernelGGL((summary_kernel<false, false>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
     else
-        hipLaunchKernelGGL(summary_kernel<true>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
+        hipLaunchKernelGGL((summary_kernel<true, false>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_summary_regions(const SummaryRegionArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
+    if (args.vals)
+        hipLaunchKernelGGL((summary_kernel<false, true>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL((summary_kernel<true, true>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
     return hipGetLastError();
 }
 
@@ -1039,8 +1078,13 @@ __device__ __forceinline__ uint32_t select_find_seg(const SelectArgs &a, uint32_
 // workgroup's tiles lie in one region at a time, whose 64 reads x 128 bins are an LDS table (32 KB, five workgroups per CU)
 // that goes out with one agent-scope atomic per nonzero cell; SCAN: the pairs of all reads arrive mixed, global atomics.
 // Neighbouring records belong to one read but to different bins, so the LDS atomics of a wave spread over a row of the table.
-template <bool kSeed>
-__global__ __launch_bounds__(kSelThreads) void select_score_kernel(const SelectArgs a)
+// is the window at global position pos on the side of the regions the selection is made among?  (plain arguments: always)
+__device__ __forceinline__ bool select_side(const SelectArgs &, uint32_t) { return true; }
+__device__ __forceinline__ bool select_side(const SelectRegionArgs &a, uint32_t pos) { return regions_contains(a.reg, pos) != (a.drop != 0); }
+
+// kFilter (vsc_search_select_regions): a record on the wrong side of the regions is dropped like the excluded locus.
+template <bool kSeed, bool kFilter>
+__global__ __launch_bounds__(kSelThreads) void select_score_kernel(const std::conditional_t<kFilter, SelectRegionArgs, SelectArgs> a)
 {
     __shared__ uint32_t s_hist[kSeed ? kRegionReads * kSelBins : 1];
     const uint32_t t = threadIdx.x;
@@ -1075,7 +1119,8 @@ __global__ __launch_bounds__(kSelThreads) void select_score_kernel(const SelectA
             const uint64_t at = sg.in_off + i;
             uint32_t read, mask, score = kSelDropped;
             uint64_t locus;
-            if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus)) {
+            if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus) &&
+                select_side(a, (uint32_t)locus)) {
                 int ub;
                 const uint32_t sc = (uint32_t)__builtin_rint(mit_score(mask, &ub) * 0x1p24);  // <= 100 * 2^24 < 2^31; as summary_kernel
                 if (sc >= a.min_score) {
@@ -1207,9 +1252,20 @@ hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream)
     if (args.n_tiles == 0) return hipSuccess;
     const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
     if (args.vals)
-        hipLaunchKernelGGL(select_score_kernel<false>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+        hipLaunchKernelGGL((select_score_kernel<false, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
     else
-        hipLaunchKernelGGL(select_score_kernel<true>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
+        hipLaunchKernelGGL((select_score_kernel<true, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_score_regions(const SelectRegionArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
+    if (args.vals)
+        hipLaunchKernelGGL((select_score_kernel<false, true>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL((select_score_kernel<true, true>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -706,42 +706,57 @@ int vsc_multi_search(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *gu
     });
 }
 
-int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
-                             const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
+}  // extern "C"
+
+namespace {
+
+// o += p, as the rows of genome shards add: fixed-point MIT sums and counts exactly; a locus lies in one shard only
+void add_row(vsc_guide_summary &o, const vsc_guide_summary &p)
+{
+    o.mit_sum += p.mit_sum;
+    for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.nm[k] += p.nm[k];
+    o.mit_ub += p.mit_ub;
+    o.on_target |= p.on_target;
+}
+
+// vsc_multi_search_summary (regions == null) and vsc_multi_search_summary_regions (`who`)
+int multi_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                  const vsc_locus *exclude, const vsc_regions *regions, vsc_guide_summary *out, vsc_guide_summary *out_in, const std::string &who)
 {
     return mguarded(m, [&]() -> int {
     if (!m) return VSC_ERR_INVALID;
     m->err.clear();
-    if (!g || g->multi != m || !params || (n_guides && (!guides || !out)))
-        return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_summary: null argument");
+    if (!g || g->multi != m || !params || (n_guides && (!guides || !out || (regions && !out_in))))
+        return mfail(m, VSC_ERR_INVALID, who + ": null argument");
     if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
         for (uint32_t i = 0; i < n_guides; ++i)
             if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
-                return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_summary: excluded locus outside the genome's contigs or strands");
+                return mfail(m, VSC_ERR_INVALID, who + ": excluded locus outside the genome's contigs or strands");
     const auto t0 = clk::now();
     const size_t n = m->ctx.size();
     std::vector<int> rc(n, VSC_OK);
-    std::vector<std::vector<vsc_guide_summary>> part(n);
+    std::vector<std::vector<vsc_guide_summary>> part(n), part_in(n);
     on_all(n, [&](size_t r) {
         if (!g->shard[r]) return;
         part[r].resize(n_guides);
-        rc[r] = vsc_search_summary(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, part[r].data());
+        if (regions) {
+            part_in[r].resize(n_guides);
+            rc[r] = vsc_search_summary_regions(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, regions, part[r].data(), part_in[r].data());
+        } else {
+            rc[r] = vsc_search_summary(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, part[r].data());
+        }
     });
     for (size_t r = 0; r < n; ++r)
         if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
     const double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    // the rows add exactly (fixed-point MIT sums, counts); a locus lies in one shard only
     std::fill(out, out + n_guides, vsc_guide_summary{});
+    if (regions) std::fill(out_in, out_in + n_guides, vsc_guide_summary{});
     vsc_multi_timing mt{};
     for (size_t r = 0; r < n; ++r) {
         if (!g->shard[r]) continue;
         for (uint32_t i = 0; i < n_guides; ++i) {
-            const vsc_guide_summary &p = part[r][i];
-            vsc_guide_summary &o = out[i];
-            o.mit_sum += p.mit_sum;
-            for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.nm[k] += p.nm[k];
-            o.mit_ub += p.mit_ub;
-            o.on_target |= p.on_target;
+            add_row(out[i], part[r][i]);
+            if (regions) add_row(out_in[i], part_in[r][i]);
         }
         vsc_timing t{};
         (void)vsc_ctx_timing(m->ctx[r], &t);
@@ -758,41 +773,44 @@ int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint
     });
 }
 
-int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
-                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
-                            vsc_guide_summary *summary, vsc_hits **out)
+// vsc_multi_search_select (filter == null) and vsc_multi_search_select_regions (`who`)
+int multi_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                 const vsc_select *select, const vsc_region_filter *filter, const vsc_locus *exclude, vsc_guide_summary *summary,
+                 vsc_guide_summary *summary_in, vsc_hits **out, const std::string &who)
 {
     return mguarded(m, [&]() -> int {
     if (!m || !out) return VSC_ERR_INVALID;
     *out = nullptr;
     m->err.clear();
     if (!g || g->multi != m || !params || !select || (n_guides && !guides))
-        return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: null argument");
-    if (select->reserved[0] || select->reserved[1]) return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: reserved fields must be 0");
+        return mfail(m, VSC_ERR_INVALID, who + ": null argument");
+    if (select->reserved[0] || select->reserved[1]) return mfail(m, VSC_ERR_INVALID, who + ": reserved fields must be 0");
+    if (filter && (!filter->regions || filter->scope > VSC_REGION_DROP || filter->reserved))  // (checked here too, as the loci below)
+        return mfail(m, VSC_ERR_INVALID, who + ": a filter needs regions, a scope of 0 or 1 and a reserved field of 0");
+    if (!filter && summary_in) return mfail(m, VSC_ERR_INVALID, who + ": summary_in without a filter");
     if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
         for (uint32_t i = 0; i < n_guides; ++i)
             if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
-                return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_select: excluded locus outside the genome's contigs or strands");
+                return mfail(m, VSC_ERR_INVALID, who + ": excluded locus outside the genome's contigs or strands");
     const size_t n = m->ctx.size();
-    std::vector<std::vector<vsc_guide_summary>> part(summary ? n : 0);
-    for (size_t r = 0; r < part.size(); ++r)
-        if (g->shard[r]) part[r].resize(n_guides);
+    std::vector<std::vector<vsc_guide_summary>> part(summary ? n : 0), part_in(summary_in ? n : 0);
+    for (auto *pp : {&part, &part_in})
+        for (size_t r = 0; r < pp->size(); ++r)
+            if (g->shard[r]) (*pp)[r].resize(n_guides);
     auto select_on = [&](size_t r, vsc_hits **h) {
-        return vsc_search_select(m->ctx[r], g->shard[r], guides, n_guides, params, select, exclude, summary ? part[r].data() : nullptr, h);
+        vsc_guide_summary *rows = summary ? part[r].data() : nullptr;
+        if (!filter) return vsc_search_select(m->ctx[r], g->shard[r], guides, n_guides, params, select, exclude, rows, h);
+        return vsc_search_select_regions(m->ctx[r], g->shard[r], guides, n_guides, params, select, filter, exclude, rows,
+                                         summary_in ? part_in[r].data() : nullptr, h);
     };
     // the rows add exactly, as in vsc_multi_search_summary
     auto add_rows = [&]() {
-        if (!summary) return;
-        std::fill(summary, summary + n_guides, vsc_guide_summary{});
-        for (size_t r = 0; r < n; ++r) {
-            if (!g->shard[r]) continue;
-            for (uint32_t i = 0; i < n_guides; ++i) {
-                const vsc_guide_summary &p = part[r][i];
-                vsc_guide_summary &o = summary[i];
-                o.mit_sum += p.mit_sum;
-                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.nm[k] += p.nm[k];
-                o.mit_ub += p.mit_ub;
-                o.on_target |= p.on_target;
+        for (auto pr : {std::make_pair(summary, &part), std::make_pair(summary_in, &part_in)}) {
+            if (!pr.first) continue;
+            std::fill(pr.first, pr.first + n_guides, vsc_guide_summary{});
+            for (size_t r = 0; r < n; ++r) {
+                if (!g->shard[r]) continue;
+                for (uint32_t i = 0; i < n_guides; ++i) add_row(pr.first[i], (*pr.second)[r][i]);
             }
         }
     };
@@ -887,6 +905,41 @@ int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint6
     m->timing = mt;
     return VSC_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                             const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
+{
+    return multi_summary(m, g, guides, n_guides, params, exclude, nullptr, out, nullptr, "vsc_multi_search_summary");
+}
+
+int vsc_multi_search_summary_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                     const vsc_search_params *params, const vsc_locus *exclude, const vsc_regions *regions,
+                                     vsc_guide_summary *out_all, vsc_guide_summary *out_in)
+{
+    if (!m) return VSC_ERR_INVALID;
+    if (!regions) return mfail(m, VSC_ERR_INVALID, "vsc_multi_search_summary_regions: null argument");
+    return multi_summary(m, g, guides, n_guides, params, exclude, regions, out_all, out_in, "vsc_multi_search_summary_regions");
+}
+
+int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                            vsc_guide_summary *summary, vsc_hits **out)
+{
+    return multi_select(m, g, guides, n_guides, params, select, nullptr, exclude, summary, nullptr, out, "vsc_multi_search_select");
+}
+
+int vsc_multi_search_select_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                    const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
+                                    const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
+                                    vsc_hits **out)
+{
+    return multi_select(m, g, guides, n_guides, params, select, filter, exclude, summary_all, summary_in, out,
+                        "vsc_multi_search_select_regions");
 }
 
 int vsc_multi_search_stream(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,

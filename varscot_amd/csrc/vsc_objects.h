@@ -81,6 +81,10 @@ struct vsc_ctx {
     vsc::DeviceBuf sum_rows, sum_excl;  // vsc_search_summary: the per-read rows it adds into, the excluded loci
     // vsc_search_select: per-read tables of a pass (score histograms, thresholds, counts, cursors, list starts), the candidates' keys and masks
     vsc::DeviceBuf sel_hist, sel_tabs, sel_keys, sel_masks;
+    // vsc_search_*_regions: the rows over the hits in the regions (beside sum_rows), and the device copy of the regions this
+    // context used last - start[], end_max[], class table in one buffer - keyed by the serial number of the vsc_regions
+    vsc::DeviceBuf sum_rows_in, regions_buf;
+    uint64_t regions_serial = 0;  // 0: none resident
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -102,6 +106,7 @@ struct vsc_genome {
     vsc_ctx *ctx = nullptr;
     uint32_t *d_hi = nullptr, *d_lo = nullptr, *d_nm = nullptr;
     uint32_t *d_contig_off = nullptr, *d_contig_end = nullptr;
+    std::vector<uint32_t> h_contig_off, h_contig_end;  // the same table on the host (what regions are checked against)
     uint2 *d_hl = nullptr;  // interleaved planes, built on first scoring call
     uint64_t first_word = 0, own_words = 0, dev_words = 0;
     uint32_t n_tiles = 0, n_contigs = 0;
@@ -129,6 +134,19 @@ struct vsc_genome {
     uint64_t ix_vert_bytes = 0, ix_edge_words = 0;  // sizes of d_ix_vert / d_ix_edge (the index file stores them)
     uint64_t index_bytes = 0;
     double index_ms = 0;
+};
+
+// An annotation as the sinks test hits against it (include/varscot_hip.h; built by vsc_regions.cpp).  Immutable once built.
+struct vsc_regions {
+    std::vector<uint32_t> start, end_max, cls;  // vsc::RegionsView's arrays
+    std::vector<uint32_t> contig_off, contig_len;  // the genome's table the intervals were placed in
+    uint32_t rule = 0, block_shift = 0, n_blocks = 0;
+    uint64_t serial = 0;  // process-wide, handed out by vsc_regions_build: what a context's device copy is keyed by
+    vsc_regions_stats stats{};
+    vsc::RegionsView view() const
+    {
+        return vsc::RegionsView{start.data(), end_max.data(), cls.data(), (uint32_t)start.size(), n_blocks, block_shift, rule};
+    }
 };
 
 struct vsc_hits {

@@ -137,6 +137,25 @@ def synthetic_guides(n, seed=SEED_GUIDES):
     return ids, seqs
 
 
+SEED_REGIONS = 0x5EED0005
+
+
+def synthetic_regions(table, n, fraction, seed=SEED_REGIONS):
+    """A synthetic annotation for a contig table: n intervals at uniformly random places whose lengths (uniform in 0.5 .. 1.5
+    of the mean) add up to `fraction` of the genome - exon-like for n = 250 000, fraction = 0.03 on 3 Gbp (mean 360 bases).
+    They may overlap (the union is slightly less than the sum) and are in no order.  Returns an INTERVAL_DTYPE array."""
+    from . import _lib
+    rng = np.random.default_rng(seed)
+    lens = np.asarray(table["length"], dtype=np.int64)
+    mean = max(1.0, fraction * lens.sum() / max(n, 1))
+    c = rng.choice(len(lens), size=n, p=lens / lens.sum())
+    ln = np.maximum(1, (mean * rng.uniform(0.5, 1.5, size=n)).astype(np.int64))
+    start = (rng.random(n) * np.maximum(lens[c] - ln, 1)).astype(np.int64)
+    iv = np.zeros(n, dtype=_lib.INTERVAL_DTYPE)
+    iv["contig"], iv["start"], iv["end"] = c, start, np.minimum(start + ln, lens[c])
+    return iv
+
+
 def plant_sites(packed, guides, n_sites, max_sub, seed=0x5EED0004):
     """Copies reads into the genome (either strand, 0..max_sub substitutions in the first 20 bases)
     at seeded positions well inside contigs.  Returns [(guide, contig, pos, strand, n_sub)]."""
