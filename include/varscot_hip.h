@@ -364,6 +364,60 @@ int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint
                               const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
                               const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
                               vsc_hits **out);
+/*
+ * Guide discovery: which guides does a target contain?  A CANDIDATE is a 23-base window w = c[p, p + 23) of the forward genome,
+ * wholly inside contig c (p + 23 == length is allowed), without N, with
+ *   strand '+'  w[21..23) == pam              the guide is g = w
+ *   strand '-'  w[0..2)  == revcomp(pam)      the guide is g = revcomp(w)
+ * and locus (c, p, strand) in vsc_hit / vsc_locus coordinates: vsc_search(g, 0 mismatches) reports that locus, and exclude =
+ * locus gives on_target = 1 (with a PAM other than GG / GA the search needs the same extra_pam).  It is KEPT when, with
+ * g[0..20) the protospacer in guide orientation,
+ *   pam[2]      g[21], g[22] equal these two letters (ACGT, any case; anything else: VSC_ERR_INVALID) - the GUIDE's PAM, NGG
+ *               by default, not the off-target PAM set of vsc_search_params
+ *   strands     0 both, 1 '+' only, 2 '-' only (> 2: VSC_ERR_INVALID)
+ *   gc_min/max  the number of G / C in g[0..20) lies in [gc_min, gc_max]; gc_max == 0: no upper bound (a zeroed struct filters
+ *               nothing); either > 20, or gc_min > gc_max != 0: VSC_ERR_INVALID
+ *   max_t_run   the longest run of T in g[0..20) is <= max_t_run; 0: no limit (3 is CRISPOR's TTTT rule)
+ *   regions     NULL: every window of the genome or shard; else the window is in the regions under their own rule
+ *               (vsc_regions_contains); regions built for another contig table: VSC_ERR_INVALID
+ *   max_guides  0: no cap; when more candidates are kept the call returns VSC_ERR_RANGE, vsc_last_error names the count and
+ *               nothing is returned
+ * params == NULL or a non-zero reserved field: VSC_ERR_INVALID.  A zeroed struct with pam = "GG" is the default.
+ * The result is ordered by ascending (contig, pos), '+' before '-' at one position - the ascending global position, so the
+ * results of genome shards concatenate in shard order to the whole genome's (a shard enumerates the windows that START in its
+ * own words, as the searches do).  The bytes depend on the genome and the parameters only: every candidate is written at a
+ * rank computed from per-tile counts (count pass, scan, write pass), nothing is appended through an atomic.
+ * codes = vsc_pack_guide codes (what every search takes), loci usable as `exclude` as they are: "every guide in these exons,
+ * ranked by specificity" is this call followed by vsc_search_summary on the same resident genome.
+ * vsc_ctx_timing afterwards: scan_ms = total_ms = the enumeration kernels, sites = candidates kept, genome_bytes = plane
+ * bytes the kernels read (with regions only tiles that hold a block of the class table that is not OUT are visited), the
+ * sort, score and hit fields 0.  Scratch comes from the context's pools (vsc_ctx_release_scratch gives it back); the result
+ * owns its two arrays until vsc_guides_free.
+ * Replaces, for a caller who has a target and not yet the loci: the extraction of on-targets from a BED
+ * (variant_processing/extract_fasta_ontargets.h:92-139), which needs every 23-mer's coordinates up front.
+ */
+typedef struct {
+    char pam[2];
+    uint8_t strands, gc_min, gc_max, max_t_run;
+    uint16_t reserved0;
+    uint64_t max_guides;
+    uint32_t reserved[2];
+} vsc_enum_params;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_enum_params) == 24, "vsc_enum_params layout");
+#else
+_Static_assert(sizeof(vsc_enum_params) == 24, "vsc_enum_params layout");
+#endif
+typedef struct vsc_guides vsc_guides;
+int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions /* may be NULL */,
+                         const vsc_enum_params *params, vsc_guides **out);
+uint64_t vsc_guides_count(const vsc_guides *guides);
+/* Host copies of the two arrays (made on first use; valid until vsc_guides_free).  Either pointer may be NULL. */
+int vsc_guides_data(vsc_guides *guides, const uint64_t **codes, const vsc_locus **loci);
+/* Device pointers (valid until vsc_guides_free); NULL for a host-only object (vsc_multi_guides_enumerate's) and when the
+ * result is empty. */
+int vsc_guides_data_dev(const vsc_guides *guides, const void **codes_dev, const void **loci_dev);
+int vsc_guides_free(vsc_guides *guides);
 /* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
  * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
 double vsc_mit_specificity(uint64_t mit_sum);
@@ -536,6 +590,13 @@ int vsc_multi_search_select_regions(vsc_multi *m, const vsc_multi_genome *g, con
                                     const vsc_search_params *params, const vsc_select *select, const vsc_region_filter *filter,
                                     const vsc_locus *exclude, vsc_guide_summary *summary_all, vsc_guide_summary *summary_in,
                                     vsc_hits **out);
+/* vsc_guides_enumerate over the device set: every shard enumerates the windows that start in its own words on its own context
+ * and host thread (as vsc_multi_search_summary does); shards partition the positions in ascending order, so the shards' arrays
+ * concatenated in shard order on the host ARE the whole genome's result.  *out is a host-only object (vsc_guides_data_dev
+ * gives NULL), released with vsc_guides_free.  max_guides holds for the total (a shard that exceeds it alone ends the call
+ * early; vsc_multi_last_error then names that shard's count). */
+int vsc_multi_guides_enumerate(vsc_multi *m, const vsc_multi_genome *g, const vsc_regions *regions,
+                               const vsc_enum_params *params, vsc_guides **out);
 /* (vsc_multi_search_stream, which scores on the owning shard, is declared behind the classifier below.) */
 
 /* ---- variant windows (row R8) ------------------------------------------------------------------- */

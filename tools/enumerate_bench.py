@@ -1,0 +1,111 @@
+"""Guide discovery (vsc_guides_enumerate) on the synthetic hg38-sized genome of varscot_amd.synth, one GPU.
+
+    python tools/enumerate_bench.py                       both cases, JSON to profiles/enumerate.json (and stdout)
+    python tools/enumerate_bench.py --case regions --calls 1 --warmup 1     (what a kernel trace needs)
+
+Cases
+  genome   every candidate of the whole genome: NGG, both strands, no filter, no regions
+  regions  the candidates of the 250 000-interval exon-like annotation (synth.synthetic_regions, 3 % of the genome), under both
+           rules (+ the same with CRISPOR-like filters: GC 8..14 of 20, no TTTT)
+Every case: W warm-up calls, then K timed calls, fastest .. slowest.  A call is the C entry point alone - the result stays on
+the device and is freed again (the host copy of 4e8 candidates would time the PCIe link): host wall time per call (it contains
+the hipMalloc of the result, which the context cannot pool: the caller owns it) and the enumeration kernels' own time
+(vsc_timing.scan_ms: count pass + scan, write pass).
+Reported beside them: candidates, the BYTE FLOOR from the shapes - plane bytes read per pass (vsc_timing.genome_bytes: 768
+bytes per visited tile and pass) + 24 bytes written per candidate - and floor / kernel time against the copy bandwidths DESIGN
+8 item 3 records for this part (library device-to-device copy 4.56 TB/s, float4 copy kernel 6.3 TB/s).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import varscot_amd as va  # noqa: E402
+from varscot_amd import _lib, dist as vdist, synth  # noqa: E402
+from varscot_amd.api import _enum_params  # noqa: E402
+
+COPY_TBS = {"device_copy": 4.56, "float4_copy_kernel": 6.3}  # DESIGN 8 item 3 (tools/gpu.sh bw)
+
+
+def one_call(ctx, genome, regions, params):
+    """(wall ms, kernels ms, candidates, plane bytes read) of one vsc_guides_enumerate; the result is freed"""
+    L = va.lib()
+    h = C.c_void_p()
+    t0 = time.perf_counter()
+    _lib.check(L.vsc_guides_enumerate(ctx._h, genome._h, regions._h if regions is not None else None, C.byref(params), C.byref(h)),
+               ctx._h)
+    wall = (time.perf_counter() - t0) * 1e3
+    n = int(L.vsc_guides_count(h))
+    L.vsc_guides_free(h)
+    t = ctx.timing()
+    assert t["sites"] == n
+    return wall, t["scan_ms"], n, t["genome_bytes"]
+
+
+def measure(ctx, genome, regions, params, calls, warmup):
+    for _ in range(warmup):
+        one_call(ctx, genome, regions, params)
+    runs = [one_call(ctx, genome, regions, params) for _ in range(calls)]
+    assert len({(r[2], r[3]) for r in runs}) == 1
+    n, plane_bytes = runs[0][2], runs[0][3]
+    floor = plane_bytes + 24 * n
+    kernel = sorted(r[1] for r in runs)
+    wall = sorted(r[0] for r in runs)
+    out = {"candidates": n, "plane_bytes_read": plane_bytes, "floor_bytes": floor, "kernels_ms": kernel, "wall_ms": wall,
+           "floor_tb_per_s_at_fastest": floor / (kernel[0] * 1e-3) / 1e12 if kernel[0] > 0 else None}
+    for name, tbs in COPY_TBS.items():
+        out["floor_ms_at_" + name] = floor / (tbs * 1e12) * 1e3
+        out["share_of_" + name] = (floor / (kernel[0] * 1e-3) / 1e12) / tbs if kernel[0] > 0 else None
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--case", default="both", choices=["genome", "regions", "both"])
+    ap.add_argument("--calls", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--bases", type=int, default=3_000_000_000, help="genome size (default: the hg38-sized synthetic genome)")
+    ap.add_argument("--intervals", type=int, default=250_000)
+    ap.add_argument("--fraction", type=float, default=0.03)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "enumerate.json"))
+    args = ap.parse_args()
+    table, _ = synth.contig_table(args.bases)
+    span = int(table[-1]["offset"]) + int(table[-1]["length"]) + 1
+    n_words = (span + 31) // 32
+    wb, we = vdist.shard_words(n_words, 0, 1)
+    hi, lo, nm, _, _, _ = synth.synthetic_planes(args.bases, wb, min(we + 1, n_words))
+    ctx = va.Context(0)
+    genome = va.Genome.from_shard(ctx, hi, lo, nm, wb, we - wb, table)
+    del hi, lo, nm
+    res = {"genome_bases": args.bases, "calls": args.calls, "warmup": args.warmup, "copy_tb_per_s": COPY_TBS, "cases": {}}
+    plain = _enum_params("GG", "both", (0, 0), 0, 0)
+    if args.case in ("genome", "both"):
+        res["cases"]["genome_NGG_both_strands"] = measure(ctx, genome, None, plain, args.calls, args.warmup)
+        print(json.dumps({"genome_NGG_both_strands": res["cases"]["genome_NGG_both_strands"]}), flush=True)
+    if args.case in ("regions", "both"):
+        iv = synth.synthetic_regions(table, args.intervals, args.fraction)
+        strict = _enum_params("GG", "both", (8, 14), 3, 0)
+        for rule in ("overlap", "inside"):
+            regions = va.Regions(va.PackedGenome(None, None, None, table), iv, rule=rule)
+            for label, p in (("", plain), ("_gc8-14_t3", strict)):
+                key = "regions_%s%s" % (rule, label)
+                res["cases"][key] = dict(measure(ctx, genome, regions, p, args.calls, args.warmup), intervals=args.intervals,
+                                         fraction=args.fraction, info=regions.info())
+                print(json.dumps({key: res["cases"][key]}), flush=True)
+            regions.close()
+    genome.close()
+    ctx.close()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -178,6 +178,30 @@ int main()
                 CHECK(vsc_multi_search_select_regions(m, g, codes.data(), (uint32_t)codes.size(), &params, &sel, &flt, nullptr, nullptr, nullptr,
                                                       &some) == VSC_ERR_INVALID && !some, "a bad filter is refused");
             }
+            // guide discovery: every shard's arrays, joined in shard order = one entry per tile, ascending; the cap holds for the total
+            {
+                vsc_enum_params ep{};
+                ep.pam[0] = ep.pam[1] = 'G';
+                vsc_guides *found = nullptr;
+                CHECK(vsc_multi_guides_enumerate(m, g, nullptr, &ep, &found) == VSC_OK && found, "enumerate: %s", vsc_multi_last_error(m));
+                if (found) {
+                    const uint64_t *fc = nullptr;
+                    const vsc_locus *fl = nullptr;
+                    CHECK(vsc_guides_data(found, &fc, &fl) == VSC_OK && vsc_guides_count(found) == tiles, "enumerate: %llu guides",
+                          (unsigned long long)vsc_guides_count(found));
+                    for (uint64_t t = 0; t < tiles && t < vsc_guides_count(found); ++t)
+                        if (fc[t] != t || fl[t].pos != t * 2048) {
+                            CHECK(false, "guide %llu of the enumeration over %d shards", (unsigned long long)t, n);
+                            break;
+                        }
+                    vsc_guides_free(found);
+                }
+                ep.max_guides = tiles - 1;
+                CHECK(vsc_multi_guides_enumerate(m, g, nullptr, &ep, &found) == VSC_ERR_RANGE && !found, "the cap holds for the total");
+                ep.max_guides = tiles;
+                CHECK(vsc_multi_guides_enumerate(m, g, nullptr, &ep, &found) == VSC_OK && found, "a cap at the count");
+                vsc_guides_free(found);
+            }
             // streams: batch sizes that give 1, 2, 3, many batches (a ragged last one), every scoring mode
             for (uint32_t batch : {173u, 100u, 64u, 7u, 1u})
                 for (uint32_t mode : {(uint32_t)VSC_MULTI_SCORE_NONE, (uint32_t)VSC_MULTI_SCORE_ROWS, (uint32_t)VSC_MULTI_SCORE_VOTES}) {

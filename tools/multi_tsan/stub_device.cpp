@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <mutex>
+#include <string>
 #include <thread>
 
 #include "stub_device.h"
@@ -237,6 +238,43 @@ int vsc_search_select(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides,
         h->host.swap(kept);
         h->n = h->host.size();
     }
+    return VSC_OK;
+}
+
+// (vsc_multi_guides_enumerate: every shard "finds" one guide per own tile - code = the tile's global number, locus position =
+// its first base - so that the concatenation in shard order is the ascending list of all tiles)
+int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *g, const vsc_regions *, const vsc_enum_params *p, vsc_guides **out)
+{
+    *out = nullptr;
+    std::this_thread::sleep_for(std::chrono::microseconds(stub::mix(g->first_word) % 500));
+    const uint64_t tiles = (g->own_words + 63) / 64;
+    if (p->max_guides && tiles > p->max_guides) {
+        ctx->err = "stub: " + std::to_string(tiles) + " candidates exceed max_guides";
+        return VSC_ERR_RANGE;
+    }
+    vsc_guides *r = new vsc_guides();
+    for (uint64_t t = 0; t < tiles; ++t) {
+        r->codes.push_back(g->first_word / 64 + t);
+        r->loci.push_back(vsc_locus{0, (uint32_t)((g->first_word + 64 * t) * 32), (uint32_t)(t & 1), 0});
+    }
+    r->n = tiles;
+    r->host_valid = true;
+    ctx->timing = vsc_timing{};
+    ctx->timing.total_ms = 1.0;
+    ctx->timing.sites = tiles;
+    *out = r;
+    return VSC_OK;
+}
+uint64_t vsc_guides_count(const vsc_guides *g) { return g ? g->n : 0; }
+int vsc_guides_data(vsc_guides *g, const uint64_t **codes, const vsc_locus **loci)
+{
+    if (codes) *codes = g->codes.data();
+    if (loci) *loci = g->loci.data();
+    return VSC_OK;
+}
+int vsc_guides_free(vsc_guides *g)
+{
+    delete g;
     return VSC_OK;
 }
 

@@ -11,7 +11,7 @@ set -o pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd); TAG=${TAG:-r04}; LOG=$ROOT/profiles/${TAG}_sanitizers_cpu.txt
 HIPCC=/opt/rocm/bin/hipcc; CXX=/opt/rocm/lib/llvm/bin/clang++
 RT=$(dirname "$($CXX -print-file-name=libclang_rt.asan-x86_64.so)")
-SRCS="vsc_kernels.hip vsc_seed.hip vsc_sort.hip vsc_api.cpp vsc_pack.cpp vsc_windows.cpp vsc_multi.cpp vsc_regions.cpp"
+SRCS="vsc_kernels.hip vsc_seed.hip vsc_sort.hip vsc_enum.hip vsc_api.cpp vsc_pack.cpp vsc_windows.cpp vsc_multi.cpp vsc_regions.cpp"
 TOOLS="bidir_index bidir_mapping vcf_loader bam_merger_ref_only bam_merger fasta_writer classification_pipeline varscot_pipeline guide_summary"
 : > "$LOG"
 build() {  # build NAME "sanitizer flags"
@@ -41,7 +41,7 @@ asan|all)
     echo "# AddressSanitizer + UndefinedBehaviorSanitizer (host code; clang $($CXX --version | head -1))" | tee -a "$LOG"
     build asan "-fsanitize=address,undefined -fno-sanitize-recover=undefined"
     run asan libclang_rt.asan-x86_64.so "ASAN_OPTIONS=detect_leaks=0:abort_on_error=0 UBSAN_OPTIONS=print_stacktrace=1" \
-        tests/test_abi.py tests/test_variants.py tests/test_tools.py tests/test_summary_cpu.py tests/test_select_cpu.py tests/test_regions_cpu.py ;;&
+        tests/test_abi.py tests/test_variants.py tests/test_tools.py tests/test_summary_cpu.py tests/test_select_cpu.py tests/test_regions_cpu.py tests/test_enumerate_cpu.py ;;&
 tsan|all)
     echo "# ThreadSanitizer (host code)" | tee -a "$LOG"
     build tsan "-fsanitize=thread"

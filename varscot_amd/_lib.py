@@ -55,6 +55,16 @@ class RegionFilter(C.Structure):
     _fields_ = [("regions", C.c_void_p), ("scope", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class EnumParams(C.Structure):
+    """vsc_enum_params (vsc_guides_enumerate): the guide's PAM, strands (0 both, 1 '+', 2 '-'), GC bounds and largest T run over
+    the 20 protospacer bases (0 = no upper bound / no limit), max_guides (0 = no cap)."""
+    _fields_ = [("pam", C.c_char * 2), ("strands", C.c_uint8), ("gc_min", C.c_uint8), ("gc_max", C.c_uint8),
+                ("max_t_run", C.c_uint8), ("reserved0", C.c_uint16), ("max_guides", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(EnumParams) == 24
+
+
 class RegionsStats(C.Structure):
     """vsc_regions_stats (vsc_regions_info)."""
     _fields_ = [("intervals", C.c_uint64), ("rule", C.c_uint32), ("block_bases", C.c_uint32), ("blocks_out", C.c_uint64),
@@ -162,6 +172,11 @@ SYMBOLS = [
     ("vsc_search_summary_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
     ("vsc_search_select_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), C.POINTER(RegionFilter),
                                             _vp, _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_guides_enumerate", C.c_int, [_vp, _vp, _vp, C.POINTER(EnumParams), C.POINTER(_vp)]),
+    ("vsc_guides_count", C.c_uint64, [_vp]),
+    ("vsc_guides_data", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("vsc_guides_data_dev", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("vsc_guides_free", C.c_int, [_vp]),
     ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),
@@ -194,6 +209,7 @@ SYMBOLS = [
     ("vsc_multi_search_summary_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
     ("vsc_multi_search_select_regions", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select),
                                                   C.POINTER(RegionFilter), _vp, _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_multi_guides_enumerate", C.c_int, [_vp, _vp, _vp, C.POINTER(EnumParams), C.POINTER(_vp)]),
     ("vsc_multi_search_stream", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.c_uint32, C.POINTER(MultiScore), MULTI_BATCH_FN, _vp]),
     ("vsc_windows_build", C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_uint32,
                                     C.POINTER(_vp), C.c_char_p, C.c_size_t]),

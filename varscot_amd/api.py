@@ -27,6 +27,46 @@ def pack_guides(guides):
     return out
 
 
+def unpack_guides(codes):
+    """uint64 codes (pack_guides, enumerate_guides) -> 23-nt strings: base i = "ACGT"[code >> 2 i & 3]."""
+    c = np.ascontiguousarray(codes, dtype=np.uint64).reshape(-1, 1)
+    idx = ((c >> (2 * np.arange(READ_LEN, dtype=np.uint64))) & np.uint64(3)).astype(np.intp)
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)[idx]
+    return [row.tobytes().decode() for row in letters]
+
+
+def _enum_params(pam, strands, gc, max_t_run, max_guides):
+    """vsc_enum_params of enumerate_guides' arguments.  Only what cannot be put into the struct is refused here: the library
+    checks the values (a PAM letter outside ACGT, gc bounds above 20, ... are VSC_ERR_INVALID there)."""
+    b = pam if isinstance(pam, bytes) else pam.encode()
+    if len(b) != 2:
+        raise ValueError("the guide PAM must be 2 letters (NGG: 'GG')")
+    if strands not in ("both", "+", "-", 0, 1, 2, 3):
+        raise ValueError("strands must be 'both', '+' or '-'")
+    gc_min, gc_max = gc
+    p = _lib.EnumParams()
+    p.pam = b
+    p.strands = {"both": 0, "+": 1, "-": 2}.get(strands, strands)
+    p.gc_min, p.gc_max, p.max_t_run, p.max_guides = int(gc_min), int(gc_max), int(max_t_run), int(max_guides)
+    return p
+
+
+def _guides_arrays(handle, check_fn):
+    """(codes uint64[n], loci LOCUS_DTYPE[n]) copied out of a vsc_guides, which is freed."""
+    L = lib()
+    try:
+        n = int(L.vsc_guides_count(handle))
+        pc, pl = C.c_void_p(), C.c_void_p()
+        check_fn(L.vsc_guides_data(handle, C.byref(pc), C.byref(pl)))
+        if n == 0:
+            return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=_lib.LOCUS_DTYPE)
+        codes = np.frombuffer((C.c_char * (n * 8)).from_address(pc.value), dtype=np.uint64).copy()
+        loci = np.frombuffer((C.c_char * (n * 16)).from_address(pl.value), dtype=_lib.LOCUS_DTYPE).copy()
+        return codes, loci
+    finally:
+        L.vsc_guides_free(handle)
+
+
 def _loci(exclude, n):
     """(contig, pos, strand) per guide -> vsc_locus array (None stays None)."""
     if exclude is None:
@@ -387,6 +427,27 @@ class Genome:
         hits = Hits(self, h, codes)
         return (hits, rows, inside) if summary else hits
 
+    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None):
+        """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
+        `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
+        everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
+        than max_t_run T in them (0: no limit).  Returns (codes uint64[n], loci LOCUS_DTYPE[n]) in ascending (contig, pos),
+        '+' before '-': codes are what every search takes, loci what `exclude` takes.  More than max_guides (0: no cap)
+        candidates raise VarscotError -34.  params: an EnumParams to pass as it is (tests)."""
+        p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
+        h = C.c_void_p()
+        check(lib().vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
+              self.ctx._h)
+        return _guides_arrays(h, lambda code: check(code, self.ctx._h))
+
+    def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, **search_options):
+        """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
+        max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
+        summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
+        A PAM other than GG / GA needs extra_pam=pam among the search options for the guide's own locus to be a hit."""
+        codes, loci = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides)
+        return codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)
+
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)
         and on_batch(hits, first_guide, n_guides) is called with every batch's result - a Hits object that is
@@ -709,6 +770,15 @@ class MultiGenome:
         if not summary:
             return res
         return (res, rows) if flt is None else (res, rows, inside)
+
+    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None):
+        """vsc_multi_guides_enumerate: Genome.enumerate_guides over the shards, their arrays joined in shard order on the
+        host - the same bytes as one device gives."""
+        p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
+        h = C.c_void_p()
+        self.multi._check(lib().vsc_multi_guides_enumerate(self.multi._h, self._h, regions._h if regions is not None else None,
+                                                           C.byref(p), C.byref(h)))
+        return _guides_arrays(h, self.multi._check)
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

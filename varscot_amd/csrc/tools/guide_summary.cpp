@@ -5,6 +5,12 @@
 //   -R reads.fa       23-mers (non-ACGT letters become A); nothing is excluded
 //   -B ontargets.bed  BED6 on-targets, the 23-mer extracted as fasta_writer does (extract_fasta_ontargets.h:92-139); the
 //                     on-target locus itself (chr, start, strand) is left out of the counts and reported as onTargetFound
+//   -E targets.bed    BED3+ intervals of a target: the guides are the candidates the device finds in them (vsc_guides_enumerate:
+//                     N-free 23-mers with the guide PAM -p, default GG, on the strands -s; inside the intervals by the rule -e,
+//                     default inside; GC bounds -g MIN,MAX and largest T run -t over the 20 protospacer bases), in enumeration
+//                     order (chrom, start, '+' before '-'), guideId = chrom:start:strand; the candidate's own locus is left out
+//                     as -B's is.  -L guides.bed writes them as BED6 (chrom start start+23 guideId 0 strand), the on-target
+//                     format the VARSCOT driver and -B read.  A guide PAM other than GG / GA is searched as -P unless -P is given.
 // Output (-O, default stdout): one line per guide in input order under the header
 //   #guideId guideSeq mitSpecScore offtargetCount onTargetFound mm0 .. mm<M> mitHitSum
 // mitSpecScore = floor(100 / (100 + mitHitSum) * 100 + 0.5) (CRISPOR's guide score and Python 2 round()),
@@ -55,6 +61,13 @@ int main(int argc, char **argv)
         {'a', "region-rule", "overlap (default): a hit is in the regions when its window shares a base with an interval; "
                              "inside: when it lies fully inside one interval", false},
         {'X', "region-scope", "keep | drop: list in the -T file only hits in the regions / outside them (needs -A and -T)", false},
+        {'E', "targets", "Path to target intervals (.bed, BED3+): the guides are the candidate guides found in them, each with its own locus excluded", false},
+        {'e', "target-rule", "inside (default): a candidate's 23-base window lies fully inside one -E interval; overlap: it shares a base with one", false},
+        {'p', "guide-pam", "PAM of the guides to find with -E, two letters of ACGT (default GG)", false},
+        {'g', "gc", "MIN,MAX: keep -E candidates with MIN <= G/C among the 20 protospacer bases <= MAX, 0 .. 20 (MAX 0: no upper bound)", false},
+        {'t', "t-run", "Keep -E candidates whose longest run of T in the protospacer is at most this, 0 .. 20 (0, the default: no limit; 3 drops TTTT)", false},
+        {'s', "strands", "+ | - | both (default): strands on which -E looks for guides", false},
+        {'L', "list-guides", "Path to a BED6 file (.bed) that receives the -E candidates: chrom start end guideId 0 strand", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -62,13 +75,16 @@ int main(int argc, char **argv)
     if (pr) return pr == 1;
     const std::string genome_path = opts[0].value, index_prefix = opts[1].value, reads_path = opts[2].value, bed_path = opts[3].value;
     const std::string out_path = opts[5].value, pam = opts[6].value;
-    if (opts[2].set == opts[3].set) {
-        std::fprintf(stderr, "%s: give the guides with exactly one of -R (reads) and -B (on-targets)\n", argv[0]);
+    const bool discover = opts[14].set;
+    const std::string targets_path = opts[14].value, guides_bed_path = opts[20].value;
+    if ((int)opts[2].set + (int)opts[3].set + (int)discover != 1) {
+        std::fprintf(stderr, "%s: give the guides with exactly one of -R (reads), -B (on-targets) and -E (targets to find guides in)\n", argv[0]);
         return 1;
     }
     if (!has_extension(genome_path, {"fa", "fasta"}) || (opts[2].set && !has_extension(reads_path, {"fa", "fasta"})) ||
-        (opts[3].set && !has_extension(bed_path, {"bed"})) || (opts[5].set && !has_extension(out_path, {"tsv", "txt"}))) {
-        std::fprintf(stderr, "%s: genome and reads must be .fa/.fasta files, on-targets a .bed file, the output a .tsv/.txt file\n", argv[0]);
+        (opts[3].set && !has_extension(bed_path, {"bed"})) || (opts[5].set && !has_extension(out_path, {"tsv", "txt"})) ||
+        (discover && !has_extension(targets_path, {"bed"})) || (opts[20].set && !has_extension(guides_bed_path, {"bed"}))) {
+        std::fprintf(stderr, "%s: genome and reads must be .fa/.fasta files, on-targets, targets and the guide list .bed files, the output a .tsv/.txt file\n", argv[0]);
         return 1;
     }
     char *end = nullptr;
@@ -142,6 +158,62 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: -a chooses the rule of the -A regions: give -A\n", argv[0]);
         return 1;
     }
+    // -E and its filters (vsc_enum_params)
+    vsc_enum_params ep{};
+    ep.pam[0] = ep.pam[1] = 'G';
+    uint32_t target_rule = VSC_REGION_INSIDE;
+    for (int k : {15, 16, 17, 18, 19, 20})
+        if (opts[k].set && !discover) {
+            std::fprintf(stderr, "%s: -%c belongs to the guide discovery of -E: give -E\n", argv[0], opts[k].short_name);
+            return 1;
+        }
+    if (opts[15].set) {
+        if (opts[15].value != "overlap" && opts[15].value != "inside") {
+            std::fprintf(stderr, "%s: -e takes inside or overlap, not '%s'\n", argv[0], opts[15].value.c_str());
+            return 1;
+        }
+        target_rule = opts[15].value == "inside" ? VSC_REGION_INSIDE : VSC_REGION_OVERLAP;
+    }
+    if (opts[16].set) {
+        const std::string &v = opts[16].value;
+        const std::string acgt = "ACGTacgt";
+        if (v.size() != 2 || acgt.find(v[0]) == std::string::npos || acgt.find(v[1]) == std::string::npos) {
+            std::fprintf(stderr, "%s: -p takes the two PAM letters of the guides (ACGT), e.g. GG, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        ep.pam[0] = v[0];
+        ep.pam[1] = v[1];
+    }
+    if (opts[17].set) {
+        const std::string &v = opts[17].value;
+        char *e1 = nullptr, *e2 = nullptr;
+        const long lo = std::strtol(v.c_str(), &e1, 10);
+        const long hi = (e1 != v.c_str() && *e1 == ',') ? std::strtol(e1 + 1, &e2, 10) : -1;
+        if (e1 == v.c_str() || *e1 != ',' || e2 == e1 + 1 || *e2 || lo < 0 || lo > 20 || hi < 0 || hi > 20 || (hi && lo > hi)) {
+            std::fprintf(stderr, "%s: -g takes MIN,MAX with 0 <= MIN <= MAX <= 20 (MAX 0: no upper bound), not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        ep.gc_min = (uint8_t)lo;
+        ep.gc_max = (uint8_t)hi;
+    }
+    if (opts[18].set) {
+        const std::string &v = opts[18].value;
+        char *tend = nullptr;
+        const long k = std::strtol(v.c_str(), &tend, 10);
+        if (v.empty() || *tend || k < 0 || k > 20) {
+            std::fprintf(stderr, "%s: -t takes the largest run of T, 0 (no limit) .. 20, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        ep.max_t_run = (uint8_t)k;
+    }
+    if (opts[19].set) {
+        const std::string &v = opts[19].value;
+        if (v != "+" && v != "-" && v != "both") {
+            std::fprintf(stderr, "%s: -s takes +, - or both, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        ep.strands = v == "+" ? 1 : v == "-" ? 2 : 0;
+    }
     std::vector<int> devices;  // -D 0 | -D 0,1,2,3 (an id may repeat: several shards on one device)
     {
         const std::string d = opts[7].set ? opts[7].value : "0";
@@ -166,7 +238,8 @@ int main(int argc, char **argv)
     vsc_multi *multi = nullptr;
     vsc_multi_genome *mgenome = nullptr;
     vsc_hits *hits = nullptr;
-    vsc_regions *regions = nullptr;
+    vsc_regions *regions = nullptr, *targets = nullptr;
+    vsc_guides *found = nullptr;
     int rc = 1;
     try {
         const PackedIndex ix = read_index(index_prefix);
@@ -174,10 +247,35 @@ int main(int argc, char **argv)
         int64_t mtime = 0;
         if (ix.src_size && (!file_stamp(genome_path, &size, &mtime) || size != ix.src_size || mtime != ix.src_mtime))
             throw std::runtime_error("index " + index_path(index_prefix) + " was not packed from " + genome_path);
+        std::map<std::string, uint32_t> by_chrom;  // first word of the contig name, as the -T file prints it
+        for (size_t c = ix.names.size(); c-- > 0;) by_chrom[ix.names[c].substr(0, ix.names[c].find_first_of(" \t"))] = (uint32_t)c;
+        auto read_bed3 = [&](const std::string &path, const std::string &flag) {  // the intervals of a BED3+ file (-A, -E)
+            std::ifstream bed(path);
+            if (!bed) throw std::runtime_error("Could not open the " + flag + " file.");
+            std::vector<vsc_interval> iv;
+            std::string line;
+            while (std::getline(bed, line)) {
+                if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+                std::istringstream is(line);
+                std::string chr;
+                unsigned long long start = 0, stop = 0;
+                if (!(is >> chr >> start >> stop)) throw std::runtime_error(flag + ": not a BED line: '" + line + "'");
+                auto it = by_chrom.find(chr);
+                if (it == by_chrom.end()) throw std::runtime_error(flag + ": no sequence '" + chr + "' in the genome");
+                if (start > stop || stop > 0xFFFFFFFFull) throw std::runtime_error(flag + ": bad interval in '" + line + "'");
+                iv.push_back(vsc_interval{it->second, (uint32_t)start, (uint32_t)stop, 0u});
+            }
+            return iv;
+        };
         // the guides (+ their excluded loci)
         std::vector<std::string> ids, seqs;
         std::vector<vsc_locus> loci;
-        if (opts[2].set) {
+        if (discover) {  // the guides themselves come from the device, below
+            const std::vector<vsc_interval> iv = read_bed3(targets_path, "-E");
+            if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), target_rule, &targets) != VSC_OK)
+                throw std::runtime_error("could not build the regions of the -E file");
+            std::fprintf(stderr, "Targets loaded (total: %zu).\n", iv.size());
+        } else if (opts[2].set) {
             for (auto &r : read_fasta(reads_path)) {
                 ids.push_back(r.id);
                 seqs.push_back(r.seq);
@@ -207,25 +305,9 @@ int main(int argc, char **argv)
                 throw std::runtime_error("guide '" + ids[i] + "' is not 23 nt long (VARSCOT searches 20 nt + PAM)");
             codes[i] = vsc_pack_guide(seqs[i].c_str());
         }
-        std::fprintf(stderr, "Guides loaded (total: %zu).\n", seqs.size());
+        if (!discover) std::fprintf(stderr, "Guides loaded (total: %zu).\n", seqs.size());
         if (annotated) {
-            std::map<std::string, uint32_t> by_chrom;  // first word of the contig name, as the -T file prints it
-            for (size_t c = ix.names.size(); c-- > 0;) by_chrom[ix.names[c].substr(0, ix.names[c].find_first_of(" \t"))] = (uint32_t)c;
-            std::ifstream bed(regions_path);
-            if (!bed) throw std::runtime_error("Could not open the -A file.");
-            std::vector<vsc_interval> iv;
-            std::string line;
-            while (std::getline(bed, line)) {
-                if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
-                std::istringstream is(line);
-                std::string chr;
-                unsigned long long start = 0, stop = 0;
-                if (!(is >> chr >> start >> stop)) throw std::runtime_error("-A: not a BED line: '" + line + "'");
-                auto it = by_chrom.find(chr);
-                if (it == by_chrom.end()) throw std::runtime_error("-A: no sequence '" + chr + "' in the genome");
-                if (start > stop || stop > 0xFFFFFFFFull) throw std::runtime_error("-A: bad interval in '" + line + "'");
-                iv.push_back(vsc_interval{it->second, (uint32_t)start, (uint32_t)stop, 0u});
-            }
+            const std::vector<vsc_interval> iv = read_bed3(regions_path, "-A");
             if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), region_rule, &regions) != VSC_OK)
                 throw std::runtime_error("could not build the regions of the -A file");
             filter.regions = regions;
@@ -256,6 +338,46 @@ int main(int argc, char **argv)
             p.has_extra_pam = 1;
             p.extra_pam[0] = pam[0];
             p.extra_pam[1] = pam[1];
+        }
+        if (discover) {
+            st = multi ? vsc_multi_guides_enumerate(multi, mgenome, targets, &ep, &found) : vsc_guides_enumerate(ctx, genome, targets, &ep, &found);
+            if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+            const uint64_t *fc = nullptr;
+            const vsc_locus *fl = nullptr;
+            if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
+            const uint64_t n = vsc_guides_count(found);
+            if (n >= (1ull << 31)) throw std::runtime_error("-E: too many candidates for one search; narrow the targets or the filters");
+            codes.assign(fc, fc + n);
+            loci.assign(fl, fl + n);
+            std::string bed6;
+            for (uint64_t i = 0; i < n; ++i) {
+                const std::string &name = ix.names[fl[i].contig];
+                const std::string chrom = name.substr(0, name.find_first_of(" \t"));
+                const char strand = fl[i].strand ? '-' : '+';
+                std::string seq(VSC_READ_LEN, 'A');
+                for (int j = 0; j < VSC_READ_LEN; ++j) seq[j] = "ACGT"[(fc[i] >> (2 * j)) & 3u];
+                ids.push_back(chrom + ':' + std::to_string(fl[i].pos) + ':' + strand);
+                seqs.push_back(seq);
+                if (opts[20].set)
+                    bed6 += chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
+                            "\t0\t" + strand + '\n';
+            }
+            if (opts[20].set) {
+                std::ofstream out(guides_bed_path);
+                if (!out.is_open()) throw std::runtime_error("Could not open the -L path.");
+                out << bed6;
+                out.close();
+                if (!out) throw std::runtime_error("Could not write the -L file.");
+            }
+            std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
+            // the guide's own locus is a hit only if the search allows its PAM
+            const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');
+            if (!canonical && !p.has_extra_pam) {
+                p.has_extra_pam = 1;
+                p.extra_pam[0] = ep.pam[0];
+                p.extra_pam[1] = ep.pam[1];
+                std::fprintf(stderr, "%s: searching with -P %c%c, the guide PAM of -p\n", argv[0], ep.pam[0], ep.pam[1]);
+            }
         }
         std::vector<vsc_guide_summary> sum(codes.size()), sum_in(annotated ? codes.size() : 0);
         const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
@@ -380,7 +502,9 @@ int main(int argc, char **argv)
         rc = 1;
     }
     if (hits) vsc_hits_free(hits);
+    vsc_guides_free(found);
     vsc_regions_free(regions);
+    vsc_regions_free(targets);
     if (multi) {
         vsc_multi_genome_free(mgenome);
         vsc_multi_destroy(multi);

@@ -9,10 +9,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
 
@@ -211,7 +213,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
-                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf})
+                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs})
         b->release();
     ctx->regions_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
@@ -2109,6 +2111,166 @@ int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint
     if (!filter && summary_in) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select_regions: summary_in without a filter");
     return search_select(ctx, genome, guides, n_guides, params, select, filter, exclude, summary_all, summary_in, out,
                          "vsc_search_select_regions");
+}
+
+// ---- guide discovery (kernels: vsc_enum.hip) -------------------------------------------------------------------------------
+// Count pass over the work list, exclusive scan of the per-tile counts, one 8-byte read-back (the total: it sizes the result
+// and is what max_guides is checked against), write pass into the result's own arrays.
+int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const vsc_enum_params *params,
+                         vsc_guides **out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    ctx->err.clear();
+    if (!genome || !params) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: null argument");
+    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: genome belongs to another context");
+    const int p0 = base_code(params->pam[0]), p1 = base_code(params->pam[1]);
+    if (p0 > 3 || p1 > 3) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: the PAM must be two letters of ACGT");
+    if (params->strands > 2) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: strands must be 0 (both), 1 ('+') or 2 ('-')");
+    if (params->gc_min > 20 || params->gc_max > 20 || (params->gc_max && params->gc_min > params->gc_max))
+        return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: GC bounds must satisfy gc_min <= gc_max <= 20 (gc_max 0: no upper bound)");
+    if (params->reserved0 || params->reserved[0] || params->reserved[1])
+        return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: reserved fields must be 0");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EnumArgs a{};
+    if (regions) {
+        const int rrc = resident_regions(ctx, genome, regions, "vsc_guides_enumerate", a.reg);
+        if (rrc != VSC_OK) return rrc;
+    }
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.pam = pam_masks(p0, p1);
+    a.keep_fwd = params->strands != 2 ? 0xFFFFFFFFu : 0u;
+    a.keep_rev = params->strands != 1 ? 0xFFFFFFFFu : 0u;
+    a.gc_min = params->gc_min;
+    a.gc_max = params->gc_max ? params->gc_max : 20u;
+    a.max_t_run = params->max_t_run;
+    a.filter = (a.gc_min > 0 || a.gc_max < 20 || a.max_t_run) ? 1u : 0u;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+
+    // the work list: with regions, the tiles that hold a block of the class table that is not OUT (a block is >= 32 starts,
+    // a tile 2 048: 64 blocks or fewer); without, every tile of the shard
+    std::vector<uint32_t> work;
+    uint32_t n_work = genome->d_hi ? genome->n_tiles : 0;
+    if (regions && n_work) {
+        const uint32_t shift = regions->block_shift;
+        for (uint32_t t = 0; t < genome->n_tiles; ++t) {
+            const uint64_t p = (uint64_t)a.first_pos + (uint64_t)t * kTileBases;
+            const uint64_t b0 = p >> shift, b1 = std::min<uint64_t>((p + kTileBases - 1) >> shift, (uint64_t)regions->n_blocks - 1);
+            bool any = false;
+            for (uint64_t b = b0; !any && regions->n_blocks && b <= b1; ++b) any = ((regions->cls[b >> 4] >> (2 * (b & 15))) & 3u) != kRegOut;
+            if (any) work.push_back(t);
+        }
+        n_work = (uint32_t)work.size();
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    vsc_guides *g = new (std::nothrow) vsc_guides();
+    if (!g) return fail(ctx, VSC_ERR_NOMEM, "vsc_guides_enumerate: out of host memory");
+    std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> holder(g, vsc_guides_free);
+    g->ctx = ctx;
+    unsigned long long total = 0;
+    if (n_work) {
+        // scratch: [work list][counts][offsets], 256-byte aligned parts
+        const size_t list_bytes = ((size_t)n_work * sizeof(uint32_t) + 255) / 256 * 256;
+        VSC_HIP(ctx, ctx->enum_tabs.ensure(2 * list_bytes + ((size_t)n_work + 1) * sizeof(unsigned long long)));
+        char *base = (char *)ctx->enum_tabs.p;
+        unsigned long long *d_off = (unsigned long long *)(base + 2 * list_bytes);
+        if (regions) {
+            VSC_HIP(ctx, hipMemcpyAsync(base, work.data(), (size_t)n_work * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            a.work = (const uint32_t *)base;
+        }
+        a.n_work = n_work;
+        a.tile_count = (uint32_t *)(base + list_bytes);
+        a.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        VSC_HIP(ctx, launch_enum(a, false, regions != nullptr, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list above is this call's vector)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+        t.passes = 1;
+        if (params->max_guides && total > params->max_guides) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "vsc_guides_enumerate: %llu candidates exceed max_guides = %llu", total,
+                          (unsigned long long)params->max_guides);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        if (total) {
+            g->loci_at = ((size_t)total * sizeof(uint64_t) + 255) / 256 * 256;
+            VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
+            a.codes = (unsigned long long *)g->storage.p;
+            a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+            VSC_HIP(ctx, launch_enum(a, true, regions != nullptr, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+            t.passes = 2;
+        }
+    }
+    g->n = total;
+    if (total == 0) g->host_valid = true;
+    t.total_ms = t.scan_ms;
+    t.sites = total;
+    ctx->timing = t;
+    *out = holder.release();
+    return VSC_OK;
+    });
+}
+
+uint64_t vsc_guides_count(const vsc_guides *guides) { return guides ? guides->n : 0; }
+
+int vsc_guides_data(vsc_guides *guides, const uint64_t **codes, const vsc_locus **loci)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    return guarded(guides->ctx, [&]() -> int {
+    if (!guides->host_valid) {
+        vsc_ctx *ctx = guides->ctx;
+        guides->codes.resize(guides->n);
+        guides->loci.resize(guides->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->codes.data(), guides->storage.p, guides->n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->loci.data(), (const char *)guides->storage.p + guides->loci_at, guides->n * sizeof(vsc_locus),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        guides->host_valid = true;
+    }
+    if (codes) *codes = guides->codes.data();
+    if (loci) *loci = guides->loci.data();
+    return VSC_OK;
+    });
+}
+
+int vsc_guides_data_dev(const vsc_guides *guides, const void **codes_dev, const void **loci_dev)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    const bool dev = guides->ctx && guides->n && guides->storage.p;
+    if (codes_dev) *codes_dev = dev ? guides->storage.p : nullptr;
+    if (loci_dev) *loci_dev = dev ? (const char *)guides->storage.p + guides->loci_at : nullptr;
+    return VSC_OK;
+}
+
+int vsc_guides_free(vsc_guides *guides)
+{
+    if (!guides) return VSC_OK;
+    if (guides->ctx && guides->storage.p) {
+        (void)hipSetDevice(guides->ctx->device);
+        guides->storage.release();
+    }
+    delete guides;
+    return VSC_OK;
 }
 
 double vsc_mit_specificity(uint64_t mit_sum)

@@ -926,6 +926,68 @@ int vsc_multi_search_summary_regions(vsc_multi *m, const vsc_multi_genome *g, co
     return multi_summary(m, g, guides, n_guides, params, exclude, regions, out_all, out_in, "vsc_multi_search_summary_regions");
 }
 
+// Every shard enumerates the windows that start in its own words; shards ascend in position, so their arrays in shard order
+// are the whole genome's result.  No record moves between devices: the arrays go to the host and are joined there.
+int vsc_multi_guides_enumerate(vsc_multi *m, const vsc_multi_genome *g, const vsc_regions *regions, const vsc_enum_params *params,
+                               vsc_guides **out)
+{
+    return mguarded(m, [&]() -> int {
+    if (!m || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    m->err.clear();
+    if (!g || g->multi != m || !params) return mfail(m, VSC_ERR_INVALID, "vsc_multi_guides_enumerate: null argument");
+    const auto t0 = clk::now();
+    const size_t n = m->ctx.size();
+    std::vector<int> rc(n, VSC_OK);
+    std::vector<vsc_guides *> part(n, nullptr);
+    struct FreeParts {
+        std::vector<vsc_guides *> &p;
+        ~FreeParts()
+        {
+            for (vsc_guides *x : p) vsc_guides_free(x);
+        }
+    } free_parts{part};
+    std::vector<const uint64_t *> codes(n, nullptr);
+    std::vector<const vsc_locus *> loci(n, nullptr);
+    on_all(n, [&](size_t r) {
+        if (!g->shard[r]) return;  // (a small genome: this shard owns no words of it; some shard always does)
+        rc[r] = vsc_guides_enumerate(m->ctx[r], g->shard[r], regions, params, &part[r]);
+        if (rc[r] == VSC_OK) rc[r] = vsc_guides_data(part[r], &codes[r], &loci[r]);
+    });
+    for (size_t r = 0; r < n; ++r)
+        if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
+    const double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    uint64_t total = 0;
+    for (size_t r = 0; r < n; ++r) total += vsc_guides_count(part[r]);
+    if (params->max_guides && total > params->max_guides)
+        return mfail(m, VSC_ERR_RANGE, "vsc_multi_guides_enumerate: " + std::to_string(total) + " candidates exceed max_guides = " +
+                                           std::to_string(params->max_guides));
+    std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> res(new vsc_guides(), vsc_guides_free);
+    res->codes.reserve(total);
+    res->loci.reserve(total);
+    vsc_multi_timing mt{};
+    for (size_t r = 0; r < n; ++r) {
+        if (!part[r]) continue;
+        const uint64_t k = vsc_guides_count(part[r]);
+        res->codes.insert(res->codes.end(), codes[r], codes[r] + k);
+        res->loci.insert(res->loci.end(), loci[r], loci[r] + k);
+        vsc_timing t{};
+        (void)vsc_ctx_timing(m->ctx[r], &t);
+        mt.search_ms_max = std::max(mt.search_ms_max, t.total_ms);
+    }
+    res->n = total;
+    res->host_valid = true;
+    mt.search_wall_ms = wall;
+    mt.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    mt.n_devices = (uint32_t)n;
+    mt.used_rccl = 0;
+    mt.batches = 1;
+    m->timing = mt;
+    *out = res.release();
+    return VSC_OK;
+    });
+}
+
 int vsc_multi_search_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                             const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
                             vsc_guide_summary *summary, vsc_hits **out)

@@ -85,6 +85,8 @@ struct vsc_ctx {
     // context used last - start[], end_max[], class table in one buffer - keyed by the serial number of the vsc_regions
     vsc::DeviceBuf sum_rows_in, regions_buf;
     uint64_t regions_serial = 0;  // 0: none resident
+    // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan
+    vsc::DeviceBuf enum_tabs;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -158,6 +160,17 @@ struct vsc_hits {
     bool host_valid = false;
 };
 
+// The candidates of vsc_guides_enumerate: two device arrays the object owns (ctx != null), or host arrays only
+// (vsc_multi_guides_enumerate: ctx == null, host_valid from the start).
+struct vsc_guides {
+    vsc_ctx *ctx = nullptr;
+    vsc::DeviceBuf storage;  // codes (n x 8 bytes), then the loci (n x 16 bytes) from loci_at on
+    size_t loci_at = 0;
+    uint64_t n = 0;
+    std::vector<uint64_t> codes;
+    std::vector<vsc_locus> loci;
+    bool host_valid = false;
+};
 
 namespace vsc {
 // A genome object that only carries the contig table (no planes, nothing to search): what vsc_hits_merge_packed
