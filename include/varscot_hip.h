@@ -336,6 +336,38 @@ void vsc_regions_free(vsc_regions *r);
 int vsc_regions_contains(const vsc_regions *r, uint32_t contig, uint32_t pos);
 int vsc_regions_info(const vsc_regions *r, vsc_regions_stats *out);
 /*
+ * Labels: WHICH interval is a window in?  The LABEL of the window that starts at (contig, pos) under a vsc_regions is the
+ * index, in the caller's iv[] array as it was passed to vsc_regions_build, of one interval the window is in under the set's
+ * rule (it shares a base with it / lies fully inside it).  Dropped empty intervals still count in the numbering: the index
+ * addresses the caller's own table of names.  If no interval qualifies the label is VSC_REGION_NONE.  When several qualify
+ * the label is the most specific one:
+ *   1. the one with the largest start;
+ *   2. among those, the one with the smallest (clipped) end;
+ *   3. among those, the one with the lowest input index.
+ * With genes and their exons in one BED file a hit in an exon is labelled with the exon and a hit in an intron with the gene;
+ * exact duplicates resolve to the first one given.  For every (contig, pos) of the genome
+ *   vsc_regions_locate(r, contig, pos) != VSC_REGION_NONE  <=>  vsc_regions_contains(r, contig, pos) == 1,
+ * the cut-off windows at a contig's end that the host call allows included.
+ * vsc_regions_locate: host only, no device needed; VSC_REGION_NONE also for r == NULL, a contig or position outside the
+ * genome, and a set of more than 0xFFFFFFFE input intervals (labels are 32-bit: such a set is built without the label
+ * structure, and the two calls below return VSC_ERR_RANGE for it).
+ * vsc_hits_locate / vsc_guides_locate: labels[i] = the label of record / candidate i, computed on the device over the
+ * object's own arrays where they lie, by one gather kernel (class table, binary search over the sorted starts, a walk over
+ * the enclosing intervals whose length is bounded by the nesting depth of the annotation, not by its size); labels: host
+ * memory, vsc_hits_count / vsc_guides_count entries.  A record whose contig is outside the regions' contig table, or whose
+ * window does not lie wholly inside its contig, gets VSC_REGION_NONE.  vsc_hits_locate runs on the hits' own context - for a
+ * merged multi-device result that is the result context (vsc_multi_result_ctx).  vsc_guides_locate labels the host-only
+ * object of vsc_multi_guides_enumerate on the host.  The context keeps the device copy of the label structure of the regions
+ * it located against last, beside the copy the sinks use (uploaded on first use, given back by vsc_ctx_release_scratch); a
+ * caller who never asks for labels uploads nothing.  Neither call changes the object it labels, the order of anything, or
+ * what vsc_ctx_timing reports.  n == 0: VSC_OK, nothing is launched.  A NULL argument: VSC_ERR_INVALID.
+ * Replaces: the per-off-target annotation lookup CRISPOR reports as locusDesc ("exon:FANCF", "intron:ELAVL2";
+ * workflow/pipeline-comparison), and the host-side join of vsc_guides_enumerate's candidates back to the target intervals
+ * they came from ("the four best guides per gene").
+ */
+#define VSC_REGION_NONE 0xFFFFFFFFu
+uint32_t vsc_regions_locate(const vsc_regions *r, uint32_t contig, uint32_t pos);
+/*
  * vsc_search_summary with a second set of rows: out_all = exactly what vsc_search_summary writes for the same arguments,
  * out_in = the same fields over the counted hits that are in the regions (on_target as in out_all: the excluded locus is
  * counted in neither).  One search, one pass of the summary kernel over the records where they lie; positions are global, so
@@ -418,6 +450,9 @@ int vsc_guides_data(vsc_guides *guides, const uint64_t **codes, const vsc_locus 
  * result is empty. */
 int vsc_guides_data_dev(const vsc_guides *guides, const void **codes_dev, const void **loci_dev);
 int vsc_guides_free(vsc_guides *guides);
+/* The labels of a result's records / of the candidates under `regions` (see vsc_regions_locate above). */
+int vsc_hits_locate(vsc_hits *hits, const vsc_regions *regions, uint32_t *labels);
+int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *labels);
 /* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
  * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
 double vsc_mit_specificity(uint64_t mit_sum);

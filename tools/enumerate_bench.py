@@ -2,6 +2,7 @@
 
     python tools/enumerate_bench.py                       both cases, JSON to profiles/enumerate.json (and stdout)
     python tools/enumerate_bench.py --case regions --calls 1 --warmup 1     (what a kernel trace needs)
+    python tools/enumerate_bench.py --locate              the labelling of the exon-like candidates, JSON to profiles/locate.json
 
 Cases
   genome   every candidate of the whole genome: NGG, both strands, no filter, no regions
@@ -14,6 +15,10 @@ the hipMalloc of the result, which the context cannot pool: the caller owns it) 
 Reported beside them: candidates, the BYTE FLOOR from the shapes - plane bytes read per pass (vsc_timing.genome_bytes: 768
 bytes per visited tile and pass) + 24 bytes written per candidate - and floor / kernel time against the copy bandwidths DESIGN
 8 item 3 records for this part (library device-to-device copy 4.56 TB/s, float4 copy kernel 6.3 TB/s).
+--locate: the candidates of the exon-like annotation (overlap, no filter) stay on the device and vsc_guides_locate labels them
+against the same annotation: the first call (it uploads the label structure: 12 bytes per interval), then W warm-up and K timed
+calls - host wall time per call, which holds the kernel and the copy of 4 bytes per candidate to the host; the library's own
+laps (upload / kernel / copy, vsc_debug_set_host_timing) go to stderr beside it.  Floor: 16 bytes read + 4 written per record.
 """
 import argparse
 import ctypes as C
@@ -21,6 +26,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -65,6 +72,34 @@ def measure(ctx, genome, regions, params, calls, warmup):
     return out
 
 
+def measure_locate(ctx, genome, regions, params, calls, warmup):
+    """vsc_guides_locate over the candidates of `regions`, labelled against `regions`"""
+    L = va.lib()
+    h = C.c_void_p()
+    _lib.check(L.vsc_guides_enumerate(ctx._h, genome._h, regions._h, C.byref(params), C.byref(h)), ctx._h)
+    n = int(L.vsc_guides_count(h))
+    labels = np.empty(n, dtype=np.uint32)
+
+    def call():
+        t0 = time.perf_counter()
+        _lib.check(L.vsc_guides_locate(h, regions._h, _lib.ptr(labels)), ctx._h)
+        return (time.perf_counter() - t0) * 1e3
+
+    L.vsc_debug_set_host_timing(1)
+    first = call()
+    for _ in range(warmup):
+        call()
+    wall = sorted(call() for _ in range(calls))
+    L.vsc_debug_set_host_timing(0)
+    L.vsc_guides_free(h)
+    floor = 20 * n
+    out = {"records": n, "labelled": int((labels != va.REGION_NONE).sum()), "floor_bytes": floor, "first_call_ms": first,
+           "wall_ms": wall, "upload_bytes": 12 * regions.info()["intervals"]}
+    for name, tbs in COPY_TBS.items():
+        out["floor_ms_at_" + name] = floor / (tbs * 1e12) * 1e3
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--case", default="both", choices=["genome", "regions", "both"])
@@ -73,8 +108,11 @@ def main():
     ap.add_argument("--bases", type=int, default=3_000_000_000, help="genome size (default: the hg38-sized synthetic genome)")
     ap.add_argument("--intervals", type=int, default=250_000)
     ap.add_argument("--fraction", type=float, default=0.03)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "enumerate.json"))
+    ap.add_argument("--locate", action="store_true", help="time vsc_guides_locate over the exon-like candidates instead")
+    ap.add_argument("--out", default=None, help="default: profiles/enumerate.json (--locate: profiles/locate.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "locate.json" if args.locate else "enumerate.json")
     table, _ = synth.contig_table(args.bases)
     span = int(table[-1]["offset"]) + int(table[-1]["length"]) + 1
     n_words = (span + 31) // 32
@@ -85,6 +123,14 @@ def main():
     del hi, lo, nm
     res = {"genome_bases": args.bases, "calls": args.calls, "warmup": args.warmup, "copy_tb_per_s": COPY_TBS, "cases": {}}
     plain = _enum_params("GG", "both", (0, 0), 0, 0)
+    if args.locate:
+        args.case = "locate"
+        iv = synth.synthetic_regions(table, args.intervals, args.fraction)
+        regions = va.Regions(va.PackedGenome(None, None, None, table), iv, rule="overlap")
+        res["cases"]["guides_locate_overlap"] = dict(measure_locate(ctx, genome, regions, plain, args.calls, args.warmup),
+                                                     intervals=args.intervals, fraction=args.fraction)
+        print(json.dumps(res["cases"]), flush=True)
+        regions.close()
     if args.case in ("genome", "both"):
         res["cases"]["genome_NGG_both_strands"] = measure(ctx, genome, None, plain, args.calls, args.warmup)
         print(json.dumps({"genome_NGG_both_strands": res["cases"]["genome_NGG_both_strands"]}), flush=True)

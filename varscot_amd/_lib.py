@@ -48,6 +48,7 @@ assert C.sizeof(Select) == 16
 INTERVAL_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4")])
 REGION_OVERLAP, REGION_INSIDE = 0, 1
 REGION_KEEP, REGION_DROP = 0, 1
+REGION_NONE = 0xFFFFFFFF  # VSC_REGION_NONE: the label of a window that is in no interval
 
 
 class RegionFilter(C.Structure):
@@ -177,6 +178,9 @@ SYMBOLS = [
     ("vsc_guides_data", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     ("vsc_guides_data_dev", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     ("vsc_guides_free", C.c_int, [_vp]),
+    ("vsc_regions_locate", C.c_uint32, [_vp, C.c_uint32, C.c_uint32]),
+    ("vsc_hits_locate", C.c_int, [_vp, _vp, _vp]),
+    ("vsc_guides_locate", C.c_int, [_vp, _vp, _vp]),
     ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),

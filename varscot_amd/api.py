@@ -51,18 +51,38 @@ def _enum_params(pam, strands, gc, max_t_run, max_guides):
     return p
 
 
-def _guides_arrays(handle, check_fn):
-    """(codes uint64[n], loci LOCUS_DTYPE[n]) copied out of a vsc_guides, which is freed."""
+def _label_regions(labels, regions):
+    """The Regions that enumerate_guides' labels= option asks to label against: None (labels=False), `regions` (labels=True)
+    or the Regions given as labels= itself."""
+    if labels is None or labels is False:
+        return None
+    if labels is True:
+        if regions is None:
+            raise ValueError("labels=True labels the candidates with the interval of `regions` they lie in: give regions")
+        return regions
+    if not isinstance(labels, Regions):
+        raise ValueError("labels must be False, True or a Regions")
+    return labels
+
+
+def _guides_arrays(handle, check_fn, label_regions=None):
+    """(codes uint64[n], loci LOCUS_DTYPE[n]) copied out of a vsc_guides, which is freed - with label_regions also the
+    candidates' labels under those regions (uint32[n], vsc_guides_locate), taken before the handle goes."""
     L = lib()
     try:
         n = int(L.vsc_guides_count(handle))
         pc, pl = C.c_void_p(), C.c_void_p()
         check_fn(L.vsc_guides_data(handle, C.byref(pc), C.byref(pl)))
         if n == 0:
-            return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=_lib.LOCUS_DTYPE)
-        codes = np.frombuffer((C.c_char * (n * 8)).from_address(pc.value), dtype=np.uint64).copy()
-        loci = np.frombuffer((C.c_char * (n * 16)).from_address(pl.value), dtype=_lib.LOCUS_DTYPE).copy()
-        return codes, loci
+            codes, loci = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=_lib.LOCUS_DTYPE)
+        else:
+            codes = np.frombuffer((C.c_char * (n * 8)).from_address(pc.value), dtype=np.uint64).copy()
+            loci = np.frombuffer((C.c_char * (n * 16)).from_address(pl.value), dtype=_lib.LOCUS_DTYPE).copy()
+        if label_regions is None:
+            return codes, loci
+        labels = np.full(n, _lib.REGION_NONE, dtype=np.uint32)
+        check_fn(L.vsc_guides_locate(handle, label_regions._h, ptr(labels)))
+        return codes, loci, labels
     finally:
         L.vsc_guides_free(handle)
 
@@ -136,6 +156,11 @@ class Regions:
     def contains(self, contig, pos):
         """Is the window that starts at (contig, pos) in the regions?  (vsc_regions_contains, on the host)"""
         return bool(lib().vsc_regions_contains(self._h, int(contig), int(pos)))
+
+    def locate(self, contig, pos):
+        """The label of the window that starts at (contig, pos): the index in `intervals` of the most specific interval it is
+        in - largest start, then smallest end, then first given - or REGION_NONE.  (vsc_regions_locate, on the host)"""
+        return int(lib().vsc_regions_locate(self._h, int(contig), int(pos)))
 
     def info(self):
         """vsc_regions_info: intervals kept, rule, block_bases and the class table's blocks_out / blocks_in / blocks_mixed."""
@@ -427,26 +452,34 @@ class Genome:
         hits = Hits(self, h, codes)
         return (hits, rows, inside) if summary else hits
 
-    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None):
+    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
+                         labels=False):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
         than max_t_run T in them (0: no limit).  Returns (codes uint64[n], loci LOCUS_DTYPE[n]) in ascending (contig, pos),
         '+' before '-': codes are what every search takes, loci what `exclude` takes.  More than max_guides (0: no cap)
-        candidates raise VarscotError -34.  params: an EnumParams to pass as it is (tests)."""
+        candidates raise VarscotError -34.  params: an EnumParams to pass as it is (tests).
+        labels=True (needs regions; or labels=another Regions): returns (codes, loci, labels uint32[n]) - per candidate the
+        index of the interval it lies in, REGION_NONE if none, as Regions.locate gives it (vsc_guides_locate, on the device)."""
+        lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         h = C.c_void_p()
         check(lib().vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        return _guides_arrays(h, lambda code: check(code, self.ctx._h))
+        return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
 
-    def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, **search_options):
+    def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
+               **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
-        A PAM other than GG / GA needs extra_pam=pam among the search options for the guide's own locus to be a hit."""
-        codes, loci = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides)
-        return codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)
+        A PAM other than GG / GA needs extra_pam=pam among the search options for the guide's own locus to be a hit.
+        labels: as enumerate_guides; the labels then come last: (codes, loci, rows, labels)."""
+        found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
+                                      labels=labels)
+        codes, loci = found[0], found[1]
+        return (codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)) + tuple(found[2:])
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)
@@ -531,6 +564,13 @@ class Hits:
             return np.zeros(0, dtype=HIT_DTYPE)
         buf = (C.c_char * (n * HIT_DTYPE.itemsize)).from_address(p.value)
         return np.frombuffer(buf, dtype=HIT_DTYPE).copy()
+
+    def locate(self, regions):
+        """vsc_hits_locate: per record the index of the interval of `regions` its window is in (uint32[len(self)], REGION_NONE:
+        in none), as Regions.locate gives it - computed on the device over the records where they lie."""
+        labels = np.full(len(self), _lib.REGION_NONE, dtype=np.uint32)
+        check(lib().vsc_hits_locate(self._h, regions._h, ptr(labels)), self.ctx._h)
+        return labels
 
     def copy_to(self, dst_ptr, dst_is_device):
         """Copy the records to caller memory (e.g. the data_ptr() of a uint8 tensor handed to RCCL)."""
@@ -771,14 +811,16 @@ class MultiGenome:
             return res
         return (res, rows) if flt is None else (res, rows, inside)
 
-    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None):
+    def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
+                         labels=False):
         """vsc_multi_guides_enumerate: Genome.enumerate_guides over the shards, their arrays joined in shard order on the
-        host - the same bytes as one device gives."""
+        host - the same bytes as one device gives (the labels of labels= too: looked up on the host)."""
+        lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         h = C.c_void_p()
         self.multi._check(lib().vsc_multi_guides_enumerate(self.multi._h, self._h, regions._h if regions is not None else None,
                                                            C.byref(p), C.byref(h)))
-        return _guides_arrays(h, self.multi._check)
+        return _guides_arrays(h, self.multi._check, lab)
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

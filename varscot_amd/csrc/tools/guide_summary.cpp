@@ -29,6 +29,11 @@
 // to that side.  With -A and -T but no -X the genome is searched twice: the unfiltered listing (vsc_search_select_regions
 // takes region rows only beside a filter) and then the region rows (vsc_search_summary_regions); with -X one search gives
 // both.  Without -A the output is what it was.
+// -N name|coords names the interval a listed hit or a found guide lies in (vsc_hits_locate / vsc_guides_locate: of the intervals
+// it is in, the one with the largest start, then the smallest end, then the first in the file - the exon before its gene):
+// with -A and -T the -T file gains a last column `region`, with -E and -L every -L line a 7th column.  name prints the 4th
+// column of that BED line, or chrom:start-end as the line has them if it has only three; coords always the latter; - if the
+// hit is in no interval.  Without -N every output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -68,6 +73,8 @@ int main(int argc, char **argv)
         {'t', "t-run", "Keep -E candidates whose longest run of T in the protospacer is at most this, 0 .. 20 (0, the default: no limit; 3 drops TTTT)", false},
         {'s', "strands", "+ | - | both (default): strands on which -E looks for guides", false},
         {'L', "list-guides", "Path to a BED6 file (.bed) that receives the -E candidates: chrom start end guideId 0 strand", false},
+        {'N', "region-names", "name | coords: add the interval a hit lies in to the -T file (of the -A regions) and the interval a guide "
+                              "was found in to the -L file (of the -E targets), as the BED line's 4th column or as chrom:start-end", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -214,6 +221,18 @@ int main(int argc, char **argv)
         }
         ep.strands = v == "+" ? 1 : v == "-" ? 2 : 0;
     }
+    const bool naming = opts[21].set;
+    if (naming) {
+        if (opts[21].value != "name" && opts[21].value != "coords") {
+            std::fprintf(stderr, "%s: -N takes name or coords, not '%s'\n", argv[0], opts[21].value.c_str());
+            return 1;
+        }
+        if (!(annotated && listing) && !(discover && opts[20].set)) {
+            std::fprintf(stderr, "%s: -N names the -A interval of a hit in the -T file or the -E interval of a guide in the -L file: give -A and -T, or -E and -L\n", argv[0]);
+            return 1;
+        }
+    }
+    const bool by_name = naming && opts[21].value == "name";
     std::vector<int> devices;  // -D 0 | -D 0,1,2,3 (an id may repeat: several shards on one device)
     {
         const std::string d = opts[7].set ? opts[7].value : "0";
@@ -249,7 +268,8 @@ int main(int argc, char **argv)
             throw std::runtime_error("index " + index_path(index_prefix) + " was not packed from " + genome_path);
         std::map<std::string, uint32_t> by_chrom;  // first word of the contig name, as the -T file prints it
         for (size_t c = ix.names.size(); c-- > 0;) by_chrom[ix.names[c].substr(0, ix.names[c].find_first_of(" \t"))] = (uint32_t)c;
-        auto read_bed3 = [&](const std::string &path, const std::string &flag) {  // the intervals of a BED3+ file (-A, -E)
+        // the intervals of a BED3+ file (-A, -E); desc (-N): what names each of them - its 4th column or chrom:start-end as given
+        auto read_bed3 = [&](const std::string &path, const std::string &flag, std::vector<std::string> *desc) {
             std::ifstream bed(path);
             if (!bed) throw std::runtime_error("Could not open the " + flag + " file.");
             std::vector<vsc_interval> iv;
@@ -264,14 +284,20 @@ int main(int argc, char **argv)
                 if (it == by_chrom.end()) throw std::runtime_error(flag + ": no sequence '" + chr + "' in the genome");
                 if (start > stop || stop > 0xFFFFFFFFull) throw std::runtime_error(flag + ": bad interval in '" + line + "'");
                 iv.push_back(vsc_interval{it->second, (uint32_t)start, (uint32_t)stop, 0u});
+                if (desc) {
+                    std::string name;
+                    if (!by_name || !(is >> name)) name = chr + ':' + std::to_string(start) + '-' + std::to_string(stop);
+                    desc->push_back(name);
+                }
             }
             return iv;
         };
         // the guides (+ their excluded loci)
         std::vector<std::string> ids, seqs;
         std::vector<vsc_locus> loci;
+        std::vector<std::string> region_desc, target_desc;  // -N: per line of the -A / -E file
         if (discover) {  // the guides themselves come from the device, below
-            const std::vector<vsc_interval> iv = read_bed3(targets_path, "-E");
+            const std::vector<vsc_interval> iv = read_bed3(targets_path, "-E", naming && opts[20].set ? &target_desc : nullptr);
             if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), target_rule, &targets) != VSC_OK)
                 throw std::runtime_error("could not build the regions of the -E file");
             std::fprintf(stderr, "Targets loaded (total: %zu).\n", iv.size());
@@ -307,7 +333,7 @@ int main(int argc, char **argv)
         }
         if (!discover) std::fprintf(stderr, "Guides loaded (total: %zu).\n", seqs.size());
         if (annotated) {
-            const std::vector<vsc_interval> iv = read_bed3(regions_path, "-A");
+            const std::vector<vsc_interval> iv = read_bed3(regions_path, "-A", naming && listing ? &region_desc : nullptr);
             if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), region_rule, &regions) != VSC_OK)
                 throw std::runtime_error("could not build the regions of the -A file");
             filter.regions = regions;
@@ -349,6 +375,9 @@ int main(int argc, char **argv)
             if (n >= (1ull << 31)) throw std::runtime_error("-E: too many candidates for one search; narrow the targets or the filters");
             codes.assign(fc, fc + n);
             loci.assign(fl, fl + n);
+            std::vector<uint32_t> from(target_desc.empty() ? 0 : n);  // -N: the -E interval each candidate lies in
+            if (!from.empty() && (st = vsc_guides_locate(found, targets, from.data())) != VSC_OK)
+                throw std::runtime_error(multi || st == VSC_ERR_RANGE ? "could not name the targets of the candidates" : vsc_last_error(ctx));
             std::string bed6;
             for (uint64_t i = 0; i < n; ++i) {
                 const std::string &name = ix.names[fl[i].contig];
@@ -360,7 +389,7 @@ int main(int argc, char **argv)
                 seqs.push_back(seq);
                 if (opts[20].set)
                     bed6 += chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
-                            "\t0\t" + strand + '\n';
+                            "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) + '\n';
             }
             if (opts[20].set) {
                 std::ofstream out(guides_bed_path);
@@ -474,7 +503,12 @@ int main(int argc, char **argv)
                 if (rec[a].guide != rec[b].guide) return rec[a].guide < rec[b].guide;
                 return score[a] > score[b];
             });
-            std::string list = "#guideId\trank\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tmitScore\tsequence\n";
+            const bool named = naming && annotated;  // -N: the -A interval each record lies in
+            std::vector<uint32_t> in(named ? n : 0);
+            if (named && n && (st = vsc_hits_locate(hits, regions, in.data())) != VSC_OK)
+                throw std::runtime_error(st == VSC_ERR_RANGE ? "could not name the regions of the hits" : vsc_last_error(hctx));
+            std::string list = std::string("#guideId\trank\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tmitScore\tsequence") +
+                               (named ? "\tregion\n" : "\n");
             std::string window(VSC_READ_LEN, 'N');
             uint32_t rank = 0;
             for (uint64_t j = 0; j < n; ++j) {
@@ -488,7 +522,8 @@ int main(int argc, char **argv)
                 std::snprintf(buf, sizeof buf, "%.6f", (double)score[order[j]] * 0x1p-24);
                 list += ids[h.guide] + '\t' + std::to_string(rank) + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' +
                         std::to_string(h.pos) + '\t' + std::to_string(h.pos + VSC_READ_LEN) + '\t' + (VSC_HIT_STRAND(h.info) ? '-' : '+') + '\t' +
-                        std::to_string(VSC_HIT_NM(h.info)) + '\t' + (positions.empty() ? "-" : positions) + '\t' + buf + '\t' + window + '\n';
+                        std::to_string(VSC_HIT_NM(h.info)) + '\t' + (positions.empty() ? "-" : positions) + '\t' + buf + '\t' + window +
+                        (named ? '\t' + (in[order[j]] < region_desc.size() ? region_desc[in[order[j]]] : "-") : "") + '\n';
             }
             std::ofstream out(hits_path);
             if (!out.is_open()) throw std::runtime_error("Could not open the -T path.");

@@ -213,9 +213,10 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
-                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs})
+                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out})
         b->release();
     ctx->regions_serial = 0;
+    ctx->locate_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
     ctx->forest.nodes.release();
@@ -1830,15 +1831,10 @@ int upload_summary_state(vsc_ctx *ctx, uint32_t n_guides, bool rows, const std::
     return VSC_OK;
 }
 
-// The device copy of `regions` on this context (`who`: the caller, for error texts): the context keeps the copy of the regions
-// it used last, keyed by their serial number; another set is uploaded over it on the context's stream.  The regions must
-// have been built for the genome's contig table.
-int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const char *who, RegionsView &dev)
+// The device copy of `regions` on this context: the context keeps the copy of the regions it used last, keyed by their serial
+// number; another set is uploaded over it on the context's stream.
+int upload_regions(vsc_ctx *ctx, const vsc_regions *regions, RegionsView &dev)
 {
-    bool same = regions->contig_off.size() == genome->n_contigs;
-    for (uint32_t c = 0; same && c < genome->n_contigs; ++c)  // (the genome's host copy of its table: no device read per call)
-        same = genome->h_contig_off[c] == regions->contig_off[c] && genome->h_contig_end[c] - genome->h_contig_off[c] == regions->contig_len[c];
-    if (!same) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": the regions were built for another contig table").c_str());
     const size_t n = regions->start.size(), cls_at = (2 * n * sizeof(uint32_t) + 255) / 256 * 256;
     if (ctx->regions_serial != regions->serial) {
         ctx->regions_serial = 0;
@@ -1857,6 +1853,69 @@ int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *
     dev.start = (const uint32_t *)p;
     dev.end_max = (const uint32_t *)p + n;
     dev.cls = (const uint32_t *)(p + cls_at);
+    return VSC_OK;
+}
+
+// upload_regions for a call that takes a genome (`who`: the caller, for error texts): the regions must have been built for
+// the genome's contig table.
+int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const char *who, RegionsView &dev)
+{
+    bool same = regions->contig_off.size() == genome->n_contigs;
+    for (uint32_t c = 0; same && c < genome->n_contigs; ++c)  // (the genome's host copy of its table: no device read per call)
+        same = genome->h_contig_off[c] == regions->contig_off[c] && genome->h_contig_end[c] - genome->h_contig_off[c] == regions->contig_len[c];
+    if (!same) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": the regions were built for another contig table").c_str());
+    return upload_regions(ctx, regions, dev);
+}
+
+// The labels of n 16-byte records on ctx's device (vsc_hit or vsc_locus) into host memory: the regions' copy the sinks use
+// (start[], class table), beside it the label structure - end[], index[], up[], the contig offsets and lengths the regions
+// were built for, in one buffer keyed by the regions' serial number as regions_buf is - then locate_kernel and one copy back.
+// The context's timing is left as it is.
+int locate_records(vsc_ctx *ctx, const vsc_regions *regions, const void *records, uint64_t n, bool hit_records, uint32_t *labels,
+                   const char *who)
+{
+    ctx->err.clear();
+    if (!regions->has_locate) return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": the regions hold more intervals than a 32-bit label can number").c_str());
+    HostTimer lap;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    LocateArgs a{};
+    const int urc = upload_regions(ctx, regions, a.reg);
+    if (urc != VSC_OK) return urc;
+    const size_t m = regions->loc_end.size(), nc = regions->contig_off.size();
+    if (ctx->locate_serial != regions->serial) {
+        ctx->locate_serial = 0;
+        VSC_HIP(ctx, ctx->locate_buf.ensure((3 * m + 2 * nc + 1) * sizeof(uint32_t)));  // (+ 1: never empty)
+        uint32_t *p = (uint32_t *)ctx->locate_buf.p;
+        if (m) {
+            VSC_HIP(ctx, hipMemcpyAsync(p, regions->loc_end.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(p + m, regions->loc_index.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(p + 2 * m, regions->loc_up.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+        if (nc) {
+            VSC_HIP(ctx, hipMemcpyAsync(p + 3 * m, regions->contig_off.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(p + 3 * m + nc, regions->contig_len.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the regions as soon as its call returns)
+        ctx->locate_serial = regions->serial;
+    }
+    lap.lap("locate: tables resident");
+    const uint32_t *p = (const uint32_t *)ctx->locate_buf.p;
+    a.loc = LocateView{p, p + m, p + 2 * m};
+    a.contig_off = p + 3 * m;
+    a.contig_len = p + 3 * m + nc;
+    a.n_contigs = (uint32_t)nc;
+    a.records = (const uint4 *)records;
+    a.n = n;
+    VSC_HIP(ctx, ctx->locate_out.ensure(n * sizeof(uint32_t)));
+    a.labels = (uint32_t *)ctx->locate_out.p;
+    VSC_HIP(ctx, launch_locate(a, hit_records, ctx->n_cus, ctx->stream));
+    if (lap.on) {
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        lap.lap("locate: kernel");
+    }
+    VSC_HIP(ctx, hipMemcpyAsync(labels, a.labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    lap.lap("locate: labels to the host");
     return VSC_OK;
 }
 
@@ -2271,6 +2330,35 @@ int vsc_guides_free(vsc_guides *guides)
     }
     delete guides;
     return VSC_OK;
+}
+
+int vsc_hits_locate(vsc_hits *hits, const vsc_regions *regions, uint32_t *labels)
+{
+    if (!hits || !regions || (hits->n && !labels)) return VSC_ERR_INVALID;
+    if (hits->n == 0) return VSC_OK;
+    return guarded(hits->ctx, [&]() -> int {
+    return locate_records(hits->ctx, regions, hits->d_records, hits->n, true, labels, "vsc_hits_locate");
+    });
+}
+
+int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *labels)
+{
+    if (!guides || !regions || (guides->n && !labels)) return VSC_ERR_INVALID;
+    if (guides->n == 0) return VSC_OK;
+    if (!guides->ctx) {  // vsc_multi_guides_enumerate's host-only object: the same labels by the host's lookup
+        if (!regions->has_locate) return VSC_ERR_RANGE;
+        for (uint64_t i = 0; i < guides->n; ++i) {
+            const vsc_locus &l = guides->loci[i];
+            const bool whole = l.contig < regions->contig_len.size() && l.pos <= regions->contig_len[l.contig] &&
+                               regions->contig_len[l.contig] - l.pos >= (uint32_t)VSC_READ_LEN;
+            labels[i] = whole ? vsc_regions_locate(regions, l.contig, l.pos) : VSC_REGION_NONE;
+        }
+        return VSC_OK;
+    }
+    return guarded(guides->ctx, [&]() -> int {
+    return locate_records(guides->ctx, regions, (const char *)guides->storage.p + guides->loci_at, guides->n, false, labels,
+                          "vsc_guides_locate");
+    });
 }
 
 double vsc_mit_specificity(uint64_t mit_sum)

@@ -8,6 +8,9 @@
 // the same masks - enum_kernel<false> counts per tile, enum_scan_kernel turns the counts into offsets, enum_kernel<true>
 // recomputes the masks and writes every candidate at  tile offset + wave prefix over the lanes + rank inside the lane.  The
 // bytes depend on the planes and the parameters only: no atomic, no work cursor, tile i of the work list is wave i.
+//
+// At the end of the file: locate_kernel (vsc_hits_locate / vsc_guides_locate), the other reader of the regions'
+// class table outside the sinks - per record the interval of the regions its window lies in.
 #include "vsc_internal.h"
 #include "vsc_device.h"
 #include "vsc_enum.h"
@@ -197,6 +200,47 @@ hipError_t launch_enum(const EnumArgs &args, bool write, bool regions, hipStream
 hipError_t launch_enum_scan(const uint32_t *tile_count, uint32_t n, unsigned long long *tile_off, hipStream_t stream)
 {
     hipLaunchKernelGGL(enum_scan_kernel, dim3(1), dim3(1024), 0, stream, tile_count, n, tile_off);
+    return hipGetLastError();
+}
+
+// ---- labels --------------------------------------------------------------------------------------------------
+// labels[i] = the label of record i under the regions: one record per lane and step (one 16-byte load), grid-stride over the
+// 64-bit count.  A record outside the contig table, a window that leaves its contig and a start in an OUT block are
+// kLocateNone without a further read; IN and MIXED blocks take the binary search over start[] and the walk over up[]
+// (regions_locate, vsc_enum.h).  A gather bound by the latency of its dependent loads: no LDS, no atomics, one coalesced
+// 4-byte store per lane.  Every index is checked against its array's length before it is used.
+constexpr int kLocateThreads = 256;
+
+template <bool kHit>
+__global__ __launch_bounds__(kLocateThreads) void locate_kernel(const LocateArgs a)
+{
+    const unsigned long long stride = (unsigned long long)gridDim.x * kLocateThreads;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * kLocateThreads + threadIdx.x; i < a.n; i += stride) {
+        const uint4 r = a.records[i];
+        const uint32_t contig = kHit ? r.y : r.x, pos = kHit ? r.z : r.y;
+        uint32_t label = kLocateNone;
+        if (contig < a.n_contigs) {
+            const uint32_t len = a.contig_len[contig];
+            if (pos <= len && len - pos >= (uint32_t)VSC_READ_LEN) {  // pos + 23 <= len, without the overflow
+                const uint32_t g = a.contig_off[contig] + pos;
+                const uint32_t b = g >> a.reg.block_shift;
+                const uint32_t c = b < a.reg.n_blocks ? (a.reg.cls[b >> 4] >> (2u * (b & 15u))) & 3u : kRegOut;
+                if (c != kRegOut) label = regions_locate(a.reg, a.loc, g, VSC_READ_LEN);
+            }
+        }
+        a.labels[i] = label;
+    }
+}
+
+hipError_t launch_locate(const LocateArgs &args, bool hit_records, int n_cus, hipStream_t stream)
+{
+    if (args.n == 0) return hipSuccess;
+    // 8 workgroups of 4 waves per CU fill every SIMD's 8 wave slots; fewer when the records do not need them
+    const unsigned long long want = (args.n + kLocateThreads - 1) / kLocateThreads;
+    const unsigned long long cap = (unsigned long long)(n_cus > 0 ? n_cus : 256) * 8u;
+    const dim3 grid((uint32_t)(want < cap ? want : cap)), block(kLocateThreads);
+    if (hit_records) hipLaunchKernelGGL((locate_kernel<true>), grid, block, 0, stream, args);
+    else hipLaunchKernelGGL((locate_kernel<false>), grid, block, 0, stream, args);
     return hipGetLastError();
 }
 

@@ -85,6 +85,11 @@ struct vsc_ctx {
     // context used last - start[], end_max[], class table in one buffer - keyed by the serial number of the vsc_regions
     vsc::DeviceBuf sum_rows_in, regions_buf;
     uint64_t regions_serial = 0;  // 0: none resident
+    // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
+    // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
+    // way to the host
+    vsc::DeviceBuf locate_buf, locate_out;
+    uint64_t locate_serial = 0;  // 0: none resident
     // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan
     vsc::DeviceBuf enum_tabs;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
@@ -142,6 +147,10 @@ struct vsc_genome {
 struct vsc_regions {
     std::vector<uint32_t> start, end_max, cls;  // vsc::RegionsView's arrays
     std::vector<uint32_t> contig_off, contig_len;  // the genome's table the intervals were placed in
+    // vsc::LocateView's arrays (vsc_enum.h): the kept intervals by (start ascending, end descending, input index descending).
+    // has_locate == false: more input intervals than a 32-bit label can number, the three arrays are empty
+    std::vector<uint32_t> loc_end, loc_index, loc_up;
+    bool has_locate = false;
     uint32_t rule = 0, block_shift = 0, n_blocks = 0;
     uint64_t serial = 0;  // process-wide, handed out by vsc_regions_build: what a context's device copy is keyed by
     vsc_regions_stats stats{};

@@ -1,12 +1,14 @@
 // vsc_regions.cpp - the interval sets of include/varscot_hip.h (vsc_regions_*): validation, global coordinates, the sorted
 // starts with the running maximum of the ends, and the coarse class table.  Host C++ only, no device call: the membership
-// test itself is vsc::regions_contains (vsc_internal.h), which the summary and selection kernels share.
+// test itself is vsc::regions_contains (vsc_internal.h), which the summary and selection kernels share.  The label structure
+// (which interval: vsc_regions_locate) is built here as well; its lookup is vsc::regions_locate (vsc_enum.h).
 #include <algorithm>
 #include <atomic>
 #include <new>
 #include <utility>
 #include <vector>
 
+#include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
 
@@ -63,12 +65,19 @@ int vsc_regions_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_i
         }
         std::vector<std::pair<uint32_t, uint32_t>> g;  // global [start, end)
         g.reserve(n);
+        struct Numbered {
+            uint32_t start, end, index;
+        };
+        std::vector<Numbered> byspec;  // the same intervals with their place in iv[] (labels are 32-bit: not beyond 0xFFFFFFFE)
+        const bool numbered = n <= 0xFFFFFFFEull;
+        if (numbered) byspec.reserve(n);
         for (uint64_t i = 0; i < n; ++i) {
             const vsc_interval &v = iv[i];
             if (v.contig >= n_contigs || v.start > v.end || v.reserved) return VSC_ERR_INVALID;
             const uint32_t end = std::min(v.end, r->contig_len[v.contig]);
             if (v.start >= end) continue;  // empty, or beyond the contig
             g.emplace_back(r->contig_off[v.contig] + v.start, r->contig_off[v.contig] + end);
+            if (numbered) byspec.push_back(Numbered{g.back().first, g.back().second, (uint32_t)i});
         }
         std::sort(g.begin(), g.end());
         r->start.resize(g.size());
@@ -80,6 +89,30 @@ int vsc_regions_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_i
             r->end_max[i] = run;
         }
         r->rule = rule;
+        // the label structure, eagerly (the object is immutable and shared between threads): of the intervals before a bound on
+        // the start, the last one in this order whose end is large enough is the most specific one - largest start, smallest end,
+        // lowest input index.  up[k] = the previous entry with a greater end, by a monotonic stack: the entries between it and k
+        // end no later than k does, so a walk that finds end[k] too small skips them
+        if (numbered) {
+            std::sort(byspec.begin(), byspec.end(), [](const Numbered &a, const Numbered &b) {
+                if (a.start != b.start) return a.start < b.start;
+                if (a.end != b.end) return a.end > b.end;
+                return a.index > b.index;
+            });
+            const size_t m = byspec.size();
+            r->loc_end.resize(m);
+            r->loc_index.resize(m);
+            r->loc_up.resize(m);
+            std::vector<uint32_t> stack;  // entries whose ends strictly decrease
+            for (size_t k = 0; k < m; ++k) {
+                r->loc_end[k] = byspec[k].end;
+                r->loc_index[k] = byspec[k].index;
+                while (!stack.empty() && r->loc_end[stack.back()] <= byspec[k].end) stack.pop_back();
+                r->loc_up[k] = stack.empty() ? kLocateNone : stack.back();
+                stack.push_back((uint32_t)k);
+            }
+            r->has_locate = true;
+        }
         // the class table: the smallest blocks that keep it within kRegMaxBlocks
         uint32_t shift = kRegMinBlockShift;
         while (((total + (1ull << shift) - 1) >> shift) > kRegMaxBlocks) ++shift;
@@ -126,6 +159,19 @@ int vsc_regions_contains(const vsc_regions *r, uint32_t contig, uint32_t pos)
     if (!r || contig >= r->contig_len.size() || pos >= r->contig_len[contig]) return 0;
     const uint32_t left = r->contig_len[contig] - pos;  // a window at the contig's end is cut off there
     return regions_contains(r->view(), r->contig_off[contig] + pos, std::min<uint32_t>(left, VSC_READ_LEN)) ? 1 : 0;
+}
+
+uint32_t vsc_regions_locate(const vsc_regions *r, uint32_t contig, uint32_t pos)
+{
+    if (!r || !r->has_locate || contig >= r->contig_len.size() || pos >= r->contig_len[contig]) return VSC_REGION_NONE;
+    const uint32_t left = r->contig_len[contig] - pos;  // a window at the contig's end is cut off there, as in vsc_regions_contains
+    const uint32_t len = std::min<uint32_t>(left, VSC_READ_LEN), g = r->contig_off[contig] + pos;
+    const RegionsView v = r->view();
+    if (len == (uint32_t)VSC_READ_LEN) {  // (the table describes whole windows)
+        const uint32_t b = g >> v.block_shift;
+        if (b >= v.n_blocks || ((v.cls[b >> 4] >> (2u * (b & 15u))) & 3u) == kRegOut) return VSC_REGION_NONE;
+    }
+    return regions_locate(v, LocateView{r->loc_end.data(), r->loc_index.data(), r->loc_up.data()}, g, len);
 }
 
 int vsc_regions_info(const vsc_regions *r, vsc_regions_stats *out)
