@@ -1,6 +1,7 @@
 // vsc_api.cpp - the C ABI of include/varscot_hip.h: context, resident genome, search orchestration
-// (scan -> radix sort -> record assembly) and per-hit scoring.  Host C++ only; all device work is in
-// vsc_kernels.hip.  No CPU implementation of the search exists in this library: without a HIP
+// (find -> summary / selection -> bin sort, one pass loop: run_search) and per-hit scoring.  Host C++ only; all device
+// work is in the kernel files - vsc_kernels.hip (scan, summary, selection, scoring, forest, merge), vsc_seed.hip (seed
+// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels).  No CPU implementation of the search exists in this library: without a HIP
 // device every compute entry point fails with VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
 #include <atomic>
@@ -56,6 +57,9 @@ int fail(vsc_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)
     }
     return code;
 }
+
+// fail with the caller's name in front of the text: "<who>: <what>"
+int fail_in(vsc_ctx *ctx, int code, const char *who, const char *what) { return fail(ctx, code, (std::string(who) + ": " + what).c_str()); }
 
 #define VSC_HIP(ctx, call)                                                 \
     do {                                                                   \
@@ -474,7 +478,7 @@ hipError_t build_index(vsc_ctx *ctx, vsc_genome *g, const vsc_search_params *par
     VSC_TRY(ctx->counters.ensure(kCounterWords * sizeof(unsigned long long)));
     a.counters = (unsigned long long *)ctx->counters.p;
     unsigned long long cnt[kCntSlots];
-    VSC_TRY(hipEventRecord(ctx->ev[5], st));
+    VSC_TRY(hipEventRecord(ctx->ev[kEvIndexStart], st));
     // pass 1: count (capacity 0: nothing is written, the cursor still counts)
     VSC_TRY(hipMemsetAsync(ctx->counters.p, 0, sizeof cnt, st));
     VSC_TRY(launch_scan(a, n_groups, true, st));
@@ -668,7 +672,7 @@ hipError_t build_index(vsc_ctx *ctx, vsc_genome *g, const vsc_search_params *par
     step(hipMalloc((void **)&g->d_ix_vert, vb));
     if (e == hipSuccess) step(launch_seed_transpose(sites16, g->d_ix_chunk_tab, g->ix_chunks, g->d_ix_vert, st));
     if (e == hipSuccess) step(launch_seed_chunk_flags(g->d_ix_chunk_tab, g->ix_chunks, g->d_ix_edge, st));
-    step(hipEventRecord(ctx->ev[6], st));
+    step(hipEventRecord(ctx->ev[kEvIndexEnd], st));
     step(hipStreamSynchronize(st));
     ht.lap("index: chunk table, bit-sliced blocks");
     release();
@@ -677,7 +681,7 @@ hipError_t build_index(vsc_ctx *ctx, vsc_genome *g, const vsc_search_params *par
         return e;
     }
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev[5], ctx->ev[6]);
+    (void)hipEventElapsedTime(&ms, ctx->ev[kEvIndexStart], ctx->ev[kEvIndexEnd]);
     g->index_ms = ms;
     g->index_sites = S;
     g->sites = S;
@@ -1257,7 +1261,11 @@ struct PassFound {
     uint32_t pos_base = 0;
     bool bases = false;  // SEED: every record's site lo plane lies beside it in ctx->vals_a (feature rows wanted)
     bool selected = false;  // select_pass has run: n, segs, cap describe the survivors, packed records at the start of ctx->keys_a
-    std::vector<uint64_t> sel_off;  // select_pass's host staging (uploaded with hipMemcpyAsync: it must outlive the pass)
+    // host staging of the sinks, uploaded with hipMemcpyAsync: it lives here because the pass outlives every such copy (each
+    // sink synchronises before the next stage or the next pass touches it) - select_pass's offsets, sink_input's tables
+    std::vector<uint64_t> sel_off;
+    std::vector<SumSeg> sink_segs;
+    std::vector<uint32_t> sink_tile0;
 };
 
 // words within k substitutions of a 7-base segment (k < 0: none)
@@ -1363,7 +1371,7 @@ hipError_t seed_plan(vsc_ctx *ctx, const vsc_genome *genome, const uint32_t *gp,
     VSC_TRY(hipMemsetAsync(ctx->seed_lrest.p, 0xFF, list_cap * sizeof(uint2), ctx->stream));  // padding: y = ~0, skipped
     VSC_TRY(launch_seed_lists((const uint2 *)ctx->guides.p, n_guides, plan, (uint32_t *)ctx->seed_off.p, (uint32_t *)ctx->seed_poff.p,
                               (uint2 *)ctx->seed_lrest.p, ctx->stream));
-    VSC_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
+    VSC_TRY(hipEventRecord(ctx->ev[kEvPrepEnd], ctx->stream));
     sa.chunk_tab = genome->d_ix_chunk_tab;
     sa.n_chunks = genome->ix_chunks;
     sa.vert = genome->d_ix_vert;
@@ -1432,7 +1440,7 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     for (uint32_t i = 0; i < n_guides; ++i) guide_planes(guides[i], &gp[2 * (size_t)i], &gp[2 * (size_t)i + 1]);
     VSC_HIP(ctx, ctx->guides.ensure(gp.size() * sizeof(uint32_t)));
     VSC_HIP(ctx, ctx->counters.ensure(kCounterWords * sizeof(unsigned long long)));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvPassStart], ctx->stream));
     VSC_HIP(ctx, hipMemcpyAsync(ctx->guides.p, gp.data(), gp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 
     const double own_bases = (double)genome->n_tiles * kTileBases;
@@ -1462,7 +1470,7 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         a.k_half = m / 2;  // bidir_mapping.cpp:129-146
         n_groups = scan_groups(ctx, a.n_tiles);
         t.genome_bytes += (uint64_t)genome->n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvPrepEnd], ctx->stream));
     } else {
         VSC_HIP(ctx, seed_plan(ctx, genome, gp.data(), n_guides, f, sa, &n_groups, &seed_shared));
         f.cap = sa.part_cap * f.n_parts;
@@ -1476,7 +1484,7 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
             return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in a block of 64 reads");
         VSC_HIP(ctx, ctx->keys_a.ensure(f.cap * sizeof(uint64_t)));
         VSC_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSearchStart], ctx->stream));
         if (algo == VSC_ALGO_SCAN) {
             VSC_HIP(ctx, ctx->vals_a.ensure(f.cap * sizeof(uint32_t)));
             a.hit_keys = (uint64_t *)ctx->keys_a.p;
@@ -1491,7 +1499,7 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
             }
             VSC_HIP(ctx, launch_seed_sliced(sa, n_groups, seed_shared, ctx->stream));
         }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSearchEnd], ctx->stream));
         VSC_HIP(ctx, hipMemcpyAsync(cnt, ctx->counters.p, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream));
         if (algo == VSC_ALGO_SEED)
             VSC_HIP(ctx, hipMemcpyAsync(&list_total, (const uint32_t *)ctx->seed_poff.p + kLists, sizeof list_total, hipMemcpyDeviceToHost, ctx->stream));
@@ -1511,9 +1519,9 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         }
     }
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[7]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvPassStart], ctx->ev[kEvPrepEnd]));
     t.prep_ms += ms;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvSearchStart], ctx->ev[kEvSearchEnd]));
     t.scan_ms += ms;
 
     // ---- the records: one segment of pairs (SCAN) or one per region (SEED) ----------------------------------------
@@ -1546,16 +1554,44 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     return VSC_OK;
 }
 
-// The end of a sink: waits for the pass; the sink's own stage (ev[3] -> ev[4]) is finalize_ms, the whole pass total_ms.
+// The input of the summary and the selection kernels - the fields both argument structs begin with: the pass's records where
+// the search left them, and f.segs on the device (in ctx->sort_segs) as segments relative to the pass's first read with the
+// prefix of their tile counts, for tiles of `tile` records.  The tables are staged in f (see PassFound).
+template <class Args> hipError_t sink_input(vsc_ctx *ctx, PassFound &f, uint32_t tile, bool excluded, Args &a)
+{
+    f.sink_segs.clear();
+    f.sink_tile0.assign(1, 0);
+    for (const SortSeg &sg : f.segs) {
+        f.sink_segs.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
+        f.sink_tile0.push_back(f.sink_tile0.back() + (sg.n_in + tile - 1) / tile);
+    }
+    const size_t seg_bytes = f.sink_segs.size() * sizeof(SumSeg), tile0_bytes = f.sink_tile0.size() * sizeof(uint32_t);
+    const size_t tile0_at = (seg_bytes + 255) / 256 * 256;
+    VSC_TRY(ctx->sort_segs.ensure(tile0_at + tile0_bytes));
+    VSC_TRY(hipMemcpyAsync(ctx->sort_segs.p, f.sink_segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSC_TRY(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, f.sink_tile0.data(), tile0_bytes, hipMemcpyHostToDevice, ctx->stream));
+    a.recs = (const uint64_t *)ctx->keys_a.p;
+    a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
+    a.segs = (const SumSeg *)ctx->sort_segs.p;
+    a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
+    a.n_segs = (uint32_t)f.sink_segs.size();
+    a.n_tiles = f.sink_tile0.back();
+    a.pos_pad = f.pos_pad;
+    a.pos_base = f.pos_base;
+    a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+    return hipSuccess;
+}
+
+// The end of a sink: waits for the pass; the sink's own stage (kEvSinkStart -> kEvSinkEnd) is finalize_ms, the whole pass total_ms.
 hipError_t end_pass(vsc_ctx *ctx, PassFound &f, const char *lap, vsc_timing &t)
 {
-    VSC_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
+    VSC_TRY(hipEventRecord(ctx->ev[kEvSinkEnd], ctx->stream));
     VSC_TRY(hipStreamSynchronize(ctx->stream));
     f.ht.lap(lap);
     float ms = 0;
-    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]));
+    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[kEvSinkStart], ctx->ev[kEvSinkEnd]));
     t.finalize_ms += ms;
-    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
+    VSC_TRY(hipEventElapsedTime(&ms, ctx->ev[kEvPassStart], ctx->ev[kEvSinkEnd]));
     t.total_ms += ms;
     t.read_passes++;
     return hipSuccess;
@@ -1635,14 +1671,14 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
             rows.rows = (uint4 *)ctx->score_feat.p;
             rows.rows_first = used;
         }
-        VSC_HIP(ctx, bin_sort(ctx, genome, std::move(f.segs), src, other, f.key_bits, f.pos_pad, f.pos_base, hits->d_records, ctx->ev[3],
+        VSC_HIP(ctx, bin_sort(ctx, genome, std::move(f.segs), src, other, f.key_bits, f.pos_pad, f.pos_base, hits->d_records, ctx->ev[kEvSinkStart],
                               &info, f.algo == VSC_ALGO_SEED || f.selected ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr));
     } else {
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
     }
     VSC_HIP(ctx, end_pass(ctx, f, "sort + finalize + sync", t));
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvSearchEnd], ctx->ev[kEvSinkStart]));
     t.sort_ms += ms;
     t.sort_levels = std::max(t.sort_levels, info.levels);
     t.sort_bin_bits = std::max(t.sort_bin_bits, info.bin_bits);
@@ -1657,38 +1693,19 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
 // reg: the device copy of the regions (resident_regions) - the rows over the hits inside go to ctx->sum_rows_in as well.
 int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, bool last = true, const RegionsView *reg = nullptr)
 {
-    std::vector<SumSeg> ss;
-    std::vector<uint32_t> tile0(1, 0);
-    for (const SortSeg &sg : f.segs) {
-        ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
-        tile0.push_back(tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
-    }
     SummaryRegionArgs a{};
-    if (!ss.empty()) {
-        const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
-        VSC_HIP(ctx, ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t),
-                                    hipMemcpyHostToDevice, ctx->stream));
-        a.recs = (const uint64_t *)ctx->keys_a.p;
-        a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
-        a.segs = (const SumSeg *)ctx->sort_segs.p;
-        a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
-        a.n_segs = (uint32_t)ss.size();
-        a.n_tiles = tile0.back();
-        a.pos_pad = f.pos_pad;
-        a.pos_base = f.pos_base;
-        a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+    if (!f.segs.empty()) {
+        VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
         a.out = (unsigned long long *)ctx->sum_rows.p + (size_t)f.guide_base * kSumWords;
         if (reg) {
             a.reg = *reg;
             a.out_in = (unsigned long long *)ctx->sum_rows_in.p + (size_t)f.guide_base * kSumWords;
         }
     }
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
     VSC_HIP(ctx, reg ? launch_summary_regions(a, ctx->stream) : launch_summary(a, ctx->stream));
     if (last) VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
-    else VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the uploads above read this call's vectors)
+    else VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (select_pass rewrites f.segs and the staging the copies above read)
     return VSC_OK;
 }
 
@@ -1706,35 +1723,17 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     f.selected = true;
     if (f.n == 0) return VSC_OK;
     hipStream_t st = ctx->stream;
-    std::vector<SumSeg> ss;
-    std::vector<uint32_t> tile0(1, 0);
-    for (const SortSeg &sg : f.segs) {
-        ss.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
-        tile0.push_back(tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
-    }
-    const size_t tile0_at = (ss.size() * sizeof(SumSeg) + 255) / 256 * 256;
-    VSC_HIP(ctx, ctx->sort_segs.ensure(tile0_at + tile0.size() * sizeof(uint32_t)));
-    VSC_HIP(ctx, hipMemcpyAsync(ctx->sort_segs.p, ss.data(), ss.size() * sizeof(SumSeg), hipMemcpyHostToDevice, st));
-    VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, tile0.data(), tile0.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    // per-read tables: thr, count, cursor, the regions' smallest thresholds (32-bit), then the lists' and the survivors' starts (64-bit)
-    const size_t words = ((size_t)n_reads + 63) / 64 * 64;
-    VSC_HIP(ctx, ctx->sel_tabs.ensure(4 * words * sizeof(uint32_t) + 2 * words * sizeof(uint64_t)));
-    VSC_HIP(ctx, ctx->sel_hist.ensure((size_t)n_reads * kSelBins * sizeof(uint32_t)));
-    VSC_HIP(ctx, ctx->vals_b.ensure((size_t)tile0.back() * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
     SelectRegionArgs a{};
+    VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
     if (reg) {
         a.reg = *reg;
         a.drop = drop;
     }
-    a.recs = (const uint64_t *)ctx->keys_a.p;
-    a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
-    a.segs = (const SumSeg *)ctx->sort_segs.p;
-    a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
-    a.n_segs = (uint32_t)ss.size();
-    a.n_tiles = tile0.back();
-    a.pos_pad = f.pos_pad;
-    a.pos_base = f.pos_base;
-    a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+    // per-read tables: thr, count, cursor, the regions' smallest thresholds (32-bit), then the lists' and the survivors' starts (64-bit)
+    const size_t words = ((size_t)n_reads + 63) / 64 * 64;
+    VSC_HIP(ctx, ctx->sel_tabs.ensure(4 * words * sizeof(uint32_t) + 2 * words * sizeof(uint64_t)));
+    VSC_HIP(ctx, ctx->sel_hist.ensure((size_t)n_reads * kSelBins * sizeof(uint32_t)));
+    VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.n_tiles * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
     a.min_score = sel.min_score;
     a.top_k = sel.top_k;
     a.n_reads = n_reads;
@@ -1804,7 +1803,7 @@ int excluded_loci(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *exclu
         const vsc_locus &l = exclude[i];
         if (l.contig == UINT32_MAX) continue;
         if (l.contig >= genome->n_contigs || l.strand > 1)
-            return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": excluded locus outside the genome's contigs or strands").c_str());
+            return fail_in(ctx, VSC_ERR_INVALID, who, "excluded locus outside the genome's contigs or strands");
         if (l.pos >= end[l.contig] - off[l.contig]) continue;  // no window starts there: nothing to exclude
         excl[i] = (uint64_t)l.strand << 32 | (off[l.contig] + l.pos);
     }
@@ -1863,7 +1862,7 @@ int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *
     bool same = regions->contig_off.size() == genome->n_contigs;
     for (uint32_t c = 0; same && c < genome->n_contigs; ++c)  // (the genome's host copy of its table: no device read per call)
         same = genome->h_contig_off[c] == regions->contig_off[c] && genome->h_contig_end[c] - genome->h_contig_off[c] == regions->contig_len[c];
-    if (!same) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": the regions were built for another contig table").c_str());
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the regions were built for another contig table");
     return upload_regions(ctx, regions, dev);
 }
 
@@ -1875,7 +1874,7 @@ int locate_records(vsc_ctx *ctx, const vsc_regions *regions, const void *records
                    const char *who)
 {
     ctx->err.clear();
-    if (!regions->has_locate) return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": the regions hold more intervals than a 32-bit label can number").c_str());
+    if (!regions->has_locate) return fail_in(ctx, VSC_ERR_RANGE, who, "the regions hold more intervals than a 32-bit label can number");
     HostTimer lap;
     VSC_HIP(ctx, hipSetDevice(ctx->device));
     LocateArgs a{};
@@ -1924,12 +1923,12 @@ int search_setup(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides,
                  const vsc_search_params *params, const char *who, vsc_timing *t)
 {
     ctx->err.clear();
-    if (!genome || !params || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
-    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": genome belongs to another context").c_str());
+    if (!genome || !params || (n_guides && !guides)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
     if (params->max_mismatches > VSC_MAX_MISMATCHES)  // read_mapping/bidir_mapping.cpp:234-238
         return fail(ctx, VSC_ERR_INVALID, "Maximum number of mismatches must lie between 0 and 8.");
-    if (params->algorithm > VSC_ALGO_SEED) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": unknown algorithm").c_str());
-    if (n_guides >= (1u << 31)) return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": too many reads").c_str());
+    if (params->algorithm > VSC_ALGO_SEED) return fail_in(ctx, VSC_ERR_INVALID, who, "unknown algorithm");
+    if (n_guides >= (1u << 31)) return fail_in(ctx, VSC_ERR_RANGE, who, "too many reads");
     VSC_HIP(ctx, hipSetDevice(ctx->device));
     *t = vsc_timing{};
     t->index_ms = ctx->timing.index_ms;
@@ -1957,41 +1956,100 @@ int search_setup(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides,
     return VSC_OK;
 }
 
-// The batch loop of vsc_search_stream / vsc_search_stream_rows (`who`): one pass per batch into a result of its own, which
-// deliver(hits, first, count, t) hands on.  rows: the seed search writes the hits' feature rows with the records.
-template <class Deliver>
-int stream_batches(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
-                   uint32_t batch_reads, bool rows, const char *who, bool have_callback, Deliver &&deliver)
+// What a search call wants from every pass (run_search).
+enum class Records { kNone, kAccumulate, kPerBatch };  // no result; one result over all passes; one per batch, handed to `deliver`
+struct SearchPlan {
+    SearchPlan(const char *who_, Records records_, vsc_hits **out_ = nullptr) : who(who_), records(records_), out(out_) {}
+    const char *who;                       // the entry point, for error texts
+    Records records;
+    vsc_hits **out;                        // kAccumulate: where the result goes
+    const vsc_locus *exclude = nullptr;    // per read (null: none)
+    const vsc_regions *regions = nullptr;  // what rows_in counts in and the filter selects by
+    vsc_guide_summary *rows = nullptr, *rows_in = nullptr;  // the row sets to write, in host memory (null: not wanted)
+    bool selects = false;                  // the call takes a vsc_select: checked after search_setup, as the call always did
+    const vsc_select *select = nullptr;
+    const vsc_region_filter *filter = nullptr;  // (its fields have been checked)
+    uint32_t batch_reads = 0;              // kPerBatch: reads per batch (0 or too many: kMaxPassReads)
+    // kPerBatch: deliver(deliver_self, hits, first read, reads, t) hands a batch on; what it adds to t.score_ms stays in the call's timing
+    int (*deliver)(void *, vsc_hits *, uint32_t, uint32_t, vsc_timing &) = nullptr;
+    void *deliver_self = nullptr;
+    bool keep_bases = false;  // the seed search keeps the sites' bases: the hits' feature rows are written with the records
+};
+
+// The one pass loop behind every search entry point: search_setup; the call's state on the device (excluded loci, regions,
+// zeroed rows); per pass of at most kMaxPassReads reads find_pass, then what the plan asks for - summarize_pass, select_pass,
+// sort_pass - the read index being the major sort key, so that the passes' records simply follow each other; the rows and the
+// timing at the end.
+int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+               const SearchPlan &p)
 {
-    return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
+    int rc = search_setup(ctx, genome, guides, n_guides, params, p.who, &t);
     if (rc != VSC_OK) return rc;
-    if (!have_callback) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null callback").c_str());
-    if (batch_reads == 0 || batch_reads > (uint32_t)kMaxPassReads) batch_reads = kMaxPassReads;
-    for (uint32_t first = 0; first < n_guides; first += batch_reads) {
-        const uint32_t count = std::min<uint32_t>(batch_reads, n_guides - first);
-        vsc_hits *hits = new (std::nothrow) vsc_hits();
-        if (!hits) return fail(ctx, VSC_ERR_NOMEM, (std::string(who) + ": out of host memory").c_str());
+    const bool per_batch = p.records == Records::kPerBatch;
+    if (per_batch && !p.deliver) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null callback");
+    if (p.selects && !p.select) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
+    if (p.selects && (p.select->reserved[0] || p.select->reserved[1])) return fail_in(ctx, VSC_ERR_INVALID, p.who, "reserved fields must be 0");
+    std::vector<uint64_t> excl;
+    if ((rc = excluded_loci(ctx, genome, p.exclude, n_guides, p.who, excl)) != VSC_OK) return rc;
+    RegionsView reg{};
+    if (p.regions && (rc = resident_regions(ctx, genome, p.regions, p.who, reg)) != VSC_OK) return rc;
+    // the summary kernel writes both sets of rows or the plain one: rows_in alone takes the plain rows along
+    const bool rows = p.rows || p.rows_in;
+    if ((rc = upload_summary_state(ctx, n_guides, rows, excl, p.rows_in != nullptr)) != VSC_OK) return rc;
+    // nothing to decide: the records go to the sort as the search hands them over
+    const bool selecting = p.select && (p.select->top_k || p.select->min_score || !excl.empty() || p.filter);
+    const uint32_t step = per_batch && p.batch_reads && p.batch_reads <= (uint32_t)kMaxPassReads ? p.batch_reads : (uint32_t)kMaxPassReads;
+
+    std::unique_ptr<vsc_hits, int (*)(vsc_hits *)> hits(nullptr, vsc_hits_free);
+    uint64_t used = 0;  // records in `hits`
+    auto fresh_result = [&]() {
+        hits.reset(new (std::nothrow) vsc_hits());
+        if (!hits) return fail_in(ctx, VSC_ERR_NOMEM, p.who, "out of host memory");
         hits->ctx = ctx;
+        used = 0;
+        return VSC_OK;
+    };
+    auto seal_result = [&]() {
+        hits->n = used;
+        if (used == 0) hits->host_valid = true;
+    };
+    if (p.records == Records::kAccumulate && (rc = fresh_result()) != VSC_OK) return rc;
+    for (uint32_t first = 0; first < n_guides; first += step) {
+        const uint32_t count = std::min<uint32_t>(step, n_guides - first);
+        if (per_batch && (rc = fresh_result()) != VSC_OK) return rc;
+        // (an accumulated result grows to its expected final size at once)
+        const uint64_t projected = !per_batch && first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
         PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, rows && t.algorithm == VSC_ALGO_SEED, t, f);
-        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, 0, 0, t);
-        if (prc == VSC_OK) {
-            hits->n = f.n;
-            if (f.n == 0) hits->host_valid = true;
+        rc = find_pass(ctx, genome, guides + first, count, first, params, p.keep_bases && t.algorithm == VSC_ALGO_SEED, t, f);
+        // (with another sink to follow, the summary leaves the end of the pass - and finalize_ms - to the sort)
+        if (rc == VSC_OK && rows) rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone, p.rows_in ? &reg : nullptr);
+        if (rc == VSC_OK && selecting) rc = select_pass(ctx, f, count, *p.select, !excl.empty(), p.filter ? &reg : nullptr, p.filter ? p.filter->scope : 0u);
+        if (rc == VSC_OK && p.records != Records::kNone) rc = sort_pass(ctx, genome, f, hits.get(), used, projected, t);
+        if (rc != VSC_OK) return rc;
+        used += f.n;
+        if (per_batch) {
+            seal_result();
             ctx->timing = t;
             ctx->timing.score_ms = 0;
-            prc = deliver(hits, first, count, t);
-            if (prc != VSC_OK && ctx->err.empty()) ctx->err = std::string(who) + ": the batch callback failed";
+            rc = p.deliver(p.deliver_self, hits.get(), first, count, t);
+            if (rc != VSC_OK && ctx->err.empty()) (void)fail_in(ctx, rc, p.who, "the batch callback failed");
+            hits.reset();  // (before the next batch: its records go into this one's storage)
+            if (rc != VSC_OK) return rc;
         }
-        vsc_hits_free(hits);
-        if (prc != VSC_OK) return prc;
+    }
+    if (rows && n_guides) {
+        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+        if (p.rows) VSC_HIP(ctx, hipMemcpyAsync(p.rows, ctx->sum_rows.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (p.rows_in) VSC_HIP(ctx, hipMemcpyAsync(p.rows_in, ctx->sum_rows_in.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->timing = t;
+    if (p.records == Records::kAccumulate) {
+        seal_result();
+        *p.out = hits.release();
+    }
     return VSC_OK;
-    });
 }
 
 // vsc_search_summary (regions == null) and vsc_search_summary_regions (`who`)
@@ -2000,36 +2058,13 @@ int search_summary(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guide
 {
     return guarded(ctx, [&]() -> int {
     if (!ctx) return VSC_ERR_INVALID;
-    if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
-    vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
-    if (rc != VSC_OK) return rc;
-    std::vector<uint64_t> excl;
-    const int erc = excluded_loci(ctx, genome, exclude, n_guides, who, excl);
-    if (erc != VSC_OK) return erc;
-    RegionsView reg{};
-    if (regions) {
-        const int rrc = resident_regions(ctx, genome, regions, who, reg);
-        if (rrc != VSC_OK) return rrc;
-    }
-    const int urc = upload_summary_state(ctx, n_guides, true, excl, regions != nullptr);
-    if (urc != VSC_OK) return urc;
-    // passes of at most kMaxPassReads reads, as vsc_search; every pass adds into its own slice of the rows
-    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
-        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
-        if (prc == VSC_OK) prc = summarize_pass(ctx, f, !excl.empty(), t, true, regions ? &reg : nullptr);
-        if (prc != VSC_OK) return prc;
-    }
-    if (n_guides) {
-        VSC_HIP(ctx, hipMemcpyAsync(out, ctx->sum_rows.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
-        if (regions)
-            VSC_HIP(ctx, hipMemcpyAsync(out_in, ctx->sum_rows_in.p, (size_t)n_guides * sizeof(vsc_guide_summary), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->timing = t;
-    return VSC_OK;
+    if (n_guides && !out) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    SearchPlan p(who, Records::kNone);
+    p.exclude = exclude;
+    p.regions = regions;
+    p.rows = out;
+    p.rows_in = out_in;
+    return run_search(ctx, genome, guides, n_guides, params, p);
     });
 }
 
@@ -2041,59 +2076,34 @@ int search_select(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides
     return guarded(ctx, [&]() -> int {
     if (!ctx || !out) return VSC_ERR_INVALID;
     *out = nullptr;
-    vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, who, &t);
-    if (rc != VSC_OK) return rc;
-    if (!select) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null argument").c_str());
-    if (select->reserved[0] || select->reserved[1]) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": reserved fields must be 0").c_str());
-    std::vector<uint64_t> excl;
-    const int erc = excluded_loci(ctx, genome, exclude, n_guides, who, excl);
-    if (erc != VSC_OK) return erc;
-    RegionsView reg{};
-    if (filter) {
-        const int rrc = resident_regions(ctx, genome, filter->regions, who, reg);
-        if (rrc != VSC_OK) return rrc;
+    SearchPlan p(who, Records::kAccumulate, out);
+    p.exclude = exclude;
+    p.regions = filter ? filter->regions : nullptr;
+    p.rows = summary;
+    p.rows_in = summary_in;
+    p.selects = true;
+    p.select = select;
+    p.filter = filter;
+    return run_search(ctx, genome, guides, n_guides, params, p);
+    });
+}
+
+// vsc_search_stream / vsc_search_stream_rows (`who`): one pass per batch into a result of its own, which deliver hands on.
+// rows: the seed search writes the hits' feature rows with the records.
+template <class Deliver>
+int search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                  uint32_t batch_reads, bool rows, const char *who, bool have_callback, Deliver deliver)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    SearchPlan p(who, Records::kPerBatch);
+    p.batch_reads = batch_reads;
+    p.keep_bases = rows;
+    if (have_callback) {
+        p.deliver = [](void *self, vsc_hits *hits, uint32_t first, uint32_t count, vsc_timing &t) { return (*(Deliver *)self)(hits, first, count, t); };
+        p.deliver_self = &deliver;
     }
-    // the summary kernel writes both sets of rows or the plain one: summary_in alone takes the plain rows along
-    const bool rows = summary != nullptr || summary_in != nullptr;
-    const int urc = upload_summary_state(ctx, n_guides, rows, excl, summary_in != nullptr);
-    if (urc != VSC_OK) return urc;
-    // nothing to decide: the records go to the sort as vsc_search hands them over
-    const bool selecting = select->top_k || select->min_score || !excl.empty() || filter;
-    vsc_hits *hits = new (std::nothrow) vsc_hits();
-    if (!hits) return fail(ctx, VSC_ERR_NOMEM, (std::string(who) + ": out of host memory").c_str());
-    hits->ctx = ctx;
-    uint64_t used = 0;
-    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
-        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
-        PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
-        if (prc == VSC_OK && rows) prc = summarize_pass(ctx, f, !excl.empty(), t, false, summary_in ? &reg : nullptr);
-        if (prc == VSC_OK && selecting) prc = select_pass(ctx, f, count, *select, !excl.empty(), filter ? &reg : nullptr, filter ? filter->scope : 0u);
-        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
-        if (prc != VSC_OK) {
-            vsc_hits_free(hits);
-            return prc;
-        }
-        used += f.n;
-    }
-    if (rows && n_guides) {
-        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
-        hipError_t e = hipSuccess;
-        if (summary) e = hipMemcpyAsync(summary, ctx->sum_rows.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && summary_in) e = hipMemcpyAsync(summary_in, ctx->sum_rows_in.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            vsc_hits_free(hits);
-            VSC_HIP(ctx, e);
-        }
-    }
-    hits->n = used;
-    if (used == 0) hits->host_valid = true;
-    ctx->timing = t;
-    *out = hits;
-    return VSC_OK;
+    return run_search(ctx, genome, guides, n_guides, params, p);
     });
 }
 
@@ -2107,32 +2117,8 @@ int vsc_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     return guarded(ctx, [&]() -> int {
     if (!ctx || !out) return VSC_ERR_INVALID;
     *out = nullptr;
-    vsc_timing t{};
-    const int rc = search_setup(ctx, genome, guides, n_guides, params, "vsc_search", &t);
-    if (rc != VSC_OK) return rc;
-    vsc_hits *hits = new (std::nothrow) vsc_hits();
-    if (!hits) return fail(ctx, VSC_ERR_NOMEM, "vsc_search: out of host memory");
-    hits->ctx = ctx;
-    // a pass takes at most kMaxPassReads reads (256 output regions of 64 reads); larger sets are searched
-    // pass by pass - the read index is the major sort key, so the passes' results simply follow each other
-    uint64_t used = 0;
-    for (uint32_t first = 0; first < n_guides; first += kMaxPassReads) {
-        const uint32_t count = std::min<uint32_t>(kMaxPassReads, n_guides - first);
-        const uint64_t projected = first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
-        PassFound f;
-        int prc = find_pass(ctx, genome, guides + first, count, first, params, false, t, f);
-        if (prc == VSC_OK) prc = sort_pass(ctx, genome, f, hits, used, projected, t);
-        if (prc != VSC_OK) {
-            vsc_hits_free(hits);
-            return prc;
-        }
-        used += f.n;
-    }
-    hits->n = used;
-    if (used == 0) hits->host_valid = true;
-    ctx->timing = t;
-    *out = hits;
-    return VSC_OK;
+    SearchPlan p("vsc_search", Records::kAccumulate, out);
+    return run_search(ctx, genome, guides, n_guides, params, p);
     });
 }
 
@@ -2247,14 +2233,14 @@ int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regio
         a.n_work = n_work;
         a.tile_count = (uint32_t *)(base + list_bytes);
         a.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
         VSC_HIP(ctx, launch_enum(a, false, regions != nullptr, ctx->stream));
         VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
         VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list above is this call's vector)
         float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
         t.scan_ms += ms;
         t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
         t.passes = 1;
@@ -2269,11 +2255,11 @@ int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regio
             VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
             a.codes = (unsigned long long *)g->storage.p;
             a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
             VSC_HIP(ctx, launch_enum(a, true, regions != nullptr, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
             VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
             t.scan_ms += ms;
             t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
             t.passes = 2;
@@ -2370,7 +2356,7 @@ double vsc_mit_specificity(uint64_t mit_sum)
 int vsc_search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                       const vsc_search_params *params, uint32_t batch_reads, vsc_batch_fn on_batch, void *user)
 {
-    return stream_batches(ctx, genome, guides, n_guides, params, batch_reads, false, "vsc_search_stream", on_batch != nullptr,
+    return search_stream(ctx, genome, guides, n_guides, params, batch_reads, false, "vsc_search_stream", on_batch != nullptr,
                           [&](vsc_hits *hits, uint32_t first, uint32_t count, vsc_timing &t) {
                               const int prc = on_batch(user, hits, first, count);
                               t.score_ms += ctx->timing.score_ms;  // what the callback's scoring calls measured
@@ -2381,7 +2367,7 @@ int vsc_search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *gu
 int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
                            const vsc_search_params *params, uint32_t batch_reads, vsc_rows_batch_fn on_batch, void *user)
 {
-    return stream_batches(ctx, genome, guides, n_guides, params, batch_reads, true, "vsc_search_stream_rows", on_batch != nullptr,
+    return search_stream(ctx, genome, guides, n_guides, params, batch_reads, true, "vsc_search_stream_rows", on_batch != nullptr,
                           [&](vsc_hits *hits, uint32_t first, uint32_t count, vsc_timing &t) {
                               // the seed search wrote the rows with the records; the streaming scan's hits (small searches on a
                               // genome without an index) are scored the usual way
@@ -2483,10 +2469,10 @@ int vsc_hits_merge(vsc_ctx *ctx, const void *records, int records_on_device, con
     uint64_t *shard_off_dev = bound + nb;
     if (e == hipSuccess)
         step(hipMemcpyAsync(shard_off_dev, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    step(hipEventRecord(ctx->ev[0], ctx->stream));
+    step(hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
     if (e == hipSuccess)
         step(launch_merge(records_dev, shard_off_dev, n_shards, K, bound, (uint64_t *)ctx->vals_a.p, hits->d_records, ctx->stream));
-    step(hipEventRecord(ctx->ev[1], ctx->stream));
+    step(hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     step(hipStreamSynchronize(ctx->stream));
     if (e != hipSuccess) {
         vsc_hits_free(hits);
@@ -2825,16 +2811,16 @@ int vsc_score_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits *hits,
         if (mit) s.mit = (double *)ctx->score_mit.p;
         if (mit_flags) s.mit_flags = (uint8_t *)ctx->score_flags.p;
         if (features) s.features = (uint8_t *)ctx->score_feat.p;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
         VSC_HIP(ctx, launch_score(s, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
         if (mit) VSC_HIP(ctx, hipMemcpyAsync(mit + done, s.mit, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (mit_flags) VSC_HIP(ctx, hipMemcpyAsync(mit_flags + done, s.mit_flags, m, hipMemcpyDeviceToHost, ctx->stream));
         if (features)
             VSC_HIP(ctx, hipMemcpyAsync(features + done * VSC_N_FEATURES, s.features, m * VSC_N_FEATURES, hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
         total_ms += ms;
     }
     ctx->timing.score_ms = total_ms;
@@ -2876,16 +2862,16 @@ int vsc_score_pairs(vsc_ctx *ctx, const uint64_t *on_targets, const uint64_t *of
         VSC_HIP(ctx, ctx->score_feat.ensure(n * VSC_N_FEATURES));
         d_feat = (uint8_t *)ctx->score_feat.p;
     }
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
     VSC_HIP(ctx, launch_score_pairs((const uint2 *)d_planes, (const uint2 *)(d_planes + 2 * n), d_masks, n, d_mit, d_flags,
                                     d_feat, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     if (mit) VSC_HIP(ctx, hipMemcpyAsync(mit, d_mit, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (mit_flags) VSC_HIP(ctx, hipMemcpyAsync(mit_flags, d_flags, n, hipMemcpyDeviceToHost, ctx->stream));
     if (features) VSC_HIP(ctx, hipMemcpyAsync(features, d_feat, n * VSC_N_FEATURES, hipMemcpyDeviceToHost, ctx->stream));
     VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
     ctx->timing.score_ms = ms;
     return VSC_OK;
     });
@@ -2918,7 +2904,7 @@ int vsc_score_hits_packed(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits
         s.n = m;
         if (mit_host) s.mit = (double *)ctx->score_mit.p;
         uint4 *dst = packed_dev ? (uint4 *)packed_dev + done * 4 : (uint4 *)ctx->score_feat.p;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
         // large results on a large genome: visit the rows genome slice by genome slice (launch_score_schedule)
         uint32_t kSliceShift = 28;  // 2^28 positions = 64 MB of interleaved planes
         const uint64_t positions = genome->dev_words * 32;
@@ -2944,13 +2930,13 @@ int vsc_score_hits_packed(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits
             }
         }
         VSC_HIP(ctx, launch_score_packed(s, dst, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
         if (packed_host)
             VSC_HIP(ctx, hipMemcpyAsync(packed_host + done * 16, dst, m * VSC_PACKED_FEATURE_BYTES, hipMemcpyDeviceToHost, ctx->stream));
         if (mit_host) VSC_HIP(ctx, hipMemcpyAsync(mit_host + done, s.mit, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
         total_ms += ms;
     }
     ctx->timing.score_ms = total_ms;
@@ -2991,11 +2977,11 @@ int prepare_forest(vsc_ctx *ctx, const vsc_rf_model *model, const char *who)
 {
     if (!model || !model->node_status || !model->feature || !model->left || !model->right || !model->split ||
         !model->node_class || model->n_trees == 0 || model->n_nodes == 0)
-        return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null or empty forest").c_str());
+        return fail_in(ctx, VSC_ERR_INVALID, who, "null or empty forest");
     const size_t nn = (size_t)model->n_trees * model->n_nodes;
     if (model->n_nodes > (uint32_t)kRfMaxNodes || (size_t)model->n_nodes * sizeof(uint32_t) > (size_t)kRfTileBytes)
-        return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": a tree has more nodes than the kernel stages at once").c_str());
-    if (model->n_trees > 65535u) return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": more than 65 535 trees").c_str());
+        return fail_in(ctx, VSC_ERR_RANGE, who, "a tree has more nodes than the kernel stages at once");
+    if (model->n_trees > 65535u) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 65 535 trees");
     uint64_t h = 0xcbf29ce484222325ull ^ ((uint64_t)model->n_trees << 32 | model->n_nodes);
     h = hash_words(model->node_status, nn, h);
     h = hash_words(model->feature, nn * 2, h);
@@ -3014,7 +3000,7 @@ int prepare_forest(vsc_ctx *ctx, const vsc_rf_model *model, const char *who)
         if (model->node_status[i] == 1 && model->feature[i] == VSC_N_FEATURES) thr.push_back(model->split[i]);
     std::sort(thr.begin(), thr.end());
     thr.erase(std::unique(thr.begin(), thr.end()), thr.end());
-    if (thr.size() > 255) return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": the forest splits the on-target activity at more than 255 values").c_str());
+    if (thr.size() > 255) return fail_in(ctx, VSC_ERR_RANGE, who, "the forest splits the on-target activity at more than 255 values");
     // the distinct tests (column, integer threshold); a split below zero is never met, one at or above 255 always
     struct Split { uint16_t col; uint8_t thr; bool never; };
     auto split_of = [&](size_t i) {
@@ -3033,8 +3019,8 @@ int prepare_forest(vsc_ctx *ctx, const vsc_rf_model *model, const char *who)
         const uint32_t own = (uint32_t)(i % model->n_nodes) + 1;  // 1-based index of this node in its tree
         if (ft > VSC_N_FEATURES || model->left[i] <= own || model->right[i] <= own || model->left[i] > model->n_nodes ||
             model->right[i] > model->n_nodes)
-            return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": malformed forest (feature or daughter index out of range, or a daughter that does not lie behind its parent)").c_str());
-        if (!(model->split[i] == model->split[i])) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": malformed forest (NaN split)").c_str());
+            return fail_in(ctx, VSC_ERR_INVALID, who, "malformed forest (feature or daughter index out of range, or a daughter that does not lie behind its parent)");
+        if (!(model->split[i] == model->split[i])) return fail_in(ctx, VSC_ERR_INVALID, who, "malformed forest (NaN split)");
         const Split sp = split_of(i);
         if (!sp.never) keys.push_back((uint32_t)sp.col << 8 | sp.thr);
     }
@@ -3042,7 +3028,7 @@ int prepare_forest(vsc_ctx *ctx, const vsc_rf_model *model, const char *who)
     keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
     if (keys.empty()) keys.push_back(0);  // (a forest of stumps without a usable split still needs a test table)
     if (keys.size() > (size_t)kRfMaxTests)
-        return fail(ctx, VSC_ERR_RANGE, (std::string(who) + ": the forest uses more than 1 024 distinct (predictor, threshold) tests").c_str());
+        return fail_in(ctx, VSC_ERR_RANGE, who, "the forest uses more than 1 024 distinct (predictor, threshold) tests");
     // tests sorted by the row word they read (the kernel walks the words in a compile-time loop)
     std::vector<RfTest> tests(keys.size());
     for (size_t i = 0; i < keys.size(); ++i) {
@@ -3224,7 +3210,7 @@ int rf_predict(vsc_ctx *ctx, const vsc_rf_model *model, const uint8_t *dense, co
                const double *activity, uint64_t n, double *prob, uint8_t *cls, uint8_t *tie, const char *who)
 {
     ctx->err.clear();
-    if (n && ((!dense && !packed) || !activity)) return fail(ctx, VSC_ERR_INVALID, (std::string(who) + ": null or empty argument").c_str());
+    if (n && ((!dense && !packed) || !activity)) return fail_in(ctx, VSC_ERR_INVALID, who, "null or empty argument");
     const int frc = prepare_forest(ctx, model, who);
     if (frc != VSC_OK) return frc;
     if (n == 0) return VSC_OK;
@@ -3254,9 +3240,9 @@ int rf_predict(vsc_ctx *ctx, const vsc_rf_model *model, const uint8_t *dense, co
     const uint64_t tiles = (n + kRfRows - 1) / kRfRows;
     a.tree_splits = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)2 * ctx->n_cus / tiles, 32, model->n_trees}));
     if (a.tree_splits > 1) VSC_HIP(ctx, hipMemsetAsync(a.votes, 0, n * sizeof(uint32_t), ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
     VSC_HIP(ctx, launch_rf_predict(a, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     std::vector<uint32_t> votes(n);
     VSC_HIP(ctx, hipMemcpyAsync(votes.data(), a.votes, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3266,7 +3252,7 @@ int rf_predict(vsc_ctx *ctx, const vsc_rf_model *model, const uint8_t *dense, co
         if (tie) tie[i] = 2 * votes[i] == model->n_trees;
     }
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
     ctx->timing.score_ms = ms;
     return VSC_OK;
 }
@@ -3339,14 +3325,14 @@ int vsc_score_classify_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hi
         a.n = m;
         a.votes16 = votes_dev ? (uint16_t *)votes_dev + done : (uint16_t *)ctx->score_flags.p;
         a.tree_splits = 1;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
         VSC_HIP(ctx, launch_rf_predict(a, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
         if (votes_host) VSC_HIP(ctx, hipMemcpyAsync(votes_host + done, a.votes16, m * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
         if (mit_host) VSC_HIP(ctx, hipMemcpyAsync(mit_host + done, a.score.mit, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
         total_ms += ms;
     }
     ctx->timing.score_ms = total_ms;

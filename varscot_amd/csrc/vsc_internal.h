@@ -1,4 +1,4 @@
-// vsc_internal.h - types shared by the C-ABI host code (vsc_api.cpp) and the HIP kernels
+// vsc_internal.h - types shared by the host code (vsc_api.cpp, vsc_multi.cpp) and the HIP kernels in vsc_seed.hip, vsc_sort.hip, vsc_enum.hip and the first kernel file
 // (vsc_kernels.hip).  Not installed; the public contract is include/varscot_hip.h.
 #pragma once
 

@@ -719,6 +719,43 @@ void add_row(vsc_guide_summary &o, const vsc_guide_summary &p)
     o.on_target |= p.on_target;
 }
 
+// out[i] = the sum of the shards' rows part[r][i] (a shard that owns no words of the genome has none); out == null: not wanted
+void add_shard_rows(const vsc_multi_genome *g, const std::vector<std::vector<vsc_guide_summary>> &part, uint32_t n_guides, vsc_guide_summary *out)
+{
+    if (!out) return;
+    std::fill(out, out + n_guides, vsc_guide_summary{});
+    for (size_t r = 0; r < part.size(); ++r)
+        for (uint32_t i = 0; g->shard[r] && i < n_guides; ++i) add_row(out[i], part[r][i]);
+}
+
+// The excluded loci of `who` against the genome's contig table.  (The shards check them too, but a shard that owns no words
+// of the genome does not search.)
+int check_excluded(vsc_multi *m, const vsc_multi_genome *g, const vsc_locus *exclude, uint32_t n_guides, const std::string &who)
+{
+    for (uint32_t i = 0; exclude && i < n_guides; ++i)
+        if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
+            return mfail(m, VSC_ERR_INVALID, who + ": excluded locus outside the genome's contigs or strands");
+    return VSC_OK;
+}
+
+// The timing of a call that fans out over the shards and joins their results on the host, begun at t0: tm[r] = shard r's own
+// timing (zero: it owns no words), wall = the fan-out up to the last shard, merge_ms = what followed on the first device.
+void store_join_timing(vsc_multi *m, const std::vector<vsc_timing> &tm, double wall, clk::time_point t0, bool used_rccl, double merge_ms = 0)
+{
+    vsc_multi_timing mt{};
+    for (const vsc_timing &t : tm) {
+        mt.search_ms_max = std::max(mt.search_ms_max, t.total_ms);
+        mt.hits += t.hits;
+    }
+    mt.search_wall_ms = wall;
+    mt.merge_ms = merge_ms;
+    mt.total_ms = ms_between(t0, clk::now());
+    mt.n_devices = (uint32_t)tm.size();
+    mt.used_rccl = used_rccl ? 1u : 0u;
+    mt.batches = 1;
+    m->timing = mt;
+}
+
 // vsc_multi_search_summary (regions == null) and vsc_multi_search_summary_regions (`who`)
 int multi_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
                   const vsc_locus *exclude, const vsc_regions *regions, vsc_guide_summary *out, vsc_guide_summary *out_in, const std::string &who)
@@ -728,14 +765,13 @@ int multi_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guide
     m->err.clear();
     if (!g || g->multi != m || !params || (n_guides && (!guides || !out || (regions && !out_in))))
         return mfail(m, VSC_ERR_INVALID, who + ": null argument");
-    if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
-        for (uint32_t i = 0; i < n_guides; ++i)
-            if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
-                return mfail(m, VSC_ERR_INVALID, who + ": excluded locus outside the genome's contigs or strands");
+    const int erc = check_excluded(m, g, exclude, n_guides, who);
+    if (erc != VSC_OK) return erc;
     const auto t0 = clk::now();
     const size_t n = m->ctx.size();
     std::vector<int> rc(n, VSC_OK);
     std::vector<std::vector<vsc_guide_summary>> part(n), part_in(n);
+    std::vector<vsc_timing> tm(n);
     on_all(n, [&](size_t r) {
         if (!g->shard[r]) return;
         part[r].resize(n_guides);
@@ -745,30 +781,14 @@ int multi_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guide
         } else {
             rc[r] = vsc_search_summary(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, part[r].data());
         }
+        (void)vsc_ctx_timing(m->ctx[r], &tm[r]);
     });
     for (size_t r = 0; r < n; ++r)
         if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
-    const double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    std::fill(out, out + n_guides, vsc_guide_summary{});
-    if (regions) std::fill(out_in, out_in + n_guides, vsc_guide_summary{});
-    vsc_multi_timing mt{};
-    for (size_t r = 0; r < n; ++r) {
-        if (!g->shard[r]) continue;
-        for (uint32_t i = 0; i < n_guides; ++i) {
-            add_row(out[i], part[r][i]);
-            if (regions) add_row(out_in[i], part_in[r][i]);
-        }
-        vsc_timing t{};
-        (void)vsc_ctx_timing(m->ctx[r], &t);
-        mt.search_ms_max = std::max(mt.search_ms_max, t.total_ms);
-        mt.hits += t.hits;
-    }
-    mt.search_wall_ms = wall;
-    mt.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    mt.n_devices = (uint32_t)n;
-    mt.used_rccl = m->use_rccl ? 1u : 0u;
-    mt.batches = 1;
-    m->timing = mt;
+    const double wall = ms_between(t0, clk::now());
+    add_shard_rows(g, part, n_guides, out);
+    if (regions) add_shard_rows(g, part_in, n_guides, out_in);
+    store_join_timing(m, tm, wall, t0, m->use_rccl);
     return VSC_OK;
     });
 }
@@ -788,10 +808,8 @@ int multi_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides
     if (filter && (!filter->regions || filter->scope > VSC_REGION_DROP || filter->reserved))  // (checked here too, as the loci below)
         return mfail(m, VSC_ERR_INVALID, who + ": a filter needs regions, a scope of 0 or 1 and a reserved field of 0");
     if (!filter && summary_in) return mfail(m, VSC_ERR_INVALID, who + ": summary_in without a filter");
-    if (exclude)  // (checked here too: a shard that owns no words of the genome does not search)
-        for (uint32_t i = 0; i < n_guides; ++i)
-            if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= g->table->n_contigs) || exclude[i].strand > 1)
-                return mfail(m, VSC_ERR_INVALID, who + ": excluded locus outside the genome's contigs or strands");
+    const int erc = check_excluded(m, g, exclude, n_guides, who);
+    if (erc != VSC_OK) return erc;
     const size_t n = m->ctx.size();
     std::vector<std::vector<vsc_guide_summary>> part(summary ? n : 0), part_in(summary_in ? n : 0);
     for (auto *pp : {&part, &part_in})
@@ -805,14 +823,8 @@ int multi_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides
     };
     // the rows add exactly, as in vsc_multi_search_summary
     auto add_rows = [&]() {
-        for (auto pr : {std::make_pair(summary, &part), std::make_pair(summary_in, &part_in)}) {
-            if (!pr.first) continue;
-            std::fill(pr.first, pr.first + n_guides, vsc_guide_summary{});
-            for (size_t r = 0; r < n; ++r) {
-                if (!g->shard[r]) continue;
-                for (uint32_t i = 0; i < n_guides; ++i) add_row(pr.first[i], (*pr.second)[r][i]);
-            }
-        }
+        add_shard_rows(g, part, n_guides, summary);
+        add_shard_rows(g, part_in, n_guides, summary_in);
     };
     if (select->top_k == 0) {
         // nothing to cut: the shards' survivors are the result - through the packed exchange, they can be many
@@ -891,18 +903,7 @@ int multi_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides
     const int mrc = vsc_hits_merge(m->merge_ctx, all.data(), 0, counts.data(), (uint32_t)n, n_guides, out);
     if (mrc != VSC_OK) return mfail(m, mrc, std::string("merge: ") + vsc_last_error(m->merge_ctx));
     add_rows();
-    vsc_multi_timing mt{};
-    for (size_t r = 0; r < n; ++r) {
-        mt.search_ms_max = std::max(mt.search_ms_max, tm[r].total_ms);
-        mt.hits += tm[r].hits;
-    }
-    mt.search_wall_ms = wall;
-    mt.merge_ms = ms_between(t_cut, clk::now());
-    mt.total_ms = ms_between(t0, clk::now());
-    mt.n_devices = (uint32_t)n;
-    mt.used_rccl = m->use_rccl ? 1u : 0u;
-    mt.batches = 1;
-    m->timing = mt;
+    store_join_timing(m, tm, wall, t0, m->use_rccl, ms_between(t_cut, clk::now()));
     return VSC_OK;
     });
 }
@@ -949,14 +950,16 @@ int vsc_multi_guides_enumerate(vsc_multi *m, const vsc_multi_genome *g, const vs
     } free_parts{part};
     std::vector<const uint64_t *> codes(n, nullptr);
     std::vector<const vsc_locus *> loci(n, nullptr);
+    std::vector<vsc_timing> tm(n);
     on_all(n, [&](size_t r) {
         if (!g->shard[r]) return;  // (a small genome: this shard owns no words of it; some shard always does)
         rc[r] = vsc_guides_enumerate(m->ctx[r], g->shard[r], regions, params, &part[r]);
+        (void)vsc_ctx_timing(m->ctx[r], &tm[r]);
         if (rc[r] == VSC_OK) rc[r] = vsc_guides_data(part[r], &codes[r], &loci[r]);
     });
     for (size_t r = 0; r < n; ++r)
         if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
-    const double wall = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    const double wall = ms_between(t0, clk::now());
     uint64_t total = 0;
     for (size_t r = 0; r < n; ++r) total += vsc_guides_count(part[r]);
     if (params->max_guides && total > params->max_guides)
@@ -965,24 +968,15 @@ int vsc_multi_guides_enumerate(vsc_multi *m, const vsc_multi_genome *g, const vs
     std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> res(new vsc_guides(), vsc_guides_free);
     res->codes.reserve(total);
     res->loci.reserve(total);
-    vsc_multi_timing mt{};
     for (size_t r = 0; r < n; ++r) {
         if (!part[r]) continue;
         const uint64_t k = vsc_guides_count(part[r]);
         res->codes.insert(res->codes.end(), codes[r], codes[r] + k);
         res->loci.insert(res->loci.end(), loci[r], loci[r] + k);
-        vsc_timing t{};
-        (void)vsc_ctx_timing(m->ctx[r], &t);
-        mt.search_ms_max = std::max(mt.search_ms_max, t.total_ms);
     }
     res->n = total;
     res->host_valid = true;
-    mt.search_wall_ms = wall;
-    mt.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    mt.n_devices = (uint32_t)n;
-    mt.used_rccl = 0;
-    mt.batches = 1;
-    m->timing = mt;
+    store_join_timing(m, tm, wall, t0, false);  // (an enumeration finds no hits: the shards' timings count none)
     *out = res.release();
     return VSC_OK;
     });

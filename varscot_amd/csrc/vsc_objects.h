@@ -1,5 +1,6 @@
 // vsc_objects.h - the objects behind the opaque handles of include/varscot_hip.h, shared by the host-side
-// translation units of the library (vsc_api.cpp, vsc_multi.cpp).  Not installed.
+// translation units of the library (vsc_api.cpp, vsc_multi.cpp, vsc_regions.cpp) and by the device stand-in of the CPU
+// tests (tools/multi_tsan/stub_device.cpp).  Not installed.
 #pragma once
 
 #include <string>
@@ -57,12 +58,33 @@ bool host_timing_on();
 
 }  // namespace vsc
 
+// The events of a context (vsc_ctx::ev), by what its stream has reached when they are recorded.  A search pass records
+// kEvPassStart .. kEvSinkEnd and kEvPrepEnd: prep_ms = pass start -> prep end, scan_ms = search start -> end, sort_ms = search
+// end -> sink start, finalize_ms = sink start -> end (the sink's last stage), total_ms = pass start -> sink end.  The index
+// build has a pair of its own: it runs inside a search call, before the first pass.  The calls that are no search pass
+// (scoring, forest, merge, enumeration) time their one or two stages with the first four events under the kEvStage names.
+enum vsc_event {
+    kEvPassStart = 0,
+    kEvSearchStart,
+    kEvSearchEnd,
+    kEvSinkStart,
+    kEvSinkEnd,
+    kEvIndexStart,
+    kEvIndexEnd,
+    kEvPrepEnd,
+    kEvCount,
+    kEvStageStart = kEvPassStart,
+    kEvStageEnd = kEvSearchStart,
+    kEvStage2Start = kEvSearchEnd,
+    kEvStage2End = kEvSinkStart,
+};
+
 struct vsc_ctx {
     int device = 0;
     int n_cus = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t ev[kEvCount] = {};  // by vsc_event
     std::string err;
     vsc_timing timing{};
     vsc_debug_params dbg = vsc::default_debug_params();  // test / experiment hooks (include/varscot_hip_debug.h)
