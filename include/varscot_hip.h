@@ -709,6 +709,66 @@ int vsc_score_classify_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hi
                             const double *guide_activity, const vsc_rf_model *model, uint64_t first, uint64_t count, void *votes_dev,
                             uint16_t *votes_host, double *mit_host);
 
+/*
+ * Per-guide summary and selection BY THE CLASSIFIER: how many of a guide's off-targets does the forest call active, and which
+ * are its most probably active sites - without the records.  votes(h) is the number vsc_score_classify_hits writes for hit h
+ * for the same genome, guides, guide_activity and model (trees voting class "1"; the row from the guide and the site's 23 bases
+ * in read orientation, the activity that of the hit's guide).  The counted hits of guide i are exactly those of
+ * vsc_search_summary: the hits vsc_search returns, minus the one at exclude[i] if it is a hit.  Over them:
+ *   votes_sum     sum of votes(h): the expected number of active off-targets * n_trees
+ *   active        hits with 2 * votes >  n_trees (class "1")
+ *   ties          hits with 2 * votes == n_trees
+ *   active_nm[k]  the active ones with NM = k
+ * Every field is a sum of integers: independent of the order of the records, exact when passes or genome shards are added.
+ * The forest is walked over the search kernel's records where they lie (one word of votes beside every record slot); the
+ * rows and the selection are taken from those words: no sort of all hits, no 16-byte records, no votes leave the device.
+ * Selection (vsc_select_votes): of the counted hits with votes >= min_votes (0: no floor) the first top_k (0: no limit) in
+ * the total order votes descending, strand '+' before '-', global position ascending - vsc_search_select's tie-break.  The
+ * result is an ordinary vsc_hits sorted as vsc_search sorts it that holds the survivors only; their votes are what
+ * vsc_score_classify_hits gives on that (small) result.  Selection composes over genome shards as vsc_search_select's does.
+ * cls, cls->model, cls->guide_activity (n_guides > 0) or select NULL, a non-zero reserved field, a model of 0 trees or of
+ * more than the 16-bit votes hold (65 535), an excluded locus vsc_search_summary refuses: VSC_ERR_INVALID.  n_guides == 0:
+ * VSC_OK, nothing is launched.  out (optional) / summary (optional): the rows vsc_search_summary writes, from the same search.
+ * vsc_ctx_timing afterwards: as after vsc_search_summary / vsc_search_select, with score_ms = the classify kernel (in neither
+ * sort_ms nor finalize_ms); hits = all hits found.
+ * Replaces, for a screen: variant_processing/merge_output_bam.h:696-708 (feature rows as text) +
+ * classification/classificationPipeline.R:21-49 (read them back, predict) + a per-guide aggregate of the predictions.
+ */
+typedef struct {
+    uint64_t votes_sum;     /* sum of votes(h) over the counted hits: expected active off-targets * n_trees */
+    uint64_t active;        /* counted hits with 2 * votes >  n_trees  (class "1") */
+    uint64_t ties;          /* counted hits with 2 * votes == n_trees */
+    uint64_t active_nm[9];  /* the active ones by NM */
+} vsc_guide_votes;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_guide_votes) == 96, "vsc_guide_votes layout");
+#else
+_Static_assert(sizeof(vsc_guide_votes) == 96, "vsc_guide_votes layout");
+#endif
+typedef struct {
+    uint32_t top_k;      /* hits kept per guide, best first by (votes desc, strand, position); 0 = no limit */
+    uint32_t min_votes;  /* keep hits with votes >= min_votes; 0 = no floor */
+    uint32_t reserved[2];
+} vsc_select_votes;
+typedef struct {
+    const vsc_rf_model *model;     /* the forest */
+    const double *guide_activity;  /* on-target activity per read (n_guides values) */
+    uint32_t reserved[2];
+} vsc_classify;
+int vsc_search_summary_classified(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                                  const vsc_search_params *params, const vsc_locus *exclude, const vsc_classify *cls,
+                                  vsc_guide_summary *out /* optional */, vsc_guide_votes *out_votes);
+int vsc_search_select_classified(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                                 const vsc_search_params *params, const vsc_select_votes *select, const vsc_classify *cls,
+                                 const vsc_locus *exclude, vsc_guide_summary *summary /* optional */,
+                                 vsc_guide_votes *votes_rows /* optional */, vsc_hits **out);
+/* vsc_search_summary_classified over the device set: every shard summarises its own windows on its own context, the rows are
+ * added on the host (as vsc_multi_search_summary adds them).  (Selection by votes over several devices is not offered: the
+ * re-selection on the result device would need the votes of merged records, which no shard holds there.) */
+int vsc_multi_search_summary_classified(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                        const vsc_search_params *params, const vsc_locus *exclude, const vsc_classify *cls,
+                                        vsc_guide_summary *out /* optional */, vsc_guide_votes *out_votes);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -197,6 +197,20 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides
     return VSC_OK;
 }
 
+// (vsc_multi_search_summary_classified: the stand-in has no forest - every stub hit gets one vote and is no active one)
+int vsc_search_summary_classified(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                                  const vsc_locus *ex, const vsc_classify *, vsc_guide_summary *out, vsc_guide_votes *out_votes)
+{
+    std::vector<vsc_guide_summary> rows(n_guides);
+    const int rc = vsc_search_summary(ctx, g, guides, n_guides, p, ex, rows.data());
+    for (uint32_t i = 0; rc == VSC_OK && i < n_guides; ++i) {
+        if (out) out[i] = rows[i];
+        out_votes[i] = vsc_guide_votes{};
+        out_votes[i].votes_sum = rows[i].nm[0];
+    }
+    return rc;
+}
+
 // (the region-aware sinks: the stand-in has no regions - its hits count as inside)
 int vsc_search_summary_regions(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
                                const vsc_locus *ex, const vsc_regions *, vsc_guide_summary *out_all, vsc_guide_summary *out_in)

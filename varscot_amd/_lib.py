@@ -23,6 +23,9 @@ N_FEATURES = 442
 SUMMARY_DTYPE = np.dtype([("mit_sum", "<u8"), ("nm", "<u8", (9,)), ("mit_ub", "<u8"), ("on_target", "<u4"),
                           ("reserved", "<u4")])
 assert SUMMARY_DTYPE.itemsize == 96
+# vsc_guide_votes (vsc_search_summary_classified): 96 bytes per guide
+VOTES_DTYPE = np.dtype([("votes_sum", "<u8"), ("active", "<u8"), ("ties", "<u8"), ("active_nm", "<u8", (9,))])
+assert VOTES_DTYPE.itemsize == 96
 # vsc_locus: an excluded locus (contig == 0xFFFFFFFF: none)
 LOCUS_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
 
@@ -101,6 +104,19 @@ class MultiTiming(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class SelectVotes(C.Structure):
+    """vsc_select_votes: per guide, the top_k hits by the forest's votes among those >= min_votes (0 = no limit / no floor)."""
+    _fields_ = [("top_k", C.c_uint32), ("min_votes", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class Classify(C.Structure):
+    """vsc_classify: the forest and the reads' on-target activities of the classified sinks."""
+    _fields_ = [("model", C.POINTER(RfModel)), ("guide_activity", C.c_void_p), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(SelectVotes) == 16 and C.sizeof(Classify) == 24
 
 
 class MultiScore(C.Structure):
@@ -227,6 +243,10 @@ SYMBOLS = [
     ("vsc_rf_predict", C.c_int, [_vp, C.POINTER(RfModel), _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_rf_predict_packed", C.c_int, [_vp, C.POINTER(RfModel), _vp, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_score_classify_hits", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(RfModel), C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    ("vsc_search_summary_classified", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, C.POINTER(Classify), _vp, _vp]),
+    ("vsc_search_select_classified", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(SelectVotes),
+                                               C.POINTER(Classify), _vp, _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_multi_search_summary_classified", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, C.POINTER(Classify), _vp, _vp]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)

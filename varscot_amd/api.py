@@ -120,6 +120,22 @@ def _select(top_k, min_score):
     return s
 
 
+def _classify(forest, activity, n):
+    """vsc_classify for a classifier.Forest and one on-target activity per guide; returns (struct, what it points at)."""
+    act = np.ascontiguousarray(activity, dtype=np.float64)
+    if len(act) != n:
+        raise ValueError("one on-target activity per guide")
+    model = _lib.RfModel(forest.n_trees, forest.n_nodes, ptr(forest.status), ptr(forest.feature), ptr(forest.left), ptr(forest.right),
+                         ptr(forest.split), ptr(forest.node_class))
+    return _lib.Classify(C.pointer(model), ptr(act), (C.c_uint32 * 2)(0, 0)), (model, act)
+
+
+def expected_active(votes_rows, n_trees):
+    """The expected number of active off-targets per guide - the sum of the forest's probabilities votes / n_trees over the
+    guide's counted hits - from the VOTES_DTYPE rows of summarize_classified."""
+    return votes_rows["votes_sum"].astype(np.float64) / float(n_trees)
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -451,6 +467,44 @@ class Genome:
                                               ptr(ex), ptr(rows), ptr(inside), C.byref(h)), self.ctx._h)
         hits = Hits(self, h, codes)
         return (hits, rows, inside) if summary else hits
+
+    def summarize_classified(self, guides, max_mismatches, forest, activity, extra_pam=None, algorithm="auto", exclude=None):
+        """vsc_search_summary_classified: summarize() and, from the same search, the classifier's rows - per guide the sum of
+        the forest's votes over the counted hits, the hits it calls active (2 * votes > n_trees), the ties and the active
+        ones by NM - without the records.  forest: a classifier.Forest; activity: the on-target activity per guide.
+        Returns (SUMMARY_DTYPE rows, VOTES_DTYPE rows)."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        cls, keep = _classify(forest, activity, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        votes = np.zeros(len(codes), dtype=_lib.VOTES_DTYPE)
+        check(lib().vsc_search_summary_classified(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), C.byref(cls),
+                                                  ptr(out), ptr(votes)), self.ctx._h)
+        del keep
+        return out, votes
+
+    def search_select_classified(self, guides, max_mismatches, forest, activity, top_k=0, min_votes=0, extra_pam=None,
+                                 algorithm="auto", exclude=None, summary=False):
+        """vsc_search_select_classified: per guide, of the hits search() would return (minus the excluded locus), those with at
+        least min_votes of the forest's votes and of them the top_k best by (votes descending, strand, position); 0 = no floor
+        / no limit.  Returns Hits sorted as search() sorts them (forest.classify_hits gives the survivors' votes) - or, with
+        summary=True, (Hits, SUMMARY_DTYPE rows, VOTES_DTYPE rows) over all counted hits from the one search."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        cls, keep = _classify(forest, activity, len(codes))
+        sel = _lib.SelectVotes(int(top_k), int(min_votes), (C.c_uint32 * 2)(0, 0))
+        rows = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if summary else None
+        votes = np.zeros(len(codes), dtype=_lib.VOTES_DTYPE) if summary else None
+        h = C.c_void_p()
+        check(lib().vsc_search_select_classified(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), C.byref(cls),
+                                                 ptr(ex), ptr(rows), ptr(votes), C.byref(h)), self.ctx._h)
+        del keep
+        hits = Hits(self, h, codes)
+        return (hits, rows, votes) if summary else hits
 
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False):
@@ -785,6 +839,20 @@ class MultiGenome:
         self.multi._check(lib().vsc_multi_search_summary_regions(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
                                                                  regions._h, ptr(out), ptr(inside)))
         return out, inside
+
+    def summarize_classified(self, guides, max_mismatches, forest, activity, extra_pam=None, algorithm="auto", exclude=None):
+        """vsc_multi_search_summary_classified: Genome.summarize_classified over the shards, both row sets added on the host."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = Genome._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        cls, keep = _classify(forest, activity, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        votes = np.zeros(len(codes), dtype=_lib.VOTES_DTYPE)
+        self.multi._check(lib().vsc_multi_search_summary_classified(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
+                                                                    C.byref(cls), ptr(out), ptr(votes)))
+        del keep
+        return out, votes
 
     def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
                       summary=False, regions=None, region_scope="keep"):

@@ -34,6 +34,15 @@
 // with -A and -T the -T file gains a last column `region`, with -E and -L every -L line a 7th column.  name prints the 4th
 // column of that BED line, or chrom:start-end as the line has them if it has only three; coords always the latter; - if the
 // hit is in no interval.  Without -N every output is what it was.
+// -F model.vscrf with -C activity.txt (the on-target activity table the mergers read: guideId, sequence, activity per line; every
+// guide needs a line) adds what the CLASSIFIER says of every guide's off-targets (vsc_search_summary_classified) - the columns
+//   rfExpectedActive rfActive rfTies ra0 .. ra<M>
+// = the sum of the forest's probabilities (votes / trees) over the counted hits, the hits it calls active (more than half of the
+// trees), those with exactly half, and the active ones by mismatch count - behind all other columns, from the same search unless
+// -A or a listing by MIT score need one of their own.  With -T, -r votes ranks the listing by the forest's votes instead of the
+// MIT score (vsc_search_select_classified; -r mit is the default): -K still applies, -V MIN lists only off-targets with at least
+// MIN votes (-S belongs to -r mit), the ranks follow (votes descending, '+' before '-', position) and the listing gains a last
+// column rfVotes.  -r votes runs on one device and without -A.  Without -F every output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -43,6 +52,7 @@
 #include <map>
 #include <sstream>
 
+#include "forest_host.hpp"
 #include "merge_host.hpp"
 
 using namespace vsc_host;
@@ -75,6 +85,10 @@ int main(int argc, char **argv)
         {'L', "list-guides", "Path to a BED6 file (.bed) that receives the -E candidates: chrom start end guideId 0 strand", false},
         {'N', "region-names", "name | coords: add the interval a hit lies in to the -T file (of the -A regions) and the interval a guide "
                               "was found in to the -L file (of the -E targets), as the BED line's 4th column or as chrom:start-end", false},
+        {'F', "forest", "Path to a classifier (.vscrf): adds the columns rfExpectedActive rfActive rfTies ra0 .. ra<M> (needs -C)", false},
+        {'C', "activity", "Path to the on-target activities (guideId, sequence, activity per line) of the guides, for -F", false},
+        {'r', "rank-by", "mit (default) | votes: rank the -T listing by MIT score or by the classifier's votes (votes needs -F; adds the column rfVotes)", false},
+        {'V', "min-votes", "With -r votes: list only off-targets with at least this many of the forest's votes (default: no floor)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -252,6 +266,34 @@ int main(int argc, char **argv)
         }
     }
 
+    // -F / -C / -r / -V: the classifier
+    const bool classified = opts[22].set;
+    if (opts[22].set != opts[23].set || (classified && !has_extension(opts[22].value, {"vscrf"}))) {
+        std::fprintf(stderr, "%s: the classifier needs both -F (a .vscrf forest) and -C (the guides' on-target activities)\n", argv[0]);
+        return 1;
+    }
+    if (opts[24].set && opts[24].value != "mit" && opts[24].value != "votes") {
+        std::fprintf(stderr, "%s: -r takes mit or votes, not '%s'\n", argv[0], opts[24].value.c_str());
+        return 1;
+    }
+    const bool by_votes = opts[24].set && opts[24].value == "votes";
+    vsc_select_votes vsel{};
+    vsel.top_k = sel.top_k;
+    if (by_votes && (!classified || !listing || annotated || opts[9].set || devices.size() != 1)) {
+        std::fprintf(stderr, "%s: -r votes ranks the -T listing by the classifier: give -T, -F and -C, on one device, without -A and -S\n", argv[0]);
+        return 1;
+    }
+    if (opts[25].set) {
+        const std::string &v = opts[25].value;
+        char *vend = nullptr;
+        const long long k = std::strtoll(v.c_str(), &vend, 10);
+        if (!by_votes || v.empty() || *vend || k < 0 || k > 65535) {
+            std::fprintf(stderr, "%s: -V takes a number of votes, 0 .. 65535, with -r votes, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        vsel.min_votes = (uint32_t)k;
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_genome *genome = nullptr;
     vsc_multi *multi = nullptr;
@@ -411,7 +453,29 @@ int main(int argc, char **argv)
         std::vector<vsc_guide_summary> sum(codes.size()), sum_in(annotated ? codes.size() : 0);
         const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
         const uint32_t n_codes = (uint32_t)codes.size();
-        if (annotated && listing) {  // without -X the listing is not filtered: the rows then come from a second search, a summary call
+        // -F / -C: the forest over the feature matrix's columns, one activity per guide
+        vsc_forest::Forest forest;
+        vsc_rf_model model{};
+        std::vector<double> activity(classified ? codes.size() : 0);
+        std::vector<vsc_guide_votes> votes_rows(classified ? codes.size() : 0);
+        vsc_classify cls{};
+        if (classified) {
+            forest = vsc_forest::load_forest(opts[22].value);
+            vsc_forest::bind_features(forest, [](const std::string &) { return true; });
+            model = vsc_forest::model_of(forest);
+            const auto table = vsc_merge::read_tuscan(opts[23].value);
+            for (size_t i = 0; i < ids.size(); ++i) {
+                auto it = table.find(ids[i]);
+                if (it == table.end()) throw std::runtime_error("-C: no on-target activity for guide '" + ids[i] + "'");
+                activity[i] = it->second;
+            }
+            cls.model = &model;
+            cls.guide_activity = activity.data();
+        }
+        if (by_votes) {
+            st = vsc_search_select_classified(ctx, genome, codes.data(), n_codes, &p, &vsel, &cls, ex, sum.data(), votes_rows.data(), &hits);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        } else if (annotated && listing) {  // without -X the listing is not filtered: the rows then come from a second search, a summary call
             const vsc_region_filter *flt = opts[13].set ? &filter : nullptr;
             vsc_guide_summary *rows_in = flt ? sum_in.data() : nullptr;
             st = multi ? vsc_multi_search_select_regions(multi, mgenome, codes.data(), n_codes, &p, &sel, flt, ex, sum.data(), rows_in, &hits)
@@ -431,11 +495,18 @@ int main(int argc, char **argv)
             st = vsc_search_select(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, &sel, ex, sum.data(), &hits);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         } else if (multi) {
-            st = vsc_multi_search_summary(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
+            st = classified ? vsc_multi_search_summary_classified(multi, mgenome, codes.data(), n_codes, &p, ex, &cls, sum.data(), votes_rows.data())
+                            : vsc_multi_search_summary(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
         } else {
-            st = vsc_search_summary(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
+            st = classified ? vsc_search_summary_classified(ctx, genome, codes.data(), n_codes, &p, ex, &cls, sum.data(), votes_rows.data())
+                            : vsc_search_summary(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+        if (classified && !by_votes && (annotated || listing)) {  // (those calls take no forest: the classifier's rows from a search of their own)
+            st = multi ? vsc_multi_search_summary_classified(multi, mgenome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data())
+                       : vsc_search_summary_classified(ctx, genome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
         }
 
         std::string text = "#guideId\tguideSeq\tmitSpecScore\tofftargetCount\tonTargetFound";
@@ -445,6 +516,10 @@ int main(int argc, char **argv)
             text += "\tregionMitSpecScore\tregionCount";
             for (long k = 0; k <= mm; ++k) text += "\trmm" + std::to_string(k);
             text += "\tregionMitHitSum";
+        }
+        if (classified) {
+            text += "\trfExpectedActive\trfActive\trfTies";
+            for (long k = 0; k <= mm; ++k) text += "\tra" + std::to_string(k);
         }
         text += '\n';
         char buf[64];
@@ -467,6 +542,12 @@ int main(int argc, char **argv)
                 for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(r.nm[k]);
                 std::snprintf(buf, sizeof buf, "%.6f", (double)r.mit_sum * 0x1p-24);
                 text += '\t' + std::string(buf);
+            }
+            if (classified) {
+                const vsc_guide_votes &v = votes_rows[i];
+                std::snprintf(buf, sizeof buf, "%.6f", (double)v.votes_sum / (double)model.n_trees);
+                text += '\t' + std::string(buf) + '\t' + std::to_string(v.active) + '\t' + std::to_string(v.ties);
+                for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(v.active_nm[k]);
             }
             text += '\n';
         }
@@ -499,16 +580,20 @@ int main(int argc, char **argv)
                 score[i] = (uint32_t)std::nearbyint(mit[i] * 0x1p24);
                 order[i] = i;
             }
+            std::vector<uint16_t> votes(by_votes ? n : 0);  // -r votes: the survivors' votes, from the classifier over the small result
+            if (by_votes && n && vsc_score_classify_hits(ctx, genome, hits, codes.data(), n_codes, activity.data(), &model, 0, n, nullptr,
+                                                         votes.data(), nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {  // (stable: ties keep the result order)
                 if (rec[a].guide != rec[b].guide) return rec[a].guide < rec[b].guide;
-                return score[a] > score[b];
+                return by_votes ? votes[a] > votes[b] : score[a] > score[b];
             });
             const bool named = naming && annotated;  // -N: the -A interval each record lies in
             std::vector<uint32_t> in(named ? n : 0);
             if (named && n && (st = vsc_hits_locate(hits, regions, in.data())) != VSC_OK)
                 throw std::runtime_error(st == VSC_ERR_RANGE ? "could not name the regions of the hits" : vsc_last_error(hctx));
             std::string list = std::string("#guideId\trank\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tmitScore\tsequence") +
-                               (named ? "\tregion\n" : "\n");
+                               (named ? "\tregion" : "") + (by_votes ? "\trfVotes\n" : "\n");
             std::string window(VSC_READ_LEN, 'N');
             uint32_t rank = 0;
             for (uint64_t j = 0; j < n; ++j) {
@@ -523,7 +608,8 @@ int main(int argc, char **argv)
                 list += ids[h.guide] + '\t' + std::to_string(rank) + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' +
                         std::to_string(h.pos) + '\t' + std::to_string(h.pos + VSC_READ_LEN) + '\t' + (VSC_HIT_STRAND(h.info) ? '-' : '+') + '\t' +
                         std::to_string(VSC_HIT_NM(h.info)) + '\t' + (positions.empty() ? "-" : positions) + '\t' + buf + '\t' + window +
-                        (named ? '\t' + (in[order[j]] < region_desc.size() ? region_desc[in[order[j]]] : "-") : "") + '\n';
+                        (named ? '\t' + (in[order[j]] < region_desc.size() ? region_desc[in[order[j]]] : "-") : "") +
+                        (by_votes ? '\t' + std::to_string(votes[order[j]]) : "") + '\n';
             }
             std::ofstream out(hits_path);
             if (!out.is_open()) throw std::runtime_error("Could not open the -T path.");

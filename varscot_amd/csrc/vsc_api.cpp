@@ -213,7 +213,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     if (!ctx) return VSC_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (DeviceBuf *b : {&ctx->counters, &ctx->guides, &ctx->score_guides, &ctx->keys_a, &ctx->keys_b, &ctx->vals_a, &ctx->vals_b,
+    for (DeviceBuf *b : {&ctx->counters, &ctx->guides, &ctx->score_guides, &ctx->keys_a, &ctx->keys_b, &ctx->vals_a, &ctx->vals_b, &ctx->votes_rows,
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
@@ -1266,6 +1266,8 @@ struct PassFound {
     std::vector<uint64_t> sel_off;
     std::vector<SumSeg> sink_segs;
     std::vector<uint32_t> sink_tile0;
+    bool sink_staged = false;  // classify_pass has put the sinks' tables on the device: the sinks behind it take them as they are
+    bool classified = false;   // ... and its kernel has run between kEvClassStart and kEvClassEnd
 };
 
 // words within k substitutions of a 7-base segment (k < 0: none)
@@ -1559,17 +1561,21 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
 // prefix of their tile counts, for tiles of `tile` records.  The tables are staged in f (see PassFound).
 template <class Args> hipError_t sink_input(vsc_ctx *ctx, PassFound &f, uint32_t tile, bool excluded, Args &a)
 {
-    f.sink_segs.clear();
-    f.sink_tile0.assign(1, 0);
-    for (const SortSeg &sg : f.segs) {
-        f.sink_segs.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
-        f.sink_tile0.push_back(f.sink_tile0.back() + (sg.n_in + tile - 1) / tile);
+    if (!f.sink_staged) {
+        f.sink_segs.clear();
+        f.sink_tile0.assign(1, 0);
+        for (const SortSeg &sg : f.segs) {
+            f.sink_segs.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
+            f.sink_tile0.push_back(f.sink_tile0.back() + (sg.n_in + tile - 1) / tile);
+        }
     }
     const size_t seg_bytes = f.sink_segs.size() * sizeof(SumSeg), tile0_bytes = f.sink_tile0.size() * sizeof(uint32_t);
     const size_t tile0_at = (seg_bytes + 255) / 256 * 256;
-    VSC_TRY(ctx->sort_segs.ensure(tile0_at + tile0_bytes));
-    VSC_TRY(hipMemcpyAsync(ctx->sort_segs.p, f.sink_segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSC_TRY(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, f.sink_tile0.data(), tile0_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (!f.sink_staged) {
+        VSC_TRY(ctx->sort_segs.ensure(tile0_at + tile0_bytes));
+        VSC_TRY(hipMemcpyAsync(ctx->sort_segs.p, f.sink_segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+        VSC_TRY(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, f.sink_tile0.data(), tile0_bytes, hipMemcpyHostToDevice, ctx->stream));
+    }
     a.recs = (const uint64_t *)ctx->keys_a.p;
     a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
     a.segs = (const SumSeg *)ctx->sort_segs.p;
@@ -1687,6 +1693,73 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
     return VSC_OK;
 }
 
+// the forest calls further down, which classify_pass shares with vsc_score_classify_hits
+int prepare_forest(vsc_ctx *ctx, const vsc_rf_model *model, const char *who);
+void fill_forest(RfArgs &a, const vsc_ctx *ctx);
+int resident_ranks(vsc_ctx *ctx, const double *guide_activity, uint32_t n_guides);
+
+// Classify stage (vsc_search_*_classified), between find_pass and the sinks: rf_predict_kernel walks the forest (made resident
+// by prepare_forest, the reads' activity ranks by resident_ranks, the interleaved planes by ensure_hl - all before the first
+// pass) over the records where the search kernel left them and leaves every record slot's votes in ctx->vals_b, one word per
+// slot of every tile of kSumTile - the layout of SelectArgs::score, which select_pass then takes as its keys.  The sinks'
+// tables it stages serve the sinks behind it.  Few rows: the trees are split over several workgroups per row tile, the votes
+// meet in atomics.  Nothing is read back: the kernel's time (kEvClassStart -> kEvClassEnd) is taken at the end of the pass.
+int classify_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, uint32_t n_reads, bool excluded)
+{
+    if (f.segs.empty()) return VSC_OK;
+    RfArgs a{};
+    SelectArgs in{};
+    VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, in));
+    f.sink_staged = true;
+    fill_forest(a, ctx);
+    a.score.hl = genome->d_hl;
+    a.score.first_pos = (uint32_t)(genome->first_word * 32);
+    a.score.n_plane_words = genome->dev_words;
+    a.score.guides = (const uint2 *)ctx->guides.p;  // the pass's reads
+    a.act_rank = (const uint8_t *)ctx->forest.ranks.p + f.guide_base;
+    a.recs = in.recs;
+    a.vals = in.vals;
+    a.segs = in.segs;
+    a.seg_tile0 = in.seg_tile0;
+    a.n_segs = in.n_segs;
+    a.n_tiles = in.n_tiles;
+    a.pos_pad = in.pos_pad;
+    a.pos_base = in.pos_base;
+    a.excl = in.excl;
+    a.n_reads = n_reads;
+    a.n = (uint64_t)in.n_tiles * kSumTile;
+    VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.n * sizeof(uint32_t)));
+    a.slot_votes = (uint32_t *)ctx->vals_b.p;
+    const uint64_t groups = a.n / kRfRows;
+    a.tree_splits = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)2 * ctx->n_cus / groups, 32, ctx->forest.n_trees}));
+    if (a.tree_splits > 1) VSC_HIP(ctx, hipMemsetAsync(a.slot_votes, 0, (size_t)a.n * sizeof(uint32_t), ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvClassStart], ctx->stream));
+    VSC_HIP(ctx, launch_rf_predict(a, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvClassEnd], ctx->stream));
+    f.classified = true;
+    return VSC_OK;
+}
+
+hipError_t end_pass(vsc_ctx *ctx, PassFound &f, const char *lap, vsc_timing &t);
+
+// Votes summary sink (vsc_search_*_classified), behind classify_pass: votes_summary_kernel adds the votes words into the pass's
+// rows of ctx->votes_rows.  first: no sink ran before it in this pass (it opens finalize_ms); last: none follows (it ends the pass).
+int votes_summary_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, bool excluded, vsc_timing &t, bool first, bool last)
+{
+    VotesSummaryArgs a{};
+    if (!f.segs.empty()) {
+        VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
+        a.out = (unsigned long long *)ctx->votes_rows.p + (size_t)f.guide_base * kSumWords;
+        a.votes = (const uint32_t *)ctx->vals_b.p;
+        a.n_trees = ctx->forest.n_trees;
+        a.n_reads = n_reads;
+    }
+    if (first && last) VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
+    VSC_HIP(ctx, launch_votes_summary(a, ctx->stream));
+    if (last) VSC_HIP(ctx, end_pass(ctx, f, "votes summary + sync", t));
+    return VSC_OK;
+}
+
 // Summary sink (vsc_search_summary): summary_kernel adds the records where they lie into the pass's rows of ctx->sum_rows,
 // minus its loci in ctx->sum_excl if `excluded`.  No sort, no result buffer: finalize_ms times that kernel, sort_ms stays 0.
 // last = false (vsc_search_select with a summary): another sink follows and ends the pass; the kernel has run on return.
@@ -1717,8 +1790,9 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
 // placed record (ctx->vals_b: the scores), 512 bytes per read of the pass (histograms) and 12 bytes per candidate.  One read-back
 // (the reads' candidate counts), as find_pass has one for its counters.
 // reg / drop: the selection is made among the records on one side of the regions (SelectRegionArgs).
+// vote_trees (vsc_search_select_classified): the keys are the votes classify_pass left in ctx->vals_b, of a forest of that many trees.
 int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &sel, bool excluded, const RegionsView *reg = nullptr,
-                uint32_t drop = 0)
+                uint32_t drop = 0, uint32_t vote_trees = 0)
 {
     f.selected = true;
     if (f.n == 0) return VSC_OK;
@@ -1735,6 +1809,7 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     VSC_HIP(ctx, ctx->sel_hist.ensure((size_t)n_reads * kSelBins * sizeof(uint32_t)));
     VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.n_tiles * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
     a.min_score = sel.min_score;
+    a.vote_trees = vote_trees;
     a.top_k = sel.top_k;
     a.n_reads = n_reads;
     // enough workgroups for every CU, few table flushes per region
@@ -1974,6 +2049,13 @@ struct SearchPlan {
     int (*deliver)(void *, vsc_hits *, uint32_t, uint32_t, vsc_timing &) = nullptr;
     void *deliver_self = nullptr;
     bool keep_bases = false;  // the seed search keeps the sites' bases: the hits' feature rows are written with the records
+    // vsc_search_*_classified: the forest and the activities (checked after search_setup), the votes rows to write (null: not
+    // wanted), the selection by votes (select_votes != null: the call takes one)
+    bool classifies = false;
+    const vsc_classify *classify = nullptr;
+    vsc_guide_votes *votes_rows = nullptr;
+    bool selects_votes = false;
+    const vsc_select_votes *select_votes = nullptr;
 };
 
 // The one pass loop behind every search entry point: search_setup; the call's state on the device (excluded loci, regions,
@@ -1990,6 +2072,14 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     if (per_batch && !p.deliver) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null callback");
     if (p.selects && !p.select) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
     if (p.selects && (p.select->reserved[0] || p.select->reserved[1])) return fail_in(ctx, VSC_ERR_INVALID, p.who, "reserved fields must be 0");
+    if (p.classifies) {
+        if (!p.classify || !p.classify->model || (n_guides && !p.classify->guide_activity) || (p.selects_votes && !p.select_votes))
+            return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
+        if (p.classify->reserved[0] || p.classify->reserved[1] || (p.select_votes && (p.select_votes->reserved[0] || p.select_votes->reserved[1])))
+            return fail_in(ctx, VSC_ERR_INVALID, p.who, "reserved fields must be 0");
+        if (p.classify->model->n_trees == 0 || p.classify->model->n_trees > 65535u)
+            return fail_in(ctx, VSC_ERR_INVALID, p.who, "a forest of 0 trees, or of more than the 16-bit votes hold");
+    }
     std::vector<uint64_t> excl;
     if ((rc = excluded_loci(ctx, genome, p.exclude, n_guides, p.who, excl)) != VSC_OK) return rc;
     RegionsView reg{};
@@ -1998,7 +2088,25 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     const bool rows = p.rows || p.rows_in;
     if ((rc = upload_summary_state(ctx, n_guides, rows, excl, p.rows_in != nullptr)) != VSC_OK) return rc;
     // nothing to decide: the records go to the sort as the search hands them over
-    const bool selecting = p.select && (p.select->top_k || p.select->min_score || !excl.empty() || p.filter);
+    vsc_select by_votes{};  // the selection by votes in select_pass's terms
+    if (p.select_votes) {
+        by_votes.top_k = p.select_votes->top_k;
+        by_votes.min_score = p.select_votes->min_votes;
+    }
+    const vsc_select *const select = p.select_votes ? &by_votes : p.select;
+    const bool selecting = select && (select->top_k || select->min_score || !excl.empty() || p.filter);
+    // the classifier runs when something reads its votes: the rows, or a selection that decides anything
+    const bool classifying = p.classifies && n_guides && (p.votes_rows || selecting);
+    if (classifying) {
+        if ((rc = prepare_forest(ctx, p.classify->model, p.who)) != VSC_OK) return rc;
+        if ((rc = resident_ranks(ctx, p.classify->guide_activity, n_guides)) != VSC_OK) return rc;
+        VSC_HIP(ctx, ensure_hl(ctx, genome));
+        if (p.votes_rows) {
+            VSC_HIP(ctx, ctx->votes_rows.ensure((size_t)n_guides * sizeof(vsc_guide_votes)));
+            VSC_HIP(ctx, hipMemsetAsync(ctx->votes_rows.p, 0, (size_t)n_guides * sizeof(vsc_guide_votes), ctx->stream));
+        }
+    }
+    const uint32_t vote_trees = classifying && p.select_votes ? p.classify->model->n_trees : 0u;
     const uint32_t step = per_batch && p.batch_reads && p.batch_reads <= (uint32_t)kMaxPassReads ? p.batch_reads : (uint32_t)kMaxPassReads;
 
     std::unique_ptr<vsc_hits, int (*)(vsc_hits *)> hits(nullptr, vsc_hits_free);
@@ -2022,11 +2130,21 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
         const uint64_t projected = !per_batch && first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
         PassFound f;
         rc = find_pass(ctx, genome, guides + first, count, first, params, p.keep_bases && t.algorithm == VSC_ALGO_SEED, t, f);
+        const bool votes_rows = classifying && p.votes_rows;
+        if (rc == VSC_OK && classifying) rc = classify_pass(ctx, genome, f, count, !excl.empty());
         // (with another sink to follow, the summary leaves the end of the pass - and finalize_ms - to the sort)
-        if (rc == VSC_OK && rows) rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone, p.rows_in ? &reg : nullptr);
-        if (rc == VSC_OK && selecting) rc = select_pass(ctx, f, count, *p.select, !excl.empty(), p.filter ? &reg : nullptr, p.filter ? p.filter->scope : 0u);
+        if (rc == VSC_OK && rows) rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone && !votes_rows, p.rows_in ? &reg : nullptr);
+        if (rc == VSC_OK && votes_rows) rc = votes_summary_pass(ctx, f, count, !excl.empty(), t, !rows, p.records == Records::kNone);
+        if (rc == VSC_OK && selecting)
+            rc = select_pass(ctx, f, count, *select, !excl.empty(), p.filter ? &reg : nullptr, p.filter ? p.filter->scope : 0u, vote_trees);
         if (rc == VSC_OK && p.records != Records::kNone) rc = sort_pass(ctx, genome, f, hits.get(), used, projected, t);
         if (rc != VSC_OK) return rc;
+        if (f.classified) {  // (the pass has ended: its stream is idle)
+            float ms = 0;
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvClassStart], ctx->ev[kEvClassEnd]));
+            t.score_ms += ms;
+            if (p.records != Records::kNone) t.sort_ms -= ms;  // (sort_ms spans search end -> sink start: the classifier ran in between)
+        }
         used += f.n;
         if (per_batch) {
             seal_result();
@@ -2042,6 +2160,10 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
         const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
         if (p.rows) VSC_HIP(ctx, hipMemcpyAsync(p.rows, ctx->sum_rows.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
         if (p.rows_in) VSC_HIP(ctx, hipMemcpyAsync(p.rows_in, ctx->sum_rows_in.p, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (classifying && p.votes_rows) {
+        VSC_HIP(ctx, hipMemcpyAsync(p.votes_rows, ctx->votes_rows.p, (size_t)n_guides * sizeof(vsc_guide_votes), hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->timing = t;
@@ -2156,6 +2278,42 @@ int vsc_search_select_regions(vsc_ctx *ctx, const vsc_genome *genome, const uint
     if (!filter && summary_in) return fail(ctx, VSC_ERR_INVALID, "vsc_search_select_regions: summary_in without a filter");
     return search_select(ctx, genome, guides, n_guides, params, select, filter, exclude, summary_all, summary_in, out,
                          "vsc_search_select_regions");
+}
+
+int vsc_search_summary_classified(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                                  const vsc_search_params *params, const vsc_locus *exclude, const vsc_classify *cls,
+                                  vsc_guide_summary *out, vsc_guide_votes *out_votes)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (n_guides && !out_votes) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary_classified: null argument");
+    SearchPlan p("vsc_search_summary_classified", Records::kNone);
+    p.exclude = exclude;
+    p.rows = out;
+    p.classifies = true;
+    p.classify = cls;
+    p.votes_rows = out_votes;
+    return run_search(ctx, genome, guides, n_guides, params, p);
+    });
+}
+
+int vsc_search_select_classified(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                                 const vsc_search_params *params, const vsc_select_votes *select, const vsc_classify *cls,
+                                 const vsc_locus *exclude, vsc_guide_summary *summary, vsc_guide_votes *votes_rows, vsc_hits **out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    SearchPlan p("vsc_search_select_classified", Records::kAccumulate, out);
+    p.exclude = exclude;
+    p.rows = summary;
+    p.classifies = true;
+    p.classify = cls;
+    p.votes_rows = votes_rows;
+    p.selects_votes = true;
+    p.select_votes = select;
+    return run_search(ctx, genome, guides, n_guides, params, p);
+    });
 }
 
 // ---- guide discovery (kernels: vsc_enum.hip) -------------------------------------------------------------------------------
@@ -3205,6 +3363,24 @@ uint8_t activity_rank(const std::vector<double> &thr, double activity)
     return (uint8_t)(std::lower_bound(thr.begin(), thr.end(), activity) - thr.begin());  // thresholds strictly below
 }
 
+// The reads' activity ranks for the resident forest in ctx->forest.ranks: uploaded when the activities or the forest differ from
+// the last call's (vsc_score_classify_hits batch after batch, the passes of vsc_search_*_classified).
+int resident_ranks(vsc_ctx *ctx, const double *guide_activity, uint32_t n_guides)
+{
+    const uint64_t rank_key = hash_words(guide_activity, (size_t)n_guides * sizeof(double), ctx->forest.fingerprint ^ n_guides);
+    if (!ctx->forest.ranks.p || ctx->forest.ranks_key != rank_key || ctx->forest.ranks_n != n_guides) {
+        std::vector<uint8_t> ranks(std::max<uint32_t>(n_guides, 1));
+        for (uint32_t g = 0; g < n_guides; ++g) ranks[g] = activity_rank(ctx->forest.thresholds, guide_activity[g]);
+        ctx->forest.ranks_n = ~0u;
+        VSC_HIP(ctx, ctx->forest.ranks.ensure(ranks.size()));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->forest.ranks.p, ranks.data(), ranks.size(), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `ranks` goes out of scope
+        ctx->forest.ranks_key = rank_key;
+        ctx->forest.ranks_n = n_guides;
+    }
+    return VSC_OK;
+}
+
 // vsc_rf_predict / vsc_rf_predict_packed: the rows from the host (dense) or from host / device memory (packed)
 int rf_predict(vsc_ctx *ctx, const vsc_rf_model *model, const uint8_t *dense, const void *packed, int packed_on_device,
                const double *activity, uint64_t n, double *prob, uint8_t *cls, uint8_t *tie, const char *who)
@@ -3298,17 +3474,8 @@ int vsc_score_classify_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hi
     VSC_HIP(ctx, ensure_hl(ctx, genome));
     // the reads' activity ranks: uploaded when the activities or the forest differ from the last call's (a streamed search
     // classifies batch after batch with the same ones)
-    const uint64_t rank_key = hash_words(guide_activity, (size_t)n_guides * sizeof(double), ctx->forest.fingerprint ^ n_guides);
-    if (!ctx->forest.ranks.p || ctx->forest.ranks_key != rank_key || ctx->forest.ranks_n != n_guides) {
-        std::vector<uint8_t> ranks(std::max<uint32_t>(n_guides, 1));
-        for (uint32_t g = 0; g < n_guides; ++g) ranks[g] = activity_rank(ctx->forest.thresholds, guide_activity[g]);
-        ctx->forest.ranks_n = ~0u;
-        VSC_HIP(ctx, ctx->forest.ranks.ensure(ranks.size()));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->forest.ranks.p, ranks.data(), ranks.size(), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // `ranks` goes out of scope
-        ctx->forest.ranks_key = rank_key;
-        ctx->forest.ranks_n = n_guides;
-    }
+    const int rrc = resident_ranks(ctx, guide_activity, n_guides);
+    if (rrc != VSC_OK) return rrc;
     // 2 bytes (+ 8 with the MIT score) per hit of scratch: one pass for any result that fits the device at all
     uint64_t rows = 0;
     VSC_HIP(ctx, score_scratch(ctx, count, mit_host ? sizeof(double) : 0, votes_dev ? 0 : sizeof(uint16_t), 0, &rows));

@@ -293,6 +293,8 @@ struct RfTest {
     uint16_t pad;
 };
 
+struct SumSeg;  // (below: the per-guide summary)
+
 struct RfArgs {
     const uint32_t *nodes;      // [n_trees * n_nodes], tree-major
     const uint8_t *depth;       // [n_trees] steps from the root to the deepest terminal node
@@ -312,6 +314,20 @@ struct RfArgs {
     uint16_t *votes16;          // ... or 16-bit (fused path; tree_splits == 1)
     uint32_t tree_splits;       // gridDim.y: every workgroup row walks n_trees / tree_splits trees
     ScoreArgs score;            // fused path: hits, planes, reads (+ optional MIT output)
+    // classify in place (mode 3): the rows are the search kernel's records where they lie (`recs` non-null; the two forms
+    // SummaryArgs describes), 512 row slots per workgroup = a quarter of a tile of kSumTile; the votes go into one word per
+    // record slot of every tile (SelectArgs::score's layout; kSelDropped: sentinel, read beyond the pass, excluded locus), added
+    // with atomics into a zeroed array when tree_splits > 1.  score.hl / first_pos: the planes; score.guides and act_rank:
+    // per pass-local read
+    const uint64_t *recs;
+    const uint32_t *vals;
+    const SumSeg *segs;
+    const uint32_t *seg_tile0;
+    uint32_t n_segs, n_tiles;
+    uint32_t pos_pad, pos_base;
+    const uint64_t *excl;
+    uint32_t n_reads;
+    uint32_t *slot_votes;
 };
 
 // ---- per-guide summary (vsc_search_summary; summary_kernel in vsc_kernels.hip) ----------------------------------------------
@@ -343,6 +359,14 @@ struct SummaryArgs {
     unsigned long long *out;    // kSumWords per pass-local read, zeroed once per call
 };
 
+// Votes summary (vsc_search_summary_classified; votes_summary_kernel): SummaryArgs' input + the votes word of every record slot
+// (RfArgs::slot_votes), added into rows of kSumWords words per pass-local read, the layout of vsc_guide_votes: votes_sum, active,
+// ties, active_nm[0..8].
+struct VotesSummaryArgs : SummaryArgs {
+    const uint32_t *votes;
+    uint32_t n_trees, n_reads;
+};
+
 // ---- per-guide selection (vsc_search_select; select_*_kernel in vsc_kernels.hip) -------------------------------------------
 // An exact per-read radix select on the composite key  score (31 bits) << 33 | ~(strand << 32 | global position) (33 bits):
 // the larger key is the better hit (score descending, '+' before '-', position ascending), and keys are unique per read.
@@ -366,6 +390,8 @@ struct SelectArgs {
     uint32_t pos_pad, pos_base;
     const uint64_t *excl;       // per pass-local read, as SummaryArgs (null: none)
     uint32_t min_score;         // records below it are dropped
+    uint32_t vote_trees;        // 0: the score is rint(MIT * 2^24), computed in round 1; else the forest's tree count: `score` holds
+                                // the records' votes on entry (classify in place), min_score is a floor on them, linear bins
     uint32_t top_k;             // 0: no limit
     uint32_t n_reads;           // reads of the pass
     uint32_t tiles_per_block;   // kSelMinTilesPerBlock .. kSelMaxTilesPerBlock
@@ -445,6 +471,7 @@ struct SelectRegionArgs : SelectArgs {
 hipError_t launch_scan(const ScanArgs &args, int n_groups, bool extract, hipStream_t stream);
 hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream);
 hipError_t launch_summary_regions(const SummaryRegionArgs &args, hipStream_t stream);
+hipError_t launch_votes_summary(const VotesSummaryArgs &args, hipStream_t stream);
 hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream);      // round 1: scores + histograms
 hipError_t launch_select_score_regions(const SelectRegionArgs &args, hipStream_t stream);  // ... on one side of the regions only
 hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream);  // histograms -> thr, count

@@ -1043,9 +1043,27 @@ __device__ __forceinline__ uint32_t select_bin(uint32_t score)
     return 1u + 4u * e + mant;
 }
 
+// The key of the selection as a policy of rounds 1 and 2 (the later rounds see composite keys only): where a record's score
+// comes from and its monotone coarse bin.  SelectMitKey: rint(MIT * 2^24) computed in round 1, the logarithmic bins above.
+// SelectVotesKey (vsc_search_select_classified): the votes the classifier left in the score word (kSelDropped: not a counted hit);
+// votes lie evenly in 0 .. n_trees, so the bins are linear - 0 .. n_trees onto the kSelBins - 1 non-zero bins (the logarithmic
+// bins would put 512 .. 1000 votes into four).
+struct SelectMitKey {
+    static constexpr bool kStored = false;
+    static __device__ __forceinline__ uint32_t bin(const SelectArgs &, uint32_t score) { return select_bin(score); }
+};
+struct SelectVotesKey {
+    static constexpr bool kStored = true;
+    static __device__ __forceinline__ uint32_t bin(const SelectArgs &a, uint32_t votes)
+    {
+        return 1u + min(votes, a.vote_trees) * (uint32_t)(kSelBins - 2) / a.vote_trees;  // 1 .. kSelBins - 1
+    }
+};
+
 // record `at` of segment sg: pass-local read, strand << 32 | global position, mismatch mask; false: a sentinel
-template <bool kSeed>
-__device__ __forceinline__ bool select_decode(const SelectArgs &a, const SumSeg &sg, uint64_t at, uint32_t &read, uint64_t &locus, uint32_t &mask)
+// (Args: SelectArgs, or any struct with its recs, vals, pos_pad, pos_base - the classifier's RfArgs)
+template <bool kSeed, class Args>
+__device__ __forceinline__ bool select_decode(const Args &a, const SumSeg &sg, uint64_t at, uint32_t &read, uint64_t &locus, uint32_t &mask)
 {
     const uint64_t r = a.recs[at];
     if (kSeed) {
@@ -1063,7 +1081,7 @@ __device__ __forceinline__ bool select_decode(const SelectArgs &a, const SumSeg 
 }
 
 // the segment that holds tile `tile`: last s with seg_tile0[s] <= tile
-__device__ __forceinline__ uint32_t select_find_seg(const SelectArgs &a, uint32_t tile)
+template <class Args> __device__ __forceinline__ uint32_t select_find_seg(const Args &a, uint32_t tile)
 {
     uint32_t lo = 0, hi = a.n_segs;
     while (hi - lo > 1) {
@@ -1083,7 +1101,7 @@ __device__ __forceinline__ bool select_side(const SelectArgs &, uint32_t) { retu
 __device__ __forceinline__ bool select_side(const SelectRegionArgs &a, uint32_t pos) { return regions_contains(a.reg, pos) != (a.drop != 0); }
 
 // kFilter (vsc_search_select_regions): a record on the wrong side of the regions is dropped like the excluded locus.
-template <bool kSeed, bool kFilter>
+template <bool kSeed, bool kFilter, class Key = SelectMitKey>
 __global__ __launch_bounds__(kSelThreads) void select_score_kernel(const std::conditional_t<kFilter, SelectRegionArgs, SelectArgs> a)
 {
     __shared__ uint32_t s_hist[kSeed ? kRegionReads * kSelBins : 1];
@@ -1119,14 +1137,23 @@ __global__ __launch_bounds__(kSelThreads) void select_score_kernel(const std::co
             const uint64_t at = sg.in_off + i;
             uint32_t read, mask, score = kSelDropped;
             uint64_t locus;
-            if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus) &&
+            if constexpr (Key::kStored) {
+                // the classifier has been here: the word holds the record's votes, or kSelDropped for what is no counted hit
+                const uint32_t sc = a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t];
+                if (sc != kSelDropped && sc >= a.min_score && select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads &&
+                    select_side(a, (uint32_t)locus)) {
+                    score = sc;
+                    if (kSeed) atomicAdd(&s_hist[(read - sg.first_read) * kSelBins + Key::bin(a, sc)], 1u);
+                    else atomicAdd(&a.hist[(size_t)read * kSelBins + Key::bin(a, sc)], 1u);
+                }
+            } else if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus) &&
                 select_side(a, (uint32_t)locus)) {
                 int ub;
                 const uint32_t sc = (uint32_t)__builtin_rint(mit_score(mask, &ub) * 0x1p24);  // <= 100 * 2^24 < 2^31; as summary_kernel
                 if (sc >= a.min_score) {
                     score = sc;
-                    if (kSeed) atomicAdd(&s_hist[(read - sg.first_read) * kSelBins + select_bin(sc)], 1u);
-                    else atomicAdd(&a.hist[(size_t)read * kSelBins + select_bin(sc)], 1u);
+                    if (kSeed) atomicAdd(&s_hist[(read - sg.first_read) * kSelBins + Key::bin(a, sc)], 1u);
+                    else atomicAdd(&a.hist[(size_t)read * kSelBins + Key::bin(a, sc)], 1u);
                 }
             }
             a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t] = score;
@@ -1158,7 +1185,7 @@ __global__ __launch_bounds__(kSelThreads) void select_threshold_kernel(const Sel
 // Round 2, over the scores round 1 left: the records of the bins >= their read's threshold go, as composite key + mask, into
 // the read's candidate list (the lists' starts: prefix sums of the counts).  SEED: a score below every threshold of its
 // region - nearly all of them - is done with its 4 bytes; the record is read for the others only.
-template <bool kSeed>
+template <bool kSeed, class Key = SelectMitKey>
 __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(const SelectArgs a)
 {
     const uint32_t t = threadIdx.x;
@@ -1175,7 +1202,7 @@ __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(const Selec
             if (i >= sg.n) break;
             const uint32_t sc = a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t];
             if (sc == kSelDropped) continue;
-            const uint32_t bin = select_bin(sc);
+            const uint32_t bin = Key::bin(a, sc);
             if (kSeed && bin < region_thr) continue;  // (most records: below every threshold of the region, the record is not read)
             uint32_t read, mask;
             uint64_t locus;
@@ -1247,11 +1274,126 @@ __global__ __launch_bounds__(kSelThreads) void select_resolve_kernel(const Selec
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// per-guide votes summary (vsc_search_summary_classified): votes_sum, active, ties, active_nm[0..8]; VotesSummaryArgs
+// ------------------------------------------------------------------------------------------------
+// Over the votes words the classifier left beside the records (rf_predict_kernel, classify in place), tiled and accumulated as
+// summary_kernel does: every lane takes kSumItems CONSECUTIVE record slots - 32 bytes of votes, and 64 bytes of records of which
+// it reads only those the classifier counted, for the read and the mismatch mask - and keeps one running accumulator for the
+// read it is on, flushed when the read changes and at the end of the tile: into the region's LDS table (SEED), which goes out
+// with one agent-scope atomic per nonzero cell, or straight into the result (SCAN: the reads arrive mixed).
+template <bool kSeed>
+__global__ __launch_bounds__(kSumThreads) void votes_summary_kernel(const VotesSummaryArgs a)
+{
+    static_assert(kSumCounts == 2 + VSC_MAX_MISMATCHES + 1 && kSumWords == kSumCounts + 1, "vsc_guide_votes: votes_sum + active, ties, active_nm[9]");
+    __shared__ unsigned long long s_sum[kSeed ? kRegionReads : 1];
+    __shared__ uint32_t s_cnt[kSeed ? kRegionReads * kSumCounts : 1];
+    const uint32_t t = threadIdx.x;
+    if (kSeed) {
+        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSumCounts); i += kSumThreads) s_cnt[i] = 0;
+        for (uint32_t i = t; i < (uint32_t)kRegionReads; i += kSumThreads) s_sum[i] = 0;
+        block_sync();
+    }
+    const uint32_t tile_begin = blockIdx.x * kSumTilesPerBlock, tile_end = min(tile_begin + (uint32_t)kSumTilesPerBlock, a.n_tiles);
+    if (tile_begin >= tile_end) return;
+    uint32_t seg = select_find_seg(a, tile_begin);
+    auto flush_table = [&](const SumSeg &sg) {
+        block_sync();
+        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSumWords); i += kSumThreads) {
+            const uint32_t r = i / kSumWords, f = i % kSumWords;
+            unsigned long long v;
+            if (f == 0) {
+                v = s_sum[r];
+                s_sum[r] = 0;
+            } else {
+                v = s_cnt[r * kSumCounts + f - 1];
+                s_cnt[r * kSumCounts + f - 1] = 0;
+            }
+            if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
+        }
+        block_sync();
+    };
+    for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
+        if (tile >= a.seg_tile0[seg + 1]) {
+            if (kSeed) flush_table(a.segs[seg]);
+            while (tile >= a.seg_tile0[seg + 1]) ++seg;
+        }
+        const SumSeg sg = a.segs[seg];
+        const uint32_t slot0 = t * (uint32_t)kSumItems;  // this lane's slots of the tile
+        const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile + slot0;
+        uint32_t cur = ~0u, vsum = 0, act = 0, tie = 0;
+        uint64_t nm = 0;
+        auto flush = [&]() {
+            if (cur == ~0u) return;
+            if (kSeed) {
+                const uint32_t row = cur - sg.first_read;
+                if (vsum) atomicAdd(&s_sum[row], (unsigned long long)vsum);
+                if (act) atomicAdd(&s_cnt[row * kSumCounts], act);
+                if (tie) atomicAdd(&s_cnt[row * kSumCounts + 1], tie);
+#pragma unroll
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+                    const uint32_t c = (uint32_t)(nm >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    if (c) atomicAdd(&s_cnt[row * kSumCounts + 2 + k], c);
+                }
+            } else {
+                unsigned long long *o = a.out + (size_t)cur * kSumWords;
+                if (vsum) atomicAdd(&o[0], (unsigned long long)vsum);
+                if (act) atomicAdd(&o[1], (unsigned long long)act);
+                if (tie) atomicAdd(&o[2], (unsigned long long)tie);
+#pragma unroll
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+                    const uint32_t c = (uint32_t)(nm >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
+                    if (c) atomicAdd(&o[3 + k], (unsigned long long)c);
+                }
+            }
+            vsum = act = tie = 0;
+            nm = 0;
+        };
+        for (int k = 0; k < kSumItems; ++k) {
+            if (first + (uint32_t)k >= sg.n) break;
+            const uint32_t v = a.votes[(uint64_t)tile * kSumTile + slot0 + (uint32_t)k];
+            if (v == kSelDropped) continue;  // no counted hit: the record is not read
+            uint32_t read, mask;
+            uint64_t locus;
+            if (!select_decode<kSeed>(a, sg, sg.in_off + first + (uint32_t)k, read, locus, mask) || read >= a.n_reads) continue;
+            if (read != cur) {
+                flush();
+                cur = read;
+            }
+            vsum += v;
+            if (2u * v > a.n_trees) {
+                act += 1u;
+                nm += 1ull << (kSumCountBits * __popc(mask));
+            } else if (2u * v == a.n_trees) {
+                tie += 1u;
+            }
+        }
+        flush();
+    }
+    if (kSeed) flush_table(a.segs[seg]);
+}
+
+hipError_t launch_votes_summary(const VotesSummaryArgs &args, hipStream_t stream)
+{
+    if (args.n_tiles == 0) return hipSuccess;
+    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
+    if (args.vals)
+        hipLaunchKernelGGL(votes_summary_kernel<false>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    else
+        hipLaunchKernelGGL(votes_summary_kernel<true>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
 hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream)
 {
     if (args.n_tiles == 0) return hipSuccess;
     const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
-    if (args.vals)
+    if (args.vote_trees) {
+        if (args.vals)
+            hipLaunchKernelGGL((select_score_kernel<false, false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+        else
+            hipLaunchKernelGGL((select_score_kernel<true, false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    } else if (args.vals)
         hipLaunchKernelGGL((select_score_kernel<false, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
     else
         hipLaunchKernelGGL((select_score_kernel<true, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
@@ -1280,7 +1422,12 @@ hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream)
 {
     if (args.n_tiles == 0) return hipSuccess;
     const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
-    if (args.vals)
+    if (args.vote_trees) {
+        if (args.vals)
+            hipLaunchKernelGGL((select_compact_kernel<false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+        else
+            hipLaunchKernelGGL((select_compact_kernel<true, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
+    } else if (args.vals)
         hipLaunchKernelGGL(select_compact_kernel<false>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
     else
         hipLaunchKernelGGL(select_compact_kernel<true>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
@@ -1326,7 +1473,12 @@ __device__ __forceinline__ void rf_row_words(const uint32_t (&w)[16], uint32_t r
     r[19] = rank;
 }
 
-// kMode 0: dense rows, 1: packed rows, 2: rows computed here from the hits of a.score (score -> classify fused)
+// kMode 0: dense rows, 1: packed rows, 2: rows computed here from the hits of a.score (score -> classify fused),
+// 3 (SCAN records) / 4 (SEED records): classify in place - rows computed here from the search kernel's records where they lie.
+// Workgroup b takes row slots (b % 4) * 512 .. of tile b / 4 (tiles of kSumTile slots, addressed as summary_kernel and
+// select_score_kernel address them); a slot that holds no counted hit (beyond the segment, sentinel, read beyond the pass,
+// excluded locus) walks the forest as an all-zero row, as a dead row of the other modes does, and gets kSelDropped.  The site's
+// planes come from the interleaved planes at the record's global position - the shard's first (site_planes without the contig table).
 template <int kMode> __global__ __launch_bounds__(kRfRows) void rf_predict_kernel(const RfArgs a)
 {
     extern __shared__ uint32_t s_dyn[];
@@ -1344,7 +1496,20 @@ template <int kMode> __global__ __launch_bounds__(kRfRows) void rf_predict_kerne
     uint32_t *const s_bits = s_dyn;
     uint32_t *const s_tile = s_dyn + (pairs ? (size_t)kRfPairBitsBytes / sizeof(uint32_t) : (size_t)n_words * kRfRows);
     const uint64_t row = (uint64_t)blockIdx.x * kRfRows + t;
-    const bool live = row < a.n;
+    bool live = row < a.n;
+    uint32_t rec_read = 0;  // (modes 3, 4) pass-local read and strand << 32 | global position of the slot's record
+    uint64_t rec_locus = 0;
+    if (kMode >= 3) {
+        static_assert(kSumTile % kRfRows == 0, "a workgroup's row slots lie in one tile");
+        const uint32_t tile = blockIdx.x / (uint32_t)(kSumTile / kRfRows);
+        const uint32_t seg = select_find_seg(a, tile);
+        const SumSeg sg = a.segs[seg];
+        const uint32_t i = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile + (blockIdx.x % (uint32_t)(kSumTile / kRfRows)) * (uint32_t)kRfRows + t;
+        uint32_t mask;
+        live = i < sg.n && select_decode<kMode == 4>(a, sg, sg.in_off + i, rec_read, rec_locus, mask) && rec_read < a.n_reads &&
+               !(a.excl && a.excl[rec_read] == rec_locus) &&
+               (uint64_t)(((uint32_t)rec_locus - a.score.first_pos) >> 5) + 1u < a.score.n_plane_words;  // (every window of the shard: its planes are padded)
+    }
     if (kMode == 0) {
         // dense rows (the command-line tool's path): one byte load per test
         const uint32_t rank = live ? a.act_rank[row] : 0u;
@@ -1371,6 +1536,19 @@ template <int kMode> __global__ __launch_bounds__(kRfRows) void rf_predict_kerne
                     w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
                 }
                 rank = a.act_rank[row];
+            } else if (kMode >= 3) {
+                const uint32_t rel = (uint32_t)rec_locus - a.score.first_pos;
+                const uint64_t wi = rel >> 5;
+                const uint32_t sh = rel & 31u;
+                const uint2 w0 = a.score.hl[wi], w1 = a.score.hl[wi + 1];
+                uint32_t oh = funnel(w1.x, w0.x, sh) & kMask23, ol = funnel(w1.y, w0.y, sh) & kMask23;
+                if (rec_locus >> 32) {
+                    oh = revcomp_plane(oh);
+                    ol = revcomp_plane(ol);
+                }
+                const uint2 g = a.score.guides[rec_read];
+                feature_row_packed(g.x, g.y, oh, ol, w);
+                rank = a.act_rank[rec_read];
             } else {
                 // the row of hit `row`, as score_packed_kernel computes it - kept in registers, never stored
                 const vsc_hit h = a.score.hits[row];
@@ -1569,6 +1747,17 @@ template <int kMode> __global__ __launch_bounds__(kRfRows) void rf_predict_kerne
             if (k + 1 < nt) ones += n1 >> 31;
         }
     }
+    if (kMode >= 3) {
+        // one word per record slot (row = tile * kSumTile + slot): the votes, or the dropped marker - from the first tree split only
+        if (!live) {
+            if (blockIdx.y == 0) a.slot_votes[row] = kSelDropped;
+        } else if (a.tree_splits > 1) {
+            atomicAdd(&a.slot_votes[row], ones);
+        } else {
+            a.slot_votes[row] = ones;
+        }
+        return;
+    }
     if (!live) return;
     if (kMode == 2)
         a.votes16[row] = (uint16_t)ones;
@@ -1591,8 +1780,9 @@ hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream)
     // test bits + the tree tile (+ a sink node per chain)
     const size_t lds = args.compact == 2u ? (size_t)kRfPairBitsBytes + kRfPairTileBytes + 8 * kRfChains
                                           : n_words * kRfRows * sizeof(uint32_t) + (size_t)kRfTileBytes + 4 * kRfChains;
-    const int mode = args.dense ? 0 : (args.packed ? 1 : 2);
+    const int mode = args.recs ? (args.vals ? 3 : 4) : args.dense ? 0 : (args.packed ? 1 : 2);
     if (mode == 2 && args.tree_splits != 1) return hipErrorInvalidValue;
+    if (mode >= 3 && (args.n != (uint64_t)args.n_tiles * kSumTile || args.tree_splits == 0 || args.tree_splits > 65535u)) return hipErrorInvalidValue;
     auto go = [&](auto kernel) {
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -1601,6 +1791,8 @@ hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream)
     };
     if (mode == 0) return go(rf_predict_kernel<0>);
     if (mode == 1) return go(rf_predict_kernel<1>);
+    if (mode == 3) return go(rf_predict_kernel<3>);
+    if (mode == 4) return go(rf_predict_kernel<4>);
     return go(rf_predict_kernel<2>);
 }
 

@@ -793,6 +793,56 @@ int multi_summary(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guide
     });
 }
 
+// o += p, as the votes rows of genome shards add: every field is a sum of integers
+void add_votes_row(vsc_guide_votes &o, const vsc_guide_votes &p)
+{
+    o.votes_sum += p.votes_sum;
+    o.active += p.active;
+    o.ties += p.ties;
+    for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.active_nm[k] += p.active_nm[k];
+}
+
+// vsc_multi_search_summary_classified: multi_summary's route with the classifier's rows beside the (optional) plain ones
+int multi_summary_classified(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                             const vsc_locus *exclude, const vsc_classify *cls, vsc_guide_summary *out, vsc_guide_votes *out_votes)
+{
+    const std::string who = "vsc_multi_search_summary_classified";
+    return mguarded(m, [&]() -> int {
+    if (!m) return VSC_ERR_INVALID;
+    m->err.clear();
+    if (!g || g->multi != m || !params || !cls || !cls->model || (n_guides && (!guides || !out_votes || !cls->guide_activity)))
+        return mfail(m, VSC_ERR_INVALID, who + ": null argument");
+    if (cls->reserved[0] || cls->reserved[1]) return mfail(m, VSC_ERR_INVALID, who + ": reserved fields must be 0");
+    if (cls->model->n_trees == 0 || cls->model->n_trees > 65535u)
+        return mfail(m, VSC_ERR_INVALID, who + ": a forest of 0 trees, or of more than the 16-bit votes hold");
+    const int erc = check_excluded(m, g, exclude, n_guides, who);
+    if (erc != VSC_OK) return erc;
+    const auto t0 = clk::now();
+    const size_t n = m->ctx.size();
+    std::vector<int> rc(n, VSC_OK);
+    std::vector<std::vector<vsc_guide_summary>> part(n);
+    std::vector<std::vector<vsc_guide_votes>> part_votes(n);
+    std::vector<vsc_timing> tm(n);
+    on_all(n, [&](size_t r) {
+        if (!g->shard[r]) return;
+        if (out) part[r].resize(n_guides);
+        part_votes[r].resize(n_guides);
+        rc[r] = vsc_search_summary_classified(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, cls, out ? part[r].data() : nullptr,
+                                              part_votes[r].data());
+        (void)vsc_ctx_timing(m->ctx[r], &tm[r]);
+    });
+    for (size_t r = 0; r < n; ++r)
+        if (rc[r] != VSC_OK) return mfail(m, rc[r], "shard " + std::to_string(r) + ": " + vsc_last_error(m->ctx[r]));
+    const double wall = ms_between(t0, clk::now());
+    add_shard_rows(g, part, n_guides, out);
+    std::fill(out_votes, out_votes + n_guides, vsc_guide_votes{});
+    for (size_t r = 0; r < n; ++r)
+        for (uint32_t i = 0; g->shard[r] && i < n_guides; ++i) add_votes_row(out_votes[i], part_votes[r][i]);
+    store_join_timing(m, tm, wall, t0, m->use_rccl);
+    return VSC_OK;
+    });
+}
+
 // vsc_multi_search_select (filter == null) and vsc_multi_search_select_regions (`who`)
 int multi_select(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
                  const vsc_select *select, const vsc_region_filter *filter, const vsc_locus *exclude, vsc_guide_summary *summary,
@@ -916,6 +966,13 @@ int vsc_multi_search_summary(vsc_multi *m, const vsc_multi_genome *g, const uint
                              const vsc_search_params *params, const vsc_locus *exclude, vsc_guide_summary *out)
 {
     return multi_summary(m, g, guides, n_guides, params, exclude, nullptr, out, nullptr, "vsc_multi_search_summary");
+}
+
+int vsc_multi_search_summary_classified(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                        const vsc_search_params *params, const vsc_locus *exclude, const vsc_classify *cls,
+                                        vsc_guide_summary *out, vsc_guide_votes *out_votes)
+{
+    return multi_summary_classified(m, g, guides, n_guides, params, exclude, cls, out, out_votes);
 }
 
 int vsc_multi_search_summary_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,

@@ -72,6 +72,8 @@ enum vsc_event {
     kEvIndexStart,
     kEvIndexEnd,
     kEvPrepEnd,
+    kEvClassStart,  // the classify kernel of a pass (vsc_search_*_classified): score_ms
+    kEvClassEnd,
     kEvCount,
     kEvStageStart = kEvPassStart,
     kEvStageEnd = kEvSearchStart,
@@ -106,6 +108,8 @@ struct vsc_ctx {
     // vsc_search_*_regions: the rows over the hits in the regions (beside sum_rows), and the device copy of the regions this
     // context used last - start[], end_max[], class table in one buffer - keyed by the serial number of the vsc_regions
     vsc::DeviceBuf sum_rows_in, regions_buf;
+    // vsc_search_*_classified: the per-read vsc_guide_votes rows (the votes words beside the records lie in vals_b)
+    vsc::DeviceBuf votes_rows;
     uint64_t regions_serial = 0;  // 0: none resident
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
