@@ -663,6 +663,102 @@ const char *vsc_windows_name(const vsc_windows *w, uint32_t i, uint32_t *len);
 const uint64_t *vsc_windows_name_offsets(const vsc_windows *w);
 void vsc_windows_free(vsc_windows *w);
 
+/* ---- variant-aware screen: the window side of the mergers on the device ------------------------------ */
+/*
+ * A hit of the window-genome search is a hit IN A WINDOW; the mergers turn it into a hit of the individual's genome
+ * (variant_processing/filter_output_bam.h:279-317 filterSnpAlignment, :189-263 getSnpType): with id = the window's id split on
+ * '_', chr = id[0] and pos1 = pos + (uint32) atoi(id[1]) (32-bit wrap; a negative start and a non-numeric field are legal; a
+ * chromosome name that holds '_' is cut at it and its fields shift, as in the reference), the triples (id[k], id[k+1], id[k+2]),
+ * k = 3, 6, ..., are the window's variants: position p = atoi(id[k]), lengths of the ref and the alt allele.  A variant is
+ * COVERED by [pos1, pos1 + 23) if p lies in it (equal lengths) or p + 1 or p + max(len) - 1 does (an indel: only its two end
+ * points are tested); an uncovered indel met before the first covered variant moves the position by len_ref - len_alt;
+ * pos2 = pos1 + that sum.  The tag is REF if nothing is covered, else VAR_<chr>_<id[k] of the covered ones, comma separated>.
+ * key = (guide, chr, pos2, strand, the window's 23 bases, mismatch mask, tag).  Record i of a result in vsc_search order is
+ *   the ON-TARGET  iff exclude[guide] names a locus and chr is that contig, pos2 its position, the strands agree, NM = 0 and the
+ *                  tag is REF (the caller's contract, as for vsc_search_summary: exclude[i] is the locus guide i was taken from);
+ *   a DUPLICATE    iff i > 0 and key_i == key_(i-1) - the record before it, whatever that one's fate; duplicates that are not
+ *                  neighbours are kept, as in the reference (:303-306);
+ *   COUNTED        iff it is neither.
+ * vsc_variant_map (host only, immutable, usable from several threads, like vsc_regions): every id parsed once into the reference
+ * contig (found by the first word of the contig's name, as an FAI index does; UINT32_MAX if unknown - such hits are counted and
+ * can never be the on-target), the start, and a flat table of (p, len_ref, len_alt, tag_id) per variant, tag_id numbering the
+ * distinct (id[0], id[k]) strings so that tags compare as integers.
+ * vsc_variant_map_build: ids / id_offsets = the id pool and the n_windows + 1 offsets exactly as vsc_windows_name(w, 0, NULL) and
+ * vsc_windows_name_offsets return them (id i = bytes [off[i], off[i+1] - 1), a separator byte behind every id);
+ * window_contigs = the window genome's table; ref_contigs / ref_names = the reference's.  n_windows == 0 is valid.  A null
+ * argument that is needed or offsets that do not ascend: VSC_ERR_INVALID.
+ */
+typedef struct vsc_variant_map vsc_variant_map;
+typedef struct {
+    uint64_t windows;       /* windows of the map */
+    uint64_t variants;      /* (window, variant) entries of the flat table */
+    uint64_t unknown_chr;   /* windows whose chromosome is not a contig of the reference */
+    uint32_t max_variants;  /* most variants in one window */
+    uint32_t reserved;
+} vsc_variant_map_stats;
+typedef struct {
+    uint32_t contig; /* reference contig of chr, UINT32_MAX: unknown */
+    uint32_t pos;    /* pos2 */
+    uint32_t n_var;  /* covered variants (0: the tag is REF) */
+    uint32_t flags;  /* VSC_VARIANT_* */
+} vsc_variant_label;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_variant_label) == 16, "vsc_variant_label layout");
+#else
+_Static_assert(sizeof(vsc_variant_label) == 16, "vsc_variant_label layout");
+#endif
+#define VSC_VARIANT_VAR 1u       /* the tag is not REF */
+#define VSC_VARIANT_DUP 2u       /* dropped: the same key as the record before it */
+#define VSC_VARIANT_ON_TARGET 4u /* dropped: the guide's own locus */
+int vsc_variant_map_build(const char *ids, const uint64_t *id_offsets, const vsc_contig *window_contigs, uint32_t n_windows,
+                          const vsc_contig *ref_contigs, const char *const *ref_names, uint32_t n_ref_contigs,
+                          vsc_variant_map **out);
+void vsc_variant_map_free(vsc_variant_map *map);
+int vsc_variant_map_info(const vsc_variant_map *map, vsc_variant_map_stats *out);
+/* The INSIDE-rule regions of filterRefAlignment (variant_processing/filter_output_bam.h:70-124) over the reference's contig
+ * table: one interval [start, start + window length) per window with a known chromosome and start >= 0 (`pos >= atoi(start)`
+ * compares unsigned with int there: a negative start shadows nothing).  vsc_search_summary_regions' out_all - out_in and
+ * vsc_search_select_regions with VSC_REGION_DROP under these regions are the reference side of the merge.  Released with
+ * vsc_regions_free. */
+int vsc_variant_map_shadow(const vsc_variant_map *map, vsc_regions **out);
+/* The host's answer for the window position (window, pos): contig, pos2, n_var and VSC_VARIANT_VAR (never DUP / ON_TARGET: those
+ * need the records).  window >= the map's windows or a null argument: VSC_ERR_INVALID. */
+int vsc_variant_map_locate(const vsc_variant_map *map, uint32_t window, uint32_t pos, vsc_variant_label *label);
+/* The tag text of (window, pos) - "REF" or "VAR_<chr>_<positions>" - into buf (NUL-terminated, cut at len - 1); returns the
+ * text's full length, or a negative status. */
+int64_t vsc_variant_map_tag(const vsc_variant_map *map, uint32_t window, uint32_t pos, char *buf, size_t len);
+/*
+ * labels[i] = the label of record i of `hits`, a result of a search of win_genome (any vsc_search* result in vsc_search order,
+ * on the hits' own context, which must be win_genome's), flags included; exclude: NULL or n_guides loci IN REFERENCE
+ * COORDINATES (contig >= the reference's contig count and not UINT32_MAX, or strand > 1: VSC_ERR_INVALID).  One kernel over the
+ * records where they lie (variant_merge_kernel: the window's table entry, a walk over the window's variants, the key compared
+ * with the neighbour's - cheap fields, covered tag ids in lockstep, the 23 bases of both windows from the resident planes);
+ * the map's device copy is kept by the context (given back by vsc_ctx_release_scratch).  labels: host memory, vsc_hits_count
+ * entries.  A map whose window count or lengths differ from win_genome's contig table, a record whose contig or position lies
+ * outside the map, a record guide >= n_guides when exclude is given, or a null argument: VSC_ERR_INVALID.  n == 0: VSC_OK,
+ * nothing is launched.  vsc_ctx_timing is left as it is.
+ * Replaces: filterSnpAlignment + getSnpType per record on the host (variant_processing/filter_output_bam.h:189-317).
+ */
+int vsc_hits_variants(vsc_hits *hits, const vsc_genome *win_genome, const vsc_variant_map *map, const vsc_locus *exclude,
+                      uint32_t n_guides, vsc_variant_label *labels);
+/*
+ * The screen: per guide the summary of the COUNTED window hits, without the records.  out_all = over all counted records,
+ * out_var (optional) = over those whose tag is not REF, fields as vsc_search_summary computes them (nm by popcount of the
+ * mask, mit_sum += rint(MIT * 2^24), mit_ub); on_target = 1 in both rows if the on-target was met in a window;
+ * duplicates (optional) = dropped duplicates per guide (every record flagged VSC_VARIANT_DUP).  The guides are searched in batches of batch_reads (0 or more than
+ * 16 384: 16 384) as vsc_search_stream searches them; every batch's sorted records are summarised where they lie and let go:
+ * no record leaves the device.  Batches end on guide boundaries, so the neighbour rule needs nothing across them and the rows
+ * do not depend on batch_reads.  The guide's rows in the individual's genome = (out_all - out_in of vsc_search_summary_regions
+ * on the reference under vsc_variant_map_shadow's regions) + out_all of this call, field by field: the per-guide aggregation of
+ * the rows mergeResults prints (variant_processing/merge_output_bam.h:46-215).
+ * vsc_ctx_timing afterwards reports as after vsc_search (sums over the batches), the merge kernel in finalize_ms.
+ * Replaces, for a screen: bidir_mapping on the SNP genome + filterSnpAlignment / getSnpType + the MIT scores of the merger.
+ */
+int vsc_search_summary_variants(vsc_ctx *ctx, const vsc_genome *win_genome, const vsc_variant_map *map, const uint64_t *guides,
+                                uint32_t n_guides, const vsc_search_params *params, const vsc_locus *exclude, uint32_t batch_reads,
+                                vsc_guide_summary *out_all, vsc_guide_summary *out_var /* optional */,
+                                uint64_t *duplicates /* optional */);
+
 /* ---- classifier ---------------------------------------------------------------------------------- */
 /*
  * A trained random forest as randomForest stores it ($forest of the object in

@@ -11,7 +11,7 @@ set -o pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd); TAG=${TAG:-r04}; LOG=$ROOT/profiles/${TAG}_sanitizers_cpu.txt
 HIPCC=/opt/rocm/bin/hipcc; CXX=/opt/rocm/lib/llvm/bin/clang++
 RT=$(dirname "$($CXX -print-file-name=libclang_rt.asan-x86_64.so)")
-SRCS="vsc_kernels.hip vsc_seed.hip vsc_sort.hip vsc_enum.hip vsc_api.cpp vsc_pack.cpp vsc_windows.cpp vsc_multi.cpp vsc_regions.cpp"
+SRCS="vsc_kernels.hip vsc_seed.hip vsc_sort.hip vsc_enum.hip vsc_variants.hip vsc_api.cpp vsc_pack.cpp vsc_windows.cpp vsc_multi.cpp vsc_regions.cpp vsc_varmap.cpp"
 TOOLS="bidir_index bidir_mapping vcf_loader bam_merger_ref_only bam_merger fasta_writer classification_pipeline varscot_pipeline guide_summary"
 : > "$LOG"
 build() {  # build NAME "sanitizer flags"

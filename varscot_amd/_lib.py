@@ -51,6 +51,9 @@ assert C.sizeof(Select) == 16
 INTERVAL_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4")])
 REGION_OVERLAP, REGION_INSIDE = 0, 1
 REGION_KEEP, REGION_DROP = 0, 1
+# vsc_variant_label: a window hit in chromosome coordinates (vsc_hits_variants, vsc_variant_map_locate)
+VARIANT_LABEL_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("n_var", "<u4"), ("flags", "<u4")])
+VARIANT_VAR, VARIANT_DUP, VARIANT_ON_TARGET = 1, 2, 4  # VSC_VARIANT_*
 REGION_NONE = 0xFFFFFFFF  # VSC_REGION_NONE: the label of a window that is in no interval
 
 
@@ -76,6 +79,15 @@ class RegionsStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VariantMapStats(C.Structure):
+    """vsc_variant_map_stats (vsc_variant_map_info)."""
+    _fields_ = [("windows", C.c_uint64), ("variants", C.c_uint64), ("unknown_chr", C.c_uint64), ("max_variants", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
 class RfModel(C.Structure):
@@ -240,6 +252,14 @@ SYMBOLS = [
     ("vsc_windows_name", _vp, [_vp, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("vsc_windows_name_offsets", _vp, [_vp]),
     ("vsc_windows_free", None, [_vp]),
+    ("vsc_variant_map_build", C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_variant_map_free", None, [_vp]),
+    ("vsc_variant_map_info", C.c_int, [_vp, C.POINTER(VariantMapStats)]),
+    ("vsc_variant_map_shadow", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_variant_map_locate", C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    ("vsc_variant_map_tag", C.c_int64, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
+    ("vsc_hits_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("vsc_search_summary_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, C.c_uint32, _vp, _vp, _vp]),
     ("vsc_rf_predict", C.c_int, [_vp, C.POINTER(RfModel), _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_rf_predict_packed", C.c_int, [_vp, C.POINTER(RfModel), _vp, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_score_classify_hits", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(RfModel), C.c_uint64, C.c_uint64, _vp, _vp, _vp]),

@@ -196,6 +196,86 @@ class Regions:
             pass
 
 
+class VariantMap:
+    """The ids of a variant-window genome parsed for the merge (vsc_variant_map): per window the reference contig of its
+    chromosome, its start and its variants.  windows_genome: the PackedGenome variant_windows returned (its `names` are the ids),
+    reference: the PackedGenome the windows were built from.  Host-side and immutable, as Regions; a context keeps a device copy
+    while it is the last map it merged against."""
+
+    def __init__(self, windows_genome, reference):
+        names = windows_genome.names
+        n = len(names)
+        if isinstance(names, LazyNames):  # the library's own pool, as it is
+            pool, offsets = np.ascontiguousarray(names._pool), np.ascontiguousarray(names._off, dtype=np.uint64)
+        else:
+            raw = [x.encode() + b"\n" for x in names]
+            pool = np.frombuffer(b"".join(raw) or b"\n", dtype=np.uint8).copy()
+            offsets = np.concatenate([[0], np.cumsum([len(x) for x in raw])]).astype(np.uint64)
+        contigs = np.ascontiguousarray(windows_genome.contigs, dtype=CONTIG_DTYPE)
+        if len(contigs) != n:
+            raise ValueError("the window genome has %d contigs and %d names" % (len(contigs), n))
+        ref_contigs = np.ascontiguousarray(reference.contigs, dtype=CONTIG_DTYPE)
+        ref_names = (C.c_char_p * len(reference.names))(*[x.encode() for x in reference.names])
+        self.n_windows = n
+        self._h = C.c_void_p()
+        check(lib().vsc_variant_map_build(ptr(pool), ptr(offsets), ptr(contigs), n, ptr(ref_contigs), ref_names, len(ref_contigs),
+                                          C.byref(self._h)))
+
+    def shadow(self):
+        """vsc_variant_map_shadow: the INSIDE-rule Regions over the reference that filterRefAlignment tests reference hits
+        against - a reference hit in them is shadowed by a window."""
+        r = Regions.__new__(Regions)
+        r.rule = "inside"
+        r._h = C.c_void_p()
+        check(lib().vsc_variant_map_shadow(self._h, C.byref(r._h)))
+        return r
+
+    def locate(self, window, pos):
+        """vsc_variant_map_locate: the VARIANT_LABEL_DTYPE record of the window position - reference contig (0xFFFFFFFF:
+        unknown), position on the chromosome, covered variants, VARIANT_VAR."""
+        out = np.zeros(1, dtype=_lib.VARIANT_LABEL_DTYPE)
+        check(lib().vsc_variant_map_locate(self._h, int(window), int(pos), ptr(out)))
+        return out[0]
+
+    def tag(self, window, pos):
+        """vsc_variant_map_tag: "REF" or "VAR_<chr>_<positions of the covered variants>"."""
+        n = int(lib().vsc_variant_map_tag(self._h, int(window), int(pos), None, 0))
+        if n < 0:
+            check(n)
+        buf = C.create_string_buffer(n + 1)
+        lib().vsc_variant_map_tag(self._h, int(window), int(pos), buf, n + 1)
+        return buf.value.decode()
+
+    def info(self):
+        """vsc_variant_map_info: windows, variants, unknown_chr (windows of a chromosome the reference does not have),
+        max_variants (most variants in one window)."""
+        st = _lib.VariantMapStats()
+        check(lib().vsc_variant_map_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if self._h:
+            lib().vsc_variant_map_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def individual_rows(ref_all, ref_in, win_all):
+    """A guide's rows in the individual's genome: the reference hits no window shadows (ref_all - ref_in of
+    Genome.summarize(..., regions=vmap.shadow())) plus the counted window hits (Genome.summarize_variants' `all` rows), field
+    by field; on_target: met on either side.  SUMMARY_DTYPE rows in, SUMMARY_DTYPE rows out."""
+    out = np.zeros(len(ref_all), dtype=_lib.SUMMARY_DTYPE)
+    for f in ("mit_sum", "nm", "mit_ub"):
+        out[f] = ref_all[f] - ref_in[f] + win_all[f]
+    out["on_target"] = (ref_all["on_target"] != 0) | (win_all["on_target"] != 0)
+    return out
+
+
 class PackedGenome:
     """The host-side packed planes of a genome (0.375 byte per base) plus its contig table.
 
@@ -440,6 +520,21 @@ class Genome:
                                                ptr(inside)), self.ctx._h)
         return out, inside
 
+    def summarize_variants(self, guides, max_mismatches, vmap, exclude=None, batch=0, extra_pam=None, algorithm="auto"):
+        """vsc_search_summary_variants on a window genome: per guide the SUMMARY_DTYPE rows over the counted window hits
+        (`all`), over those that carry a variant (`var`), and the dropped duplicates - (all, var, duplicates).  vmap: the
+        VariantMap of this genome; exclude: None or one (contig, pos, strand) per guide IN REFERENCE COORDINATES, the locus the
+        guide was taken from; batch: guides per pass (0: the default), the rows do not depend on it."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        rows, var = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE), np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE)
+        dups = np.zeros(len(codes), dtype=np.uint64)
+        check(lib().vsc_search_summary_variants(self.ctx._h, self._h, vmap._h, ptr(codes), len(codes), C.byref(p), ptr(ex), int(batch),
+                                                ptr(rows), ptr(var), ptr(dups)), self.ctx._h)
+        return rows, var, dups
+
     def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
                       summary=False, regions=None, region_scope="keep"):
         """vsc_search_select: per guide, of the hits search() would return (minus the excluded locus), those with
@@ -624,6 +719,15 @@ class Hits:
         in none), as Regions.locate gives it - computed on the device over the records where they lie."""
         labels = np.full(len(self), _lib.REGION_NONE, dtype=np.uint32)
         check(lib().vsc_hits_locate(self._h, regions._h, ptr(labels)), self.ctx._h)
+        return labels
+
+    def variants(self, vmap, exclude=None):
+        """vsc_hits_variants on a result of a window genome's search: per record a VARIANT_LABEL_DTYPE row - reference contig,
+        position on the chromosome, covered variants, flags VARIANT_VAR / VARIANT_DUP / VARIANT_ON_TARGET - computed on the
+        device over the records where they lie.  exclude: None or one (contig, pos, strand) per guide in reference coordinates."""
+        labels = np.zeros(len(self), dtype=_lib.VARIANT_LABEL_DTYPE)
+        ex = _loci(exclude, len(self.codes))
+        check(lib().vsc_hits_variants(self._h, self.genome._h, vmap._h, ptr(ex), len(self.codes), ptr(labels)), self.ctx._h)
         return labels
 
     def copy_to(self, dst_ptr, dst_is_device):

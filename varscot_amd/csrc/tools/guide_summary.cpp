@@ -43,6 +43,17 @@
 // MIT score (vsc_search_select_classified; -r mit is the default): -K still applies, -V MIN lists only off-targets with at least
 // MIN votes (-S belongs to -r mit), the ranks follow (votes descending, '+' before '-', position) and the listing gains a last
 // column rfVotes.  -r votes runs on one device and without -A.  Without -F every output is what it was.
+// -v sample.vcf [-n SAMPLE] screens the guides in ONE INDIVIDUAL'S genome: SAMPLE is the 0-based sample column of the VCF
+// (default 0, as vcf_loader counts them).  The alt-allele windows are built from the packed planes (vsc_windows_build), the
+// reference is searched with the windows' shadow as regions (vsc_search_summary_regions under vsc_variant_map_shadow: a
+// reference hit that lies inside a window is the window search's to report), the window genome is loaded on the same device and
+// screened (vsc_search_summary_variants: hits in chromosome coordinates, the mergers' duplicates and the on-target dropped), and
+// every line gains, behind all other columns,
+//   indMitSpecScore indCount imm0 .. imm<M> indMitHitSum varCount vmm0 .. vmm<M> varMitHitSum varDuplicates
+// ind* = the guide in the individual's genome (unshadowed reference hits + counted window hits: the rows bam_merger prints, per
+// guide), var* = the counted window hits that cover a variant, varDuplicates = window hits dropped as duplicates.  A sample
+// without variants gives the reference's numbers and zeros.  -v runs on one device and not with -A, -X, -T or -F.  Without -v
+// every output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -89,6 +100,9 @@ int main(int argc, char **argv)
         {'C', "activity", "Path to the on-target activities (guideId, sequence, activity per line) of the guides, for -F", false},
         {'r', "rank-by", "mit (default) | votes: rank the -T listing by MIT score or by the classifier's votes (votes needs -F; adds the column rfVotes)", false},
         {'V', "min-votes", "With -r votes: list only off-targets with at least this many of the forest's votes (default: no floor)", false},
+        {'v', "vcf", "Path to a VCF (.vcf): adds the columns of the guides in that individual's genome, ind* and var* "
+                     "(one device; not with -A, -X, -T, -F)", false},
+        {'n', "sample", "With -v: 0-based sample column of the VCF (default 0)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -294,8 +308,33 @@ int main(int argc, char **argv)
         vsel.min_votes = (uint32_t)k;
     }
 
+    // -v / -n: the individual
+    const bool individual = opts[26].set;
+    uint32_t vcf_sample = 0;
+    if (individual && !has_extension(opts[26].value, {"vcf"})) {
+        std::fprintf(stderr, "%s: the -v file must be a .vcf file\n", argv[0]);
+        return 1;
+    }
+    if (individual && (annotated || opts[13].set || listing || classified || devices.size() != 1)) {
+        std::fprintf(stderr, "%s: -v screens one individual on one device: it does not combine with -A, -X, -T, -F or a device list\n", argv[0]);
+        return 1;
+    }
+    if (opts[27].set) {
+        const std::string &v = opts[27].value;
+        char *nend = nullptr;
+        const long long k = std::strtoll(v.c_str(), &nend, 10);
+        if (!individual || v.empty() || *nend || k < 0 || k > 0xFFFFFFFFll) {
+            std::fprintf(stderr, "%s: -n takes the 0-based sample column of the -v file, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        vcf_sample = (uint32_t)k;
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_genome *genome = nullptr;
+    vsc_genome *win_genome = nullptr;
+    vsc_windows *windows = nullptr;
+    vsc_variant_map *vmap = nullptr;
     vsc_multi *multi = nullptr;
     vsc_multi_genome *mgenome = nullptr;
     vsc_hits *hits = nullptr;
@@ -450,7 +489,9 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "%s: searching with -P %c%c, the guide PAM of -p\n", argv[0], ep.pam[0], ep.pam[1]);
             }
         }
-        std::vector<vsc_guide_summary> sum(codes.size()), sum_in(annotated ? codes.size() : 0);
+        std::vector<vsc_guide_summary> sum(codes.size()), sum_in(annotated || individual ? codes.size() : 0);
+        std::vector<vsc_guide_summary> win_all(individual ? codes.size() : 0), win_var(win_all.size());
+        std::vector<uint64_t> win_dups(win_all.size());
         const vsc_locus *ex = loci.empty() ? nullptr : loci.data();
         const uint32_t n_codes = (uint32_t)codes.size();
         // -F / -C: the forest over the feature matrix's columns, one activity per guide
@@ -472,7 +513,32 @@ int main(int argc, char **argv)
             cls.model = &model;
             cls.guide_activity = activity.data();
         }
-        if (by_votes) {
+        if (individual) {
+            std::vector<const char *> names;
+            for (const std::string &n : ix.names) names.push_back(n.c_str());
+            char why[512] = "";
+            if (vsc_windows_build(opts[26].value.c_str(), vcf_sample, VSC_READ_LEN, 0, ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs.data(),
+                                  names.data(), (uint32_t)ix.contigs.size(), &windows, why, sizeof why) != VSC_OK)
+                throw std::runtime_error(std::string("-v: ") + (why[0] ? why : "could not build the variant windows"));
+            const uint32_t n_win = vsc_windows_count(windows);
+            std::fprintf(stderr, "Variant windows built (total: %u).\n", n_win);
+            if (vsc_variant_map_build(n_win ? vsc_windows_name(windows, 0, nullptr) : nullptr, n_win ? vsc_windows_name_offsets(windows) : nullptr,
+                                      n_win ? vsc_windows_contigs(windows) : nullptr, n_win, ix.contigs.data(), names.data(),
+                                      (uint32_t)ix.contigs.size(), &vmap) != VSC_OK ||
+                vsc_variant_map_shadow(vmap, &regions) != VSC_OK)
+                throw std::runtime_error("-v: could not parse the ids of the variant windows");
+            // the reference side: all hits (the columns every run prints) and those a window shadows
+            st = vsc_search_summary_regions(ctx, genome, codes.data(), n_codes, &p, ex, regions, sum.data(), sum_in.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            if (n_win) {  // the window side, on the same device
+                st = vsc_genome_load(ctx, vsc_windows_plane(windows, 0), vsc_windows_plane(windows, 1), vsc_windows_plane(windows, 2), 0,
+                                     vsc_windows_words(windows), vsc_windows_words(windows), vsc_windows_contigs(windows), n_win, &win_genome);
+                if (st == VSC_OK)
+                    st = vsc_search_summary_variants(ctx, win_genome, vmap, codes.data(), n_codes, &p, ex, 0, win_all.data(), win_var.data(),
+                                                     win_dups.data());
+                if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            }
+        } else if (by_votes) {
             st = vsc_search_select_classified(ctx, genome, codes.data(), n_codes, &p, &vsel, &cls, ex, sum.data(), votes_rows.data(), &hits);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         } else if (annotated && listing) {  // without -X the listing is not filtered: the rows then come from a second search, a summary call
@@ -521,6 +587,13 @@ int main(int argc, char **argv)
             text += "\trfExpectedActive\trfActive\trfTies";
             for (long k = 0; k <= mm; ++k) text += "\tra" + std::to_string(k);
         }
+        if (individual) {
+            text += "\tindMitSpecScore\tindCount";
+            for (long k = 0; k <= mm; ++k) text += "\timm" + std::to_string(k);
+            text += "\tindMitHitSum\tvarCount";
+            for (long k = 0; k <= mm; ++k) text += "\tvmm" + std::to_string(k);
+            text += "\tvarMitHitSum\tvarDuplicates";
+        }
         text += '\n';
         char buf[64];
         for (size_t i = 0; i < sum.size(); ++i) {
@@ -548,6 +621,23 @@ int main(int argc, char **argv)
                 std::snprintf(buf, sizeof buf, "%.6f", (double)v.votes_sum / (double)model.n_trees);
                 text += '\t' + std::string(buf) + '\t' + std::to_string(v.active) + '\t' + std::to_string(v.ties);
                 for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(v.active_nm[k]);
+            }
+            if (individual) {  // unshadowed reference hits + counted window hits; then the window hits that cover a variant
+                const vsc_guide_summary &in = sum_in[i], &w = win_all[i], &v = win_var[i];
+                const uint64_t ind_mit = s.mit_sum - in.mit_sum + w.mit_sum;
+                uint64_t ind = 0, var = 0;
+                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+                    ind += s.nm[k] - in.nm[k] + w.nm[k];
+                    var += v.nm[k];
+                }
+                std::snprintf(buf, sizeof buf, "%.0f", std::floor(vsc_mit_specificity(ind_mit) + 0.5));
+                text += '\t' + std::string(buf) + '\t' + std::to_string(ind);
+                for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(s.nm[k] - in.nm[k] + w.nm[k]);
+                std::snprintf(buf, sizeof buf, "%.6f", (double)ind_mit * 0x1p-24);
+                text += '\t' + std::string(buf) + '\t' + std::to_string(var);
+                for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(v.nm[k]);
+                std::snprintf(buf, sizeof buf, "%.6f", (double)v.mit_sum * 0x1p-24);
+                text += '\t' + std::string(buf) + '\t' + std::to_string(win_dups[i]);
             }
             text += '\n';
         }
@@ -630,8 +720,11 @@ int main(int argc, char **argv)
         vsc_multi_genome_free(mgenome);
         vsc_multi_destroy(multi);
     } else {
+        if (win_genome) vsc_genome_free(win_genome);
         vsc_genome_free(genome);
         vsc_ctx_destroy(ctx);
     }
+    vsc_variant_map_free(vmap);
+    if (windows) vsc_windows_free(windows);
     return rc;
 }

@@ -18,6 +18,7 @@
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
+#include "vsc_varmap.h"
 
 using namespace vsc;
 
@@ -217,10 +218,12 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
-                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out})
+                         &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
+                         &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels})
         b->release();
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
+    ctx->varmap_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
     ctx->forest.nodes.release();
@@ -2229,6 +2232,79 @@ int search_stream(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides
     });
 }
 
+
+// ---- variant-aware screen (vsc_hits_variants, vsc_search_summary_variants) -------------------------------------
+// The device copy of `map` on this context - windows (n + 1 entries), then variants, in one buffer keyed by the map's serial
+// number as regions_buf is - and the checks every call makes: the map was built for win_genome's contig table, the excluded
+// loci lie in the reference's.  Fills a.map, the planes, the contig table and a.exclude / a.n_guides.
+int resident_variant_map(vsc_ctx *ctx, const vsc_genome *win_genome, const vsc_variant_map *map, const vsc_locus *exclude, uint32_t n_guides,
+                         const char *who, VariantArgs &a)
+{
+    if (win_genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    const uint32_t n_win = (uint32_t)(map->win.size() - 1);
+    bool same = n_win == win_genome->n_contigs;
+    for (uint32_t c = 0; same && c < n_win; ++c) same = win_genome->h_contig_end[c] - win_genome->h_contig_off[c] == map->win_len[c];
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the variant map was built for another window genome");
+    for (uint32_t i = 0; exclude && i < n_guides; ++i)
+        if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= map->ref_contigs.size()) || exclude[i].strand > 1)
+            return fail_in(ctx, VSC_ERR_INVALID, who, "excluded locus outside the reference's contigs or strands");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t win_bytes = map->win.size() * sizeof(VarWindow), var_bytes = map->var.size() * sizeof(VarEntry);
+    if (ctx->varmap_serial != map->serial) {
+        ctx->varmap_serial = 0;
+        VSC_HIP(ctx, ctx->varmap_buf.ensure(win_bytes + var_bytes));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->varmap_buf.p, map->win.data(), win_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (var_bytes)
+            VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->varmap_buf.p + win_bytes, map->var.data(), var_bytes, hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the map as soon as its call returns)
+        ctx->varmap_serial = map->serial;
+    }
+    a.map = VarMapView{(const VarWindow *)ctx->varmap_buf.p, (const VarEntry *)((const char *)ctx->varmap_buf.p + win_bytes), n_win,
+                       (uint32_t)map->var.size()};
+    a.hi = win_genome->d_hi;
+    a.lo = win_genome->d_lo;
+    a.first_pos = (uint32_t)(win_genome->first_word * 32);
+    a.n_plane_words = win_genome->dev_words;
+    a.contig_off = win_genome->d_contig_off;
+    a.contig_end = win_genome->d_contig_end;
+    a.n_guides = n_guides;
+    a.exclude = nullptr;
+    if (exclude && n_guides) {
+        VSC_HIP(ctx, ctx->var_excl.ensure((size_t)n_guides * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->var_excl.p, exclude, (size_t)n_guides * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.exclude = (const uint4 *)ctx->var_excl.p;
+    }
+    return VSC_OK;
+}
+
+// The call's state on the device: the error flag (its own 256 bytes), then - rows wanted - the zeroed rows over all counted
+// records, those over the VAR ones and the duplicate counts.
+constexpr size_t kVarStateHead = 256;
+int variant_state(vsc_ctx *ctx, uint32_t n_guides, bool rows, VariantArgs &a)
+{
+    const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+    const size_t bytes = kVarStateHead + (rows ? 2 * row_bytes + (size_t)n_guides * sizeof(uint64_t) : 0);
+    VSC_HIP(ctx, ctx->var_state.ensure(bytes));
+    VSC_HIP(ctx, hipMemsetAsync(ctx->var_state.p, 0, bytes, ctx->stream));
+    char *p = (char *)ctx->var_state.p;
+    a.error = (uint32_t *)p;
+    if (rows) {
+        a.rows_all = (unsigned long long *)(p + kVarStateHead);
+        a.rows_var = (unsigned long long *)(p + kVarStateHead + row_bytes);
+        a.dups = (unsigned long long *)(p + kVarStateHead + 2 * row_bytes);
+    }
+    return VSC_OK;
+}
+
+// has the kernel met a record outside the map? (after the stream has been waited for)
+int variant_error(vsc_ctx *ctx, const VariantArgs &a, const char *who)
+{
+    uint32_t bad = 0;
+    VSC_HIP(ctx, hipMemcpy(&bad, a.error, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail_in(ctx, VSC_ERR_INVALID, who, "a record lies outside the variant map, its window or the guides");
+    return VSC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2538,6 +2614,69 @@ int vsc_search_stream_rows(vsc_ctx *ctx, const vsc_genome *genome, const uint64_
                               }
                               return on_batch(user, hits, first, count, hits->n ? ctx->score_feat.p : nullptr);
                           });
+}
+
+int vsc_hits_variants(vsc_hits *hits, const vsc_genome *win_genome, const vsc_variant_map *map, const vsc_locus *exclude,
+                      uint32_t n_guides, vsc_variant_label *labels)
+{
+    if (!hits || !win_genome || !map || (hits->n && !labels)) return VSC_ERR_INVALID;
+    vsc_ctx *ctx = hits->ctx;
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    VariantArgs a{};
+    int rc = resident_variant_map(ctx, win_genome, map, exclude, n_guides, "vsc_hits_variants", a);
+    if (rc != VSC_OK || hits->n == 0) return rc;
+    if ((rc = variant_state(ctx, 0, false, a)) != VSC_OK) return rc;
+    a.records = (const uint4 *)hits->d_records;
+    a.n = hits->n;
+    VSC_HIP(ctx, ctx->var_labels.ensure(hits->n * sizeof(vsc_variant_label)));
+    a.labels = (uint4 *)ctx->var_labels.p;
+    VSC_HIP(ctx, launch_variant_merge(a, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(labels, a.labels, hits->n * sizeof(vsc_variant_label), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return variant_error(ctx, a, "vsc_hits_variants");
+    });
+}
+
+int vsc_search_summary_variants(vsc_ctx *ctx, const vsc_genome *win_genome, const vsc_variant_map *map, const uint64_t *guides,
+                                uint32_t n_guides, const vsc_search_params *params, const vsc_locus *exclude, uint32_t batch_reads,
+                                vsc_guide_summary *out_all, vsc_guide_summary *out_var, uint64_t *duplicates)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const who = "vsc_search_summary_variants";
+    if (!win_genome || !map || !params || (n_guides && (!guides || !out_all))) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    VariantArgs a{};
+    const int rc = guarded(ctx, [&]() -> int {
+        ctx->err.clear();
+        const int mrc = resident_variant_map(ctx, win_genome, map, exclude, n_guides, who, a);
+        return mrc != VSC_OK ? mrc : variant_state(ctx, n_guides, true, a);
+    });
+    if (rc != VSC_OK) return rc;
+    // every batch's sorted records are summarised where they lie; the batch is freed when this returns
+    const int src = search_stream(ctx, win_genome, guides, n_guides, params, batch_reads, false, who, true,
+                                  [&](vsc_hits *hits, uint32_t, uint32_t, vsc_timing &t) -> int {
+                                      if (hits->n == 0) return VSC_OK;
+                                      a.records = (const uint4 *)hits->d_records;
+                                      a.n = hits->n;
+                                      VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+                                      VSC_HIP(ctx, launch_variant_merge(a, ctx->stream));
+                                      VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+                                      VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                                      float ms = 0;
+                                      VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+                                      t.finalize_ms += ms;
+                                      t.total_ms += ms;
+                                      return VSC_OK;
+                                  });
+    if (src != VSC_OK || n_guides == 0) return src;
+    return guarded(ctx, [&]() -> int {
+        const size_t row_bytes = (size_t)n_guides * sizeof(vsc_guide_summary);
+        VSC_HIP(ctx, hipMemcpyAsync(out_all, a.rows_all, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_var) VSC_HIP(ctx, hipMemcpyAsync(out_var, a.rows_var, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (duplicates) VSC_HIP(ctx, hipMemcpyAsync(duplicates, a.dups, (size_t)n_guides * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return variant_error(ctx, a, who);
+    });
 }
 
 uint64_t vsc_hits_count(const vsc_hits *hits) { return hits ? hits->n : 0; }

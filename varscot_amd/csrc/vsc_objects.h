@@ -116,6 +116,11 @@ struct vsc_ctx {
     // way to the host
     vsc::DeviceBuf locate_buf, locate_out;
     uint64_t locate_serial = 0;  // 0: none resident
+    // vsc_hits_variants / vsc_search_summary_variants: the device copy of the variant map this context merged against last -
+    // windows, then variants, keyed by the map's serial number - the call's state (error flag, then the zeroed rows and
+    // duplicate counts), the excluded loci in reference coordinates, and the labels on their way to the host
+    vsc::DeviceBuf varmap_buf, var_state, var_excl, var_labels;
+    uint64_t varmap_serial = 0;  // 0: none resident
     // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan
     vsc::DeviceBuf enum_tabs;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
