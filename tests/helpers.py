@@ -268,3 +268,97 @@ def guideseq_mini_genome(golden_dir):
             planted[i] = (names.index(t), ci, pos, 0 if strand == "+" else 1, nm, row)
         contigs.append("".join(seq))
     return names, guides, list(UCSC_HG19_ORDER), contigs, planted
+
+
+# ---- what the sinks' tests check against: aggregation and selection on the host, the oracle's hits with their scores ----------
+def aggregate(hits, n_guides, mit, ub, exclude=None):
+    """Summary rows from records (HIT_DTYPE) and their MIT scores / UB flags (numpy, order-free)."""
+    import varscot_amd as va
+    out = np.zeros(n_guides, dtype=va.SUMMARY_DTYPE)
+    g = hits["guide"].astype(np.int64)
+    strand = (hits["info"] >> 31).astype(np.int64)
+    keep = np.ones(len(hits), dtype=bool)
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).reshape(-1, 3)
+        hit_ex = (hits["contig"] == ex[g, 0]) & (hits["pos"] == ex[g, 1]) & (strand == ex[g, 2])
+        out["on_target"][g[hit_ex]] = 1
+        keep = ~hit_ex
+    g, h = g[keep], hits[keep]
+    fixed = np.rint(np.asarray(mit, dtype=np.float64)[keep] * 2.0 ** 24).astype(np.uint64)
+    np.add.at(out["mit_sum"], g, fixed)
+    np.add.at(out["mit_ub"], g, np.asarray(ub, dtype=np.uint64)[keep])
+    nm = ((h["info"] >> 23) & 31).astype(np.int64)
+    np.add.at(out["nm"], (g, nm), 1)
+    return out
+
+
+def by_result_order(h):
+    return h[np.lexsort((h["pos"], h["contig"], h["info"] >> 31, h["guide"]))]
+
+
+def cut(hits, score, top_k=0, min_score=0, exclude=None, ranked=False):
+    """The selection on the host: hits (HIT_DTYPE, any order) with their fixed-point scores -> the selected records in
+    result order (ranked=True: per guide in rank order)."""
+    hits, score = np.asarray(hits), np.asarray(score, dtype=np.int64)
+    g = hits["guide"].astype(np.int64)
+    strand = (hits["info"] >> 31).astype(np.int64)
+    keep = score >= int(min_score)
+    if exclude is not None:
+        ex = np.asarray(exclude, dtype=np.int64).reshape(-1, 3)
+        keep &= ~((hits["contig"] == ex[g, 0]) & (hits["pos"] == ex[g, 1]) & (strand == ex[g, 2]))
+    h, s = hits[keep], score[keep]
+    order = np.lexsort((h["pos"], h["contig"], h["info"] >> 31, -s, h["guide"]))
+    h = h[order]
+    gg = h["guide"].astype(np.int64)
+    rank = np.arange(len(h)) - np.searchsorted(gg, gg, side="left")
+    if top_k:
+        h = h[rank < top_k]
+    return h if ranked else by_result_order(h)
+
+
+def oracle_hits(oracle, contigs, guides, m, pam=None):
+    """Every hit of the oracle with its rint(MIT * 2^24), MIT score and UB flag."""
+    want = oracle.search(contigs, guides, m, extra_pam=pam, mode=oracle.MODE_PREDICATE)
+    cache = {}
+    mit, ub = np.zeros(len(want)), np.zeros(len(want), dtype=np.uint64)
+    for i, info in enumerate(want["info"]):
+        mask = int(info) & 0x7FFFFF
+        if mask not in cache:
+            cache[mask] = oracle.mit_score([b for b in range(23) if (mask >> b) & 1] or [-1])
+        mit[i], ub[i] = cache[mask][0], cache[mask][1]
+    return want, np.rint(mit * 2.0 ** 24).astype(np.int64), mit, ub
+
+
+def select(gen, guides, m, top_k=0, min_score=0, **kw):
+    h = gen.search_select(guides, m, top_k=top_k, min_score=min_score, **kw)
+    rec = h.to_numpy()
+    h.close()
+    return rec
+
+
+def inside_numpy(packed, iv, rule, hits, chunk=4096):
+    """Membership of the hits' windows, every (hit, interval) pair against the definition (ends clipped to the contig)."""
+    lens = packed.contigs["length"].astype(np.int64)
+    off = packed.contigs["offset"].astype(np.int64)
+    s = off[iv[:, 0]] + iv[:, 1]
+    e = off[iv[:, 0]] + np.minimum(iv[:, 2], lens[iv[:, 0]])
+    keep = s < e
+    s, e = s[keep], e[keep]
+    pos = off[hits["contig"]] + hits["pos"].astype(np.int64)
+    out = np.zeros(len(hits), dtype=bool)
+    for a in range(0, len(hits), chunk):
+        p = pos[a:a + chunk, None]
+        out[a:a + chunk] = (((s[None, :] < p + 23) & (e[None, :] > p)) if rule == "overlap" else
+                            ((s[None, :] <= p) & (e[None, :] >= p + 23))).any(axis=1)
+    return out
+
+
+def selected(gen, guides, m, forest, act, **kw):
+    h = gen.search_select_classified(guides, m, forest, act, **kw)
+    if isinstance(h, tuple):
+        got = (h[0].to_numpy().copy(),) + h[1:]
+        h[0].close()
+        return got
+    got = h.to_numpy().copy()
+    h.close()
+    return got

@@ -12,7 +12,7 @@ import pytest
 import varscot_amd as va
 from classified_cases import (NONE, SYNTHETIC_ACTIVITIES, by_result_order, cut_by_votes, oracle_votes, record_route, rows_of_hits,
                               synthetic_forest)
-from helpers import make_genome, random_guides, random_seq, real_guides, revcomp
+from helpers import make_genome, random_guides, random_seq, real_guides, revcomp, selected
 from varscot_amd import _lib
 from varscot_amd.classifier import DEFAULT_MODEL, Forest, feature_names
 
@@ -51,17 +51,6 @@ def shipped(ctx, golden_dir):
     routes = {a: record_route(gen, forest, guides, act, 7, a) for a in ("scan", "seed")}
     yield dict(guides=guides, act=act, contigs=contigs, gen=gen, forest=forest, routes=routes)
     gen.close()
-
-
-def selected(gen, guides, m, forest, act, **kw):
-    h = gen.search_select_classified(guides, m, forest, act, **kw)
-    if isinstance(h, tuple):
-        got = (h[0].to_numpy().copy(),) + h[1:]
-        h[0].close()
-        return got
-    got = h.to_numpy().copy()
-    h.close()
-    return got
 
 
 # ------------------------------------------------------------------------------------ 1. parity, shipped forest

@@ -8,10 +8,9 @@ import numpy as np
 import pytest
 
 import varscot_amd as va
-from helpers import make_genome, random_guides
+from helpers import aggregate, cut, inside_numpy, make_genome, oracle_hits, random_guides
 from regions_cases import LENS, P_MINUS, P_PLUS, annotation, brute_force, member
-from test_select import cut, oracle_hits
-from test_summary import aggregate, planted
+from test_summary import planted
 
 pytestmark = pytest.mark.gpu
 
@@ -68,23 +67,6 @@ def random_cover(rng, packed, n, fraction):
     ln = rng.integers(max(1, int(mean / 10)), int(2 * mean), size=n)
     start = (rng.random(n) * lens[c]).astype(np.int64)
     return np.stack([c, start, start + ln], axis=1)
-
-
-def inside_numpy(packed, iv, rule, hits, chunk=4096):
-    """Membership of the hits' windows, every (hit, interval) pair against the definition (ends clipped to the contig)."""
-    lens = packed.contigs["length"].astype(np.int64)
-    off = packed.contigs["offset"].astype(np.int64)
-    s = off[iv[:, 0]] + iv[:, 1]
-    e = off[iv[:, 0]] + np.minimum(iv[:, 2], lens[iv[:, 0]])
-    keep = s < e
-    s, e = s[keep], e[keep]
-    pos = off[hits["contig"]] + hits["pos"].astype(np.int64)
-    out = np.zeros(len(hits), dtype=bool)
-    for a in range(0, len(hits), chunk):
-        p = pos[a:a + chunk, None]
-        out[a:a + chunk] = (((s[None, :] < p + 23) & (e[None, :] > p)) if rule == "overlap" else
-                            ((s[None, :] <= p) & (e[None, :] >= p + 23))).any(axis=1)
-    return out
 
 
 # ------------------------------------------------------------------------------------ 1. parity with the oracle

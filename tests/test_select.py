@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import varscot_amd as va
-from helpers import make_genome, random_guides, random_seq, repeat_rich_genome
-from test_summary import aggregate, planted
+from helpers import aggregate, by_result_order, cut, make_genome, oracle_hits, random_guides, random_seq, repeat_rich_genome, select
+from test_summary import planted
 
 pytestmark = pytest.mark.gpu
 
@@ -27,43 +27,6 @@ def ctx():
     c.close()
 
 
-def by_result_order(h):
-    return h[np.lexsort((h["pos"], h["contig"], h["info"] >> 31, h["guide"]))]
-
-
-def cut(hits, score, top_k=0, min_score=0, exclude=None, ranked=False):
-    """The selection on the host: hits (HIT_DTYPE, any order) with their fixed-point scores -> the selected records in
-    result order (ranked=True: per guide in rank order)."""
-    hits, score = np.asarray(hits), np.asarray(score, dtype=np.int64)
-    g = hits["guide"].astype(np.int64)
-    strand = (hits["info"] >> 31).astype(np.int64)
-    keep = score >= int(min_score)
-    if exclude is not None:
-        ex = np.asarray(exclude, dtype=np.int64).reshape(-1, 3)
-        keep &= ~((hits["contig"] == ex[g, 0]) & (hits["pos"] == ex[g, 1]) & (strand == ex[g, 2]))
-    h, s = hits[keep], score[keep]
-    order = np.lexsort((h["pos"], h["contig"], h["info"] >> 31, -s, h["guide"]))
-    h = h[order]
-    gg = h["guide"].astype(np.int64)
-    rank = np.arange(len(h)) - np.searchsorted(gg, gg, side="left")
-    if top_k:
-        h = h[rank < top_k]
-    return h if ranked else by_result_order(h)
-
-
-def oracle_hits(oracle, contigs, guides, m, pam=None):
-    """Every hit of the oracle with its rint(MIT * 2^24), MIT score and UB flag."""
-    want = oracle.search(contigs, guides, m, extra_pam=pam, mode=oracle.MODE_PREDICATE)
-    cache = {}
-    mit, ub = np.zeros(len(want)), np.zeros(len(want), dtype=np.uint64)
-    for i, info in enumerate(want["info"]):
-        mask = int(info) & 0x7FFFFF
-        if mask not in cache:
-            cache[mask] = oracle.mit_score([b for b in range(23) if (mask >> b) & 1] or [-1])
-        mit[i], ub[i] = cache[mask][0], cache[mask][1]
-    return want, np.rint(mit * 2.0 ** 24).astype(np.int64), mit, ub
-
-
 def device_hits(gen, guides, m, algo, pam=None):
     """The same from vsc_search + vsc_score_hits (inputs too large for the character-level oracle)."""
     hits = gen.search(guides, m, extra_pam=pam, algorithm=algo)
@@ -71,13 +34,6 @@ def device_hits(gen, guides, m, algo, pam=None):
     mit = hits.scores(mit=True)[0] if len(rec) else np.zeros(0)
     hits.close()
     return rec, np.rint(mit * 2.0 ** 24).astype(np.int64)
-
-
-def select(gen, guides, m, top_k=0, min_score=0, **kw):
-    h = gen.search_select(guides, m, top_k=top_k, min_score=min_score, **kw)
-    rec = h.to_numpy()
-    h.close()
-    return rec
 
 
 # ------------------------------------------------------------------------------------ 1. parity with the oracle

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import varscot_amd as va
-from helpers import make_genome, plant, random_guides, random_seq, revcomp
+from helpers import aggregate, make_genome, plant, random_guides, random_seq, revcomp
 
 pytestmark = pytest.mark.gpu
 
@@ -22,26 +22,6 @@ def ctx():
     c = va.Context(0)
     yield c
     c.close()
-
-
-def aggregate(hits, n_guides, mit, ub, exclude=None):
-    """Summary rows from records (HIT_DTYPE) and their MIT scores / UB flags (numpy, order-free)."""
-    out = np.zeros(n_guides, dtype=va.SUMMARY_DTYPE)
-    g = hits["guide"].astype(np.int64)
-    strand = (hits["info"] >> 31).astype(np.int64)
-    keep = np.ones(len(hits), dtype=bool)
-    if exclude is not None:
-        ex = np.asarray(exclude, dtype=np.int64).reshape(-1, 3)
-        hit_ex = (hits["contig"] == ex[g, 0]) & (hits["pos"] == ex[g, 1]) & (strand == ex[g, 2])
-        out["on_target"][g[hit_ex]] = 1
-        keep = ~hit_ex
-    g, h = g[keep], hits[keep]
-    fixed = np.rint(np.asarray(mit, dtype=np.float64)[keep] * 2.0 ** 24).astype(np.uint64)
-    np.add.at(out["mit_sum"], g, fixed)
-    np.add.at(out["mit_ub"], g, np.asarray(ub, dtype=np.uint64)[keep])
-    nm = ((h["info"] >> 23) & 31).astype(np.int64)
-    np.add.at(out["nm"], (g, nm), 1)
-    return out
 
 
 def oracle_summary(oracle, contigs, guides, m, extra_pam=None, exclude=None):

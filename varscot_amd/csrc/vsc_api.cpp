@@ -1264,13 +1264,14 @@ struct PassFound {
     uint32_t pos_base = 0;
     bool bases = false;  // SEED: every record's site lo plane lies beside it in ctx->vals_a (feature rows wanted)
     bool selected = false;  // select_pass has run: n, segs, cap describe the survivors, packed records at the start of ctx->keys_a
-    // host staging of the sinks, uploaded with hipMemcpyAsync: it lives here because the pass outlives every such copy (each
-    // sink synchronises before the next stage or the next pass touches it) - select_pass's offsets, sink_input's tables
+    // host staging of the sinks, uploaded with hipMemcpyAsync: it lives here because the pass outlives every such copy (the
+    // pass ends with a synchronise) - select_pass's offsets, written once behind a synchronise of its own, and sink_input's
+    // tables, written once per pass
     std::vector<uint64_t> sel_off;
     std::vector<SumSeg> sink_segs;
     std::vector<uint32_t> sink_tile0;
-    bool sink_staged = false;  // classify_pass has put the sinks' tables on the device: the sinks behind it take them as they are
-    bool classified = false;   // ... and its kernel has run between kEvClassStart and kEvClassEnd
+    SinkInput sink{};         // what sink_input staged (recs null: nothing yet)
+    bool classified = false;  // classify_pass's kernel has run between kEvClassStart and kEvClassEnd
 };
 
 // words within k substitutions of a 7-base segment (k < 0: none)
@@ -1559,27 +1560,27 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     return VSC_OK;
 }
 
-// The input of the summary and the selection kernels - the fields both argument structs begin with: the pass's records where
-// the search left them, and f.segs on the device (in ctx->sort_segs) as segments relative to the pass's first read with the
-// prefix of their tile counts, for tiles of `tile` records.  The tables are staged in f (see PassFound).
-template <class Args> hipError_t sink_input(vsc_ctx *ctx, PassFound &f, uint32_t tile, bool excluded, Args &a)
+// The sinks' input of the pass (SinkInput, vsc_internal.h) in f.sink: the pass's records where the search left them, and f.segs
+// on the device (in ctx->sort_segs) as segments relative to the pass's first read with the prefix of their tile counts.  The
+// first sink of the pass that asks builds and uploads the tables (staged in f, see PassFound); the others take them as they
+// are - every sink of a pass runs before select_pass and sort_pass put ctx->sort_segs and f.segs to their own use.
+// What the callers keep to: every sink of a pass passes the same `excluded` (only the first call reads it; run_search hands
+// all of them !excl.empty()), and f.sink holds device addresses of ctx->keys_a, vals_a, sort_segs and sum_excl, so none of
+// these buffers goes through ensure() between the first sink_input of a pass and the last sink's launch.
+hipError_t sink_input(vsc_ctx *ctx, PassFound &f, bool excluded)
 {
-    if (!f.sink_staged) {
-        f.sink_segs.clear();
-        f.sink_tile0.assign(1, 0);
-        for (const SortSeg &sg : f.segs) {
-            f.sink_segs.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
-            f.sink_tile0.push_back(f.sink_tile0.back() + (sg.n_in + tile - 1) / tile);
-        }
+    if (f.sink.recs) return hipSuccess;
+    f.sink_tile0.assign(1, 0);
+    for (const SortSeg &sg : f.segs) {
+        f.sink_segs.push_back(SumSeg{sg.in_off, sg.n_in, sg.guide_base - f.guide_base});
+        f.sink_tile0.push_back(f.sink_tile0.back() + (sg.n_in + kSumTile - 1) / kSumTile);
     }
     const size_t seg_bytes = f.sink_segs.size() * sizeof(SumSeg), tile0_bytes = f.sink_tile0.size() * sizeof(uint32_t);
     const size_t tile0_at = (seg_bytes + 255) / 256 * 256;
-    if (!f.sink_staged) {
-        VSC_TRY(ctx->sort_segs.ensure(tile0_at + tile0_bytes));
-        VSC_TRY(hipMemcpyAsync(ctx->sort_segs.p, f.sink_segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
-        VSC_TRY(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, f.sink_tile0.data(), tile0_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    a.recs = (const uint64_t *)ctx->keys_a.p;
+    VSC_TRY(ctx->sort_segs.ensure(tile0_at + tile0_bytes));
+    VSC_TRY(hipMemcpyAsync(ctx->sort_segs.p, f.sink_segs.data(), seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSC_TRY(hipMemcpyAsync((char *)ctx->sort_segs.p + tile0_at, f.sink_tile0.data(), tile0_bytes, hipMemcpyHostToDevice, ctx->stream));
+    SinkInput &a = f.sink;
     a.vals = f.algo == VSC_ALGO_SCAN ? (const uint32_t *)ctx->vals_a.p : nullptr;
     a.segs = (const SumSeg *)ctx->sort_segs.p;
     a.seg_tile0 = (const uint32_t *)((char *)ctx->sort_segs.p + tile0_at);
@@ -1588,6 +1589,7 @@ template <class Args> hipError_t sink_input(vsc_ctx *ctx, PassFound &f, uint32_t
     a.pos_pad = f.pos_pad;
     a.pos_base = f.pos_base;
     a.excl = excluded ? (const uint64_t *)ctx->sum_excl.p + f.guide_base : nullptr;
+    a.recs = (const uint64_t *)ctx->keys_a.p;
     return hipSuccess;
 }
 
@@ -1704,33 +1706,23 @@ int resident_ranks(vsc_ctx *ctx, const double *guide_activity, uint32_t n_guides
 // Classify stage (vsc_search_*_classified), between find_pass and the sinks: rf_predict_kernel walks the forest (made resident
 // by prepare_forest, the reads' activity ranks by resident_ranks, the interleaved planes by ensure_hl - all before the first
 // pass) over the records where the search kernel left them and leaves every record slot's votes in ctx->vals_b, one word per
-// slot of every tile of kSumTile - the layout of SelectArgs::score, which select_pass then takes as its keys.  The sinks'
-// tables it stages serve the sinks behind it.  Few rows: the trees are split over several workgroups per row tile, the votes
-// meet in atomics.  Nothing is read back: the kernel's time (kEvClassStart -> kEvClassEnd) is taken at the end of the pass.
+// slot of every tile of kSumTile - the layout of SelectArgs::score, which select_pass then takes as its keys.  Few rows: the
+// trees are split over several workgroups per row tile, the votes meet in atomics.  Nothing is read back: the kernel's time
+// (kEvClassStart -> kEvClassEnd) is taken at the end of the pass.
 int classify_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, uint32_t n_reads, bool excluded)
 {
     if (f.segs.empty()) return VSC_OK;
     RfArgs a{};
-    SelectArgs in{};
-    VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, in));
-    f.sink_staged = true;
+    VSC_HIP(ctx, sink_input(ctx, f, excluded));
     fill_forest(a, ctx);
+    a.in = f.sink;
     a.score.hl = genome->d_hl;
     a.score.first_pos = (uint32_t)(genome->first_word * 32);
     a.score.n_plane_words = genome->dev_words;
     a.score.guides = (const uint2 *)ctx->guides.p;  // the pass's reads
     a.act_rank = (const uint8_t *)ctx->forest.ranks.p + f.guide_base;
-    a.recs = in.recs;
-    a.vals = in.vals;
-    a.segs = in.segs;
-    a.seg_tile0 = in.seg_tile0;
-    a.n_segs = in.n_segs;
-    a.n_tiles = in.n_tiles;
-    a.pos_pad = in.pos_pad;
-    a.pos_base = in.pos_base;
-    a.excl = in.excl;
     a.n_reads = n_reads;
-    a.n = (uint64_t)in.n_tiles * kSumTile;
+    a.n = (uint64_t)a.in.n_tiles * kSumTile;
     VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.n * sizeof(uint32_t)));
     a.slot_votes = (uint32_t *)ctx->vals_b.p;
     const uint64_t groups = a.n / kRfRows;
@@ -1751,7 +1743,8 @@ int votes_summary_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, bool exclud
 {
     VotesSummaryArgs a{};
     if (!f.segs.empty()) {
-        VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
+        VSC_HIP(ctx, sink_input(ctx, f, excluded));
+        static_cast<SinkInput &>(a) = f.sink;
         a.out = (unsigned long long *)ctx->votes_rows.p + (size_t)f.guide_base * kSumWords;
         a.votes = (const uint32_t *)ctx->vals_b.p;
         a.n_trees = ctx->forest.n_trees;
@@ -1765,13 +1758,19 @@ int votes_summary_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, bool exclud
 
 // Summary sink (vsc_search_summary): summary_kernel adds the records where they lie into the pass's rows of ctx->sum_rows,
 // minus its loci in ctx->sum_excl if `excluded`.  No sort, no result buffer: finalize_ms times that kernel, sort_ms stays 0.
-// last = false (vsc_search_select with a summary): another sink follows and ends the pass; the kernel has run on return.
+// last = false (vsc_search_select with a summary): another sink follows and ends the pass; the kernel is then only enqueued.
+// Nothing waits for it here: the copies sink_input enqueued read f.sink_segs and f.sink_tile0, which are written once per
+// pass and live until the pass has ended; what the later stages rewrite (f.segs, f.n, f.cap, f.sel_off, ctx->sort_segs) is
+// read by no host-to-device copy of the sinks, and the stream orders their device work behind this kernel.  The host-timer
+// lap of the stage that synchronises next ("select: scores + thresholds + sync", or the sort's) therefore takes in this
+// kernel's time; vsc_timing, which is taken from events, is as it was.
 // reg: the device copy of the regions (resident_regions) - the rows over the hits inside go to ctx->sum_rows_in as well.
 int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, bool last = true, const RegionsView *reg = nullptr)
 {
     SummaryRegionArgs a{};
     if (!f.segs.empty()) {
-        VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
+        VSC_HIP(ctx, sink_input(ctx, f, excluded));
+        static_cast<SinkInput &>(a) = f.sink;
         a.out = (unsigned long long *)ctx->sum_rows.p + (size_t)f.guide_base * kSumWords;
         if (reg) {
             a.reg = *reg;
@@ -1781,7 +1780,6 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
     VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
     VSC_HIP(ctx, reg ? launch_summary_regions(a, ctx->stream) : launch_summary(a, ctx->stream));
     if (last) VSC_HIP(ctx, end_pass(ctx, f, "summary + sync", t));
-    else VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (select_pass rewrites f.segs and the staging the copies above read)
     return VSC_OK;
 }
 
@@ -1801,7 +1799,8 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     if (f.n == 0) return VSC_OK;
     hipStream_t st = ctx->stream;
     SelectRegionArgs a{};
-    VSC_HIP(ctx, sink_input(ctx, f, kSumTile, excluded, a));
+    VSC_HIP(ctx, sink_input(ctx, f, excluded));
+    static_cast<SinkInput &>(a) = f.sink;
     if (reg) {
         a.reg = *reg;
         a.drop = drop;

@@ -1,4 +1,4 @@
-// vsc_device.h - device helpers shared by the kernels of vsc_kernels.hip and vsc_seed.hip.
+// vsc_device.h - device helpers shared by the kernels of vsc_kernels.hip, vsc_seed.hip and vsc_sort.hip.
 #pragma once
 
 #include "vsc_internal.h"
@@ -57,6 +57,18 @@ __device__ __forceinline__ bool is_contig_end(const uint32_t *contig_end, uint32
         if (contig_end[mid] < p) lo = mid + 1; else hi = mid;
     }
     return lo < n_contigs && contig_end[lo] == p;
+}
+
+// The segment that holds tile `tile` of a tiled segment table (the bin sort's SortArgs, the sinks' SinkInput): last s with
+// seg_tile0[s] <= tile (wave-uniform arguments: scalar loads).
+__device__ __forceinline__ uint32_t segment_of_tile(const uint32_t *seg_tile0, uint32_t n_segs, uint32_t tile)
+{
+    uint32_t lo = 0, hi = n_segs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (seg_tile0[mid] <= tile) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // ------------------------------------------------------------------------------------------------

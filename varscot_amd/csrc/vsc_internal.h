@@ -260,6 +260,33 @@ struct SeedArgs {
     unsigned long long *counters;  // kCntPart + 4 p + {0,1,2}, kCntSites (= pairs compared), kCntVisited, kCntOverflow, cursors
 };
 
+// ---- the record sinks' input ---------------------------------------------------------------------------------------------
+// Every consumer of a pass's records - summary_kernel, votes_summary_kernel, select_score_kernel / select_compact_kernel and
+// rf_predict_kernel's classify in place - reads them where the search kernel left them: the packed records of every region
+// that holds any (SEED; sentinels among them) or the one span of (key, value) pairs (SCAN).  The spans are cut into tiles of
+// kSumTile record slots; slot k of tile i is word i * kSumTile + k of every array that lies beside the records (scores, votes).
+// A workgroup walks a range of consecutive tiles; a SEED workgroup's tiles lie in one region at a time - 64 reads (helpers: vsc_sink.h).
+constexpr int kSumThreads = 256;
+constexpr int kSumItems = 8;      // consecutive records a lane takes (one running accumulator per lane)
+constexpr int kSumTile = kSumThreads * kSumItems;
+constexpr int kSumTilesPerBlock = 8;
+
+struct SumSeg {
+    uint64_t in_off;      // first record of the region (SEED) / of the pairs (SCAN)
+    uint32_t n;           // records in the span (SEED: sentinels included)
+    uint32_t first_read;  // pass-local index of the region's first read (SCAN: 0, the key holds the pass-local read)
+};
+
+struct SinkInput {
+    const uint64_t *recs;       // SEED: packed records; SCAN: keys (read << 33 | strand << 32 | global position)
+    const uint32_t *vals;       // SCAN: NM << 23 | mask; SEED: null
+    const SumSeg *segs;
+    const uint32_t *seg_tile0;  // [n_segs + 1]: first tile (kSumTile records) of every segment
+    uint32_t n_segs, n_tiles;
+    uint32_t pos_pad, pos_base; // SEED: the pass's position encoding (vsc_sort.hip pack_pair)
+    const uint64_t *excl;       // per pass-local read: strand << 32 | global position of the excluded locus, ~0: none (null: none)
+};
+
 // ---- random-forest inference ---------------------------------------------------------------------------------
 // Every split of the forest is a TEST `x <= thr` on a small non-negative integer: the predictors of the feature
 // matrix are flags and counts (`x <= split` is `x <= floor(split)`), and the on-target activity (a double, constant
@@ -293,8 +320,6 @@ struct RfTest {
     uint16_t pad;
 };
 
-struct SumSeg;  // (below: the per-guide summary)
-
 struct RfArgs {
     const uint32_t *nodes;      // [n_trees * n_nodes], tree-major
     const uint8_t *depth;       // [n_trees] steps from the root to the deepest terminal node
@@ -314,52 +339,28 @@ struct RfArgs {
     uint16_t *votes16;          // ... or 16-bit (fused path; tree_splits == 1)
     uint32_t tree_splits;       // gridDim.y: every workgroup row walks n_trees / tree_splits trees
     ScoreArgs score;            // fused path: hits, planes, reads (+ optional MIT output)
-    // classify in place (mode 3): the rows are the search kernel's records where they lie (`recs` non-null; the two forms
-    // SummaryArgs describes), 512 row slots per workgroup = a quarter of a tile of kSumTile; the votes go into one word per
+    // classify in place (modes 3, 4): the rows are the search kernel's records where they lie (`in.recs` non-null: the sinks'
+    // input, SinkInput above), 512 row slots per workgroup = a quarter of a tile of kSumTile; the votes go into one word per
     // record slot of every tile (SelectArgs::score's layout; kSelDropped: sentinel, read beyond the pass, excluded locus), added
     // with atomics into a zeroed array when tree_splits > 1.  score.hl / first_pos: the planes; score.guides and act_rank:
     // per pass-local read
-    const uint64_t *recs;
-    const uint32_t *vals;
-    const SumSeg *segs;
-    const uint32_t *seg_tile0;
-    uint32_t n_segs, n_tiles;
-    uint32_t pos_pad, pos_base;
-    const uint64_t *excl;
+    SinkInput in;
     uint32_t n_reads;
     uint32_t *slot_votes;
 };
 
 // ---- per-guide summary (vsc_search_summary; summary_kernel in vsc_kernels.hip) ----------------------------------------------
-// The kernel reads the search kernel's records where they lie - the packed records of every region (SEED) or the (key, value)
-// pairs (SCAN) - and adds them into one row of kSumWords 64-bit words per read of the pass, the layout of vsc_guide_summary:
-// mit_sum, nm[0..8], mit_ub, on_target (low half of the last word).
+// The kernel adds the records of its SinkInput into one row of kSumWords 64-bit words per read of the pass, the layout of
+// vsc_guide_summary: mit_sum, nm[0..8], mit_ub, on_target (low half of the last word).
 constexpr int kSumWords = 12;
 constexpr int kSumCounts = 11;    // LDS counters per read of the region: nm[0..8], mit_ub, on_target
-constexpr int kSumThreads = 256;
-constexpr int kSumItems = 8;      // consecutive records a lane takes (one running accumulator per lane)
-constexpr int kSumTile = kSumThreads * kSumItems;
-constexpr int kSumTilesPerBlock = 8;
 constexpr int kSumCountBits = 7;  // nm counters of a lane packed into one 64-bit word (9 x 7 bits; a lane adds <= kSumItems)
 
-struct SumSeg {
-    uint64_t in_off;      // first record of the region (SEED) / of the pairs (SCAN)
-    uint32_t n;           // records in the span (SEED: sentinels included)
-    uint32_t first_read;  // pass-local index of the region's first read (SCAN: 0, the key holds the pass-local read)
-};
-
-struct SummaryArgs {
-    const uint64_t *recs;       // SEED: packed records; SCAN: keys (read << 33 | strand << 32 | global position)
-    const uint32_t *vals;       // SCAN: NM << 23 | mask; SEED: null
-    const SumSeg *segs;
-    const uint32_t *seg_tile0;  // [n_segs + 1]: first tile (kSumTile records) of every segment
-    uint32_t n_segs, n_tiles;
-    uint32_t pos_pad, pos_base; // SEED: the pass's position encoding (vsc_sort.hip pack_pair)
-    const uint64_t *excl;       // per pass-local read: strand << 32 | global position of the excluded locus, ~0: none (null: none)
+struct SummaryArgs : SinkInput {
     unsigned long long *out;    // kSumWords per pass-local read, zeroed once per call
 };
 
-// Votes summary (vsc_search_summary_classified; votes_summary_kernel): SummaryArgs' input + the votes word of every record slot
+// Votes summary (vsc_search_summary_classified; votes_summary_kernel): the same input + the votes word of every record slot
 // (RfArgs::slot_votes), added into rows of kSumWords words per pass-local read, the layout of vsc_guide_votes: votes_sum, active,
 // ties, active_nm[0..8].
 struct VotesSummaryArgs : SummaryArgs {
@@ -370,7 +371,7 @@ struct VotesSummaryArgs : SummaryArgs {
 // ---- per-guide selection (vsc_search_select; select_*_kernel in vsc_kernels.hip) -------------------------------------------
 // An exact per-read radix select on the composite key  score (31 bits) << 33 | ~(strand << 32 | global position) (33 bits):
 // the larger key is the better hit (score descending, '+' before '-', position ascending), and keys are unique per read.
-// Round 1 runs over the records where the search kernel left them (the two forms SummaryArgs describes): every record's
+// Round 1 runs over the records where the search kernel left them (SinkInput): every record's
 // score goes into a word beside it and into its read's histogram over kSelBins monotone coarse bins of the score.  From the
 // histogram every read gets its threshold bin (the bin the K-th best lies in); round 2 copies the records of the bins >=
 // the threshold - the candidates - into per-read lists; the later rounds (select_resolve_kernel) run over a read's list only.
@@ -381,14 +382,7 @@ constexpr int kSelMinTilesPerBlock = 8;    // every CU a few workgroups (one LDS
 constexpr uint32_t kSelDropped = ~0u;    // score word of a record that is no candidate (sentinel, excluded locus, below the floor)
 constexpr int kSelKeyPosBits = 33;
 
-struct SelectArgs {
-    const uint64_t *recs;       // as SummaryArgs
-    const uint32_t *vals;
-    const SumSeg *segs;
-    const uint32_t *seg_tile0;
-    uint32_t n_segs, n_tiles;
-    uint32_t pos_pad, pos_base;
-    const uint64_t *excl;       // per pass-local read, as SummaryArgs (null: none)
+struct SelectArgs : SinkInput {
     uint32_t min_score;         // records below it are dropped
     uint32_t vote_trees;        // 0: the score is rint(MIT * 2^24), computed in round 1; else the forest's tree count: `score` holds
                                 // the records' votes on entry (classify in place), min_score is a floor on them, linear bins

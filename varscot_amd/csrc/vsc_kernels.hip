@@ -13,6 +13,7 @@
 // no MFMA: the comparison is not a dense contraction.
 #include "vsc_internal.h"
 #include "vsc_device.h"
+#include "vsc_sink.h"
 #include "vsc_mit.h"
 
 #include <cstring>
@@ -822,43 +823,15 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const std::conditi
     __shared__ uint64_t s_rec[kWavesPerGroup][kWave * kStride];
     __shared__ uint32_t s_val[kSeed ? 1 : kWavesPerGroup][kSeed ? 1 : kWave * kStride];
     __shared__ unsigned long long s_mit[kSeed ? kTabReads : 1];
-    __shared__ uint32_t s_cnt[kSeed ? kTabReads * kSumCounts : 1];
+    __shared__ uint32_t s_cnt[(kSeed ? kTabReads : 1) * kSumCounts];  // (SCAN: unused, a one-row table so that the helpers' row count is deduced)
     const uint32_t t = threadIdx.x, lane = t % kWave, wave = t / kWave;
-    if (kSeed) {
-        for (uint32_t i = t; i < kTabReads * kSumCounts; i += kSumThreads) s_cnt[i] = 0;
-        for (uint32_t i = t; i < kTabReads; i += kSumThreads) s_mit[i] = 0;
-        block_sync();
-    }
+    if (kSeed) sink_table_zero<kSumThreads>(s_mit, s_cnt, t);
     const uint32_t tile_begin = blockIdx.x * kSumTilesPerBlock, tile_end = min(tile_begin + (uint32_t)kSumTilesPerBlock, a.n_tiles);
-    uint32_t seg = 0;
-    {
-        uint32_t lo = 0, hi = a.n_segs;  // last s with seg_tile0[s] <= tile_begin
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (a.seg_tile0[mid] <= tile_begin) lo = mid; else hi = mid;
-        }
-        seg = lo;
-    }
+    uint32_t seg = segment_of_tile(a.seg_tile0, a.n_segs, tile_begin);
     // the region's LDS table -> the result rows of its reads
     auto flush_table = [&](const SumSeg &sg) {
-        block_sync();
-        for (uint32_t i = t; i < kTabReads * kSumWords; i += kSumThreads) {
-            const uint32_t r = i / kSumWords, f = i % kSumWords;
-            unsigned long long v;
-            if (f == 0) {
-                v = s_mit[r];
-                s_mit[r] = 0;
-            } else {
-                v = s_cnt[r * kSumCounts + f - 1];
-                s_cnt[r * kSumCounts + f - 1] = 0;
-            }
-            if constexpr (kRegions) {
-                if (v) atomicAdd(&(r < (uint32_t)kRegionReads ? a.out : a.out_in)[(size_t)(sg.first_read + (r & (kRegionReads - 1))) * kSumWords + f], v);
-            } else {
-                if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
-            }
-        }
-        block_sync();
+        if constexpr (kRegions) sink_table_flush<kSumThreads>(s_mit, s_cnt, t, sg, a.out, a.out_in);
+        else sink_table_flush<kSumThreads>(s_mit, s_cnt, t, sg, a.out);
     };
     for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
         if (tile >= a.seg_tile0[seg + 1]) {
@@ -890,34 +863,25 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const std::conditi
         uint64_t cnt_in = 0;  // (kRegions) the same over the records in the regions
         unsigned long long mit_in = 0;
         uint32_t ub_in = 0;
-        // one accumulator set into one LDS row (SEED) / one result row (SCAN)
-        auto flush_row = [&](uint32_t row, unsigned long long *o, unsigned long long m, uint64_t c9, uint32_t u) {
-            if (kSeed) {
-                if (m) atomicAdd(&s_mit[row], m);
-#pragma unroll
-                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(c9 >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
-                    if (c) atomicAdd(&s_cnt[row * kSumCounts + k], c);
-                }
-                if (u) atomicAdd(&s_cnt[row * kSumCounts + 9], u);
-                if (on) atomicAdd(&s_cnt[row * kSumCounts + 10], on);
-            } else {
-                if (m) atomicAdd(&o[0], m);
-#pragma unroll
-                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(c9 >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
-                    if (c) atomicAdd(&o[1 + k], (unsigned long long)c);
-                }
-                if (u) atomicAdd(&o[10], (unsigned long long)u);
-                if (on) atomicAdd(&o[11], (unsigned long long)on);
-            }
+        // one accumulator set into a row: its sum word and the counters behind it (an LDS row, SEED; a result row, SCAN)
+        auto flush_row = [&](unsigned long long *sum, auto *counts, unsigned long long m, uint64_t c9, uint32_t u) {
+            using T = std::remove_pointer_t<decltype(counts)>;
+            if (m) atomicAdd(sum, m);
+            sink_add_counts(counts, c9);
+            if (u) atomicAdd(&counts[9], (T)u);
+            if (on) atomicAdd(&counts[10], (T)on);
         };
         auto flush = [&]() {
             if (cur == ~0u) return;
-            const uint32_t r = kSeed ? cur - sg.first_read : 0u;
-            flush_row(r, a.out + (size_t)cur * kSumWords, mit, cnt, ub);
+            if constexpr (kSeed) {
+                const uint32_t r = cur - sg.first_read;
+                flush_row(&s_mit[r], &s_cnt[r * kSumCounts], mit, cnt, ub);
+                if constexpr (kRegions) flush_row(&s_mit[kRegionReads + r], &s_cnt[(kRegionReads + r) * kSumCounts], mit_in, cnt_in, ub_in);
+            } else {
+                flush_row(&a.out[(size_t)cur * kSumWords], &a.out[(size_t)cur * kSumWords + 1], mit, cnt, ub);
+                if constexpr (kRegions) flush_row(&a.out_in[(size_t)cur * kSumWords], &a.out_in[(size_t)cur * kSumWords + 1], mit_in, cnt_in, ub_in);
+            }
             if constexpr (kRegions) {
-                flush_row(kRegionReads + r, a.out_in + (size_t)cur * kSumWords, mit_in, cnt_in, ub_in);
                 cnt_in = 0;
                 mit_in = 0;
                 ub_in = 0;
@@ -929,19 +893,9 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const std::conditi
         for (int k = 0; k < kSumItems; ++k) {
             if (lane * kSumItems + (uint32_t)k >= n) break;
             const uint64_t r = s_rec[wave][lane * kStride + k];
+            if (sink_sentinel<kSeed>(r)) continue;
             uint32_t read, strand, pos, mask;
-            if (kSeed) {
-                if (r >> 63) continue;  // sentinel: a reserved slot nobody wrote
-                read = sg.first_read + (uint32_t)((r >> kRecReadShift) & (kRegionReads - 1));
-                strand = (uint32_t)(r >> kRecStrandShift) & 1u;
-                pos = ((uint32_t)(r >> kRecPosShift) >> a.pos_pad) + a.pos_base;
-                mask = (uint32_t)r & kMask23;
-            } else {
-                read = (uint32_t)(r >> 33);
-                strand = (uint32_t)(r >> 32) & 1u;
-                pos = (uint32_t)r;
-                mask = s_val[wave][lane * kStride + k] & kMask23;
-            }
+            sink_decode_word<kSeed>(a, sg, r, kSeed ? 0u : s_val[wave][lane * kStride + k], read, strand, pos, mask);
             if (read != cur) {
                 flush();
                 cur = read;
@@ -969,26 +923,24 @@ __global__ __launch_bounds__(kSumThreads) void summary_kernel(const std::conditi
     if (kSeed && tile_begin < tile_end) flush_table(a.segs[seg]);
 }
 
-hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream)
+// The SCAN (args.vals) or the SEED instantiation of a kernel that walks the tiles of its SinkInput, tiles_per_block per workgroup.
+template <class Args>
+hipError_t launch_sink(void (*scan)(Args), void (*seed)(Args), const Args &args, uint32_t tiles_per_block, uint32_t threads, hipStream_t stream)
 {
     if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
-    if (args.vals)
-        hipLaunchKernelGGL((summary_kernel<false, false>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL((summary_kernel<true, false>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
+    void (*const kernel)(Args) = args.vals ? scan : seed;
+    hipLaunchKernelGGL(kernel, dim3((args.n_tiles + tiles_per_block - 1) / tiles_per_block), dim3(threads), 0, stream, args);
     return hipGetLastError();
+}
+
+hipError_t launch_summary(const SummaryArgs &args, hipStream_t stream)
+{
+    return launch_sink(summary_kernel<false, false>, summary_kernel<true, false>, args, kSumTilesPerBlock, kSumThreads, stream);
 }
 
 hipError_t launch_summary_regions(const SummaryRegionArgs &args, hipStream_t stream)
 {
-    if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
-    if (args.vals)
-        hipLaunchKernelGGL((summary_kernel<false, true>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL((summary_kernel<true, true>), dim3(blocks), dim3(kSumThreads), 0, stream, args);
-    return hipGetLastError();
+    return launch_sink(summary_kernel<false, true>, summary_kernel<true, true>, args, kSumTilesPerBlock, kSumThreads, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1022,37 +974,6 @@ struct SelectVotesKey {
     }
 };
 
-// record `at` of segment sg: pass-local read, strand << 32 | global position, mismatch mask; false: a sentinel
-// (Args: SelectArgs, or any struct with its recs, vals, pos_pad, pos_base - the classifier's RfArgs)
-template <bool kSeed, class Args>
-__device__ __forceinline__ bool select_decode(const Args &a, const SumSeg &sg, uint64_t at, uint32_t &read, uint64_t &locus, uint32_t &mask)
-{
-    const uint64_t r = a.recs[at];
-    if (kSeed) {
-        if (r >> 63) return false;
-        read = sg.first_read + (uint32_t)((r >> kRecReadShift) & (kRegionReads - 1));
-        const uint32_t pos = ((uint32_t)(r >> kRecPosShift) >> a.pos_pad) + a.pos_base;
-        locus = ((r >> kRecStrandShift) & 1ull) << 32 | pos;
-        mask = (uint32_t)r & kMask23;
-    } else {
-        read = (uint32_t)(r >> 33);
-        locus = r & ((1ull << kSelKeyPosBits) - 1ull);
-        mask = a.vals[at] & kMask23;
-    }
-    return true;
-}
-
-// the segment that holds tile `tile`: last s with seg_tile0[s] <= tile
-template <class Args> __device__ __forceinline__ uint32_t select_find_seg(const Args &a, uint32_t tile)
-{
-    uint32_t lo = 0, hi = a.n_segs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a.seg_tile0[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // Round 1, over the records where the search kernel left them (tiled as summary_kernel tiles them): every record's score
 // into the word beside it (kSelDropped: sentinel, excluded locus, below the floor) and into its read's histogram.  SEED: a
 // workgroup's tiles lie in one region at a time, whose 64 reads x 128 bins are an LDS table (32 KB, five workgroups per CU)
@@ -1073,7 +994,8 @@ __global__ __launch_bounds__(kSelThreads) void select_score_kernel(const std::co
         block_sync();
     }
     const uint32_t tile_begin = blockIdx.x * a.tiles_per_block, tile_end = min(tile_begin + a.tiles_per_block, a.n_tiles);
-    uint32_t seg = select_find_seg(a, tile_begin);
+    uint32_t seg = segment_of_tile(a.seg_tile0, a.n_segs, tile_begin);
+    // the region's histograms -> those of its reads
     auto flush_table = [&](const SumSeg &sg) {
         block_sync();
         for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSelBins); i += kSelThreads) {
@@ -1102,13 +1024,13 @@ __global__ __launch_bounds__(kSelThreads) void select_score_kernel(const std::co
             if constexpr (Key::kStored) {
                 // the classifier has been here: the word holds the record's votes, or kSelDropped for what is no counted hit
                 const uint32_t sc = a.score[(uint64_t)tile * kSumTile + (uint32_t)k * kSelThreads + t];
-                if (sc != kSelDropped && sc >= a.min_score && select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads &&
+                if (sc != kSelDropped && sc >= a.min_score && sink_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads &&
                     select_side(a, (uint32_t)locus)) {
                     score = sc;
                     if (kSeed) atomicAdd(&s_hist[(read - sg.first_read) * kSelBins + Key::bin(a, sc)], 1u);
                     else atomicAdd(&a.hist[(size_t)read * kSelBins + Key::bin(a, sc)], 1u);
                 }
-            } else if (select_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus) &&
+            } else if (sink_decode<kSeed>(a, sg, at, read, locus, mask) && read < a.n_reads && !(a.excl && a.excl[read] == locus) &&
                 select_side(a, (uint32_t)locus)) {
                 int ub;
                 const uint32_t sc = (uint32_t)__builtin_rint(mit_score(mask, &ub) * 0x1p24);  // <= 100 * 2^24 < 2^31; as summary_kernel
@@ -1152,7 +1074,7 @@ __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(const Selec
 {
     const uint32_t t = threadIdx.x;
     const uint32_t tile_begin = blockIdx.x * a.tiles_per_block, tile_end = min(tile_begin + a.tiles_per_block, a.n_tiles);
-    uint32_t seg = select_find_seg(a, tile_begin);
+    uint32_t seg = segment_of_tile(a.seg_tile0, a.n_segs, tile_begin);
     for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
         while (tile >= a.seg_tile0[seg + 1]) ++seg;
         const SumSeg sg = a.segs[seg];
@@ -1168,7 +1090,7 @@ __global__ __launch_bounds__(kSelThreads) void select_compact_kernel(const Selec
             if (kSeed && bin < region_thr) continue;  // (most records: below every threshold of the region, the record is not read)
             uint32_t read, mask;
             uint64_t locus;
-            if (!select_decode<kSeed>(a, sg, sg.in_off + i, read, locus, mask)) continue;
+            if (!sink_decode<kSeed>(a, sg, sg.in_off + i, read, locus, mask)) continue;
             if (bin < a.thr[read]) continue;
             const uint32_t slot = atomicAdd(&a.cursor[read], 1u);
             if (slot >= a.count[read]) continue;  // (cannot happen: the histogram counted these very records)
@@ -1249,35 +1171,15 @@ __global__ __launch_bounds__(kSumThreads) void votes_summary_kernel(const VotesS
 {
     static_assert(kSumCounts == 2 + VSC_MAX_MISMATCHES + 1 && kSumWords == kSumCounts + 1, "vsc_guide_votes: votes_sum + active, ties, active_nm[9]");
     __shared__ unsigned long long s_sum[kSeed ? kRegionReads : 1];
-    __shared__ uint32_t s_cnt[kSeed ? kRegionReads * kSumCounts : 1];
+    __shared__ uint32_t s_cnt[(kSeed ? kRegionReads : 1) * kSumCounts];  // (SCAN: unused, one row - as in summary_kernel)
     const uint32_t t = threadIdx.x;
-    if (kSeed) {
-        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSumCounts); i += kSumThreads) s_cnt[i] = 0;
-        for (uint32_t i = t; i < (uint32_t)kRegionReads; i += kSumThreads) s_sum[i] = 0;
-        block_sync();
-    }
+    if (kSeed) sink_table_zero<kSumThreads>(s_sum, s_cnt, t);
     const uint32_t tile_begin = blockIdx.x * kSumTilesPerBlock, tile_end = min(tile_begin + (uint32_t)kSumTilesPerBlock, a.n_tiles);
     if (tile_begin >= tile_end) return;
-    uint32_t seg = select_find_seg(a, tile_begin);
-    auto flush_table = [&](const SumSeg &sg) {
-        block_sync();
-        for (uint32_t i = t; i < (uint32_t)(kRegionReads * kSumWords); i += kSumThreads) {
-            const uint32_t r = i / kSumWords, f = i % kSumWords;
-            unsigned long long v;
-            if (f == 0) {
-                v = s_sum[r];
-                s_sum[r] = 0;
-            } else {
-                v = s_cnt[r * kSumCounts + f - 1];
-                s_cnt[r * kSumCounts + f - 1] = 0;
-            }
-            if (v) atomicAdd(&a.out[(size_t)(sg.first_read + r) * kSumWords + f], v);
-        }
-        block_sync();
-    };
+    uint32_t seg = segment_of_tile(a.seg_tile0, a.n_segs, tile_begin);
     for (uint32_t tile = tile_begin; tile < tile_end; ++tile) {
         if (tile >= a.seg_tile0[seg + 1]) {
-            if (kSeed) flush_table(a.segs[seg]);
+            if (kSeed) sink_table_flush<kSumThreads>(s_sum, s_cnt, t, a.segs[seg], a.out);
             while (tile >= a.seg_tile0[seg + 1]) ++seg;
         }
         const SumSeg sg = a.segs[seg];
@@ -1285,29 +1187,18 @@ __global__ __launch_bounds__(kSumThreads) void votes_summary_kernel(const VotesS
         const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile + slot0;
         uint32_t cur = ~0u, vsum = 0, act = 0, tie = 0;
         uint64_t nm = 0;
+        // the accumulator into a row: its sum word and the counters behind it (an LDS row, SEED; a result row, SCAN)
+        auto flush_row = [&](unsigned long long *sum, auto *counts) {
+            using T = std::remove_pointer_t<decltype(counts)>;
+            if (vsum) atomicAdd(sum, (unsigned long long)vsum);
+            if (act) atomicAdd(&counts[0], (T)act);
+            if (tie) atomicAdd(&counts[1], (T)tie);
+            sink_add_counts(&counts[2], nm);
+        };
         auto flush = [&]() {
             if (cur == ~0u) return;
-            if (kSeed) {
-                const uint32_t row = cur - sg.first_read;
-                if (vsum) atomicAdd(&s_sum[row], (unsigned long long)vsum);
-                if (act) atomicAdd(&s_cnt[row * kSumCounts], act);
-                if (tie) atomicAdd(&s_cnt[row * kSumCounts + 1], tie);
-#pragma unroll
-                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(nm >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
-                    if (c) atomicAdd(&s_cnt[row * kSumCounts + 2 + k], c);
-                }
-            } else {
-                unsigned long long *o = a.out + (size_t)cur * kSumWords;
-                if (vsum) atomicAdd(&o[0], (unsigned long long)vsum);
-                if (act) atomicAdd(&o[1], (unsigned long long)act);
-                if (tie) atomicAdd(&o[2], (unsigned long long)tie);
-#pragma unroll
-                for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
-                    const uint32_t c = (uint32_t)(nm >> (kSumCountBits * k)) & ((1u << kSumCountBits) - 1u);
-                    if (c) atomicAdd(&o[3 + k], (unsigned long long)c);
-                }
-            }
+            if constexpr (kSeed) flush_row(&s_sum[cur - sg.first_read], &s_cnt[(cur - sg.first_read) * kSumCounts]);
+            else flush_row(&a.out[(size_t)cur * kSumWords], &a.out[(size_t)cur * kSumWords + 1]);
             vsum = act = tie = 0;
             nm = 0;
         };
@@ -1317,7 +1208,7 @@ __global__ __launch_bounds__(kSumThreads) void votes_summary_kernel(const VotesS
             if (v == kSelDropped) continue;  // no counted hit: the record is not read
             uint32_t read, mask;
             uint64_t locus;
-            if (!select_decode<kSeed>(a, sg, sg.in_off + first + (uint32_t)k, read, locus, mask) || read >= a.n_reads) continue;
+            if (!sink_decode<kSeed>(a, sg, sg.in_off + first + (uint32_t)k, read, locus, mask) || read >= a.n_reads) continue;
             if (read != cur) {
                 flush();
                 cur = read;
@@ -1332,45 +1223,25 @@ __global__ __launch_bounds__(kSumThreads) void votes_summary_kernel(const VotesS
         }
         flush();
     }
-    if (kSeed) flush_table(a.segs[seg]);
+    if (kSeed) sink_table_flush<kSumThreads>(s_sum, s_cnt, t, a.segs[seg], a.out);
 }
 
 hipError_t launch_votes_summary(const VotesSummaryArgs &args, hipStream_t stream)
 {
-    if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + kSumTilesPerBlock - 1) / kSumTilesPerBlock;
-    if (args.vals)
-        hipLaunchKernelGGL(votes_summary_kernel<false>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL(votes_summary_kernel<true>, dim3(blocks), dim3(kSumThreads), 0, stream, args);
-    return hipGetLastError();
+    return launch_sink(votes_summary_kernel<false>, votes_summary_kernel<true>, args, kSumTilesPerBlock, kSumThreads, stream);
 }
 
 hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream)
 {
-    if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
-    if (args.vote_trees) {
-        if (args.vals)
-            hipLaunchKernelGGL((select_score_kernel<false, false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-        else
-            hipLaunchKernelGGL((select_score_kernel<true, false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    } else if (args.vals)
-        hipLaunchKernelGGL((select_score_kernel<false, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL((select_score_kernel<true, false>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    return hipGetLastError();
+    if (args.vote_trees)
+        return launch_sink(select_score_kernel<false, false, SelectVotesKey>, select_score_kernel<true, false, SelectVotesKey>, args,
+                           args.tiles_per_block, kSelThreads, stream);
+    return launch_sink(select_score_kernel<false, false>, select_score_kernel<true, false>, args, args.tiles_per_block, kSelThreads, stream);
 }
 
 hipError_t launch_select_score_regions(const SelectRegionArgs &args, hipStream_t stream)
 {
-    if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
-    if (args.vals)
-        hipLaunchKernelGGL((select_score_kernel<false, true>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL((select_score_kernel<true, true>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    return hipGetLastError();
+    return launch_sink(select_score_kernel<false, true>, select_score_kernel<true, true>, args, args.tiles_per_block, kSelThreads, stream);
 }
 
 hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream)
@@ -1382,18 +1253,10 @@ hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream)
 
 hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream)
 {
-    if (args.n_tiles == 0) return hipSuccess;
-    const unsigned blocks = (args.n_tiles + args.tiles_per_block - 1) / args.tiles_per_block;
-    if (args.vote_trees) {
-        if (args.vals)
-            hipLaunchKernelGGL((select_compact_kernel<false, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-        else
-            hipLaunchKernelGGL((select_compact_kernel<true, SelectVotesKey>), dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    } else if (args.vals)
-        hipLaunchKernelGGL(select_compact_kernel<false>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    else
-        hipLaunchKernelGGL(select_compact_kernel<true>, dim3(blocks), dim3(kSelThreads), 0, stream, args);
-    return hipGetLastError();
+    if (args.vote_trees)
+        return launch_sink(select_compact_kernel<false, SelectVotesKey>, select_compact_kernel<true, SelectVotesKey>, args, args.tiles_per_block,
+                           kSelThreads, stream);
+    return launch_sink(select_compact_kernel<false>, select_compact_kernel<true>, args, args.tiles_per_block, kSelThreads, stream);
 }
 
 hipError_t launch_select_resolve(const SelectArgs &args, hipStream_t stream)
@@ -1464,12 +1327,12 @@ template <int kMode> __global__ __launch_bounds__(kRfRows) void rf_predict_kerne
     if (kMode >= 3) {
         static_assert(kSumTile % kRfRows == 0, "a workgroup's row slots lie in one tile");
         const uint32_t tile = blockIdx.x / (uint32_t)(kSumTile / kRfRows);
-        const uint32_t seg = select_find_seg(a, tile);
-        const SumSeg sg = a.segs[seg];
-        const uint32_t i = (tile - a.seg_tile0[seg]) * (uint32_t)kSumTile + (blockIdx.x % (uint32_t)(kSumTile / kRfRows)) * (uint32_t)kRfRows + t;
+        const uint32_t seg = segment_of_tile(a.in.seg_tile0, a.in.n_segs, tile);
+        const SumSeg sg = a.in.segs[seg];
+        const uint32_t i = (tile - a.in.seg_tile0[seg]) * (uint32_t)kSumTile + (blockIdx.x % (uint32_t)(kSumTile / kRfRows)) * (uint32_t)kRfRows + t;
         uint32_t mask;
-        live = i < sg.n && select_decode<kMode == 4>(a, sg, sg.in_off + i, rec_read, rec_locus, mask) && rec_read < a.n_reads &&
-               !(a.excl && a.excl[rec_read] == rec_locus) &&
+        live = i < sg.n && sink_decode<kMode == 4>(a.in, sg, sg.in_off + i, rec_read, rec_locus, mask) && rec_read < a.n_reads &&
+               !(a.in.excl && a.in.excl[rec_read] == rec_locus) &&
                (uint64_t)(((uint32_t)rec_locus - a.score.first_pos) >> 5) + 1u < a.score.n_plane_words;  // (every window of the shard: its planes are padded)
     }
     if (kMode == 0) {
@@ -1742,9 +1605,9 @@ hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream)
     // test bits + the tree tile (+ a sink node per chain)
     const size_t lds = args.compact == 2u ? (size_t)kRfPairBitsBytes + kRfPairTileBytes + 8 * kRfChains
                                           : n_words * kRfRows * sizeof(uint32_t) + (size_t)kRfTileBytes + 4 * kRfChains;
-    const int mode = args.recs ? (args.vals ? 3 : 4) : args.dense ? 0 : (args.packed ? 1 : 2);
+    const int mode = args.in.recs ? (args.in.vals ? 3 : 4) : args.dense ? 0 : (args.packed ? 1 : 2);
     if (mode == 2 && args.tree_splits != 1) return hipErrorInvalidValue;
-    if (mode >= 3 && (args.n != (uint64_t)args.n_tiles * kSumTile || args.tree_splits == 0 || args.tree_splits > 65535u)) return hipErrorInvalidValue;
+    if (mode >= 3 && (args.n != (uint64_t)args.in.n_tiles * kSumTile || args.tree_splits == 0 || args.tree_splits > 65535u)) return hipErrorInvalidValue;
     auto go = [&](auto kernel) {
         hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;

@@ -85,17 +85,6 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t *s, uint32_t n
     return total;
 }
 
-// the segment that holds tile `tile`: last s with seg_tile0[s] <= tile (wave-uniform arguments: scalar loads)
-__device__ __forceinline__ uint32_t segment_of_tile(const uint32_t *seg_tile0, uint32_t n_segs, uint32_t tile)
-{
-    uint32_t lo = 0, hi = n_segs;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (seg_tile0[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // level 0: a (key, value) pair of the streaming scan -> packed record (the read's region is the bin, not part of it)
 __device__ __forceinline__ uint64_t pack_pair(uint64_t key, uint32_t val, uint32_t pos_pad, uint32_t pos_base)
 {
