@@ -453,6 +453,81 @@ int vsc_guides_free(vsc_guides *guides);
 /* The labels of a result's records / of the candidates under `regions` (see vsc_regions_locate above). */
 int vsc_hits_locate(vsc_hits *hits, const vsc_regions *regions, uint32_t *labels);
 int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *labels);
+/*
+ * Paired-nickase screen (Cas9 D10A double nickase, dimeric FokI-dCas9): a design of TWO guides cuts only where an off-target
+ * of one guide and an off-target of the other lie close together on opposite strands.  Coordinates are vsc_hit's and
+ * vsc_locus': pos = 0-based leftmost base of the 23-base window on the forward genome, strand 1 = '-'.  Two windows on the
+ * same contig and on opposite strands have
+ *     delta = pos(the '+' window) - pos(the '-' window)      (signed)
+ * and are PAIRED under [delta_min, delta_max] iff delta_min <= delta <= delta_max.  delta does not depend on which guide sits
+ * on which strand, and the reverse complement of a locus has the same delta, so one range meets both orientations of an
+ * off-target locus.  The nickase literature's offset (gap between the protospacers' PAM-distal ends, negative = overlap) is
+ * delta - 23; PAM-out (the '-' window to the left) is delta > 0, PAM-in a negative range.  Windows on different contigs or on
+ * the same strand never pair.  pos +- delta is computed in 64-bit signed integers and clipped to [0, UINT32_MAX].
+ * delta_min > delta_max, a bound outside +-2^30 or a non-zero reserved field: VSC_ERR_INVALID.
+ *
+ * vsc_loci_pairs: host only, no device needed.  Every (a, b) - indices into loci[], any order of loci[] - with loci[a] a '-'
+ * window, loci[b] a '+' window and the two PAIRED, in ascending (a, b).  Entries with contig == UINT32_MAX (or a strand > 1)
+ * take part in nothing; two equal loci are two entries.  *n_pairs = the full count, always; pairs == NULL only counts; a count
+ * above capacity is VSC_ERR_RANGE and nothing is written.  Replaces a host loop over vsc_guides_enumerate's loci.
+ * vsc_guides_pairs: the same contract and bytes over the object's own loci, computed on the device over the array where it
+ * lies (ascending (contig, pos, '+' before '-'): per '-' candidate one bound and a walk that keeps '+'; count, scan, write as
+ * vsc_guides_enumerate, no append atomic - the bytes depend on the input only).  A host-only object
+ * (vsc_multi_guides_enumerate's) is answered by vsc_loci_pairs.  pairs: host memory.  More than 2^32 - 2048 candidates:
+ * VSC_ERR_RANGE.  The object and what vsc_ctx_timing reports stay as they are.
+ *
+ * vsc_hits_pairs: the join.  hits: any result in vsc_search order (vsc_search, vsc_search_select*, a merged multi-device
+ * result); the call runs on the hits' own context, as vsc_hits_locate.  For pair j = (a, b) a PAIRED SITE is a record of guide
+ * a and a record of guide b whose windows are PAIRED - either strand assignment.  With exclude (n_guides loci, as
+ * vsc_search_summary's; no genome is at hand, so of an entry only strand > 1 is refused) the pair's ON-TARGET - a-record at
+ * exclude[a], b-record at exclude[b] in contig, position and strand - is not counted and sets on_target = 1.  Over the
+ * counted sites of pair j, rows[j] holds
+ *   sites      their number
+ *   nm_sum[k]  sites with NM(a-record) + NM(b-record) = k
+ *   nm_max[k]  sites with max(NM(a-record), NM(b-record)) = k
+ * sites (optional, host memory, `capacity` entries): the counted sites in ascending (pair, a_rec, b_rec) - a_rec, b_rec:
+ * record indices into hits, delta as above; the sites of one pair are contiguous, prefix sums of rows[].sites are their
+ * offsets.  *n_sites (optional) = the full total.  A total above capacity when sites != NULL: VSC_ERR_RANGE, rows and *n_sites
+ * are valid (size a second call from them).  a == b, an index >= n_guides, a record whose guide is >= n_guides, n_guides >=
+ * 2^31, a NULL hits / p / rows (n_pairs > 0), a NULL pairs when n_pairs > 0: VSC_ERR_INVALID.  More than 2^32 - 1 records, or
+ * - when sites are asked for - more than 2^32 - 2048 (pair, a-record) work items: VSC_ERR_RANGE.  n_pairs == 0 or an empty
+ * result: VSC_OK, zeroed rows, nothing is launched.  A guide may be in any number of pairs; duplicate pairs get a row each.
+ * The records and what vsc_ctx_timing reports stay as they are; scratch comes from the context's pools
+ * (vsc_ctx_release_scratch gives it back).
+ * Replaces: nothing in the reference (it has no pair notion; its mergers' rows are per guide); for a caller, the copy of all
+ * records to the host and a join there.
+ */
+typedef struct {
+    int32_t delta_min, delta_max;
+    uint32_t reserved[2];
+} vsc_pair_params;
+typedef struct {
+    uint32_t a, b; /* a: the '-' window / first guide, b: the '+' window / second guide */
+} vsc_guide_pair;
+typedef struct {
+    uint64_t sites;
+    uint64_t nm_sum[17];
+    uint64_t nm_max[9];
+    uint32_t on_target;
+    uint32_t reserved;
+} vsc_pair_summary;
+typedef struct {
+    uint32_t pair, a_rec, b_rec;
+    int32_t delta;
+} vsc_pair_site;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pair_params) == 16 && sizeof(vsc_guide_pair) == 8, "vsc_pair_params / vsc_guide_pair layout");
+static_assert(sizeof(vsc_pair_summary) == 224 && sizeof(vsc_pair_site) == 16, "vsc_pair_summary / vsc_pair_site layout");
+#else
+_Static_assert(sizeof(vsc_pair_params) == 16 && sizeof(vsc_guide_pair) == 8, "vsc_pair_params / vsc_guide_pair layout");
+_Static_assert(sizeof(vsc_pair_summary) == 224 && sizeof(vsc_pair_site) == 16, "vsc_pair_summary / vsc_pair_site layout");
+#endif
+int vsc_loci_pairs(const vsc_locus *loci, uint64_t n, const vsc_pair_params *p, vsc_guide_pair *pairs, uint64_t capacity,
+                   uint64_t *n_pairs);
+int vsc_guides_pairs(vsc_guides *guides, const vsc_pair_params *p, vsc_guide_pair *pairs, uint64_t capacity, uint64_t *n_pairs);
+int vsc_hits_pairs(vsc_hits *hits, uint32_t n_guides, const vsc_guide_pair *pairs, uint32_t n_pairs, const vsc_pair_params *p,
+                   const vsc_locus *exclude /* optional, n_guides */, vsc_pair_summary *rows /* n_pairs */,
+                   vsc_pair_site *sites /* optional */, uint64_t capacity, uint64_t *n_sites /* optional */);
 /* CRISPOR's guide specificity from a mit_sum: (100 / (100 + mit_sum * 2^-24)) * 100 in that order.  The tools round
  * it with floor(x + 0.5), the round() CRISPOR used.  Host only, no device needed. */
 double vsc_mit_specificity(uint64_t mit_sum);

@@ -72,6 +72,34 @@ class EnumParams(C.Structure):
 assert C.sizeof(EnumParams) == 24
 
 
+class PairParams(C.Structure):
+    """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
+    _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class GuidePair(C.Structure):
+    """vsc_guide_pair: a = the '-' window (vsc_loci_pairs) / first guide, b = the '+' window / second guide."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
+
+
+class PairSummary(C.Structure):
+    """vsc_pair_summary (vsc_hits_pairs): the counted paired sites of one pair, by NM sum and by larger NM."""
+    _fields_ = [("sites", C.c_uint64), ("nm_sum", C.c_uint64 * 17), ("nm_max", C.c_uint64 * 9), ("on_target", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class PairSite(C.Structure):
+    """vsc_pair_site: one paired site - the pair, its two records in the result, delta = pos('+') - pos('-')."""
+    _fields_ = [("pair", C.c_uint32), ("a_rec", C.c_uint32), ("b_rec", C.c_uint32), ("delta", C.c_int32)]
+
+
+assert C.sizeof(PairParams) == 16 and C.sizeof(GuidePair) == 8 and C.sizeof(PairSummary) == 224 and C.sizeof(PairSite) == 16
+PAIR_SUMMARY_DTYPE = np.dtype([("sites", "<u8"), ("nm_sum", "<u8", (17,)), ("nm_max", "<u8", (9,)), ("on_target", "<u4"),
+                               ("reserved", "<u4")])
+PAIR_SITE_DTYPE = np.dtype([("pair", "<u4"), ("a_rec", "<u4"), ("b_rec", "<u4"), ("delta", "<i4")])
+assert PAIR_SUMMARY_DTYPE.itemsize == 224 and PAIR_SITE_DTYPE.itemsize == 16
+
+
 class RegionsStats(C.Structure):
     """vsc_regions_stats (vsc_regions_info)."""
     _fields_ = [("intervals", C.c_uint64), ("rule", C.c_uint32), ("block_bases", C.c_uint32), ("blocks_out", C.c_uint64),
@@ -209,6 +237,10 @@ SYMBOLS = [
     ("vsc_regions_locate", C.c_uint32, [_vp, C.c_uint32, C.c_uint32]),
     ("vsc_hits_locate", C.c_int, [_vp, _vp, _vp]),
     ("vsc_guides_locate", C.c_int, [_vp, _vp, _vp]),
+    ("vsc_loci_pairs", C.c_int, [_vp, C.c_uint64, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("vsc_guides_pairs", C.c_int, [_vp, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("vsc_hits_pairs", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(PairParams), _vp, _vp, _vp, C.c_uint64,
+                                 C.POINTER(C.c_uint64)]),
     ("vsc_mit_specificity", C.c_double, [C.c_uint64]),
     ("vsc_hits_count", C.c_uint64, [_vp]),
     ("vsc_hits_data_dev", _vp, [_vp]),

@@ -87,6 +87,47 @@ def _guides_arrays(handle, check_fn, label_regions=None):
         L.vsc_guides_free(handle)
 
 
+def nickase_delta(offset_min, offset_max):
+    """The delta range of a nickase offset range: offset = the gap between the two protospacers' PAM-distal ends (negative:
+    they overlap), delta = pos('+' window) - pos('-' window) = offset + 23."""
+    return int(offset_min) + READ_LEN, int(offset_max) + READ_LEN
+
+
+def _pair_params(delta):
+    """vsc_pair_params of a (delta_min, delta_max) pair; the library checks the values."""
+    lo, hi = delta
+    if not (-2 ** 31 <= int(lo) < 2 ** 31 and -2 ** 31 <= int(hi) < 2 ** 31):
+        raise ValueError("delta bounds must fit 32 signed bits")
+    p = _lib.PairParams()
+    p.delta_min, p.delta_max = int(lo), int(hi)
+    return p
+
+
+def _collect_pairs(call):
+    """call(pairs_ptr, capacity, byref(count)) -> status, run twice: count, then fill.  Returns uint32[n, 2]."""
+    n = C.c_uint64()
+    call(None, 0, C.byref(n))
+    out = np.zeros((int(n.value), 2), dtype=np.uint32)
+    if n.value:
+        call(ptr(out), int(n.value), C.byref(n))
+    return out
+
+
+def pair_loci(loci, delta):
+    """vsc_loci_pairs, on the host: every (a, b) with loci[a] a '-' window, loci[b] a '+' window on the same contig and
+    delta[0] <= pos(b) - pos(a) <= delta[1], as uint32[n, 2] in ascending (a, b).  loci: LOCUS_DTYPE or (contig, pos, strand)
+    rows, in any order; contig 0xFFFFFFFF takes part in nothing."""
+    lo = _loci(loci, len(loci))
+    p = _pair_params(delta)
+    return _collect_pairs(lambda out, cap, n: check(lib().vsc_loci_pairs(ptr(lo), len(lo), C.byref(p), out, cap, n)))
+
+
+def _guides_pairs(handle, check_fn, delta):
+    """vsc_guides_pairs of a vsc_guides (on its device; a host-only object: on the host) as uint32[n, 2]."""
+    p = _pair_params(delta)
+    return _collect_pairs(lambda out, cap, n: check_fn(lib().vsc_guides_pairs(handle, C.byref(p), out, cap, n)))
+
+
 def _loci(exclude, n):
     """(contig, pos, strand) per guide -> vsc_locus array (None stays None)."""
     if exclude is None:
@@ -618,6 +659,30 @@ class Genome:
               self.ctx._h)
         return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
 
+    def enumerate_pairs(self, delta, regions=None, **filters):
+        """enumerate_guides(regions, **filters) and the guide pairs among its candidates (vsc_guides_pairs, on the device
+        over the candidates where they lie): returns (codes, loci, pairs) - pairs uint32[n, 2], every (a, b) with candidate
+        a on '-', candidate b on '+' of the same contig and delta[0] <= pos(b) - pos(a) <= delta[1] (nickase_delta turns an
+        offset range into one), in ascending (a, b).  With labels= the labels come last."""
+        lab = _label_regions(filters.pop("labels", False), regions)
+        params = filters.pop("params", None)
+        p = params if params is not None else _enum_params(filters.pop("pam", "GG"), filters.pop("strands", "both"),
+                                                           filters.pop("gc", (0, 0)), filters.pop("max_t_run", 0),
+                                                           filters.pop("max_guides", 0))
+        if filters:
+            raise TypeError("unknown filter: %s" % ", ".join(sorted(filters)))
+        h = C.c_void_p()
+        check(lib().vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
+              self.ctx._h)
+        chk = lambda code: check(code, self.ctx._h)  # noqa: E731
+        try:
+            pairs = _guides_pairs(h, chk, delta)
+        except BaseException:
+            lib().vsc_guides_free(h)
+            raise
+        found = _guides_arrays(h, chk, lab)
+        return (found[0], found[1], pairs) + tuple(found[2:])
+
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
                **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
@@ -729,6 +794,38 @@ class Hits:
         ex = _loci(exclude, len(self.codes))
         check(lib().vsc_hits_variants(self._h, self.genome._h, vmap._h, ptr(ex), len(self.codes), ptr(labels)), self.ctx._h)
         return labels
+
+    def pairs(self, pairs, delta, n_guides=None, exclude=None, sites=False, max_sites=0):
+        """vsc_hits_pairs: for every guide pair (a, b) of `pairs` (uint32[n, 2]) the paired sites - a record of guide a and a
+        record of guide b on opposite strands of one contig with delta[0] <= pos('+') - pos('-') <= delta[1] - joined on the
+        device over the records where they lie.  Returns the rows (PAIR_SUMMARY_DTYPE[n]: sites, nm_sum, nm_max, on_target);
+        with sites=True (rows, site records PAIR_SITE_DTYPE in ascending (pair, a_rec, b_rec)).  exclude: None or one
+        (contig, pos, strand) per guide - the paired site at exclude[a], exclude[b] is the pair's on-target and is not
+        counted.  n_guides: the guides the records were searched with (default: this result's).  max_sites: 0 sizes the site
+        array from the rows (a second call); a max_sites below the total raises VarscotError -34."""
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        if n_guides is None:
+            if self.codes is None:
+                raise ValueError("a merged result does not know its guides: give n_guides")
+            n_guides = len(self.codes)
+        p = _pair_params(delta)
+        ex = _loci(exclude, int(n_guides))
+        rows = np.zeros(len(pr), dtype=_lib.PAIR_SUMMARY_DTYPE)
+        total = C.c_uint64()
+        L = lib()
+        if not sites:
+            check(L.vsc_hits_pairs(self._h, int(n_guides), ptr(pr), len(pr), C.byref(p), ptr(ex), ptr(rows), None, 0,
+                                   C.byref(total)), self.ctx._h)
+            return rows
+        cap = int(max_sites)
+        if cap == 0:  # size the sites from the rows
+            check(L.vsc_hits_pairs(self._h, int(n_guides), ptr(pr), len(pr), C.byref(p), ptr(ex), ptr(rows), None, 0,
+                                   C.byref(total)), self.ctx._h)
+            cap = int(total.value)
+        out = np.zeros(max(cap, 1), dtype=_lib.PAIR_SITE_DTYPE)
+        check(L.vsc_hits_pairs(self._h, int(n_guides), ptr(pr), len(pr), C.byref(p), ptr(ex), ptr(rows), ptr(out), cap,
+                               C.byref(total)), self.ctx._h)
+        return rows, out[:int(total.value)].copy()
 
     def copy_to(self, dst_ptr, dst_is_device):
         """Copy the records to caller memory (e.g. the data_ptr() of a uint8 tensor handed to RCCL)."""
@@ -993,6 +1090,27 @@ class MultiGenome:
         self.multi._check(lib().vsc_multi_guides_enumerate(self.multi._h, self._h, regions._h if regions is not None else None,
                                                            C.byref(p), C.byref(h)))
         return _guides_arrays(h, self.multi._check, lab)
+
+    def enumerate_pairs(self, delta, regions=None, **filters):
+        """Genome.enumerate_pairs over the shards: the joined host-only candidates are paired on the host (vsc_guides_pairs
+        hands them to vsc_loci_pairs) - the same bytes as one device gives."""
+        lab = _label_regions(filters.pop("labels", False), regions)
+        params = filters.pop("params", None)
+        p = params if params is not None else _enum_params(filters.pop("pam", "GG"), filters.pop("strands", "both"),
+                                                           filters.pop("gc", (0, 0)), filters.pop("max_t_run", 0),
+                                                           filters.pop("max_guides", 0))
+        if filters:
+            raise TypeError("unknown filter: %s" % ", ".join(sorted(filters)))
+        h = C.c_void_p()
+        self.multi._check(lib().vsc_multi_guides_enumerate(self.multi._h, self._h, regions._h if regions is not None else None,
+                                                           C.byref(p), C.byref(h)))
+        try:
+            pairs = _guides_pairs(h, self.multi._check, delta)
+        except BaseException:
+            lib().vsc_guides_free(h)
+            raise
+        found = _guides_arrays(h, self.multi._check, lab)
+        return (found[0], found[1], pairs) + tuple(found[2:])
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto", score=None,
                         forest=None, guide_activity=None):

@@ -54,6 +54,17 @@
 // guide), var* = the counted window hits that cover a variant, varDuplicates = window hits dropped as duplicates.  A sample
 // without variants gives the reference's numbers and zeros.  -v runs on one device and not with -A, -X, -T or -F.  Without -v
 // every output is what it was.
+// -J pairs.tsv with -j MIN,MAX screens GUIDE PAIRS for a paired-nickase design (Cas9 D10A, FokI-dCas9): the pairs are every
+// guide on '-' with every guide on '+' of the same sequence whose offset - the gap between the two protospacers' PAM-distal
+// ends, negative when they overlap; PAM-out pairs only need MIN > -23 - lies in MIN .. MAX (with -E found on the device among
+// the candidates, vsc_guides_pairs; with -B among the on-targets, vsc_loci_pairs; -R has no loci: a usage error).  One more
+// search keeps the guides' records on the device and joins them there (vsc_hits_pairs): a pair's off-target is a locus where a
+// hit of one guide and a hit of the other lie on opposite strands within the same offset range - the pair's own locus left out
+// and reported as onTarget.  One line per pair, in ascending (guideA, guideB) input order, under
+//   #pairId guideA guideB offset sites onTarget minNmSum ps0 .. ps<2M>
+// pairId = guideA|guideB, guideA the '-' guide, sites = the paired off-target sites, minNmSum = the smallest sum of the two
+// hits' mismatches among them (- if none), ps<k> = sites with that sum.  -J does not combine with -v.  Without -J every other
+// output is what it was; the -T listing gains nothing.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -103,6 +114,9 @@ int main(int argc, char **argv)
         {'v', "vcf", "Path to a VCF (.vcf): adds the columns of the guides in that individual's genome, ind* and var* "
                      "(one device; not with -A, -X, -T, -F)", false},
         {'n', "sample", "With -v: 0-based sample column of the VCF (default 0)", false},
+        {'j', "pair-offset", "MIN,MAX: the nickase offset range of the guide pairs of -J (gap between the protospacers' PAM-distal ends, "
+                             "negative: overlap; e.g. -4,20); required with -J", false},
+        {'J', "pairs", "Path to the TSV file of the guide pairs and their paired off-target sites (.tsv/.txt); needs -j and -E or -B", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -330,6 +344,40 @@ int main(int argc, char **argv)
         vcf_sample = (uint32_t)k;
     }
 
+    // -j / -J: the guide pairs
+    const bool pairing = opts[29].set;
+    const std::string pairs_path = opts[29].value;
+    vsc_pair_params pp{};
+    if (pairing != opts[28].set) {
+        std::fprintf(stderr, "%s: the pair screen needs both -J (the pairs' file) and -j MIN,MAX (the offset range)\n", argv[0]);
+        return 1;
+    }
+    if (pairing) {
+        const std::string &v = opts[28].value;
+        char *e1 = nullptr, *e2 = nullptr;
+        const long lo = std::strtol(v.c_str(), &e1, 10);
+        const long hi = (e1 != v.c_str() && *e1 == ',') ? std::strtol(e1 + 1, &e2, 10) : 0;
+        const long lim = (1l << 30) - VSC_READ_LEN;
+        if (e1 == v.c_str() || *e1 != ',' || e2 == e1 + 1 || *e2 || lo > hi || lo < -lim || hi > lim) {
+            std::fprintf(stderr, "%s: -j takes MIN,MAX with MIN <= MAX, e.g. -4,20, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        pp.delta_min = (int32_t)lo + VSC_READ_LEN;  // delta = pos('+') - pos('-') = offset + 23
+        pp.delta_max = (int32_t)hi + VSC_READ_LEN;
+        if (!has_extension(pairs_path, {"tsv", "txt"})) {
+            std::fprintf(stderr, "%s: the -J file must be a .tsv/.txt file\n", argv[0]);
+            return 1;
+        }
+        if (opts[2].set) {
+            std::fprintf(stderr, "%s: -J pairs guides by their loci, which -R reads do not have: give the guides with -E or -B\n", argv[0]);
+            return 1;
+        }
+        if (individual) {
+            std::fprintf(stderr, "%s: -J does not combine with -v\n", argv[0]);
+            return 1;
+        }
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_genome *genome = nullptr;
     vsc_genome *win_genome = nullptr;
@@ -337,7 +385,7 @@ int main(int argc, char **argv)
     vsc_variant_map *vmap = nullptr;
     vsc_multi *multi = nullptr;
     vsc_multi_genome *mgenome = nullptr;
-    vsc_hits *hits = nullptr;
+    vsc_hits *hits = nullptr, *pair_hits = nullptr;
     vsc_regions *regions = nullptr, *targets = nullptr;
     vsc_guides *found = nullptr;
     int rc = 1;
@@ -707,12 +755,53 @@ int main(int argc, char **argv)
             out.close();
             if (!out) throw std::runtime_error("Could not write the -T file.");
         }
+        if (pairing) {
+            // the pairs among the guides' loci, then one search that keeps the records and the join over them on the device
+            uint64_t n_found = 0;
+            std::vector<vsc_guide_pair> pairs;
+            for (int pass = 0; pass < 2; ++pass) {  // count, then fill
+                st = discover ? vsc_guides_pairs(found, &pp, pass ? pairs.data() : nullptr, pairs.size(), &n_found)
+                              : vsc_loci_pairs(loci.data(), loci.size(), &pp, pass ? pairs.data() : nullptr, pairs.size(), &n_found);
+                if (st != VSC_OK) throw std::runtime_error(discover && !multi ? vsc_last_error(ctx) : "could not pair the guides");
+                if (n_found > 0xFFFFFFFFull) throw std::runtime_error("-J: too many guide pairs for one join; narrow -j or the targets");
+                pairs.resize(n_found);
+            }
+            std::fprintf(stderr, "Guide pairs found (total: %zu).\n", pairs.size());
+            std::vector<vsc_pair_summary> prow(pairs.size());
+            if (!pairs.empty()) {
+                st = multi ? vsc_multi_search(multi, mgenome, codes.data(), n_codes, &p, &pair_hits) : vsc_search(ctx, genome, codes.data(), n_codes, &p, &pair_hits);
+                if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+                st = vsc_hits_pairs(pair_hits, n_codes, pairs.data(), (uint32_t)pairs.size(), &pp, ex, prow.data(), nullptr, 0, nullptr);
+                if (st != VSC_OK) throw std::runtime_error(vsc_last_error(multi ? vsc_multi_result_ctx(multi) : ctx));
+            }
+            std::string list = "#pairId\tguideA\tguideB\toffset\tsites\tonTarget\tminNmSum";
+            for (long k = 0; k <= 2 * mm; ++k) list += "\tps" + std::to_string(k);
+            list += '\n';
+            for (size_t j = 0; j < pairs.size(); ++j) {
+                const vsc_guide_pair &q = pairs[j];
+                const vsc_pair_summary &r = prow[j];
+                int min_sum = -1;
+                for (int k = 16; k >= 0; --k)
+                    if (r.nm_sum[k]) min_sum = k;
+                const long long offset = (long long)loci[q.b].pos - (long long)loci[q.a].pos - VSC_READ_LEN;
+                list += ids[q.a] + '|' + ids[q.b] + '\t' + ids[q.a] + '\t' + ids[q.b] + '\t' + std::to_string(offset) + '\t' +
+                        std::to_string(r.sites) + '\t' + std::to_string(r.on_target) + '\t' + (min_sum < 0 ? "-" : std::to_string(min_sum));
+                for (long k = 0; k <= 2 * mm; ++k) list += '\t' + std::to_string(r.nm_sum[k]);
+                list += '\n';
+            }
+            std::ofstream out(pairs_path);
+            if (!out.is_open()) throw std::runtime_error("Could not open the -J path.");
+            out << list;
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the -J file.");
+        }
         rc = 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "ERROR: %s\n", e.what());
         rc = 1;
     }
     if (hits) vsc_hits_free(hits);
+    if (pair_hits) vsc_hits_free(pair_hits);
     vsc_guides_free(found);
     vsc_regions_free(regions);
     vsc_regions_free(targets);

@@ -1,7 +1,7 @@
 // vsc_api.cpp - the C ABI of include/varscot_hip.h: context, resident genome, search orchestration
 // (find -> summary / selection -> bin sort, one pass loop: run_search) and per-hit scoring.  Host C++ only; all device
 // work is in the kernel files - vsc_kernels.hip (scan, summary, selection, scoring, forest, merge), vsc_seed.hip (seed
-// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels).  No CPU implementation of the search exists in this library: without a HIP
+// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites).  No CPU implementation of the search exists in this library: without a HIP
 // device every compute entry point fails with VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
 #include <atomic>
@@ -18,6 +18,7 @@
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
+#include "vsc_pairs.h"
 #include "vsc_varmap.h"
 
 using namespace vsc;
@@ -219,7 +220,8 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->sort_over, &ctx->seed_off,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
-                         &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels})
+                         &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
+                         &ctx->pairs_out})
         b->release();
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
@@ -2577,6 +2579,227 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
     return guarded(guides->ctx, [&]() -> int {
     return locate_records(guides->ctx, regions, (const char *)guides->storage.p + guides->loci_at, guides->n, false, labels,
                           "vsc_guides_locate");
+    });
+}
+
+}  // extern "C"
+
+// ---- paired-nickase screen -------------------------------------------------------------------------------------
+namespace {
+
+int pair_params_check(const vsc_pair_params *p)
+{
+    if (!p || p->reserved[0] || p->reserved[1] || !pair_params_ok(p->delta_min, p->delta_max)) return VSC_ERR_INVALID;
+    return VSC_OK;
+}
+
+// The pairs of a candidate array on ctx's device (vsc_guides_pairs): count per '-' candidate, exclusive scan, one 8-byte
+// read-back (the total, checked against the capacity), write pass, one copy to the host.
+int guides_pairs_device(vsc_guides *g, const vsc_pair_params *p, vsc_guide_pair *pairs, uint64_t capacity, uint64_t *n_pairs)
+{
+    vsc_ctx *ctx = g->ctx;
+    ctx->err.clear();
+    if (g->n > 0xFFFFFFFFull - 2048) return fail(ctx, VSC_ERR_RANGE, "vsc_guides_pairs: more candidates than the 32-bit item space holds");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t n = (uint32_t)g->n;
+    const size_t count_bytes = ((size_t)n * sizeof(uint32_t) + 255) / 256 * 256;
+    VSC_HIP(ctx, ctx->pairs_items.ensure(count_bytes + ((size_t)n + 1) * sizeof(unsigned long long)));
+    PairLociArgs a{};
+    a.loci = (const uint4 *)((const char *)g->storage.p + g->loci_at);
+    a.n = n;
+    a.delta_min = p->delta_min;
+    a.delta_max = p->delta_max;
+    a.item_count = (uint32_t *)ctx->pairs_items.p;
+    unsigned long long *d_off = (unsigned long long *)((char *)ctx->pairs_items.p + count_bytes);
+    a.item_off = d_off;
+    VSC_HIP(ctx, launch_pair_loci(a, false, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, launch_enum_scan(a.item_count, n, d_off, ctx->stream));
+    unsigned long long total = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_pairs = total;
+    if (!pairs || total == 0) return VSC_OK;
+    if (total > capacity) return fail(ctx, VSC_ERR_RANGE, "vsc_guides_pairs: more pairs than the capacity");
+    VSC_HIP(ctx, ctx->pairs_out.ensure((size_t)total * sizeof(vsc_guide_pair)));
+    a.pairs = (uint2 *)ctx->pairs_out.p;
+    VSC_HIP(ctx, launch_pair_loci(a, true, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(pairs, a.pairs, (size_t)total * sizeof(vsc_guide_pair), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VSC_OK;
+}
+
+// The join of vsc_hits_pairs; the arguments are checked, rows[] zeroed and *total = 0 already.
+int hits_pairs_device(vsc_hits *hits, uint32_t n_guides, const vsc_guide_pair *pairs, uint32_t n_pairs, const vsc_pair_params *p,
+                      const vsc_locus *exclude, vsc_pair_summary *rows, vsc_pair_site *sites, uint64_t capacity, uint64_t *total)
+{
+    vsc_ctx *ctx = hits->ctx;
+    const char *const who = "vsc_hits_pairs";
+    HostTimer lap;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t n = (uint32_t)hits->n;
+    vsc_hit last{};  // the records ascend by guide: the last one holds the largest
+    VSC_HIP(ctx, hipMemcpyAsync(&last, hits->d_records + (n - 1), sizeof last, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (last.guide >= n_guides) return fail_in(ctx, VSC_ERR_INVALID, who, "a record's guide is not below n_guides");
+
+    // tables, 256-byte aligned parts: [segment starts][pairs][item offsets of the pairs][excluded loci][rows]
+    auto round = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t n_seg = 2 * (size_t)n_guides + 1;
+    const size_t pairs_at = round(n_seg * sizeof(uint32_t));
+    const size_t off_at = pairs_at + round((size_t)n_pairs * sizeof(vsc_guide_pair));
+    const size_t excl_at = off_at + round(((size_t)n_pairs + 1) * sizeof(unsigned long long));
+    const size_t rows_at = excl_at + round(exclude ? (size_t)n_guides * sizeof(vsc_locus) : 0);
+    const size_t row_bytes = (size_t)n_pairs * sizeof(vsc_pair_summary);
+    VSC_HIP(ctx, ctx->pairs_tabs.ensure(rows_at + row_bytes));
+    char *base = (char *)ctx->pairs_tabs.p;
+
+    PairSegArgs sa{};
+    sa.records = (const uint4 *)hits->d_records;
+    sa.n = n;
+    sa.n_guides = n_guides;
+    sa.seg = (uint32_t *)base;
+    VSC_HIP(ctx, launch_pair_segments(sa, ctx->stream));
+    std::vector<uint32_t> seg(n_seg);
+    VSC_HIP(ctx, hipMemcpyAsync(seg.data(), sa.seg, n_seg * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    lap.lap("pairs: segment table");
+    // the work items: (pair j, record of guide a_j), flattened by the prefix sum of the record counts
+    std::vector<unsigned long long> pair_off((size_t)n_pairs + 1);
+    unsigned long long n_items = 0;
+    for (uint32_t j = 0; j < n_pairs; ++j) {
+        pair_off[j] = n_items;
+        n_items += seg[2 * (size_t)pairs[j].a + 2] - seg[2 * (size_t)pairs[j].a];
+    }
+    pair_off[n_pairs] = n_items;
+    if (n_items == 0) return VSC_OK;
+    if (sites && n_items > 0xFFFFFFFFull - 2048)
+        return fail_in(ctx, VSC_ERR_RANGE, who, "more (pair, record) work items than the site pass can number (fewer pairs per call)");
+
+    PairJoinArgs a{};
+    a.records = sa.records;
+    a.seg = sa.seg;
+    a.pairs = (const uint2 *)(base + pairs_at);
+    a.pair_off = (const unsigned long long *)(base + off_at);
+    a.n_pairs = n_pairs;
+    a.n_items = n_items;
+    a.delta_min = p->delta_min;
+    a.delta_max = p->delta_max;
+    a.rows = (unsigned long long *)(base + rows_at);
+    VSC_HIP(ctx, hipMemcpyAsync(base + pairs_at, pairs, (size_t)n_pairs * sizeof(vsc_guide_pair), hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(base + off_at, pair_off.data(), pair_off.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+    if (exclude) {
+        VSC_HIP(ctx, hipMemcpyAsync(base + excl_at, exclude, (size_t)n_guides * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.exclude = (const uint4 *)(base + excl_at);
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.rows, 0, row_bytes, ctx->stream));
+    unsigned long long *d_off = nullptr;
+    if (sites) {
+        const size_t count_bytes = round((size_t)n_items * sizeof(uint32_t));
+        VSC_HIP(ctx, ctx->pairs_items.ensure(count_bytes + ((size_t)n_items + 1) * sizeof(unsigned long long)));
+        a.item_count = (uint32_t *)ctx->pairs_items.p;
+        d_off = (unsigned long long *)((char *)ctx->pairs_items.p + count_bytes);
+        a.item_off = d_off;
+    }
+    VSC_HIP(ctx, launch_pair_join(a, false, ctx->n_cus, ctx->stream));
+    if (sites) VSC_HIP(ctx, launch_enum_scan(a.item_count, (uint32_t)n_items, d_off, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(rows, a.rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: pair_off above is this call's vector)
+    lap.lap("pairs: count pass, rows");
+    for (uint32_t j = 0; j < n_pairs; ++j) *total += rows[j].sites;
+    if (!sites || *total == 0) return VSC_OK;
+    if (*total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more paired sites than the capacity (the rows are valid)");
+    VSC_HIP(ctx, ctx->pairs_out.ensure((size_t)*total * sizeof(vsc_pair_site)));
+    a.sites = (uint4 *)ctx->pairs_out.p;
+    VSC_HIP(ctx, launch_pair_join(a, true, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(sites, a.sites, (size_t)*total * sizeof(vsc_pair_site), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    lap.lap("pairs: write pass, sites");
+    return VSC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_loci_pairs(const vsc_locus *loci, uint64_t n, const vsc_pair_params *p, vsc_guide_pair *pairs, uint64_t capacity,
+                   uint64_t *n_pairs)
+{
+    if (!n_pairs) return VSC_ERR_INVALID;
+    *n_pairs = 0;
+    if (pair_params_check(p) != VSC_OK || (n && !loci)) return VSC_ERR_INVALID;
+    if (n > 0xFFFFFFFFull) return VSC_ERR_RANGE;  // (a and b are 32-bit indices)
+    return guarded(nullptr, [&]() -> int {
+    // the entries that take part, by (contig, pos, strand, index): the order vsc_guides_enumerate gives, the index in word 3
+    std::vector<uint4> s;
+    s.reserve(n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (loci[i].contig != kPairNoContig && loci[i].strand <= 1) s.push_back(make_uint4(loci[i].contig, loci[i].pos, loci[i].strand, (uint32_t)i));
+    std::sort(s.begin(), s.end(), [](const uint4 &x, const uint4 &y) {
+        return x.x != y.x ? x.x < y.x : x.y != y.y ? x.y < y.y : x.z != y.z ? x.z < y.z : x.w < y.w;
+    });
+    const uint32_t m = (uint32_t)s.size();
+    // pair_loci_kernel's walk per '-' entry: first to count, then - when the pairs fit - to write
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < m; ++i) {
+            uint32_t lo, hi;
+            if (s[i].z != 1u || !pair_range(s[i].y, 1u, p->delta_min, p->delta_max, &lo, &hi)) continue;
+            for (uint32_t k = pair_lower_bound<false>(s.data(), 0u, m, s[i].x, lo); k < m && !pair_after<false>(s[k], s[i].x, hi); ++k) {
+                if (s[k].z != 0u) continue;
+                if (pass) pairs[at] = vsc_guide_pair{s[i].w, s[k].w};
+                ++at;
+            }
+        }
+        if (pass == 0) {
+            *n_pairs = at;
+            if (!pairs || at == 0) return VSC_OK;
+            if (at > capacity) return VSC_ERR_RANGE;
+        }
+    }
+    std::sort(pairs, pairs + *n_pairs, [](const vsc_guide_pair &x, const vsc_guide_pair &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+    return VSC_OK;
+    });
+}
+
+int vsc_guides_pairs(vsc_guides *guides, const vsc_pair_params *p, vsc_guide_pair *pairs, uint64_t capacity, uint64_t *n_pairs)
+{
+    if (!guides || !n_pairs) return VSC_ERR_INVALID;
+    *n_pairs = 0;
+    if (pair_params_check(p) != VSC_OK) {
+        if (guides->ctx) (void)fail(guides->ctx, VSC_ERR_INVALID, "vsc_guides_pairs: delta_min <= delta_max within +-2^30 and zeroed reserved fields are needed");
+        return VSC_ERR_INVALID;
+    }
+    if (guides->n == 0) return VSC_OK;
+    if (!guides->ctx)  // vsc_multi_guides_enumerate's host-only object: the same pairs by the host's walk
+        return vsc_loci_pairs(guides->loci.data(), guides->n, p, pairs, capacity, n_pairs);
+    return guarded(guides->ctx, [&]() -> int { return guides_pairs_device(guides, p, pairs, capacity, n_pairs); });
+}
+
+int vsc_hits_pairs(vsc_hits *hits, uint32_t n_guides, const vsc_guide_pair *pairs, uint32_t n_pairs, const vsc_pair_params *p,
+                   const vsc_locus *exclude, vsc_pair_summary *rows, vsc_pair_site *sites, uint64_t capacity, uint64_t *n_sites)
+{
+    if (n_sites) *n_sites = 0;
+    if (!hits) return VSC_ERR_INVALID;
+    vsc_ctx *ctx = hits->ctx;
+    const char *const who = "vsc_hits_pairs";
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    if (!p || (n_pairs && (!pairs || !rows))) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (pair_params_check(p) != VSC_OK)
+        return fail_in(ctx, VSC_ERR_INVALID, who, "delta_min <= delta_max within +-2^30 and zeroed reserved fields are needed");
+    if (n_guides > 0x7FFFFFFFu) return fail_in(ctx, VSC_ERR_INVALID, who, "n_guides must be below 2^31");
+    for (uint32_t j = 0; j < n_pairs; ++j)
+        if (pairs[j].a == pairs[j].b || pairs[j].a >= n_guides || pairs[j].b >= n_guides)
+            return fail_in(ctx, VSC_ERR_INVALID, who, "a pair needs two different guides below n_guides");
+    for (uint32_t i = 0; exclude && i < n_guides; ++i)
+        if (exclude[i].contig != UINT32_MAX && exclude[i].strand > 1) return fail_in(ctx, VSC_ERR_INVALID, who, "excluded locus with a strand above 1");
+    if (hits->n > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^32 - 1 records");
+    if (n_pairs) std::memset(rows, 0, (size_t)n_pairs * sizeof(vsc_pair_summary));
+    if (n_pairs == 0 || hits->n == 0) return VSC_OK;
+    uint64_t total = 0;
+    const int rc = hits_pairs_device(hits, n_guides, pairs, n_pairs, p, exclude, rows, sites, capacity, &total);
+    if (n_sites) *n_sites = total;
+    return rc;
     });
 }
 

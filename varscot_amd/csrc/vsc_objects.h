@@ -123,6 +123,9 @@ struct vsc_ctx {
     uint64_t varmap_serial = 0;  // 0: none resident
     // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan
     vsc::DeviceBuf enum_tabs;
+    // vsc_hits_pairs / vsc_guides_pairs: the call's tables (segment starts, pairs, their item offsets, excluded loci, rows),
+    // the per-item counts with their exclusive scan, and the sites / pairs on their way to the host
+    vsc::DeviceBuf pairs_tabs, pairs_items, pairs_out;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
