@@ -34,7 +34,8 @@ typedef struct {
     int32_t seed_tight;          /* -1 default: segment thresholds follow what the site's PAM leaves of the limit, the cut chosen by the
                                     cost model; 0: floor(m / 3) in all three; 1 + k0 + 3 k1: segments 0 / 1 within k0 / k1 substitutions (if that is a valid cut) */
     int32_t rf_form;             /* -1 default (the best node form the forest allows); 0: plain nodes; 1: at most the compact form; 2 = -1 */
-    uint32_t reserved[1];
+    uint32_t seed_parts;         /* seed search whose records go straight to the sort: launches the chunk range is cut into, the level-1
+                                    partition of each running beside the next; 0: the library's choice, 1: one launch, n: n parts */
 } vsc_debug_params;
 
 /* Replaces the context's hooks (NULL: back to the defaults). */

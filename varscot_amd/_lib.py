@@ -174,7 +174,7 @@ class DebugParams(C.Structure):
                 ("sort_optimistic", C.c_int32), ("sort_slot_cap", C.c_uint32), ("score_chunk", C.c_uint64),
                 ("score_slices", C.c_int32), ("score_slice_shift", C.c_uint32), ("seed_shared", C.c_int32),
                 ("seed_group_out", C.c_int32), ("seed_tight", C.c_int32), ("rf_form", C.c_int32),
-                ("reserved", C.c_uint32 * 1)]
+                ("seed_parts", C.c_uint32)]
     SIGNED_DEFAULT = ("sort_xcd", "sort_optimistic", "score_slices", "seed_shared", "seed_group_out", "seed_tight", "rf_form")
 
     @classmethod

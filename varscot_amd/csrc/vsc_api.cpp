@@ -200,6 +200,7 @@ int vsc_ctx_create_masked(int device_id, const uint32_t *cu_mask, uint32_t n_mas
         return VSC_ERR_DEVICE;
     }
     ctx->own_stream = true;
+    ctx->cu_masked = cu_mask && n_mask_words;
     ctx->n_cus = prop.multiProcessorCount;
     for (auto &e : ctx->ev)
         if (hipEventCreate(&e) != hipSuccess) {
@@ -217,7 +218,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (DeviceBuf *b : {&ctx->counters, &ctx->guides, &ctx->score_guides, &ctx->keys_a, &ctx->keys_b, &ctx->vals_a, &ctx->vals_b, &ctx->votes_rows,
                          &ctx->score_mit, &ctx->score_flags, &ctx->score_feat, &ctx->score_sched, &ctx->sort_segs, &ctx->sort_tabs,
-                         &ctx->sort_over, &ctx->seed_off,
+                         &ctx->sort_over, &ctx->seed_off, &ctx->seed_fill,
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
@@ -240,6 +241,10 @@ int vsc_ctx_destroy(vsc_ctx *ctx)
     (void)vsc_ctx_release_scratch(ctx);
     for (auto &e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto &e : ctx->part_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->stream_b) (void)hipStreamDestroy(ctx->stream_b);
+    if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return VSC_OK;
@@ -589,7 +594,7 @@ hipError_t build_index(vsc_ctx *ctx, vsc_genome *g, const vsc_search_params *par
         tile0.assign(kBins1 + 1, 0);
         uint64_t at = 0, t2 = 0;
         for (uint32_t i = 0; i < kBins1; ++i) {
-            segs[i] = SortSeg{at, at, 0, h1[i], 0};
+            segs[i] = SortSeg{at, at, 0, h1[i], 0, i, 0};
             tile0[i] = (uint32_t)t2;
             t2 += (h1[i] + kSortTile - 1) / kSortTile;
             at += h1[i];
@@ -982,6 +987,53 @@ struct SortRows {
     uint64_t rows_first = 0;
 };
 
+// Level 1 of a seed search whose records go straight to the sort (find_pass): the block fill table that says which slots
+// of the search's buffer hold records, how many they are, and - a search in parts - the slot partition that has already run,
+// part by part, beside the search: bin_sort then starts at the bin starts.
+struct SortLevel1 {
+    const uint32_t *fill = nullptr;  // SeedArgs.fill (null: unused slots hold sentinels)
+    unsigned fill_shift = 0;
+    uint64_t n_real = 0;             // records among the segments' slots
+    bool done = false;               // the partition has run (slot mode, over one segment per part and region)
+    unsigned bits = 0;               // ... on this many key bits, into slots of slot_cap records; segment i is region i
+    uint64_t slot_cap = 0;
+};
+
+// The first partition level's key bits for segments of at most n_max records (0: the finalize kernel takes them as they are)
+unsigned level_bits(uint64_t n_max, uint64_t sort_cap, unsigned max_bits, unsigned rem, size_t n_segs)
+{
+    if (n_max <= sort_cap || rem == 0) return 0;
+    const uint64_t want = std::max<uint64_t>(1, sort_cap * 7 / 10);  // average bin: 70 % of what the finalize kernel holds
+    unsigned bits = std::min<unsigned>({std::max(1u, ceil_log2((n_max + want - 1) / want)), max_bits, rem});
+    while (bits > 1 && ((uint64_t)n_segs << bits) > (1ull << 22)) --bits;  // bounded bin tables
+    return bits;
+}
+
+// the hooks' say on the sort's constants (varscot_hip_debug.h)
+void sort_limits(const vsc_debug_params &dbg, uint64_t *sort_cap, unsigned *max_bits, uint64_t *slot_cap)
+{
+    *sort_cap = kSortCap;
+    *max_bits = kSortMaxBinBits;
+    if (dbg.sort_cap) *sort_cap = std::min<uint64_t>(kSortCap, std::max<uint32_t>(16, dbg.sort_cap));
+    if (dbg.sort_max_bits) *max_bits = std::min<unsigned>(kSortMaxBinBits, std::max<uint32_t>(1, dbg.sort_max_bits));
+    // a slot holds a quarter more than the finalize kernel orders in LDS: bins between the two go to another level
+    // from their slot, bins beyond make the level fall back
+    *slot_cap = dbg.sort_slot_cap ? dbg.sort_slot_cap : (*sort_cap + *sort_cap / 4 + 15) / 16 * 16;
+    *slot_cap = std::max<uint64_t>(*slot_cap, 16);
+}
+
+// does the slot layout of a level (n_bins slots of slot_cap records for n_all records) fit the device beside everything else?
+bool slots_fit(uint64_t n_bins, uint64_t slot_cap, uint64_t n_all, size_t other_cap, size_t side_cap, bool side)
+{
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const uint64_t room = (uint64_t)free_b + other_cap;  // (the buffer's present allocation is given back first)
+    const uint64_t slot_records = n_bins * slot_cap;
+    // (a search that keeps the sites' bases has a side word beside every slot)
+    const uint64_t slot_bytes = slot_records * (sizeof(uint64_t) + (side ? sizeof(uint32_t) : 0));
+    return !(slot_records > 4 * n_all + (1ull << 20) || slot_bytes + (1ull << 30) > room + side_cap);
+}
+
 struct SortInfo {
     unsigned levels = 0;     // partition levels run (0: every region fitted the finalize kernel as it was)
     unsigned bin_bits = 0;   // key bits of the first partition level
@@ -1001,7 +1053,7 @@ struct SortInfo {
 // with the histogram and clears *slots, so that later searches of this genome and budget go the exact way at once.
 hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg> segs, uint64_t *src, uint64_t *other,
                     unsigned key_bits, unsigned pos_pad, uint32_t pos_base, vsc_hit *out, hipEvent_t ev_sorted, SortInfo *info,
-                    DeviceBuf *other_buf = nullptr, bool *slots = nullptr, const SortRows *rows = nullptr)
+                    DeviceBuf *other_buf = nullptr, bool *slots = nullptr, const SortRows *rows = nullptr, const SortLevel1 *l1 = nullptr)
 {
     uint32_t *side_src = rows ? rows->side_src : nullptr, *side_other = nullptr;
     // (key_bits counts the meaningful bits: the pos_pad zero bits at the bottom of every position field are not among them)
@@ -1011,14 +1063,9 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
     // test hooks (varscot_hip_debug.h): a smaller bin capacity / fewer bits per level make the partition levels
     // and the oversize path run on inputs of a few thousand records
     const vsc_debug_params &dbg = ctx->dbg;
-    uint64_t sort_cap = kSortCap;
-    unsigned max_bits = kSortMaxBinBits;
-    if (dbg.sort_cap) sort_cap = std::min<uint64_t>(kSortCap, std::max<uint32_t>(16, dbg.sort_cap));
-    if (dbg.sort_max_bits) max_bits = std::min<unsigned>(kSortMaxBinBits, std::max<uint32_t>(1, dbg.sort_max_bits));
-    // a slot holds a quarter more than the finalize kernel orders in LDS: bins between the two go to another level
-    // from their slot, bins beyond make the level fall back
-    uint64_t slot_cap = dbg.sort_slot_cap ? dbg.sort_slot_cap : (sort_cap + sort_cap / 4 + 15) / 16 * 16;
-    slot_cap = std::max<uint64_t>(slot_cap, 16);
+    uint64_t sort_cap, slot_cap;
+    unsigned max_bits;
+    sort_limits(dbg, &sort_cap, &max_bits, &slot_cap);
     for (unsigned level = 1; !segs.empty(); ++level) {
         if (level > 48) return hipErrorUnknown;  // cannot happen: every level consumes key bits, keys are unique
         uint64_t n_max = 0, n_all = 0;
@@ -1026,33 +1073,29 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
             n_max = std::max<uint64_t>(n_max, s.n_in);
             n_all += s.n_in;
         }
-        unsigned bits = 0;
-        if (n_max > sort_cap) {
-            if (rem == 0) return hipErrorUnknown;
-            const uint64_t want = std::max<uint64_t>(1, sort_cap * 7 / 10);  // average bin: 70 % of what the finalize kernel holds
-            bits = std::min<unsigned>({std::max(1u, ceil_log2((n_max + want - 1) / want)), max_bits, rem});
-            while (bits > 1 && ((uint64_t)segs.size() << bits) > (1ull << 22)) --bits;  // bounded bin tables
-        }
+        if (n_max > sort_cap && rem == 0) return hipErrorUnknown;
+        // (level 1 of a search in parts: the partition has run - on the bits chosen before the search, into the slots made then)
+        bool parted = level == 1 && l1 && l1->done;
+        const uint32_t *const fill = level == 1 && l1 ? l1->fill : nullptr;
+        const uint64_t n_moved = fill ? l1->n_real : n_all;  // records the level's kernels move (the fill table leaves the rest out)
+        const unsigned bits = parted ? l1->bits : level_bits(n_max, sort_cap, max_bits, rem, segs.size());
+        if (parted) slot_cap = l1->slot_cap;
         const size_t n_segs = segs.size();
         const size_t n_bins = n_segs << bits;
-        bool use_slots = level == 1 && bits && slots && other_buf && (dbg.sort_optimistic == 1 || (dbg.sort_optimistic != 0 && *slots));
-        if (level == 1 && bits && other_buf) {
+        for (size_t i = 0; i < n_segs; ++i) segs[i].region = (uint32_t)i;
+        bool use_slots = parted || (level == 1 && bits && slots && other_buf && (dbg.sort_optimistic == 1 || (dbg.sort_optimistic != 0 && *slots)));
+        if (parted) {
+            other = (uint64_t *)other_buf->p;
+        } else if (level == 1 && bits && other_buf) {
             // the level's destination is sized here, once, for the layout that will be used: fixed slots (n_bins x slot
             // capacity: 1.8 - 3.6 x the records with average bins at 70 % of the finalize kernel's capacity) when they are
             // allowed and fit the device beside everything else, the compact layout otherwise
             uint64_t span = 1;
             for (const SortSeg &sg : segs) span = std::max<uint64_t>(span, sg.out_off + sg.n_in);
             const uint64_t slot_records = (uint64_t)n_bins * slot_cap;
-            if (use_slots && dbg.sort_optimistic != 1) {
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-                const uint64_t room = (uint64_t)free_b + other_buf->cap;  // (the buffer's present allocation is given back first)
-                // (a search that keeps the sites' bases has a side word beside every slot)
-                const uint64_t slot_bytes = slot_records * (sizeof(uint64_t) + (rows ? sizeof(uint32_t) : 0));
-                if (slot_records > 4 * n_all + (1ull << 20) || slot_bytes + (1ull << 30) > room + (rows ? rows->side_other->cap : 0)) {
-                    use_slots = false;
-                    *slots = false;  // remembered per genome and budget: later searches do not ask again
-                }
+            if (use_slots && dbg.sort_optimistic != 1 && !slots_fit(n_bins, slot_cap, n_all, other_buf->cap, rows ? rows->side_other->cap : 0, rows != nullptr)) {
+                use_slots = false;
+                *slots = false;  // remembered per genome and budget: later searches do not ask again
             }
             // (never less than the compact layout: a slot partition that overflows runs again the exact way, into the same buffer)
             hipError_t ge = other_buf->ensure((size_t)(use_slots ? std::max(slot_records, span) : span) * sizeof(uint64_t));
@@ -1094,7 +1137,8 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
                 std::fprintf(stderr, "[vsc sort] level %u: %zu segments, %llu records, largest %llu, %u bits (of %u left), cap %llu%s\n", level,
                              n_segs, (unsigned long long)n_all, (unsigned long long)n_max, bits, rem, (unsigned long long)sort_cap,
                              use_slots ? ", slot mode" : "");
-            VSC_TRY(hipMemsetAsync(d_n_over, 0, 3 * sizeof(uint32_t), st));
+            // (parted: word 2, the partition's overflow flag, was cleared before the first part and may be raised by now)
+            VSC_TRY(hipMemsetAsync(d_n_over, 0, (parted ? 2 : 3) * sizeof(uint32_t), st));
             FinArgs f{};
             f.segs = d_segs;
             f.n_segs = (uint32_t)n_segs;
@@ -1121,20 +1165,24 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
                 a.bin_start = a.cursor + n_bins;
                 a.bin_bits = bits;
                 a.bin_shift = kRecPosShift + pos_pad + rem - bits;
+                a.fill = fill;
+                a.fill_shift = fill ? l1->fill_shift : 0;
                 if (dbg.sort_xcd != 0 && tiles >= 64) a.xcd_tiles = (uint32_t)((tiles + 7) / 8);
                 if (use_slots) {
                     // partition first (cursors from zero), then the bin starts of the RESULT from the cursors
                     a.hist = a.cursor;
                     a.slot_cap = (uint32_t)slot_cap;
                     a.overflow = d_n_over + 2;
-                    VSC_TRY(hipMemsetAsync(a.cursor, 0, n_bins * sizeof(uint32_t), st));
-                    VSC_TRY(launch_bin_partition(a, st));
+                    if (!parted) {
+                        VSC_TRY(hipMemsetAsync(a.cursor, 0, n_bins * sizeof(uint32_t), st));
+                        VSC_TRY(launch_bin_partition(a, st));
+                    }
                     VSC_TRY(launch_bin_scan(a, st));
                 } else {
                     VSC_TRY(hipMemsetAsync(a.hist, 0, n_bins * sizeof(uint32_t), st));
                     VSC_TRY(launch_bin_hist(a, st));
                     VSC_TRY(launch_bin_scan(a, st));
-                    if (dbg.sort_debug >= 2) {
+                    if (dbg.sort_debug >= 2 && !fill) {
                         // recount every bin on the host and compare with the device histogram
                         std::vector<uint32_t> h(n_bins);
                         VSC_TRY(hipMemcpyAsync(h.data(), a.hist, n_bins * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -1162,6 +1210,9 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
                 f.bin_bits = bits;
                 f.slot_cap = a.slot_cap;
                 f.overflow = a.overflow;
+            } else if (fill) {
+                // no partition: the finalize kernel reads the search's buffer, whose unused slots get their sentinels now
+                VSC_TRY(launch_fill_holes(d_segs, (uint32_t)n_segs, src, fill, l1->fill_shift, st));
             }
             if (!sorted_marked && ev_sorted) {
                 VSC_TRY(hipEventRecord(ev_sorted, st));
@@ -1189,10 +1240,11 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
                     // a bin outgrew its slot: the source is untouched, nothing was finalized (the finalize kernel left at
                     // once) - the same level again, exactly.  What the failed attempt moved: the partition's read + write
                     use_slots = false;
+                    parted = false;
                     *slots = false;
                     if (info) {
                         info->slot_fallbacks++;
-                        info->bytes += 16 * n_all;
+                        info->bytes += 16 * n_moved;
                     }
                     continue;
                 }
@@ -1200,9 +1252,9 @@ hipError_t bin_sort(vsc_ctx *ctx, const vsc_genome *genome, std::vector<SortSeg>
             if (info && bits) {
                 if (info->levels == 0) info->bin_bits = bits;
                 info->levels++;
-                info->bytes += (use_slots ? 16 : 24) * n_all;  // (histogram read,) partition read + write
+                info->bytes += (use_slots ? 16 : 24) * n_moved;  // (histogram read,) partition read + write
             }
-            if (info) info->bytes += 24 * n_all;  // finalize: 8-byte read, 16-byte write
+            if (info) info->bytes += 24 * n_moved;  // finalize: 8-byte read, 16-byte write
             if (info && rows) info->bytes += (bits ? 8 : 0) * n_all + (4 + 12 + 64) * n_all;  // side words moved, read (twice: + the records again), rows written
             break;
         }
@@ -1274,6 +1326,7 @@ struct PassFound {
     std::vector<uint32_t> sink_tile0;
     SinkInput sink{};         // what sink_input staged (recs null: nothing yet)
     bool classified = false;  // classify_pass's kernel has run between kEvClassStart and kEvClassEnd
+    SortLevel1 l1;            // SEED, records for the sort alone: the block fill table; a search in parts: its level-1 partition
 };
 
 // words within k substitutions of a 7-base segment (k < 0: none)
@@ -1431,10 +1484,179 @@ hipError_t seed_plan(vsc_ctx *ctx, const vsc_genome *genome, const uint32_t *gp,
     return hipSuccess;
 }
 
+// ---- a seed search in parts -------------------------------------------------------------------------------------------------
+// In slot mode the level-1 partition appends a tile's records to their bins through the bin cursors: it needs no histogram and
+// no total, so it can start on the records of the chunks searched so far.  The chunk range is cut into K launches; the
+// partition of part i runs on the context's second stream beside part i + 1, which leaves it room on every CU (three search
+// workgroups instead of six: registers and LDS then hold one partition workgroup as well).  Only the bin starts and the last
+// stage wait for all records (bin_sort, SortLevel1.done).
+constexpr uint32_t kSeedPartsDefault = 1;       // launches of a search that qualifies (hook seed_parts = 0)
+constexpr uint32_t kSeedPartsMax = 64;
+// search workgroups per CU beside a partition.  Per SIMD the search's waves take 80 registers each, a partition workgroup's
+// two waves 104 each (92 + 5 accumulation registers, allocated in eights): 4 x 80 + 208 = 528 of 512 - with four search
+// workgroups no partition workgroup ever became resident (kernel trace: the first part's partition ended after the search) -,
+// 3 x 80 + 208 = 448; LDS 3 x 20 992 + 74 752 of 163 840 bytes.
+constexpr uint32_t kSeedPartGroupsPerCu = 3;
+// A part pays a launch tail of the search, a partition launch and an event round trip through the host - some tens of
+// microseconds - to hide its partition: 2^27 records are 0.4 ms of partition at 4.85 TB/s, ten times that.
+constexpr uint64_t kSeedPartMinRecords = 1ull << 27;
+
+// How many launches the pass's search is cut into, with the level-1 layout (l1.bits, l1.slot_cap) its partitions will use:
+// chosen before the search, from what the last search of this genome and budget produced.  1: one launch, the sort as ever.
+// Always 1: per-wave chunks (sparse searches), a context bound to a set of CUs, a genome whose bins have outgrown their slots
+// at this budget (or the hook that forbids slots), slots that do not fit the device, and - unless the hook forces parts - a
+// pass that needs no partition level or expects fewer than kSeedPartMinRecords records per part.
+uint32_t plan_parts(vsc_ctx *ctx, const vsc_genome *genome, const PassFound &f, const SeedArgs &sa, uint32_t n_guides, bool shared, SortLevel1 &l1)
+{
+    const vsc_debug_params &dbg = ctx->dbg;
+    uint32_t want = dbg.seed_parts ? dbg.seed_parts : kSeedPartsDefault;
+    if (want <= 1 || !shared || ctx->cu_masked || dbg.sort_optimistic == 0 || !genome->sort_slots_ok[f.max_mm]) return 1;
+    const double rate = genome->seen_rate[f.max_mm];  // records per read of the fullest region
+    const uint64_t n_max = (uint64_t)(rate * std::min<uint32_t>(n_guides, kRegionReads)), n_all = (uint64_t)(rate * n_guides);
+    want = std::min<uint32_t>({want, std::max<uint32_t>(1, sa.n_chunks), kSeedPartsMax});
+    if (!dbg.seed_parts && n_all < (uint64_t)want * kSeedPartMinRecords) return 1;
+    uint64_t sort_cap, slot_cap;
+    unsigned max_bits;
+    sort_limits(dbg, &sort_cap, &max_bits, &slot_cap);
+    unsigned bits = level_bits(n_max, sort_cap, max_bits, f.key_bits, (size_t)f.n_parts);
+    if (bits == 0) {
+        if (!dbg.seed_parts) return 1;
+        bits = 1;  // (forced: a partition level the records would not need)
+    }
+    if (dbg.sort_optimistic != 1 && !slots_fit((uint64_t)f.n_parts << bits, slot_cap, std::max<uint64_t>(n_all, 1), ctx->keys_b.cap, 0, false)) return 1;
+    l1.bits = bits;
+    l1.slot_cap = slot_cap;
+    return want;
+}
+
+size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+
+// The search of a pass in K parts with their level-1 partitions (above).  Stream A = ctx->stream: the parts back to back, after
+// each a copy of the counters to pinned memory and an event.  The host waits for event i while part i + 1 is queued, cuts the
+// records of part i - per region [cursor after part i - 1, cursor after part i) - into segments and launches their partition
+// on stream B; A waits for B at the end.  Ordering is by events alone.  cnt: the counters after the last part; l1.done unless
+// records were lost (the caller runs the pass again, in one launch).
+hipError_t search_in_parts(vsc_ctx *ctx, PassFound &f, const SeedArgs &all, uint32_t K, bool shared, unsigned long long *cnt, size_t cnt_bytes,
+                           uint32_t *list_total, float *scan_ms)
+{
+    const hipStream_t A = ctx->stream;
+    SeedArgs sa = all;
+    const uint32_t R = (uint32_t)f.n_parts;
+    const size_t cnt_at = 0, segs_at = round256(cnt_bytes), tile_at = segs_at + round256(R * sizeof(SortSeg));
+    const size_t stride = tile_at + round256((R + 1) * sizeof(uint32_t)), dev_stride = stride - segs_at;
+    if (!ctx->stream_b) VSC_TRY(hipStreamCreateWithFlags(&ctx->stream_b, hipStreamNonBlocking));
+    const hipStream_t B = ctx->stream_b;
+    while (ctx->part_ev.size() < 3 * (size_t)K + 1) {
+        hipEvent_t e = nullptr;
+        VSC_TRY(hipEventCreate(&e));
+        ctx->part_ev.push_back(e);
+    }
+    if (ctx->pinned_cap < K * stride + 256) {
+        if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+        ctx->pinned = nullptr;
+        ctx->pinned_cap = 0;
+        VSC_TRY(hipHostMalloc(&ctx->pinned, K * stride + 256, hipHostMallocDefault));
+        ctx->pinned_cap = K * stride + 256;
+    }
+    char *const pin = (char *)ctx->pinned;
+    uint32_t *const pin_total = (uint32_t *)(pin + K * stride);
+    SortLevel1 &l1 = f.l1;
+    const size_t n_bins = (size_t)R << l1.bits;
+    // the level's tables and its destination, as bin_sort would make them (it finds them made)
+    VSC_TRY(ctx->keys_b.ensure(std::max<uint64_t>((uint64_t)n_bins * l1.slot_cap, f.cap) * sizeof(uint64_t)));
+    VSC_TRY(ctx->sort_tabs.ensure(3 * n_bins * sizeof(uint32_t)));
+    VSC_TRY(ctx->sort_over.ensure(256 + n_bins * sizeof(SortSeg)));
+    VSC_TRY(ctx->sort_segs.ensure(std::max<size_t>(K * dev_stride, round256(R * sizeof(SortSeg)) + (R + 1) * sizeof(uint32_t))));
+    SortArgs pa{};
+    pa.n_segs = R;
+    pa.in = (const uint64_t *)ctx->keys_a.p;
+    pa.out = (uint64_t *)ctx->keys_b.p;
+    pa.cursor = (uint32_t *)ctx->sort_tabs.p + n_bins;
+    pa.hist = pa.cursor;
+    pa.bin_start = pa.cursor + n_bins;
+    pa.bin_bits = l1.bits;
+    pa.bin_shift = kRecPosShift + f.pos_pad + f.key_bits - l1.bits;
+    pa.fill = l1.fill;
+    pa.fill_shift = l1.fill_shift;
+    pa.slot_cap = (uint32_t)l1.slot_cap;
+    pa.overflow = (uint32_t *)ctx->sort_over.p + 2;
+    VSC_TRY(hipMemsetAsync(pa.cursor, 0, n_bins * sizeof(uint32_t), A));
+    VSC_TRY(hipMemsetAsync(ctx->sort_over.p, 0, 3 * sizeof(uint32_t), A));
+    VSC_TRY(hipMemcpyAsync(pin_total, (const uint32_t *)ctx->seed_poff.p + kLists, sizeof(uint32_t), hipMemcpyDeviceToHost, A));
+    VSC_TRY(hipEventRecord(ctx->ev[kEvSearchStart], A));
+    for (uint32_t i = 0; i < K; ++i) {
+        // part i: chunks [n i / K, n (i + 1) / K) - its own piece of the chunk table, sliced by the 32 work cursors as a whole table is
+        const uint32_t chunk_first = (uint32_t)((uint64_t)all.n_chunks * i / K);
+        sa.chunk_tab = all.chunk_tab + chunk_first;
+        sa.n_chunks = (uint32_t)((uint64_t)all.n_chunks * (i + 1) / K) - chunk_first;
+        // part 1 has the CUs to itself, the others share them with a partition (the hook overrides both)
+        const uint32_t per_cu = ctx->dbg.seed_groups_per_cu ? ctx->dbg.seed_groups_per_cu : (i ? kSeedPartGroupsPerCu : (uint32_t)kSlicedWavesPerSimd);
+        const uint32_t n_grabs = (sa.n_chunks + kSlicedGrab - 1) / kSlicedGrab;
+        const uint32_t n_waves = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)ctx->n_cus * per_cu * kWavesPerGroup, shared ? n_grabs * kWavesPerGroup : n_grabs));
+        if (i) VSC_TRY(hipMemsetAsync(sa.counters + kCursorBase, 0, (size_t)kCursors * kCursorStride * sizeof(unsigned long long), A));
+        VSC_TRY(hipEventRecord(ctx->part_ev[3 * i], A));
+        VSC_TRY(launch_seed_sliced(sa, (int)((n_waves + kWavesPerGroup - 1) / kWavesPerGroup), shared, A));
+        VSC_TRY(hipEventRecord(ctx->part_ev[3 * i + 1], A));
+        VSC_TRY(hipMemcpyAsync(pin + i * stride + cnt_at, sa.counters, cnt_bytes, hipMemcpyDeviceToHost, A));
+        VSC_TRY(hipEventRecord(ctx->part_ev[3 * i + 2], A));
+    }
+    VSC_TRY(hipEventRecord(ctx->ev[kEvSearchEnd], A));
+    bool lost = false;
+    for (uint32_t i = 0; i < K; ++i) {
+        VSC_TRY(hipEventSynchronize(ctx->part_ev[3 * i + 2]));
+        const unsigned long long *const now = (const unsigned long long *)(pin + i * stride + cnt_at);
+        const unsigned long long *const before = i ? (const unsigned long long *)(pin + (i - 1) * stride + cnt_at) : nullptr;
+        if (now[kCntOverflow]) lost = true;
+        if (lost) continue;  // (the parts still queued run out; nothing more is partitioned)
+        SortSeg *const segs = (SortSeg *)(pin + i * stride + segs_at);
+        uint32_t *const tile0 = (uint32_t *)(pin + i * stride + tile_at);
+        uint64_t tiles = 0;
+        for (uint32_t q = 0; q < R; ++q) {
+            const uint64_t b = before ? before[kCntPart + 4 * q] : 0, e = now[kCntPart + 4 * q];
+            const uint64_t at = (uint64_t)q * sa.part_cap + b;
+            segs[q] = SortSeg{at, at, 0, (uint32_t)(e - b), 0, q, 0};
+            tile0[q] = (uint32_t)tiles;
+            tiles += (e - b + kSortTile - 1) / kSortTile;
+        }
+        tile0[R] = (uint32_t)tiles;
+        if (tiles == 0) continue;
+        if (tiles >= (1ull << 31)) return hipErrorInvalidValue;
+        char *const dev = (char *)ctx->sort_segs.p + i * dev_stride;
+        VSC_TRY(hipStreamWaitEvent(B, ctx->part_ev[3 * i + 2], 0));
+        VSC_TRY(hipMemcpyAsync(dev, segs, dev_stride, hipMemcpyHostToDevice, B));
+        pa.segs = (const SortSeg *)dev;
+        pa.seg_tile0 = (const uint32_t *)(dev + (tile_at - segs_at));
+        pa.n_tiles = (uint32_t)tiles;
+        pa.xcd_tiles = 0;
+        pa.xcd_by_region = 0;
+        if (ctx->dbg.sort_xcd != 0 && tiles >= 64) {
+            // XCD x takes the segments of regions [R x / 8, R (x + 1) / 8): the same regions in every part
+            pa.xcd_by_region = 1;
+            for (uint32_t x = 0; x <= 8; ++x) pa.xcd_first[x] = tile0[(uint64_t)R * x / 8];
+            for (uint32_t x = 0; x < 8; ++x) pa.xcd_tiles = std::max(pa.xcd_tiles, pa.xcd_first[x + 1] - pa.xcd_first[x]);
+        }
+        VSC_TRY(launch_bin_partition(pa, B));
+    }
+    VSC_TRY(hipEventRecord(ctx->part_ev[3 * K], B));
+    VSC_TRY(hipStreamWaitEvent(A, ctx->part_ev[3 * K], 0));
+    std::memcpy(cnt, pin + (K - 1) * stride + cnt_at, cnt_bytes);
+    *list_total = *pin_total;
+    *scan_ms = 0;
+    for (uint32_t i = 0; i < K; ++i) {
+        float ms = 0;
+        VSC_TRY(hipEventElapsedTime(&ms, ctx->part_ev[3 * i], ctx->part_ev[3 * i + 1]));
+        *scan_ms += ms;
+    }
+    l1.done = !lost;
+    if (lost) VSC_TRY(hipStreamSynchronize(A));  // (B's partitions included: the pass starts over)
+    return hipSuccess;
+}
+
 // The search of a pass over guides[0 .. n_guides) (<= kMaxPassReads; read indices guide_base + i) up to final records, with
 // the genome's sizing hints it learns.  keep_bases (SEED): every hit's site lo plane beside its record.  Timings ADD to t.
+// sort_only: the sort is the only reader of the records (SEED: block fill table instead of sentinels, perhaps a search in parts).
 int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, uint32_t guide_base,
-              const vsc_search_params *params, bool keep_bases, vsc_timing &t, PassFound &f)
+              const vsc_search_params *params, bool keep_bases, bool sort_only, vsc_timing &t, PassFound &f)
 {
     const int algo = (int)t.algorithm;  // search_setup's choice
     const uint32_t m = params->max_mismatches;
@@ -1469,6 +1691,11 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     SeedArgs sa{};
     int n_groups = 1;
     bool seed_shared = false;
+    // records that go to the sort and nowhere else (no other sink walks them, no side words): the unused tails of the
+    // search's blocks are named by the block fill table instead of being written as sentinels and read back
+    const bool use_fill = algo == VSC_ALGO_SEED && sort_only && !keep_bases;
+    uint32_t n_parts_k = 1;  // launches of the search (plan_parts)
+    auto owners_of = [](const SeedArgs &s, int groups) { return (uint64_t)(s.group_out ? groups : groups * kWavesPerGroup); };
     if (algo == VSC_ALGO_SCAN) {
         fill_pam(a, params);
         fill_genome(a, ctx, genome);
@@ -1481,17 +1708,50 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvPrepEnd], ctx->stream));
     } else {
         VSC_HIP(ctx, seed_plan(ctx, genome, gp.data(), n_guides, f, sa, &n_groups, &seed_shared));
+        if (use_fill) {
+            // a tile of the sort never straddles regions, and a block of the fill table never does (reserve divides kSortTile);
+            // every launch of a search in parts leaves a block open per owner and region
+            n_parts_k = plan_parts(ctx, genome, f, sa, n_guides, seed_shared, f.l1);
+            sa.part_cap += (uint64_t)(n_parts_k - 1) * owners_of(sa, n_groups) * sa.reserve;
+            sa.part_cap = (sa.part_cap + kSortTile - 1) / kSortTile * kSortTile;
+        }
         f.cap = sa.part_cap * f.n_parts;
     }
 
     f.ht.lap("prep enqueue");
     uint32_t list_total = 0;
+    float parts_ms = -1;  // a search in parts: the sum of its launches
     for (unsigned tries = 0;; ++tries) {
         // (the kernel keeps a block number in 20 bits, all ones meaning "full": part_cap / reserve < 2^20 - 1)
         if (algo == VSC_ALGO_SEED && (sa.part_cap >= (1ull << 32) - (1u << 20) || sa.part_cap >= ((uint64_t)sa.reserve << 20) - sa.reserve))
             return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in a block of 64 reads");
         VSC_HIP(ctx, ctx->keys_a.ensure(f.cap * sizeof(uint64_t)));
         VSC_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, kCounterWords * sizeof(unsigned long long), ctx->stream));
+        if (use_fill) {
+            const size_t fill_bytes = (size_t)(f.cap >> sa.reserve_log2) * sizeof(uint32_t);
+            VSC_HIP(ctx, ctx->seed_fill.ensure(fill_bytes));
+            VSC_HIP(ctx, hipMemsetAsync(ctx->seed_fill.p, 0xFF, fill_bytes, ctx->stream));  // every block "full" until a wave leaves it open
+            sa.fill = (uint32_t *)ctx->seed_fill.p;
+            f.l1.fill = sa.fill;
+            f.l1.fill_shift = sa.reserve_log2;
+        }
+        if (n_parts_k > 1) {
+            sa.hit_recs = (uint64_t *)ctx->keys_a.p;
+            VSC_HIP(ctx, search_in_parts(ctx, f, sa, n_parts_k, seed_shared, cnt, sizeof cnt, &list_total, &parts_ms));
+            f.ht.lap("search in parts");
+            t.passes++;
+            if (!cnt[kCntOverflow]) break;
+            if (tries >= 2) return fail(ctx, VSC_ERR_DEVICE, "vsc_search: hit buffer overflowed repeatedly");
+            // records were lost: the whole pass again in one launch, with room for what the counters say
+            uint64_t need = 0;
+            for (int q = 0; q < f.n_parts; ++q) need = std::max<uint64_t>(need, cnt[kCntPart + 4 * q] + cnt[kCntPart + 4 * q + 2]);
+            n_parts_k = 1;
+            f.l1.done = false;
+            sa.part_cap = need + (need >> 6) + 4096 + owners_of(sa, n_groups) * sa.reserve;
+            sa.part_cap = (sa.part_cap + kSortTile - 1) / kSortTile * kSortTile;
+            f.cap = sa.part_cap * f.n_parts;
+            continue;
+        }
         VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSearchStart], ctx->stream));
         if (algo == VSC_ALGO_SCAN) {
             VSC_HIP(ctx, ctx->vals_a.ensure(f.cap * sizeof(uint32_t)));
@@ -1520,7 +1780,8 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         if (algo == VSC_ALGO_SEED) {
             uint64_t need = 0;
             for (int q = 0; q < f.n_parts; ++q) need = std::max<uint64_t>(need, cnt[kCntPart + 4 * q] + cnt[kCntPart + 4 * q + 2]);
-            sa.part_cap = need + (need >> 6) + 4096 + (uint64_t)(sa.group_out ? n_groups : n_groups * kWavesPerGroup) * sa.reserve;
+            sa.part_cap = need + (need >> 6) + 4096 + owners_of(sa, n_groups) * sa.reserve;
+            if (use_fill) sa.part_cap = (sa.part_cap + kSortTile - 1) / kSortTile * kSortTile;
             f.cap = sa.part_cap * f.n_parts;
         } else {
             f.cap = cnt[kCntHits] + (cnt[kCntHits] >> 6) + 4096;
@@ -1529,7 +1790,11 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     float ms = 0;
     VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvPassStart], ctx->ev[kEvPrepEnd]));
     t.prep_ms += ms;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvSearchStart], ctx->ev[kEvSearchEnd]));
+    if (f.l1.done) {
+        ms = parts_ms;
+    } else {
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvSearchStart], ctx->ev[kEvSearchEnd]));
+    }
     t.scan_ms += ms;
 
     // ---- the records: one segment of pairs (SCAN) or one per region (SEED) ----------------------------------------
@@ -1551,10 +1816,12 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         for (int q = 0; q < f.n_parts; ++q) {
             const uint64_t placed = cnt[kCntPart + 4 * q], real = placed - cnt[kCntPart + 4 * q + 1];
             fullest = std::max(fullest, (double)placed / std::min<uint32_t>(kRegionReads, n_guides - (uint32_t)q * kRegionReads));
-            if (placed) f.segs.push_back(SortSeg{(uint64_t)q * sa.part_cap, (uint64_t)q * sa.part_cap, f.n, (uint32_t)placed,
-                                                 guide_base + (uint32_t)q * kRegionReads});
+            // (a search in parts: every region, so that segment i is region i, as its partitions had it)
+            if (placed || f.l1.done) f.segs.push_back(SortSeg{(uint64_t)q * sa.part_cap, (uint64_t)q * sa.part_cap, f.n, (uint32_t)placed,
+                                                              guide_base + (uint32_t)q * kRegionReads, (uint32_t)q, 0});
             f.n += real;
         }
+        f.l1.n_real = f.n;
         genome->seen_rate[m] = fullest;
         // (the sort's second buffer, ctx->keys_b, is sized by bin_sort for the layout its first level uses)
     }
@@ -1685,7 +1952,8 @@ int sort_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, vsc_hits *hi
             rows.rows_first = used;
         }
         VSC_HIP(ctx, bin_sort(ctx, genome, std::move(f.segs), src, other, f.key_bits, f.pos_pad, f.pos_base, hits->d_records, ctx->ev[kEvSinkStart],
-                              &info, f.algo == VSC_ALGO_SEED || f.selected ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr));
+                              &info, f.algo == VSC_ALGO_SEED || f.selected ? &ctx->keys_b : nullptr, slots, f.bases ? &rows : nullptr,
+                              f.algo == VSC_ALGO_SEED && !f.selected && (f.l1.fill || f.l1.done) ? &f.l1 : nullptr));
     } else {
         VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
     }
@@ -2133,8 +2401,10 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
         // (an accumulated result grows to its expected final size at once)
         const uint64_t projected = !per_batch && first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
         PassFound f;
-        rc = find_pass(ctx, genome, guides + first, count, first, params, p.keep_bases && t.algorithm == VSC_ALGO_SEED, t, f);
         const bool votes_rows = classifying && p.votes_rows;
+        // (the sort is the records' only reader: no classifier, no rows, no selection walks them where the search left them)
+        const bool sort_only = p.records != Records::kNone && !classifying && !rows && !selecting;
+        rc = find_pass(ctx, genome, guides + first, count, first, params, p.keep_bases && t.algorithm == VSC_ALGO_SEED, sort_only, t, f);
         if (rc == VSC_OK && classifying) rc = classify_pass(ctx, genome, f, count, !excl.empty());
         // (with another sink to follow, the summary leaves the end of the pass - and finalize_ms - to the sort)
         if (rc == VSC_OK && rows) rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone && !votes_rows, p.rows_in ? &reg : nullptr);

@@ -144,8 +144,12 @@ struct SortSeg {
     uint64_t in_off;     // first record of the segment in the level's source buffer
     uint64_t out_off;    // first record of the segment's span in the level's destination buffer
     uint64_t final_off;  // index of the segment's first vsc_hit in the result
-    uint32_t n_in;       // records in the source span (level 1: sentinels included)
+    uint32_t n_in;       // records in the source span (level 1: sentinels / unused block tails included)
     uint32_t guide_base; // read index of the region's first read
+    // whose bin cursors and slots a partition appends to: (region << bin_bits) + bin.  The segment's own index, except
+    // where a region's records arrive in several segments (a search in parts: one segment per part and region)
+    uint32_t region = 0;
+    uint32_t pad = 0;
 };
 
 struct SortArgs {
@@ -165,6 +169,14 @@ struct SortArgs {
     uint32_t pos_pad;              // level 0: left shift of the position field
     uint32_t pos_base;             // level 0: first global position of the shard (records hold positions relative to it)
     uint32_t xcd_tiles;            // partition: tiles per XCD (0: workgroup b takes tile b)
+    // a search in parts: XCD x takes tiles [xcd_first[x], xcd_first[x + 1]) - the segments of ITS regions, the same regions in
+    // every part, so that the pieces of one bin still meet in one L2 (xcd_tiles = the longest of the eight ranges)
+    uint32_t xcd_by_region;
+    uint32_t xcd_first[9];
+    // the block fill table of the search's records (SeedArgs::fill; null: unused slots hold sentinels): record i of `in` is
+    // valid iff (i & ((1 << fill_shift) - 1)) < fill[i >> fill_shift]; the slots of a hole are not read
+    const uint32_t *fill;
+    uint32_t fill_shift;
     // slot mode (no histogram pass): bin i of the level owns records [i * slot_cap, (i + 1) * slot_cap) of `out`; the
     // partition reserves room with `cursor` (zeroed) alone and raises *overflow when a bin does not fit its slot -
     // the caller then repeats the level with the histogram.  0: exact mode (bin_start from the histogram)
@@ -235,6 +247,9 @@ struct SeedPlan {
 };
 
 struct SeedArgs {
+    // (a search cut into several launches hands each launch its part of the table: chunk_tab + first chunk, n_chunks = the part's
+    // chunks - an entry names its sites and blocks by absolute index.  The launches share the region cursors; every launch
+    // opens fresh blocks and closes them)
     const uint4 *chunk_tab;        // [n_chunks] {first site, site count, bucket | first '-' rank << 16 | edge << 28 | class << 29, first vertical block}
     const uint32_t *vert;          // bit-sliced copies of the sites: kVertWords words per block of 32 sites (see seed_transpose_kernel)
     const uint2 *list_rest;        // per list entry {rest(hi) | rest(lo) << 16, read | budget per class << 16 ..}
@@ -258,6 +273,11 @@ struct SeedArgs {
     uint32_t n_parts;              // regions in use (region of a hit = read index >> kRegionBits)
     unsigned long long part_cap;   // records per region
     unsigned long long *counters;  // kCntPart + 4 p + {0,1,2}, kCntSites (= pairs compared), kCntVisited, kCntOverflow, cursors
+    // Block fill table (null: the unused tail of every open block is written as sentinels and counted in kCntPart + 4 p + 1):
+    // one word per block of `reserve` records of hit_recs - part_cap is a multiple of reserve, so block b of region p is word
+    // (p * part_cap >> reserve_log2) + b -, set to all ones ("full") before the launch; a wave that leaves a block open at the
+    // end of the kernel stores the records it holds.  Slots past that count are never written, and never read by the sort.
+    uint32_t *fill;
 };
 
 // ---- the record sinks' input ---------------------------------------------------------------------------------------------
@@ -476,6 +496,9 @@ hipError_t launch_bin_hist(const SortArgs &args, hipStream_t stream);
 hipError_t launch_bin_scan(const SortArgs &args, hipStream_t stream);
 hipError_t launch_bin_partition(const SortArgs &args, hipStream_t stream);
 hipError_t launch_bin_finalize(const FinArgs &args, int max_groups, hipStream_t stream);
+// writes the sentinel into the unused slots of the segments' blocks (a level 1 that needs no partition: the finalize kernel reads
+// the search's records as they lie)
+hipError_t launch_fill_holes(const SortSeg *segs, uint32_t n_segs, uint64_t *recs, const uint32_t *fill, uint32_t fill_shift, hipStream_t stream);
 hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);

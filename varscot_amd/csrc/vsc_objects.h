@@ -102,6 +102,16 @@ struct vsc_ctx {
     std::vector<vsc::SortSeg> host_segs;
     std::vector<uint32_t> host_tile0;  // bin sort: segment table + tile starts, per-bin tables, oversize list + counter
     vsc::DeviceBuf seed_off, seed_poff, seed_lrest;  // per-search read lists: bucket counts, padded list starts, entries
+    vsc::DeviceBuf seed_fill;  // the block fill table of a seed search whose records go straight to the sort (SeedArgs.fill)
+    // A seed search in parts (find_pass): the level-1 partition of every part runs on stream_b beside the next part of the
+    // search on `stream`, ordered by the events of part_ev alone (per part: start, end, counters copied; then the join);
+    // `pinned` stages what goes to and from the device while kernels run (per part: the counters, the segments, their tiles).
+    // All made on first use.  cu_masked: the context's stream is bound to a set of CUs - such a context never searches in parts.
+    hipStream_t stream_b = nullptr;
+    std::vector<hipEvent_t> part_ev;
+    void *pinned = nullptr;
+    size_t pinned_cap = 0;
+    bool cu_masked = false;
     vsc::DeviceBuf sum_rows, sum_excl;  // vsc_search_summary: the per-read rows it adds into, the excluded loci
     // vsc_search_select: per-read tables of a pass (score histograms, thresholds, counts, cursors, list starts), the candidates' keys and masks
     vsc::DeviceBuf sel_hist, sel_tabs, sel_keys, sel_masks;

@@ -615,7 +615,8 @@ __device__ __forceinline__ void sliced_store(const SeedArgs &a, SeedWave &w, boo
     }
 }
 
-// end of the kernel: the open blocks are filled up with sentinels, which the sort drops (group-shared blocks: behind
+// end of the kernel: what the open blocks hold goes into the block fill table (the sort reads no slot past it), or -
+// without a table - the open blocks are filled up with sentinels, which the sort drops (group-shared blocks: behind
 // the workgroup's last barrier, region q by wave q mod 4)
 __device__ __forceinline__ void sliced_finish_hits(const SeedArgs &a, SeedWave &w, uint32_t first, uint32_t step)
 {
@@ -625,6 +626,15 @@ __device__ __forceinline__ void sliced_finish_hits(const SeedArgs &a, SeedWave &
         if ((state >> kPartBlockShift) == kPartDeadBlock) continue;
         const uint32_t base = (state >> kPartBlockShift) << a.reserve_log2, used = state & kPartUsedMask;
         const uint32_t left = used < a.reserve ? a.reserve - used : 0u;
+        if (a.fill) {
+            // (left == 0 also is "no block yet": block number 0 with `reserve` records claimed - not this wave's to close)
+            // (the unused slots are still counted: the host takes the region's records as slots reserved less slots unused)
+            if (w.lane == 0 && left) {
+                a.fill[(((unsigned long long)q * a.part_cap) >> a.reserve_log2) + (state >> kPartBlockShift)] = used;
+                atomicAdd(&a.counters[kCntPart + 4 * q + 1], (unsigned long long)left);
+            }
+            continue;
+        }
         for (uint32_t i = w.lane; i < left; i += kWave) a.hit_recs[(unsigned long long)q * a.part_cap + base + used + i] = kRecSentinel;
         if (w.lane == 0 && left) atomicAdd(&a.counters[kCntPart + 4 * q + 1], (unsigned long long)left);
     }

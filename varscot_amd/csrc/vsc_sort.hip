@@ -85,6 +85,13 @@ __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t *s, uint32_t n
     return total;
 }
 
+// Block fill table (SortArgs.fill): what the block of record slot `at` holds.  A thread's two consecutive slots (tile_record)
+// lie in one block - blocks are at least 64 slots, and segments and tiles start on block boundaries.
+__device__ __forceinline__ bool slot_filled(const SortArgs &a, uint64_t at, uint32_t held)
+{
+    return ((uint32_t)at & ((1u << a.fill_shift) - 1u)) < held;
+}
+
 // level 0: a (key, value) pair of the streaming scan -> packed record (the read's region is the bin, not part of it)
 __device__ __forceinline__ uint64_t pack_pair(uint64_t key, uint32_t val, uint32_t pos_pad, uint32_t pos_base)
 {
@@ -97,7 +104,7 @@ __device__ __forceinline__ uint64_t pack_pair(uint64_t key, uint32_t val, uint32
 // ------------------------------------------------------------------------------------------------
 // histogram: records per (segment, bin)
 // ------------------------------------------------------------------------------------------------
-template <bool kPairs>
+template <bool kPairs, bool kFill = false>
 __global__ __launch_bounds__(kSortThreads) void bin_hist_kernel(const SortArgs a)
 {
     __shared__ uint32_t s_hist[1 << kSortMaxBinBits];
@@ -113,7 +120,7 @@ __global__ __launch_bounds__(kSortThreads) void bin_hist_kernel(const SortArgs a
             block_sync();
             for (uint32_t b = t; b < nbins; b += kSortThreads) {
                 const uint32_t c = s_hist[b];
-                if (c) atomicAdd(&a.hist[((size_t)seg << a.bin_bits) + b], c);
+                if (c) atomicAdd(&a.hist[((size_t)a.segs[seg].region << a.bin_bits) + b], c);
                 s_hist[b] = 0;
             }
             block_sync();
@@ -124,12 +131,21 @@ __global__ __launch_bounds__(kSortThreads) void bin_hist_kernel(const SortArgs a
         const uint32_t n = min(sg.n_in - first, (uint32_t)kSortTile);
         // all sixteen loads first, without branches (see bin_partition_kernel), then the counting
         uint64_t r[kSortItems];
+        uint32_t held[kFill ? kSortItems / kLaneRun : 1];
+        if (kFill) {
+#pragma unroll
+            for (int j = 0; j < kSortItems / kLaneRun; ++j) {
+                const uint32_t i = tile_record(j * kLaneRun, t);
+                held[j] = a.fill[(sg.in_off + first + (i < n ? i : 0u)) >> a.fill_shift];
+            }
+        }
 #pragma unroll
         for (int k = 0; k < kSortItems; ++k) {
             const uint32_t i = tile_record(k, t);
-            const uint64_t at = sg.in_off + first + (i < n ? i : 0u);
+            const bool valid = i < n && (!kFill || slot_filled(a, sg.in_off + first + i, held[kFill ? k / kLaneRun : 0]));
+            const uint64_t at = sg.in_off + first + (valid ? i : 0u);
             const uint64_t v = kPairs ? a.pair_keys[at] : a.in[at];
-            r[k] = i < n ? v : kRecSentinel;
+            r[k] = valid ? v : kRecSentinel;
         }
 #pragma unroll
         for (int k = 0; k < kSortItems; ++k) {
@@ -143,7 +159,7 @@ __global__ __launch_bounds__(kSortThreads) void bin_hist_kernel(const SortArgs a
     block_sync();
     for (uint32_t b = t; b < nbins; b += kSortThreads) {
         const uint32_t c = s_hist[b];
-        if (c) atomicAdd(&a.hist[((size_t)seg << a.bin_bits) + b], c);
+        if (c) atomicAdd(&a.hist[((size_t)a.segs[seg].region << a.bin_bits) + b], c);
     }
 }
 
@@ -153,6 +169,8 @@ hipError_t launch_bin_hist(const SortArgs &args, hipStream_t stream)
     const unsigned blocks = (args.n_tiles + kHistTiles - 1) / kHistTiles;
     if (args.pair_keys)
         hipLaunchKernelGGL(bin_hist_kernel<true>, dim3(blocks), dim3(kSortThreads), 0, stream, args);
+    else if (args.fill)
+        hipLaunchKernelGGL((bin_hist_kernel<false, true>), dim3(blocks), dim3(kSortThreads), 0, stream, args);
     else
         hipLaunchKernelGGL(bin_hist_kernel<false>, dim3(blocks), dim3(kSortThreads), 0, stream, args);
     return hipGetLastError();
@@ -188,7 +206,7 @@ hipError_t launch_bin_scan(const SortArgs &args, hipStream_t stream)
 // ------------------------------------------------------------------------------------------------
 // kSide: every record has a 32-bit side word in a parallel array (the site's lo plane of a search that keeps the sites'
 // bases): it is moved with its record - through the same LDS buffer, in a second pass over the tile's slots.
-template <bool kPairs, bool kSide = false>
+template <bool kPairs, bool kSide = false, bool kFill = false>
 __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortArgs a)
 {
     __shared__ uint64_t s_rec[kSortTile];
@@ -205,7 +223,10 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
     // eighth of the tiles, i.e. whole regions: the pieces different tiles append to one bin then meet in ONE L2,
     // which merges them into full lines before they leave for HBM.  (Speed only: nothing depends on the placement.)
     uint32_t tile = blockIdx.x;
-    if (a.xcd_tiles) {
+    if (a.xcd_by_region) {
+        tile = a.xcd_first[blockIdx.x & 7u] + (blockIdx.x >> 3);
+        if (tile >= a.xcd_first[(blockIdx.x & 7u) + 1u]) return;
+    } else if (a.xcd_tiles) {
         tile = (blockIdx.x & 7u) * a.xcd_tiles + (blockIdx.x >> 3);
         if ((blockIdx.x >> 3) >= a.xcd_tiles || tile >= a.n_tiles) return;
     }
@@ -213,6 +234,15 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
     const SortSeg sg = a.segs[seg];
     const uint32_t first = (tile - a.seg_tile0[seg]) * (uint32_t)kSortTile;
     const uint32_t n = min(sg.n_in - first, (uint32_t)kSortTile);
+    // what the blocks of this thread's slots hold: asked for before the tables are cleared, needed behind the barrier
+    uint32_t held[kFill ? kSortItems / kLaneRun : 1];
+    if (kFill) {
+#pragma unroll
+        for (int j = 0; j < kSortItems / kLaneRun; ++j) {
+            const uint32_t i = tile_record(j * kLaneRun, t);
+            held[j] = a.fill[(sg.in_off + first + (i < n ? i : 0u)) >> a.fill_shift];
+        }
+    }
     for (uint32_t b = t; b < nbins + kWave; b += kSortThreads) s_cnt[b] = 0;
     for (uint32_t b = t; b < (1u << kSortMaxBinBits) / 32u + 1u; b += kSortThreads) s_over[b] = 0;
     block_sync();
@@ -225,7 +255,8 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
 #pragma unroll
     for (int k = 0; k < kSortItems; ++k) {
         const uint32_t i = tile_record(k, t);
-        const bool in_tile = i < n;
+        // (a slot its block does not hold: the clamped address, a sentinel in the register - nothing of a hole is fetched)
+        const bool in_tile = i < n && (!kFill || slot_filled(a, sg.in_off + first + i, held[kFill ? k / kLaneRun : 0]));
         const uint64_t at = sg.in_off + first + (in_tile ? i : 0u);
         if (kSide) side[k] = a.side_in[at];
         if (kPairs) {
@@ -256,7 +287,7 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
     for (int j = 0; j < kOwnBins; ++j) {
         const uint32_t b = t + (uint32_t)j * kSortThreads;
         const uint32_t c = b < nbins ? s_cnt[b] : 0u;
-        uint32_t at = c ? atomicAdd(&a.cursor[((size_t)seg << a.bin_bits) + b], c) : 0u;
+        uint32_t at = c ? atomicAdd(&a.cursor[((size_t)sg.region << a.bin_bits) + b], c) : 0u;
         if (a.slot_cap && c && at + c > a.slot_cap) {  // the bin outgrew its slot: this level is repeated with a histogram
             atomicOr(a.overflow, 1u);
             atomicOr(&s_over[b >> 5], 1u << (b & 31u));
@@ -306,7 +337,7 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
         const uint32_t in_bin = kPairs ? s_gbase[b] + (i - s_cnt[b]) : s_cnt[b] + i;
         const bool skip = any_over && ((s_over[b >> 5] >> (b & 31u)) & 1u);
         if (a.slot_cap) {
-            if (!skip) a.out[(((uint64_t)seg << a.bin_bits) + b) * a.slot_cap + in_bin] = x;
+            if (!skip) a.out[(((uint64_t)sg.region << a.bin_bits) + b) * a.slot_cap + in_bin] = x;
         } else {
             a.out[sg.out_off + in_bin] = x;
         }
@@ -333,7 +364,7 @@ __global__ __launch_bounds__(kSortThreads) void bin_partition_kernel(const SortA
                 const uint32_t in_bin = s_cnt[b] + i;  // (kSide is never level 0)
                 const bool skip = any_over && ((s_over[b >> 5] >> (b & 31u)) & 1u);
                 if (a.slot_cap) {
-                    if (!skip) a.side_out[(((uint64_t)seg << a.bin_bits) + b) * a.slot_cap + in_bin] = s_side[i];
+                    if (!skip) a.side_out[(((uint64_t)sg.region << a.bin_bits) + b) * a.slot_cap + in_bin] = s_side[i];
                 } else {
                     a.side_out[sg.out_off + in_bin] = s_side[i];
                 }
@@ -350,8 +381,32 @@ hipError_t launch_bin_partition(const SortArgs &args, hipStream_t stream)
         hipLaunchKernelGGL(bin_partition_kernel<true>, dim3(blocks), dim3(kSortThreads), 0, stream, args);
     else if (args.side_in)
         hipLaunchKernelGGL((bin_partition_kernel<false, true>), dim3(blocks), dim3(kSortThreads), 0, stream, args);
+    else if (args.fill)
+        hipLaunchKernelGGL((bin_partition_kernel<false, false, true>), dim3(blocks), dim3(kSortThreads), 0, stream, args);
     else
         hipLaunchKernelGGL(bin_partition_kernel<false>, dim3(blocks), dim3(kSortThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// a level 1 without a partition: the finalize kernel reads the search's records where they lie, so the slots the
+// block fill table leaves out get their sentinels after all (a few thousand records per region at the most).
+// One workgroup per segment, a wave per block.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fill_holes_kernel(const SortSeg *segs, uint64_t *recs, const uint32_t *fill, uint32_t fill_shift)
+{
+    const SortSeg sg = segs[blockIdx.x];
+    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, block = 1u << fill_shift;
+    for (uint32_t b0 = wave * block; b0 < sg.n_in; b0 += (256 / kWave) * block) {
+        const uint32_t held = min(fill[(sg.in_off + b0) >> fill_shift], block);
+        for (uint32_t i = held + lane; i < block && b0 + i < sg.n_in; i += kWave) recs[sg.in_off + b0 + i] = kRecSentinel;
+    }
+}
+
+hipError_t launch_fill_holes(const SortSeg *segs, uint32_t n_segs, uint64_t *recs, const uint32_t *fill, uint32_t fill_shift, hipStream_t stream)
+{
+    if (n_segs == 0) return hipSuccess;
+    hipLaunchKernelGGL(fill_holes_kernel, dim3(n_segs), dim3(256), 0, stream, segs, recs, fill, fill_shift);
     return hipGetLastError();
 }
 
@@ -417,6 +472,8 @@ __device__ __forceinline__ void finalize_bin(const FinArgs &a, const uint32_t wh
                 o.final_off = dst;
                 o.n_in = n_src;
                 o.guide_base = sg.guide_base;
+                o.region = 0;  // (the host numbers the next level's segments)
+                o.pad = 0;
                 a.over[slot] = o;
             }
         }
