@@ -117,7 +117,10 @@ typedef struct {
     uint64_t list_entries;   /* VSC_ALGO_SEED: entries of the per-bucket read lists the last pass made (8 bytes each, padding included) */
     uint32_t seed_cut;       /* VSC_ALGO_SEED: k0 | k1 << 4 - substitutions within which read segments 0 and 1 were searched (the third:
                                 what the site's PAM leaves of the limit - k0 - k1 - 2) */
-    uint32_t reserved;
+    uint32_t seed_layout;    /* VSC_ALGO_SEED: how the last pass's search laid its records out (0 for VSC_ALGO_SCAN) - bit 0: one chunk per
+                                workgroup (else per wave); bit 1: workgroup-shared open output blocks (else per wave); bit 2: unused block
+                                tails named by the block fill table (else written as sentinels); bits 4..7: log2 of the slots per block
+                                (6..10); bits 8..15: launches the search was cut into (1..64; 1 after a rerun for lost records) */
 } vsc_timing;
 
 /* ---- context ------------------------------------------------------------------------------- */

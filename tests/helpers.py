@@ -316,17 +316,22 @@ def cut(hits, score, top_k=0, min_score=0, exclude=None, ranked=False):
     return h if ranked else by_result_order(h)
 
 
-def oracle_hits(oracle, contigs, guides, m, pam=None):
-    """Every hit of the oracle with its rint(MIT * 2^24), MIT score and UB flag."""
-    want = oracle.search(contigs, guides, m, extra_pam=pam, mode=oracle.MODE_PREDICATE)
+def oracle_scores(oracle, hits):
+    """(rint(MIT * 2^24), MIT score, UB flag) of records, by the oracle's mit_score over their mismatch masks."""
     cache = {}
-    mit, ub = np.zeros(len(want)), np.zeros(len(want), dtype=np.uint64)
-    for i, info in enumerate(want["info"]):
+    mit, ub = np.zeros(len(hits)), np.zeros(len(hits), dtype=np.uint64)
+    for i, info in enumerate(hits["info"]):
         mask = int(info) & 0x7FFFFF
         if mask not in cache:
             cache[mask] = oracle.mit_score([b for b in range(23) if (mask >> b) & 1] or [-1])
         mit[i], ub[i] = cache[mask][0], cache[mask][1]
-    return want, np.rint(mit * 2.0 ** 24).astype(np.int64), mit, ub
+    return np.rint(mit * 2.0 ** 24).astype(np.int64), mit, ub
+
+
+def oracle_hits(oracle, contigs, guides, m, pam=None):
+    """Every hit of the oracle with its rint(MIT * 2^24), MIT score and UB flag."""
+    want = oracle.search(contigs, guides, m, extra_pam=pam, mode=oracle.MODE_PREDICATE)
+    return (want,) + oracle_scores(oracle, want)
 
 
 def select(gen, guides, m, top_k=0, min_score=0, **kw):

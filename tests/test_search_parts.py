@@ -5,7 +5,10 @@ import numpy as np
 import pytest
 
 import varscot_amd as va
-from helpers import make_genome, mutate, random_guides, random_seq
+from helpers import aggregate
+from layouts import decode
+from parts_cases import MORE_READS_MARKED, more_reads_case, no_hit_case, overflow_case, repeat_rich, repeat_rich_case, repeat_rich_scores
+from sink_walk_case import M as SINK_M, sink_walk_case
 
 pytestmark = pytest.mark.gpu
 
@@ -24,30 +27,14 @@ def hooks(ctx):
     ctx.set_debug()
 
 
-def repeat_rich(seed, n_guides, n_pieces):
-    """The construction of test_sort_without_the_histogram_pass_and_its_fallback: a contig of mutated read copies."""
-    rng = np.random.default_rng(seed)
-    guides = random_guides(rng, n_guides)
-    pieces = []
-    for _ in range(n_pieces):
-        g = guides[int(rng.integers(0, len(guides)))]
-        pieces.append(mutate(rng, g, int(rng.integers(0, 7)), 0, 20) + random_seq(rng, int(rng.integers(0, 3))))
-    contigs = make_genome(seed, [60000, 20000], guides, 8, n_plant=200) + ["".join(pieces)]
-    return guides, contigs
-
-
 @pytest.fixture(scope="module")
 def case(oracle):
-    """70 guides (two regions), > 8 000 hits at m = 8; the oracle's records, computed once and never changed."""
-    guides, contigs = repeat_rich(4711, 70, 9000)
-    want = oracle.search_fast(contigs, guides, 8)
-    assert len(want) > 8000
-    want.setflags(write=False)
-    return guides, contigs, va.PackedGenome.from_sequences(contigs), want
+    """70 guides (two regions), > 8 000 hits at m = 8; the oracle's records, computed once and never changed (parts_cases.py)."""
+    return repeat_rich_case(oracle)
 
 
-def search(ctx, gen, guides, want):
-    h = gen.search(guides, 8, algorithm="seed")
+def search(ctx, gen, guides, want, m=8):
+    h = gen.search(guides, m, algorithm="seed")
     got = h.to_numpy().copy()
     h.close()
     assert got.tobytes() == want.tobytes()
@@ -174,3 +161,226 @@ def test_sort_bytes_count_records_only(ctx, hooks, case, parts):
     assert (t["sort_levels"], t["sort_fallbacks"]) == (1, 0)
     assert t["sort_bytes"] == 40 * len(want)
     gen.close()
+
+
+# ---- the branches of a search in parts: every case with chunk sharing, against the oracle byte for byte, the number of launches
+# read from vsc_timing.seed_layout (tests/layouts.py)
+def launches(t):
+    """Launches of the search behind ctx.timing() = t; a search in parts is one that only the sort reads (the fill table)."""
+    layout = decode(t["seed_layout"])
+    assert layout["shared"] and layout["fill"], layout
+    return layout["launches"]
+
+
+def test_lost_records_rerun_the_pass_in_one_launch(ctx, hooks, oracle):
+    """The genome of test_hit_buffer_overflow_is_retried - 40 copies of one read, 60 000 perfect sites, 2 400 000 hits at m = 0
+    where the estimate allows about a million - in three parts: records are lost, the pass runs again in ONE launch (passes
+    == 2, the fill table written anew); the next search knows the rate, loses nothing and is cut into three.
+    Slots of 32 768 records, taken without asking whether they pay (sort_optimistic = 1): a bin of the rerun's level - a
+    read, a strand, a quarter of the positions - holds up to 21 846 of a read's 60 000 records, and a genome that has shown
+    a bin outgrowing its slot is never searched in parts again (plan_parts)."""
+    guides, packed, want = overflow_case(oracle)
+    assert len(want) == 2_400_000 and np.all(want["pos"] % 24 == 0)
+    hooks(seed_parts=3, seed_shared=1, sort_optimistic=1, sort_slot_cap=32768)
+    gen = ctx.load_genome(packed)
+    try:
+        t = search(ctx, gen, guides, want, m=0)
+        assert t["passes"] == 2 and t["hits"] == len(want), t
+        assert launches(t) == 1 and t["sort_fallbacks"] == 0
+        t = search(ctx, gen, guides, want, m=0)
+        assert t["passes"] == 1 and t["hits"] == len(want), t
+        assert launches(t) == 3 and t["sort_fallbacks"] == 0
+    finally:
+        gen.close()
+
+
+def test_parts_with_a_region_without_records(ctx, hooks, oracle):
+    """The guide set of test_sink_walk.py: 200 reads, region 1 (reads 64 .. 127) without any record, the last region of 8
+    reads.  In parts every region is a segment of the level, the empty one too."""
+    c = sink_walk_case(oracle)
+    hooks(seed_parts=3, seed_shared=1)
+    gen = ctx.load_genome(c["packed"])
+    try:
+        for _ in range(2):
+            t = search(ctx, gen, c["guides"], c["hits"], m=SINK_M)
+            assert launches(t) == 3 and t["sort_fallbacks"] == 0 and t["passes"] == 1, t
+    finally:
+        gen.close()
+
+
+def test_parts_without_any_hit(ctx, hooks, oracle):
+    """No hit at all, four parts: segments of no records in every part, nothing for the level to do - 0 records and no error,
+    with 70 reads and with one read (one region of one read)."""
+    guides, packed, want = no_hit_case(oracle)
+    hooks(seed_parts=4, seed_shared=1)
+    gen = ctx.load_genome(packed)
+    try:
+        for reads in (guides, guides[:1]):
+            t = search(ctx, gen, reads, want, m=0)
+            assert t["hits"] == 0 and launches(t) == 4, t
+    finally:
+        gen.close()
+
+
+def test_parts_with_one_read(ctx, hooks, case, oracle):
+    """One read: one region of one read, its records through the parts' level."""
+    guides, contigs, packed, _ = case
+    want = oracle.search_fast(contigs, guides[:1], 8)
+    assert len(want) > 50
+    hooks(seed_parts=3, seed_shared=1)
+    gen = ctx.load_genome(packed)
+    try:
+        assert launches(search(ctx, gen, guides[:1], want)) == 3
+    finally:
+        gen.close()
+
+
+def test_parts_in_the_second_read_pass(ctx, hooks, oracle):
+    """The inputs of test_more_reads_than_one_pass_takes, 16 384 + 301 reads, both passes in two parts: the second pass has
+    read indices from 16 384 on, its records go behind the first one's, and it finds the level's tables of the first.
+    The sort's hooks pin the plan.  Without them the first pass (256 regions) is one launch - its slots would not pay -
+    and its sort asks slots_fit about the regions that hold records: the answer hangs on how many record slots the search
+    placed, open block tails included, which differs from run to run with the number of workgroups that met a hit; a "no"
+    clears the genome's sort_slots_ok, and plan_parts then keeps the second pass in one launch.  sort_optimistic = 1 takes
+    slots without asking, slots of 4 096 records hold every bin of 1 668 hits."""
+    guides, packed, want = more_reads_case(oracle)
+    hooks(seed_parts=2, seed_shared=1, sort_optimistic=1, sort_slot_cap=4096)
+    gen = ctx.load_genome(packed)
+    try:
+        t = search(ctx, gen, guides, want, m=5)
+    finally:
+        gen.close()
+    assert (t["read_passes"], t["passes"], t["sort_fallbacks"]) == (2, 2, 0), t
+    assert launches(t) == 2 and t["hits"] == len(want), t
+    assert {int(g) for g in want["guide"]} >= set(MORE_READS_MARKED[:3])
+
+
+def test_streamed_batches_in_parts(ctx, hooks, case):
+    """search_streamed in batches of 48 reads: the second batch starts behind the first one's records (used > 0)."""
+    guides, _, packed, want = case
+    hooks(seed_parts=3, seed_shared=1)
+    gen = ctx.load_genome(packed)
+    recs, seen = [], []
+
+    def on_batch(h, first, count):
+        recs.append(h.to_numpy().copy())
+        seen.append(launches(ctx.timing()))
+
+    try:
+        gen.search_streamed(guides, 8, on_batch, batch=48, algorithm="seed")
+    finally:
+        gen.close()
+    assert seen == [3, 3]
+    assert np.concatenate(recs).tobytes() == want.tobytes()
+
+
+def merged(parts):
+    """The records of the shards as one result, as tests/fuzz_gpu.py merges them: shards partition the positions, a stable sort
+    on (guide, strand) merges them."""
+    got = np.concatenate(parts)
+    key = (got["guide"].astype(np.int64) << 1) | (got["info"] >> 31)
+    return got[np.argsort(key, kind="stable")]
+
+
+def test_shards_in_parts(ctx, hooks, case):
+    """Ranks 0 and 1 of a world of two on one context: the second shard's positions count from its first word (pos_base != 0)."""
+    guides, _, packed, want = case
+    hooks(seed_parts=3, seed_shared=1)
+    parts = []
+    for rank in range(2):
+        gen = ctx.load_genome(packed, rank, 2)
+        try:
+            h = gen.search(guides, 8, algorithm="seed")
+            parts.append(h.to_numpy().copy())
+            h.close()
+        finally:
+            gen.close()
+        assert launches(ctx.timing()) == 3
+    assert all(len(p) for p in parts)
+    assert merged(parts).tobytes() == want.tobytes()
+
+
+def test_multi_context_in_parts(case):
+    """MultiContext([0, 0]): two contexts on the device, each searching its shard in parts."""
+    import ctypes as C
+    from varscot_amd import _lib
+    guides, _, packed, want = case
+    m = va.MultiContext([0, 0])
+    try:
+        m.set_debug(seed_parts=3, seed_shared=1)
+        g = m.load_genome(packed)
+        h = g.search(guides, 8, algorithm="seed")
+        got = h.to_numpy().copy()
+        h.close()
+        for i in range(2):
+            t = _lib.Timing()
+            assert va.lib().vsc_ctx_timing(C.c_void_p(va.lib().vsc_multi_ctx(m._h, i)), C.byref(t)) == 0
+            assert launches(t.as_dict()) == 3
+        g.close()
+    finally:
+        m.close()
+    assert got.tobytes() == want.tobytes()
+
+
+def test_release_scratch_between_searches_in_parts(ctx, hooks, case):
+    """vsc_ctx_release_scratch gives the level's tables, its segments and its destination back; the second stream, the events
+    and the pinned block stay.  The next search in parts makes the former again."""
+    guides, _, packed, want = case
+    hooks(seed_parts=3, seed_shared=1)
+    gen = ctx.load_genome(packed)
+    try:
+        assert launches(search(ctx, gen, guides, want)) == 3
+        ctx.release_scratch()
+        assert launches(search(ctx, gen, guides, want)) == 3
+    finally:
+        gen.close()
+
+
+def test_masked_context_stays_in_one_launch(case):
+    """A context bound to a set of CUs (here: all of them) has no second stream on those CUs: one launch whatever the hook says."""
+    import torch
+    guides, _, packed, want = case
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    mask = np.zeros((n_cus + 31) // 32, dtype=np.uint32)
+    for cu in range(n_cus):
+        mask[cu // 32] |= np.uint32(1 << (cu % 32))
+    own = va.Context(0, cu_mask=mask)
+    try:
+        own.set_debug(seed_parts=3, seed_shared=1)
+        gen = own.load_genome(packed)
+        assert launches(search(own, gen, guides, want)) == 1
+        gen.close()
+    finally:
+        own.close()
+
+
+def test_parts_on_the_callers_stream(case, oracle):
+    """vsc_ctx_set_stream: the context works on a stream of the caller's, behind work of the caller's that is still running
+    when the library queues its own - some tenths of a second of matrix products whose last result is checked afterwards; a
+    search in parts orders its second stream against that stream by events alone.  One launch, three launches and a summary:
+    the oracle's."""
+    import torch
+    guides, _, packed, want = case
+    mit, ub = repeat_rich_scores(oracle)
+    stream = torch.cuda.Stream()
+    own = va.Context(0)
+    try:
+        own.set_stream(stream.cuda_stream)
+        n = 4096
+        with torch.cuda.stream(stream):
+            ones = torch.ones(n, n, device="cuda:0")
+            busy = ones
+            for _ in range(200):  # (ones @ ones = n everywhere: exact in fp32, the chain stays at ones)
+                busy = (busy @ ones) * (1.0 / n)
+        gen = own.load_genome(packed)
+        for parts in (1, 3):
+            own.set_debug(seed_parts=parts, seed_shared=1)
+            assert launches(search(own, gen, guides, want)) == parts
+        rows = gen.summarize(guides, 8, algorithm="seed")
+        assert rows.tobytes() == aggregate(want, len(guides), mit, ub).tobytes()
+        gen.close()
+        stream.synchronize()
+        assert bool((busy == 1.0).all())
+    finally:
+        stream.synchronize()
+        own.close()

@@ -130,10 +130,10 @@ class Timing(C.Structure):
                 ("genome_bytes", C.c_uint64), ("passes", C.c_uint32), ("algorithm", C.c_uint32),
                 ("sort_bytes", C.c_uint64), ("sort_levels", C.c_uint32), ("sort_bin_bits", C.c_uint32),
                 ("read_passes", C.c_uint32), ("sort_fallbacks", C.c_uint32), ("list_entries", C.c_uint64), ("seed_cut", C.c_uint32),
-                ("reserved", C.c_uint32)]
+                ("seed_layout", C.c_uint32)]
 
     def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class MultiTiming(C.Structure):

@@ -1802,6 +1802,7 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
         genome->sites = cnt[kCntSites];
         t.sites = cnt[kCntSites];
         t.pairs += cnt[kCntSites] * n_guides;
+        t.seed_layout = 0;
         f.n = cnt[kCntHits];
         genome->seen_rate[m] = (double)f.n / n_guides;
         if (f.n >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search: more than 2^32 hits in one scan pass (split the read set)");
@@ -1809,6 +1810,8 @@ int find_pass(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, ui
     } else {
         t.list_entries = list_total;
         t.seed_cut = sa.k_seg0 | (sa.k_seg1 << 4);
+        // the layout of the attempt that produced the records (after a lost-records rerun: one launch)
+        t.seed_layout = (seed_shared ? 1u : 0u) | (sa.group_out ? 2u : 0u) | (use_fill ? 4u : 0u) | (sa.reserve_log2 << 4) | (n_parts_k << 8);
         t.sites = genome->index_sites;
         t.pairs += cnt[kCntSites];
         t.genome_bytes += cnt[kCntVisited] * kVertWords * sizeof(uint32_t) / kSlicedSites;  // sites visited, 3.5 bytes each bit-sliced
