@@ -457,6 +457,91 @@ int vsc_guides_free(vsc_guides *guides);
 int vsc_hits_locate(vsc_hits *hits, const vsc_regions *regions, uint32_t *labels);
 int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *labels);
 /*
+ * Bulge-tolerant search: the sites at which Cas9 cuts although the target carries one or two extra bases (a DNA bulge) or
+ * lacks one or two (an RNA bulge) - what Cas-OFFinder and CRISPRitz report beside the substitution-only sites of vsc_search.
+ *
+ * READ    r[0..23), as the searches take it (vsc_pack_guide: non-ACGT becomes A).  r[0..20) is the protospacer, r[20..23) the
+ *         PAM letters; the PAM letters count towards the mismatches, exactly as in the plain search.
+ * SITE    budget m = max_mismatches in 0..8.  Site length L = 23 + d, d in {-2, -1, +1, +2}, limited by rna_max / dna_max in
+ *         0..2.  The site is c[p, p + L) of contig c; in read orientation s = c[p, p + L) on '+' and revcomp(c[p, p + L)) on '-'.
+ * The site (g, strand, c, p, d) is a hit iff all four of these hold:
+ *   1. p + L <= len(c).  The right-edge rule of the plain predicate is not applied.
+ *   2. s[L-2..L) is in {GG, GA} + {-P}: the PAM set of vsc_search_params.
+ *   3. No N (non-ACGT genome letter) appears anywhere in the L bases, the bulged bases included.
+ *   4. min_i nm(i) <= m, with nm(i) = the number of unequal pairs when
+ *        DNA bulge, b = d > 0, i in [1, 19]:        r[j] pairs s[j] for j < i and s[j + b] for i <= j < 23; s[i..i+b) is unpaired
+ *        RNA bulge, b = -d > 0, 1 <= i, i + b <= 19: r[j] pairs s[j] for j < i and s[j - b] for i + b <= j < 23; r[i..i+b) is unpaired
+ * RECORD  one per hit site: NM = min_i nm(i), index = the smallest i that reaches it.  d = 0 is vsc_search's business and is
+ *         never reported here.  A plain hit with NM <= m - 1 has bulged neighbours at index 1 (the site one base longer or
+ *         shorter at its 5' end pairs as the plain window does but for r[0]); they ARE reported, as Cas-OFFinder reports them.
+ * ORDER   ascending (guide, strand, contig, pos, d).  The bytes depend on the planes and the parameters only: every record is
+ *         written at a rank computed from counts (count pass, scan, write pass), nothing is appended through an atomic.
+ *
+ * params: max_mismatches and the PAM set as for vsc_search; algorithm must be VSC_ALGO_AUTO or VSC_ALGO_SCAN (the seed index is
+ * neither needed nor used; anything else: VSC_ERR_INVALID).  bulge_params: dna_max and rna_max both 0, or either above 2, or a
+ * non-zero reserved field: VSC_ERR_INVALID.  guide_batch = reads per round of the count / scan / write passes (0: 16; more
+ * than 64: 64) - it bounds the counter scratch (8 bytes per read of a round and 2 048 bases) and never changes the result.
+ * max_hits: 0 no cap; when there are more records the call returns VSC_ERR_RANGE, vsc_last_error names the count and nothing
+ * is returned (as vsc_guides_enumerate).  out == NULL: no record is allocated or written (rows only); rows == NULL: records
+ * only; both NULL: VSC_ERR_INVALID.  rows: host memory, n_guides entries - count[k][nm] = hits of the guide with class k
+ * (ascending d: RNA 2, RNA 1, DNA 1, DNA 2) and NM = nm.  n_guides == 0: VSC_OK, nothing is launched (*out = an empty result).
+ * A genome loaded as one shard reports the sites that START in its own words (one halo word covers the 25 bases); the records
+ * of all shards, merged by the order above, are the whole genome's.
+ * vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = PAM-valid N-free candidate sites examined (all
+ * enabled classes, both strands), pairs = site x read comparisons, passes = rounds; the sort, finalize and score fields 0.
+ */
+typedef struct {
+    uint32_t guide;  /* index of the read in input order */
+    uint32_t contig;
+    uint32_t pos;    /* 0-based start of the site's L bases on the forward genome */
+    uint32_t info;   /* bit 31 strand (1 = '-') | bit 12 kind (0 DNA, 1 RNA) | bits 10..11 size | bits 5..9 index | bits 0..4 NM */
+} vsc_bulge_hit;
+#define VSC_BULGE_STRAND(info) (((info) >> 31) & 1u)
+#define VSC_BULGE_KIND(info) (((info) >> 12) & 1u) /* VSC_BULGE_DNA / VSC_BULGE_RNA */
+#define VSC_BULGE_SIZE(info) (((info) >> 10) & 3u)
+#define VSC_BULGE_INDEX(info) (((info) >> 5) & 31u)
+#define VSC_BULGE_NM(info) ((info)&31u)
+#define VSC_BULGE_DNA 0u
+#define VSC_BULGE_RNA 1u
+/* d = site length - 23: +size for a DNA bulge, -size for an RNA bulge */
+#define VSC_BULGE_D(info) (VSC_BULGE_KIND(info) ? -(int)VSC_BULGE_SIZE(info) : (int)VSC_BULGE_SIZE(info))
+#define VSC_BULGE_INFO(strand, kind, size, index, nm) \
+    ((uint32_t)(strand) << 31 | (uint32_t)(kind) << 12 | (uint32_t)(size) << 10 | (uint32_t)(index) << 5 | (uint32_t)(nm))
+#define VSC_BULGE_CLASSES 4 /* rows of vsc_bulge_summary, ascending d: RNA 2, RNA 1, DNA 1, DNA 2 */
+typedef struct {
+    uint32_t dna_max, rna_max; /* 0..2 each, not both 0 */
+    uint32_t guide_batch;      /* 0: default */
+    uint32_t reserved;
+    uint64_t max_hits;         /* 0: no cap */
+} vsc_bulge_params;
+typedef struct {
+    uint32_t count[VSC_BULGE_CLASSES][VSC_MAX_MISMATCHES + 1];
+} vsc_bulge_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_bulge_hit) == 16, "vsc_bulge_hit layout");
+static_assert(sizeof(vsc_bulge_params) == 24, "vsc_bulge_params layout");
+static_assert(sizeof(vsc_bulge_summary) == 144, "vsc_bulge_summary layout");
+#else
+_Static_assert(sizeof(vsc_bulge_hit) == 16, "vsc_bulge_hit layout");
+_Static_assert(sizeof(vsc_bulge_params) == 24, "vsc_bulge_params layout");
+_Static_assert(sizeof(vsc_bulge_summary) == 144, "vsc_bulge_summary layout");
+#endif
+typedef struct vsc_bulge_hits vsc_bulge_hits;
+int vsc_search_bulges(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                      const vsc_search_params *params, const vsc_bulge_params *bulge_params, vsc_bulge_hits **out /* may be NULL */,
+                      vsc_bulge_summary *rows /* may be NULL */);
+uint64_t vsc_bulge_hits_count(const vsc_bulge_hits *hits);
+/* Host copy of the records (made on first use; valid until vsc_bulge_hits_free). */
+int vsc_bulge_hits_data(vsc_bulge_hits *hits, const vsc_bulge_hit **out);
+/* Device pointer (valid until vsc_bulge_hits_free); NULL when the result is empty. */
+const void *vsc_bulge_hits_data_dev(const vsc_bulge_hits *hits);
+int vsc_bulge_hits_free(vsc_bulge_hits *hits);
+/* The definition above for ONE read and ONE site in read orientation, on the host (no device needed): guide_code = a
+ * vsc_pack_guide code, site_text = the 23 + d letters of s (ACGT, any case), d in {-2, -1, +1, +2}.  *nm = min_i nm(i), *index
+ * = the smallest i that reaches it (either may be NULL).  It runs the function the kernels run.  A wrong d, a text of
+ * another length or a letter that is not ACGT (such a site is never a hit): VSC_ERR_INVALID. */
+int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t *nm, uint32_t *index);
+/*
  * Paired-nickase screen (Cas9 D10A double nickase, dimeric FokI-dCas9): a design of TWO guides cuts only where an off-target
  * of one guide and an off-target of the other lie close together on opposite strands.  Coordinates are vsc_hit's and
  * vsc_locus': pos = 0-based leftmost base of the 23-base window on the forward genome, strand 1 = '-'.  Two windows on the

@@ -72,6 +72,20 @@ class EnumParams(C.Structure):
 assert C.sizeof(EnumParams) == 24
 
 
+class BulgeParams(C.Structure):
+    """vsc_bulge_params (vsc_search_bulges): largest DNA / RNA bulge (0..2, not both 0), reads per round (0 = default), max_hits
+    (0 = no cap)."""
+    _fields_ = [("dna_max", C.c_uint32), ("rna_max", C.c_uint32), ("guide_batch", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_hits", C.c_uint64)]
+
+
+assert C.sizeof(BulgeParams) == 24
+# vsc_bulge_hit: pos = start of the site's 23 + d bases; info = strand << 31 | kind << 12 | size << 10 | index << 5 | NM
+BULGE_HIT_DTYPE = np.dtype([("guide", "<u4"), ("contig", "<u4"), ("pos", "<u4"), ("info", "<u4")])
+BULGE_DNA, BULGE_RNA = 0, 1
+BULGE_CLASSES = 4  # rows of vsc_bulge_summary, ascending d: RNA 2, RNA 1, DNA 1, DNA 2
+
+
 class PairParams(C.Structure):
     """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
     _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -237,6 +251,12 @@ SYMBOLS = [
     ("vsc_regions_locate", C.c_uint32, [_vp, C.c_uint32, C.c_uint32]),
     ("vsc_hits_locate", C.c_int, [_vp, _vp, _vp]),
     ("vsc_guides_locate", C.c_int, [_vp, _vp, _vp]),
+    ("vsc_search_bulges", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(BulgeParams), C.POINTER(_vp), _vp]),
+    ("vsc_bulge_hits_count", C.c_uint64, [_vp]),
+    ("vsc_bulge_hits_data", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_bulge_hits_data_dev", _vp, [_vp]),
+    ("vsc_bulge_hits_free", C.c_int, [_vp]),
+    ("vsc_bulge_align", C.c_int, [C.c_uint64, C.c_char_p, C.c_int, _u32p, _u32p]),
     ("vsc_loci_pairs", C.c_int, [_vp, C.c_uint64, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_guides_pairs", C.c_int, [_vp, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_hits_pairs", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(PairParams), _vp, _vp, _vp, C.c_uint64,

@@ -35,6 +35,31 @@ def unpack_guides(codes):
     return [row.tobytes().decode() for row in letters]
 
 
+BULGE_HIT_DTYPE = _lib.BULGE_HIT_DTYPE
+
+
+def unpack_bulge_info(info):
+    """The fields of vsc_bulge_hit.info (VSC_BULGE_* of the header), of one word or an array of them: a dict of strand (1 =
+    '-'), kind (0 DNA, 1 RNA), size, d (site length - 23: +size DNA, -size RNA), index and nm."""
+    w = np.asarray(info, dtype=np.uint32)
+    kind, size = (w >> np.uint32(12)) & np.uint32(1), (w >> np.uint32(10)) & np.uint32(3)
+    return {"strand": w >> np.uint32(31), "kind": kind, "size": size,
+            "d": np.where(kind == 1, -size.astype(np.int32), size.astype(np.int32)),
+            "index": (w >> np.uint32(5)) & np.uint32(31), "nm": w & np.uint32(31)}
+
+
+def bulge_align(read, site, d):
+    """vsc_bulge_align: (NM, index) of one 23-nt read against one site of 23 + d letters in read orientation, d in -2, -1, 1, 2 -
+    the definition of the bulge search on the host, by the function the kernels run.  No device is needed."""
+    r = read if isinstance(read, bytes) else read.encode()
+    s = site if isinstance(site, bytes) else site.encode()
+    if len(r) != READ_LEN:
+        raise ValueError("the read has length %d; a read is 23 nt (20 nt + PAM)" % len(r))
+    nm, index = C.c_uint32(), C.c_uint32()
+    check(lib().vsc_bulge_align(lib().vsc_pack_guide(r), s, int(d), C.byref(nm), C.byref(index)))
+    return int(nm.value), int(index.value)
+
+
 def _enum_params(pam, strands, gc, max_t_run, max_guides):
     """vsc_enum_params of enumerate_guides' arguments.  Only what cannot be put into the struct is refused here: the library
     checks the values (a PAM letter outside ACGT, gc bounds above 20, ... are VSC_ERR_INVALID there)."""
@@ -542,6 +567,36 @@ class Genome:
         h = C.c_void_p()
         check(lib().vsc_search(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(h)), self.ctx._h)
         return Hits(self, h, codes)
+
+    def search_bulges(self, guides, max_mismatches, dna=1, rna=1, extra_pam=None, max_hits=0, guide_batch=0, records=True,
+                      rows=True):
+        """vsc_search_bulges: the sites of 23 + d bases, d in -rna .. -1 and 1 .. dna, that pair with a guide within
+        max_mismatches when one or two bases of the site (DNA bulge) or of the guide (RNA bulge) stay unpaired.  The bulged
+        neighbours of plain hits are among them; d = 0 is search()'s.  Returns (BULGE_HIT_DTYPE records in ascending (guide,
+        strand, contig, pos, d) order | None, uint32 rows of shape (n, 4, 9) - hits by class (RNA 2, RNA 1, DNA 1, DNA 2) and
+        NM | None).  max_hits: 0 = no cap, else VSC_ERR_RANGE when there are more records; guide_batch never changes the result."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, ALGO_SCAN)
+        bp = _lib.BulgeParams(int(dna), int(rna), int(guide_batch), 0, int(max_hits))
+        L = lib()
+        h = C.c_void_p()
+        out_rows = np.zeros((len(codes), _lib.BULGE_CLASSES, 9), dtype=np.uint32) if rows else None
+        check(L.vsc_search_bulges(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(bp),
+                                  C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+        if not records:
+            return None, out_rows
+        try:
+            n = int(L.vsc_bulge_hits_count(h))
+            data = C.c_void_p()
+            check(L.vsc_bulge_hits_data(h, C.byref(data)), self.ctx._h)
+            if n == 0:
+                recs = np.zeros(0, dtype=BULGE_HIT_DTYPE)
+            else:
+                recs = np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy()
+        finally:
+            L.vsc_bulge_hits_free(h)
+        return recs, out_rows
 
     def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):
         """vsc_search_summary: per guide, the NM counts, the fixed-point MIT sum (units of 2^-24), the reference-UB count

@@ -65,6 +65,16 @@
 // pairId = guideA|guideB, guideA the '-' guide, sites = the paired off-target sites, minNmSum = the smallest sum of the two
 // hits' mismatches among them (- if none), ps<k> = sites with that sum.  -J does not combine with -v.  Without -J every other
 // output is what it was; the -T listing gains nothing.
+// -u DNA,RNA (e.g. -u 1,1; each 0 .. 2, not both 0) adds the BULGED sites (vsc_search_bulges): the sites one or two bases longer
+// (DNA bulge) or shorter (RNA bulge) than 23 that pair with the guide within -M when the extra bases of the site or of the guide
+// stay unpaired.  Every line gains, behind all other columns, bulgeCount and per enabled class in ascending site length -
+// br2 br1 bd1 bd2 = RNA bulge of 2, of 1, DNA bulge of 1, of 2 - the columns <class>mm0 .. <class>mm<M>.  The bulged neighbours of
+// a plain off-target (the same locus one base longer or shorter at its 5' end) are among them, as in Cas-OFFinder's output.
+// -U bulges.tsv (needs -u) lists the sites, in ascending (guide, strand, chrom, start, site length) order, under
+//   #guideId chrom start end strand kind size index mismatches sequence
+// kind = DNA | RNA, index = the read position in front of which the bulge lies (the smallest that gives the fewest mismatches),
+// sequence = the site's forward-genome bases.  -u runs on one device and does not combine with -v or -J.  Without -u every
+// output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -117,6 +127,9 @@ int main(int argc, char **argv)
         {'j', "pair-offset", "MIN,MAX: the nickase offset range of the guide pairs of -J (gap between the protospacers' PAM-distal ends, "
                              "negative: overlap; e.g. -4,20); required with -J", false},
         {'J', "pairs", "Path to the TSV file of the guide pairs and their paired off-target sites (.tsv/.txt); needs -j and -E or -B", false},
+        {'u', "bulges", "DNA,RNA: largest DNA and RNA bulge, 0 .. 2 each (e.g. 1,1): adds the columns bulgeCount and <class>mm0 .. <class>mm<M> "
+                        "of the bulged sites (one device; not with -v, -J)", false},
+        {'U', "bulge-hits", "Path to the TSV file of the bulged sites (.tsv/.txt); needs -u", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -378,8 +391,34 @@ int main(int argc, char **argv)
         }
     }
 
+    // -u / -U: the bulged sites
+    const bool bulged = opts[30].set;
+    const std::string bulges_path = opts[31].value;
+    vsc_bulge_params bp{};
+    if (bulged) {
+        const std::string &v = opts[30].value;
+        char *e1 = nullptr, *e2 = nullptr;
+        const long dna = std::strtol(v.c_str(), &e1, 10);
+        const long rna = (e1 != v.c_str() && *e1 == ',') ? std::strtol(e1 + 1, &e2, 10) : -1;
+        if (e1 == v.c_str() || *e1 != ',' || e2 == e1 + 1 || *e2 || dna < 0 || dna > 2 || rna < 0 || rna > 2 || (dna == 0 && rna == 0)) {
+            std::fprintf(stderr, "%s: -u takes DNA,RNA, the largest bulges, 0 .. 2 each and not both 0 (e.g. 1,1), not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        bp.dna_max = (uint32_t)dna;
+        bp.rna_max = (uint32_t)rna;
+        if (individual || pairing || devices.size() != 1) {
+            std::fprintf(stderr, "%s: -u searches the bulged sites on one device: it does not combine with -v, -J or a device list\n", argv[0]);
+            return 1;
+        }
+    }
+    if (opts[31].set && (!bulged || !has_extension(bulges_path, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: -U lists the bulged sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
+        return 1;
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_genome *genome = nullptr;
+    vsc_bulge_hits *bulge_hits = nullptr;
     vsc_genome *win_genome = nullptr;
     vsc_windows *windows = nullptr;
     vsc_variant_map *vmap = nullptr;
@@ -622,6 +661,14 @@ int main(int argc, char **argv)
                        : vsc_search_summary_classified(ctx, genome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data());
             if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
         }
+        std::vector<vsc_bulge_summary> bulge_rows(bulged ? codes.size() : 0);
+        if (bulged) {
+            st = vsc_search_bulges(ctx, genome, codes.data(), n_codes, &p, &bp, opts[31].set ? &bulge_hits : nullptr, bulge_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+        // the enabled bulge classes in the rows' order (ascending site length) and their column prefixes
+        static const char *const kBulgeClass[VSC_BULGE_CLASSES] = {"br2", "br1", "bd1", "bd2"};
+        const bool bulge_on[VSC_BULGE_CLASSES] = {bp.rna_max >= 2, bp.rna_max >= 1, bp.dna_max >= 1, bp.dna_max >= 2};
 
         std::string text = "#guideId\tguideSeq\tmitSpecScore\tofftargetCount\tonTargetFound";
         for (long k = 0; k <= mm; ++k) text += "\tmm" + std::to_string(k);
@@ -641,6 +688,11 @@ int main(int argc, char **argv)
             text += "\tindMitHitSum\tvarCount";
             for (long k = 0; k <= mm; ++k) text += "\tvmm" + std::to_string(k);
             text += "\tvarMitHitSum\tvarDuplicates";
+        }
+        if (bulged) {
+            text += "\tbulgeCount";
+            for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                for (long k = 0; bulge_on[c] && k <= mm; ++k) text += std::string("\t") + kBulgeClass[c] + "mm" + std::to_string(k);
         }
         text += '\n';
         char buf[64];
@@ -686,6 +738,15 @@ int main(int argc, char **argv)
                 for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(v.nm[k]);
                 std::snprintf(buf, sizeof buf, "%.6f", (double)v.mit_sum * 0x1p-24);
                 text += '\t' + std::string(buf) + '\t' + std::to_string(win_dups[i]);
+            }
+            if (bulged) {
+                const vsc_bulge_summary &b = bulge_rows[i];
+                uint64_t all = 0;
+                for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                    for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) all += b.count[c][k];
+                text += '\t' + std::to_string(all);
+                for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                    for (long k = 0; bulge_on[c] && k <= mm; ++k) text += '\t' + std::to_string(b.count[c][k]);
             }
             text += '\n';
         }
@@ -755,6 +816,29 @@ int main(int argc, char **argv)
             out.close();
             if (!out) throw std::runtime_error("Could not write the -T file.");
         }
+        if (bulge_hits) {
+            const vsc_bulge_hit *rec = nullptr;
+            if (vsc_bulge_hits_data(bulge_hits, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const uint64_t n = vsc_bulge_hits_count(bulge_hits);
+            std::string list = "#guideId\tchrom\tstart\tend\tstrand\tkind\tsize\tindex\tmismatches\tsequence\n";
+            std::string site;
+            for (uint64_t j = 0; j < n; ++j) {
+                const vsc_bulge_hit &h = rec[j];
+                const uint32_t len = (uint32_t)(VSC_READ_LEN + VSC_BULGE_D(h.info));
+                const std::string &name = ix.names[h.contig];
+                site.assign(len, 'N');
+                vsc_unpack_bases(ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs[h.contig].offset + h.pos, len, &site[0]);
+                list += ids[h.guide] + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' + std::to_string(h.pos) + '\t' +
+                        std::to_string(h.pos + len) + '\t' + (VSC_BULGE_STRAND(h.info) ? '-' : '+') + '\t' +
+                        (VSC_BULGE_KIND(h.info) == VSC_BULGE_RNA ? "RNA" : "DNA") + '\t' + std::to_string(VSC_BULGE_SIZE(h.info)) + '\t' +
+                        std::to_string(VSC_BULGE_INDEX(h.info)) + '\t' + std::to_string(VSC_BULGE_NM(h.info)) + '\t' + site + '\n';
+            }
+            std::ofstream out(bulges_path);
+            if (!out.is_open()) throw std::runtime_error("Could not open the -U path.");
+            out << list;
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the -U file.");
+        }
         if (pairing) {
             // the pairs among the guides' loci, then one search that keeps the records and the join over them on the device
             uint64_t n_found = 0;
@@ -802,6 +886,7 @@ int main(int argc, char **argv)
     }
     if (hits) vsc_hits_free(hits);
     if (pair_hits) vsc_hits_free(pair_hits);
+    vsc_bulge_hits_free(bulge_hits);
     vsc_guides_free(found);
     vsc_regions_free(regions);
     vsc_regions_free(targets);

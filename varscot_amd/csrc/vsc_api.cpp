@@ -1,7 +1,7 @@
 // vsc_api.cpp - the C ABI of include/varscot_hip.h: context, resident genome, search orchestration
 // (find -> summary / selection -> bin sort, one pass loop: run_search) and per-hit scoring.  Host C++ only; all device
 // work is in the kernel files - vsc_kernels.hip (scan, summary, selection, scoring, forest, merge), vsc_seed.hip (seed
-// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites).  No CPU implementation of the search exists in this library: without a HIP
+// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites), vsc_bulge.hip (bulge-tolerant search).  No CPU implementation of the search exists in this library: without a HIP
 // device every compute entry point fails with VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
 #include <atomic>
@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "vsc_bulge.h"
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
@@ -222,7 +223,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out})
+                         &ctx->pairs_out, &ctx->bulge_tabs})
         b->release();
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
@@ -2823,6 +2824,250 @@ int vsc_guides_free(vsc_guides *guides)
         guides->storage.release();
     }
     delete guides;
+    return VSC_OK;
+}
+
+// ---- bulge-tolerant search (kernels: vsc_bulge.hip) -----------------------------------------------------------
+// Per round of guide_batch reads: count pass (hits per (read, strand, tile) cell), sums per 64 cells, exclusive scan of the
+// sums, one 8-byte read-back (the round's records), write pass into the round's own buffer.  The rounds' buffers are
+// consecutive pieces of the result (the order starts with the read); with more than one round they are copied into one array.
+int vsc_search_bulges(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
+                      const vsc_bulge_params *bulge_params, vsc_bulge_hits **out, vsc_bulge_summary *rows)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (out) *out = nullptr;
+    ctx->err.clear();
+    if (!out && !rows) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: neither records nor rows are asked for");
+    if (!genome || !params || !bulge_params || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: null argument");
+    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: genome belongs to another context");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: max_mismatches must be 0..8");
+    if (params->algorithm != VSC_ALGO_AUTO && params->algorithm != VSC_ALGO_SCAN)
+        return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: algorithm must be VSC_ALGO_AUTO or VSC_ALGO_SCAN (no seed index is used)");
+    if (bulge_params->dna_max > 2 || bulge_params->rna_max > 2 || (bulge_params->dna_max == 0 && bulge_params->rna_max == 0))
+        return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: dna_max and rna_max must be 0..2 and not both 0");
+    if (bulge_params->reserved) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: reserved fields must be 0");
+    std::unique_ptr<vsc_bulge_hits, int (*)(vsc_bulge_hits *)> holder(nullptr, vsc_bulge_hits_free);
+    if (out) {
+        holder.reset(new (std::nothrow) vsc_bulge_hits());
+        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_bulges: out of host memory");
+        holder->ctx = ctx;
+        holder->host_valid = true;  // (empty until records are written)
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    t.algorithm = VSC_ALGO_SCAN;
+    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_bulge_summary));
+    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
+    if (n_guides == 0 || n_tiles == 0) {
+        t.pairs = 0;
+        ctx->timing = t;
+        if (out) *out = holder.release();
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    ScanArgs pams{};
+    fill_pam(pams, params);
+    BulgeArgs a{};
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.n_tiles = n_tiles;
+    a.max_mm = params->max_mismatches;
+    a.n_pam = pams.n_pam;
+    for (uint32_t i = 0; i < pams.n_pam; ++i) a.pam[i] = pams.pam[i];
+    a.dna_max = bulge_params->dna_max;
+    a.rna_max = bulge_params->rna_max;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+
+    const uint32_t batch = std::min(bulge_params->guide_batch ? std::min(bulge_params->guide_batch, kBulgeMaxBatch) : kBulgeDefaultBatch, n_guides);
+    // scratch, 256-byte aligned parts: [rows of all reads][site counter] | per round: [reads][counts][chunk sums][chunk offsets]
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
+    const uint64_t max_chunks = (max_cells + kBulgeChunk - 1) / kBulgeChunk;
+    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_bulges: counter table too large");
+    const size_t rows_bytes = up((size_t)n_guides * kBulgeRowWords * sizeof(uint32_t));
+    auto read_slots = [](uint32_t n) { return ((size_t)n + kBulgeUnroll - 1) / kBulgeUnroll * (kBulgeUnroll / 2) + kBulgeUnroll / 2; };  // uint4s: two reads each
+    const size_t reads_bytes = up(read_slots(batch) * sizeof(uint4));
+    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
+    VSC_HIP(ctx, ctx->bulge_tabs.ensure(rows_bytes + 256 + reads_bytes + count_bytes + sums_bytes + (size_t)(max_chunks + 1) * sizeof(unsigned long long)));
+    char *base = (char *)ctx->bulge_tabs.p;
+    uint32_t *d_rows = (uint32_t *)base;
+    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
+    uint4 *d_reads = (uint4 *)(base + rows_bytes + 256);
+    uint32_t *d_count = (uint32_t *)((char *)d_reads + reads_bytes);
+    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
+    unsigned long long *d_off = (unsigned long long *)((char *)d_sums + sums_bytes);
+    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
+    a.guides = d_reads;
+    a.count = d_count;
+    a.chunk_off = d_off;
+    a.sites = d_sites;
+    a.rows = rows ? d_rows : nullptr;
+
+    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
+    struct Release {
+        std::vector<DeviceBuf> &v;
+        ~Release()
+        {
+            for (auto &b : v) b.release();
+        }
+    } release{pieces};
+    std::vector<uint64_t> piece_n;
+    std::vector<uint4> reads;
+    unsigned long long total = 0, found = 0;
+    // the count pass of the round that starts at read g0 (and, for records, the offsets of its cells): found = its records
+    auto count_round = [&](uint32_t g0) -> int {
+        const uint32_t n = std::min(batch, n_guides - g0);
+        reads.assign(read_slots(n), make_uint4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < n; ++i) {
+            uint32_t h, l;
+            guide_planes(guides[g0 + i], &h, &l);
+            uint4 &r = reads[i / 2];
+            if (i & 1) r.z = h, r.w = l; else r.x = h, r.y = l;
+        }
+        VSC_HIP(ctx, hipMemcpyAsync(d_reads, reads.data(), reads.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+        a.n_guides = n;
+        a.guide_base = g0;
+        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
+        const uint64_t cells = (uint64_t)2 * n * n_tiles;
+        const uint32_t chunks = (uint32_t)((cells + kBulgeChunk - 1) / kBulgeChunk);
+        found = 0;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_bulge_count(a, ctx->n_cus, ctx->stream));
+        if (out) {
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
+            VSC_HIP(ctx, launch_enum_scan(d_sums, chunks, d_off, ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + chunks, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `reads` is reused by the next round)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        t.passes += 1;
+        total += found;
+        return VSC_OK;
+    };
+    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
+        int rc = count_round(g0);
+        if (rc != VSC_OK) return rc;
+        if (bulge_params->max_hits && total > bulge_params->max_hits) {
+            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
+            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
+                if ((rc = count_round(h0)) != VSC_OK) return rc;
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "vsc_search_bulges: %llu records exceed max_hits = %llu", total,
+                          (unsigned long long)bulge_params->max_hits);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        float ms = 0;
+        pieces.emplace_back();
+        piece_n.push_back(found);
+        a.records = nullptr;
+        a.n_records = found;
+        if (found) {
+            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_bulge_hit)));
+            a.records = (uint4 *)pieces.back().p;
+        }
+        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch_bulge_write(a, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        }
+    }
+    unsigned long long sites = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
+    if (rows)
+        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_bulge_summary), hipMemcpyDeviceToHost, ctx->stream));
+    if (out && total) {
+        if (pieces.size() == 1) {
+            holder->storage = pieces[0];
+            pieces[0] = DeviceBuf();
+        } else {
+            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_bulge_hit)));
+            size_t at = 0;
+            for (size_t i = 0; i < pieces.size(); ++i) {
+                if (piece_n[i])
+                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_bulge_hit),
+                                                hipMemcpyDeviceToDevice, ctx->stream));
+                at += (size_t)piece_n[i] * sizeof(vsc_bulge_hit);
+            }
+        }
+        holder->n = total;
+        holder->host_valid = false;
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows && !out)
+        for (uint32_t g = 0; g < n_guides; ++g)
+            for (uint32_t k = 0; k < kBulgeRowWords; ++k) total += (&rows[g].count[0][0])[k];
+    t.total_ms = t.scan_ms;
+    t.hits = total;
+    t.sites = sites;
+    t.pairs = sites * n_guides;
+    ctx->timing = t;
+    if (out) *out = holder.release();
+    return VSC_OK;
+    });
+}
+
+uint64_t vsc_bulge_hits_count(const vsc_bulge_hits *hits) { return hits ? hits->n : 0; }
+
+int vsc_bulge_hits_data(vsc_bulge_hits *hits, const vsc_bulge_hit **out)
+{
+    if (!hits || !out) return VSC_ERR_INVALID;
+    return guarded(hits->ctx, [&]() -> int {
+    if (!hits->host_valid) {
+        vsc_ctx *ctx = hits->ctx;
+        hits->host.resize(hits->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(hits->host.data(), hits->storage.p, hits->n * sizeof(vsc_bulge_hit), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hits->host_valid = true;
+    }
+    *out = hits->host.data();
+    return VSC_OK;
+    });
+}
+
+const void *vsc_bulge_hits_data_dev(const vsc_bulge_hits *hits) { return hits && hits->n ? hits->storage.p : nullptr; }
+
+int vsc_bulge_hits_free(vsc_bulge_hits *hits)
+{
+    if (!hits) return VSC_OK;
+    if (hits->ctx && hits->storage.p) {
+        (void)hipSetDevice(hits->ctx->device);
+        hits->storage.release();
+    }
+    delete hits;
+    return VSC_OK;
+}
+
+int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t *nm, uint32_t *index)
+{
+    if (!site_text || d < -2 || d > 2 || d == 0) return VSC_ERR_INVALID;
+    const size_t len = (size_t)(VSC_READ_LEN + d);
+    if (std::strlen(site_text) != len) return VSC_ERR_INVALID;
+    uint32_t sh = 0, sl = 0, rh, rl;
+    for (size_t j = 0; j < len; ++j) {
+        const int c = base_code(site_text[j]);
+        if (c > 3) return VSC_ERR_INVALID;
+        sh |= (uint32_t)(c >> 1) << j;
+        sl |= (uint32_t)(c & 1) << j;
+    }
+    guide_planes(guide_code, &rh, &rl);
+    uint32_t at = 0;
+    const uint32_t best = bulge_align(rh, rl, sh, sl, d, &at);
+    if (nm) *nm = best;
+    if (index) *index = at;
     return VSC_OK;
 }
 

@@ -136,6 +136,9 @@ struct vsc_ctx {
     // vsc_hits_pairs / vsc_guides_pairs: the call's tables (segment starts, pairs, their item offsets, excluded loci, rows),
     // the per-item counts with their exclusive scan, and the sites / pairs on their way to the host
     vsc::DeviceBuf pairs_tabs, pairs_items, pairs_out;
+    // vsc_search_bulges: the call's rows and site counter, then per round the reads' planes, the counts per (read, strand,
+    // tile) cell, their sums per 64 cells and the scan of those - guide_batch bounds it
+    vsc::DeviceBuf bulge_tabs;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -222,6 +225,15 @@ struct vsc_guides {
     uint64_t n = 0;
     std::vector<uint64_t> codes;
     std::vector<vsc_locus> loci;
+    bool host_valid = false;
+};
+
+// The records of vsc_search_bulges: one device array the object owns.
+struct vsc_bulge_hits {
+    vsc_ctx *ctx = nullptr;
+    vsc::DeviceBuf storage;
+    uint64_t n = 0;
+    std::vector<vsc_bulge_hit> host;
     bool host_valid = false;
 };
 
