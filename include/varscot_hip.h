@@ -542,6 +542,96 @@ int vsc_bulge_hits_free(vsc_bulge_hits *hits);
  * another length or a letter that is not ACGT (such a site is never a hit): VSC_ERR_INVALID. */
 int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t *nm, uint32_t *index);
 /*
+ * Pattern search: any PAM and any guide length of 16 .. 32 bases - SaCas9 (21-22 + NNGRRT), Cas12a (TTTV at the 5' end +
+ * 23-25), SpCas9-NG / SpRY (NGN, NRN), truncated guides, NRG as one PAM, degenerate letters in a guide.  The pattern / query
+ * model of Cas-OFFinder: an IUPAC pattern that the site must satisfy, IUPAC guides whose N positions are not compared, and a
+ * mismatch budget.
+ *
+ * LETTERS  The 15 IUPAC letters ACGT RYSWKM BDHV N, in any case, each as its set of bases.  Anything else, U included, gives
+ *          VSC_ERR_INVALID.  comp() of a letter is the letter of the complemented set.
+ * PATTERN  P[0..L), 16 <= L <= 32.  Every guide G[0..L) has the same length L.  Both are IUPAC.  A guide's N positions are the
+ *          ones that are not compared; for Cas-OFFinder-style queries these are the PAM positions.  A guide that spells its PAM
+ *          letters has them counted, exactly as the plain search counts r[20..23).
+ * SITE     (g, strand, c, p).  It is c[p, p + L) of contig c.  In read orientation, s = c[p, p + L) on '+' and
+ *          revcomp(c[p, p + L)) on '-'.
+ * HIT      The site is a hit iff all four hold:
+ *            1. p + L <= len(c).
+ *            2. There is no N in the L bases.  N here means a non-ACGT genome letter; the planes keep no ambiguity codes.
+ *            3. s[j] is in P[j] for every j.
+ *            4. NM = #{ j : s[j] is not in G[j] } <= m, with m in 0..VSC_MAX_MISMATCHES.
+ *          There is no right-edge rule.  A site that satisfies the pattern on both strands is reported on both.  This happens
+ *          with a palindromic pattern.
+ * RECORD   Five uint32_t, vsc_pattern_hit { guide, contig, pos, info, mask }, 20 bytes.  pos is the 0-based start on the
+ *          forward genome.  info = strand << 31 | NM (NM in the low 6 bits).  mask bit i is set when forward-genome window
+ *          position i is a mismatch.  This is vsc_hit's convention.  On '-' it is the read-orientation mask with bit j moved to
+ *          L-1-j.
+ * ROWS     vsc_pattern_summary { uint32_t count[VSC_MAX_MISMATCHES + 1]; } per guide, 36 bytes.
+ * ORDER    Ascending (guide, strand, contig, pos).  The bytes depend on the planes and the parameters only.  Every record is
+ *          written at a rank computed from counts.  Nothing is appended through an atomic and nothing is sorted.
+ *          vsc_guides_enumerate and vsc_search_bulges work the same way.
+ *
+ * vsc_search_pattern: pattern = L letters, guides = n_guides * L letters without terminators.  len outside 16..32, a letter
+ * that is no IUPAC letter, max_mismatches above 8, a non-zero reserved field or both outputs NULL: VSC_ERR_INVALID.
+ * guide_batch = guides per round of the count / scan / write passes (0: 16; more than 64: 64) - it bounds the counter scratch
+ * (8 bytes per guide of a round and 2 048 bases) and never changes the result.  max_hits: 0 no cap; when there are more records
+ * the call returns VSC_ERR_RANGE, vsc_last_error names the count and nothing is returned.  out == NULL: no record is allocated
+ * or written (rows only); rows == NULL: records only.  rows: host memory, n_guides entries.  n_guides == 0: VSC_OK, nothing is
+ * launched (*out = an empty result).  A genome loaded as one shard reports the sites that START in its own words (one halo word
+ * covers the 32 bases); the records of all shards, merged by the order above, are the whole genome's.  No seed index is used
+ * and none is needed; MIT scores, classifier rows, bulges and guide discovery are defined for 20 + NGG only and stay with
+ * their own calls.
+ * vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = candidates (sites that satisfy the pattern and hold
+ * no N, both strands), pairs = candidate x guide comparisons, passes = rounds; the sort, finalize and score fields 0.
+ */
+typedef struct {
+    uint32_t guide;  /* index of the guide in input order */
+    uint32_t contig;
+    uint32_t pos;    /* 0-based start of the site's L bases on the forward genome */
+    uint32_t info;   /* bit 31 strand (1 = '-') | bits 0..5 NM */
+    uint32_t mask;   /* bit i: forward-genome window position i is a mismatch */
+} vsc_pattern_hit;
+#define VSC_PATTERN_STRAND(info) (((info) >> 31) & 1u)
+#define VSC_PATTERN_NM(info) ((info)&63u)
+#define VSC_PATTERN_INFO(strand, nm) ((uint32_t)(strand) << 31 | (uint32_t)(nm))
+#define VSC_PATTERN_MIN_LEN 16
+#define VSC_PATTERN_MAX_LEN 32
+typedef struct {
+    uint32_t max_mismatches; /* 0..VSC_MAX_MISMATCHES */
+    uint32_t guide_batch;    /* 0: default */
+    uint64_t max_hits;       /* 0: no cap */
+    uint32_t reserved[2];
+} vsc_pattern_params;
+typedef struct {
+    uint32_t count[VSC_MAX_MISMATCHES + 1];
+} vsc_pattern_summary;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pattern_hit) == 20, "vsc_pattern_hit layout");
+static_assert(sizeof(vsc_pattern_params) == 24, "vsc_pattern_params layout");
+static_assert(sizeof(vsc_pattern_summary) == 36, "vsc_pattern_summary layout");
+#else
+_Static_assert(sizeof(vsc_pattern_hit) == 20, "vsc_pattern_hit layout");
+_Static_assert(sizeof(vsc_pattern_params) == 24, "vsc_pattern_params layout");
+_Static_assert(sizeof(vsc_pattern_summary) == 36, "vsc_pattern_summary layout");
+#endif
+typedef struct vsc_pattern_hits vsc_pattern_hits;
+int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides /* n_guides * len letters */,
+                       uint32_t n_guides, uint32_t len, const vsc_pattern_params *params, vsc_pattern_hits **out /* may be NULL */,
+                       vsc_pattern_summary *rows /* may be NULL */);
+uint64_t vsc_pattern_hits_count(const vsc_pattern_hits *hits);
+/* Host copy of the records (made on first use; valid until vsc_pattern_hits_free). */
+int vsc_pattern_hits_data(vsc_pattern_hits *hits, const vsc_pattern_hit **out);
+/* Device pointer (valid until vsc_pattern_hits_free); NULL when the result is empty. */
+const void *vsc_pattern_hits_data_dev(const vsc_pattern_hits *hits);
+int vsc_pattern_hits_free(vsc_pattern_hits *hits);
+/* Conditions 2 and 3 and the count of condition 4 for ONE guide and ONE site in read orientation, on the host (no device
+ * needed): pattern, guide and site_text = len letters each.  *hit = 1 when the site holds ACGT only and satisfies the pattern
+ * (the caller compares *nm with its budget), *nm = the mismatches against the guide, *mask = bit j set when s[j] is not in G[j]
+ * (read orientation; any of the three may be NULL).  A site letter outside ACGT makes the site no hit: *hit = 0, *nm = 0,
+ * *mask = 0.  It runs the function the kernels run.  len outside 16..32, a NULL text or a pattern / guide letter that is no
+ * IUPAC letter: VSC_ERR_INVALID. */
+int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm,
+                      uint32_t *mask);
+/*
  * Paired-nickase screen (Cas9 D10A double nickase, dimeric FokI-dCas9): a design of TWO guides cuts only where an off-target
  * of one guide and an off-target of the other lie close together on opposite strands.  Coordinates are vsc_hit's and
  * vsc_locus': pos = 0-based leftmost base of the 23-base window on the forward genome, strand 1 = '-'.  Two windows on the

@@ -86,6 +86,18 @@ BULGE_DNA, BULGE_RNA = 0, 1
 BULGE_CLASSES = 4  # rows of vsc_bulge_summary, ascending d: RNA 2, RNA 1, DNA 1, DNA 2
 
 
+class PatternParams(C.Structure):
+    """vsc_pattern_params (vsc_search_pattern): mismatch budget (0..8), guides per round (0 = default), max_hits (0 = no cap)."""
+    _fields_ = [("max_mismatches", C.c_uint32), ("guide_batch", C.c_uint32), ("max_hits", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(PatternParams) == 24
+# vsc_pattern_hit: pos = start of the site's L bases; info = strand << 31 | NM; mask bit i = forward-genome position i mismatches
+PATTERN_HIT_DTYPE = np.dtype([("guide", "<u4"), ("contig", "<u4"), ("pos", "<u4"), ("info", "<u4"), ("mask", "<u4")])
+assert PATTERN_HIT_DTYPE.itemsize == 20
+PATTERN_MIN_LEN, PATTERN_MAX_LEN = 16, 32
+
+
 class PairParams(C.Structure):
     """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
     _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -257,6 +269,12 @@ SYMBOLS = [
     ("vsc_bulge_hits_data_dev", _vp, [_vp]),
     ("vsc_bulge_hits_free", C.c_int, [_vp]),
     ("vsc_bulge_align", C.c_int, [C.c_uint64, C.c_char_p, C.c_int, _u32p, _u32p]),
+    ("vsc_search_pattern", C.c_int, [_vp, _vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(PatternParams), C.POINTER(_vp), _vp]),
+    ("vsc_pattern_hits_count", C.c_uint64, [_vp]),
+    ("vsc_pattern_hits_data", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_pattern_hits_data_dev", _vp, [_vp]),
+    ("vsc_pattern_hits_free", C.c_int, [_vp]),
+    ("vsc_pattern_match", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, _u32p, _u32p, _u32p]),
     ("vsc_loci_pairs", C.c_int, [_vp, C.c_uint64, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_guides_pairs", C.c_int, [_vp, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_hits_pairs", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(PairParams), _vp, _vp, _vp, C.c_uint64,

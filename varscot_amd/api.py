@@ -60,6 +60,51 @@ def bulge_align(read, site, d):
     return int(nm.value), int(index.value)
 
 
+PATTERN_HIT_DTYPE = _lib.PATTERN_HIT_DTYPE
+
+# Presets of search_pattern: name -> (PAM at the 5' end, protospacer length, PAM at the 3' end).  pattern_strings() makes the
+# pattern and the guide of a protospacer from a row; any other shape is two strings written by hand.
+PATTERNS = {
+    "SpCas9": ("", 20, "NGG"),
+    "SpCas9-NRG": ("", 20, "NRG"),
+    "SpCas9-NG": ("", 20, "NGN"),
+    "SaCas9": ("", 21, "NNGRRT"),
+    "Cas12a": ("TTTV", 23, ""),
+}
+
+
+def pattern_strings(preset, protospacer=None):
+    """(pattern, guide) of a row of PATTERNS (its name, or a (5' PAM, length, 3' PAM) tuple): the pattern is the PAM letters
+    around N x length, the guide the protospacer with N at the PAM positions - they are not compared, as in Cas-OFFinder.
+    Without a protospacer the guide is None."""
+    five, n, three = PATTERNS[preset] if isinstance(preset, str) else preset
+    pattern = five + "N" * n + three
+    if protospacer is None:
+        return pattern, None
+    if len(protospacer) != n:
+        raise ValueError("the protospacer has %d letters; this preset takes %d" % (len(protospacer), n))
+    return pattern, "N" * len(five) + protospacer + "N" * len(three)
+
+
+def unpack_pattern_info(info):
+    """The fields of vsc_pattern_hit.info (VSC_PATTERN_* of the header), of one word or an array of them: a dict of strand
+    (1 = '-') and nm."""
+    w = np.asarray(info, dtype=np.uint32)
+    return {"strand": w >> np.uint32(31), "nm": w & np.uint32(63)}
+
+
+def pattern_match(pattern, guide, site):
+    """vsc_pattern_match: (hit, nm, mask) of one site in read orientation under one pattern and one guide, all of one length
+    in 16..32 - hit = the site holds ACGT only and satisfies the pattern, nm and mask (bit j: site letter j is not in guide
+    letter j) = the compare the kernels run.  No device is needed."""
+    p, g, s = (x if isinstance(x, bytes) else x.encode() for x in (pattern, guide, site))
+    if not len(p) == len(g) == len(s):
+        raise ValueError("pattern, guide and site must have the same length (%d, %d, %d)" % (len(p), len(g), len(s)))
+    hit, nm, mask = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().vsc_pattern_match(p, g, s, len(p), C.byref(hit), C.byref(nm), C.byref(mask)))
+    return bool(hit.value), int(nm.value), int(mask.value)
+
+
 def _enum_params(pam, strands, gc, max_t_run, max_guides):
     """vsc_enum_params of enumerate_guides' arguments.  Only what cannot be put into the struct is refused here: the library
     checks the values (a PAM letter outside ACGT, gc bounds above 20, ... are VSC_ERR_INVALID there)."""
@@ -596,6 +641,37 @@ class Genome:
                 recs = np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy()
         finally:
             L.vsc_bulge_hits_free(h)
+        return recs, out_rows
+
+    def search_pattern(self, pattern, guides, max_mismatches, max_hits=0, guide_batch=0, records=True, rows=True):
+        """vsc_search_pattern: the sites of len(pattern) = 16..32 bases that satisfy the IUPAC pattern, hold no N and differ
+        from a guide in at most max_mismatches positions; a guide's N positions are not compared.  guides: strings of the
+        pattern's length (PATTERNS / pattern_strings make both from a protospacer).  Returns (PATTERN_HIT_DTYPE records in
+        ascending (guide, strand, contig, pos) order | None, uint32 rows of shape (n, 9) - hits by NM | None).  max_hits: 0 = no
+        cap, else VSC_ERR_RANGE when there are more records; guide_batch never changes the result."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+        for i, g in enumerate(gs):
+            if len(g) != len(p):
+                raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+        pp = _lib.PatternParams(int(max_mismatches), int(guide_batch), int(max_hits))
+        L = lib()
+        h = C.c_void_p()
+        out_rows = np.zeros((len(gs), 9), dtype=np.uint32) if rows else None
+        check(L.vsc_search_pattern(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp),
+                                   C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+        if not records:
+            return None, out_rows
+        try:
+            n = int(L.vsc_pattern_hits_count(h))
+            data = C.c_void_p()
+            check(L.vsc_pattern_hits_data(h, C.byref(data)), self.ctx._h)
+            if n == 0:
+                recs = np.zeros(0, dtype=PATTERN_HIT_DTYPE)
+            else:
+                recs = np.frombuffer((C.c_char * (n * 20)).from_address(data.value), dtype=PATTERN_HIT_DTYPE).copy()
+        finally:
+            L.vsc_pattern_hits_free(h)
         return recs, out_rows
 
     def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):

@@ -1,7 +1,7 @@
 // vsc_api.cpp - the C ABI of include/varscot_hip.h: context, resident genome, search orchestration
 // (find -> summary / selection -> bin sort, one pass loop: run_search) and per-hit scoring.  Host C++ only; all device
 // work is in the kernel files - vsc_kernels.hip (scan, summary, selection, scoring, forest, merge), vsc_seed.hip (seed
-// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites), vsc_bulge.hip (bulge-tolerant search).  No CPU implementation of the search exists in this library: without a HIP
+// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites), vsc_bulge.hip (bulge-tolerant search), vsc_pattern.hip (pattern search).  No CPU implementation of the search exists in this library: without a HIP
 // device every compute entry point fails with VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
 #include <atomic>
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vsc_bulge.h"
+#include "vsc_pattern.h"
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
@@ -223,7 +224,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs})
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs})
         b->release();
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
@@ -3068,6 +3069,267 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
     const uint32_t best = bulge_align(rh, rl, sh, sl, d, &at);
     if (nm) *nm = best;
     if (index) *index = at;
+    return VSC_OK;
+}
+
+// ---- pattern search (kernels: vsc_pattern.hip) ----------------------------------------------------------------
+// The rounds of vsc_search_bulges: count pass, sums, exclusive scan, one 8-byte read-back, write pass into the round's own
+// buffer; the rounds' buffers are consecutive pieces of the result.  The sums are taken twice - per 64 cells and per 64 of
+// those - so that the one-workgroup scan sees a 64th of the chunks (at 3 Gbp and 16 guides: 11 000 entries, not 730 000).
+int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
+                       const vsc_pattern_params *params, vsc_pattern_hits **out, vsc_pattern_summary *rows)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (out) *out = nullptr;
+    ctx->err.clear();
+    if (!out && !rows) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: neither records nor rows are asked for");
+    if (!genome || !params || !pattern || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: null argument");
+    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: the pattern must have 16..32 letters");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: max_mismatches must be 0..8");
+    if (params->reserved[0] || params->reserved[1]) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: reserved fields must be 0");
+    uint8_t sets[kPatMaxLen], rc_sets[kPatMaxLen];
+    if (!pattern_sets(pattern, len, sets)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: the pattern holds a letter that is no IUPAC letter");
+    PatternArgs a{};
+    pattern_front(sets, len, &a.front[0]);
+    pattern_revcomp(sets, len, rc_sets);
+    pattern_front(rc_sets, len, &a.front[1]);
+    // every guide as two uint4: its planes for '+', those of its reverse complement for '-'
+    std::vector<uint4> planes((size_t)2 * n_guides);
+    for (uint32_t g = 0; g < n_guides; ++g) {
+        if (!pattern_sets(guides + (size_t)g * len, len, sets)) {
+            char msg[120];
+            std::snprintf(msg, sizeof msg, "vsc_search_pattern: guide %u holds a letter that is no IUPAC letter", g);
+            return fail(ctx, VSC_ERR_INVALID, msg);
+        }
+        pattern_revcomp(sets, len, rc_sets);
+        const PatPlanes f = pattern_planes(sets, len), r = pattern_planes(rc_sets, len);
+        planes[2 * (size_t)g] = make_uint4(f.a, f.c, f.g, f.t);
+        planes[2 * (size_t)g + 1] = make_uint4(r.a, r.c, r.g, r.t);
+    }
+    std::unique_ptr<vsc_pattern_hits, int (*)(vsc_pattern_hits *)> holder(nullptr, vsc_pattern_hits_free);
+    if (out) {
+        holder.reset(new (std::nothrow) vsc_pattern_hits());
+        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_pattern: out of host memory");
+        holder->ctx = ctx;
+        holder->host_valid = true;  // (empty until records are written)
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    t.algorithm = VSC_ALGO_SCAN;
+    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_pattern_summary));
+    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
+    if (n_guides == 0 || n_tiles == 0) {
+        t.pairs = 0;
+        ctx->timing = t;
+        if (out) *out = holder.release();
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.n_tiles = n_tiles;
+    a.len = len;
+    a.max_mm = params->max_mismatches;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+
+    const uint32_t batch = std::min(params->guide_batch ? std::min(params->guide_batch, kPatMaxBatch) : kPatDefaultBatch, n_guides);
+    // scratch, 256-byte aligned parts: [rows of all guides][site counter] | per round: [guides][counts][chunk sums][group sums][group offsets]
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
+    const uint64_t max_chunks = (max_cells + kPatChunk - 1) / kPatChunk;
+    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_pattern: counter table too large");
+    const uint64_t max_groups = (max_chunks + kPatChunk - 1) / kPatChunk;  // the one-workgroup scan takes these, not the chunks
+    const size_t rows_bytes = up((size_t)n_guides * kPatRowWords * sizeof(uint32_t));
+    auto table_slots = [](uint32_t n) { return (n + kPatUnroll - 1) / kPatUnroll * kPatUnroll + kPatUnroll; };  // uint4s of one strand's table
+    const size_t guides_bytes = up((size_t)2 * table_slots(batch) * sizeof(uint4));
+    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
+    const size_t groups_bytes = up((size_t)max_groups * sizeof(uint32_t));
+    VSC_HIP(ctx, ctx->pattern_tabs.ensure(rows_bytes + 256 + guides_bytes + count_bytes + sums_bytes + groups_bytes +
+                                          (size_t)(max_groups + 1) * sizeof(unsigned long long)));
+    char *base = (char *)ctx->pattern_tabs.p;
+    uint32_t *d_rows = (uint32_t *)base;
+    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
+    uint4 *d_guides = (uint4 *)(base + rows_bytes + 256);
+    uint32_t *d_count = (uint32_t *)((char *)d_guides + guides_bytes);
+    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
+    uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
+    unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
+    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
+    a.guides = d_guides;
+    a.count = d_count;
+    a.chunk_sum = d_sums;
+    a.group_off = d_off;
+    a.rows = rows ? d_rows : nullptr;
+
+    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
+    struct Release {
+        std::vector<DeviceBuf> &v;
+        ~Release()
+        {
+            for (auto &b : v) b.release();
+        }
+    } release{pieces};
+    std::vector<uint64_t> piece_n;
+    std::vector<uint4> staged;
+    unsigned long long total = 0, found = 0;
+    // the count pass of the round that starts at guide g0 (and, for records, the offsets of its cells): found = its records
+    auto count_round = [&](uint32_t g0) -> int {
+        const uint32_t n = std::min(batch, n_guides - g0);
+        const uint32_t stride = table_slots(n);
+        staged.assign((size_t)2 * stride, make_uint4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < n; ++i) {
+            staged[i] = planes[2 * (size_t)(g0 + i)];
+            staged[stride + i] = planes[2 * (size_t)(g0 + i) + 1];
+        }
+        a.guide_stride = stride;
+        VSC_HIP(ctx, hipMemcpyAsync(d_guides, staged.data(), staged.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+        a.n_guides = n;
+        a.guide_base = g0;
+        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
+        const uint64_t cells = (uint64_t)2 * n * n_tiles;
+        const uint32_t chunks = (uint32_t)((cells + kPatChunk - 1) / kPatChunk), groups = (chunks + kPatChunk - 1) / kPatChunk;
+        found = 0;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_pattern_count(a, ctx->n_cus, ctx->stream));
+        if (out) {
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_sums, chunks, d_groups, ctx->stream));
+            VSC_HIP(ctx, launch_enum_scan(d_groups, groups, d_off, ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + groups, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `staged` is reused by the next round)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        t.passes += 1;
+        total += found;
+        return VSC_OK;
+    };
+    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
+        int rc = count_round(g0);
+        if (rc != VSC_OK) return rc;
+        if (params->max_hits && total > params->max_hits) {
+            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
+            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
+                if ((rc = count_round(h0)) != VSC_OK) return rc;
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "vsc_search_pattern: %llu records exceed max_hits = %llu", total, (unsigned long long)params->max_hits);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        float ms = 0;
+        pieces.emplace_back();
+        piece_n.push_back(found);
+        a.records = nullptr;
+        a.n_records = found;
+        if (found) {
+            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_pattern_hit)));
+            a.records = (uint32_t *)pieces.back().p;
+        }
+        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch_pattern_write(a, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        }
+    }
+    unsigned long long sites = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
+    if (rows)
+        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_pattern_summary), hipMemcpyDeviceToHost, ctx->stream));
+    if (out && total) {
+        if (pieces.size() == 1) {
+            holder->storage = pieces[0];
+            pieces[0] = DeviceBuf();
+        } else {
+            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_pattern_hit)));
+            size_t at = 0;
+            for (size_t i = 0; i < pieces.size(); ++i) {
+                if (piece_n[i])
+                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_pattern_hit),
+                                                hipMemcpyDeviceToDevice, ctx->stream));
+                at += (size_t)piece_n[i] * sizeof(vsc_pattern_hit);
+            }
+        }
+        holder->n = total;
+        holder->host_valid = false;
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows && !out)
+        for (uint32_t g = 0; g < n_guides; ++g)
+            for (uint32_t k = 0; k < kPatRowWords; ++k) total += rows[g].count[k];
+    t.total_ms = t.scan_ms;
+    t.hits = total;
+    t.sites = sites;
+    t.pairs = sites * n_guides;
+    ctx->timing = t;
+    if (out) *out = holder.release();
+    return VSC_OK;
+    });
+}
+
+uint64_t vsc_pattern_hits_count(const vsc_pattern_hits *hits) { return hits ? hits->n : 0; }
+
+int vsc_pattern_hits_data(vsc_pattern_hits *hits, const vsc_pattern_hit **out)
+{
+    if (!hits || !out) return VSC_ERR_INVALID;
+    return guarded(hits->ctx, [&]() -> int {
+    if (!hits->host_valid) {
+        vsc_ctx *ctx = hits->ctx;
+        hits->host.resize(hits->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(hits->host.data(), hits->storage.p, hits->n * sizeof(vsc_pattern_hit), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hits->host_valid = true;
+    }
+    *out = hits->host.data();
+    return VSC_OK;
+    });
+}
+
+const void *vsc_pattern_hits_data_dev(const vsc_pattern_hits *hits) { return hits && hits->n ? hits->storage.p : nullptr; }
+
+int vsc_pattern_hits_free(vsc_pattern_hits *hits)
+{
+    if (!hits) return VSC_OK;
+    if (hits->ctx && hits->storage.p) {
+        (void)hipSetDevice(hits->ctx->device);
+        hits->storage.release();
+    }
+    delete hits;
+    return VSC_OK;
+}
+
+int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm, uint32_t *mask)
+{
+    if (!pattern || !guide || !site_text || len < kPatMinLen || len > kPatMaxLen) return VSC_ERR_INVALID;
+    uint8_t p_sets[kPatMaxLen], g_sets[kPatMaxLen];
+    if (!pattern_sets(pattern, len, p_sets) || !pattern_sets(guide, len, g_sets)) return VSC_ERR_INVALID;
+    uint32_t sh = 0, sl = 0;
+    bool acgt = true;
+    for (uint32_t j = 0; j < len; ++j) {
+        const int c = base_code(site_text[j]);
+        if (c > 3) {
+            acgt = false;
+            break;
+        }
+        sh |= (uint32_t)(c >> 1) << j;
+        sl |= (uint32_t)(c & 1) << j;
+    }
+    const uint32_t x = acgt ? pattern_mismatch(sh, sl, pattern_planes(g_sets, len)) : 0u;
+    if (hit) *hit = acgt && pattern_mismatch(sh, sl, pattern_planes(p_sets, len)) == 0u;
+    if (nm) *nm = (uint32_t)__builtin_popcount(x);
+    if (mask) *mask = x;
     return VSC_OK;
 }
 

@@ -139,6 +139,9 @@ struct vsc_ctx {
     // vsc_search_bulges: the call's rows and site counter, then per round the reads' planes, the counts per (read, strand,
     // tile) cell, their sums per 64 cells and the scan of those - guide_batch bounds it
     vsc::DeviceBuf bulge_tabs;
+    // vsc_search_pattern: the same parts - rows and site counter, then per round the guides' planes, the counts per cell,
+    // their sums per 64 cells and the scan of those
+    vsc::DeviceBuf pattern_tabs;
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -234,6 +237,15 @@ struct vsc_bulge_hits {
     vsc::DeviceBuf storage;
     uint64_t n = 0;
     std::vector<vsc_bulge_hit> host;
+    bool host_valid = false;
+};
+
+// The records of vsc_search_pattern: one device array the object owns.
+struct vsc_pattern_hits {
+    vsc_ctx *ctx = nullptr;
+    vsc::DeviceBuf storage;
+    uint64_t n = 0;
+    std::vector<vsc_pattern_hit> host;
     bool host_valid = false;
 };
 

@@ -1,0 +1,336 @@
+// vsc_pattern.hip - the pattern search (vsc_search_pattern): every site of L = 16 .. 32 bases of the resident
+// planes that satisfies an IUPAC pattern, holds no N and lies within the budget of an IUPAC guide, as vsc_pattern_hit records in
+// ascending (guide, strand, contig, pos) order and / or as per-guide rows of counts by NM.
+//
+// The front end is enum_kernel's and bulge_front's: a tile of 2 048 site starts per wave step, one 32-start word of each plane
+// per lane plus its right neighbour - a site of 32 bases that starts at bit 31 ends at bit 62 of the pair.  Per strand one
+// start mask, 32 starts per instruction: no N in the L bases, and for every pattern position that is not N one funnel shift
+// of each plane and the position's truth table over (hi, lo).  The '-' strand is the reverse complement of the pattern as a
+// second forward pattern: nothing is bit-reversed anywhere.
+//
+// The candidate walk is scan_kernel's queue, not the lane walk of the bulge kernels: per strand the starts of the tile are
+// compacted into the wave's LDS queue (rank = lanes in front + order in the lane), and every step takes kPatSlots x 64 of them,
+// all lanes busy, against the round's guides; the guides' planes come through the constant address space (scalar loads), four
+// guides per load, the next four fetched while these are compared.  DESIGN 4.17 says why.
+//
+// The back end is count, scan, write, as vsc_bulge.hip's, with one count per CELL (guide of the round, strand, tile):
+//   pattern_count_kernel    hits per cell: the ballots of a guide's compares are added in lane g of the wave.
+//   bulge_chunk_sum_kernel twice + enum_scan_kernel (vsc_bulge.hip, vsc_enum.hip)  the cells' counts to sums per 64 cells, those
+//                           to sums per 64 x 64 cells, and only these - a 64th of the chunks - through the one-workgroup scan.
+//   pattern_write_kernel    only the tiles with a cell that is not empty are visited again, and of those only the live cells;
+//                           every hit goes to  group offset + chunks before it in the group + cells before it in the chunk +
+//                           hits of earlier steps + lanes in front.  The rows come from this pass.
+// No record is placed through an atomic and nothing is sorted: the bytes depend on the planes and the parameters only.
+#include "vsc_internal.h"
+#include "vsc_device.h"
+#include "vsc_pattern.h"
+
+namespace vsc {
+
+namespace {
+
+constexpr uint32_t kPatQueue = kTileBases;  // every start of a tile can be a candidate (a pattern of N only)
+
+// The wave's LDS: the tile's words of both planes (65 each: the last lane's right neighbour) and the queue of starts.
+struct PatLds {
+    uint32_t h[kTileWords + 2], l[kTileWords + 2];
+    uint16_t q[kPatQueue];  // lane << 5 | bit, ascending
+    uint32_t row[16];       // write pass: the cell's hits by NM
+};
+
+// The start mask of one strand: bit b = the site that starts at bit b of the lane's word satisfies the table.
+__device__ __forceinline__ uint32_t pattern_starts(const PatFront &f, uint32_t H0, uint32_t H1, uint32_t L0, uint32_t L1)
+{
+    uint32_t ok = ~0u;
+    for (uint32_t i = 0; i < f.n; ++i) {
+        const uint32_t e = f.ent[i], j = e & 31u;  // wave-uniform
+        const uint32_t h = funnel(H1, H0, j), l = funnel(L1, L0, j);
+        const uint32_t tA = 0u - ((e >> 8) & 1u), tC = 0u - ((e >> 9) & 1u), tG = 0u - ((e >> 10) & 1u), tT = 0u - ((e >> 11) & 1u);
+        ok &= (~h & ~l & tA) | (~h & l & tC) | (h & ~l & tG) | (h & l & tT);
+    }
+    return ok;
+}
+
+// The tile's words into LDS and the two start masks.
+__device__ __forceinline__ void pattern_tile(const PatternArgs &a, uint32_t tile, uint32_t lane, PatLds &s, uint32_t *mf, uint32_t *mr)
+{
+    const size_t wi = (size_t)tile * kTileWords + lane;  // (< n_tiles * 64, and the planes are padded by kPadWords)
+    const uint32_t H0 = a.hi[wi], H1 = a.hi[wi + 1];
+    const uint32_t L0 = a.lo[wi], L1 = a.lo[wi + 1];
+    const uint32_t N0 = a.nm[wi], N1 = a.nm[wi + 1];
+    uint64_t nn = ((uint64_t)N1 << 32) | N0;
+    nn |= nn >> 1;
+    nn |= nn >> 2;
+    nn |= nn >> 4;
+    nn |= nn >> 8;  // bit i covers positions i .. i+15
+    const uint32_t clean = ~(uint32_t)(nn | nn >> (a.len - kPatMinLen));  // no N in positions i .. i+L-1
+    *mf = pattern_starts(a.front[0], H0, H1, L0, L1) & clean;
+    *mr = pattern_starts(a.front[1], H0, H1, L0, L1) & clean;
+    s.h[lane] = H0;
+    s.l[lane] = L0;
+    if (lane == kWave - 1) {
+        s.h[kWave] = H1;
+        s.l[kWave] = L1;
+    }
+}
+
+// exclusive prefix of v over the lanes of the wave; *total = the wave's sum (enum_kernel's)
+__device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t lane, uint32_t *total)
+{
+    uint32_t s = v;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)s, d, kWave);
+        if (lane >= (uint32_t)d) s += o;
+    }
+    *total = uniform((uint32_t)__shfl((int)s, kWave - 1, kWave));
+    return s - v;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, kWave);
+    return v;
+}
+
+// The starts of mask m into the queue, in ascending order over the wave; returns how many there are.  The hand-offs before
+// (the planes, the queue's last readers) and after are the caller's.
+__device__ __forceinline__ uint32_t pattern_enqueue(PatLds &s, uint32_t m, uint32_t lane)
+{
+    uint32_t total;
+    uint32_t at = wave_exclusive((uint32_t)__popc(m), lane, &total);
+    for (; m; m &= m - 1u) s.q[at++] = (uint16_t)(lane << 5 | (uint32_t)__builtin_ctz(m));  // (at < 2 048: one entry per start)
+    return total;
+}
+
+// the L (and more) bases from queue entry e on, on the forward genome
+__device__ __forceinline__ void pattern_site(const PatLds &s, uint32_t e, uint32_t *wh, uint32_t *wl)
+{
+    const uint32_t src = e >> 5, b = e & 31u;  // (src <= 63: src + 1 <= 64 is the last lane's right neighbour)
+    *wh = funnel(s.h[src + 1], s.h[src], b);
+    *wl = funnel(s.l[src + 1], s.l[src], b);
+}
+
+__device__ __forceinline__ PatPlanes planes_of(v4u v) { return PatPlanes{v.x, v.y, v.z, v.w}; }
+
+typedef uint32_t v16u __attribute__((ext_vector_type(16)));
+typedef const __attribute__((address_space(4))) v16u *const_v16u_ptr;
+
+// One step of the count pass: kSlots x 64 queued sites from `base` on against every guide of the round; lane g adds the hits
+// of guide g to cnt.  An instance per number of slots (kPatSlots of them) instead of a test per slot and guide: the last step
+// of a tile is as cheap per pair as a full one.
+template <uint32_t kSlots>
+__device__ __forceinline__ void pattern_count_step(const PatLds &s, const_v16u_ptr gq, uint32_t n_guides, uint32_t m,
+                                                   uint32_t base, uint32_t total, uint32_t lane, uint32_t &cnt)
+{
+    uint32_t wh[kSlots], wl[kSlots], dead[kSlots];
+#pragma unroll
+    for (uint32_t j = 0; j < kSlots; ++j) {
+        const uint32_t idx = base + j * kWave + lane;
+        const bool live = idx < total;
+        pattern_site(s, live ? s.q[idx] : 0u, &wh[j], &wl[j]);
+        dead[j] = live ? 0u : 33u;  // added to the popcount (v_bcnt's own addend): an empty slot is over every budget
+    }
+    // four guides per scalar load (64 bytes), the next four fetched while these are compared: a wave waits for the scalar
+    // cache once per four guides, and the table ends with four spare guides
+    v16u next = gq[0];
+    for (uint32_t g = 0; g < n_guides; g += kPatUnroll) {
+        const v16u cur = next;
+        next = gq[g / kPatUnroll + 1u];
+#pragma unroll
+        for (uint32_t u = 0; u < kPatUnroll; ++u) {
+            const PatPlanes planes{cur[4 * u], cur[4 * u + 1], cur[4 * u + 2], cur[4 * u + 3]};
+            uint32_t hits = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < kSlots; ++j) {
+                const uint32_t nm = (uint32_t)__popc(pattern_mismatch(wh[j], wl[j], planes)) + dead[j];
+                hits += (uint32_t)__popcll(__ballot(nm <= m));
+            }
+            if (lane == g + u) cnt += hits;  // (a guide that pads the last four is all zero: it allows nothing and never hits)
+        }
+    }
+}
+
+// tiles [*t0, *t1) of wave `w` of `n_waves`: runs of consecutive tiles, so that the cells a wave stores lie side by side
+__device__ __forceinline__ void pattern_tile_run(uint32_t n_tiles, uint32_t w, uint32_t n_waves, uint32_t *t0, uint32_t *t1)
+{
+    const uint32_t per = (n_tiles + n_waves - 1u) / n_waves;
+    const uint64_t first = (uint64_t)w * per;
+    *t0 = first < n_tiles ? (uint32_t)first : n_tiles;
+    *t1 = first + per < n_tiles ? (uint32_t)(first + per) : n_tiles;
+}
+
+}  // namespace
+
+// ---- count pass --------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_count_kernel(const PatternArgs a)
+{
+    __shared__ PatLds s_lds[kWavesPerGroup];
+    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    PatLds &s = s_lds[wave];
+    uint32_t t0, t1;
+    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    const uint32_t m = a.max_mm;
+    unsigned long long sites = 0;
+    for (uint32_t tile = t0; tile < t1; ++tile) {
+        uint32_t mask[2];
+        wave_sync();  // (the last tile's readers of the planes and the queue are done)
+        pattern_tile(a, tile, lane, s, &mask[0], &mask[1]);
+        uint32_t cnt[2] = {0, 0};  // lane g: the hits of guide g of the round, per strand
+#pragma unroll
+        for (uint32_t strand = 0; strand < 2; ++strand) {
+            if (strand) wave_sync();  // (the '+' steps have read the queue)
+            const uint32_t total = pattern_enqueue(s, mask[strand], lane);
+            wave_sync();
+            sites += total;
+            const const_v16u_ptr gq = (const_v16u_ptr)(uintptr_t)(a.guides + strand * a.guide_stride);
+            for (uint32_t base = 0; base < total; base += kPatSlots * kWave) {
+                const uint32_t left = (total - base + kWave - 1u) / kWave;  // wave-uniform: steps of 64 sites that are left
+                if (left >= 4u) pattern_count_step<4>(s, gq, a.n_guides, m, base, total, lane, cnt[strand]);
+                else if (left == 3u) pattern_count_step<3>(s, gq, a.n_guides, m, base, total, lane, cnt[strand]);
+                else if (left == 2u) pattern_count_step<2>(s, gq, a.n_guides, m, base, total, lane, cnt[strand]);
+                else pattern_count_step<1>(s, gq, a.n_guides, m, base, total, lane, cnt[strand]);
+            }
+        }
+        // the tile's cells: (guide, strand) of the round -> count[(2 g + strand) * n_tiles + tile]
+        if (lane < a.n_guides) {
+            a.count[(size_t)(2u * lane) * a.n_tiles + tile] = cnt[0];
+            a.count[(size_t)(2u * lane + 1u) * a.n_tiles + tile] = cnt[1];
+        }
+    }
+    if (lane == 0 && sites) atomicAdd(a.sites, sites);
+}
+
+// ---- write pass --------------------------------------------------------------------------------------------------------
+namespace {
+
+// hits of all cells before `cell`: the offset of its group of 64 chunks + the chunks of the group in front of its own + the
+// cells of the chunk in front of it (two loads per lane)
+__device__ __forceinline__ unsigned long long pattern_cell_offset(const PatternArgs &a, unsigned long long cell, uint32_t lane)
+{
+    const unsigned long long chunk = cell / kPatChunk, group = chunk / kPatChunk;
+    const unsigned long long first_chunk = group * kPatChunk, first_cell = chunk * kPatChunk;
+    const uint32_t chunks = wave_sum(lane < (uint32_t)(chunk - first_chunk) ? a.chunk_sum[first_chunk + lane] : 0u);
+    const uint32_t cells = wave_sum(lane < (uint32_t)(cell - first_cell) ? a.count[first_cell + lane] : 0u);
+    return a.group_off[group] + chunks + cells;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(const PatternArgs a)
+{
+    __shared__ PatLds s_lds[kWavesPerGroup];
+    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    PatLds &s = s_lds[wave];
+    if (lane < 16u) s.row[lane] = 0;
+    uint32_t t0, t1;
+    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
+    const uint32_t m = a.max_mm;
+    uint32_t c_id = 0, c_off = 1, c_end = 0;  // the contig of the lane's last hit: [c_off, c_end) in global positions (empty at first)
+    for (uint32_t tile = t0; tile < t1; ++tile) {
+        // which cells of the round have a hit in this tile: lane l looks at cell l (guide l / 2, strand l & 1), then at 64 + l
+        const uint32_t n_cells = 2u * a.n_guides;
+        const uint64_t live_lo = __ballot(lane < n_cells && a.count[(size_t)lane * a.n_tiles + tile] != 0);
+        uint64_t live_hi = 0;
+        if (n_cells > (uint32_t)kWave) live_hi = __ballot(kWave + lane < n_cells && a.count[(size_t)(kWave + lane) * a.n_tiles + tile] != 0);
+        if ((live_lo | live_hi) == 0) continue;
+        uint32_t mask[2];
+        wave_sync();  // (the last tile's readers of the planes and the queue are done)
+        pattern_tile(a, tile, lane, s, &mask[0], &mask[1]);
+        const uint32_t tile_pos = a.first_pos + tile * (uint32_t)kTileBases;
+        for (uint32_t strand = 0; strand < 2; ++strand) {
+            const uint64_t odd = 0xAAAAAAAAAAAAAAAAull;
+            const uint64_t sel = strand ? odd : odd >> 1;
+            if (((live_lo | live_hi) & sel) == 0) continue;  // wave-uniform: no guide has a hit on this strand
+            wave_sync();  // (the '+' steps have read the queue)
+            const uint32_t total = pattern_enqueue(s, mask[strand], lane);
+            wave_sync();
+            for (uint32_t g = 0; g < a.n_guides; ++g) {
+                const uint64_t word = g < 32u ? live_lo : live_hi;
+                if (((word >> (2u * (g & 31u) + strand)) & 1u) == 0) continue;  // wave-uniform
+                const PatPlanes planes = planes_of(gp[strand * a.guide_stride + g]);
+                const unsigned long long cell = (unsigned long long)(2u * g + strand) * a.n_tiles + tile;
+                unsigned long long at = a.records ? pattern_cell_offset(a, cell, lane) : 0ull;
+                for (uint32_t base = 0; base < total; base += kWave) {
+                    const uint32_t idx = base + lane;
+                    const bool live = idx < total;
+                    const uint32_t e = live ? s.q[idx] : 0u;
+                    uint32_t wh, wl;
+                    pattern_site(s, e, &wh, &wl);
+                    const uint32_t x = pattern_mismatch(wh, wl, planes);  // the mismatches at forward-genome positions
+                    const uint32_t nm = (uint32_t)__popc(x);
+                    const bool hit = live && nm <= m;
+                    const uint64_t hits = __ballot(hit);
+                    if (hits == 0) continue;
+                    if (hit) {
+                        if (a.rows) atomicAdd(&s.row[nm], 1u);
+                        if (a.records) {
+                            const uint32_t pos = tile_pos + e;  // (e = lane << 5 | bit = the start's offset in the tile)
+                            if (pos >= c_end || pos < c_off) {  // the last contig that starts at or before pos (an N-free site lies inside one contig)
+                                uint32_t lo = 0, hi = a.n_contigs;
+                                while (lo < hi) {
+                                    const uint32_t mid = (lo + hi) >> 1;
+                                    if (a.contig_off[mid] <= pos) lo = mid + 1; else hi = mid;
+                                }
+                                c_id = lo ? lo - 1u : 0u;
+                                c_off = a.contig_off[c_id];
+                                c_end = a.contig_end[c_id];
+                            }
+                            const unsigned long long r = at + lanes_below(hits);
+                            // (r < n_records whenever both passes see the same planes: the test keeps a write inside the result if not)
+                            if (r < a.n_records) {
+                                uint32_t *rec = a.records + r * kPatRecordWords;
+                                rec[0] = a.guide_base + g;
+                                rec[1] = c_id;
+                                rec[2] = pos - c_off;
+                                rec[3] = strand << 31 | nm;
+                                rec[4] = x;
+                            }
+                        }
+                    }
+                    at += (uint32_t)__popcll(hits);
+                }
+                if (a.rows) {
+                    wave_sync();
+                    const uint32_t v = lane < kPatRowWords ? s.row[lane] : 0u;
+                    if (v) {
+                        atomicAdd(&a.rows[(size_t)(a.guide_base + g) * kPatRowWords + lane], v);
+                        s.row[lane] = 0;
+                    }
+                    wave_sync();
+                }
+            }
+        }
+    }
+}
+
+// ---- launches ----------------------------------------------------------------------------------------------------------
+namespace {
+
+// 8 workgroups of 4 waves per CU fill every SIMD's 8 wave slots (8 x 19 KB of LDS); fewer when the tiles do not need them
+dim3 pattern_grid(uint32_t n_tiles, int n_cus)
+{
+    const uint32_t want = (n_tiles + kWavesPerGroup - 1) / kWavesPerGroup;
+    const uint32_t cap = (uint32_t)(n_cus > 0 ? n_cus : 256) * 8u;
+    return dim3(want < cap ? want : cap);
+}
+
+}  // namespace
+
+hipError_t launch_pattern_count(const PatternArgs &args, int n_cus, hipStream_t stream)
+{
+    if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
+    hipLaunchKernelGGL(pattern_count_kernel, pattern_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_pattern_write(const PatternArgs &args, int n_cus, hipStream_t stream)
+{
+    if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
+    hipLaunchKernelGGL(pattern_write_kernel, pattern_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    return hipGetLastError();
+}
+
+}  // namespace vsc
