@@ -578,8 +578,8 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
  * or written (rows only); rows == NULL: records only.  rows: host memory, n_guides entries.  n_guides == 0: VSC_OK, nothing is
  * launched (*out = an empty result).  A genome loaded as one shard reports the sites that START in its own words (one halo word
  * covers the 32 bases); the records of all shards, merged by the order above, are the whole genome's.  No seed index is used
- * and none is needed; MIT scores, classifier rows, bulges and guide discovery are defined for 20 + NGG only and stay with
- * their own calls.
+ * and none is needed; MIT scores, classifier rows and bulges are defined for 20 + NGG only and stay with their own calls.
+ * The guides of a pattern are found by vsc_guides_enumerate_pattern (below).
  * vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = candidates (sites that satisfy the pattern and hold
  * no N, both strands), pairs = candidate x guide comparisons, passes = rounds; the sort, finalize and score fields 0.
  */
@@ -631,6 +631,83 @@ int vsc_pattern_hits_free(vsc_pattern_hits *hits);
  * IUPAC letter: VSC_ERR_INVALID. */
 int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm,
                       uint32_t *mask);
+/*
+ * Pattern guide discovery: which guides of ANY nuclease does a target contain?  vsc_guides_enumerate for a pattern - the
+ * beginning of the route that vsc_search_pattern continues: "every Cas12a guide in these exons with its off-target counts" is
+ * this call, vsc_pattern_guide_text and vsc_search_pattern (rows only) on one resident genome.
+ *
+ * PATTERN    P[0..L), 16 <= L <= 32, IUPAC, exactly as vsc_search_pattern takes it (same letters, same refusals).
+ * PROTOSP.   a range [a, a + k) of read positions, 1 <= k, a + k <= L: the part of the site that is the guide proper
+ *            (SaCas9: a = 0, k = 21 of L = 27; Cas12a: a = 4, k = 23 of L = 27).  The filters look at it and nothing else.
+ * CANDIDATE  (strand, c, p): the site c[p, p + L) of the forward genome with p + L <= len(c) (no right-edge rule), no non-ACGT
+ *            genome letter in it, and s[j] in P[j] for every j, where s = c[p, p + L) on '+' and revcomp(c[p, p + L)) on '-'
+ *            (conditions 1-3 of vsc_search_pattern's HIT).  A site that satisfies the pattern on both strands is two
+ *            candidates.  On '-' the protospacer is forward window positions [L - a - k, L - a).
+ * KEPT       strands  0 both, 1 '+' only, 2 '-' only.
+ *            gc       #G/C in s[a, a + k) lies in [gc_min, gc_max]; gc_max == 0: no upper bound (a zeroed struct filters
+ *                     nothing).  Either > k, or gc_min > gc_max != 0: VSC_ERR_INVALID.
+ *            t run    the longest run of T inside s[a, a + k) is <= max_t_run (0: no limit).  Letters outside the protospacer
+ *                     neither start nor extend a run: TTT at the protospacer's end followed by a T of the PAM is a run of 3.
+ *            targets  NULL: every site of the genome or shard.  Else n vsc_interval (0-based half-open, any order, nested and
+ *                     overlapping as they come, end clipped to the contig, empty ones dropped; n == 0: nothing is kept) and a
+ *                     rule applied to the L-base site:
+ *                       VSC_REGION_OVERLAP  p < end and p + L > start for some interval
+ *                       VSC_REGION_INSIDE   start <= p and p + L <= end for ONE interval (a site across the seam of two
+ *                                           abutting intervals is not inside)
+ *                     contig >= n_contigs, start > end, a non-zero reserved field, an unknown rule: VSC_ERR_INVALID.
+ *            max_guides  0: no cap; more kept: VSC_ERR_RANGE, the count in vsc_last_error, nothing returned.
+ * ORDER      ascending (contig, pos), '+' before '-' at one position.  A shard enumerates the sites that START in its own
+ *            words; shard results concatenate in shard order to the whole genome's.  The bytes depend on the planes and
+ *            the parameters only: count pass, scan, write pass - no append atomic, no sort.
+ * RECORD     code: uint64_t, hi plane << 32 | lo plane of s in READ orientation, bit j = s[j], A 00 C 01 G 10 T 11 as (hi, lo),
+ *            bits from L on zero.  locus: vsc_locus { c, p, strand, 0 } - pos is the site's start on the forward genome, which
+ *            is vsc_pattern_hit.pos of the hit that vsc_search_pattern reports for this guide at NM 0.
+ *
+ * For L = 23, P = N x 21 + GG and the protospacer (0, 20) this is vsc_guides_enumerate's definition with pam "GG", filter by
+ * filter, and with targets vsc_regions_contains on the same intervals under the same rule.  The targets are a plain array, not
+ * a vsc_regions: that object's class table is built for 23-base windows.  Here the intervals become sorted, disjoint ranges
+ * of site starts ([start - L + 1, end) / [start, end - L] per interval, clipped to the contig, then the union), which holds
+ * for any L; only the tiles that meet a range are visited.
+ * vsc_guides_enumerate_pattern: pattern = len letters.  A NULL argument but `targets`, len outside 16..32, a letter that is no
+ * IUPAC letter, a protospacer outside the pattern or empty, strands > 2, the gc refusals above, a non-zero reserved field or
+ * n_targets != 0 with targets == NULL: VSC_ERR_INVALID.  The result owns its two arrays until vsc_pattern_guides_free;
+ * scratch comes from the context's pools (vsc_ctx_release_scratch gives it back).
+ * vsc_ctx_timing afterwards, as vsc_guides_enumerate: scan_ms = total_ms = the kernels, sites = candidates kept,
+ * genome_bytes = plane bytes the kernels read, everything else 0.
+ * vsc_pattern_guide_text (host only, no device needed): the letters of one code into out[0 .. len), no terminator - inside
+ * the protospacer the site's letter; outside it N when spell == 0 (the Cas-OFFinder query form: those positions are not
+ * compared by vsc_search_pattern) and the site's letter when spell == 1.  Upper-case ACGT.  The output is exactly one guide
+ * of vsc_search_pattern's `guides` argument.  len outside 16..32, a protospacer outside the pattern or empty, spell > 1, a
+ * code with a bit from len on set in either plane, out == NULL: VSC_ERR_INVALID.
+ * Not provided: a vsc_multi_* entry point (the pattern search has none either; shard results concatenate, see ORDER),
+ * labels (which target interval a candidate lies in), guide pairs, and MIT or classifier scores for patterns - those stay
+ * defined for 20 + NGG with vsc_guides_enumerate's family.
+ */
+typedef struct {
+    uint8_t ps_start, ps_len; /* the protospacer [ps_start, ps_start + ps_len) in read positions */
+    uint8_t strands, gc_min, gc_max, max_t_run;
+    uint16_t reserved0;
+    uint32_t rule; /* VSC_REGION_OVERLAP / VSC_REGION_INSIDE: how `targets` are applied (ignored when targets == NULL) */
+    uint32_t reserved1;
+    uint64_t max_guides;
+    uint32_t reserved[2];
+} vsc_pattern_enum_params;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pattern_enum_params) == 32, "vsc_pattern_enum_params layout");
+#else
+_Static_assert(sizeof(vsc_pattern_enum_params) == 32, "vsc_pattern_enum_params layout");
+#endif
+typedef struct vsc_pattern_guides vsc_pattern_guides;
+int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, uint32_t len,
+                                 const vsc_pattern_enum_params *params, const vsc_interval *targets /* may be NULL */,
+                                 uint64_t n_targets, vsc_pattern_guides **out);
+uint64_t vsc_pattern_guides_count(const vsc_pattern_guides *guides);
+/* Host copies of the two arrays (made on first use; valid until vsc_pattern_guides_free).  Either pointer may be NULL. */
+int vsc_pattern_guides_data(vsc_pattern_guides *guides, const uint64_t **codes, const vsc_locus **loci);
+/* Device pointers (valid until vsc_pattern_guides_free); NULL when the result is empty. */
+int vsc_pattern_guides_data_dev(const vsc_pattern_guides *guides, const void **codes_dev, const void **loci_dev);
+int vsc_pattern_guides_free(vsc_pattern_guides *guides);
+int vsc_pattern_guide_text(uint64_t code, uint32_t len, uint32_t ps_start, uint32_t ps_len, uint32_t spell, char *out /* len letters */);
 /*
  * Paired-nickase screen (Cas9 D10A double nickase, dimeric FokI-dCas9): a design of TWO guides cuts only where an off-target
  * of one guide and an off-target of the other lie close together on opposite strands.  Coordinates are vsc_hit's and

@@ -49,8 +49,15 @@ int vsc_ctx_create_masked(int device_id, const uint32_t *cu_mask, uint32_t n_wor
 /* Host-side lap times of vsc_search and vsc_windows_build on stderr (process-wide; 0 = off). */
 void vsc_debug_set_host_timing(int on);
 
+/* The host half of vsc_guides_enumerate_pattern's target test on its own (no device needed): the intervals as the sorted,
+ * disjoint ranges of site starts the kernels look up, in GLOBAL positions (contig offset + position), for sites of `len`
+ * bases.  ranges: 2 * capacity words, [lo, hi) per range; *n_ranges = how many there are (nothing is written when there are
+ * more than capacity: VSC_ERR_RANGE).  VSC_ERR_INVALID as the call refuses. */
+int vsc_debug_pattern_target_ranges(const vsc_contig *contigs, uint32_t n_contigs, const vsc_interval *iv, uint64_t n, uint32_t rule,
+                                    uint32_t len, uint32_t *ranges, uint64_t capacity, uint64_t *n_ranges);
+
 typedef struct {
-    int32_t rccl;              /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
+    int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */
     const char *rccl_library;  /* NULL: librccl.so.1 / librccl.so; else the one name to dlopen (tests: a name that fails) */
 } vsc_multi_debug_params;

@@ -98,6 +98,18 @@ assert PATTERN_HIT_DTYPE.itemsize == 20
 PATTERN_MIN_LEN, PATTERN_MAX_LEN = 16, 32
 
 
+class PatternEnumParams(C.Structure):
+    """vsc_pattern_enum_params (vsc_guides_enumerate_pattern): the protospacer [ps_start, ps_start + ps_len) in read positions,
+    strands (0 both, 1 '+', 2 '-'), GC bounds and largest T run over the protospacer (0 = no upper bound / no limit), the rule
+    the targets are applied with (REGION_OVERLAP / REGION_INSIDE), max_guides (0 = no cap)."""
+    _fields_ = [("ps_start", C.c_uint8), ("ps_len", C.c_uint8), ("strands", C.c_uint8), ("gc_min", C.c_uint8), ("gc_max", C.c_uint8),
+                ("max_t_run", C.c_uint8), ("reserved0", C.c_uint16), ("rule", C.c_uint32), ("reserved1", C.c_uint32),
+                ("max_guides", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(PatternEnumParams) == 32
+
+
 class PairParams(C.Structure):
     """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
     _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -275,6 +287,12 @@ SYMBOLS = [
     ("vsc_pattern_hits_data_dev", _vp, [_vp]),
     ("vsc_pattern_hits_free", C.c_int, [_vp]),
     ("vsc_pattern_match", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, _u32p, _u32p, _u32p]),
+    ("vsc_guides_enumerate_pattern", C.c_int, [_vp, _vp, C.c_char_p, C.c_uint32, C.POINTER(PatternEnumParams), _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_count", C.c_uint64, [_vp]),
+    ("vsc_pattern_guides_data", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("vsc_pattern_guides_data_dev", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("vsc_pattern_guides_free", C.c_int, [_vp]),
+    ("vsc_pattern_guide_text", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p]),
     ("vsc_loci_pairs", C.c_int, [_vp, C.c_uint64, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_guides_pairs", C.c_int, [_vp, C.POINTER(PairParams), _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_hits_pairs", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.POINTER(PairParams), _vp, _vp, _vp, C.c_uint64,
@@ -345,6 +363,7 @@ DEBUG_SYMBOLS = [
     ("vsc_ctx_get_debug_params", C.c_int, [_vp, C.POINTER(DebugParams)]),
     ("vsc_debug_set_host_timing", None, [C.c_int]),
     ("vsc_ctx_create_masked", C.c_int, [C.c_int, _vp, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_debug_pattern_target_ranges", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_multi_create_debug", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(MultiDebugParams), C.POINTER(_vp)]),
 ]
 

@@ -86,6 +86,66 @@ def pattern_strings(preset, protospacer=None):
     return pattern, "N" * len(five) + protospacer + "N" * len(three)
 
 
+def pattern_protospacer(preset):
+    """(start, length) of the protospacer in the pattern of a row of PATTERNS (its name, or a (5' PAM, length, 3' PAM) tuple):
+    what enumerate_pattern takes as `protospacer`."""
+    five, n, _ = PATTERNS[preset] if isinstance(preset, str) else preset
+    return len(five), n
+
+
+def pattern_guide_text(code, length, protospacer, spell_pam=False):
+    """vsc_pattern_guide_text: the `length` letters of one code of enumerate_pattern - the site's letters inside the
+    protospacer (start, length), outside it N (the query form: not compared by search_pattern) or, with spell_pam, the site's
+    letters.  No device is needed."""
+    out = C.create_string_buffer(int(length))
+    check(lib().vsc_pattern_guide_text(int(code), int(length), int(protospacer[0]), int(protospacer[1]), 1 if spell_pam else 0, out))
+    return out.raw.decode()
+
+
+class PatternGuides:
+    """The candidates of Genome.enumerate_pattern: codes (uint64: hi plane << 32 | lo plane of the site in read orientation),
+    loci (LOCUS_DTYPE, pos = the site's start on the forward genome) in ascending (contig, pos), '+' before '-'."""
+
+    def __init__(self, pattern, protospacer, codes, loci):
+        self.pattern, self.protospacer, self.codes, self.loci = pattern, (int(protospacer[0]), int(protospacer[1])), codes, loci
+
+    def __len__(self):
+        return len(self.codes)
+
+    def text(self, spell_pam=False):
+        """The guides as strings that search_pattern takes: N outside the protospacer, or the site's letters there too."""
+        return [pattern_guide_text(c, len(self.pattern), self.protospacer, spell_pam) for c in self.codes]
+
+
+def _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides):
+    """vsc_pattern_enum_params of enumerate_pattern's arguments.  Only what cannot be put into the struct is refused here: the
+    library checks the values."""
+    if rule not in ("overlap", "inside", 0, 1):
+        raise ValueError("rule must be 'overlap' or 'inside'")
+    if strands not in ("both", "+", "-", 0, 1, 2, 3):
+        raise ValueError("strands must be 'both', '+' or '-'")
+    fields = [int(protospacer[0]), int(protospacer[1]), {"both": 0, "+": 1, "-": 2}.get(strands, strands), int(gc[0]), int(gc[1]), int(max_t_run)]
+    if any(not 0 <= v <= 255 for v in fields):
+        raise ValueError("protospacer, gc and max_t_run must lie in 0..255")
+    p = _lib.PatternEnumParams()
+    p.ps_start, p.ps_len, p.strands, p.gc_min, p.gc_max, p.max_t_run = fields
+    p.rule = {"overlap": _lib.REGION_OVERLAP, "inside": _lib.REGION_INSIDE}.get(rule, rule)
+    p.max_guides = int(max_guides)
+    return p
+
+
+def _intervals(targets):
+    """INTERVAL_DTYPE array of (contig, start, end) triples (or of such an array), as Regions takes them."""
+    if isinstance(targets, np.ndarray) and targets.dtype == _lib.INTERVAL_DTYPE:
+        return np.ascontiguousarray(targets)
+    a = np.asarray(targets, dtype=np.int64).reshape(-1, 3)
+    if len(a) and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError("interval fields must fit 32 unsigned bits")
+    iv = np.zeros(len(a), dtype=_lib.INTERVAL_DTYPE)
+    iv["contig"], iv["start"], iv["end"] = a[:, 0], a[:, 1], a[:, 2]
+    return iv
+
+
 def unpack_pattern_info(info):
     """The fields of vsc_pattern_hit.info (VSC_PATTERN_* of the header), of one word or an array of them: a dict of strand
     (1 = '-') and nm."""
@@ -673,6 +733,47 @@ class Genome:
         finally:
             L.vsc_pattern_hits_free(h)
         return recs, out_rows
+
+    def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
+                          max_guides=0, params=None):
+        """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
+        letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
+        (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
+        than max_t_run T in it (0: no limit).  targets: None (everywhere) or (contig, start, end) triples / an INTERVAL_DTYPE
+        array, applied to the whole site under `rule` ("overlap" / "inside"); an empty list keeps nothing.  Returns a
+        PatternGuides (.codes, .loci, .text()) in ascending (contig, pos), '+' before '-'.  More than max_guides (0: no cap)
+        candidates raise VarscotError -34.  params: a PatternEnumParams to pass as it is (tests)."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
+        iv = None if targets is None else _intervals(targets)
+        # (an empty target set is a pointer that is not NULL with n = 0)
+        iv_ptr = None if iv is None else ptr(iv if len(iv) else np.zeros(1, dtype=_lib.INTERVAL_DTYPE))
+        L = lib()
+        h = C.c_void_p()
+        check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
+                                             C.byref(h)), self.ctx._h)
+        try:
+            n = int(L.vsc_pattern_guides_count(h))
+            pc, pl = C.c_void_p(), C.c_void_p()
+            check(L.vsc_pattern_guides_data(h, C.byref(pc), C.byref(pl)), self.ctx._h)
+            if n == 0:
+                codes, loci = np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=_lib.LOCUS_DTYPE)
+            else:
+                codes = np.frombuffer((C.c_char * (n * 8)).from_address(pc.value), dtype=np.uint64).copy()
+                loci = np.frombuffer((C.c_char * (n * 16)).from_address(pl.value), dtype=_lib.LOCUS_DTYPE).copy()
+        finally:
+            L.vsc_pattern_guides_free(h)
+        return PatternGuides(p.decode(), protospacer, codes, loci)
+
+    def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, **filters):
+        """Every guide of `targets` under a pattern, with its off-target counts: enumerate_pattern(pattern, protospacer,
+        targets, **filters) followed by search_pattern (rows only) of the guides in query form on the same resident genome.
+        Returns (PatternGuides, uint32 rows of shape (n, 9)); count[0] is reduced by one for the guide's own locus, which is
+        always a hit at NM 0 (the query form has N outside the protospacer)."""
+        found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
+        _, rows = self.search_pattern(pattern, found.text(), max_mismatches, guide_batch=guide_batch, records=False)
+        rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
+        return found, rows
 
     def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):
         """vsc_search_summary: per guide, the NM counts, the fixed-point MIT sum (units of 2^-24), the reference-UB count

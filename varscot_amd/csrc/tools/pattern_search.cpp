@@ -1,12 +1,17 @@
 // pattern_search - off-targets of any nuclease and guide shape over a packed genome: an IUPAC pattern the site must satisfy
 // (the PAM, at either end or both), IUPAC guides of the pattern's length (N = not compared) and a mismatch budget - the
 // pattern / query model of Cas-OFFinder.  Per-guide counts by mismatches (-O) and / or the hits themselves (-T).
+// With -E the guides are not given but found: every site of the genome, or of the -B targets, that satisfies the pattern
+// (vsc_guides_enumerate_pattern), filtered over the -p protospacer, written as a TSV of guide, contig, pos and strand - and,
+// with -M and -O, screened in the same run (the design: every guide of the targets with its off-target counts).
 // Host C++ only: the search runs in libvarscot_hip.so (vsc_search_pattern); there is no CPU search here.  Every argument is
 // checked before a device is opened.
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <fstream>
+#include <map>
+#include <sstream>
 
 #include "vsc_host.hpp"
 
@@ -24,6 +29,40 @@ bool iupac(char c)
 // chrom and guideId are the first word of the FASTA header, as guide_summary prints them
 std::string first_word(const std::string &s) { return s.substr(0, s.find_first_of(" \t")); }
 
+// "a,b" as two integers in 0..255
+bool two_numbers(const std::string &s, long *a, long *b)
+{
+    char *end = nullptr;
+    *a = std::strtol(s.c_str(), &end, 10);
+    if (end == s.c_str() || *end != ',') return false;
+    const char *second = end + 1;
+    *b = std::strtol(second, &end, 10);
+    return end != second && !*end && *a >= 0 && *a <= 255 && *b >= 0 && *b <= 255;
+}
+
+// the -B intervals: BED3+, chrom = first word of a contig name
+std::vector<vsc_interval> read_targets(const std::string &path, const PackedIndex &ix)
+{
+    std::map<std::string, uint32_t> by_chrom;
+    for (size_t c = ix.names.size(); c-- > 0;) by_chrom[first_word(ix.names[c])] = (uint32_t)c;
+    std::ifstream bed(path);
+    if (!bed) throw std::runtime_error("Could not open the -B file.");
+    std::vector<vsc_interval> iv;
+    std::string line;
+    while (std::getline(bed, line)) {
+        if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+        std::istringstream is(line);
+        std::string chr;
+        unsigned long long start = 0, stop = 0;
+        if (!(is >> chr >> start >> stop)) throw std::runtime_error("-B: not a BED line: '" + line + "'");
+        auto it = by_chrom.find(chr);
+        if (it == by_chrom.end()) throw std::runtime_error("-B: no sequence '" + chr + "' in the genome");
+        if (start > stop || stop > 0xFFFFFFFFull) throw std::runtime_error("-B: bad interval in '" + line + "'");
+        iv.push_back(vsc_interval{it->second, (uint32_t)start, (uint32_t)stop, 0u});
+    }
+    return iv;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -31,17 +70,33 @@ int main(int argc, char **argv)
     std::vector<Option> opts = {
         {'i', "index", "Prefix of the packed genome (bidir_index -I)", true},
         {'q', "pattern", "IUPAC pattern of 16..32 letters that a site must satisfy, e.g. NNNNNNNNNNNNNNNNNNNNNGRRT", true},
-        {'R', "guides", "FASTA of the guides: IUPAC records of the pattern's length, N = position not compared", true},
-        {'M', "mismatches", "Number of allowed mismatches (0..8)", true},
+        {'R', "guides", "FASTA of the guides: IUPAC records of the pattern's length, N = position not compared", false},
+        {'M', "mismatches", "Number of allowed mismatches (0..8)", false},
         {'D', "device", "HIP device index (default 0)", false},
         {'O', "output", "Summary TSV: #guideId guideSeq offtargetCount mm0 .. mm<M>", false},
         {'T', "hits", "Hits TSV: #guideId chrom start end strand mismatches mismatchPositions sequence", false},
+        {'E', "enumerate", "Guides TSV: #guide chrom pos strand - the guides are FOUND in the genome instead of read from -R "
+                           "(needs -p; with -M and -O they are screened in the same run, their own locus not counted)", false},
+        {'B', "targets", "With -E: target intervals (.bed, BED3+); without, the whole genome is enumerated", false},
+        {'p', "protospacer", "With -E: START,LENGTH of the protospacer in the pattern (SaCas9 0,21; Cas12a 4,23); the filters look at it", false},
+        {'r', "rule", "With -B: overlap (default; the site shares a base with a target) or inside (it lies in one target)", false},
+        {'s', "strands", "With -E: both (default), + or -", false},
+        {'g', "gc", "With -E: MIN,MAX number of G/C in the protospacer (MAX 0: no upper bound)", false},
+        {'t', "t-run", "With -E: longest run of T allowed in the protospacer (0: no limit)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
-                              "the pattern and differ from a guide in at most -M compared positions. Give -O, -T or both.");
+                              "the pattern and differ from a guide in at most -M compared positions. Give -O, -T or both. "
+                              "With -E the guides are enumerated from the genome or the -B targets.");
     if (pr) return pr == 1;
     const std::string prefix = opts[0].value, pattern = opts[1].value, guides_path = opts[2].value;
+    const bool enumerate = opts[7].set;
+    if (!enumerate)
+        for (int k : {2, 3})
+            if (!opts[k].set) {
+                std::fprintf(stderr, "%s: Missing value for option: -%c\n", argv[0], opts[k].short_name);
+                return 1;
+            }
     if (pattern.size() < VSC_PATTERN_MIN_LEN || pattern.size() > VSC_PATTERN_MAX_LEN) {
         std::fprintf(stderr, "%s: the pattern must have 16..32 letters, '%s' has %zu\n", argv[0], pattern.c_str(), pattern.size());
         return 1;
@@ -51,24 +106,88 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "%s: '%c' in the pattern '%s' is no IUPAC letter\n", argv[0], c, pattern.c_str());
             return 1;
         }
-    if (!has_extension(guides_path, {"fa", "fasta"}) || (opts[5].set && !has_extension(opts[5].value, {"tsv", "txt"})) ||
+    if ((opts[2].set && !has_extension(guides_path, {"fa", "fasta"})) || (opts[5].set && !has_extension(opts[5].value, {"tsv", "txt"})) ||
         (opts[6].set && !has_extension(opts[6].value, {"tsv", "txt"}))) {
         std::fprintf(stderr, "%s: the guides must be a .fa/.fasta file, the outputs .tsv/.txt files\n", argv[0]);
         return 1;
     }
-    if (!opts[5].set && !opts[6].set) {
+    if (!enumerate && !opts[5].set && !opts[6].set) {
         std::fprintf(stderr, "%s: give -O, -T or both\n", argv[0]);
         return 1;
     }
-    char *end = nullptr;
-    const long mm = std::strtol(opts[3].value.c_str(), &end, 10);
-    if (end == opts[3].value.c_str() || *end) {
-        std::fprintf(stderr, "%s: the given value '%s' cannot be casted to integer\n", argv[0], opts[3].value.c_str());
-        return 1;
+    vsc_pattern_enum_params ep{};
+    if (!enumerate) {
+        for (int k = 8; k <= 13; ++k)
+            if (opts[k].set) {
+                std::fprintf(stderr, "%s: -%c belongs to the enumeration: give -E\n", argv[0], opts[k].short_name);
+                return 1;
+            }
+    } else {
+        if (opts[2].set || opts[6].set) {
+            std::fprintf(stderr, "%s: -E finds the guides in the genome: -R and -T cannot be given with it\n", argv[0]);
+            return 1;
+        }
+        if (opts[3].set != opts[5].set) {
+            std::fprintf(stderr, "%s: with -E, -M and -O go together (the screened rows) or are both left out\n", argv[0]);
+            return 1;
+        }
+        if (!has_extension(opts[7].value, {"tsv", "txt"}) || (opts[8].set && !has_extension(opts[8].value, {"bed"}))) {
+            std::fprintf(stderr, "%s: the -E output must be a .tsv/.txt file, the -B targets a .bed file\n", argv[0]);
+            return 1;
+        }
+        long a = 0, k = 0;
+        if (!opts[9].set || !two_numbers(opts[9].value, &a, &k) || k < 1 || a + k > (long)pattern.size()) {
+            std::fprintf(stderr, "%s: -E needs -p START,LENGTH with 1 <= LENGTH and START + LENGTH <= %zu, the pattern's length\n", argv[0], pattern.size());
+            return 1;
+        }
+        ep.ps_start = (uint8_t)a;
+        ep.ps_len = (uint8_t)k;
+        if (opts[10].set) {
+            if (!opts[8].set || (opts[10].value != "overlap" && opts[10].value != "inside")) {
+                std::fprintf(stderr, "%s: -r takes overlap or inside and needs -B\n", argv[0]);
+                return 1;
+            }
+            ep.rule = opts[10].value == "inside" ? VSC_REGION_INSIDE : VSC_REGION_OVERLAP;
+        }
+        if (opts[11].set) {
+            const std::string &s = opts[11].value;
+            if (s != "both" && s != "+" && s != "-") {
+                std::fprintf(stderr, "%s: -s takes both, + or -\n", argv[0]);
+                return 1;
+            }
+            ep.strands = s == "both" ? 0 : (s == "+" ? 1 : 2);
+        }
+        if (opts[12].set) {
+            long lo = 0, hi = 0;
+            if (!two_numbers(opts[12].value, &lo, &hi) || lo > k || hi > k || (hi && lo > hi)) {
+                std::fprintf(stderr, "%s: -g takes MIN,MAX with MIN <= MAX <= %ld, the protospacer's length (MAX 0: no upper bound)\n", argv[0], k);
+                return 1;
+            }
+            ep.gc_min = (uint8_t)lo;
+            ep.gc_max = (uint8_t)hi;
+        }
+        if (opts[13].set) {
+            char *e = nullptr;
+            const long run = std::strtol(opts[13].value.c_str(), &e, 10);
+            if (e == opts[13].value.c_str() || *e || run < 0 || run > 255) {
+                std::fprintf(stderr, "%s: -t takes a run length of 0..255\n", argv[0]);
+                return 1;
+            }
+            ep.max_t_run = (uint8_t)run;
+        }
     }
-    if (mm < 0 || mm > VSC_MAX_MISMATCHES) {
-        std::fprintf(stderr, "Error: Maximum number of mismatches must lie between 0 and 8.\n");
-        return 1;
+    char *end = nullptr;
+    long mm = 0;
+    if (opts[3].set) {
+        mm = std::strtol(opts[3].value.c_str(), &end, 10);
+        if (end == opts[3].value.c_str() || *end) {
+            std::fprintf(stderr, "%s: the given value '%s' cannot be casted to integer\n", argv[0], opts[3].value.c_str());
+            return 1;
+        }
+        if (mm < 0 || mm > VSC_MAX_MISMATCHES) {
+            std::fprintf(stderr, "Error: Maximum number of mismatches must lie between 0 and 8.\n");
+            return 1;
+        }
     }
     long device = 0;
     if (opts[4].set) {
@@ -82,20 +201,26 @@ int main(int argc, char **argv)
     vsc_ctx *ctx = nullptr;
     vsc_genome *genome = nullptr;
     vsc_pattern_hits *hits = nullptr;
+    vsc_pattern_guides *found = nullptr;
     int rc = 1;
     try {
-        const auto guides = read_fasta(guides_path);
+        std::vector<FastaRecord> guides;
         const uint32_t len = (uint32_t)pattern.size();
         std::string letters;
-        for (const auto &g : guides) {
-            if (g.seq.size() != len)
-                throw std::runtime_error("guide '" + g.id + "' has " + std::to_string(g.seq.size()) + " letters, the pattern has " + std::to_string(len));
-            for (char c : g.seq)
-                if (!iupac(c)) throw std::runtime_error("guide '" + g.id + "' holds '" + std::string(1, c) + "', which is no IUPAC letter");
-            letters += g.seq;
+        if (!enumerate) {
+            guides = read_fasta(guides_path);
+            for (const auto &g : guides) {
+                if (g.seq.size() != len)
+                    throw std::runtime_error("guide '" + g.id + "' has " + std::to_string(g.seq.size()) + " letters, the pattern has " + std::to_string(len));
+                for (char c : g.seq)
+                    if (!iupac(c)) throw std::runtime_error("guide '" + g.id + "' holds '" + std::string(1, c) + "', which is no IUPAC letter");
+                letters += g.seq;
+            }
+            std::printf("Guides loaded (total: %zu).\n", guides.size());
         }
-        std::printf("Guides loaded (total: %zu).\n", guides.size());
         const PackedIndex ix = read_index(prefix);
+        std::vector<vsc_interval> targets;
+        if (opts[8].set) targets = read_targets(opts[8].value, ix);
         int st = vsc_ctx_create((int)device, &ctx);
         if (st != VSC_OK) throw std::runtime_error(st == VSC_ERR_NODEVICE ? "no HIP device available (there is no CPU fallback)" : "could not create the device context");
         st = vsc_genome_load(ctx, ix.hi.data(), ix.lo.data(), ix.nm.data(), 0, ix.hi.size(), ix.hi.size(), ix.contigs.data(),
@@ -103,12 +228,45 @@ int main(int argc, char **argv)
         if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         std::printf("Index loaded.\n");
 
-        vsc_pattern_params p{};
-        p.max_mismatches = (uint32_t)mm;
+        const vsc_locus *loci = nullptr;
+        if (enumerate) {
+            // an empty -B file is a target set that holds nothing: a pointer that is not NULL with n = 0
+            const vsc_interval none{};
+            st = vsc_guides_enumerate_pattern(ctx, genome, pattern.c_str(), len, &ep, opts[8].set ? (targets.empty() ? &none : targets.data()) : nullptr,
+                                              targets.size(), &found);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const uint64_t n = vsc_pattern_guides_count(found);
+            const uint64_t *codes = nullptr;
+            st = vsc_pattern_guides_data(found, &codes, &loci);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            std::printf("Guides found (total: %llu).\n", (unsigned long long)n);
+            std::ofstream out(opts[7].value);
+            if (!out.is_open()) throw std::runtime_error("Could not open output path.");
+            out << "#guide\tchrom\tpos\tstrand\n";
+            guides.resize(n);
+            letters.resize(n * len);
+            for (uint64_t i = 0; i < n; ++i) {
+                if (vsc_pattern_guide_text(codes[i], len, ep.ps_start, ep.ps_len, 0, &letters[i * len]) != VSC_OK)
+                    throw std::runtime_error("a code of the enumeration is no guide");
+                guides[i].seq = letters.substr(i * len, len);
+                guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
+                out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+') << '\n';
+            }
+            if (!out) throw std::runtime_error("Write error on " + opts[7].value);
+        }
+
         std::vector<vsc_pattern_summary> rows(guides.size());
-        st = vsc_search_pattern(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, opts[6].set ? &hits : nullptr,
-                                rows.data());
-        if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        if (!enumerate || opts[3].set) {
+            if (guides.size() > 0xFFFFFFFFull) throw std::runtime_error("more guides than one search takes");
+            vsc_pattern_params p{};
+            p.max_mismatches = (uint32_t)mm;
+            st = vsc_search_pattern(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, opts[6].set ? &hits : nullptr,
+                                    rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            // a found guide's own locus is a hit at 0 mismatches (N at the positions outside the protospacer): not an off-target
+            if (enumerate)
+                for (auto &r : rows) r.count[0] -= r.count[0] ? 1u : 0u;
+        }
 
         if (opts[5].set) {
             std::ofstream out(opts[5].value);
@@ -157,6 +315,7 @@ int main(int argc, char **argv)
         rc = 1;
     }
     vsc_pattern_hits_free(hits);
+    vsc_pattern_guides_free(found);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);
     return rc;

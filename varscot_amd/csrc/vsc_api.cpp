@@ -17,6 +17,7 @@
 
 #include "vsc_bulge.h"
 #include "vsc_pattern.h"
+#include "vsc_pattern_enum.h"
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
@@ -3330,6 +3331,216 @@ int vsc_pattern_match(const char *pattern, const char *guide, const char *site_t
     if (hit) *hit = acgt && pattern_mismatch(sh, sl, pattern_planes(p_sets, len)) == 0u;
     if (nm) *nm = (uint32_t)__builtin_popcount(x);
     if (mask) *mask = x;
+    return VSC_OK;
+}
+
+// ---- pattern guide discovery (kernels: the end of vsc_pattern.hip) --------------------------------------------
+// vsc_guides_enumerate's passes - count over the work list, exclusive scan of the per-tile counts, one 8-byte read-back, write
+// into the result's own arrays - behind the pattern search's front end.  The targets are no vsc_regions: their intervals
+// become ranges of site starts on the host (pattern_target_ranges), the work list holds the tiles that meet one.
+int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, uint32_t len, const vsc_pattern_enum_params *params,
+                                 const vsc_interval *targets, uint64_t n_targets, vsc_pattern_guides **out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    ctx->err.clear();
+    const char *const fn = "vsc_guides_enumerate_pattern";
+    auto refuse = [&](const char *what) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "%s: %s", fn, what);
+        return fail(ctx, VSC_ERR_INVALID, msg);
+    };
+    if (!genome || !params || !pattern || (n_targets && !targets)) return refuse("null argument");
+    if (genome->ctx != ctx) return refuse("genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return refuse("the pattern must have 16..32 letters");
+    uint8_t sets[kPatMaxLen], rc_sets[kPatMaxLen];
+    if (!pattern_sets(pattern, len, sets)) return refuse("the pattern holds a letter that is no IUPAC letter");
+    const uint32_t ps_a = params->ps_start, ps_k = params->ps_len;
+    if (ps_k == 0 || ps_a + ps_k > len) return refuse("the protospacer must be a non-empty range of the pattern's positions");
+    if (params->strands > 2) return refuse("strands must be 0 (both), 1 ('+') or 2 ('-')");
+    if (params->gc_min > ps_k || params->gc_max > ps_k || (params->gc_max && params->gc_min > params->gc_max))
+        return refuse("GC bounds must satisfy gc_min <= gc_max <= the protospacer's length (gc_max 0: no upper bound)");
+    if (params->reserved0 || params->reserved1 || params->reserved[0] || params->reserved[1]) return refuse("reserved fields must be 0");
+    std::vector<PatStartRange> ranges;
+    if (targets) {
+        if (params->rule != VSC_REGION_OVERLAP && params->rule != VSC_REGION_INSIDE) return refuse("unknown target rule");
+        if (pattern_target_ranges(genome->h_contig_off.data(), genome->h_contig_end.data(), genome->n_contigs, targets, n_targets, params->rule,
+                                  len, &ranges) != VSC_OK)
+            return refuse("a target interval is outside the contig table, has start > end or a non-zero reserved field");
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    PatEnumArgs a{};
+    pattern_front(sets, len, &a.front[0]);
+    pattern_revcomp(sets, len, rc_sets);
+    pattern_front(rc_sets, len, &a.front[1]);
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.len = len;
+    a.len_mask = len < 32u ? (1u << len) - 1u : ~0u;
+    a.keep_fwd = params->strands != 2 ? 0xFFFFFFFFu : 0u;
+    a.keep_rev = params->strands != 1 ? 0xFFFFFFFFu : 0u;
+    const uint32_t ps_bits = ps_k < 32u ? (1u << ps_k) - 1u : ~0u;
+    a.ps_fwd = ps_bits << ps_a;
+    a.ps_rev = ps_bits << (len - ps_a - ps_k);
+    a.gc_min = params->gc_min;
+    a.gc_max = params->gc_max ? params->gc_max : ps_k;
+    a.max_t_run = params->max_t_run;
+    a.filter = (a.gc_min > 0 || a.gc_max < ps_k || a.max_t_run) ? 1u : 0u;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+
+    // the work list: with targets, the tiles of the shard that hold a start of a range; without, every tile of the shard
+    std::vector<uint32_t> work;
+    uint32_t n_work = genome->d_hi ? genome->n_tiles : 0;
+    if (targets) {
+        const uint64_t first = a.first_pos, last = first + (uint64_t)n_work * kTileBases;  // the shard's starts: [first, last)
+        for (const PatStartRange &r : ranges) {
+            const uint64_t lo = std::max<uint64_t>(r.lo, first), hi = std::min<uint64_t>(r.hi, last);
+            if (lo >= hi) continue;
+            const uint32_t t0 = (uint32_t)((lo - first) / kTileBases), t1 = (uint32_t)((hi - 1 - first) / kTileBases);
+            for (uint32_t t = t0; t <= t1; ++t)
+                if (work.empty() || work.back() < t) work.push_back(t);  // (the ranges ascend)
+        }
+        n_work = (uint32_t)work.size();
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    vsc_pattern_guides *g = new (std::nothrow) vsc_pattern_guides();
+    if (!g) return fail(ctx, VSC_ERR_NOMEM, "vsc_guides_enumerate_pattern: out of host memory");
+    std::unique_ptr<vsc_pattern_guides, int (*)(vsc_pattern_guides *)> holder(g, vsc_pattern_guides_free);
+    g->ctx = ctx;
+    unsigned long long total = 0;
+    if (n_work) {
+        // scratch: [work list][counts][offsets][ranges], 256-byte aligned parts
+        const size_t list_bytes = ((size_t)n_work * sizeof(uint32_t) + 255) / 256 * 256;
+        const size_t off_bytes = (((size_t)n_work + 1) * sizeof(unsigned long long) + 255) / 256 * 256;
+        VSC_HIP(ctx, ctx->enum_tabs.ensure(2 * list_bytes + off_bytes + ranges.size() * sizeof(PatStartRange)));
+        char *base = (char *)ctx->enum_tabs.p;
+        unsigned long long *d_off = (unsigned long long *)(base + 2 * list_bytes);
+        if (targets) {
+            VSC_HIP(ctx, hipMemcpyAsync(base, work.data(), (size_t)n_work * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(base + 2 * list_bytes + off_bytes, ranges.data(), ranges.size() * sizeof(PatStartRange),
+                                        hipMemcpyHostToDevice, ctx->stream));
+            a.work = (const uint32_t *)base;
+            a.ranges = (const uint2 *)(base + 2 * list_bytes + off_bytes);
+            a.n_ranges = (uint32_t)ranges.size();
+        }
+        a.n_work = n_work;
+        a.tile_count = (uint32_t *)(base + list_bytes);
+        a.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_pattern_enum(a, false, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list and the ranges above are this call's vectors)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+        t.passes = 1;
+        if (params->max_guides && total > params->max_guides) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "vsc_guides_enumerate_pattern: %llu candidates exceed max_guides = %llu", total,
+                          (unsigned long long)params->max_guides);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        if (total) {
+            g->loci_at = ((size_t)total * sizeof(uint64_t) + 255) / 256 * 256;
+            VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
+            a.codes = (unsigned long long *)g->storage.p;
+            a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
+            a.n_out = total;
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch_pattern_enum(a, true, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+            t.passes = 2;
+        }
+    }
+    g->n = total;
+    if (total == 0) g->host_valid = true;
+    t.total_ms = t.scan_ms;
+    t.sites = total;
+    ctx->timing = t;
+    *out = holder.release();
+    return VSC_OK;
+    });
+}
+
+uint64_t vsc_pattern_guides_count(const vsc_pattern_guides *guides) { return guides ? guides->n : 0; }
+
+int vsc_pattern_guides_data(vsc_pattern_guides *guides, const uint64_t **codes, const vsc_locus **loci)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    return guarded(guides->ctx, [&]() -> int {
+    if (!guides->host_valid) {
+        vsc_ctx *ctx = guides->ctx;
+        guides->codes.resize(guides->n);
+        guides->loci.resize(guides->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->codes.data(), guides->storage.p, guides->n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->loci.data(), (const char *)guides->storage.p + guides->loci_at, guides->n * sizeof(vsc_locus),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        guides->host_valid = true;
+    }
+    if (codes) *codes = guides->codes.data();
+    if (loci) *loci = guides->loci.data();
+    return VSC_OK;
+    });
+}
+
+int vsc_pattern_guides_data_dev(const vsc_pattern_guides *guides, const void **codes_dev, const void **loci_dev)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    const bool dev = guides->n && guides->storage.p;
+    if (codes_dev) *codes_dev = dev ? guides->storage.p : nullptr;
+    if (loci_dev) *loci_dev = dev ? (const char *)guides->storage.p + guides->loci_at : nullptr;
+    return VSC_OK;
+}
+
+int vsc_pattern_guides_free(vsc_pattern_guides *guides)
+{
+    if (!guides) return VSC_OK;
+    if (guides->ctx && guides->storage.p) {
+        (void)hipSetDevice(guides->ctx->device);
+        guides->storage.release();
+    }
+    delete guides;
+    return VSC_OK;
+}
+
+int vsc_pattern_guide_text(uint64_t code, uint32_t len, uint32_t ps_start, uint32_t ps_len, uint32_t spell, char *out)
+{
+    return pattern_guide_text(code, len, ps_start, ps_len, spell, out);
+}
+
+int vsc_debug_pattern_target_ranges(const vsc_contig *contigs, uint32_t n_contigs, const vsc_interval *iv, uint64_t n, uint32_t rule,
+                                    uint32_t len, uint32_t *ranges, uint64_t capacity, uint64_t *n_ranges)
+{
+    if ((n_contigs && !contigs) || !n_ranges || (capacity && !ranges) || len < kPatMinLen || len > kPatMaxLen) return VSC_ERR_INVALID;
+    std::vector<uint32_t> off(n_contigs), end(n_contigs);
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        off[c] = (uint32_t)contigs[c].offset;
+        end[c] = off[c] + contigs[c].length;
+    }
+    std::vector<PatStartRange> r;
+    const int rc = pattern_target_ranges(off.data(), end.data(), n_contigs, iv, n, rule, len, &r);
+    if (rc != VSC_OK) return rc;
+    *n_ranges = r.size();
+    if (r.size() > capacity) return VSC_ERR_RANGE;
+    for (size_t i = 0; i < r.size(); ++i) {
+        ranges[2 * i] = r[i].lo;
+        ranges[2 * i + 1] = r[i].hi;
+    }
     return VSC_OK;
 }
 

@@ -131,7 +131,8 @@ struct vsc_ctx {
     // duplicate counts), the excluded loci in reference coordinates, and the labels on their way to the host
     vsc::DeviceBuf varmap_buf, var_state, var_excl, var_labels;
     uint64_t varmap_serial = 0;  // 0: none resident
-    // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan
+    // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan;
+    // vsc_guides_enumerate_pattern: the same three parts, then the targets' start ranges
     vsc::DeviceBuf enum_tabs;
     // vsc_hits_pairs / vsc_guides_pairs: the call's tables (segment starts, pairs, their item offsets, excluded loci, rows),
     // the per-item counts with their exclusive scan, and the sites / pairs on their way to the host
@@ -246,6 +247,17 @@ struct vsc_pattern_hits {
     vsc::DeviceBuf storage;
     uint64_t n = 0;
     std::vector<vsc_pattern_hit> host;
+    bool host_valid = false;
+};
+
+// The candidates of vsc_guides_enumerate_pattern: two device arrays the object owns, as vsc_guides'.
+struct vsc_pattern_guides {
+    vsc_ctx *ctx = nullptr;
+    vsc::DeviceBuf storage;  // codes (n x 8 bytes), then the loci (n x 16 bytes) from loci_at on
+    size_t loci_at = 0;
+    uint64_t n = 0;
+    std::vector<uint64_t> codes;
+    std::vector<vsc_locus> loci;
     bool host_valid = false;
 };
 

@@ -21,9 +21,13 @@
 //                           every hit goes to  group offset + chunks before it in the group + cells before it in the chunk +
 //                           hits of earlier steps + lanes in front.  The rows come from this pass.
 // No record is placed through an atomic and nothing is sorted: the bytes depend on the planes and the parameters only.
+//
+// Behind the search: pattern_enum_kernel (vsc_guides_enumerate_pattern) - the same front end without the queue,
+// in front of enum_kernel's count / scan / write.
 #include "vsc_internal.h"
 #include "vsc_device.h"
 #include "vsc_pattern.h"
+#include "vsc_pattern_enum.h"
 
 namespace vsc {
 
@@ -51,12 +55,15 @@ __device__ __forceinline__ uint32_t pattern_starts(const PatFront &f, uint32_t H
     return ok;
 }
 
-// The tile's words into LDS and the two start masks.
-__device__ __forceinline__ void pattern_tile(const PatternArgs &a, uint32_t tile, uint32_t lane, PatLds &s, uint32_t *mf, uint32_t *mr)
+// A lane's word of each plane with its right neighbour, and the two start masks of its 32 starts (both searches' and the
+// enumeration's front end).  kArgs: PatternArgs or PatEnumArgs.
+template <typename kArgs>
+__device__ __forceinline__ void pattern_words(const kArgs &a, uint32_t tile, uint32_t lane, uint32_t &H0, uint32_t &H1, uint32_t &L0,
+                                              uint32_t &L1, uint32_t *mf, uint32_t *mr)
 {
     const size_t wi = (size_t)tile * kTileWords + lane;  // (< n_tiles * 64, and the planes are padded by kPadWords)
-    const uint32_t H0 = a.hi[wi], H1 = a.hi[wi + 1];
-    const uint32_t L0 = a.lo[wi], L1 = a.lo[wi + 1];
+    H0 = a.hi[wi], H1 = a.hi[wi + 1];
+    L0 = a.lo[wi], L1 = a.lo[wi + 1];
     const uint32_t N0 = a.nm[wi], N1 = a.nm[wi + 1];
     uint64_t nn = ((uint64_t)N1 << 32) | N0;
     nn |= nn >> 1;
@@ -66,6 +73,13 @@ __device__ __forceinline__ void pattern_tile(const PatternArgs &a, uint32_t tile
     const uint32_t clean = ~(uint32_t)(nn | nn >> (a.len - kPatMinLen));  // no N in positions i .. i+L-1
     *mf = pattern_starts(a.front[0], H0, H1, L0, L1) & clean;
     *mr = pattern_starts(a.front[1], H0, H1, L0, L1) & clean;
+}
+
+// The tile's words into LDS and the two start masks.
+__device__ __forceinline__ void pattern_tile(const PatternArgs &a, uint32_t tile, uint32_t lane, PatLds &s, uint32_t *mf, uint32_t *mr)
+{
+    uint32_t H0, H1, L0, L1;
+    pattern_words(a, tile, lane, H0, H1, L0, L1, mf, mr);
     s.h[lane] = H0;
     s.l[lane] = L0;
     if (lane == kWave - 1) {
@@ -306,6 +320,117 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
     }
 }
 
+// ---- pattern guide discovery (vsc_guides_enumerate_pattern) ---------------------------------------------------
+// The searches' front end in front of enum_kernel's back end (vsc_enum.hip): one wave per tile of the work list, the start
+// masks of both strands from pattern_words, no LDS - there is no guide loop, so no queue.  Two passes over the same masks:
+// pattern_enum_kernel<false> counts per tile, enum_scan_kernel turns the counts into offsets, pattern_enum_kernel<true>
+// recomputes the masks and writes every candidate at  tile offset + wave prefix over the lanes + rank inside the lane.
+namespace {
+
+// The sequence filters on one site; wh / wl = its bases on the forward genome from the start on, ps = the protospacer's bits
+// of this strand.  G/C stay G/C under the complement, a T of the guide is an A of the window on '-', and a run is as long
+// read backwards - so neither plane is reversed.  The bits outside ps are 0 in y: they neither start nor extend a run.
+__device__ __forceinline__ bool pattern_sequence_ok(const PatEnumArgs &a, uint32_t wh, uint32_t wl, uint32_t ps, bool rev)
+{
+    const uint32_t gc = (uint32_t)__popc((wh ^ wl) & ps);
+    if (gc < a.gc_min || gc > a.gc_max) return false;
+    if (a.max_t_run) {
+        uint32_t y = (rev ? ~(wh | wl) : wh & wl) & ps;                // T of the guide
+        for (uint32_t i = 0; i < a.max_t_run && y; ++i) y &= y >> 1;  // every step shortens every run by one
+        if (y) return false;                                          // a run of more than max_t_run is left
+    }
+    return true;
+}
+
+// Which of the 32 starts from global position `base` on lie in the ranges: the first range that ends behind base by binary
+// search, then the ranges that begin before base + 32 (disjoint and not abutting: 16 at the most).
+__device__ __forceinline__ uint32_t pattern_range_mask(const PatEnumArgs &a, uint32_t base)
+{
+    uint32_t lo = 0, hi = a.n_ranges;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.ranges[mid].y <= base) lo = mid + 1; else hi = mid;
+    }
+    uint32_t m = 0;
+    for (uint32_t k = lo; k < a.n_ranges; ++k) {
+        const uint2 r = a.ranges[k];  // (r.y > base)
+        if ((uint64_t)r.x >= (uint64_t)base + 32u) break;
+        const uint32_t s = r.x > base ? r.x - base : 0u;          // 0 .. 31
+        const uint32_t e = r.y - base < 32u ? r.y - base : 32u;   // s + 1 .. 32
+        m |= (e < 32u ? (1u << e) - 1u : ~0u) & ~((1u << s) - 1u);
+    }
+    return m;
+}
+
+// the L-bit plane p of a forward site as the plane of its reverse complement: bit j to L - 1 - j, inverted; bits from L on 0
+__device__ __forceinline__ uint32_t pattern_revcomp_plane(uint32_t p, uint32_t len) { return (~__brev(p)) >> (32u - len); }
+
+}  // namespace
+
+template <bool kWrite, bool kTargets>
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_enum_kernel(const PatEnumArgs a)
+{
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint32_t item = blockIdx.x * kWavesPerGroup + threadIdx.x / kWave;  // wave-uniform
+    if (item >= a.n_work) return;
+    const uint32_t tile = a.work ? a.work[item] : item;
+    uint32_t H0, H1, L0, L1, mf, mr;
+    pattern_words(a, tile, lane, H0, H1, L0, L1, &mf, &mr);
+    mf &= a.keep_fwd;
+    mr &= a.keep_rev;
+    const uint32_t base_pos = a.first_pos + tile * (uint32_t)kTileBases + lane * 32u;
+    if (kTargets) {
+        const uint32_t in = pattern_range_mask(a, base_pos);
+        mf &= in;
+        mr &= in;
+    }
+    // ---- per-site tests, only where one is asked for (a.filter is wave-uniform): set bit by set bit ----
+    if (a.filter) {
+        for (uint32_t m = mf | mr; m; m &= m - 1u) {
+            const uint32_t b = (uint32_t)__builtin_ctz(m), bit = 1u << b;
+            const uint32_t wh = funnel(H1, H0, b), wl = funnel(L1, L0, b);
+            if ((mf & bit) && !pattern_sequence_ok(a, wh, wl, a.ps_fwd, false)) mf &= ~bit;
+            if ((mr & bit) && !pattern_sequence_ok(a, wh, wl, a.ps_rev, true)) mr &= ~bit;
+        }
+    }
+    // ---- rank: tile offset + wave prefix over the lanes + order inside the lane ----
+    uint32_t total;
+    const uint32_t before = wave_exclusive((uint32_t)__popc(mf) + (uint32_t)__popc(mr), lane, &total);
+    if (!kWrite) {
+        if (lane == 0) a.tile_count[item] = total;
+        return;
+    }
+    if (total == 0) return;
+    unsigned long long at = a.tile_off[item] + before;
+    uint32_t c = 0, c_end = 0;  // the contig of the lane's last candidate: [.., c_end) in global positions
+    for (uint32_t m = mf | mr; m; m &= m - 1u) {
+        const uint32_t b = (uint32_t)__builtin_ctz(m), bit = 1u << b;
+        const uint32_t pos = base_pos + b;
+        if (pos >= c_end) {  // c = the last contig that starts at or before pos (an N-free site lies inside one contig)
+            uint32_t lo = 0, hi = a.n_contigs;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.contig_off[mid] <= pos) lo = mid + 1; else hi = mid;
+            }
+            c = lo ? lo - 1u : 0u;
+            c_end = a.contig_end[c];
+        }
+        const uint32_t wh = funnel(H1, H0, b), wl = funnel(L1, L0, b);
+        const uint32_t rel = pos - a.contig_off[c];
+        // (at < n_out whenever both passes see the same planes: the test keeps a write inside the result if not)
+        if ((mf & bit) && at < a.n_out) {
+            a.codes[at] = (unsigned long long)(wh & a.len_mask) << 32 | (wl & a.len_mask);
+            a.loci[at] = make_uint4(c, rel, 0u, 0u);
+        }
+        at += (mf & bit) ? 1u : 0u;
+        if ((mr & bit) && at < a.n_out) {
+            a.codes[at] = (unsigned long long)pattern_revcomp_plane(wh, a.len) << 32 | pattern_revcomp_plane(wl, a.len);
+            a.loci[at] = make_uint4(c, rel, 1u, 0u);
+        }
+        at += (mr & bit) ? 1u : 0u;
+    }
+}
+
 // ---- launches ----------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -330,6 +455,22 @@ hipError_t launch_pattern_write(const PatternArgs &args, int n_cus, hipStream_t 
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
     hipLaunchKernelGGL(pattern_write_kernel, pattern_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    return hipGetLastError();
+}
+
+// work item i is wave i, as launch_enum
+hipError_t launch_pattern_enum(const PatEnumArgs &args, bool write, hipStream_t stream)
+{
+    if (args.n_work == 0) return hipSuccess;
+    const dim3 grid((args.n_work + kWavesPerGroup - 1) / kWavesPerGroup), block(kWave * kWavesPerGroup);
+    const bool targets = args.ranges != nullptr;
+    if (write) {
+        if (targets) hipLaunchKernelGGL((pattern_enum_kernel<true, true>), grid, block, 0, stream, args);
+        else hipLaunchKernelGGL((pattern_enum_kernel<true, false>), grid, block, 0, stream, args);
+    } else {
+        if (targets) hipLaunchKernelGGL((pattern_enum_kernel<false, true>), grid, block, 0, stream, args);
+        else hipLaunchKernelGGL((pattern_enum_kernel<false, false>), grid, block, 0, stream, args);
+    }
     return hipGetLastError();
 }
 
