@@ -578,7 +578,8 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
  * or written (rows only); rows == NULL: records only.  rows: host memory, n_guides entries.  n_guides == 0: VSC_OK, nothing is
  * launched (*out = an empty result).  A genome loaded as one shard reports the sites that START in its own words (one halo word
  * covers the 32 bases); the records of all shards, merged by the order above, are the whole genome's.  No seed index is used
- * and none is needed; MIT scores, classifier rows and bulges are defined for 20 + NGG only and stay with their own calls.
+ * and none is needed; MIT scores and classifier rows are defined for 20 + NGG only and stay with their own calls (bulges under a
+ * pattern: since added, vsc_search_pattern_bulges below).
  * The guides of a pattern are found by vsc_guides_enumerate_pattern (below).
  * vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = candidates (sites that satisfy the pattern and hold
  * no N, both strands), pairs = candidate x guide comparisons, passes = rounds; the sort, finalize and score fields 0.
@@ -631,6 +632,70 @@ int vsc_pattern_hits_free(vsc_pattern_hits *hits);
  * IUPAC letter: VSC_ERR_INVALID. */
 int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm,
                       uint32_t *mask);
+/*
+ * Bulges under a pattern: vsc_search_bulges for any nuclease - the DNA / RNA bulge report of Cas-OFFinder and CRISPRitz for
+ * SaCas9, Cas12a, SpCas9-NG, truncated guides.  The pattern / guide model of vsc_search_pattern with the pairing of
+ * vsc_search_bulges, in the record and the rows of vsc_search_bulges.
+ *
+ * INPUT    Pattern P[0..L) and guides G[0..L), IUPAC, exactly as vsc_search_pattern takes them (same letters, same refusals),
+ *          a budget m in 0..8, dna_max / rna_max in 0..2 (not both 0), and the PROTOSPACER (a, n): read positions [a, e),
+ *          e = a + n, the part of the guide in which a bulge may lie (SaCas9 (0, 21), Cas12a (4, 23), SpCas9 (0, 20)).
+ * REFUSED  (VSC_ERR_INVALID)  n < 4 or e > L;  P[j] != N for some a <= j < e (a pattern constrains the PAM, not the
+ *          protospacer; this is what makes the pattern condition independent of the split point);  L + dna_max > 32 or
+ *          L - rna_max < 16 (the front end's word pair and its N fold);  everything vsc_search_pattern refuses.
+ * SITE     (g, strand, c, p, d), d in {-rna_max..-1} + {1..dna_max}: c[p, p + L + d) of contig c; in read orientation
+ *          s = that text on '+', its reverse complement on '-'.
+ * PAIRING  DNA bulge (b = d > 0), split point i in [a+1, e-1]:  position j pairs s[j] for j < i and s[j + b] for j >= i;
+ *          s[i .. i+b) is unpaired.
+ *          RNA bulge (b = -d > 0), a+1 <= i and i + b <= e-1:  position j pairs s[j] for j < i and s[j - b] for j >= i + b;
+ *          guide positions [i, i+b) are unpaired and never counted.
+ *          So positions j <= a always pair from the 5' end, positions j >= e-1 always from the 3' end, whatever i is.
+ * HIT      iff  1. p + L + d <= len(c);  2. no N in the L + d bases, the unpaired ones included;
+ *               3. s[j] in P[j] for j < a and s[j + d] in P[j] for j >= e  (= the site satisfies
+ *                  P[0..a) + N x (n + d) + P[e..L), Cas-OFFinder's bulged pattern);
+ *               4. NM = min_i nm(i) <= m, nm(i) = #{ paired j : the paired site base is not in G[j] }.  A guide's N positions
+ *                  never count; spelled PAM letters count, through the pairing above.
+ * RECORD   vsc_bulge_hit as it is (16 bytes, VSC_BULGE_* macros): d = site length - L, index = the smallest i that reaches NM
+ *          (<= 31: fits the 5 bits), NM.  One record per hit site.  d = 0 is vsc_search_pattern's and is never reported here.
+ *          The bulged neighbours of plain hits (index a+1) are reported, as by vsc_search_bulges.
+ * ROWS     vsc_bulge_summary as it is: count[class][NM], classes ascending d.
+ * ORDER    ascending (guide, strand, contig, pos, d); the bytes depend on the planes and the parameters only - ranks from counts,
+ *          no atomic append, no sort, guide_batch never changes them.
+ *
+ * Under N x 21 + GR, the protospacer (0, 20) and spelled 23-letter ACGT guides this is vsc_search_bulges' definition word for
+ * word, and the records are byte-equal to its (default PAM set).
+ * vsc_search_pattern_bulges: the result object is vsc_search_bulges' (vsc_bulge_hits_count / _data / _data_dev / _free).
+ * max_hits, guide_batch (0: 16; more than 64: 64), n_guides == 0, out == NULL (rows only), rows == NULL (records only), both
+ * NULL (VSC_ERR_INVALID), shards and scratch (the context's pools; vsc_ctx_release_scratch gives it back) behave as
+ * vsc_search_pattern's.  vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = candidates of the enabled
+ * classes on both strands (sites that satisfy their class's bulged pattern and hold no N), pairs = sites x guides, passes =
+ * rounds.
+ * vsc_pattern_bulge_align: the definition for ONE guide and ONE site on the host (no device needed), by the functions the
+ * kernels run.  site_text = len + d letters in read orientation, d in {-2, -1, +1, +2}.  *hit = 1 when the site holds ACGT only
+ * and satisfies condition 3 (the caller compares *nm with its budget); then *nm = NM and *index = the smallest split point that
+ * reaches it.  A non-ACGT site letter or a site that fails condition 3: *hit = 0, *nm = 0, *index = 0.  Any of the three may
+ * be NULL.  Everything REFUSED above (with dna_max / rna_max = the size of d), a wrong d, a NULL text or a site text of another
+ * length: VSC_ERR_INVALID.
+ * Not provided: a vsc_multi_* entry point (shard results merge by ORDER), a seed index for patterns, MIT or classifier scores
+ * for other nucleases, and suppressing the bulged neighbours of plain hits.
+ */
+typedef struct {
+    uint32_t max_mismatches; /* 0..VSC_MAX_MISMATCHES */
+    uint32_t guide_batch;    /* 0: default */
+    uint64_t max_hits;       /* 0: no cap */
+    uint32_t proto_start, proto_len; /* the protospacer [proto_start, proto_start + proto_len) in read positions */
+    uint32_t dna_max, rna_max;       /* 0..2 each, not both 0 */
+} vsc_pattern_bulge_params;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pattern_bulge_params) == 32, "vsc_pattern_bulge_params layout");
+#else
+_Static_assert(sizeof(vsc_pattern_bulge_params) == 32, "vsc_pattern_bulge_params layout");
+#endif
+int vsc_search_pattern_bulges(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides /* n_guides * len letters */,
+                              uint32_t n_guides, uint32_t len, const vsc_pattern_bulge_params *params, vsc_bulge_hits **out /* may be NULL */,
+                              vsc_bulge_summary *rows /* may be NULL */);
+int vsc_pattern_bulge_align(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t proto_start,
+                            uint32_t proto_len, int d, uint32_t *hit, uint32_t *nm, uint32_t *index);
 /*
  * Pattern guide discovery: which guides of ANY nuclease does a target contain?  vsc_guides_enumerate for a pattern - the
  * beginning of the route that vsc_search_pattern continues: "every Cas12a guide in these exons with its off-target counts" is

@@ -110,6 +110,17 @@ class PatternEnumParams(C.Structure):
 assert C.sizeof(PatternEnumParams) == 32
 
 
+class PatternBulgeParams(C.Structure):
+    """vsc_pattern_bulge_params (vsc_search_pattern_bulges): mismatch budget (0..8), guides per round (0 = default), max_hits
+    (0 = no cap), the protospacer [proto_start, proto_start + proto_len) in read positions, largest DNA / RNA bulge (0..2, not
+    both 0)."""
+    _fields_ = [("max_mismatches", C.c_uint32), ("guide_batch", C.c_uint32), ("max_hits", C.c_uint64), ("proto_start", C.c_uint32),
+                ("proto_len", C.c_uint32), ("dna_max", C.c_uint32), ("rna_max", C.c_uint32)]
+
+
+assert C.sizeof(PatternBulgeParams) == 32
+
+
 class PairParams(C.Structure):
     """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
     _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -287,6 +298,8 @@ SYMBOLS = [
     ("vsc_pattern_hits_data_dev", _vp, [_vp]),
     ("vsc_pattern_hits_free", C.c_int, [_vp]),
     ("vsc_pattern_match", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, _u32p, _u32p, _u32p]),
+    ("vsc_search_pattern_bulges", C.c_int, [_vp, _vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(PatternBulgeParams), C.POINTER(_vp), _vp]),
+    ("vsc_pattern_bulge_align", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p]),
     ("vsc_guides_enumerate_pattern", C.c_int, [_vp, _vp, C.c_char_p, C.c_uint32, C.POINTER(PatternEnumParams), _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_pattern_guides_count", C.c_uint64, [_vp]),
     ("vsc_pattern_guides_data", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),

@@ -165,6 +165,20 @@ def pattern_match(pattern, guide, site):
     return bool(hit.value), int(nm.value), int(mask.value)
 
 
+def pattern_bulge_align(pattern, guide, site, protospacer, d):
+    """vsc_pattern_bulge_align: (hit, nm, index) of one site of len(pattern) + d letters in read orientation under one pattern
+    and one guide, d in -2, -1, 1, 2, with a bulge inside protospacer = (start, length) - hit = the site holds ACGT only and
+    satisfies the bulged pattern, nm = the fewest mismatches over the split points, index = the smallest split point that
+    reaches it: the definition of search_pattern_bulges on the host, by the functions the kernels run.  No device is needed."""
+    p, g, s = (x if isinstance(x, bytes) else x.encode() for x in (pattern, guide, site))
+    if len(p) != len(g):
+        raise ValueError("pattern and guide must have the same length (%d, %d)" % (len(p), len(g)))
+    hit, nm, index = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(lib().vsc_pattern_bulge_align(p, g, s, len(p), int(protospacer[0]), int(protospacer[1]), int(d), C.byref(hit), C.byref(nm),
+                                        C.byref(index)))
+    return bool(hit.value), int(nm.value), int(index.value)
+
+
 def _enum_params(pam, strands, gc, max_t_run, max_guides):
     """vsc_enum_params of enumerate_guides' arguments.  Only what cannot be put into the struct is refused here: the library
     checks the values (a PAM letter outside ACGT, gc bounds above 20, ... are VSC_ERR_INVALID there)."""
@@ -732,6 +746,42 @@ class Genome:
                 recs = np.frombuffer((C.c_char * (n * 20)).from_address(data.value), dtype=PATTERN_HIT_DTYPE).copy()
         finally:
             L.vsc_pattern_hits_free(h)
+        return recs, out_rows
+
+    def search_pattern_bulges(self, pattern, guides, max_mismatches, protospacer, dna=1, rna=1, max_hits=0, guide_batch=0,
+                              records=True, rows=True):
+        """vsc_search_pattern_bulges: search_bulges for any nuclease - the sites of len(pattern) + d bases, d in -rna .. -1 and
+        1 .. dna, that satisfy the pattern with its protospacer = (start, length) stretched or shortened by d, hold no N and pair
+        with a guide within max_mismatches when d bases of the site (DNA bulge) or -d positions of the guide (RNA bulge) inside
+        the protospacer stay unpaired.  pattern and guides as search_pattern takes them; the pattern must be N over the
+        protospacer (pattern_protospacer gives it for a preset).  Returns (BULGE_HIT_DTYPE records in ascending (guide, strand,
+        contig, pos, d) order | None, uint32 rows of shape (n, 4, 9) - hits by class (RNA 2, RNA 1, DNA 1, DNA 2) and NM | None);
+        unpack_bulge_info reads the info word, d = site length - len(pattern).  max_hits: 0 = no cap, else VSC_ERR_RANGE when
+        there are more records; guide_batch never changes the result."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+        for i, g in enumerate(gs):
+            if len(g) != len(p):
+                raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+        pp = _lib.PatternBulgeParams(int(max_mismatches), int(guide_batch), int(max_hits), int(protospacer[0]), int(protospacer[1]),
+                                     int(dna), int(rna))
+        L = lib()
+        h = C.c_void_p()
+        out_rows = np.zeros((len(gs), _lib.BULGE_CLASSES, 9), dtype=np.uint32) if rows else None
+        check(L.vsc_search_pattern_bulges(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp),
+                                          C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+        if not records:
+            return None, out_rows
+        try:
+            n = int(L.vsc_bulge_hits_count(h))
+            data = C.c_void_p()
+            check(L.vsc_bulge_hits_data(h, C.byref(data)), self.ctx._h)
+            if n == 0:
+                recs = np.zeros(0, dtype=BULGE_HIT_DTYPE)
+            else:
+                recs = np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy()
+        finally:
+            L.vsc_bulge_hits_free(h)
         return recs, out_rows
 
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,

@@ -4,6 +4,13 @@
 // With -E the guides are not given but found: every site of the genome, or of the -B targets, that satisfies the pattern
 // (vsc_guides_enumerate_pattern), filtered over the -p protospacer, written as a TSV of guide, contig, pos and strand - and,
 // with -M and -O, screened in the same run (the design: every guide of the targets with its off-target counts).
+// -u DNA,RNA (e.g. -u 1,1; each 0 .. 2, not both 0; needs -p) adds the BULGED sites (vsc_search_pattern_bulges): the sites one or
+// two bases longer (DNA bulge) or shorter (RNA bulge) than the pattern that pair with the guide within -M when the extra bases
+// of the site or of the guide, inside the -p protospacer, stay unpaired.  The -O summary gains, behind its columns, bulgeCount
+// and per enabled class in ascending site length - br2 br1 bd1 bd2 - the columns <class>mm0 .. <class>mm<M>; -U bulges.tsv
+// lists the sites in ascending (guide, strand, chrom, start, site length) order under guide_summary -U's columns
+//   #guideId chrom start end strand kind size index mismatches sequence
+// Without -u every output is what it was.
 // Host C++ only: the search runs in libvarscot_hip.so (vsc_search_pattern); there is no CPU search here.  Every argument is
 // checked before a device is opened.
 #include <cstdio>
@@ -78,11 +85,15 @@ int main(int argc, char **argv)
         {'E', "enumerate", "Guides TSV: #guide chrom pos strand - the guides are FOUND in the genome instead of read from -R "
                            "(needs -p; with -M and -O they are screened in the same run, their own locus not counted)", false},
         {'B', "targets", "With -E: target intervals (.bed, BED3+); without, the whole genome is enumerated", false},
-        {'p', "protospacer", "With -E: START,LENGTH of the protospacer in the pattern (SaCas9 0,21; Cas12a 4,23); the filters look at it", false},
+        {'p', "protospacer", "With -E or -u: START,LENGTH of the protospacer in the pattern (SaCas9 0,21; Cas12a 4,23); the -E filters look "
+                             "at it, the bulges of -u lie in it", false},
         {'r', "rule", "With -B: overlap (default; the site shares a base with a target) or inside (it lies in one target)", false},
         {'s', "strands", "With -E: both (default), + or -", false},
         {'g', "gc", "With -E: MIN,MAX number of G/C in the protospacer (MAX 0: no upper bound)", false},
         {'t', "t-run", "With -E: longest run of T allowed in the protospacer (0: no limit)", false},
+        {'u', "bulges", "DNA,RNA: largest DNA and RNA bulge, 0 .. 2 each (e.g. 1,1; needs -p): adds the bulged sites - -O gains bulgeCount "
+                        "and <class>mm0 .. <class>mm<M> (br2 br1 bd1 bd2)", false},
+        {'U', "bulge-hits", "Path to the TSV file of the bulged sites (.tsv/.txt); needs -u", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -111,14 +122,15 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: the guides must be a .fa/.fasta file, the outputs .tsv/.txt files\n", argv[0]);
         return 1;
     }
-    if (!enumerate && !opts[5].set && !opts[6].set) {
+    const bool bulged = opts[14].set;
+    if (!enumerate && !opts[5].set && !opts[6].set && !(bulged && opts[15].set)) {
         std::fprintf(stderr, "%s: give -O, -T or both\n", argv[0]);
         return 1;
     }
     vsc_pattern_enum_params ep{};
     if (!enumerate) {
         for (int k = 8; k <= 13; ++k)
-            if (opts[k].set) {
+            if (opts[k].set && !(k == 9 && bulged)) {
                 std::fprintf(stderr, "%s: -%c belongs to the enumeration: give -E\n", argv[0], opts[k].short_name);
                 return 1;
             }
@@ -176,6 +188,40 @@ int main(int argc, char **argv)
             ep.max_t_run = (uint8_t)run;
         }
     }
+    // -u / -U: the bulged sites
+    vsc_pattern_bulge_params bp{};
+    if (bulged) {
+        long dna = 0, rna = 0, a = 0, k = 0;
+        if (!two_numbers(opts[14].value, &dna, &rna) || dna > 2 || rna > 2 || (dna == 0 && rna == 0)) {
+            std::fprintf(stderr, "%s: -u takes DNA,RNA, the largest bulges, 0 .. 2 each and not both 0 (e.g. 1,1), not '%s'\n", argv[0], opts[14].value.c_str());
+            return 1;
+        }
+        if (!opts[9].set || !two_numbers(opts[9].value, &a, &k) || k < 4 || a + k > (long)pattern.size()) {
+            std::fprintf(stderr, "%s: -u needs -p START,LENGTH with 4 <= LENGTH and START + LENGTH <= %zu, the pattern's length\n", argv[0], pattern.size());
+            return 1;
+        }
+        for (long j = a; j < a + k; ++j)
+            if (pattern[(size_t)j] != 'N' && pattern[(size_t)j] != 'n') {
+                std::fprintf(stderr, "%s: -u: the pattern must be N at every position of the -p protospacer\n", argv[0]);
+                return 1;
+            }
+        if ((long)pattern.size() + dna > VSC_PATTERN_MAX_LEN || (long)pattern.size() - rna < VSC_PATTERN_MIN_LEN) {
+            std::fprintf(stderr, "%s: -u: the pattern's length + DNA must not exceed 32 and its length - RNA must be at least 16\n", argv[0]);
+            return 1;
+        }
+        if (enumerate && !opts[3].set) {
+            std::fprintf(stderr, "%s: with -E, -u screens the found guides: give -M and -O\n", argv[0]);
+            return 1;
+        }
+        bp.proto_start = (uint32_t)a;
+        bp.proto_len = (uint32_t)k;
+        bp.dna_max = (uint32_t)dna;
+        bp.rna_max = (uint32_t)rna;
+    }
+    if (opts[15].set && (!bulged || !has_extension(opts[15].value, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: -U lists the bulged sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
+        return 1;
+    }
     char *end = nullptr;
     long mm = 0;
     if (opts[3].set) {
@@ -202,6 +248,7 @@ int main(int argc, char **argv)
     vsc_genome *genome = nullptr;
     vsc_pattern_hits *hits = nullptr;
     vsc_pattern_guides *found = nullptr;
+    vsc_bulge_hits *bulge_hits = nullptr;
     int rc = 1;
     try {
         std::vector<FastaRecord> guides;
@@ -267,18 +314,41 @@ int main(int argc, char **argv)
             if (enumerate)
                 for (auto &r : rows) r.count[0] -= r.count[0] ? 1u : 0u;
         }
+        // the bulged sites of the same guides (the bulged neighbours of a found guide's own locus are among them)
+        std::vector<vsc_bulge_summary> bulge_rows(bulged ? guides.size() : 0);
+        const bool bulge_on[VSC_BULGE_CLASSES] = {bp.rna_max >= 2, bp.rna_max >= 1, bp.dna_max >= 1, bp.dna_max >= 2};
+        static const char *const kBulgeClass[VSC_BULGE_CLASSES] = {"br2", "br1", "bd1", "bd2"};
+        if (bulged) {
+            bp.max_mismatches = (uint32_t)mm;
+            st = vsc_search_pattern_bulges(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &bp,
+                                           opts[15].set ? &bulge_hits : nullptr, bulge_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
 
         if (opts[5].set) {
             std::ofstream out(opts[5].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
             out << "#guideId\tguideSeq\tofftargetCount";
             for (long k = 0; k <= mm; ++k) out << "\tmm" << k;
+            if (bulged) {
+                out << "\tbulgeCount";
+                for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                    for (long k = 0; bulge_on[c] && k <= mm; ++k) out << '\t' << kBulgeClass[c] << "mm" << k;
+            }
             out << '\n';
             for (size_t g = 0; g < guides.size(); ++g) {
                 uint64_t total = 0;
                 for (long k = 0; k <= mm; ++k) total += rows[g].count[k];
                 out << first_word(guides[g].id) << '\t' << guides[g].seq << '\t' << total;
                 for (long k = 0; k <= mm; ++k) out << '\t' << rows[g].count[k];
+                if (bulged) {
+                    uint64_t bulge_total = 0;
+                    for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                        for (long k = 0; bulge_on[c] && k <= mm; ++k) bulge_total += bulge_rows[g].count[c][k];
+                    out << '\t' << bulge_total;
+                    for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
+                        for (long k = 0; bulge_on[c] && k <= mm; ++k) out << '\t' << bulge_rows[g].count[c][k];
+                }
                 out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[5].value);
@@ -309,6 +379,32 @@ int main(int argc, char **argv)
             out << text;
             if (!out) throw std::runtime_error("Write error on " + opts[6].value);
         }
+        if (bulge_hits) {
+            const vsc_bulge_hit *rec = nullptr;
+            if (vsc_bulge_hits_data(bulge_hits, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const uint64_t n = vsc_bulge_hits_count(bulge_hits);
+            std::ofstream out(opts[15].value);
+            if (!out.is_open()) throw std::runtime_error("Could not open the -U path.");
+            out << "#guideId\tchrom\tstart\tend\tstrand\tkind\tsize\tindex\tmismatches\tsequence\n";
+            std::string site, text;
+            for (uint64_t j = 0; j < n; ++j) {
+                const vsc_bulge_hit &h = rec[j];
+                const uint32_t site_len = (uint32_t)((int)len + VSC_BULGE_D(h.info));
+                site.assign(site_len, 'N');
+                vsc_unpack_bases(ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs[h.contig].offset + h.pos, site_len, &site[0]);
+                text += first_word(guides[h.guide].id) + '\t' + first_word(ix.names[h.contig]) + '\t' + std::to_string(h.pos) + '\t' +
+                        std::to_string(h.pos + site_len) + '\t' + (VSC_BULGE_STRAND(h.info) ? '-' : '+') + '\t' +
+                        (VSC_BULGE_KIND(h.info) == VSC_BULGE_RNA ? "RNA" : "DNA") + '\t' + std::to_string(VSC_BULGE_SIZE(h.info)) + '\t' +
+                        std::to_string(VSC_BULGE_INDEX(h.info)) + '\t' + std::to_string(VSC_BULGE_NM(h.info)) + '\t' + site + '\n';
+                if (text.size() > (1u << 22)) {
+                    out << text;
+                    text.clear();
+                }
+            }
+            out << text;
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the -U file.");
+        }
         rc = 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "ERROR: %s\n", e.what());
@@ -316,6 +412,7 @@ int main(int argc, char **argv)
     }
     vsc_pattern_hits_free(hits);
     vsc_pattern_guides_free(found);
+    vsc_bulge_hits_free(bulge_hits);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);
     return rc;

@@ -18,6 +18,7 @@
 #include "vsc_bulge.h"
 #include "vsc_pattern.h"
 #include "vsc_pattern_enum.h"
+#include "vsc_pattern_bulge.h"
 #include "vsc_enum.h"
 #include "vsc_internal.h"
 #include "vsc_objects.h"
@@ -3331,6 +3332,250 @@ int vsc_pattern_match(const char *pattern, const char *guide, const char *site_t
     if (hit) *hit = acgt && pattern_mismatch(sh, sl, pattern_planes(p_sets, len)) == 0u;
     if (nm) *nm = (uint32_t)__builtin_popcount(x);
     if (mask) *mask = x;
+    return VSC_OK;
+}
+
+// ---- bulges under a pattern (kernels: vsc_pattern_bulge.hip) ---------------------------------------------------
+// vsc_search_pattern's rounds and scratch (the context's pattern pool) with vsc_search_bulges' result object and rows.  Per
+// enabled class the front end gets two tables: the bulged pattern over L + d positions and its reverse complement.
+int vsc_search_pattern_bulges(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
+                              const vsc_pattern_bulge_params *params, vsc_bulge_hits **out, vsc_bulge_summary *rows)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (out) *out = nullptr;
+    ctx->err.clear();
+    const char *const fn = "vsc_search_pattern_bulges";
+    auto refuse = [&](const char *what) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "%s: %s", fn, what);
+        return fail(ctx, VSC_ERR_INVALID, msg);
+    };
+    if (!out && !rows) return refuse("neither records nor rows are asked for");
+    if (!genome || !params || !pattern || (n_guides && !guides)) return refuse("null argument");
+    if (genome->ctx != ctx) return refuse("genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return refuse("the pattern must have 16..32 letters");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return refuse("max_mismatches must be 0..8");
+    uint8_t sets[kPatMaxLen], bulged[kPatMaxLen], rc_sets[kPatMaxLen];
+    if (!pattern_sets(pattern, len, sets)) return refuse("the pattern holds a letter that is no IUPAC letter");
+    if (const char *why = pattern_bulge_refusal(sets, len, params->proto_start, params->proto_len, params->dna_max, params->rna_max))
+        return refuse(why);
+    PatBulgeArgs a{};
+    a.len = len;
+    a.proto_a = params->proto_start;
+    a.proto_e = params->proto_start + params->proto_len;
+    for (uint32_t k = 0; k < kBulgeClasses; ++k) {
+        const int d = bulge_d_of_class(k);
+        if (d < 0 ? (uint32_t)-d > params->rna_max : (uint32_t)d > params->dna_max) continue;
+        a.classes |= 1u << k;
+        const uint32_t site_len = (uint32_t)((int)len + d);
+        pattern_bulged(sets, len, a.proto_a, a.proto_e, d, bulged);
+        pattern_front(bulged, site_len, &a.front[k][0]);
+        pattern_revcomp(bulged, site_len, rc_sets);
+        pattern_front(rc_sets, site_len, &a.front[k][1]);
+    }
+    // every guide as one uint4: its planes in read orientation (the kernels turn the '-' sites)
+    std::vector<uint4> planes(n_guides);
+    for (uint32_t g = 0; g < n_guides; ++g) {
+        if (!pattern_sets(guides + (size_t)g * len, len, sets)) {
+            char msg[120];
+            std::snprintf(msg, sizeof msg, "%s: guide %u holds a letter that is no IUPAC letter", fn, g);
+            return fail(ctx, VSC_ERR_INVALID, msg);
+        }
+        const PatPlanes f = pattern_planes(sets, len);
+        planes[g] = make_uint4(f.a, f.c, f.g, f.t);
+    }
+    std::unique_ptr<vsc_bulge_hits, int (*)(vsc_bulge_hits *)> holder(nullptr, vsc_bulge_hits_free);
+    if (out) {
+        holder.reset(new (std::nothrow) vsc_bulge_hits());
+        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_pattern_bulges: out of host memory");
+        holder->ctx = ctx;
+        holder->host_valid = true;  // (empty until records are written)
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    t.algorithm = VSC_ALGO_SCAN;
+    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_bulge_summary));
+    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
+    if (n_guides == 0 || n_tiles == 0) {
+        t.pairs = 0;
+        ctx->timing = t;
+        if (out) *out = holder.release();
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.n_tiles = n_tiles;
+    a.max_mm = params->max_mismatches;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+
+    const uint32_t batch = std::min(params->guide_batch ? std::min(params->guide_batch, kPatMaxBatch) : kPatDefaultBatch, n_guides);
+    // scratch, 256-byte aligned parts: [rows of all guides][site counter] | per round: [guides][counts][chunk sums][group sums][group offsets]
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
+    const uint64_t max_chunks = (max_cells + kPatChunk - 1) / kPatChunk;
+    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_pattern_bulges: counter table too large");
+    const uint64_t max_groups = (max_chunks + kPatChunk - 1) / kPatChunk;  // the one-workgroup scan takes these, not the chunks
+    const size_t rows_bytes = up((size_t)n_guides * kBulgeRowWords * sizeof(uint32_t));
+    auto table_slots = [](uint32_t n) { return (n + kPatUnroll - 1) / kPatUnroll * kPatUnroll + kPatUnroll; };  // uint4s of the table
+    const size_t guides_bytes = up((size_t)table_slots(batch) * sizeof(uint4));
+    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
+    const size_t groups_bytes = up((size_t)max_groups * sizeof(uint32_t));
+    VSC_HIP(ctx, ctx->pattern_tabs.ensure(rows_bytes + 256 + guides_bytes + count_bytes + sums_bytes + groups_bytes +
+                                          (size_t)(max_groups + 1) * sizeof(unsigned long long)));
+    char *base = (char *)ctx->pattern_tabs.p;
+    uint32_t *d_rows = (uint32_t *)base;
+    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
+    uint4 *d_guides = (uint4 *)(base + rows_bytes + 256);
+    uint32_t *d_count = (uint32_t *)((char *)d_guides + guides_bytes);
+    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
+    uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
+    unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
+    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
+    a.guides = d_guides;
+    a.count = d_count;
+    a.chunk_sum = d_sums;
+    a.group_off = d_off;
+    a.rows = rows ? d_rows : nullptr;
+
+    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
+    struct Release {
+        std::vector<DeviceBuf> &v;
+        ~Release()
+        {
+            for (auto &b : v) b.release();
+        }
+    } release{pieces};
+    std::vector<uint64_t> piece_n;
+    std::vector<uint4> staged;
+    unsigned long long total = 0, found = 0;
+    // the count pass of the round that starts at guide g0 (and, for records, the offsets of its cells): found = its records
+    auto count_round = [&](uint32_t g0) -> int {
+        const uint32_t n = std::min(batch, n_guides - g0);
+        staged.assign(table_slots(n), make_uint4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < n; ++i) staged[i] = planes[g0 + i];
+        VSC_HIP(ctx, hipMemcpyAsync(d_guides, staged.data(), staged.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+        a.n_guides = n;
+        a.guide_base = g0;
+        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
+        const uint64_t cells = (uint64_t)2 * n * n_tiles;
+        const uint32_t chunks = (uint32_t)((cells + kPatChunk - 1) / kPatChunk), groups = (chunks + kPatChunk - 1) / kPatChunk;
+        found = 0;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_pattern_bulge_count(a, ctx->n_cus, ctx->stream));
+        if (out) {
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_sums, chunks, d_groups, ctx->stream));
+            VSC_HIP(ctx, launch_enum_scan(d_groups, groups, d_off, ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + groups, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `staged` is reused by the next round)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        t.passes += 1;
+        total += found;
+        return VSC_OK;
+    };
+    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
+        int rc = count_round(g0);
+        if (rc != VSC_OK) return rc;
+        if (params->max_hits && total > params->max_hits) {
+            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
+            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
+                if ((rc = count_round(h0)) != VSC_OK) return rc;
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "%s: %llu records exceed max_hits = %llu", fn, total, (unsigned long long)params->max_hits);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        float ms = 0;
+        pieces.emplace_back();
+        piece_n.push_back(found);
+        a.records = nullptr;
+        a.n_records = found;
+        if (found) {
+            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_bulge_hit)));
+            a.records = (uint4 *)pieces.back().p;
+        }
+        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch_pattern_bulge_write(a, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        }
+    }
+    unsigned long long sites = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
+    if (rows)
+        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_bulge_summary), hipMemcpyDeviceToHost, ctx->stream));
+    if (out && total) {
+        if (pieces.size() == 1) {
+            holder->storage = pieces[0];
+            pieces[0] = DeviceBuf();
+        } else {
+            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_bulge_hit)));
+            size_t at = 0;
+            for (size_t i = 0; i < pieces.size(); ++i) {
+                if (piece_n[i])
+                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_bulge_hit),
+                                                hipMemcpyDeviceToDevice, ctx->stream));
+                at += (size_t)piece_n[i] * sizeof(vsc_bulge_hit);
+            }
+        }
+        holder->n = total;
+        holder->host_valid = false;
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows && !out)
+        for (uint32_t g = 0; g < n_guides; ++g)
+            for (uint32_t k = 0; k < kBulgeRowWords; ++k) total += (&rows[g].count[0][0])[k];
+    t.total_ms = t.scan_ms;
+    t.hits = total;
+    t.sites = sites;
+    t.pairs = sites * n_guides;
+    ctx->timing = t;
+    if (out) *out = holder.release();
+    return VSC_OK;
+    });
+}
+
+int vsc_pattern_bulge_align(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t proto_start, uint32_t proto_len,
+                            int d, uint32_t *hit, uint32_t *nm, uint32_t *index)
+{
+    if (!pattern || !guide || !site_text || len < kPatMinLen || len > kPatMaxLen || d < -2 || d > 2 || d == 0) return VSC_ERR_INVALID;
+    uint8_t p_sets[kPatMaxLen], g_sets[kPatMaxLen], bulged[kPatMaxLen];
+    if (!pattern_sets(pattern, len, p_sets) || !pattern_sets(guide, len, g_sets)) return VSC_ERR_INVALID;
+    if (pattern_bulge_refusal(p_sets, len, proto_start, proto_len, d > 0 ? (uint32_t)d : 0u, d < 0 ? (uint32_t)-d : 0u)) return VSC_ERR_INVALID;
+    const uint32_t site_len = (uint32_t)((int)len + d), a = proto_start, e = proto_start + proto_len;
+    if (strnlen(site_text, site_len + 1u) != site_len) return VSC_ERR_INVALID;
+    uint32_t sh = 0, sl = 0;
+    bool acgt = true;
+    for (uint32_t j = 0; j < site_len; ++j) {
+        const int c = base_code(site_text[j]);
+        if (c > 3) {
+            acgt = false;
+            break;
+        }
+        sh |= (uint32_t)(c >> 1) << j;
+        sl |= (uint32_t)(c & 1) << j;
+    }
+    pattern_bulged(p_sets, len, a, e, d, bulged);
+    const bool ok = acgt && pattern_mismatch(sh, sl, pattern_planes(bulged, site_len)) == 0u;
+    uint32_t at = 0;
+    const uint32_t best = ok ? pattern_bulge_align(sh, sl, pattern_planes(g_sets, len), a, e, d, &at) : 0u;
+    if (hit) *hit = ok;
+    if (nm) *nm = best;
+    if (index) *index = ok ? at : 0u;
     return VSC_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "vsc_internal.h"
 #include "vsc_device.h"
 #include "vsc_pattern.h"
+#include "vsc_pattern_device.h"
 #include "vsc_pattern_enum.h"
 
 namespace vsc {
@@ -41,19 +42,6 @@ struct PatLds {
     uint16_t q[kPatQueue];  // lane << 5 | bit, ascending
     uint32_t row[16];       // write pass: the cell's hits by NM
 };
-
-// The start mask of one strand: bit b = the site that starts at bit b of the lane's word satisfies the table.
-__device__ __forceinline__ uint32_t pattern_starts(const PatFront &f, uint32_t H0, uint32_t H1, uint32_t L0, uint32_t L1)
-{
-    uint32_t ok = ~0u;
-    for (uint32_t i = 0; i < f.n; ++i) {
-        const uint32_t e = f.ent[i], j = e & 31u;  // wave-uniform
-        const uint32_t h = funnel(H1, H0, j), l = funnel(L1, L0, j);
-        const uint32_t tA = 0u - ((e >> 8) & 1u), tC = 0u - ((e >> 9) & 1u), tG = 0u - ((e >> 10) & 1u), tT = 0u - ((e >> 11) & 1u);
-        ok &= (~h & ~l & tA) | (~h & l & tC) | (h & ~l & tG) | (h & l & tT);
-    }
-    return ok;
-}
 
 // A lane's word of each plane with its right neighbour, and the two start masks of its 32 starts (both searches' and the
 // enumeration's front end).  kArgs: PatternArgs or PatEnumArgs.
@@ -88,26 +76,6 @@ __device__ __forceinline__ void pattern_tile(const PatternArgs &a, uint32_t tile
     }
 }
 
-// exclusive prefix of v over the lanes of the wave; *total = the wave's sum (enum_kernel's)
-__device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t lane, uint32_t *total)
-{
-    uint32_t s = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)s, d, kWave);
-        if (lane >= (uint32_t)d) s += o;
-    }
-    *total = uniform((uint32_t)__shfl((int)s, kWave - 1, kWave));
-    return s - v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, kWave);
-    return v;
-}
-
 // The starts of mask m into the queue, in ascending order over the wave; returns how many there are.  The hand-offs before
 // (the planes, the queue's last readers) and after are the caller's.
 __device__ __forceinline__ uint32_t pattern_enqueue(PatLds &s, uint32_t m, uint32_t lane)
@@ -127,9 +95,6 @@ __device__ __forceinline__ void pattern_site(const PatLds &s, uint32_t e, uint32
 }
 
 __device__ __forceinline__ PatPlanes planes_of(v4u v) { return PatPlanes{v.x, v.y, v.z, v.w}; }
-
-typedef uint32_t v16u __attribute__((ext_vector_type(16)));
-typedef const __attribute__((address_space(4))) v16u *const_v16u_ptr;
 
 // One step of the count pass: kSlots x 64 queued sites from `base` on against every guide of the round; lane g adds the hits
 // of guide g to cnt.  An instance per number of slots (kPatSlots of them) instead of a test per slot and guide: the last step
@@ -164,15 +129,6 @@ __device__ __forceinline__ void pattern_count_step(const PatLds &s, const_v16u_p
             if (lane == g + u) cnt += hits;  // (a guide that pads the last four is all zero: it allows nothing and never hits)
         }
     }
-}
-
-// tiles [*t0, *t1) of wave `w` of `n_waves`: runs of consecutive tiles, so that the cells a wave stores lie side by side
-__device__ __forceinline__ void pattern_tile_run(uint32_t n_tiles, uint32_t w, uint32_t n_waves, uint32_t *t0, uint32_t *t1)
-{
-    const uint32_t per = (n_tiles + n_waves - 1u) / n_waves;
-    const uint64_t first = (uint64_t)w * per;
-    *t0 = first < n_tiles ? (uint32_t)first : n_tiles;
-    *t1 = first + per < n_tiles ? (uint32_t)(first + per) : n_tiles;
 }
 
 }  // namespace
