@@ -125,6 +125,21 @@ def test_max_hits(edge, edge_gen):
     same(search(edge_gen, edge, max_hits=n), edge["hits"], len(edge["guides"]))
 
 
+def test_max_hits_in_the_first_round(edge, edge_gen):
+    """The cap trips in round 0: the rounds behind it are counted only (the message names the whole call's records), nothing
+    of them is written, and the next call finds the context and the genome as they were."""
+    n, n_guides = len(edge["hits"]), len(edge["guides"])
+    batch = next(b for b in range(1, n_guides + 1) if sum(h[0] < b for h in edge["hits"]) >= 2)
+    first = sum(h[0] < batch for h in edge["hits"])
+    cap = first - 1
+    assert cap >= 1 and first > cap and -(-n_guides // batch) - 1 >= 2 and n > first
+    with pytest.raises(va.VarscotError) as err:
+        search(edge_gen, edge, max_hits=cap, guide_batch=batch)
+    assert err.value.code == -34 and (" %d records" % n) in str(err.value) and ("max_hits = %d" % cap) in str(err.value)
+    assert "vsc_search_pattern_bulges" in str(err.value)
+    same(search(edge_gen, edge, guide_batch=batch), edge["hits"], n_guides)
+
+
 # ---- 7. shards ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("world", [2, 3])
 def test_shards_merge_to_the_whole(ctx, edge, world):

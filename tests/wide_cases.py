@@ -21,7 +21,7 @@ import pattern_enum_cases as pe
 
 TILE = 2048
 GAP = 64
-WAVES_PER_GROUP, GROUPS_PER_CU = 4, 8   # pattern_grid / bulge_grid / pb_grid: at most CUs x 8 workgroups of 4 waves
+WAVES_PER_GROUP, GROUPS_PER_CU = 4, 8   # cell_grid (vsc_cells_device.h): at most CUs x 8 workgroups of 4 waves
 CHUNK = 64                              # cells per chunk, chunks per group
 SCAN_THREADS = 1024                     # enum_scan_kernel: one workgroup; beyond 1 024 entries a thread walks several
 SHORT_MAX, BODY_TILES = 900, 3

@@ -1,8 +1,18 @@
 // vsc_api.cpp - the C ABI of include/varscot_hip.h: context, resident genome, search orchestration
-// (find -> summary / selection -> bin sort, one pass loop: run_search) and per-hit scoring.  Host C++ only; all device
-// work is in the kernel files - vsc_kernels.hip (scan, summary, selection, scoring, forest, merge), vsc_seed.hip (seed
-// index and search), vsc_sort.hip (bin sort), vsc_enum.hip (guide discovery, labels), vsc_pairs.hip (guide pairs and their paired sites), vsc_bulge.hip (bulge-tolerant search), vsc_pattern.hip (pattern search).  No CPU implementation of the search exists in this library: without a HIP
-// device every compute entry point fails with VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
+// (find -> summary / selection -> bin sort, one pass loop: run_search), the count / scan / write searches and
+// enumerations (one rounds driver: run_rounds; one two-pass body: run_enumeration) and per-hit scoring.  Host C++ only; all
+// device work is in the kernel files:
+//   vsc_kernels.hip        scan, summary, selection, scoring, forest, merge
+//   vsc_seed.hip           seed index and search
+//   vsc_sort.hip           bin sort
+//   vsc_enum.hip           guide discovery, labels
+//   vsc_pairs.hip          guide pairs and their paired sites
+//   vsc_variants.hip       the window side of the variant mergers
+//   vsc_bulge.hip          bulge-tolerant search
+//   vsc_pattern.hip        pattern search, pattern guide discovery
+//   vsc_pattern_bulge.hip  bulges under a pattern
+// No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
+// VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -2583,6 +2593,345 @@ int variant_error(vsc_ctx *ctx, const VariantArgs &a, const char *who)
     return VSC_OK;
 }
 
+// the planes and the contig table of a resident genome, as the kernels of the enumerations and of the rounds read them
+template <class Args> void bind_genome(Args &a, const vsc_genome *genome)
+{
+    a.hi = genome->d_hi;
+    a.lo = genome->d_lo;
+    a.nm = genome->d_nm;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+}
+
+// ---- the result objects of the enumerations and of the rounds (vsc::GuideList, vsc::RecordList) ---------------------------
+template <class Guides> int guide_list_data(Guides *guides, const uint64_t **codes, const vsc_locus **loci)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    return guarded(guides->ctx, [&]() -> int {
+    if (!guides->host_valid) {
+        vsc_ctx *ctx = guides->ctx;
+        guides->codes.resize(guides->n);
+        guides->loci.resize(guides->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->codes.data(), guides->storage.p, guides->n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(guides->loci.data(), (const char *)guides->storage.p + guides->loci_at, guides->n * sizeof(vsc_locus),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        guides->host_valid = true;
+    }
+    if (codes) *codes = guides->codes.data();
+    if (loci) *loci = guides->loci.data();
+    return VSC_OK;
+    });
+}
+
+int guide_list_data_dev(const GuideList *guides, const void **codes_dev, const void **loci_dev)
+{
+    if (!guides) return VSC_ERR_INVALID;
+    const bool dev = guides->ctx && guides->n && guides->storage.p;  // (storage is a context's: no ctx, no storage)
+    if (codes_dev) *codes_dev = dev ? guides->storage.p : nullptr;
+    if (loci_dev) *loci_dev = dev ? (const char *)guides->storage.p + guides->loci_at : nullptr;
+    return VSC_OK;
+}
+
+template <class Hits> int record_list_data(Hits *hits, const typename Hits::record **out)
+{
+    if (!hits || !out) return VSC_ERR_INVALID;
+    return guarded(hits->ctx, [&]() -> int {
+    if (!hits->host_valid) {
+        vsc_ctx *ctx = hits->ctx;
+        hits->host.resize(hits->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(hits->host.data(), hits->storage.p, hits->n * sizeof(typename Hits::record), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hits->host_valid = true;
+    }
+    *out = hits->host.data();
+    return VSC_OK;
+    });
+}
+
+template <class Rec> const void *record_list_data_dev(const RecordList<Rec> *hits) { return hits && hits->n ? hits->storage.p : nullptr; }
+
+// frees a GuideList or a RecordList by its handle type (the objects have no virtual destructor)
+template <class Object> int object_free(Object *o)
+{
+    if (!o) return VSC_OK;
+    if (o->ctx && o->storage.p) {
+        (void)hipSetDevice(o->ctx->device);
+        o->storage.release();
+    }
+    delete o;
+    return VSC_OK;
+}
+
+// ---- the two passes of the enumerations ----------------------------------------------------------------
+// Count pass over the work list, exclusive scan of the per-tile counts, one 8-byte read-back (the total: it sizes the result
+// and is what max_guides is checked against), write pass into the result's own arrays.  The caller has filled `a` but for
+// the work list, the counts, the offsets and the result; work == null: tiles 0 .. n_work - 1.  `tail` is a table of the
+// caller's that goes to the device behind the scratch of the passes.  launch(d_tail, total, write) starts a pass.
+template <class Guides, class Args, class Launch>
+int run_enumeration(vsc_ctx *ctx, const char *fn, Args &a, const std::vector<uint32_t> *work, uint32_t n_work, const void *tail,
+                    size_t tail_bytes, uint64_t max_guides, Guides **out, Launch launch)
+{
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    std::unique_ptr<Guides, int (*)(Guides *)> g(new (std::nothrow) Guides(), object_free<Guides>);
+    if (!g) return fail_in(ctx, VSC_ERR_NOMEM, fn, "out of host memory");
+    g->ctx = ctx;
+    unsigned long long total = 0;
+    if (n_work) {
+        // scratch: [work list][counts][offsets][tail], 256-byte aligned parts
+        const size_t list_bytes = round256((size_t)n_work * sizeof(uint32_t));
+        const size_t off_bytes = round256(((size_t)n_work + 1) * sizeof(unsigned long long));
+        VSC_HIP(ctx, ctx->enum_tabs.ensure(2 * list_bytes + off_bytes + tail_bytes));
+        char *base = (char *)ctx->enum_tabs.p;
+        unsigned long long *d_off = (unsigned long long *)(base + 2 * list_bytes);
+        char *d_tail = tail_bytes ? base + 2 * list_bytes + off_bytes : nullptr;
+        if (work) {
+            VSC_HIP(ctx, hipMemcpyAsync(base, work->data(), (size_t)n_work * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            a.work = (const uint32_t *)base;
+        }
+        if (tail_bytes) VSC_HIP(ctx, hipMemcpyAsync(d_tail, tail, tail_bytes, hipMemcpyHostToDevice, ctx->stream));
+        a.n_work = n_work;
+        a.tile_count = (uint32_t *)(base + list_bytes);
+        a.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch(d_tail, total, false));
+        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list and the tail are the caller's vectors)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+        t.passes = 1;
+        if (max_guides && total > max_guides) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "%s: %llu candidates exceed max_guides = %llu", fn, total, (unsigned long long)max_guides);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        if (total) {
+            g->loci_at = round256((size_t)total * sizeof(uint64_t));
+            VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
+            a.codes = (unsigned long long *)g->storage.p;
+            a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch(d_tail, total, true));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
+            t.passes = 2;
+        }
+    }
+    g->n = total;
+    if (total == 0) g->host_valid = true;
+    t.total_ms = t.scan_ms;
+    t.sites = total;
+    ctx->timing = t;
+    *out = g.release();
+    return VSC_OK;
+}
+
+// ---- the rounds of the count / scan / write searches ---------------------------------------------------------
+// Per round of `batch` guides: count pass (hits per (guide, strand, tile) cell), sums per 64 cells - and, with two levels,
+// per 64 of those, so that the one-workgroup scan sees a 64th of the chunks (at 3 Gbp and 16 guides: 11 000 entries, not
+// 730 000) - exclusive scan of the sums, one 8-byte read-back (the round's records), write pass into the round's own buffer.
+// The rounds' buffers are consecutive pieces of the result (the order starts with the guide); with more than one round they
+// are copied into one array.
+static_assert(kPatChunk == kBulgeChunk, "the sums of every round are taken per kBulgeChunk cells");
+
+// What a search tells run_rounds about itself.
+struct RoundsPlan {
+    const char *fn;  // for messages
+    uint32_t n_guides, n_tiles;
+    uint32_t batch;       // guides per round
+    DeviceBuf *pool;      // the context's scratch of the search's family
+    uint32_t levels;      // 1: offsets per chunk of 64 cells; 2: per group of 64 chunks
+    uint32_t row_words;   // 32-bit words of a guide's row
+    uint64_t max_hits;    // 0: no cap
+};
+
+// What the launches of a round are bound to.
+struct Round {
+    uint32_t g0, n;                 // guides [g0, g0 + n) of the call
+    const uint4 *guides;            // the round's table, as the search staged it
+    uint32_t *count;                // hits per cell
+    const uint32_t *chunk_sum;      // two levels: hits per chunk
+    const unsigned long long *off;  // hits of all cells before a chunk (one level) or a group (two)
+    unsigned long long *sites;
+    uint32_t *rows;                 // null: no rows are asked for
+    void *records;                  // write pass: the round's piece (null: it has no records)
+    unsigned long long n_records;
+};
+
+// table_uint4s(n): the uint4s of the table of a round of n guides; stage(g0, n, table): fills that table, zeroed, for guides
+// [g0, g0 + n); launch(round, write): the count or the write kernel on the round.
+template <class Hits, class Slots, class Stage, class Launch>
+int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Slots table_uint4s, Stage stage, Launch launch)
+{
+    const size_t rec_bytes = sizeof(typename Hits::record);
+    std::unique_ptr<Hits, int (*)(Hits *)> holder(nullptr, object_free<Hits>);
+    if (out) {
+        holder.reset(new (std::nothrow) Hits());
+        if (!holder) return fail_in(ctx, VSC_ERR_NOMEM, p.fn, "out of host memory");
+        holder->ctx = ctx;
+        holder->host_valid = true;  // (empty until records are written)
+    }
+    vsc_timing t{};
+    t.index_ms = ctx->timing.index_ms;
+    t.algorithm = VSC_ALGO_SCAN;
+    const size_t rows_words = (size_t)p.n_guides * p.row_words;
+    if (rows) std::memset(rows, 0, rows_words * sizeof(uint32_t));
+    const uint32_t n_guides = p.n_guides, n_tiles = p.n_tiles, batch = p.batch;
+    if (n_guides == 0 || n_tiles == 0) {
+        t.pairs = 0;
+        ctx->timing = t;
+        if (out) *out = holder.release();
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    // scratch, 256-byte aligned parts: [rows of all guides][site counter] | per round: [guides][counts][chunk sums][group sums
+    // (two levels)][offsets of the chunks or groups]
+    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
+    const uint64_t max_chunks = (max_cells + kBulgeChunk - 1) / kBulgeChunk;
+    if (max_chunks >= (1ull << 32)) return fail_in(ctx, VSC_ERR_RANGE, p.fn, "counter table too large");
+    const bool grouped = p.levels == 2;
+    const uint64_t max_groups = (max_chunks + kBulgeChunk - 1) / kBulgeChunk;  // the one-workgroup scan takes these, not the chunks
+    const size_t rows_bytes = round256(rows_words * sizeof(uint32_t));
+    const size_t table_bytes = round256((size_t)table_uint4s(batch) * sizeof(uint4));
+    const size_t count_bytes = round256((size_t)max_cells * sizeof(uint32_t)), sums_bytes = round256((size_t)max_chunks * sizeof(uint32_t));
+    const size_t groups_bytes = grouped ? round256((size_t)max_groups * sizeof(uint32_t)) : 0;
+    VSC_HIP(ctx, p.pool->ensure(rows_bytes + 256 + table_bytes + count_bytes + sums_bytes + groups_bytes +
+                                (size_t)((grouped ? max_groups : max_chunks) + 1) * sizeof(unsigned long long)));
+    char *base = (char *)p.pool->p;
+    uint32_t *d_rows = (uint32_t *)base;
+    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
+    uint4 *d_table = (uint4 *)(base + rows_bytes + 256);
+    uint32_t *d_count = (uint32_t *)((char *)d_table + table_bytes);
+    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
+    uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
+    unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
+    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
+    Round r{};
+    r.guides = d_table;
+    r.count = d_count;
+    r.chunk_sum = d_sums;
+    r.off = d_off;
+    r.rows = rows ? d_rows : nullptr;
+
+    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
+    struct Release {
+        std::vector<DeviceBuf> &v;
+        ~Release()
+        {
+            for (auto &b : v) b.release();
+        }
+    } release{pieces};
+    std::vector<uint64_t> piece_n;
+    std::vector<uint4> staged;
+    unsigned long long total = 0, found = 0;
+    // the count pass of the round that starts at guide g0 (and, for records, the offsets of its cells): found = its records
+    auto count_round = [&](uint32_t g0) -> int {
+        r.g0 = g0;
+        r.n = std::min(batch, n_guides - g0);
+        staged.assign(table_uint4s(r.n), make_uint4(0, 0, 0, 0));
+        stage(g0, r.n, staged.data());
+        VSC_HIP(ctx, hipMemcpyAsync(d_table, staged.data(), staged.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+        r.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
+        const uint64_t cells = (uint64_t)2 * r.n * n_tiles;
+        const uint32_t chunks = (uint32_t)((cells + kBulgeChunk - 1) / kBulgeChunk), groups = (chunks + kBulgeChunk - 1) / kBulgeChunk;
+        const uint32_t scanned = grouped ? groups : chunks;
+        found = 0;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch(r, false));
+        if (out) {
+            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
+            if (grouped) VSC_HIP(ctx, launch_bulge_chunk_sums(d_sums, chunks, d_groups, ctx->stream));
+            VSC_HIP(ctx, launch_enum_scan(grouped ? d_groups : d_sums, scanned, d_off, ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + scanned, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `staged` is reused by the next round)
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        t.scan_ms += ms;
+        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        t.passes += 1;
+        total += found;
+        return VSC_OK;
+    };
+    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
+        int rc = count_round(g0);
+        if (rc != VSC_OK) return rc;
+        if (p.max_hits && total > p.max_hits) {
+            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
+            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
+                if ((rc = count_round(h0)) != VSC_OK) return rc;
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "%s: %llu records exceed max_hits = %llu", p.fn, total, (unsigned long long)p.max_hits);
+            return fail(ctx, VSC_ERR_RANGE, msg);
+        }
+        float ms = 0;
+        pieces.emplace_back();
+        piece_n.push_back(found);
+        r.records = nullptr;
+        r.n_records = found;
+        if (found) {
+            VSC_HIP(ctx, pieces.back().ensure((size_t)found * rec_bytes));
+            r.records = pieces.back().p;
+        }
+        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch(r, true));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.scan_ms += ms;
+            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
+        }
+    }
+    unsigned long long sites = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, rows_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out && total) {
+        if (pieces.size() == 1) {
+            holder->storage = pieces[0];
+            pieces[0] = DeviceBuf();
+        } else {
+            VSC_HIP(ctx, holder->storage.ensure((size_t)total * rec_bytes));
+            size_t at = 0;
+            for (size_t i = 0; i < pieces.size(); ++i) {
+                if (piece_n[i])
+                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * rec_bytes, hipMemcpyDeviceToDevice,
+                                                ctx->stream));
+                at += (size_t)piece_n[i] * rec_bytes;
+            }
+        }
+        holder->n = total;
+        holder->host_valid = false;
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rows && !out)
+        for (size_t k = 0; k < rows_words; ++k) total += rows[k];
+    t.total_ms = t.scan_ms;
+    t.hits = total;
+    t.sites = sites;
+    t.pairs = sites * n_guides;
+    ctx->timing = t;
+    if (out) *out = holder.release();
+    return VSC_OK;
+}
+
+// uint4s of one table of n pattern guides: padded to kPatUnroll, plus kPatUnroll spare (the count pass fetches ahead)
+uint32_t pattern_table_slots(uint32_t n) { return (n + kPatUnroll - 1) / kPatUnroll * kPatUnroll + kPatUnroll; }
+
+
 }  // namespace
 
 extern "C" {
@@ -2670,9 +3019,7 @@ int vsc_search_select_classified(vsc_ctx *ctx, const vsc_genome *genome, const u
     });
 }
 
-// ---- guide discovery (kernels: vsc_enum.hip) -------------------------------------------------------------------------------
-// Count pass over the work list, exclusive scan of the per-tile counts, one 8-byte read-back (the total: it sizes the result
-// and is what max_guides is checked against), write pass into the result's own arrays.
+// ---- guide discovery (kernels: vsc_enum.hip; the passes: run_enumeration) --------------------------------------------------
 int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const vsc_enum_params *params,
                          vsc_guides **out)
 {
@@ -2680,25 +3027,22 @@ int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regio
     if (!ctx || !out) return VSC_ERR_INVALID;
     *out = nullptr;
     ctx->err.clear();
-    if (!genome || !params) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: null argument");
-    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: genome belongs to another context");
+    const char *const fn = "vsc_guides_enumerate";
+    if (!genome || !params) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
     const int p0 = base_code(params->pam[0]), p1 = base_code(params->pam[1]);
-    if (p0 > 3 || p1 > 3) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: the PAM must be two letters of ACGT");
-    if (params->strands > 2) return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: strands must be 0 (both), 1 ('+') or 2 ('-')");
+    if (p0 > 3 || p1 > 3) return fail_in(ctx, VSC_ERR_INVALID, fn, "the PAM must be two letters of ACGT");
+    if (params->strands > 2) return fail_in(ctx, VSC_ERR_INVALID, fn, "strands must be 0 (both), 1 ('+') or 2 ('-')");
     if (params->gc_min > 20 || params->gc_max > 20 || (params->gc_max && params->gc_min > params->gc_max))
-        return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: GC bounds must satisfy gc_min <= gc_max <= 20 (gc_max 0: no upper bound)");
-    if (params->reserved0 || params->reserved[0] || params->reserved[1])
-        return fail(ctx, VSC_ERR_INVALID, "vsc_guides_enumerate: reserved fields must be 0");
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "GC bounds must satisfy gc_min <= gc_max <= 20 (gc_max 0: no upper bound)");
+    if (params->reserved0 || params->reserved[0] || params->reserved[1]) return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields must be 0");
     VSC_HIP(ctx, hipSetDevice(ctx->device));
     EnumArgs a{};
     if (regions) {
-        const int rrc = resident_regions(ctx, genome, regions, "vsc_guides_enumerate", a.reg);
+        const int rrc = resident_regions(ctx, genome, regions, fn, a.reg);
         if (rrc != VSC_OK) return rrc;
     }
-    a.hi = genome->d_hi;
-    a.lo = genome->d_lo;
-    a.nm = genome->d_nm;
-    a.first_pos = (uint32_t)(genome->first_word * 32);
+    bind_genome(a, genome);
     a.pam = pam_masks(p0, p1);
     a.keep_fwd = params->strands != 2 ? 0xFFFFFFFFu : 0u;
     a.keep_rev = params->strands != 1 ? 0xFFFFFFFFu : 0u;
@@ -2706,9 +3050,6 @@ int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regio
     a.gc_max = params->gc_max ? params->gc_max : 20u;
     a.max_t_run = params->max_t_run;
     a.filter = (a.gc_min > 0 || a.gc_max < 20 || a.max_t_run) ? 1u : 0u;
-    a.contig_off = genome->d_contig_off;
-    a.contig_end = genome->d_contig_end;
-    a.n_contigs = genome->n_contigs;
 
     // the work list: with regions, the tiles that hold a block of the class table that is not OUT (a block is >= 32 starts,
     // a tile 2 048: 64 blocks or fewer); without, every tile of the shard
@@ -2725,115 +3066,20 @@ int vsc_guides_enumerate(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regio
         }
         n_work = (uint32_t)work.size();
     }
-    vsc_timing t{};
-    t.index_ms = ctx->timing.index_ms;
-    vsc_guides *g = new (std::nothrow) vsc_guides();
-    if (!g) return fail(ctx, VSC_ERR_NOMEM, "vsc_guides_enumerate: out of host memory");
-    std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> holder(g, vsc_guides_free);
-    g->ctx = ctx;
-    unsigned long long total = 0;
-    if (n_work) {
-        // scratch: [work list][counts][offsets], 256-byte aligned parts
-        const size_t list_bytes = ((size_t)n_work * sizeof(uint32_t) + 255) / 256 * 256;
-        VSC_HIP(ctx, ctx->enum_tabs.ensure(2 * list_bytes + ((size_t)n_work + 1) * sizeof(unsigned long long)));
-        char *base = (char *)ctx->enum_tabs.p;
-        unsigned long long *d_off = (unsigned long long *)(base + 2 * list_bytes);
-        if (regions) {
-            VSC_HIP(ctx, hipMemcpyAsync(base, work.data(), (size_t)n_work * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            a.work = (const uint32_t *)base;
-        }
-        a.n_work = n_work;
-        a.tile_count = (uint32_t *)(base + list_bytes);
-        a.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-        VSC_HIP(ctx, launch_enum(a, false, regions != nullptr, ctx->stream));
-        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list above is this call's vector)
-        float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-        t.scan_ms += ms;
-        t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
-        t.passes = 1;
-        if (params->max_guides && total > params->max_guides) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "vsc_guides_enumerate: %llu candidates exceed max_guides = %llu", total,
-                          (unsigned long long)params->max_guides);
-            return fail(ctx, VSC_ERR_RANGE, msg);
-        }
-        if (total) {
-            g->loci_at = ((size_t)total * sizeof(uint64_t) + 255) / 256 * 256;
-            VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
-            a.codes = (unsigned long long *)g->storage.p;
-            a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-            VSC_HIP(ctx, launch_enum(a, true, regions != nullptr, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-            t.scan_ms += ms;
-            t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
-            t.passes = 2;
-        }
-    }
-    g->n = total;
-    if (total == 0) g->host_valid = true;
-    t.total_ms = t.scan_ms;
-    t.sites = total;
-    ctx->timing = t;
-    *out = holder.release();
-    return VSC_OK;
+    return run_enumeration(ctx, fn, a, regions ? &work : nullptr, n_work, nullptr, 0, params->max_guides, out,
+                           [&](const void *, unsigned long long, bool write) { return launch_enum(a, write, regions != nullptr, ctx->stream); });
     });
 }
 
 uint64_t vsc_guides_count(const vsc_guides *guides) { return guides ? guides->n : 0; }
-
-int vsc_guides_data(vsc_guides *guides, const uint64_t **codes, const vsc_locus **loci)
-{
-    if (!guides) return VSC_ERR_INVALID;
-    return guarded(guides->ctx, [&]() -> int {
-    if (!guides->host_valid) {
-        vsc_ctx *ctx = guides->ctx;
-        guides->codes.resize(guides->n);
-        guides->loci.resize(guides->n);
-        VSC_HIP(ctx, hipSetDevice(ctx->device));
-        VSC_HIP(ctx, hipMemcpyAsync(guides->codes.data(), guides->storage.p, guides->n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(guides->loci.data(), (const char *)guides->storage.p + guides->loci_at, guides->n * sizeof(vsc_locus),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        guides->host_valid = true;
-    }
-    if (codes) *codes = guides->codes.data();
-    if (loci) *loci = guides->loci.data();
-    return VSC_OK;
-    });
-}
-
+int vsc_guides_data(vsc_guides *guides, const uint64_t **codes, const vsc_locus **loci) { return guide_list_data(guides, codes, loci); }
 int vsc_guides_data_dev(const vsc_guides *guides, const void **codes_dev, const void **loci_dev)
 {
-    if (!guides) return VSC_ERR_INVALID;
-    const bool dev = guides->ctx && guides->n && guides->storage.p;
-    if (codes_dev) *codes_dev = dev ? guides->storage.p : nullptr;
-    if (loci_dev) *loci_dev = dev ? (const char *)guides->storage.p + guides->loci_at : nullptr;
-    return VSC_OK;
+    return guide_list_data_dev(guides, codes_dev, loci_dev);
 }
+int vsc_guides_free(vsc_guides *guides) { return object_free(guides); }
 
-int vsc_guides_free(vsc_guides *guides)
-{
-    if (!guides) return VSC_OK;
-    if (guides->ctx && guides->storage.p) {
-        (void)hipSetDevice(guides->ctx->device);
-        guides->storage.release();
-    }
-    delete guides;
-    return VSC_OK;
-}
-
-// ---- bulge-tolerant search (kernels: vsc_bulge.hip) -----------------------------------------------------------
-// Per round of guide_batch reads: count pass (hits per (read, strand, tile) cell), sums per 64 cells, exclusive scan of the
-// sums, one 8-byte read-back (the round's records), write pass into the round's own buffer.  The rounds' buffers are
-// consecutive pieces of the result (the order starts with the read); with more than one round they are copied into one array.
+// ---- bulge-tolerant search (kernels: vsc_bulge.hip; the rounds: run_rounds, one level of sums) ----------------
 int vsc_search_bulges(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *params,
                       const vsc_bulge_params *bulge_params, vsc_bulge_hits **out, vsc_bulge_summary *rows)
 {
@@ -2841,218 +3087,61 @@ int vsc_search_bulges(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *gu
     if (!ctx) return VSC_ERR_INVALID;
     if (out) *out = nullptr;
     ctx->err.clear();
-    if (!out && !rows) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: neither records nor rows are asked for");
-    if (!genome || !params || !bulge_params || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: null argument");
-    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: genome belongs to another context");
-    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: max_mismatches must be 0..8");
+    const char *const fn = "vsc_search_bulges";
+    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, fn, "neither records nor rows are asked for");
+    if (!genome || !params || !bulge_params || (n_guides && !guides)) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail_in(ctx, VSC_ERR_INVALID, fn, "max_mismatches must be 0..8");
     if (params->algorithm != VSC_ALGO_AUTO && params->algorithm != VSC_ALGO_SCAN)
-        return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: algorithm must be VSC_ALGO_AUTO or VSC_ALGO_SCAN (no seed index is used)");
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "algorithm must be VSC_ALGO_AUTO or VSC_ALGO_SCAN (no seed index is used)");
     if (bulge_params->dna_max > 2 || bulge_params->rna_max > 2 || (bulge_params->dna_max == 0 && bulge_params->rna_max == 0))
-        return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: dna_max and rna_max must be 0..2 and not both 0");
-    if (bulge_params->reserved) return fail(ctx, VSC_ERR_INVALID, "vsc_search_bulges: reserved fields must be 0");
-    std::unique_ptr<vsc_bulge_hits, int (*)(vsc_bulge_hits *)> holder(nullptr, vsc_bulge_hits_free);
-    if (out) {
-        holder.reset(new (std::nothrow) vsc_bulge_hits());
-        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_bulges: out of host memory");
-        holder->ctx = ctx;
-        holder->host_valid = true;  // (empty until records are written)
-    }
-    vsc_timing t{};
-    t.index_ms = ctx->timing.index_ms;
-    t.algorithm = VSC_ALGO_SCAN;
-    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_bulge_summary));
-    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
-    if (n_guides == 0 || n_tiles == 0) {
-        t.pairs = 0;
-        ctx->timing = t;
-        if (out) *out = holder.release();
-        return VSC_OK;
-    }
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "dna_max and rna_max must be 0..2 and not both 0");
+    if (bulge_params->reserved) return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields must be 0");
     ScanArgs pams{};
     fill_pam(pams, params);
     BulgeArgs a{};
-    a.hi = genome->d_hi;
-    a.lo = genome->d_lo;
-    a.nm = genome->d_nm;
-    a.first_pos = (uint32_t)(genome->first_word * 32);
-    a.n_tiles = n_tiles;
+    bind_genome(a, genome);
+    a.n_tiles = genome->d_hi ? genome->n_tiles : 0;
     a.max_mm = params->max_mismatches;
     a.n_pam = pams.n_pam;
     for (uint32_t i = 0; i < pams.n_pam; ++i) a.pam[i] = pams.pam[i];
     a.dna_max = bulge_params->dna_max;
     a.rna_max = bulge_params->rna_max;
-    a.contig_off = genome->d_contig_off;
-    a.contig_end = genome->d_contig_end;
-    a.n_contigs = genome->n_contigs;
 
+    static_assert(sizeof(vsc_bulge_summary) == kBulgeRowWords * sizeof(uint32_t), "a row is its counts");
     const uint32_t batch = std::min(bulge_params->guide_batch ? std::min(bulge_params->guide_batch, kBulgeMaxBatch) : kBulgeDefaultBatch, n_guides);
-    // scratch, 256-byte aligned parts: [rows of all reads][site counter] | per round: [reads][counts][chunk sums][chunk offsets]
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
-    const uint64_t max_chunks = (max_cells + kBulgeChunk - 1) / kBulgeChunk;
-    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_bulges: counter table too large");
-    const size_t rows_bytes = up((size_t)n_guides * kBulgeRowWords * sizeof(uint32_t));
-    auto read_slots = [](uint32_t n) { return ((size_t)n + kBulgeUnroll - 1) / kBulgeUnroll * (kBulgeUnroll / 2) + kBulgeUnroll / 2; };  // uint4s: two reads each
-    const size_t reads_bytes = up(read_slots(batch) * sizeof(uint4));
-    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
-    VSC_HIP(ctx, ctx->bulge_tabs.ensure(rows_bytes + 256 + reads_bytes + count_bytes + sums_bytes + (size_t)(max_chunks + 1) * sizeof(unsigned long long)));
-    char *base = (char *)ctx->bulge_tabs.p;
-    uint32_t *d_rows = (uint32_t *)base;
-    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
-    uint4 *d_reads = (uint4 *)(base + rows_bytes + 256);
-    uint32_t *d_count = (uint32_t *)((char *)d_reads + reads_bytes);
-    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
-    unsigned long long *d_off = (unsigned long long *)((char *)d_sums + sums_bytes);
-    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
-    a.guides = d_reads;
-    a.count = d_count;
-    a.chunk_off = d_off;
-    a.sites = d_sites;
-    a.rows = rows ? d_rows : nullptr;
-
-    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
-    struct Release {
-        std::vector<DeviceBuf> &v;
-        ~Release()
-        {
-            for (auto &b : v) b.release();
-        }
-    } release{pieces};
-    std::vector<uint64_t> piece_n;
-    std::vector<uint4> reads;
-    unsigned long long total = 0, found = 0;
-    // the count pass of the round that starts at read g0 (and, for records, the offsets of its cells): found = its records
-    auto count_round = [&](uint32_t g0) -> int {
-        const uint32_t n = std::min(batch, n_guides - g0);
-        reads.assign(read_slots(n), make_uint4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < n; ++i) {
-            uint32_t h, l;
-            guide_planes(guides[g0 + i], &h, &l);
-            uint4 &r = reads[i / 2];
-            if (i & 1) r.z = h, r.w = l; else r.x = h, r.y = l;
-        }
-        VSC_HIP(ctx, hipMemcpyAsync(d_reads, reads.data(), reads.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
-        a.n_guides = n;
-        a.guide_base = g0;
-        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
-        const uint64_t cells = (uint64_t)2 * n * n_tiles;
-        const uint32_t chunks = (uint32_t)((cells + kBulgeChunk - 1) / kBulgeChunk);
-        found = 0;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-        VSC_HIP(ctx, launch_bulge_count(a, ctx->n_cus, ctx->stream));
-        if (out) {
-            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
-            VSC_HIP(ctx, launch_enum_scan(d_sums, chunks, d_off, ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
-        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + chunks, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `reads` is reused by the next round)
-        float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-        t.scan_ms += ms;
-        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        t.passes += 1;
-        total += found;
-        return VSC_OK;
-    };
-    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
-        int rc = count_round(g0);
-        if (rc != VSC_OK) return rc;
-        if (bulge_params->max_hits && total > bulge_params->max_hits) {
-            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
-            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
-                if ((rc = count_round(h0)) != VSC_OK) return rc;
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "vsc_search_bulges: %llu records exceed max_hits = %llu", total,
-                          (unsigned long long)bulge_params->max_hits);
-            return fail(ctx, VSC_ERR_RANGE, msg);
-        }
-        float ms = 0;
-        pieces.emplace_back();
-        piece_n.push_back(found);
-        a.records = nullptr;
-        a.n_records = found;
-        if (found) {
-            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_bulge_hit)));
-            a.records = (uint4 *)pieces.back().p;
-        }
-        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-            VSC_HIP(ctx, launch_bulge_write(a, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-            t.scan_ms += ms;
-            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        }
-    }
-    unsigned long long sites = 0;
-    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
-    if (rows)
-        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_bulge_summary), hipMemcpyDeviceToHost, ctx->stream));
-    if (out && total) {
-        if (pieces.size() == 1) {
-            holder->storage = pieces[0];
-            pieces[0] = DeviceBuf();
-        } else {
-            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_bulge_hit)));
-            size_t at = 0;
-            for (size_t i = 0; i < pieces.size(); ++i) {
-                if (piece_n[i])
-                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_bulge_hit),
-                                                hipMemcpyDeviceToDevice, ctx->stream));
-                at += (size_t)piece_n[i] * sizeof(vsc_bulge_hit);
+    const RoundsPlan plan{fn, n_guides, a.n_tiles, batch, &ctx->bulge_tabs, 1, kBulgeRowWords, bulge_params->max_hits};
+    return run_rounds(
+        ctx, plan, out, (uint32_t *)rows,
+        // two reads per uint4: padded to kBulgeUnroll reads, plus four spare
+        [](uint32_t n) { return (n + kBulgeUnroll - 1) / kBulgeUnroll * (kBulgeUnroll / 2) + kBulgeUnroll / 2; },
+        [&](uint32_t g0, uint32_t n, uint4 *table) {
+            for (uint32_t i = 0; i < n; ++i) {
+                uint32_t h, l;
+                guide_planes(guides[g0 + i], &h, &l);
+                uint4 &r = table[i / 2];
+                if (i & 1) r.z = h, r.w = l; else r.x = h, r.y = l;
             }
-        }
-        holder->n = total;
-        holder->host_valid = false;
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rows && !out)
-        for (uint32_t g = 0; g < n_guides; ++g)
-            for (uint32_t k = 0; k < kBulgeRowWords; ++k) total += (&rows[g].count[0][0])[k];
-    t.total_ms = t.scan_ms;
-    t.hits = total;
-    t.sites = sites;
-    t.pairs = sites * n_guides;
-    ctx->timing = t;
-    if (out) *out = holder.release();
-    return VSC_OK;
+        },
+        [&](const Round &r, bool write) {
+            a.guides = r.guides;
+            a.n_guides = r.n;
+            a.guide_base = r.g0;
+            a.count = r.count;
+            a.chunk_off = r.off;
+            a.sites = r.sites;
+            a.rows = r.rows;
+            a.records = (uint4 *)r.records;
+            a.n_records = r.n_records;
+            return write ? launch_bulge_write(a, ctx->n_cus, ctx->stream) : launch_bulge_count(a, ctx->n_cus, ctx->stream);
+        });
     });
 }
 
 uint64_t vsc_bulge_hits_count(const vsc_bulge_hits *hits) { return hits ? hits->n : 0; }
-
-int vsc_bulge_hits_data(vsc_bulge_hits *hits, const vsc_bulge_hit **out)
-{
-    if (!hits || !out) return VSC_ERR_INVALID;
-    return guarded(hits->ctx, [&]() -> int {
-    if (!hits->host_valid) {
-        vsc_ctx *ctx = hits->ctx;
-        hits->host.resize(hits->n);
-        VSC_HIP(ctx, hipSetDevice(ctx->device));
-        VSC_HIP(ctx, hipMemcpyAsync(hits->host.data(), hits->storage.p, hits->n * sizeof(vsc_bulge_hit), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hits->host_valid = true;
-    }
-    *out = hits->host.data();
-    return VSC_OK;
-    });
-}
-
-const void *vsc_bulge_hits_data_dev(const vsc_bulge_hits *hits) { return hits && hits->n ? hits->storage.p : nullptr; }
-
-int vsc_bulge_hits_free(vsc_bulge_hits *hits)
-{
-    if (!hits) return VSC_OK;
-    if (hits->ctx && hits->storage.p) {
-        (void)hipSetDevice(hits->ctx->device);
-        hits->storage.release();
-    }
-    delete hits;
-    return VSC_OK;
-}
+int vsc_bulge_hits_data(vsc_bulge_hits *hits, const vsc_bulge_hit **out) { return record_list_data(hits, out); }
+const void *vsc_bulge_hits_data_dev(const vsc_bulge_hits *hits) { return record_list_data_dev(hits); }
+int vsc_bulge_hits_free(vsc_bulge_hits *hits) { return object_free(hits); }
 
 int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t *nm, uint32_t *index)
 {
@@ -3074,10 +3163,7 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
     return VSC_OK;
 }
 
-// ---- pattern search (kernels: vsc_pattern.hip) ----------------------------------------------------------------
-// The rounds of vsc_search_bulges: count pass, sums, exclusive scan, one 8-byte read-back, write pass into the round's own
-// buffer; the rounds' buffers are consecutive pieces of the result.  The sums are taken twice - per 64 cells and per 64 of
-// those - so that the one-workgroup scan sees a 64th of the chunks (at 3 Gbp and 16 guides: 11 000 entries, not 730 000).
+// ---- pattern search (kernels: vsc_pattern.hip; the rounds: run_rounds, two levels of sums) -------------------
 int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
                        const vsc_pattern_params *params, vsc_pattern_hits **out, vsc_pattern_summary *rows)
 {
@@ -3085,14 +3171,15 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
     if (!ctx) return VSC_ERR_INVALID;
     if (out) *out = nullptr;
     ctx->err.clear();
-    if (!out && !rows) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: neither records nor rows are asked for");
-    if (!genome || !params || !pattern || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: null argument");
-    if (genome->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: genome belongs to another context");
-    if (len < kPatMinLen || len > kPatMaxLen) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: the pattern must have 16..32 letters");
-    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: max_mismatches must be 0..8");
-    if (params->reserved[0] || params->reserved[1]) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: reserved fields must be 0");
+    const char *const fn = "vsc_search_pattern";
+    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, fn, "neither records nor rows are asked for");
+    if (!genome || !params || !pattern || (n_guides && !guides)) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern must have 16..32 letters");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail_in(ctx, VSC_ERR_INVALID, fn, "max_mismatches must be 0..8");
+    if (params->reserved[0] || params->reserved[1]) return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields must be 0");
     uint8_t sets[kPatMaxLen], rc_sets[kPatMaxLen];
-    if (!pattern_sets(pattern, len, sets)) return fail(ctx, VSC_ERR_INVALID, "vsc_search_pattern: the pattern holds a letter that is no IUPAC letter");
+    if (!pattern_sets(pattern, len, sets)) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern holds a letter that is no IUPAC letter");
     PatternArgs a{};
     pattern_front(sets, len, &a.front[0]);
     pattern_revcomp(sets, len, rc_sets);
@@ -3102,7 +3189,7 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
     for (uint32_t g = 0; g < n_guides; ++g) {
         if (!pattern_sets(guides + (size_t)g * len, len, sets)) {
             char msg[120];
-            std::snprintf(msg, sizeof msg, "vsc_search_pattern: guide %u holds a letter that is no IUPAC letter", g);
+            std::snprintf(msg, sizeof msg, "%s: guide %u holds a letter that is no IUPAC letter", fn, g);
             return fail(ctx, VSC_ERR_INVALID, msg);
         }
         pattern_revcomp(sets, len, rc_sets);
@@ -3110,207 +3197,46 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
         planes[2 * (size_t)g] = make_uint4(f.a, f.c, f.g, f.t);
         planes[2 * (size_t)g + 1] = make_uint4(r.a, r.c, r.g, r.t);
     }
-    std::unique_ptr<vsc_pattern_hits, int (*)(vsc_pattern_hits *)> holder(nullptr, vsc_pattern_hits_free);
-    if (out) {
-        holder.reset(new (std::nothrow) vsc_pattern_hits());
-        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_pattern: out of host memory");
-        holder->ctx = ctx;
-        holder->host_valid = true;  // (empty until records are written)
-    }
-    vsc_timing t{};
-    t.index_ms = ctx->timing.index_ms;
-    t.algorithm = VSC_ALGO_SCAN;
-    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_pattern_summary));
-    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
-    if (n_guides == 0 || n_tiles == 0) {
-        t.pairs = 0;
-        ctx->timing = t;
-        if (out) *out = holder.release();
-        return VSC_OK;
-    }
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
-    a.hi = genome->d_hi;
-    a.lo = genome->d_lo;
-    a.nm = genome->d_nm;
-    a.first_pos = (uint32_t)(genome->first_word * 32);
-    a.n_tiles = n_tiles;
+    bind_genome(a, genome);
+    a.n_tiles = genome->d_hi ? genome->n_tiles : 0;
     a.len = len;
     a.max_mm = params->max_mismatches;
-    a.contig_off = genome->d_contig_off;
-    a.contig_end = genome->d_contig_end;
-    a.n_contigs = genome->n_contigs;
 
+    static_assert(sizeof(vsc_pattern_summary) == kPatRowWords * sizeof(uint32_t), "a row is its counts");
     const uint32_t batch = std::min(params->guide_batch ? std::min(params->guide_batch, kPatMaxBatch) : kPatDefaultBatch, n_guides);
-    // scratch, 256-byte aligned parts: [rows of all guides][site counter] | per round: [guides][counts][chunk sums][group sums][group offsets]
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
-    const uint64_t max_chunks = (max_cells + kPatChunk - 1) / kPatChunk;
-    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_pattern: counter table too large");
-    const uint64_t max_groups = (max_chunks + kPatChunk - 1) / kPatChunk;  // the one-workgroup scan takes these, not the chunks
-    const size_t rows_bytes = up((size_t)n_guides * kPatRowWords * sizeof(uint32_t));
-    auto table_slots = [](uint32_t n) { return (n + kPatUnroll - 1) / kPatUnroll * kPatUnroll + kPatUnroll; };  // uint4s of one strand's table
-    const size_t guides_bytes = up((size_t)2 * table_slots(batch) * sizeof(uint4));
-    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
-    const size_t groups_bytes = up((size_t)max_groups * sizeof(uint32_t));
-    VSC_HIP(ctx, ctx->pattern_tabs.ensure(rows_bytes + 256 + guides_bytes + count_bytes + sums_bytes + groups_bytes +
-                                          (size_t)(max_groups + 1) * sizeof(unsigned long long)));
-    char *base = (char *)ctx->pattern_tabs.p;
-    uint32_t *d_rows = (uint32_t *)base;
-    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
-    uint4 *d_guides = (uint4 *)(base + rows_bytes + 256);
-    uint32_t *d_count = (uint32_t *)((char *)d_guides + guides_bytes);
-    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
-    uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
-    unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
-    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
-    a.guides = d_guides;
-    a.count = d_count;
-    a.chunk_sum = d_sums;
-    a.group_off = d_off;
-    a.rows = rows ? d_rows : nullptr;
-
-    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
-    struct Release {
-        std::vector<DeviceBuf> &v;
-        ~Release()
-        {
-            for (auto &b : v) b.release();
-        }
-    } release{pieces};
-    std::vector<uint64_t> piece_n;
-    std::vector<uint4> staged;
-    unsigned long long total = 0, found = 0;
-    // the count pass of the round that starts at guide g0 (and, for records, the offsets of its cells): found = its records
-    auto count_round = [&](uint32_t g0) -> int {
-        const uint32_t n = std::min(batch, n_guides - g0);
-        const uint32_t stride = table_slots(n);
-        staged.assign((size_t)2 * stride, make_uint4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < n; ++i) {
-            staged[i] = planes[2 * (size_t)(g0 + i)];
-            staged[stride + i] = planes[2 * (size_t)(g0 + i) + 1];
-        }
-        a.guide_stride = stride;
-        VSC_HIP(ctx, hipMemcpyAsync(d_guides, staged.data(), staged.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
-        a.n_guides = n;
-        a.guide_base = g0;
-        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
-        const uint64_t cells = (uint64_t)2 * n * n_tiles;
-        const uint32_t chunks = (uint32_t)((cells + kPatChunk - 1) / kPatChunk), groups = (chunks + kPatChunk - 1) / kPatChunk;
-        found = 0;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-        VSC_HIP(ctx, launch_pattern_count(a, ctx->n_cus, ctx->stream));
-        if (out) {
-            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
-            VSC_HIP(ctx, launch_bulge_chunk_sums(d_sums, chunks, d_groups, ctx->stream));
-            VSC_HIP(ctx, launch_enum_scan(d_groups, groups, d_off, ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
-        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + groups, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `staged` is reused by the next round)
-        float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-        t.scan_ms += ms;
-        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        t.passes += 1;
-        total += found;
-        return VSC_OK;
-    };
-    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
-        int rc = count_round(g0);
-        if (rc != VSC_OK) return rc;
-        if (params->max_hits && total > params->max_hits) {
-            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
-            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
-                if ((rc = count_round(h0)) != VSC_OK) return rc;
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "vsc_search_pattern: %llu records exceed max_hits = %llu", total, (unsigned long long)params->max_hits);
-            return fail(ctx, VSC_ERR_RANGE, msg);
-        }
-        float ms = 0;
-        pieces.emplace_back();
-        piece_n.push_back(found);
-        a.records = nullptr;
-        a.n_records = found;
-        if (found) {
-            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_pattern_hit)));
-            a.records = (uint32_t *)pieces.back().p;
-        }
-        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-            VSC_HIP(ctx, launch_pattern_write(a, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-            t.scan_ms += ms;
-            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        }
-    }
-    unsigned long long sites = 0;
-    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
-    if (rows)
-        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_pattern_summary), hipMemcpyDeviceToHost, ctx->stream));
-    if (out && total) {
-        if (pieces.size() == 1) {
-            holder->storage = pieces[0];
-            pieces[0] = DeviceBuf();
-        } else {
-            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_pattern_hit)));
-            size_t at = 0;
-            for (size_t i = 0; i < pieces.size(); ++i) {
-                if (piece_n[i])
-                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_pattern_hit),
-                                                hipMemcpyDeviceToDevice, ctx->stream));
-                at += (size_t)piece_n[i] * sizeof(vsc_pattern_hit);
+    const RoundsPlan plan{fn, n_guides, a.n_tiles, batch, &ctx->pattern_tabs, 2, kPatRowWords, params->max_hits};
+    return run_rounds(
+        ctx, plan, out, (uint32_t *)rows,
+        // two tables, '+' and '-', one stride apart
+        [](uint32_t n) { return 2 * pattern_table_slots(n); },
+        [&](uint32_t g0, uint32_t n, uint4 *table) {
+            const uint32_t stride = pattern_table_slots(n);
+            for (uint32_t i = 0; i < n; ++i) {
+                table[i] = planes[2 * (size_t)(g0 + i)];
+                table[stride + i] = planes[2 * (size_t)(g0 + i) + 1];
             }
-        }
-        holder->n = total;
-        holder->host_valid = false;
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rows && !out)
-        for (uint32_t g = 0; g < n_guides; ++g)
-            for (uint32_t k = 0; k < kPatRowWords; ++k) total += rows[g].count[k];
-    t.total_ms = t.scan_ms;
-    t.hits = total;
-    t.sites = sites;
-    t.pairs = sites * n_guides;
-    ctx->timing = t;
-    if (out) *out = holder.release();
-    return VSC_OK;
+        },
+        [&](const Round &r, bool write) {
+            a.guides = r.guides;
+            a.guide_stride = pattern_table_slots(r.n);
+            a.n_guides = r.n;
+            a.guide_base = r.g0;
+            a.count = r.count;
+            a.chunk_sum = r.chunk_sum;
+            a.group_off = r.off;
+            a.sites = r.sites;
+            a.rows = r.rows;
+            a.records = (uint32_t *)r.records;
+            a.n_records = r.n_records;
+            return write ? launch_pattern_write(a, ctx->n_cus, ctx->stream) : launch_pattern_count(a, ctx->n_cus, ctx->stream);
+        });
     });
 }
 
 uint64_t vsc_pattern_hits_count(const vsc_pattern_hits *hits) { return hits ? hits->n : 0; }
-
-int vsc_pattern_hits_data(vsc_pattern_hits *hits, const vsc_pattern_hit **out)
-{
-    if (!hits || !out) return VSC_ERR_INVALID;
-    return guarded(hits->ctx, [&]() -> int {
-    if (!hits->host_valid) {
-        vsc_ctx *ctx = hits->ctx;
-        hits->host.resize(hits->n);
-        VSC_HIP(ctx, hipSetDevice(ctx->device));
-        VSC_HIP(ctx, hipMemcpyAsync(hits->host.data(), hits->storage.p, hits->n * sizeof(vsc_pattern_hit), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hits->host_valid = true;
-    }
-    *out = hits->host.data();
-    return VSC_OK;
-    });
-}
-
-const void *vsc_pattern_hits_data_dev(const vsc_pattern_hits *hits) { return hits && hits->n ? hits->storage.p : nullptr; }
-
-int vsc_pattern_hits_free(vsc_pattern_hits *hits)
-{
-    if (!hits) return VSC_OK;
-    if (hits->ctx && hits->storage.p) {
-        (void)hipSetDevice(hits->ctx->device);
-        hits->storage.release();
-    }
-    delete hits;
-    return VSC_OK;
-}
+int vsc_pattern_hits_data(vsc_pattern_hits *hits, const vsc_pattern_hit **out) { return record_list_data(hits, out); }
+const void *vsc_pattern_hits_data_dev(const vsc_pattern_hits *hits) { return record_list_data_dev(hits); }
+int vsc_pattern_hits_free(vsc_pattern_hits *hits) { return object_free(hits); }
 
 int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm, uint32_t *mask)
 {
@@ -3346,20 +3272,15 @@ int vsc_search_pattern_bulges(vsc_ctx *ctx, const vsc_genome *genome, const char
     if (out) *out = nullptr;
     ctx->err.clear();
     const char *const fn = "vsc_search_pattern_bulges";
-    auto refuse = [&](const char *what) {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "%s: %s", fn, what);
-        return fail(ctx, VSC_ERR_INVALID, msg);
-    };
-    if (!out && !rows) return refuse("neither records nor rows are asked for");
-    if (!genome || !params || !pattern || (n_guides && !guides)) return refuse("null argument");
-    if (genome->ctx != ctx) return refuse("genome belongs to another context");
-    if (len < kPatMinLen || len > kPatMaxLen) return refuse("the pattern must have 16..32 letters");
-    if (params->max_mismatches > VSC_MAX_MISMATCHES) return refuse("max_mismatches must be 0..8");
+    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, fn, "neither records nor rows are asked for");
+    if (!genome || !params || !pattern || (n_guides && !guides)) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern must have 16..32 letters");
+    if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail_in(ctx, VSC_ERR_INVALID, fn, "max_mismatches must be 0..8");
     uint8_t sets[kPatMaxLen], bulged[kPatMaxLen], rc_sets[kPatMaxLen];
-    if (!pattern_sets(pattern, len, sets)) return refuse("the pattern holds a letter that is no IUPAC letter");
+    if (!pattern_sets(pattern, len, sets)) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern holds a letter that is no IUPAC letter");
     if (const char *why = pattern_bulge_refusal(sets, len, params->proto_start, params->proto_len, params->dna_max, params->rna_max))
-        return refuse(why);
+        return fail_in(ctx, VSC_ERR_INVALID, fn, why);
     PatBulgeArgs a{};
     a.len = len;
     a.proto_a = params->proto_start;
@@ -3385,167 +3306,28 @@ int vsc_search_pattern_bulges(vsc_ctx *ctx, const vsc_genome *genome, const char
         const PatPlanes f = pattern_planes(sets, len);
         planes[g] = make_uint4(f.a, f.c, f.g, f.t);
     }
-    std::unique_ptr<vsc_bulge_hits, int (*)(vsc_bulge_hits *)> holder(nullptr, vsc_bulge_hits_free);
-    if (out) {
-        holder.reset(new (std::nothrow) vsc_bulge_hits());
-        if (!holder) return fail(ctx, VSC_ERR_NOMEM, "vsc_search_pattern_bulges: out of host memory");
-        holder->ctx = ctx;
-        holder->host_valid = true;  // (empty until records are written)
-    }
-    vsc_timing t{};
-    t.index_ms = ctx->timing.index_ms;
-    t.algorithm = VSC_ALGO_SCAN;
-    if (rows) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_bulge_summary));
-    const uint32_t n_tiles = genome->d_hi ? genome->n_tiles : 0;
-    if (n_guides == 0 || n_tiles == 0) {
-        t.pairs = 0;
-        ctx->timing = t;
-        if (out) *out = holder.release();
-        return VSC_OK;
-    }
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
-    a.hi = genome->d_hi;
-    a.lo = genome->d_lo;
-    a.nm = genome->d_nm;
-    a.first_pos = (uint32_t)(genome->first_word * 32);
-    a.n_tiles = n_tiles;
+    bind_genome(a, genome);
+    a.n_tiles = genome->d_hi ? genome->n_tiles : 0;
     a.max_mm = params->max_mismatches;
-    a.contig_off = genome->d_contig_off;
-    a.contig_end = genome->d_contig_end;
-    a.n_contigs = genome->n_contigs;
 
     const uint32_t batch = std::min(params->guide_batch ? std::min(params->guide_batch, kPatMaxBatch) : kPatDefaultBatch, n_guides);
-    // scratch, 256-byte aligned parts: [rows of all guides][site counter] | per round: [guides][counts][chunk sums][group sums][group offsets]
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const uint64_t max_cells = (uint64_t)2 * batch * n_tiles;
-    const uint64_t max_chunks = (max_cells + kPatChunk - 1) / kPatChunk;
-    if (max_chunks >= (1ull << 32)) return fail(ctx, VSC_ERR_RANGE, "vsc_search_pattern_bulges: counter table too large");
-    const uint64_t max_groups = (max_chunks + kPatChunk - 1) / kPatChunk;  // the one-workgroup scan takes these, not the chunks
-    const size_t rows_bytes = up((size_t)n_guides * kBulgeRowWords * sizeof(uint32_t));
-    auto table_slots = [](uint32_t n) { return (n + kPatUnroll - 1) / kPatUnroll * kPatUnroll + kPatUnroll; };  // uint4s of the table
-    const size_t guides_bytes = up((size_t)table_slots(batch) * sizeof(uint4));
-    const size_t count_bytes = up((size_t)max_cells * sizeof(uint32_t)), sums_bytes = up((size_t)max_chunks * sizeof(uint32_t));
-    const size_t groups_bytes = up((size_t)max_groups * sizeof(uint32_t));
-    VSC_HIP(ctx, ctx->pattern_tabs.ensure(rows_bytes + 256 + guides_bytes + count_bytes + sums_bytes + groups_bytes +
-                                          (size_t)(max_groups + 1) * sizeof(unsigned long long)));
-    char *base = (char *)ctx->pattern_tabs.p;
-    uint32_t *d_rows = (uint32_t *)base;
-    unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
-    uint4 *d_guides = (uint4 *)(base + rows_bytes + 256);
-    uint32_t *d_count = (uint32_t *)((char *)d_guides + guides_bytes);
-    uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
-    uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
-    unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
-    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
-    a.guides = d_guides;
-    a.count = d_count;
-    a.chunk_sum = d_sums;
-    a.group_off = d_off;
-    a.rows = rows ? d_rows : nullptr;
-
-    std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
-    struct Release {
-        std::vector<DeviceBuf> &v;
-        ~Release()
-        {
-            for (auto &b : v) b.release();
-        }
-    } release{pieces};
-    std::vector<uint64_t> piece_n;
-    std::vector<uint4> staged;
-    unsigned long long total = 0, found = 0;
-    // the count pass of the round that starts at guide g0 (and, for records, the offsets of its cells): found = its records
-    auto count_round = [&](uint32_t g0) -> int {
-        const uint32_t n = std::min(batch, n_guides - g0);
-        staged.assign(table_slots(n), make_uint4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < n; ++i) staged[i] = planes[g0 + i];
-        VSC_HIP(ctx, hipMemcpyAsync(d_guides, staged.data(), staged.size() * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
-        a.n_guides = n;
-        a.guide_base = g0;
-        a.sites = g0 ? d_sites + 1 : d_sites;  // (every round sees the same sites: the first counts them, the others add into a spare word)
-        const uint64_t cells = (uint64_t)2 * n * n_tiles;
-        const uint32_t chunks = (uint32_t)((cells + kPatChunk - 1) / kPatChunk), groups = (chunks + kPatChunk - 1) / kPatChunk;
-        found = 0;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-        VSC_HIP(ctx, launch_pattern_bulge_count(a, ctx->n_cus, ctx->stream));
-        if (out) {
-            VSC_HIP(ctx, launch_bulge_chunk_sums(d_count, cells, d_sums, ctx->stream));
-            VSC_HIP(ctx, launch_bulge_chunk_sums(d_sums, chunks, d_groups, ctx->stream));
-            VSC_HIP(ctx, launch_enum_scan(d_groups, groups, d_off, ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
-        if (out) VSC_HIP(ctx, hipMemcpyAsync(&found, d_off + groups, sizeof found, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: `staged` is reused by the next round)
-        float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-        t.scan_ms += ms;
-        t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        t.passes += 1;
-        total += found;
-        return VSC_OK;
-    };
-    for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
-        int rc = count_round(g0);
-        if (rc != VSC_OK) return rc;
-        if (params->max_hits && total > params->max_hits) {
-            // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
-            for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
-                if ((rc = count_round(h0)) != VSC_OK) return rc;
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "%s: %llu records exceed max_hits = %llu", fn, total, (unsigned long long)params->max_hits);
-            return fail(ctx, VSC_ERR_RANGE, msg);
-        }
-        float ms = 0;
-        pieces.emplace_back();
-        piece_n.push_back(found);
-        a.records = nullptr;
-        a.n_records = found;
-        if (found) {
-            VSC_HIP(ctx, pieces.back().ensure((size_t)found * sizeof(vsc_bulge_hit)));
-            a.records = (uint4 *)pieces.back().p;
-        }
-        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-            VSC_HIP(ctx, launch_pattern_bulge_write(a, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-            t.scan_ms += ms;
-            t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
-        }
-    }
-    unsigned long long sites = 0;
-    VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
-    if (rows)
-        VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)n_guides * sizeof(vsc_bulge_summary), hipMemcpyDeviceToHost, ctx->stream));
-    if (out && total) {
-        if (pieces.size() == 1) {
-            holder->storage = pieces[0];
-            pieces[0] = DeviceBuf();
-        } else {
-            VSC_HIP(ctx, holder->storage.ensure((size_t)total * sizeof(vsc_bulge_hit)));
-            size_t at = 0;
-            for (size_t i = 0; i < pieces.size(); ++i) {
-                if (piece_n[i])
-                    VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * sizeof(vsc_bulge_hit),
-                                                hipMemcpyDeviceToDevice, ctx->stream));
-                at += (size_t)piece_n[i] * sizeof(vsc_bulge_hit);
-            }
-        }
-        holder->n = total;
-        holder->host_valid = false;
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rows && !out)
-        for (uint32_t g = 0; g < n_guides; ++g)
-            for (uint32_t k = 0; k < kBulgeRowWords; ++k) total += (&rows[g].count[0][0])[k];
-    t.total_ms = t.scan_ms;
-    t.hits = total;
-    t.sites = sites;
-    t.pairs = sites * n_guides;
-    ctx->timing = t;
-    if (out) *out = holder.release();
-    return VSC_OK;
+    const RoundsPlan plan{fn, n_guides, a.n_tiles, batch, &ctx->pattern_tabs, 2, kBulgeRowWords, params->max_hits};
+    return run_rounds(
+        ctx, plan, out, (uint32_t *)rows, pattern_table_slots,
+        [&](uint32_t g0, uint32_t n, uint4 *table) { std::copy_n(planes.begin() + g0, n, table); },
+        [&](const Round &r, bool write) {
+            a.guides = r.guides;
+            a.n_guides = r.n;
+            a.guide_base = r.g0;
+            a.count = r.count;
+            a.chunk_sum = r.chunk_sum;
+            a.group_off = r.off;
+            a.sites = r.sites;
+            a.rows = r.rows;
+            a.records = (uint4 *)r.records;
+            a.n_records = r.n_records;
+            return write ? launch_pattern_bulge_write(a, ctx->n_cus, ctx->stream) : launch_pattern_bulge_count(a, ctx->n_cus, ctx->stream);
+        });
     });
 }
 
@@ -3580,9 +3362,8 @@ int vsc_pattern_bulge_align(const char *pattern, const char *guide, const char *
 }
 
 // ---- pattern guide discovery (kernels: the end of vsc_pattern.hip) --------------------------------------------
-// vsc_guides_enumerate's passes - count over the work list, exclusive scan of the per-tile counts, one 8-byte read-back, write
-// into the result's own arrays - behind the pattern search's front end.  The targets are no vsc_regions: their intervals
-// become ranges of site starts on the host (pattern_target_ranges), the work list holds the tiles that meet one.
+// vsc_guides_enumerate's passes (run_enumeration) behind the pattern search's front end.  The targets are no vsc_regions: their
+// intervals become ranges of site starts on the host (pattern_target_ranges), the work list holds the tiles that meet one.
 int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, uint32_t len, const vsc_pattern_enum_params *params,
                                  const vsc_interval *targets, uint64_t n_targets, vsc_pattern_guides **out)
 {
@@ -3591,38 +3372,32 @@ int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const c
     *out = nullptr;
     ctx->err.clear();
     const char *const fn = "vsc_guides_enumerate_pattern";
-    auto refuse = [&](const char *what) {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "%s: %s", fn, what);
-        return fail(ctx, VSC_ERR_INVALID, msg);
-    };
-    if (!genome || !params || !pattern || (n_targets && !targets)) return refuse("null argument");
-    if (genome->ctx != ctx) return refuse("genome belongs to another context");
-    if (len < kPatMinLen || len > kPatMaxLen) return refuse("the pattern must have 16..32 letters");
+    if (!genome || !params || !pattern || (n_targets && !targets)) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    if (len < kPatMinLen || len > kPatMaxLen) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern must have 16..32 letters");
     uint8_t sets[kPatMaxLen], rc_sets[kPatMaxLen];
-    if (!pattern_sets(pattern, len, sets)) return refuse("the pattern holds a letter that is no IUPAC letter");
+    if (!pattern_sets(pattern, len, sets)) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern holds a letter that is no IUPAC letter");
     const uint32_t ps_a = params->ps_start, ps_k = params->ps_len;
-    if (ps_k == 0 || ps_a + ps_k > len) return refuse("the protospacer must be a non-empty range of the pattern's positions");
-    if (params->strands > 2) return refuse("strands must be 0 (both), 1 ('+') or 2 ('-')");
+    if (ps_k == 0 || ps_a + ps_k > len)
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "the protospacer must be a non-empty range of the pattern's positions");
+    if (params->strands > 2) return fail_in(ctx, VSC_ERR_INVALID, fn, "strands must be 0 (both), 1 ('+') or 2 ('-')");
     if (params->gc_min > ps_k || params->gc_max > ps_k || (params->gc_max && params->gc_min > params->gc_max))
-        return refuse("GC bounds must satisfy gc_min <= gc_max <= the protospacer's length (gc_max 0: no upper bound)");
-    if (params->reserved0 || params->reserved1 || params->reserved[0] || params->reserved[1]) return refuse("reserved fields must be 0");
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "GC bounds must satisfy gc_min <= gc_max <= the protospacer's length (gc_max 0: no upper bound)");
+    if (params->reserved0 || params->reserved1 || params->reserved[0] || params->reserved[1])
+        return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields must be 0");
     std::vector<PatStartRange> ranges;
     if (targets) {
-        if (params->rule != VSC_REGION_OVERLAP && params->rule != VSC_REGION_INSIDE) return refuse("unknown target rule");
+        if (params->rule != VSC_REGION_OVERLAP && params->rule != VSC_REGION_INSIDE) return fail_in(ctx, VSC_ERR_INVALID, fn, "unknown target rule");
         if (pattern_target_ranges(genome->h_contig_off.data(), genome->h_contig_end.data(), genome->n_contigs, targets, n_targets, params->rule,
                                   len, &ranges) != VSC_OK)
-            return refuse("a target interval is outside the contig table, has start > end or a non-zero reserved field");
+            return fail_in(ctx, VSC_ERR_INVALID, fn, "a target interval is outside the contig table, has start > end or a non-zero reserved field");
     }
     VSC_HIP(ctx, hipSetDevice(ctx->device));
     PatEnumArgs a{};
     pattern_front(sets, len, &a.front[0]);
     pattern_revcomp(sets, len, rc_sets);
     pattern_front(rc_sets, len, &a.front[1]);
-    a.hi = genome->d_hi;
-    a.lo = genome->d_lo;
-    a.nm = genome->d_nm;
-    a.first_pos = (uint32_t)(genome->first_word * 32);
+    bind_genome(a, genome);
     a.len = len;
     a.len_mask = len < 32u ? (1u << len) - 1u : ~0u;
     a.keep_fwd = params->strands != 2 ? 0xFFFFFFFFu : 0u;
@@ -3634,9 +3409,6 @@ int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const c
     a.gc_max = params->gc_max ? params->gc_max : ps_k;
     a.max_t_run = params->max_t_run;
     a.filter = (a.gc_min > 0 || a.gc_max < ps_k || a.max_t_run) ? 1u : 0u;
-    a.contig_off = genome->d_contig_off;
-    a.contig_end = genome->d_contig_end;
-    a.n_contigs = genome->n_contigs;
 
     // the work list: with targets, the tiles of the shard that hold a start of a range; without, every tile of the shard
     std::vector<uint32_t> work;
@@ -3652,116 +3424,24 @@ int vsc_guides_enumerate_pattern(vsc_ctx *ctx, const vsc_genome *genome, const c
         }
         n_work = (uint32_t)work.size();
     }
-    vsc_timing t{};
-    t.index_ms = ctx->timing.index_ms;
-    vsc_pattern_guides *g = new (std::nothrow) vsc_pattern_guides();
-    if (!g) return fail(ctx, VSC_ERR_NOMEM, "vsc_guides_enumerate_pattern: out of host memory");
-    std::unique_ptr<vsc_pattern_guides, int (*)(vsc_pattern_guides *)> holder(g, vsc_pattern_guides_free);
-    g->ctx = ctx;
-    unsigned long long total = 0;
-    if (n_work) {
-        // scratch: [work list][counts][offsets][ranges], 256-byte aligned parts
-        const size_t list_bytes = ((size_t)n_work * sizeof(uint32_t) + 255) / 256 * 256;
-        const size_t off_bytes = (((size_t)n_work + 1) * sizeof(unsigned long long) + 255) / 256 * 256;
-        VSC_HIP(ctx, ctx->enum_tabs.ensure(2 * list_bytes + off_bytes + ranges.size() * sizeof(PatStartRange)));
-        char *base = (char *)ctx->enum_tabs.p;
-        unsigned long long *d_off = (unsigned long long *)(base + 2 * list_bytes);
-        if (targets) {
-            VSC_HIP(ctx, hipMemcpyAsync(base, work.data(), (size_t)n_work * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(base + 2 * list_bytes + off_bytes, ranges.data(), ranges.size() * sizeof(PatStartRange),
-                                        hipMemcpyHostToDevice, ctx->stream));
-            a.work = (const uint32_t *)base;
-            a.ranges = (const uint2 *)(base + 2 * list_bytes + off_bytes);
-            a.n_ranges = (uint32_t)ranges.size();
-        }
-        a.n_work = n_work;
-        a.tile_count = (uint32_t *)(base + list_bytes);
-        a.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-        VSC_HIP(ctx, launch_pattern_enum(a, false, ctx->stream));
-        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_work, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + n_work, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (also: the work list and the ranges above are this call's vectors)
-        float ms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-        t.scan_ms += ms;
-        t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
-        t.passes = 1;
-        if (params->max_guides && total > params->max_guides) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "vsc_guides_enumerate_pattern: %llu candidates exceed max_guides = %llu", total,
-                          (unsigned long long)params->max_guides);
-            return fail(ctx, VSC_ERR_RANGE, msg);
-        }
-        if (total) {
-            g->loci_at = ((size_t)total * sizeof(uint64_t) + 255) / 256 * 256;
-            VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)total * sizeof(vsc_locus)));
-            a.codes = (unsigned long long *)g->storage.p;
-            a.loci = (uint4 *)((char *)g->storage.p + g->loci_at);
-            a.n_out = total;
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-            VSC_HIP(ctx, launch_pattern_enum(a, true, ctx->stream));
-            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-            t.scan_ms += ms;
-            t.genome_bytes += (uint64_t)n_work * kTileWords * 3 * sizeof(uint32_t);
-            t.passes = 2;
-        }
-    }
-    g->n = total;
-    if (total == 0) g->host_valid = true;
-    t.total_ms = t.scan_ms;
-    t.sites = total;
-    ctx->timing = t;
-    *out = holder.release();
-    return VSC_OK;
+    // the ranges go to the device with the work list (with targets and a tile to visit there is a range)
+    return run_enumeration(ctx, fn, a, targets ? &work : nullptr, n_work, ranges.data(), ranges.size() * sizeof(PatStartRange), params->max_guides, out,
+                           [&](const void *d_ranges, unsigned long long total, bool write) {
+                               a.ranges = (const uint2 *)d_ranges;
+                               a.n_ranges = (uint32_t)ranges.size();
+                               a.n_out = total;
+                               return launch_pattern_enum(a, write, ctx->stream);
+                           });
     });
 }
 
 uint64_t vsc_pattern_guides_count(const vsc_pattern_guides *guides) { return guides ? guides->n : 0; }
-
-int vsc_pattern_guides_data(vsc_pattern_guides *guides, const uint64_t **codes, const vsc_locus **loci)
-{
-    if (!guides) return VSC_ERR_INVALID;
-    return guarded(guides->ctx, [&]() -> int {
-    if (!guides->host_valid) {
-        vsc_ctx *ctx = guides->ctx;
-        guides->codes.resize(guides->n);
-        guides->loci.resize(guides->n);
-        VSC_HIP(ctx, hipSetDevice(ctx->device));
-        VSC_HIP(ctx, hipMemcpyAsync(guides->codes.data(), guides->storage.p, guides->n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(guides->loci.data(), (const char *)guides->storage.p + guides->loci_at, guides->n * sizeof(vsc_locus),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        guides->host_valid = true;
-    }
-    if (codes) *codes = guides->codes.data();
-    if (loci) *loci = guides->loci.data();
-    return VSC_OK;
-    });
-}
-
+int vsc_pattern_guides_data(vsc_pattern_guides *guides, const uint64_t **codes, const vsc_locus **loci) { return guide_list_data(guides, codes, loci); }
 int vsc_pattern_guides_data_dev(const vsc_pattern_guides *guides, const void **codes_dev, const void **loci_dev)
 {
-    if (!guides) return VSC_ERR_INVALID;
-    const bool dev = guides->n && guides->storage.p;
-    if (codes_dev) *codes_dev = dev ? guides->storage.p : nullptr;
-    if (loci_dev) *loci_dev = dev ? (const char *)guides->storage.p + guides->loci_at : nullptr;
-    return VSC_OK;
+    return guide_list_data_dev(guides, codes_dev, loci_dev);
 }
-
-int vsc_pattern_guides_free(vsc_pattern_guides *guides)
-{
-    if (!guides) return VSC_OK;
-    if (guides->ctx && guides->storage.p) {
-        (void)hipSetDevice(guides->ctx->device);
-        guides->storage.release();
-    }
-    delete guides;
-    return VSC_OK;
-}
+int vsc_pattern_guides_free(vsc_pattern_guides *guides) { return object_free(guides); }
 
 int vsc_pattern_guide_text(uint64_t code, uint32_t len, uint32_t ps_start, uint32_t ps_len, uint32_t spell, char *out)
 {

@@ -19,11 +19,14 @@
 //                       with one atomic.
 // No record is placed through an atomic and nothing is sorted: the bytes depend on the planes and the parameters only.
 #include "vsc_internal.h"
+#include "vsc_cells_device.h"
 #include "vsc_device.h"
 #include "vsc_enum.h"
 #include "vsc_bulge.h"
 
 namespace vsc {
+
+static_assert(kBulgeChunk == kCellChunk, "cell_offset takes one load per lane");
 
 namespace {
 
@@ -103,34 +106,6 @@ __device__ __forceinline__ void bulge_site(const BulgeTile &t, uint32_t b, uint3
     *sl = rev ? (~__brev(wl)) >> (32u - len) : wl;
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, kWave);
-    return v;
-}
-
-// exclusive prefix of v over the lanes of the wave (enum_kernel's)
-__device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t lane)
-{
-    uint32_t s = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)s, d, kWave);
-        if (lane >= (uint32_t)d) s += o;
-    }
-    return s - v;
-}
-
-// tiles [*t0, *t1) of wave `w` of `n_waves`: runs of consecutive tiles, so that the cells a wave stores lie side by side
-__device__ __forceinline__ void bulge_tile_run(uint32_t n_tiles, uint32_t w, uint32_t n_waves, uint32_t *t0, uint32_t *t1)
-{
-    const uint32_t per = (n_tiles + n_waves - 1u) / n_waves;
-    const uint64_t first = (uint64_t)w * per;
-    *t0 = first < n_tiles ? (uint32_t)first : n_tiles;
-    *t1 = first + per < n_tiles ? (uint32_t)(first + per) : n_tiles;
-}
-
 }  // namespace
 
 // ---- count pass --------------------------------------------------------------------------------------------------------
@@ -145,7 +120,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void bulge_count_kernel(cons
     for (uint32_t i = lane; i < 2 * kBulgeMaxBatch; i += kWave) cnt[i] = 0;
     wave_sync();
     uint32_t t0, t1;
-    bulge_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
     const uint32_t m = a.max_mm;
     unsigned long long sites = 0;
@@ -272,14 +247,6 @@ __device__ __forceinline__ void bulge_walk_lane(const BulgeArgs &a, const BulgeT
     }
 }
 
-// hits of all cells before `cell`: the chunk's offset + the cells of the chunk in front of it (one load per lane)
-__device__ __forceinline__ unsigned long long bulge_cell_offset(const BulgeArgs &a, unsigned long long cell, uint32_t lane)
-{
-    const unsigned long long first = cell & ~(unsigned long long)(kBulgeChunk - 1u);
-    const uint32_t before = wave_sum(lane < (uint32_t)(cell - first) ? a.count[first + lane] : 0u);
-    return a.chunk_off[cell / kBulgeChunk] + before;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kWave *kWavesPerGroup) void bulge_write_kernel(const BulgeArgs a)
@@ -290,7 +257,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void bulge_write_kernel(cons
     s_row[wave][lane] = 0;
     wave_sync();
     uint32_t t0, t1;
-    bulge_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
     for (uint32_t tile = t0; tile < t1; ++tile) {
         // which reads of the round have a hit in this tile: lane l looks at cell l (read l / 2, strand l & 1)
@@ -318,8 +285,8 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void bulge_write_kernel(cons
             }
             if (a.records) {
                 const unsigned long long cell = (unsigned long long)(2u * g) * a.n_tiles + tile;
-                const unsigned long long at_f = bulge_cell_offset(a, cell, lane) + wave_exclusive(nf, lane);
-                const unsigned long long at_r = bulge_cell_offset(a, cell + a.n_tiles, lane) + wave_exclusive(nr, lane);
+                const unsigned long long at_f = cell_offset(a.count, a.chunk_off, cell, lane) + wave_exclusive(nf, lane);
+                const unsigned long long at_r = cell_offset(a.count, a.chunk_off, cell + a.n_tiles, lane) + wave_exclusive(nr, lane);
                 bulge_walk_lane<true>(a, t, rh, rl, a.guide_base + g, nullptr, nf, nr, at_f, at_r);
             }
         }
@@ -327,29 +294,17 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void bulge_write_kernel(cons
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-namespace {
-
-// 8 workgroups of 4 waves per CU fill every SIMD's 8 wave slots; fewer when the tiles do not need them
-dim3 bulge_grid(uint32_t n_tiles, int n_cus)
-{
-    const uint32_t want = (n_tiles + kWavesPerGroup - 1) / kWavesPerGroup;
-    const uint32_t cap = (uint32_t)(n_cus > 0 ? n_cus : 256) * 8u;
-    return dim3(want < cap ? want : cap);
-}
-
-}  // namespace
-
 hipError_t launch_bulge_count(const BulgeArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(bulge_count_kernel, bulge_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(bulge_count_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 
 hipError_t launch_bulge_write(const BulgeArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(bulge_write_kernel, bulge_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(bulge_write_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -220,11 +220,13 @@ struct vsc_hits {
     bool host_valid = false;
 };
 
-// The candidates of vsc_guides_enumerate: two device arrays the object owns (ctx != null), or host arrays only
-// (vsc_multi_guides_enumerate: ctx == null, host_valid from the start).
-struct vsc_guides {
+namespace vsc {
+
+// Candidate guides: two device arrays the object owns (ctx != null), or host arrays only (vsc_multi_guides_enumerate:
+// ctx == null, host_valid from the start).
+struct GuideList {
     vsc_ctx *ctx = nullptr;
-    vsc::DeviceBuf storage;  // codes (n x 8 bytes), then the loci (n x 16 bytes) from loci_at on
+    DeviceBuf storage;  // codes (n x 8 bytes), then the loci (n x 16 bytes) from loci_at on
     size_t loci_at = 0;
     uint64_t n = 0;
     std::vector<uint64_t> codes;
@@ -232,34 +234,24 @@ struct vsc_guides {
     bool host_valid = false;
 };
 
-// The records of vsc_search_bulges: one device array the object owns.
-struct vsc_bulge_hits {
+// The records of a count / scan / write search: one device array the object owns.
+template <class Rec> struct RecordList {
+    typedef Rec record;
     vsc_ctx *ctx = nullptr;
-    vsc::DeviceBuf storage;
+    DeviceBuf storage;
     uint64_t n = 0;
-    std::vector<vsc_bulge_hit> host;
+    std::vector<Rec> host;
     bool host_valid = false;
 };
 
-// The records of vsc_search_pattern: one device array the object owns.
-struct vsc_pattern_hits {
-    vsc_ctx *ctx = nullptr;
-    vsc::DeviceBuf storage;
-    uint64_t n = 0;
-    std::vector<vsc_pattern_hit> host;
-    bool host_valid = false;
-};
+}  // namespace vsc
 
-// The candidates of vsc_guides_enumerate_pattern: two device arrays the object owns, as vsc_guides'.
-struct vsc_pattern_guides {
-    vsc_ctx *ctx = nullptr;
-    vsc::DeviceBuf storage;  // codes (n x 8 bytes), then the loci (n x 16 bytes) from loci_at on
-    size_t loci_at = 0;
-    uint64_t n = 0;
-    std::vector<uint64_t> codes;
-    std::vector<vsc_locus> loci;
-    bool host_valid = false;
-};
+// The four handles of include/varscot_hip.h behind which these stand: the candidates of vsc_guides_enumerate and of
+// vsc_guides_enumerate_pattern, the records of vsc_search_bulges (and vsc_search_pattern_bulges) and of vsc_search_pattern.
+struct vsc_guides : vsc::GuideList {};
+struct vsc_pattern_guides : vsc::GuideList {};
+struct vsc_bulge_hits : vsc::RecordList<vsc_bulge_hit> {};
+struct vsc_pattern_hits : vsc::RecordList<vsc_pattern_hit> {};
 
 namespace vsc {
 // A genome object that only carries the contig table (no planes, nothing to search): what vsc_hits_merge_packed

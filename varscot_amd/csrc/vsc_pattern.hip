@@ -32,6 +32,8 @@
 
 namespace vsc {
 
+static_assert(kPatChunk == kCellChunk, "cell_offset takes one load per lane");
+
 namespace {
 
 constexpr uint32_t kPatQueue = kTileBases;  // every start of a tile can be a candidate (a pattern of N only)
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_count_kernel(co
     const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     PatLds &s = s_lds[wave];
     uint32_t t0, t1;
-    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const uint32_t m = a.max_mm;
     unsigned long long sites = 0;
     for (uint32_t tile = t0; tile < t1; ++tile) {
@@ -173,21 +175,6 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_count_kernel(co
 }
 
 // ---- write pass --------------------------------------------------------------------------------------------------------
-namespace {
-
-// hits of all cells before `cell`: the offset of its group of 64 chunks + the chunks of the group in front of its own + the
-// cells of the chunk in front of it (two loads per lane)
-__device__ __forceinline__ unsigned long long pattern_cell_offset(const PatternArgs &a, unsigned long long cell, uint32_t lane)
-{
-    const unsigned long long chunk = cell / kPatChunk, group = chunk / kPatChunk;
-    const unsigned long long first_chunk = group * kPatChunk, first_cell = chunk * kPatChunk;
-    const uint32_t chunks = wave_sum(lane < (uint32_t)(chunk - first_chunk) ? a.chunk_sum[first_chunk + lane] : 0u);
-    const uint32_t cells = wave_sum(lane < (uint32_t)(cell - first_cell) ? a.count[first_cell + lane] : 0u);
-    return a.group_off[group] + chunks + cells;
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(const PatternArgs a)
 {
     __shared__ PatLds s_lds[kWavesPerGroup];
@@ -195,7 +182,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
     PatLds &s = s_lds[wave];
     if (lane < 16u) s.row[lane] = 0;
     uint32_t t0, t1;
-    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
     const uint32_t m = a.max_mm;
     uint32_t c_id = 0, c_off = 1, c_end = 0;  // the contig of the lane's last hit: [c_off, c_end) in global positions (empty at first)
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
                 if (((word >> (2u * (g & 31u) + strand)) & 1u) == 0) continue;  // wave-uniform
                 const PatPlanes planes = planes_of(gp[strand * a.guide_stride + g]);
                 const unsigned long long cell = (unsigned long long)(2u * g + strand) * a.n_tiles + tile;
-                unsigned long long at = a.records ? pattern_cell_offset(a, cell, lane) : 0ull;
+                unsigned long long at = a.records ? cell_offset(a.count, a.chunk_sum, a.group_off, cell, lane) : 0ull;
                 for (uint32_t base = 0; base < total; base += kWave) {
                     const uint32_t idx = base + lane;
                     const bool live = idx < total;
@@ -388,29 +375,17 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_enum_kernel(con
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-namespace {
-
-// 8 workgroups of 4 waves per CU fill every SIMD's 8 wave slots (8 x 19 KB of LDS); fewer when the tiles do not need them
-dim3 pattern_grid(uint32_t n_tiles, int n_cus)
-{
-    const uint32_t want = (n_tiles + kWavesPerGroup - 1) / kWavesPerGroup;
-    const uint32_t cap = (uint32_t)(n_cus > 0 ? n_cus : 256) * 8u;
-    return dim3(want < cap ? want : cap);
-}
-
-}  // namespace
-
 hipError_t launch_pattern_count(const PatternArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(pattern_count_kernel, pattern_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(pattern_count_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 
 hipError_t launch_pattern_write(const PatternArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(pattern_write_kernel, pattern_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(pattern_write_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 

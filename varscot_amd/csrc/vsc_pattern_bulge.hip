@@ -26,6 +26,8 @@
 
 namespace vsc {
 
+static_assert(kPatChunk == kCellChunk, "cell_offset takes one load per lane");
+
 namespace {
 
 constexpr uint32_t kPbRowWords = kBulgeRowWords;  // 36 of the 64 words of PbLds::row
@@ -160,16 +162,6 @@ __device__ __forceinline__ void pb_count_step(const PbLds &s, const_v16u_ptr gq,
     }
 }
 
-// hits of all cells before `cell` (pattern_cell_offset's sums: group offset + chunks in front + cells in front)
-__device__ __forceinline__ unsigned long long pb_cell_offset(const PatBulgeArgs &a, unsigned long long cell, uint32_t lane)
-{
-    const unsigned long long chunk = cell / kPatChunk, group = chunk / kPatChunk;
-    const unsigned long long first_chunk = group * kPatChunk, first_cell = chunk * kPatChunk;
-    const uint32_t chunks = wave_sum(lane < (uint32_t)(chunk - first_chunk) ? a.chunk_sum[first_chunk + lane] : 0u);
-    const uint32_t cells = wave_sum(lane < (uint32_t)(cell - first_cell) ? a.count[first_cell + lane] : 0u);
-    return a.group_off[group] + chunks + cells;
-}
-
 }  // namespace
 
 // ---- count pass --------------------------------------------------------------------------------------------------------
@@ -179,7 +171,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_bulge_count_ker
     const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
     PbLds &s = s_lds[wave];
     uint32_t t0, t1;
-    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const PbConst c = pb_const(a);
     const const_v16u_ptr gq = (const_v16u_ptr)(uintptr_t)a.guides;
     unsigned long long sites = 0;
@@ -224,7 +216,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_bulge_write_ker
     PbLds &s = s_lds[wave];
     s.row[lane] = 0;
     uint32_t t0, t1;
-    pattern_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
+    cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const PbConst c = pb_const(a);
     const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
     uint32_t c_id = 0, c_off = 1, c_end = 0;  // the contig of the lane's last hit: [c_off, c_end) in global positions (empty at first)
@@ -254,7 +246,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_bulge_write_ker
                 const v4u gg = gp[g];
                 const PatPlanes planes{gg.x, gg.y, gg.z, gg.w};
                 const unsigned long long cell = (unsigned long long)(2u * g + strand) * a.n_tiles + tile;
-                unsigned long long at = a.records ? pb_cell_offset(a, cell, lane) : 0ull;
+                unsigned long long at = a.records ? cell_offset(a.count, a.chunk_sum, a.group_off, cell, lane) : 0ull;
                 for (uint32_t win0 = 0; win0 < all; win0 += kPatBulgeQueue) {
                     if (windows || !queued) {
                         wave_sync();  // (the queue's last readers are done)
@@ -316,29 +308,17 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_bulge_write_ker
 }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------
-namespace {
-
-// 8 workgroups of 4 waves per CU fill every SIMD's 8 wave slots (8 x 19 KB of LDS); fewer when the tiles do not need them
-dim3 pb_grid(uint32_t n_tiles, int n_cus)
-{
-    const uint32_t want = (n_tiles + kWavesPerGroup - 1) / kWavesPerGroup;
-    const uint32_t cap = (uint32_t)(n_cus > 0 ? n_cus : 256) * 8u;
-    return dim3(want < cap ? want : cap);
-}
-
-}  // namespace
-
 hipError_t launch_pattern_bulge_count(const PatBulgeArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(pattern_bulge_count_kernel, pb_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(pattern_bulge_count_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 
 hipError_t launch_pattern_bulge_write(const PatBulgeArgs &args, int n_cus, hipStream_t stream)
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
-    hipLaunchKernelGGL(pattern_bulge_write_kernel, pb_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    hipLaunchKernelGGL(pattern_bulge_write_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // vsc_pattern_device.h - device helpers that the kernels of vsc_pattern.hip share with those of
-// vsc_pattern_bulge.hip (4.19): the front end's start mask of one table, the wave's prefix and sum, a wave's run of tiles.
+// vsc_pattern_bulge.hip (4.19): the front end's start mask of one table (the wave and cell helpers: vsc_cells_device.h).
 #pragma once
 
+#include "vsc_cells_device.h"
 #include "vsc_device.h"
 #include "vsc_pattern.h"
 
@@ -20,36 +21,7 @@ __device__ __forceinline__ uint32_t pattern_starts(const PatFront &f, uint32_t H
     return ok;
 }
 
-// exclusive prefix of v over the lanes of the wave; *total = the wave's sum (enum_kernel's)
-__device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t lane, uint32_t *total)
-{
-    uint32_t s = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)s, d, kWave);
-        if (lane >= (uint32_t)d) s += o;
-    }
-    *total = uniform((uint32_t)__shfl((int)s, kWave - 1, kWave));
-    return s - v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, kWave);
-    return v;
-}
-
 typedef uint32_t v16u __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(4))) v16u *const_v16u_ptr;
-
-// tiles [*t0, *t1) of wave `w` of `n_waves`: runs of consecutive tiles, so that the cells a wave stores lie side by side
-__device__ __forceinline__ void pattern_tile_run(uint32_t n_tiles, uint32_t w, uint32_t n_waves, uint32_t *t0, uint32_t *t1)
-{
-    const uint32_t per = (n_tiles + n_waves - 1u) / n_waves;
-    const uint64_t first = (uint64_t)w * per;
-    *t0 = first < n_tiles ? (uint32_t)first : n_tiles;
-    *t1 = first + per < n_tiles ? (uint32_t)(first + per) : n_tiles;
-}
 
 }  // namespace vsc
