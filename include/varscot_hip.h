@@ -1260,6 +1260,87 @@ int vsc_multi_search_summary_classified(vsc_multi *m, const vsc_multi_genome *g,
                                         const vsc_search_params *params, const vsc_locus *exclude, const vsc_classify *cls,
                                         vsc_guide_summary *out /* optional */, vsc_guide_votes *out_votes);
 
+/* ---- table-driven off-target scores (CFD form): per hit, per guide, top-K ------------------------------------ */
+/*
+ * A score that is a product of weights looked up by (read position, guide base, site base) times a weight for the site's PAM
+ * dinucleotide - the form of the CFD score.  The library ships no table: the caller brings one (vsc_score_table_build).
+ *
+ * TABLE   pair[20][4][4] and pam[16], doubles.
+ *         pair[j][g][s] is the weight of guide base g against site base s at read position j.
+ *           j = 0 is the PAM-distal end.
+ *           Bases are coded A 0, C 1, G 2, T 3, as vsc_pack_guide codes them.
+ *           s is the letter of the site in READ orientation. This is the letter CRISPOR's offtargetSeq column shows.
+ *         pam[4 * s21 + s22] is the weight of the site's letters at read positions 21 and 22.
+ *         Every weight is finite and lies in [0, 1]. pair[j][b][b] is exactly 1.
+ *         Anything else: VSC_ERR_INVALID.
+ * SCORE   For a hit with read r and site s in read orientation:
+ *           s = w on '+', revcomp(w) on '-', where w is the 23-base window.
+ *           x = 1.0.
+ *           For j = 0, 1, ..., 19 in this order: if r[j] != s[j] then x = x * pair[j][r[j]][s[j]].
+ *           Then x = x * pam[s[21], s[22]].
+ *         Arithmetic is fp64, one rounding per multiplication, no contraction.
+ *         Positions 20..22 of the read and bits 20..22 of the mismatch mask take no part.
+ *         On '-' the record's mask bit i is read position 22 - i.
+ * FIXED   f = rint(x * 2^30), round half to even. f <= 2^30.
+ *         This is the unit of every sum, floor and selection key. It is exact under any order, pass split or shard split.
+ * HITS    Exactly the hits of vsc_search / vsc_search_summary for the same genome, guides and params, minus exclude[i].
+ *         A site whose PAM is not in the search's PAM set is not a hit, whatever pam[] says.
+ *         extra_pam is how NAG sites get in.
+ * ROWS    vsc_guide_table_row { uint64_t score_sum, positive, positive_nm[9], reserved; }, 96 bytes.
+ *         It is vsc_guide_votes' shape, so the sinks' LDS table and add_shard_rows serve it.
+ *         positive counts the hits with f > 0.
+ *         positive_nm[k] counts those with NM = k.
+ * SPEC    vsc_table_specificity(sum) = 100.0 / (100.0 + sum * 2^-30) * 100.0, evaluated in that order.
+ *         The tools round it with floor(x + 0.5), as they do for MIT.
+ *
+ * vsc_score_table is host-only and immutable; a context keeps the device copy of the table it used last (keyed by the table's
+ * serial number) and vsc_ctx_release_scratch gives it back.  vsc_table_score scores one (guide, site) pair on the host - both
+ * vsc_pack_guide codes in read orientation - with the very function the kernels call.  vsc_score_hits_table scores rows
+ * [first, first + count) of a sorted result (either output may be NULL; the row range and the pass-wise scratch of
+ * vsc_score_hits; a record that is no hit of this genome and these guides - its window outside the genome's planes, its guide
+ * index >= n_guides - scores 0, as no result of the library's searches over them does).  vsc_search_summary_table writes one row per guide (plain: the rows of vsc_search_summary from the same
+ * search, optional).  vsc_search_select_table is vsc_search_select with the key f: min_score is in f units, the order is f
+ * descending, '+' before '-', global position ascending, the result is sorted as vsc_search sorts; with top_k = 0,
+ * min_score = 0 and no exclude it returns vsc_search's bytes.  vsc_multi_search_summary_table adds the shards' rows on the
+ * host.  Multi-device selection by table score is not offered (as for votes), nor a call with a table and the classifier at
+ * once.  vsc_ctx_timing afterwards: score_ms = the table score kernel.
+ */
+typedef struct vsc_score_table vsc_score_table;
+typedef struct {
+    uint64_t score_sum;       /* sum of f over the counted hits */
+    uint64_t positive;        /* counted hits with f > 0 */
+    uint64_t positive_nm[9];  /* those by NM */
+    uint64_t reserved;        /* 0 */
+} vsc_guide_table_row;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_guide_table_row) == 96, "vsc_guide_table_row layout");
+#else
+_Static_assert(sizeof(vsc_guide_table_row) == 96, "vsc_guide_table_row layout");
+#endif
+typedef struct {
+    uint64_t serial;        /* process-wide number of the table */
+    uint32_t zero_weights;  /* weights that are exactly 0 */
+    uint32_t reserved;
+} vsc_score_table_stats;
+int vsc_score_table_build(const double *pair /* [20][4][4] */, const double *pam /* [16] */, vsc_score_table **out);
+int vsc_score_table_free(vsc_score_table *table);
+int vsc_score_table_info(const vsc_score_table *table, vsc_score_table_stats *out);
+int vsc_table_score(const vsc_score_table *table, uint64_t guide_code, uint64_t site_code, double *score /* optional */,
+                    uint32_t *fixed /* optional */);
+double vsc_table_specificity(uint64_t score_sum);
+int vsc_score_hits_table(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits *hits, const uint64_t *guides, uint32_t n_guides,
+                         uint64_t first, uint64_t count, const vsc_score_table *table, double *scores /* optional */,
+                         uint32_t *fixed /* optional */);
+int vsc_search_summary_table(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                             const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
+                             vsc_guide_summary *plain /* optional */, vsc_guide_table_row *out);
+int vsc_search_select_table(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                            const vsc_score_table *table, vsc_guide_table_row *rows /* optional */, vsc_hits **out);
+int vsc_multi_search_summary_table(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                   const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
+                                   vsc_guide_summary *plain /* optional */, vsc_guide_table_row *out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -197,6 +197,24 @@ int vsc_search_summary(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides
     return VSC_OK;
 }
 
+// (vsc_multi_search_summary_table: the stand-in reads no table - every stub hit scores one unit of 2^30)
+int vsc_search_summary_table(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
+                             const vsc_locus *ex, const vsc_score_table *, vsc_guide_summary *plain, vsc_guide_table_row *out)
+{
+    std::vector<vsc_guide_summary> rows(n_guides);
+    const int rc = vsc_search_summary(ctx, g, guides, n_guides, p, ex, rows.data());
+    for (uint32_t i = 0; rc == VSC_OK && i < n_guides; ++i) {
+        if (plain) plain[i] = rows[i];
+        out[i] = vsc_guide_table_row{};
+        for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) {
+            out[i].positive += rows[i].nm[k];
+            out[i].positive_nm[k] = rows[i].nm[k];
+        }
+        out[i].score_sum = out[i].positive << 30;
+    }
+    return rc;
+}
+
 // (vsc_multi_search_summary_classified: the stand-in has no forest - every stub hit gets one vote and is no active one)
 int vsc_search_summary_classified(vsc_ctx *ctx, const vsc_genome *g, const uint64_t *guides, uint32_t n_guides, const vsc_search_params *p,
                                   const vsc_locus *ex, const vsc_classify *, vsc_guide_summary *out, vsc_guide_votes *out_votes)

@@ -26,6 +26,9 @@ assert SUMMARY_DTYPE.itemsize == 96
 # vsc_guide_votes (vsc_search_summary_classified): 96 bytes per guide
 VOTES_DTYPE = np.dtype([("votes_sum", "<u8"), ("active", "<u8"), ("ties", "<u8"), ("active_nm", "<u8", (9,))])
 assert VOTES_DTYPE.itemsize == 96
+# vsc_guide_table_row (vsc_search_summary_table): 96 bytes per guide
+TABLE_ROW_DTYPE = np.dtype([("score_sum", "<u8"), ("positive", "<u8"), ("positive_nm", "<u8", (9,)), ("reserved", "<u8")])
+assert TABLE_ROW_DTYPE.itemsize == 96
 # vsc_locus: an excluded locus (contig == 0xFFFFFFFF: none)
 LOCUS_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("strand", "<u4"), ("reserved", "<u4")])
 
@@ -216,6 +219,11 @@ class MultiScore(C.Structure):
 MULTI_SCORE_NONE, MULTI_SCORE_ROWS, MULTI_SCORE_VOTES = 0, 1, 2
 
 
+class ScoreTableStats(C.Structure):
+    """vsc_score_table_stats"""
+    _fields_ = [("serial", C.c_uint64), ("zero_weights", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -368,6 +376,16 @@ SYMBOLS = [
     ("vsc_search_select_classified", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(SelectVotes),
                                                C.POINTER(Classify), _vp, _vp, _vp, C.POINTER(_vp)]),
     ("vsc_multi_search_summary_classified", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, C.POINTER(Classify), _vp, _vp]),
+    ("vsc_score_table_build", C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    ("vsc_score_table_free", C.c_int, [_vp]),
+    ("vsc_score_table_info", C.c_int, [_vp, C.POINTER(ScoreTableStats)]),
+    ("vsc_table_score", C.c_int, [_vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("vsc_table_specificity", C.c_double, [C.c_uint64]),
+    ("vsc_score_hits_table", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
+    ("vsc_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
+    ("vsc_search_select_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, _vp,
+                                          C.POINTER(_vp)]),
+    ("vsc_multi_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)

@@ -321,6 +321,125 @@ def expected_active(votes_rows, n_trees):
     return votes_rows["votes_sum"].astype(np.float64) / float(n_trees)
 
 
+TABLE_ROW_DTYPE = _lib.TABLE_ROW_DTYPE
+TABLE_ONE = 1 << 30  # the fixed-point unit of the table scores: f = rint(score * 2^30)
+
+
+def table_specificity(score_sum):
+    """A guide's specificity from a table row's score_sum (vsc_table_specificity): 100 / (100 + sum * 2^-30) * 100 - for a CFD
+    table CRISPOR's cfdSpecScore before rounding (the tools round with floor(x + 0.5))."""
+    return lib().vsc_table_specificity(int(score_sum))
+
+
+def _base(letter, what):
+    i = "ACGT".find(letter.upper().replace("U", "T")) if len(letter) == 1 else -1
+    if i < 0:
+        raise ValueError("%s: %r is no base" % (what, letter))
+    return i
+
+
+class ScoreTable:
+    """A table-driven off-target score (vsc_score_table; the CFD form): pair[20][4][4] - the weight of guide base g against
+    site base s (the site's letter in READ orientation) at read position j, j = 0 the PAM-distal end, bases A 0, C 1, G 2,
+    T 3 - and pam[16], the weight of the site's letters at read positions 21 and 22 (4 * first + second).  Every weight in
+    [0, 1], pair[j][b][b] == 1.  The package ships no table."""
+
+    def __init__(self, pair, pam):
+        self.pair = np.ascontiguousarray(pair, dtype=np.float64)
+        self.pam = np.ascontiguousarray(pam, dtype=np.float64).reshape(-1)
+        if self.pair.shape != (20, 4, 4) or self.pam.shape != (16,):
+            raise ValueError("a score table is pair[20][4][4] and pam[16]")
+        h = C.c_void_p()
+        self._h = None
+        check(lib().vsc_score_table_build(ptr(self.pair), ptr(self.pam), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_tsv(cls, path, default=None):
+        """A table from a text file: a line is `j<TAB>g<TAB>s<TAB>w` (j 0-based read position, g the guide's letter, s the
+        site's letter in read orientation) or `PAM<TAB>XY<TAB>w`; '#' starts a comment, a weight of '?' stands for an
+        entry that is not known.  Entries that are missing or unknown are an error unless default= gives their weight."""
+        pair = np.full((20, 4, 4), np.nan)
+        pam = np.full(16, np.nan)
+        for b in range(4):
+            pair[:, b, b] = 1.0
+        with open(path) as fh:
+            for n, line in enumerate(fh, 1):
+                f = line.split("#", 1)[0].split()
+                if not f:
+                    continue
+                where = "%s:%d" % (path, n)
+                try:
+                    w = np.nan if f[-1] == "?" else float(f[-1])
+                    if f[0] == "PAM" and len(f) == 3 and len(f[1]) == 2:
+                        pam[4 * _base(f[1][0], where) + _base(f[1][1], where)] = w
+                    elif len(f) == 4 and 0 <= int(f[0]) < 20:
+                        pair[int(f[0]), _base(f[1], where), _base(f[2], where)] = w
+                    else:
+                        raise ValueError("neither 'j g s w' nor 'PAM XY w'")
+                except ValueError as e:
+                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+        missing = int(np.isnan(pair).sum() + np.isnan(pam).sum())
+        if missing:
+            if default is None:
+                raise ValueError("%s: %d entries are missing or unknown and no default= is given" % (path, missing))
+            pair[np.isnan(pair)] = float(default)
+            pam[np.isnan(pam)] = float(default)
+        return cls(pair, pam)
+
+    @classmethod
+    def from_doench(cls, mm_scores, pam_scores, default=None):
+        """A table from dictionaries keyed the way Doench et al.'s published CFD calculator is remembered to key its pickles:
+        mm_scores["rX:dY,pos"] with X the guide's letter (T written U), Y the COMPLEMENT of the site's letter and pos
+        1-based; pam_scores["XY"] for the site's last two letters.  NOTHING PINS THIS MAPPING: the reference this project is
+        tested against holds no copy of those files - check a few scores against a calculator you trust before relying on
+        it.  Entries the dictionaries lack are an error unless default= gives their weight."""
+        comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+        pair = np.ones((20, 4, 4))
+        pam = np.empty(16)
+        missing = 0
+        for j in range(20):
+            for g, gl in enumerate("ACGT"):
+                for s, sl in enumerate("ACGT"):
+                    if g != s:
+                        w = mm_scores.get("r%s:d%s,%d" % (gl.replace("T", "U"), comp[sl], j + 1), default)
+                        missing += w is None
+                        pair[j, g, s] = np.nan if w is None else float(w)
+        for a, al in enumerate("ACGT"):
+            for b, bl in enumerate("ACGT"):
+                w = pam_scores.get(al + bl, default)
+                missing += w is None
+                pam[4 * a + b] = np.nan if w is None else float(w)
+        if missing:
+            raise ValueError("%d entries are missing and no default= is given" % missing)
+        return cls(pair, pam)
+
+    def info(self):
+        st = _lib.ScoreTableStats()
+        check(lib().vsc_score_table_info(self._h, C.byref(st)))
+        return {"serial": int(st.serial), "zero_weights": int(st.zero_weights)}
+
+    def score(self, guide, site, fixed=False):
+        """vsc_table_score: the score of one guide against one site, both 23-nt strings (or pack_guides codes) in read
+        orientation; fixed=True: (score, rint(score * 2^30))."""
+        g = int(guide) if isinstance(guide, (int, np.integer)) else int(pack_guides([guide])[0])
+        s = int(site) if isinstance(site, (int, np.integer)) else int(pack_guides([site])[0])
+        x, f = C.c_double(), C.c_uint32()
+        check(lib().vsc_table_score(self._h, g, s, C.byref(x), C.byref(f)))
+        return (x.value, f.value) if fixed else x.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsc_score_table_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -924,6 +1043,38 @@ class Genome:
         hits = Hits(self, h, codes)
         return (hits, rows, votes) if summary else hits
 
+    def summarize_table(self, guides, max_mismatches, table, extra_pam=None, algorithm="auto", exclude=None, plain=False):
+        """vsc_search_summary_table: per guide, over the hits search() would return (minus the excluded locus), the sum of the
+        table's fixed-point scores (units of 2^-30; table_specificity() turns it into a specificity), the hits that score
+        above 0 and those by NM - without the records.  table: a ScoreTable.  Returns TABLE_ROW_DTYPE rows - or, with
+        plain=True, (SUMMARY_DTYPE rows of summarize(), those rows) from the one search."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if plain else None
+        rows = np.zeros(len(codes), dtype=_lib.TABLE_ROW_DTYPE)
+        check(lib().vsc_search_summary_table(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex), table._h, ptr(out),
+                                             ptr(rows)), self.ctx._h)
+        return (out, rows) if plain else rows
+
+    def search_select_table(self, guides, max_mismatches, table, top_k=0, min_score=0, extra_pam=None, algorithm="auto",
+                            exclude=None, summary=False):
+        """vsc_search_select_table: search_select() with the table's fixed-point score as the key - min_score in units of
+        2^-30, order (score descending, strand, position).  Returns Hits sorted as search() sorts them (Hits.table_scores
+        gives the survivors' scores) - or, with summary=True, (Hits, TABLE_ROW_DTYPE rows over all counted hits)."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        sel = _select(top_k, min_score)
+        ex = _loci(exclude, len(codes))
+        rows = np.zeros(len(codes), dtype=_lib.TABLE_ROW_DTYPE) if summary else None
+        h = C.c_void_p()
+        check(lib().vsc_search_select_table(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(sel), ptr(ex), table._h,
+                                            ptr(rows), C.byref(h)), self.ctx._h)
+        hits = Hits(self, h, codes)
+        return (hits, rows) if summary else hits
+
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
@@ -1132,6 +1283,16 @@ class Hits:
                                    first, count, ptr(m), ptr(fl), ptr(ft)), self.genome.ctx._h)
         return m, fl, ft
 
+    def table_scores(self, table, first=0, count=None, scores=True, fixed=True):
+        """vsc_score_hits_table: (score float64[count] | None, fixed uint32[count] | None) of rows first .. first + count under
+        a ScoreTable - per hit what ScoreTable.score gives for the hit's guide and its site in read orientation."""
+        count = len(self) - first if count is None else count
+        x = np.empty(count, dtype=np.float64) if scores else None
+        f = np.empty(count, dtype=np.uint32) if fixed else None
+        check(lib().vsc_score_hits_table(self.genome.ctx._h, self.genome._h, self._h, ptr(self.codes), len(self.codes), first, count,
+                                         table._h, ptr(x), ptr(f)), self.genome.ctx._h)
+        return x, f
+
     def packed_features(self, first=0, count=None, to_host=True, mit=False, dev_ptr=None):
         """vsc_score_hits_packed: 64-byte feature rows (uint32[count, 16]) and optionally MIT scores.
         dev_ptr: device memory for count * 64 bytes (e.g. a torch tensor's data_ptr()) that receives the rows;
@@ -1336,6 +1497,18 @@ class MultiGenome:
                                                                     C.byref(cls), ptr(out), ptr(votes)))
         del keep
         return out, votes
+
+    def summarize_table(self, guides, max_mismatches, table, extra_pam=None, algorithm="auto", exclude=None, plain=False):
+        """vsc_multi_search_summary_table: Genome.summarize_table over the shards, the rows added on the host."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = Genome._params(max_mismatches, extra_pam, algorithm)
+        ex = _loci(exclude, len(codes))
+        out = np.zeros(len(codes), dtype=_lib.SUMMARY_DTYPE) if plain else None
+        rows = np.zeros(len(codes), dtype=_lib.TABLE_ROW_DTYPE)
+        self.multi._check(lib().vsc_multi_search_summary_table(self.multi._h, self._h, ptr(codes), len(codes), C.byref(p), ptr(ex),
+                                                               table._h, ptr(out), ptr(rows)))
+        return (out, rows) if plain else rows
 
     def search_select(self, guides, max_mismatches, top_k=0, min_score=0, extra_pam=None, algorithm="auto", exclude=None,
                       summary=False, regions=None, region_scope="keep"):

@@ -75,6 +75,15 @@
 // kind = DNA | RNA, index = the read position in front of which the bulge lies (the smallest that gives the fewest mismatches),
 // sequence = the site's forward-genome bases.  -u runs on one device and does not combine with -v or -J.  Without -u every
 // output is what it was.
+// -W table.tsv scores every off-target with a TABLE (vsc_search_summary_table; the CFD form: a product of weights by position,
+// guide base and site base times a weight for the site's PAM letters).  The file holds one entry per line, `j g s w` (0-based
+// read position, guide letter, site letter in read orientation, weight) or `PAM XY w`; '#' starts a comment; the diagonal is 1;
+// every other entry must be there.  Every line gains, behind all other columns,
+//   tableScoreSum tableSpecScore tablePositive
+// = the sum of the counted hits' scores (fixed point, 2^-30 units, %.6f), floor(100 / (100 + sum) * 100 + 0.5) - for a CFD table
+// CRISPOR's cfdSpecScore - and the hits that score above 0.  With -T the listing is selected and ranked by the table score
+// (vsc_search_select_table): -K the best K, -S a floor on the table score, 0 .. 1, and a last column tableScore (%.9f); that
+// runs on one device, without -A and -r votes.  -W does not combine with -v.  Without -W every output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -130,6 +139,8 @@ int main(int argc, char **argv)
         {'u', "bulges", "DNA,RNA: largest DNA and RNA bulge, 0 .. 2 each (e.g. 1,1): adds the columns bulgeCount and <class>mm0 .. <class>mm<M> "
                         "of the bulged sites (one device; not with -v, -J)", false},
         {'U', "bulge-hits", "Path to the TSV file of the bulged sites (.tsv/.txt); needs -u", false},
+        {'W', "score-table", "Path to a score table (.tsv/.txt; lines 'j g s w' and 'PAM XY w'): adds the columns tableScoreSum tableSpecScore "
+                             "tablePositive; with -T, -K / -S (then a table score, 0 .. 1) select by the table score", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -176,11 +187,15 @@ int main(int argc, char **argv)
         const std::string &v = opts[9].value;
         char *send = nullptr;
         const double x = std::strtod(v.c_str(), &send);
+        if (opts[32].set && (v.empty() || *send || !(x >= 0.0 && x <= 1.0))) {
+            std::fprintf(stderr, "%s: with -W, -S takes a table score, 0 .. 1, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
         if (v.empty() || *send || !(x >= 0.0 && x <= 100.0)) {
             std::fprintf(stderr, "%s: -S takes an MIT score, 0 .. 100, not '%s'\n", argv[0], v.c_str());
             return 1;
         }
-        sel.min_score = (uint32_t)std::ceil(x * 0x1p24);  // the smallest fixed-point score that is >= x
+        sel.min_score = (uint32_t)std::ceil(x * (opts[32].set ? 0x1p30 : 0x1p24));  // the smallest fixed-point score that is >= x
     }
     if ((opts[8].set || opts[9].set) && !listing) {
         std::fprintf(stderr, "%s: -K / -S select the off-targets listed in the -T file: give -T\n", argv[0]);
@@ -416,7 +431,19 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    // -W: the score table
+    const bool tabled = opts[32].set;
+    if (tabled && !has_extension(opts[32].value, {"tsv", "txt"})) {
+        std::fprintf(stderr, "%s: the -W table must be a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
+    if (tabled && (individual || (listing && (annotated || by_votes || devices.size() != 1)))) {
+        std::fprintf(stderr, "%s: -W does not combine with -v; with -T it selects by the table score on one device, without -A and -r votes\n", argv[0]);
+        return 1;
+    }
+
     vsc_ctx *ctx = nullptr;
+    vsc_score_table *table = nullptr;
     vsc_genome *genome = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
     vsc_genome *win_genome = nullptr;
@@ -600,6 +627,48 @@ int main(int argc, char **argv)
             cls.model = &model;
             cls.guide_activity = activity.data();
         }
+        // -W: the table's entries; the diagonal is 1, every other entry has to be in the file
+        std::vector<vsc_guide_table_row> table_rows(tabled ? codes.size() : 0);
+        bool table_done = false;
+        if (tabled) {
+            std::ifstream in(opts[32].value);
+            if (!in) throw std::runtime_error("Could not open the -W file.");
+            std::vector<double> pair(20 * 4 * 4, std::nan("")), pamw(16, std::nan(""));  // (NaN: not given yet)
+            for (int j = 0; j < 20; ++j)
+                for (int b = 0; b < 4; ++b) pair[(j * 4 + b) * 4 + b] = 1.0;
+            auto base = [](const std::string &t, size_t at) {
+                static const std::string letters = "ACGT";
+                const char c = at < t.size() ? (char)std::toupper((unsigned char)t[at]) : '?';
+                return (int)letters.find(c == 'U' ? 'T' : c);  // (-1: no base)
+            };
+            std::string line;
+            while (std::getline(in, line)) {
+                line = line.substr(0, line.find('#'));
+                std::istringstream is(line);
+                std::string a, b, c, rest;
+                double w = 0;
+                if (!(is >> a)) continue;
+                const std::string bad = "-W: neither 'j g s w' nor 'PAM XY w': '" + line + "'";
+                if (a == "PAM") {
+                    if (!(is >> b >> w) || (is >> rest) || std::isnan(w) || b.size() != 2 || base(b, 0) < 0 || base(b, 1) < 0)
+                        throw std::runtime_error(bad);
+                    pamw[4 * base(b, 0) + base(b, 1)] = w;
+                } else {
+                    char *jend = nullptr;
+                    const long j = std::strtol(a.c_str(), &jend, 10);
+                    if (*jend || j < 0 || j > 19 || !(is >> b >> c >> w) || (is >> rest) || std::isnan(w) || b.size() != 1 || c.size() != 1 ||
+                        base(b, 0) < 0 || base(c, 0) < 0)
+                        throw std::runtime_error(bad);
+                    pair[(j * 4 + base(b, 0)) * 4 + base(c, 0)] = w;
+                }
+            }
+            for (double w : pair)
+                if (std::isnan(w)) throw std::runtime_error("-W: the table lacks an entry (240 'j g s w' lines and 16 'PAM XY w' lines make a table)");
+            for (double w : pamw)
+                if (std::isnan(w)) throw std::runtime_error("-W: the table lacks a PAM entry (16 'PAM XY w' lines)");
+            if (vsc_score_table_build(pair.data(), pamw.data(), &table) != VSC_OK)
+                throw std::runtime_error("-W: every weight lies in 0 .. 1 and the weight of a base against itself is 1");
+        }
         if (individual) {
             std::vector<const char *> names;
             for (const std::string &n : ix.names) names.push_back(n.c_str());
@@ -628,6 +697,11 @@ int main(int argc, char **argv)
         } else if (by_votes) {
             st = vsc_search_select_classified(ctx, genome, codes.data(), n_codes, &p, &vsel, &cls, ex, sum.data(), votes_rows.data(), &hits);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        } else if (tabled && listing) {  // the listing by the table score and its rows from one search, the plain rows from a second
+            st = vsc_search_select_table(ctx, genome, codes.data(), n_codes, &p, &sel, ex, table, table_rows.data(), &hits);
+            if (st == VSC_OK) st = vsc_search_summary(ctx, genome, codes.data(), n_codes, &p, ex, sum.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            table_done = true;
         } else if (annotated && listing) {  // without -X the listing is not filtered: the rows then come from a second search, a summary call
             const vsc_region_filter *flt = opts[13].set ? &filter : nullptr;
             vsc_guide_summary *rows_in = flt ? sum_in.data() : nullptr;
@@ -648,13 +722,22 @@ int main(int argc, char **argv)
             st = vsc_search_select(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, &sel, ex, sum.data(), &hits);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         } else if (multi) {
+            table_done = tabled && !classified;  // (the plain rows and the table's from one search)
             st = classified ? vsc_multi_search_summary_classified(multi, mgenome, codes.data(), n_codes, &p, ex, &cls, sum.data(), votes_rows.data())
+                 : tabled   ? vsc_multi_search_summary_table(multi, mgenome, codes.data(), n_codes, &p, ex, table, sum.data(), table_rows.data())
                             : vsc_multi_search_summary(multi, mgenome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_multi_last_error(multi));
         } else {
+            table_done = tabled && !classified;
             st = classified ? vsc_search_summary_classified(ctx, genome, codes.data(), n_codes, &p, ex, &cls, sum.data(), votes_rows.data())
+                 : tabled   ? vsc_search_summary_table(ctx, genome, codes.data(), n_codes, &p, ex, table, sum.data(), table_rows.data())
                             : vsc_search_summary(ctx, genome, codes.data(), (uint32_t)codes.size(), &p, ex, sum.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+        if (tabled && !table_done) {  // (the calls above take no table: its rows from a search of their own)
+            st = multi ? vsc_multi_search_summary_table(multi, mgenome, codes.data(), n_codes, &p, ex, table, nullptr, table_rows.data())
+                       : vsc_search_summary_table(ctx, genome, codes.data(), n_codes, &p, ex, table, nullptr, table_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
         }
         if (classified && !by_votes && (annotated || listing)) {  // (those calls take no forest: the classifier's rows from a search of their own)
             st = multi ? vsc_multi_search_summary_classified(multi, mgenome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data())
@@ -682,6 +765,7 @@ int main(int argc, char **argv)
             text += "\trfExpectedActive\trfActive\trfTies";
             for (long k = 0; k <= mm; ++k) text += "\tra" + std::to_string(k);
         }
+        if (tabled) text += "\ttableScoreSum\ttableSpecScore\ttablePositive";
         if (individual) {
             text += "\tindMitSpecScore\tindCount";
             for (long k = 0; k <= mm; ++k) text += "\timm" + std::to_string(k);
@@ -721,6 +805,13 @@ int main(int argc, char **argv)
                 std::snprintf(buf, sizeof buf, "%.6f", (double)v.votes_sum / (double)model.n_trees);
                 text += '\t' + std::string(buf) + '\t' + std::to_string(v.active) + '\t' + std::to_string(v.ties);
                 for (long k = 0; k <= mm; ++k) text += '\t' + std::to_string(v.active_nm[k]);
+            }
+            if (tabled) {
+                const vsc_guide_table_row &r = table_rows[i];
+                std::snprintf(buf, sizeof buf, "%.6f", (double)r.score_sum * 0x1p-30);
+                text += '\t' + std::string(buf);
+                std::snprintf(buf, sizeof buf, "%.0f", std::floor(vsc_table_specificity(r.score_sum) + 0.5));
+                text += '\t' + std::string(buf) + '\t' + std::to_string(r.positive);
             }
             if (individual) {  // unshadowed reference hits + counted window hits; then the window hits that cover a variant
                 const vsc_guide_summary &in = sum_in[i], &w = win_all[i], &v = win_var[i];
@@ -783,16 +874,20 @@ int main(int argc, char **argv)
             if (by_votes && n && vsc_score_classify_hits(ctx, genome, hits, codes.data(), n_codes, activity.data(), &model, 0, n, nullptr,
                                                          votes.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            const bool by_table = tabled;  // (a listing beside -W is one by the table score)
+            std::vector<uint32_t> fixed(by_table ? n : 0);  // the survivors' table scores, over the small result
+            if (by_table && n && vsc_score_hits_table(ctx, genome, hits, codes.data(), n_codes, 0, n, table, nullptr, fixed.data()) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {  // (stable: ties keep the result order)
                 if (rec[a].guide != rec[b].guide) return rec[a].guide < rec[b].guide;
-                return by_votes ? votes[a] > votes[b] : score[a] > score[b];
+                return by_table ? fixed[a] > fixed[b] : by_votes ? votes[a] > votes[b] : score[a] > score[b];
             });
             const bool named = naming && annotated;  // -N: the -A interval each record lies in
             std::vector<uint32_t> in(named ? n : 0);
             if (named && n && (st = vsc_hits_locate(hits, regions, in.data())) != VSC_OK)
                 throw std::runtime_error(st == VSC_ERR_RANGE ? "could not name the regions of the hits" : vsc_last_error(hctx));
             std::string list = std::string("#guideId\trank\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tmitScore\tsequence") +
-                               (named ? "\tregion" : "") + (by_votes ? "\trfVotes\n" : "\n");
+                               (named ? "\tregion" : "") + (by_table ? "\ttableScore\n" : by_votes ? "\trfVotes\n" : "\n");
             std::string window(VSC_READ_LEN, 'N');
             uint32_t rank = 0;
             for (uint64_t j = 0; j < n; ++j) {
@@ -803,12 +898,14 @@ int main(int argc, char **argv)
                 for (int b = 0; b < VSC_READ_LEN; ++b)
                     if ((VSC_HIT_MASK(h.info) >> b) & 1u) positions += (positions.empty() ? "" : ",") + std::to_string(b);
                 vsc_unpack_bases(ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs[h.contig].offset + h.pos, VSC_READ_LEN, &window[0]);
+                char tbuf[32] = "";
+                if (by_table) std::snprintf(tbuf, sizeof tbuf, "\t%.9f", (double)fixed[order[j]] * 0x1p-30);
                 std::snprintf(buf, sizeof buf, "%.6f", (double)score[order[j]] * 0x1p-24);
                 list += ids[h.guide] + '\t' + std::to_string(rank) + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' +
                         std::to_string(h.pos) + '\t' + std::to_string(h.pos + VSC_READ_LEN) + '\t' + (VSC_HIT_STRAND(h.info) ? '-' : '+') + '\t' +
                         std::to_string(VSC_HIT_NM(h.info)) + '\t' + (positions.empty() ? "-" : positions) + '\t' + buf + '\t' + window +
                         (named ? '\t' + (in[order[j]] < region_desc.size() ? region_desc[in[order[j]]] : "-") : "") +
-                        (by_votes ? '\t' + std::to_string(votes[order[j]]) : "") + '\n';
+                        (by_table ? std::string(tbuf) : by_votes ? '\t' + std::to_string(votes[order[j]]) : "") + '\n';
             }
             std::ofstream out(hits_path);
             if (!out.is_open()) throw std::runtime_error("Could not open the -T path.");
@@ -885,6 +982,7 @@ int main(int argc, char **argv)
         rc = 1;
     }
     if (hits) vsc_hits_free(hits);
+    vsc_score_table_free(table);
     if (pair_hits) vsc_hits_free(pair_hits);
     vsc_bulge_hits_free(bulge_hits);
     vsc_guides_free(found);

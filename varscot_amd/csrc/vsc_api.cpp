@@ -33,6 +33,7 @@
 #include "vsc_internal.h"
 #include "vsc_objects.h"
 #include "vsc_pairs.h"
+#include "vsc_table.h"
 #include "vsc_varmap.h"
 
 using namespace vsc;
@@ -236,8 +237,9 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs})
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->table_buf, &ctx->table_rows})
         b->release();
+    ctx->table_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
     ctx->varmap_serial = 0;
@@ -2024,6 +2026,63 @@ int classify_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, uint32_t
 
 hipError_t end_pass(vsc_ctx *ctx, PassFound &f, const char *lap, vsc_timing &t);
 
+// The device copy of `table` on this context: the context keeps the copy of the table it used last, keyed by its serial
+// number; another table is uploaded over it on the context's stream.
+int resident_table(vsc_ctx *ctx, const vsc_score_table *table)
+{
+    if (ctx->table_serial == table->serial && ctx->table_buf.p) return VSC_OK;
+    ctx->table_serial = 0;
+    VSC_HIP(ctx, ctx->table_buf.ensure(sizeof table->w));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->table_buf.p, table->w, sizeof table->w, hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the table as soon as its call returns)
+    ctx->table_serial = table->serial;
+    return VSC_OK;
+}
+
+// Table score stage (vsc_search_*_table), between find_pass and the sinks, where classify_pass sits for the classifier:
+// table_score_kernel scores the records where the search kernel left them (the table made resident by resident_table, the
+// interleaved planes by ensure_hl - both before the first pass) and leaves every record slot's fixed-point score in
+// ctx->vals_b, one word per slot of every tile of kSumTile - the layout of SelectArgs::score, which select_pass then takes as
+// its keys.  Nothing is read back: the kernel's time (kEvClassStart -> kEvClassEnd) is taken at the end of the pass.
+int table_score_pass(vsc_ctx *ctx, const vsc_genome *genome, PassFound &f, uint32_t n_reads, bool excluded)
+{
+    if (f.segs.empty()) return VSC_OK;
+    TableArgs a{};
+    VSC_HIP(ctx, sink_input(ctx, f, excluded));
+    a.in = f.sink;
+    a.weights = (const double *)ctx->table_buf.p;
+    a.hl = genome->d_hl;
+    a.first_pos = (uint32_t)(genome->first_word * 32);
+    a.n_plane_words = genome->dev_words;
+    a.guides = (const uint2 *)ctx->guides.p;  // the pass's reads
+    a.n_reads = n_reads;
+    VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.in.n_tiles * kSumTile * sizeof(uint32_t)));
+    a.slot_fixed = (uint32_t *)ctx->vals_b.p;
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvClassStart], ctx->stream));
+    VSC_HIP(ctx, launch_table_score(a, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvClassEnd], ctx->stream));
+    f.classified = true;
+    return VSC_OK;
+}
+
+// Table summary sink (vsc_search_*_table), behind table_score_pass: table_summary_kernel adds the fixed-point words into the
+// pass's rows of ctx->table_rows.  first / last: as votes_summary_pass takes them.
+int table_summary_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, bool excluded, vsc_timing &t, bool first, bool last)
+{
+    TableSummaryArgs a{};
+    if (!f.segs.empty()) {
+        VSC_HIP(ctx, sink_input(ctx, f, excluded));
+        static_cast<SinkInput &>(a) = f.sink;
+        a.out = (unsigned long long *)ctx->table_rows.p + (size_t)f.guide_base * kSumWords;
+        a.fixed = (const uint32_t *)ctx->vals_b.p;
+        a.n_reads = n_reads;
+    }
+    if (first && last) VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkStart], ctx->stream));
+    VSC_HIP(ctx, launch_table_summary(a, ctx->stream));
+    if (last) VSC_HIP(ctx, end_pass(ctx, f, "table summary + sync", t));
+    return VSC_OK;
+}
+
 // Votes summary sink (vsc_search_*_classified), behind classify_pass: votes_summary_kernel adds the votes words into the pass's
 // rows of ctx->votes_rows.  first: no sink ran before it in this pass (it opens finalize_ms); last: none follows (it ends the pass).
 int votes_summary_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, bool excluded, vsc_timing &t, bool first, bool last)
@@ -2079,8 +2138,9 @@ int summarize_pass(vsc_ctx *ctx, PassFound &f, bool excluded, vsc_timing &t, boo
 // (the reads' candidate counts), as find_pass has one for its counters.
 // reg / drop: the selection is made among the records on one side of the regions (SelectRegionArgs).
 // vote_trees (vsc_search_select_classified): the keys are the votes classify_pass left in ctx->vals_b, of a forest of that many trees.
+// table_key (vsc_search_select_table): the keys are the fixed-point scores table_score_pass left there.
 int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &sel, bool excluded, const RegionsView *reg = nullptr,
-                uint32_t drop = 0, uint32_t vote_trees = 0)
+                uint32_t drop = 0, uint32_t vote_trees = 0, uint32_t table_key = 0)
 {
     f.selected = true;
     if (f.n == 0) return VSC_OK;
@@ -2099,6 +2159,7 @@ int select_pass(vsc_ctx *ctx, PassFound &f, uint32_t n_reads, const vsc_select &
     VSC_HIP(ctx, ctx->vals_b.ensure((size_t)a.n_tiles * kSumTile * sizeof(uint32_t)));  // (the records the search placed, tiles rounded up)
     a.min_score = sel.min_score;
     a.vote_trees = vote_trees;
+    a.table_key = table_key;
     a.top_k = sel.top_k;
     a.n_reads = n_reads;
     // enough workgroups for every CU, few table flushes per region
@@ -2345,6 +2406,11 @@ struct SearchPlan {
     vsc_guide_votes *votes_rows = nullptr;
     bool selects_votes = false;
     const vsc_select_votes *select_votes = nullptr;
+    // vsc_search_*_table: the score table (checked after search_setup), the table rows to write (null: not wanted); a call
+    // that selects (`selects`) then selects by the table score
+    bool tables = false;
+    const vsc_score_table *table = nullptr;
+    vsc_guide_table_row *table_rows = nullptr;
 };
 
 // The one pass loop behind every search entry point: search_setup; the call's state on the device (excluded loci, regions,
@@ -2361,6 +2427,7 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     if (per_batch && !p.deliver) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null callback");
     if (p.selects && !p.select) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
     if (p.selects && (p.select->reserved[0] || p.select->reserved[1])) return fail_in(ctx, VSC_ERR_INVALID, p.who, "reserved fields must be 0");
+    if (p.tables && !p.table) return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
     if (p.classifies) {
         if (!p.classify || !p.classify->model || (n_guides && !p.classify->guide_activity) || (p.selects_votes && !p.select_votes))
             return fail_in(ctx, VSC_ERR_INVALID, p.who, "null argument");
@@ -2396,6 +2463,16 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
         }
     }
     const uint32_t vote_trees = classifying && p.select_votes ? p.classify->model->n_trees : 0u;
+    // the table scores are computed when something reads them: the rows, or a selection that decides anything
+    const bool tabling = p.tables && n_guides && (p.table_rows || selecting);
+    if (tabling) {
+        if ((rc = resident_table(ctx, p.table)) != VSC_OK) return rc;
+        VSC_HIP(ctx, ensure_hl(ctx, genome));
+        if (p.table_rows) {
+            VSC_HIP(ctx, ctx->table_rows.ensure((size_t)n_guides * sizeof(vsc_guide_table_row)));
+            VSC_HIP(ctx, hipMemsetAsync(ctx->table_rows.p, 0, (size_t)n_guides * sizeof(vsc_guide_table_row), ctx->stream));
+        }
+    }
     const uint32_t step = per_batch && p.batch_reads && p.batch_reads <= (uint32_t)kMaxPassReads ? p.batch_reads : (uint32_t)kMaxPassReads;
 
     std::unique_ptr<vsc_hits, int (*)(vsc_hits *)> hits(nullptr, vsc_hits_free);
@@ -2419,15 +2496,20 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
         const uint64_t projected = !per_batch && first ? (uint64_t)((double)used / first * n_guides * 1.02) + 4096 : 0;
         PassFound f;
         const bool votes_rows = classifying && p.votes_rows;
-        // (the sort is the records' only reader: no classifier, no rows, no selection walks them where the search left them)
-        const bool sort_only = p.records != Records::kNone && !classifying && !rows && !selecting;
+        const bool table_rows = tabling && p.table_rows;
+        // (the sort is the records' only reader: no classifier, no table, no rows, no selection walks them where the search left them)
+        const bool sort_only = p.records != Records::kNone && !classifying && !tabling && !rows && !selecting;
         rc = find_pass(ctx, genome, guides + first, count, first, params, p.keep_bases && t.algorithm == VSC_ALGO_SEED, sort_only, t, f);
         if (rc == VSC_OK && classifying) rc = classify_pass(ctx, genome, f, count, !excl.empty());
+        if (rc == VSC_OK && tabling) rc = table_score_pass(ctx, genome, f, count, !excl.empty());
         // (with another sink to follow, the summary leaves the end of the pass - and finalize_ms - to the sort)
-        if (rc == VSC_OK && rows) rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone && !votes_rows, p.rows_in ? &reg : nullptr);
+        if (rc == VSC_OK && rows)
+            rc = summarize_pass(ctx, f, !excl.empty(), t, p.records == Records::kNone && !votes_rows && !table_rows, p.rows_in ? &reg : nullptr);
         if (rc == VSC_OK && votes_rows) rc = votes_summary_pass(ctx, f, count, !excl.empty(), t, !rows, p.records == Records::kNone);
+        if (rc == VSC_OK && table_rows) rc = table_summary_pass(ctx, f, count, !excl.empty(), t, !rows, p.records == Records::kNone);
         if (rc == VSC_OK && selecting)
-            rc = select_pass(ctx, f, count, *select, !excl.empty(), p.filter ? &reg : nullptr, p.filter ? p.filter->scope : 0u, vote_trees);
+            rc = select_pass(ctx, f, count, *select, !excl.empty(), p.filter ? &reg : nullptr, p.filter ? p.filter->scope : 0u, vote_trees,
+                             tabling ? 1u : 0u);
         if (rc == VSC_OK && p.records != Records::kNone) rc = sort_pass(ctx, genome, f, hits.get(), used, projected, t);
         if (rc != VSC_OK) return rc;
         if (f.classified) {  // (the pass has ended: its stream is idle)
@@ -2455,6 +2537,10 @@ int run_search(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, u
     }
     if (classifying && p.votes_rows) {
         VSC_HIP(ctx, hipMemcpyAsync(p.votes_rows, ctx->votes_rows.p, (size_t)n_guides * sizeof(vsc_guide_votes), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (tabling && p.table_rows) {
+        VSC_HIP(ctx, hipMemcpyAsync(p.table_rows, ctx->table_rows.p, (size_t)n_guides * sizeof(vsc_guide_table_row), hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->timing = t;
@@ -3015,6 +3101,41 @@ int vsc_search_select_classified(vsc_ctx *ctx, const vsc_genome *genome, const u
     p.votes_rows = votes_rows;
     p.selects_votes = true;
     p.select_votes = select;
+    return run_search(ctx, genome, guides, n_guides, params, p);
+    });
+}
+
+int vsc_search_summary_table(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                             const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
+                             vsc_guide_summary *plain, vsc_guide_table_row *out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    if (n_guides && !out) return fail(ctx, VSC_ERR_INVALID, "vsc_search_summary_table: null argument");
+    SearchPlan p("vsc_search_summary_table", Records::kNone);
+    p.exclude = exclude;
+    p.rows = plain;
+    p.tables = true;
+    p.table = table;
+    p.table_rows = out;
+    return run_search(ctx, genome, guides, n_guides, params, p);
+    });
+}
+
+int vsc_search_select_table(vsc_ctx *ctx, const vsc_genome *genome, const uint64_t *guides, uint32_t n_guides,
+                            const vsc_search_params *params, const vsc_select *select, const vsc_locus *exclude,
+                            const vsc_score_table *table, vsc_guide_table_row *rows, vsc_hits **out)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    SearchPlan p("vsc_search_select_table", Records::kAccumulate, out);
+    p.exclude = exclude;
+    p.selects = true;
+    p.select = select;
+    p.tables = true;
+    p.table = table;
+    p.table_rows = rows;
     return run_search(ctx, genome, guides, n_guides, params, p);
     });
 }
@@ -4253,6 +4374,106 @@ int vsc_score_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits *hits,
         if (mit_flags) VSC_HIP(ctx, hipMemcpyAsync(mit_flags + done, s.mit_flags, m, hipMemcpyDeviceToHost, ctx->stream));
         if (features)
             VSC_HIP(ctx, hipMemcpyAsync(features + done * VSC_N_FEATURES, s.features, m * VSC_N_FEATURES, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        total_ms += ms;
+    }
+    ctx->timing.score_ms = total_ms;
+    return VSC_OK;
+    });
+}
+
+// ---- table-driven scores (the score: vsc_table.h, the kernels: vsc_table.hip) ---------------------------------
+int vsc_score_table_build(const double *pair, const double *pam, vsc_score_table **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!pair || !pam) return VSC_ERR_INVALID;
+    static std::atomic<uint64_t> serial{0};
+    vsc_score_table *t = new (std::nothrow) vsc_score_table();
+    if (!t) return VSC_ERR_NOMEM;
+    static_assert(sizeof t->w == kTableWeights * sizeof(double), "vsc_score_table holds pair[20][4][4] and pam[16]");
+    std::memcpy(t->w, pair, kTablePairs * sizeof(double));
+    std::memcpy(t->w + kTablePairs, pam, 16 * sizeof(double));
+    if (!table_valid(t->w)) {  // a weight outside [0, 1] (NaN included) or a diagonal entry other than 1
+        delete t;
+        return VSC_ERR_INVALID;
+    }
+    for (double w : t->w) t->zeros += w == 0.0;
+    t->serial = serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    *out = t;
+    return VSC_OK;
+}
+
+int vsc_score_table_free(vsc_score_table *table)
+{
+    delete table;
+    return VSC_OK;
+}
+
+int vsc_score_table_info(const vsc_score_table *table, vsc_score_table_stats *out)
+{
+    if (!table || !out) return VSC_ERR_INVALID;
+    *out = vsc_score_table_stats{table->serial, table->zeros, 0};
+    return VSC_OK;
+}
+
+int vsc_table_score(const vsc_score_table *table, uint64_t guide_code, uint64_t site_code, double *score, uint32_t *fixed)
+{
+    if (!table) return VSC_ERR_INVALID;
+    uint32_t gh, gl, sh, sl;
+    guide_planes(guide_code, &gh, &gl);
+    guide_planes(site_code, &sh, &sl);
+    const double x = table_score(table->w, gh, gl, sh, sl);
+    if (score) *score = x;
+    if (fixed) *fixed = table_fixed(x);
+    return VSC_OK;
+}
+
+double vsc_table_specificity(uint64_t score_sum)
+{
+    return 100.0 / (100.0 + (double)score_sum * 0x1p-30) * 100.0;
+}
+
+int vsc_score_hits_table(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hits *hits, const uint64_t *guides, uint32_t n_guides,
+                         uint64_t first, uint64_t count, const vsc_score_table *table, double *scores, uint32_t *fixed)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    ctx->err.clear();
+    if (!genome || !hits || !table || (n_guides && !guides)) return fail(ctx, VSC_ERR_INVALID, "vsc_score_hits_table: null argument");
+    if (genome->ctx != ctx || hits->ctx != ctx) return fail(ctx, VSC_ERR_INVALID, "vsc_score_hits_table: genome or hits belong to another context");
+    if (first > hits->n || count > hits->n - first) return fail(ctx, VSC_ERR_INVALID, "vsc_score_hits_table: row range outside the result");
+    ctx->timing.score_ms = 0;
+    if (count == 0 || (!scores && !fixed)) return VSC_OK;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    VSC_HIP(ctx, upload_read_planes(ctx, guides, n_guides));
+    VSC_HIP(ctx, ensure_hl(ctx, genome));
+    const int trc = resident_table(ctx, table);
+    if (trc != VSC_OK) return trc;
+    uint64_t rows = 0;
+    VSC_HIP(ctx, score_scratch(ctx, count, scores ? sizeof(double) : 0, fixed ? sizeof(uint32_t) : 0, 0, &rows));
+    double total_ms = 0;
+    for (uint64_t done = 0; done < count; done += rows) {  // one pass unless the scratch buffers had to be smaller than the result
+        const uint64_t m = std::min(rows, count - done);
+        TableArgs a{};
+        a.weights = (const double *)ctx->table_buf.p;
+        a.hl = genome->d_hl;
+        a.first_pos = (uint32_t)(genome->first_word * 32);
+        a.n_plane_words = genome->dev_words;
+        a.contig_off = genome->d_contig_off;
+        a.guides = (const uint2 *)ctx->score_guides.p;
+        a.n_reads = n_guides;
+        a.hits = hits->d_records + first + done;
+        a.n = m;
+        if (scores) a.scores = (double *)ctx->score_mit.p;
+        if (fixed) a.fixed = (uint32_t *)ctx->score_flags.p;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_table_score(a, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        if (scores) VSC_HIP(ctx, hipMemcpyAsync(scores + done, a.scores, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (fixed) VSC_HIP(ctx, hipMemcpyAsync(fixed + done, a.fixed, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         float ms = 0;
         VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));

@@ -388,6 +388,34 @@ struct VotesSummaryArgs : SummaryArgs {
     uint32_t n_trees, n_reads;
 };
 
+// ---- table-driven score (vsc_score_hits_table, vsc_search_*_table; vsc_table.hip, vsc_table.h) ---------------------------------
+// table_score_kernel scores sorted hits (`hits` non-null: one double and / or one fixed-point word per hit) or the search
+// kernel's records where they lie (`in.recs` non-null: one fixed-point word per record slot of every tile - SelectArgs::score's
+// layout; kSelDropped: sentinel, slot beyond its segment, read beyond the pass, excluded locus).
+struct TableArgs {
+    const double *weights;      // kTableWeights doubles: pair[20][4][4], pam[16]
+    const uint2 *hl;            // interleaved (hi, lo) plane words of the shard
+    uint32_t first_pos;
+    uint64_t n_plane_words;
+    const uint32_t *contig_off; // sorted hits only
+    const uint2 *guides;        // (hi plane, lo plane) per read (records: per pass-local read)
+    const vsc_hit *hits;
+    uint64_t n;
+    double *scores;             // may be null
+    uint32_t *fixed;            // may be null
+    SinkInput in;
+    uint32_t n_reads;           // reads of the pass (sorted hits: of the call)
+    uint32_t *slot_fixed;
+};
+
+// Table summary (vsc_search_summary_table; table_summary_kernel): the sinks' input + the fixed-point word of every record slot,
+// added into rows of kSumWords words per pass-local read, the layout of vsc_guide_table_row: score_sum, positive,
+// positive_nm[0..8], reserved.
+struct TableSummaryArgs : SummaryArgs {
+    const uint32_t *fixed;
+    uint32_t n_reads;
+};
+
 // ---- per-guide selection (vsc_search_select; select_*_kernel in vsc_kernels.hip) -------------------------------------------
 // An exact per-read radix select on the composite key  score (31 bits) << 33 | ~(strand << 32 | global position) (33 bits):
 // the larger key is the better hit (score descending, '+' before '-', position ascending), and keys are unique per read.
@@ -406,6 +434,8 @@ struct SelectArgs : SinkInput {
     uint32_t min_score;         // records below it are dropped
     uint32_t vote_trees;        // 0: the score is rint(MIT * 2^24), computed in round 1; else the forest's tree count: `score` holds
                                 // the records' votes on entry (classify in place), min_score is a floor on them, linear bins
+    uint32_t table_key;         // non-zero (vsc_search_select_table): `score` holds the records' fixed-point table scores on entry
+                                // (table_score_kernel), min_score is a floor on them, the logarithmic bins
     uint32_t top_k;             // 0: no limit
     uint32_t n_reads;           // reads of the pass
     uint32_t tiles_per_block;   // kSelMinTilesPerBlock .. kSelMaxTilesPerBlock
@@ -500,6 +530,9 @@ hipError_t launch_bin_finalize(const FinArgs &args, int max_groups, hipStream_t 
 // the search's records as they lie)
 hipError_t launch_fill_holes(const SortSeg *segs, uint32_t n_segs, uint64_t *recs, const uint32_t *fill, uint32_t fill_shift, hipStream_t stream);
 hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream);
+// vsc_table.hip
+hipError_t launch_table_score(const TableArgs &args, hipStream_t stream);
+hipError_t launch_table_summary(const TableSummaryArgs &args, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

@@ -973,6 +973,12 @@ struct SelectVotesKey {
         return 1u + min(votes, a.vote_trees) * (uint32_t)(kSelBins - 2) / a.vote_trees;  // 1 .. kSelBins - 1
     }
 };
+// SelectTableKey (vsc_search_select_table): the fixed-point table score table_score_kernel left in the score word (<= 2^30;
+// kSelDropped: not a counted hit).  Products of weights pile up near 0 as MIT scores do: the logarithmic bins.
+struct SelectTableKey {
+    static constexpr bool kStored = true;
+    static __device__ __forceinline__ uint32_t bin(const SelectArgs &, uint32_t fixed) { return select_bin(fixed); }
+};
 
 // Round 1, over the records where the search kernel left them (tiled as summary_kernel tiles them): every record's score
 // into the word beside it (kSelDropped: sentinel, excluded locus, below the floor) and into its read's histogram.  SEED: a
@@ -1233,6 +1239,9 @@ hipError_t launch_votes_summary(const VotesSummaryArgs &args, hipStream_t stream
 
 hipError_t launch_select_score(const SelectArgs &args, hipStream_t stream)
 {
+    if (args.table_key)
+        return launch_sink(select_score_kernel<false, false, SelectTableKey>, select_score_kernel<true, false, SelectTableKey>, args,
+                           args.tiles_per_block, kSelThreads, stream);
     if (args.vote_trees)
         return launch_sink(select_score_kernel<false, false, SelectVotesKey>, select_score_kernel<true, false, SelectVotesKey>, args,
                            args.tiles_per_block, kSelThreads, stream);
@@ -1253,6 +1262,9 @@ hipError_t launch_select_threshold(const SelectArgs &args, hipStream_t stream)
 
 hipError_t launch_select_compact(const SelectArgs &args, hipStream_t stream)
 {
+    if (args.table_key)
+        return launch_sink(select_compact_kernel<false, SelectTableKey>, select_compact_kernel<true, SelectTableKey>, args, args.tiles_per_block,
+                           kSelThreads, stream);
     if (args.vote_trees)
         return launch_sink(select_compact_kernel<false, SelectVotesKey>, select_compact_kernel<true, SelectVotesKey>, args, args.tiles_per_block,
                            kSelThreads, stream);

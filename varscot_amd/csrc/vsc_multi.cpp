@@ -606,6 +606,14 @@ void add_row(vsc_guide_votes &o, const vsc_guide_votes &p)
     for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.active_nm[k] += p.active_nm[k];
 }
 
+// ... and the table rows: sums of fixed-point scores and counts
+void add_row(vsc_guide_table_row &o, const vsc_guide_table_row &p)
+{
+    o.score_sum += p.score_sum;
+    o.positive += p.positive;
+    for (int k = 0; k <= VSC_MAX_MISMATCHES; ++k) o.positive_nm[k] += p.positive_nm[k];
+}
+
 // Where a shard's call writes its rows: one vector per shard, n_guides rows where the shard owns words of the genome and the
 // rows are wanted.  (Made before the fan-out, on the calling thread: no allocation can fail on a shard's thread.)
 template <class Row> std::vector<std::vector<Row>> shard_rows(const vsc_multi_genome *g, uint32_t n_guides, bool wanted)
@@ -660,6 +668,8 @@ struct RowsWanted {
     vsc_guide_summary *out, *out_in;
     vsc_guide_votes *out_votes;
     const char *who;             // the entry point, for the error texts
+    const vsc_score_table *table = nullptr;    // the table form: out_table, `out` optional (null: not that form)
+    vsc_guide_table_row *out_table = nullptr;
 };
 
 // vsc_multi_search_summary, _regions and _classified: every shard summarises its own windows with the single-device call of the
@@ -679,9 +689,11 @@ int join_rows(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, u
     if (erc != VSC_OK) return erc;
     auto part = shard_rows<vsc_guide_summary>(g, n_guides, w.out), part_in = shard_rows<vsc_guide_summary>(g, n_guides, w.regions);
     auto part_votes = shard_rows<vsc_guide_votes>(g, n_guides, w.cls);
+    auto part_table = shard_rows<vsc_guide_table_row>(g, n_guides, w.table);
     FanOut fo;
     const int rc = fan_out(m, g, &fo, [&](size_t r) {
         vsc_guide_summary *rows = w.out ? part[r].data() : nullptr;
+        if (w.table) return vsc_search_summary_table(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, w.table, rows, part_table[r].data());
         if (w.cls) return vsc_search_summary_classified(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, w.cls, rows, part_votes[r].data());
         if (w.regions) return vsc_search_summary_regions(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, w.regions, rows, part_in[r].data());
         return vsc_search_summary(m->ctx[r], g->shard[r], guides, n_guides, params, exclude, rows);
@@ -690,6 +702,7 @@ int join_rows(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, u
     add_shard_rows(g, part, n_guides, w.out);
     add_shard_rows(g, part_in, n_guides, w.out_in);
     add_shard_rows(g, part_votes, n_guides, w.out_votes);
+    add_shard_rows(g, part_table, n_guides, w.out_table);
     store_join_timing(m, fo, m->use_rccl);
     return VSC_OK;
     });
@@ -976,6 +989,17 @@ int vsc_multi_search_summary_classified(vsc_multi *m, const vsc_multi_genome *g,
     const bool null_arg = !g || g->multi != m || !params || !cls || !cls->model || (n_guides && (!guides || !out_votes || !cls->guide_activity));
     return join_rows(m, g, guides, n_guides, params, exclude, null_arg,
                      RowsWanted{nullptr, cls, out, nullptr, out_votes, "vsc_multi_search_summary_classified"});
+}
+
+int vsc_multi_search_summary_table(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
+                                   const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
+                                   vsc_guide_summary *plain, vsc_guide_table_row *out)
+{
+    const bool null_arg = !g || g->multi != m || !params || !table || (n_guides && (!guides || !out));
+    RowsWanted w{nullptr, nullptr, plain, nullptr, nullptr, "vsc_multi_search_summary_table"};
+    w.table = table;
+    w.out_table = out;
+    return join_rows(m, g, guides, n_guides, params, exclude, null_arg, w);
 }
 
 int vsc_multi_search_summary_regions(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,

@@ -121,6 +121,11 @@ struct vsc_ctx {
     // vsc_search_*_classified: the per-read vsc_guide_votes rows (the votes words beside the records lie in vals_b)
     vsc::DeviceBuf votes_rows;
     uint64_t regions_serial = 0;  // 0: none resident
+    // vsc_score_hits_table / vsc_search_*_table: the device copy of the score table this context used last (336 doubles, keyed
+    // by the table's serial number) and the per-read vsc_guide_table_row rows (the fixed-point words beside the records lie
+    // in vals_b; vsc_score_hits_table's outputs go through score_mit / score_flags)
+    vsc::DeviceBuf table_buf, table_rows;
+    uint64_t table_serial = 0;  // 0: none resident
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
@@ -209,6 +214,13 @@ struct vsc_regions {
     {
         return vsc::RegionsView{start.data(), end_max.data(), cls.data(), (uint32_t)start.size(), n_blocks, block_shift, rule};
     }
+};
+
+// A score table (include/varscot_hip.h "TABLE"; built and checked by vsc_score_table_build).  Host-only, immutable once built.
+struct vsc_score_table {
+    double w[336];        // pair[20][4][4], then pam[16] (vsc_table.h: kTableWeights)
+    uint64_t serial = 0;  // process-wide, handed out by vsc_score_table_build: what a context's device copy is keyed by
+    uint32_t zeros = 0;   // weights that are exactly 0
 };
 
 struct vsc_hits {
