@@ -1341,6 +1341,121 @@ int vsc_multi_search_summary_table(vsc_multi *m, const vsc_multi_genome *g, cons
                                    const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
                                    vsc_guide_summary *plain /* optional */, vsc_guide_table_row *out);
 
+/* ---- on-target efficiency of candidate guides (linear position-specific models) ------------------------------ */
+/*
+ * "Will this guide cut at its own site?" for the scores that are an intercept plus one weight per (position, base) and per
+ * (position, dinucleotide) over a context window around the site, plus a term in the G/C count of a range - the form of
+ * Doench 2014 "Rule Set 1" and of Moreno-Mateos 2015 "CRISPRscan" - optionally pushed through a logistic link.  The library
+ * ships no model: the caller brings the weights (vsc_eff_model_build).
+ *
+ * SHAPE    vsc_eff_shape { up, site_len, down, gc_start, gc_len, link, reserved[2] }.
+ *          C = up + site_len + down is the context length: the site and its flanks.
+ *          up, down <= 16.  site_len 16 .. 32: 23 for vsc_guides' candidates, the pattern's length for vsc_pattern_guides'.
+ *          C <= 64.
+ *          The G/C range is [gc_start, gc_start + gc_len) in context coordinates and lies inside the context.
+ *          gc_len == 0: no G/C term.
+ *          link is VSC_EFF_IDENTITY or VSC_EFF_LOGISTIC.
+ *          Anything else, or a non-zero reserved field: VSC_ERR_INVALID.
+ * CONTEXT  of a locus (c, p, strand), in READ orientation:
+ *            '+': c[p - up, p + site_len + down).
+ *            '-': revcomp(c[p - down, p + site_len + up)).
+ *          Context position up is the first base of the site as the guide reads it.
+ *          It is defined only when it lies wholly inside contig c and holds no non-ACGT letter.
+ * MODEL    intercept, mono[C][4], di[C - 1][16] indexed 4 * b_j + b_{j+1}, gc[gc_len + 1] (NULL iff gc_len == 0).
+ *          Bases are coded A 0, C 1, G 2, T 3.
+ *          Every value is a finite double.  Anything else: VSC_ERR_INVALID.
+ *          -0.0 is stored as +0.0.
+ * LINEAR   The linear predictor, fp64, in this order:
+ *            x = intercept.
+ *            For j = 0 .. C - 1 ascending: x = x + mono[j][b_j].
+ *            For j = 0 .. C - 2 ascending: x = x + di[j][4 * b_j + b_{j+1}].
+ *            If gc_len: x = x + gc[number of G and C in the range].
+ *          Each addition rounds once.  There is no multiplication, so nothing contracts.
+ *          Device, host (vsc_eff_score_text) and any restatement that adds in this order agree to the bit.
+ * UNDEF    An undefined predictor is the quiet NaN with bits 0x7FF8000000000000.
+ *          Each candidate falls in exactly one class, tested in this order (vsc_eff_stats counts them; they add up to n):
+ *            invalid       contig >= n_contigs, strand > 1, or the site itself leaves its contig.
+ *            off_contig    the flanks leave the contig.
+ *            not_resident  the context is not wholly inside the plane words this genome object was loaded with.
+ *                          (A shard: nothing in front of first_word, nothing behind its halo.)
+ *            has_n         the context holds a non-ACGT letter.
+ *            defined
+ * LINK     identity: the score is x.  logistic: 1.0 / (1.0 + exp(-x)).
+ *          vsc_eff_link evaluates it on the HOST, with the C library's exp.
+ *          The device never calls exp: its exp is another function and the bits would differ.
+ *          Floors (min_linear) are in the linear domain.  link(undefined) = undefined.
+ *
+ * vsc_eff_model is host-only and immutable.  vsc_eff_model_info returns its process-wide serial number, its shape and the
+ * count of weights (mono, di, gc) that are not 0.  A context keeps the device copy of the model it used last, keyed by the
+ * serial number; vsc_ctx_release_scratch gives it back, with the candidates and scores on their way.
+ * vsc_eff_score_text scores one context of C letters (any case) in read orientation on the host, with the very function the
+ * kernels call; a non-ACGT letter gives undefined (VSC_OK), a text of another length is VSC_ERR_INVALID.
+ *
+ * vsc_loci_efficiency: linear[i] = the predictor of loci[i] (host arrays, n entries; a locus names the site's first base on
+ * the forward strand, as everywhere).  One upload, one kernel, one copy back.  stats is optional.  n == 0: VSC_OK, nothing is
+ * launched.  vsc_guides_efficiency scores the candidates where they lie on the device - no locus travels - and requires
+ * site_len == 23 (else VSC_ERR_INVALID); the host-only object of vsc_multi_guides_enumerate goes the vsc_loci_efficiency way.
+ * vsc_pattern_guides_efficiency is the same for vsc_pattern_guides: site_len is the pattern's length, which the CALLER vouches
+ * for, as with vsc_pattern_guide_text.  linear[i] belongs to candidate i.  A genome of another context, an object of another
+ * context, a NULL model or a NULL linear with n > 0: VSC_ERR_INVALID.
+ *
+ * vsc_guides_filter_efficiency / vsc_pattern_guides_filter_efficiency: *out = the candidates of `in` whose predictor is
+ * defined and >= min_linear - codes and loci copied unchanged, in the input's order; `in` stays as it is.  Count pass, scan,
+ * write pass over tiles of 1 024 candidates: no append atomic, the bytes depend on the input and the model only.  min_linear
+ * NaN: VSC_ERR_INVALID.  -inf keeps every defined candidate, +inf none (an empty result is a result).  The result is a normal
+ * object of its kind on ctx's device: the searches, vsc_guides_locate, vsc_guides_pairs and these calls take it as any other.
+ * A host-only input is uploaded first.
+ *
+ * vsc_ctx_timing afterwards: score_ms = total_ms = the kernel (the filter: both passes and the scan), sites = n, genome_bytes
+ * = 16 bytes of locus read and 8 bytes of score written per candidate (the filter: the loci read twice, 24 bytes read and 24
+ * written per survivor).  The other fields are 0.
+ *
+ * Not offered: a vsc_multi_* entry (the multi-device enumeration already joins its candidates on the host, and a shard cannot
+ * see in front of its first word - load the genome on one device, or score by vsc_loci_efficiency there); ranking or top-K
+ * per target interval; neural scores (Rule Set 2 / 3, DeepCpf1).
+ */
+#define VSC_EFF_IDENTITY 0
+#define VSC_EFF_LOGISTIC 1
+typedef struct vsc_eff_model vsc_eff_model;
+typedef struct {
+    uint32_t up, site_len, down; /* C = up + site_len + down */
+    uint32_t gc_start, gc_len;   /* context coordinates; gc_len 0: no G/C term */
+    uint32_t link;               /* VSC_EFF_* */
+    uint32_t reserved[2];        /* 0 */
+} vsc_eff_shape;
+typedef struct {
+    uint64_t serial;          /* process-wide number of the model */
+    vsc_eff_shape shape;
+    uint32_t nonzero_weights; /* entries of mono, di and gc that are not 0 */
+    uint32_t reserved;
+} vsc_eff_model_stats;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t reserved[3]; /* 0 */
+} vsc_eff_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_eff_stats) == 64, "vsc_eff_stats layout");
+#else
+_Static_assert(sizeof(vsc_eff_stats) == 64, "vsc_eff_stats layout");
+#endif
+int vsc_eff_model_build(const vsc_eff_shape *shape, double intercept, const double *mono /* [C][4] */,
+                        const double *di /* [C - 1][16] */, const double *gc /* [gc_len + 1]; NULL iff gc_len == 0 */,
+                        vsc_eff_model **out);
+int vsc_eff_model_free(vsc_eff_model *model);
+int vsc_eff_model_info(const vsc_eff_model *model, vsc_eff_model_stats *out);
+int vsc_eff_score_text(const vsc_eff_model *model, const char *context /* C letters, read orientation */, double *linear);
+double vsc_eff_link(const vsc_eff_model *model, double linear);
+int vsc_loci_efficiency(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n,
+                        const vsc_eff_model *model, double *linear /* host, n */, vsc_eff_stats *stats /* optional */);
+int vsc_guides_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_eff_model *model,
+                          double *linear /* host, one per candidate */, vsc_eff_stats *stats /* optional */);
+int vsc_pattern_guides_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_eff_model *model,
+                                  double *linear /* host, one per candidate */, vsc_eff_stats *stats /* optional */);
+int vsc_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_eff_model *model,
+                                 double min_linear, vsc_guides **out);
+int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
+                                         const vsc_eff_model *model, double min_linear, vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -56,6 +56,12 @@ void vsc_debug_set_host_timing(int on);
 int vsc_debug_pattern_target_ranges(const vsc_contig *contigs, uint32_t n_contigs, const vsc_interval *iv, uint64_t n, uint32_t rule,
                                     uint32_t len, uint32_t *ranges, uint64_t capacity, uint64_t *n_ranges);
 
+/* A vsc_guides made of the caller's arrays (tests of the calls that take one: candidates no enumeration would return, more of
+ * them than a small genome holds).  ctx != NULL: the arrays are copied to its device, as vsc_guides_enumerate leaves its
+ * result; ctx == NULL: a host-only object, as vsc_multi_guides_enumerate returns.  Nothing is checked.  Freed with
+ * vsc_guides_free. */
+int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

@@ -224,6 +224,30 @@ class ScoreTableStats(C.Structure):
     _fields_ = [("serial", C.c_uint64), ("zero_weights", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+EFF_IDENTITY, EFF_LOGISTIC = 0, 1  # VSC_EFF_*
+
+
+class EffShape(C.Structure):
+    """vsc_eff_shape: the context window of an efficiency model (C = up + site_len + down), its G/C range in context
+    coordinates (gc_len 0: no G/C term) and its link."""
+    _fields_ = [("up", C.c_uint32), ("site_len", C.c_uint32), ("down", C.c_uint32), ("gc_start", C.c_uint32), ("gc_len", C.c_uint32),
+                ("link", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class EffModelStats(C.Structure):
+    """vsc_eff_model_stats"""
+    _fields_ = [("serial", C.c_uint64), ("shape", EffShape), ("nonzero_weights", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class EffStats(C.Structure):
+    """vsc_eff_stats: the candidates of a call by class; the five counts add up to n."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n")}
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -386,6 +410,16 @@ SYMBOLS = [
     ("vsc_search_select_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, _vp,
                                           C.POINTER(_vp)]),
     ("vsc_multi_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
+    ("vsc_eff_model_build", C.c_int, [C.POINTER(EffShape), C.c_double, _vp, _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_eff_model_free", C.c_int, [_vp]),
+    ("vsc_eff_model_info", C.c_int, [_vp, C.POINTER(EffModelStats)]),
+    ("vsc_eff_score_text", C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
+    ("vsc_eff_link", C.c_double, [_vp, C.c_double]),
+    ("vsc_loci_efficiency", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_guides_efficiency", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_pattern_guides_efficiency", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)
@@ -396,6 +430,7 @@ DEBUG_SYMBOLS = [
     ("vsc_ctx_create_masked", C.c_int, [C.c_int, _vp, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_debug_pattern_target_ranges", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_multi_create_debug", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(MultiDebugParams), C.POINTER(_vp)]),
+    ("vsc_debug_guides_from_host", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(_vp)]),
 ]
 
 _lib = None

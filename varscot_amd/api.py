@@ -440,6 +440,189 @@ class ScoreTable:
             pass
 
 
+EFF_UNDEFINED_BITS = 0x7FF8000000000000  # the one NaN an undefined efficiency predictor is
+
+
+class EfficiencyModel:
+    """An on-target efficiency model (vsc_eff_model): a linear predictor over the context of a site - `up` bases in front of
+    it, its site_len bases, `down` bases behind it, C = up + site_len + down, in READ orientation - that is
+    intercept + sum_j mono[j][b_j] + sum_j di[j][4 b_j + b_{j+1}] + gc[G/C count of gc_range], bases A 0, C 1, G 2, T 3, added
+    in exactly that order (include/varscot_hip.h "LINEAR").  mono is [C][4], di [C - 1][16], gc [gc_range[1] + 1] with
+    gc_range = (start, length) in context coordinates (both None: no G/C term).  link: "identity" or "logistic" - the link is
+    applied on the host by link(); every device call works in the linear domain.  The package ships no model."""
+
+    LINKS = {"identity": _lib.EFF_IDENTITY, "logistic": _lib.EFF_LOGISTIC}
+
+    def __init__(self, up, site_len, down, intercept, mono, di, gc=None, gc_range=None, link="identity", shape=None):
+        """shape: an EffShape to pass as it is (tests)."""
+        if link not in self.LINKS:
+            raise ValueError("link must be 'identity' or 'logistic'")
+        if (gc is None) != (gc_range is None) and shape is None:
+            raise ValueError("gc and gc_range come together")
+        self.up, self.site_len, self.down, self.link_name = int(up), int(site_len), int(down), link
+        self.intercept = float(intercept)
+        self.mono = np.ascontiguousarray(mono, dtype=np.float64)
+        self.di = np.ascontiguousarray(di, dtype=np.float64)
+        self.gc = None if gc is None else np.ascontiguousarray(gc, dtype=np.float64).reshape(-1)
+        self.gc_range = None if gc_range is None else (int(gc_range[0]), int(gc_range[1]))
+        self._h = None
+        if shape is None:
+            fields = (self.up, self.site_len, self.down) + (self.gc_range or (0, 0))
+            if any(not 0 <= v < 2 ** 32 for v in fields):
+                raise ValueError("the shape's fields must fit 32 unsigned bits")
+            C_ = self.context_len
+            if self.mono.shape != (C_, 4) or self.di.shape != (max(C_ - 1, 0), 16) or \
+                    (self.gc is not None and len(self.gc) != self.gc_range[1] + 1):
+                raise ValueError("an efficiency model of context length %d is mono[%d][4], di[%d][16] and gc[gc_len + 1]" % (C_, C_, C_ - 1))
+            shape = _lib.EffShape(self.up, self.site_len, self.down, fields[3], fields[4], self.LINKS[link])
+        h = C.c_void_p()
+        check(lib().vsc_eff_model_build(C.byref(shape), self.intercept, ptr(self.mono), ptr(self.di), ptr(self.gc), C.byref(h)))
+        self._h = h
+
+    @property
+    def context_len(self):
+        return self.up + self.site_len + self.down
+
+    @classmethod
+    def from_features(cls, up, site_len, down, intercept, features, gc=None, gc_range=None, link="identity"):
+        """A model from a parameter list as the papers print it: (pos, letters, weight) triples - pos 0-based in context
+        coordinates, letters one base (mono) or two (the dinucleotide that starts at pos).  What the list does not name
+        weighs 0; a feature named twice is an error."""
+        C_ = int(up) + int(site_len) + int(down)
+        mono, di = np.zeros((C_, 4)), np.zeros((max(C_ - 1, 0), 16))
+        seen = set()
+        for pos, letters, weight in features:
+            pos, key = int(pos), (int(pos), letters.upper().replace("U", "T"))
+            if key in seen:
+                raise ValueError("feature (%d, %r) is given twice" % (pos, letters))
+            seen.add(key)
+            if len(letters) not in (1, 2) or not 0 <= pos <= C_ - len(letters):
+                raise ValueError("feature (%d, %r): one or two letters that lie inside the context of %d" % (pos, letters, C_))
+            b = [_base(ch, "feature (%d, %r)" % (pos, letters)) for ch in letters]
+            if len(b) == 1:
+                mono[pos, b[0]] = float(weight)
+            else:
+                di[pos, 4 * b[0] + b[1]] = float(weight)
+        return cls(up, site_len, down, intercept, mono, di, gc=gc, gc_range=gc_range, link=link)
+
+    @classmethod
+    def from_tsv(cls, path):
+        """A model from the text file to_tsv writes (tools/README.md): tab- or blank-separated lines `shape up site_len down`,
+        `link identity|logistic`, `intercept x`, `gc_range start length`, `mono pos X w`, `di pos XY w`, `gc count w`; '#'
+        starts a comment.  `shape` comes before every weight, `gc_range` before every `gc`.  What the file does not name
+        weighs 0.  An unknown key, a weight before its shape, a line given twice and anything that does not parse are
+        refused with the line number."""
+        shape = gc_range = None
+        intercept, link, feats, gc_w = 0.0, "identity", [], {}
+        once = set()
+        with open(path) as fh:
+            for n, line in enumerate(fh, 1):
+                f = line.split("#", 1)[0].split()
+                if not f:
+                    continue
+                where = "%s:%d" % (path, n)
+                try:
+                    key, a = f[0], f[1:]
+                    if key in ("shape", "link", "intercept", "gc_range"):
+                        if key in once:
+                            raise ValueError("'%s' is given twice" % key)
+                        once.add(key)
+                    if key in ("mono", "di", "gc") and shape is None:
+                        raise ValueError("'%s' before the 'shape' line" % key)
+                    if key == "shape" and len(a) == 3:
+                        shape = tuple(int(v) for v in a)
+                    elif key == "link" and len(a) == 1:
+                        if a[0] not in cls.LINKS:
+                            raise ValueError("link must be 'identity' or 'logistic'")
+                        link = a[0]
+                    elif key == "intercept" and len(a) == 1:
+                        intercept = float(a[0])
+                    elif key == "gc_range" and len(a) == 2:
+                        gc_range = (int(a[0]), int(a[1]))
+                    elif key in ("mono", "di") and len(a) == 3:
+                        if len(a[1]) != (1 if key == "mono" else 2):
+                            raise ValueError("'%s' takes %s" % (key, "one letter" if key == "mono" else "two letters"))
+                        if (int(a[0]), a[1].upper()) in once:
+                            raise ValueError("feature (%s, %s) is given twice" % (a[0], a[1]))
+                        once.add((int(a[0]), a[1].upper()))
+                        if not 0 <= int(a[0]) <= sum(shape) - len(a[1]):
+                            raise ValueError("position %s lies outside the context of %d" % (a[0], sum(shape)))
+                        for ch in a[1]:
+                            _base(ch, where)
+                        feats.append((int(a[0]), a[1], float(a[2])))
+                    elif key == "gc" and len(a) == 2:
+                        if gc_range is None:
+                            raise ValueError("'gc' before the 'gc_range' line")
+                        if int(a[0]) in gc_w or not 0 <= int(a[0]) <= gc_range[1]:
+                            raise ValueError("G/C count %s is given twice or lies outside 0..%d" % (a[0], gc_range[1]))
+                        gc_w[int(a[0])] = float(a[1])
+                    else:
+                        raise ValueError("unknown key or wrong number of fields: %r" % " ".join(f))
+                except ValueError as e:
+                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+        if shape is None:
+            raise ValueError("%s: no 'shape' line" % path)
+        gc = None if gc_range is None else [gc_w.get(k, 0.0) for k in range(gc_range[1] + 1)]
+        return cls.from_features(shape[0], shape[1], shape[2], intercept, feats, gc=gc, gc_range=gc_range, link=link)
+
+    def to_tsv(self, path):
+        """The model as a text file from_tsv reads back to the bit: the weights that are not 0, as repr() prints them."""
+        with open(path, "w") as fh:
+            fh.write("# on-target efficiency model: context = %d upstream + %d site + %d downstream bases, read orientation\n"
+                     % (self.up, self.site_len, self.down))
+            fh.write("shape\t%d\t%d\t%d\nlink\t%s\nintercept\t%r\n" % (self.up, self.site_len, self.down, self.link_name, self.intercept))
+            if self.gc_range is not None:
+                fh.write("gc_range\t%d\t%d\n" % self.gc_range)
+            for j, b in zip(*np.nonzero(self.mono)):
+                fh.write("mono\t%d\t%s\t%r\n" % (j, "ACGT"[b], float(self.mono[j, b])))
+            for j, d in zip(*np.nonzero(self.di)):
+                fh.write("di\t%d\t%s%s\t%r\n" % (j, "ACGT"[d // 4], "ACGT"[d % 4], float(self.di[j, d])))
+            if self.gc is not None:
+                for k in np.nonzero(self.gc)[0]:
+                    fh.write("gc\t%d\t%r\n" % (k, float(self.gc[k])))
+
+    def info(self):
+        st = _lib.EffModelStats()
+        check(lib().vsc_eff_model_info(self._h, C.byref(st)))
+        s = st.shape
+        return {"serial": int(st.serial), "up": int(s.up), "site_len": int(s.site_len), "down": int(s.down), "gc_start": int(s.gc_start),
+                "gc_len": int(s.gc_len), "link": {v: k for k, v in self.LINKS.items()}[int(s.link)],
+                "nonzero_weights": int(st.nonzero_weights)}
+
+    def score_text(self, context):
+        """vsc_eff_score_text: the linear predictor of one context of C letters in read orientation, on the host by the
+        function the kernels run; a letter outside ACGT gives the undefined NaN.  No device is needed."""
+        b = context if isinstance(context, bytes) else context.encode()
+        x = C.c_double()
+        check(lib().vsc_eff_score_text(self._h, b, C.byref(x)))
+        return x.value
+
+    def link(self, x):
+        """vsc_eff_link: a linear predictor (or an array of them) through the model's link, on the host."""
+        L = lib()
+        if np.ndim(x) == 0:
+            return L.vsc_eff_link(self._h, float(x))
+        a = np.asarray(x, dtype=np.float64)
+        return np.array([L.vsc_eff_link(self._h, float(v)) for v in a.reshape(-1)], dtype=np.float64).reshape(a.shape)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsc_eff_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _eff_partial(stats, allow_partial):
+    if stats["not_resident"] and not allow_partial:
+        raise ValueError("%d candidates have a context that is not resident on this genome object (a shard holds nothing in "
+                         "front of its first word); allow_partial=True returns them as undefined" % stats["not_resident"])
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -904,24 +1087,35 @@ class Genome:
         return recs, out_rows
 
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
-                          max_guides=0, params=None):
+                          max_guides=0, params=None, efficiency=None, min_efficiency=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
         than max_t_run T in it (0: no limit).  targets: None (everywhere) or (contig, start, end) triples / an INTERVAL_DTYPE
         array, applied to the whole site under `rule` ("overlap" / "inside"); an empty list keeps nothing.  Returns a
         PatternGuides (.codes, .loci, .text()) in ascending (contig, pos), '+' before '-'.  More than max_guides (0: no cap)
-        candidates raise VarscotError -34.  params: a PatternEnumParams to pass as it is (tests)."""
+        candidates raise VarscotError -34.  params: a PatternEnumParams to pass as it is (tests).
+        efficiency= an EfficiencyModel whose site_len is the pattern's length: returns (PatternGuides, linear float64[n]) - the
+        candidates' predictors, computed where the candidates lie on the device (vsc_pattern_guides_efficiency).
+        min_efficiency=x (needs efficiency=): only the candidates whose predictor is defined and >= x, linear domain
+        (vsc_pattern_guides_filter_efficiency)."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
         # (an empty target set is a pointer that is not NULL with n = 0)
         iv_ptr = None if iv is None else ptr(iv if len(iv) else np.zeros(1, dtype=_lib.INTERVAL_DTYPE))
         L = lib()
+        self._eff_args(efficiency, min_efficiency, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
+        linear, held = None, [h]
         try:
+            if efficiency is not None:
+                linear = self._eff_on_handle(held, efficiency, min_efficiency, L.vsc_pattern_guides_count,
+                                             L.vsc_pattern_guides_efficiency, L.vsc_pattern_guides_filter_efficiency,
+                                             L.vsc_pattern_guides_free)
+            h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
             check(L.vsc_pattern_guides_data(h, C.byref(pc), C.byref(pl)), self.ctx._h)
@@ -931,18 +1125,72 @@ class Genome:
                 codes = np.frombuffer((C.c_char * (n * 8)).from_address(pc.value), dtype=np.uint64).copy()
                 loci = np.frombuffer((C.c_char * (n * 16)).from_address(pl.value), dtype=_lib.LOCUS_DTYPE).copy()
         finally:
-            L.vsc_pattern_guides_free(h)
-        return PatternGuides(p.decode(), protospacer, codes, loci)
+            L.vsc_pattern_guides_free(held[0])
+        found = PatternGuides(p.decode(), protospacer, codes, loci)
+        return found if efficiency is None else (found, linear)
 
     def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, **filters):
         """Every guide of `targets` under a pattern, with its off-target counts: enumerate_pattern(pattern, protospacer,
         targets, **filters) followed by search_pattern (rows only) of the guides in query form on the same resident genome.
         Returns (PatternGuides, uint32 rows of shape (n, 9)); count[0] is reduced by one for the guide's own locus, which is
-        always a hit at NM 0 (the query form has N outside the protospacer)."""
+        always a hit at NM 0 (the query form has N outside the protospacer).  With efficiency= (and min_efficiency=) among
+        the filters, as enumerate_pattern takes them: only the survivors are searched, and their predictors come last."""
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
+        extra = ()
+        if filters.get("efficiency") is not None:
+            found, extra = found[0], (found[1],)
         _, rows = self.search_pattern(pattern, found.text(), max_mismatches, guide_batch=guide_batch, records=False)
         rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
-        return found, rows
+        return (found, rows) + extra
+
+    # ---- on-target efficiency (vsc_*_efficiency) ------------------------------------------------------------------------
+    @staticmethod
+    def _eff_args(model, floor, site_len):
+        if model is None:
+            if floor is not None:
+                raise ValueError("min_efficiency needs efficiency=model")
+            return
+        if not isinstance(model, EfficiencyModel):
+            raise ValueError("efficiency must be an EfficiencyModel")
+        if model.site_len != site_len:
+            raise ValueError("the model's site_len is %d; these candidates are %d bases long" % (model.site_len, site_len))
+
+    def _eff_on_handle(self, held, model, floor, count_fn, score_fn, filter_fn, free_fn):
+        """The predictors of the candidate handle held[0] under a model, computed where the candidates lie.  With a floor the
+        handle is first replaced by the filter's result: the input is freed and held[0] is the result - the caller frees
+        held[0], whatever happens here."""
+        if floor is not None:
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], model._h, float(floor), C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        linear = np.empty(int(count_fn(held[0])), dtype=np.float64)
+        st = _lib.EffStats()
+        check(score_fn(self.ctx._h, self._h, held[0], model._h, ptr(linear), C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return linear
+
+    def efficiency(self, loci_or_found, model, allow_partial=False):
+        """vsc_loci_efficiency: the linear predictors of candidates under an EfficiencyModel, computed on the device from the
+        resident planes: (linear float64[n], stats).  loci_or_found: what enumerate_guides returns (its loci are taken), a
+        PatternGuides, or a LOCUS_DTYPE array / (contig, pos, strand) rows - a locus names the site's first base on the
+        forward strand.  An undefined predictor is the NaN with bits EFF_UNDEFINED_BITS; stats counts the candidates by
+        class: defined, invalid, off_contig, not_resident, has_n.  Raises when a context is not resident on this object (a
+        shard) unless allow_partial=True."""
+        if isinstance(loci_or_found, PatternGuides):
+            loci = loci_or_found.loci
+        elif isinstance(loci_or_found, tuple) and len(loci_or_found) >= 2 and isinstance(loci_or_found[1], np.ndarray) \
+                and loci_or_found[1].dtype == _lib.LOCUS_DTYPE:
+            loci = loci_or_found[1]
+        else:
+            loci = loci_or_found
+        lo = _loci(loci, len(loci))
+        linear = np.empty(len(lo), dtype=np.float64)
+        st = _lib.EffStats()
+        check(lib().vsc_loci_efficiency(self.ctx._h, self._h, ptr(lo), len(lo), model._h, ptr(linear), C.byref(st)), self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        return linear, stats
 
     def summarize(self, guides, max_mismatches, extra_pam=None, algorithm="auto", exclude=None, regions=None):
         """vsc_search_summary: per guide, the NM counts, the fixed-point MIT sum (units of 2^-24), the reference-UB count
@@ -1076,7 +1324,7 @@ class Genome:
         return (hits, rows) if summary else hits
 
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
-                         labels=False):
+                         labels=False, efficiency=None, min_efficiency=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -1084,13 +1332,27 @@ class Genome:
         '+' before '-': codes are what every search takes, loci what `exclude` takes.  More than max_guides (0: no cap)
         candidates raise VarscotError -34.  params: an EnumParams to pass as it is (tests).
         labels=True (needs regions; or labels=another Regions): returns (codes, loci, labels uint32[n]) - per candidate the
-        index of the interval it lies in, REGION_NONE if none, as Regions.locate gives it (vsc_guides_locate, on the device)."""
+        index of the interval it lies in, REGION_NONE if none, as Regions.locate gives it (vsc_guides_locate, on the device).
+        efficiency= an EfficiencyModel with site_len 23: the candidates' linear predictors (float64[n], computed where the
+        candidates lie on the device: vsc_guides_efficiency) come last in the returned tuple.  min_efficiency=x (needs
+        efficiency=): only the candidates whose predictor is defined and >= x, linear domain (vsc_guides_filter_efficiency)."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
+        self._eff_args(efficiency, min_efficiency, READ_LEN)
+        L = lib()
         h = C.c_void_p()
-        check(lib().vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
+        check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
+        if efficiency is None:
+            return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
+        held = [h]
+        try:
+            linear = self._eff_on_handle(held, efficiency, min_efficiency, L.vsc_guides_count, L.vsc_guides_efficiency,
+                                         L.vsc_guides_filter_efficiency, L.vsc_guides_free)
+        except BaseException:
+            L.vsc_guides_free(held[0])
+            raise
+        return _guides_arrays(held[0], lambda code: check(code, self.ctx._h), lab) + (linear,)
 
     def enumerate_pairs(self, delta, regions=None, **filters):
         """enumerate_guides(regions, **filters) and the guide pairs among its candidates (vsc_guides_pairs, on the device
@@ -1117,14 +1379,16 @@ class Genome:
         return (found[0], found[1], pairs) + tuple(found[2:])
 
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
-               **search_options):
+               efficiency=None, min_efficiency=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
         A PAM other than GG / GA needs extra_pam=pam among the search options for the guide's own locus to be a hit.
-        labels: as enumerate_guides; the labels then come last: (codes, loci, rows, labels)."""
+        labels: as enumerate_guides; the labels then come last: (codes, loci, rows, labels).
+        efficiency= / min_efficiency=: as enumerate_guides; only the survivors are searched, and the linear predictors come
+        last of all: (codes, loci, rows[, labels], linear)."""
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
-                                      labels=labels)
+                                      labels=labels, efficiency=efficiency, min_efficiency=min_efficiency)
         codes, loci = found[0], found[1]
         return (codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)) + tuple(found[2:])
 

@@ -84,6 +84,15 @@
 // CRISPOR's cfdSpecScore - and the hits that score above 0.  With -T the listing is selected and ranked by the table score
 // (vsc_search_select_table): -K the best K, -S a floor on the table score, 0 .. 1, and a last column tableScore (%.9f); that
 // runs on one device, without -A and -r votes.  -W does not combine with -v.  Without -W every output is what it was.
+// -Y model.tsv (needs -E, one device) scores every found guide's ON-TARGET EFFICIENCY with a linear position-specific model
+// (vsc_guides_efficiency; the form of Rule Set 1 and CRISPRscan: an intercept plus a weight per (position, base) and per
+// (position, dinucleotide) over a context window around the site plus a G/C term; the file is what
+// varscot_amd.EfficiencyModel.to_tsv writes, tools/README.md; its site_len must be 23).  The -L listing gains two last columns,
+//   efficiencyLinear efficiency
+// = the linear predictor (%.17g; NA when the context leaves its sequence or holds an N) and the predictor through the model's
+// link.  -y MIN (needs -Y) keeps only the candidates whose predictor is defined and >= MIN, linear domain
+// (vsc_guides_filter_efficiency), BEFORE the off-target search: every output holds the survivors only.  Without -Y every
+// output is what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -93,6 +102,7 @@
 #include <map>
 #include <sstream>
 
+#include "eff_model_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
 
@@ -141,6 +151,9 @@ int main(int argc, char **argv)
         {'U', "bulge-hits", "Path to the TSV file of the bulged sites (.tsv/.txt); needs -u", false},
         {'W', "score-table", "Path to a score table (.tsv/.txt; lines 'j g s w' and 'PAM XY w'): adds the columns tableScoreSum tableSpecScore "
                              "tablePositive; with -T, -K / -S (then a table score, 0 .. 1) select by the table score", false},
+        {'Y', "efficiency-model", "Path to an on-target efficiency model (.tsv/.txt; lines shape, link, intercept, gc_range, mono, di, gc): "
+                                  "adds the columns efficiencyLinear efficiency to the -L file (needs -E, one device)", false},
+        {'y', "min-efficiency", "Keep only the -E candidates whose efficiency predictor is defined and >= this value, linear domain (needs -Y)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -290,6 +303,30 @@ int main(int argc, char **argv)
             return 1;
         }
         ep.strands = v == "+" ? 1 : v == "-" ? 2 : 0;
+    }
+    // -Y / -y: the efficiency model of the found guides
+    const bool efficient = opts[33].set;
+    double min_eff = 0.0;
+    if (opts[34].set && !efficient) {
+        std::fprintf(stderr, "%s: -y is a floor on the efficiency predictor of the -Y model: give -Y\n", argv[0]);
+        return 1;
+    }
+    if (efficient && !discover) {
+        std::fprintf(stderr, "%s: -Y scores the guides that -E finds: give -E\n", argv[0]);
+        return 1;
+    }
+    if (efficient && !has_extension(opts[33].value, {"tsv", "txt"})) {
+        std::fprintf(stderr, "%s: the -Y model must be a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
+    if (opts[34].set) {
+        const std::string &v = opts[34].value;
+        char *yend = nullptr;
+        min_eff = std::strtod(v.c_str(), &yend);
+        if (v.empty() || *yend || std::isnan(min_eff)) {
+            std::fprintf(stderr, "%s: -y takes a floor on the linear predictor, a number, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
     }
     const bool naming = opts[21].set;
     if (naming) {
@@ -442,8 +479,14 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    if (efficient && devices.size() != 1) {
+        std::fprintf(stderr, "%s: -Y scores the candidates on one device: it does not combine with a device list\n", argv[0]);
+        return 1;
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
+    vsc_eff_model *eff_model = nullptr;
     vsc_genome *genome = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
     vsc_genome *win_genome = nullptr;
@@ -456,6 +499,12 @@ int main(int argc, char **argv)
     vsc_guides *found = nullptr;
     int rc = 1;
     try {
+        if (efficient) {  // (read before the index and the device: a model that does not fit costs nothing)
+            vsc_eff_shape eff_shape{};
+            eff_model = load_eff_model(opts[33].value, &eff_shape);
+            if (eff_shape.site_len != (uint32_t)VSC_READ_LEN)
+                throw std::runtime_error("-Y: the model's site_len is " + std::to_string(eff_shape.site_len) + "; the guides are 23 bases long");
+        }
         const PackedIndex ix = read_index(index_prefix);
         uint64_t size = 0;
         int64_t mtime = 0;
@@ -563,6 +612,17 @@ int main(int argc, char **argv)
         if (discover) {
             st = multi ? vsc_multi_guides_enumerate(multi, mgenome, targets, &ep, &found) : vsc_guides_enumerate(ctx, genome, targets, &ep, &found);
             if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+            std::vector<double> eff_linear;
+            if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
+                if (opts[34].set) {
+                    vsc_guides *kept = nullptr;
+                    if (vsc_guides_filter_efficiency(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                    vsc_guides_free(found);
+                    found = kept;
+                }
+                eff_linear.resize(vsc_guides_count(found));
+                if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            }
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -584,7 +644,8 @@ int main(int argc, char **argv)
                 seqs.push_back(seq);
                 if (opts[20].set)
                     bed6 += chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
-                            "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) + '\n';
+                            "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
+                            (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") + '\n';
             }
             if (opts[20].set) {
                 std::ofstream out(guides_bed_path);
@@ -983,6 +1044,7 @@ int main(int argc, char **argv)
     }
     if (hits) vsc_hits_free(hits);
     vsc_score_table_free(table);
+    vsc_eff_model_free(eff_model);
     if (pair_hits) vsc_hits_free(pair_hits);
     vsc_bulge_hits_free(bulge_hits);
     vsc_guides_free(found);

@@ -11,6 +11,11 @@
 // lists the sites in ascending (guide, strand, chrom, start, site length) order under guide_summary -U's columns
 //   #guideId chrom start end strand kind size index mismatches sequence
 // Without -u every output is what it was.
+// -Y model.tsv (needs -E) scores every found guide's ON-TARGET EFFICIENCY with a linear position-specific model
+// (vsc_pattern_guides_efficiency; the file is what varscot_amd.EfficiencyModel.to_tsv writes, tools/README.md; its site_len
+// must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
+// its sequence or holds an N) and efficiency (the predictor through the model's link).  -y MIN (needs -Y) keeps only the
+// candidates whose predictor is defined and >= MIN, linear domain, BEFORE the search.  Without -Y every output is what it was.
 // Host C++ only: the search runs in libvarscot_hip.so (vsc_search_pattern); there is no CPU search here.  Every argument is
 // checked before a device is opened.
 #include <cstdio>
@@ -20,6 +25,7 @@
 #include <map>
 #include <sstream>
 
+#include "eff_model_host.hpp"
 #include "vsc_host.hpp"
 
 using namespace vsc_host;
@@ -94,6 +100,9 @@ int main(int argc, char **argv)
         {'u', "bulges", "DNA,RNA: largest DNA and RNA bulge, 0 .. 2 each (e.g. 1,1; needs -p): adds the bulged sites - -O gains bulgeCount "
                         "and <class>mm0 .. <class>mm<M> (br2 br1 bd1 bd2)", false},
         {'U', "bulge-hits", "Path to the TSV file of the bulged sites (.tsv/.txt); needs -u", false},
+        {'Y', "efficiency-model", "With -E: path to an on-target efficiency model (.tsv/.txt) whose site_len is the pattern's length: "
+                                  "the -E listing gains the columns efficiencyLinear efficiency", false},
+        {'y', "min-efficiency", "With -Y: keep only the candidates whose efficiency predictor is defined and >= this value, linear domain", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -222,6 +231,30 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: -U lists the bulged sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
         return 1;
     }
+    // -Y / -y: the efficiency model of the found guides
+    const bool efficient = opts[16].set;
+    double min_eff = 0.0;
+    if (opts[17].set && !efficient) {
+        std::fprintf(stderr, "%s: -y is a floor on the efficiency predictor of the -Y model: give -Y\n", argv[0]);
+        return 1;
+    }
+    if (efficient && !enumerate) {
+        std::fprintf(stderr, "%s: -Y scores the guides that -E finds: give -E\n", argv[0]);
+        return 1;
+    }
+    if (efficient && !has_extension(opts[16].value, {"tsv", "txt"})) {
+        std::fprintf(stderr, "%s: the -Y model must be a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
+    if (opts[17].set) {
+        const std::string &v = opts[17].value;
+        char *yend = nullptr;
+        min_eff = std::strtod(v.c_str(), &yend);
+        if (v.empty() || *yend || min_eff != min_eff) {
+            std::fprintf(stderr, "%s: -y takes a floor on the linear predictor, a number, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+    }
     char *end = nullptr;
     long mm = 0;
     if (opts[3].set) {
@@ -249,10 +282,17 @@ int main(int argc, char **argv)
     vsc_pattern_hits *hits = nullptr;
     vsc_pattern_guides *found = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
+    vsc_eff_model *eff_model = nullptr;
     int rc = 1;
     try {
         std::vector<FastaRecord> guides;
         const uint32_t len = (uint32_t)pattern.size();
+        if (efficient) {  // (read before the index and the device: a model that does not fit costs nothing)
+            vsc_eff_shape eff_shape{};
+            eff_model = load_eff_model(opts[16].value, &eff_shape);
+            if (eff_shape.site_len != len)
+                throw std::runtime_error("-Y: the model's site_len is " + std::to_string(eff_shape.site_len) + "; the pattern has " + std::to_string(len) + " letters");
+        }
         std::string letters;
         if (!enumerate) {
             guides = read_fasta(guides_path);
@@ -282,6 +322,17 @@ int main(int argc, char **argv)
             st = vsc_guides_enumerate_pattern(ctx, genome, pattern.c_str(), len, &ep, opts[8].set ? (targets.empty() ? &none : targets.data()) : nullptr,
                                               targets.size(), &found);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<double> eff_linear;
+            if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
+                if (opts[17].set) {
+                    vsc_pattern_guides *kept = nullptr;
+                    if (vsc_pattern_guides_filter_efficiency(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                    vsc_pattern_guides_free(found);
+                    found = kept;
+                }
+                eff_linear.resize(vsc_pattern_guides_count(found));
+                if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            }
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -289,7 +340,7 @@ int main(int argc, char **argv)
             std::printf("Guides found (total: %llu).\n", (unsigned long long)n);
             std::ofstream out(opts[7].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
-            out << "#guide\tchrom\tpos\tstrand\n";
+            out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -297,7 +348,9 @@ int main(int argc, char **argv)
                     throw std::runtime_error("a code of the enumeration is no guide");
                 guides[i].seq = letters.substr(i * len, len);
                 guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
-                out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+') << '\n';
+                out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+');
+                if (efficient) out << '\t' << eff_text(eff_linear[i]) << '\t' << eff_text(vsc_eff_link(eff_model, eff_linear[i]));
+                out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }
@@ -412,6 +465,7 @@ int main(int argc, char **argv)
     }
     vsc_pattern_hits_free(hits);
     vsc_pattern_guides_free(found);
+    vsc_eff_model_free(eff_model);
     vsc_bulge_hits_free(bulge_hits);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);

@@ -11,6 +11,7 @@
 //   vsc_bulge.hip          bulge-tolerant search
 //   vsc_pattern.hip        pattern search, pattern guide discovery
 //   vsc_pattern_bulge.hip  bulges under a pattern
+//   vsc_efficiency.hip     on-target efficiency of candidates
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "vsc_bulge.h"
+#include "vsc_efficiency.h"
 #include "vsc_pattern.h"
 #include "vsc_pattern_enum.h"
 #include "vsc_pattern_bulge.h"
@@ -237,9 +239,11 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->table_buf, &ctx->table_rows})
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
+                         &ctx->eff_out})
         b->release();
     ctx->table_serial = 0;
+    ctx->eff_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
     ctx->varmap_serial = 0;
@@ -336,6 +340,7 @@ int vsc_genome_load(vsc_ctx *ctx, const uint32_t *hi, const uint32_t *lo, const 
     g->first_word = first_word;
     g->own_words = own_words;
     g->dev_words = dev_words;
+    g->held_words = n_words;
     g->n_tiles = (uint32_t)n_tiles;
     g->n_contigs = n_contigs;
     g->h_contig_off = off;
@@ -3616,6 +3621,304 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
     return guarded(guides->ctx, [&]() -> int {
     return locate_records(guides->ctx, regions, (const char *)guides->storage.p + guides->loci_at, guides->n, false, labels,
                           "vsc_guides_locate");
+    });
+}
+
+}  // extern "C"
+
+// ---- on-target efficiency (the definition: vsc_efficiency.h, the kernels: vsc_efficiency.hip) -------------------
+namespace {
+
+// The device copy of `model` on this context, as resident_table keeps the score table's: the copy of the model the context
+// used last, keyed by its serial number; another model is uploaded over it on the context's stream.
+int resident_eff_model(vsc_ctx *ctx, const vsc_eff_model *model, EffModelView &view)
+{
+    if (!(ctx->eff_serial == model->serial && ctx->eff_buf.p)) {
+        ctx->eff_serial = 0;
+        const size_t bytes = model->w.size() * sizeof(double);
+        VSC_HIP(ctx, ctx->eff_buf.ensure(bytes));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_buf.p, model->w.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the model as soon as its call returns)
+        ctx->eff_serial = model->serial;
+    }
+    view = EffModelView{(const double *)ctx->eff_buf.p, model->intercept, model->shape, (uint32_t)model->w.size()};
+    return VSC_OK;
+}
+
+// the planes of a resident genome as eff_context reads them (an object that carries the contig table only holds no word)
+EffPlanes eff_planes(const vsc_genome *g)
+{
+    const bool planes = g->d_hi && g->d_lo && g->d_nm;
+    return EffPlanes{g->d_hi, g->d_lo, g->d_nm, g->first_word, planes ? g->held_words : 0, planes ? g->dev_words : 0,
+                     g->d_contig_off, g->d_contig_end, g->n_contigs};
+}
+
+int eff_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_model *model, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !model) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    return VSC_OK;
+}
+
+// The predictors of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first) - into host memory:
+// the model resident, eff_score_kernel, one copy back of the scores and one of the class counts.
+int eff_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_model *model, const void *d_loci, const vsc_locus *h_loci,
+              uint64_t n, double *linear, vsc_eff_stats *stats, const char *who)
+{
+    if (stats) *stats = vsc_eff_stats{};
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        return VSC_OK;
+    }
+    if (!linear) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EffArgs a{};
+    const int mrc = resident_eff_model(ctx, model, a.m);
+    if (mrc != VSC_OK) return mrc;
+    a.g = eff_planes(genome);
+    a.n = n;
+    const size_t head = 256;  // the class counts, in front of the scores
+    static_assert(kEffClasses * sizeof(unsigned long long) <= 256, "the class counts fit their part of eff_out");
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(double)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.linear = (double *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_eff_score(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kEffClasses] = {};
+    VSC_HIP(ctx, hipMemcpyAsync(linear, a.linear, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+    }
+    t.score_ms = t.total_ms = ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(double));
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+// vsc_guides_efficiency / vsc_pattern_guides_efficiency: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int eff_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_eff_model *model, bool need_23, double *linear,
+                     vsc_eff_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const int rc = eff_check(ctx, genome, model, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
+    const bool dev = guides->ctx != nullptr;
+    return eff_score(ctx, genome, model, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
+                     guides->n, linear, stats, who);
+    });
+}
+
+// vsc_guides_filter_efficiency / vsc_pattern_guides_filter_efficiency: run_enumeration's two passes over tiles of kEffTile
+// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the efficiency calls report theirs.
+template <class Guides>
+int eff_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_eff_model *model, bool need_23, double min_linear, Guides **out,
+               const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    const int rc = eff_check(ctx, genome, model, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
+    if (std::isnan(min_linear)) return fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN");
+    const uint64_t n = in->n;
+    const uint64_t tiles = (n + kEffTile - 1) / kEffTile;
+    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EffFilterArgs a{};
+    const int mrc = resident_eff_model(ctx, model, a.m);
+    if (mrc != VSC_OK) return mrc;
+    a.g = eff_planes(genome);
+    a.n = n;
+    a.min_linear = min_linear;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_eff_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_eff_model_build(const vsc_eff_shape *shape, double intercept, const double *mono, const double *di, const double *gc,
+                        vsc_eff_model **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!shape || !mono || !di) return VSC_ERR_INVALID;
+    if (shape->reserved[0] || shape->reserved[1] || shape->link > VSC_EFF_LOGISTIC) return VSC_ERR_INVALID;
+    const EffShape s{shape->up, shape->site_len, shape->down, shape->gc_start, shape->gc_len};
+    if (!eff_shape_valid(s) || (s.gc_len != 0) != (gc != nullptr)) return VSC_ERR_INVALID;
+    return guarded(nullptr, [&]() -> int {
+    static std::atomic<uint64_t> serial{0};
+    std::unique_ptr<vsc_eff_model> m(new vsc_eff_model());
+    const uint32_t C = eff_context_len(s);
+    m->shape = s;
+    m->link = shape->link;
+    m->w.assign(eff_n_weights(s), 0.0);
+    bool finite = std::isfinite(intercept);
+    auto put = [&](uint32_t at, double v) {  // -0.0 is stored as +0.0: x is then never -0.0, and x + 0.0 keeps its bits
+        finite = finite && std::isfinite(v);
+        m->w[at] = v == 0.0 ? 0.0 : v;
+        m->nonzero += v != 0.0;
+    };
+    for (uint32_t i = 0; i < 4 * C; ++i) put(i, mono[i]);
+    for (uint32_t j = 0; j + 1 < C; ++j)
+        for (uint32_t b0 = 0; b0 < 4; ++b0)
+            for (uint32_t b1 = 0; b1 < 4; ++b1) put(eff_di_at(C) + 16 * j + b0 + 4 * b1, di[16 * j + 4 * b0 + b1]);
+    for (uint32_t k = 0; s.gc_len && k <= s.gc_len; ++k) put(eff_gc_at(C) + k, gc[k]);
+    if (!finite) return VSC_ERR_INVALID;
+    m->intercept = intercept == 0.0 ? 0.0 : intercept;
+    m->serial = serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    *out = m.release();
+    return VSC_OK;
+    });
+}
+
+int vsc_eff_model_free(vsc_eff_model *model)
+{
+    delete model;
+    return VSC_OK;
+}
+
+int vsc_eff_model_info(const vsc_eff_model *model, vsc_eff_model_stats *out)
+{
+    if (!model || !out) return VSC_ERR_INVALID;
+    const EffShape &s = model->shape;
+    *out = vsc_eff_model_stats{model->serial, vsc_eff_shape{s.up, s.site_len, s.down, s.gc_start, s.gc_len, model->link, {0, 0}}, model->nonzero, 0};
+    return VSC_OK;
+}
+
+int vsc_eff_score_text(const vsc_eff_model *model, const char *context, double *linear)
+{
+    if (!model || !context || !linear) return VSC_ERR_INVALID;
+    const uint32_t C = eff_context_len(model->shape);
+    if (strnlen(context, C + 1) != C) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    *linear = eff_undefined();
+    for (uint32_t j = 0; j < C; ++j) {
+        const int b = base_code(context[j]);
+        if (b > 3) return VSC_OK;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+    }
+    *linear = eff_linear(model->w.data(), model->intercept, model->shape, ch, cl);
+    return VSC_OK;
+}
+
+double vsc_eff_link(const vsc_eff_model *model, double linear)
+{
+    if (!model || std::isnan(linear)) return eff_undefined();
+    return model->link == VSC_EFF_LOGISTIC ? 1.0 / (1.0 + std::exp(-linear)) : linear;
+}
+
+int vsc_loci_efficiency(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_eff_model *model,
+                        double *linear, vsc_eff_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_efficiency";
+    const int rc = eff_check(ctx, genome, model, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    return eff_score(ctx, genome, model, nullptr, loci, n, linear, stats, fn);
+    });
+}
+
+int vsc_guides_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_eff_model *model, double *linear,
+                          vsc_eff_stats *stats)
+{
+    return eff_score_guides(ctx, genome, guides, model, true, linear, stats, "vsc_guides_efficiency");
+}
+
+int vsc_pattern_guides_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_eff_model *model,
+                                  double *linear, vsc_eff_stats *stats)
+{
+    return eff_score_guides(ctx, genome, guides, model, false, linear, stats, "vsc_pattern_guides_efficiency");
+}
+
+int vsc_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_eff_model *model, double min_linear,
+                                 vsc_guides **out)
+{
+    return eff_filter(ctx, genome, in, model, true, min_linear, out, "vsc_guides_filter_efficiency");
+}
+
+int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_eff_model *model,
+                                         double min_linear, vsc_pattern_guides **out)
+{
+    return eff_filter(ctx, genome, in, model, false, min_linear, out, "vsc_pattern_guides_filter_efficiency");
+}
+
+int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (n && (!codes || !loci)) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> g(new vsc_guides(), object_free<vsc_guides>);
+    g->n = n;
+    g->codes.assign(codes, codes + n);
+    g->loci.assign(loci, loci + n);
+    g->host_valid = true;
+    if (ctx && n) {
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        g->ctx = ctx;
+        g->loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, g->storage.ensure(g->loci_at + (size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(g->storage.p, codes, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync((char *)g->storage.p + g->loci_at, loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    g->ctx = ctx;
+    *out = g.release();
+    return VSC_OK;
     });
 }
 

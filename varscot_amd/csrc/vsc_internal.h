@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "varscot_hip.h"
+#include "vsc_efficiency.h"
 
 namespace vsc {
 
@@ -533,6 +534,40 @@ hipError_t launch_rf_predict(const RfArgs &args, hipStream_t stream);
 // vsc_table.hip
 hipError_t launch_table_score(const TableArgs &args, hipStream_t stream);
 hipError_t launch_table_summary(const TableSummaryArgs &args, hipStream_t stream);
+// vsc_efficiency.hip (the definition: vsc_efficiency.h).  The model as the kernels read it: the weights in the
+// order of vsc_efficiency.h (the context's device copy), at most kEffMaxWeights of them.
+struct EffModelView {
+    const double *w;
+    double intercept;
+    EffShape shape;
+    uint32_t n_weights;
+};
+struct EffArgs {
+    EffPlanes g;
+    EffModelView m;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    double *linear;               // [n] out: the predictor, kEffUndefinedBits where it is undefined
+    unsigned long long *stats;    // [kEffClasses], zeroed before the launch: the kernel adds its candidates per class
+};
+// the filter's two passes, driven by run_enumeration (vsc_api.cpp): tile i of the work list = candidates [i * kEffTile, ..)
+constexpr uint32_t kEffTile = 1024;
+struct EffFilterArgs {
+    EffPlanes g;
+    EffModelView m;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    double min_linear;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_eff_score(const EffArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_eff_filter(const EffFilterArgs &args, bool write, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

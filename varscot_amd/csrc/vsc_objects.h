@@ -126,6 +126,11 @@ struct vsc_ctx {
     // in vals_b; vsc_score_hits_table's outputs go through score_mit / score_flags)
     vsc::DeviceBuf table_buf, table_rows;
     uint64_t table_serial = 0;  // 0: none resident
+    // vsc_*_efficiency: the device copy of the efficiency model this context used last (its weights in the order of
+    // vsc_efficiency.h, keyed by the model's serial number), the candidates of a call that brings them from the host (loci;
+    // the filter of a host-only object: codes, then loci) and the call's outputs (the class counts, then the scores)
+    vsc::DeviceBuf eff_buf, eff_in, eff_out;
+    uint64_t eff_serial = 0;  // 0: none resident
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
@@ -172,6 +177,7 @@ struct vsc_genome {
     std::vector<uint32_t> h_contig_off, h_contig_end;  // the same table on the host (what regions are checked against)
     uint2 *d_hl = nullptr;  // interleaved planes, built on first scoring call
     uint64_t first_word = 0, own_words = 0, dev_words = 0;
+    uint64_t held_words = 0;  // the words the genome was loaded with (own + halo): what dev_words pads with N is not the genome's
     uint32_t n_tiles = 0, n_contigs = 0;
     uint64_t device_bytes = 0;
     // sites, seen_rate, sort_slots_ok: sizing hints that searches learn (mutable: a search takes the genome as const)
@@ -221,6 +227,16 @@ struct vsc_score_table {
     double w[336];        // pair[20][4][4], then pam[16] (vsc_table.h: kTableWeights)
     uint64_t serial = 0;  // process-wide, handed out by vsc_score_table_build: what a context's device copy is keyed by
     uint32_t zeros = 0;   // weights that are exactly 0
+};
+
+// An efficiency model (include/varscot_hip.h "MODEL"; built and checked by vsc_eff_model_build).  Host-only, immutable once built.
+struct vsc_eff_model {
+    vsc::EffShape shape{};
+    uint32_t link = 0;
+    double intercept = 0;
+    std::vector<double> w;  // mono, the transposed di, gc (vsc_efficiency.h): what the device copy holds
+    uint64_t serial = 0;    // process-wide, handed out by vsc_eff_model_build: what a context's device copy is keyed by
+    uint32_t nonzero = 0;   // weights that are not 0
 };
 
 struct vsc_hits {
