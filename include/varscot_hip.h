@@ -578,8 +578,8 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
  * or written (rows only); rows == NULL: records only.  rows: host memory, n_guides entries.  n_guides == 0: VSC_OK, nothing is
  * launched (*out = an empty result).  A genome loaded as one shard reports the sites that START in its own words (one halo word
  * covers the 32 bases); the records of all shards, merged by the order above, are the whole genome's.  No seed index is used
- * and none is needed; MIT scores and classifier rows are defined for 20 + NGG only and stay with their own calls (bulges under a
- * pattern: since added, vsc_search_pattern_bulges below).
+ * and none is needed; MIT scores and classifier rows are defined for 20 + NGG only and stay with their own calls (table scores: since
+ * added, vsc_search_pattern_table further down; bulges under a pattern: since added, vsc_search_pattern_bulges below).
  * The guides of a pattern are found by vsc_guides_enumerate_pattern (below).
  * vsc_ctx_timing afterwards: scan_ms = total_ms = the kernels, hits, sites = candidates (sites that satisfy the pattern and hold
  * no N, both strands), pairs = candidate x guide comparisons, passes = rounds; the sort, finalize and score fields 0.
@@ -1340,6 +1340,100 @@ int vsc_search_select_table(vsc_ctx *ctx, const vsc_genome *genome, const uint64
 int vsc_multi_search_summary_table(vsc_multi *m, const vsc_multi_genome *g, const uint64_t *guides, uint32_t n_guides,
                                    const vsc_search_params *params, const vsc_locus *exclude, const vsc_score_table *table,
                                    vsc_guide_summary *plain /* optional */, vsc_guide_table_row *out);
+
+/* ---- table scores for pattern hits: per hit, per guide, floor and top-K --------------------------------------- */
+/*
+ * The score above for any nuclease: a product of weights by (protospacer position, guide base, site base) times a weight for
+ * the site's letters at up to four PAM positions, over the hits of vsc_search_pattern.  The library ships no table.
+ *
+ * TABLE   vsc_pattern_table, host-only and immutable, with a process-wide serial number like vsc_score_table.
+ *         Shape: { len L (16..32), ps_start, ps_len (ps_len >= 1, ps_start + ps_len <= L), n_pam (0..4), pam_pos[4] }.
+ *         pam_pos[0..n_pam) are read positions, strictly ascending, all below L and outside [ps_start, ps_start + ps_len).
+ *         Weights: pair[ps_len][4][4] and pam[4^n_pam], doubles.
+ *         pair[i][g][s] is the weight of guide base g against site base s at read position ps_start + i.
+ *           Bases are A 0, C 1, G 2, T 3.
+ *           s is the site's letter in READ orientation, that is pattern orientation.
+ *         pam[k] has k = sum over t of s[pam_pos[t]] * 4^(n_pam - 1 - t).  With n_pam = 0 there is one weight, pam[0].
+ *         Every weight is finite and lies in [0, 1]. pair[i][b][b] is exactly 1.
+ *         Anything else, or a bad shape: VSC_ERR_INVALID.
+ * SCORE   For a hit of guide G at a site with s in read orientation (w on '+', revcomp(w) on '-'):
+ *           x = 1.0.
+ *           For i = 0 .. ps_len - 1 in this order, with j = ps_start + i:
+ *             if G[j] is one of A, C, G, T and s[j] != G[j] then x = x * pair[i][G[j]][s[j]].
+ *           Then x = x * pam[k].
+ *         Arithmetic is fp64, one rounding per multiplication, no contraction.
+ *         A protospacer position whose guide letter is degenerate (N or any other IUPAC set) takes no part, even where it
+ *         counts as a mismatch in NM.  Guide letters outside the protospacer take no part.
+ * FIXED   f = rint(x * 2^30), round half to even. f <= 2^30.  The unit of every sum, floor and selection key, as above.
+ * HITS    Exactly the hits of vsc_search_pattern for the same planes, pattern, guides and params.
+ *         A table whose len is not the call's len: VSC_ERR_INVALID.
+ * ROWS    vsc_guide_table_row per guide: score_sum, positive (hits with f > 0) and positive_nm[NM] over ALL hits, before any
+ *         selection.  vsc_table_specificity applies to score_sum as it does above.
+ * SELECT  vsc_pattern_select { top_k, min_score, reserved[2] }.
+ *         Per guide, the survivors are the hits with f >= min_score.
+ *         Of those, the first top_k (0: all) are kept under the ranking f descending, then strand, contig, pos ascending.
+ *         The result stays in record order (guide, strand, contig, pos). One uint32_t f per record runs parallel to the records.
+ *         With select == NULL or { 0, 0 } the records are vsc_search_pattern's bytes.
+ *         max_hits caps the RETURNED records: the survivors.  When there are more, the call returns VSC_ERR_RANGE,
+ *         vsc_last_error names their count and nothing is returned.
+ * SHARDS  Rows of shards add: they are integers.  Records and f words of shards merge by record order.  Top-K across shards
+ *         is the caller's re-cut and is not offered here.
+ * ANCHOR  With L = 23, protospacer (0, 20), pam_pos = {21, 22} and a vsc_score_table's weights, f equals vsc_table_score's f
+ *         bit for bit for every (guide, site).
+ *
+ * vsc_pattern_table_score scores one guide (len IUPAC letters) against one site (len letters of ACGT in read orientation; any
+ * other letter: VSC_ERR_INVALID) on the host, with the very function the kernels call.  vsc_search_pattern_table takes
+ * vsc_search_pattern's arguments and refusals, a table and an optional selection; out, rows (the NM rows) and table_rows may
+ * each be NULL, all three NULL: VSC_ERR_INVALID.  A non-zero reserved field of select: VSC_ERR_INVALID.  out == NULL: no
+ * record is allocated or written and select is not applied (the rows are over all hits in any case).  The score is taken in
+ * the write pass, where the hit is found; the selection, when one is asked for, runs per round behind it.
+ * vsc_pattern_hits_scores / _dev return the f words of a scored result (NULL / VSC_ERR_INVALID on a result of
+ * vsc_search_pattern).  The context keeps the device copy of the table it used last, keyed by the serial number;
+ * vsc_ctx_release_scratch gives it back.  vsc_ctx_timing afterwards: score_ms = the selection stage, the rest as after
+ * vsc_search_pattern (scan_ms includes the scored write pass).
+ */
+typedef struct vsc_pattern_table vsc_pattern_table;
+typedef struct {
+    uint32_t len;        /* L, 16..32 */
+    uint32_t ps_start;   /* the protospacer: read positions [ps_start, ps_start + ps_len) */
+    uint32_t ps_len;
+    uint32_t n_pam;      /* 0..4 */
+    uint32_t pam_pos[4]; /* read positions of the PAM letters that the score looks at; unused entries 0 */
+} vsc_pattern_table_shape;
+typedef struct {
+    uint64_t serial;        /* process-wide number of the table */
+    uint32_t zero_weights;  /* weights that are exactly 0 */
+    uint32_t reserved;
+    vsc_pattern_table_shape shape;
+} vsc_pattern_table_stats;
+typedef struct {
+    uint32_t top_k;      /* 0: all */
+    uint32_t min_score;  /* in f units */
+    uint32_t reserved[2];
+} vsc_pattern_select;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pattern_table_shape) == 32, "vsc_pattern_table_shape layout");
+static_assert(sizeof(vsc_pattern_table_stats) == 48, "vsc_pattern_table_stats layout");
+static_assert(sizeof(vsc_pattern_select) == 16, "vsc_pattern_select layout");
+#else
+_Static_assert(sizeof(vsc_pattern_table_shape) == 32, "vsc_pattern_table_shape layout");
+_Static_assert(sizeof(vsc_pattern_table_stats) == 48, "vsc_pattern_table_stats layout");
+_Static_assert(sizeof(vsc_pattern_select) == 16, "vsc_pattern_select layout");
+#endif
+int vsc_pattern_table_build(const vsc_pattern_table_shape *shape, const double *pair /* [ps_len][4][4] */,
+                            const double *pam /* [4^n_pam] */, vsc_pattern_table **out);
+int vsc_pattern_table_free(vsc_pattern_table *table);
+int vsc_pattern_table_info(const vsc_pattern_table *table, vsc_pattern_table_stats *out);
+int vsc_pattern_table_score(const vsc_pattern_table *table, const char *guide, const char *site_text /* read orientation, len letters */,
+                            double *score /* optional */, uint32_t *fixed /* optional */);
+int vsc_search_pattern_table(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides,
+                             uint32_t len, const vsc_pattern_params *params, const vsc_pattern_table *table,
+                             const vsc_pattern_select *select /* may be NULL */, vsc_pattern_hits **out /* may be NULL */,
+                             vsc_pattern_summary *rows /* may be NULL */, vsc_guide_table_row *table_rows /* may be NULL */);
+/* Host copy of the f words (made on first use; valid until vsc_pattern_hits_free). */
+int vsc_pattern_hits_scores(vsc_pattern_hits *hits, const uint32_t **fixed);
+/* Device pointer (valid until vsc_pattern_hits_free); NULL when the result is empty or not a scored one. */
+const void *vsc_pattern_hits_scores_dev(const vsc_pattern_hits *hits);
 
 /* ---- on-target efficiency of candidate guides (linear position-specific models) ------------------------------ */
 /*

@@ -224,6 +224,24 @@ class ScoreTableStats(C.Structure):
     _fields_ = [("serial", C.c_uint64), ("zero_weights", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PatternTableShape(C.Structure):
+    """vsc_pattern_table_shape: the length, the protospacer [ps_start, ps_start + ps_len) and the read positions of the PAM
+    letters that a pattern table looks at."""
+    _fields_ = [("len", C.c_uint32), ("ps_start", C.c_uint32), ("ps_len", C.c_uint32), ("n_pam", C.c_uint32), ("pam_pos", C.c_uint32 * 4)]
+
+
+class PatternTableStats(C.Structure):
+    """vsc_pattern_table_stats"""
+    _fields_ = [("serial", C.c_uint64), ("zero_weights", C.c_uint32), ("reserved", C.c_uint32), ("shape", PatternTableShape)]
+
+
+class PatternSelect(C.Structure):
+    """vsc_pattern_select (vsc_search_pattern_table): per guide the hits with f >= min_score, of those the top_k (0: all) best"""
+    _fields_ = [("top_k", C.c_uint32), ("min_score", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(PatternTableShape) == 32 and C.sizeof(PatternTableStats) == 48 and C.sizeof(PatternSelect) == 16
+
 EFF_IDENTITY, EFF_LOGISTIC = 0, 1  # VSC_EFF_*
 
 
@@ -409,6 +427,14 @@ SYMBOLS = [
     ("vsc_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
     ("vsc_search_select_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), C.POINTER(Select), _vp, _vp, _vp,
                                           C.POINTER(_vp)]),
+    ("vsc_pattern_table_build", C.c_int, [C.POINTER(PatternTableShape), _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_pattern_table_free", C.c_int, [_vp]),
+    ("vsc_pattern_table_info", C.c_int, [_vp, C.POINTER(PatternTableStats)]),
+    ("vsc_pattern_table_score", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("vsc_search_pattern_table", C.c_int, [_vp, _vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(PatternParams), _vp,
+                                           C.POINTER(PatternSelect), C.POINTER(_vp), _vp, _vp]),
+    ("vsc_pattern_hits_scores", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_pattern_hits_scores_dev", _vp, [_vp]),
     ("vsc_multi_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
     ("vsc_eff_model_build", C.c_int, [C.POINTER(EffShape), C.c_double, _vp, _vp, _vp, C.POINTER(_vp)]),
     ("vsc_eff_model_free", C.c_int, [_vp]),

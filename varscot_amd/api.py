@@ -440,6 +440,136 @@ class ScoreTable:
             pass
 
 
+class PatternTable:
+    """A table score for the hits of a pattern search (vsc_pattern_table; the CFD form for any nuclease): length = the pattern's
+    L, protospacer = (start, length) in read positions, pair[ps_len][4][4] - the weight of guide base g against site base s
+    (the site's letter in READ orientation) at read position start + i, bases A 0, C 1, G 2, T 3 - pam_positions = up to four
+    read positions outside the protospacer, ascending, and pam[4 ** len(pam_positions)], the weight of the site's letters
+    there (first position most significant).  Every weight in [0, 1], pair[i][b][b] == 1.  The package ships no table."""
+
+    def __init__(self, length, protospacer, pair, pam_positions=(), pam=(1.0,)):
+        self.length = int(length)
+        self.protospacer = (int(protospacer[0]), int(protospacer[1]))
+        self.pam_positions = tuple(int(q) for q in pam_positions)
+        self.pair = np.ascontiguousarray(pair, dtype=np.float64)
+        self.pam = np.ascontiguousarray(pam, dtype=np.float64).reshape(-1)
+        if len(self.pam_positions) > 4:
+            raise ValueError("a pattern table looks at four PAM positions at the most")
+        if self.pair.shape != (self.protospacer[1], 4, 4) or self.pam.shape != (4 ** len(self.pam_positions),):
+            raise ValueError("a pattern table is pair[ps_len][4][4] and pam[4 ** n_pam]")
+        shape = _lib.PatternTableShape(self.length, self.protospacer[0], self.protospacer[1], len(self.pam_positions))
+        for t, q in enumerate(self.pam_positions):
+            shape.pam_pos[t] = q
+        h = C.c_void_p()
+        self._h = None
+        check(lib().vsc_pattern_table_build(C.byref(shape), ptr(self.pair), ptr(self.pam), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_score_table(cls, table):
+        """The SpCas9 shape with a ScoreTable's weights: 23 letters, protospacer (0, 20), PAM positions (21, 22) - every score
+        is that table's, bit for bit."""
+        return cls(23, (0, 20), table.pair, (21, 22), table.pam)
+
+    @classmethod
+    def from_tsv(cls, path):
+        """A table from the text file to_tsv writes (tools/README.md): tab- or blank-separated lines `shape L ps_start ps_len`,
+        `pam_pos p...` (none: no PAM letter is looked at), `pair j g s w` (j the 0-based READ position, g the guide's letter, s
+        the site's letter in read orientation), `pam LETTERS w` (one letter per PAM position, '-' when there is none); '#'
+        starts a comment.  `shape` comes first.  pair[j][b][b] is 1 and is not written; every other entry must be there."""
+        shape, pam_pos, pair, pam = None, (), None, None
+        with open(path) as fh:
+            for n, line in enumerate(fh, 1):
+                f = line.split("#", 1)[0].split()
+                if not f:
+                    continue
+                where = "%s:%d" % (path, n)
+                try:
+                    key, a = f[0], f[1:]
+                    if key != "shape" and shape is None:
+                        raise ValueError("'%s' before the 'shape' line" % key)
+                    if key == "shape" and len(a) == 3 and shape is None:
+                        shape = tuple(int(v) for v in a)
+                        if not 0 < shape[2] <= 32:
+                            raise ValueError("the protospacer has 1..32 positions")
+                        pair = np.full((shape[2], 4, 4), np.nan)
+                        for b in range(4):
+                            pair[:, b, b] = 1.0
+                        pam = np.full(1, np.nan)
+                    elif key == "pam_pos" and len(a) <= 4 and not pam_pos and np.isnan(pam).all():
+                        pam_pos = tuple(int(v) for v in a)
+                        pam = np.full(4 ** len(pam_pos), np.nan)
+                    elif key == "pair" and len(a) == 4:
+                        i = int(a[0]) - shape[1]
+                        if not 0 <= i < shape[2]:
+                            raise ValueError("position %s lies outside the protospacer" % a[0])
+                        pair[i, _base(a[1], where), _base(a[2], where)] = float(a[3])
+                    elif key == "pam" and len(a) == 2:
+                        letters = "" if a[0] == "-" else a[0]
+                        if len(letters) != len(pam_pos):
+                            raise ValueError("'pam' takes one letter per PAM position")
+                        k = 0
+                        for ch in letters:
+                            k = 4 * k + _base(ch, where)
+                        pam[k] = float(a[1])
+                    else:
+                        raise ValueError("unknown key, a line given twice or wrong number of fields: %r" % " ".join(f))
+                except ValueError as e:
+                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+        if shape is None:
+            raise ValueError("%s: no 'shape' line" % path)
+        missing = int(np.isnan(pair).sum() + np.isnan(pam).sum())
+        if missing:
+            raise ValueError("%s: %d entries are missing" % (path, missing))
+        return cls(shape[0], (shape[1], shape[2]), pair, pam_pos, pam)
+
+    def to_tsv(self, path):
+        """The table as a text file from_tsv reads back to the bit: the weights as repr() prints them."""
+        with open(path, "w") as fh:
+            fh.write("# pattern score table: %d letters, protospacer at %d + %d, read orientation\n"
+                     % (self.length, self.protospacer[0], self.protospacer[1]))
+            fh.write("shape\t%d\t%d\t%d\n" % (self.length, self.protospacer[0], self.protospacer[1]))
+            fh.write("pam_pos%s\n" % "".join("\t%d" % q for q in self.pam_positions))
+            for i in range(self.protospacer[1]):
+                for g in range(4):
+                    for b in range(4):
+                        if g != b:
+                            fh.write("pair\t%d\t%s\t%s\t%r\n" % (self.protospacer[0] + i, "ACGT"[g], "ACGT"[b], float(self.pair[i, g, b])))
+            n = len(self.pam_positions)
+            for k in range(4 ** n):
+                letters = "".join("ACGT"[(k >> (2 * (n - 1 - t))) & 3] for t in range(n)) or "-"
+                fh.write("pam\t%s\t%r\n" % (letters, float(self.pam[k])))
+
+    def info(self):
+        st = _lib.PatternTableStats()
+        check(lib().vsc_pattern_table_info(self._h, C.byref(st)))
+        return {"serial": int(st.serial), "zero_weights": int(st.zero_weights), "length": int(st.shape.len),
+                "protospacer": (int(st.shape.ps_start), int(st.shape.ps_len)),
+                "pam_positions": tuple(int(st.shape.pam_pos[t]) for t in range(st.shape.n_pam))}
+
+    def score(self, guide, site, fixed=False):
+        """vsc_pattern_table_score: the score of one guide (IUPAC letters) against one site (ACGT, read orientation), both of
+        the table's length; fixed=True: (score, rint(score * 2^30))."""
+        g = guide if isinstance(guide, bytes) else guide.encode()
+        t = site if isinstance(site, bytes) else site.encode()
+        if len(g) != self.length or len(t) != self.length:
+            raise ValueError("guide and site have the table's %d letters" % self.length)
+        x, f = C.c_double(), C.c_uint32()
+        check(lib().vsc_pattern_table_score(self._h, g, t, C.byref(x), C.byref(f)))
+        return (x.value, f.value) if fixed else x.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsc_pattern_table_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 EFF_UNDEFINED_BITS = 0x7FF8000000000000  # the one NaN an undefined efficiency predictor is
 
 
@@ -1050,6 +1180,42 @@ class Genome:
             L.vsc_pattern_hits_free(h)
         return recs, out_rows
 
+    def search_pattern_table(self, pattern, guides, max_mismatches, table, top_k=0, min_score=0, max_hits=0, guide_batch=0,
+                             records=True, rows=True):
+        """vsc_search_pattern_table: search_pattern with every hit scored by a PatternTable of the pattern's length.  Per guide
+        the hits with f >= min_score (f = rint(score * 2^30), TABLE_ONE = 1.0) survive, and of those the top_k (0: all) under f
+        descending, then record order; the result stays in record order.  Returns (PATTERN_HIT_DTYPE records | None, uint32 f
+        per record | None, uint32 rows of shape (n, 9) - hits by NM | None, TABLE_ROW_DTYPE rows | None); both kinds of rows are
+        over ALL hits, before the selection.  max_hits caps the returned records; guide_batch never changes the result."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+        for i, g in enumerate(gs):
+            if len(g) != len(p):
+                raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+        pp = _lib.PatternParams(int(max_mismatches), int(guide_batch), int(max_hits))
+        sel = _lib.PatternSelect(int(top_k), int(min_score))
+        L = lib()
+        h = C.c_void_p()
+        out_rows = np.zeros((len(gs), 9), dtype=np.uint32) if rows else None
+        out_table = np.zeros(len(gs), dtype=TABLE_ROW_DTYPE) if rows else None
+        check(L.vsc_search_pattern_table(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp), table._h, C.byref(sel),
+                                         C.byref(h) if records else None, ptr(out_rows), ptr(out_table)), self.ctx._h)
+        if not records:
+            return None, None, out_rows, out_table
+        try:
+            n = int(L.vsc_pattern_hits_count(h))
+            data, side = C.c_void_p(), C.c_void_p()
+            check(L.vsc_pattern_hits_data(h, C.byref(data)), self.ctx._h)
+            check(L.vsc_pattern_hits_scores(h, C.byref(side)), self.ctx._h)
+            if n == 0:
+                recs, fixed = np.zeros(0, dtype=PATTERN_HIT_DTYPE), np.zeros(0, dtype=np.uint32)
+            else:
+                recs = np.frombuffer((C.c_char * (n * 20)).from_address(data.value), dtype=PATTERN_HIT_DTYPE).copy()
+                fixed = np.frombuffer((C.c_char * (n * 4)).from_address(side.value), dtype=np.uint32).copy()
+        finally:
+            L.vsc_pattern_hits_free(h)
+        return recs, fixed, out_rows, out_table
+
     def search_pattern_bulges(self, pattern, guides, max_mismatches, protospacer, dna=1, rna=1, max_hits=0, guide_batch=0,
                               records=True, rows=True):
         """vsc_search_pattern_bulges: search_bulges for any nuclease - the sites of len(pattern) + d bases, d in -rna .. -1 and
@@ -1129,16 +1295,30 @@ class Genome:
         found = PatternGuides(p.decode(), protospacer, codes, loci)
         return found if efficiency is None else (found, linear)
 
-    def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, **filters):
+    def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, table=None, **filters):
         """Every guide of `targets` under a pattern, with its off-target counts: enumerate_pattern(pattern, protospacer,
         targets, **filters) followed by search_pattern (rows only) of the guides in query form on the same resident genome.
         Returns (PatternGuides, uint32 rows of shape (n, 9)); count[0] is reduced by one for the guide's own locus, which is
         always a hit at NM 0 (the query form has N outside the protospacer).  With efficiency= (and min_efficiency=) among
-        the filters, as enumerate_pattern takes them: only the survivors are searched, and their predictors come last."""
+        the filters, as enumerate_pattern takes them: only the survivors are searched, and their predictors come last.
+        table= a PatternTable: search_pattern_table instead, and the TABLE_ROW_DTYPE rows follow the NM rows - each with the
+        guide's own locus taken out as well, by the host's score of the guide (query form) against its own site (the
+        candidate's letters, PAM included), as count[0] is reduced."""
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
         extra = ()
         if filters.get("efficiency") is not None:
             found, extra = found[0], (found[1],)
+        if table is not None:
+            queries = found.text()
+            _, _, rows, trows = self.search_pattern_table(pattern, queries, max_mismatches, table, guide_batch=guide_batch, records=False)
+            rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
+            for i, (q, own) in enumerate(zip(queries, found.text(spell_pam=True))):
+                f = table.score(q, own, fixed=True)[1]
+                trows["score_sum"][i] -= f
+                if f:
+                    trows["positive"][i] -= 1
+                    trows["positive_nm"][i, 0] -= 1
+            return (found, rows, trows) + extra
         _, rows = self.search_pattern(pattern, found.text(), max_mismatches, guide_batch=guide_batch, records=False)
         rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
         return (found, rows) + extra

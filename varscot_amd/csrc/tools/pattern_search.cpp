@@ -16,8 +16,18 @@
 // must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
 // its sequence or holds an N) and efficiency (the predictor through the model's link).  -y MIN (needs -Y) keeps only the
 // candidates whose predictor is defined and >= MIN, linear domain, BEFORE the search.  Without -Y every output is what it was.
+// -W table.tsv scores every hit with a pattern TABLE (vsc_search_pattern_table; the CFD form for any nuclease: a product of
+// weights by protospacer position, guide base and site base times a weight for the site's letters at up to four PAM positions;
+// the file is what varscot_amd.PatternTable.to_tsv writes, tools/README.md: `shape L ps_start ps_len`, `pam_pos p...`,
+// `pair j g s w`, `pam LETTERS w`; its L must be the pattern's length).  The -O summary gains, behind all other columns,
+//   tableScoreSum tableSpecScore tablePositive
+// = the sum of the hits' scores (fixed point, 2^-30 units, %.6f), floor(100 / (100 + sum) * 100 + 0.5) and the hits that score
+// above 0; with -E a found guide's own locus is taken out of them as it is out of mm0.  With -T the listing is selected by the
+// table score: -K the best K of every guide, -S a floor on the score, 0 .. 1, and a last column tableScore (%.9f); the summary
+// stays over all hits.  -K and -S need -W and -T.  Without -W every output is what it was.
 // Host C++ only: the search runs in libvarscot_hip.so (vsc_search_pattern); there is no CPU search here.  Every argument is
 // checked before a device is opened.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
@@ -76,6 +86,81 @@ std::vector<vsc_interval> read_targets(const std::string &path, const PackedInde
     return iv;
 }
 
+// the -W file: what varscot_amd.PatternTable.to_tsv writes
+vsc_pattern_table *load_pattern_table(const std::string &path, vsc_pattern_table_shape *shape)
+{
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("Could not open the -W file.");
+    vsc_pattern_table_shape s{};
+    bool have_shape = false, have_pam_pos = false;
+    std::vector<double> pair, pam(1, NAN);
+    std::string line;
+    size_t n = 0;
+    auto base = [](char c) { return c == 'A' || c == 'a' ? 0 : c == 'C' || c == 'c' ? 1 : c == 'G' || c == 'g' ? 2 : c == 'T' || c == 't' || c == 'U' || c == 'u' ? 3 : -1; };
+    while (std::getline(in, line)) {
+        ++n;
+        const auto bad = [&](const std::string &what) { return std::runtime_error("-W: " + path + ":" + std::to_string(n) + ": " + what); };
+        std::istringstream is(line.substr(0, line.find('#')));
+        std::vector<std::string> f;
+        for (std::string w; is >> w;) f.push_back(w);
+        if (f.empty()) continue;
+        const auto integer = [&](const std::string &v) {
+            char *e = nullptr;
+            const long x = std::strtol(v.c_str(), &e, 10);
+            if (e == v.c_str() || *e || x < 0 || x > 64) throw bad("'" + v + "' is no position");
+            return (uint32_t)x;
+        };
+        const auto number = [&](const std::string &v) {
+            char *e = nullptr;
+            const double x = std::strtod(v.c_str(), &e);
+            if (e == v.c_str() || *e || !std::isfinite(x)) throw bad("'" + v + "' is no finite number");
+            return x;
+        };
+        if (f[0] != "shape" && !have_shape) throw bad("'" + f[0] + "' before the 'shape' line");
+        if (f[0] == "shape" && f.size() == 4 && !have_shape) {
+            s.len = integer(f[1]), s.ps_start = integer(f[2]), s.ps_len = integer(f[3]);
+            if (s.ps_len < 1 || s.ps_len > 32) throw bad("the protospacer has 1..32 positions");
+            pair.assign((size_t)s.ps_len * 16, NAN);
+            for (uint32_t i = 0; i < s.ps_len; ++i)
+                for (uint32_t b = 0; b < 4; ++b) pair[(i * 4 + b) * 4 + b] = 1.0;
+            have_shape = true;
+        } else if (f[0] == "pam_pos" && f.size() <= 5 && !have_pam_pos) {
+            s.n_pam = (uint32_t)f.size() - 1;
+            for (uint32_t t = 0; t < s.n_pam; ++t) s.pam_pos[t] = integer(f[1 + t]);
+            pam.assign((size_t)1 << (2 * s.n_pam), NAN);
+            have_pam_pos = true;
+        } else if (f[0] == "pair" && f.size() == 5 && f[2].size() == 1 && f[3].size() == 1) {
+            const uint32_t j = integer(f[1]);
+            const int g = base(f[2][0]), b = base(f[3][0]);
+            if (j < s.ps_start || j >= s.ps_start + s.ps_len) throw bad("position " + f[1] + " lies outside the protospacer");
+            if (g < 0 || b < 0) throw bad("'" + f[2] + "' or '" + f[3] + "' is no base");
+            pair[((size_t)(j - s.ps_start) * 4 + (size_t)g) * 4 + (size_t)b] = number(f[4]);
+        } else if (f[0] == "pam" && f.size() == 3) {
+            const std::string letters = f[1] == "-" ? "" : f[1];
+            if (letters.size() != s.n_pam) throw bad("'pam' takes one letter per PAM position");
+            size_t k = 0;
+            for (char c : letters) {
+                if (base(c) < 0) throw bad("'" + f[1] + "' holds a letter that is no base");
+                k = 4 * k + (size_t)base(c);
+            }
+            have_pam_pos = true;  // (a 'pam_pos' line behind a weight would resize the weights)
+            pam[k] = number(f[2]);
+        } else {
+            throw bad("unknown key, a line given twice or wrong number of fields");
+        }
+    }
+    if (!have_shape) throw std::runtime_error("-W: " + path + ": no 'shape' line");
+    size_t missing = 0;
+    for (double w : pair) missing += std::isnan(w);
+    for (double w : pam) missing += std::isnan(w);
+    if (missing) throw std::runtime_error("-W: " + path + ": " + std::to_string(missing) + " entries are missing");
+    vsc_pattern_table *t = nullptr;
+    if (vsc_pattern_table_build(&s, pair.data(), pam.data(), &t) != VSC_OK)
+        throw std::runtime_error("-W: " + path + ": not a table (a bad shape, a weight outside 0 .. 1 or a diagonal entry that is not 1)");
+    *shape = s;
+    return t;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -103,6 +188,10 @@ int main(int argc, char **argv)
         {'Y', "efficiency-model", "With -E: path to an on-target efficiency model (.tsv/.txt) whose site_len is the pattern's length: "
                                   "the -E listing gains the columns efficiencyLinear efficiency", false},
         {'y', "min-efficiency", "With -Y: keep only the candidates whose efficiency predictor is defined and >= this value, linear domain", false},
+        {'W', "score-table", "Path to a pattern score table (.tsv/.txt; what PatternTable.to_tsv writes) of the pattern's length: -O gains the "
+                             "columns tableScoreSum tableSpecScore tablePositive, -T the column tableScore", false},
+        {'K', "top", "With -W: list the K best hits of every guide by table score in the -T file (default: no limit)", false},
+        {'S', "min-score", "With -W: list only hits with a table score >= this value, 0 .. 1, in the -T file (default: no floor)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -255,6 +344,41 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // -W / -K / -S: the table score of the hits
+    const bool tabled = opts[18].set;
+    vsc_pattern_select sel{};
+    if ((opts[19].set || opts[20].set) && (!tabled || !opts[6].set)) {
+        std::fprintf(stderr, "%s: -K and -S select the -T listing by the score of the -W table: give -W and -T\n", argv[0]);
+        return 1;
+    }
+    if (tabled && !has_extension(opts[18].value, {"tsv", "txt"})) {
+        std::fprintf(stderr, "%s: the -W table must be a .tsv/.txt file\n", argv[0]);
+        return 1;
+    }
+    if (tabled && !opts[3].set) {
+        std::fprintf(stderr, "%s: -W scores the hits of a search: give -M (with -E: -M and -O)\n", argv[0]);
+        return 1;
+    }
+    if (opts[19].set) {
+        char *kend = nullptr;
+        const std::string &v = opts[19].value;
+        const long long k = std::strtoll(v.c_str(), &kend, 10);
+        if (v.empty() || *kend || k < 1 || k > 0xFFFFFFFFll) {
+            std::fprintf(stderr, "%s: -K takes a count of 1 or more, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        sel.top_k = (uint32_t)k;
+    }
+    if (opts[20].set) {
+        char *send = nullptr;
+        const std::string &v = opts[20].value;
+        const double x = std::strtod(v.c_str(), &send);
+        if (v.empty() || *send || !(x >= 0.0 && x <= 1.0)) {
+            std::fprintf(stderr, "%s: -S takes a table score of 0 .. 1, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        sel.min_score = (uint32_t)std::ceil(x * 0x1p30);  // the smallest fixed-point score that is >= x
+    }
     char *end = nullptr;
     long mm = 0;
     if (opts[3].set) {
@@ -283,6 +407,7 @@ int main(int argc, char **argv)
     vsc_pattern_guides *found = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
     vsc_eff_model *eff_model = nullptr;
+    vsc_pattern_table *table = nullptr;
     int rc = 1;
     try {
         std::vector<FastaRecord> guides;
@@ -292,6 +417,12 @@ int main(int argc, char **argv)
             eff_model = load_eff_model(opts[16].value, &eff_shape);
             if (eff_shape.site_len != len)
                 throw std::runtime_error("-Y: the model's site_len is " + std::to_string(eff_shape.site_len) + "; the pattern has " + std::to_string(len) + " letters");
+        }
+        if (tabled) {  // (read before the index and the device, as the model is)
+            vsc_pattern_table_shape table_shape{};
+            table = load_pattern_table(opts[18].value, &table_shape);
+            if (table_shape.len != len)
+                throw std::runtime_error("-W: the table is built for " + std::to_string(table_shape.len) + " letters; the pattern has " + std::to_string(len));
         }
         std::string letters;
         if (!enumerate) {
@@ -316,6 +447,7 @@ int main(int argc, char **argv)
         std::printf("Index loaded.\n");
 
         const vsc_locus *loci = nullptr;
+        std::vector<uint32_t> own_fixed;  // -E with -W: the table score of every found guide against its own site
         if (enumerate) {
             // an empty -B file is a target set that holds nothing: a pointer that is not NULL with n = 0
             const vsc_interval none{};
@@ -347,6 +479,14 @@ int main(int argc, char **argv)
                 if (vsc_pattern_guide_text(codes[i], len, ep.ps_start, ep.ps_len, 0, &letters[i * len]) != VSC_OK)
                     throw std::runtime_error("a code of the enumeration is no guide");
                 guides[i].seq = letters.substr(i * len, len);
+                if (tabled) {
+                    char own[VSC_PATTERN_MAX_LEN];
+                    uint32_t f = 0;
+                    if (vsc_pattern_guide_text(codes[i], len, ep.ps_start, ep.ps_len, 1, own) != VSC_OK ||
+                        vsc_pattern_table_score(table, guides[i].seq.c_str(), own, nullptr, &f) != VSC_OK)
+                        throw std::runtime_error("a code of the enumeration is no site");
+                    own_fixed.push_back(f);
+                }
                 guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
                 out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+');
                 if (efficient) out << '\t' << eff_text(eff_linear[i]) << '\t' << eff_text(vsc_eff_link(eff_model, eff_linear[i]));
@@ -356,16 +496,26 @@ int main(int argc, char **argv)
         }
 
         std::vector<vsc_pattern_summary> rows(guides.size());
+        std::vector<vsc_guide_table_row> table_rows(tabled ? guides.size() : 0);
         if (!enumerate || opts[3].set) {
             if (guides.size() > 0xFFFFFFFFull) throw std::runtime_error("more guides than one search takes");
             vsc_pattern_params p{};
             p.max_mismatches = (uint32_t)mm;
-            st = vsc_search_pattern(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, opts[6].set ? &hits : nullptr,
-                                    rows.data());
+            if (tabled)
+                st = vsc_search_pattern_table(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, table, &sel,
+                                              opts[6].set ? &hits : nullptr, rows.data(), table_rows.data());
+            else
+                st = vsc_search_pattern(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, opts[6].set ? &hits : nullptr,
+                                        rows.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             // a found guide's own locus is a hit at 0 mismatches (N at the positions outside the protospacer): not an off-target
             if (enumerate)
                 for (auto &r : rows) r.count[0] -= r.count[0] ? 1u : 0u;
+            if (enumerate && tabled)
+                for (size_t g = 0; g < table_rows.size(); ++g) {
+                    table_rows[g].score_sum -= own_fixed[g];
+                    if (own_fixed[g]) table_rows[g].positive -= 1, table_rows[g].positive_nm[0] -= 1;
+                }
         }
         // the bulged sites of the same guides (the bulged neighbours of a found guide's own locus are among them)
         std::vector<vsc_bulge_summary> bulge_rows(bulged ? guides.size() : 0);
@@ -388,6 +538,7 @@ int main(int argc, char **argv)
                 for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
                     for (long k = 0; bulge_on[c] && k <= mm; ++k) out << '\t' << kBulgeClass[c] << "mm" << k;
             }
+            if (tabled) out << "\ttableScoreSum\ttableSpecScore\ttablePositive";
             out << '\n';
             for (size_t g = 0; g < guides.size(); ++g) {
                 uint64_t total = 0;
@@ -402,6 +553,13 @@ int main(int argc, char **argv)
                     for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
                         for (long k = 0; bulge_on[c] && k <= mm; ++k) out << '\t' << bulge_rows[g].count[c][k];
                 }
+                if (tabled) {
+                    char buf[64];
+                    std::snprintf(buf, sizeof buf, "\t%.6f", (double)table_rows[g].score_sum * 0x1p-30);
+                    out << buf;
+                    std::snprintf(buf, sizeof buf, "\t%.0f", std::floor(vsc_table_specificity(table_rows[g].score_sum) + 0.5));
+                    out << buf << '\t' << table_rows[g].positive;
+                }
                 out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[5].value);
@@ -411,9 +569,11 @@ int main(int argc, char **argv)
             const vsc_pattern_hit *h = nullptr;
             st = vsc_pattern_hits_data(hits, &h);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const uint32_t *fixed = nullptr;
+            if (tabled && vsc_pattern_hits_scores(hits, &fixed) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             std::ofstream out(opts[6].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
-            out << "#guideId\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tsequence\n";
+            out << "#guideId\tchrom\tstart\tend\tstrand\tmismatches\tmismatchPositions\tsequence" << (tabled ? "\ttableScore\n" : "\n");
             std::string window(len, 'N'), text;
             for (uint64_t i = 0; i < n; ++i) {
                 const vsc_pattern_hit &r = h[i];
@@ -423,7 +583,13 @@ int main(int argc, char **argv)
                     if ((r.mask >> b) & 1u) where += (where.empty() ? "" : ",") + std::to_string(b);
                 text += first_word(guides[r.guide].id) + '\t' + first_word(ix.names[r.contig]) + '\t' + std::to_string(r.pos) + '\t' + std::to_string(r.pos + len) + '\t' +
                         (VSC_PATTERN_STRAND(r.info) ? '-' : '+') + '\t' + std::to_string(VSC_PATTERN_NM(r.info)) + '\t' + (where.empty() ? "-" : where) +
-                        '\t' + window + '\n';
+                        '\t' + window;
+                if (tabled) {
+                    char buf[32];
+                    std::snprintf(buf, sizeof buf, "\t%.9f", (double)fixed[i] * 0x1p-30);
+                    text += buf;
+                }
+                text += '\n';
                 if (text.size() > (1u << 22)) {
                     out << text;
                     text.clear();
@@ -466,6 +632,7 @@ int main(int argc, char **argv)
     vsc_pattern_hits_free(hits);
     vsc_pattern_guides_free(found);
     vsc_eff_model_free(eff_model);
+    vsc_pattern_table_free(table);
     vsc_bulge_hits_free(bulge_hits);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);

@@ -239,10 +239,11 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
                          &ctx->eff_out})
         b->release();
     ctx->table_serial = 0;
+    ctx->pattern_table_serial = 0;
     ctx->eff_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
@@ -2044,6 +2045,19 @@ int resident_table(vsc_ctx *ctx, const vsc_score_table *table)
     return VSC_OK;
 }
 
+// ... and of a pattern table (vsc_search_pattern_table), the same way
+int resident_pattern_table(vsc_ctx *ctx, const vsc_pattern_table *table)
+{
+    if (ctx->pattern_table_serial == table->serial && ctx->pattern_table_buf.p) return VSC_OK;
+    ctx->pattern_table_serial = 0;
+    const size_t bytes = pattern_table_weights(table->shape) * sizeof(double);
+    VSC_HIP(ctx, ctx->pattern_table_buf.ensure(bytes));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->pattern_table_buf.p, table->w, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the table as soon as its call returns)
+    ctx->pattern_table_serial = table->serial;
+    return VSC_OK;
+}
+
 // Table score stage (vsc_search_*_table), between find_pass and the sinks, where classify_pass sits for the classifier:
 // table_score_kernel scores the records where the search kernel left them (the table made resident by resident_table, the
 // interleaved planes by ensure_hl - both before the first pass) and leaves every record slot's fixed-point score in
@@ -2837,6 +2851,13 @@ int run_enumeration(vsc_ctx *ctx, const char *fn, Args &a, const std::vector<uin
 // are copied into one array.
 static_assert(kPatChunk == kBulgeChunk, "the sums of every round are taken per kBulgeChunk cells");
 
+// What vsc_search_pattern_table adds to the rounds: per record one 32-bit side word behind the records, a second
+// set of rows (64-bit words), and - with a selection - a stage behind every round's write pass, which then writes to scratch.
+struct RoundsScore {
+    unsigned long long *rows;   // host: kPatTableRowWords words per guide (null: not asked for)
+    uint32_t top_k, min_score;  // both 0: no selection stage
+};
+
 // What a search tells run_rounds about itself.
 struct RoundsPlan {
     const char *fn;  // for messages
@@ -2846,6 +2867,7 @@ struct RoundsPlan {
     uint32_t levels;      // 1: offsets per chunk of 64 cells; 2: per group of 64 chunks
     uint32_t row_words;   // 32-bit words of a guide's row
     uint64_t max_hits;    // 0: no cap
+    const RoundsScore *score = nullptr;  // the scored pattern search alone
 };
 
 // What the launches of a round are bound to.
@@ -2859,6 +2881,8 @@ struct Round {
     uint32_t *rows;                 // null: no rows are asked for
     void *records;                  // write pass: the round's piece (null: it has no records)
     unsigned long long n_records;
+    uint32_t *side;                 // a scored search: the side words of the round's records (null as `records` is)
+    unsigned long long *rows64;     // ... and its second rows (null: not asked for)
 };
 
 // table_uint4s(n): the uint4s of the table of a round of n guides; stage(g0, n, table): fills that table, zeroed, for guides
@@ -2873,12 +2897,17 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
         if (!holder) return fail_in(ctx, VSC_ERR_NOMEM, p.fn, "out of host memory");
         holder->ctx = ctx;
         holder->host_valid = true;  // (empty until records are written)
+        holder->has_side = holder->side_host_valid = p.score != nullptr;
     }
     vsc_timing t{};
     t.index_ms = ctx->timing.index_ms;
     t.algorithm = VSC_ALGO_SCAN;
     const size_t rows_words = (size_t)p.n_guides * p.row_words;
     if (rows) std::memset(rows, 0, rows_words * sizeof(uint32_t));
+    unsigned long long *const rows64 = p.score ? p.score->rows : nullptr;
+    const size_t rows64_words = rows64 ? (size_t)p.n_guides * kPatTableRowWords : 0;
+    if (rows64) std::memset(rows64, 0, rows64_words * sizeof(unsigned long long));
+    const bool selecting = p.score && out && (p.score->top_k || p.score->min_score);
     const uint32_t n_guides = p.n_guides, n_tiles = p.n_tiles, batch = p.batch;
     if (n_guides == 0 || n_tiles == 0) {
         t.pairs = 0;
@@ -2895,21 +2924,25 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
     const bool grouped = p.levels == 2;
     const uint64_t max_groups = (max_chunks + kBulgeChunk - 1) / kBulgeChunk;  // the one-workgroup scan takes these, not the chunks
     const size_t rows_bytes = round256(rows_words * sizeof(uint32_t));
+    const size_t rows64_bytes = round256(rows64_words * sizeof(unsigned long long)), sel_bytes = selecting ? round256(batch * sizeof(uint4)) : 0;
     const size_t table_bytes = round256((size_t)table_uint4s(batch) * sizeof(uint4));
     const size_t count_bytes = round256((size_t)max_cells * sizeof(uint32_t)), sums_bytes = round256((size_t)max_chunks * sizeof(uint32_t));
     const size_t groups_bytes = grouped ? round256((size_t)max_groups * sizeof(uint32_t)) : 0;
-    VSC_HIP(ctx, p.pool->ensure(rows_bytes + 256 + table_bytes + count_bytes + sums_bytes + groups_bytes +
+    VSC_HIP(ctx, p.pool->ensure(rows_bytes + 256 + rows64_bytes + sel_bytes + table_bytes + count_bytes + sums_bytes + groups_bytes +
                                 (size_t)((grouped ? max_groups : max_chunks) + 1) * sizeof(unsigned long long)));
     char *base = (char *)p.pool->p;
     uint32_t *d_rows = (uint32_t *)base;
     unsigned long long *d_sites = (unsigned long long *)(base + rows_bytes);
-    uint4 *d_table = (uint4 *)(base + rows_bytes + 256);
+    unsigned long long *d_rows64 = (unsigned long long *)(base + rows_bytes + 256);  // (a scored search: zeroed with the rows)
+    uint4 *d_sel = (uint4 *)((char *)d_rows64 + rows64_bytes);
+    uint4 *d_table = (uint4 *)((char *)d_sel + sel_bytes);
     uint32_t *d_count = (uint32_t *)((char *)d_table + table_bytes);
     uint32_t *d_sums = (uint32_t *)((char *)d_count + count_bytes);
     uint32_t *d_groups = (uint32_t *)((char *)d_sums + sums_bytes);
     unsigned long long *d_off = (unsigned long long *)((char *)d_groups + groups_bytes);
-    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256, ctx->stream));
+    VSC_HIP(ctx, hipMemsetAsync(base, 0, rows_bytes + 256 + rows64_bytes, ctx->stream));
     Round r{};
+    r.rows64 = rows64 ? d_rows64 : nullptr;
     r.guides = d_table;
     r.count = d_count;
     r.chunk_sum = d_sums;
@@ -2917,13 +2950,21 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
     r.rows = rows ? d_rows : nullptr;
 
     std::vector<DeviceBuf> pieces;  // the rounds' records (released on every way out)
+    DeviceBuf raw;                  // with a selection: a round's records and side words before it
     struct Release {
         std::vector<DeviceBuf> &v;
+        DeviceBuf &raw;
         ~Release()
         {
             for (auto &b : v) b.release();
+            raw.release();
         }
-    } release{pieces};
+    } release{pieces, raw};
+    // a piece of n records: the records, then - a scored search - their side words from side_at(n) on
+    const size_t side_bytes = p.score ? sizeof(uint32_t) : 0;
+    auto side_at = [&](uint64_t n) { return round256((size_t)n * rec_bytes); };
+    auto piece_bytes = [&](uint64_t n) { return side_bytes ? side_at(n) + (size_t)n * side_bytes : (size_t)n * rec_bytes; };
+    std::vector<uint4> sel_host;
     std::vector<uint64_t> piece_n;
     std::vector<uint4> staged;
     unsigned long long total = 0, found = 0;
@@ -2960,7 +3001,7 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
     for (uint32_t g0 = 0; g0 < n_guides; g0 += batch) {
         int rc = count_round(g0);
         if (rc != VSC_OK) return rc;
-        if (p.max_hits && total > p.max_hits) {
+        if (!selecting && p.max_hits && total > p.max_hits) {
             // the count the message names is the whole call's: the remaining rounds are counted, nothing more is written
             for (uint32_t h0 = g0 + batch; h0 < n_guides; h0 += batch)
                 if ((rc = count_round(h0)) != VSC_OK) return rc;
@@ -2972,12 +3013,15 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
         pieces.emplace_back();
         piece_n.push_back(found);
         r.records = nullptr;
+        r.side = nullptr;
         r.n_records = found;
         if (found) {
-            VSC_HIP(ctx, pieces.back().ensure((size_t)found * rec_bytes));
-            r.records = pieces.back().p;
+            DeviceBuf &into = selecting ? raw : pieces.back();
+            VSC_HIP(ctx, into.ensure(piece_bytes(found)));
+            r.records = into.p;
+            if (side_bytes) r.side = (uint32_t *)((char *)into.p + side_at(found));
         }
-        if (found || rows) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
+        if (found || rows || rows64) {  // (rows without records: the write pass adds the rows of the cells that are not empty and writes nothing)
             VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
             VSC_HIP(ctx, launch(r, true));
             VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
@@ -2986,26 +3030,75 @@ int run_rounds(vsc_ctx *ctx, const RoundsPlan &p, Hits **out, uint32_t *rows, Sl
             t.scan_ms += ms;
             t.genome_bytes += (uint64_t)n_tiles * kTileWords * 3 * sizeof(uint32_t);
         }
+        if (selecting && found) {
+            // the selection stage: every guide's threshold, one read-back of the survivors per guide (they size the round's
+            // piece), then the walk that keeps them in record order
+            PatSelectArgs sa{};
+            sa.count = r.count;
+            sa.chunk_sum = r.chunk_sum;
+            sa.group_off = r.off;
+            sa.n_tiles = n_tiles;
+            sa.n_guides = r.n;
+            sa.n_records = found;
+            sa.records = (const uint32_t *)r.records;
+            sa.fixed = r.side;
+            sa.top_k = p.score->top_k;
+            sa.min_score = p.score->min_score;
+            sa.sel = d_sel;
+            sel_host.resize(r.n);
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+            VSC_HIP(ctx, launch_pattern_select(sa, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(sel_host.data(), d_sel, r.n * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            unsigned long long kept = 0;
+            for (const uint4 &q : sel_host) kept += (unsigned long long)q.w << 32 | q.z;
+            if (kept) {
+                VSC_HIP(ctx, pieces.back().ensure(piece_bytes(kept)));
+                sa.out_records = (uint32_t *)pieces.back().p;
+                sa.out_fixed = (uint32_t *)((char *)pieces.back().p + side_at(kept));
+                sa.n_out = kept;
+                VSC_HIP(ctx, launch_pattern_select_walk(sa, ctx->stream));
+            }
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+            t.score_ms += ms;
+            piece_n.back() = kept;
+            total = total - found + kept;
+        }
+    }
+    if (selecting && p.max_hits && total > p.max_hits) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "%s: %llu records exceed max_hits = %llu", p.fn, total, (unsigned long long)p.max_hits);
+        return fail(ctx, VSC_ERR_RANGE, msg);
     }
     unsigned long long sites = 0;
     VSC_HIP(ctx, hipMemcpyAsync(&sites, d_sites, sizeof sites, hipMemcpyDeviceToHost, ctx->stream));
     if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, rows_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (rows64) VSC_HIP(ctx, hipMemcpyAsync(rows64, d_rows64, rows64_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     if (out && total) {
         if (pieces.size() == 1) {
             holder->storage = pieces[0];
             pieces[0] = DeviceBuf();
         } else {
-            VSC_HIP(ctx, holder->storage.ensure((size_t)total * rec_bytes));
-            size_t at = 0;
+            VSC_HIP(ctx, holder->storage.ensure(piece_bytes(total)));
+            size_t at = 0, at_side = side_at(total);
             for (size_t i = 0; i < pieces.size(); ++i) {
-                if (piece_n[i])
+                if (piece_n[i]) {
                     VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at, pieces[i].p, (size_t)piece_n[i] * rec_bytes, hipMemcpyDeviceToDevice,
                                                 ctx->stream));
+                    if (side_bytes)
+                        VSC_HIP(ctx, hipMemcpyAsync((char *)holder->storage.p + at_side, (char *)pieces[i].p + side_at(piece_n[i]),
+                                                    (size_t)piece_n[i] * side_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+                }
                 at += (size_t)piece_n[i] * rec_bytes;
+                at_side += (size_t)piece_n[i] * side_bytes;
             }
         }
         holder->n = total;
         holder->host_valid = false;
+        holder->side_at = side_at(total);
+        holder->side_host_valid = false;
     }
     VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (rows && !out)
@@ -3290,28 +3383,32 @@ int vsc_bulge_align(uint64_t guide_code, const char *site_text, int d, uint32_t 
 }
 
 // ---- pattern search (kernels: vsc_pattern.hip; the rounds: run_rounds, two levels of sums) -------------------
-int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
-                       const vsc_pattern_params *params, vsc_pattern_hits **out, vsc_pattern_summary *rows)
+// table != null: vsc_search_pattern_table - the scored write pass, the table rows and the selection stage
+static int search_pattern_call(vsc_ctx *ctx, const char *fn, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides,
+                               uint32_t len, const vsc_pattern_params *params, const vsc_pattern_table *table, const vsc_pattern_select *select,
+                               vsc_pattern_hits **out, vsc_pattern_summary *rows, vsc_guide_table_row *table_rows)
 {
     return guarded(ctx, [&]() -> int {
     if (!ctx) return VSC_ERR_INVALID;
     if (out) *out = nullptr;
     ctx->err.clear();
-    const char *const fn = "vsc_search_pattern";
-    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, fn, "neither records nor rows are asked for");
+    if (!out && !rows && !table_rows) return fail_in(ctx, VSC_ERR_INVALID, fn, table ? "neither records nor rows of either kind are asked for" : "neither records nor rows are asked for");
     if (!genome || !params || !pattern || (n_guides && !guides)) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
     if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
     if (len < kPatMinLen || len > kPatMaxLen) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern must have 16..32 letters");
     if (params->max_mismatches > VSC_MAX_MISMATCHES) return fail_in(ctx, VSC_ERR_INVALID, fn, "max_mismatches must be 0..8");
     if (params->reserved[0] || params->reserved[1]) return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields must be 0");
+    if (table && table->shape.len != len) return fail_in(ctx, VSC_ERR_INVALID, fn, "the table is built for another length");
+    if (select && (select->reserved[0] || select->reserved[1])) return fail_in(ctx, VSC_ERR_INVALID, fn, "reserved fields of the selection must be 0");
     uint8_t sets[kPatMaxLen], rc_sets[kPatMaxLen];
     if (!pattern_sets(pattern, len, sets)) return fail_in(ctx, VSC_ERR_INVALID, fn, "the pattern holds a letter that is no IUPAC letter");
     PatternArgs a{};
     pattern_front(sets, len, &a.front[0]);
     pattern_revcomp(sets, len, rc_sets);
     pattern_front(rc_sets, len, &a.front[1]);
-    // every guide as two uint4: its planes for '+', those of its reverse complement for '-'
-    std::vector<uint4> planes((size_t)2 * n_guides);
+    // every guide as two uint4: its planes for '+', those of its reverse complement for '-' (scored: a third, its
+    // read-orientation planes as the score reads them)
+    std::vector<uint4> planes((size_t)2 * n_guides), reads(table ? n_guides : 0);
     for (uint32_t g = 0; g < n_guides; ++g) {
         if (!pattern_sets(guides + (size_t)g * len, len, sets)) {
             char msg[120];
@@ -3322,6 +3419,11 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
         const PatPlanes f = pattern_planes(sets, len), r = pattern_planes(rc_sets, len);
         planes[2 * (size_t)g] = make_uint4(f.a, f.c, f.g, f.t);
         planes[2 * (size_t)g + 1] = make_uint4(r.a, r.c, r.g, r.t);
+        if (table) {
+            uint32_t gh, gl, single;
+            pattern_table_guide(sets, len, &gh, &gl, &single);
+            reads[g] = make_uint4(gh, gl, single, 0);
+        }
     }
     bind_genome(a, genome);
     a.n_tiles = genome->d_hi ? genome->n_tiles : 0;
@@ -3329,17 +3431,38 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
     a.max_mm = params->max_mismatches;
 
     static_assert(sizeof(vsc_pattern_summary) == kPatRowWords * sizeof(uint32_t), "a row is its counts");
+    static_assert(sizeof(vsc_guide_table_row) == kPatTableRowWords * sizeof(unsigned long long), "a table row is its twelve words");
+    static_assert(sizeof(vsc_pattern_table_shape) == sizeof(PatTableShape), "the shape is the kernels'");
     const uint32_t batch = std::min(params->guide_batch ? std::min(params->guide_batch, kPatMaxBatch) : kPatDefaultBatch, n_guides);
-    const RoundsPlan plan{fn, n_guides, a.n_tiles, batch, &ctx->pattern_tabs, 2, kPatRowWords, params->max_hits};
+    RoundsPlan plan{fn, n_guides, a.n_tiles, batch, &ctx->pattern_tabs, 2, kPatRowWords, params->max_hits};
+    RoundsScore scored{(unsigned long long *)table_rows, select ? select->top_k : 0u, select ? select->min_score : 0u};
+    PatScoreArgs sc{};
+    std::vector<vsc_pattern_summary> own_rows;  // table rows alone: the NM rows are what the call's hit count comes from
+    if (table) {
+        plan.score = &scored;
+        sc.shape = table->shape;
+        if (n_guides && a.n_tiles) {
+            VSC_HIP(ctx, hipSetDevice(ctx->device));
+            const int trc = resident_pattern_table(ctx, table);
+            if (trc != VSC_OK) return trc;
+        }
+        sc.weights = (const double *)ctx->pattern_table_buf.p;
+        if (!out && !rows) {
+            own_rows.resize(n_guides);
+            rows = own_rows.data();
+        }
+    }
+    const uint32_t tables = table ? 3 : 2;
     return run_rounds(
         ctx, plan, out, (uint32_t *)rows,
-        // two tables, '+' and '-', one stride apart
-        [](uint32_t n) { return 2 * pattern_table_slots(n); },
-        [&](uint32_t g0, uint32_t n, uint4 *table) {
+        // two tables, '+' and '-', one stride apart (scored: a third, the guides in read orientation)
+        [tables](uint32_t n) { return tables * pattern_table_slots(n); },
+        [&](uint32_t g0, uint32_t n, uint4 *tab) {
             const uint32_t stride = pattern_table_slots(n);
             for (uint32_t i = 0; i < n; ++i) {
-                table[i] = planes[2 * (size_t)(g0 + i)];
-                table[stride + i] = planes[2 * (size_t)(g0 + i) + 1];
+                tab[i] = planes[2 * (size_t)(g0 + i)];
+                tab[stride + i] = planes[2 * (size_t)(g0 + i) + 1];
+                if (table) tab[2 * stride + i] = reads[g0 + i];
             }
         },
         [&](const Round &r, bool write) {
@@ -3354,9 +3477,118 @@ int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *patte
             a.rows = r.rows;
             a.records = (uint32_t *)r.records;
             a.n_records = r.n_records;
+            if (write && table) {
+                sc.fixed = r.side;
+                sc.table_rows = r.rows64;
+                return launch_pattern_write_scored(a, sc, ctx->n_cus, ctx->stream);
+            }
             return write ? launch_pattern_write(a, ctx->n_cus, ctx->stream) : launch_pattern_count(a, ctx->n_cus, ctx->stream);
         });
     });
+}
+
+int vsc_search_pattern(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
+                       const vsc_pattern_params *params, vsc_pattern_hits **out, vsc_pattern_summary *rows)
+{
+    return search_pattern_call(ctx, "vsc_search_pattern", genome, pattern, guides, n_guides, len, params, nullptr, nullptr, out, rows, nullptr);
+}
+
+// ---- table scores for pattern hits (the score: vsc_pattern_table.h; the kernels: vsc_pattern.hip) -------------
+int vsc_search_pattern_table(vsc_ctx *ctx, const vsc_genome *genome, const char *pattern, const char *guides, uint32_t n_guides, uint32_t len,
+                             const vsc_pattern_params *params, const vsc_pattern_table *table, const vsc_pattern_select *select,
+                             vsc_pattern_hits **out, vsc_pattern_summary *rows, vsc_guide_table_row *table_rows)
+{
+    if (!table) {
+        if (out) *out = nullptr;
+        return ctx ? fail_in(ctx, VSC_ERR_INVALID, "vsc_search_pattern_table", "null argument") : VSC_ERR_INVALID;
+    }
+    return search_pattern_call(ctx, "vsc_search_pattern_table", genome, pattern, guides, n_guides, len, params, table, select, out, rows,
+                               table_rows);
+}
+
+int vsc_pattern_hits_scores(vsc_pattern_hits *hits, const uint32_t **fixed)
+{
+    if (!hits || !fixed || !hits->has_side) return VSC_ERR_INVALID;
+    return guarded(hits->ctx, [&]() -> int {
+    if (!hits->side_host_valid) {
+        vsc_ctx *ctx = hits->ctx;
+        hits->side_host.resize(hits->n);
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, hipMemcpyAsync(hits->side_host.data(), (const char *)hits->storage.p + hits->side_at, hits->n * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hits->side_host_valid = true;
+    }
+    *fixed = hits->side_host.data();
+    return VSC_OK;
+    });
+}
+
+const void *vsc_pattern_hits_scores_dev(const vsc_pattern_hits *hits)
+{
+    return hits && hits->has_side && hits->n ? (const char *)hits->storage.p + hits->side_at : nullptr;
+}
+
+int vsc_pattern_table_build(const vsc_pattern_table_shape *shape, const double *pair, const double *pam, vsc_pattern_table **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!shape || !pair || !pam) return VSC_ERR_INVALID;
+    static std::atomic<uint64_t> serial{0};
+    PatTableShape sh{};
+    std::memcpy(&sh, shape, sizeof sh);
+    if (!pattern_table_shape_valid(sh)) return VSC_ERR_INVALID;  // (before the weights are read: the shape sizes them)
+    for (uint32_t t = sh.n_pam; t < kPatTableMaxPam; ++t) sh.pam_pos[t] = 0;
+    vsc_pattern_table *t = new (std::nothrow) vsc_pattern_table();
+    if (!t) return VSC_ERR_NOMEM;
+    t->shape = sh;
+    const uint32_t pairs = pattern_table_pairs(sh), n = pattern_table_weights(sh);
+    std::memcpy(t->w, pair, pairs * sizeof(double));
+    std::memcpy(t->w + pairs, pam, (n - pairs) * sizeof(double));
+    if (!pattern_table_valid(sh, t->w)) {  // a weight outside [0, 1] (NaN included) or a diagonal entry other than 1
+        delete t;
+        return VSC_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n; ++i) t->zeros += t->w[i] == 0.0;
+    t->serial = serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    *out = t;
+    return VSC_OK;
+}
+
+int vsc_pattern_table_free(vsc_pattern_table *table)
+{
+    delete table;
+    return VSC_OK;
+}
+
+int vsc_pattern_table_info(const vsc_pattern_table *table, vsc_pattern_table_stats *out)
+{
+    if (!table || !out) return VSC_ERR_INVALID;
+    *out = vsc_pattern_table_stats{};
+    out->serial = table->serial;
+    out->zero_weights = table->zeros;
+    std::memcpy(&out->shape, &table->shape, sizeof out->shape);
+    return VSC_OK;
+}
+
+int vsc_pattern_table_score(const vsc_pattern_table *table, const char *guide, const char *site_text, double *score, uint32_t *fixed)
+{
+    if (!table || !guide || !site_text) return VSC_ERR_INVALID;
+    const uint32_t len = table->shape.len;
+    uint8_t sets[kPatMaxLen];
+    if (!pattern_sets(guide, len, sets)) return VSC_ERR_INVALID;
+    uint32_t gh, gl, single, sh = 0, sl = 0;
+    pattern_table_guide(sets, len, &gh, &gl, &single);
+    for (uint32_t j = 0; j < len; ++j) {
+        const int c = base_code(site_text[j]);
+        if (c > 3) return VSC_ERR_INVALID;
+        sh |= (uint32_t)(c >> 1) << j;
+        sl |= (uint32_t)(c & 1) << j;
+    }
+    const double x = pattern_table_score(table->w, table->shape, gh, gl, single, sh, sl);
+    if (score) *score = x;
+    if (fixed) *fixed = table_fixed(x);
+    return VSC_OK;
 }
 
 uint64_t vsc_pattern_hits_count(const vsc_pattern_hits *hits) { return hits ? hits->n : 0; }

@@ -8,6 +8,7 @@
 
 #include "varscot_hip_debug.h"
 #include "vsc_internal.h"
+#include "vsc_pattern_table.h"
 
 namespace vsc {
 
@@ -153,6 +154,10 @@ struct vsc_ctx {
     // vsc_search_pattern: the same parts - rows and site counter, then per round the guides' planes, the counts per cell,
     // their sums per 64 cells and the scan of those
     vsc::DeviceBuf pattern_tabs;
+    // vsc_search_pattern_table: the device copy of the pattern table this context used last (at most 768 doubles, keyed by
+    // the table's serial number)
+    vsc::DeviceBuf pattern_table_buf;
+    uint64_t pattern_table_serial = 0;  // 0: none resident
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -229,6 +234,15 @@ struct vsc_score_table {
     uint32_t zeros = 0;   // weights that are exactly 0
 };
 
+// A pattern score table (include/varscot_hip.h "TABLE" of vsc_search_pattern_table; built and checked by
+// vsc_pattern_table_build).  Host-only, immutable once built.
+struct vsc_pattern_table {
+    vsc::PatTableShape shape{};
+    double w[vsc::kPatTableMaxWeights] = {};  // pair[ps_len][4][4], then pam[4^n_pam] (vsc_pattern_table.h)
+    uint64_t serial = 0;  // process-wide, handed out by vsc_pattern_table_build: what a context's device copy is keyed by
+    uint32_t zeros = 0;   // weights that are exactly 0
+};
+
 // An efficiency model (include/varscot_hip.h "MODEL"; built and checked by vsc_eff_model_build).  Host-only, immutable once built.
 struct vsc_eff_model {
     vsc::EffShape shape{};
@@ -270,6 +284,11 @@ template <class Rec> struct RecordList {
     uint64_t n = 0;
     std::vector<Rec> host;
     bool host_valid = false;
+    // a scored search (vsc_search_pattern_table): one uint32_t per record behind the records, side_at bytes into storage
+    bool has_side = false;
+    size_t side_at = 0;
+    std::vector<uint32_t> side_host;
+    bool side_host_valid = false;
 };
 
 }  // namespace vsc

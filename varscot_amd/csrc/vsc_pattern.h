@@ -8,6 +8,7 @@
 #pragma once
 
 #include "vsc_internal.h"
+#include "vsc_pattern_table.h"
 
 namespace vsc {
 
@@ -138,8 +139,36 @@ struct PatternArgs {
     uint32_t *rows;                // write pass: vsc_pattern_summary rows of ALL guides, zeroed once per call (null: records only)
 };
 
+// What the scored write pass (vsc_search_pattern_table) takes beside PatternArgs.  PatternArgs::guides then holds
+// a third table, 2 * guide_stride in: per guide (gh, gl, single, 0), its read-orientation planes as pattern_table_guide makes them.
+constexpr uint32_t kPatTableRowWords = 12;  // vsc_guide_table_row as 64-bit words: score_sum, positive, positive_nm[9], reserved
+struct PatScoreArgs {
+    PatTableShape shape;
+    const double *weights;           // device: pattern_table_weights(shape) doubles
+    uint32_t *fixed;                 // f per record, parallel to PatternArgs::records (null when those are)
+    unsigned long long *table_rows;  // vsc_guide_table_row rows of ALL guides, zeroed once per call (null: not asked for)
+};
+
+// The selection stage behind the scored write pass: per guide of the round the hits with f >= min_score, of those the first
+// top_k (0: all) by f descending, then record order - in record order.
+struct PatSelectArgs {
+    const uint32_t *count, *chunk_sum;     // the round's cells, as the write pass read them: guide r's records are those of
+    const unsigned long long *group_off;   // cells [2 r * n_tiles, 2 (r + 1) * n_tiles) - one contiguous segment
+    uint32_t n_tiles, n_guides;
+    unsigned long long n_records;          // the round's records before the selection
+    const uint32_t *records, *fixed;       // ... and where the write pass left them
+    uint32_t top_k, min_score;
+    uint4 *sel;                            // per guide of the round: (T, take, kept low, kept high)
+    uint32_t *out_records, *out_fixed;     // walk: the round's survivors
+    unsigned long long n_out;
+};
+
 // waves of either pass: each takes a run of consecutive tiles
 hipError_t launch_pattern_count(const PatternArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_pattern_write(const PatternArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_pattern_write_scored(const PatternArgs &args, const PatScoreArgs &score, int n_cus, hipStream_t stream);
+// one workgroup per guide of the round: the threshold (T, take, kept) of every guide, then the walk that keeps the survivors
+hipError_t launch_pattern_select(const PatSelectArgs &args, hipStream_t stream);
+hipError_t launch_pattern_select_walk(const PatSelectArgs &args, hipStream_t stream);
 
 }  // namespace vsc

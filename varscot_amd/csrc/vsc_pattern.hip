@@ -22,6 +22,9 @@
 //                           hits of earlier steps + lanes in front.  The rows come from this pass.
 // No record is placed through an atomic and nothing is sorted: the bytes depend on the planes and the parameters only.
 //
+// Beside the write pass: pattern_write_scored_kernel (vsc_search_pattern_table) - the same pass, every hit lane also
+// taking the table score of its site, and pattern_select_kernel / pattern_select_walk_kernel, the floor and the top K per guide.
+//
 // Behind the search: pattern_enum_kernel (vsc_guides_enumerate_pattern) - the same front end without the queue,
 // in front of enum_kernel's count / scan / write.
 #include "vsc_internal.h"
@@ -97,6 +100,15 @@ __device__ __forceinline__ void pattern_site(const PatLds &s, uint32_t e, uint32
 }
 
 __device__ __forceinline__ PatPlanes planes_of(v4u v) { return PatPlanes{v.x, v.y, v.z, v.w}; }
+
+// the L-bit plane p of a forward site as the plane of its reverse complement: bit j to L - 1 - j, inverted; bits from L on 0
+__device__ __forceinline__ uint32_t pattern_revcomp_plane(uint32_t p, uint32_t len) { return (~__brev(p)) >> (32u - len); }
+
+// The scored write pass's LDS beside PatLds: the cell's table row (score_sum, positive_nm; positive is their sum).
+struct PatScoreLds {
+    unsigned long long sum;
+    uint32_t pos[kPatRowWords];
+};
 
 // One step of the count pass: kSlots x 64 queued sites from `base` on against every guide of the round; lane g adds the hits
 // of guide g to cnt.  An instance per number of slots (kPatSlots of them) instead of a test per slot and guide: the last step
@@ -175,12 +187,22 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_count_kernel(co
 }
 
 // ---- write pass --------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(const PatternArgs a)
+namespace {
+
+// kScore: the scored pass of vsc_search_pattern_table - every hit lane also takes the product of the table over
+// its site, which it holds in registers, and the cell's table row is gathered beside the NM row.  w: the table's weights in
+// LDS, rows_lds: the waves' table rows.  The unscored instance is the kernel of DESIGN 4.17: the same registers and LDS.
+template <bool kScore>
+__device__ __forceinline__ void pattern_write(const PatternArgs &a, const PatScoreArgs &sc, PatLds *lds, const double *w, PatScoreLds *rows_lds)
 {
-    __shared__ PatLds s_lds[kWavesPerGroup];
     const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    PatLds &s = s_lds[wave];
+    PatLds &s = lds[wave];
+    PatScoreLds &ts = rows_lds[kScore ? wave : 0u];
     if (lane < 16u) s.row[lane] = 0;
+    if (kScore) {
+        if (lane < kPatRowWords) ts.pos[lane] = 0;
+        if (lane == 0) ts.sum = 0;
+    }
     uint32_t t0, t1;
     cell_tile_run(a.n_tiles, blockIdx.x * kWavesPerGroup + wave, gridDim.x * kWavesPerGroup, &t0, &t1);
     const const_v4u_ptr gp = (const_v4u_ptr)(uintptr_t)a.guides;
@@ -208,6 +230,8 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
                 const uint64_t word = g < 32u ? live_lo : live_hi;
                 if (((word >> (2u * (g & 31u) + strand)) & 1u) == 0) continue;  // wave-uniform
                 const PatPlanes planes = planes_of(gp[strand * a.guide_stride + g]);
+                v4u read{};  // kScore: the guide in read orientation (gh, gl, single)
+                if (kScore) read = gp[2u * a.guide_stride + g];
                 const unsigned long long cell = (unsigned long long)(2u * g + strand) * a.n_tiles + tile;
                 unsigned long long at = a.records ? cell_offset(a.count, a.chunk_sum, a.group_off, cell, lane) : 0ull;
                 for (uint32_t base = 0; base < total; base += kWave) {
@@ -223,6 +247,17 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
                     if (hits == 0) continue;
                     if (hit) {
                         if (a.rows) atomicAdd(&s.row[nm], 1u);
+                        uint32_t f = 0;
+                        if (kScore) {
+                            // the site in read orientation: as it lies on '+', reversed and complemented on '-'
+                            const uint32_t rh = strand ? pattern_revcomp_plane(wh, a.len) : wh;
+                            const uint32_t rl = strand ? pattern_revcomp_plane(wl, a.len) : wl;
+                            f = table_fixed(pattern_table_score(w, sc.shape, read.x, read.y, read.z, rh, rl));
+                            if (sc.table_rows) {
+                                atomicAdd(&ts.sum, (unsigned long long)f);
+                                if (f) atomicAdd(&ts.pos[nm], 1u);
+                            }
+                        }
                         if (a.records) {
                             const uint32_t pos = tile_pos + e;  // (e = lane << 5 | bit = the start's offset in the tile)
                             if (pos >= c_end || pos < c_off) {  // the last contig that starts at or before pos (an N-free site lies inside one contig)
@@ -244,6 +279,7 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
                                 rec[2] = pos - c_off;
                                 rec[3] = strand << 31 | nm;
                                 rec[4] = x;
+                                if (kScore) sc.fixed[r] = f;
                             }
                         }
                     }
@@ -258,8 +294,175 @@ __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(co
                     }
                     wave_sync();
                 }
+                if (kScore && sc.table_rows) {
+                    // the cell's table row: positive_nm from lanes 0..8, positive (their sum) from lane 9, score_sum from lane 10
+                    wave_sync();
+                    const uint32_t v = lane < kPatRowWords ? ts.pos[lane] : 0u;
+                    const uint32_t positive = wave_sum(v);
+                    const unsigned long long sum = ts.sum;
+                    wave_sync();
+                    unsigned long long *row = sc.table_rows + (size_t)(a.guide_base + g) * kPatTableRowWords;
+                    if (lane < kPatRowWords && v) {
+                        atomicAdd(&row[2u + lane], (unsigned long long)v);
+                        ts.pos[lane] = 0;
+                    }
+                    if (lane == kPatRowWords && positive) atomicAdd(&row[1], (unsigned long long)positive);
+                    if (lane == kPatRowWords + 1u && sum) {
+                        atomicAdd(&row[0], sum);
+                        ts.sum = 0;
+                    }
+                    wave_sync();
+                }
             }
         }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_kernel(const PatternArgs a)
+{
+    __shared__ PatLds s_lds[kWavesPerGroup];
+    PatScoreLds none;
+    pattern_write<false>(a, PatScoreArgs{}, s_lds, nullptr, &none);
+}
+
+// ---- scored write pass (vsc_search_pattern_table) ----------------------------------------------------------
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_write_scored_kernel(const PatternArgs a, const PatScoreArgs sc)
+{
+    __shared__ PatLds s_lds[kWavesPerGroup];
+    __shared__ PatScoreLds s_rows[kWavesPerGroup];
+    __shared__ double s_w[kPatTableMaxWeights];
+    const uint32_t n_w = pattern_table_weights(sc.shape);  // (<= kPatTableMaxWeights: the host has checked the shape)
+    for (uint32_t i = threadIdx.x; i < n_w && i < kPatTableMaxWeights; i += kWave * kWavesPerGroup) s_w[i] = sc.weights[i];
+    block_sync();
+    pattern_write<true>(a, sc, s_lds, s_w, s_rows);
+}
+
+// ---- selection stage --------------------------------------------------------------------------------------
+// One workgroup per guide of the round.  The guide's records are one segment of the round's: from the offset of its first
+// '+' cell to that of the next guide's.  pattern_select_kernel finds, by an exact radix select over the segment's f words
+// (four 8-bit digits from the top: f <= 2^30), the value T of the top_k-th survivor and how many records with f = T are
+// still to take; pattern_select_walk_kernel then walks the segment in record order, 256 records a step, and keeps f > T and
+// the first `take` records with f = T - the ranking's tie-break IS the record order.  Nothing is appended through an atomic.
+namespace {
+
+constexpr uint32_t kPatSelThreads = kWave * kWavesPerGroup;
+
+// [*begin, *end) of guide r's records among the round's (every wave computes both: cell_offset is a wave's)
+__device__ __forceinline__ void select_segment(const PatSelectArgs &a, uint32_t r, uint32_t lane, unsigned long long *begin, unsigned long long *end)
+{
+    unsigned long long b = cell_offset(a.count, a.chunk_sum, a.group_off, (unsigned long long)(2u * r) * a.n_tiles, lane);
+    unsigned long long e = r + 1u < a.n_guides ? cell_offset(a.count, a.chunk_sum, a.group_off, (unsigned long long)(2u * r + 2u) * a.n_tiles, lane)
+                                               : a.n_records;
+    if (e > a.n_records) e = a.n_records;  // (never, when the passes saw the same planes: keeps every read inside the arrays)
+    if (b > e) b = e;
+    *begin = b;
+    *end = e;
+}
+
+// exclusive prefix of v over the workgroup's threads and *total = the sum; ws: kWavesPerGroup words of LDS
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *ws, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    uint32_t wave_total;
+    const uint32_t in_wave = wave_exclusive(v, lane, &wave_total);
+    block_sync();  // (the last step's readers of ws are done)
+    if (lane == 0) ws[wave] = wave_total;
+    block_sync();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kWavesPerGroup; ++k) {
+        const uint32_t t = ws[k];
+        before += k < wave ? t : 0u;
+        all += t;
+    }
+    *total = all;
+    return before + in_wave;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_select_kernel(const PatSelectArgs a)
+{
+    __shared__ uint32_t s_hist[256];
+    __shared__ uint32_t s_state[4];  // prefix, k, done
+    const uint32_t r = blockIdx.x, tid = threadIdx.x, lane = tid % kWave;
+    unsigned long long begin, end;
+    select_segment(a, r, lane, &begin, &end);
+    const unsigned long long n = end - begin;
+    const uint32_t *f = a.fixed + begin;
+    uint32_t prefix = 0, mask = 0, k = a.top_k;
+    for (uint32_t pass = 0; pass < 4u; ++pass) {
+        const uint32_t shift = 24u - 8u * pass;
+        s_hist[tid] = 0;  // (kPatSelThreads == 256)
+        block_sync();
+        for (unsigned long long i = tid; i < n; i += kPatSelThreads) {
+            const uint32_t v = f[i];
+            if (v >= a.min_score && (v & mask) == prefix) atomicAdd(&s_hist[(v >> shift) & 255u], 1u);
+        }
+        block_sync();
+        if (tid == 0) {
+            uint32_t done = 0;
+            if (pass == 0) {
+                unsigned long long survivors = 0;
+                for (uint32_t b = 0; b < 256u; ++b) survivors += s_hist[b];
+                if (a.top_k == 0 || survivors <= a.top_k) {  // all of them: f > min_score, and every record with f = min_score
+                    a.sel[r] = make_uint4(a.min_score, ~0u, (uint32_t)survivors, (uint32_t)(survivors >> 32));
+                    done = 1;
+                }
+            }
+            if (!done) {
+                // the digit of the k-th largest: the first bin from the top at which the count reaches k
+                uint32_t b = 255u, above = 0;
+                while (b > 0u && above + s_hist[b] < k) above += s_hist[b--];
+                s_state[0] = prefix | b << shift;
+                s_state[1] = k - above;
+            }
+            s_state[2] = done;
+        }
+        block_sync();
+        if (s_state[2]) return;  // (uniform over the workgroup)
+        prefix = s_state[0];
+        k = s_state[1];
+        mask |= 255u << shift;
+        block_sync();  // (s_state and s_hist are written again)
+    }
+    if (tid == 0) a.sel[r] = make_uint4(prefix, k, a.top_k, 0u);  // T = prefix; k of the records with f = T are taken
+}
+
+__global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_select_walk_kernel(const PatSelectArgs a)
+{
+    __shared__ uint32_t s_ws[kWavesPerGroup], s_ws2[kWavesPerGroup];
+    const uint32_t r = blockIdx.x, tid = threadIdx.x, lane = tid % kWave;
+    unsigned long long begin, end;
+    select_segment(a, r, lane, &begin, &end);
+    const unsigned long long n = end - begin;
+    unsigned long long out = 0;  // the survivors of the guides in front
+    for (uint32_t q = 0; q < r; ++q) out += (unsigned long long)a.sel[q].w << 32 | a.sel[q].z;
+    const uint4 mine = a.sel[r];
+    const uint32_t T = mine.x;
+    const unsigned long long take = mine.y == ~0u ? ~0ull : mine.y;
+    unsigned long long ties = 0;  // records with f = T in front of this step
+    for (unsigned long long base = 0; base < n; base += kPatSelThreads) {
+        const unsigned long long i = base + tid;
+        const bool live = i < n;
+        const uint32_t v = live ? a.fixed[begin + i] : 0u;
+        const bool tie = live && v == T;
+        uint32_t step_ties, step_kept;
+        const uint32_t tie_rank = block_exclusive(tie ? 1u : 0u, s_ws, &step_ties);
+        const bool keep = live && (v > T || (tie && ties + tie_rank < take));
+        const uint32_t rank = block_exclusive(keep ? 1u : 0u, s_ws2, &step_kept);
+        const unsigned long long at = out + rank;
+        if (keep && at < a.n_out) {
+            const uint32_t *src = a.records + (begin + i) * kPatRecordWords;
+            uint32_t *dst = a.out_records + at * kPatRecordWords;
+#pragma unroll
+            for (uint32_t k = 0; k < kPatRecordWords; ++k) dst[k] = src[k];
+            a.out_fixed[at] = v;
+        }
+        ties += step_ties;
+        out += step_kept;
     }
 }
 
@@ -304,9 +507,6 @@ __device__ __forceinline__ uint32_t pattern_range_mask(const PatEnumArgs &a, uin
     }
     return m;
 }
-
-// the L-bit plane p of a forward site as the plane of its reverse complement: bit j to L - 1 - j, inverted; bits from L on 0
-__device__ __forceinline__ uint32_t pattern_revcomp_plane(uint32_t p, uint32_t len) { return (~__brev(p)) >> (32u - len); }
 
 }  // namespace
 
@@ -386,6 +586,27 @@ hipError_t launch_pattern_write(const PatternArgs &args, int n_cus, hipStream_t 
 {
     if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
     hipLaunchKernelGGL(pattern_write_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_pattern_write_scored(const PatternArgs &args, const PatScoreArgs &score, int n_cus, hipStream_t stream)
+{
+    if (args.n_tiles == 0 || args.n_guides == 0) return hipSuccess;
+    hipLaunchKernelGGL(pattern_write_scored_kernel, cell_grid(args.n_tiles, n_cus), dim3(kWave * kWavesPerGroup), 0, stream, args, score);
+    return hipGetLastError();
+}
+
+hipError_t launch_pattern_select(const PatSelectArgs &args, hipStream_t stream)
+{
+    if (args.n_guides == 0) return hipSuccess;
+    hipLaunchKernelGGL(pattern_select_kernel, dim3(args.n_guides), dim3(kWave * kWavesPerGroup), 0, stream, args);
+    return hipGetLastError();
+}
+
+hipError_t launch_pattern_select_walk(const PatSelectArgs &args, hipStream_t stream)
+{
+    if (args.n_guides == 0) return hipSuccess;
+    hipLaunchKernelGGL(pattern_select_walk_kernel, dim3(args.n_guides), dim3(kWave * kWavesPerGroup), 0, stream, args);
     return hipGetLastError();
 }
 
