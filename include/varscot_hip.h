@@ -474,6 +474,7 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
  * RECORD  one per hit site: NM = min_i nm(i), index = the smallest i that reaches it.  d = 0 is vsc_search's business and is
  *         never reported here.  A plain hit with NM <= m - 1 has bulged neighbours at index 1 (the site one base longer or
  *         shorter at its 5' end pairs as the plain window does but for r[0]); they ARE reported, as Cas-OFFinder reports them.
+ *         vsc_hits_sites (below) collapses them with the plain hits into one record per cut site.
  * ORDER   ascending (guide, strand, contig, pos, d).  The bytes depend on the planes and the parameters only: every record is
  *         written at a rank computed from counts (count pass, scan, write pass), nothing is appended through an atomic.
  *
@@ -677,7 +678,7 @@ int vsc_pattern_match(const char *pattern, const char *guide, const char *site_t
  * be NULL.  Everything REFUSED above (with dna_max / rna_max = the size of d), a wrong d, a NULL text or a site text of another
  * length: VSC_ERR_INVALID.
  * Not provided: a vsc_multi_* entry point (shard results merge by ORDER), a seed index for patterns, MIT or classifier scores
- * for other nucleases, and suppressing the bulged neighbours of plain hits.
+ * for other nucleases.  Suppressing the bulged neighbours of plain hits: since added, vsc_hits_sites below.
  */
 typedef struct {
     uint32_t max_mismatches; /* 0..VSC_MAX_MISMATCHES */
@@ -696,6 +697,101 @@ int vsc_search_pattern_bulges(vsc_ctx *ctx, const vsc_genome *genome, const char
                               vsc_bulge_summary *rows /* may be NULL */);
 int vsc_pattern_bulge_align(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t proto_start,
                             uint32_t proto_len, int d, uint32_t *hit, uint32_t *nm, uint32_t *index);
+/*
+ * Cut sites: the plain and the bulged alignments of a search collapsed into one record per genomic cut site - the merge step
+ * that CRISPRitz and CRISPRme run over a bulge report before anything is counted or ranked.  One cut site shows up as up to
+ * five alignments: the plain window plus the sites one or two bases longer or shorter that share its PAM.
+ *
+ * An ALIGNMENT is a record of a plain search or of a bulge search over the same guides and genome.
+ *   - Plain records are vsc_hit or vsc_pattern_hit.  Their d is 0.
+ *   - Bulged records are vsc_bulge_hit.  Their d is in {-2, -1, +1, +2}.
+ *   - The site length is len + d.
+ * Parameters: len is 23 for SpCas9, or the pattern's length.  anchor is one of:
+ *   - VSC_SITE_ANCHOR_END: the 3' end of the site in read orientation is the fixed, PAM-side end.  SpCas9 and SaCas9 use this.
+ *   - VSC_SITE_ANCHOR_START: the 5' end is fixed.  Cas12a uses this.
+ * The anchor coordinate a of an alignment at forward start pos:
+ *     anchor  strand  a
+ *     END     '+'     pos + len + d
+ *     END     '-'     pos
+ *     START   '+'     pos
+ *     START   '-'     pos + len + d
+ * A SITE is the set of all input alignments with equal (guide, strand, contig, a).
+ *   - A site has at most five members, one per d.
+ *   - On the strand where a = pos, a site's members share pos.
+ *   - On the other strand, the member with d' starts at pos + d - d'.  len cancels out of membership.
+ * Its BEST alignment is the minimum under (NM + |d|, |d|, DNA before RNA).  The order is total inside a site.  A plain hit
+ * therefore beats its own index-1 bulged neighbours (equal cost, smaller |d|).
+ * Output is one record per site, in ascending (guide, strand, contig, pos, d) order OF THE BEST ALIGNMENT.  This is the order
+ * the inputs have.
+ *
+ * vsc_hits_sites / vsc_pattern_hits_sites: the collapse on the device, over the records of two results where they lie - a
+ * flag pass (one alignment per lane: a bounded walk in its own list, one binary search in the other), a scan of the 64-record
+ * tiles' counts, one read-back that sizes the result, a write pass.  No sort, no append atomic: the bytes depend on the inputs
+ * only.  Rules for both:
+ *   - Either input may be NULL or empty.  Both NULL is VSC_ERR_INVALID.  A result of another context: VSC_ERR_INVALID.
+ *   - out or rows may be NULL.  Both NULL is VSC_ERR_INVALID.  rows: host memory, n_guides entries.
+ *   - A record whose guide is >= n_guides, a non-zero reserved field, an unknown anchor, or len outside 16..32: VSC_ERR_INVALID.
+ *   - More than 2^32 - 1 alignments in total: VSC_ERR_RANGE.
+ *   - Inputs must be in the order their searches return.  The results of vsc_search_select* qualify.  The order is NOT
+ *     verified: records in another order give sites that mean nothing (no access leaves the lists, every walk is bounded).
+ *   - The inputs and vsc_ctx_timing stay as they are, as with vsc_hits_pairs.
+ *   - Scratch comes from the context's pools and is returned by vsc_ctx_release_scratch.
+ * Shards: the members of one site can start in different shards, so the call is defined on MERGED records - the plain result
+ * of a multi-device search, bulged records merged by their order on the host through vsc_sites_collapse.  There is no
+ * vsc_multi_* entry.
+ * vsc_sites_collapse / vsc_sites_collapse_pattern: the same definition on host arrays, by the functions the kernels run; they
+ * need no device.  sites: room for `capacity` records or NULL (count and rows only); *n_sites (optional) = the number of
+ * sites.  More sites than capacity when sites != NULL: VSC_ERR_RANGE, nothing is written to sites (rows and *n_sites are
+ * valid).  The refusals of the device calls apply.
+ * Not provided: merging sites whose anchors merely lie close (CRISPRme's 3-bp window: it needs chaining over anchor order),
+ * scores for bulged alignments, leaving out the on-target, a vsc_multi_* entry point.
+ */
+#define VSC_SITE_ANCHOR_END 0u
+#define VSC_SITE_ANCHOR_START 1u
+#define VSC_SITE_ABSENT 31u /* a members field without a member */
+#define VSC_SITE_MEMBER_NM(members, d) (((members) >> (5 * ((d) + 2))) & 31u)
+#define VSC_SITE_MEMBERS(members) (((members) >> 25) & 7u)
+typedef struct {
+    uint32_t guide, contig, pos; /* of the best alignment */
+    uint32_t info;     /* VSC_BULGE_* layout; a plain best has size 0, kind 0, index 0 */
+    uint32_t anchor;   /* a, forward genome */
+    uint32_t members;  /* bits 5k..5k+4, k = d + 2: NM of the member with that d, 31 = absent; bits 25..27 = number of members */
+    uint32_t best;     /* index of the best alignment in ITS input list (plain if size 0, else bulged) */
+    uint32_t reserved; /* 0 */
+} vsc_site;
+typedef struct {
+    uint32_t sites, alignments;  /* sites of the guide; input records of the guide */
+    uint32_t bulge_only;         /* sites without a plain member */
+    uint32_t count[3][VSC_MAX_MISMATCHES + 1]; /* sites by |d| and NM of the best */
+} vsc_site_summary;
+typedef struct { uint32_t len, anchor, reserved[2]; } vsc_site_params;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_site) == 32, "vsc_site layout");
+static_assert(sizeof(vsc_site_summary) == 120, "vsc_site_summary layout");
+static_assert(sizeof(vsc_site_params) == 16, "vsc_site_params layout");
+#else
+_Static_assert(sizeof(vsc_site) == 32, "vsc_site layout");
+_Static_assert(sizeof(vsc_site_summary) == 120, "vsc_site_summary layout");
+_Static_assert(sizeof(vsc_site_params) == 16, "vsc_site_params layout");
+#endif
+typedef struct vsc_sites vsc_sites;
+int vsc_hits_sites(vsc_ctx *ctx, vsc_hits *plain /* may be NULL */, vsc_bulge_hits *bulged /* may be NULL */, uint32_t n_guides,
+                   const vsc_site_params *params, vsc_sites **out /* may be NULL */, vsc_site_summary *rows /* may be NULL */);
+int vsc_pattern_hits_sites(vsc_ctx *ctx, vsc_pattern_hits *plain /* may be NULL */, vsc_bulge_hits *bulged /* may be NULL */,
+                           uint32_t n_guides, const vsc_site_params *params, vsc_sites **out /* may be NULL */,
+                           vsc_site_summary *rows /* may be NULL */);
+uint64_t vsc_sites_count(const vsc_sites *sites);
+/* Host copy of the records (made on first use; valid until vsc_sites_free). */
+int vsc_sites_data(vsc_sites *sites, const vsc_site **out);
+/* Device pointer (valid until vsc_sites_free); NULL when the result is empty. */
+const void *vsc_sites_data_dev(const vsc_sites *sites);
+int vsc_sites_free(vsc_sites *sites);
+int vsc_sites_collapse(const vsc_hit *plain, uint64_t n_plain, const vsc_bulge_hit *bulged, uint64_t n_bulged, uint32_t n_guides,
+                       const vsc_site_params *params, vsc_site *sites /* may be NULL */, uint64_t capacity, uint64_t *n_sites,
+                       vsc_site_summary *rows /* may be NULL */);
+int vsc_sites_collapse_pattern(const vsc_pattern_hit *plain, uint64_t n_plain, const vsc_bulge_hit *bulged, uint64_t n_bulged,
+                               uint32_t n_guides, const vsc_site_params *params, vsc_site *sites /* may be NULL */, uint64_t capacity,
+                               uint64_t *n_sites, vsc_site_summary *rows /* may be NULL */);
 /*
  * Pattern guide discovery: which guides of ANY nuclease does a target contain?  vsc_guides_enumerate for a pattern - the
  * beginning of the route that vsc_search_pattern continues: "every Cas12a guide in these exons with its off-target counts" is

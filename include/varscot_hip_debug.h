@@ -62,6 +62,11 @@ int vsc_debug_pattern_target_ranges(const vsc_contig *contigs, uint32_t n_contig
  * vsc_guides_free. */
 int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out);
 
+/* The device milliseconds of the context's last vsc_hits_sites / vsc_pattern_hits_sites, between HIP events on its stream:
+ * the flag pass with the scan, and the write pass (either may be NULL).  The call leaves vsc_ctx_timing alone; this is where
+ * tools/sites_bench.py reads what its kernels took. */
+int vsc_debug_sites_ms(const vsc_ctx *ctx, double *flag_scan_ms, double *write_ms);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

@@ -124,6 +124,23 @@ class PatternBulgeParams(C.Structure):
 assert C.sizeof(PatternBulgeParams) == 32
 
 
+class SiteParams(C.Structure):
+    """vsc_site_params (vsc_hits_sites, vsc_sites_collapse): the plain site length (23, or the pattern's) and the anchor."""
+    _fields_ = [("len", C.c_uint32), ("anchor", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(SiteParams) == 16
+SITE_ANCHOR_END, SITE_ANCHOR_START = 0, 1
+SITE_ABSENT = 31  # a members field without a member
+# vsc_site: guide, contig, pos, info of the best alignment (info in the vsc_bulge_hit layout; a plain best has size 0); anchor = a;
+# members = NM per d in 5-bit fields (d = -2 lowest), the number of members in bits 25..27; best = its index in its input list
+SITE_DTYPE = np.dtype([("guide", "<u4"), ("contig", "<u4"), ("pos", "<u4"), ("info", "<u4"), ("anchor", "<u4"), ("members", "<u4"),
+                       ("best", "<u4"), ("reserved", "<u4")])
+# vsc_site_summary: count[|d|][NM of the best]
+SITE_ROW_DTYPE = np.dtype([("sites", "<u4"), ("alignments", "<u4"), ("bulge_only", "<u4"), ("count", "<u4", (3, 9))])
+assert SITE_DTYPE.itemsize == 32 and SITE_ROW_DTYPE.itemsize == 120
+
+
 class PairParams(C.Structure):
     """vsc_pair_params: two windows on opposite strands of one contig are PAIRED iff delta_min <= pos('+') - pos('-') <= delta_max."""
     _fields_ = [("delta_min", C.c_int32), ("delta_max", C.c_int32), ("reserved", C.c_uint32 * 2)]
@@ -350,6 +367,16 @@ SYMBOLS = [
     ("vsc_pattern_match", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, _u32p, _u32p, _u32p]),
     ("vsc_search_pattern_bulges", C.c_int, [_vp, _vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(PatternBulgeParams), C.POINTER(_vp), _vp]),
     ("vsc_pattern_bulge_align", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u32p, _u32p, _u32p]),
+    ("vsc_hits_sites", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SiteParams), C.POINTER(_vp), _vp]),
+    ("vsc_pattern_hits_sites", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SiteParams), C.POINTER(_vp), _vp]),
+    ("vsc_sites_count", C.c_uint64, [_vp]),
+    ("vsc_sites_data", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_sites_data_dev", _vp, [_vp]),
+    ("vsc_sites_free", C.c_int, [_vp]),
+    ("vsc_sites_collapse", C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.POINTER(SiteParams), _vp, C.c_uint64,
+                                     C.POINTER(C.c_uint64), _vp]),
+    ("vsc_sites_collapse_pattern", C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_uint32, C.POINTER(SiteParams), _vp, C.c_uint64,
+                                             C.POINTER(C.c_uint64), _vp]),
     ("vsc_guides_enumerate_pattern", C.c_int, [_vp, _vp, C.c_char_p, C.c_uint32, C.POINTER(PatternEnumParams), _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_pattern_guides_count", C.c_uint64, [_vp]),
     ("vsc_pattern_guides_data", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
@@ -457,6 +484,7 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_pattern_target_ranges", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_multi_create_debug", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(MultiDebugParams), C.POINTER(_vp)]),
     ("vsc_debug_guides_from_host", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_debug_sites_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 ]
 
 _lib = None

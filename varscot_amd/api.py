@@ -48,6 +48,49 @@ def unpack_bulge_info(info):
             "index": (w >> np.uint32(5)) & np.uint32(31), "nm": w & np.uint32(31)}
 
 
+SITE_DTYPE = _lib.SITE_DTYPE
+SITE_ROW_DTYPE = _lib.SITE_ROW_DTYPE
+_SITE_ANCHORS = {"end": _lib.SITE_ANCHOR_END, "start": _lib.SITE_ANCHOR_START}
+
+
+def unpack_site_members(members):
+    """The fields of vsc_site.members, of one word or an array of them: a dict of nm (int64, a last axis of five entries for
+    d = -2, -1, 0, 1, 2; -1 where the site has no member with that d) and count (the number of members)."""
+    m = np.asarray(members, dtype=np.uint32)
+    nm = ((m[..., None] >> (5 * np.arange(5, dtype=np.uint32))) & 31).astype(np.int64)
+    nm[nm == _lib.SITE_ABSENT] = -1
+    return {"nm": nm, "count": ((m >> 25) & 7).astype(np.int64)}
+
+
+def _site_params(length, anchor):
+    if anchor not in _SITE_ANCHORS:
+        raise ValueError("anchor must be 'end' or 'start', not %r" % (anchor,))
+    return _lib.SiteParams(int(length), _SITE_ANCHORS[anchor])
+
+
+def collapse_sites(plain, bulged, n_guides, length=23, anchor="end"):
+    """vsc_sites_collapse / vsc_sites_collapse_pattern: plain records (HIT_DTYPE or PATTERN_HIT_DTYPE; the dtype picks the
+    function) and bulged records (BULGE_HIT_DTYPE) of the same guides and genome, each in the order its search returns,
+    collapsed into one SITE_DTYPE record per cut site - the definition of Genome.search_sites on the host, by the functions the
+    kernels run.  Either may be None (not both).  Returns (sites in the order of their best alignments, SITE_ROW_DTYPE rows
+    per guide).  No device is needed."""
+    p = _site_params(length, anchor)
+    pattern = plain is not None and np.asarray(plain).dtype == PATTERN_HIT_DTYPE
+    if plain is not None:
+        plain = np.ascontiguousarray(plain, dtype=PATTERN_HIT_DTYPE if pattern else HIT_DTYPE)
+    if bulged is not None:
+        bulged = np.ascontiguousarray(bulged, dtype=BULGE_HIT_DTYPE)
+    n_plain, n_bulged = (0 if plain is None else len(plain)), (0 if bulged is None else len(bulged))
+    fn = lib().vsc_sites_collapse_pattern if pattern else lib().vsc_sites_collapse
+    rows = np.zeros(int(n_guides), dtype=SITE_ROW_DTYPE)
+    sites = np.zeros(n_plain + n_bulged, dtype=SITE_DTYPE)
+    n = C.c_uint64(0)
+    # (an empty array has a data pointer of its own: None is what says "no such list")
+    check(fn(None if plain is None else plain.ctypes.data_as(C.c_void_p), n_plain, None if bulged is None else bulged.ctypes.data_as(C.c_void_p),
+             n_bulged, int(n_guides), C.byref(p), sites.ctypes.data_as(C.c_void_p), len(sites), C.byref(n), rows.ctypes.data_as(C.c_void_p)))
+    return sites[:n.value].copy(), rows
+
+
 def bulge_align(read, site, d):
     """vsc_bulge_align: (NM, index) of one 23-nt read against one site of 23 + d letters in read orientation, d in -2, -1, 1, 2 -
     the definition of the bulge search on the host, by the function the kernels run.  No device is needed."""
@@ -1251,6 +1294,79 @@ class Genome:
         finally:
             L.vsc_bulge_hits_free(h)
         return recs, out_rows
+
+    def _collapse(self, fn, plain_h, bulged_h, n_guides, params, records, rows):
+        """vsc_hits_sites / vsc_pattern_hits_sites over two device results: (SITE_DTYPE records | None, SITE_ROW_DTYPE rows | None)."""
+        L = lib()
+        h = C.c_void_p()
+        out_rows = np.zeros(n_guides, dtype=SITE_ROW_DTYPE) if rows else None
+        check(fn(self.ctx._h, plain_h, bulged_h, n_guides, C.byref(params), C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+        if not records:
+            return None, out_rows
+        try:
+            n = int(L.vsc_sites_count(h))
+            data = C.c_void_p()
+            check(L.vsc_sites_data(h, C.byref(data)), self.ctx._h)
+            if n == 0:
+                recs = np.zeros(0, dtype=SITE_DTYPE)
+            else:
+                recs = np.frombuffer((C.c_char * (n * 32)).from_address(data.value), dtype=SITE_DTYPE).copy()
+        finally:
+            L.vsc_sites_free(h)
+        return recs, out_rows
+
+    def search_sites(self, guides, max_mismatches, dna=1, rna=1, extra_pam=None, algorithm="auto", guide_batch=0, records=True,
+                     rows=True):
+        """The cut sites of a search: vsc_search, vsc_search_bulges and vsc_hits_sites with the two intermediate results kept on
+        the device (and freed) - the plain hits and the bulged alignments of 23 + d bases collapsed into one SITE_DTYPE record
+        per (guide, strand, contig, PAM-side end), with the best alignment's fields (fewest mismatches + bulge bases, then the
+        smaller bulge, then DNA before RNA) and the NM of every member (unpack_site_members).  Returns (records in the order of
+        their best alignments | None, SITE_ROW_DTYPE rows per guide | None).  collapse_sites is the same on host arrays."""
+        codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
+        codes = np.ascontiguousarray(codes, dtype=np.uint64)
+        p = self._params(max_mismatches, extra_pam, algorithm)
+        bp = _lib.BulgeParams(int(dna), int(rna), int(guide_batch), 0, 0)
+        pb = self._params(max_mismatches, extra_pam, ALGO_SCAN)
+        L = lib()
+        plain, bulged = C.c_void_p(), C.c_void_p()
+        try:
+            check(L.vsc_search(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(plain)), self.ctx._h)
+            check(L.vsc_search_bulges(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(pb), C.byref(bp), C.byref(bulged), None), self.ctx._h)
+            return self._collapse(L.vsc_hits_sites, plain, bulged, len(codes), _site_params(23, "end"), records, rows)
+        finally:
+            L.vsc_bulge_hits_free(bulged)
+            L.vsc_hits_free(plain)
+
+    def search_pattern_sites(self, pattern, guides, max_mismatches, protospacer, dna=1, rna=1, anchor=None, guide_batch=0, records=True,
+                             rows=True):
+        """search_sites for any nuclease: vsc_search_pattern, vsc_search_pattern_bulges and vsc_pattern_hits_sites on the device.
+        anchor: "end" (the site's 3' end in read orientation is the fixed, PAM-side end: SpCas9, SaCas9), "start" (the 5' end:
+        Cas12a) or None - "end" when the protospacer starts at 0, "start" when it ends at the pattern's end, else ValueError."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+        for i, g in enumerate(gs):
+            if len(g) != len(p):
+                raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+        if anchor is None:
+            if int(protospacer[0]) == 0:
+                anchor = "end"
+            elif int(protospacer[0]) + int(protospacer[1]) == len(p):
+                anchor = "start"
+            else:
+                raise ValueError("the protospacer touches neither end of the pattern: say anchor='end' or 'start'")
+        sp = _site_params(len(p), anchor)
+        pp = _lib.PatternParams(int(max_mismatches), int(guide_batch), 0)
+        pbp = _lib.PatternBulgeParams(int(max_mismatches), int(guide_batch), 0, int(protospacer[0]), int(protospacer[1]), int(dna), int(rna))
+        L = lib()
+        plain, bulged = C.c_void_p(), C.c_void_p()
+        try:
+            check(L.vsc_search_pattern(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp), C.byref(plain), None), self.ctx._h)
+            check(L.vsc_search_pattern_bulges(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pbp), C.byref(bulged), None),
+                  self.ctx._h)
+            return self._collapse(L.vsc_pattern_hits_sites, plain, bulged, len(gs), sp, records, rows)
+        finally:
+            L.vsc_bulge_hits_free(bulged)
+            L.vsc_pattern_hits_free(plain)
 
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
                           max_guides=0, params=None, efficiency=None, min_efficiency=None):

@@ -75,6 +75,13 @@
 // kind = DNA | RNA, index = the read position in front of which the bulge lies (the smallest that gives the fewest mismatches),
 // sequence = the site's forward-genome bases.  -u runs on one device and does not combine with -v or -J.  Without -u every
 // output is what it was.
+// -Z sites.tsv (needs -u, as -U) collapses the plain and the bulged alignments into CUT SITES on the device (vsc_hits_sites): one
+// record per (guide, strand, chrom, PAM-side end) with its best alignment - fewest mismatches + bulge bases, then the smaller
+// bulge, then DNA before RNA.  Every line gains, behind all other columns, siteCount siteBulgeOnly (the sites; those without a
+// plain member).  The listing, in ascending (guide, strand, chrom, start, site length) order of the best alignments, goes under
+//   #guideId chrom start end strand kind size index mismatches members sequence
+// kind = plain | DNA | RNA, members = the site's alignments as d:mismatches (e.g. -1:3,0:2,+1:3), sequence = the best
+// alignment's forward-genome bases.  Without -Z every output is what it was.
 // -W table.tsv scores every off-target with a TABLE (vsc_search_summary_table; the CFD form: a product of weights by position,
 // guide base and site base times a weight for the site's PAM letters).  The file holds one entry per line, `j g s w` (0-based
 // read position, guide letter, site letter in read orientation, weight) or `PAM XY w`; '#' starts a comment; the diagonal is 1;
@@ -154,6 +161,8 @@ int main(int argc, char **argv)
         {'Y', "efficiency-model", "Path to an on-target efficiency model (.tsv/.txt; lines shape, link, intercept, gc_range, mono, di, gc): "
                                   "adds the columns efficiencyLinear efficiency to the -L file (needs -E, one device)", false},
         {'y', "min-efficiency", "Keep only the -E candidates whose efficiency predictor is defined and >= this value, linear domain (needs -Y)", false},
+        {'Z', "sites", "Path to the TSV file of the cut sites (.tsv/.txt): the plain and the bulged alignments collapsed per PAM-side end; "
+                       "adds the columns siteCount siteBulgeOnly; needs -u", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -468,6 +477,13 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    const bool sited = opts[35].set;
+    const std::string sites_path = opts[35].value;
+    if (sited && (!bulged || !has_extension(sites_path, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: -Z lists the cut sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
+        return 1;
+    }
+
     // -W: the score table
     const bool tabled = opts[32].set;
     if (tabled && !has_extension(opts[32].value, {"tsv", "txt"})) {
@@ -489,6 +505,8 @@ int main(int argc, char **argv)
     vsc_eff_model *eff_model = nullptr;
     vsc_genome *genome = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
+    vsc_hits *site_plain = nullptr;
+    vsc_sites *sites = nullptr;
     vsc_genome *win_genome = nullptr;
     vsc_windows *windows = nullptr;
     vsc_variant_map *vmap = nullptr;
@@ -807,7 +825,14 @@ int main(int argc, char **argv)
         }
         std::vector<vsc_bulge_summary> bulge_rows(bulged ? codes.size() : 0);
         if (bulged) {
-            st = vsc_search_bulges(ctx, genome, codes.data(), n_codes, &p, &bp, opts[31].set ? &bulge_hits : nullptr, bulge_rows.data());
+            st = vsc_search_bulges(ctx, genome, codes.data(), n_codes, &p, &bp, opts[31].set || sited ? &bulge_hits : nullptr, bulge_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+        std::vector<vsc_site_summary> site_rows(sited ? codes.size() : 0);
+        if (sited) {  // the plain records kept on the device beside the bulged ones, collapsed where they lie
+            const vsc_site_params sp{VSC_READ_LEN, VSC_SITE_ANCHOR_END, {0, 0}};
+            st = vsc_search(ctx, genome, codes.data(), n_codes, &p, &site_plain);
+            if (st == VSC_OK) st = vsc_hits_sites(ctx, site_plain, bulge_hits, n_codes, &sp, &sites, site_rows.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         }
         // the enabled bulge classes in the rows' order (ascending site length) and their column prefixes
@@ -839,6 +864,7 @@ int main(int argc, char **argv)
             for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
                 for (long k = 0; bulge_on[c] && k <= mm; ++k) text += std::string("\t") + kBulgeClass[c] + "mm" + std::to_string(k);
         }
+        if (sited) text += "\tsiteCount\tsiteBulgeOnly";
         text += '\n';
         char buf[64];
         for (size_t i = 0; i < sum.size(); ++i) {
@@ -900,6 +926,7 @@ int main(int argc, char **argv)
                 for (int c = 0; c < VSC_BULGE_CLASSES; ++c)
                     for (long k = 0; bulge_on[c] && k <= mm; ++k) text += '\t' + std::to_string(b.count[c][k]);
             }
+            if (sited) text += '\t' + std::to_string(site_rows[i].sites) + '\t' + std::to_string(site_rows[i].bulge_only);
             text += '\n';
         }
         if (opts[5].set) {
@@ -974,7 +1001,7 @@ int main(int argc, char **argv)
             out.close();
             if (!out) throw std::runtime_error("Could not write the -T file.");
         }
-        if (bulge_hits) {
+        if (bulge_hits && opts[31].set) {
             const vsc_bulge_hit *rec = nullptr;
             if (vsc_bulge_hits_data(bulge_hits, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_bulge_hits_count(bulge_hits);
@@ -996,6 +1023,11 @@ int main(int argc, char **argv)
             out << list;
             out.close();
             if (!out) throw std::runtime_error("Could not write the -U file.");
+        }
+        if (sited) {
+            const vsc_site *rec = nullptr;
+            if (vsc_sites_data(sites, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            write_sites(sites_path, "-Z", rec, vsc_sites_count(sites), VSC_READ_LEN, ids, ix);
         }
         if (pairing) {
             // the pairs among the guides' loci, then one search that keeps the records and the join over them on the device
@@ -1047,6 +1079,8 @@ int main(int argc, char **argv)
     vsc_eff_model_free(eff_model);
     if (pair_hits) vsc_hits_free(pair_hits);
     vsc_bulge_hits_free(bulge_hits);
+    vsc_sites_free(sites);
+    if (site_plain) vsc_hits_free(site_plain);
     vsc_guides_free(found);
     vsc_regions_free(regions);
     vsc_regions_free(targets);

@@ -11,6 +11,12 @@
 // lists the sites in ascending (guide, strand, chrom, start, site length) order under guide_summary -U's columns
 //   #guideId chrom start end strand kind size index mismatches sequence
 // Without -u every output is what it was.
+// -Z sites.tsv (needs -u, as -U) collapses the plain and the bulged alignments into CUT SITES on the device
+// (vsc_pattern_hits_sites): one record per (guide, strand, chrom, PAM-side end) - the site's 3' end in read orientation when the
+// -p protospacer starts the pattern, its 5' end when it ends the pattern (Cas12a) - with its best alignment.  The -O summary
+// gains, behind all other columns, siteCount siteBulgeOnly; the listing goes under guide_summary -Z's columns
+//   #guideId chrom start end strand kind size index mismatches members sequence
+// Without -Z every output is what it was.
 // -Y model.tsv (needs -E) scores every found guide's ON-TARGET EFFICIENCY with a linear position-specific model
 // (vsc_pattern_guides_efficiency; the file is what varscot_amd.EfficiencyModel.to_tsv writes, tools/README.md; its site_len
 // must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
@@ -192,6 +198,8 @@ int main(int argc, char **argv)
                              "columns tableScoreSum tableSpecScore tablePositive, -T the column tableScore", false},
         {'K', "top", "With -W: list the K best hits of every guide by table score in the -T file (default: no limit)", false},
         {'S', "min-score", "With -W: list only hits with a table score >= this value, 0 .. 1, in the -T file (default: no floor)", false},
+        {'Z', "sites", "Path to the TSV file of the cut sites (.tsv/.txt): the plain and the bulged alignments collapsed per PAM-side end; "
+                       "-O gains siteCount siteBulgeOnly; needs -u and a -p protospacer at one end of the pattern", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -221,7 +229,8 @@ int main(int argc, char **argv)
         return 1;
     }
     const bool bulged = opts[14].set;
-    if (!enumerate && !opts[5].set && !opts[6].set && !(bulged && opts[15].set)) {
+    const bool sited = opts[21].set;
+    if (!enumerate && !opts[5].set && !opts[6].set && !(bulged && (opts[15].set || sited))) {
         std::fprintf(stderr, "%s: give -O, -T or both\n", argv[0]);
         return 1;
     }
@@ -320,6 +329,19 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "%s: -U lists the bulged sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
         return 1;
     }
+    vsc_site_params sp{};
+    if (sited) {
+        if (!bulged || !has_extension(opts[21].value, {"tsv", "txt"})) {
+            std::fprintf(stderr, "%s: -Z lists the cut sites of -u in a .tsv/.txt file: give -u\n", argv[0]);
+            return 1;
+        }
+        if (bp.proto_start != 0 && bp.proto_start + bp.proto_len != pattern.size()) {
+            std::fprintf(stderr, "%s: -Z: the -p protospacer must start or end the pattern (the other end is the sites' fixed end)\n", argv[0]);
+            return 1;
+        }
+        sp.len = (uint32_t)pattern.size();
+        sp.anchor = bp.proto_start == 0 ? VSC_SITE_ANCHOR_END : VSC_SITE_ANCHOR_START;
+    }
     // -Y / -y: the efficiency model of the found guides
     const bool efficient = opts[16].set;
     double min_eff = 0.0;
@@ -406,6 +428,8 @@ int main(int argc, char **argv)
     vsc_pattern_hits *hits = nullptr;
     vsc_pattern_guides *found = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
+    vsc_pattern_hits *site_plain = nullptr;
+    vsc_sites *sites = nullptr;
     vsc_eff_model *eff_model = nullptr;
     vsc_pattern_table *table = nullptr;
     int rc = 1;
@@ -524,7 +548,15 @@ int main(int argc, char **argv)
         if (bulged) {
             bp.max_mismatches = (uint32_t)mm;
             st = vsc_search_pattern_bulges(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &bp,
-                                           opts[15].set ? &bulge_hits : nullptr, bulge_rows.data());
+                                           opts[15].set || sited ? &bulge_hits : nullptr, bulge_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
+        std::vector<vsc_site_summary> site_rows(sited ? guides.size() : 0);
+        if (sited) {  // all plain records kept on the device beside the bulged ones, collapsed where they lie
+            vsc_pattern_params p{};
+            p.max_mismatches = (uint32_t)mm;
+            st = vsc_search_pattern(ctx, genome, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, &site_plain, nullptr);
+            if (st == VSC_OK) st = vsc_pattern_hits_sites(ctx, site_plain, bulge_hits, (uint32_t)guides.size(), &sp, &sites, site_rows.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         }
 
@@ -539,6 +571,7 @@ int main(int argc, char **argv)
                     for (long k = 0; bulge_on[c] && k <= mm; ++k) out << '\t' << kBulgeClass[c] << "mm" << k;
             }
             if (tabled) out << "\ttableScoreSum\ttableSpecScore\ttablePositive";
+            if (sited) out << "\tsiteCount\tsiteBulgeOnly";
             out << '\n';
             for (size_t g = 0; g < guides.size(); ++g) {
                 uint64_t total = 0;
@@ -560,6 +593,7 @@ int main(int argc, char **argv)
                     std::snprintf(buf, sizeof buf, "\t%.0f", std::floor(vsc_table_specificity(table_rows[g].score_sum) + 0.5));
                     out << buf << '\t' << table_rows[g].positive;
                 }
+                if (sited) out << '\t' << site_rows[g].sites << '\t' << site_rows[g].bulge_only;
                 out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[5].value);
@@ -598,7 +632,14 @@ int main(int argc, char **argv)
             out << text;
             if (!out) throw std::runtime_error("Write error on " + opts[6].value);
         }
-        if (bulge_hits) {
+        if (sited) {
+            const vsc_site *rec = nullptr;
+            if (vsc_sites_data(sites, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<std::string> ids;
+            for (const auto &g : guides) ids.push_back(first_word(g.id));
+            write_sites(opts[21].value, "-Z", rec, vsc_sites_count(sites), len, ids, ix);
+        }
+        if (bulge_hits && opts[15].set) {
             const vsc_bulge_hit *rec = nullptr;
             if (vsc_bulge_hits_data(bulge_hits, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_bulge_hits_count(bulge_hits);
@@ -634,6 +675,8 @@ int main(int argc, char **argv)
     vsc_eff_model_free(eff_model);
     vsc_pattern_table_free(table);
     vsc_bulge_hits_free(bulge_hits);
+    vsc_sites_free(sites);
+    vsc_pattern_hits_free(site_plain);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);
     return rc;

@@ -478,4 +478,42 @@ inline bool has_extension(const std::string &path, std::initializer_list<const c
     return false;
 }
 
+// The -Z listing of guide_summary and pattern_search: the cut sites of vsc_hits_sites / vsc_pattern_hits_sites, one line per
+// site with its best alignment's fields, the members as d:mismatches and the best alignment's forward-genome bases.
+// len = the plain site length, ids = the guides' names, ix = the packed genome (planes, contigs, names).
+template <class Index>
+void write_sites(const std::string &path, const char *option, const vsc_site *rec, uint64_t n, uint32_t len, const std::vector<std::string> &ids,
+                 const Index &ix)
+{
+    std::ofstream out(path);
+    if (!out.is_open()) throw std::runtime_error(std::string("Could not open the ") + option + " path.");
+    out << "#guideId\tchrom\tstart\tend\tstrand\tkind\tsize\tindex\tmismatches\tmembers\tsequence\n";
+    std::string site, text;
+    for (uint64_t j = 0; j < n; ++j) {
+        const vsc_site &s = rec[j];
+        const uint32_t site_len = (uint32_t)((int)len + VSC_BULGE_D(s.info));
+        const std::string &name = ix.names[s.contig];
+        site.assign(site_len, 'N');
+        vsc_unpack_bases(ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs[s.contig].offset + s.pos, site_len, &site[0]);
+        std::string members;
+        for (int d = -2; d <= 2; ++d) {
+            const uint32_t nm = VSC_SITE_MEMBER_NM(s.members, d);
+            if (nm == VSC_SITE_ABSENT) continue;
+            members += (members.empty() ? "" : ",") + std::string(d > 0 ? "+" : "") + std::to_string(d) + ':' + std::to_string(nm);
+        }
+        text += ids[s.guide] + '\t' + name.substr(0, name.find_first_of(" \t")) + '\t' + std::to_string(s.pos) + '\t' + std::to_string(s.pos + site_len) +
+                '\t' + (VSC_BULGE_STRAND(s.info) ? '-' : '+') + '\t' +
+                (VSC_BULGE_SIZE(s.info) == 0 ? "plain" : VSC_BULGE_KIND(s.info) == VSC_BULGE_RNA ? "RNA" : "DNA") + '\t' +
+                std::to_string(VSC_BULGE_SIZE(s.info)) + '\t' + std::to_string(VSC_BULGE_INDEX(s.info)) + '\t' + std::to_string(VSC_BULGE_NM(s.info)) +
+                '\t' + members + '\t' + site + '\n';
+        if (text.size() > (1u << 22)) {
+            out << text;
+            text.clear();
+        }
+    }
+    out << text;
+    out.close();
+    if (!out) throw std::runtime_error(std::string("Could not write the ") + option + " file.");
+}
+
 }  // namespace vsc_host

@@ -35,6 +35,7 @@
 #include "vsc_internal.h"
 #include "vsc_objects.h"
 #include "vsc_pairs.h"
+#include "vsc_sites.h"
 #include "vsc_table.h"
 #include "vsc_varmap.h"
 
@@ -239,7 +240,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
                          &ctx->eff_out})
         b->release();
     ctx->table_serial = 0;
@@ -5538,6 +5539,200 @@ int vsc_score_classify_hits(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hi
     ctx->timing.score_ms = total_ms;
     return VSC_OK;
     });
+}
+
+}  // extern "C"
+
+// ---- cut sites: vsc_hits_sites / vsc_pattern_hits_sites on the device, vsc_sites_collapse* on the host ---------
+namespace {
+
+int site_params_check(const vsc_site_params *p)
+{
+    if (!p || p->reserved[0] || p->reserved[1] || p->anchor > VSC_SITE_ANCHOR_START) return VSC_ERR_INVALID;
+    return p->len >= VSC_PATTERN_MIN_LEN && p->len <= VSC_PATTERN_MAX_LEN ? VSC_OK : VSC_ERR_INVALID;
+}
+
+// The definition on host arrays, by vsc_sites.h's gather: the flags of both lists, the survivors in front of every record, and
+// for every best alignment the rank the write pass of vsc_sites.hip gives it.
+template <int kPlain>
+int sites_collapse_host(const void *plain, uint64_t n_plain, const vsc_bulge_hit *bulged, uint64_t n_bulged, uint32_t n_guides,
+                        const vsc_site_params *p, vsc_site *sites, uint64_t capacity, uint64_t *n_sites, vsc_site_summary *rows)
+{
+    if (n_sites) *n_sites = 0;
+    if (site_params_check(p) != VSC_OK || (n_plain && !plain) || (n_bulged && !bulged) || (!plain && !bulged) || (!rows && !sites && !n_sites))
+        return VSC_ERR_INVALID;
+    if (n_plain + n_bulged > 0xFFFFFFFFull || n_plain > 0xFFFFFFFFull || n_bulged > 0xFFFFFFFFull) return VSC_ERR_RANGE;
+    return guarded(nullptr, [&]() -> int {
+    const uint32_t np = (uint32_t)n_plain, nb = (uint32_t)n_bulged;
+    auto load = [&](bool in_bulged, uint32_t i) { return in_bulged ? site_load<kSiteBulge>(bulged, i) : site_load<kPlain>(plain, i); };
+    for (int l = 0; l < 2; ++l)
+        for (uint32_t i = 0; i < (l ? nb : np); ++i)
+            if (load(l, i).guide >= n_guides) return VSC_ERR_INVALID;
+    std::vector<uint32_t> row_words;
+    if (rows) row_words.assign((size_t)n_guides * kSiteRowWords, 0u);
+    // before[l][i] = best alignments among records [0, i) of list l
+    std::vector<uint32_t> before[2];
+    before[0].assign((size_t)np + 1, 0u);
+    before[1].assign((size_t)nb + 1, 0u);
+    for (int l = 0; l < 2; ++l)
+        for (uint32_t i = 0; i < (l ? nb : np); ++i) {
+            const SiteAln x = load(l, i);
+            const SiteView v = site_gather<kPlain>(plain, np, bulged, nb, l, i, x, p->len, p->anchor);
+            before[l][i + 1] = before[l][i] + (v.best == site_rank(x.d, x.nm) ? 1u : 0u);
+            if (rows) ++row_words[(size_t)x.guide * kSiteRowWords + kSiteRowAlignments];
+        }
+    const uint64_t total = (uint64_t)before[0][np] + before[1][nb];
+    if (n_sites) *n_sites = total;
+    const bool write = sites && total <= capacity;
+    for (int l = 0; l < 2; ++l)
+        for (uint32_t i = 0; i < (l ? nb : np); ++i) {
+            if (before[l][i + 1] == before[l][i]) continue;
+            const SiteAln x = load(l, i);
+            const SiteView v = site_gather<kPlain>(plain, np, bulged, nb, l, i, x, p->len, p->anchor);
+            if (write) {
+                const uint32_t j = site_other_below<kPlain>(plain, np, bulged, nb, l, x);
+                site_record(x, i, v, p->len, p->anchor, (uint32_t *)&sites[(size_t)before[l][i] + before[l ^ 1][j]]);
+            }
+            if (rows) {
+                uint32_t *row = &row_words[(size_t)x.guide * kSiteRowWords];
+                ++row[kSiteRowSites];
+                ++row[site_row_count_word(x)];
+                if (site_bulge_only(v)) ++row[kSiteRowBulgeOnly];
+            }
+        }
+    if (rows && n_guides) std::memcpy(rows, row_words.data(), row_words.size() * sizeof(uint32_t));
+    return sites && !write ? VSC_ERR_RANGE : VSC_OK;
+    });
+}
+
+// The device call behind both entry points: d_plain / n_plain = the plain result's records (kind = kSiteHit / kSitePattern).
+int hits_sites_device(vsc_ctx *ctx, const char *who, int kind, const void *d_plain, uint64_t n_plain, vsc_bulge_hits *bulged,
+                      uint32_t n_guides, const vsc_site_params *p, vsc_sites **out, vsc_site_summary *rows)
+{
+    ctx->err.clear();
+    if (site_params_check(p) != VSC_OK)
+        return fail_in(ctx, VSC_ERR_INVALID, who, "len in 16..32, a known anchor and zeroed reserved fields are needed");
+    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, who, "neither records nor rows are asked for");
+    const uint64_t n_bulged = bulged ? bulged->n : 0;
+    if (n_plain + n_bulged > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^32 - 1 alignments");
+    if (rows && n_guides) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_site_summary));
+    std::unique_ptr<vsc_sites, int (*)(vsc_sites *)> res(nullptr, object_free<vsc_sites>);
+    if (out) {
+        res.reset(new (std::nothrow) vsc_sites());
+        if (!res) return fail_in(ctx, VSC_ERR_NOMEM, who, "out of host memory");
+        res->ctx = ctx;
+    }
+    SiteArgs a{};
+    a.plain = d_plain;
+    a.bulged = n_bulged ? bulged->storage.p : nullptr;
+    a.n_plain = (uint32_t)n_plain;
+    a.n_bulged = (uint32_t)n_bulged;
+    a.tiles_plain = (uint32_t)((n_plain + kSiteTile - 1) / kSiteTile);
+    a.tiles_bulged = (uint32_t)((n_bulged + kSiteTile - 1) / kSiteTile);
+    a.n_guides = n_guides;
+    a.len = p->len;
+    a.anchor = p->anchor;
+    const uint32_t n_tiles = a.tiles_plain + a.tiles_bulged;
+    if (n_tiles) {
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        // scratch, 256-byte aligned parts: [ballots][offsets + total, then the invalid flag][rows][counts]
+        const size_t off_at = round256((size_t)n_tiles * sizeof(unsigned long long));
+        const size_t flag_at = off_at + ((size_t)n_tiles + 1) * sizeof(unsigned long long);
+        const size_t rows_at = round256(flag_at + 8);
+        const size_t row_bytes = rows ? (size_t)n_guides * sizeof(vsc_site_summary) : 0;
+        const size_t count_at = rows_at + round256(row_bytes);
+        VSC_HIP(ctx, ctx->sites_tabs.ensure(count_at + (size_t)n_tiles * sizeof(uint32_t)));
+        char *base = (char *)ctx->sites_tabs.p;
+        a.ballot = (unsigned long long *)base;
+        a.tile_off = (const unsigned long long *)(base + off_at);
+        a.invalid = (uint32_t *)(base + flag_at);
+        a.rows = row_bytes ? (uint32_t *)(base + rows_at) : nullptr;
+        a.tile_count = (uint32_t *)(base + count_at);
+        VSC_HIP(ctx, hipMemsetAsync(base + flag_at, 0, rows_at + row_bytes - flag_at, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+        VSC_HIP(ctx, launch_site_flag(a, kind, ctx->n_cus, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(a.tile_count, n_tiles, (unsigned long long *)(base + off_at), ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+        // one read-back: the total (it sizes the result) with the invalid flag behind it
+        unsigned long long back[2] = {0, 0};
+        VSC_HIP(ctx, hipMemcpyAsync(back, a.tile_off + n_tiles, sizeof back, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if ((uint32_t)back[1]) return fail_in(ctx, VSC_ERR_INVALID, who, "a record's guide is not below n_guides");
+        a.n_sites = back[0];
+        if (out && a.n_sites) {
+            VSC_HIP(ctx, res->storage.ensure((size_t)a.n_sites * sizeof(vsc_site)));
+            a.sites = (uint4 *)res->storage.p;
+            res->n = a.n_sites;
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        if (a.sites || a.rows) VSC_HIP(ctx, launch_site_write(a, kind, ctx->n_cus, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        if (a.rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float ms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+        ctx->sites_ms[0] = ms;
+        VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        ctx->sites_ms[1] = ms;
+    }
+    if (out) *out = res.release();
+    return VSC_OK;
+}
+
+template <class Plain>
+int hits_sites_entry(vsc_ctx *ctx, const char *who, int kind, Plain *plain, const void *d_plain, vsc_bulge_hits *bulged, uint32_t n_guides,
+                     const vsc_site_params *p, vsc_sites **out, vsc_site_summary *rows)
+{
+    if (out) *out = nullptr;
+    if (!ctx) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    if (!plain && !bulged) return fail_in(ctx, VSC_ERR_INVALID, who, "neither plain nor bulged records");
+    if ((plain && plain->ctx != ctx) || (bulged && bulged->ctx != ctx)) return fail_in(ctx, VSC_ERR_INVALID, who, "a result of another context");
+    return hits_sites_device(ctx, who, kind, plain && plain->n ? d_plain : nullptr, plain ? plain->n : 0, bulged, n_guides, p, out, rows);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_hits_sites(vsc_ctx *ctx, vsc_hits *plain, vsc_bulge_hits *bulged, uint32_t n_guides, const vsc_site_params *params, vsc_sites **out,
+                   vsc_site_summary *rows)
+{
+    return hits_sites_entry(ctx, "vsc_hits_sites", kSiteHit, plain, plain ? (const void *)plain->d_records : nullptr, bulged, n_guides, params, out,
+                            rows);
+}
+
+int vsc_pattern_hits_sites(vsc_ctx *ctx, vsc_pattern_hits *plain, vsc_bulge_hits *bulged, uint32_t n_guides, const vsc_site_params *params,
+                           vsc_sites **out, vsc_site_summary *rows)
+{
+    return hits_sites_entry(ctx, "vsc_pattern_hits_sites", kSitePattern, plain, plain ? (const void *)plain->storage.p : nullptr, bulged, n_guides,
+                            params, out, rows);
+}
+
+uint64_t vsc_sites_count(const vsc_sites *sites) { return sites ? sites->n : 0; }
+int vsc_sites_data(vsc_sites *sites, const vsc_site **out) { return record_list_data(sites, out); }
+const void *vsc_sites_data_dev(const vsc_sites *sites) { return record_list_data_dev(sites); }
+int vsc_sites_free(vsc_sites *sites) { return object_free(sites); }
+
+int vsc_sites_collapse(const vsc_hit *plain, uint64_t n_plain, const vsc_bulge_hit *bulged, uint64_t n_bulged, uint32_t n_guides,
+                       const vsc_site_params *params, vsc_site *sites, uint64_t capacity, uint64_t *n_sites, vsc_site_summary *rows)
+{
+    return sites_collapse_host<kSiteHit>(plain, n_plain, bulged, n_bulged, n_guides, params, sites, capacity, n_sites, rows);
+}
+
+int vsc_sites_collapse_pattern(const vsc_pattern_hit *plain, uint64_t n_plain, const vsc_bulge_hit *bulged, uint64_t n_bulged, uint32_t n_guides,
+                               const vsc_site_params *params, vsc_site *sites, uint64_t capacity, uint64_t *n_sites, vsc_site_summary *rows)
+{
+    return sites_collapse_host<kSitePattern>(plain, n_plain, bulged, n_bulged, n_guides, params, sites, capacity, n_sites, rows);
+}
+
+int vsc_debug_sites_ms(const vsc_ctx *ctx, double *flag_scan_ms, double *write_ms)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    if (flag_scan_ms) *flag_scan_ms = ctx->sites_ms[0];
+    if (write_ms) *write_ms = ctx->sites_ms[1];
+    return VSC_OK;
 }
 
 }  // extern "C"

@@ -158,6 +158,10 @@ struct vsc_ctx {
     // the table's serial number)
     vsc::DeviceBuf pattern_table_buf;
     uint64_t pattern_table_serial = 0;  // 0: none resident
+    // vsc_hits_sites: the tiles' ballots, their offsets, the invalid flag, the rows and the tiles' counts; the milliseconds of
+    // the call's two stages (flag pass + scan, write pass: vsc_debug_sites_ms - vsc_ctx_timing is not the call's to change)
+    vsc::DeviceBuf sites_tabs;
+    double sites_ms[2] = {0, 0};
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -293,12 +297,14 @@ template <class Rec> struct RecordList {
 
 }  // namespace vsc
 
-// The four handles of include/varscot_hip.h behind which these stand: the candidates of vsc_guides_enumerate and of
-// vsc_guides_enumerate_pattern, the records of vsc_search_bulges (and vsc_search_pattern_bulges) and of vsc_search_pattern.
+// The five handles of include/varscot_hip.h behind which these stand: the candidates of vsc_guides_enumerate and of
+// vsc_guides_enumerate_pattern, the records of vsc_search_bulges (and vsc_search_pattern_bulges), of vsc_search_pattern and of
+// vsc_hits_sites.
 struct vsc_guides : vsc::GuideList {};
 struct vsc_pattern_guides : vsc::GuideList {};
 struct vsc_bulge_hits : vsc::RecordList<vsc_bulge_hit> {};
 struct vsc_pattern_hits : vsc::RecordList<vsc_pattern_hit> {};
+struct vsc_sites : vsc::RecordList<vsc_site> {};
 
 namespace vsc {
 // A genome object that only carries the contig table (no planes, nothing to search): what vsc_hits_merge_packed
