@@ -744,7 +744,8 @@ int vsc_pattern_bulge_align(const char *pattern, const char *guide, const char *
  * sites.  More sites than capacity when sites != NULL: VSC_ERR_RANGE, nothing is written to sites (rows and *n_sites are
  * valid).  The refusals of the device calls apply.
  * Not provided: merging sites whose anchors merely lie close (CRISPRme's 3-bp window: it needs chaining over anchor order),
- * scores for bulged alignments, leaving out the on-target, a vsc_multi_* entry point.
+ * leaving out the on-target, a vsc_multi_* entry point.  Scores for bulged alignments and for sites: since added,
+ * vsc_bulge_hits_table / vsc_sites_table below.
  */
 #define VSC_SITE_ANCHOR_END 0u
 #define VSC_SITE_ANCHOR_START 1u
@@ -1530,6 +1531,112 @@ int vsc_search_pattern_table(vsc_ctx *ctx, const vsc_genome *genome, const char 
 int vsc_pattern_hits_scores(vsc_pattern_hits *hits, const uint32_t **fixed);
 /* Device pointer (valid until vsc_pattern_hits_free); NULL when the result is empty or not a scored one. */
 const void *vsc_pattern_hits_scores_dev(const vsc_pattern_hits *hits);
+
+/* ---- table scores for bulged alignments and cut sites: per record, per guide, top-K sites --------------------- */
+/*
+ * The score above over everything the searches report: the bulged alignments of vsc_search_bulges /
+ * vsc_search_pattern_bulges and the cut sites of vsc_hits_sites / vsc_pattern_hits_sites.  CRISPRitz and CRISPRme score every
+ * bulged alignment, keep the best-scoring alignment of each cluster and rank the clusters; this is that listing's score,
+ * rows and cut.  The library ships no weights.
+ *
+ * TABLE   vsc_bulge_table, host-only and immutable, with a process-wide serial number like the other tables.  Built from a
+ *         vsc_pattern_table (its shape and weights are COPIED: the new table does not depend on the old one's lifetime) plus
+ *         two arrays of doubles, dna[ps_len][4] and rna[ps_len][4].  Write a = ps_start, e = ps_start + ps_len.
+ *         dna[i][s] is the weight of one unpaired site base s (read orientation, A 0 C 1 G 2 T 3) when the bulge lies in
+ *           front of read position a + i.
+ *         rna[i][g] is the weight of the unpaired guide base g at read position a + i.
+ *         Every weight is finite and lies in [0, 1]; ps_len >= 4.  Anything else: VSC_ERR_INVALID.
+ *         Row 0 of dna and rows 0 and ps_len - 1 of rna are never read; they are still validated.
+ *         With L = 23, protospacer (0, 20), pam_pos {21, 22} and a vsc_score_table's weights this is the SpCas9 form.
+ * SCORE   of a bulged alignment: guide G (L IUPAC letters), site s (L + d letters in read orientation), d in {-2, -1, +1, +2},
+ *         split index i = the record's VSC_BULGE_INDEX as vsc_pattern_bulge_align defines it.  The paired site q:
+ *           DNA bulge (b = d > 0):   q[j] = s[j] for j < i, q[j] = s[j + b] for j >= i.
+ *           RNA bulge (b = -d > 0):  q[j] = s[j] for j < i, q[j] = s[j - b] for j >= i + b; positions [i, i + b) carry no letter.
+ *         Then, in this order:
+ *           1. x = the SCORE of vsc_search_pattern_table of G against q, the unpaired positions taking no part: the
+ *              mismatch weights in ascending position, then the PAM weight of q at pam_pos.
+ *           2. DNA bulge: for t = 0 .. b - 1 in this order, x = x * dna[i - a][s[i + t]].
+ *           3. RNA bulge: for t = 0 .. b - 1 in this order, if G[i + t] is one of A, C, G, T then
+ *              x = x * rna[i + t - a][G[i + t]].  A degenerate letter takes no part, as everywhere else.
+ *         fp64, one rounding per multiplication, no contraction.  f = rint(x * 2^30) as above, f <= 2^30.
+ *         The score belongs to the alignment the search REPORTS: the smallest i that reaches NM.  It is not a maximum over
+ *         the split points.
+ *         With every dna and rna weight equal to 1.0, f is vsc_pattern_table_score's f of (G, q), bit for bit.
+ *         A record outside the definition scores f = 0 and nothing is read outside an array: a guide index >= n_guides, a
+ *         size of 0 or 3, L + d outside 16..32, i outside a + 1 .. e - 1 (RNA: i + b <= e - 1), a contig index >= the
+ *         genome's contig count, a site that leaves its contig, a site that touches a plane word outside the words the
+ *         genome was loaded with.  A span of 34 letters at bit offset 31 touches three 32-base words; every one of them is
+ *         checked.  A shard is loaded with one halo word behind its own words: a record that needs a second one scores 0 on
+ *         that shard.
+ * SITE    A vsc_site names guide, strand, contig, anchor and, in members, which d in -2 .. +2 are present.  In read
+ *         orientation every member's letters are the L + d letters that end at the anchor (VSC_SITE_ANCHOR_END) or begin
+ *         there (VSC_SITE_ANCHOR_START); all lie inside one span of L + (the largest d present) letters, fetched once.  For
+ *         each present member (NM, i) is recomputed - vsc_pattern_bulge_align's walk, the plain compare for d = 0 - and the
+ *         member scored as above (d = 0: the SCORE of vsc_search_pattern_table).  No record list is looked up: the site
+ *         record, the planes and the guide are enough.
+ *         vsc_site_score { best, top, top_d, reserved }, 16 bytes: best = f of the record's best alignment, top = the
+ *         largest f among the members, top_d = d + 2 of the member that attains it - on equal f the member that is smaller
+ *         under the site's order (NM + |d|, |d|, DNA before RNA).  A site outside the definition (as above, or whose best
+ *         alignment is not among its members): all zero.
+ * ROWS    vsc_guide_table_row per guide.  vsc_bulge_hits_table: score_sum = sum of f, positive = records with f > 0,
+ *         positive_nm[k] = those by the record's NM (clamped to 8).  vsc_sites_table: score_sum = sum of top, positive = sites
+ *         with top > 0, positive_nm[k] = those by the best alignment's NM (clamped to 8), over ALL sites, before any
+ *         selection.  vsc_table_specificity(score_sum) applies as it does above: a bulge-aware specificity.
+ * SELECT  vsc_pattern_select as it is, with the key top: per guide the survivors are the sites with top >= min_score, of
+ *         those the first top_k (0: all) are kept under the ranking top descending, then record order; the result stays in
+ *         record order.  NULL or { 0, 0 } returns every site.  A non-zero reserved field: VSC_ERR_INVALID.
+ *
+ * vsc_bulge_table_score: one guide (len IUPAC letters) against one site (len + d letters of ACGT in read orientation) on the
+ * host, with the very functions the kernels call; d = 0 gives the plain score (*nm = the mismatches, *index = 0), otherwise
+ * (*nm, *index) are vsc_pattern_bulge_align's walk over the table's protospacer.  A d outside -2 .. 2, len + d outside
+ * 16..32 or a letter that is not ACGT: VSC_ERR_INVALID.  All four outputs are optional.
+ * vsc_bulge_hits_table scores the records of a bulge result where they lie: fixed (host, one word per record) or rows may be
+ * NULL, both NULL: VSC_ERR_INVALID.  vsc_sites_table scores the sites of a result of vsc_hits_sites /
+ * vsc_pattern_hits_sites: *out is a NEW vsc_sites that holds the survivors and their score records (vsc_sites_scores / _dev;
+ * VSC_ERR_INVALID / NULL on an unscored result); the input is not modified.  out or rows may be NULL, both NULL:
+ * VSC_ERR_INVALID.  For both: guides are n_guides * len IUPAC letters (a caller with vsc_pack_guide codes spells them first);
+ * a table whose len is not len, params->len other than len, a result or a genome of another context: VSC_ERR_INVALID; an
+ * empty input returns VSC_OK and launches nothing; the inputs and vsc_ctx_timing stay as they are.  The context keeps the
+ * device copy of the table it used last, keyed by the serial number; vsc_ctx_release_scratch gives it back.
+ * Not provided: weights, a maximum over split points, scores of variant-window hits, a vsc_multi_* entry (sites are defined
+ * on merged records).
+ */
+typedef struct vsc_bulge_table vsc_bulge_table;
+typedef struct {
+    uint64_t serial;        /* process-wide number of the table */
+    uint32_t zero_weights;  /* weights that are exactly 0, dna and rna included */
+    uint32_t reserved;
+    vsc_pattern_table_shape shape;
+} vsc_bulge_table_stats;
+typedef struct {
+    uint32_t best;     /* f of the record's best alignment */
+    uint32_t top;      /* the largest f among the members */
+    uint32_t top_d;    /* d + 2 of the member that attains top */
+    uint32_t reserved; /* 0 */
+} vsc_site_score;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_bulge_table_stats) == 48, "vsc_bulge_table_stats layout");
+static_assert(sizeof(vsc_site_score) == 16, "vsc_site_score layout");
+#else
+_Static_assert(sizeof(vsc_bulge_table_stats) == 48, "vsc_bulge_table_stats layout");
+_Static_assert(sizeof(vsc_site_score) == 16, "vsc_site_score layout");
+#endif
+int vsc_bulge_table_build(const vsc_pattern_table *base, const double *dna /* [ps_len][4] */, const double *rna /* [ps_len][4] */,
+                          vsc_bulge_table **out);
+int vsc_bulge_table_free(vsc_bulge_table *table);
+int vsc_bulge_table_info(const vsc_bulge_table *table, vsc_bulge_table_stats *out);
+int vsc_bulge_table_score(const vsc_bulge_table *table, const char *guide, const char *site_text /* len + d letters, read orientation */,
+                          int d, uint32_t *nm, uint32_t *index, double *score, uint32_t *fixed);
+int vsc_bulge_hits_table(vsc_ctx *ctx, const vsc_genome *genome, vsc_bulge_hits *hits, const char *guides /* n_guides * len letters */,
+                         uint32_t n_guides, uint32_t len, const vsc_bulge_table *table,
+                         uint32_t *fixed /* host, one per record, may be NULL */, vsc_guide_table_row *rows /* may be NULL */);
+int vsc_sites_table(vsc_ctx *ctx, const vsc_genome *genome, vsc_sites *sites, const vsc_site_params *params, const char *guides,
+                    uint32_t n_guides, uint32_t len, const vsc_bulge_table *table, const vsc_pattern_select *select /* may be NULL */,
+                    vsc_sites **out /* may be NULL */, vsc_guide_table_row *rows /* may be NULL */);
+/* Host copy of the score records (made on first use; valid until vsc_sites_free). */
+int vsc_sites_scores(vsc_sites *sites, const vsc_site_score **out);
+/* Device pointer (valid until vsc_sites_free); NULL when the result is empty or not a scored one. */
+const void *vsc_sites_scores_dev(const vsc_sites *sites);
 
 /* ---- on-target efficiency of candidate guides (linear position-specific models) ------------------------------ */
 /*

@@ -67,6 +67,18 @@ int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_lo
  * tools/sites_bench.py reads what its kernels took. */
 int vsc_debug_sites_ms(const vsc_ctx *ctx, double *flag_scan_ms, double *write_ms);
 
+/* The device milliseconds of the context's last vsc_sites_table / vsc_bulge_hits_table, between HIP events on its stream: the
+ * score kernel, the selection's bounds and radix select, and its walk (any may be NULL; vsc_bulge_hits_table and a call
+ * without a selection leave the last two 0).  The calls leave vsc_ctx_timing alone; tools/site_table_bench.py reads this. */
+int vsc_debug_site_table_ms(const vsc_ctx *ctx, double *score_ms, double *select_ms, double *walk_ms);
+
+/* A vsc_bulge_hits / vsc_sites object over n records copied from the host as they are - for the tests of vsc_bulge_hits_table
+ * and vsc_sites_table: lists of chosen lengths, and records that no search returns (a guide index too large, a split point
+ * outside the protospacer, a position behind its contig), which those calls must score 0 without reading outside an array.
+ * Nothing is verified.  Freed with vsc_bulge_hits_free / vsc_sites_free. */
+int vsc_debug_bulge_hits_from_host(vsc_ctx *ctx, const vsc_bulge_hit *records, uint64_t n, vsc_bulge_hits **out);
+int vsc_debug_sites_from_host(vsc_ctx *ctx, const vsc_site *records, uint64_t n, vsc_sites **out);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

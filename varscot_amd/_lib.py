@@ -257,7 +257,16 @@ class PatternSelect(C.Structure):
     _fields_ = [("top_k", C.c_uint32), ("min_score", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class BulgeTableStats(C.Structure):
+    """vsc_bulge_table_stats"""
+    _fields_ = [("serial", C.c_uint64), ("zero_weights", C.c_uint32), ("reserved", C.c_uint32), ("shape", PatternTableShape)]
+
+
+# vsc_site_score (vsc_sites_table): f of the record's best alignment, the largest f among the members, d + 2 of that member
+SITE_SCORE_DTYPE = np.dtype([("best", "<u4"), ("top", "<u4"), ("top_d", "<u4"), ("reserved", "<u4")])
+
 assert C.sizeof(PatternTableShape) == 32 and C.sizeof(PatternTableStats) == 48 and C.sizeof(PatternSelect) == 16
+assert C.sizeof(BulgeTableStats) == 48 and SITE_SCORE_DTYPE.itemsize == 16
 
 EFF_IDENTITY, EFF_LOGISTIC = 0, 1  # VSC_EFF_*
 
@@ -463,6 +472,16 @@ SYMBOLS = [
     ("vsc_pattern_hits_scores", C.c_int, [_vp, C.POINTER(_vp)]),
     ("vsc_pattern_hits_scores_dev", _vp, [_vp]),
     ("vsc_multi_search_summary_table", C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, _vp, _vp, _vp]),
+    ("vsc_bulge_table_build", C.c_int, [_vp, _vp, _vp, C.POINTER(_vp)]),
+    ("vsc_bulge_table_free", C.c_int, [_vp]),
+    ("vsc_bulge_table_info", C.c_int, [_vp, C.POINTER(BulgeTableStats)]),
+    ("vsc_bulge_table_score", C.c_int, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("vsc_bulge_hits_table", C.c_int, [_vp, _vp, _vp, C.c_char_p, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    ("vsc_sites_table", C.c_int, [_vp, _vp, _vp, C.POINTER(SiteParams), C.c_char_p, C.c_uint32, C.c_uint32, _vp, C.POINTER(PatternSelect),
+                                  C.POINTER(_vp), _vp]),
+    ("vsc_sites_scores", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("vsc_sites_scores_dev", _vp, [_vp]),
     ("vsc_eff_model_build", C.c_int, [C.POINTER(EffShape), C.c_double, _vp, _vp, _vp, C.POINTER(_vp)]),
     ("vsc_eff_model_free", C.c_int, [_vp]),
     ("vsc_eff_model_info", C.c_int, [_vp, C.POINTER(EffModelStats)]),
@@ -485,6 +504,9 @@ DEBUG_SYMBOLS = [
     ("vsc_multi_create_debug", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(MultiDebugParams), C.POINTER(_vp)]),
     ("vsc_debug_guides_from_host", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_sites_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("vsc_debug_site_table_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("vsc_debug_bulge_hits_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_debug_sites_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
 ]
 
 _lib = None

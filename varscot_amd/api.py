@@ -520,45 +520,50 @@ class PatternTable:
         `pam_pos p...` (none: no PAM letter is looked at), `pair j g s w` (j the 0-based READ position, g the guide's letter, s
         the site's letter in read orientation), `pam LETTERS w` (one letter per PAM position, '-' when there is none); '#'
         starts a comment.  `shape` comes first.  pair[j][b][b] is 1 and is not written; every other entry must be there."""
-        shape, pam_pos, pair, pam = None, (), None, None
         with open(path) as fh:
-            for n, line in enumerate(fh, 1):
-                f = line.split("#", 1)[0].split()
-                if not f:
-                    continue
-                where = "%s:%d" % (path, n)
-                try:
-                    key, a = f[0], f[1:]
-                    if key != "shape" and shape is None:
-                        raise ValueError("'%s' before the 'shape' line" % key)
-                    if key == "shape" and len(a) == 3 and shape is None:
-                        shape = tuple(int(v) for v in a)
-                        if not 0 < shape[2] <= 32:
-                            raise ValueError("the protospacer has 1..32 positions")
-                        pair = np.full((shape[2], 4, 4), np.nan)
-                        for b in range(4):
-                            pair[:, b, b] = 1.0
-                        pam = np.full(1, np.nan)
-                    elif key == "pam_pos" and len(a) <= 4 and not pam_pos and np.isnan(pam).all():
-                        pam_pos = tuple(int(v) for v in a)
-                        pam = np.full(4 ** len(pam_pos), np.nan)
-                    elif key == "pair" and len(a) == 4:
-                        i = int(a[0]) - shape[1]
-                        if not 0 <= i < shape[2]:
-                            raise ValueError("position %s lies outside the protospacer" % a[0])
-                        pair[i, _base(a[1], where), _base(a[2], where)] = float(a[3])
-                    elif key == "pam" and len(a) == 2:
-                        letters = "" if a[0] == "-" else a[0]
-                        if len(letters) != len(pam_pos):
-                            raise ValueError("'pam' takes one letter per PAM position")
-                        k = 0
-                        for ch in letters:
-                            k = 4 * k + _base(ch, where)
-                        pam[k] = float(a[1])
-                    else:
-                        raise ValueError("unknown key, a line given twice or wrong number of fields: %r" % " ".join(f))
-                except ValueError as e:
-                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+            return cls._from_lines(path, enumerate(fh, 1))
+
+    @classmethod
+    def _from_lines(cls, path, numbered):
+        """from_tsv over (line number, line) pairs of the file `path` (BulgeTable.from_tsv hands over the lines that are not its own)."""
+        shape, pam_pos, pair, pam = None, (), None, None
+        for n, line in numbered:
+            f = line.split("#", 1)[0].split()
+            if not f:
+                continue
+            where = "%s:%d" % (path, n)
+            try:
+                key, a = f[0], f[1:]
+                if key != "shape" and shape is None:
+                    raise ValueError("'%s' before the 'shape' line" % key)
+                if key == "shape" and len(a) == 3 and shape is None:
+                    shape = tuple(int(v) for v in a)
+                    if not 0 < shape[2] <= 32:
+                        raise ValueError("the protospacer has 1..32 positions")
+                    pair = np.full((shape[2], 4, 4), np.nan)
+                    for b in range(4):
+                        pair[:, b, b] = 1.0
+                    pam = np.full(1, np.nan)
+                elif key == "pam_pos" and len(a) <= 4 and not pam_pos and np.isnan(pam).all():
+                    pam_pos = tuple(int(v) for v in a)
+                    pam = np.full(4 ** len(pam_pos), np.nan)
+                elif key == "pair" and len(a) == 4:
+                    i = int(a[0]) - shape[1]
+                    if not 0 <= i < shape[2]:
+                        raise ValueError("position %s lies outside the protospacer" % a[0])
+                    pair[i, _base(a[1], where), _base(a[2], where)] = float(a[3])
+                elif key == "pam" and len(a) == 2:
+                    letters = "" if a[0] == "-" else a[0]
+                    if len(letters) != len(pam_pos):
+                        raise ValueError("'pam' takes one letter per PAM position")
+                    k = 0
+                    for ch in letters:
+                        k = 4 * k + _base(ch, where)
+                    pam[k] = float(a[1])
+                else:
+                    raise ValueError("unknown key, a line given twice or wrong number of fields: %r" % " ".join(f))
+            except ValueError as e:
+                raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
         if shape is None:
             raise ValueError("%s: no 'shape' line" % path)
         missing = int(np.isnan(pair).sum() + np.isnan(pam).sum())
@@ -604,6 +609,122 @@ class PatternTable:
     def close(self):
         if getattr(self, "_h", None):
             lib().vsc_pattern_table_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SITE_SCORE_DTYPE = _lib.SITE_SCORE_DTYPE
+
+
+class BulgeTable:
+    """A table score for bulged alignments and cut sites (vsc_bulge_table): a PatternTable (or a ScoreTable, taken as
+    PatternTable.from_score_table takes it) for the paired positions plus dna[ps_len][4] - the weight of one unpaired SITE base
+    s (read orientation, A 0 C 1 G 2 T 3) when the bulge lies in front of read position ps_start + i - and rna[ps_len][4] - the
+    weight of the unpaired GUIDE base g at read position ps_start + i.  Every weight in [0, 1]; the protospacer has at least
+    four positions.  The base's weights are copied: the BulgeTable does not need it afterwards.  The package ships no table."""
+
+    def __init__(self, base, dna, rna):
+        own = isinstance(base, ScoreTable)
+        pt = PatternTable.from_score_table(base) if own else base
+        try:
+            self.length, self.protospacer, self.pam_positions = pt.length, pt.protospacer, pt.pam_positions
+            self.pair, self.pam = pt.pair.copy(), pt.pam.copy()
+            self.dna = np.ascontiguousarray(dna, dtype=np.float64)
+            self.rna = np.ascontiguousarray(rna, dtype=np.float64)
+            if self.dna.shape != (self.protospacer[1], 4) or self.rna.shape != (self.protospacer[1], 4):
+                raise ValueError("a bulge table is dna[ps_len][4] and rna[ps_len][4]")
+            h = C.c_void_p()
+            self._h = None
+            check(lib().vsc_bulge_table_build(pt._h, ptr(self.dna), ptr(self.rna), C.byref(h)))
+            self._h = h
+        finally:
+            if own:
+                pt.close()
+
+    @classmethod
+    def from_tsv(cls, path, base_path=None):
+        """A table from the text file to_tsv writes: the pattern table's file format (PatternTable.from_tsv) plus lines
+        `dna j s w` and `rna j g w`, j the 0-based READ position, s / g a letter of ACGT; '#' starts a comment.  Every entry
+        of both arrays must be there.  base_path: the pattern table's lines are in that file and `path` holds the dna and rna
+        lines alone (what the tools take as -W and -w)."""
+        lines, extra = [], []
+        with open(path) as fh:
+            for n, line in enumerate(fh, 1):
+                f = line.split("#", 1)[0].split()
+                (extra if f and f[0] in ("dna", "rna") else lines).append((n, line, f))
+        if base_path is None:
+            base = PatternTable._from_lines(path, ((n, line) for n, line, _ in lines))
+        else:
+            for n, _, f in lines:
+                if f:
+                    raise ValueError("%s:%d: unknown key %r (only 'dna' and 'rna' lines)" % (path, n, f[0]))
+            base = PatternTable.from_tsv(base_path)
+        try:
+            a, k = base.protospacer
+            arr = {"dna": np.full((k, 4), np.nan), "rna": np.full((k, 4), np.nan)}
+            for n, _, f in extra:
+                where = "%s:%d" % (path, n)
+                try:
+                    if len(f) != 4:
+                        raise ValueError("'%s' takes a position, a letter and a weight" % f[0])
+                    i = int(f[1]) - a
+                    if not 0 <= i < k:
+                        raise ValueError("position %s lies outside the protospacer" % f[1])
+                    b = _base(f[2], where)
+                    if not np.isnan(arr[f[0]][i, b]):
+                        raise ValueError("a line given twice: %r" % " ".join(f))
+                    arr[f[0]][i, b] = float(f[3])
+                except ValueError as e:
+                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+            missing = int(np.isnan(arr["dna"]).sum() + np.isnan(arr["rna"]).sum())
+            if missing:
+                raise ValueError("%s: %d entries are missing" % (path, missing))
+            return cls(base, arr["dna"], arr["rna"])
+        finally:
+            base.close()
+
+    def to_tsv(self, path, base_path=None):
+        """The dna and rna lines as from_tsv reads them back to the bit.  base_path: where the pattern table's lines go (None:
+        into the same file, in front)."""
+        base = PatternTable(self.length, self.protospacer, self.pair, self.pam_positions, self.pam)
+        try:
+            base.to_tsv(path if base_path is None else base_path)
+        finally:
+            base.close()
+        with open(path, "a" if base_path is None else "w") as fh:
+            fh.write("# bulge weights: dna = an unpaired site base in front of the position, rna = the unpaired guide base at it\n")
+            for key, arr in (("dna", self.dna), ("rna", self.rna)):
+                for i in range(self.protospacer[1]):
+                    for b in range(4):
+                        fh.write("%s\t%d\t%s\t%r\n" % (key, self.protospacer[0] + i, "ACGT"[b], float(arr[i, b])))
+
+    def info(self):
+        st = _lib.BulgeTableStats()
+        check(lib().vsc_bulge_table_info(self._h, C.byref(st)))
+        return {"serial": int(st.serial), "zero_weights": int(st.zero_weights), "length": int(st.shape.len),
+                "protospacer": (int(st.shape.ps_start), int(st.shape.ps_len)),
+                "pam_positions": tuple(int(st.shape.pam_pos[t]) for t in range(st.shape.n_pam))}
+
+    def score(self, guide, site, d, fixed=False):
+        """vsc_bulge_table_score: one guide (IUPAC letters, the table's length) against one site of length + d letters (ACGT,
+        read orientation), d in -2 .. 2; the split point is the smallest that reaches NM.  Returns (nm, index, score), with
+        fixed=True (nm, index, score, rint(score * 2^30)); d = 0: the plain score, index 0."""
+        g = guide if isinstance(guide, bytes) else guide.encode()
+        t = site if isinstance(site, bytes) else site.encode()
+        if len(g) != self.length or len(t) != self.length + int(d):
+            raise ValueError("the guide has the table's %d letters, the site d more" % self.length)
+        nm, index, x, f = C.c_uint32(), C.c_uint32(), C.c_double(), C.c_uint32()
+        check(lib().vsc_bulge_table_score(self._h, g, t, int(d), C.byref(nm), C.byref(index), C.byref(x), C.byref(f)))
+        return (nm.value, index.value, x.value, f.value) if fixed else (nm.value, index.value, x.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsc_bulge_table_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -1163,12 +1284,14 @@ class Genome:
         return Hits(self, h, codes)
 
     def search_bulges(self, guides, max_mismatches, dna=1, rna=1, extra_pam=None, max_hits=0, guide_batch=0, records=True,
-                      rows=True):
+                      rows=True, table=None):
         """vsc_search_bulges: the sites of 23 + d bases, d in -rna .. -1 and 1 .. dna, that pair with a guide within
         max_mismatches when one or two bases of the site (DNA bulge) or of the guide (RNA bulge) stay unpaired.  The bulged
         neighbours of plain hits are among them; d = 0 is search()'s.  Returns (BULGE_HIT_DTYPE records in ascending (guide,
         strand, contig, pos, d) order | None, uint32 rows of shape (n, 4, 9) - hits by class (RNA 2, RNA 1, DNA 1, DNA 2) and
-        NM | None).  max_hits: 0 = no cap, else VSC_ERR_RANGE when there are more records; guide_batch never changes the result."""
+        NM | None).  max_hits: 0 = no cap, else VSC_ERR_RANGE when there are more records; guide_batch never changes the result.
+        table: a BulgeTable of 23 letters - the return gains (uint32 f per record | None, TABLE_ROW_DTYPE rows | None), scored by
+        vsc_bulge_hits_table over the records where they lie."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = self._params(max_mismatches, extra_pam, ALGO_SCAN)
@@ -1177,20 +1300,20 @@ class Genome:
         h = C.c_void_p()
         out_rows = np.zeros((len(codes), _lib.BULGE_CLASSES, 9), dtype=np.uint32) if rows else None
         check(L.vsc_search_bulges(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(bp),
-                                  C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+                                  C.byref(h) if records or table is not None else None, ptr(out_rows)), self.ctx._h)
+        if table is not None:
+            try:
+                fixed, table_rows = self._bulge_scores(h, [t.encode() for t in unpack_guides(codes)], table, records, rows)
+            except Exception:
+                L.vsc_bulge_hits_free(h)
+                raise
+            if not records:
+                L.vsc_bulge_hits_free(h)
+                return None, out_rows, None, table_rows
+            return self._bulge_records(h) + (out_rows, fixed, table_rows)
         if not records:
             return None, out_rows
-        try:
-            n = int(L.vsc_bulge_hits_count(h))
-            data = C.c_void_p()
-            check(L.vsc_bulge_hits_data(h, C.byref(data)), self.ctx._h)
-            if n == 0:
-                recs = np.zeros(0, dtype=BULGE_HIT_DTYPE)
-            else:
-                recs = np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy()
-        finally:
-            L.vsc_bulge_hits_free(h)
-        return recs, out_rows
+        return self._bulge_records(h) + (out_rows,)
 
     def search_pattern(self, pattern, guides, max_mismatches, max_hits=0, guide_batch=0, records=True, rows=True):
         """vsc_search_pattern: the sites of len(pattern) = 16..32 bases that satisfy the IUPAC pattern, hold no N and differ
@@ -1259,8 +1382,21 @@ class Genome:
             L.vsc_pattern_hits_free(h)
         return recs, fixed, out_rows, out_table
 
+    def _bulge_records(self, h):
+        """(records,) of a bulge result, which is freed."""
+        L = lib()
+        try:
+            n = int(L.vsc_bulge_hits_count(h))
+            data = C.c_void_p()
+            check(L.vsc_bulge_hits_data(h, C.byref(data)), self.ctx._h)
+            if n == 0:
+                return (np.zeros(0, dtype=BULGE_HIT_DTYPE),)
+            return (np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy(),)
+        finally:
+            L.vsc_bulge_hits_free(h)
+
     def search_pattern_bulges(self, pattern, guides, max_mismatches, protospacer, dna=1, rna=1, max_hits=0, guide_batch=0,
-                              records=True, rows=True):
+                              records=True, rows=True, table=None):
         """vsc_search_pattern_bulges: search_bulges for any nuclease - the sites of len(pattern) + d bases, d in -rna .. -1 and
         1 .. dna, that satisfy the pattern with its protospacer = (start, length) stretched or shortened by d, hold no N and pair
         with a guide within max_mismatches when d bases of the site (DNA bulge) or -d positions of the guide (RNA bulge) inside
@@ -1268,7 +1404,8 @@ class Genome:
         protospacer (pattern_protospacer gives it for a preset).  Returns (BULGE_HIT_DTYPE records in ascending (guide, strand,
         contig, pos, d) order | None, uint32 rows of shape (n, 4, 9) - hits by class (RNA 2, RNA 1, DNA 1, DNA 2) and NM | None);
         unpack_bulge_info reads the info word, d = site length - len(pattern).  max_hits: 0 = no cap, else VSC_ERR_RANGE when
-        there are more records; guide_batch never changes the result."""
+        there are more records; guide_batch never changes the result.  table: a BulgeTable of the pattern's length - the return
+        gains (uint32 f per record | None, TABLE_ROW_DTYPE rows | None), as search_bulges'."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
         for i, g in enumerate(gs):
@@ -1280,20 +1417,68 @@ class Genome:
         h = C.c_void_p()
         out_rows = np.zeros((len(gs), _lib.BULGE_CLASSES, 9), dtype=np.uint32) if rows else None
         check(L.vsc_search_pattern_bulges(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp),
-                                          C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+                                          C.byref(h) if records or table is not None else None, ptr(out_rows)), self.ctx._h)
+        if table is not None:
+            try:
+                fixed, table_rows = self._bulge_scores(h, gs, table, records, rows)
+            except Exception:
+                L.vsc_bulge_hits_free(h)
+                raise
+            if not records:
+                L.vsc_bulge_hits_free(h)
+                return None, out_rows, None, table_rows
+            return self._bulge_records(h) + (out_rows, fixed, table_rows)
         if not records:
             return None, out_rows
+        return self._bulge_records(h) + (out_rows,)
+
+    def _bulge_scores(self, bulged_h, texts, table, records, rows):
+        """vsc_bulge_hits_table over a device result: (uint32 f per record | None, TABLE_ROW_DTYPE rows | None)."""
+        L = lib()
+        n = int(L.vsc_bulge_hits_count(bulged_h))
+        fixed = np.zeros(n, dtype=np.uint32) if records else None
+        out_rows = np.zeros(len(texts), dtype=TABLE_ROW_DTYPE) if rows else None
+        check(L.vsc_bulge_hits_table(self.ctx._h, self._h, bulged_h, b"".join(texts), len(texts), table.length, table._h, ptr(fixed),
+                                     ptr(out_rows)), self.ctx._h)
+        return fixed, out_rows
+
+    def _site_scores(self, sites_h, params, texts, table, top_k, min_score, records, rows):
+        """vsc_sites_table over a device result: (SITE_DTYPE records | None, SITE_SCORE_DTYPE records | None, TABLE_ROW_DTYPE
+        rows | None) - the records are the survivors of the selection, the rows are over all sites."""
+        L = lib()
+        h = C.c_void_p()
+        sel = _lib.PatternSelect(int(top_k), int(min_score))
+        out_rows = np.zeros(len(texts), dtype=TABLE_ROW_DTYPE) if rows else None
+        check(L.vsc_sites_table(self.ctx._h, self._h, sites_h, C.byref(params), b"".join(texts), len(texts), table.length, table._h,
+                                C.byref(sel), C.byref(h) if records else None, ptr(out_rows)), self.ctx._h)
+        if not records:
+            return None, None, out_rows
         try:
-            n = int(L.vsc_bulge_hits_count(h))
-            data = C.c_void_p()
-            check(L.vsc_bulge_hits_data(h, C.byref(data)), self.ctx._h)
+            n = int(L.vsc_sites_count(h))
+            data, side = C.c_void_p(), C.c_void_p()
+            check(L.vsc_sites_data(h, C.byref(data)), self.ctx._h)
+            check(L.vsc_sites_scores(h, C.byref(side)), self.ctx._h)
             if n == 0:
-                recs = np.zeros(0, dtype=BULGE_HIT_DTYPE)
+                recs, scores = np.zeros(0, dtype=SITE_DTYPE), np.zeros(0, dtype=SITE_SCORE_DTYPE)
             else:
-                recs = np.frombuffer((C.c_char * (n * 16)).from_address(data.value), dtype=BULGE_HIT_DTYPE).copy()
+                recs = np.frombuffer((C.c_char * (n * 32)).from_address(data.value), dtype=SITE_DTYPE).copy()
+                scores = np.frombuffer((C.c_char * (n * 16)).from_address(side.value), dtype=SITE_SCORE_DTYPE).copy()
         finally:
-            L.vsc_bulge_hits_free(h)
-        return recs, out_rows
+            L.vsc_sites_free(h)
+        return recs, scores, out_rows
+
+    def _collapse_scored(self, fn, plain_h, bulged_h, texts, params, table, top_k, min_score, records, rows):
+        """The collapse with its records kept on the device, then _site_scores: (records | None, SITE_ROW_DTYPE rows | None,
+        score records | None, TABLE_ROW_DTYPE rows | None)."""
+        L = lib()
+        h = C.c_void_p()
+        site_rows = np.zeros(len(texts), dtype=SITE_ROW_DTYPE) if rows else None
+        check(fn(self.ctx._h, plain_h, bulged_h, len(texts), C.byref(params), C.byref(h), ptr(site_rows)), self.ctx._h)
+        try:
+            recs, scores, table_rows = self._site_scores(h, params, texts, table, top_k, min_score, records, rows)
+        finally:
+            L.vsc_sites_free(h)
+        return recs, site_rows, scores, table_rows
 
     def _collapse(self, fn, plain_h, bulged_h, n_guides, params, records, rows):
         """vsc_hits_sites / vsc_pattern_hits_sites over two device results: (SITE_DTYPE records | None, SITE_ROW_DTYPE rows | None)."""
@@ -1316,12 +1501,16 @@ class Genome:
         return recs, out_rows
 
     def search_sites(self, guides, max_mismatches, dna=1, rna=1, extra_pam=None, algorithm="auto", guide_batch=0, records=True,
-                     rows=True):
+                     rows=True, table=None, top_k=0, min_score=0):
         """The cut sites of a search: vsc_search, vsc_search_bulges and vsc_hits_sites with the two intermediate results kept on
         the device (and freed) - the plain hits and the bulged alignments of 23 + d bases collapsed into one SITE_DTYPE record
         per (guide, strand, contig, PAM-side end), with the best alignment's fields (fewest mismatches + bulge bases, then the
         smaller bulge, then DNA before RNA) and the NM of every member (unpack_site_members).  Returns (records in the order of
-        their best alignments | None, SITE_ROW_DTYPE rows per guide | None).  collapse_sites is the same on host arrays."""
+        their best alignments | None, SITE_ROW_DTYPE rows per guide | None).  collapse_sites is the same on host arrays.
+        table: a BulgeTable of 23 letters - every site is scored by vsc_sites_table where the collapse left it; per guide the
+        sites with top >= min_score survive, of those the top_k (0: all) under top descending, then record order.  The return
+        gains (SITE_SCORE_DTYPE records of the surviving sites | None, TABLE_ROW_DTYPE rows | None); both kinds of rows are over
+        ALL sites."""
         codes = guides if isinstance(guides, np.ndarray) else pack_guides(guides)
         codes = np.ascontiguousarray(codes, dtype=np.uint64)
         p = self._params(max_mismatches, extra_pam, algorithm)
@@ -1332,16 +1521,20 @@ class Genome:
         try:
             check(L.vsc_search(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(p), C.byref(plain)), self.ctx._h)
             check(L.vsc_search_bulges(self.ctx._h, self._h, ptr(codes), len(codes), C.byref(pb), C.byref(bp), C.byref(bulged), None), self.ctx._h)
+            if table is not None:
+                return self._collapse_scored(L.vsc_hits_sites, plain, bulged, [t.encode() for t in unpack_guides(codes)],
+                                             _site_params(23, "end"), table, top_k, min_score, records, rows)
             return self._collapse(L.vsc_hits_sites, plain, bulged, len(codes), _site_params(23, "end"), records, rows)
         finally:
             L.vsc_bulge_hits_free(bulged)
             L.vsc_hits_free(plain)
 
     def search_pattern_sites(self, pattern, guides, max_mismatches, protospacer, dna=1, rna=1, anchor=None, guide_batch=0, records=True,
-                             rows=True):
+                             rows=True, table=None, top_k=0, min_score=0):
         """search_sites for any nuclease: vsc_search_pattern, vsc_search_pattern_bulges and vsc_pattern_hits_sites on the device.
         anchor: "end" (the site's 3' end in read orientation is the fixed, PAM-side end: SpCas9, SaCas9), "start" (the 5' end:
-        Cas12a) or None - "end" when the protospacer starts at 0, "start" when it ends at the pattern's end, else ValueError."""
+        Cas12a) or None - "end" when the protospacer starts at 0, "start" when it ends at the pattern's end, else ValueError.
+        table, top_k, min_score: as search_sites takes them, a BulgeTable of the pattern's length."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
         for i, g in enumerate(gs):
@@ -1363,6 +1556,8 @@ class Genome:
             check(L.vsc_search_pattern(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp), C.byref(plain), None), self.ctx._h)
             check(L.vsc_search_pattern_bulges(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pbp), C.byref(bulged), None),
                   self.ctx._h)
+            if table is not None:
+                return self._collapse_scored(L.vsc_pattern_hits_sites, plain, bulged, gs, sp, table, top_k, min_score, records, rows)
             return self._collapse(L.vsc_pattern_hits_sites, plain, bulged, len(gs), sp, records, rows)
         finally:
             L.vsc_bulge_hits_free(bulged)

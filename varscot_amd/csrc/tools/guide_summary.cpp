@@ -82,6 +82,12 @@
 //   #guideId chrom start end strand kind size index mismatches members sequence
 // kind = plain | DNA | RNA, members = the site's alignments as d:mismatches (e.g. -1:3,0:2,+1:3), sequence = the best
 // alignment's forward-genome bases.  Without -Z every output is what it was.
+// -w bulge.tsv (needs -W, -u and -Z) scores the cut sites on the device (vsc_sites_table): -W stays the base table, the -w file
+// holds the bulge weights, `dna j s w` (one unpaired site base s when the bulge lies in front of read position j) and
+// `rna j g w` (the unpaired guide base g at read position j), every j in 0 .. 19 and every base once.  Every line gains, behind
+// all other columns, siteScoreSum siteSpecScore sitePositive (over the sites' largest member scores); the -Z listing gains
+// tableScore (that score, %.9f) and scoredAs (the d of the member that attains it) and is cut per guide by -K / -S on that
+// score.  Without -w every output is what it was.
 // -W table.tsv scores every off-target with a TABLE (vsc_search_summary_table; the CFD form: a product of weights by position,
 // guide base and site base times a weight for the site's PAM letters).  The file holds one entry per line, `j g s w` (0-based
 // read position, guide letter, site letter in read orientation, weight) or `PAM XY w`; '#' starts a comment; the diagonal is 1;
@@ -163,6 +169,9 @@ int main(int argc, char **argv)
         {'y', "min-efficiency", "Keep only the -E candidates whose efficiency predictor is defined and >= this value, linear domain (needs -Y)", false},
         {'Z', "sites", "Path to the TSV file of the cut sites (.tsv/.txt): the plain and the bulged alignments collapsed per PAM-side end; "
                        "adds the columns siteCount siteBulgeOnly; needs -u", false},
+        {'w', "bulge-table", "Path to the bulge weights (.tsv/.txt; lines 'dna j s w' and 'rna j g w', j = read position 0 .. 19) beside the -W table: "
+                             "the cut sites are scored; adds the columns siteScoreSum siteSpecScore sitePositive, and tableScore scoredAs to the -Z "
+                             "file, which -K / -S then cut by the site's score; needs -W, -u and -Z", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -219,7 +228,7 @@ int main(int argc, char **argv)
         }
         sel.min_score = (uint32_t)std::ceil(x * (opts[32].set ? 0x1p30 : 0x1p24));  // the smallest fixed-point score that is >= x
     }
-    if ((opts[8].set || opts[9].set) && !listing) {
+    if ((opts[8].set || opts[9].set) && !listing && !opts[36].set) {
         std::fprintf(stderr, "%s: -K / -S select the off-targets listed in the -T file: give -T\n", argv[0]);
         return 1;
     }
@@ -495,6 +504,13 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    // -w: the bulge weights beside -W
+    const bool site_scored = opts[36].set;
+    if (site_scored && (!tabled || !bulged || !sited || !has_extension(opts[36].value, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: -w scores the cut sites of -Z with the bulge weights of a .tsv/.txt file beside the -W table: give -W, -u and -Z\n", argv[0]);
+        return 1;
+    }
+
     if (efficient && devices.size() != 1) {
         std::fprintf(stderr, "%s: -Y scores the candidates on one device: it does not combine with a device list\n", argv[0]);
         return 1;
@@ -502,6 +518,8 @@ int main(int argc, char **argv)
 
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
+    vsc_bulge_table *bulge_table = nullptr;
+    vsc_sites *scored_sites = nullptr;
     vsc_eff_model *eff_model = nullptr;
     vsc_genome *genome = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
@@ -747,6 +765,18 @@ int main(int argc, char **argv)
                 if (std::isnan(w)) throw std::runtime_error("-W: the table lacks a PAM entry (16 'PAM XY w' lines)");
             if (vsc_score_table_build(pair.data(), pamw.data(), &table) != VSC_OK)
                 throw std::runtime_error("-W: every weight lies in 0 .. 1 and the weight of a base against itself is 1");
+            if (site_scored) {  // the same weights as a pattern table of the SpCas9 shape, plus the -w lines
+                const vsc_pattern_table_shape spcas9{VSC_READ_LEN, 0, 20, 2, {21, 22, 0, 0}};
+                vsc_pattern_table *base = nullptr;
+                if (vsc_pattern_table_build(&spcas9, pair.data(), pamw.data(), &base) != VSC_OK) throw std::runtime_error("-W: no pattern table");
+                try {
+                    bulge_table = read_bulge_table(opts[36].value, "-w", base);
+                } catch (...) {
+                    vsc_pattern_table_free(base);
+                    throw;
+                }
+                vsc_pattern_table_free(base);
+            }
         }
         if (individual) {
             std::vector<const char *> names;
@@ -835,6 +865,17 @@ int main(int argc, char **argv)
             if (st == VSC_OK) st = vsc_hits_sites(ctx, site_plain, bulge_hits, n_codes, &sp, &sites, site_rows.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         }
+        std::vector<vsc_guide_table_row> site_table_rows(site_scored ? codes.size() : 0);
+        if (site_scored) {  // the sites scored where the collapse left them; -K / -S cut the listing, the rows are over all sites
+            const vsc_site_params sp{VSC_READ_LEN, VSC_SITE_ANCHOR_END, {0, 0}};
+            const vsc_pattern_select ssel{sel.top_k, sel.min_score, {0, 0}};
+            std::string spelled;
+            for (uint64_t code : codes)
+                for (int j = 0; j < VSC_READ_LEN; ++j) spelled += "ACGT"[(code >> (2 * j)) & 3u];
+            st = vsc_sites_table(ctx, genome, sites, &sp, spelled.data(), n_codes, VSC_READ_LEN, bulge_table, &ssel, &scored_sites,
+                                 site_table_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
         // the enabled bulge classes in the rows' order (ascending site length) and their column prefixes
         static const char *const kBulgeClass[VSC_BULGE_CLASSES] = {"br2", "br1", "bd1", "bd2"};
         const bool bulge_on[VSC_BULGE_CLASSES] = {bp.rna_max >= 2, bp.rna_max >= 1, bp.dna_max >= 1, bp.dna_max >= 2};
@@ -865,6 +906,7 @@ int main(int argc, char **argv)
                 for (long k = 0; bulge_on[c] && k <= mm; ++k) text += std::string("\t") + kBulgeClass[c] + "mm" + std::to_string(k);
         }
         if (sited) text += "\tsiteCount\tsiteBulgeOnly";
+        if (site_scored) text += "\tsiteScoreSum\tsiteSpecScore\tsitePositive";
         text += '\n';
         char buf[64];
         for (size_t i = 0; i < sum.size(); ++i) {
@@ -927,6 +969,13 @@ int main(int argc, char **argv)
                     for (long k = 0; bulge_on[c] && k <= mm; ++k) text += '\t' + std::to_string(b.count[c][k]);
             }
             if (sited) text += '\t' + std::to_string(site_rows[i].sites) + '\t' + std::to_string(site_rows[i].bulge_only);
+            if (site_scored) {
+                const vsc_guide_table_row &r = site_table_rows[i];
+                std::snprintf(buf, sizeof buf, "%.6f", (double)r.score_sum * 0x1p-30);
+                text += '\t' + std::string(buf);
+                std::snprintf(buf, sizeof buf, "%.0f", std::floor(vsc_table_specificity(r.score_sum) + 0.5));
+                text += '\t' + std::string(buf) + '\t' + std::to_string(r.positive);
+            }
             text += '\n';
         }
         if (opts[5].set) {
@@ -1026,8 +1075,11 @@ int main(int argc, char **argv)
         }
         if (sited) {
             const vsc_site *rec = nullptr;
-            if (vsc_sites_data(sites, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
-            write_sites(sites_path, "-Z", rec, vsc_sites_count(sites), VSC_READ_LEN, ids, ix);
+            const vsc_site_score *scores = nullptr;
+            vsc_sites *listed = site_scored ? scored_sites : sites;
+            if (vsc_sites_data(listed, &rec) != VSC_OK || (site_scored && vsc_sites_scores(listed, &scores) != VSC_OK))
+                throw std::runtime_error(vsc_last_error(ctx));
+            write_sites(sites_path, "-Z", rec, vsc_sites_count(listed), VSC_READ_LEN, ids, ix, scores);
         }
         if (pairing) {
             // the pairs among the guides' loci, then one search that keeps the records and the join over them on the device
@@ -1076,6 +1128,8 @@ int main(int argc, char **argv)
     }
     if (hits) vsc_hits_free(hits);
     vsc_score_table_free(table);
+    vsc_bulge_table_free(bulge_table);
+    vsc_sites_free(scored_sites);
     vsc_eff_model_free(eff_model);
     if (pair_hits) vsc_hits_free(pair_hits);
     vsc_bulge_hits_free(bulge_hits);

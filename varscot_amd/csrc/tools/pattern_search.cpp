@@ -17,6 +17,10 @@
 // gains, behind all other columns, siteCount siteBulgeOnly; the listing goes under guide_summary -Z's columns
 //   #guideId chrom start end strand kind size index mismatches members sequence
 // Without -Z every output is what it was.
+// -w bulge.tsv (needs -W, -u, -p and -Z) scores the cut sites on the device (vsc_sites_table): -W stays the base table, whose
+// protospacer must be -p's; the -w file holds `dna j s w` and `rna j g w` for every protospacer position j and base
+// (tools/README.md).  The -O summary gains siteScoreSum siteSpecScore sitePositive behind all other columns, the -Z listing
+// tableScore (%.9f) and scoredAs, and -K / -S cut the -Z listing per guide by that score.  Without -w every output is what it was.
 // -Y model.tsv (needs -E) scores every found guide's ON-TARGET EFFICIENCY with a linear position-specific model
 // (vsc_pattern_guides_efficiency; the file is what varscot_amd.EfficiencyModel.to_tsv writes, tools/README.md; its site_len
 // must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
@@ -200,6 +204,9 @@ int main(int argc, char **argv)
         {'S', "min-score", "With -W: list only hits with a table score >= this value, 0 .. 1, in the -T file (default: no floor)", false},
         {'Z', "sites", "Path to the TSV file of the cut sites (.tsv/.txt): the plain and the bulged alignments collapsed per PAM-side end; "
                        "-O gains siteCount siteBulgeOnly; needs -u and a -p protospacer at one end of the pattern", false},
+        {'w', "bulge-table", "Path to the bulge weights (.tsv/.txt; lines 'dna j s w' and 'rna j g w', j = read position in the protospacer) beside "
+                             "the -W table: the cut sites are scored; -O gains siteScoreSum siteSpecScore sitePositive, the -Z file tableScore "
+                             "scoredAs, and -K / -S cut the -Z listing by the site's score; needs -W, -u, -p and -Z", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -369,7 +376,12 @@ int main(int argc, char **argv)
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     vsc_pattern_select sel{};
-    if ((opts[19].set || opts[20].set) && (!tabled || !opts[6].set)) {
+    const bool site_scored = opts[22].set;
+    if (site_scored && (!tabled || !bulged || !sited || !has_extension(opts[22].value, {"tsv", "txt"}))) {
+        std::fprintf(stderr, "%s: -w scores the cut sites of -Z with the bulge weights of a .tsv/.txt file beside the -W table: give -W, -u, -p and -Z\n", argv[0]);
+        return 1;
+    }
+    if ((opts[19].set || opts[20].set) && (!tabled || (!opts[6].set && !site_scored))) {
         std::fprintf(stderr, "%s: -K and -S select the -T listing by the score of the -W table: give -W and -T\n", argv[0]);
         return 1;
     }
@@ -432,6 +444,8 @@ int main(int argc, char **argv)
     vsc_sites *sites = nullptr;
     vsc_eff_model *eff_model = nullptr;
     vsc_pattern_table *table = nullptr;
+    vsc_bulge_table *bulge_table = nullptr;
+    vsc_sites *scored_sites = nullptr;
     int rc = 1;
     try {
         std::vector<FastaRecord> guides;
@@ -447,6 +461,11 @@ int main(int argc, char **argv)
             table = load_pattern_table(opts[18].value, &table_shape);
             if (table_shape.len != len)
                 throw std::runtime_error("-W: the table is built for " + std::to_string(table_shape.len) + " letters; the pattern has " + std::to_string(len));
+            if (site_scored) {
+                if (table_shape.ps_start != bp.proto_start || table_shape.ps_len != bp.proto_len)
+                    throw std::runtime_error("-w: the -W table's protospacer is not the -p protospacer");
+                bulge_table = read_bulge_table(opts[22].value, "-w", table);
+            }
         }
         std::string letters;
         if (!enumerate) {
@@ -559,6 +578,12 @@ int main(int argc, char **argv)
             if (st == VSC_OK) st = vsc_pattern_hits_sites(ctx, site_plain, bulge_hits, (uint32_t)guides.size(), &sp, &sites, site_rows.data());
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
         }
+        std::vector<vsc_guide_table_row> site_table_rows(site_scored ? guides.size() : 0);
+        if (site_scored) {  // the sites scored where the collapse left them; -K / -S cut the listing, the rows are over all sites
+            st = vsc_sites_table(ctx, genome, sites, &sp, letters.c_str(), (uint32_t)guides.size(), len, bulge_table, &sel, &scored_sites,
+                                 site_table_rows.data());
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
 
         if (opts[5].set) {
             std::ofstream out(opts[5].value);
@@ -572,6 +597,7 @@ int main(int argc, char **argv)
             }
             if (tabled) out << "\ttableScoreSum\ttableSpecScore\ttablePositive";
             if (sited) out << "\tsiteCount\tsiteBulgeOnly";
+            if (site_scored) out << "\tsiteScoreSum\tsiteSpecScore\tsitePositive";
             out << '\n';
             for (size_t g = 0; g < guides.size(); ++g) {
                 uint64_t total = 0;
@@ -594,6 +620,13 @@ int main(int argc, char **argv)
                     out << buf << '\t' << table_rows[g].positive;
                 }
                 if (sited) out << '\t' << site_rows[g].sites << '\t' << site_rows[g].bulge_only;
+                if (site_scored) {
+                    char buf[64];
+                    std::snprintf(buf, sizeof buf, "\t%.6f", (double)site_table_rows[g].score_sum * 0x1p-30);
+                    out << buf;
+                    std::snprintf(buf, sizeof buf, "\t%.0f", std::floor(vsc_table_specificity(site_table_rows[g].score_sum) + 0.5));
+                    out << buf << '\t' << site_table_rows[g].positive;
+                }
                 out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[5].value);
@@ -634,10 +667,13 @@ int main(int argc, char **argv)
         }
         if (sited) {
             const vsc_site *rec = nullptr;
-            if (vsc_sites_data(sites, &rec) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const vsc_site_score *scores = nullptr;
+            vsc_sites *listed = site_scored ? scored_sites : sites;
+            if (vsc_sites_data(listed, &rec) != VSC_OK || (site_scored && vsc_sites_scores(listed, &scores) != VSC_OK))
+                throw std::runtime_error(vsc_last_error(ctx));
             std::vector<std::string> ids;
             for (const auto &g : guides) ids.push_back(first_word(g.id));
-            write_sites(opts[21].value, "-Z", rec, vsc_sites_count(sites), len, ids, ix);
+            write_sites(opts[21].value, "-Z", rec, vsc_sites_count(listed), len, ids, ix, scores);
         }
         if (bulge_hits && opts[15].set) {
             const vsc_bulge_hit *rec = nullptr;
@@ -674,6 +710,8 @@ int main(int argc, char **argv)
     vsc_pattern_guides_free(found);
     vsc_eff_model_free(eff_model);
     vsc_pattern_table_free(table);
+    vsc_bulge_table_free(bulge_table);
+    vsc_sites_free(scored_sites);
     vsc_bulge_hits_free(bulge_hits);
     vsc_sites_free(sites);
     vsc_pattern_hits_free(site_plain);

@@ -10,11 +10,14 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -482,12 +485,14 @@ inline bool has_extension(const std::string &path, std::initializer_list<const c
 // site with its best alignment's fields, the members as d:mismatches and the best alignment's forward-genome bases.
 // len = the plain site length, ids = the guides' names, ix = the packed genome (planes, contigs, names).
 template <class Index>
+// scores != nullptr (a result of vsc_sites_table): two more columns, tableScore (the site's top, %.9f) and scoredAs (the d of the
+// member that attains it, written as `members` writes it)
 void write_sites(const std::string &path, const char *option, const vsc_site *rec, uint64_t n, uint32_t len, const std::vector<std::string> &ids,
-                 const Index &ix)
+                 const Index &ix, const vsc_site_score *scores = nullptr)
 {
     std::ofstream out(path);
     if (!out.is_open()) throw std::runtime_error(std::string("Could not open the ") + option + " path.");
-    out << "#guideId\tchrom\tstart\tend\tstrand\tkind\tsize\tindex\tmismatches\tmembers\tsequence\n";
+    out << "#guideId\tchrom\tstart\tend\tstrand\tkind\tsize\tindex\tmismatches\tmembers\tsequence" << (scores ? "\ttableScore\tscoredAs\n" : "\n");
     std::string site, text;
     for (uint64_t j = 0; j < n; ++j) {
         const vsc_site &s = rec[j];
@@ -505,7 +510,14 @@ void write_sites(const std::string &path, const char *option, const vsc_site *re
                 '\t' + (VSC_BULGE_STRAND(s.info) ? '-' : '+') + '\t' +
                 (VSC_BULGE_SIZE(s.info) == 0 ? "plain" : VSC_BULGE_KIND(s.info) == VSC_BULGE_RNA ? "RNA" : "DNA") + '\t' +
                 std::to_string(VSC_BULGE_SIZE(s.info)) + '\t' + std::to_string(VSC_BULGE_INDEX(s.info)) + '\t' + std::to_string(VSC_BULGE_NM(s.info)) +
-                '\t' + members + '\t' + site + '\n';
+                '\t' + members + '\t' + site;
+        if (scores) {
+            char buf[64];
+            const int d = (int)scores[j].top_d - 2;
+            std::snprintf(buf, sizeof buf, "\t%.9f\t%s%d", (double)scores[j].top * 0x1p-30, d > 0 ? "+" : "", d);
+            text += buf;
+        }
+        text += '\n';
         if (text.size() > (1u << 22)) {
             out << text;
             text.clear();
@@ -514,6 +526,44 @@ void write_sites(const std::string &path, const char *option, const vsc_site *re
     out << text;
     out.close();
     if (!out) throw std::runtime_error(std::string("Could not write the ") + option + " file.");
+}
+
+// The bulge table of -w: the pattern table `base` (the tool's -W) plus the lines `dna j s w` and `rna j g w` of `path` - j the
+// 0-based read position inside the protospacer, s / g a letter of ACGT; '#' starts a comment; every entry of both arrays has to
+// be there.  The base's weights are copied: the caller frees it when it likes.
+inline vsc_bulge_table *read_bulge_table(const std::string &path, const char *option, const vsc_pattern_table *base)
+{
+    const std::string opt(option);
+    vsc_pattern_table_stats st{};
+    if (vsc_pattern_table_info(base, &st) != VSC_OK) throw std::runtime_error(opt + ": no base table");
+    const vsc_pattern_table_shape &shape = st.shape;
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("Could not open the " + opt + " file.");
+    std::vector<double> dna((size_t)shape.ps_len * 4, std::nan("")), rna((size_t)shape.ps_len * 4, std::nan(""));
+    std::string line;
+    while (std::getline(in, line)) {
+        line = line.substr(0, line.find('#'));
+        std::istringstream is(line);
+        std::string key, pos, letter, rest;
+        double w = 0;
+        if (!(is >> key)) continue;
+        char *jend = nullptr;
+        static const std::string letters = "ACGT";
+        if ((key != "dna" && key != "rna") || !(is >> pos >> letter >> w) || (is >> rest) || std::isnan(w) || letter.size() != 1)
+            throw std::runtime_error(opt + ": neither 'dna j s w' nor 'rna j g w': '" + line + "'");
+        const long j = std::strtol(pos.c_str(), &jend, 10);
+        const size_t b = letters.find((char)std::toupper((unsigned char)letter[0]));
+        if (*jend || j < (long)shape.ps_start || j >= (long)(shape.ps_start + shape.ps_len) || b == std::string::npos)
+            throw std::runtime_error(opt + ": a position outside the protospacer or a letter that is no base: '" + line + "'");
+        (key == "dna" ? dna : rna)[(size_t)(j - shape.ps_start) * 4 + b] = w;
+    }
+    for (size_t i = 0; i < dna.size(); ++i)
+        if (std::isnan(dna[i]) || std::isnan(rna[i]))
+            throw std::runtime_error(opt + ": the weights lack an entry (a 'dna' and an 'rna' line for every protospacer position and base)");
+    vsc_bulge_table *table = nullptr;
+    if (vsc_bulge_table_build(base, dna.data(), rna.data(), &table) != VSC_OK)
+        throw std::runtime_error(opt + ": every weight lies in 0 .. 1 and the protospacer has at least four positions");
+    return table;
 }
 
 }  // namespace vsc_host

@@ -36,6 +36,7 @@
 #include "vsc_objects.h"
 #include "vsc_pairs.h"
 #include "vsc_sites.h"
+#include "vsc_bulge_table.h"
 #include "vsc_table.h"
 #include "vsc_varmap.h"
 
@@ -240,11 +241,13 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->seed_poff, &ctx->seed_lrest, &ctx->sum_rows, &ctx->sum_excl, &ctx->sel_hist, &ctx->sel_tabs, &ctx->sel_keys,
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
-                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
+                         &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
+                         &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
                          &ctx->eff_out})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
+    ctx->bulge_table_serial = 0;
     ctx->eff_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
@@ -5732,6 +5735,361 @@ int vsc_debug_sites_ms(const vsc_ctx *ctx, double *flag_scan_ms, double *write_m
     if (!ctx) return VSC_ERR_INVALID;
     if (flag_scan_ms) *flag_scan_ms = ctx->sites_ms[0];
     if (write_ms) *write_ms = ctx->sites_ms[1];
+    return VSC_OK;
+}
+
+}  // extern "C"
+
+// ---- table scores for bulged alignments and cut sites (the score: vsc_bulge_table.h; the kernels: vsc_bulge_table.hip) ----
+namespace {
+
+// the device copy of a bulge table: uploaded unless this context used this very table last
+int resident_bulge_table(vsc_ctx *ctx, const vsc_bulge_table *table)
+{
+    if (ctx->bulge_table_serial == table->serial && ctx->bulge_table_buf.p) return VSC_OK;
+    ctx->bulge_table_serial = 0;
+    const size_t bytes = bulge_table_weights(table->shape) * sizeof(double);
+    VSC_HIP(ctx, ctx->bulge_table_buf.ensure(bytes));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->bulge_table_buf.p, table->w, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the table may be freed when the call returns)
+    ctx->bulge_table_serial = table->serial;
+    return VSC_OK;
+}
+
+// What both device calls share: the checks of (genome, guides, len, table), the guides' words and planes, the table and the
+// zeroed rows on the device.  The call's tables in ctx->site_table_tabs, 256-byte aligned parts:
+// [guides: two uint4 each][rows][bounds: n_guides + 1 words][sel: a uint4 per guide]
+struct BulgeTableCall {
+    BulgeTableArgs a{};
+    std::vector<uint4> host_guides;  // (outlives the asynchronous upload)
+    size_t rows_at = 0, row_bytes = 0, bounds_at = 0, sel_at = 0;
+};
+
+int bulge_table_prepare(vsc_ctx *ctx, const char *who, const vsc_genome *genome, const char *guides, uint32_t n_guides, uint32_t len,
+                        const vsc_bulge_table *table, bool want_rows, BulgeTableCall *call)
+{
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "a genome of another context");
+    if (table->shape.len != len) return fail_in(ctx, VSC_ERR_INVALID, who, "the table's len is not the call's");
+    if (n_guides && !guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    call->host_guides.resize(2 * (size_t)n_guides);
+    for (uint32_t g = 0; g < n_guides; ++g) {
+        uint8_t sets[kPatMaxLen];
+        if (!pattern_sets(guides + (size_t)g * len, len, sets)) return fail_in(ctx, VSC_ERR_INVALID, who, "a guide letter that is no IUPAC letter");
+        const BulgeGuide b = bulge_table_guide(sets, len);
+        call->host_guides[2 * (size_t)g] = make_uint4(b.gh, b.gl, b.single, 0u);
+        call->host_guides[2 * (size_t)g + 1] = make_uint4(b.planes.a, b.planes.c, b.planes.g, b.planes.t);
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const int trc = resident_bulge_table(ctx, table);
+    if (trc != VSC_OK) return trc;
+    const size_t guide_bytes = call->host_guides.size() * sizeof(uint4);
+    call->rows_at = round256(guide_bytes);
+    call->row_bytes = want_rows ? (size_t)n_guides * sizeof(vsc_guide_table_row) : 0;
+    call->bounds_at = call->rows_at + round256(call->row_bytes);
+    call->sel_at = call->bounds_at + round256(((size_t)n_guides + 1) * sizeof(uint32_t));
+    VSC_HIP(ctx, ctx->site_table_tabs.ensure(call->sel_at + round256((size_t)n_guides * sizeof(uint4)) + 256));
+    char *base = (char *)ctx->site_table_tabs.p;
+    if (guide_bytes) VSC_HIP(ctx, hipMemcpyAsync(base, call->host_guides.data(), guide_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (call->row_bytes) VSC_HIP(ctx, hipMemsetAsync(base + call->rows_at, 0, call->row_bytes, ctx->stream));
+    BulgeTableArgs &a = call->a;
+    // held_words: what the genome was loaded with (vsc_genome_load pads the device planes with kPadWords behind them); a
+    // genome object without planes (genome_table_only) holds none, and every record scores 0 over it
+    a.planes = BulgePlanes{genome->d_hi, genome->d_lo, (uint32_t)(genome->first_word * 32), genome->d_hi ? (uint32_t)genome->held_words : 0u,
+                           genome->d_contig_off, genome->d_contig_end, genome->n_contigs};
+    std::memcpy(&a.shape, &table->shape, sizeof a.shape);
+    a.weights = (const double *)ctx->bulge_table_buf.p;
+    a.guides = (const uint4 *)base;
+    a.n_guides = n_guides;
+    a.rows = call->row_bytes ? (unsigned long long *)(base + call->rows_at) : nullptr;
+    return VSC_OK;
+}
+
+// Results from host arrays (tests: records of chosen lengths and records that no search returns)
+template <class List, class Rec> int record_list_from_host(vsc_ctx *ctx, const Rec *records, uint64_t n, List **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!ctx || (n && !records)) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    std::unique_ptr<List, int (*)(List *)> r(new List(), object_free<List>);
+    r->ctx = ctx;
+    r->n = n;
+    if (n) {
+        VSC_HIP(ctx, hipSetDevice(ctx->device));
+        VSC_HIP(ctx, r->storage.ensure((size_t)n * sizeof(Rec)));
+        VSC_HIP(ctx, hipMemcpyAsync(r->storage.p, records, (size_t)n * sizeof(Rec), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *out = r.release();
+    return VSC_OK;
+    });
+}
+
+int stage_ms(vsc_ctx *ctx, int from, int to, double *out)
+{
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[from], ctx->ev[to]));
+    *out = ms;
+    return VSC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_bulge_table_build(const vsc_pattern_table *base, const double *dna, const double *rna, vsc_bulge_table **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!base || !dna || !rna) return VSC_ERR_INVALID;
+    static std::atomic<uint64_t> serial{0};
+    if (base->shape.ps_len < kPatBulgeMinProto) return VSC_ERR_INVALID;  // (before the weights are read: the shape sizes them)
+    vsc_bulge_table *t = new (std::nothrow) vsc_bulge_table();
+    if (!t) return VSC_ERR_NOMEM;
+    t->shape = base->shape;
+    const uint32_t n_base = pattern_table_weights(t->shape), rows = t->shape.ps_len * 4u;
+    std::memcpy(t->w, base->w, n_base * sizeof(double));
+    std::memcpy(t->w + bulge_table_dna_at(t->shape), dna, rows * sizeof(double));
+    std::memcpy(t->w + bulge_table_rna_at(t->shape), rna, rows * sizeof(double));
+    if (!bulge_table_valid(t->shape, t->w)) {  // a weight outside [0, 1], NaN included
+        delete t;
+        return VSC_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < bulge_table_weights(t->shape); ++i) t->zeros += t->w[i] == 0.0;
+    t->serial = serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    *out = t;
+    return VSC_OK;
+}
+
+int vsc_bulge_table_free(vsc_bulge_table *table)
+{
+    delete table;
+    return VSC_OK;
+}
+
+int vsc_bulge_table_info(const vsc_bulge_table *table, vsc_bulge_table_stats *out)
+{
+    if (!table || !out) return VSC_ERR_INVALID;
+    *out = vsc_bulge_table_stats{};
+    out->serial = table->serial;
+    out->zero_weights = table->zeros;
+    std::memcpy(&out->shape, &table->shape, sizeof out->shape);
+    return VSC_OK;
+}
+
+int vsc_bulge_table_score(const vsc_bulge_table *table, const char *guide, const char *site_text, int d, uint32_t *nm, uint32_t *index,
+                          double *score, uint32_t *fixed)
+{
+    if (!table || !guide || !site_text || d < -2 || d > 2) return VSC_ERR_INVALID;
+    const uint32_t len = table->shape.len;
+    const int m = (int)len + d;
+    if (m < (int)kPatMinLen || m > (int)kPatMaxLen) return VSC_ERR_INVALID;
+    uint8_t sets[kPatMaxLen];
+    if (!pattern_sets(guide, len, sets)) return VSC_ERR_INVALID;
+    uint32_t sh = 0, sl = 0;
+    for (int j = 0; j < m; ++j) {
+        const int c = base_code(site_text[j]);
+        if (c > 3) return VSC_ERR_INVALID;
+        sh |= (uint32_t)(c >> 1) << j;
+        sl |= (uint32_t)(c & 1) << j;
+    }
+    const BulgeGuide g = bulge_table_guide(sets, len);
+    uint32_t n = 0, i = 0;
+    double x;
+    if (d == 0) {
+        n = (uint32_t)__builtin_popcount(pattern_mismatch(sh, sl, g.planes));
+        x = pattern_table_score(table->w, table->shape, g.gh, g.gl, g.single, sh, sl);
+    } else {
+        n = pattern_bulge_align(sh, sl, g.planes, table->shape.ps_start, table->shape.ps_start + table->shape.ps_len, d, &i);
+        x = bulge_table_score(table->w, table->shape, g.gh, g.gl, g.single, sh, sl, d, i);
+    }
+    if (nm) *nm = n;
+    if (index) *index = i;
+    if (score) *score = x;
+    if (fixed) *fixed = table_fixed(x);
+    return VSC_OK;
+}
+
+int vsc_bulge_hits_table(vsc_ctx *ctx, const vsc_genome *genome, vsc_bulge_hits *hits, const char *guides, uint32_t n_guides, uint32_t len,
+                         const vsc_bulge_table *table, uint32_t *fixed, vsc_guide_table_row *rows)
+{
+    const char *who = "vsc_bulge_hits_table";
+    if (!ctx) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    if (!genome || !hits || !table) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (!fixed && !rows) return fail_in(ctx, VSC_ERR_INVALID, who, "neither scores nor rows are asked for");
+    if (hits->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "a result of another context");
+    if (hits->n > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^32 - 1 records");
+    BulgeTableCall call;
+    if (rows && n_guides) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_guide_table_row));
+    if (table->shape.len != len) return fail_in(ctx, VSC_ERR_INVALID, who, "the table's len is not the call's");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "a genome of another context");
+    if (hits->n == 0) return VSC_OK;
+    const int rc = bulge_table_prepare(ctx, who, genome, guides, n_guides, len, table, rows != nullptr, &call);
+    if (rc != VSC_OK) return rc;
+    BulgeTableArgs &a = call.a;
+    a.n = (uint32_t)hits->n;
+    a.hits = (const uint4 *)hits->storage.p;
+    if (fixed) {
+        VSC_HIP(ctx, ctx->site_table_scores.ensure((size_t)a.n * sizeof(uint32_t)));
+        a.fixed = (uint32_t *)ctx->site_table_scores.p;
+    }
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_bulge_table(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    if (fixed) VSC_HIP(ctx, hipMemcpyAsync(fixed, a.fixed, (size_t)a.n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (a.rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.rows, call.row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->site_table_ms[1] = ctx->site_table_ms[2] = 0;
+    return stage_ms(ctx, kEvStageStart, kEvStageEnd, &ctx->site_table_ms[0]);
+    });
+}
+
+int vsc_sites_table(vsc_ctx *ctx, const vsc_genome *genome, vsc_sites *sites, const vsc_site_params *params, const char *guides,
+                    uint32_t n_guides, uint32_t len, const vsc_bulge_table *table, const vsc_pattern_select *select, vsc_sites **out,
+                    vsc_guide_table_row *rows)
+{
+    const char *who = "vsc_sites_table";
+    if (out) *out = nullptr;
+    if (!ctx) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    if (!genome || !sites || !table) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (!out && !rows) return fail_in(ctx, VSC_ERR_INVALID, who, "neither records nor rows are asked for");
+    if (site_params_check(params) != VSC_OK || params->len != len)
+        return fail_in(ctx, VSC_ERR_INVALID, who, "params: len = the call's len, a known anchor and zeroed reserved fields are needed");
+    if (select && (select->reserved[0] || select->reserved[1])) return fail_in(ctx, VSC_ERR_INVALID, who, "a non-zero reserved field of select");
+    if (sites->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "a result of another context");
+    if (table->shape.len != len) return fail_in(ctx, VSC_ERR_INVALID, who, "the table's len is not the call's");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "a genome of another context");
+    if (sites->n > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^32 - 1 sites");
+    if (rows && n_guides) std::memset(rows, 0, (size_t)n_guides * sizeof(vsc_guide_table_row));
+    std::unique_ptr<vsc_sites, int (*)(vsc_sites *)> res(nullptr, object_free<vsc_sites>);
+    if (out) {
+        res.reset(new (std::nothrow) vsc_sites());
+        if (!res) return fail_in(ctx, VSC_ERR_NOMEM, who, "out of host memory");
+        res->ctx = ctx;
+        res->has_scores = true;
+    }
+    if (sites->n == 0) {
+        if (out) *out = res.release();
+        return VSC_OK;
+    }
+    BulgeTableCall call;
+    const int rc = bulge_table_prepare(ctx, who, genome, guides, n_guides, len, table, rows != nullptr, &call);
+    if (rc != VSC_OK) return rc;
+    BulgeTableArgs &a = call.a;
+    const uint32_t n = (uint32_t)sites->n;
+    a.n = n;
+    a.sites = (const uint4 *)sites->storage.p;
+    a.anchor = params->anchor;
+    const bool selects = out && select && (select->top_k || select->min_score);
+    const size_t site_bytes = round256((size_t)n * sizeof(vsc_site));
+    if (selects) {  // all the sites' scores go to scratch: the result is sized by the selection
+        VSC_HIP(ctx, ctx->site_table_scores.ensure((size_t)n * sizeof(vsc_site_score)));
+        a.scores = (uint4 *)ctx->site_table_scores.p;
+    } else if (out) {  // every site stays: its record is copied, its scores are written where they stay
+        VSC_HIP(ctx, res->storage.ensure(site_bytes + (size_t)n * sizeof(vsc_site_score)));
+        res->n = n;
+        res->scores_at = site_bytes;
+        VSC_HIP(ctx, hipMemcpyAsync(res->storage.p, sites->storage.p, (size_t)n * sizeof(vsc_site), hipMemcpyDeviceToDevice, ctx->stream));
+        a.scores = (uint4 *)((char *)res->storage.p + site_bytes);
+    }
+    ctx->site_table_ms[1] = ctx->site_table_ms[2] = 0;
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_site_table(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    if (a.rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.rows, call.row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (selects && n_guides) {
+        char *base = (char *)ctx->site_table_tabs.p;
+        SiteSelectArgs s{};
+        s.sites = a.sites;
+        s.scores = a.scores;
+        s.n = n;
+        s.n_guides = n_guides;
+        s.bounds = (uint32_t *)(base + call.bounds_at);
+        s.top_k = select->top_k;
+        s.min_score = select->min_score;
+        s.sel = (uint4 *)(base + call.sel_at);
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_site_bounds(s, ctx->stream));
+        VSC_HIP(ctx, launch_site_select(s, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        // one read-back: every guide's survivors (they size the result)
+        std::vector<uint4> sel(n_guides);
+        VSC_HIP(ctx, hipMemcpyAsync(sel.data(), s.sel, (size_t)n_guides * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        unsigned long long kept = 0;
+        for (const uint4 &q : sel) kept += (unsigned long long)q.w << 32 | q.z;
+        if (kept > n) kept = n;  // (never, when the sites are in their order: segments of a list in another order may overlap)
+        s.n_out = kept;
+        if (kept) {
+            const size_t kept_bytes = round256((size_t)kept * sizeof(vsc_site));
+            VSC_HIP(ctx, res->storage.ensure(kept_bytes + (size_t)kept * sizeof(vsc_site_score)));
+            res->n = kept;
+            res->scores_at = kept_bytes;
+            s.out_sites = (uint4 *)res->storage.p;
+            s.out_scores = (uint4 *)((char *)res->storage.p + kept_bytes);
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSinkEnd], ctx->stream));
+            VSC_HIP(ctx, launch_site_select_walk(s, ctx->stream));
+            VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvPrepEnd], ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        int trc = stage_ms(ctx, kEvStage2Start, kEvStage2End, &ctx->site_table_ms[1]);
+        if (trc == VSC_OK && kept) trc = stage_ms(ctx, kEvSinkEnd, kEvPrepEnd, &ctx->site_table_ms[2]);
+        if (trc != VSC_OK) return trc;
+    } else {
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const int trc = stage_ms(ctx, kEvStageStart, kEvStageEnd, &ctx->site_table_ms[0]);
+    if (trc != VSC_OK) return trc;
+    if (out) *out = res.release();
+    return VSC_OK;
+    });
+}
+
+int vsc_sites_scores(vsc_sites *sites, const vsc_site_score **out)
+{
+    if (!sites || !out || !sites->has_scores) return VSC_ERR_INVALID;
+    return guarded(sites->ctx, [&]() -> int {
+    if (!sites->scores_host_valid) {
+        vsc_ctx *ctx = sites->ctx;
+        sites->scores_host.resize(sites->n);
+        if (sites->n) {
+            VSC_HIP(ctx, hipSetDevice(ctx->device));
+            VSC_HIP(ctx, hipMemcpyAsync(sites->scores_host.data(), (const char *)sites->storage.p + sites->scores_at,
+                                        sites->n * sizeof(vsc_site_score), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        sites->scores_host_valid = true;
+    }
+    *out = sites->scores_host.data();
+    return VSC_OK;
+    });
+}
+
+const void *vsc_sites_scores_dev(const vsc_sites *sites)
+{
+    return sites && sites->has_scores && sites->n ? (const char *)sites->storage.p + sites->scores_at : nullptr;
+}
+
+int vsc_debug_bulge_hits_from_host(vsc_ctx *ctx, const vsc_bulge_hit *records, uint64_t n, vsc_bulge_hits **out)
+{
+    return record_list_from_host(ctx, records, n, out);
+}
+
+int vsc_debug_sites_from_host(vsc_ctx *ctx, const vsc_site *records, uint64_t n, vsc_sites **out)
+{
+    return record_list_from_host(ctx, records, n, out);
+}
+
+int vsc_debug_site_table_ms(const vsc_ctx *ctx, double *score_ms, double *select_ms, double *walk_ms)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    if (score_ms) *score_ms = ctx->site_table_ms[0];
+    if (select_ms) *select_ms = ctx->site_table_ms[1];
+    if (walk_ms) *walk_ms = ctx->site_table_ms[2];
     return VSC_OK;
 }
 

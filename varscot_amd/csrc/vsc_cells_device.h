@@ -42,6 +42,27 @@ __device__ __forceinline__ uint32_t wave_exclusive(uint32_t v, uint32_t lane, ui
     return s - v;
 }
 
+// exclusive prefix of v over the workgroup's threads and *total = the sum; ws: kWavesPerGroup words of LDS (the selection
+// walks of vsc_pattern.hip and vsc_bulge_table.hip)
+__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *ws, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+    uint32_t wave_total;
+    const uint32_t in_wave = wave_exclusive(v, lane, &wave_total);
+    block_sync();  // (the last step's readers of ws are done)
+    if (lane == 0) ws[wave] = wave_total;
+    block_sync();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kWavesPerGroup; ++k) {
+        const uint32_t t = ws[k];
+        before += k < wave ? t : 0u;
+        all += t;
+    }
+    *total = all;
+    return before + in_wave;
+}
+
 // tiles [*t0, *t1) of wave `w` of `n_waves`: runs of consecutive tiles, so that the cells a wave stores lie side by side
 __device__ __forceinline__ void cell_tile_run(uint32_t n_tiles, uint32_t w, uint32_t n_waves, uint32_t *t0, uint32_t *t1)
 {

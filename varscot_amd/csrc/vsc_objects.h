@@ -162,6 +162,13 @@ struct vsc_ctx {
     // the call's two stages (flag pass + scan, write pass: vsc_debug_sites_ms - vsc_ctx_timing is not the call's to change)
     vsc::DeviceBuf sites_tabs;
     double sites_ms[2] = {0, 0};
+    // vsc_bulge_hits_table / vsc_sites_table: the device copy of the bulge table this context used last (at most 1 024 doubles,
+    // keyed by the table's serial number), the call's tables (the guides' words and planes, the rows, the selection's bounds
+    // and thresholds), the score records of a call that selects, and the milliseconds of the call's stages (score kernel,
+    // bounds + select, walk: vsc_debug_site_table_ms)
+    vsc::DeviceBuf bulge_table_buf, site_table_tabs, site_table_scores;
+    uint64_t bulge_table_serial = 0;  // 0: none resident
+    double site_table_ms[3] = {0, 0, 0};
     // the forest of the last classification call, as the kernels read it (prepare_forest in vsc_api.cpp)
     struct Forest {
         vsc::DeviceBuf nodes, ranks;   // nodes + tree depths + test table; activity ranks of the reads of a fused call
@@ -247,6 +254,15 @@ struct vsc_pattern_table {
     uint32_t zeros = 0;   // weights that are exactly 0
 };
 
+// A bulge score table (include/varscot_hip.h "TABLE" of vsc_bulge_hits_table; built and checked by vsc_bulge_table_build).
+// Host-only, immutable once built.
+struct vsc_bulge_table {
+    vsc::PatTableShape shape{};
+    double w[vsc::kPatTableMaxWeights + 2 * vsc::kPatTableMaxLen * 4] = {};  // the pattern table's, then dna, then rna (vsc_bulge_table.h)
+    uint64_t serial = 0;  // process-wide, handed out by vsc_bulge_table_build: what a context's device copy is keyed by
+    uint32_t zeros = 0;   // weights that are exactly 0
+};
+
 // An efficiency model (include/varscot_hip.h "MODEL"; built and checked by vsc_eff_model_build).  Host-only, immutable once built.
 struct vsc_eff_model {
     vsc::EffShape shape{};
@@ -304,7 +320,13 @@ struct vsc_guides : vsc::GuideList {};
 struct vsc_pattern_guides : vsc::GuideList {};
 struct vsc_bulge_hits : vsc::RecordList<vsc_bulge_hit> {};
 struct vsc_pattern_hits : vsc::RecordList<vsc_pattern_hit> {};
-struct vsc_sites : vsc::RecordList<vsc_site> {};
+struct vsc_sites : vsc::RecordList<vsc_site> {
+    // a scored result (vsc_sites_table): one vsc_site_score per record behind the records, scores_at bytes into storage
+    bool has_scores = false;
+    size_t scores_at = 0;
+    std::vector<vsc_site_score> scores_host;
+    bool scores_host_valid = false;
+};
 
 namespace vsc {
 // A genome object that only carries the contig table (no planes, nothing to search): what vsc_hits_merge_packed

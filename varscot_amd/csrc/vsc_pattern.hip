@@ -361,26 +361,6 @@ __device__ __forceinline__ void select_segment(const PatSelectArgs &a, uint32_t 
     *end = e;
 }
 
-// exclusive prefix of v over the workgroup's threads and *total = the sum; ws: kWavesPerGroup words of LDS
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *ws, uint32_t *total)
-{
-    const uint32_t lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    uint32_t wave_total;
-    const uint32_t in_wave = wave_exclusive(v, lane, &wave_total);
-    block_sync();  // (the last step's readers of ws are done)
-    if (lane == 0) ws[wave] = wave_total;
-    block_sync();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kWavesPerGroup; ++k) {
-        const uint32_t t = ws[k];
-        before += k < wave ? t : 0u;
-        all += t;
-    }
-    *total = all;
-    return before + in_wave;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kWave *kWavesPerGroup) void pattern_select_kernel(const PatSelectArgs a)
