@@ -1532,6 +1532,98 @@ int vsc_pattern_hits_scores(vsc_pattern_hits *hits, const uint32_t **fixed);
 /* Device pointer (valid until vsc_pattern_hits_free); NULL when the result is empty or not a scored one. */
 const void *vsc_pattern_hits_scores_dev(const vsc_pattern_hits *hits);
 
+/* ---- variant-aware pattern screen: any nuclease in an individual's genome ----------------------------- */
+/*
+ * The two mergers above for the records of vsc_search_pattern / vsc_search_pattern_table: sites of L = 16..32 bases, 20-byte
+ * vsc_pattern_hit records, the windows built with seq_len = L (vsc_windows_build).  Everything above holds with 23 replaced by L.
+ * WINDOW SIDE     Per record i of a pattern search of the window genome, in that search's order (guide, strand, contig, pos):
+ *                 pos1 = pos + (uint32) start(window); a variant is COVERED by [pos1, pos1 + L) under the rule above; an uncovered
+ *                 indel met before the first covered variant moves the position; pos2, n_var and the tag follow (getSnpType
+ *                 with seq_len = L).  key = (guide, chr number, pos2, strand, the site's L bases from the window planes, info
+ *                 word, mask word, tag ids).  The record is the ON-TARGET iff exclude[guide] names a locus, the window's
+ *                 reference contig, pos2 and the strand equal it, NM = 0 and n_var = 0; a DUPLICATE iff i > 0 and its key equals
+ *                 the key of record i - 1, whatever that record's own fate (the neighbour rule of the reference, kept on purpose);
+ *                 COUNTED otherwise.  The pattern search has no right-edge rule: a site that ends at a window's last base IS a
+ *                 hit here, although the plain search drops it - so at L = 23 the pattern records hold every record of the plain
+ *                 search and, besides, such sites.
+ * REFERENCE SIDE  A record of the same search of the reference genome is SHADOWED iff [pos, pos + L) lies fully inside one
+ *                 interval of vsc_variant_map_shadow's set (filterRefAlignment with seq_len = L): with the intervals sorted by
+ *                 start and end_max their running maximum, n = #{start <= pos}, inside iff n > 0 and end_max[n - 1] >= pos + L
+ *                 (vsc_regions_contains answers for 23-base windows only).  It is the ON-TARGET iff its (contig, pos, strand)
+ *                 equal exclude[guide] and NM = 0; COUNTED iff it is neither shadowed nor the on-target.
+ * THE INDIVIDUAL  A guide's rows in the individual's genome = the reference side's counted rows + the window side's counted
+ *                 rows, field by field.  All fields are integers.
+ * ROWS            vsc_pattern_variant_row { count[NM], on_target, dropped }, 48 bytes: count = counted records by NM;
+ *                 on_target = 1 if the on-target was met on that side; dropped = shadowed records (reference side), duplicates
+ *                 (window side), 0 in the rows over the VAR records.  With a table: vsc_guide_table_row over the same counted
+ *                 records (score_sum = the integer sum of their f words, positive, positive_nm).
+ */
+typedef struct {
+    uint32_t count[VSC_MAX_MISMATCHES + 1];
+    uint32_t on_target;
+    uint64_t dropped;
+} vsc_pattern_variant_row;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pattern_variant_row) == 48, "vsc_pattern_variant_row layout");
+#else
+_Static_assert(sizeof(vsc_pattern_variant_row) == 48, "vsc_pattern_variant_row layout");
+#endif
+#define VSC_PATTERN_REF_SHADOWED 1u  /* dropped: the site lies inside a window */
+#define VSC_PATTERN_REF_ON_TARGET 2u /* dropped: the guide's own locus */
+/* vsc_variant_map_locate / vsc_variant_map_tag for a site of len bases (16..32; len = 23: the same answers).  len outside
+ * 16..32, window >= the map's windows or a null argument: VSC_ERR_INVALID. */
+int vsc_variant_map_locate_len(const vsc_variant_map *map, uint32_t window, uint32_t pos, uint32_t len, vsc_variant_label *label);
+int64_t vsc_variant_map_tag_len(const vsc_variant_map *map, uint32_t window, uint32_t pos, uint32_t len, char *buf, size_t buflen);
+/* 1 if the len bases from pos of reference contig ref_contig on lie inside one shadow interval (REFERENCE SIDE above), else 0 -
+ * also where no site of len bases starts (pos + len beyond the contig).  len outside 16..32, ref_contig >= the reference's
+ * contigs or a null map: VSC_ERR_INVALID.  Replaces: the loop of filterRefAlignment (filter_output_bam.h:95-118) per record. */
+int vsc_variant_map_shadows(const vsc_variant_map *map, uint32_t ref_contig, uint32_t pos, uint32_t len);
+/*
+ * labels[i] = the label of record i of `hits`, a result of vsc_search_pattern / vsc_search_pattern_table on win_genome (on the
+ * hits' own context), flags included (WINDOW SIDE above); L = the length the hits were searched with.  exclude: NULL or
+ * n_guides loci in reference coordinates.  One kernel over the records where they lie (pattern_variant_merge_kernel: the
+ * records staged through LDS as coalesced words, the walk, the key compared with the neighbour's - cheap fields, covered tag ids
+ * in lockstep, the L bases of both sites from the resident planes).  Refusals (VSC_ERR_INVALID, vsc_last_error names them): a map
+ * whose window count or lengths differ from win_genome's contig table, a record outside the map or its window, a record guide
+ * >= n_guides when exclude is given, an exclude contig >= the reference's contigs (and not UINT32_MAX) or strand > 1, a null
+ * argument.  An empty result: VSC_OK, nothing is launched.  vsc_ctx_timing is left as it is.
+ * Replaces: filterSnpAlignment + getSnpType per record on the host (variant_processing/filter_output_bam.h:189-317).
+ */
+int vsc_pattern_hits_variants(vsc_pattern_hits *hits, const vsc_genome *win_genome, const vsc_variant_map *map,
+                              const vsc_locus *exclude, uint32_t n_guides, vsc_variant_label *labels);
+/*
+ * flags[i] = VSC_PATTERN_REF_SHADOWED | VSC_PATTERN_REF_ON_TARGET of record i of `hits`, a result of a pattern search of
+ * ref_genome, the genome the map's reference contigs describe (REFERENCE SIDE above; pattern_shadow_kernel).  Refusals as above,
+ * with a ref_genome whose contig table is not the map's reference in place of the window genome's.
+ * Replaces: filterRefAlignment per record on the host (variant_processing/filter_output_bam.h:70-124).
+ */
+int vsc_pattern_hits_shadowed(vsc_pattern_hits *hits, const vsc_genome *ref_genome, const vsc_variant_map *map,
+                              const vsc_locus *exclude, uint32_t n_guides, uint8_t *flags);
+/*
+ * The screen: both sides per guide, without the records.  ref_rows / win_rows = the rows over the counted records of either side
+ * (dropped: the shadowed records / the duplicates), var_rows (optional) = over the window side's counted VAR records; with a
+ * table (vsc_search_pattern_table's scores) ref_table / win_table / var_table = the table rows over the same records - without
+ * a table the three must be NULL.  All outputs: host memory, n_guides entries.  The guides are searched in chunks of chunk_guides
+ * (0 or more than 64: 64); each chunk is a whole (scored) pattern search per side under `params`, whose records stay on the
+ * device, are consumed where they lie and are freed; max_hits caps a chunk's records per side.  Chunks end on guide boundaries,
+ * so the rows depend neither on chunk_guides nor on guide_batch.  The map's device copy and the shadow arrays are kept by the
+ * context, keyed by the map's serial (vsc_ctx_release_scratch gives them back).  Refusals as for the two calls above, and: a
+ * table whose len is not `len`, table rows wanted without a table.  n_guides == 0: VSC_OK, nothing is launched.  A map without
+ * windows (a sample without alt alleles; no genome can be loaded from it) takes win_genome == NULL: the reference side alone.
+ * vsc_ctx_timing afterwards: the sums over the chunks' searches, the merge kernels in finalize_ms.
+ * Replaces, for a screen: the searches' records on the host + filterRefAlignment + filterSnpAlignment / getSnpType + the
+ * per-guide aggregation of the rows mergeResults prints (variant_processing/merge_output_bam.h:46-215).
+ * Not provided: bulged alignments and cut sites in windows, the merged records as one sorted result, top-K in the individual.
+ */
+int vsc_search_pattern_variants(vsc_ctx *ctx, const vsc_genome *ref_genome, const vsc_genome *win_genome,
+                                const vsc_variant_map *map, const char *pattern, const char *guides, uint32_t n_guides,
+                                uint32_t len, const vsc_pattern_params *params, const vsc_pattern_table *table /* may be NULL */,
+                                const vsc_locus *exclude /* may be NULL, reference coordinates */, uint32_t chunk_guides,
+                                vsc_pattern_variant_row *ref_rows, vsc_pattern_variant_row *win_rows,
+                                vsc_pattern_variant_row *var_rows /* may be NULL */,
+                                vsc_guide_table_row *ref_table, vsc_guide_table_row *win_table,
+                                vsc_guide_table_row *var_table /* the three: NULL without a table */);
+
 /* ---- table scores for bulged alignments and cut sites: per record, per guide, top-K sites --------------------- */
 /*
  * The score above over everything the searches report: the bulged alignments of vsc_search_bulges /
@@ -1598,8 +1690,8 @@ const void *vsc_pattern_hits_scores_dev(const vsc_pattern_hits *hits);
  * a table whose len is not len, params->len other than len, a result or a genome of another context: VSC_ERR_INVALID; an
  * empty input returns VSC_OK and launches nothing; the inputs and vsc_ctx_timing stay as they are.  The context keeps the
  * device copy of the table it used last, keyed by the serial number; vsc_ctx_release_scratch gives it back.
- * Not provided: weights, a maximum over split points, scores of variant-window hits, a vsc_multi_* entry (sites are defined
- * on merged records).
+ * Not provided: weights, a maximum over split points, scores of variant-window hits (since added for pattern hits: 4.25,
+ * vsc_search_pattern_variants above), a vsc_multi_* entry (sites are defined on merged records).
  */
 typedef struct vsc_bulge_table vsc_bulge_table;
 typedef struct {

@@ -57,6 +57,10 @@ REGION_KEEP, REGION_DROP = 0, 1
 # vsc_variant_label: a window hit in chromosome coordinates (vsc_hits_variants, vsc_variant_map_locate)
 VARIANT_LABEL_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("n_var", "<u4"), ("flags", "<u4")])
 VARIANT_VAR, VARIANT_DUP, VARIANT_ON_TARGET = 1, 2, 4  # VSC_VARIANT_*
+# vsc_pattern_variant_row: a guide's counted pattern hits of one side of the individual's genome (vsc_search_pattern_variants)
+PATTERN_VARIANT_ROW_DTYPE = np.dtype([("count", "<u4", (9,)), ("on_target", "<u4"), ("dropped", "<u8")])
+assert PATTERN_VARIANT_ROW_DTYPE.itemsize == 48
+PATTERN_REF_SHADOWED, PATTERN_REF_ON_TARGET = 1, 2  # VSC_PATTERN_REF_*
 REGION_NONE = 0xFFFFFFFF  # VSC_REGION_NONE: the label of a window that is in no interval
 
 
@@ -447,6 +451,13 @@ SYMBOLS = [
     ("vsc_variant_map_tag", C.c_int64, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
     ("vsc_hits_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     ("vsc_search_summary_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(SearchParams), _vp, C.c_uint32, _vp, _vp, _vp]),
+    ("vsc_variant_map_locate_len", C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    ("vsc_variant_map_tag_len", C.c_int64, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
+    ("vsc_variant_map_shadows", C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("vsc_pattern_hits_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("vsc_pattern_hits_shadowed", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp]),
+    ("vsc_search_pattern_variants", C.c_int, [_vp, _vp, _vp, _vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(PatternParams), _vp,
+                                              _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("vsc_rf_predict", C.c_int, [_vp, C.POINTER(RfModel), _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_rf_predict_packed", C.c_int, [_vp, C.POINTER(RfModel), _vp, C.c_int, _vp, C.c_uint64, _vp, _vp, _vp]),
     ("vsc_score_classify_hits", C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(RfModel), C.c_uint64, C.c_uint64, _vp, _vp, _vp]),

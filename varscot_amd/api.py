@@ -1011,21 +1011,38 @@ class VariantMap:
         check(lib().vsc_variant_map_shadow(self._h, C.byref(r._h)))
         return r
 
-    def locate(self, window, pos):
-        """vsc_variant_map_locate: the VARIANT_LABEL_DTYPE record of the window position - reference contig (0xFFFFFFFF:
-        unknown), position on the chromosome, covered variants, VARIANT_VAR."""
+    def locate(self, window, pos, length=23):
+        """vsc_variant_map_locate (length = 23) / vsc_variant_map_locate_len (a site of `length` = 16..32 bases): the
+        VARIANT_LABEL_DTYPE record of the window position - reference contig (0xFFFFFFFF: unknown), position on the chromosome,
+        covered variants, VARIANT_VAR."""
         out = np.zeros(1, dtype=_lib.VARIANT_LABEL_DTYPE)
-        check(lib().vsc_variant_map_locate(self._h, int(window), int(pos), ptr(out)))
+        if int(length) == READ_LEN:
+            check(lib().vsc_variant_map_locate(self._h, int(window), int(pos), ptr(out)))
+        else:
+            check(lib().vsc_variant_map_locate_len(self._h, int(window), int(pos), int(length), ptr(out)))
         return out[0]
 
-    def tag(self, window, pos):
-        """vsc_variant_map_tag: "REF" or "VAR_<chr>_<positions of the covered variants>"."""
-        n = int(lib().vsc_variant_map_tag(self._h, int(window), int(pos), None, 0))
+    def tag(self, window, pos, length=23):
+        """vsc_variant_map_tag / vsc_variant_map_tag_len: "REF" or "VAR_<chr>_<positions of the covered variants>" of the site of
+        `length` bases at the window position."""
+        if int(length) == READ_LEN:
+            call = lambda buf, n: lib().vsc_variant_map_tag(self._h, int(window), int(pos), buf, n)
+        else:
+            call = lambda buf, n: lib().vsc_variant_map_tag_len(self._h, int(window), int(pos), int(length), buf, n)
+        n = int(call(None, 0))
         if n < 0:
             check(n)
         buf = C.create_string_buffer(n + 1)
-        lib().vsc_variant_map_tag(self._h, int(window), int(pos), buf, n + 1)
+        call(buf, n + 1)
         return buf.value.decode()
+
+    def shadows(self, contig, pos, length):
+        """vsc_variant_map_shadows: do the `length` bases from `pos` of reference contig `contig` on lie inside one window's
+        interval - is a reference hit there shadowed by a window?"""
+        r = int(lib().vsc_variant_map_shadows(self._h, int(contig), int(pos), int(length)))
+        if r < 0:
+            check(r)
+        return bool(r)
 
     def info(self):
         """vsc_variant_map_info: windows, variants, unknown_chr (windows of a chromosome the reference does not have),
@@ -1044,6 +1061,47 @@ class VariantMap:
             self.close()
         except Exception:
             pass
+
+
+def individual_pattern_rows(ref, win):
+    """A guide's rows in the individual's genome: the reference side's counted rows plus the window side's (the `ref` and `win`
+    arrays of pattern_variants_screen, or its `ref_table` and `win_table`), field by field; on_target: met on either side;
+    `dropped` / `reserved` stay 0.  Rows of either dtype in, the same dtype out."""
+    out = np.zeros(len(ref), dtype=ref.dtype)
+    for f in ref.dtype.names:
+        if f == "on_target":
+            out[f] = (ref[f] != 0) | (win[f] != 0)
+        elif f not in ("dropped", "reserved"):
+            out[f] = ref[f] + win[f]
+    return out
+
+
+def pattern_variants_screen(ref_genome, win_genome, vmap, pattern, guides, max_mismatches, table=None, exclude=None, chunk=0, guide_batch=0,
+                            max_hits=0):
+    """vsc_search_pattern_variants: the pattern search of both genomes of an individual - ref_genome, the resident reference, and
+    win_genome, the resident variant windows built with seq_len = len(pattern) - merged per guide on the device.  Returns a dict
+    of PATTERN_VARIANT_ROW_DTYPE arrays "ref" (counted reference hits; dropped = shadowed by a window), "win" (counted window
+    hits; dropped = duplicates), "var" (the window hits that carry a variant) and, with a PatternTable, TABLE_ROW_DTYPE arrays
+    "ref_table", "win_table", "var_table" over the same records (None without a table).  exclude: None or one (contig, pos,
+    strand) per guide in reference coordinates; chunk: guides per search (0: 64) - the rows depend neither on it nor on
+    guide_batch; max_hits caps a chunk's records per side.  win_genome = None with a map without windows (a sample without alt
+    alleles): the reference side alone."""
+    p = pattern if isinstance(pattern, bytes) else pattern.encode()
+    gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+    for i, g in enumerate(gs):
+        if len(g) != len(p):
+            raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+    n = len(gs)
+    pp = _lib.PatternParams(int(max_mismatches), int(guide_batch), int(max_hits))
+    ex = _loci(exclude, n)
+    out = {k: np.zeros(n, dtype=_lib.PATTERN_VARIANT_ROW_DTYPE) for k in ("ref", "win", "var")}
+    for k in ("ref_table", "win_table", "var_table"):
+        out[k] = np.zeros(n, dtype=_lib.TABLE_ROW_DTYPE) if table is not None else None
+    ctx = ref_genome.ctx
+    check(lib().vsc_search_pattern_variants(ctx._h, ref_genome._h, win_genome._h if win_genome is not None else None, vmap._h, p, b"".join(gs), n, len(p), C.byref(pp),
+                                            table._h if table is not None else None, ptr(ex), int(chunk), ptr(out["ref"]), ptr(out["win"]),
+                                            ptr(out["var"]), ptr(out["ref_table"]), ptr(out["win_table"]), ptr(out["var_table"])), ctx._h)
+    return out
 
 
 def individual_rows(ref_all, ref_in, win_all):
@@ -1381,6 +1439,24 @@ class Genome:
         finally:
             L.vsc_pattern_hits_free(h)
         return recs, fixed, out_rows, out_table
+
+    def search_pattern_hits(self, pattern, guides, max_mismatches, table=None, max_hits=0, guide_batch=0):
+        """vsc_search_pattern (table=None) or vsc_search_pattern_table without a selection, the records kept on the device:
+        a PatternHits object (to_numpy, scores, variants, shadowed; close it when done)."""
+        p = pattern if isinstance(pattern, bytes) else pattern.encode()
+        gs = [g if isinstance(g, bytes) else g.encode() for g in guides]
+        for i, g in enumerate(gs):
+            if len(g) != len(p):
+                raise ValueError("guide %d has %d letters; the pattern has %d" % (i, len(g), len(p)))
+        pp = _lib.PatternParams(int(max_mismatches), int(guide_batch), int(max_hits))
+        h = C.c_void_p()
+        if table is None:
+            check(lib().vsc_search_pattern(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp), C.byref(h), None), self.ctx._h)
+        else:
+            sel = _lib.PatternSelect(0, 0)
+            check(lib().vsc_search_pattern_table(self.ctx._h, self._h, p, b"".join(gs), len(gs), len(p), C.byref(pp), table._h, C.byref(sel),
+                                                 C.byref(h), None, None), self.ctx._h)
+        return PatternHits(self, h, len(gs), len(p), table is not None)
 
     def _bulge_records(self, h):
         """(records,) of a bulge result, which is freed."""
@@ -2064,6 +2140,64 @@ class Hits:
         if self._h:
             if self._owned:
                 lib().vsc_hits_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PatternHits:
+    """Result of one pattern search kept on the device (vsc_pattern_hits; Genome.search_pattern_hits): PATTERN_HIT_DTYPE
+    records in ascending (guide, strand, contig, pos) order, with one f word per record when the search was scored."""
+
+    def __init__(self, genome, handle, n_guides, length, scored):
+        self.genome, self._h, self.n_guides, self.length, self.scored = genome, handle, n_guides, length, scored
+        self.ctx = genome.ctx
+        self.ctx._children.add(self)
+
+    def __len__(self):
+        return int(lib().vsc_pattern_hits_count(self._h))
+
+    def _copy(self, fn, itemsize, dtype):
+        n = len(self)
+        data = C.c_void_p()
+        check(fn(self._h, C.byref(data)), self.ctx._h)
+        if n == 0:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (n * itemsize)).from_address(data.value), dtype=dtype).copy()
+
+    def to_numpy(self):
+        return self._copy(lib().vsc_pattern_hits_data, 20, PATTERN_HIT_DTYPE)
+
+    def scores(self):
+        """vsc_pattern_hits_scores: f = rint(score * 2^30) per record of a scored search."""
+        if not self.scored:
+            raise ValueError("the search was not scored")
+        return self._copy(lib().vsc_pattern_hits_scores, 4, np.uint32)
+
+    def variants(self, vmap, exclude=None):
+        """vsc_pattern_hits_variants on a result of a window genome's pattern search: per record a VARIANT_LABEL_DTYPE row -
+        reference contig, position on the chromosome, covered variants, flags VARIANT_VAR / VARIANT_DUP / VARIANT_ON_TARGET.
+        exclude: None or one (contig, pos, strand) per guide in reference coordinates."""
+        labels = np.zeros(len(self), dtype=_lib.VARIANT_LABEL_DTYPE)
+        ex = _loci(exclude, self.n_guides)
+        check(lib().vsc_pattern_hits_variants(self._h, self.genome._h, vmap._h, ptr(ex), self.n_guides, ptr(labels)), self.ctx._h)
+        return labels
+
+    def shadowed(self, vmap, exclude=None):
+        """vsc_pattern_hits_shadowed on a result of the reference genome's pattern search: per record a uint8 of
+        PATTERN_REF_SHADOWED (the site lies inside a window of vmap) | PATTERN_REF_ON_TARGET (the guide's own locus)."""
+        flags = np.zeros(len(self), dtype=np.uint8)
+        ex = _loci(exclude, self.n_guides)
+        check(lib().vsc_pattern_hits_shadowed(self._h, self.genome._h, vmap._h, ptr(ex), self.n_guides, ptr(flags)), self.ctx._h)
+        return flags
+
+    def close(self):
+        if self._h:
+            lib().vsc_pattern_hits_free(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

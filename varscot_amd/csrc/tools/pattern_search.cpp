@@ -17,6 +17,12 @@
 // gains, behind all other columns, siteCount siteBulgeOnly; the listing goes under guide_summary -Z's columns
 //   #guideId chrom start end strand kind size index mismatches members sequence
 // Without -Z every output is what it was.
+// -v in.vcf [-n SAMPLE] (needs -O and -M) screens the guides in an individual's genome as well (vsc_search_pattern_variants):
+// variant windows of the pattern's length are built from the packed planes, searched on the same context and merged with the
+// reference hits per guide on the device.  -O gains indCount imm0 .. imm<M> (the reference hits no window shadows plus the
+// counted window hits) varCount vmm0 .. vmm<M> (the window hits that carry a variant) varDuplicates refShadowed, with -W also
+// indScoreSum indSpec varScoreSum.  With -E the enumerated loci are the excluded on-targets, with -R nothing is excluded.
+// Without -v every output is what it was.
 // -w bulge.tsv (needs -W, -u, -p and -Z) scores the cut sites on the device (vsc_sites_table): -W stays the base table, whose
 // protospacer must be -p's; the -w file holds `dna j s w` and `rna j g w` for every protospacer position j and base
 // (tools/README.md).  The -O summary gains siteScoreSum siteSpecScore sitePositive behind all other columns, the -Z listing
@@ -207,6 +213,11 @@ int main(int argc, char **argv)
         {'w', "bulge-table", "Path to the bulge weights (.tsv/.txt; lines 'dna j s w' and 'rna j g w', j = read position in the protospacer) beside "
                              "the -W table: the cut sites are scored; -O gains siteScoreSum siteSpecScore sitePositive, the -Z file tableScore "
                              "scoredAs, and -K / -S cut the -Z listing by the site's score; needs -W, -u, -p and -Z", false},
+        {'v', "vcf", "Path to a .vcf file: the guides are screened in that individual's genome as well (variant windows of the pattern's "
+                     "length; the reference hits no window shadows plus the window hits) - -O gains indCount imm0 .. imm<M> varCount "
+                     "vmm0 .. vmm<M> varDuplicates refShadowed, with -W also indScoreSum indSpec varScoreSum; needs -O and -M, not with "
+                     "-u -U -Z -w -T -K -S", false},
+        {'n', "sample", "With -v: 0-based sample column of the .vcf file (default 0)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -237,6 +248,31 @@ int main(int argc, char **argv)
     }
     const bool bulged = opts[14].set;
     const bool sited = opts[21].set;
+    // -v / -n: the individual
+    const bool individual = opts[23].set;
+    uint32_t vcf_sample = 0;
+    if (individual && !has_extension(opts[23].value, {"vcf"})) {
+        std::fprintf(stderr, "%s: the -v file must be a .vcf file\n", argv[0]);
+        return 1;
+    }
+    if (individual && (opts[14].set || opts[15].set || opts[21].set || opts[22].set || opts[6].set || opts[19].set || opts[20].set)) {
+        std::fprintf(stderr, "%s: -v screens plain pattern hits per guide: it does not combine with -u, -U, -Z, -w, -T, -K or -S\n", argv[0]);
+        return 1;
+    }
+    if (individual && (!opts[5].set || !opts[3].set)) {
+        std::fprintf(stderr, "%s: -v adds columns to the -O summary of a search: give -O and -M\n", argv[0]);
+        return 1;
+    }
+    if (opts[24].set) {
+        const std::string &v = opts[24].value;
+        char *nend = nullptr;
+        const long long k = std::strtoll(v.c_str(), &nend, 10);
+        if (!individual || v.empty() || *nend || k < 0 || k > 0xFFFFFFFFll) {
+            std::fprintf(stderr, "%s: -n takes the 0-based sample column of the -v file, not '%s'\n", argv[0], v.c_str());
+            return 1;
+        }
+        vcf_sample = (uint32_t)k;
+    }
     if (!enumerate && !opts[5].set && !opts[6].set && !(bulged && (opts[15].set || sited))) {
         std::fprintf(stderr, "%s: give -O, -T or both\n", argv[0]);
         return 1;
@@ -446,6 +482,9 @@ int main(int argc, char **argv)
     vsc_pattern_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
     vsc_sites *scored_sites = nullptr;
+    vsc_windows *windows = nullptr;
+    vsc_variant_map *vmap = nullptr;
+    vsc_genome *win_genome = nullptr;
     int rc = 1;
     try {
         std::vector<FastaRecord> guides;
@@ -560,6 +599,37 @@ int main(int argc, char **argv)
                     if (own_fixed[g]) table_rows[g].positive -= 1, table_rows[g].positive_nm[0] -= 1;
                 }
         }
+        // -v: the same search in the individual's genome - windows of the pattern's length from the packed planes, on the same
+        // context; with -E the enumerated loci are the excluded on-targets, with -R nothing is excluded
+        std::vector<vsc_pattern_variant_row> ind_ref(individual ? guides.size() : 0), ind_win(ind_ref.size()), ind_var(ind_ref.size());
+        std::vector<vsc_guide_table_row> ind_ref_table(individual && tabled ? guides.size() : 0), ind_win_table(ind_ref_table.size()),
+            ind_var_table(ind_ref_table.size());
+        if (individual) {
+            std::vector<const char *> names;
+            for (const std::string &n : ix.names) names.push_back(n.c_str());
+            char why[512] = "";
+            if (vsc_windows_build(opts[23].value.c_str(), vcf_sample, len, 0, ix.hi.data(), ix.lo.data(), ix.nm.data(), ix.contigs.data(), names.data(),
+                                  (uint32_t)ix.contigs.size(), &windows, why, sizeof why) != VSC_OK)
+                throw std::runtime_error(std::string("-v: ") + (why[0] ? why : "could not build the variant windows"));
+            const uint32_t n_win = vsc_windows_count(windows);
+            std::fprintf(stderr, "Variant windows built (total: %u).\n", n_win);
+            if (vsc_variant_map_build(n_win ? vsc_windows_name(windows, 0, nullptr) : nullptr, n_win ? vsc_windows_name_offsets(windows) : nullptr,
+                                      n_win ? vsc_windows_contigs(windows) : nullptr, n_win, ix.contigs.data(), names.data(),
+                                      (uint32_t)ix.contigs.size(), &vmap) != VSC_OK)
+                throw std::runtime_error("-v: could not parse the ids of the variant windows");
+            if (n_win) {
+                st = vsc_genome_load(ctx, vsc_windows_plane(windows, 0), vsc_windows_plane(windows, 1), vsc_windows_plane(windows, 2), 0,
+                                     vsc_windows_words(windows), vsc_windows_words(windows), vsc_windows_contigs(windows), n_win, &win_genome);
+                if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            }
+            vsc_pattern_params p{};
+            p.max_mismatches = (uint32_t)mm;
+            st = vsc_search_pattern_variants(ctx, genome, win_genome, vmap, pattern.c_str(), letters.c_str(), (uint32_t)guides.size(), len, &p, table,
+                                             enumerate ? loci : nullptr, 0, ind_ref.data(), ind_win.data(), ind_var.data(),
+                                             tabled ? ind_ref_table.data() : nullptr, tabled ? ind_win_table.data() : nullptr,
+                                             tabled ? ind_var_table.data() : nullptr);
+            if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+        }
         // the bulged sites of the same guides (the bulged neighbours of a found guide's own locus are among them)
         std::vector<vsc_bulge_summary> bulge_rows(bulged ? guides.size() : 0);
         const bool bulge_on[VSC_BULGE_CLASSES] = {bp.rna_max >= 2, bp.rna_max >= 1, bp.dna_max >= 1, bp.dna_max >= 2};
@@ -598,6 +668,14 @@ int main(int argc, char **argv)
             if (tabled) out << "\ttableScoreSum\ttableSpecScore\ttablePositive";
             if (sited) out << "\tsiteCount\tsiteBulgeOnly";
             if (site_scored) out << "\tsiteScoreSum\tsiteSpecScore\tsitePositive";
+            if (individual) {
+                out << "\tindCount";
+                for (long k = 0; k <= mm; ++k) out << "\timm" << k;
+                out << "\tvarCount";
+                for (long k = 0; k <= mm; ++k) out << "\tvmm" << k;
+                out << "\tvarDuplicates\trefShadowed";
+                if (tabled) out << "\tindScoreSum\tindSpec\tvarScoreSum";
+            }
             out << '\n';
             for (size_t g = 0; g < guides.size(); ++g) {
                 uint64_t total = 0;
@@ -626,6 +704,25 @@ int main(int argc, char **argv)
                     out << buf;
                     std::snprintf(buf, sizeof buf, "\t%.0f", std::floor(vsc_table_specificity(site_table_rows[g].score_sum) + 0.5));
                     out << buf << '\t' << site_table_rows[g].positive;
+                }
+                if (individual) {
+                    uint64_t ind_total = 0, var_total = 0;
+                    for (long k = 0; k <= mm; ++k) ind_total += (uint64_t)ind_ref[g].count[k] + ind_win[g].count[k], var_total += ind_var[g].count[k];
+                    out << '\t' << ind_total;
+                    for (long k = 0; k <= mm; ++k) out << '\t' << (uint64_t)ind_ref[g].count[k] + ind_win[g].count[k];
+                    out << '\t' << var_total;
+                    for (long k = 0; k <= mm; ++k) out << '\t' << ind_var[g].count[k];
+                    out << '\t' << ind_win[g].dropped << '\t' << ind_ref[g].dropped;
+                    if (tabled) {
+                        const uint64_t ind_sum = ind_ref_table[g].score_sum + ind_win_table[g].score_sum;
+                        char buf[64];
+                        std::snprintf(buf, sizeof buf, "\t%.6f", (double)ind_sum * 0x1p-30);
+                        out << buf;
+                        std::snprintf(buf, sizeof buf, "\t%.0f", std::floor(vsc_table_specificity(ind_sum) + 0.5));
+                        out << buf;
+                        std::snprintf(buf, sizeof buf, "\t%.6f", (double)ind_var_table[g].score_sum * 0x1p-30);
+                        out << buf;
+                    }
                 }
                 out << '\n';
             }
@@ -715,6 +812,9 @@ int main(int argc, char **argv)
     vsc_bulge_hits_free(bulge_hits);
     vsc_sites_free(sites);
     vsc_pattern_hits_free(site_plain);
+    vsc_genome_free(win_genome);
+    vsc_variant_map_free(vmap);
+    vsc_windows_free(windows);
     vsc_genome_free(genome);
     vsc_ctx_destroy(ctx);
     return rc;

@@ -39,6 +39,7 @@
 #include "vsc_bulge_table.h"
 #include "vsc_table.h"
 #include "vsc_varmap.h"
+#include "vsc_pattern_variants.h"
 
 using namespace vsc;
 
@@ -243,7 +244,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
                          &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
-                         &ctx->eff_out})
+                         &ctx->eff_out, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
@@ -252,6 +253,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
     ctx->varmap_serial = 0;
+    ctx->pv_shadow_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
     ctx->spare_records.clear();
     ctx->forest.nodes.release();
@@ -2639,9 +2641,13 @@ int resident_variant_map(vsc_ctx *ctx, const vsc_genome *win_genome, const vsc_v
 {
     if (win_genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
     const uint32_t n_win = (uint32_t)(map->win.size() - 1);
-    bool same = n_win == win_genome->n_contigs;
-    for (uint32_t c = 0; same && c < n_win; ++c) same = win_genome->h_contig_end[c] - win_genome->h_contig_off[c] == map->win_len[c];
+    // (both objects are immutable and the serial is process-wide: a pair that has passed need not be walked again - millions of
+    // windows per call otherwise)
+    bool same = win_genome->checked_map_serial == map->serial || n_win == win_genome->n_contigs;
+    for (uint32_t c = 0; same && win_genome->checked_map_serial != map->serial && c < n_win; ++c)
+        same = win_genome->h_contig_end[c] - win_genome->h_contig_off[c] == map->win_len[c];
     if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the variant map was built for another window genome");
+    win_genome->checked_map_serial = map->serial;
     for (uint32_t i = 0; exclude && i < n_guides; ++i)
         if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= map->ref_contigs.size()) || exclude[i].strand > 1)
             return fail_in(ctx, VSC_ERR_INVALID, who, "excluded locus outside the reference's contigs or strands");
@@ -3457,7 +3463,7 @@ static int search_pattern_call(vsc_ctx *ctx, const char *fn, const vsc_genome *g
         }
     }
     const uint32_t tables = table ? 3 : 2;
-    return run_rounds(
+    const int rounds_rc = run_rounds(
         ctx, plan, out, (uint32_t *)rows,
         // two tables, '+' and '-', one stride apart (scored: a third, the guides in read orientation)
         [tables](uint32_t n) { return tables * pattern_table_slots(n); },
@@ -3488,6 +3494,8 @@ static int search_pattern_call(vsc_ctx *ctx, const char *fn, const vsc_genome *g
             }
             return write ? launch_pattern_write(a, ctx->n_cus, ctx->stream) : launch_pattern_count(a, ctx->n_cus, ctx->stream);
         });
+    if (rounds_rc == VSC_OK && out && *out) (*out)->site_len = len;  // (what vsc_pattern_hits_variants walks with)
+    return rounds_rc;
     });
 }
 
@@ -3599,6 +3607,246 @@ uint64_t vsc_pattern_hits_count(const vsc_pattern_hits *hits) { return hits ? hi
 int vsc_pattern_hits_data(vsc_pattern_hits *hits, const vsc_pattern_hit **out) { return record_list_data(hits, out); }
 const void *vsc_pattern_hits_data_dev(const vsc_pattern_hits *hits) { return record_list_data_dev(hits); }
 int vsc_pattern_hits_free(vsc_pattern_hits *hits) { return object_free(hits); }
+
+// ---- variant-aware pattern screen (kernels: vsc_pattern_variants.hip) ------------------------------------------
+// The window side's tables: resident_variant_map's checks and device copies, as the pattern kernels read them.
+static int pv_bind_window(vsc_ctx *ctx, const vsc_genome *win_genome, const vsc_variant_map *map, const vsc_locus *exclude, uint32_t n_guides,
+                          const char *who, PatVarArgs &a)
+{
+    VariantArgs v{};
+    const int rc = resident_variant_map(ctx, win_genome, map, exclude, n_guides, who, v);
+    if (rc != VSC_OK) return rc;
+    a.map = v.map;
+    a.hi = v.hi;
+    a.lo = v.lo;
+    a.first_pos = v.first_pos;
+    a.n_plane_words = v.n_plane_words;
+    a.contig_off = v.contig_off;
+    a.contig_end = v.contig_end;
+    a.n_contigs = v.map.n_windows;
+    a.exclude = v.exclude;
+    a.n_guides = n_guides;
+    return VSC_OK;
+}
+
+// The reference side's: ref_genome carries the contig table the map was built over; the shadow intervals - start[], then
+// end_max[] - in one buffer keyed by the map's serial; the excluded loci in `excl` (the window side's copy, or this call's).
+static int pv_bind_reference(vsc_ctx *ctx, const vsc_genome *ref_genome, const vsc_variant_map *map, const vsc_locus *exclude,
+                             uint32_t n_guides, const uint4 *resident_exclude, const char *who, PatVarArgs &a)
+{
+    if (ref_genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    bool same = ref_genome->n_contigs == map->ref_contigs.size();
+    for (uint32_t c = 0; same && c < ref_genome->n_contigs; ++c)
+        same = ref_genome->h_contig_off[c] == map->ref_contigs[c].offset &&
+               ref_genome->h_contig_end[c] - ref_genome->h_contig_off[c] == map->ref_contigs[c].length;
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the variant map was built over another reference genome");
+    for (uint32_t i = 0; exclude && i < n_guides; ++i)
+        if ((exclude[i].contig != UINT32_MAX && exclude[i].contig >= map->ref_contigs.size()) || exclude[i].strand > 1)
+            return fail_in(ctx, VSC_ERR_INVALID, who, "excluded locus outside the reference's contigs or strands");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = map->shadow_start.size(), bytes = n * sizeof(uint32_t);
+    if (ctx->pv_shadow_serial != map->serial) {
+        ctx->pv_shadow_serial = 0;
+        VSC_HIP(ctx, ctx->pv_shadow_buf.ensure(2 * bytes + 256));  // (never empty: a device copy has an address)
+        if (n) {
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->pv_shadow_buf.p, map->shadow_start.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->pv_shadow_buf.p + bytes, map->shadow_end_max.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the map as soon as its call returns)
+        ctx->pv_shadow_serial = map->serial;
+    }
+    a.sh_start = (const uint32_t *)ctx->pv_shadow_buf.p;
+    a.sh_end_max = (const uint32_t *)((const char *)ctx->pv_shadow_buf.p + bytes);
+    a.sh_n = (uint32_t)n;
+    a.contig_off = ref_genome->d_contig_off;
+    a.contig_end = ref_genome->d_contig_end;
+    a.n_contigs = ref_genome->n_contigs;
+    a.n_guides = n_guides;
+    a.exclude = nullptr;
+    if (exclude && n_guides) {
+        if (resident_exclude) a.exclude = resident_exclude;
+        else {
+            VSC_HIP(ctx, ctx->var_excl.ensure((size_t)n_guides * sizeof(vsc_locus)));
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->var_excl.p, exclude, (size_t)n_guides * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+            a.exclude = (const uint4 *)ctx->var_excl.p;
+        }
+    }
+    return VSC_OK;
+}
+
+// A call's state on the device: the error flag (its own 256 bytes), then `extra` zeroed bytes (the screen's rows).
+constexpr size_t kPvStateHead = 256;
+static int pv_state(vsc_ctx *ctx, size_t extra)
+{
+    VSC_HIP(ctx, ctx->pv_state.ensure(kPvStateHead + extra));
+    VSC_HIP(ctx, hipMemsetAsync(ctx->pv_state.p, 0, kPvStateHead + extra, ctx->stream));
+    return VSC_OK;
+}
+
+// has a kernel met a record outside the tables? (after the stream has been waited for)
+static int pv_error(vsc_ctx *ctx, const char *who)
+{
+    uint32_t bad = 0;
+    VSC_HIP(ctx, hipMemcpy(&bad, ctx->pv_state.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail_in(ctx, VSC_ERR_INVALID, who, "a record lies outside the variant map, its window or contig, or the guides");
+    return VSC_OK;
+}
+
+// the records of a pattern result (and, scored, their f words) where they lie
+static void pv_bind_records(const vsc_pattern_hits *hits, PatVarArgs &a)
+{
+    a.records = (const uint32_t *)hits->storage.p;
+    a.fixed = hits->has_side ? (const uint32_t *)((const char *)hits->storage.p + hits->side_at) : nullptr;
+    a.n = hits->n;
+    a.len = hits->site_len;
+}
+
+int vsc_pattern_hits_variants(vsc_pattern_hits *hits, const vsc_genome *win_genome, const vsc_variant_map *map, const vsc_locus *exclude,
+                              uint32_t n_guides, vsc_variant_label *labels)
+{
+    if (!hits || !hits->ctx) return VSC_ERR_INVALID;
+    vsc_ctx *ctx = hits->ctx;
+    const char *const who = "vsc_pattern_hits_variants";
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    if (!win_genome || !map || (hits->n && !labels)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    PatVarArgs a{};
+    int rc = pv_bind_window(ctx, win_genome, map, exclude, n_guides, who, a);
+    if (rc != VSC_OK || hits->n == 0) return rc;
+    if (hits->site_len < kPatVarMinLen || hits->site_len > kPatVarMaxLen) return fail_in(ctx, VSC_ERR_INVALID, who, "the records are no pattern search's");
+    if ((rc = pv_state(ctx, 0)) != VSC_OK) return rc;
+    a.error = (uint32_t *)ctx->pv_state.p;
+    pv_bind_records(hits, a);
+    a.fixed = nullptr;  // (labels only: the scores are not read)
+    VSC_HIP(ctx, ctx->var_labels.ensure(hits->n * sizeof(vsc_variant_label)));
+    a.labels = (uint4 *)ctx->var_labels.p;
+    VSC_HIP(ctx, launch_pattern_variant_merge(a, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(labels, a.labels, hits->n * sizeof(vsc_variant_label), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return pv_error(ctx, who);
+    });
+}
+
+int vsc_pattern_hits_shadowed(vsc_pattern_hits *hits, const vsc_genome *ref_genome, const vsc_variant_map *map, const vsc_locus *exclude,
+                              uint32_t n_guides, uint8_t *flags)
+{
+    if (!hits || !hits->ctx) return VSC_ERR_INVALID;
+    vsc_ctx *ctx = hits->ctx;
+    const char *const who = "vsc_pattern_hits_shadowed";
+    return guarded(ctx, [&]() -> int {
+    ctx->err.clear();
+    if (!ref_genome || !map || (hits->n && !flags)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    PatVarArgs a{};
+    int rc = pv_bind_reference(ctx, ref_genome, map, exclude, n_guides, nullptr, who, a);
+    if (rc != VSC_OK || hits->n == 0) return rc;
+    if (hits->site_len < kPatVarMinLen || hits->site_len > kPatVarMaxLen) return fail_in(ctx, VSC_ERR_INVALID, who, "the records are no pattern search's");
+    if ((rc = pv_state(ctx, 0)) != VSC_OK) return rc;
+    a.error = (uint32_t *)ctx->pv_state.p;
+    pv_bind_records(hits, a);
+    a.fixed = nullptr;
+    VSC_HIP(ctx, ctx->pv_flags.ensure(hits->n));
+    a.flags = (uint8_t *)ctx->pv_flags.p;
+    VSC_HIP(ctx, launch_pattern_shadow(a, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(flags, a.flags, hits->n, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return pv_error(ctx, who);
+    });
+}
+
+int vsc_search_pattern_variants(vsc_ctx *ctx, const vsc_genome *ref_genome, const vsc_genome *win_genome, const vsc_variant_map *map,
+                                const char *pattern, const char *guides, uint32_t n_guides, uint32_t len, const vsc_pattern_params *params,
+                                const vsc_pattern_table *table, const vsc_locus *exclude, uint32_t chunk_guides,
+                                vsc_pattern_variant_row *ref_rows, vsc_pattern_variant_row *win_rows, vsc_pattern_variant_row *var_rows,
+                                vsc_guide_table_row *ref_table, vsc_guide_table_row *win_table, vsc_guide_table_row *var_table)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const who = "vsc_search_pattern_variants";
+    static_assert(sizeof(vsc_pattern_variant_row) == sizeof(PatVarRow), "the rows are the kernels'");
+    static_assert(sizeof(vsc_guide_table_row) == kPatVarTableWords * sizeof(unsigned long long), "a table row is its twelve words");
+    PatVarArgs aw{}, ar{};
+    const size_t row_bytes = (size_t)n_guides * sizeof(PatVarRow), table_bytes = (size_t)n_guides * sizeof(vsc_guide_table_row);
+    const int rc = guarded(ctx, [&]() -> int {
+        ctx->err.clear();
+        // (a sample without alt alleles has no windows and no window genome: win_genome may be null with such a map)
+        if (!ref_genome || !map || (!win_genome && map->win.size() > 1) || !pattern || !params || (n_guides && (!guides || !ref_rows || !win_rows)))
+            return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+        if (!table && (ref_table || win_table || var_table)) return fail_in(ctx, VSC_ERR_INVALID, who, "table rows are asked for without a table");
+        if (table && n_guides && (!ref_table || !win_table)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+        if (len < kPatVarMinLen || len > kPatVarMaxLen) return fail_in(ctx, VSC_ERR_INVALID, who, "the pattern must have 16..32 letters");
+        if (table && table->shape.len != len) return fail_in(ctx, VSC_ERR_INVALID, who, "the table is built for another length");
+        int brc = win_genome ? pv_bind_window(ctx, win_genome, map, exclude, n_guides, who, aw) : VSC_OK;
+        if (brc != VSC_OK) return brc;
+        if ((brc = pv_bind_reference(ctx, ref_genome, map, exclude, n_guides, aw.exclude, who, ar)) != VSC_OK) return brc;
+        return pv_state(ctx, 3 * row_bytes + 3 * table_bytes);
+    });
+    if (rc != VSC_OK) return rc;
+    char *const state = (char *)ctx->pv_state.p;
+    PatVarRow *const d_rows = (PatVarRow *)(state + kPvStateHead);  // ref, win, var
+    unsigned long long *const d_table = (unsigned long long *)(state + kPvStateHead + 3 * row_bytes);
+    const size_t table_words = (size_t)n_guides * kPatVarTableWords;
+    aw.error = ar.error = (uint32_t *)state;
+    const uint32_t chunk = chunk_guides == 0 || chunk_guides > 64 ? 64 : chunk_guides;
+    vsc_timing sum{};
+    sum.index_ms = ctx->timing.index_ms;
+    sum.algorithm = VSC_ALGO_SCAN;
+    for (uint32_t g0 = 0; g0 < n_guides; g0 += chunk) {
+        const uint32_t cn = std::min(chunk, n_guides - g0);
+        for (int side = 0; side < (win_genome ? 2 : 1); ++side) {  // the reference, then the windows
+            vsc_pattern_hits *hits = nullptr;
+            const int src = search_pattern_call(ctx, who, side ? win_genome : ref_genome, pattern, guides + (size_t)g0 * len, cn, len, params, table,
+                                                nullptr, &hits, nullptr, nullptr);
+            if (src != VSC_OK) return src;
+            std::unique_ptr<vsc_pattern_hits, int (*)(vsc_pattern_hits *)> holder(hits, object_free<vsc_pattern_hits>);
+            const vsc_timing &t = ctx->timing;
+            sum.scan_ms += t.scan_ms;
+            sum.score_ms += t.score_ms;
+            sum.total_ms += t.total_ms;
+            sum.hits += t.hits;
+            sum.sites += t.sites;
+            sum.pairs += t.pairs;
+            sum.passes += t.passes;
+            sum.genome_bytes += t.genome_bytes;
+            if (hits->n == 0) continue;
+            const int mrc = guarded(ctx, [&]() -> int {
+                PatVarArgs &a = side ? aw : ar;
+                pv_bind_records(hits, a);
+                const uint4 *const all_exclude = a.exclude;
+                if (all_exclude) a.exclude = all_exclude + g0;  // the chunk's guides are numbered from 0
+                a.n_guides = cn;
+                a.rows_all = d_rows + (side ? n_guides : 0) + g0;
+                a.rows_var = side && var_rows ? d_rows + 2 * (size_t)n_guides + g0 : nullptr;
+                a.table_all = table ? d_table + (side ? table_words : 0) + (size_t)g0 * kPatVarTableWords : nullptr;
+                a.table_var = side && table && var_table ? d_table + 2 * table_words + (size_t)g0 * kPatVarTableWords : nullptr;
+                VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+                const hipError_t le = side ? launch_pattern_variant_merge(a, ctx->stream) : launch_pattern_shadow(a, ctx->stream);
+                a.exclude = all_exclude;
+                VSC_HIP(ctx, le);
+                VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+                VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the records are freed when this round ends)
+                float ms = 0;
+                VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+                sum.finalize_ms += ms;
+                sum.total_ms += ms;
+                return VSC_OK;
+            });
+            if (mrc != VSC_OK) return mrc;
+        }
+    }
+    return guarded(ctx, [&]() -> int {
+        ctx->timing = sum;
+        if (n_guides == 0) return VSC_OK;
+        VSC_HIP(ctx, hipMemcpyAsync(ref_rows, d_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(win_rows, d_rows + n_guides, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (var_rows) VSC_HIP(ctx, hipMemcpyAsync(var_rows, d_rows + 2 * (size_t)n_guides, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (table) {
+            VSC_HIP(ctx, hipMemcpyAsync(ref_table, d_table, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(win_table, d_table + table_words, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (var_table) VSC_HIP(ctx, hipMemcpyAsync(var_table, d_table + 2 * table_words, table_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return pv_error(ctx, who);
+    });
+}
 
 int vsc_pattern_match(const char *pattern, const char *guide, const char *site_text, uint32_t len, uint32_t *hit, uint32_t *nm, uint32_t *mask)
 {

@@ -142,6 +142,10 @@ struct vsc_ctx {
     // duplicate counts), the excluded loci in reference coordinates, and the labels on their way to the host
     vsc::DeviceBuf varmap_buf, var_state, var_excl, var_labels;
     uint64_t varmap_serial = 0;  // 0: none resident
+    // the pattern variant screen: the shadow intervals of the map last used (start[], then end_max[]), the call's
+    // state (error flag and rows), and the flags of vsc_pattern_hits_shadowed
+    vsc::DeviceBuf pv_shadow_buf, pv_state, pv_flags;
+    uint64_t pv_shadow_serial = 0;
     // vsc_guides_enumerate: the work list (tiles to visit), the per-tile counts and their exclusive scan;
     // vsc_guides_enumerate_pattern: the same three parts, then the targets' start ranges
     vsc::DeviceBuf enum_tabs;
@@ -198,6 +202,7 @@ struct vsc_genome {
     uint64_t device_bytes = 0;
     // sites, seen_rate, sort_slots_ok: sizing hints that searches learn (mutable: a search takes the genome as const)
     mutable uint64_t sites = 0;  // PAM-valid windows seen by the last scan (sizes the next hit buffer)
+    mutable uint64_t checked_map_serial = 0;  // the vsc_variant_map whose windows were last found to be this genome's contigs (0: none)
     // hits per read the last search with mismatch budget m produced (scan: all reads; seed: the fullest output
     // region) - real genomes are not the uniform model the first buffer size comes from
     mutable double seen_rate[VSC_MAX_MISMATCHES + 1] = {};
@@ -309,6 +314,7 @@ template <class Rec> struct RecordList {
     size_t side_at = 0;
     std::vector<uint32_t> side_host;
     bool side_host_valid = false;
+    uint32_t site_len = 0;  // a pattern search: the length L it was searched with (what vsc_pattern_hits_variants walks with)
 };
 
 }  // namespace vsc

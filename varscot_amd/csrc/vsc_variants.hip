@@ -57,7 +57,7 @@ __global__ __launch_bounds__(kVarThreads) void variant_merge_kernel(const Varian
     uint32_t pos2 = 0, n_var = ~0u;
     if (have) {
         r = a.records[i];
-        if (var_record_ok(a, r)) varmap_walk(a.map, r.y, r.z, &pos2, &n_var);
+        if (var_record_ok(a, r)) varmap_walk(a.map, r.y, r.z, VSC_READ_LEN, &pos2, &n_var);
         else *a.error = 1u;
     }
     const bool ok = n_var != ~0u;
@@ -78,11 +78,11 @@ __global__ __launch_bounds__(kVarThreads) void variant_merge_kernel(const Varian
             } else {  // the record before this workgroup's first
                 q = a.records[i - 1];
                 ql = make_uint2(0u, ~0u);
-                if (var_record_ok(a, q)) varmap_walk(a.map, q.y, q.z, &ql.x, &ql.y);
+                if (var_record_ok(a, q)) varmap_walk(a.map, q.y, q.z, VSC_READ_LEN, &ql.x, &ql.y);
             }
             // key = (guide, chr, pos2, strand, bases, mask, tag): the info word holds strand and mask
             if (ql.y != ~0u && q.x == r.x && q.w == r.w && ql.x == pos2 && ql.y == n_var && a.map.win[q.y].chr_id == win.chr_id) {
-                bool same = n_var == 0 || var_tags_equal(a.map, r.y, r.z, q.y, q.z, n_var);
+                bool same = n_var == 0 || var_tags_equal(a.map, r.y, r.z, q.y, q.z, n_var, VSC_READ_LEN);
                 if (same) {
                     uint32_t rh, rl, qh, ql2;
                     var_site_planes(a, r, rh, rl);

@@ -10,7 +10,9 @@
 #include <unordered_map>
 #include <vector>
 
-#include "vsc_varmap.h"
+#include <algorithm>
+
+#include "vsc_pattern_variants.h"
 
 using namespace vsc;
 
@@ -84,6 +86,23 @@ int vsc_variant_map_build(const char *ids, const uint64_t *id_offsets, const vsc
             m->win_len.push_back(window_contigs[w].length);
         }
         m->win.push_back(VarWindow{UINT32_MAX, 0u, (uint32_t)m->var.size(), UINT32_MAX});
+        // the shadow intervals as vsc_variant_map_shadow hands them to vsc_regions_build: cut at the contig's end, sorted
+        std::vector<std::pair<uint32_t, uint32_t>> iv;
+        for (uint32_t w = 0; w < n_windows; ++w) {
+            const VarWindow &vw = m->win[w];
+            if (vw.contig == UINT32_MAX || (int32_t)vw.start < 0) continue;
+            const vsc_contig &rc = m->ref_contigs[vw.contig];
+            const uint64_t end = std::min<uint64_t>((uint64_t)vw.start + m->win_len[w], rc.length);
+            if (vw.start >= end) continue;
+            iv.emplace_back((uint32_t)(rc.offset + vw.start), (uint32_t)(rc.offset + end));
+        }
+        std::sort(iv.begin(), iv.end());
+        uint32_t run = 0;
+        for (const auto &i : iv) {
+            run = std::max(run, i.second);
+            m->shadow_start.push_back(i.first);
+            m->shadow_end_max.push_back(run);
+        }
         m->stats.windows = n_windows;
         m->stats.variants = m->var.size();
         m->serial = g_serial.fetch_add(1, std::memory_order_relaxed) + 1;
@@ -127,16 +146,36 @@ int vsc_variant_map_shadow(const vsc_variant_map *map, vsc_regions **out)
 
 int vsc_variant_map_locate(const vsc_variant_map *map, uint32_t window, uint32_t pos, vsc_variant_label *label)
 {
-    if (!map || !label || (size_t)window + 1 >= map->win.size()) return VSC_ERR_INVALID;
+    return vsc_variant_map_locate_len(map, window, pos, VSC_READ_LEN, label);
+}
+
+int vsc_variant_map_locate_len(const vsc_variant_map *map, uint32_t window, uint32_t pos, uint32_t len, vsc_variant_label *label)
+{
+    if (!map || !label || (size_t)window + 1 >= map->win.size() || len < kPatVarMinLen || len > kPatVarMaxLen) return VSC_ERR_INVALID;
     uint32_t pos2, n_var;
-    varmap_walk(map->view(), window, pos, &pos2, &n_var);
+    varmap_walk(map->view(), window, pos, len, &pos2, &n_var);
     *label = vsc_variant_label{map->win[window].contig, pos2, n_var, n_var ? VSC_VARIANT_VAR : 0u};
     return VSC_OK;
 }
 
+int vsc_variant_map_shadows(const vsc_variant_map *map, uint32_t ref_contig, uint32_t pos, uint32_t len)
+{
+    if (!map || ref_contig >= map->ref_contigs.size() || len < kPatVarMinLen || len > kPatVarMaxLen) return VSC_ERR_INVALID;
+    const vsc_contig &rc = map->ref_contigs[ref_contig];
+    if (rc.length < len || pos > rc.length - len) return 0;  // (no site of len bases starts there)
+    return shadow_search(map->shadow_start.data(), map->shadow_end_max.data(), (uint32_t)map->shadow_start.size(),
+                         (uint32_t)(rc.offset + pos), len) ? 1 : 0;
+}
+
 int64_t vsc_variant_map_tag(const vsc_variant_map *map, uint32_t window, uint32_t pos, char *buf, size_t len)
 {
-    if (!map || (len && !buf) || (size_t)window + 1 >= map->win.size()) return VSC_ERR_INVALID;
+    return vsc_variant_map_tag_len(map, window, pos, VSC_READ_LEN, buf, len);
+}
+
+int64_t vsc_variant_map_tag_len(const vsc_variant_map *map, uint32_t window, uint32_t pos, uint32_t site_len, char *buf, size_t len)
+{
+    if (!map || (len && !buf) || (size_t)window + 1 >= map->win.size() || site_len < kPatVarMinLen || site_len > kPatVarMaxLen)
+        return VSC_ERR_INVALID;
     try {
         const VarMapView v = map->view();
         const uint32_t pos1 = pos + v.win[window].start;
@@ -144,7 +183,7 @@ int64_t vsc_variant_map_tag(const vsc_variant_map *map, uint32_t window, uint32_
         uint32_t b, e;
         var_range(v, window, &b, &e);
         for (uint32_t k = b; k < e; ++k)
-            if (var_covered(v.var[k], pos1)) {
+            if (var_covered(v.var[k], pos1, site_len)) {
                 tag += tag.empty() ? "VAR_" + map->chr_names[v.win[window].chr_id] + "_" : std::string(",");
                 tag.append(map->text, map->text_off[k], map->text_off[k + 1] - map->text_off[k]);
             }

@@ -33,11 +33,12 @@ struct VarMapView {
     uint32_t n_windows, n_variants;
 };
 
-// Is the variant covered by the 23 bases from pos1 on?  A substitution of equal lengths by its position, an indel by its two
-// end points p + 1 and p + max(len) - 1 (:203-252; the reference computes in long).
-__host__ __device__ inline bool var_covered(const VarEntry &e, uint32_t pos1)
+// Is the variant covered by the `len` bases from pos1 on (len = the site's length: VSC_READ_LEN for the plain search, the
+// pattern's L for pattern hits)?  A substitution of equal lengths by its position, an indel by its two end points
+// p + 1 and p + max(len) - 1 (:203-252; the reference computes in long).
+__host__ __device__ inline bool var_covered(const VarEntry &e, uint32_t pos1, uint32_t len)
 {
-    const long long lo = (long long)pos1, hi = lo + VSC_READ_LEN, p = e.p;
+    const long long lo = (long long)pos1, hi = lo + (long long)len, p = e.p;
     if (e.len_ref == e.len_alt) return lo <= p && p < hi;
     const long long far = p + (long long)(e.len_ref > e.len_alt ? e.len_ref : e.len_alt) - 1;
     return (lo <= p + 1 && p + 1 < hi) || (lo <= far && far < hi);
@@ -53,34 +54,35 @@ __host__ __device__ inline void var_range(const VarMapView &m, uint32_t w, uint3
     *e = last;
 }
 
-// getSnpType for the window position (w, pos), w < n_windows: pos1 = pos + start; the covered variants are counted, an
-// uncovered indel before the first covered variant moves the position by len_ref - len_alt (int arithmetic in the reference:
-// 32-bit wrap here); *pos2 = pos1 + that sum, *n_var = covered variants.
-__host__ __device__ inline void varmap_walk(const VarMapView &m, uint32_t w, uint32_t pos, uint32_t *pos2, uint32_t *n_var)
+// getSnpType for the site of `len` bases at the window position (w, pos), w < n_windows: pos1 = pos + start; the covered
+// variants are counted, an uncovered indel before the first covered variant moves the position by len_ref - len_alt (int
+// arithmetic in the reference: 32-bit wrap here); *pos2 = pos1 + that sum, *n_var = covered variants.
+__host__ __device__ inline void varmap_walk(const VarMapView &m, uint32_t w, uint32_t pos, uint32_t len, uint32_t *pos2, uint32_t *n_var)
 {
     const uint32_t pos1 = pos + m.win[w].start;
     uint32_t b, e, shift = 0, n = 0;
     var_range(m, w, &b, &e);
     for (uint32_t k = b; k < e; ++k) {
         const VarEntry v = m.var[k];
-        if (var_covered(v, pos1)) ++n;
+        if (var_covered(v, pos1, len)) ++n;
         else if (n == 0 && v.len_ref != v.len_alt) shift += v.len_ref - v.len_alt;
     }
     *pos2 = pos1 + shift;
     *n_var = n;
 }
 
-// Do the two window positions carry the same tag?  Both have n covered variants (n > 0: the caller has compared the counts and
+// Do the two sites of `len` bases at two window positions carry the same tag?  Both have n covered variants (n > 0: the caller has compared the counts and
 // the chromosomes): the covered tag ids of the two windows, in lockstep.
-__host__ __device__ inline bool var_tags_equal(const VarMapView &m, uint32_t wa, uint32_t posa, uint32_t wb, uint32_t posb, uint32_t n)
+__host__ __device__ inline bool var_tags_equal(const VarMapView &m, uint32_t wa, uint32_t posa, uint32_t wb, uint32_t posb, uint32_t n,
+                                              uint32_t len)
 {
     const uint32_t pa = posa + m.win[wa].start, pb = posb + m.win[wb].start;
     uint32_t ka, ea, kb, eb;
     var_range(m, wa, &ka, &ea);
     var_range(m, wb, &kb, &eb);
     for (uint32_t i = 0; i < n; ++i) {
-        while (ka < ea && !var_covered(m.var[ka], pa)) ++ka;
-        while (kb < eb && !var_covered(m.var[kb], pb)) ++kb;
+        while (ka < ea && !var_covered(m.var[ka], pa, len)) ++ka;
+        while (kb < eb && !var_covered(m.var[kb], pb, len)) ++kb;
         if (ka >= ea || kb >= eb) return false;  // (cannot happen with the counts equal)
         if (m.var[ka].tag_id != m.var[kb].tag_id) return false;
         ++ka;
@@ -120,6 +122,9 @@ struct vsc_variant_map {
     std::vector<std::string> chr_names;
     std::string text;
     std::vector<uint32_t> text_off;   // n_variants + 1
+    // the shadow intervals of vsc_variant_map_shadow in the reference's global positions, sorted by start: start[] and the
+    // running maximum of their ends (vsc::shadow_search, vsc_pattern_variants.h: the reference side for a site of any length)
+    std::vector<uint32_t> shadow_start, shadow_end_max;
     uint64_t serial = 0;  // process-wide, as vsc_regions': what a context's device copy is keyed by
     vsc_variant_map_stats stats{};
     vsc::VarMapView view() const { return vsc::VarMapView{win.data(), var.data(), (uint32_t)(win.size() - 1), (uint32_t)var.size()}; }
