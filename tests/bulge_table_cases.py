@@ -3,6 +3,8 @@ in plain Python, letter by letter.  Nothing here calls the library: py_bulge_sco
 one site, one d and one split point in IEEE doubles and the fixed order; member() recomputes (NM, i) with
 pattern_bulge_cases.best; site_scores() is the member loop of a cut site; bulged_scored() / site_records() / rows / cut() apply
 them to the alignments and sites of the other *_cases restatements."""
+import functools
+
 import numpy as np
 
 import pattern_bulge_cases as pbc
@@ -80,9 +82,12 @@ def member(table, guide, s, d):
     return nm, i, ptc.py_fixed(py_bulge_score(table, guide, s, d, i))
 
 
+_clean = functools.lru_cache(maxsize=16)(pc.genome_of)  # (a contig's letters once, not once per site)
+
+
 def text_of(contigs, strand, c, pos, n):
     """The n letters at forward position pos of contig c in read orientation."""
-    w = pc.genome_of(contigs[c])[pos:pos + n]
+    w = _clean(contigs[c])[pos:pos + n]
     assert len(w) == n and pos >= 0
     return w if strand == 0 else pc.rc(w)
 
@@ -150,6 +155,44 @@ def cut(site_guides, top, top_k=0, min_score=0):
             idx = sorted(idx, key=lambda k: (-int(top[k]), k))[:top_k]
         keep.extend(idx)
     return np.array(sorted(keep), dtype=np.int64)
+
+
+# ---- the site selection digit by digit ------------------------------------------------------------------------------------
+def digits_bulge_table():
+    """pattern_table_cases.digits_table() with dyadic bulge weights: dna 1 - 2^-min(3 + i + 7 b, 29), rna 1 - 2^-min(2 + i + 5 b,
+    29) for protospacer position i and base b - a site's top then agrees with its neighbours' in its upper bytes as the pattern
+    hits' f does."""
+    t = ptc.digits_table()
+    i, b = np.arange(20)[:, None], np.arange(4)[None, :]
+    t["dna"] = 1.0 - 2.0 ** -np.minimum(3 + i + 7 * b, 29)
+    t["rna"] = 1.0 - 2.0 ** -np.minimum(2 + i + 5 * b, 29)
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def digits_sites():
+    """pattern_table_cases.digits_scenario()'s genome and guides as cut sites at dna = rna = 1: the plain hits and the bulged
+    alignments of the pattern restatements, collapsed and scored, and the cuts that ptc.digit_cases finds on `top`.  The floors
+    are ptc.digit_floors', on top."""
+    d = ptc.digits_scenario()
+    pattern, contigs, guides, m, proto = d["pattern"], d["contigs"], d["guides"], d["m"], (0, 20)
+    n = len(guides)
+    table = digits_bulge_table()
+    plain_rec = pc.arrays(d["hits"], n)[0]
+    plain = sc.plain_of_pattern(plain_rec)
+    hits, _ = pbc.brute_force(contigs, pattern, guides, proto, m, 1, 1)
+    bulged = sc.bulged_of_hits(hits)
+    sites = sc.collapse(plain, bulged, len(pattern), "end")
+    site_rec, site_rows = sc.arrays(sites, plain, bulged, n)
+    scores, rows = site_records(table, contigs, guides, sites, n, "end")
+    guide_of, top = site_rec["guide"], scores["top"]
+    found = ptc.digit_cases(guide_of, top, n)
+    s = {"pattern": pattern, "proto": proto, "contigs": contigs, "guides": guides, "m": m, "table": table, "sites": sites, "site_rec": site_rec,
+         "site_rows": site_rows, "scores": scores, "rows": rows, "cases": [c[:2] for c in found], "serves": [c[2] for c in found]}
+    unmet = ptc.digit_floors(guide_of, top, n, s["cases"], lambda k, ms: cut(guide_of, top, k, ms))
+    assert not unmet, unmet
+    assert any(len(x[4]) > 1 for x in sites) and (scores["top"] != scores["best"]).any()  # sites of several members, scored as another
+    return s
 
 
 def make_table(va, table):

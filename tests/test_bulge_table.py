@@ -2,8 +2,8 @@
 records of vsc_bulge_hits_table / vsc_sites_table byte for byte what the definition gives when it is restated in plain Python
 (tests/bulge_table_cases.py) - over the edge and homopolymer scenarios, budgets and classes, Cas12a and SaCas9 through the
 pattern calls, SpCas9 as a pattern, list lengths around one workgroup, records that no search returns (each scores 0), sites
-at the ends of contigs and of the planes, the two outputs, the selection's ties, repetition, the table cache and the timing
-fields."""
+at the ends of contigs and of the planes, the two outputs, the selection's ties and its digit passes, repetition, the table
+cache and the timing fields."""
 import ctypes as C
 
 import numpy as np
@@ -174,6 +174,36 @@ def test_selection_over_several_guides_in_one_workgroup(edge, sp):
         same_bytes(got[0], edge["site_rec"][keep])
         same_bytes(got[1], edge["scores"][keep])
         same_bytes(got[2], edge["rows"])
+
+
+@pytest.fixture(scope="module")
+def digits(ctx):
+    s = dict(btc.digits_sites())
+    s["keep"] = {case: btc.cut(s["site_rec"]["guide"], s["scores"]["top"], *case) for case in s["cases"]}
+    s["obj"] = btc.make_table(va, s["table"])
+    s["gen"] = ctx.load_genome(va.PackedGenome.from_sequences(s["contigs"]))
+    yield s
+    s["gen"].close()
+    s["obj"].close()
+
+
+def test_site_selection_digit_by_digit(digits):
+    """digits_sites(): the pattern hits' digit cases on the site copy of the select - thresholds that share one, two and three
+    digits of `top` with their neighbours, ties over the steps of the walk, T = 0, floors at and beside T."""
+    s = digits
+    search = lambda **kw: s["gen"].search_pattern_sites(s["pattern"], s["guides"], s["m"], s["proto"], dna=1, rna=1, table=s["obj"], **kw)
+    full = search()
+    same_bytes(full[0], s["site_rec"])  # the collapse and the scores first: a failure below is the selection's
+    same_bytes(full[1], s["site_rows"])
+    same_bytes(full[2], s["scores"])
+    same_bytes(full[3], s["rows"])
+    for (top_k, min_score), keep in s["keep"].items():
+        got = search(top_k=top_k, min_score=min_score)
+        assert len(got[0]) == len(keep), (top_k, min_score)
+        same_bytes(got[0], s["site_rec"][keep])
+        same_bytes(got[2], s["scores"][keep])
+        same_bytes(got[1], s["site_rows"])  # the rows are over all sites, whatever is kept
+        same_bytes(got[3], s["rows"])
 
 
 # ---- 2. the pattern form --------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Table scores of bulged alignments without a device: vsc_bulge_table_score bit for bit what the definition gives when it is
 restated in plain Python (tests/bulge_table_cases.py) - every d, every split point, the SpCas9, SaCas9 and Cas12a shapes, IUPAC
-guide letters at unpaired and at mismatched positions - the two anchors (all-ones weights against vsc_pattern_table_score, the
+guide letters at unpaired and at mismatched positions - the floors of the site digits scenario, the two anchors (all-ones weights against vsc_pattern_table_score, the
 SpCas9 form against vsc_table_score), what vsc_bulge_table_build refuses, the text file, the layouts through a C compiler and
 the wrappers' argument checks."""
 import ctypes as C
@@ -34,6 +34,34 @@ def test_new_symbols_are_declared_exported_and_bound():
     assert "vsc_debug_site_table_ms" in {n for n, _, _ in _lib.DEBUG_SYMBOLS}
     assert va.lib().vsc_abi_version() == 5 and re.search(r"#define\s+VSC_ABI_VERSION\s+5\b", HEADER)
     assert "It is not a maximum over" in HEADER and "scores for bulged alignments" not in HEADER.split("vsc_sites_collapse / vsc_sites_collapse_pattern")[1].split("*/")[0].split("since added")[0]
+
+
+def test_the_site_digits_scenario_holds_its_floors():
+    """digits_sites(): the conditions of pattern_table_cases.digit_floors on `top`, by name, with cut() against a second
+    restatement - np.lexsort on (-top, record index) per guide - over every case."""
+    s = btc.digits_sites()
+    guide_of, top = s["site_rec"]["guide"].astype(np.int64), s["scores"]["top"].astype(np.int64)
+    n = len(s["guides"])
+
+    def lexsort_cut(top_k, min_score):
+        keep = []
+        for g in range(n):
+            idx = np.nonzero((guide_of == g) & (top >= min_score))[0]
+            if top_k and len(idx) > top_k:
+                idx = idx[np.lexsort((idx, -top[idx]))[:top_k]]
+            keep.extend(int(i) for i in idx)
+        return np.array(sorted(keep), dtype=np.int64)
+
+    assert len(s["cases"]) == len(set(s["cases"])) == len(s["serves"]) <= ptc.MAX_CASES
+    for top_k, min_score in s["cases"]:
+        assert (btc.cut(guide_of, top, top_k, min_score) == lexsort_cut(top_k, min_score)).all(), (top_k, min_score)
+    unmet = ptc.digit_floors(guide_of, top, n, s["cases"], lexsort_cut)
+    assert not unmet, "digits_sites() does not reach: %s" % ", ".join(unmet)
+    assert len(np.unique(top)) > 200 and (top == 0).any() and len({int(d) for d in s["scores"]["top_d"]}) >= 2
+    assert s["table"]["dna"].shape == s["table"]["rna"].shape == (20, 4)
+    for key in ("pair", "dna", "rna"):  # dyadic: 1 - w is a power of two (or w is 0 or 1)
+        w = 1.0 - s["table"][key][(s["table"][key] > 0) & (s["table"][key] < 1)]
+        assert (np.frexp(w)[0] == 0.5).all(), key
 
 
 def guide_kinds(rng, pattern, proto):

@@ -1,7 +1,7 @@
 """vsc_search_pattern_table on the device: the records byte for byte vsc_search_pattern's, f per record the host's score of the
 guide and the site's text, both kinds of rows and the selection byte for byte what the restatement gives
 (tests/pattern_table_cases.py) - over the lengths, the PAM places and the budgets; the SpCas9 anchor against the plain path's
-table scores; ties across the K-th place; the rounds; the outputs, the cap, shards, repetition, the table cache; and
+table scores; ties across the K-th place; the radix select digit by digit and behind the first group of cells; the rounds; the outputs, the cap, shards, repetition, the table cache; and
 design_pattern(table=)."""
 import ctypes as C
 
@@ -137,6 +137,67 @@ def test_selection_scenario(sel, sel_gen, batch):
         keep = tc.cut(hits, f, **kw)
         got = sel_gen.search_pattern_table(p, gs, m, obj, guide_batch=batch, **kw)
         same(got, sel["rec"][keep], f[keep], sel["rows"], sel["trows"])   # the rows are over all hits, whatever is kept
+
+
+def digits_fixture(ctx, s):
+    """A digits scenario with the restatement's arrays, its cut per case, the table and the resident genome."""
+    s = dict(s)
+    s["rec"], s["rows"] = pc.arrays(s["hits"], len(s["guides"]))
+    s["trows"] = tc.table_rows(s["hits"], s["f"], len(s["guides"]))
+    s["keep"] = {case: tc.cut(s["hits"], s["f"], *case) for case in s["cases"]}
+    s["obj"] = tc.make_table(va, s["table"])
+    s["gen"] = ctx.load_genome(va.PackedGenome.from_sequences(s["contigs"]))
+    return s
+
+
+@pytest.fixture(scope="module")
+def digits(ctx):
+    s = digits_fixture(ctx, tc.digits_scenario())
+    yield s
+    s["gen"].close()
+    s["obj"].close()
+
+
+@pytest.fixture(scope="module")
+def wide(ctx):
+    s = digits_fixture(ctx, tc.digits_wide())
+    yield s
+    s["gen"].close()
+    s["obj"].close()
+
+
+def test_selection_digit_by_digit(digits):
+    """digits_scenario(): thresholds that share one, two and three digits with their neighbours, ties over the steps of the walk,
+    T = 0, floors at and beside T - every case of the list, under three round sizes."""
+    s = digits
+    p, gs, m, obj, gen, rec, f = s["pattern"], s["guides"], s["m"], s["obj"], s["gen"], s["rec"], s["f"]
+    same(gen.search_pattern_table(p, gs, m, obj), rec, f, s["rows"], s["trows"])  # the search and the scores first: a failure below is the selection's
+    for batch in (0, 1, 3):
+        for (top_k, min_score), keep in s["keep"].items():
+            got = gen.search_pattern_table(p, gs, m, obj, top_k=top_k, min_score=min_score, guide_batch=batch)
+            assert len(got[0]) == len(keep), (batch, top_k, min_score)
+            same(got, rec[keep], f[keep], s["rows"], s["trows"])
+
+
+def test_selection_beyond_the_first_group_of_cells(ctx, wide):
+    """digits_wide(): at guide_batch = 64 the segments of guides 59 to 62 begin in the second group of 64 x 64 cells, and guides
+    64 and 65 are a round of their own; at 16 every round has one group.  The cap counts the survivors there as well."""
+    s = wide
+    p, gs, m, obj, gen, rec, f = s["pattern"], s["guides"], s["m"], s["obj"], s["gen"], s["rec"], s["f"]
+    same(gen.search_pattern_table(p, gs, m, obj, guide_batch=64), rec, f, s["rows"], s["trows"])
+    assert ctx.timing()["passes"] == 2
+    for batch in (64, 16):
+        for (top_k, min_score), keep in s["keep"].items():
+            got = gen.search_pattern_table(p, gs, m, obj, top_k=top_k, min_score=min_score, guide_batch=batch)
+            assert len(got[0]) == len(keep), (batch, top_k, min_score)
+            same(got, rec[keep], f[keep], s["rows"], s["trows"])
+    (top_k, min_score), keep = next(iter(s["keep"].items()))  # the case that truncates inside a second-group guide's ties
+    n = len(keep)
+    assert 0 < n < len(rec)
+    same(gen.search_pattern_table(p, gs, m, obj, top_k=top_k, min_score=min_score, guide_batch=64, max_hits=n), rec[keep], f[keep], s["rows"], s["trows"])
+    with pytest.raises(va.VarscotError) as err:
+        gen.search_pattern_table(p, gs, m, obj, top_k=top_k, min_score=min_score, guide_batch=64, max_hits=n - 1)
+    assert err.value.code == -34 and (" %d records" % n) in str(err.value)
 
 
 # ---- 4. rounds ------------------------------------------------------------------------------------------------------------

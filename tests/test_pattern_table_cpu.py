@@ -1,7 +1,8 @@
 """The pattern table score without a device: vsc_pattern_table_score against the restatement (tests/pattern_table_cases.py) bit
-for bit over random shapes, the SpCas9 anchor over every row of the CRISPOR fixture, what vsc_pattern_table_build refuses, the
-header's structs under a C and a C++ compiler, the TSV round trip and pattern_search's argument checks.  (The refusals of
-vsc_search_pattern_table itself need a context, that is a device: tests/test_pattern_table.py.)"""
+for bit over random shapes, the floors of the digit scenarios by name, the SpCas9 anchor over every row of the CRISPOR fixture,
+what vsc_pattern_table_build refuses, the header's structs under a C and a C++ compiler, the TSV round trip and pattern_search's
+argument checks.  (The refusals of vsc_search_pattern_table itself need a context, that is a device:
+tests/test_pattern_table.py.)"""
 import ctypes as C
 import os
 import re
@@ -27,6 +28,53 @@ _bits = lambda x: struct.pack("<d", x)
 def test_the_scenarios_hold_their_floors():
     s = tc.select_scenario()
     assert len(s["hits"]) == len(s["f"]) and tc.edge_table(23, "both")["f"].dtype == np.uint32
+
+
+def lexsort_cut(guide_of, f, n_guides, top_k, min_score):
+    """cut() once more, on the f array alone: per guide np.lexsort on (-f, record index) over the survivors."""
+    guide_of, f = np.asarray(guide_of), np.asarray(f, dtype=np.int64)
+    keep = []
+    for g in range(n_guides):
+        idx = np.nonzero((guide_of == g) & (f >= min_score))[0]
+        if top_k and len(idx) > top_k:
+            idx = idx[np.lexsort((idx, -f[idx]))[:top_k]]
+        keep.extend(int(i) for i in idx)
+    return np.array(sorted(keep), dtype=np.int64)
+
+
+def test_the_digit_scenarios_hold_their_floors():
+    """digits_scenario() and digits_wide(): every condition that keeps the device tests from hiding a failure, by name, on the
+    restatement's own output; and cut() against a second restatement over every case."""
+    s = tc.digits_scenario()
+    guide_of = [h[0] for h in s["hits"]]
+    assert len(s["contigs"]) == 1 and len(s["contigs"][0]) < 80000 and len(s["guides"]) == 4
+    assert len(s["cases"]) == len(set(s["cases"])) == len(s["serves"]) <= tc.MAX_CASES
+    for top_k, min_score in s["cases"]:
+        assert (tc.cut(s["hits"], s["f"], top_k, min_score) == lexsort_cut(guide_of, s["f"], 4, top_k, min_score)).all(), (top_k, min_score)
+    unmet = tc.digit_floors(guide_of, s["f"], 4, s["cases"], lambda k, ms: lexsort_cut(guide_of, s["f"], 4, k, ms))
+    assert not unmet, "digits_scenario() does not reach: %s" % ", ".join(unmet)
+    # the conditions bite: without its cases below the top digit, without its long segments, the list is found wanting
+    few = tc.digit_floors(guide_of, s["f"], 4, [c for c in s["cases"] if c[0] in (1, 700, 701, 300, 301)], lambda k, ms: tc.cut(s["hits"], s["f"], k, ms))
+    assert {"larger 1", "larger 2", "T = 0", "min_score = T"} <= set(few)
+    short = [k for k, h in enumerate(s["hits"]) if h[0] == 3]
+    assert {"ties over steps", "two and three steps", "empty segment"} <= set(
+        tc.digit_floors([0] * len(short), s["f"][short], 1, s["cases"], lambda k, ms: lexsort_cut([0] * len(short), s["f"][short], 1, k, ms)))
+    assert len(np.unique(s["f"])) > 200 and (s["f"] == 0).any()
+    w = tc.digits_wide()
+    n_tiles = len(w["contigs"][0]) // pc.TILE
+    guide_of = [h[0] for h in w["hits"]]
+    assert len(w["guides"]) == 66 and len(w["contigs"][0]) < 80000, "digits_wide(): sizes"
+    assert 2 * 64 * n_tiles > 4096, "digits_wide(): one round of 64 guides has two groups of cells"
+    beyond = {g for g in set(guide_of) if g < 64 and 2 * g * n_tiles >= 4096}
+    assert len(beyond) >= 2, "digits_wide(): two guides with records begin in the second group"
+    truncated_ties = False
+    for top_k, min_score in w["cases"]:
+        keep = tc.cut(w["hits"], w["f"], top_k, min_score)
+        assert (keep == lexsort_cut(guide_of, w["f"], 66, top_k, min_score)).all(), (top_k, min_score)
+        assert {64, 65} <= {guide_of[i] for i in keep}, "digits_wide(): the second round keeps records of its own"
+        t = tc.case_facts(guide_of, w["f"], 66, keep, top_k, min_score)
+        truncated_ties |= any(g in beyond and t[g]["kept_ties"] and t[g]["dropped_ties"] for g in t)
+    assert truncated_ties, "digits_wide(): a guide of the second group truncates inside its ties"
 
 
 # ------------------------------------------------------------------------------------ 1. the definition, bit for bit
