@@ -1845,6 +1845,105 @@ int vsc_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_gui
 int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
                                          const vsc_eff_model *model, double min_linear, vsc_pattern_guides **out);
 
+/* ---- microhomology and out-of-frame scores of candidate guides ------------------------------------------------ */
+/*
+ * "When this guide cuts, will the repair knock the gene out?": the microhomology score of Bae, Kweon, Kim & Kim (Nat. Methods
+ * 2014) over the bases around the cut site - every microhomology-mediated deletion, weighted by its length and G/C content -
+ * and the share of it whose deletion length is no multiple of three (the "Out-of-Frame" column of guide-design tools).  A
+ * formula: there is no model to bring.
+ *
+ * SHAPE    site_len 16 .. 32, cut 0 .. site_len, flank F 8 .. 32;  W = 2 F <= 64.
+ *          cut: the break lies between read positions cut - 1 and cut of the site (SpCas9 23-mer: 17).
+ * CONTEXT  of a locus (c, p, strand) - p the site's first base on the forward strand, as everywhere - in READ orientation:
+ *          read positions [cut - F, cut + F) relative to the site's first read base; it may reach outside the site on either side.
+ *            '+': c[p + cut - F, p + cut + F)
+ *            '-': revcomp(c[p + site_len - cut - F, p + site_len - cut + F))
+ * CLASS    one per candidate, tested in this order (as vsc_eff_stats):
+ *            invalid      contig, strand, or the SITE leaves its contig
+ *            off_contig   the context does
+ *            not_resident the context is not wholly in the words this genome object was loaded with
+ *            has_n
+ *            defined
+ * ROWS     over the context s[0, W), left = F:
+ *            every (i, j, k) with 2 <= k <= F - 1, 0 <= i, i + k <= F, F <= j, j + k <= W, s[i, i + k) == s[j, j + k).
+ *          A row is DROPPED when another row with the same j - i contains it (i' <= i, i + k <= i' + k').
+ *          This is the published script, its range(2, left) included.
+ * SCORE    of a kept row:
+ *            d = j - i (the deletion length), g = number of G/C in s[i, i + k),
+ *            v = T[d] * (k + g), in TENTHS of the published score.
+ *            T[d] = round(exp(-d / 20), 3) * 1000 as an integer, d = 0 .. 63:
+ *                   1000, 951, 905, 861, 819, 779, 741, 705, 670, 638, 607, ... 47, 45, 43
+ * OUTPUT   two uint32 per candidate:
+ *            sum = sum of v over kept rows
+ *            oof = the same over rows with d % 3 != 0
+ *          Both are 0xFFFFFFFF (VSC_MH_UNDEFINED) unless the class is defined.  sum <= 4.1e6.
+ *          mhScore = sum / 10.
+ *          oofScore = 100 * oof / sum (0 when sum == 0).
+ *          Both are fp64 on the HOST only (vsc_mh_scores), one division each.
+ * FILTER   keep a candidate iff all three hold, tested in uint64; with sum == 0 the last holds only for min_oof_permille == 0:
+ *            its class is defined
+ *            sum >= min_sum
+ *            1000 * oof >= min_oof_permille * sum
+ *
+ * The integers are the exact value: every weight is a whole number of thousandths, so sum / 10 is the published sum without a
+ * rounding.  The published script adds floats and truncates; where its float sum lands just under a whole number its int() is
+ * one below sum / 10 rounded down.  No bit-parity with that int() is claimed.  Device, host (vsc_mh_score_text) and the row
+ * list restated in integers agree to the bit.
+ *
+ * vsc_mh_score_text scores one context of W = 2 * flank letters (any case) in read orientation on the host, with the very
+ * function the kernels call; a non-ACGT letter gives the undefined pair (VSC_OK), a text of another length or a flank outside
+ * 8 .. 32 is VSC_ERR_INVALID.  vsc_mh_scores turns a pair into the two doubles; the undefined pair gives two NaNs (VSC_OK),
+ * oof > sum is VSC_ERR_INVALID.
+ *
+ * vsc_loci_microhomology: pairs[2 i], pairs[2 i + 1] = sum, oof of loci[i] (host arrays, n entries).  One upload, one kernel,
+ * one copy back.  stats is optional: the candidates by class (they add up to n), the kernel's time and the call's wall time
+ * in milliseconds.  n == 0: VSC_OK, nothing is launched.  vsc_guides_microhomology scores the candidates where they lie on the
+ * device - no locus travels - and requires site_len == 23 (else VSC_ERR_INVALID); the host-only object of
+ * vsc_multi_guides_enumerate goes the vsc_loci_microhomology way.  vsc_pattern_guides_microhomology is the same for
+ * vsc_pattern_guides: site_len is the pattern's length, which the CALLER vouches for.  A shape outside SHAPE or with a non-zero
+ * reserved field, a genome of another context, an object of another context, a NULL shape or NULL pairs with n > 0:
+ * VSC_ERR_INVALID.
+ *
+ * vsc_guides_filter_microhomology / vsc_pattern_guides_filter_microhomology: *out = the candidates of `in` that pass FILTER -
+ * codes and loci copied unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of
+ * 1 024 candidates: no append atomic, the bytes depend on the input, the shape and the floors only.  min_oof_permille > 1000:
+ * VSC_ERR_INVALID.  The result is a normal object of its kind on ctx's device, as the efficiency filter's is.
+ *
+ * vsc_ctx_timing afterwards: as after the efficiency calls (8 bytes written per candidate).  The scratch is the efficiency
+ * calls'; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: a vsc_multi_* entry (for the reason given above for the efficiency calls); ranking or top-K by oofScore;
+ * indel-outcome models that need trained weights; windows with left != right.
+ */
+#define VSC_MH_UNDEFINED 0xFFFFFFFFu
+typedef struct {
+    uint32_t site_len, cut, flank;
+    uint32_t reserved; /* 0 */
+} vsc_mh_shape;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    double kernel_ms, wall_ms;
+    uint64_t reserved; /* 0 */
+} vsc_mh_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_mh_stats) == 64 && sizeof(vsc_mh_shape) == 16, "vsc_mh_stats / vsc_mh_shape layout");
+#else
+_Static_assert(sizeof(vsc_mh_stats) == 64 && sizeof(vsc_mh_shape) == 16, "vsc_mh_stats / vsc_mh_shape layout");
+#endif
+int vsc_mh_score_text(const char *context /* 2 * flank letters, read orientation */, uint32_t flank, uint32_t *sum, uint32_t *oof);
+int vsc_mh_scores(uint32_t sum, uint32_t oof, double *mh_score, double *oof_score);
+int vsc_loci_microhomology(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n,
+                           const vsc_mh_shape *shape, uint32_t *pairs /* host, 2 n */, vsc_mh_stats *stats /* optional */);
+int vsc_guides_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_mh_shape *shape,
+                             uint32_t *pairs /* host, two per candidate */, vsc_mh_stats *stats /* optional */);
+int vsc_pattern_guides_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_mh_shape *shape,
+                                     uint32_t *pairs /* host, two per candidate */, vsc_mh_stats *stats /* optional */);
+int vsc_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_mh_shape *shape,
+                                    uint32_t min_sum, uint32_t min_oof_permille, vsc_guides **out);
+int vsc_pattern_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
+                                            const vsc_mh_shape *shape, uint32_t min_sum, uint32_t min_oof_permille,
+                                            vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -296,6 +296,29 @@ class EffStats(C.Structure):
         return {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n")}
 
 
+MH_UNDEFINED = 0xFFFFFFFF  # VSC_MH_UNDEFINED
+
+
+class MhShape(C.Structure):
+    """vsc_mh_shape: the site's length, the cut (the break lies between read positions cut - 1 and cut) and the flank F; the
+    context is read positions [cut - F, cut + F)."""
+    _fields_ = [("site_len", C.c_uint32), ("cut", C.c_uint32), ("flank", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MhStats(C.Structure):
+    """vsc_mh_stats: the candidates of a call by class (the five counts add up to n), the kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("kernel_ms", C.c_double), ("wall_ms", C.c_double), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n")}
+        d.update(kernel_ms=float(self.kernel_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(MhShape) == 16 and C.sizeof(MhStats) == 64
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -503,6 +526,13 @@ SYMBOLS = [
     ("vsc_pattern_guides_efficiency", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
     ("vsc_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
+    ("vsc_mh_score_text", C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("vsc_mh_scores", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("vsc_loci_microhomology", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(MhShape), _vp, C.POINTER(MhStats)]),
+    ("vsc_guides_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), _vp, C.POINTER(MhStats)]),
+    ("vsc_pattern_guides_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), _vp, C.POINTER(MhStats)]),
+    ("vsc_guides_filter_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)

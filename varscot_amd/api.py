@@ -917,6 +917,58 @@ def _eff_partial(stats, allow_partial):
                          "front of its first word); allow_partial=True returns them as undefined" % stats["not_resident"])
 
 
+MH_UNDEFINED = _lib.MH_UNDEFINED  # sum and oof of a candidate whose microhomology score is undefined
+
+
+class MicrohomologyShape:
+    """vsc_mh_shape: where the microhomology score looks.  site_len 16..32 is the candidates' length (23 for
+    enumerate_guides', the pattern's for enumerate_pattern's), cut 0..site_len says that the break lies between read positions
+    cut - 1 and cut of the site (SpCas9: 17; Cas12a TTTV + 23: 22), flank 8..32 is the number of bases taken on either side
+    of the break.  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, cut=17, flank=30, validate=True):
+        self.site_len, self.cut, self.flank = int(site_len), int(cut), int(flank)
+        if validate and not (16 <= self.site_len <= 32 and 0 <= self.cut <= self.site_len and 8 <= self.flank <= 32):
+            raise ValueError("a microhomology shape has site_len 16..32, cut 0..site_len and flank 8..32")
+
+    def _struct(self):
+        return _lib.MhShape(self.site_len, self.cut, self.flank, 0)
+
+    def __repr__(self):
+        return "MicrohomologyShape(site_len=%d, cut=%d, flank=%d)" % (self.site_len, self.cut, self.flank)
+
+
+def microhomology_text(context, flank=None):
+    """vsc_mh_score_text: (sum, oof) of one context of 2 * flank letters (any case) in read orientation - the break in its
+    middle - on the host, by the function the kernels call.  sum is the microhomology score in tenths, oof the part of it whose
+    deletion length is no multiple of three; a non-ACGT letter gives (MH_UNDEFINED, MH_UNDEFINED).  flank=None: half the
+    text's length."""
+    b = context if isinstance(context, bytes) else context.encode()
+    if flank is None:
+        if len(b) % 2:
+            raise ValueError("a microhomology context has an even number of letters")
+        flank = len(b) // 2
+    s, o = C.c_uint32(), C.c_uint32()
+    check(lib().vsc_mh_score_text(b, int(flank), C.byref(s), C.byref(o)))
+    return int(s.value), int(o.value)
+
+
+def microhomology_scores(pairs):
+    """vsc_mh_scores: (mhScore, oofScore) float64 arrays for (sum, oof) pairs - sum / 10 and 100 * oof / sum (0 where sum is 0),
+    NaN where the pair is undefined.  pairs: one pair or an array of shape (n, 2)."""
+    a = np.asarray(pairs, dtype=np.uint32)
+    flat = a.reshape(-1, 2)
+    mh, oof = np.empty(len(flat), dtype=np.float64), np.empty(len(flat), dtype=np.float64)
+    L = lib()
+    x, y = C.c_double(), C.c_double()
+    for i, (s, o) in enumerate(flat):
+        check(L.vsc_mh_scores(int(s), int(o), C.byref(x), C.byref(y)))
+        mh[i], oof[i] = x.value, y.value
+    if a.ndim == 1:
+        return float(mh[0]), float(oof[0])
+    return mh, oof
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -1640,7 +1692,8 @@ class Genome:
             L.vsc_pattern_hits_free(plain)
 
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
-                          max_guides=0, params=None, efficiency=None, min_efficiency=None):
+                          max_guides=0, params=None, efficiency=None, min_efficiency=None, microhomology=None,
+                          min_out_of_frame=None, min_microhomology=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -1651,7 +1704,12 @@ class Genome:
         efficiency= an EfficiencyModel whose site_len is the pattern's length: returns (PatternGuides, linear float64[n]) - the
         candidates' predictors, computed where the candidates lie on the device (vsc_pattern_guides_efficiency).
         min_efficiency=x (needs efficiency=): only the candidates whose predictor is defined and >= x, linear domain
-        (vsc_pattern_guides_filter_efficiency)."""
+        (vsc_pattern_guides_filter_efficiency).
+        microhomology= a MicrohomologyShape whose site_len is the pattern's length: the candidates' (sum, oof) pairs
+        (uint32[n, 2], vsc_pattern_guides_microhomology) come last, after the predictors when both are asked for.
+        min_out_of_frame=x (per cent) / min_microhomology=y (score units; both need microhomology=): only the candidates
+        whose score is defined, at least y, and out of frame for at least x per cent of it
+        (vsc_pattern_guides_filter_microhomology).  Both floors are applied on the device, in either order the same bytes."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -1659,15 +1717,16 @@ class Genome:
         iv_ptr = None if iv is None else ptr(iv if len(iv) else np.zeros(1, dtype=_lib.INTERVAL_DTYPE))
         L = lib()
         self._eff_args(efficiency, min_efficiency, len(p))
+        mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
-        linear, held = None, [h]
+        held = [h]
         try:
-            if efficiency is not None:
-                linear = self._eff_on_handle(held, efficiency, min_efficiency, L.vsc_pattern_guides_count,
-                                             L.vsc_pattern_guides_efficiency, L.vsc_pattern_guides_filter_efficiency,
-                                             L.vsc_pattern_guides_free)
+            extra = self._scores_on_handle(held, efficiency, min_efficiency, mh, L.vsc_pattern_guides_count,
+                                           (L.vsc_pattern_guides_efficiency, L.vsc_pattern_guides_filter_efficiency),
+                                           (L.vsc_pattern_guides_microhomology, L.vsc_pattern_guides_filter_microhomology),
+                                           L.vsc_pattern_guides_free)
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -1680,21 +1739,22 @@ class Genome:
         finally:
             L.vsc_pattern_guides_free(held[0])
         found = PatternGuides(p.decode(), protospacer, codes, loci)
-        return found if efficiency is None else (found, linear)
+        return (found,) + extra if extra else found
 
     def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, table=None, **filters):
         """Every guide of `targets` under a pattern, with its off-target counts: enumerate_pattern(pattern, protospacer,
         targets, **filters) followed by search_pattern (rows only) of the guides in query form on the same resident genome.
         Returns (PatternGuides, uint32 rows of shape (n, 9)); count[0] is reduced by one for the guide's own locus, which is
         always a hit at NM 0 (the query form has N outside the protospacer).  With efficiency= (and min_efficiency=) among
-        the filters, as enumerate_pattern takes them: only the survivors are searched, and their predictors come last.
+        the filters, as enumerate_pattern takes them: only the survivors are searched, and their predictors come last; the
+        same holds for microhomology= (and its floors), whose pairs come after the predictors.
         table= a PatternTable: search_pattern_table instead, and the TABLE_ROW_DTYPE rows follow the NM rows - each with the
         guide's own locus taken out as well, by the host's score of the guide (query form) against its own site (the
         candidate's letters, PAM included), as count[0] is reduced."""
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
         extra = ()
-        if filters.get("efficiency") is not None:
-            found, extra = found[0], (found[1],)
+        if isinstance(found, tuple):
+            found, extra = found[0], tuple(found[1:])
         if table is not None:
             queries = found.text()
             _, _, rows, trows = self.search_pattern_table(pattern, queries, max_mismatches, table, guide_batch=guide_batch, records=False)
@@ -1722,20 +1782,100 @@ class Genome:
         if model.site_len != site_len:
             raise ValueError("the model's site_len is %d; these candidates are %d bases long" % (model.site_len, site_len))
 
-    def _eff_on_handle(self, held, model, floor, count_fn, score_fn, filter_fn, free_fn):
+    def _eff_on_handle(self, held, model, floor, count_fn, score_fn, filter_fn, free_fn, score=True):
         """The predictors of the candidate handle held[0] under a model, computed where the candidates lie.  With a floor the
         handle is first replaced by the filter's result: the input is freed and held[0] is the result - the caller frees
-        held[0], whatever happens here."""
+        held[0], whatever happens here.  score=False: the filter only."""
         if floor is not None:
             out = C.c_void_p()
             check(filter_fn(self.ctx._h, self._h, held[0], model._h, float(floor), C.byref(out)), self.ctx._h)
             free_fn(held[0])
             held[0] = out
+        if not score:
+            return None
         linear = np.empty(int(count_fn(held[0])), dtype=np.float64)
         st = _lib.EffStats()
         check(score_fn(self.ctx._h, self._h, held[0], model._h, ptr(linear), C.byref(st)), self.ctx._h)
         _eff_partial(st.as_dict(), False)
         return linear
+
+    # ---- microhomology and out-of-frame scores (vsc_*_microhomology) ----------------------------------------------------
+    @staticmethod
+    def _mh_args(shape, min_oof, min_sum, site_len):
+        """(shape, min_sum in tenths, min_oof in per mille) - the floors None when neither is given - or None without a
+        shape.  min_out_of_frame is in per cent and becomes per mille here, once: round(10 * x); min_microhomology is in the
+        published score's units and becomes tenths: ceil(10 * x)."""
+        if shape is None:
+            if min_oof is not None or min_sum is not None:
+                raise ValueError("min_out_of_frame / min_microhomology need microhomology=shape")
+            return None
+        if not isinstance(shape, MicrohomologyShape):
+            raise ValueError("microhomology must be a MicrohomologyShape")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        if min_oof is None and min_sum is None:
+            return shape, None, None
+        permille = 0 if min_oof is None else int(round(10.0 * float(min_oof)))
+        tenths = 0 if min_sum is None else int(np.ceil(10.0 * float(min_sum) - 1e-9))
+        if not 0 <= permille <= 1000:
+            raise ValueError("min_out_of_frame is a share in per cent, 0 .. 100")
+        if not 0 <= tenths <= 0xFFFFFFFF:
+            raise ValueError("min_microhomology is out of range")
+        return shape, tenths, permille
+
+    def _mh_on_handle(self, held, mh, count_fn, score_fn, filter_fn, free_fn, score=True):
+        """As _eff_on_handle, for the microhomology pairs: mh = what _mh_args returned."""
+        shape, tenths, permille = mh
+        sh = shape._struct()
+        if tenths is not None:
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), tenths, permille, C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not score:
+            return None
+        pairs = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.MhStats()
+        check(score_fn(self.ctx._h, self._h, held[0], C.byref(sh), ptr(pairs), C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return pairs
+
+    def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn):
+        """Both floors, then both scores over the survivors: the extras of an enumeration, the efficiency predictors before
+        the microhomology pairs.  held[0] is replaced as _eff_on_handle replaces it."""
+        if efficiency is not None:
+            self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
+        if mh is not None:
+            self._mh_on_handle(held, mh, count_fn, mh_fns[0], mh_fns[1], free_fn, score=False)
+        extra = ()
+        if efficiency is not None:
+            extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
+        if mh is not None:
+            extra += (self._mh_on_handle(held, (mh[0], None, None), count_fn, mh_fns[0], mh_fns[1], free_fn),)
+        return extra
+
+    def microhomology(self, loci_or_found, shape, allow_partial=False):
+        """vsc_loci_microhomology: the microhomology pairs of candidates under a MicrohomologyShape, computed on the device from
+        the resident planes: (uint32[n, 2], stats) - column 0 is sum (the score of Bae et al. 2014 in tenths), column 1 oof
+        (the part of it whose deletion length is no multiple of three); microhomology_scores turns them into mhScore and
+        oofScore.  loci_or_found: as Genome.efficiency takes it.  An undefined pair is (MH_UNDEFINED, MH_UNDEFINED); stats
+        counts the candidates by class - defined, invalid, off_contig, not_resident, has_n - and holds kernel_ms and wall_ms.
+        Raises when a context is not resident on this object (a shard) unless allow_partial=True."""
+        if isinstance(loci_or_found, PatternGuides):
+            loci = loci_or_found.loci
+        elif isinstance(loci_or_found, tuple) and len(loci_or_found) >= 2 and isinstance(loci_or_found[1], np.ndarray) \
+                and loci_or_found[1].dtype == _lib.LOCUS_DTYPE:
+            loci = loci_or_found[1]
+        else:
+            loci = loci_or_found
+        lo = _loci(loci, len(loci))
+        pairs = np.empty((len(lo), 2), dtype=np.uint32)
+        st = _lib.MhStats()
+        sh = shape._struct()
+        check(lib().vsc_loci_microhomology(self.ctx._h, self._h, ptr(lo), len(lo), C.byref(sh), ptr(pairs), C.byref(st)), self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        return pairs, stats
 
     def efficiency(self, loci_or_found, model, allow_partial=False):
         """vsc_loci_efficiency: the linear predictors of candidates under an EfficiencyModel, computed on the device from the
@@ -1891,7 +2031,8 @@ class Genome:
         return (hits, rows) if summary else hits
 
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
-                         labels=False, efficiency=None, min_efficiency=None):
+                         labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
+                         min_microhomology=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -1902,24 +2043,30 @@ class Genome:
         index of the interval it lies in, REGION_NONE if none, as Regions.locate gives it (vsc_guides_locate, on the device).
         efficiency= an EfficiencyModel with site_len 23: the candidates' linear predictors (float64[n], computed where the
         candidates lie on the device: vsc_guides_efficiency) come last in the returned tuple.  min_efficiency=x (needs
-        efficiency=): only the candidates whose predictor is defined and >= x, linear domain (vsc_guides_filter_efficiency)."""
+        efficiency=): only the candidates whose predictor is defined and >= x, linear domain (vsc_guides_filter_efficiency).
+        microhomology= a MicrohomologyShape with site_len 23: the candidates' (sum, oof) pairs (uint32[n, 2],
+        vsc_guides_microhomology) come last of all, after the predictors.  min_out_of_frame=x (per cent) /
+        min_microhomology=y (score units; both need microhomology=): only the candidates whose score is defined, at least y,
+        and out of frame for at least x per cent of it (vsc_guides_filter_microhomology)."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
+        mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None:
+        if efficiency is None and mh is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
-            linear = self._eff_on_handle(held, efficiency, min_efficiency, L.vsc_guides_count, L.vsc_guides_efficiency,
-                                         L.vsc_guides_filter_efficiency, L.vsc_guides_free)
+            extra = self._scores_on_handle(held, efficiency, min_efficiency, mh, L.vsc_guides_count,
+                                           (L.vsc_guides_efficiency, L.vsc_guides_filter_efficiency),
+                                           (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free)
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
-        return _guides_arrays(held[0], lambda code: check(code, self.ctx._h), lab) + (linear,)
+        return _guides_arrays(held[0], lambda code: check(code, self.ctx._h), lab) + extra
 
     def enumerate_pairs(self, delta, regions=None, **filters):
         """enumerate_guides(regions, **filters) and the guide pairs among its candidates (vsc_guides_pairs, on the device
@@ -1946,16 +2093,20 @@ class Genome:
         return (found[0], found[1], pairs) + tuple(found[2:])
 
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
-               efficiency=None, min_efficiency=None, **search_options):
+               efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
+               **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
         A PAM other than GG / GA needs extra_pam=pam among the search options for the guide's own locus to be a hit.
         labels: as enumerate_guides; the labels then come last: (codes, loci, rows, labels).
         efficiency= / min_efficiency=: as enumerate_guides; only the survivors are searched, and the linear predictors come
-        last of all: (codes, loci, rows[, labels], linear)."""
+        last of all: (codes, loci, rows[, labels], linear).  microhomology= / min_out_of_frame= / min_microhomology=: as
+        enumerate_guides; the pairs come after the predictors."""
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
-                                      labels=labels, efficiency=efficiency, min_efficiency=min_efficiency)
+                                      labels=labels, efficiency=efficiency, min_efficiency=min_efficiency,
+                                      microhomology=microhomology, min_out_of_frame=min_out_of_frame,
+                                      min_microhomology=min_microhomology)
         codes, loci = found[0], found[1]
         return (codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)) + tuple(found[2:])
 

@@ -104,7 +104,12 @@
 //   efficiencyLinear efficiency
 // = the linear predictor (%.17g; NA when the context leaves its sequence or holds an N) and the predictor through the model's
 // link.  -y MIN (needs -Y) keeps only the candidates whose predictor is defined and >= MIN, linear domain
-// (vsc_guides_filter_efficiency), BEFORE the off-target search: every output holds the survivors only.  Without -Y every
+// (vsc_guides_filter_efficiency), BEFORE the off-target search: every output holds the survivors only.
+// -H FLANK[,CUT] (needs -E, one device) scores every found guide's MICROHOMOLOGY around its cut site (vsc_guides_microhomology: the
+// score of Bae et al. 2014 over FLANK bases on either side of the break in front of read position CUT, default 17): the -L
+// listing gains the last columns mhScore oofScore (%.17g; NA when the window leaves its sequence or holds an N).  -m
+// MIN_OOF[,MIN_MH] (needs -H) keeps only the candidates whose out-of-frame share is at least MIN_OOF per cent and whose score is
+// at least MIN_MH (vsc_guides_filter_microhomology), BEFORE the off-target search, as -y does.  Without -Y every
 // output is what it was.
 #include <algorithm>
 #include <cmath>
@@ -116,6 +121,7 @@
 #include <sstream>
 
 #include "eff_model_host.hpp"
+#include "mh_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
 
@@ -172,6 +178,11 @@ int main(int argc, char **argv)
         {'w', "bulge-table", "Path to the bulge weights (.tsv/.txt; lines 'dna j s w' and 'rna j g w', j = read position 0 .. 19) beside the -W table: "
                              "the cut sites are scored; adds the columns siteScoreSum siteSpecScore sitePositive, and tableScore scoredAs to the -Z "
                              "file, which -K / -S then cut by the site's score; needs -W, -u and -Z", false},
+        {'H', "microhomology", "FLANK[,CUT]: adds the columns mhScore oofScore (the microhomology score of Bae et al. 2014 and its out-of-frame "
+                               "share in per cent) to the -L file, over FLANK bases (8 .. 32) on either side of the break in front of read "
+                               "position CUT (default 17) (needs -E, one device)", false},
+        {'m', "min-out-of-frame", "MIN_OOF[,MIN_MH]: keep only the -E candidates whose out-of-frame share is at least MIN_OOF per cent and whose "
+                                  "microhomology score is at least MIN_MH (needs -H)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -346,6 +357,15 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // -H / -m: the microhomology scores of the found guides
+    MhOptions mh;
+    {
+        const std::string why = parse_mh_options(opts[37].set, opts[37].value, opts[38].set, opts[38].value, discover, (uint32_t)VSC_READ_LEN, 17, &mh);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     const bool naming = opts[21].set;
     if (naming) {
         if (opts[21].value != "name" && opts[21].value != "coords") {
@@ -516,6 +536,11 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    if (mh.on && devices.size() != 1) {
+        std::fprintf(stderr, "%s: -H scores the candidates on one device: it does not combine with a device list\n", argv[0]);
+        return 1;
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -656,9 +681,21 @@ int main(int argc, char **argv)
                     vsc_guides_free(found);
                     found = kept;
                 }
+            }
+            if (mh.floored) {  // -m: the same for the microhomology floors
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_microhomology(ctx, genome, found, &mh.shape, mh.min_sum, mh.min_oof_permille, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
+            if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
+            std::vector<uint32_t> mh_pairs(mh.on ? 2 * vsc_guides_count(found) : 0);
+            if (mh.on && vsc_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -681,7 +718,8 @@ int main(int argc, char **argv)
                 if (opts[20].set)
                     bed6 += chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
                             "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
-                            (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") + '\n';
+                            (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
+                            (mh.on ? mh_columns(&mh_pairs[2 * i]) : "") + '\n';
             }
             if (opts[20].set) {
                 std::ofstream out(guides_bed_path);

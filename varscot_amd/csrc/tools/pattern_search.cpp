@@ -32,6 +32,12 @@
 // must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
 // its sequence or holds an N) and efficiency (the predictor through the model's link).  -y MIN (needs -Y) keeps only the
 // candidates whose predictor is defined and >= MIN, linear domain, BEFORE the search.  Without -Y every output is what it was.
+// -H FLANK[,CUT] (needs -E) scores every found guide's MICROHOMOLOGY around its cut site (vsc_pattern_guides_microhomology: the
+// score of Bae et al. 2014 over FLANK bases on either side of the break in front of read position CUT; default CUT: 3 bases
+// before the end of a protospacer that starts the pattern - SpCas9, SaCas9 - else 18 bases behind its start - Cas12a): the -E
+// listing gains the last columns mhScore oofScore (%.17g; NA when the window leaves its sequence or holds an N).  -m
+// MIN_OOF[,MIN_MH] (needs -H) keeps only the candidates whose out-of-frame share is at least MIN_OOF per cent and whose score
+// is at least MIN_MH, BEFORE the search.
 // -W table.tsv scores every hit with a pattern TABLE (vsc_search_pattern_table; the CFD form for any nuclease: a product of
 // weights by protospacer position, guide base and site base times a weight for the site's letters at up to four PAM positions;
 // the file is what varscot_amd.PatternTable.to_tsv writes, tools/README.md: `shape L ps_start ps_len`, `pam_pos p...`,
@@ -52,6 +58,7 @@
 #include <sstream>
 
 #include "eff_model_host.hpp"
+#include "mh_host.hpp"
 #include "vsc_host.hpp"
 
 using namespace vsc_host;
@@ -218,6 +225,12 @@ int main(int argc, char **argv)
                      "vmm0 .. vmm<M> varDuplicates refShadowed, with -W also indScoreSum indSpec varScoreSum; needs -O and -M, not with "
                      "-u -U -Z -w -T -K -S", false},
         {'n', "sample", "With -v: 0-based sample column of the .vcf file (default 0)", false},
+        {'H', "microhomology", "With -E: FLANK[,CUT]: the -E listing gains the columns mhScore oofScore (the microhomology score of Bae et al. "
+                               "2014 and its out-of-frame share in per cent) over FLANK bases (8 .. 32) on either side of the break in front "
+                               "of read position CUT (default: 3 bases before the end of a -p protospacer that starts the pattern, else 18 "
+                               "bases behind its start)", false},
+        {'m', "min-out-of-frame", "With -H: MIN_OOF[,MIN_MH]: keep only the candidates whose out-of-frame share is at least MIN_OOF per cent "
+                                  "and whose microhomology score is at least MIN_MH", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -409,6 +422,18 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // -H / -m: the microhomology scores of the found guides
+    MhOptions mh;
+    {
+        const uint32_t plen = (uint32_t)pattern.size();
+        uint32_t cut = ep.ps_start == 0 ? (ep.ps_len >= 3 ? ep.ps_len - 3 : 0) : ep.ps_start + 18;
+        if (cut > plen) cut = plen;
+        const std::string why = parse_mh_options(opts[25].set, opts[25].value, opts[26].set, opts[26].value, enumerate, plen, cut, &mh);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     vsc_pattern_select sel{};
@@ -544,9 +569,21 @@ int main(int argc, char **argv)
                     vsc_pattern_guides_free(found);
                     found = kept;
                 }
+            }
+            if (mh.floored) {  // -m: the same for the microhomology floors
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_microhomology(ctx, genome, found, &mh.shape, mh.min_sum, mh.min_oof_permille, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
+            if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
+            std::vector<uint32_t> mh_pairs(mh.on ? 2 * vsc_pattern_guides_count(found) : 0);
+            if (mh.on && vsc_pattern_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -554,7 +591,7 @@ int main(int argc, char **argv)
             std::printf("Guides found (total: %llu).\n", (unsigned long long)n);
             std::ofstream out(opts[7].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
-            out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << '\n';
+            out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -572,6 +609,7 @@ int main(int argc, char **argv)
                 guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
                 out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+');
                 if (efficient) out << '\t' << eff_text(eff_linear[i]) << '\t' << eff_text(vsc_eff_link(eff_model, eff_linear[i]));
+                if (mh.on) out << mh_columns(&mh_pairs[2 * i]);
                 out << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);

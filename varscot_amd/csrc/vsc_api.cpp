@@ -12,6 +12,7 @@
 //   vsc_pattern.hip        pattern search, pattern guide discovery
 //   vsc_pattern_bulge.hip  bulges under a pattern
 //   vsc_efficiency.hip     on-target efficiency of candidates
+//   vsc_mh.hip             microhomology and out-of-frame scores of candidates
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
@@ -4378,6 +4379,223 @@ int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome,
                                          double min_linear, vsc_pattern_guides **out)
 {
     return eff_filter(ctx, genome, in, model, false, min_linear, out, "vsc_pattern_guides_filter_efficiency");
+}
+
+}  // extern "C"
+
+// ---- microhomology and out-of-frame scores (the definition: vsc_mh.h, the kernels: vsc_mh.hip) ------------------
+namespace {
+
+double wall_ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int mh_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_mh_shape *shape, MhShape &s, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    s = MhShape{shape->site_len, shape->cut, shape->flank};
+    if (shape->reserved || !mh_shape_valid(s)) return fail_in(ctx, VSC_ERR_INVALID, who, "site_len 16 .. 32, cut 0 .. site_len, flank 8 .. 32");
+    return VSC_OK;
+}
+
+// The pairs of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first) - into host memory:
+// mh_score_kernel, one copy back of the pairs and one of the class counts.  The scratch is the efficiency calls'.
+int mh_score_loci(vsc_ctx *ctx, const vsc_genome *genome, const MhShape &shape, const void *d_loci, const vsc_locus *h_loci, uint64_t n,
+                  uint32_t *pairs, vsc_mh_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) *stats = vsc_mh_stats{};
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        return VSC_OK;
+    }
+    if (!pairs) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    MhArgs a{};
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n = n;
+    const size_t head = 256;  // the class counts, in front of the pairs
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_mh_score(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kEffClasses] = {};
+    VSC_HIP(ctx, hipMemcpyAsync(pairs, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    t.score_ms = t.total_ms = ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+// vsc_guides_microhomology / vsc_pattern_guides_microhomology: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int mh_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_mh_shape *shape, bool need_23, uint32_t *pairs,
+                    vsc_mh_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    MhShape s{};
+    const int rc = mh_check(ctx, genome, shape, s, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    const bool dev = guides->ctx != nullptr;
+    return mh_score_loci(ctx, genome, s, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
+                         guides->n, pairs, stats, who);
+    });
+}
+
+// vsc_guides_filter_microhomology / vsc_pattern_guides_filter_microhomology: run_enumeration's two passes over tiles of kMhTile
+// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the scoring calls report theirs.
+template <class Guides>
+int mh_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_mh_shape *shape, bool need_23, uint32_t min_sum,
+              uint32_t min_oof_permille, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    MhShape s{};
+    const int rc = mh_check(ctx, genome, shape, s, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (min_oof_permille > 1000u) return fail_in(ctx, VSC_ERR_INVALID, who, "min_oof_permille is more than 1000");
+    const uint64_t n = in->n;
+    const uint64_t tiles = (n + kMhTile - 1) / kMhTile;
+    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    MhFilterArgs a{};
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.n = n;
+    a.min_sum = min_sum;
+    a.min_oof_permille = min_oof_permille;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_mh_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_mh_score_text(const char *context, uint32_t flank, uint32_t *sum, uint32_t *oof)
+{
+    if (!context || !sum || !oof) return VSC_ERR_INVALID;
+    if (flank < kMhMinFlank || flank > kMhMaxFlank) return VSC_ERR_INVALID;
+    const uint32_t W = 2u * flank;
+    if (strnlen(context, W + 1) != W) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    *sum = *oof = kMhUndefined;
+    for (uint32_t j = 0; j < W; ++j) {
+        const int b = base_code(context[j]);
+        if (b > 3) return VSC_OK;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+    }
+    mh_score(ch, cl, flank, sum, oof);
+    return VSC_OK;
+}
+
+int vsc_mh_scores(uint32_t sum, uint32_t oof, double *mh_score_out, double *oof_score_out)
+{
+    if (!mh_score_out || !oof_score_out) return VSC_ERR_INVALID;
+    if (sum == kMhUndefined || oof > sum) {
+        *mh_score_out = *oof_score_out = eff_undefined();
+        return sum == kMhUndefined && oof == kMhUndefined ? VSC_OK : VSC_ERR_INVALID;
+    }
+    *mh_score_out = (double)sum / 10.0;
+    *oof_score_out = sum ? 100.0 * (double)oof / (double)sum : 0.0;
+    return VSC_OK;
+}
+
+int vsc_loci_microhomology(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_mh_shape *shape,
+                           uint32_t *pairs, vsc_mh_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_microhomology";
+    MhShape s{};
+    const int rc = mh_check(ctx, genome, shape, s, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    return mh_score_loci(ctx, genome, s, nullptr, loci, n, pairs, stats, fn);
+    });
+}
+
+int vsc_guides_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_mh_shape *shape, uint32_t *pairs,
+                             vsc_mh_stats *stats)
+{
+    return mh_score_guides(ctx, genome, guides, shape, true, pairs, stats, "vsc_guides_microhomology");
+}
+
+int vsc_pattern_guides_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_mh_shape *shape,
+                                     uint32_t *pairs, vsc_mh_stats *stats)
+{
+    return mh_score_guides(ctx, genome, guides, shape, false, pairs, stats, "vsc_pattern_guides_microhomology");
+}
+
+int vsc_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_mh_shape *shape, uint32_t min_sum,
+                                    uint32_t min_oof_permille, vsc_guides **out)
+{
+    return mh_filter(ctx, genome, in, shape, true, min_sum, min_oof_permille, out, "vsc_guides_filter_microhomology");
+}
+
+int vsc_pattern_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_mh_shape *shape,
+                                            uint32_t min_sum, uint32_t min_oof_permille, vsc_pattern_guides **out)
+{
+    return mh_filter(ctx, genome, in, shape, false, min_sum, min_oof_permille, out, "vsc_pattern_guides_filter_microhomology");
 }
 
 int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out)

@@ -7,6 +7,7 @@
 
 #include "varscot_hip.h"
 #include "vsc_efficiency.h"
+#include "vsc_mh.h"
 
 namespace vsc {
 
@@ -568,6 +569,33 @@ struct EffFilterArgs {
 };
 hipError_t launch_eff_score(const EffArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_eff_filter(const EffFilterArgs &args, bool write, hipStream_t stream);
+// vsc_mh.hip (the definition: vsc_mh.h)
+struct MhArgs {
+    EffPlanes g;
+    MhShape shape;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: (sum, oof), kMhUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kEffClasses], zeroed before the launch: the kernel adds its candidates per class
+};
+// the filter's two passes, driven by run_enumeration (vsc_api.cpp): tile i of the work list = candidates [i * kMhTile, ..)
+constexpr uint32_t kMhTile = 1024;
+struct MhFilterArgs {
+    EffPlanes g;
+    MhShape shape;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    uint32_t min_sum, min_oof_permille;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_mh_score(const MhArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_mh_filter(const MhFilterArgs &args, bool write, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

@@ -129,7 +129,8 @@ struct vsc_ctx {
     uint64_t table_serial = 0;  // 0: none resident
     // vsc_*_efficiency: the device copy of the efficiency model this context used last (its weights in the order of
     // vsc_efficiency.h, keyed by the model's serial number), the candidates of a call that brings them from the host (loci;
-    // the filter of a host-only object: codes, then loci) and the call's outputs (the class counts, then the scores)
+    // the filter of a host-only object: codes, then loci) and the call's outputs (the class counts, then the scores).
+    // vsc_*_microhomology (no model) bring their candidates in eff_in and leave their pairs in eff_out as well.
     vsc::DeviceBuf eff_buf, eff_in, eff_out;
     uint64_t eff_serial = 0;  // 0: none resident
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
