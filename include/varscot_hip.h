@@ -1912,8 +1912,8 @@ int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome,
  * vsc_ctx_timing afterwards: as after the efficiency calls (8 bytes written per candidate).  The scratch is the efficiency
  * calls'; vsc_ctx_release_scratch gives it back.
  *
- * Not offered: a vsc_multi_* entry (for the reason given above for the efficiency calls); ranking or top-K by oofScore;
- * indel-outcome models that need trained weights; windows with left != right.
+ * Not offered: a vsc_multi_* entry (for the reason given above for the efficiency calls); indel-outcome models that need
+ * trained weights; windows with left != right.  (Ranking and top-K per target: vsc_*_pick below.)
  */
 #define VSC_MH_UNDEFINED 0xFFFFFFFFu
 typedef struct {
@@ -1943,6 +1943,93 @@ int vsc_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_
 int vsc_pattern_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
                                             const vsc_mh_shape *shape, uint32_t min_sum, uint32_t min_oof_permille,
                                             vsc_pattern_guides **out);
+
+/* ---- the best K guides per target, with spacing ------------------------------------------------- */
+/*
+ * The fifth step of a design: of the candidates of every target choose the K best under a caller-made key, no two of them
+ * closer than `spacing` bases at their cut sites, so that one SNP or one small deletion does not disable all of them.  A
+ * target is a number: an interval, or a group of intervals (the exons of a gene).  This text is normative:
+ *
+ * SHAPE      site_len 16 .. 32, cut 0 .. site_len (SpCas9 23-mer: 17), k 1 .. 32, spacing uint32 (0: none),
+ *            min_key uint64 (0: none), reserved fields 0.
+ * CANDIDATE  i = 0 .. n - 1 (n <= 0xFFFFFFFE): locus (c, p, strand) as everywhere (p = first base of the site on the forward
+ *            strand), key[i] uint64 (LARGER IS BETTER), target[i] uint32 in [0, n_targets) or VSC_REGION_NONE.
+ * CUT COORDINATE   x = p + cut on '+', p + site_len - cut on '-'  (the centre of vsc_mh's context).
+ * ELIGIBLE   contig and strand valid, the site inside its contig, target[i] < n_targets, key[i] >= min_key.
+ *            Every other candidate is never picked and is counted in its class in the stats (invalid, no_target,
+ *            bad_target, below_min_key; tested in this order).
+ * BEFORE     a before b  <=>  key[a] > key[b], or key[a] == key[b] and a < b.          (a total order)
+ * CONFLICT   a, b of one target conflict <=> same contig and |x_a - x_b| < spacing, in 64-bit arithmetic.
+ *            spacing 0: never.  spacing >= 1: a '+' and a '-' candidate with one cut coordinate conflict.
+ * PICK of target t   picked = [];  repeat: among the eligible candidates of t that are not picked and conflict with no
+ *            picked one, take the first under BEFORE and append it; stop at k picks or when none is left.
+ * OUTPUT     picks[t * k + r] = index of the r-th pick of t, VSC_PICK_NONE (0xFFFFFFFF) beyond counts[t];  counts[t];
+ *            optional rank[i] = r if i is the r-th pick of its target, else VSC_PICK_NONE;
+ *            optional `picked`: a new candidate object holding the picked candidates in ascending index.
+ * TARGETS    either target[] is given (host array), or regions (+ optional group[]): label = vsc_regions_locate of the
+ *            site's first base under the regions' own rule, target = group ? group[label] : label; a group entry may be
+ *            VSC_REGION_NONE ("this interval belongs to no target"); group has one entry per INPUT interval.
+ *
+ * The output is fully determined by the inputs.  It does not depend on launch shape, on the order in which waves finish, or
+ * on any atomic.
+ *
+ * vsc_pick_host is the definition as straightforward host code and needs no device: contigs gives the contig lengths, loci,
+ * target and key are host arrays of n entries, picks has n_targets * k entries, counts n_targets, rank (optional) n.  It is
+ * also the route for the host-only object of vsc_multi_guides_enumerate.  vsc_loci_pick takes the same host arrays, in any
+ * order, and picks on the device; vsc_loci_pick_regions is the same with regions (+ optional group) in place of target[]: the
+ * loci are uploaded and labelled on the device as vsc_guides_pick labels its candidates.  vsc_guides_pick / vsc_pattern_guides_pick take the candidates where they lie on the
+ * device; exactly one of `regions` (+ optional `group`) and `target` is given.  With regions the labels are made on the device
+ * inside the first kernel and no label leaves it.  key: a host array of vsc_guides_count entries, uploaded through context
+ * scratch that vsc_ctx_release_scratch gives back.  vsc_guides_pick requires site_len == 23; for vsc_pattern_guides the CALLER
+ * vouches for site_len.  `picked` may be NULL; otherwise *picked is a normal object of its kind on ctx's device (for a
+ * host-only input: a host-only object) that every later call takes, freed as every such object.  stats is optional.
+ *
+ * VSC_ERR_INVALID: a shape outside SHAPE or a non-zero reserved field; a NULL argument; an object or genome of another
+ * context; site_len != 23 for vsc_guides; both or neither of regions and target; a group without regions; regions built for
+ * another contig table; a group entry >= n_targets that is not VSC_REGION_NONE.  VSC_ERR_RANGE: regions without the label
+ * structure (as vsc_guides_locate); n > 0xFFFFFFFE.  n == 0: VSC_OK, nothing is launched, counts zeroed, picks all
+ * VSC_PICK_NONE.  Every refusal comes before anything is written.  vsc_last_error names the reason.
+ *
+ * Not offered: a vsc_multi_* entry (the host-only object goes through vsc_pick_host); keys composed on the device; weights or
+ * trained models; an optimal instead of the greedy choice under spacing.
+ */
+#define VSC_PICK_NONE 0xFFFFFFFFu
+typedef struct {
+    uint32_t site_len, cut, k, spacing;
+    uint64_t min_key;
+    uint64_t reserved; /* 0 */
+} vsc_pick_params;
+typedef struct {
+    uint64_t eligible, invalid, no_target, bad_target, below_min_key; /* the candidates by class: they add up to n */
+    uint64_t targets_picked; /* targets with at least one pick */
+    uint64_t targets_short;  /* targets that end short of k although eligible candidates were left (spacing exhausted) */
+    uint64_t picks;
+    double kernel_ms, wall_ms;
+    double stage_ms[4];      /* mark + scan, scatter, select, rank + picked (device calls; 0 from vsc_pick_host) */
+    uint64_t reserved[2];    /* 0 */
+} vsc_pick_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_pick_params) == 32 && sizeof(vsc_pick_stats) == 128, "vsc_pick_params / vsc_pick_stats layout");
+#else
+_Static_assert(sizeof(vsc_pick_params) == 32 && sizeof(vsc_pick_stats) == 128, "vsc_pick_params / vsc_pick_stats layout");
+#endif
+int vsc_pick_host(const vsc_contig *contigs, uint32_t n_contigs, const vsc_locus *loci, uint64_t n, const uint32_t *target,
+                  const uint64_t *key, uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks /* n_targets * k */,
+                  uint32_t *counts /* n_targets */, uint32_t *rank /* optional, n */, vsc_pick_stats *stats /* optional */);
+int vsc_loci_pick(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n, const uint32_t *target /* host */,
+                  const uint64_t *key /* host */, uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks, uint32_t *counts,
+                  uint32_t *rank /* optional */, vsc_pick_stats *stats /* optional */);
+int vsc_loci_pick_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n, const vsc_regions *regions,
+                          const uint32_t *group /* optional, host */, const uint64_t *key /* host */, uint32_t n_targets,
+                          const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank /* optional */,
+                          vsc_pick_stats *stats /* optional */);
+int vsc_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_regions *regions, const uint32_t *group,
+                    const uint32_t *target, uint32_t n_targets, const uint64_t *key, const vsc_pick_params *params, uint32_t *picks,
+                    uint32_t *counts, uint32_t *rank /* optional */, vsc_guides **picked /* optional */, vsc_pick_stats *stats /* optional */);
+int vsc_pattern_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_regions *regions,
+                            const uint32_t *group, const uint32_t *target, uint32_t n_targets, const uint64_t *key,
+                            const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank /* optional */,
+                            vsc_pattern_guides **picked /* optional */, vsc_pick_stats *stats /* optional */);
 
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*

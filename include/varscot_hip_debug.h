@@ -61,6 +61,8 @@ int vsc_debug_pattern_target_ranges(const vsc_contig *contigs, uint32_t n_contig
  * result; ctx == NULL: a host-only object, as vsc_multi_guides_enumerate returns.  Nothing is checked.  Freed with
  * vsc_guides_free. */
 int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out);
+/* The same for a vsc_pattern_guides (freed with vsc_pattern_guides_free). */
+int vsc_debug_pattern_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_pattern_guides **out);
 
 /* The device milliseconds of the context's last vsc_hits_sites / vsc_pattern_hits_sites, between HIP events on its stream:
  * the flag pass with the scan, and the write pass (either may be NULL).  The call leaves vsc_ctx_timing alone; this is where

@@ -318,6 +318,31 @@ class MhStats(C.Structure):
 
 assert C.sizeof(MhShape) == 16 and C.sizeof(MhStats) == 64
 
+PICK_NONE = 0xFFFFFFFF  # VSC_PICK_NONE: a picks entry beyond counts[t], the rank of a candidate that is not picked
+
+
+class PickParams(C.Structure):
+    """vsc_pick_params: the sites' length and cut, k picks per target at least `spacing` bases apart, the floor on the key."""
+    _fields_ = [("site_len", C.c_uint32), ("cut", C.c_uint32), ("k", C.c_uint32), ("spacing", C.c_uint32), ("min_key", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+class PickStats(C.Structure):
+    """vsc_pick_stats: the candidates of a call by class (the five counts add up to n), the targets with a pick, the targets
+    that end short of k with eligible candidates left, the picks, and the times."""
+    _fields_ = [("eligible", C.c_uint64), ("invalid", C.c_uint64), ("no_target", C.c_uint64), ("bad_target", C.c_uint64),
+                ("below_min_key", C.c_uint64), ("targets_picked", C.c_uint64), ("targets_short", C.c_uint64), ("picks", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double), ("stage_ms", C.c_double * 4), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("eligible", "invalid", "no_target", "bad_target", "below_min_key", "targets_picked",
+                                                "targets_short", "picks")}
+        d.update(kernel_ms=float(self.kernel_ms), wall_ms=float(self.wall_ms), stage_ms=[float(x) for x in self.stage_ms])
+        return d
+
+
+assert C.sizeof(PickParams) == 32 and C.sizeof(PickStats) == 128
+
 
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
@@ -533,6 +558,16 @@ SYMBOLS = [
     ("vsc_pattern_guides_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), _vp, C.POINTER(MhStats)]),
     ("vsc_guides_filter_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_microhomology", C.c_int, [_vp, _vp, _vp, C.POINTER(MhShape), C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_pick_host", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp, C.c_uint32, C.POINTER(PickParams), _vp, _vp, _vp,
+                                C.POINTER(PickStats)]),
+    ("vsc_loci_pick", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.c_uint32, C.POINTER(PickParams), _vp, _vp, _vp,
+                                C.POINTER(PickStats)]),
+    ("vsc_loci_pick_regions", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32, C.POINTER(PickParams), _vp, _vp, _vp,
+                                        C.POINTER(PickStats)]),
+    ("vsc_guides_pick", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(PickParams), _vp, _vp, _vp, C.POINTER(_vp),
+                                  C.POINTER(PickStats)]),
+    ("vsc_pattern_guides_pick", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(PickParams), _vp, _vp, _vp,
+                                          C.POINTER(_vp), C.POINTER(PickStats)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)
@@ -544,6 +579,7 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_pattern_target_ranges", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("vsc_multi_create_debug", C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(MultiDebugParams), C.POINTER(_vp)]),
     ("vsc_debug_guides_from_host", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_debug_pattern_guides_from_host", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_sites_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("vsc_debug_site_table_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("vsc_debug_bulge_hits_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),

@@ -969,6 +969,114 @@ def microhomology_scores(pairs):
     return mh, oof
 
 
+PICK_NONE = _lib.PICK_NONE  # a picks entry beyond counts[t]; the rank of a candidate that is not picked
+
+
+class PickShape:
+    """vsc_pick_params: k picks per target (1..32) whose cut sites lie at least `spacing` bases apart (0: no spacing), for
+    sites of site_len bases (16..32) cut between read positions cut - 1 and cut (SpCas9: 17); candidates whose key is below
+    min_key are never picked.  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, k, spacing=0, site_len=READ_LEN, cut=17, min_key=0, validate=True):
+        self.k, self.spacing, self.site_len, self.cut, self.min_key = int(k), int(spacing), int(site_len), int(cut), int(min_key)
+        if validate and not (1 <= self.k <= 32 and 0 <= self.spacing < 2 ** 32 and 16 <= self.site_len <= 32
+                             and 0 <= self.cut <= self.site_len and 0 <= self.min_key < 2 ** 64):
+            raise ValueError("a pick shape has k 1..32, spacing and min_key unsigned, site_len 16..32 and cut 0..site_len")
+
+    def _struct(self):
+        return _lib.PickParams(self.site_len, self.cut, self.k, self.spacing, self.min_key, 0)
+
+    def __repr__(self):
+        return "PickShape(k=%d, spacing=%d, site_len=%d, cut=%d, min_key=%d)" % (self.k, self.spacing, self.site_len, self.cut,
+                                                                                 self.min_key)
+
+
+def order_bits(values):
+    """The monotone map of float64 to uint64: all bits of a negative number flipped, the sign bit of every other - so that
+    a < b as numbers implies order_bits(a) < order_bits(b) (-0.0 lies just below +0.0).  NaN maps to 0, below everything."""
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    b = v.view(np.uint64)
+    out = np.where((b >> np.uint64(63)).astype(bool), ~b, b ^ np.uint64(1 << 63)).astype(np.uint64)
+    out[np.isnan(v)] = 0
+    return out
+
+
+def pick_key(columns, bits):
+    """One uint64 key per candidate out of unsigned integer columns in priority order: column i is clipped to its bits[i] bits
+    and the columns are packed most significant first, so that the larger key is the better candidate when larger is better
+    in every column.  More than 64 bits in all, a bit count outside 1..64, a signed or float column or columns of different
+    lengths are refused."""
+    if len(columns) != len(bits) or not columns:
+        raise ValueError("one bit count per column")
+    if any(not (1 <= int(b) <= 64) for b in bits) or sum(int(b) for b in bits) > 64:
+        raise ValueError("every column takes 1..64 bits and all of them at most 64")
+    n = len(columns[0])
+    key = np.zeros(n, dtype=np.uint64)
+    for col, b in zip(columns, bits):
+        c = np.asarray(col)
+        if c.dtype.kind != "u" or c.ndim != 1 or len(c) != n:
+            raise ValueError("a key column is a one-dimensional unsigned integer array, all of one length")
+        top = np.uint64(2 ** int(b) - 1)
+        key = (key << np.uint64(int(b) % 64)) | np.minimum(c.astype(np.uint64), top)
+    return key
+
+
+def _pick_arrays(n, n_targets, k, rank):
+    return (np.full((n_targets, k), PICK_NONE, dtype=np.uint32), np.zeros(n_targets, dtype=np.uint32),
+            np.full(n, PICK_NONE, dtype=np.uint32) if rank else None)
+
+
+def _pick_loci(loci_or_found):
+    """(codes or None, loci) of what a pick call is given: a PatternGuides, enumerate_guides' tuple, or loci."""
+    if isinstance(loci_or_found, PatternGuides):
+        return loci_or_found.codes, loci_or_found.loci
+    if isinstance(loci_or_found, tuple) and len(loci_or_found) >= 2 and isinstance(loci_or_found[1], np.ndarray) \
+            and loci_or_found[1].dtype == _lib.LOCUS_DTYPE:
+        return loci_or_found[0], loci_or_found[1]
+    return None, loci_or_found
+
+
+def pick_host(contigs, loci, target, key, n_targets, shape, rank=False):
+    """vsc_pick_host: the definition of the per-target pick as host code - no device.  contigs: a CONTIG_DTYPE array (a
+    PackedGenome's .contigs); loci, target (uint32, REGION_NONE: no target) and key (uint64, larger is better): one entry per
+    candidate.  Returns (picks uint32[n_targets, k], counts uint32[n_targets][, rank uint32[n]], stats)."""
+    ct = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE)
+    lo = _loci(loci, len(loci))
+    tg = np.ascontiguousarray(target, dtype=np.uint32)
+    ky = np.ascontiguousarray(key, dtype=np.uint64)
+    if len(tg) != len(lo) or len(ky) != len(lo):
+        raise ValueError("one target and one key per candidate")
+    picks, counts, rk = _pick_arrays(len(lo), int(n_targets), shape.k, rank)
+    st = _lib.PickStats()
+    sh = shape._struct()
+    check(lib().vsc_pick_host(ptr(ct), len(ct), ptr(lo), len(lo), ptr(tg), ptr(ky), int(n_targets), C.byref(sh), ptr(picks), ptr(counts),
+                              ptr(rk) if rk is not None else None, C.byref(st)))
+    return (picks, counts) + ((rk,) if rank else ()) + (st.as_dict(),)
+
+
+# The fixed quantisation of the columns a design call (and the tools' -b) can rank by: (bits, what the column is made from)
+PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20}
+
+
+def pick_column(name, values):
+    """One key column in the tools' fixed quantisation (PICK_COLUMNS bits): mit / table: rint(100 x specificity) of float64
+    specificities; eff: the top 20 bits of order_bits of the linear predictors; oof: floor(1000 oof / sum) of (sum, oof)
+    pairs, undefined -> 0; mh: min(sum, 2^20 - 1) of the pairs, undefined -> 0."""
+    if name in ("mit", "table"):  # (NaN and negative values: 0, as the undefined values of the other columns)
+        v = np.asarray(values, dtype=np.float64)
+        return np.rint(100.0 * np.where(np.isnan(v) | (v <= 0), 0.0, np.minimum(v, 1e6))).astype(np.uint64)
+    if name == "eff":
+        return order_bits(values) >> np.uint64(44)
+    pairs = np.asarray(values, dtype=np.uint32).reshape(-1, 2).astype(np.uint64)
+    undefined = pairs[:, 0] == MH_UNDEFINED
+    if name == "oof":
+        q = np.uint64(1000) * pairs[:, 1] // np.maximum(pairs[:, 0], np.uint64(1))
+        return np.where(undefined | (pairs[:, 0] == 0), np.uint64(0), q).astype(np.uint64)
+    if name == "mh":
+        return np.where(undefined, np.uint64(0), np.minimum(pairs[:, 0], np.uint64(2 ** 20 - 1))).astype(np.uint64)
+    raise ValueError("a pick column is one of mit, table, eff, oof, mh")
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -998,6 +1106,7 @@ class Regions:
             iv["contig"], iv["start"], iv["end"] = a[:, 0], a[:, 1], a[:, 2]
         contigs = np.ascontiguousarray(packed_genome.contigs, dtype=CONTIG_DTYPE)
         self.rule = rule
+        self.n_intervals = len(iv)
         self._h = C.c_void_p()
         check(lib().vsc_regions_build(ptr(contigs), len(contigs), ptr(iv), len(iv),
                                       _lib.REGION_INSIDE if rule == "inside" else _lib.REGION_OVERLAP, C.byref(self._h)))
@@ -1741,7 +1850,8 @@ class Genome:
         found = PatternGuides(p.decode(), protospacer, codes, loci)
         return (found,) + extra if extra else found
 
-    def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, table=None, **filters):
+    def design_pattern(self, pattern, protospacer, max_mismatches, targets=None, guide_batch=0, table=None, pick=None, pick_by=None,
+                       pick_groups=None, **filters):
         """Every guide of `targets` under a pattern, with its off-target counts: enumerate_pattern(pattern, protospacer,
         targets, **filters) followed by search_pattern (rows only) of the guides in query form on the same resident genome.
         Returns (PatternGuides, uint32 rows of shape (n, 9)); count[0] is reduced by one for the guide's own locus, which is
@@ -1750,7 +1860,12 @@ class Genome:
         same holds for microhomology= (and its floors), whose pairs come after the predictors.
         table= a PatternTable: search_pattern_table instead, and the TABLE_ROW_DTYPE rows follow the NM rows - each with the
         guide's own locus taken out as well, by the host's score of the guide (query form) against its own site (the
-        candidate's letters, PAM included), as count[0] is reduced."""
+        candidate's letters, PAM included), as count[0] is reduced.
+        pick= a PickShape whose site_len is the pattern's length (with pick_by= / pick_groups=): as Genome.design takes them,
+        over `targets` as a Regions under the enumeration's rule; the columns are "table" (the default; needs table=), "eff",
+        "oof" and "mh".  (picks, counts) come last of all."""
+        if pick is None and (pick_by is not None or pick_groups is not None):
+            raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
         extra = ()
         if isinstance(found, tuple):
@@ -1765,10 +1880,32 @@ class Genome:
                 if f:
                     trows["positive"][i] -= 1
                     trows["positive_nm"][i, 0] -= 1
-            return (found, rows, trows) + extra
-        _, rows = self.search_pattern(pattern, found.text(), max_mismatches, guide_batch=guide_batch, records=False)
-        rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
-        return (found, rows) + extra
+            out = (found, rows, trows) + extra
+        else:
+            _, rows = self.search_pattern(pattern, found.text(), max_mismatches, guide_batch=guide_batch, records=False)
+            rows[:, 0] -= np.minimum(rows[:, 0], 1).astype(np.uint32)
+            out = (found, rows) + extra
+        if pick is None:
+            return out
+        return self._design_pattern_pick(out, found, extra, targets, table, pick, pick_by, pick_groups, filters)
+
+    def _design_pattern_pick(self, out, found, extra, targets, table, pick, pick_by, pick_groups, filters):
+        if targets is None or self.packed is None:
+            raise ValueError("pick= needs targets and a genome made from a PackedGenome")
+        if isinstance(pick, PickShape) and pick.site_len != len(found.pattern):
+            raise ValueError("pick.site_len is %d, the pattern has %d letters" % (pick.site_len, len(found.pattern)))
+        rest = list(extra)
+        linear = rest.pop(0) if filters.get("efficiency") is not None else None
+        pairs = rest.pop(0) if filters.get("microhomology") is not None else None
+        spec = None
+        if table is not None:
+            spec = np.array([table_specificity(x) for x in out[2]["score_sum"]], dtype=np.float64)
+        regions = Regions(self.packed, targets, rule=filters.get("rule", "overlap"))
+        try:
+            return tuple(out) + self._pick_found(pick, pick_by, pick_groups, regions, found,
+                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs})
+        finally:
+            regions.close()
 
     # ---- on-target efficiency (vsc_*_efficiency) ------------------------------------------------------------------------
     @staticmethod
@@ -1876,6 +2013,74 @@ class Genome:
         stats = st.as_dict()
         _eff_partial(stats, allow_partial)
         return pairs, stats
+
+    def pick(self, loci_or_found, key, shape, regions=None, groups=None, target=None, n_targets=None, rank=False):
+        """The best shape.k candidates of every target under `key` (uint64 per candidate, larger is better), no two of one
+        target closer than shape.spacing bases at their cut sites - picked on the device.  loci_or_found: as
+        Genome.efficiency takes it.  The targets: either target= (uint32 per candidate, REGION_NONE: none; vsc_loci_pick) with
+        n_targets=, or regions= a Regions - the target of a candidate is the label of its first base, or groups[label] with
+        groups= (uint32 per interval as given to the Regions, REGION_NONE: the interval belongs to no target); the labels are
+        made on the device inside the first kernel (vsc_loci_pick_regions).
+        n_targets defaults to the largest target + 1 / the number of groups' targets / the number of intervals.  Returns
+        (picks uint32[n_targets, k], counts uint32[n_targets][, rank uint32[n]], stats): picks[t, r] is the index of the r-th
+        pick of target t, PICK_NONE beyond counts[t]; rank[i] = r where candidate i is the r-th pick of its target."""
+        codes, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        ky = np.ascontiguousarray(key, dtype=np.uint64)
+        if len(ky) != n:
+            raise ValueError("one key per candidate")
+        if (regions is None) == (target is None):
+            raise ValueError("exactly one of regions= and target= must be given")
+        if groups is not None and regions is None:
+            raise ValueError("groups= needs regions=")
+        L = lib()
+        st = _lib.PickStats()
+        sh = shape._struct()
+        if target is not None:
+            tg = np.ascontiguousarray(target, dtype=np.uint32)
+            if len(tg) != n:
+                raise ValueError("one target per candidate")
+            if n_targets is None:
+                named = tg[tg != _lib.REGION_NONE]
+                n_targets = int(named.max()) + 1 if len(named) else 0
+            picks, counts, rk = _pick_arrays(n, int(n_targets), shape.k, rank)
+            check(L.vsc_loci_pick(self.ctx._h, self._h, ptr(lo), n, ptr(tg), ptr(ky), int(n_targets), C.byref(sh), ptr(picks), ptr(counts),
+                                  ptr(rk) if rk is not None else None, C.byref(st)), self.ctx._h)
+            return (picks, counts) + ((rk,) if rank else ()) + (st.as_dict(),)
+        gr = None
+        if groups is not None:
+            gr = np.ascontiguousarray(groups, dtype=np.uint32)
+            if len(gr) != regions.n_intervals:
+                raise ValueError("groups holds %d entries for %d intervals" % (len(gr), regions.n_intervals))
+            if n_targets is None:
+                named = gr[gr != _lib.REGION_NONE]
+                n_targets = int(named.max()) + 1 if len(named) else 0
+        elif n_targets is None:
+            n_targets = regions.n_intervals
+        picks, counts, rk = _pick_arrays(n, int(n_targets), shape.k, rank)
+        check(L.vsc_loci_pick_regions(self.ctx._h, self._h, ptr(lo), n, regions._h, ptr(gr) if gr is not None else None, ptr(ky), int(n_targets),
+                                      C.byref(sh), ptr(picks), ptr(counts), ptr(rk) if rk is not None else None, C.byref(st)), self.ctx._h)
+        return (picks, counts) + ((rk,) if rank else ()) + (st.as_dict(),)
+
+    def _pick_found(self, pick, pick_by, pick_groups, regions, loci_or_found, columns):
+        """design's / design_pattern's pick= : the key out of the columns the call computed (columns: name -> values, None
+        where the call did not compute it) in the fixed quantisation of pick_column, then Genome.pick."""
+        if not isinstance(pick, PickShape):
+            raise ValueError("pick must be a PickShape")
+        if regions is None:
+            raise ValueError("pick= needs targets")
+        names = list(pick_by) if pick_by is not None else [next(iter(columns))]
+        cols = []
+        for name in names:
+            if name not in columns:
+                raise ValueError("this call cannot rank by %r" % (name,))
+            if columns[name] is None:
+                raise ValueError("pick_by=%r needs the option that computes it" % (name,))
+            cols.append(pick_column(name, columns[name]))
+        key = pick_key(cols, [PICK_COLUMNS[name] for name in names])
+        picks, counts, _ = self.pick(loci_or_found, key, pick, regions=regions, groups=pick_groups)
+        return picks, counts
 
     def efficiency(self, loci_or_found, model, allow_partial=False):
         """vsc_loci_efficiency: the linear predictors of candidates under an EfficiencyModel, computed on the device from the
@@ -2094,7 +2299,7 @@ class Genome:
 
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
                efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
-               **search_options):
+               pick=None, pick_by=None, pick_groups=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -2102,13 +2307,30 @@ class Genome:
         labels: as enumerate_guides; the labels then come last: (codes, loci, rows, labels).
         efficiency= / min_efficiency=: as enumerate_guides; only the survivors are searched, and the linear predictors come
         last of all: (codes, loci, rows[, labels], linear).  microhomology= / min_out_of_frame= / min_microhomology=: as
-        enumerate_guides; the pairs come after the predictors."""
+        enumerate_guides; the pairs come after the predictors.
+        pick= a PickShape: the best pick.k guides of every interval of `regions` (pick_groups= uint32 per interval: of every
+        group of intervals), Genome.pick under a key made of what this call computed - pick_by= column names in priority
+        order out of "mit" (the default; rint(100 x specificity), 14 bits), "eff" (the top 20 bits of order_bits of the
+        predictor), "oof" (floor(1000 oof / sum), 10 bits) and "mh" (min(sum, 2^20 - 1), 20 bits); a column whose option was
+        not given is refused.  (picks, counts) come last of all.  Without pick= nothing changes."""
+        if pick is None and (pick_by is not None or pick_groups is not None):
+            raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
                                       labels=labels, efficiency=efficiency, min_efficiency=min_efficiency,
                                       microhomology=microhomology, min_out_of_frame=min_out_of_frame,
                                       min_microhomology=min_microhomology)
         codes, loci = found[0], found[1]
-        return (codes, loci, self.summarize(codes, max_mismatches, exclude=loci, **search_options)) + tuple(found[2:])
+        rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
+        out = (codes, loci, rows) + tuple(found[2:])
+        if pick is None:
+            return out
+        extra = list(found[3:] if len(found) > 2 and _label_regions(labels, regions) is not None else found[2:])
+        linear = extra.pop(0) if efficiency is not None else None
+        pairs = extra.pop(0) if microhomology is not None else None
+        all_rows = rows[0] if isinstance(rows, tuple) else rows
+        spec = np.array([mit_specificity(x) for x in all_rows["mit_sum"]], dtype=np.float64)
+        return out + self._pick_found(pick, pick_by, pick_groups, regions, (codes, loci),
+                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs})
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)

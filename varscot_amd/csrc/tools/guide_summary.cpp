@@ -111,6 +111,10 @@
 // MIN_OOF[,MIN_MH] (needs -H) keeps only the candidates whose out-of-frame share is at least MIN_OOF per cent and whose score is
 // at least MIN_MH (vsc_guides_filter_microhomology), BEFORE the off-target search, as -y does.  Without -Y every
 // output is what it was.
+// -k K[,SPACING] [-b COLS] [-c interval|name] (needs -E and -L, one device) picks the K best guides of every -E target, their cut
+// sites at least SPACING bases apart (vsc_guides_pick; tools/pick_host.hpp makes the key from mit, table, eff, oof, mh
+// in the order of -b): the -L listing, written after the search whose rows rank the guides, gains the last columns pickTarget
+// pickRank (NA NA where a guide is not picked).  Without -k every output is byte for byte what it was.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -122,6 +126,7 @@
 
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
+#include "pick_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
 
@@ -183,6 +188,11 @@ int main(int argc, char **argv)
                                "position CUT (default 17) (needs -E, one device)", false},
         {'m', "min-out-of-frame", "MIN_OOF[,MIN_MH]: keep only the -E candidates whose out-of-frame share is at least MIN_OOF per cent and whose "
                                   "microhomology score is at least MIN_MH (needs -H)", false},
+        {'k', "pick", "K[,SPACING]: pick the K best guides (1 .. 32) of every -E target, their cut sites at least SPACING bases apart; adds the "
+                      "columns pickTarget pickRank to the -L file (needs -E and -L, one device)", false},
+        {'b', "pick-by", "With -k: what to rank by, comma-separated in priority order, out of mit (default), table (needs -W), eff (needs -Y), "
+                         "oof, mh (need -H)", false},
+        {'c', "pick-target", "With -k: interval (default; every -E interval is a target) or name (the -E intervals with one BED name are one target)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -541,6 +551,22 @@ int main(int argc, char **argv)
         return 1;
     }
 
+    // -k / -b / -c: the best guides of every -E target
+    PickOptions pick;
+    {
+        std::map<std::string, std::string> needs;
+        if (!tabled) needs["table"] = "give -W";
+        if (!efficient) needs["eff"] = "give -Y";
+        if (!mh.on) needs["oof"] = needs["mh"] = "give -H";
+        std::string why = parse_pick_options(opts[39].set, opts[39].value, opts[40].set, opts[40].value, opts[41].set, opts[41].value, discover, "-E",
+                                             devices.size() != 1, needs, &pick);
+        if (why.empty() && pick.on && !opts[20].set) why = "-k marks its picks in the -L file: give -L";
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -601,6 +627,9 @@ int main(int argc, char **argv)
         std::vector<std::string> ids, seqs;
         std::vector<vsc_locus> loci;
         std::vector<std::string> region_desc, target_desc;  // -N: per line of the -A / -E file
+        std::vector<uint32_t> pick_group;       // -k -c name: the target of every -E interval
+        std::vector<std::string> target_names;  // -k: what pickTarget prints per target
+        if (pick.on) pick_targets(pick, targets_path, "-E", &pick_group, &target_names);  // (before a device is opened: -c name may refuse the file)
         if (discover) {  // the guides themselves come from the device, below
             const std::vector<vsc_interval> iv = read_bed3(targets_path, "-E", naming && opts[20].set ? &target_desc : nullptr);
             if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), iv.data(), iv.size(), target_rule, &targets) != VSC_OK)
@@ -670,10 +699,12 @@ int main(int argc, char **argv)
             p.extra_pam[0] = pam[0];
             p.extra_pam[1] = pam[1];
         }
+        std::vector<double> eff_linear;    // -Y: the found guides' predictors
+        std::vector<uint32_t> mh_pairs;    // -H: their (sum, oof) pairs
+        std::vector<std::string> bed_lines;  // -k: the -L lines wait for the search, whose rows the picks rank by
         if (discover) {
             st = multi ? vsc_multi_guides_enumerate(multi, mgenome, targets, &ep, &found) : vsc_guides_enumerate(ctx, genome, targets, &ep, &found);
             if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
-            std::vector<double> eff_linear;
             if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
                 if (opts[34].set) {
                     vsc_guides *kept = nullptr;
@@ -693,7 +724,7 @@ int main(int argc, char **argv)
                 eff_linear.resize(vsc_guides_count(found));
                 if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
-            std::vector<uint32_t> mh_pairs(mh.on ? 2 * vsc_guides_count(found) : 0);
+            mh_pairs.resize(mh.on ? 2 * vsc_guides_count(found) : 0);
             if (mh.on && vsc_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t *fc = nullptr;
@@ -715,13 +746,16 @@ int main(int argc, char **argv)
                 for (int j = 0; j < VSC_READ_LEN; ++j) seq[j] = "ACGT"[(fc[i] >> (2 * j)) & 3u];
                 ids.push_back(chrom + ':' + std::to_string(fl[i].pos) + ':' + strand);
                 seqs.push_back(seq);
-                if (opts[20].set)
-                    bed6 += chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
+                if (opts[20].set) {
+                    const std::string line = chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
                             "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
                             (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
-                            (mh.on ? mh_columns(&mh_pairs[2 * i]) : "") + '\n';
+                            (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
+                    if (pick.on) bed_lines.push_back(line);
+                    else bed6 += line + '\n';
+                }
             }
-            if (opts[20].set) {
+            if (opts[20].set && !pick.on) {
                 std::ofstream out(guides_bed_path);
                 if (!out.is_open()) throw std::runtime_error("Could not open the -L path.");
                 out << bed6;
@@ -890,6 +924,26 @@ int main(int argc, char **argv)
             st = multi ? vsc_multi_search_summary_classified(multi, mgenome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data())
                        : vsc_search_summary_classified(ctx, genome, codes.data(), n_codes, &p, ex, &cls, nullptr, votes_rows.data());
             if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
+        }
+        if (pick.on) {  // -k: the picks of every target where the candidates lie, then the -L file with pickTarget pickRank
+            PickColumns cols;
+            cols.mit_rows = sum.data();
+            cols.table_rows = table_rows.data();
+            cols.eff = eff_linear.data();
+            cols.pairs = mh_pairs.data();
+            const std::vector<uint64_t> keys = pick_keys(pick, codes.size(), cols);
+            const uint32_t n_targets = (uint32_t)target_names.size();
+            const vsc_pick_params pp{(uint32_t)VSC_READ_LEN, 17, pick.k, pick.spacing, 0, 0};
+            std::vector<uint32_t> picks((size_t)n_targets * pick.k), counts(n_targets);
+            if (vsc_guides_pick(ctx, genome, found, targets, pick.by_name ? pick_group.data() : nullptr, nullptr, n_targets, keys.data(), &pp, picks.data(),
+                                counts.data(), nullptr, nullptr, nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
+            const std::vector<std::string> marks = pick_text(pick, codes.size(), target_names, picks, counts);
+            std::ofstream out(guides_bed_path);
+            if (!out.is_open()) throw std::runtime_error("Could not open the -L path.");
+            for (size_t i = 0; i < bed_lines.size(); ++i) out << bed_lines[i] << marks[i] << '\n';
+            out.close();
+            if (!out) throw std::runtime_error("Could not write the -L file.");
         }
         std::vector<vsc_bulge_summary> bulge_rows(bulged ? codes.size() : 0);
         if (bulged) {

@@ -49,6 +49,9 @@
 // stays over all hits.  -K and -S need -W and -T.  Without -W every output is what it was.
 // Host C++ only: the search runs in libvarscot_hip.so (vsc_search_pattern); there is no CPU search here.  Every argument is
 // checked before a device is opened.
+// -k K[,SPACING] -b COLS [-c interval|name] (needs -E and -B) picks the K best guides of every -B target, their cut sites at
+// least SPACING bases apart (vsc_pattern_guides_pick; tools/pick_host.hpp): ranked by table, eff, oof, mh in the order
+// of -b - pattern hits have no MIT score, so -b is required -; the -E listing gains the last columns pickTarget pickRank.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -59,6 +62,7 @@
 
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
+#include "pick_host.hpp"
 #include "vsc_host.hpp"
 
 using namespace vsc_host;
@@ -231,6 +235,11 @@ int main(int argc, char **argv)
                                "bases behind its start)", false},
         {'m', "min-out-of-frame", "With -H: MIN_OOF[,MIN_MH]: keep only the candidates whose out-of-frame share is at least MIN_OOF per cent "
                                   "and whose microhomology score is at least MIN_MH", false},
+        {'k', "pick", "With -E and -B: K[,SPACING]: pick the K best guides (1 .. 32) of every -B target, their cut sites at least SPACING bases "
+                      "apart; the -E listing gains the columns pickTarget pickRank", false},
+        {'b', "pick-by", "With -k: what to rank by, comma-separated in priority order, out of table (needs -W, -M and -O), eff (needs -Y), oof, mh "
+                         "(need -H); the default, mit, is guide_summary's: give -b", false},
+        {'c', "pick-target", "With -k: interval (default; every -B interval is a target) or name (the -B intervals with one BED name are one target)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -436,6 +445,23 @@ int main(int argc, char **argv)
     }
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
+    // -k / -b / -c: the best guides of every -B target
+    PickOptions pick;
+    // the cut that -H defaults to: three bases in front of a 3' PAM, 18 behind the start of a protospacer that follows a 5' PAM
+    const uint32_t pick_cut = std::min<uint32_t>((uint32_t)pattern.size(), ep.ps_start == 0 ? (ep.ps_len >= 3 ? ep.ps_len - 3 : 0) : ep.ps_start + 18);
+    {
+        std::map<std::string, std::string> needs;
+        needs["mit"] = "pattern hits have no MIT score; give -b";
+        if (!tabled || !opts[3].set) needs["table"] = "give -W with -M and -O";
+        if (!efficient) needs["eff"] = "give -Y";
+        if (!mh.on) needs["oof"] = needs["mh"] = "give -H";
+        const std::string why = parse_pick_options(opts[27].set, opts[27].value, opts[28].set, opts[28].value, opts[29].set, opts[29].value,
+                                                   enumerate && opts[8].set, "-E -B", opts[4].value.find(',') != std::string::npos, needs, &pick);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     vsc_pattern_select sel{};
     const bool site_scored = opts[22].set;
     if (site_scored && (!tabled || !bulged || !sited || !has_extension(opts[22].value, {"tsv", "txt"}))) {
@@ -546,6 +572,9 @@ int main(int argc, char **argv)
         const PackedIndex ix = read_index(prefix);
         std::vector<vsc_interval> targets;
         if (opts[8].set) targets = read_targets(opts[8].value, ix);
+        std::vector<uint32_t> pick_group;       // -k -c name: the target of every -B interval
+        std::vector<std::string> target_names;  // -k: what pickTarget prints per target
+        if (pick.on) pick_targets(pick, opts[8].value, "-B", &pick_group, &target_names);  // (before a device is opened: -c name may refuse the file)
         int st = vsc_ctx_create((int)device, &ctx);
         if (st != VSC_OK) throw std::runtime_error(st == VSC_ERR_NODEVICE ? "no HIP device available (there is no CPU fallback)" : "could not create the device context");
         st = vsc_genome_load(ctx, ix.hi.data(), ix.lo.data(), ix.nm.data(), 0, ix.hi.size(), ix.hi.size(), ix.contigs.data(),
@@ -554,6 +583,9 @@ int main(int argc, char **argv)
         std::printf("Index loaded.\n");
 
         const vsc_locus *loci = nullptr;
+        std::vector<double> eff_linear;       // -Y: the found guides' predictors
+        std::vector<uint32_t> mh_pairs;       // -H: their (sum, oof) pairs
+        std::vector<std::string> pick_lines;  // -k: the -E lines wait for the search, whose rows the picks may rank by
         std::vector<uint32_t> own_fixed;  // -E with -W: the table score of every found guide against its own site
         if (enumerate) {
             // an empty -B file is a target set that holds nothing: a pointer that is not NULL with n = 0
@@ -561,7 +593,6 @@ int main(int argc, char **argv)
             st = vsc_guides_enumerate_pattern(ctx, genome, pattern.c_str(), len, &ep, opts[8].set ? (targets.empty() ? &none : targets.data()) : nullptr,
                                               targets.size(), &found);
             if (st != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
-            std::vector<double> eff_linear;
             if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
                 if (opts[17].set) {
                     vsc_pattern_guides *kept = nullptr;
@@ -581,7 +612,7 @@ int main(int argc, char **argv)
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
-            std::vector<uint32_t> mh_pairs(mh.on ? 2 * vsc_pattern_guides_count(found) : 0);
+            mh_pairs.resize(mh.on ? 2 * vsc_pattern_guides_count(found) : 0);
             if (mh.on && vsc_pattern_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_pattern_guides_count(found);
@@ -591,7 +622,8 @@ int main(int argc, char **argv)
             std::printf("Guides found (total: %llu).\n", (unsigned long long)n);
             std::ofstream out(opts[7].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
-            out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "") << '\n';
+            out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
+                << (pick.on ? "\tpickTarget\tpickRank" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -607,10 +639,11 @@ int main(int argc, char **argv)
                     own_fixed.push_back(f);
                 }
                 guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
-                out << guides[i].seq << '\t' << first_word(ix.names[loci[i].contig]) << '\t' << loci[i].pos << '\t' << (loci[i].strand ? '-' : '+');
-                if (efficient) out << '\t' << eff_text(eff_linear[i]) << '\t' << eff_text(vsc_eff_link(eff_model, eff_linear[i]));
-                if (mh.on) out << mh_columns(&mh_pairs[2 * i]);
-                out << '\n';
+                std::string line = guides[i].seq + '\t' + first_word(ix.names[loci[i].contig]) + '\t' + std::to_string(loci[i].pos) + '\t' + (loci[i].strand ? '-' : '+');
+                if (efficient) line += '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i]));
+                if (mh.on) line += mh_columns(&mh_pairs[2 * i]);
+                if (pick.on) pick_lines.push_back(line);
+                else out << line << '\n';
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }
@@ -636,6 +669,37 @@ int main(int argc, char **argv)
                     table_rows[g].score_sum -= own_fixed[g];
                     if (own_fixed[g]) table_rows[g].positive -= 1, table_rows[g].positive_nm[0] -= 1;
                 }
+        }
+        if (pick.on) {  // -k: the picks of every -B target where the candidates lie; the -E listing's lines follow its header
+            vsc_regions *pick_regions = nullptr;
+            if (vsc_regions_build(ix.contigs.data(), (uint32_t)ix.contigs.size(), targets.data(), targets.size(), ep.rule, &pick_regions) != VSC_OK)
+                throw std::runtime_error("could not build the regions of the -B file");
+            int prc = VSC_OK;
+            std::vector<uint32_t> picks, counts;
+            try {
+                PickColumns cols;
+                cols.table_rows = table_rows.data();
+                cols.eff = eff_linear.data();
+                cols.pairs = mh_pairs.data();
+                const std::vector<uint64_t> keys = pick_keys(pick, guides.size(), cols);
+                const uint32_t n_targets = (uint32_t)target_names.size();
+                const vsc_pick_params pp{len, mh.on ? mh.shape.cut : pick_cut, pick.k, pick.spacing, 0, 0};
+                picks.resize((size_t)n_targets * pick.k);
+                counts.resize(n_targets);
+                prc = vsc_pattern_guides_pick(ctx, genome, found, pick_regions, pick.by_name ? pick_group.data() : nullptr, nullptr, n_targets, keys.data(), &pp,
+                                              picks.data(), counts.data(), nullptr, nullptr, nullptr);
+            } catch (...) {
+                vsc_regions_free(pick_regions);
+                throw;
+            }
+            vsc_regions_free(pick_regions);
+            if (prc != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+            const std::vector<std::string> marks = pick_text(pick, guides.size(), target_names, picks, counts);
+            std::ofstream out(opts[7].value, std::ios::app);
+            if (!out.is_open()) throw std::runtime_error("Could not open output path.");
+            for (size_t i = 0; i < pick_lines.size(); ++i) out << pick_lines[i] << marks[i] << '\n';
+            out.close();
+            if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }
         // -v: the same search in the individual's genome - windows of the pattern's length from the packed planes, on the same
         // context; with -E the enumerated loci are the excluded on-targets, with -R nothing is excluded

@@ -13,6 +13,7 @@
 //   vsc_pattern_bulge.hip  bulges under a pattern
 //   vsc_efficiency.hip     on-target efficiency of candidates
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
+//   vsc_pick.hip           the best K candidates per target, with spacing
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
 #include <algorithm>
@@ -36,6 +37,7 @@
 #include "vsc_internal.h"
 #include "vsc_objects.h"
 #include "vsc_pairs.h"
+#include "vsc_pick_device.h"
 #include "vsc_sites.h"
 #include "vsc_bulge_table.h"
 #include "vsc_table.h"
@@ -245,7 +247,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
                          &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
-                         &ctx->eff_out, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
+                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
@@ -2317,18 +2319,14 @@ int resident_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *
     return upload_regions(ctx, regions, dev);
 }
 
-// The labels of n 16-byte records on ctx's device (vsc_hit or vsc_locus) into host memory: the regions' copy the sinks use
-// (start[], class table), beside it the label structure - end[], index[], up[], the contig offsets and lengths the regions
-// were built for, in one buffer keyed by the regions' serial number as regions_buf is - then locate_kernel and one copy back.
-// The context's timing is left as it is.
-int locate_records(vsc_ctx *ctx, const vsc_regions *regions, const void *records, uint64_t n, bool hit_records, uint32_t *labels,
-                   const char *who)
+// What a kernel locates with, resident on ctx's device: the regions' copy the sinks use (start[], class table), beside it the
+// label structure - end[], index[], up[], the contig offsets and lengths the regions were built for, in one buffer keyed by
+// the regions' serial number as regions_buf is.  Fills a.reg, a.loc and the contig table of `a` (locate_records below, and
+// the first kernel of vsc_*_pick).
+int resident_locate(vsc_ctx *ctx, const vsc_regions *regions, LocateArgs &a, const char *who)
 {
-    ctx->err.clear();
     if (!regions->has_locate) return fail_in(ctx, VSC_ERR_RANGE, who, "the regions hold more intervals than a 32-bit label can number");
-    HostTimer lap;
     VSC_HIP(ctx, hipSetDevice(ctx->device));
-    LocateArgs a{};
     const int urc = upload_regions(ctx, regions, a.reg);
     if (urc != VSC_OK) return urc;
     const size_t m = regions->loc_end.size(), nc = regions->contig_off.size();
@@ -2348,12 +2346,25 @@ int locate_records(vsc_ctx *ctx, const vsc_regions *regions, const void *records
         VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the regions as soon as its call returns)
         ctx->locate_serial = regions->serial;
     }
-    lap.lap("locate: tables resident");
     const uint32_t *p = (const uint32_t *)ctx->locate_buf.p;
     a.loc = LocateView{p, p + m, p + 2 * m};
     a.contig_off = p + 3 * m;
     a.contig_len = p + 3 * m + nc;
     a.n_contigs = (uint32_t)nc;
+    return VSC_OK;
+}
+
+// The labels of n 16-byte records on ctx's device (vsc_hit or vsc_locus) into host memory: the tables resident, then
+// locate_kernel and one copy back.  The context's timing is left as it is.
+int locate_records(vsc_ctx *ctx, const vsc_regions *regions, const void *records, uint64_t n, bool hit_records, uint32_t *labels,
+                   const char *who)
+{
+    ctx->err.clear();
+    HostTimer lap;
+    LocateArgs a{};
+    const int rrc = resident_locate(ctx, regions, a, who);
+    if (rrc != VSC_OK) return rrc;
+    lap.lap("locate: tables resident");
     a.records = (const uint4 *)records;
     a.n = n;
     VSC_HIP(ctx, ctx->locate_out.ensure(n * sizeof(uint32_t)));
@@ -4598,13 +4609,17 @@ int vsc_pattern_guides_filter_microhomology(vsc_ctx *ctx, const vsc_genome *geno
     return mh_filter(ctx, genome, in, shape, false, min_sum, min_oof_permille, out, "vsc_pattern_guides_filter_microhomology");
 }
 
-int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out)
+}  // extern "C"
+
+namespace {
+
+template <class Guides> int guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, Guides **out)
 {
     if (!out) return VSC_ERR_INVALID;
     *out = nullptr;
     if (n && (!codes || !loci)) return VSC_ERR_INVALID;
     return guarded(ctx, [&]() -> int {
-    std::unique_ptr<vsc_guides, int (*)(vsc_guides *)> g(new vsc_guides(), object_free<vsc_guides>);
+    std::unique_ptr<Guides, int (*)(Guides *)> g(new Guides(), object_free<Guides>);
     g->n = n;
     g->codes.assign(codes, codes + n);
     g->loci.assign(loci, loci + n);
@@ -4622,6 +4637,413 @@ int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_lo
     *out = g.release();
     return VSC_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_guides **out)
+{
+    return guides_from_host(ctx, codes, loci, n, out);
+}
+
+int vsc_debug_pattern_guides_from_host(vsc_ctx *ctx, const uint64_t *codes, const vsc_locus *loci, uint64_t n, vsc_pattern_guides **out)
+{
+    return guides_from_host(ctx, codes, loci, n, out);
+}
+
+}  // extern "C"
+
+// ---- the best K guides per target, with spacing (the definition: vsc_pick.h, the kernels: vsc_pick.hip) ----------
+namespace {
+
+int pick_check(vsc_ctx *ctx, const vsc_pick_params *params, PickShape &s, const char *who)
+{
+    if (!params) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    s = PickShape{params->site_len, params->cut, params->k, params->spacing, params->min_key};
+    if (params->reserved || !pick_shape_valid(s))
+        return fail_in(ctx, VSC_ERR_INVALID, who, "site_len 16 .. 32, cut 0 .. site_len, k 1 .. 32, reserved 0");
+    return VSC_OK;
+}
+
+// vsc::pick_host (vsc_pick.h: the definition as host code) with its counts as a vsc_pick_stats
+void pick_host_stats(const PickShape &s, const uint32_t *contig_len, uint32_t n_contigs, const vsc_locus *loci, uint64_t n, const uint32_t *target,
+                     const uint64_t *key, uint32_t n_targets, uint32_t *picks, uint32_t *counts, uint32_t *rank, vsc_pick_stats *stats)
+{
+    static_assert(sizeof(vsc_locus) == sizeof(PickLocus), "vsc_locus is four 32-bit words");
+    uint64_t seen[kPickStats] = {};
+    pick_host(s, contig_len, n_contigs, (const PickLocus *)loci, n, target, key, n_targets, picks, counts, rank, seen);
+    if (stats) {
+        stats->eligible = seen[kPickEligible];
+        stats->invalid = seen[kPickInvalid];
+        stats->no_target = seen[kPickNoTarget];
+        stats->bad_target = seen[kPickBadTarget];
+        stats->below_min_key = seen[kPickBelowMinKey];
+        stats->targets_picked = seen[kPickStatTargets];
+        stats->targets_short = seen[kPickStatShort];
+        stats->picks = seen[kPickStatPicks];
+    }
+}
+
+// The gather of the picked candidates of a host-only object, in ascending index
+template <class Guides> int pick_gather_host(const Guides *in, const uint32_t *rank, Guides **picked)
+{
+    std::unique_ptr<Guides, int (*)(Guides *)> g(new Guides(), object_free<Guides>);
+    for (uint64_t i = 0; i < in->n; ++i)
+        if (rank[i] != kPickNone) {
+            g->codes.push_back(in->codes[i]);
+            g->loci.push_back(in->loci[i]);
+        }
+    g->n = g->codes.size();
+    g->host_valid = true;
+    *picked = g.release();
+    return VSC_OK;
+}
+
+// What a device call picks from: the loci on ctx's device already (d_loci) or the host's (h_loci: uploaded first), the keys
+// (host), and either the targets (host) or the regions (+ group, host).
+struct PickInput {
+    const void *d_loci = nullptr;
+    const vsc_locus *h_loci = nullptr;
+    uint64_t n = 0;
+    const uint64_t *key = nullptr;
+    const uint32_t *target = nullptr;
+    const vsc_regions *regions = nullptr;
+    const uint32_t *group = nullptr;
+    uint32_t n_targets = 0;
+};
+
+// Mark + scan, one 8-byte read-back (the eligible candidates: it sizes the records), scatter, select, rank; picks, counts, rank
+// and the stats to the host.  *d_rank (optional) = the ranks on the device afterwards, for the `picked` passes.
+int pick_device(vsc_ctx *ctx, const vsc_genome *genome, const PickShape &s, const PickInput &in, uint32_t *picks, uint32_t *counts, uint32_t *rank,
+                bool want_rank, const uint32_t **d_rank, vsc_pick_stats *stats, const char *who)
+{
+    const uint64_t n = in.n;
+    const uint32_t nt = in.n_targets;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    PickArgs a{};
+    a.shape = s;
+    a.n = n;
+    a.n_targets = nt;
+    a.contig_off = genome->d_contig_off;
+    a.contig_end = genome->d_contig_end;
+    a.n_contigs = genome->n_contigs;
+    size_t n_group = 0;
+    if (in.regions) {
+        LocateArgs la{};
+        const int lrc = resident_locate(ctx, in.regions, la, who);
+        if (lrc != VSC_OK) return lrc;
+        a.reg = la.reg;
+        a.loc = la.loc;
+        if (in.group) n_group = (size_t)in.regions->n_input;
+    }
+    // uploads: [keys][targets or groups][loci], 256-byte aligned parts
+    const size_t key_bytes = round256((size_t)n * sizeof(uint64_t));
+    const size_t tg_bytes = round256((in.target ? (size_t)n : n_group) * sizeof(uint32_t));
+    VSC_HIP(ctx, ctx->pick_in.ensure(key_bytes + tg_bytes + (in.h_loci ? (size_t)n * sizeof(vsc_locus) : 0) + 256));
+    char *ib = (char *)ctx->pick_in.p;
+    VSC_HIP(ctx, hipMemcpyAsync(ib, in.key, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    a.key = (const unsigned long long *)ib;
+    if (in.target) {
+        VSC_HIP(ctx, hipMemcpyAsync(ib + key_bytes, in.target, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        a.target = (const uint32_t *)(ib + key_bytes);
+    } else if (n_group) {
+        VSC_HIP(ctx, hipMemcpyAsync(ib + key_bytes, in.group, n_group * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        a.group = (const uint32_t *)(ib + key_bytes);
+        a.n_group = (uint32_t)n_group;
+    }
+    if (in.h_loci) {
+        VSC_HIP(ctx, hipMemcpyAsync(ib + key_bytes + tg_bytes, in.h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)(ib + key_bytes + tg_bytes);
+    } else {
+        a.loci = (const uint4 *)in.d_loci;
+    }
+    // tables: [stats][count][cursor] (zeroed together) [segment offsets][tgt][picks][counts][rank]
+    const size_t stats_bytes = 256, cnt_bytes = round256(((size_t)nt + 1) * sizeof(uint32_t));
+    const size_t off_bytes = round256(((size_t)nt + 1) * sizeof(unsigned long long)), tgt_bytes = round256((size_t)n * sizeof(uint32_t));
+    const size_t picks_bytes = round256((size_t)nt * s.k * sizeof(uint32_t) + 4);
+    VSC_HIP(ctx, ctx->pick_tabs.ensure(stats_bytes + 3 * cnt_bytes + off_bytes + 2 * tgt_bytes + picks_bytes));
+    char *tb = (char *)ctx->pick_tabs.p;
+    a.stats = (unsigned long long *)tb;
+    a.count = (uint32_t *)(tb + stats_bytes);
+    a.cursor = (uint32_t *)(tb + stats_bytes + cnt_bytes);
+    unsigned long long *const d_off = (unsigned long long *)(tb + stats_bytes + 2 * cnt_bytes);
+    a.seg_off = d_off;
+    a.tgt = (uint32_t *)(tb + stats_bytes + 2 * cnt_bytes + off_bytes);
+    a.picks = (uint32_t *)(tb + stats_bytes + 2 * cnt_bytes + off_bytes + tgt_bytes);
+    a.counts = (uint32_t *)(tb + stats_bytes + 2 * cnt_bytes + off_bytes + tgt_bytes + picks_bytes);
+    a.rank = (uint32_t *)(tb + stats_bytes + 3 * cnt_bytes + off_bytes + tgt_bytes + picks_bytes);
+    VSC_HIP(ctx, hipMemsetAsync(tb, 0, stats_bytes + 2 * cnt_bytes, ctx->stream));
+    hipEvent_t *const ev = ctx->ev;  // five marks: the first five events of the context
+    VSC_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+    VSC_HIP(ctx, launch_pick_mark(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, launch_enum_scan(a.count, nt, d_off, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
+    unsigned long long n_rec = 0;
+    VSC_HIP(ctx, hipMemcpyAsync(&n_rec, d_off + nt, sizeof n_rec, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_rec > n) return fail_in(ctx, VSC_ERR_DEVICE, who, "more eligible candidates than candidates");
+    const size_t rec_bytes = round256((size_t)n_rec * sizeof(uint4));
+    VSC_HIP(ctx, ctx->pick_recs.ensure(rec_bytes + (size_t)n_rec * sizeof(uint32_t) + 256));
+    a.rec = (uint4 *)ctx->pick_recs.p;
+    a.rec_index = (uint32_t *)((char *)ctx->pick_recs.p + rec_bytes);
+    a.n_rec = n_rec;
+    VSC_HIP(ctx, launch_pick_scatter(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
+    VSC_HIP(ctx, launch_pick_select(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
+    if (want_rank) {
+        VSC_HIP(ctx, hipMemsetAsync(a.rank, 0xFF, (size_t)n * sizeof(uint32_t), ctx->stream));
+        VSC_HIP(ctx, launch_pick_rank(a, ctx->n_cus, ctx->stream));
+    }
+    VSC_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
+    unsigned long long seen[kPickStats] = {};
+    if (nt) {
+        VSC_HIP(ctx, hipMemcpyAsync(picks, a.picks, (size_t)nt * s.k * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(counts, a.counts, (size_t)nt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (rank) VSC_HIP(ctx, hipMemcpyAsync(rank, a.rank, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (d_rank) *d_rank = a.rank;
+    float ms[4] = {};
+    for (int i = 0; i < 4; ++i) VSC_HIP(ctx, hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    if (stats) {
+        stats->eligible = seen[kPickEligible];
+        stats->invalid = seen[kPickInvalid];
+        stats->no_target = seen[kPickNoTarget];
+        stats->bad_target = seen[kPickBadTarget];
+        stats->below_min_key = seen[kPickBelowMinKey];
+        stats->targets_picked = seen[kPickStatTargets];
+        stats->targets_short = seen[kPickStatShort];
+        stats->picks = seen[kPickStatPicks];
+        for (int i = 0; i < 4; ++i) stats->stage_ms[i] = ms[i];
+        stats->kernel_ms = (double)ms[0] + ms[1] + ms[2] + ms[3];
+    }
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ms[0] + ms[1] + ms[2] + ms[3];
+    t.sites = n;
+    // DESIGN 4.27's floors: mark reads 16 + 8 and writes 4 per candidate; scatter reads 16 + 8 + 4 per candidate and writes 20 per
+    // record; select reads 20 per record and writes 4 k + 4 per target
+    t.genome_bytes = n * 28 + (n * 28 + n_rec * 20) + (n_rec * 20 + (uint64_t)nt * (4 * s.k + 4));
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+// the checks every call shares; nothing is written
+int pick_front(vsc_ctx *ctx, const vsc_pick_params *params, PickShape &s, uint64_t n, uint32_t n_targets, const uint64_t *key, uint32_t *picks,
+               uint32_t *counts, const char *who)
+{
+    const int rc = pick_check(ctx, params, s, who);
+    if (rc != VSC_OK) return rc;
+    if ((n_targets && (!picks || !counts)) || (n && !key)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (n > kPickMaxCandidates) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    return VSC_OK;
+}
+
+// behind every refusal: the stats zeroed; true: n == 0, the outputs are written and the call is done
+bool pick_begin(const PickShape &s, uint64_t n, uint32_t n_targets, uint32_t *picks, uint32_t *counts, uint32_t *rank, vsc_pick_stats *stats)
+{
+    if (stats) *stats = vsc_pick_stats{};
+    if (n == 0) pick_outputs_empty(s, 0, n_targets, picks, counts, rank);
+    return n == 0;
+}
+
+// regions (+ group) as a call's targets: built for the genome's contig table, with the label structure, every group entry a
+// target or VSC_REGION_NONE
+int pick_regions_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_regions *regions, const uint32_t *group, uint32_t n_targets, const char *who)
+{
+    bool same = regions->contig_off.size() == genome->n_contigs;
+    for (uint32_t c = 0; same && c < genome->n_contigs; ++c)
+        same = genome->h_contig_off[c] == regions->contig_off[c] && genome->h_contig_end[c] - genome->h_contig_off[c] == regions->contig_len[c];
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the regions were built for another contig table");
+    if (!regions->has_locate) return fail_in(ctx, VSC_ERR_RANGE, who, "the regions hold more intervals than a 32-bit label can number");
+    if (group)
+        for (uint64_t j = 0; j < regions->n_input; ++j)
+            if (group[j] != kPickNone && group[j] >= n_targets)
+                return fail_in(ctx, VSC_ERR_INVALID, who, "a group entry is neither a target nor VSC_REGION_NONE");
+    return VSC_OK;
+}
+
+// vsc_guides_pick / vsc_pattern_guides_pick
+template <class Guides>
+int pick_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_regions *regions, const uint32_t *group, const uint32_t *target,
+                uint32_t n_targets, const uint64_t *key, const vsc_pick_params *params, bool need_23, uint32_t *picks, uint32_t *counts,
+                uint32_t *rank, Guides **picked, vsc_pick_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->err.clear();
+    if (picked) *picked = nullptr;
+    if (!genome || !guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    PickShape s{};
+    const uint64_t n = guides->n;
+    const int rc = pick_front(ctx, params, s, n, n_targets, key, picks, counts, who);
+    if (rc != VSC_OK) return rc;
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if ((regions != nullptr) == (target != nullptr)) return fail_in(ctx, VSC_ERR_INVALID, who, "exactly one of regions and target must be given");
+    if (group && !regions) return fail_in(ctx, VSC_ERR_INVALID, who, "a group needs regions");
+    if (regions) {
+        const int grc = pick_regions_check(ctx, genome, regions, group, n_targets, who);
+        if (grc != VSC_OK) return grc;
+    }
+    if (pick_begin(s, n, n_targets, picks, counts, rank, stats)) {
+        if (picked) {
+            std::unique_ptr<Guides, int (*)(Guides *)> g(new Guides(), object_free<Guides>);
+            g->ctx = guides->ctx;
+            g->host_valid = true;
+            *picked = g.release();
+        }
+        return VSC_OK;
+    }
+    if (!guides->ctx) {  // vsc_multi_guides_enumerate's host-only object: the same picks by the host's definition
+        std::vector<uint32_t> tg, lens(genome->n_contigs), rk;
+        for (uint32_t c = 0; c < genome->n_contigs; ++c) lens[c] = genome->h_contig_end[c] - genome->h_contig_off[c];
+        if (regions) {
+            tg.resize((size_t)n);
+            for (uint64_t i = 0; i < n; ++i) {
+                const uint32_t label = vsc_regions_locate(regions, guides->loci[i].contig, guides->loci[i].pos);
+                tg[i] = label == VSC_REGION_NONE || !group ? label : group[label];
+            }
+            target = tg.data();
+        }
+        if (picked && !rank) {
+            rk.resize((size_t)n);
+            rank = rk.data();
+        }
+        pick_host_stats(s, lens.data(), genome->n_contigs, guides->loci.data(), n, target, key, n_targets, picks, counts, rank, stats);
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return picked ? pick_gather_host(guides, rank, picked) : VSC_OK;
+    }
+    PickInput in;
+    in.d_loci = (const char *)guides->storage.p + guides->loci_at;
+    in.n = n;
+    in.key = key;
+    in.target = target;
+    in.regions = regions;
+    in.group = group;
+    in.n_targets = n_targets;
+    const uint32_t *d_rank = nullptr;
+    const int prc = pick_device(ctx, genome, s, in, picks, counts, rank, rank || picked, &d_rank, stats, who);
+    if (prc != VSC_OK) return prc;
+    if (picked) {
+        const vsc_timing kept = ctx->timing;
+        PickGatherArgs ga{};
+        ga.in_codes = (const unsigned long long *)guides->storage.p;
+        ga.in_loci = (const uint4 *)in.d_loci;
+        ga.rank = d_rank;
+        ga.n = n;
+        const uint64_t tiles = (n + kPickTile - 1) / kPickTile;
+        const int erc = run_enumeration(ctx, who, ga, nullptr, (uint32_t)tiles, nullptr, 0, 0, picked,
+                                        [&](const void *, unsigned long long, bool write) { return launch_pick_gather(ga, write, ctx->stream); });
+        if (erc != VSC_OK) return erc;
+        if (stats) {
+            stats->stage_ms[3] += ctx->timing.scan_ms;
+            stats->kernel_ms += ctx->timing.scan_ms;
+        }
+        ctx->timing = kept;
+    }
+    if (stats) stats->wall_ms = wall_ms_since(t0);
+    return VSC_OK;
+    });
+}
+
+// vsc_loci_pick / vsc_loci_pick_regions behind their own checks: host loci, the targets as an array or as regions (+ group)
+int pick_loci(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const uint32_t *target, const vsc_regions *regions,
+              const uint32_t *group, const uint64_t *key, uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks, uint32_t *counts,
+              uint32_t *rank, vsc_pick_stats *stats, const char *fn, std::chrono::steady_clock::time_point t0)
+{
+    PickShape s{};
+    const int rc = pick_front(ctx, params, s, n, n_targets, key, picks, counts, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && (!loci || (!regions && !target))) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (regions) {
+        const int grc = pick_regions_check(ctx, genome, regions, group, n_targets, fn);
+        if (grc != VSC_OK) return grc;
+    }
+    if (pick_begin(s, n, n_targets, picks, counts, rank, stats)) return VSC_OK;
+    PickInput in;
+    in.h_loci = loci;
+    in.n = n;
+    in.key = key;
+    in.target = target;
+    in.regions = regions;
+    in.group = group;
+    in.n_targets = n_targets;
+    const int prc = pick_device(ctx, genome, s, in, picks, counts, rank, rank != nullptr, nullptr, stats, fn);
+    if (prc == VSC_OK && stats) stats->wall_ms = wall_ms_since(t0);
+    return prc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_pick_host(const vsc_contig *contigs, uint32_t n_contigs, const vsc_locus *loci, uint64_t n, const uint32_t *target, const uint64_t *key,
+                  uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank, vsc_pick_stats *stats)
+{
+    return guarded(nullptr, [&]() -> int {
+    const auto t0 = std::chrono::steady_clock::now();
+    PickShape s{};
+    if (n_contigs && !contigs) return VSC_ERR_INVALID;
+    const int rc = pick_front(nullptr, params, s, n, n_targets, key, picks, counts, "vsc_pick_host");
+    if (rc != VSC_OK) return rc;
+    if (n && (!loci || !target)) return VSC_ERR_INVALID;
+    if (pick_begin(s, n, n_targets, picks, counts, rank, stats)) return VSC_OK;
+    std::vector<uint32_t> lens(n_contigs);
+    for (uint32_t c = 0; c < n_contigs; ++c) lens[c] = contigs[c].length;
+    pick_host_stats(s, lens.data(), n_contigs, loci, n, target, key, n_targets, picks, counts, rank, stats);
+    if (stats) stats->wall_ms = wall_ms_since(t0);
+    return VSC_OK;
+    });
+}
+
+int vsc_loci_pick(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const uint32_t *target, const uint64_t *key,
+                  uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank, vsc_pick_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_pick";
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->err.clear();
+    if (!genome) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    return pick_loci(ctx, genome, loci, n, target, nullptr, nullptr, key, n_targets, params, picks, counts, rank, stats, fn, t0);
+    });
+}
+
+int vsc_loci_pick_regions(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_regions *regions, const uint32_t *group,
+                          const uint64_t *key, uint32_t n_targets, const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank,
+                          vsc_pick_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_pick_regions";
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->err.clear();
+    if (!genome || !regions) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, fn, "genome belongs to another context");
+    return pick_loci(ctx, genome, loci, n, nullptr, regions, group, key, n_targets, params, picks, counts, rank, stats, fn, t0);
+    });
+}
+
+int vsc_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_regions *regions, const uint32_t *group,
+                    const uint32_t *target, uint32_t n_targets, const uint64_t *key, const vsc_pick_params *params, uint32_t *picks,
+                    uint32_t *counts, uint32_t *rank, vsc_guides **picked, vsc_pick_stats *stats)
+{
+    return pick_guides(ctx, genome, guides, regions, group, target, n_targets, key, params, true, picks, counts, rank, picked, stats, "vsc_guides_pick");
+}
+
+int vsc_pattern_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_regions *regions, const uint32_t *group,
+                            const uint32_t *target, uint32_t n_targets, const uint64_t *key, const vsc_pick_params *params, uint32_t *picks,
+                            uint32_t *counts, uint32_t *rank, vsc_pattern_guides **picked, vsc_pick_stats *stats)
+{
+    return pick_guides(ctx, genome, guides, regions, group, target, n_targets, key, params, false, picks, counts, rank, picked, stats,
+                       "vsc_pattern_guides_pick");
 }
 
 }  // extern "C"

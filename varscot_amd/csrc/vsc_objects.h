@@ -133,6 +133,10 @@ struct vsc_ctx {
     // vsc_*_microhomology (no model) bring their candidates in eff_in and leave their pairs in eff_out as well.
     vsc::DeviceBuf eff_buf, eff_in, eff_out;
     uint64_t eff_serial = 0;  // 0: none resident
+    // vsc_*_pick: what a call uploads (keys, then the targets or the groups, then the loci of a call that brings
+    // them from the host), the call's tables (targets per candidate, per-target counts, segment offsets, cursors, stats, picks,
+    // counts, ranks) and the records of the eligible candidates in their targets' segments
+    vsc::DeviceBuf pick_in, pick_tabs, pick_recs;
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
@@ -235,6 +239,7 @@ struct vsc_regions {
     // has_locate == false: more input intervals than a 32-bit label can number, the three arrays are empty
     std::vector<uint32_t> loc_end, loc_index, loc_up;
     bool has_locate = false;
+    uint64_t n_input = 0;  // intervals the caller gave (labels number them; vsc_*_pick's group[] has one entry per each)
     uint32_t rule = 0, block_shift = 0, n_blocks = 0;
     uint64_t serial = 0;  // process-wide, handed out by vsc_regions_build: what a context's device copy is keyed by
     vsc_regions_stats stats{};

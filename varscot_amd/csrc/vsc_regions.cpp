@@ -89,6 +89,7 @@ int vsc_regions_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_i
             r->end_max[i] = run;
         }
         r->rule = rule;
+        r->n_input = n;
         // the label structure, eagerly (the object is immutable and shared between threads): of the intervals before a bound on
         // the start, the last one in this order whose end is large enough is the most specific one - largest start, smallest end,
         // lowest input index.  up[k] = the previous entry with a greater end, by a monotonic stack: the entries between it and k
