@@ -2031,6 +2031,107 @@ int vsc_pattern_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_
                             const vsc_pick_params *params, uint32_t *picks, uint32_t *counts, uint32_t *rank /* optional */,
                             vsc_pattern_guides **picked /* optional */, vsc_pick_stats *stats /* optional */);
 
+/* ---- base-editor guide design: editing windows and target join ----------------------------------- */
+/*
+ * Base editors (CBE: C->T, ABE: A->G) do not cut: they convert one kind of base inside a short window of the protospacer.
+ * "Which candidates place my base inside the window, which other editable bases (bystanders) sit there, and which guides are
+ * best for every target?" - answered on the resident genome, where the candidates lie.
+ *
+ * SHAPE    site_len 16 .. 32;  win_start, win_len with 1 <= win_len <= 16 and win_start + win_len <= site_len, in READ positions of
+ *          the site (0 = its first read base; the window may reach into PAM letters - the shape is the caller's);
+ *          from 0 .. 3 (A C G T): the base the editor converts ON THE READ STRAND (CBE: C, ABE: A);  reserved fields 0.
+ * SITE     of a locus (c, p, strand), p = first base of the site on the forward strand as everywhere, in read orientation:
+ *          '+': c[p, p + site_len);  '-': its reverse complement.  This is eff_context with up = down = 0.
+ * CLASS    one per candidate, tested in EffClass order: invalid (contig, strand, or the site leaves its contig), not_resident,
+ *          has_n (an N anywhere in the site), defined.  off_contig cannot occur; its count stays 0.
+ * MASK     bit j (0 <= j < win_len) is set iff the read base at win_start + j equals `from`.  Bits from win_len on are 0.
+ * FORWARD  position of window position j on the candidate's contig:  '+': p + win_start + j;  '-': p + site_len - 1 - (win_start + j).
+ * TARGETS  n_t points (contig, pos), STRICTLY ascending by (contig, pos), pos < the contig's length, n_t <= 0xFFFFFFFE.
+ *          A target's index is its place in the array.  NULL with n_t == 0: no targets.
+ * HITS     bit j is set iff MASK bit j is set and (the candidate's contig, FORWARD(j)) is a target.  The strand needs no rule of
+ *          its own: a '+' candidate reaches targets whose forward letter is `from`, a '-' candidate those whose forward letter
+ *          is its complement, and no candidate reaches a target with another letter.
+ * ROW      two uint32 per candidate: (mask, hits).  Both are 0xFFFFFFFF (VSC_EDIT_UNDEFINED) unless the class is defined.
+ *          Without targets hits = 0.
+ * PAIR     one per set bit of hits, 16 bytes: { candidate (index i), target (index), mask, info = at | bystanders << 8 },
+ *          at = j, bystanders = popcount(mask) - 1.  Order: ascending (candidate, target).  For a '-' candidate that is
+ *          DESCENDING j.  n <= 0xFFFFFFFE.
+ * COVERAGE optional, two uint32 per target: the number of pairs of the target, and the smallest `bystanders` among them
+ *          (0xFFFFFFFF when the target has no pair).
+ * FILTER   keep a candidate iff its class is defined, min_editable <= popcount(mask) <= max_editable, and (no targets were
+ *          given, or hits != 0).  Survivors keep their input order.
+ *
+ * The output is a function of the inputs alone: it does not depend on launch shape or wave order.  The coverage counters use
+ * integer add / min atomics, which commute; nothing else depends on an atomic's order, and the pairs have no append cursor.
+ *
+ * vsc_edit_site_text: the MASK of one site of site_len letters (any case) in read orientation on the host, by the function the
+ * kernels call.  A letter other than ACGT, a text of another length, a shape outside SHAPE: VSC_ERR_INVALID.
+ *
+ * vsc_loci_edit: loci are host entries in any order, duplicates allowed.  rows (optional): rows[2 i], rows[2 i + 1] = mask, hits of
+ * loci[i].  The pairs follow vsc_loci_pairs' contract: *n_pairs (optional) is always the full count; pairs == NULL only counts;
+ * a count above `capacity` is VSC_ERR_RANGE, and then nothing is written to `pairs`, while rows, coverage, stats and *n_pairs
+ * are valid.  coverage (optional): 2 n_t entries.  stats (optional): the candidates by class (the five counts add up to n), the
+ * candidates with a hit, the pairs, the targets with a pair, the rows kernel's time and the call's wall time in milliseconds.
+ * n == 0: VSC_OK, nothing is launched, the coverage says "no pair".  vsc_guides_edit works over the candidates where they lie on
+ * the device - no locus travels - and requires site_len == 23; the host-only object of vsc_multi_guides_enumerate goes the
+ * vsc_loci_edit way.  vsc_pattern_guides_edit is the same for vsc_pattern_guides: site_len is the pattern's length, which the
+ * CALLER vouches for, as in the pick calls.
+ *
+ * vsc_guides_filter_edit / vsc_pattern_guides_filter_edit: *out = the candidates of `in` that pass FILTER - codes and loci copied
+ * unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of 1 024 candidates, as the
+ * microhomology filter.  The result is a normal object of its kind on ctx's device.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a shape outside SHAPE or
+ * with a non-zero reserved field; NULL arguments; a genome or object of another context; site_len != 23 for vsc_guides; targets
+ * not strictly ascending, on an unknown contig, or beyond their contig; min_editable > max_editable; n_t > 0 with NULL targets.
+ * VSC_ERR_RANGE: n or n_t above 0xFFFFFFFE.  Uploads and results use context scratch; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: a vsc_multi_* entry; editing-efficiency or outcome models that need trained weights; codon consequences;
+ * sequence-context preferences of the deaminase beyond `from`; more than one window per call (call twice).
+ */
+#define VSC_EDIT_UNDEFINED 0xFFFFFFFFu
+typedef struct {
+    uint32_t site_len, win_start, win_len;
+    uint32_t from; /* 0 .. 3: A C G T */
+    uint32_t reserved[4]; /* 0 */
+} vsc_edit_shape;
+typedef struct {
+    uint32_t contig, pos;
+} vsc_edit_target;
+typedef struct {
+    uint32_t candidate, target, mask;
+    uint32_t info; /* at | bystanders << 8 */
+} vsc_edit_pair;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t with_hit, pairs, targets_covered;
+    double kernel_ms, wall_ms;
+    uint64_t reserved[2]; /* 0 */
+} vsc_edit_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_edit_shape) == 32 && sizeof(vsc_edit_target) == 8 && sizeof(vsc_edit_pair) == 16 && sizeof(vsc_edit_stats) == 96,
+              "vsc_edit_* layout");
+#else
+_Static_assert(sizeof(vsc_edit_shape) == 32 && sizeof(vsc_edit_target) == 8 && sizeof(vsc_edit_pair) == 16 && sizeof(vsc_edit_stats) == 96,
+               "vsc_edit_* layout");
+#endif
+int vsc_edit_site_text(const char *site /* site_len letters, read orientation, any case */, const vsc_edit_shape *shape, uint32_t *mask);
+int vsc_loci_edit(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                  const vsc_edit_shape *shape, const vsc_edit_target *targets /* host */, uint64_t n_t, uint32_t *rows /* host, 2 n, optional */,
+                  vsc_edit_pair *pairs /* host, optional */, uint64_t capacity, uint64_t *n_pairs /* optional */,
+                  uint32_t *coverage /* host, 2 n_t, optional */, vsc_edit_stats *stats /* optional */);
+int vsc_guides_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_edit_shape *shape,
+                    const vsc_edit_target *targets, uint64_t n_t, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity,
+                    uint64_t *n_pairs, uint32_t *coverage, vsc_edit_stats *stats);
+int vsc_pattern_guides_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_edit_shape *shape,
+                            const vsc_edit_target *targets, uint64_t n_t, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity,
+                            uint64_t *n_pairs, uint32_t *coverage, vsc_edit_stats *stats);
+int vsc_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_edit_shape *shape,
+                           const vsc_edit_target *targets, uint64_t n_t, uint32_t min_editable, uint32_t max_editable, vsc_guides **out);
+int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_edit_shape *shape,
+                                   const vsc_edit_target *targets, uint64_t n_t, uint32_t min_editable, uint32_t max_editable,
+                                   vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

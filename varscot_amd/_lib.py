@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VSC_LIB_PATH") or os.path.join(_HERE, "libvarscot_hip.so")  # override for A/B experiments
 
 VSC_OK = 0
+VSC_ERR_RANGE = -34
 ERRORS = {-22: "VSC_ERR_INVALID", -12: "VSC_ERR_NOMEM", -5: "VSC_ERR_DEVICE", -34: "VSC_ERR_RANGE",
           -19: "VSC_ERR_NODEVICE"}
 
@@ -344,6 +345,35 @@ class PickStats(C.Structure):
 assert C.sizeof(PickParams) == 32 and C.sizeof(PickStats) == 128
 
 
+EDIT_UNDEFINED = 0xFFFFFFFF  # VSC_EDIT_UNDEFINED
+EDIT_TARGET_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4")])
+EDIT_PAIR_DTYPE = np.dtype([("candidate", "<u4"), ("target", "<u4"), ("mask", "<u4"), ("info", "<u4")])
+
+
+class EditShapeStruct(C.Structure):
+    """vsc_edit_shape: the site's length, the window [win_start, win_start + win_len) in read positions and the base (0..3: A C G
+    T) the editor converts on the read strand."""
+    _fields_ = [("site_len", C.c_uint32), ("win_start", C.c_uint32), ("win_len", C.c_uint32), ("base", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class EditStats(C.Structure):
+    """vsc_edit_stats: the candidates of a call by class (the five counts add up to n), the candidates with a hit, the pairs,
+    the targets with a pair, the rows kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("with_hit", C.c_uint64), ("pairs", C.c_uint64), ("targets_covered", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n", "with_hit", "pairs",
+                                                "targets_covered")}
+        d.update(kernel_ms=float(self.kernel_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(EditShapeStruct) == 32 and C.sizeof(EditStats) == 96 and EDIT_PAIR_DTYPE.itemsize == 16 and EDIT_TARGET_DTYPE.itemsize == 8
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -568,6 +598,17 @@ SYMBOLS = [
                                   C.POINTER(PickStats)]),
     ("vsc_pattern_guides_pick", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(PickParams), _vp, _vp, _vp,
                                           C.POINTER(_vp), C.POINTER(PickStats)]),
+    ("vsc_edit_site_text", C.c_int, [C.c_char_p, C.POINTER(EditShapeStruct), C.POINTER(C.c_uint32)]),
+    ("vsc_loci_edit", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(EditShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                C.POINTER(C.c_uint64), _vp, C.POINTER(EditStats)]),
+    ("vsc_guides_edit", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                  C.POINTER(C.c_uint64), _vp, C.POINTER(EditStats)]),
+    ("vsc_pattern_guides_edit", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64), _vp, C.POINTER(EditStats)]),
+    ("vsc_guides_filter_edit", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_edit", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), _vp, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                 C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)

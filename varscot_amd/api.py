@@ -1077,6 +1077,106 @@ def pick_column(name, values):
     raise ValueError("a pick column is one of mit, table, eff, oof, mh")
 
 
+EDIT_UNDEFINED = _lib.EDIT_UNDEFINED  # mask and hits of a candidate whose site is undefined
+EDIT_PAIR_DTYPE = _lib.EDIT_PAIR_DTYPE
+
+
+class EditShape:
+    """vsc_edit_shape: where a base editor edits.  site_len 16..32 is the candidates' length (23 for enumerate_guides', the
+    pattern's for enumerate_pattern's); window = (start, length) in read positions of the site, 0 = its first read base,
+    length 1..16; base is the letter the editor converts on the read strand ("C" for a CBE, "A" for an ABE; or 0..3).
+    EDITORS holds two presets for the SpCas9 23-mer, "CBE" (window (3, 5), C) and "ABE" (window (3, 4), A): common published
+    windows and nothing more - an editor's real window depends on the deaminase, the linker and the target.
+    validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, window=(3, 5), base="C", validate=True):
+        self.site_len, self.win_start, self.win_len = int(site_len), int(window[0]), int(window[1])
+        if isinstance(base, (str, bytes)):
+            b = base.decode() if isinstance(base, bytes) else base
+            if len(b) != 1 or b.upper() not in "ACGT":
+                raise ValueError("an editor converts one of A, C, G, T")
+            self.base = "ACGT".index(b.upper())
+        else:
+            self.base = int(base)
+        if validate and not (16 <= self.site_len <= 32 and 1 <= self.win_len <= 16 and 0 <= self.win_start
+                             and self.win_start + self.win_len <= self.site_len and 0 <= self.base <= 3):
+            raise ValueError("an edit shape has site_len 16..32, a window of 1..16 bases inside the site and a base A, C, G or T")
+
+    @property
+    def window(self):
+        return self.win_start, self.win_len
+
+    def _struct(self):
+        return _lib.EditShapeStruct(self.site_len, self.win_start, self.win_len, self.base, (C.c_uint32 * 4)(0, 0, 0, 0))
+
+    def __repr__(self):
+        return "EditShape(site_len=%d, window=(%d, %d), base=%r)" % (self.site_len, self.win_start, self.win_len,
+                                                                     "ACGT"[self.base] if 0 <= self.base <= 3 else self.base)
+
+
+# Two presets for the SpCas9 23-mer (20 protospacer bases, then NGG; read position 0 is the PAM-distal end): the windows
+# commonly published for BE3 / BE4-type cytosine editors (protospacer positions 4-8) and ABE7.10-type adenine editors
+# (positions 4-7).  They are common published windows and nothing more: an editor's real window depends on the deaminase,
+# the linker and the target, and a caller who knows better passes an EditShape.
+EDITORS = {"CBE": EditShape(READ_LEN, (3, 5), "C"), "ABE": EditShape(READ_LEN, (3, 4), "A")}
+
+
+def edit_site_text(site, shape):
+    """vsc_edit_site_text: the MASK of one site of shape.site_len letters (any case) in read orientation on the host, by the
+    function the kernels call: bit j is set iff the letter at window position j is the editor's base.  A letter other than
+    ACGT or a text of another length raises VarscotError."""
+    b = site if isinstance(site, bytes) else site.encode()
+    m = C.c_uint32()
+    sh = shape._struct()
+    check(lib().vsc_edit_site_text(b, C.byref(sh), C.byref(m)))
+    return int(m.value)
+
+
+def unpack_edit_info(info):
+    """(at, bystanders) of an edit pair's info word (or an array of them): the window position of the target's base and the
+    number of other editable bases in the window."""
+    i = np.asarray(info, dtype=np.uint32)
+    return i & np.uint32(0xFF), i >> np.uint32(8)
+
+
+def edit_targets(targets):
+    """The targets of an edit call as the library takes them: (sorted EDIT_TARGET_DTYPE array without duplicates - strictly
+    ascending (contig, pos) -, order, inverse).  order[k] is the caller's index of sorted target k (the first of its
+    duplicates), inverse[i] the sorted index of the caller's target i.  targets: (contig, pos) rows or an array with
+    "contig" and "pos" fields, in any order."""
+    if isinstance(targets, np.ndarray) and targets.dtype.names and {"contig", "pos"} <= set(targets.dtype.names):
+        c, p = targets["contig"].astype(np.int64), targets["pos"].astype(np.int64)
+    else:
+        a = np.asarray(targets, dtype=np.int64).reshape(-1, 2)
+        c, p = a[:, 0], a[:, 1]
+    if len(c) and (c.min() < 0 or c.max() > 0xFFFFFFFF or p.min() < 0 or p.max() > 0xFFFFFFFF):
+        raise ValueError("a target is a (contig, pos) of unsigned 32-bit numbers")
+    key = (c.astype(np.uint64) << np.uint64(32)) | p.astype(np.uint64)
+    uniq, order, inverse = np.unique(key, return_index=True, return_inverse=True)
+    out = np.zeros(len(uniq), dtype=_lib.EDIT_TARGET_DTYPE)
+    out["contig"], out["pos"] = (uniq >> np.uint64(32)).astype(np.uint32), (uniq & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    return out, order.astype(np.int64), np.asarray(inverse, dtype=np.int64).reshape(-1)
+
+
+def edit_pick_inputs(pairs, loci, extra_columns=()):
+    """What Genome.pick takes for "of every target the K guides with the fewest bystanders": (loci[pairs.candidate],
+    pairs.target, key) - one pick candidate per edit pair, its target the pair's, its key made with pick_key so that fewer
+    bystanders is better: the first column is 15 - bystanders (4 bits).  extra_columns: (values per CANDIDATE of the edit
+    call, bits) in priority order behind it - unsigned integer arrays, larger is better (pick_column makes them)."""
+    pr = np.asarray(pairs, dtype=_lib.EDIT_PAIR_DTYPE)
+    lo = _loci(loci, len(loci))
+    cand = pr["candidate"].astype(np.int64)
+    cols = [(np.uint64(15) - (pr["info"] >> np.uint32(8)).astype(np.uint64))]
+    bits = [4]
+    for values, b in extra_columns:
+        v = np.asarray(values)
+        if v.dtype.kind != "u" or v.ndim != 1 or len(v) != len(lo):
+            raise ValueError("an extra column is a one-dimensional unsigned integer array with one value per candidate")
+        cols.append(v[cand])
+        bits.append(int(b))
+    return lo[cand], pr["target"].astype(np.uint32), pick_key(cols, bits)
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -1802,7 +1902,8 @@ class Genome:
 
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
                           max_guides=0, params=None, efficiency=None, min_efficiency=None, microhomology=None,
-                          min_out_of_frame=None, min_microhomology=None):
+                          min_out_of_frame=None, min_microhomology=None, edit=None, edit_targets=None, min_editable=None,
+                          max_editable=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -1818,7 +1919,11 @@ class Genome:
         (uint32[n, 2], vsc_pattern_guides_microhomology) come last, after the predictors when both are asked for.
         min_out_of_frame=x (per cent) / min_microhomology=y (score units; both need microhomology=): only the candidates
         whose score is defined, at least y, and out of frame for at least x per cent of it
-        (vsc_pattern_guides_filter_microhomology).  Both floors are applied on the device, in either order the same bytes."""
+        (vsc_pattern_guides_filter_microhomology).  Both floors are applied on the device, in either order the same bytes.
+        edit= an EditShape whose site_len is the pattern's length: the candidates' (mask, hits) rows (uint32[n, 2],
+        vsc_pattern_guides_edit) come last of all.  edit_targets= (contig, pos) rows / min_editable= / max_editable= (all need
+        edit=): only the candidates whose site is defined, whose window holds min_editable .. max_editable editable bases and
+        - with targets - reaches a target (vsc_pattern_guides_filter_edit), on the device after the other floors."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -1827,6 +1932,7 @@ class Genome:
         L = lib()
         self._eff_args(efficiency, min_efficiency, len(p))
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, len(p))
+        ed = self._edit_args(edit, edit_targets, min_editable, max_editable, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -1835,7 +1941,8 @@ class Genome:
             extra = self._scores_on_handle(held, efficiency, min_efficiency, mh, L.vsc_pattern_guides_count,
                                            (L.vsc_pattern_guides_efficiency, L.vsc_pattern_guides_filter_efficiency),
                                            (L.vsc_pattern_guides_microhomology, L.vsc_pattern_guides_filter_microhomology),
-                                           L.vsc_pattern_guides_free)
+                                           L.vsc_pattern_guides_free, ed,
+                                           (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -1863,7 +1970,8 @@ class Genome:
         candidate's letters, PAM included), as count[0] is reduced.
         pick= a PickShape whose site_len is the pattern's length (with pick_by= / pick_groups=): as Genome.design takes them,
         over `targets` as a Regions under the enumeration's rule; the columns are "table" (the default; needs table=), "eff",
-        "oof" and "mh".  (picks, counts) come last of all."""
+        "oof" and "mh".  (picks, counts) come last of all.  edit= (and its options), as enumerate_pattern takes them: only the
+        survivors are searched; the edit rows come after the microhomology pairs, before (picks, counts)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -1977,18 +2085,22 @@ class Genome:
         _eff_partial(st.as_dict(), False)
         return pairs
 
-    def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn):
-        """Both floors, then both scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs.  held[0] is replaced as _eff_on_handle replaces it."""
+    def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None):
+        """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
+        the microhomology pairs before the edit rows.  held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
         if mh is not None:
             self._mh_on_handle(held, mh, count_fn, mh_fns[0], mh_fns[1], free_fn, score=False)
+        if ed is not None:
+            self._edit_on_handle(held, ed, count_fn, ed_fns[0], ed_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
         if mh is not None:
             extra += (self._mh_on_handle(held, (mh[0], None, None), count_fn, mh_fns[0], mh_fns[1], free_fn),)
+        if ed is not None:
+            extra += (self._edit_on_handle(held, ed[:4] + (None,), count_fn, ed_fns[0], ed_fns[1], free_fn),)
         return extra
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
@@ -2013,6 +2125,108 @@ class Genome:
         stats = st.as_dict()
         _eff_partial(stats, allow_partial)
         return pairs, stats
+
+    # ---- base-editor windows (vsc_*_edit) --------------------------------------------------------------------------------
+    @staticmethod
+    def _edit_args(shape, targets, min_editable, max_editable, site_len):
+        """(shape, sorted targets or None, order, inverse, (min, max) or None) - or None without a shape."""
+        if shape is None:
+            if targets is not None or min_editable is not None or max_editable is not None:
+                raise ValueError("edit_targets / min_editable / max_editable need edit=shape")
+            return None
+        if isinstance(shape, str):
+            if shape not in EDITORS:
+                raise ValueError("edit names one of %s, or is an EditShape" % ", ".join(sorted(EDITORS)))
+            shape = EDITORS[shape]
+        if not isinstance(shape, EditShape):
+            raise ValueError("edit must be an EditShape or the name of a preset")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        tg = order = inverse = None
+        if targets is not None:
+            tg, order, inverse = edit_targets(targets)
+        bounds = None
+        if min_editable is not None or max_editable is not None or tg is not None:
+            bounds = (0 if min_editable is None else int(min_editable), 16 if max_editable is None else int(max_editable))
+            if not 0 <= bounds[0] <= bounds[1] <= 0xFFFFFFFF:
+                raise ValueError("0 <= min_editable <= max_editable is needed")
+        return shape, tg, order, inverse, bounds
+
+    def _edit_on_handle(self, held, ed, count_fn, rows_fn, filter_fn, free_fn, rows=True):
+        """As _mh_on_handle, for the edit rows: ed = what _edit_args returned.  With bounds (or targets) the handle is first
+        replaced by the filter's result; the rows of the survivors come back as uint32[n, 2]."""
+        shape, tg, _, _, bounds = ed
+        sh = shape._struct()
+        n_t = 0 if tg is None else len(tg)
+        tp = ptr(tg) if n_t else None
+        if bounds is not None:
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), tp, n_t, bounds[0], bounds[1], C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        r = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.EditStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), tp, n_t, ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return r
+
+    def edit(self, loci_or_found, shape, targets=None, pairs=True, coverage=False, allow_partial=False):
+        """vsc_loci_edit: the editing windows of candidates under an EditShape (or the name of a preset of EDITORS), and their
+        join with targets, on the device from the resident planes.  Returns (rows, pairs, coverage, stats).
+        rows uint32[n, 2]: (mask, hits) per candidate - bit j of mask is set iff the read base at window position j is the
+        editor's base, bit j of hits iff that base is a target as well; (EDIT_UNDEFINED, EDIT_UNDEFINED) where the site is
+        undefined.  targets: (contig, pos) rows or an array with those fields in any order, duplicates allowed (edit_targets
+        sorts them); None: no targets, hits = 0.  pairs (EDIT_PAIR_DTYPE; None with pairs=False or without targets): one per
+        set bit of hits - candidate, target (the index in the CALLER's array; of duplicates the first), mask, info
+        (unpack_edit_info: at, bystanders) - in ascending (candidate, target).  coverage (uint32[len(targets), 2] in the
+        caller's order with coverage=True, else None): pairs of the target, fewest bystanders among them (EDIT_UNDEFINED: no
+        pair).  stats: the candidates by class, with_hit, pairs, targets_covered (over distinct targets), kernel_ms, wall_ms
+        and target_order (the caller's index of every sorted target).  loci_or_found: as Genome.efficiency takes it.  Raises
+        when a site is not resident on this object (a shard) unless allow_partial=True."""
+        if isinstance(shape, str):
+            if shape not in EDITORS:
+                raise ValueError("shape names one of %s, or is an EditShape" % ", ".join(sorted(EDITORS)))
+            shape = EDITORS[shape]
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        tg = order = inverse = None
+        if targets is not None:
+            tg, order, inverse = edit_targets(targets)
+        n_t = 0 if tg is None else len(tg)
+        tp = ptr(tg) if n_t else None
+        rows = np.empty((n, 2), dtype=np.uint32)
+        cov = np.empty((n_t, 2), dtype=np.uint32) if coverage and tg is not None else None
+        want_pairs = bool(pairs) and tg is not None
+        cap = min(max(n, 1024), 1 << 22) if want_pairs else 0
+        pr = np.empty(cap, dtype=_lib.EDIT_PAIR_DTYPE) if want_pairs else None
+        st = _lib.EditStats()
+        sh = shape._struct()
+        count = C.c_uint64()
+        L = lib()
+        rc = L.vsc_loci_edit(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), tp, n_t, ptr(rows), ptr(pr), cap, C.byref(count), ptr(cov),
+                             C.byref(st))
+        if rc == _lib.VSC_ERR_RANGE and want_pairs and cap < int(count.value) <= 0xFFFFFFFE:
+            # (the rows, the coverage and the stats of the first call stand; the second brings the pairs alone)
+            cap = int(count.value)
+            pr = np.empty(cap, dtype=_lib.EDIT_PAIR_DTYPE)
+            check(L.vsc_loci_edit(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), tp, n_t, None, ptr(pr), cap, C.byref(count), None, None),
+                  self.ctx._h)
+        else:
+            check(rc, self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        if want_pairs:
+            pr = pr[:int(count.value)].copy()
+            pr["target"] = order[pr["target"].astype(np.int64)].astype(np.uint32)
+            pr = pr[np.lexsort((pr["target"], pr["candidate"]))]
+        if cov is not None:
+            cov = cov[inverse]
+        if order is not None:
+            stats["target_order"] = order
+        return rows, pr, cov, stats
 
     def pick(self, loci_or_found, key, shape, regions=None, groups=None, target=None, n_targets=None, rank=False):
         """The best shape.k candidates of every target under `key` (uint64 per candidate, larger is better), no two of one
@@ -2237,7 +2451,7 @@ class Genome:
 
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
-                         min_microhomology=None):
+                         min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2252,22 +2466,28 @@ class Genome:
         microhomology= a MicrohomologyShape with site_len 23: the candidates' (sum, oof) pairs (uint32[n, 2],
         vsc_guides_microhomology) come last of all, after the predictors.  min_out_of_frame=x (per cent) /
         min_microhomology=y (score units; both need microhomology=): only the candidates whose score is defined, at least y,
-        and out of frame for at least x per cent of it (vsc_guides_filter_microhomology)."""
+        and out of frame for at least x per cent of it (vsc_guides_filter_microhomology).
+        edit= an EditShape with site_len 23 or the name of a preset of EDITORS: the candidates' (mask, hits) rows (uint32[n, 2],
+        vsc_guides_edit) come last of all.  edit_targets= (contig, pos) rows in any order / min_editable= / max_editable= (all
+        need edit=): only the candidates whose site is defined, whose window holds min_editable .. max_editable editable
+        bases and - with targets - reaches a target (vsc_guides_filter_edit), on the device after the other floors."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, READ_LEN)
+        ed = self._edit_args(edit, edit_targets, min_editable, max_editable, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None:
+        if efficiency is None and mh is None and ed is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
             extra = self._scores_on_handle(held, efficiency, min_efficiency, mh, L.vsc_guides_count,
                                            (L.vsc_guides_efficiency, L.vsc_guides_filter_efficiency),
-                                           (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free)
+                                           (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free,
+                                           ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -2299,7 +2519,8 @@ class Genome:
 
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
                efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
-               pick=None, pick_by=None, pick_groups=None, **search_options):
+               pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
+               **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -2312,13 +2533,16 @@ class Genome:
         group of intervals), Genome.pick under a key made of what this call computed - pick_by= column names in priority
         order out of "mit" (the default; rint(100 x specificity), 14 bits), "eff" (the top 20 bits of order_bits of the
         predictor), "oof" (floor(1000 oof / sum), 10 bits) and "mh" (min(sum, 2^20 - 1), 20 bits); a column whose option was
-        not given is refused.  (picks, counts) come last of all.  Without pick= nothing changes."""
+        not given is refused.  (picks, counts) come last of all.  Without pick= nothing changes.
+        edit= / edit_targets= / min_editable= / max_editable=: as enumerate_guides; only the survivors are searched, and the
+        edit rows come after the microhomology pairs, before (picks, counts)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
                                       labels=labels, efficiency=efficiency, min_efficiency=min_efficiency,
                                       microhomology=microhomology, min_out_of_frame=min_out_of_frame,
-                                      min_microhomology=min_microhomology)
+                                      min_microhomology=min_microhomology, edit=edit, edit_targets=edit_targets,
+                                      min_editable=min_editable, max_editable=max_editable)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])

@@ -109,7 +109,11 @@
 // score of Bae et al. 2014 over FLANK bases on either side of the break in front of read position CUT, default 17): the -L
 // listing gains the last columns mhScore oofScore (%.17g; NA when the window leaves its sequence or holds an N).  -m
 // MIN_OOF[,MIN_MH] (needs -H) keeps only the candidates whose out-of-frame share is at least MIN_OOF per cent and whose score is
-// at least MIN_MH (vsc_guides_filter_microhomology), BEFORE the off-target search, as -y does.  Without -Y every
+// at least MIN_MH (vsc_guides_filter_microhomology), BEFORE the off-target search, as -y does.
+// -x CBE | ABE | START,LEN,BASE (needs -E, one device) looks at every found guide's BASE-EDITOR window (vsc_guides_edit): the -L
+// listing gains the last columns editWindow (the window's read letters) editable targetsHit.  -z targets.bed (one base per line)
+// and -l MIN,MAX (both need -x) keep only the candidates that reach a target base / hold MIN .. MAX editable bases
+// (vsc_guides_filter_edit), BEFORE the off-target search; -o pairs.tsv (needs -z) lists the pairs.  Without -Y every
 // output is what it was.
 // -k K[,SPACING] [-b COLS] [-c interval|name] (needs -E and -L, one device) picks the K best guides of every -E target, their cut
 // sites at least SPACING bases apart (vsc_guides_pick; tools/pick_host.hpp makes the key from mit, table, eff, oof, mh
@@ -126,6 +130,7 @@
 
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
+#include "edit_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
@@ -193,6 +198,12 @@ int main(int argc, char **argv)
         {'b', "pick-by", "With -k: what to rank by, comma-separated in priority order, out of mit (default), table (needs -W), eff (needs -Y), "
                          "oof, mh (need -H)", false},
         {'c', "pick-target", "With -k: interval (default; every -E interval is a target) or name (the -E intervals with one BED name are one target)", false},
+        {'x', "editor", "With -E: CBE | ABE | START,LEN,BASE: the base editor's window in read positions of the site and the base it converts; "
+                        "the guide listing gains the last columns editWindow editable targetsHit (one device)", false},
+        {'z', "edit-targets", "With -x: path to the target bases (.bed, one base per line): only the candidates whose window holds a target base "
+                              "that the editor converts are kept", false},
+        {'l', "editable", "With -x: MIN,MAX: keep only the candidates with MIN .. MAX editable bases in the window (0 .. 16)", false},
+        {'o', "edit-pairs", "With -z: path to the listing of the pairs: #chrom pos guideId at bystanders", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -567,6 +578,17 @@ int main(int argc, char **argv)
         }
     }
 
+    // -x / -z / -l / -o: the base-editor windows of the found guides
+    EditOptions edit;
+    {
+        const std::string why = parse_edit_options(opts[42].set, opts[42].value, opts[43].set, opts[43].value, opts[44].set, opts[44].value,
+                                                   opts[45].set, opts[45].value, discover, devices.size() != 1, (uint32_t)VSC_READ_LEN, &edit);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -702,6 +724,7 @@ int main(int argc, char **argv)
         std::vector<double> eff_linear;    // -Y: the found guides' predictors
         std::vector<uint32_t> mh_pairs;    // -H: their (sum, oof) pairs
         std::vector<std::string> bed_lines;  // -k: the -L lines wait for the search, whose rows the picks rank by
+        std::vector<std::string> edit_cols;  // -k with -x: the edit columns stay the last ones, behind the picks'
         if (discover) {
             st = multi ? vsc_multi_guides_enumerate(multi, mgenome, targets, &ep, &found) : vsc_guides_enumerate(ctx, genome, targets, &ep, &found);
             if (st != VSC_OK) throw std::runtime_error(multi ? vsc_multi_last_error(multi) : vsc_last_error(ctx));
@@ -720,6 +743,16 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_edit_target> edit_targets;
+            if (edit.with_targets) edit_targets = read_edit_targets(edit.targets_path, ix.names);
+            if (edit.filtered) {  // -z / -l: the same for the editor's FILTER
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_edit(ctx, genome, found, &edit.shape, edit_targets.empty() ? nullptr : edit_targets.data(), edit_targets.size(),
+                                           edit.min_editable, edit.max_editable, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -727,6 +760,14 @@ int main(int argc, char **argv)
             mh_pairs.resize(mh.on ? 2 * vsc_guides_count(found) : 0);
             if (mh.on && vsc_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<uint32_t> edit_rows;  // -x: the (mask, hits) rows, and with -o the pairs
+            std::vector<vsc_edit_pair> edit_pairs;
+            if (edit.on)
+                edit_rows_and_pairs(edit, vsc_guides_count(found), [&](uint32_t *r, vsc_edit_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_guides_edit(ctx, genome, found, &edit.shape, edit_targets.empty() ? nullptr : edit_targets.data(), edit_targets.size(), r, pp,
+                                        cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &edit_rows, &edit_pairs);
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -751,8 +792,9 @@ int main(int argc, char **argv)
                             "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
                             (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
-                    if (pick.on) bed_lines.push_back(line);
-                    else bed6 += line + '\n';
+                    const std::string ecol = edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "";
+                    if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
+                    else bed6 += line + ecol + '\n';
                 }
             }
             if (opts[20].set && !pick.on) {
@@ -762,6 +804,7 @@ int main(int argc, char **argv)
                 out.close();
                 if (!out) throw std::runtime_error("Could not write the -L file.");
             }
+            if (edit.with_pairs) write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');
@@ -941,7 +984,7 @@ int main(int argc, char **argv)
             const std::vector<std::string> marks = pick_text(pick, codes.size(), target_names, picks, counts);
             std::ofstream out(guides_bed_path);
             if (!out.is_open()) throw std::runtime_error("Could not open the -L path.");
-            for (size_t i = 0; i < bed_lines.size(); ++i) out << bed_lines[i] << marks[i] << '\n';
+            for (size_t i = 0; i < bed_lines.size(); ++i) out << bed_lines[i] << marks[i] << edit_cols[i] << '\n';
             out.close();
             if (!out) throw std::runtime_error("Could not write the -L file.");
         }

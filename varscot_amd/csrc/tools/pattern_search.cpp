@@ -38,6 +38,10 @@
 // listing gains the last columns mhScore oofScore (%.17g; NA when the window leaves its sequence or holds an N).  -m
 // MIN_OOF[,MIN_MH] (needs -H) keeps only the candidates whose out-of-frame share is at least MIN_OOF per cent and whose score
 // is at least MIN_MH, BEFORE the search.
+// -x START,LEN,BASE (needs -E; CBE | ABE for a pattern of 23 letters) looks at every found guide's BASE-EDITOR window
+// (vsc_pattern_guides_edit): the -E listing gains the last columns editWindow editable targetsHit.  -z targets.bed (one base per
+// line) and -l MIN,MAX (both need -x) keep only the candidates that reach a target base / hold MIN .. MAX editable bases, BEFORE
+// the search; -o pairs.tsv (needs -z) lists the pairs.
 // -W table.tsv scores every hit with a pattern TABLE (vsc_search_pattern_table; the CFD form for any nuclease: a product of
 // weights by protospacer position, guide base and site base times a weight for the site's letters at up to four PAM positions;
 // the file is what varscot_amd.PatternTable.to_tsv writes, tools/README.md: `shape L ps_start ps_len`, `pam_pos p...`,
@@ -62,6 +66,7 @@
 
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
+#include "edit_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
 
@@ -240,6 +245,12 @@ int main(int argc, char **argv)
         {'b', "pick-by", "With -k: what to rank by, comma-separated in priority order, out of table (needs -W, -M and -O), eff (needs -Y), oof, mh "
                          "(need -H); the default, mit, is guide_summary's: give -b", false},
         {'c', "pick-target", "With -k: interval (default; every -B interval is a target) or name (the -B intervals with one BED name are one target)", false},
+        {'x', "editor", "With -E: CBE | ABE | START,LEN,BASE: the base editor's window in read positions of the site and the base it converts; "
+                        "the -E listing gains the last columns editWindow editable targetsHit", false},
+        {'z', "edit-targets", "With -x: path to the target bases (.bed, one base per line): only the candidates whose window holds a target base "
+                              "that the editor converts are kept", false},
+        {'l', "editable", "With -x: MIN,MAX: keep only the candidates with MIN .. MAX editable bases in the window (0 .. 16)", false},
+        {'o', "edit-pairs", "With -z: path to the listing of the pairs: #chrom pos guideId at bystanders", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -443,6 +454,17 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // -x / -z / -l / -o: the base-editor windows of the found guides
+    EditOptions edit;
+    {
+        const std::string why = parse_edit_options(opts[30].set, opts[30].value, opts[31].set, opts[31].value, opts[32].set, opts[32].value,
+                                                   opts[33].set, opts[33].value, enumerate, opts[4].value.find(',') != std::string::npos,
+                                                   (uint32_t)pattern.size(), &edit);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     // -k / -b / -c: the best guides of every -B target
@@ -586,6 +608,7 @@ int main(int argc, char **argv)
         std::vector<double> eff_linear;       // -Y: the found guides' predictors
         std::vector<uint32_t> mh_pairs;       // -H: their (sum, oof) pairs
         std::vector<std::string> pick_lines;  // -k: the -E lines wait for the search, whose rows the picks may rank by
+        std::vector<std::string> edit_cols;   // -k with -x: the edit columns stay the last ones, behind the picks'
         std::vector<uint32_t> own_fixed;  // -E with -W: the table score of every found guide against its own site
         if (enumerate) {
             // an empty -B file is a target set that holds nothing: a pointer that is not NULL with n = 0
@@ -608,6 +631,16 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_edit_target> edit_targets;
+            if (edit.with_targets) edit_targets = read_edit_targets(edit.targets_path, ix.names);
+            if (edit.filtered) {  // -z / -l: the same for the editor's FILTER
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_edit(ctx, genome, found, &edit.shape, edit_targets.empty() ? nullptr : edit_targets.data(),
+                                                   edit_targets.size(), edit.min_editable, edit.max_editable, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -615,6 +648,14 @@ int main(int argc, char **argv)
             mh_pairs.resize(mh.on ? 2 * vsc_pattern_guides_count(found) : 0);
             if (mh.on && vsc_pattern_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<uint32_t> edit_rows;  // -x: the (mask, hits) rows, and with -o the pairs
+            std::vector<vsc_edit_pair> edit_pairs;
+            if (edit.on)
+                edit_rows_and_pairs(edit, vsc_pattern_guides_count(found), [&](uint32_t *r, vsc_edit_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_pattern_guides_edit(ctx, genome, found, &edit.shape, edit_targets.empty() ? nullptr : edit_targets.data(),
+                                                edit_targets.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &edit_rows, &edit_pairs);
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -623,7 +664,7 @@ int main(int argc, char **argv)
             std::ofstream out(opts[7].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
             out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
-                << (pick.on ? "\tpickTarget\tpickRank" : "") << '\n';
+                << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -642,8 +683,19 @@ int main(int argc, char **argv)
                 std::string line = guides[i].seq + '\t' + first_word(ix.names[loci[i].contig]) + '\t' + std::to_string(loci[i].pos) + '\t' + (loci[i].strand ? '-' : '+');
                 if (efficient) line += '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i]));
                 if (mh.on) line += mh_columns(&mh_pairs[2 * i]);
-                if (pick.on) pick_lines.push_back(line);
-                else out << line << '\n';
+                std::string ecol;
+                if (edit.on) {
+                    char own[VSC_PATTERN_MAX_LEN];
+                    if (vsc_pattern_guide_text(codes[i], len, ep.ps_start, ep.ps_len, 1, own) != VSC_OK) throw std::runtime_error("a code of the enumeration is no site");
+                    ecol = edit_columns(edit.shape, std::string(own, len), &edit_rows[2 * i]);
+                }
+                if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
+                else out << line << ecol << '\n';
+            }
+            if (edit.with_pairs) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }
@@ -697,7 +749,7 @@ int main(int argc, char **argv)
             const std::vector<std::string> marks = pick_text(pick, guides.size(), target_names, picks, counts);
             std::ofstream out(opts[7].value, std::ios::app);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
-            for (size_t i = 0; i < pick_lines.size(); ++i) out << pick_lines[i] << marks[i] << '\n';
+            for (size_t i = 0; i < pick_lines.size(); ++i) out << pick_lines[i] << marks[i] << edit_cols[i] << '\n';
             out.close();
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

@@ -13,6 +13,7 @@
 //   vsc_pattern_bulge.hip  bulges under a pattern
 //   vsc_efficiency.hip     on-target efficiency of candidates
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
+//   vsc_edit.hip           base-editor windows of candidates and their join with targets
 //   vsc_pick.hip           the best K candidates per target, with spacing
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
@@ -247,7 +248,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
                          &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
-                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
+                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
@@ -5044,6 +5045,328 @@ int vsc_pattern_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_
 {
     return pick_guides(ctx, genome, guides, regions, group, target, n_targets, key, params, false, picks, counts, rank, picked, stats,
                        "vsc_pattern_guides_pick");
+}
+
+}  // extern "C"
+
+// ---- base-editor windows and their join with targets (the definition: vsc_edit.h, the kernels: vsc_edit.hip) ----
+namespace {
+
+// The shape, the genome and the targets of an edit call, checked on the host; gpos = the targets' global positions.
+int edit_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_edit_shape *shape, const vsc_edit_target *targets, uint64_t n_t,
+               EditShape &s, std::vector<uint32_t> &gpos, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    s = EditShape{shape->site_len, shape->win_start, shape->win_len, shape->from};
+    if (shape->reserved[0] || shape->reserved[1] || shape->reserved[2] || shape->reserved[3] || !edit_shape_valid(s))
+        return fail_in(ctx, VSC_ERR_INVALID, who, "site_len 16 .. 32, 1 <= win_len <= 16, win_start + win_len <= site_len, from 0 .. 3, reserved fields 0");
+    if (n_t && !targets) return fail_in(ctx, VSC_ERR_INVALID, who, "targets are null with n_t > 0");
+    if (n_t > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE targets");
+    gpos.resize((size_t)n_t);
+    for (uint64_t k = 0; k < n_t; ++k) {
+        const vsc_edit_target &t = targets[k];
+        if (t.contig >= genome->n_contigs || t.contig >= genome->h_contig_off.size())
+            return fail_in(ctx, VSC_ERR_INVALID, who, "a target lies on an unknown contig");
+        const uint32_t off = genome->h_contig_off[t.contig], len = genome->h_contig_end[t.contig] - off;
+        if (t.pos >= len) return fail_in(ctx, VSC_ERR_INVALID, who, "a target lies beyond its contig");
+        if (k && !(targets[k - 1].contig < t.contig || (targets[k - 1].contig == t.contig && targets[k - 1].pos < t.pos)))
+            return fail_in(ctx, VSC_ERR_INVALID, who, "the targets are not strictly ascending by (contig, pos)");
+        gpos[k] = off + t.pos;
+    }
+    return VSC_OK;
+}
+
+// the targets' global positions at the front of edit_tabs; `more` bytes behind them (256-byte aligned) for the caller
+int edit_upload_targets(vsc_ctx *ctx, const std::vector<uint32_t> &gpos, size_t more, EditTargets &t, char **behind)
+{
+    const size_t t_bytes = round256(gpos.size() * sizeof(uint32_t) + 4);
+    VSC_HIP(ctx, ctx->edit_tabs.ensure(t_bytes + more));
+    if (!gpos.empty())
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->edit_tabs.p, gpos.data(), gpos.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    t = EditTargets{(const uint32_t *)ctx->edit_tabs.p, (uint32_t)gpos.size()};
+    if (behind) *behind = (char *)ctx->edit_tabs.p + t_bytes;
+    return VSC_OK;
+}
+
+// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): edit_rows_kernel,
+// then - with targets - the pairs' count pass over the rows, the scan, one 8-byte read-back (the pairs) and the write pass.
+int edit_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, const std::vector<uint32_t> &gpos, const void *d_loci,
+             const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+             vsc_edit_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_t = gpos.size();
+    if (stats) *stats = vsc_edit_stats{};
+    if (n_pairs) *n_pairs = 0;
+    if (coverage)
+        for (size_t k = 0; k < n_t; ++k) {
+            coverage[2 * k] = 0;
+            coverage[2 * k + 1] = kEditUndefined;
+        }
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
+    // edit_tabs: [targets][pairs per target][fewest bystanders per target][pairs per tile][offsets per tile]
+    const size_t cov_bytes = round256(n_t * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
+    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
+    EditArgs a{};
+    char *tabs = nullptr;
+    const int urc = edit_upload_targets(ctx, gpos, 2 * cov_bytes + count_bytes + off_bytes, a.targets, &tabs);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n = n;
+    const size_t head = 256;  // the counters, in front of the rows
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_edit_rows(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kEditCounts] = {};
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    EditPairArgs p{};
+    unsigned long long total = 0;
+    float pass_ms = 0;
+    if (n_t) {
+        p.shape = shape;
+        p.targets = a.targets;
+        p.contig_off = genome->d_contig_off;
+        p.loci = a.loci;
+        p.rows = a.out;
+        p.n = n;
+        p.n_work = tiles;
+        p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
+        unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
+        p.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_edit_pairs(p, false, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (n_t) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+    if (n_pairs) *n_pairs = total;
+    const bool too_many = total > kEditMaxCount, write = pairs && total && total <= capacity && !too_many, cover = total && (coverage || stats);
+    uint64_t covered = 0;
+    if (write || cover) {
+        if (write) {
+            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_edit_pair)));
+            p.pairs = (uint4 *)ctx->edit_pairs.p;
+        }
+        if (cover) {
+            p.cov_count = (uint32_t *)tabs;
+            p.cov_min = (uint32_t *)(tabs + cov_bytes);
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_t * sizeof(uint32_t), ctx->stream));
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_t * sizeof(uint32_t), ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_edit_pairs(p, true, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        std::vector<uint32_t> cov;
+        unsigned long long d_covered = 0;
+        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_edit_pair), hipMemcpyDeviceToHost, ctx->stream));
+        if (cover && !coverage) {  // the stats alone: the covered targets are counted where they lie, 8 bytes come back
+            unsigned long long *slot = a.stats + kEditCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
+            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_t, slot, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (cover) {
+            cov.resize(2 * n_t);
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_t * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_t, p.cov_min, n_t * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float wms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        pass_ms += wms;
+        covered = d_covered;
+        for (size_t k = 0; coverage && k < n_t; ++k) {
+            covered += cov[k] != 0;
+            coverage[2 * k] = cov[k];
+            coverage[2 * k + 1] = cov[n_t + k];
+        }
+    }
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+        stats->with_hit = seen[kEffClasses];
+        stats->pairs = total;
+        stats->targets_covered = covered;
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    t.score_ms = ms;
+    t.scan_ms = pass_ms;
+    t.total_ms = t.score_ms + t.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
+    ctx->timing = t;
+    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
+    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
+    return VSC_OK;
+}
+
+// vsc_guides_edit / vsc_pattern_guides_edit: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int edit_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_edit_shape *shape, const vsc_edit_target *targets, uint64_t n_t,
+                bool need_23, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+                vsc_edit_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    EditShape s{};
+    std::vector<uint32_t> gpos;
+    const int rc = edit_check(ctx, genome, shape, targets, n_t, s, gpos, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (guides->n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const bool dev = guides->ctx != nullptr;
+    return edit_run(ctx, genome, s, gpos, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
+                    guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_edit / vsc_pattern_guides_filter_edit: run_enumeration's two passes over tiles of kEditTile candidates of `in`
+// (a host-only object: uploaded first); its timing is then restated as the microhomology filter restates its own.
+template <class Guides>
+int edit_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_edit_shape *shape, const vsc_edit_target *targets, uint64_t n_t,
+                bool need_23, uint32_t min_editable, uint32_t max_editable, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    EditShape s{};
+    std::vector<uint32_t> gpos;
+    const int rc = edit_check(ctx, genome, shape, targets, n_t, s, gpos, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (min_editable > max_editable) return fail_in(ctx, VSC_ERR_INVALID, who, "min_editable is more than max_editable");
+    const uint64_t n = in->n;
+    if (n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EditFilterArgs a{};
+    const int urc = edit_upload_targets(ctx, gpos, 0, a.targets, nullptr);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.n = n;
+    a.min_editable = min_editable;
+    a.max_editable = max_editable;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    if (n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (gpos is this call's vector)
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_edit_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_edit_site_text(const char *site, const vsc_edit_shape *shape, uint32_t *mask)
+{
+    if (!site || !shape || !mask) return VSC_ERR_INVALID;
+    const EditShape s{shape->site_len, shape->win_start, shape->win_len, shape->from};
+    if (shape->reserved[0] || shape->reserved[1] || shape->reserved[2] || shape->reserved[3] || !edit_shape_valid(s)) return VSC_ERR_INVALID;
+    if (strnlen(site, s.site_len + 1) != s.site_len) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    for (uint32_t j = 0; j < s.site_len; ++j) {
+        const int b = base_code(site[j]);
+        if (b > 3) return VSC_ERR_INVALID;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+    }
+    *mask = edit_mask(ch, cl, s);
+    return VSC_OK;
+}
+
+int vsc_loci_edit(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_edit_shape *shape,
+                  const vsc_edit_target *targets, uint64_t n_t, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                  uint32_t *coverage, vsc_edit_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_edit";
+    EditShape s{};
+    std::vector<uint32_t> gpos;
+    const int rc = edit_check(ctx, genome, shape, targets, n_t, s, gpos, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return edit_run(ctx, genome, s, gpos, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_edit_shape *shape, const vsc_edit_target *targets,
+                    uint64_t n_t, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+                    vsc_edit_stats *stats)
+{
+    return edit_guides(ctx, genome, guides, shape, targets, n_t, true, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_guides_edit");
+}
+
+int vsc_pattern_guides_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_edit_shape *shape,
+                            const vsc_edit_target *targets, uint64_t n_t, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity,
+                            uint64_t *n_pairs, uint32_t *coverage, vsc_edit_stats *stats)
+{
+    return edit_guides(ctx, genome, guides, shape, targets, n_t, false, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_pattern_guides_edit");
+}
+
+int vsc_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_edit_shape *shape, const vsc_edit_target *targets,
+                           uint64_t n_t, uint32_t min_editable, uint32_t max_editable, vsc_guides **out)
+{
+    return edit_filter(ctx, genome, in, shape, targets, n_t, true, min_editable, max_editable, out, "vsc_guides_filter_edit");
+}
+
+int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_edit_shape *shape,
+                                   const vsc_edit_target *targets, uint64_t n_t, uint32_t min_editable, uint32_t max_editable,
+                                   vsc_pattern_guides **out)
+{
+    return edit_filter(ctx, genome, in, shape, targets, n_t, false, min_editable, max_editable, out, "vsc_pattern_guides_filter_edit");
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "varscot_hip.h"
 #include "vsc_efficiency.h"
 #include "vsc_mh.h"
+#include "vsc_edit.h"
 
 namespace vsc {
 
@@ -596,6 +597,52 @@ struct MhFilterArgs {
 };
 hipError_t launch_mh_score(const MhArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_mh_filter(const MhFilterArgs &args, bool write, hipStream_t stream);
+// vsc_edit.hip (the definition: vsc_edit.h)
+constexpr uint32_t kEditCounts = kEffClasses + 1;  // the classes, then the candidates with a hit
+struct EditArgs {
+    EffPlanes g;
+    EditShape shape;
+    EditTargets targets;          // n == 0: no targets, hits = 0
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: (mask, hits), kEditUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kEditCounts], zeroed before the launch: the kernel adds its candidates per class
+};
+// the pairs' and the filter's two passes: tile i = candidates [i * kEditTile, ..)
+constexpr uint32_t kEditTile = 1024;
+struct EditPairArgs {
+    EditShape shape;
+    EditTargets targets;
+    const uint32_t *contig_off;
+    const uint4 *loci;            // [n]
+    const uint2 *rows;            // [n] what edit_rows_kernel left
+    unsigned long long n;
+    uint32_t n_work;              // tiles
+    uint32_t *tile_count;         // count pass out: pairs per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    uint4 *pairs;                 // write pass out (null: coverage only)
+    uint32_t *cov_count, *cov_min;  // [targets.n] each, write pass: pairs and fewest bystanders per target, 0 / 0xFFFFFFFF before the launch; null: none
+};
+struct EditFilterArgs {
+    EffPlanes g;
+    EditShape shape;
+    EditTargets targets;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    uint32_t min_editable, max_editable;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_edit_rows(const EditArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_edit_pairs(const EditPairArgs &args, bool write, hipStream_t stream);
+hipError_t launch_edit_filter(const EditFilterArgs &args, bool write, hipStream_t stream);
+// *out (zeroed) += the entries of cov_count that are not 0
+hipError_t launch_edit_covered(const uint32_t *cov_count, uint32_t n_t, unsigned long long *out, int n_cus, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

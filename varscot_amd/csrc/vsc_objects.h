@@ -137,6 +137,9 @@ struct vsc_ctx {
     // them from the host), the call's tables (targets per candidate, per-target counts, segment offsets, cursors, stats, picks,
     // counts, ranks) and the records of the eligible candidates in their targets' segments
     vsc::DeviceBuf pick_in, pick_tabs, pick_recs;
+    // vsc_*_edit: the call's tables (the targets' global positions, the coverage counters, the pairs' per-tile
+    // counts and offsets) and its pairs; the candidates a call brings from the host and the rows lie in eff_in / eff_out
+    vsc::DeviceBuf edit_tabs, edit_pairs;
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
