@@ -2086,8 +2086,9 @@ int vsc_pattern_guides_pick(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_
  * not strictly ascending, on an unknown contig, or beyond their contig; min_editable > max_editable; n_t > 0 with NULL targets.
  * VSC_ERR_RANGE: n or n_t above 0xFFFFFFFE.  Uploads and results use context scratch; vsc_ctx_release_scratch gives it back.
  *
- * Not offered: a vsc_multi_* entry; editing-efficiency or outcome models that need trained weights; codon consequences;
+ * Not offered: a vsc_multi_* entry; editing-efficiency or outcome models that need trained weights;
  * sequence-context preferences of the deaminase beyond `from`; more than one window per call (call twice).
+ * Codon and amino-acid consequences are the next section's.
  */
 #define VSC_EDIT_UNDEFINED 0xFFFFFFFFu
 typedef struct {
@@ -2131,6 +2132,157 @@ int vsc_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *i
 int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_edit_shape *shape,
                                    const vsc_edit_target *targets, uint64_t n_t, uint32_t min_editable, uint32_t max_editable,
                                    vsc_pattern_guides **out);
+
+/* ---- coding consequences of base edits: codons, amino acids, stop gains -------------------------- */
+/*
+ * What a base editor does to the proteins: for every candidate, the codons its window converts and what becomes of them -
+ * "which guides make a stop (CRISPR-STOP / iSTOP), in which transcript, how early", "which guides fix a base while every
+ * bystander stays synonymous" - answered on the resident genome against a CDS annotation, where the candidates lie.
+ *
+ * CODE      64 amino-acid letters indexed 16 b0 + 4 b1 + b2 (A C G T = 0 .. 3), '*' = stop. NULL = the standard code:
+ *           KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF
+ * SEGMENT   { contig, start, end, transcript, strand (0 '+', 1 '-'), phase (0 .. 2, GFF column 8) }, forward genome, half-open,
+ *           non-empty, inside its contig. Segments are STRICTLY ascending by (contig, start) and do not overlap
+ *           (end_i <= start_i+1 on one contig) - one transcript set per call. A caller with overlapping isoforms calls once per set.
+ *           transcript < n_tx (dense indices into the caller's own table). All segments of a transcript lie on one contig and one
+ *           strand. Their order in the transcript is ascending start on '+' and descending start on '-'.
+ *           n <= 0xFFFFFFFE, a transcript's coding length < 2^31.
+ * CODING    the host derives, per segment: bases_before = the transcript's bases in earlier segments (transcript order).
+ *           shift = (3 - phase of the transcript's FIRST segment) % 3.
+ *           The coding index of forward position x:
+ *             '+': ci = shift + bases_before + (x - start)      '-': ci = shift + bases_before + (end - 1 - x).
+ *           codon = ci / 3, frame = ci % 3. The phase of every later segment must equal (3 - (shift + bases_before) % 3) % 3,
+ *           otherwise VSC_ERR_INVALID naming the segment.
+ *           The host also derives the previous / next segment in transcript order.
+ * CODON     of a coding base: the three bases with coding indices 3 codon .. 3 codon + 2 of its transcript, in transcript
+ *           orientation (complemented on '-'). They are found by walking to the previous / next segment (at most two hops a side:
+ *           segments of one base exist).
+ *           A codon is UNKNOWN when one of its indices lies in front of the transcript's first coding base or behind its last one,
+ *           or when one of its bases is N or not resident.
+ * PARAMS    the vsc_edit_shape of 4.28, and `to` 0 .. 3, to != from: the base the editor writes on the read strand
+ *           (CBE: T, ABE: G). OUTCOME: every base of MASK is converted (full conversion, the iSTOP assumption).
+ *           In transcript orientation a converted base goes from -> to when the candidate's strand equals the transcript's,
+ *           comp(from) -> comp(to) otherwise.
+ * EFFECT    one per (candidate, transcript, codon) with at least one MASK base in it:
+ *           ref = the codon, alt = the codon with ALL MASK bases of the window that fall in it converted. Class, tested in this order:
+ *             5 unknown       the codon is UNKNOWN (ref = alt = 0)
+ *             4 start_lost    codon == 0 and the transcript's first phase is 0
+ *                             (any change of the first codon. Alternative starts are not modelled.)
+ *             2 stop_gained   CODE[ref] != '*' and CODE[alt] == '*'
+ *             3 stop_lost     CODE[ref] == '*' and CODE[alt] != '*'
+ *             0 synonymous    CODE[ref] == CODE[alt]
+ *             1 missense      otherwise
+ *           16 bytes: { candidate, transcript, codon, info }, info = ref | alt << 6 | class << 12 | (edited bases in the codon) << 16
+ *           | at << 20, at = the smallest window position j among them.
+ *           Order: ascending candidate. Inside a candidate, ascending forward position of the codon's lowest-forward edited base.
+ *           That base emits the effect: it is an emitter iff no other base of its codon with a lower forward position is a MASK base
+ *           of the window. n <= 0xFFFFFFFE.
+ * ROW       two uint32 per candidate. word 0 = the candidate's effects by class, 5 bits each: class k in bits [5 k, 5 k + 5).
+ *           word 1 = bit j set iff MASK bit j is set and that base lies in a segment.
+ *           Both are 0xFFFFFFFF unless the candidate's CLASS (4.28) is defined.
+ * COVERAGE  optional, two uint32 per transcript: its stop_gained effects, and the smallest codon index among them (0xFFFFFFFF: none).
+ * FILTER    keep iff the class is defined, (require == 0 or some effect's class bit is in require), and no effect's class bit is in
+ *           forbid. require / forbid are masks over bits 0 .. 5. Survivors keep their input order.
+ *
+ * The output is a function of the inputs alone: it does not depend on launch shape or wave order.  The coverage counters use
+ * integer add / min atomics, which commute; nothing else depends on an atomic's order, and the records have no append cursor.
+ * In an UNKNOWN codon the edited bases and `at` are counted over the bases the transcript has.
+ *
+ * vsc_cds_build (host only): `contigs` is the genome's table (vsc_layout_contigs makes it, as for vsc_regions_build); every rule of SEGMENT
+ * and CODING is checked, a reserved field must be 0.  VSC_ERR_INVALID when a rule is broken - vsc_cds_build_error() then names
+ * the rule and the segment's index (a text of the calling thread, valid until its next vsc_cds_build) - VSC_ERR_RANGE when n is
+ * above 0xFFFFFFFE, a transcript's coding length reaches 2^31 or the contigs end beyond 2^32.  n == 0 is a valid, empty set.
+ * vsc_cds_info: the segments, n_tx, the transcripts that have a segment and the coding bases.  The object is immutable and
+ * belongs to no context; every context that uses it keeps a device copy while it is the last one it used.
+ *
+ * vsc_codon_effect (host only): the class of one effect by the function the kernels call - ref, alt 0 .. 63, first_phase
+ * 0 .. 2, code as CODE (NULL: standard).  It applies the rules from start_lost on as they are written, also to ref == alt;
+ * unknown cannot come out.  vsc_effects_site_text (host only): ROW and EFFECTS of the one site at (contig, pos, strand) from
+ * letters: texts[c] holds the letters of contig c (any case, a letter other than ACGT is an N), as many as the contig table
+ * the CDS was built with says.  row[0], row[1] = the ROW (0xFFFFFFFF twice where the site's class is not defined: the locus
+ * is invalid or the site holds an N); effects (room for 16, candidate = 0) and *n_effects = the EFFECTS.  The same inline
+ * functions, on planes packed from the letters on every call: a definition to test against, not a fast path.
+ *
+ * vsc_loci_effects: loci are host entries in any order, duplicates allowed.  rows (optional): rows[2 i], rows[2 i + 1] = the ROW
+ * of loci[i].  The records follow vsc_loci_edit's pair contract: *n_effects (optional) is always the full count; effects == NULL
+ * only counts; a count above `capacity` is VSC_ERR_RANGE, and then nothing is written to `effects`, while rows, coverage,
+ * stats and *n_effects are valid.  coverage (optional): 2 n_tx entries.  stats (optional): the candidates by class (the five
+ * counts add up to n), the candidates with an effect, the effects and the effects by class, the transcripts with a stop_gained
+ * effect, the rows kernel's time and the call's wall time in milliseconds.  n == 0: VSC_OK, nothing is launched, the coverage
+ * says "none".  vsc_guides_effects works over the candidates where they lie on the device and requires site_len == 23;
+ * vsc_pattern_guides_effects is the same for vsc_pattern_guides: site_len is the pattern's length, which the CALLER vouches for.
+ * vsc_guides_filter_effects / vsc_pattern_guides_filter_effects: *out = the candidates of `in` that pass FILTER, codes and loci
+ * copied unchanged in the input's order, as vsc_guides_filter_edit.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a shape outside SHAPE or
+ * with a non-zero reserved field; to > 3 or to == from; NULL arguments; a genome or object of another context; a CDS built with
+ * another contig table than the genome's; a code with fewer than 64 letters; site_len != 23 for vsc_guides; require or forbid
+ * with a bit above 5.  VSC_ERR_RANGE: n above 0xFFFFFFFE.  Uploads and results use context scratch;
+ * vsc_ctx_release_scratch gives it back, the device copy of the CDS included.
+ *
+ * Not offered: overlapping isoforms in one call (call once per transcript set); splice-site disruption (pass the GT / AG
+ * positions as targets of vsc_*_edit); partial-conversion outcomes; non-standard start codons; a vsc_multi_* entry.
+ */
+#define VSC_EFFECTS_UNDEFINED 0xFFFFFFFFu
+#define VSC_EFFECT_SYNONYMOUS 0u
+#define VSC_EFFECT_MISSENSE 1u
+#define VSC_EFFECT_STOP_GAINED 2u
+#define VSC_EFFECT_STOP_LOST 3u
+#define VSC_EFFECT_START_LOST 4u
+#define VSC_EFFECT_UNKNOWN 5u
+#define VSC_EFFECT_CLASSES 6u
+typedef struct {
+    uint32_t contig, start, end, transcript;
+    uint32_t strand; /* 0 '+', 1 '-' */
+    uint32_t phase;  /* 0 .. 2 */
+    uint32_t reserved[2]; /* 0 */
+} vsc_cds_segment;
+typedef struct vsc_cds vsc_cds;
+typedef struct {
+    uint64_t segments, transcripts, transcripts_used, coding_bases;
+    uint64_t reserved[4]; /* 0 */
+} vsc_cds_stats;
+typedef struct {
+    uint32_t candidate, transcript, codon;
+    uint32_t info; /* ref | alt << 6 | class << 12 | edited << 16 | at << 20 */
+} vsc_effect;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t with_effect, effects, transcripts_stopped;
+    uint64_t by_class[6]; /* VSC_EFFECT_* */
+    double kernel_ms, wall_ms;
+} vsc_effects_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_cds_segment) == 32 && sizeof(vsc_cds_stats) == 64 && sizeof(vsc_effect) == 16 && sizeof(vsc_effects_stats) == 128,
+              "vsc_effects layout");
+#else
+_Static_assert(sizeof(vsc_cds_segment) == 32 && sizeof(vsc_cds_stats) == 64 && sizeof(vsc_effect) == 16 && sizeof(vsc_effects_stats) == 128,
+               "vsc_effects layout");
+#endif
+int vsc_cds_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_cds_segment *segments, uint64_t n, uint32_t n_tx, vsc_cds **out);
+const char *vsc_cds_build_error(void);
+void vsc_cds_free(vsc_cds *cds);
+int vsc_cds_info(const vsc_cds *cds, vsc_cds_stats *out);
+int vsc_codon_effect(uint32_t ref, uint32_t alt, uint32_t codon, uint32_t first_phase, const char *code /* 64 letters, or NULL */,
+                     uint32_t *effect_class);
+int vsc_effects_site_text(const vsc_cds *cds, const char *const *texts /* one per contig */, uint32_t contig, uint32_t pos, uint32_t strand,
+                          const vsc_edit_shape *shape, uint32_t to, const char *code, uint32_t *row /* 2 */, vsc_effect *effects /* 16 */,
+                          uint32_t *n_effects);
+int vsc_loci_effects(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                     const vsc_edit_shape *shape, uint32_t to, const vsc_cds *cds, const char *code, uint32_t *rows /* host, 2 n, optional */,
+                     vsc_effect *effects /* host, optional */, uint64_t capacity, uint64_t *n_effects /* optional */,
+                     uint32_t *coverage /* host, 2 n_tx, optional */, vsc_effects_stats *stats /* optional */);
+int vsc_guides_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_edit_shape *shape, uint32_t to,
+                       const vsc_cds *cds, const char *code, uint32_t *rows, vsc_effect *effects, uint64_t capacity, uint64_t *n_effects,
+                       uint32_t *coverage, vsc_effects_stats *stats);
+int vsc_pattern_guides_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_edit_shape *shape, uint32_t to,
+                               const vsc_cds *cds, const char *code, uint32_t *rows, vsc_effect *effects, uint64_t capacity,
+                               uint64_t *n_effects, uint32_t *coverage, vsc_effects_stats *stats);
+int vsc_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_edit_shape *shape, uint32_t to,
+                              const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid, vsc_guides **out);
+int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_edit_shape *shape,
+                                      uint32_t to, const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid,
+                                      vsc_pattern_guides **out);
 
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*

@@ -374,6 +374,40 @@ class EditStats(C.Structure):
 assert C.sizeof(EditShapeStruct) == 32 and C.sizeof(EditStats) == 96 and EDIT_PAIR_DTYPE.itemsize == 16 and EDIT_TARGET_DTYPE.itemsize == 8
 
 
+EFFECTS_UNDEFINED = 0xFFFFFFFF  # VSC_EFFECTS_UNDEFINED
+EFFECT_CLASS_NAMES = ("synonymous", "missense", "stop_gained", "stop_lost", "start_lost", "unknown")  # VSC_EFFECT_*
+CDS_SEGMENT_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("transcript", "<u4"), ("strand", "<u4"),
+                              ("phase", "<u4"), ("reserved", "<u4", (2,))])
+EFFECT_DTYPE = np.dtype([("candidate", "<u4"), ("transcript", "<u4"), ("codon", "<u4"), ("info", "<u4")])
+
+
+class CdsStats(C.Structure):
+    """vsc_cds_stats: the segments, n_tx, the transcripts that have a segment and the coding bases of a CDS object."""
+    _fields_ = [("segments", C.c_uint64), ("transcripts", C.c_uint64), ("transcripts_used", C.c_uint64), ("coding_bases", C.c_uint64),
+                ("reserved", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in ("segments", "transcripts", "transcripts_used", "coding_bases")}
+
+
+class EffectsStats(C.Structure):
+    """vsc_effects_stats: the candidates of a call by class (the five counts add up to n), the candidates with an effect, the
+    effects, the transcripts with a stop_gained effect, the effects by class, the rows kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("with_effect", C.c_uint64), ("effects", C.c_uint64), ("transcripts_stopped", C.c_uint64),
+                ("by_class", C.c_uint64 * 6), ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n", "with_effect", "effects",
+                                                "transcripts_stopped")}
+        d["by_class"] = {name: int(self.by_class[k]) for k, name in enumerate(EFFECT_CLASS_NAMES)}
+        d.update(kernel_ms=float(self.kernel_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(CdsStats) == 64 and C.sizeof(EffectsStats) == 128 and CDS_SEGMENT_DTYPE.itemsize == 32 and EFFECT_DTYPE.itemsize == 16
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -609,6 +643,23 @@ SYMBOLS = [
                                          C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_edit", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), _vp, C.c_uint64, C.c_uint32, C.c_uint32,
                                                  C.POINTER(_vp)]),
+    ("vsc_cds_build", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_cds_build_error", C.c_char_p, []),
+    ("vsc_cds_free", None, [_vp]),
+    ("vsc_cds_info", C.c_int, [_vp, C.POINTER(CdsStats)]),
+    ("vsc_codon_effect", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.POINTER(C.c_uint32)]),
+    ("vsc_effects_site_text", C.c_int, [_vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(EditShapeStruct),
+                                        C.c_uint32, C.c_char_p, _vp, _vp, C.POINTER(C.c_uint32)]),
+    ("vsc_loci_effects", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, _vp, _vp,
+                                   C.c_uint64, C.POINTER(C.c_uint64), _vp, C.POINTER(EffectsStats)]),
+    ("vsc_guides_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, _vp, _vp, C.c_uint64,
+                                     C.POINTER(C.c_uint64), _vp, C.POINTER(EffectsStats)]),
+    ("vsc_pattern_guides_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, _vp, _vp,
+                                             C.c_uint64, C.POINTER(C.c_uint64), _vp, C.POINTER(EffectsStats)]),
+    ("vsc_guides_filter_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, C.c_uint32,
+                                            C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, C.c_uint32,
+                                                    C.c_uint32, C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)

@@ -1177,6 +1177,182 @@ def edit_pick_inputs(pairs, loci, extra_columns=()):
     return lo[cand], pr["target"].astype(np.uint32), pick_key(cols, bits)
 
 
+# ---- coding consequences of base edits --------------------------------------------------------------------
+# CODE: 64 amino-acid letters indexed 16 b0 + 4 b1 + b2 (A C G T = 0 .. 3), '*' = stop - the standard genetic code
+GENETIC_CODE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
+EFFECT_DTYPE = _lib.EFFECT_DTYPE
+EFFECT_CLASSES = _lib.EFFECT_CLASS_NAMES  # the name of class k; the bit of a require / forbid mask
+EFFECTS_UNDEFINED = _lib.EFFECTS_UNDEFINED  # both words of the row of a candidate whose site is undefined
+# the base the presets of EDITORS write on the read strand
+EDITOR_TO = {"CBE": "T", "ABE": "G"}
+
+
+def _effect_to(shape, to):
+    """`to` as 0..3: a letter, a number, or None - the transition partner of the shape's base (C <-> T, A <-> G)."""
+    if to is None:
+        return (shape.base + 2) % 4
+    if isinstance(to, (str, bytes)):
+        t = to.decode() if isinstance(to, bytes) else to
+        if len(t) != 1 or t.upper() not in "ACGT":
+            raise ValueError("an editor writes one of A, C, G, T")
+        return "ACGT".index(t.upper())
+    return int(to)
+
+
+def _effect_code(code):
+    """CODE as the library takes it: None (the standard code) or 64 letters."""
+    if code is None:
+        return None
+    b = code if isinstance(code, bytes) else code.encode()
+    if len(b) != 64:
+        raise ValueError("a genetic code has 64 letters")
+    return b
+
+
+def effect_class_mask(classes):
+    """The require / forbid mask of class names (EFFECT_CLASSES), one name or several; None: 0; a number passes as it is."""
+    if classes is None:
+        return 0
+    if isinstance(classes, (int, np.integer)):
+        return int(classes)
+    if isinstance(classes, str):
+        classes = [c for c in classes.split("+") if c]
+    m = 0
+    for c in classes:
+        if c not in EFFECT_CLASSES:
+            raise ValueError("an effect class is one of %s" % ", ".join(EFFECT_CLASSES))
+        m |= 1 << EFFECT_CLASSES.index(c)
+    return m
+
+
+class Cds:
+    """A CDS annotation to walk base edits against (vsc_cds): `segments` = (contig, start, end, transcript, strand, phase)
+    rows - 0-based, half-open, on the forward genome; strand 0 / "+" or 1 / "-"; phase 0..2 as in GFF column 8 - or a
+    CDS_SEGMENT_DTYPE array.  One transcript set: no two segments overlap.  sort=True (the default) orders the rows by
+    (contig, start) first; the library refuses anything else that breaks SEGMENT / CODING of include/varscot_hip.h, and
+    VarscotError then names the rule and the segment (its index after sorting).  n_tx defaults to the largest transcript +
+    1.  Host-side and immutable, as Regions; every context that uses it keeps a device copy while it is the last one it used."""
+
+    def __init__(self, packed_genome, segments, n_tx=None, sort=True):
+        if isinstance(segments, np.ndarray) and segments.dtype == _lib.CDS_SEGMENT_DTYPE:
+            sg = np.ascontiguousarray(segments).copy()
+        else:
+            rows = [tuple(r) for r in segments]
+            sg = np.zeros(len(rows), dtype=_lib.CDS_SEGMENT_DTYPE)
+            for i, r in enumerate(rows):
+                if len(r) != 6:
+                    raise ValueError("a segment is (contig, start, end, transcript, strand, phase)")
+                strand = {"+": 0, "-": 1}.get(r[4], r[4])
+                vals = [int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(strand), int(r[5])]
+                if min(vals) < 0 or max(vals) >= 2 ** 32:
+                    raise ValueError("segment fields must fit 32 unsigned bits")
+                sg[i] = (vals[0], vals[1], vals[2], vals[3], vals[4], vals[5], (0, 0))
+        if sort and len(sg):
+            sg = sg[np.lexsort((sg["start"], sg["contig"]))]
+        self.segments = sg
+        self.n_tx = int(n_tx) if n_tx is not None else (int(sg["transcript"].max()) + 1 if len(sg) else 0)
+        contigs = np.ascontiguousarray(packed_genome.contigs, dtype=CONTIG_DTYPE)
+        self._h = C.c_void_p()
+        L = lib()
+        rc = L.vsc_cds_build(ptr(contigs), len(contigs), ptr(sg) if len(sg) else None, len(sg), self.n_tx, C.byref(self._h))
+        if rc != 0:
+            raise _lib.VarscotError(rc, (L.vsc_cds_build_error() or b"").decode())
+
+    def info(self):
+        """vsc_cds_info: segments, transcripts (n_tx), transcripts_used and coding_bases."""
+        st = _lib.CdsStats()
+        check(lib().vsc_cds_info(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def close(self):
+        if self._h:
+            lib().vsc_cds_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def codon_effect(ref, alt, codon, first_phase, code=None):
+    """vsc_codon_effect: the class (0..5, EFFECT_CLASSES) of one effect by the function the kernels call.  ref, alt: codons as
+    16 b0 + 4 b1 + b2 or three letters; codon: its index in the transcript; first_phase: the phase of the transcript's first
+    segment."""
+    def num(c):
+        if isinstance(c, str):
+            return 16 * "ACGT".index(c[0]) + 4 * "ACGT".index(c[1]) + "ACGT".index(c[2])
+        return int(c)
+    out = C.c_uint32()
+    check(lib().vsc_codon_effect(num(ref), num(alt), int(codon), int(first_phase), _effect_code(code), C.byref(out)))
+    return int(out.value)
+
+
+def effects_site_text(cds, texts, contig, pos, strand, shape, to=None, code=None):
+    """vsc_effects_site_text: (row uint32[2], effects EFFECT_DTYPE[..]) of the one site at (contig, pos, strand) from letters,
+    on the host, by the functions the kernels call.  texts: the letters of every contig of the genome the Cds was built for."""
+    if isinstance(shape, str):
+        to = EDITOR_TO[shape] if to is None else to
+        shape = EDITORS[shape]
+    raw = [t if isinstance(t, bytes) else t.encode() for t in texts]
+    arr = (C.c_char_p * max(len(raw), 1))(*raw)
+    row = np.zeros(2, dtype=np.uint32)
+    eff = np.zeros(16, dtype=_lib.EFFECT_DTYPE)
+    n = C.c_uint32()
+    sh = shape._struct()
+    check(lib().vsc_effects_site_text(cds._h, arr, int(contig), int(pos), int(strand), C.byref(sh), _effect_to(shape, to), _effect_code(code),
+                                      ptr(row), ptr(eff), C.byref(n)))
+    return row, eff[:int(n.value)].copy()
+
+
+def unpack_effect_info(info):
+    """(ref, alt, class, edited, at) of an effect's info word (or an array of them): the codon before and after as
+    16 b0 + 4 b1 + b2, the class (EFFECT_CLASSES), the edited bases in the codon and the smallest window position among them."""
+    i = np.asarray(info, dtype=np.uint32)
+    return (i & np.uint32(63), (i >> np.uint32(6)) & np.uint32(63), (i >> np.uint32(12)) & np.uint32(7),
+            (i >> np.uint32(16)) & np.uint32(15), (i >> np.uint32(20)) & np.uint32(15))
+
+
+def unpack_effect_row(rows):
+    """(counts uint32[n, 6], coding uint32[n]) of effect rows uint32[n, 2]: the candidate's effects by class, and the bits
+    of its MASK that lie in a segment.  An undefined row gives zeros."""
+    r = np.asarray(rows, dtype=np.uint32).reshape(-1, 2)
+    undefined = (r[:, 0] == EFFECTS_UNDEFINED) & (r[:, 1] == EFFECTS_UNDEFINED)
+    counts = np.stack([(r[:, 0] >> np.uint32(5 * k)) & np.uint32(31) for k in range(6)], axis=1).astype(np.uint32)
+    counts[undefined] = 0
+    return counts, np.where(undefined, np.uint32(0), r[:, 1]).astype(np.uint32)
+
+
+def codon_text(codon):
+    """The three letters of a codon number 16 b0 + 4 b1 + b2."""
+    c = int(codon)
+    return "ACGT"[c >> 4 & 3] + "ACGT"[c >> 2 & 3] + "ACGT"[c & 3]
+
+
+def effects_pick_inputs(effects, loci, classes=("stop_gained",), extra_columns=()):
+    """What Genome.pick takes for "of every transcript the K guides whose effect of `classes` comes earliest in the protein":
+    (loci[effects.candidate], effects.transcript, key) over the effects of those classes - one pick candidate per effect, its
+    target the effect's transcript, its key made with pick_key so that an earlier codon is better: the first column is
+    2^31 - 1 - codon (31 bits).  extra_columns: (values per CANDIDATE of the effects call, bits) in priority order behind it
+    - unsigned integer arrays, larger is better (pick_column makes them)."""
+    ef = np.asarray(effects, dtype=_lib.EFFECT_DTYPE)
+    want = effect_class_mask(classes)
+    cls = (ef["info"] >> np.uint32(12)) & np.uint32(7)
+    ef = ef[((np.uint32(1) << cls) & np.uint32(want)) != 0]
+    lo = _loci(loci, len(loci))
+    cand = ef["candidate"].astype(np.int64)
+    cols = [np.uint64(2 ** 31 - 1) - ef["codon"].astype(np.uint64)]
+    bits = [31]
+    for values, b in extra_columns:
+        v = np.asarray(values)
+        if v.dtype.kind != "u" or v.ndim != 1 or len(v) != len(lo):
+            raise ValueError("an extra column is a one-dimensional unsigned integer array with one value per candidate")
+        cols.append(v[cand])
+        bits.append(int(b))
+    return lo[cand], ef["transcript"].astype(np.uint32), pick_key(cols, bits)
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -1903,7 +2079,7 @@ class Genome:
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
                           max_guides=0, params=None, efficiency=None, min_efficiency=None, microhomology=None,
                           min_out_of_frame=None, min_microhomology=None, edit=None, edit_targets=None, min_editable=None,
-                          max_editable=None):
+                          max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -1923,7 +2099,11 @@ class Genome:
         edit= an EditShape whose site_len is the pattern's length: the candidates' (mask, hits) rows (uint32[n, 2],
         vsc_pattern_guides_edit) come last of all.  edit_targets= (contig, pos) rows / min_editable= / max_editable= (all need
         edit=): only the candidates whose site is defined, whose window holds min_editable .. max_editable editable bases and
-        - with targets - reaches a target (vsc_pattern_guides_filter_edit), on the device after the other floors."""
+        - with targets - reaches a target (vsc_pattern_guides_filter_edit), on the device after the other floors.
+        cds= a Cds (needs edit=): the candidates' effect rows (uint32[n, 2], vsc_pattern_guides_effects) come last of all, after
+        the edit rows.  edit_to= the base the editor writes (default: the transition partner of the shape's base) /
+        require_effect= / forbid_effect= class names of EFFECT_CLASSES (all need cds=): only the candidates with an effect of
+        a required class and none of a forbidden one (vsc_pattern_guides_filter_effects), after the edit filter."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -1933,6 +2113,7 @@ class Genome:
         self._eff_args(efficiency, min_efficiency, len(p))
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, len(p))
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, len(p))
+        fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -1942,7 +2123,8 @@ class Genome:
                                            (L.vsc_pattern_guides_efficiency, L.vsc_pattern_guides_filter_efficiency),
                                            (L.vsc_pattern_guides_microhomology, L.vsc_pattern_guides_filter_microhomology),
                                            L.vsc_pattern_guides_free, ed,
-                                           (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit))
+                                           (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit), fx,
+                                           (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -1971,7 +2153,8 @@ class Genome:
         pick= a PickShape whose site_len is the pattern's length (with pick_by= / pick_groups=): as Genome.design takes them,
         over `targets` as a Regions under the enumeration's rule; the columns are "table" (the default; needs table=), "eff",
         "oof" and "mh".  (picks, counts) come last of all.  edit= (and its options), as enumerate_pattern takes them: only the
-        survivors are searched; the edit rows come after the microhomology pairs, before (picks, counts)."""
+        survivors are searched; the edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= /
+        require_effect= / forbid_effect=: as enumerate_pattern; the effect rows come after the edit rows."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -2085,15 +2268,19 @@ class Genome:
         _eff_partial(st.as_dict(), False)
         return pairs
 
-    def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None):
+    def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
+                          fx=None, fx_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs before the edit rows.  held[0] is replaced as _eff_on_handle replaces it."""
+        the microhomology pairs before the edit rows before the effect rows.  held[0] is replaced as _eff_on_handle
+        replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
         if mh is not None:
             self._mh_on_handle(held, mh, count_fn, mh_fns[0], mh_fns[1], free_fn, score=False)
         if ed is not None:
             self._edit_on_handle(held, ed, count_fn, ed_fns[0], ed_fns[1], free_fn, rows=False)
+        if fx is not None:
+            self._effects_on_handle(held, ed[0], fx, count_fn, fx_fns[0], fx_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -2101,6 +2288,8 @@ class Genome:
             extra += (self._mh_on_handle(held, (mh[0], None, None), count_fn, mh_fns[0], mh_fns[1], free_fn),)
         if ed is not None:
             extra += (self._edit_on_handle(held, ed[:4] + (None,), count_fn, ed_fns[0], ed_fns[1], free_fn),)
+        if fx is not None:
+            extra += (self._effects_on_handle(held, ed[0], fx[:2] + (0, 0) + fx[4:], count_fn, fx_fns[0], fx_fns[1], free_fn),)
         return extra
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
@@ -2171,6 +2360,89 @@ class Genome:
         check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), tp, n_t, ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
         _eff_partial(st.as_dict(), False)
         return r
+
+    # ---- coding consequences of base edits (vsc_*_effects) -----------------------------------------------------------------
+    @staticmethod
+    def _effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect):
+        """(cds, to, require mask, forbid mask, code) - or None without a Cds.  ed: what _edit_args returned."""
+        if cds is None:
+            if edit_to is not None or require_effect is not None or forbid_effect is not None:
+                raise ValueError("edit_to / require_effect / forbid_effect need cds=")
+            return None
+        if ed is None:
+            raise ValueError("cds= needs edit=shape")
+        if not isinstance(cds, Cds):
+            raise ValueError("cds must be a Cds")
+        if edit_to is None and isinstance(edit, str):
+            edit_to = EDITOR_TO[edit]
+        return cds, _effect_to(ed[0], edit_to), effect_class_mask(require_effect), effect_class_mask(forbid_effect), None
+
+    def _effects_on_handle(self, held, shape, fx, count_fn, rows_fn, filter_fn, free_fn, rows=True):
+        """As _edit_on_handle, for the effect rows: fx = what _effects_args returned.  With a require or forbid mask the handle
+        is first replaced by the filter's result; the rows of the survivors come back as uint32[n, 2]."""
+        cds, to, require, forbid, code = fx
+        sh = shape._struct()
+        if require or forbid:
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), to, cds._h, code, require, forbid, C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        r = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.EffectsStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), to, cds._h, code, ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return r
+
+    def effects(self, loci_or_found, shape, to, cds, effects=True, coverage=False, code=None, allow_partial=False):
+        """vsc_loci_effects: what a base editor's full conversion of every candidate's window does to the codons of a Cds, on
+        the device from the resident planes.  shape: an EditShape or the name of a preset of EDITORS; to: the base
+        the editor writes on the read strand (a letter or 0..3; None: EDITOR_TO of the preset, else the transition partner of
+        the shape's base).  Returns (rows, effects, coverage, stats).  rows uint32[n, 2] (unpack_effect_row): the candidate's
+        effects by class, 5 bits each, and the bits of its mask that lie in a segment; (EFFECTS_UNDEFINED, EFFECTS_UNDEFINED)
+        where the site is undefined.  effects (EFFECT_DTYPE; None with effects=False): candidate, transcript, codon, info
+        (unpack_effect_info: ref, alt, class, edited, at), ascending candidate and inside it ascending forward position.
+        coverage (uint32[cds.n_tx, 2] with coverage=True, else None): the stop_gained effects of every transcript and the
+        smallest codon among them (EFFECTS_UNDEFINED: none).  code: 64 letters instead of GENETIC_CODE.  stats: the candidates
+        by class, with_effect, effects, by_class, transcripts_stopped, kernel_ms, wall_ms.  loci_or_found: as Genome.efficiency
+        takes it.  Raises when a site is not resident on this object (a shard) unless allow_partial=True."""
+        if isinstance(shape, str):
+            if shape not in EDITORS:
+                raise ValueError("shape names one of %s, or is an EditShape" % ", ".join(sorted(EDITORS)))
+            to = EDITOR_TO[shape] if to is None else to
+            shape = EDITORS[shape]
+        if not isinstance(cds, Cds):
+            raise ValueError("cds must be a Cds")
+        t = _effect_to(shape, to)
+        cd = _effect_code(code)
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        rows = np.empty((n, 2), dtype=np.uint32)
+        cov = np.empty((cds.n_tx, 2), dtype=np.uint32) if coverage else None
+        want = bool(effects)
+        cap = min(max(n, 1024), 1 << 22) if want else 0
+        ef = np.empty(cap, dtype=_lib.EFFECT_DTYPE) if want else None
+        st = _lib.EffectsStats()
+        sh = shape._struct()
+        count = C.c_uint64()
+        L = lib()
+        rc = L.vsc_loci_effects(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), t, cds._h, cd, ptr(rows), ptr(ef), cap, C.byref(count),
+                                ptr(cov), C.byref(st))
+        if rc == _lib.VSC_ERR_RANGE and want and cap < int(count.value) <= 0xFFFFFFFE:
+            # (the rows, the coverage and the stats of the first call stand; the second brings the effects alone)
+            cap = int(count.value)
+            ef = np.empty(cap, dtype=_lib.EFFECT_DTYPE)
+            check(L.vsc_loci_effects(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), t, cds._h, cd, None, ptr(ef), cap, C.byref(count), None,
+                                     None), self.ctx._h)
+        else:
+            check(rc, self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        if want:
+            ef = ef[:int(count.value)].copy()
+        return rows, ef, cov, stats
 
     def edit(self, loci_or_found, shape, targets=None, pairs=True, coverage=False, allow_partial=False):
         """vsc_loci_edit: the editing windows of candidates under an EditShape (or the name of a preset of EDITORS), and their
@@ -2451,7 +2723,8 @@ class Genome:
 
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
-                         min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None):
+                         min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None, cds=None,
+                         edit_to=None, require_effect=None, forbid_effect=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2470,12 +2743,17 @@ class Genome:
         edit= an EditShape with site_len 23 or the name of a preset of EDITORS: the candidates' (mask, hits) rows (uint32[n, 2],
         vsc_guides_edit) come last of all.  edit_targets= (contig, pos) rows in any order / min_editable= / max_editable= (all
         need edit=): only the candidates whose site is defined, whose window holds min_editable .. max_editable editable
-        bases and - with targets - reaches a target (vsc_guides_filter_edit), on the device after the other floors."""
+        bases and - with targets - reaches a target (vsc_guides_filter_edit), on the device after the other floors.
+        cds= a Cds (needs edit=): the candidates' effect rows (uint32[n, 2], vsc_guides_effects) come last of all, after the
+        edit rows.  edit_to= the base the editor writes (default: EDITOR_TO of a preset, else the transition partner of the
+        shape's base) / require_effect= / forbid_effect= class names of EFFECT_CLASSES (all need cds=): only the candidates
+        with an effect of a required class and none of a forbidden one (vsc_guides_filter_effects), after the edit filter."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, READ_LEN)
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, READ_LEN)
+        fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
@@ -2487,7 +2765,8 @@ class Genome:
             extra = self._scores_on_handle(held, efficiency, min_efficiency, mh, L.vsc_guides_count,
                                            (L.vsc_guides_efficiency, L.vsc_guides_filter_efficiency),
                                            (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free,
-                                           ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit))
+                                           ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit), fx,
+                                           (L.vsc_guides_effects, L.vsc_guides_filter_effects))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -2520,7 +2799,7 @@ class Genome:
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
                efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
                pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
-               **search_options):
+               cds=None, edit_to=None, require_effect=None, forbid_effect=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -2535,14 +2814,16 @@ class Genome:
         predictor), "oof" (floor(1000 oof / sum), 10 bits) and "mh" (min(sum, 2^20 - 1), 20 bits); a column whose option was
         not given is refused.  (picks, counts) come last of all.  Without pick= nothing changes.
         edit= / edit_targets= / min_editable= / max_editable=: as enumerate_guides; only the survivors are searched, and the
-        edit rows come after the microhomology pairs, before (picks, counts)."""
+        edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= / require_effect= /
+        forbid_effect=: as enumerate_guides; the effect rows come after the edit rows."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
                                       labels=labels, efficiency=efficiency, min_efficiency=min_efficiency,
                                       microhomology=microhomology, min_out_of_frame=min_out_of_frame,
                                       min_microhomology=min_microhomology, edit=edit, edit_targets=edit_targets,
-                                      min_editable=min_editable, max_editable=max_editable)
+                                      min_editable=min_editable, max_editable=max_editable, cds=cds, edit_to=edit_to,
+                                      require_effect=require_effect, forbid_effect=forbid_effect)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])

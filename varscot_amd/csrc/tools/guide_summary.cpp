@@ -131,6 +131,7 @@
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
 #include "edit_host.hpp"
+#include "effects_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
@@ -204,6 +205,12 @@ int main(int argc, char **argv)
                               "that the editor converts are kept", false},
         {'l', "editable", "With -x: MIN,MAX: keep only the candidates with MIN .. MAX editable bases in the window (0 .. 16)", false},
         {'o', "edit-pairs", "With -z: path to the listing of the pairs: #chrom pos guideId at bystanders", false},
+        {'d', "cds", "With -x: path to the coding segments (.bed, BED6: chrom start end transcript phase strand): the guide listing gains the "
+                     "last columns codingEdits stopGained missense synonymous - what the editor's full conversion does to the codons", false},
+        {'2', "edit-to", "With --cds: the base the editor writes on the read strand (default: the transition partner of the base of -x)", false},
+        {'f', "effect-filter", "With --cds: REQUIRE[/FORBID], class names joined by + (synonymous missense stop_gained stop_lost start_lost "
+                               "unknown): keep only the candidates with an effect of a REQUIRE class and none of a FORBID class", false},
+        {'Q', "effects", "With --cds: path to the listing of the effects: #guideId transcript codon ref alt refAA altAA class at", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -589,6 +596,18 @@ int main(int argc, char **argv)
         }
     }
 
+    // --cds / --edit-to / --effect-filter / --effects: what the editor does to the codons
+    EffectsOptions fx;
+    {
+        const std::string why = parse_effects_options(opts[46].set, opts[46].value, opts[47].set, opts[47].value, opts[48].set, opts[48].value,
+                                                      opts[49].set, opts[49].value, edit, &fx);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+    CdsOfFile coding;
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -753,6 +772,14 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            if (fx.on) read_cds(fx.cds_path, ix.names, ix.contigs, &coding);
+            if (fx.filtered) {  // --effect-filter: the same for the effects' FILTER, after the editor's
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, fx.require, fx.forbid, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -768,6 +795,13 @@ int main(int argc, char **argv)
                                         cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &edit_rows, &edit_pairs);
+            std::vector<uint32_t> fx_rows;  // --cds: the effect rows, and with --effects the records
+            std::vector<vsc_effect> fx_records;
+            if (fx.on)
+                effects_rows_and_records(fx, vsc_guides_count(found), [&](uint32_t *r, vsc_effect *e, uint64_t cap, uint64_t *ne) {
+                    if (vsc_guides_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, r, e, cap, ne, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &fx_rows, &fx_records);
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -792,7 +826,8 @@ int main(int argc, char **argv)
                             "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
                             (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
-                    const std::string ecol = edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "";
+                    const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
+                                             (fx.on ? effects_columns(&fx_rows[2 * i]) : "");
                     if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
                     else bed6 += line + ecol + '\n';
                 }
@@ -805,6 +840,7 @@ int main(int argc, char **argv)
                 if (!out) throw std::runtime_error("Could not write the -L file.");
             }
             if (edit.with_pairs) write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
+            if (fx.with_listing) write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');

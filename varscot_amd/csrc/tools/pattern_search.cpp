@@ -67,6 +67,7 @@
 #include "eff_model_host.hpp"
 #include "mh_host.hpp"
 #include "edit_host.hpp"
+#include "effects_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
 
@@ -251,6 +252,12 @@ int main(int argc, char **argv)
                               "that the editor converts are kept", false},
         {'l', "editable", "With -x: MIN,MAX: keep only the candidates with MIN .. MAX editable bases in the window (0 .. 16)", false},
         {'o', "edit-pairs", "With -z: path to the listing of the pairs: #chrom pos guideId at bystanders", false},
+        {'d', "cds", "With -x: path to the coding segments (.bed, BED6: chrom start end transcript phase strand): the -E listing gains the "
+                     "last columns codingEdits stopGained missense synonymous - what the editor's full conversion does to the codons", false},
+        {'2', "edit-to", "With --cds: the base the editor writes on the read strand (default: the transition partner of the base of -x)", false},
+        {'f', "effect-filter", "With --cds: REQUIRE[/FORBID], class names joined by + (synonymous missense stop_gained stop_lost start_lost "
+                               "unknown): keep only the candidates with an effect of a REQUIRE class and none of a FORBID class", false},
+        {'Q', "effects", "With --cds: path to the listing of the effects: #guideId transcript codon ref alt refAA altAA class at", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -465,6 +472,17 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // --cds / --edit-to / --effect-filter / --effects: what the editor does to the codons
+    EffectsOptions fx;
+    {
+        const std::string why = parse_effects_options(opts[34].set, opts[34].value, opts[35].set, opts[35].value, opts[36].set, opts[36].value,
+                                                      opts[37].set, opts[37].value, edit, &fx);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+    CdsOfFile coding;
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     // -k / -b / -c: the best guides of every -B target
@@ -641,6 +659,14 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            if (fx.on) read_cds(fx.cds_path, ix.names, ix.contigs, &coding);
+            if (fx.filtered) {  // --effect-filter: the same for the effects' FILTER, after the editor's
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, fx.require, fx.forbid, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -656,6 +682,13 @@ int main(int argc, char **argv)
                                                 edit_targets.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &edit_rows, &edit_pairs);
+            std::vector<uint32_t> fx_rows;  // --cds: the effect rows, and with --effects the records
+            std::vector<vsc_effect> fx_records;
+            if (fx.on)
+                effects_rows_and_records(fx, vsc_pattern_guides_count(found), [&](uint32_t *r, vsc_effect *e, uint64_t cap, uint64_t *ne) {
+                    if (vsc_pattern_guides_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, r, e, cap, ne, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &fx_rows, &fx_records);
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -664,7 +697,8 @@ int main(int argc, char **argv)
             std::ofstream out(opts[7].value);
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
             out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
-                << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "") << '\n';
+                << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "")
+                << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -689,6 +723,7 @@ int main(int argc, char **argv)
                     if (vsc_pattern_guide_text(codes[i], len, ep.ps_start, ep.ps_len, 1, own) != VSC_OK) throw std::runtime_error("a code of the enumeration is no site");
                     ecol = edit_columns(edit.shape, std::string(own, len), &edit_rows[2 * i]);
                 }
+                if (fx.on) ecol += effects_columns(&fx_rows[2 * i]);
                 if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
                 else out << line << ecol << '\n';
             }
@@ -696,6 +731,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
+            }
+            if (fx.with_listing) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

@@ -248,7 +248,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
                          &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
-                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
+                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->cds_buf, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
@@ -256,6 +256,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     ctx->eff_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
+    ctx->cds_serial = 0;
     ctx->varmap_serial = 0;
     ctx->pv_shadow_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
@@ -5367,6 +5368,514 @@ int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_p
                                    vsc_pattern_guides **out)
 {
     return edit_filter(ctx, genome, in, shape, targets, n_t, false, min_editable, max_editable, out, "vsc_pattern_guides_filter_edit");
+}
+
+}  // extern "C"
+
+// ---- coding consequences of base edits (the definition: vsc_effects.h, the kernels: vsc_effects.hip) ----------
+namespace {
+
+std::atomic<uint64_t> g_cds_serial{0};
+thread_local std::string t_cds_error;
+
+int cds_refuse(int code, const char *what, uint64_t segment)
+{
+    char msg[200];
+    std::snprintf(msg, sizeof msg, "vsc_cds_build: segment %llu: %s", (unsigned long long)segment, what);
+    t_cds_error = msg;
+    return code;
+}
+
+// CODE of a call: the caller's 64 letters, or the standard code
+bool effects_code(const char *code, EffectsCode &out)
+{
+    if (code && strnlen(code, 64) != 64) return false;
+    std::memcpy(out.aa, code ? code : kStandardCode, 64);
+    return true;
+}
+
+// shape and `to` of an effects call
+bool effects_params(const vsc_edit_shape *shape, uint32_t to, EditShape &s)
+{
+    s = EditShape{shape->site_len, shape->win_start, shape->win_len, shape->from};
+    return !(shape->reserved[0] || shape->reserved[1] || shape->reserved[2] || shape->reserved[3]) && edit_shape_valid(s) && to <= 3u &&
+           to != s.from;
+}
+
+// The arguments every device entry shares, checked on the host.
+int effects_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_edit_shape *shape, uint32_t to, const vsc_cds *cds, const char *code,
+                  EditShape &s, EffectsCode &ec, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape || !cds) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!effects_params(shape, to, s))
+        return fail_in(ctx, VSC_ERR_INVALID, who,
+                       "site_len 16 .. 32, 1 <= win_len <= 16, win_start + win_len <= site_len, from 0 .. 3, to 0 .. 3 and not from, reserved fields 0");
+    if (!effects_code(code, ec)) return fail_in(ctx, VSC_ERR_INVALID, who, "the code has fewer than 64 letters");
+    bool same = cds->contig_off.size() == genome->h_contig_off.size() && genome->h_contig_off.size() == genome->h_contig_end.size();
+    for (size_t c = 0; same && c < cds->contig_off.size(); ++c)
+        same = cds->contig_off[c] == genome->h_contig_off[c] && cds->contig_off[c] + cds->contig_len[c] == genome->h_contig_end[c];
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the CDS was built with another contig table than the genome's");
+    return VSC_OK;
+}
+
+// the device copy of the segments: [global starts][segments], keyed by the object's serial number
+int effects_upload_cds(vsc_ctx *ctx, const vsc_cds *cds, CdsView &v)
+{
+    const size_t n = cds->seg.size(), start_bytes = round256(n * sizeof(uint32_t) + 4);
+    if (ctx->cds_serial != cds->serial) {
+        ctx->cds_serial = 0;
+        VSC_HIP(ctx, ctx->cds_buf.ensure(start_bytes + n * sizeof(CdsSeg) + sizeof(CdsSeg)));  // (never empty)
+        if (n) {
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->cds_buf.p, cds->gstart.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->cds_buf.p + start_bytes, cds->seg.data(), n * sizeof(CdsSeg), hipMemcpyHostToDevice,
+                                        ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the object as soon as its call returns)
+        ctx->cds_serial = cds->serial;
+    }
+    v = CdsView{(const uint32_t *)ctx->cds_buf.p, (const CdsSeg *)((const char *)ctx->cds_buf.p + start_bytes), (uint32_t)n};
+    return VSC_OK;
+}
+
+// Rows, records and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first):
+// effects_rows_kernel, then the records' count pass over the rows, the scan, one 8-byte read-back (the effects) and the write pass.
+int effects_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, uint32_t to, const vsc_cds *cds, const EffectsCode &code,
+                const void *d_loci, const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_effect *effects, uint64_t capacity,
+                uint64_t *n_effects, uint32_t *coverage, vsc_effects_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_tx = cds->n_tx;
+    if (stats) *stats = vsc_effects_stats{};
+    if (n_effects) *n_effects = 0;
+    if (coverage)
+        for (size_t k = 0; k < n_tx; ++k) {
+            coverage[2 * k] = 0;
+            coverage[2 * k + 1] = kEffectsUndefined;
+        }
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
+    // edit_tabs: [stop_gained effects per transcript][their smallest codon][effects per tile][offsets per tile]
+    const size_t cov_bytes = round256(n_tx * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
+    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
+    VSC_HIP(ctx, ctx->edit_tabs.ensure(2 * cov_bytes + count_bytes + off_bytes));
+    char *tabs = (char *)ctx->edit_tabs.p;
+    EffectsArgs a{};
+    const int urc = effects_upload_cds(ctx, cds, a.cds);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.to = to;
+    a.code = code;
+    a.n = n;
+    const size_t head = 256;  // the counters, in front of the rows
+    static_assert((kEffectsCounts + 2) * sizeof(unsigned long long) <= 256, "the counters and the covered transcripts lie in the head");
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_effects_rows(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kEffectsCounts] = {};
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    EffectsRecordArgs p{};
+    p.g = a.g;
+    p.shape = shape;
+    p.to = to;
+    p.cds = a.cds;
+    p.code = code;
+    p.loci = a.loci;
+    p.rows = a.out;
+    p.n = n;
+    p.n_work = tiles;
+    p.n_tx = (uint32_t)n_tx;
+    p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
+    unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
+    p.tile_off = d_off;
+    unsigned long long total = 0;
+    float pass_ms = 0;
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+    VSC_HIP(ctx, launch_effects_records(p, false, ctx->stream));
+    VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+    if (n_effects) *n_effects = total;
+    const bool too_many = total > kEffectsMaxCount, write = effects && total && total <= capacity && !too_many;
+    const bool cover = total && n_tx && seen[kEffClasses + 1 + kEffectStopGained] && (coverage || stats);
+    uint64_t covered = 0;
+    if (write || cover) {
+        if (write) {
+            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_effect)));
+            p.effects = (uint4 *)ctx->edit_pairs.p;
+        }
+        if (cover) {
+            p.cov_count = (uint32_t *)tabs;
+            p.cov_min = (uint32_t *)(tabs + cov_bytes);
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_tx * sizeof(uint32_t), ctx->stream));
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_tx * sizeof(uint32_t), ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_effects_records(p, true, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        std::vector<uint32_t> cov;
+        unsigned long long d_covered = 0;
+        if (write) VSC_HIP(ctx, hipMemcpyAsync(effects, p.effects, (size_t)total * sizeof(vsc_effect), hipMemcpyDeviceToHost, ctx->stream));
+        if (cover && !coverage) {  // the stats alone: the covered transcripts are counted where they lie, 8 bytes come back
+            unsigned long long *slot = a.stats + kEffectsCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
+            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_tx, slot, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (cover) {
+            cov.resize(2 * n_tx);
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_tx, p.cov_min, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float wms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        pass_ms += wms;
+        covered = d_covered;
+        for (size_t k = 0; cover && coverage && k < n_tx; ++k) {
+            covered += cov[k] != 0;
+            coverage[2 * k] = cov[k];
+            coverage[2 * k + 1] = cov[n_tx + k];
+        }
+    }
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+        stats->with_effect = seen[kEffClasses];
+        stats->effects = total;
+        for (uint32_t k = 0; k < kEffectClasses; ++k) stats->by_class[k] = seen[kEffClasses + 1 + k];
+        stats->transcripts_stopped = covered;
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    t.score_ms = ms;
+    t.scan_ms = pass_ms;
+    t.total_ms = t.score_ms + t.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
+    ctx->timing = t;
+    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE effects");
+    if (effects && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more effects than `capacity` holds; *n_effects is their number");
+    return VSC_OK;
+}
+
+// vsc_guides_effects / vsc_pattern_guides_effects: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int effects_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_edit_shape *shape, uint32_t to, const vsc_cds *cds,
+                   const char *code, bool need_23, uint32_t *rows, vsc_effect *effects, uint64_t capacity, uint64_t *n_effects,
+                   uint32_t *coverage, vsc_effects_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    EditShape s{};
+    EffectsCode ec{};
+    const int rc = effects_check(ctx, genome, shape, to, cds, code, s, ec, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (guides->n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const bool dev = guides->ctx != nullptr;
+    return effects_run(ctx, genome, s, to, cds, ec, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
+                       dev ? nullptr : guides->loci.data(), guides->n, rows, effects, capacity, n_effects, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_effects / vsc_pattern_guides_filter_effects: run_enumeration's two passes over tiles of kEditTile
+// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+template <class Guides>
+int effects_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_edit_shape *shape, uint32_t to, const vsc_cds *cds,
+                   const char *code, bool need_23, uint32_t require, uint32_t forbid, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    EditShape s{};
+    EffectsFilterArgs a{};
+    const int rc = effects_check(ctx, genome, shape, to, cds, code, s, a.code, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if ((require | forbid) >> kEffectClasses) return fail_in(ctx, VSC_ERR_INVALID, who, "require / forbid are masks over bits 0 .. 5");
+    const uint64_t n = in->n;
+    if (n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const int urc = effects_upload_cds(ctx, cds, a.cds);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.to = to;
+    a.n = n;
+    a.require = require;
+    a.forbid = forbid;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_effects_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_cds_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_cds_segment *segments, uint64_t n, uint32_t n_tx, vsc_cds **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    try {
+        t_cds_error.clear();
+        if ((n_contigs && !contigs) || (n && !segments)) {
+            t_cds_error = "vsc_cds_build: null argument";
+            return VSC_ERR_INVALID;
+        }
+        if (n > kEffectsMaxCount) {
+            t_cds_error = "vsc_cds_build: more than 0xFFFFFFFE segments";
+            return VSC_ERR_RANGE;
+        }
+        std::unique_ptr<vsc_cds> c(new vsc_cds());
+        for (uint32_t k = 0; k < n_contigs; ++k) {
+            if (contigs[k].offset + contigs[k].length >= (1ull << 32)) {
+                t_cds_error = "vsc_cds_build: the contigs end beyond 2^32";
+                return VSC_ERR_RANGE;
+            }
+            c->contig_off.push_back((uint32_t)contigs[k].offset);
+            c->contig_len.push_back(contigs[k].length);
+        }
+        c->n_tx = n_tx;
+        c->gstart.resize((size_t)n);
+        c->seg.resize((size_t)n);
+        // per transcript: its first segment in genome order, its last one, contig and strand, its bases
+        struct Tx {
+            uint32_t first = kCdsNone, last = kCdsNone, contig = 0, strand = 0;
+            uint64_t bases = 0;
+        };
+        std::vector<Tx> tx(n_tx);
+        std::vector<uint32_t> after((size_t)n, kCdsNone), before((size_t)n, kCdsNone);  // the transcript's next / previous segment in GENOME order
+        for (uint64_t i = 0; i < n; ++i) {
+            const vsc_cds_segment &s = segments[i];
+            if (s.reserved[0] || s.reserved[1]) return cds_refuse(VSC_ERR_INVALID, "a reserved field is not 0", i);
+            if (s.contig >= n_contigs) return cds_refuse(VSC_ERR_INVALID, "it lies on an unknown contig", i);
+            if (s.strand > 1u || s.phase > 2u) return cds_refuse(VSC_ERR_INVALID, "strand is 0 or 1, phase 0 .. 2", i);
+            if (s.start >= s.end) return cds_refuse(VSC_ERR_INVALID, "it is empty", i);
+            if (s.end > contigs[s.contig].length) return cds_refuse(VSC_ERR_INVALID, "it reaches beyond its contig", i);
+            if (s.transcript >= n_tx) return cds_refuse(VSC_ERR_INVALID, "its transcript is not below n_tx", i);
+            if (i) {
+                const vsc_cds_segment &q = segments[i - 1];
+                if (q.contig > s.contig || (q.contig == s.contig && q.start >= s.start))
+                    return cds_refuse(VSC_ERR_INVALID, "the segments are not strictly ascending by (contig, start)", i);
+                if (q.contig == s.contig && q.end > s.start) return cds_refuse(VSC_ERR_INVALID, "it overlaps the segment in front of it", i);
+            }
+            Tx &t = tx[s.transcript];
+            if (t.first == kCdsNone) {
+                t.first = (uint32_t)i;
+                t.contig = s.contig;
+                t.strand = s.strand;
+            } else {
+                if (t.contig != s.contig) return cds_refuse(VSC_ERR_INVALID, "its transcript lies on two contigs", i);
+                if (t.strand != s.strand) return cds_refuse(VSC_ERR_INVALID, "its transcript lies on two strands", i);
+                after[t.last] = (uint32_t)i;
+                before[i] = t.last;
+            }
+            t.last = (uint32_t)i;
+            t.bases += s.end - s.start;
+            if (t.bases + 2u >= (1ull << 31)) return cds_refuse(VSC_ERR_RANGE, "its transcript's coding length reaches 2^31", i);
+            const uint32_t off = c->contig_off[s.contig];
+            c->gstart[i] = off + s.start;
+            c->seg[i] = CdsSeg{off + s.start, off + s.end, s.transcript, 0u, kCdsNone, kCdsNone, s.strand, 0u};
+        }
+        uint64_t used = 0, bases = 0;
+        for (uint32_t k = 0; k < n_tx; ++k) {
+            const Tx &t = tx[k];
+            if (t.first == kCdsNone) continue;
+            ++used;
+            bases += t.bases;
+            // transcript order: ascending start on '+', descending on '-'
+            const std::vector<uint32_t> &fwd = t.strand ? before : after, &bwd = t.strand ? after : before;
+            const uint32_t head = t.strand ? t.last : t.first;
+            const uint32_t shift = (3u - segments[head].phase) % 3u;
+            uint32_t ci = shift;
+            for (uint32_t i = head; i != kCdsNone; i = fwd[i]) {
+                if (i != head && segments[i].phase != (3u - ci % 3u) % 3u)
+                    return cds_refuse(VSC_ERR_INVALID, "its phase does not continue its transcript's reading frame", i);
+                CdsSeg &sg = c->seg[i];
+                sg.ci0 = ci;
+                sg.prev = bwd[i];
+                sg.next = fwd[i];
+                sg.shift = shift;
+                ci += sg.gend - sg.gstart;
+            }
+        }
+        c->stats.segments = n;
+        c->stats.transcripts = n_tx;
+        c->stats.transcripts_used = used;
+        c->stats.coding_bases = bases;
+        c->serial = g_cds_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+        *out = c.release();
+        return VSC_OK;
+    } catch (const std::bad_alloc &) {
+        return VSC_ERR_NOMEM;
+    } catch (...) {
+        return VSC_ERR_INVALID;
+    }
+}
+
+const char *vsc_cds_build_error(void) { return t_cds_error.c_str(); }
+
+void vsc_cds_free(vsc_cds *cds) { delete cds; }
+
+int vsc_cds_info(const vsc_cds *cds, vsc_cds_stats *out)
+{
+    if (!cds || !out) return VSC_ERR_INVALID;
+    *out = cds->stats;
+    return VSC_OK;
+}
+
+int vsc_codon_effect(uint32_t ref, uint32_t alt, uint32_t codon, uint32_t first_phase, const char *code, uint32_t *effect_class_out)
+{
+    EffectsCode ec{};
+    if (!effect_class_out || ref > 63u || alt > 63u || first_phase > 2u || !effects_code(code, ec)) return VSC_ERR_INVALID;
+    *effect_class_out = effect_class(ref, alt, codon, first_phase == 0u, ec.aa, false);
+    return VSC_OK;
+}
+
+int vsc_effects_site_text(const vsc_cds *cds, const char *const *texts, uint32_t contig, uint32_t pos, uint32_t strand,
+                          const vsc_edit_shape *shape, uint32_t to, const char *code, uint32_t *row, vsc_effect *effects, uint32_t *n_effects)
+{
+    if (!cds || !shape || !row || !effects || !n_effects) return VSC_ERR_INVALID;
+    try {
+        EditShape s{};
+        EffectsCode ec{};
+        if (!effects_params(shape, to, s) || !effects_code(code, ec)) return VSC_ERR_INVALID;
+        const uint32_t nc = (uint32_t)cds->contig_off.size();
+        if (nc && !texts) return VSC_ERR_INVALID;
+        uint64_t total = 0;
+        for (uint32_t c = 0; c < nc; ++c) {
+            if (cds->contig_len[c] && !texts[c]) return VSC_ERR_INVALID;
+            total = std::max<uint64_t>(total, (uint64_t)cds->contig_off[c] + cds->contig_len[c]);
+        }
+        // the planes of the letters, as the genome's are packed: what lies between the contigs is N
+        const uint64_t words = (total + 31) / 32 + 1;
+        std::vector<uint32_t> hi((size_t)words, 0u), lo((size_t)words, 0u), nm((size_t)words, 0xFFFFFFFFu), ends(nc);
+        for (uint32_t c = 0; c < nc; ++c) {
+            ends[c] = cds->contig_off[c] + cds->contig_len[c];
+            for (uint32_t i = 0; i < cds->contig_len[c]; ++i) {
+                const int b = base_code(texts[c][i]);
+                if (b > 3) continue;
+                const uint64_t x = (uint64_t)cds->contig_off[c] + i;
+                nm[x >> 5] &= ~(1u << (x & 31));
+                hi[x >> 5] |= (uint32_t)(b >> 1) << (x & 31);
+                lo[x >> 5] |= (uint32_t)(b & 1) << (x & 31);
+            }
+        }
+        const EffPlanes g{hi.data(), lo.data(), nm.data(), 0, words, words, cds->contig_off.data(), ends.data(), nc};
+        *n_effects = 0;
+        row[0] = row[1] = kEffectsUndefined;
+        uint64_t ch = 0, cl = 0;
+        if (edit_site(g, s, contig, pos, strand, &ch, &cl) != kEffDefined) return VSC_OK;
+        const uint32_t mask = edit_mask(ch, cl, s);
+        uint32_t count = 0;
+        effects_row(g, cds->view(), s, to, ec.aa, cds->contig_off[contig] + edit_window_first(pos, strand, s), strand, mask, &row[0], &row[1],
+                    [&](uint32_t tx, uint32_t codon, uint32_t info) {
+                        if (count < kEditMaxWindow) effects[count++] = vsc_effect{0u, tx, codon, info};
+                    });
+        *n_effects = count;
+        return VSC_OK;
+    } catch (const std::bad_alloc &) {
+        return VSC_ERR_NOMEM;
+    } catch (...) {
+        return VSC_ERR_INVALID;
+    }
+}
+
+int vsc_loci_effects(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_edit_shape *shape, uint32_t to,
+                     const vsc_cds *cds, const char *code, uint32_t *rows, vsc_effect *effects, uint64_t capacity, uint64_t *n_effects,
+                     uint32_t *coverage, vsc_effects_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_effects";
+    EditShape s{};
+    EffectsCode ec{};
+    const int rc = effects_check(ctx, genome, shape, to, cds, code, s, ec, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return effects_run(ctx, genome, s, to, cds, ec, nullptr, loci, n, rows, effects, capacity, n_effects, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_edit_shape *shape, uint32_t to,
+                       const vsc_cds *cds, const char *code, uint32_t *rows, vsc_effect *effects, uint64_t capacity, uint64_t *n_effects,
+                       uint32_t *coverage, vsc_effects_stats *stats)
+{
+    return effects_guides(ctx, genome, guides, shape, to, cds, code, true, rows, effects, capacity, n_effects, coverage, stats,
+                          "vsc_guides_effects");
+}
+
+int vsc_pattern_guides_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_edit_shape *shape, uint32_t to,
+                               const vsc_cds *cds, const char *code, uint32_t *rows, vsc_effect *effects, uint64_t capacity,
+                               uint64_t *n_effects, uint32_t *coverage, vsc_effects_stats *stats)
+{
+    return effects_guides(ctx, genome, guides, shape, to, cds, code, false, rows, effects, capacity, n_effects, coverage, stats,
+                          "vsc_pattern_guides_effects");
+}
+
+int vsc_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_edit_shape *shape, uint32_t to,
+                              const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid, vsc_guides **out)
+{
+    return effects_filter(ctx, genome, in, shape, to, cds, code, true, require, forbid, out, "vsc_guides_filter_effects");
+}
+
+int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_edit_shape *shape,
+                                      uint32_t to, const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid,
+                                      vsc_pattern_guides **out)
+{
+    return effects_filter(ctx, genome, in, shape, to, cds, code, false, require, forbid, out, "vsc_pattern_guides_filter_effects");
 }
 
 }  // extern "C"

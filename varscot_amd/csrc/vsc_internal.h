@@ -9,6 +9,7 @@
 #include "vsc_efficiency.h"
 #include "vsc_mh.h"
 #include "vsc_edit.h"
+#include "vsc_effects.h"
 
 namespace vsc {
 
@@ -643,6 +644,59 @@ hipError_t launch_edit_pairs(const EditPairArgs &args, bool write, hipStream_t s
 hipError_t launch_edit_filter(const EditFilterArgs &args, bool write, hipStream_t stream);
 // *out (zeroed) += the entries of cov_count that are not 0
 hipError_t launch_edit_covered(const uint32_t *cov_count, uint32_t n_t, unsigned long long *out, int n_cus, hipStream_t stream);
+// vsc_effects.hip (the definition: vsc_effects.h)
+constexpr uint32_t kEffectsCounts = kEffClasses + 1 + kEffectClasses;  // the candidates' classes, the candidates with an effect, the effects by class
+struct EffectsCode {
+    uint8_t aa[64];               // CODE
+};
+struct EffectsArgs {
+    EffPlanes g;
+    EditShape shape;
+    uint32_t to;
+    CdsView cds;
+    EffectsCode code;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: ROW, kEffectsUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kEffectsCounts], zeroed before the launch
+};
+// the records' two passes: tile i = candidates [i * kEditTile, ..)
+struct EffectsRecordArgs {
+    EffPlanes g;
+    EditShape shape;
+    uint32_t to;
+    CdsView cds;
+    EffectsCode code;
+    const uint4 *loci;            // [n]
+    const uint2 *rows;            // [n] what effects_rows_kernel left
+    unsigned long long n;
+    uint32_t n_work;              // tiles
+    uint32_t *tile_count;         // count pass out: effects per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    uint4 *effects;               // write pass out (null: coverage only)
+    uint32_t *cov_count, *cov_min;  // [n_tx] each, write pass: stop_gained effects and their smallest codon per transcript, 0 / 0xFFFFFFFF before the launch; null: none
+    uint32_t n_tx;
+};
+struct EffectsFilterArgs {
+    EffPlanes g;
+    EditShape shape;
+    uint32_t to;
+    CdsView cds;
+    EffectsCode code;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    uint32_t require, forbid;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_effects_rows(const EffectsArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_effects_records(const EffectsRecordArgs &args, bool write, hipStream_t stream);
+hipError_t launch_effects_filter(const EffectsFilterArgs &args, bool write, hipStream_t stream);
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

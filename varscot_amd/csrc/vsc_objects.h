@@ -140,6 +140,10 @@ struct vsc_ctx {
     // vsc_*_edit: the call's tables (the targets' global positions, the coverage counters, the pairs' per-tile
     // counts and offsets) and its pairs; the candidates a call brings from the host and the rows lie in eff_in / eff_out
     vsc::DeviceBuf edit_tabs, edit_pairs;
+    // vsc_*_effects: the device copy of the CDS this context walked last - the segments' global starts, then the
+    // segments, keyed by the object's serial number as locate_buf is; the call's tables and records lie in edit_tabs / edit_pairs
+    vsc::DeviceBuf cds_buf;
+    uint64_t cds_serial = 0;  // 0: none resident
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
@@ -250,6 +254,18 @@ struct vsc_regions {
     {
         return vsc::RegionsView{start.data(), end_max.data(), cls.data(), (uint32_t)start.size(), n_blocks, block_shift, rule};
     }
+};
+
+// A CDS annotation as the effects kernels walk it (include/varscot_hip.h "SEGMENT / CODING"; built and checked by
+// vsc_cds_build).  Host-only, immutable once built.
+struct vsc_cds {
+    std::vector<uint32_t> contig_off, contig_len;  // the genome's table the segments were placed in
+    std::vector<uint32_t> gstart;                  // vsc::CdsView's arrays
+    std::vector<vsc::CdsSeg> seg;
+    uint32_t n_tx = 0;
+    uint64_t serial = 0;  // process-wide, handed out by vsc_cds_build: what a context's device copy is keyed by
+    vsc_cds_stats stats{};
+    vsc::CdsView view() const { return vsc::CdsView{gstart.data(), seg.data(), (uint32_t)seg.size()}; }
 };
 
 // A score table (include/varscot_hip.h "TABLE"; built and checked by vsc_score_table_build).  Host-only, immutable once built.
