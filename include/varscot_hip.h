@@ -2284,6 +2284,140 @@ int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vs
                                       uint32_t to, const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid,
                                       vsc_pattern_guides **out);
 
+/* ---- prime-editing guide design: pegRNA extensions per edit --------------------------------------- */
+/*
+ * Prime editors write substitutions, insertions and deletions behind a nick.  "Which candidates nick close enough upstream of my
+ * edit, what primer binding site (PBS) and reverse-transcriptase template (RTT) does the 3' extension need, does the edit
+ * destroy the PAM or the seed, does the extension hold a poly-T terminator?" - answered on the resident genome, where the
+ * candidates lie.  Everything is integer; device, host and a restatement on strings agree to the bit.
+ *
+ * SHAPE    site_len 16 .. 32;  down 0 .. 64 - site_len: bases of context behind the site in read orientation; C = site_len + down.
+ *          nick 1 .. site_len: the nick lies between read positions nick - 1 and nick (SpCas9 23-mer: 17).
+ *          1 <= pbs_min <= pbs_max <= nick;  1 <= rtt_min <= rtt_max <= C - nick;  pbs_max + rtt_max <= 64;
+ *          min_homology 0 .. rtt_max;  pam_start, pam_len and seed_start, seed_len: two ranges of read positions inside the site,
+ *          len 0 .. 8 (0: that flag is never set);  flags bit 0 AVOID_G_END;  reserved fields 0.
+ *          STABILITY: int32 init, mono[4], di[16], target, every |weight| <= 2^20.
+ * CONTEXT  of a locus (c, p, strand): eff_context with up = 0: '+': R = c[p, p + C);  '-': R = revcomp(c[p - down, p + site_len)).
+ *          F0 = the context's first forward position (p, or p - down).  CLASS as EffClass, in its order; off_contig CAN occur.
+ * PBS      S(L) = init + sum mono[R[j]], j in [nick - L, nick) + sum di[4 R[j] + R[j+1]], j in [nick - L, nick - 1).
+ *          pbs_len = the smallest L in [pbs_min, pbs_max] with S(L) >= target; none: pbs_len = pbs_max and WEAK.
+ *          pbs_gc = the G/C among R[nick - pbs_len, nick).
+ * EDITS    n_e entries { contig, pos, del_len 0 .. 16, ins_len 0 .. 16, ins }: forward bases [pos, pos + del_len) are replaced by
+ *          ins_len letters (2-bit code, letter k in bits 2k+1 .. 2k, the bits above them 0); del_len + ins_len >= 1;
+ *          pos + del_len <= the contig's length;  STRICTLY ascending by (contig, pos);  n_e <= 0xFFFFFFFE.
+ *          The replaced letters are not compared with ins (a substitution that writes the letter already there is the caller's business).
+ *          Every pair treats its edit alone; edits do not combine.
+ * READ     an edit is IN REACH of a defined candidate on its contig iff [pos, pos + del_len) lies inside [F0, F0 + C)
+ *          (del_len 0: F0 <= pos <= F0 + C) and e0 >= nick, with
+ *          '+': e0 = pos - F0, I = ins;   '-': e0 = C - (pos - F0) - del_len, I = revcomp(ins).
+ *          E = R[0, e0) + I + R[e0 + del_len, C): the edited strand in read orientation;  d = e0 - nick.
+ * RTT      t0 = max(rtt_min, d + ins_len + min_homology).  t = t0, or under AVOID_G_END the smallest t >= t0 with
+ *          E[nick + t - 1] != G (a position beyond E counts as not G).  The pair EXISTS iff t <= rtt_max and nick + t <= |E|.
+ *          h = t - d - ins_len.
+ * FLAGS    bit 0 PAM: E[q] != R[q] for some q of the pam range (q >= |E| counts as different);  bit 1 SEED: the same over the
+ *          seed range;  bit 2 POLY_T: E[nick - pbs_len, nick + t) holds four or more A in a row (the extension is its reverse
+ *          complement);  bit 3 WEAK (the candidate's).
+ * ROW      two uint32 per candidate: pbs = pbs_len | pbs_gc << 8 | WEAK << 16, and n_pairs.  Both 0xFFFFFFFF unless defined.
+ *          Without edits n_pairs = 0.
+ * PAIR     16 bytes { candidate, edit, info = t | d << 8 | h << 16 | flags << 24, ext = (pbs_len + t) | ext_gc << 8 | pbs_len << 16 },
+ *          ext_gc = the G/C of E[nick - pbs_len, nick + t).  Order: ascending (candidate, edit).  n <= 0xFFFFFFFE.
+ * COVERAGE optional, two uint32 per edit: its number of pairs and the smallest t among them (0xFFFFFFFF: none).
+ * FILTER   keep iff defined, (no edits given or n_pairs >= 1), and (allow_weak or not WEAK).  Survivors keep their input order.
+ * EXTENSION (host) revcomp(E[nick - pbs_len, nick + t)) as DNA letters: RTT then PBS, 5' to 3'.
+ *
+ * The output is a function of the inputs alone: it does not depend on launch shape or wave order.  The coverage and the pairs by
+ * flag use integer add / min atomics, which commute; nothing else depends on an atomic's order, and the pairs have no append
+ * cursor.  An occupancy bitmap over the edits' positions (one bit per 256 global positions) is asked before any search; it
+ * changes no output bit.
+ *
+ * vsc_prime_site_text: one context of C letters (any case) in read orientation and one edit in READ coordinates (e0, del_len, the
+ * inserted letters as the read strand has them, "" for none) on the host, by the functions the kernels call.  row[0] = the pbs
+ * word, row[1] = 1 if the pair exists and 0 otherwise; then pair[0] = info, pair[1] = ext, and extension (optional, at least 65
+ * bytes) holds the EXTENSION text.  The edit is optional (ins == NULL: the row's word alone, row[1] = 0).  A letter other than
+ * ACGT, a text of another length, a shape outside SHAPE, an edit outside [0, C] or longer than 16: VSC_ERR_INVALID.  An edit with
+ * e0 < nick is not in reach: row[1] = 0.
+ *
+ * vsc_loci_prime: loci are host entries in any order, duplicates allowed.  rows (optional): rows[2 i], rows[2 i + 1] = pbs, n_pairs
+ * of loci[i].  The pairs follow vsc_loci_edit's contract: *n_pairs (optional) is always the full count; pairs == NULL only counts;
+ * a count above `capacity` is VSC_ERR_RANGE, and then nothing is written to `pairs`, while rows, coverage, stats and *n_pairs
+ * are valid.  coverage (optional): 2 n_e entries.  stats (optional): the candidates by class (the five counts add up to n), the
+ * candidates with a pair, the weak candidates, the pairs, the pairs by flag (PAM, SEED, POLY_T, WEAK), the edits with a pair, the
+ * rows kernel's time and the call's wall time in milliseconds.  n == 0: VSC_OK, nothing is launched, the coverage says "no pair".
+ * vsc_guides_prime works over the candidates where they lie on the device - no locus travels - and requires site_len == 23; the
+ * host-only object of vsc_multi_guides_enumerate goes the vsc_loci_prime way.  vsc_pattern_guides_prime is the same for
+ * vsc_pattern_guides: site_len is the pattern's length, which the CALLER vouches for, as in the pick calls.
+ *
+ * vsc_guides_filter_prime / vsc_pattern_guides_filter_prime: *out = the candidates of `in` that pass FILTER - codes and loci
+ * copied unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of 1 024 candidates.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a shape outside SHAPE or
+ * with a non-zero reserved field; NULL arguments; a genome or object of another context; site_len != 23 for vsc_guides; edits
+ * not strictly ascending, on an unknown contig, or reaching beyond their contig; del_len or ins_len above 16, or both 0;
+ * insertion bits above ins_len; n_e > 0 with NULL edits.  VSC_ERR_RANGE: n or n_e above 0xFFFFFFFE.  Uploads and results use
+ * context scratch; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: a vsc_multi_* entry; several alleles at one position in one call (call once per allele set); more than one RTT
+ * length per pair (call again with another rtt_min); PE3 second-nick guides (vsc_loci_pairs with a delta range gives the
+ * opposite-strand candidates); efficiency models with trained weights; a shipped thermodynamic table (the caller brings mono /
+ * di); pegRNA scaffold or 3' motif text.
+ */
+#define VSC_PRIME_UNDEFINED 0xFFFFFFFFu
+#define VSC_PRIME_AVOID_G_END 1u
+#define VSC_PRIME_FLAG_PAM 1u
+#define VSC_PRIME_FLAG_SEED 2u
+#define VSC_PRIME_FLAG_POLY_T 4u
+#define VSC_PRIME_FLAG_WEAK 8u
+typedef struct {
+    uint32_t site_len, down, nick;
+    uint32_t pbs_min, pbs_max, rtt_min, rtt_max, min_homology;
+    uint32_t pam_start, pam_len, seed_start, seed_len;
+    uint32_t flags; /* VSC_PRIME_AVOID_G_END */
+    int32_t init, mono[4], di[16], target; /* STABILITY */
+    uint32_t reserved[5]; /* 0 */
+} vsc_prime_shape;
+typedef struct {
+    uint32_t contig, pos;
+    uint16_t del_len, ins_len;
+    uint32_t ins; /* letter k in bits 2k+1 .. 2k */
+} vsc_prime_edit;
+typedef struct {
+    uint32_t candidate, edit;
+    uint32_t info; /* t | d << 8 | h << 16 | flags << 24 */
+    uint32_t ext;  /* (pbs_len + t) | ext_gc << 8 | pbs_len << 16 */
+} vsc_prime_pair;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t with_pair, weak, pairs;
+    uint64_t pairs_by_flag[4]; /* PAM, SEED, POLY_T, WEAK */
+    uint64_t edits_covered;
+    double score_ms, wall_ms;
+    uint64_t reserved; /* 0 */
+} vsc_prime_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_prime_shape) == 160 && sizeof(vsc_prime_edit) == 16 && sizeof(vsc_prime_pair) == 16 && sizeof(vsc_prime_stats) == 128,
+              "vsc_prime_* layout");
+#else
+_Static_assert(sizeof(vsc_prime_shape) == 160 && sizeof(vsc_prime_edit) == 16 && sizeof(vsc_prime_pair) == 16 && sizeof(vsc_prime_stats) == 128,
+               "vsc_prime_* layout");
+#endif
+int vsc_prime_site_text(const char *context /* C letters, read orientation, any case */, const vsc_prime_shape *shape, uint32_t e0,
+                        uint32_t del_len, const char *ins /* read orientation, "" for none; NULL: no edit */, uint32_t *row /* 2 */,
+                        uint32_t *pair /* 2, optional */, char *extension /* >= 65 bytes, optional */);
+int vsc_loci_prime(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                   const vsc_prime_shape *shape, const vsc_prime_edit *edits /* host */, uint64_t n_e, uint32_t *rows /* host, 2 n, optional */,
+                   vsc_prime_pair *pairs /* host, optional */, uint64_t capacity, uint64_t *n_pairs /* optional */,
+                   uint32_t *coverage /* host, 2 n_e, optional */, vsc_prime_stats *stats /* optional */);
+int vsc_guides_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_prime_shape *shape,
+                     const vsc_prime_edit *edits, uint64_t n_e, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity,
+                     uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats);
+int vsc_pattern_guides_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_prime_shape *shape,
+                             const vsc_prime_edit *edits, uint64_t n_e, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity,
+                             uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats);
+int vsc_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_prime_shape *shape,
+                            const vsc_prime_edit *edits, uint64_t n_e, uint32_t allow_weak, vsc_guides **out);
+int vsc_pattern_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_prime_shape *shape,
+                                    const vsc_prime_edit *edits, uint64_t n_e, uint32_t allow_weak, vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

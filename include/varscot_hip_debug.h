@@ -81,6 +81,14 @@ int vsc_debug_site_table_ms(const vsc_ctx *ctx, double *score_ms, double *select
 int vsc_debug_bulge_hits_from_host(vsc_ctx *ctx, const vsc_bulge_hit *records, uint64_t n, vsc_bulge_hits **out);
 int vsc_debug_sites_from_host(vsc_ctx *ctx, const vsc_site *records, uint64_t n, vsc_sites **out);
 
+/* The occupancy bitmap in front of the edit search of vsc_*_prime and vsc_*_filter_prime on this context: 1 (the
+ * default) on, 0 off - every lane whose reach could hold an edit then searches.  No output bit depends on it; tools/prime_bench.py
+ * and the tests compare the two. */
+int vsc_debug_prime_bitmap(vsc_ctx *ctx, int on);
+/* The workgroups (of 4 waves) per CU that prime_rows_kernel's grid is capped at on this context: 0 = the default, 1 .. 64.
+ * The kernel is grid-stride: no output bit depends on it (tools/prime_bench.py times several against each other). */
+int vsc_debug_prime_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

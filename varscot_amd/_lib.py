@@ -374,6 +374,39 @@ class EditStats(C.Structure):
 assert C.sizeof(EditShapeStruct) == 32 and C.sizeof(EditStats) == 96 and EDIT_PAIR_DTYPE.itemsize == 16 and EDIT_TARGET_DTYPE.itemsize == 8
 
 
+PRIME_UNDEFINED = 0xFFFFFFFF  # VSC_PRIME_UNDEFINED
+PRIME_EDIT_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("del_len", "<u2"), ("ins_len", "<u2"), ("ins", "<u4")])
+PRIME_PAIR_DTYPE = np.dtype([("candidate", "<u4"), ("edit", "<u4"), ("info", "<u4"), ("ext", "<u4")])
+
+
+class PrimeShapeStruct(C.Structure):
+    """vsc_prime_shape: the site and its context behind it, the nick, the ranges of the PBS and RTT lengths, the homology behind
+    the edit, the PAM and seed ranges in read positions, the flags and the integer stability model of the PBS."""
+    _fields_ = [("site_len", C.c_uint32), ("down", C.c_uint32), ("nick", C.c_uint32), ("pbs_min", C.c_uint32), ("pbs_max", C.c_uint32),
+                ("rtt_min", C.c_uint32), ("rtt_max", C.c_uint32), ("min_homology", C.c_uint32), ("pam_start", C.c_uint32),
+                ("pam_len", C.c_uint32), ("seed_start", C.c_uint32), ("seed_len", C.c_uint32), ("flags", C.c_uint32),
+                ("init", C.c_int32), ("mono", C.c_int32 * 4), ("di", C.c_int32 * 16), ("target", C.c_int32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+class PrimeStats(C.Structure):
+    """vsc_prime_stats: the candidates of a call by class (the five counts add up to n), the candidates with a pair, the weak
+    candidates, the pairs, the pairs by flag (PAM, SEED, POLY_T, WEAK), the edits with a pair, the rows kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("with_pair", C.c_uint64), ("weak", C.c_uint64), ("pairs", C.c_uint64),
+                ("pairs_by_flag", C.c_uint64 * 4), ("edits_covered", C.c_uint64), ("score_ms", C.c_double), ("wall_ms", C.c_double),
+                ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n", "with_pair", "weak", "pairs",
+                                                "edits_covered")}
+        d.update(pairs_by_flag=[int(v) for v in self.pairs_by_flag], score_ms=float(self.score_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(PrimeShapeStruct) == 160 and C.sizeof(PrimeStats) == 128 and PRIME_PAIR_DTYPE.itemsize == 16 and PRIME_EDIT_DTYPE.itemsize == 16
+
+
 EFFECTS_UNDEFINED = 0xFFFFFFFF  # VSC_EFFECTS_UNDEFINED
 EFFECT_CLASS_NAMES = ("synonymous", "missense", "stop_gained", "stop_lost", "start_lost", "unknown")  # VSC_EFFECT_*
 CDS_SEGMENT_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("transcript", "<u4"), ("strand", "<u4"),
@@ -660,6 +693,15 @@ SYMBOLS = [
                                             C.c_uint32, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, C.c_uint32,
                                                     C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_prime_site_text", C.c_int, [C.c_char_p, C.POINTER(PrimeShapeStruct), C.c_uint32, C.c_uint32, C.c_char_p, _vp, _vp, _vp]),
+    ("vsc_loci_prime", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                 C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
+    ("vsc_guides_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                   C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
+    ("vsc_pattern_guides_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                           C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
+    ("vsc_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)
@@ -676,6 +718,8 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_site_table_ms", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("vsc_debug_bulge_hits_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_sites_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_debug_prime_bitmap", C.c_int, [_vp, C.c_int]),
+    ("vsc_debug_prime_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
 ]
 
 _lib = None

@@ -1177,6 +1177,218 @@ def edit_pick_inputs(pairs, loci, extra_columns=()):
     return lo[cand], pr["target"].astype(np.uint32), pick_key(cols, bits)
 
 
+# ---- prime-editing guide design -----------------------------------------------------------------------------
+PRIME_UNDEFINED = _lib.PRIME_UNDEFINED  # both words of the row of a candidate whose context is undefined
+PRIME_EDIT_DTYPE = _lib.PRIME_EDIT_DTYPE
+PRIME_PAIR_DTYPE = _lib.PRIME_PAIR_DTYPE
+PRIME_FLAGS = ("PAM", "SEED", "POLY_T", "WEAK")  # bit k of a pair's flags
+
+
+class PrimeShape:
+    """vsc_prime_shape: how a prime editor's pegRNA is laid out on a candidate.  site_len 16..32 is the candidates' length, down
+    the bases of context behind the site in read orientation (C = site_len + down <= 64), nick the read position the nick lies
+    in front of (17 for the SpCas9 23-mer).  pbs = (min, max) lengths of the primer binding site, 1 <= min <= max <= nick; rtt =
+    (min, max) lengths of the template, 1 <= min <= max <= C - nick; pbs max + rtt max <= 64.  min_homology: template bases
+    behind the edit.  pam / seed = (start, length 0..8) in read positions inside the site: a pair whose edit changes a letter
+    there carries the PAM / SEED flag.  avoid_g_end: lengthen the template until it does not end on G.  stability = (init,
+    mono[4], di[16], target): the integer model of the PBS, every |weight| <= 2^20 - the PBS is the shortest of pbs whose sum
+    reaches target, else pbs max and WEAK; None: all 0 (the PBS is pbs min).  validate=False passes the numbers to the library as
+    they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, down=41, nick=17, pbs=(13, 13), rtt=(10, 34), min_homology=5, pam=(21, 2), seed=(17, 3),
+                 avoid_g_end=True, stability=None, validate=True):
+        self.site_len, self.down, self.nick = int(site_len), int(down), int(nick)
+        self.pbs_min, self.pbs_max = int(pbs[0]), int(pbs[1])
+        self.rtt_min, self.rtt_max = int(rtt[0]), int(rtt[1])
+        self.min_homology = int(min_homology)
+        self.pam_start, self.pam_len = int(pam[0]), int(pam[1])
+        self.seed_start, self.seed_len = int(seed[0]), int(seed[1])
+        self.flags = int(avoid_g_end)
+        if stability is None:
+            stability = (0, (0,) * 4, (0,) * 16, 0)
+        self.init, self.target = int(stability[0]), int(stability[3])
+        self.mono, self.di = tuple(int(v) for v in stability[1]), tuple(int(v) for v in stability[2])
+        if len(self.mono) != 4 or len(self.di) != 16:
+            raise ValueError("a stability model has 4 mononucleotide and 16 dinucleotide weights")
+        if validate and not self.valid():
+            raise ValueError("a prime shape has site_len 16..32, down <= 64 - site_len, 1 <= nick <= site_len, 1 <= pbs min <= max "
+                             "<= nick, 1 <= rtt min <= max <= C - nick, pbs max + rtt max <= 64, min_homology <= rtt max, pam and "
+                             "seed ranges of at most 8 positions inside the site and weights of at most 2^20")
+
+    def valid(self):
+        C_ = self.site_len + self.down
+        w = (self.init, self.target) + self.mono + self.di
+
+        def inside(start, length):
+            return 0 <= length <= 8 and 0 <= start and start + length <= self.site_len
+        return (16 <= self.site_len <= 32 and 0 <= self.down <= 64 - self.site_len and 1 <= self.nick <= self.site_len
+                and 1 <= self.pbs_min <= self.pbs_max <= self.nick and 1 <= self.rtt_min <= self.rtt_max <= C_ - self.nick
+                and self.pbs_max + self.rtt_max <= 64 and 0 <= self.min_homology <= self.rtt_max
+                and inside(self.pam_start, self.pam_len) and inside(self.seed_start, self.seed_len) and self.flags in (0, 1)
+                and all(abs(v) <= 1 << 20 for v in w))
+
+    @property
+    def context_len(self):
+        return self.site_len + self.down
+
+    def _struct(self):
+        return _lib.PrimeShapeStruct(self.site_len, self.down, self.nick, self.pbs_min, self.pbs_max, self.rtt_min, self.rtt_max,
+                                     self.min_homology, self.pam_start, self.pam_len, self.seed_start, self.seed_len, self.flags,
+                                     self.init, (C.c_int32 * 4)(*self.mono), (C.c_int32 * 16)(*self.di), self.target,
+                                     (C.c_uint32 * 5)(0, 0, 0, 0, 0))
+
+    def __repr__(self):
+        return "PrimeShape(site_len=%d, down=%d, nick=%d, pbs=(%d, %d), rtt=(%d, %d), min_homology=%d, pam=(%d, %d), seed=(%d, %d), " \
+               "avoid_g_end=%r)" % (self.site_len, self.down, self.nick, self.pbs_min, self.pbs_max, self.rtt_min, self.rtt_max,
+                                    self.min_homology, self.pam_start, self.pam_len, self.seed_start, self.seed_len, bool(self.flags))
+
+
+# One preset for the SpCas9 23-mer (20 protospacer bases, then NGG; the nick lies three bases in front of the PAM): a 13-base
+# primer binding site, templates of 10 to 34 bases with at least 5 bases of homology behind the edit that do not end on G, the GG
+# of the PAM and the three protospacer bases next to the nick as the ranges whose change keeps the edited strand from being
+# nicked again.  These are commonly published settings for PE2 and nothing more: the best lengths depend on the target, and a
+# caller who knows better passes a PrimeShape (with a stability model, if the PBS is to be chosen by one).
+PRIME_EDITORS = {"PE2": PrimeShape(READ_LEN, 41, 17, (13, 13), (10, 34), 5, (21, 2), (17, 3), True)}
+
+
+def _prime_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in PRIME_EDITORS:
+            raise ValueError("%s names one of %s, or is a PrimeShape" % (what, ", ".join(sorted(PRIME_EDITORS))))
+        shape = PRIME_EDITORS[shape]
+    if not isinstance(shape, PrimeShape):
+        raise ValueError("%s must be a PrimeShape or the name of a preset" % what)
+    return shape
+
+
+def _prime_ins(ins):
+    """(ins_len, 2-bit code) of an insertion given as letters (or as (ins_len, code))."""
+    if isinstance(ins, (str, bytes)):
+        t = (ins.decode() if isinstance(ins, bytes) else ins).upper()
+        if t in ("", "-"):
+            return 0, 0
+        if len(t) > 16 or any(c not in "ACGT" for c in t):
+            raise ValueError("an insertion is at most 16 letters of ACGT")
+        return len(t), sum("ACGT".index(c) << (2 * k) for k, c in enumerate(t))
+    n, code = ins
+    return int(n), int(code)
+
+
+def prime_edits(rows):
+    """The edits of a prime call as the library takes them: (sorted PRIME_EDIT_DTYPE array - strictly ascending (contig, pos) -,
+    order, inverse).  order[k] is the caller's index of sorted edit k, inverse[i] the sorted index of the caller's edit i.  rows:
+    (contig, pos, del_len, ins) tuples with ins the inserted letters ("" or "-": none), or a PRIME_EDIT_DTYPE array, in any
+    order.  Two edits at one (contig, pos) are refused: several alleles of one position go into several calls."""
+    if isinstance(rows, np.ndarray) and rows.dtype == _lib.PRIME_EDIT_DTYPE:
+        e = rows.copy().reshape(-1)
+    else:
+        rows = list(rows)
+        e = np.zeros(len(rows), dtype=_lib.PRIME_EDIT_DTYPE)
+        for k, (contig, pos, del_len, ins) in enumerate(rows):
+            if not (0 <= int(contig) <= 0xFFFFFFFF and 0 <= int(pos) <= 0xFFFFFFFF and 0 <= int(del_len) <= 0xFFFF):
+                raise ValueError("an edit is (contig, pos, del_len, ins) of unsigned numbers")
+            n, code = _prime_ins(ins)
+            e[k] = (int(contig), int(pos), int(del_len), n, code)
+    key = (e["contig"].astype(np.uint64) << np.uint64(32)) | e["pos"].astype(np.uint64)
+    order = np.argsort(key, kind="stable").astype(np.int64)
+    if len(key) > 1 and (np.diff(key[order].astype(np.int64).view(np.uint64)) == 0).any():
+        raise ValueError("two edits at one (contig, pos): several alleles of one position go into several calls")
+    inverse = np.empty(len(order), dtype=np.int64)
+    inverse[order] = np.arange(len(order), dtype=np.int64)
+    return np.ascontiguousarray(e[order]), order, inverse
+
+
+def unpack_prime_info(info):
+    """(t, d, h, flags) of a prime pair's info word (or an array of them): the template's length, the bases between the nick and
+    the edit, the homology behind the edit, and the flags (bit k: PRIME_FLAGS[k])."""
+    i = np.asarray(info, dtype=np.uint32)
+    return i & np.uint32(0xFF), (i >> np.uint32(8)) & np.uint32(0xFF), (i >> np.uint32(16)) & np.uint32(0xFF), i >> np.uint32(24)
+
+
+def unpack_prime_ext(ext):
+    """(length, gc, pbs_len) of a prime pair's ext word (or an array of them): the extension's length (PBS + RTT), its G/C and
+    the length of its primer binding site."""
+    x = np.asarray(ext, dtype=np.uint32)
+    return x & np.uint32(0xFF), (x >> np.uint32(8)) & np.uint32(0xFF), x >> np.uint32(16)
+
+
+def unpack_prime_row(pbs):
+    """(pbs_len, pbs_gc, weak) of a prime row's first word (or an array of them)."""
+    x = np.asarray(pbs, dtype=np.uint32)
+    return x & np.uint32(0xFF), (x >> np.uint32(8)) & np.uint32(0xFF), (x >> np.uint32(16)) & np.uint32(1)
+
+
+def prime_site_text(context, shape, e0=None, del_len=0, ins=""):
+    """vsc_prime_site_text: one context of shape.context_len letters (any case) in read orientation on the host, by the
+    functions the kernels call - and, with e0, its pair with one edit in READ coordinates: read bases [e0, e0 + del_len) are
+    replaced by the letters `ins` (as the read strand has them).  Returns (pbs word, exists, info, ext, extension): exists is
+    False (and info = ext = 0, extension = "") without an edit, for an edit in front of the nick and for a pair the shape
+    refuses.  A letter other than ACGT or a text of another length raises VarscotError."""
+    b = context if isinstance(context, bytes) else context.encode()
+    sh = _prime_shape(shape)._struct()
+    row = (C.c_uint32 * 2)()
+    pair = (C.c_uint32 * 2)()
+    text = C.create_string_buffer(80)
+    it = None
+    if e0 is not None:
+        it = ins if isinstance(ins, bytes) else ins.encode()
+    check(lib().vsc_prime_site_text(b, C.byref(sh), 0 if e0 is None else int(e0), int(del_len), it, row, pair, text))
+    return int(row[0]), bool(row[1]), int(pair[0]), int(pair[1]), text.value.decode()
+
+
+def _revcomp_text(s):
+    return s.translate(str.maketrans("ACGTacgt", "TGCAtgca"))[::-1]
+
+
+def prime_extension(packed, shape, locus, edit, strict=True):
+    """The 3' extension of the pegRNA of one pair as DNA letters, RTT then PBS, 5' to 3' (EXTENSION): the context of `locus` =
+    (contig, pos, strand) out of a PackedGenome, the edit = (contig, pos, del_len, ins) in forward coordinates as prime_edits
+    takes it, turned into read coordinates and given to prime_site_text.  "" when the pair does not exist; strict=True raises
+    ValueError then."""
+    shape = _prime_shape(shape)
+    contig, pos, strand = int(locus[0]), int(locus[1]), int(locus[2])
+    C_ = shape.context_len
+    f0 = pos - shape.down if strand else pos
+    row = packed.contigs[contig]
+    seq = packed.decode(int(row["offset"]) + f0, C_) if 0 <= f0 and f0 + C_ <= int(row["length"]) else ""
+    n, code = _prime_ins(edit[3])
+    letters = "".join("ACGT"[(code >> (2 * k)) & 3] for k in range(n))
+    del_len = int(edit[2])
+    f = int(edit[1]) - f0
+    ok = int(edit[0]) == contig and 0 <= f and f + del_len <= C_ and len(seq) == C_ and "N" not in seq
+    text = ""
+    if ok:
+        e0 = C_ - f - del_len if strand else f
+        ctx_text = _revcomp_text(seq) if strand else seq
+        _, exists, _, _, text = prime_site_text(ctx_text, shape, e0, del_len, _revcomp_text(letters) if strand else letters)
+        ok = exists
+    if not ok and strict:
+        raise ValueError("the edit is not in reach of the candidate, or the shape refuses the pair")
+    return text if ok else ""
+
+
+def prime_pick_inputs(pairs, loci, extra_columns=()):
+    """What Genome.pick takes for "of every edit the K best pegRNAs": (loci[pairs.candidate], pairs.edit, key) - one pick
+    candidate per prime pair, its target the pair's edit, its key made with pick_key.  The first columns are: the edit changes
+    the PAM or the seed (1 bit, set is better: the edited strand is not nicked again); no poly-T terminator in the extension (1
+    bit); 255 - t (8 bits: the shorter template).  extra_columns: (values per CANDIDATE of the prime call, bits) in priority
+    order behind them - unsigned integer arrays, larger is better (pick_column makes them)."""
+    pr = np.asarray(pairs, dtype=_lib.PRIME_PAIR_DTYPE)
+    lo = _loci(loci, len(loci))
+    cand = pr["candidate"].astype(np.int64)
+    t, _, _, flags = unpack_prime_info(pr["info"])
+    cols = [((flags & np.uint32(3)) != 0).astype(np.uint64), ((flags & np.uint32(4)) == 0).astype(np.uint64),
+            np.uint64(255) - t.astype(np.uint64)]
+    bits = [1, 1, 8]
+    for values, b in extra_columns:
+        v = np.asarray(values)
+        if v.dtype.kind != "u" or v.ndim != 1 or len(v) != len(lo):
+            raise ValueError("an extra column is a one-dimensional unsigned integer array with one value per candidate")
+        cols.append(v[cand])
+        bits.append(int(b))
+    return lo[cand], pr["edit"].astype(np.uint32), pick_key(cols, bits)
+
+
 # ---- coding consequences of base edits (DESIGN 4.29) --------------------------------------------------------------------
 # CODE: 64 amino-acid letters indexed 16 b0 + 4 b1 + b2 (A C G T = 0 .. 3), '*' = stop - the standard genetic code
 GENETIC_CODE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
@@ -2079,7 +2291,8 @@ class Genome:
     def enumerate_pattern(self, pattern, protospacer, targets=None, rule="overlap", strands="both", gc=(0, 0), max_t_run=0,
                           max_guides=0, params=None, efficiency=None, min_efficiency=None, microhomology=None,
                           min_out_of_frame=None, min_microhomology=None, edit=None, edit_targets=None, min_editable=None,
-                          max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None):
+                          max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None,
+                          prime_edits=None, prime_allow_weak=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2103,7 +2316,11 @@ class Genome:
         cds= a Cds (needs edit=): the candidates' effect rows (uint32[n, 2], vsc_pattern_guides_effects) come last of all, after
         the edit rows.  edit_to= the base the editor writes (default: the transition partner of the shape's base) /
         require_effect= / forbid_effect= class names of EFFECT_CLASSES (all need cds=): only the candidates with an effect of
-        a required class and none of a forbidden one (vsc_pattern_guides_filter_effects), after the edit filter."""
+        a required class and none of a forbidden one (vsc_pattern_guides_filter_effects), after the edit filter.
+        prime= a PrimeShape whose site_len is the pattern's length: the candidates' (pbs, n_pairs) rows (uint32[n, 2],
+        vsc_pattern_guides_prime) come last of all.  prime_edits= (contig, pos, del_len, ins) rows / prime_allow_weak= (both need
+        prime=): only the candidates whose context is defined, that - with edits - can write one of them, and - with
+        prime_allow_weak=False - whose PBS is not WEAK (vsc_pattern_guides_filter_prime), after the edit and effects filters."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -2114,6 +2331,7 @@ class Genome:
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, len(p))
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, len(p))
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
+        pe = self._prime_args(prime, prime_edits, prime_allow_weak, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -2124,7 +2342,8 @@ class Genome:
                                            (L.vsc_pattern_guides_microhomology, L.vsc_pattern_guides_filter_microhomology),
                                            L.vsc_pattern_guides_free, ed,
                                            (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit), fx,
-                                           (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects))
+                                           (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects), pe,
+                                           (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -2154,7 +2373,8 @@ class Genome:
         over `targets` as a Regions under the enumeration's rule; the columns are "table" (the default; needs table=), "eff",
         "oof" and "mh".  (picks, counts) come last of all.  edit= (and its options), as enumerate_pattern takes them: only the
         survivors are searched; the edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= /
-        require_effect= / forbid_effect=: as enumerate_pattern; the effect rows come after the edit rows."""
+        require_effect= / forbid_effect=: as enumerate_pattern; the effect rows come after the edit rows.  prime= /
+        prime_edits= / prime_allow_weak=: as enumerate_pattern; the prime rows come after the effect rows."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -2269,10 +2489,10 @@ class Genome:
         return pairs
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
-                          fx=None, fx_fns=None):
+                          fx=None, fx_fns=None, pe=None, pe_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs before the edit rows before the effect rows.  held[0] is replaced as _eff_on_handle
-        replaces it."""
+        the microhomology pairs before the edit rows before the effect rows before the prime rows.  held[0] is replaced as
+        _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
         if mh is not None:
@@ -2281,6 +2501,8 @@ class Genome:
             self._edit_on_handle(held, ed, count_fn, ed_fns[0], ed_fns[1], free_fn, rows=False)
         if fx is not None:
             self._effects_on_handle(held, ed[0], fx, count_fn, fx_fns[0], fx_fns[1], free_fn, rows=False)
+        if pe is not None:
+            self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -2290,6 +2512,8 @@ class Genome:
             extra += (self._edit_on_handle(held, ed[:4] + (None,), count_fn, ed_fns[0], ed_fns[1], free_fn),)
         if fx is not None:
             extra += (self._effects_on_handle(held, ed[0], fx[:2] + (0, 0) + fx[4:], count_fn, fx_fns[0], fx_fns[1], free_fn),)
+        if pe is not None:
+            extra += (self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, filt=False),)
         return extra
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
@@ -2498,6 +2722,96 @@ class Genome:
             cov = cov[inverse]
         if order is not None:
             stats["target_order"] = order
+        return rows, pr, cov, stats
+
+    # ---- prime-editing extensions (vsc_*_prime) ---------------------------------------------------------------------------
+    @staticmethod
+    def _prime_args(shape, edits, allow_weak, site_len):
+        """(shape, sorted edits or None, order, inverse, allow_weak or None) - or None without a shape."""
+        if shape is None:
+            if edits is not None or allow_weak is not None:
+                raise ValueError("prime_edits / prime_allow_weak need prime=shape")
+            return None
+        shape = _prime_shape(shape, "prime")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        ed = order = inverse = None
+        if edits is not None:
+            ed, order, inverse = prime_edits(edits)
+        return shape, ed, order, inverse, None if allow_weak is None else bool(allow_weak)
+
+    def _prime_on_handle(self, held, pe, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _edit_on_handle, for the prime rows: pe = what _prime_args returned.  With edits or prime_allow_weak the handle
+        is first replaced by the filter's result (filt); the rows of the survivors come back as uint32[n, 2]."""
+        shape, ed, _, _, allow_weak = pe
+        sh = shape._struct()
+        n_e = 0 if ed is None else len(ed)
+        ep = ptr(ed) if n_e else None
+        if filt and (ed is not None or allow_weak is not None):
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), ep, n_e, 1 if allow_weak in (None, True) else 0, C.byref(out)),
+                  self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        r = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.PrimeStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), ep, n_e, ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return r
+
+    def prime(self, loci_or_found, shape, edits=None, pairs=True, coverage=False, allow_partial=False):
+        """vsc_loci_prime: the pegRNA extensions of candidates under a PrimeShape (or the name of a preset of PRIME_EDITORS) for
+        a list of wanted edits, on the device from the resident planes.  Returns (rows, pairs, coverage, stats).
+        rows uint32[n, 2]: (pbs, n_pairs) per candidate - unpack_prime_row gives pbs_len, pbs_gc and WEAK, n_pairs is the number
+        of edits the candidate can write; (PRIME_UNDEFINED, PRIME_UNDEFINED) where the context is undefined.  edits: (contig,
+        pos, del_len, ins) rows or a PRIME_EDIT_DTYPE array in any order (prime_edits sorts them and refuses two at one
+        position); None: no edits, n_pairs = 0.  pairs (PRIME_PAIR_DTYPE; None with pairs=False or without edits): candidate,
+        edit (the index in the CALLER's array), info (unpack_prime_info: t, d, h, flags), ext (unpack_prime_ext: length, gc,
+        pbs_len) - in ascending (candidate, edit).  coverage (uint32[len(edits), 2] in the caller's order with coverage=True,
+        else None): pairs of the edit, smallest t among them (PRIME_UNDEFINED: no pair).  stats: the candidates by class,
+        with_pair, weak, pairs, pairs_by_flag, edits_covered, score_ms, wall_ms and edit_order (the caller's index of every
+        sorted edit).  loci_or_found: as Genome.efficiency takes it.  Raises when a context is not resident on this object (a
+        shard) unless allow_partial=True."""
+        shape = _prime_shape(shape)
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        ed = order = inverse = None
+        if edits is not None:
+            ed, order, inverse = prime_edits(edits)
+        n_e = 0 if ed is None else len(ed)
+        ep = ptr(ed) if n_e else None
+        rows = np.empty((n, 2), dtype=np.uint32)
+        cov = np.empty((n_e, 2), dtype=np.uint32) if coverage and ed is not None else None
+        want_pairs = bool(pairs) and ed is not None
+        cap = min(max(n, 1024), 1 << 22) if want_pairs else 0
+        pr = np.empty(cap, dtype=_lib.PRIME_PAIR_DTYPE) if want_pairs else None
+        st = _lib.PrimeStats()
+        sh = shape._struct()
+        count = C.c_uint64()
+        L = lib()
+        rc = L.vsc_loci_prime(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), ep, n_e, ptr(rows), ptr(pr), cap, C.byref(count), ptr(cov),
+                              C.byref(st))
+        if rc == _lib.VSC_ERR_RANGE and want_pairs and cap < int(count.value) <= 0xFFFFFFFE:
+            # (the rows, the coverage and the stats of the first call stand; the second brings the pairs alone)
+            cap = int(count.value)
+            pr = np.empty(cap, dtype=_lib.PRIME_PAIR_DTYPE)
+            check(L.vsc_loci_prime(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), ep, n_e, None, ptr(pr), cap, C.byref(count), None, None),
+                  self.ctx._h)
+        else:
+            check(rc, self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        if want_pairs:
+            pr = pr[:int(count.value)].copy()
+            pr["edit"] = order[pr["edit"].astype(np.int64)].astype(np.uint32)
+            pr = pr[np.lexsort((pr["edit"], pr["candidate"]))]
+        if cov is not None:
+            cov = cov[inverse]
+        if order is not None:
+            stats["edit_order"] = order
         return rows, pr, cov, stats
 
     def pick(self, loci_or_found, key, shape, regions=None, groups=None, target=None, n_targets=None, rank=False):
@@ -2724,7 +3038,7 @@ class Genome:
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
                          min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None, cds=None,
-                         edit_to=None, require_effect=None, forbid_effect=None):
+                         edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2747,18 +3061,24 @@ class Genome:
         cds= a Cds (needs edit=): the candidates' effect rows (uint32[n, 2], vsc_guides_effects) come last of all, after the
         edit rows.  edit_to= the base the editor writes (default: EDITOR_TO of a preset, else the transition partner of the
         shape's base) / require_effect= / forbid_effect= class names of EFFECT_CLASSES (all need cds=): only the candidates
-        with an effect of a required class and none of a forbidden one (vsc_guides_filter_effects), after the edit filter."""
+        with an effect of a required class and none of a forbidden one (vsc_guides_filter_effects), after the edit filter.
+        prime= a PrimeShape with site_len 23 or the name of a preset of PRIME_EDITORS: the candidates' (pbs, n_pairs) rows
+        (uint32[n, 2], vsc_guides_prime) come last of all.  prime_edits= (contig, pos, del_len, ins) rows in any order /
+        prime_allow_weak= (both need prime=): only the candidates whose context is defined, that - with edits - can write one of
+        them, and - with prime_allow_weak=False - whose PBS is not WEAK (vsc_guides_filter_prime), after the edit and effects
+        filters."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
         mh = self._mh_args(microhomology, min_out_of_frame, min_microhomology, READ_LEN)
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, READ_LEN)
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
+        pe = self._prime_args(prime, prime_edits, prime_allow_weak, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None:
+        if efficiency is None and mh is None and ed is None and pe is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -2766,7 +3086,8 @@ class Genome:
                                            (L.vsc_guides_efficiency, L.vsc_guides_filter_efficiency),
                                            (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free,
                                            ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit), fx,
-                                           (L.vsc_guides_effects, L.vsc_guides_filter_effects))
+                                           (L.vsc_guides_effects, L.vsc_guides_filter_effects), pe,
+                                           (L.vsc_guides_prime, L.vsc_guides_filter_prime))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -2799,7 +3120,8 @@ class Genome:
     def design(self, regions, max_mismatches, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, labels=False,
                efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
                pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
-               cds=None, edit_to=None, require_effect=None, forbid_effect=None, **search_options):
+               cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
+               **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -2815,7 +3137,8 @@ class Genome:
         not given is refused.  (picks, counts) come last of all.  Without pick= nothing changes.
         edit= / edit_targets= / min_editable= / max_editable=: as enumerate_guides; only the survivors are searched, and the
         edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= / require_effect= /
-        forbid_effect=: as enumerate_guides; the effect rows come after the edit rows."""
+        forbid_effect=: as enumerate_guides; the effect rows come after the edit rows.  prime= / prime_edits= /
+        prime_allow_weak=: as enumerate_guides; the prime rows come after the effect rows, before (picks, counts)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -2823,7 +3146,8 @@ class Genome:
                                       microhomology=microhomology, min_out_of_frame=min_out_of_frame,
                                       min_microhomology=min_microhomology, edit=edit, edit_targets=edit_targets,
                                       min_editable=min_editable, max_editable=max_editable, cds=cds, edit_to=edit_to,
-                                      require_effect=require_effect, forbid_effect=forbid_effect)
+                                      require_effect=require_effect, forbid_effect=forbid_effect, prime=prime,
+                                      prime_edits=prime_edits, prime_allow_weak=prime_allow_weak)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])

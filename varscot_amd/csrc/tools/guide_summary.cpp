@@ -115,6 +115,11 @@
 // and -l MIN,MAX (both need -x) keep only the candidates that reach a target base / hold MIN .. MAX editable bases
 // (vsc_guides_filter_edit), BEFORE the off-target search; -o pairs.tsv (needs -z) lists the pairs.  Without -Y every
 // output is what it was.
+// --prime PE2 | SPEC (needs -E, one device) looks at the pegRNA a PRIME EDITOR needs on every found guide (vsc_guides_prime,
+// DESIGN 4.30; tools/prime_host.hpp): the candidates without a context (or, without --prime-allow-weak, with a WEAK primer binding
+// site) are dropped BEFORE the off-target search (vsc_guides_filter_prime), with --prime-edits edits.tsv those that can write none
+// of the edits as well; the -L listing gains the last columns pbsLen pbsGC primePairs; --prime-out pairs.tsv (needs --prime-edits)
+// lists the pairs with their extensions.  Without --prime every output is what it was.
 // -k K[,SPACING] [-b COLS] [-c interval|name] (needs -E and -L, one device) picks the K best guides of every -E target, their cut
 // sites at least SPACING bases apart (vsc_guides_pick; tools/pick_host.hpp makes the key from mit, table, eff, oof, mh
 // in the order of -b): the -L listing, written after the search whose rows rank the guides, gains the last columns pickTarget
@@ -132,6 +137,7 @@
 #include "mh_host.hpp"
 #include "edit_host.hpp"
 #include "effects_host.hpp"
+#include "prime_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
@@ -211,6 +217,14 @@ int main(int argc, char **argv)
         {'f', "effect-filter", "With --cds: REQUIRE[/FORBID], class names joined by + (synonymous missense stop_gained stop_lost start_lost "
                                "unknown): keep only the candidates with an effect of a REQUIRE class and none of a FORBID class", false},
         {'Q', "effects", "With --cds: path to the listing of the effects: #guideId transcript codon ref alt refAA altAA class at", false},
+        {'3', "prime", "With -E: PE2 | NICK,DOWN,PBSMIN,PBSMAX,RTTMIN,RTTMAX,HOMOLOGY,PAMSTART,PAMLEN,SEEDSTART,SEEDLEN,AVOIDG: the prime editor's "
+                       "shape; only the candidates with a defined context are kept, and the guide listing gains the last columns pbsLen pbsGC "
+                       "primePairs (one device)", false},
+        {'4', "prime-edits", "With --prime: path to the wanted edits (.tsv/.txt: chrom pos ref-length alt-letters-or--): only the candidates that "
+                             "can write one of them are kept", false},
+        {'5', "prime-allow-weak", "With --prime: keep the candidates whose primer binding site is WEAK", false, false},
+        {'6', "prime-out", "With --prime-edits: path to the listing of the pairs: #chrom pos guideId pbsLen rttLen nickToEdit homology flags "
+                           "extension", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -608,6 +622,17 @@ int main(int argc, char **argv)
     }
     CdsOfFile coding;
 
+    // --prime / --prime-edits / --prime-allow-weak / --prime-out: the pegRNA extensions of the found guides
+    PrimeOptions prime;
+    {
+        const std::string why = parse_prime_options(opts[50].set, opts[50].value, opts[51].set, opts[51].value, opts[52].set, opts[53].set,
+                                                    opts[53].value, discover, devices.size() != 1, (uint32_t)VSC_READ_LEN, &prime);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -780,6 +805,16 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_prime_edit> prime_edits;
+            if (prime.with_edits) prime_edits = read_prime_edits(prime.edits_path, ix.names);
+            if (prime.on) {  // --prime: the same for the prime editor's FILTER, after the editor's and the effects'
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_prime(ctx, genome, found, &prime.shape, prime_edits.empty() ? nullptr : prime_edits.data(), prime_edits.size(),
+                                            prime.allow_weak, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -802,6 +837,14 @@ int main(int argc, char **argv)
                     if (vsc_guides_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, r, e, cap, ne, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &fx_rows, &fx_records);
+            std::vector<uint32_t> prime_rows;  // --prime: the (pbs, n_pairs) rows, and with --prime-out the pairs
+            std::vector<vsc_prime_pair> prime_pairs;
+            if (prime.on)
+                prime_rows_and_pairs(prime, vsc_guides_count(found), [&](uint32_t *r, vsc_prime_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_guides_prime(ctx, genome, found, &prime.shape, prime_edits.empty() ? nullptr : prime_edits.data(), prime_edits.size(), r, pp,
+                                         cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &prime_rows, &prime_pairs);
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -827,7 +870,7 @@ int main(int argc, char **argv)
                             (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
                     const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
-                                             (fx.on ? effects_columns(&fx_rows[2 * i]) : "");
+                                             (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "");
                     if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
                     else bed6 += line + ecol + '\n';
                 }
@@ -841,6 +884,7 @@ int main(int argc, char **argv)
             }
             if (edit.with_pairs) write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
             if (fx.with_listing) write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
+            if (prime.with_pairs) write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, loci, ix, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');

@@ -42,6 +42,11 @@
 // (vsc_pattern_guides_edit): the -E listing gains the last columns editWindow editable targetsHit.  -z targets.bed (one base per
 // line) and -l MIN,MAX (both need -x) keep only the candidates that reach a target base / hold MIN .. MAX editable bases, BEFORE
 // the search; -o pairs.tsv (needs -z) lists the pairs.
+// --prime SPEC (needs -E; PE2 for a pattern of 23 letters; SPEC = twelve numbers, tools/prime_host.hpp) looks at the pegRNA a PRIME
+// EDITOR needs on every found guide (vsc_pattern_guides_prime): the candidates without a context (or, without
+// --prime-allow-weak, with a WEAK primer binding site) are dropped BEFORE the search, with --prime-edits edits.tsv those that can
+// write none of the edits as well; the -E listing gains the last columns pbsLen pbsGC primePairs; --prime-out pairs.tsv (needs
+// --prime-edits) lists the pairs with their extensions.
 // -W table.tsv scores every hit with a pattern TABLE (vsc_search_pattern_table; the CFD form for any nuclease: a product of
 // weights by protospacer position, guide base and site base times a weight for the site's letters at up to four PAM positions;
 // the file is what varscot_amd.PatternTable.to_tsv writes, tools/README.md: `shape L ps_start ps_len`, `pam_pos p...`,
@@ -68,6 +73,7 @@
 #include "mh_host.hpp"
 #include "edit_host.hpp"
 #include "effects_host.hpp"
+#include "prime_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
 
@@ -258,6 +264,14 @@ int main(int argc, char **argv)
         {'f', "effect-filter", "With --cds: REQUIRE[/FORBID], class names joined by + (synonymous missense stop_gained stop_lost start_lost "
                                "unknown): keep only the candidates with an effect of a REQUIRE class and none of a FORBID class", false},
         {'Q', "effects", "With --cds: path to the listing of the effects: #guideId transcript codon ref alt refAA altAA class at", false},
+        {'3', "prime", "With -E: NICK,DOWN,PBSMIN,PBSMAX,RTTMIN,RTTMAX,HOMOLOGY,PAMSTART,PAMLEN,SEEDSTART,SEEDLEN,AVOIDG (or PE2 for sites of 23 "
+                       "bases): the prime editor's shape; only the candidates with a defined context are kept, and the -E listing gains the last "
+                       "columns pbsLen pbsGC primePairs", false},
+        {'4', "prime-edits", "With --prime: path to the wanted edits (.tsv/.txt: chrom pos ref-length alt-letters-or--): only the candidates that "
+                             "can write one of them are kept", false},
+        {'5', "prime-allow-weak", "With --prime: keep the candidates whose primer binding site is WEAK", false, false},
+        {'6', "prime-out", "With --prime-edits: path to the listing of the pairs: #chrom pos guideId pbsLen rttLen nickToEdit homology flags "
+                           "extension", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -483,6 +497,17 @@ int main(int argc, char **argv)
         }
     }
     CdsOfFile coding;
+    // --prime / --prime-edits / --prime-allow-weak / --prime-out: the pegRNA extensions of the found guides
+    PrimeOptions prime;
+    {
+        const std::string why = parse_prime_options(opts[38].set, opts[38].value, opts[39].set, opts[39].value, opts[40].set, opts[41].set,
+                                                    opts[41].value, enumerate, opts[4].value.find(',') != std::string::npos,
+                                                    (uint32_t)pattern.size(), &prime);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     // -k / -b / -c: the best guides of every -B target
@@ -667,6 +692,16 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_prime_edit> prime_edits;
+            if (prime.with_edits) prime_edits = read_prime_edits(prime.edits_path, ix.names);
+            if (prime.on) {  // --prime: the same for the prime editor's FILTER, after the editor's and the effects'
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_prime(ctx, genome, found, &prime.shape, prime_edits.empty() ? nullptr : prime_edits.data(),
+                                                    prime_edits.size(), prime.allow_weak, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -689,6 +724,14 @@ int main(int argc, char **argv)
                     if (vsc_pattern_guides_effects(ctx, genome, found, &edit.shape, fx.to, coding.cds, nullptr, r, e, cap, ne, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &fx_rows, &fx_records);
+            std::vector<uint32_t> prime_rows;  // --prime: the (pbs, n_pairs) rows, and with --prime-out the pairs
+            std::vector<vsc_prime_pair> prime_pairs;
+            if (prime.on)
+                prime_rows_and_pairs(prime, vsc_pattern_guides_count(found), [&](uint32_t *r, vsc_prime_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_pattern_guides_prime(ctx, genome, found, &prime.shape, prime_edits.empty() ? nullptr : prime_edits.data(),
+                                                 prime_edits.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &prime_rows, &prime_pairs);
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -698,7 +741,7 @@ int main(int argc, char **argv)
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
             out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
                 << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "")
-                << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << '\n';
+                << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << (prime.on ? "\tpbsLen\tpbsGC\tprimePairs" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -724,6 +767,7 @@ int main(int argc, char **argv)
                     ecol = edit_columns(edit.shape, std::string(own, len), &edit_rows[2 * i]);
                 }
                 if (fx.on) ecol += effects_columns(&fx_rows[2 * i]);
+                if (prime.on) ecol += prime_columns(&prime_rows[2 * i]);
                 if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
                 else out << line << ecol << '\n';
             }
@@ -736,6 +780,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
+            }
+            if (prime.with_pairs) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, std::vector<vsc_locus>(loci, loci + n), ix, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

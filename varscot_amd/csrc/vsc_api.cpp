@@ -14,6 +14,7 @@
 //   vsc_efficiency.hip     on-target efficiency of candidates
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
 //   vsc_edit.hip           base-editor windows of candidates and their join with targets
+//   vsc_prime.hip          prime-editing extensions of candidates and their join with edits
 //   vsc_pick.hip           the best K candidates per target, with spacing
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
@@ -5368,6 +5369,427 @@ int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_p
                                    vsc_pattern_guides **out)
 {
     return edit_filter(ctx, genome, in, shape, targets, n_t, false, min_editable, max_editable, out, "vsc_pattern_guides_filter_edit");
+}
+
+}  // extern "C"
+
+// ---- prime-editing guide design (the definition: vsc_prime.h, the kernels: vsc_prime.hip) ---------------------
+namespace {
+
+const char *const kPrimeShapeRule =
+    "site_len 16 .. 32, down <= 64 - site_len, 1 <= nick <= site_len, 1 <= pbs_min <= pbs_max <= nick, 1 <= rtt_min <= rtt_max <= C - nick, "
+    "pbs_max + rtt_max <= 64, min_homology <= rtt_max, pam and seed ranges inside the site with len <= 8, flags <= 1, |weights| <= 2^20, reserved fields 0";
+
+bool prime_shape_in(const vsc_prime_shape *shape, PrimeShape &s)
+{
+    s = PrimeShape{};
+    s.site_len = shape->site_len;
+    s.down = shape->down;
+    s.nick = shape->nick;
+    s.pbs_min = shape->pbs_min;
+    s.pbs_max = shape->pbs_max;
+    s.rtt_min = shape->rtt_min;
+    s.rtt_max = shape->rtt_max;
+    s.min_homology = shape->min_homology;
+    s.pam_start = shape->pam_start;
+    s.pam_len = shape->pam_len;
+    s.seed_start = shape->seed_start;
+    s.seed_len = shape->seed_len;
+    s.flags = shape->flags;
+    s.init = shape->init;
+    for (int k = 0; k < 4; ++k) s.mono[k] = shape->mono[k];
+    for (int k = 0; k < 16; ++k) s.di[k] = shape->di[k];
+    s.target = shape->target;
+    for (uint32_t r : shape->reserved)
+        if (r) return false;
+    return prime_shape_valid(s);
+}
+
+// the edits of a call as the kernels hold them, on the host
+struct PrimeHostEdits {
+    std::vector<uint32_t> gpos;
+    std::vector<PrimeEdit> rec;
+    std::vector<uint32_t> bitmap;  // one bit per cell of 2^kPrimeCellShift global positions, over the whole genome
+};
+
+// The shape, the genome and the edits of a prime call, checked on the host.
+int prime_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e, PrimeShape &s,
+                PrimeHostEdits &h, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!prime_shape_in(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kPrimeShapeRule);
+    if (n_e && !edits) return fail_in(ctx, VSC_ERR_INVALID, who, "edits are null with n_e > 0");
+    if (n_e > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE edits");
+    h.gpos.resize((size_t)n_e);
+    h.rec.resize((size_t)n_e);
+    uint32_t genome_end = 0;
+    for (uint32_t end : genome->h_contig_end) genome_end = end > genome_end ? end : genome_end;
+    if (n_e) h.bitmap.assign(((size_t)(genome_end >> kPrimeCellShift) + 32) / 32, 0u);
+    for (uint64_t k = 0; k < n_e; ++k) {
+        const vsc_prime_edit &e = edits[k];
+        if (e.contig >= genome->n_contigs || e.contig >= genome->h_contig_off.size())
+            return fail_in(ctx, VSC_ERR_INVALID, who, "an edit lies on an unknown contig");
+        const uint32_t off = genome->h_contig_off[e.contig], len = genome->h_contig_end[e.contig] - off;
+        if (e.del_len > kPrimeMaxIndel || e.ins_len > kPrimeMaxIndel) return fail_in(ctx, VSC_ERR_INVALID, who, "an edit's del_len or ins_len is above 16");
+        if (e.del_len + e.ins_len < 1) return fail_in(ctx, VSC_ERR_INVALID, who, "an edit's del_len and ins_len are both 0");
+        const PrimeEdit rec{e.contig, e.pos, (uint32_t)e.del_len | (uint32_t)e.ins_len << 16, e.ins};
+        if (e.pos > len || e.del_len > len - e.pos) return fail_in(ctx, VSC_ERR_INVALID, who, "an edit reaches beyond its contig");
+        if (!prime_edit_valid(rec, len)) return fail_in(ctx, VSC_ERR_INVALID, who, "an edit's ins has bits above its ins_len letters");
+        if (k && !(edits[k - 1].contig < e.contig || (edits[k - 1].contig == e.contig && edits[k - 1].pos < e.pos)))
+            return fail_in(ctx, VSC_ERR_INVALID, who, "the edits are not strictly ascending by (contig, pos)");
+        const uint32_t gp = off + e.pos, cell = gp >> kPrimeCellShift;
+        h.gpos[k] = gp;
+        h.rec[k] = rec;
+        h.bitmap[cell >> 5] |= 1u << (cell & 31u);
+    }
+    return VSC_OK;
+}
+
+// the edits at the front of edit_tabs: [global positions][entries][bitmap]; `more` bytes behind them (256-byte aligned) for the caller
+int prime_upload_edits(vsc_ctx *ctx, const PrimeHostEdits &h, size_t more, PrimeEdits &e, char **behind)
+{
+    const size_t n = h.gpos.size();
+    const size_t g_bytes = round256(n * sizeof(uint32_t) + 4), r_bytes = round256(n * sizeof(PrimeEdit) + 4);
+    const size_t b_bytes = round256(h.bitmap.size() * sizeof(uint32_t) + 4);
+    VSC_HIP(ctx, ctx->edit_tabs.ensure(g_bytes + r_bytes + b_bytes + more));
+    char *base = (char *)ctx->edit_tabs.p;
+    if (n) {
+        VSC_HIP(ctx, hipMemcpyAsync(base, h.gpos.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + g_bytes, h.rec.data(), n * sizeof(PrimeEdit), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + g_bytes + r_bytes, h.bitmap.data(), h.bitmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    }
+    e = PrimeEdits{(const uint32_t *)base, (const PrimeEdit *)(base + g_bytes),
+                   n && ctx->prime_bitmap ? (const uint32_t *)(base + g_bytes + r_bytes) : nullptr, (uint32_t)n};
+    if (behind) *behind = base + g_bytes + r_bytes + b_bytes;
+    return VSC_OK;
+}
+
+// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): prime_rows_kernel,
+// then - with edits - the pairs' count pass over the rows, the scan, one 8-byte read-back (the pairs) and the write pass.
+int prime_run(vsc_ctx *ctx, const vsc_genome *genome, const PrimeShape &shape, const PrimeHostEdits &h, const void *d_loci, const vsc_locus *h_loci,
+              uint64_t n, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats,
+              const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_e = h.gpos.size();
+    if (stats) *stats = vsc_prime_stats{};
+    if (n_pairs) *n_pairs = 0;
+    if (coverage)
+        for (size_t k = 0; k < n_e; ++k) {
+            coverage[2 * k] = 0;
+            coverage[2 * k + 1] = kPrimeUndefined;
+        }
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
+    // edit_tabs behind the edits: [pairs per edit][smallest t per edit][pairs per tile][offsets per tile][pairs by flag]
+    const size_t cov_bytes = round256(n_e * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
+    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long)), flag_bytes = 256;
+    PrimeArgs a{};
+    char *tabs = nullptr;
+    const int urc = prime_upload_edits(ctx, h, 2 * cov_bytes + count_bytes + off_bytes + flag_bytes, a.edits, &tabs);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n = n;
+    const size_t head = 256;  // the counters, in front of the rows
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_prime_rows(a, ctx->n_cus, ctx->prime_groups_per_cu, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kPrimeCounts] = {};
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    PrimePairArgs p{};
+    unsigned long long total = 0;
+    float pass_ms = 0;
+    if (n_e) {
+        p.g = a.g;
+        p.shape = shape;
+        p.edits = a.edits;
+        p.loci = a.loci;
+        p.rows = a.out;
+        p.n = n;
+        p.n_work = tiles;
+        p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
+        unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
+        p.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_prime_pairs(p, false, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (n_e) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+    if (n_pairs) *n_pairs = total;
+    const bool too_many = total > kPrimeMaxCount, write = pairs && total && total <= capacity && !too_many, cover = total && (coverage || stats);
+    uint64_t covered = 0;
+    unsigned long long by_flag[kPrimeFlags] = {};
+    if (write || cover) {
+        if (write) {
+            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_prime_pair)));
+            p.pairs = (uint4 *)ctx->edit_pairs.p;
+        }
+        if (cover) {
+            p.cov_count = (uint32_t *)tabs;
+            p.cov_min = (uint32_t *)(tabs + cov_bytes);
+            p.flag_count = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes + off_bytes);
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_e * sizeof(uint32_t), ctx->stream));
+            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_e * sizeof(uint32_t), ctx->stream));
+            VSC_HIP(ctx, hipMemsetAsync(p.flag_count, 0, flag_bytes, ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_prime_pairs(p, true, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        std::vector<uint32_t> cov;
+        unsigned long long d_covered = 0;
+        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_prime_pair), hipMemcpyDeviceToHost, ctx->stream));
+        if (cover) VSC_HIP(ctx, hipMemcpyAsync(by_flag, p.flag_count, sizeof by_flag, hipMemcpyDeviceToHost, ctx->stream));
+        if (cover && !coverage) {  // the stats alone: the covered edits are counted where they lie, 8 bytes come back
+            unsigned long long *slot = a.stats + kPrimeCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
+            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_e, slot, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (cover) {
+            cov.resize(2 * n_e);
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_e * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_e, p.cov_min, n_e * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float wms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        pass_ms += wms;
+        covered = d_covered;
+        for (size_t k = 0; coverage && k < n_e; ++k) {
+            covered += cov[k] != 0;
+            coverage[2 * k] = cov[k];
+            coverage[2 * k + 1] = cov[n_e + k];
+        }
+    }
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+        stats->with_pair = seen[kEffClasses];
+        stats->weak = seen[kEffClasses + 1];
+        stats->pairs = total;
+        for (uint32_t b = 0; b < kPrimeFlags; ++b) stats->pairs_by_flag[b] = by_flag[b];
+        stats->edits_covered = covered;
+        stats->score_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    t.score_ms = ms;
+    t.scan_ms = pass_ms;
+    t.total_ms = t.score_ms + t.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
+    ctx->timing = t;
+    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
+    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
+    return VSC_OK;
+}
+
+// vsc_guides_prime / vsc_pattern_guides_prime: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int prime_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
+                 bool need_23, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+                 vsc_prime_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    PrimeShape s{};
+    PrimeHostEdits h;
+    const int rc = prime_check(ctx, genome, shape, edits, n_e, s, h, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (guides->n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const bool dev = guides->ctx != nullptr;
+    return prime_run(ctx, genome, s, h, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
+                     guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_prime / vsc_pattern_guides_filter_prime: run_enumeration's two passes over tiles of kEditTile candidates of
+// `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+template <class Guides>
+int prime_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
+                 bool need_23, uint32_t allow_weak, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    PrimeShape s{};
+    PrimeHostEdits h;
+    const int rc = prime_check(ctx, genome, shape, edits, n_e, s, h, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    const uint64_t n = in->n;
+    if (n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    PrimeFilterArgs a{};
+    const int urc = prime_upload_edits(ctx, h, 0, a.edits, nullptr);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.n = n;
+    a.allow_weak = allow_weak ? 1u : 0u;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    if (n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the edits are this call's vectors)
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_prime_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_prime_bitmap(vsc_ctx *ctx, int on)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    ctx->prime_bitmap = on != 0;
+    return VSC_OK;
+}
+
+int vsc_debug_prime_groups_per_cu(vsc_ctx *ctx, uint32_t groups)
+{
+    if (!ctx || groups > kPrimeMaxGroupsPerCu) return VSC_ERR_INVALID;
+    ctx->prime_groups_per_cu = groups;
+    return VSC_OK;
+}
+
+int vsc_prime_site_text(const char *context, const vsc_prime_shape *shape, uint32_t e0, uint32_t del_len, const char *ins, uint32_t *row,
+                        uint32_t *pair, char *extension)
+{
+    if (!context || !shape || !row) return VSC_ERR_INVALID;
+    PrimeShape s{};
+    if (!prime_shape_in(shape, s)) return VSC_ERR_INVALID;
+    const uint32_t C = prime_context_len(s);
+    if (strnlen(context, C + 1) != C) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    for (uint32_t j = 0; j < C; ++j) {
+        const int b = base_code(context[j]);
+        if (b > 3) return VSC_ERR_INVALID;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+    }
+    PrimeEdit e{0u, 0u, 0u, 0u};
+    if (ins) {
+        const size_t ins_len = strnlen(ins, kPrimeMaxIndel + 1);
+        if (ins_len > kPrimeMaxIndel || del_len > kPrimeMaxIndel || del_len + ins_len < 1 || e0 > C || del_len > C - e0) return VSC_ERR_INVALID;
+        for (size_t k = 0; k < ins_len; ++k) {
+            const int b = base_code(ins[k]);
+            if (b > 3) return VSC_ERR_INVALID;
+            e.ins |= (uint32_t)b << (2 * k);
+        }
+        e.lens = del_len | (uint32_t)ins_len << 16;
+    }
+    row[0] = prime_pbs(ch, cl, s, s.mono, s.di);
+    row[1] = 0;
+    if (pair) pair[0] = pair[1] = 0;
+    if (extension) extension[0] = 0;
+    uint32_t info = 0, ext = 0;
+    uint64_t eh = 0, el = 0;
+    if (!ins || !prime_pair(s, ch, cl, 0u, row[0], e0, e, &info, &ext, &eh, &el)) return VSC_OK;
+    row[1] = 1;
+    if (pair) {
+        pair[0] = info;
+        pair[1] = ext;
+    }
+    if (extension) {
+        const uint32_t lo = s.nick - (ext >> 16 & 0xFFu), hi = s.nick + (info & 0xFFu);
+        uint32_t o = 0;
+        for (uint32_t q = hi; q-- > lo;) extension[o++] = "TGCA"[(eh >> q & 1u) << 1 | (el >> q & 1u)];
+        extension[o] = 0;
+    }
+    return VSC_OK;
+}
+
+int vsc_loci_prime(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_prime_shape *shape,
+                   const vsc_prime_edit *edits, uint64_t n_e, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                   uint32_t *coverage, vsc_prime_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_prime";
+    PrimeShape s{};
+    PrimeHostEdits h;
+    const int rc = prime_check(ctx, genome, shape, edits, n_e, s, h, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return prime_run(ctx, genome, s, h, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_prime_shape *shape, const vsc_prime_edit *edits,
+                     uint64_t n_e, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+                     vsc_prime_stats *stats)
+{
+    return prime_guides(ctx, genome, guides, shape, edits, n_e, true, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_guides_prime");
+}
+
+int vsc_pattern_guides_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_prime_shape *shape,
+                             const vsc_prime_edit *edits, uint64_t n_e, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity,
+                             uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats)
+{
+    return prime_guides(ctx, genome, guides, shape, edits, n_e, false, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_pattern_guides_prime");
+}
+
+int vsc_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_prime_shape *shape, const vsc_prime_edit *edits,
+                            uint64_t n_e, uint32_t allow_weak, vsc_guides **out)
+{
+    return prime_filter(ctx, genome, in, shape, edits, n_e, true, allow_weak, out, "vsc_guides_filter_prime");
+}
+
+int vsc_pattern_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_prime_shape *shape,
+                                    const vsc_prime_edit *edits, uint64_t n_e, uint32_t allow_weak, vsc_pattern_guides **out)
+{
+    return prime_filter(ctx, genome, in, shape, edits, n_e, false, allow_weak, out, "vsc_pattern_guides_filter_prime");
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "vsc_efficiency.h"
 #include "vsc_mh.h"
 #include "vsc_edit.h"
+#include "vsc_prime.h"
 #include "vsc_effects.h"
 
 namespace vsc {
@@ -644,6 +645,53 @@ hipError_t launch_edit_pairs(const EditPairArgs &args, bool write, hipStream_t s
 hipError_t launch_edit_filter(const EditFilterArgs &args, bool write, hipStream_t stream);
 // *out (zeroed) += the entries of cov_count that are not 0
 hipError_t launch_edit_covered(const uint32_t *cov_count, uint32_t n_t, unsigned long long *out, int n_cus, hipStream_t stream);
+// vsc_prime.hip (the definition: vsc_prime.h)
+// the rows kernel's counters: the classes, the candidates with a pair, the weak candidates
+constexpr uint32_t kPrimeCounts = kEffClasses + 2;
+struct PrimeArgs {
+    EffPlanes g;
+    PrimeShape shape;
+    PrimeEdits edits;             // n == 0: no edits, n_pairs = 0
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: (pbs, n_pairs), kPrimeUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kPrimeCounts], zeroed before the launch: the kernel adds its candidates per counter
+};
+// the pairs' and the filter's two passes: tile i = candidates [i * kEditTile, ..)
+struct PrimePairArgs {
+    EffPlanes g;
+    PrimeShape shape;
+    PrimeEdits edits;
+    const uint4 *loci;            // [n]
+    const uint2 *rows;            // [n] what prime_rows_kernel left
+    unsigned long long n;
+    uint32_t n_work;              // tiles
+    uint32_t *tile_count;         // count pass out: pairs per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    uint4 *pairs;                 // write pass out (null: coverage and flag counts only)
+    uint32_t *cov_count, *cov_min;  // [edits.n] each, write pass: pairs and smallest t per edit, 0 / 0xFFFFFFFF before the launch; null: none
+    unsigned long long *flag_count;  // [kPrimeFlags], zeroed before the launch: the write pass adds its pairs per flag; null: none
+};
+struct PrimeFilterArgs {
+    EffPlanes g;
+    PrimeShape shape;
+    PrimeEdits edits;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    uint32_t allow_weak;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+// groups_per_cu: workgroups per CU the rows kernel's grid is capped at (0: the default, kPrimeGroupsPerCu)
+hipError_t launch_prime_rows(const PrimeArgs &args, int n_cus, uint32_t groups_per_cu, hipStream_t stream);
+hipError_t launch_prime_pairs(const PrimePairArgs &args, bool write, hipStream_t stream);
+hipError_t launch_prime_filter(const PrimeFilterArgs &args, bool write, hipStream_t stream);
+constexpr uint32_t kPrimeGroupsPerCu = 28, kPrimeMaxGroupsPerCu = 64;
 // vsc_effects.hip (the definition: vsc_effects.h)
 constexpr uint32_t kEffectsCounts = kEffClasses + 1 + kEffectClasses;  // the candidates' classes, the candidates with an effect, the effects by class
 struct EffectsCode {

@@ -140,6 +140,10 @@ struct vsc_ctx {
     // vsc_*_edit: the call's tables (the targets' global positions, the coverage counters, the pairs' per-tile
     // counts and offsets) and its pairs; the candidates a call brings from the host and the rows lie in eff_in / eff_out
     vsc::DeviceBuf edit_tabs, edit_pairs;
+    // vsc_*_prime keep their tables (the edits' global positions, the edits, the occupancy bitmap, the coverage
+    // counters, the per-tile counts and offsets) in edit_tabs and their pairs in edit_pairs as well
+    bool prime_bitmap = true;  // vsc_debug_prime_bitmap: ask the occupancy bitmap before the edit search
+    uint32_t prime_groups_per_cu = 0;  // vsc_debug_prime_groups_per_cu: the cap of prime_rows_kernel's grid (0: the default)
     // vsc_*_effects: the device copy of the CDS this context walked last - the segments' global starts, then the
     // segments, keyed by the object's serial number as locate_buf is; the call's tables and records lie in edit_tabs / edit_pairs
     vsc::DeviceBuf cds_buf;
