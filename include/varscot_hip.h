@@ -1801,7 +1801,7 @@ const void *vsc_sites_scores_dev(const vsc_sites *sites);
  *
  * Not offered: a vsc_multi_* entry (the multi-device enumeration already joins its candidates on the host, and a shard cannot
  * see in front of its first word - load the genome on one device, or score by vsc_loci_efficiency there); ranking or top-K
- * per target interval; neural scores (Rule Set 2 / 3, DeepCpf1).
+ * per target interval; neural scores (Rule Set 3, DeepCpf1).  Rule Set 2 is a tree ensemble: the next section.
  */
 #define VSC_EFF_IDENTITY 0
 #define VSC_EFF_LOGISTIC 1
@@ -1844,6 +1844,103 @@ int vsc_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_gui
                                  double min_linear, vsc_guides **out);
 int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
                                          const vsc_eff_model *model, double min_linear, vsc_pattern_guides **out);
+
+/* ---- on-target efficiency from regression-tree ensembles -------------------------------------------------------- */
+/*
+ * The same question for the scores that are a gradient-boosted ensemble of small regression trees over sequence tests - the
+ * form of Doench 2016 "Rule Set 2" / Azimuth, and of whatever a caller retrains on a screen of their own.  The library ships
+ * no model: the caller brings the trees (vsc_eff_trees_build), with a learning rate folded into the leaves.
+ *
+ * SHAPE     up, site_len, down, link as vsc_eff_shape (C = up + site_len + down <= 64, flanks <= 16, site_len 16..32);
+ *           CONTEXT, the five classes and their order, and UNDEF (the NaN 0x7FF8000000000000) are those of the linear
+ *           model - eff_context of vsc_efficiency.h is used as it is, not copied.
+ * SUMS      n_sums <= 16.  Sum i: a range [start, start + len) inside the context, int32 mono[4], int32 di[16], every |w| <= 2^20:
+ *             S_i = sum over j in the range of mono[b_j]  +  sum over j with j and j+1 in the range of di[4 b_j + b_{j+1}]
+ *           (int32, cannot overflow: 127 terms of at most 2^20).  len 0: S_i = 0.
+ * TREES     1..1024 trees, at most 8 192 nodes in all, depth (edges from the root) at most 32.  A tree's nodes are numbered from 0
+ *           (the root); an inner node's children have LARGER numbers than the node, and every node but the root is the child of
+ *           exactly one node.  Node kinds:
+ *             LEAF     value (finite double; -0.0 stored as +0.0)
+ *             BASE     pos (0..C-1), mask (4 bits):            true iff bit b_pos of mask is set
+ *             PAIR     pos_a != pos_b (0..C-1), mask (16 bits): true iff bit 4 b_{pos_a} + b_{pos_b} of mask is set
+ *             SUM      i (< n_sums), t (int32):                 true iff S_i <= t
+ *           true goes to `left`, false to `right`.  Masks 0 and all-ones are allowed (a constant test).
+ * PREDICTOR x = base;  for t = 0 .. n_trees - 1 in this order:  x = x + value(the leaf the context reaches in tree t).
+ *           fp64, one rounding per addition, no multiplication: a learning rate is folded into the leaves by the caller.
+ * LINK      identity or logistic, on the HOST only, exactly as vsc_eff_link.
+ *
+ * A model that breaks any of these rules is refused with VSC_ERR_INVALID by vsc_eff_trees_build, never at a launch: a child
+ * not larger than its parent, a child outside the tree, a node with two parents or with none, a depth of 33, 8 193 nodes, a
+ * value (or a base) that is not finite, a weight of 2^20 + 1, a range that leaves the context, pos_a == pos_b, a position
+ * outside the context, a mask wider than its kind's, a sum that does not exist, an unknown kind, a field that has no meaning
+ * for the node's kind and is not 0, a shape with a G/C range (gc_start and gc_len are 0 here).
+ *
+ * vsc_eff_trees_build: sums[n_sums] (NULL iff n_sums == 0); nodes[tree_first[n_trees]], tree t's nodes being
+ * nodes[tree_first[t] .. tree_first[t + 1]) with left / right numbered inside the tree; tree_first[0] == 0, ascending.
+ * vsc_eff_trees is host-only and immutable.  vsc_eff_trees_info returns its process-wide serial number, its shape and the
+ * counts of sums, trees and nodes by kind, and the depth of the deepest leaf.  A context keeps the device copy of the tree
+ * model it used last, keyed by the serial number, beside the linear model's; vsc_ctx_release_scratch gives it back.
+ * vsc_eff_trees_score_text and vsc_eff_trees_link are vsc_eff_score_text and vsc_eff_link for this model: the text is scored
+ * with the very functions the kernels call.
+ *
+ * vsc_loci_efficiency_trees, vsc_guides_efficiency_trees (site_len == 23), vsc_pattern_guides_efficiency_trees,
+ * vsc_guides_filter_efficiency_trees and vsc_pattern_guides_filter_efficiency_trees are the five calls above with this
+ * predictor: the same arguments, classes, stats, refusals (a NaN min_linear among them), results and vsc_ctx_timing.  The
+ * filter keeps defined && x >= min_linear; its bytes depend on the input and the model only.
+ *
+ * Not offered: shipped weights; features that are no function of the context (position in the peptide, a melting
+ * temperature as a ratio); models above the caps; random-forest averages (a division follows the sum); a vsc_multi_* entry
+ * (as above); neural scores (Rule Set 3, DeepCpf1).
+ */
+#define VSC_EFF_NODE_LEAF 0
+#define VSC_EFF_NODE_BASE 1
+#define VSC_EFF_NODE_PAIR 2
+#define VSC_EFF_NODE_SUM 3
+typedef struct vsc_eff_trees vsc_eff_trees;
+typedef struct {
+    uint32_t start, len; /* [start, start + len) in context coordinates */
+    int32_t mono[4];     /* per letter */
+    int32_t di[16];      /* 4 * b_j + b_{j+1} */
+} vsc_eff_sum;
+typedef struct {
+    uint32_t kind;        /* VSC_EFF_NODE_* */
+    uint32_t a;           /* BASE: pos; PAIR: pos_a; SUM: i; LEAF: 0 */
+    uint32_t b;           /* PAIR: pos_b; else 0 */
+    uint32_t mask;        /* BASE: 4 bits; PAIR: 16 bits; else 0 */
+    int32_t t;            /* SUM: the threshold; else 0 */
+    uint32_t left, right; /* inner nodes: the children's numbers inside the tree (true, false); LEAF: 0 */
+    uint32_t reserved;    /* 0 */
+    double value;         /* LEAF: its value; else 0 */
+} vsc_eff_node;
+typedef struct {
+    uint64_t serial; /* process-wide number of the model */
+    vsc_eff_shape shape;
+    uint32_t n_sums, n_trees, n_nodes;
+    uint32_t leaves, base_nodes, pair_nodes, sum_nodes;
+    uint32_t max_depth; /* edges from a root to the deepest leaf */
+    uint64_t reserved[2];
+} vsc_eff_trees_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_eff_sum) == 88 && sizeof(vsc_eff_node) == 40 && sizeof(vsc_eff_trees_stats) == 88, "vsc_eff_trees layout");
+#else
+_Static_assert(sizeof(vsc_eff_sum) == 88 && sizeof(vsc_eff_node) == 40 && sizeof(vsc_eff_trees_stats) == 88, "vsc_eff_trees layout");
+#endif
+int vsc_eff_trees_build(const vsc_eff_shape *shape, double base, const vsc_eff_sum *sums, uint32_t n_sums, const vsc_eff_node *nodes,
+                        const uint32_t *tree_first /* [n_trees + 1] */, uint32_t n_trees, vsc_eff_trees **out);
+int vsc_eff_trees_free(vsc_eff_trees *model);
+int vsc_eff_trees_info(const vsc_eff_trees *model, vsc_eff_trees_stats *out);
+int vsc_eff_trees_score_text(const vsc_eff_trees *model, const char *context /* C letters, read orientation */, double *linear);
+double vsc_eff_trees_link(const vsc_eff_trees *model, double linear);
+int vsc_loci_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n,
+                              const vsc_eff_trees *model, double *linear /* host, n */, vsc_eff_stats *stats /* optional */);
+int vsc_guides_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_eff_trees *model,
+                                double *linear /* host, one per candidate */, vsc_eff_stats *stats /* optional */);
+int vsc_pattern_guides_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_eff_trees *model,
+                                        double *linear /* host, one per candidate */, vsc_eff_stats *stats /* optional */);
+int vsc_guides_filter_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_eff_trees *model,
+                                       double min_linear, vsc_guides **out);
+int vsc_pattern_guides_filter_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in,
+                                               const vsc_eff_trees *model, double min_linear, vsc_pattern_guides **out);
 
 /* ---- microhomology and out-of-frame scores of candidate guides ------------------------------------------------ */
 /*

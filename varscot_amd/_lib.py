@@ -297,6 +297,23 @@ class EffStats(C.Structure):
         return {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n")}
 
 
+EFF_NODE_LEAF, EFF_NODE_BASE, EFF_NODE_PAIR, EFF_NODE_SUM = 0, 1, 2, 3  # VSC_EFF_NODE_*
+# vsc_eff_sum: a range of the context and the integer weights of its letters and dinucleotides
+EFF_SUM_DTYPE = np.dtype([("start", "<u4"), ("len", "<u4"), ("mono", "<i4", (4,)), ("di", "<i4", (16,))])
+# vsc_eff_node: one node of a regression tree, its children numbered inside the tree
+EFF_NODE_DTYPE = np.dtype([("kind", "<u4"), ("a", "<u4"), ("b", "<u4"), ("mask", "<u4"), ("t", "<i4"), ("left", "<u4"), ("right", "<u4"),
+                           ("reserved", "<u4"), ("value", "<f8")])
+
+
+class EffTreesStats(C.Structure):
+    """vsc_eff_trees_stats"""
+    _fields_ = [("serial", C.c_uint64), ("shape", EffShape), ("n_sums", C.c_uint32), ("n_trees", C.c_uint32), ("n_nodes", C.c_uint32),
+                ("leaves", C.c_uint32), ("base_nodes", C.c_uint32), ("pair_nodes", C.c_uint32), ("sum_nodes", C.c_uint32),
+                ("max_depth", C.c_uint32), ("reserved", C.c_uint64 * 2)]
+
+
+assert EFF_SUM_DTYPE.itemsize == 88 and EFF_NODE_DTYPE.itemsize == 40 and C.sizeof(EffTreesStats) == 88
+
 MH_UNDEFINED = 0xFFFFFFFF  # VSC_MH_UNDEFINED
 
 
@@ -648,6 +665,16 @@ SYMBOLS = [
     ("vsc_pattern_guides_efficiency", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
     ("vsc_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_efficiency", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
+    ("vsc_eff_trees_build", C.c_int, [C.POINTER(EffShape), C.c_double, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_eff_trees_free", C.c_int, [_vp]),
+    ("vsc_eff_trees_info", C.c_int, [_vp, C.POINTER(EffTreesStats)]),
+    ("vsc_eff_trees_score_text", C.c_int, [_vp, C.c_char_p, C.POINTER(C.c_double)]),
+    ("vsc_eff_trees_link", C.c_double, [_vp, C.c_double]),
+    ("vsc_loci_efficiency_trees", C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_guides_efficiency_trees", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_pattern_guides_efficiency_trees", C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(EffStats)]),
+    ("vsc_guides_filter_efficiency_trees", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_efficiency_trees", C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.POINTER(_vp)]),
     ("vsc_mh_score_text", C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("vsc_mh_scores", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("vsc_loci_microhomology", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(MhShape), _vp, C.POINTER(MhStats)]),

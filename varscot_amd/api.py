@@ -2,6 +2,7 @@
 search and per-hit scoring.  Thin plumbing only - every computation happens in libvarscot_hip.so.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -902,6 +903,304 @@ class EfficiencyModel:
     def close(self):
         if getattr(self, "_h", None):
             lib().vsc_eff_model_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _letter_mask(letters, width, what):
+    """The mask of a BASE test (width 1: a string of letters, bit b per letter) or of a PAIR test (width 2: a list of
+    two-letter strings, or one string of them separated by commas; bit 4 b_a + b_b per dinucleotide).  "" / "-" / []: no bit."""
+    if isinstance(letters, str):
+        items = [] if letters in ("", "-") else (list(letters) if width == 1 else letters.split(","))
+    else:
+        items = list(letters)
+    mask = 0
+    for it in items:
+        if not isinstance(it, str) or len(it) != width:
+            raise ValueError("%s: %r is no %s" % (what, it, "base" if width == 1 else "dinucleotide"))
+        code = 0
+        for ch in it:
+            code = 4 * code + _base(ch, what)
+        if mask >> code & 1:
+            raise ValueError("%s: %r is given twice" % (what, it))
+        mask |= 1 << code
+    return mask
+
+
+def _mask_letters(mask, width):
+    """The inverse of _letter_mask, as to_tsv writes it."""
+    if width == 1:
+        return "".join("ACGT"[b] for b in range(4) if mask >> b & 1) or "-"
+    return ",".join("ACGT"[d // 4] + "ACGT"[d % 4] for d in range(16) if mask >> d & 1) or "-"
+
+
+class TreeEfficiencyModel:
+    """An on-target efficiency model that is a sum of regression trees (vsc_eff_trees; include/varscot_hip.h "SUMS / TREES /
+    PREDICTOR"): x = base + the value of the leaf the context reaches in tree 0, + ... in tree 1, and so on, in this order -
+    the form of Doench 2016 "Rule Set 2" and of a scikit-learn GradientBoostingRegressor (from_sklearn).  The context is the
+    linear model's: `up` bases in front of the site, its site_len bases, `down` behind, read orientation.
+      sums   [(start, length, {letters: int weight})]: S_i = the weights of the letters ("G") and dinucleotides ("GC") inside
+             context range [start, start + length), added up - a G/C count is {"G": 1, "C": 1}.
+      trees  a list of node lists; a tree's nodes are numbered from 0 (the root) and a node's children have larger numbers:
+             ("leaf", v), ("base", pos, "AG", left, right) - true iff the letter at pos is one of these -,
+             ("pair", a, b, ["AG", "CC"], left, right) - true iff the letters at a and b are one of these pairs -,
+             ("sum", i, t, left, right) - true iff S_i <= t.  True goes left.
+    link: "identity" or "logistic", applied on the host by link().  The package ships no model."""
+
+    LINKS = EfficiencyModel.LINKS
+    KINDS = {"leaf": _lib.EFF_NODE_LEAF, "base": _lib.EFF_NODE_BASE, "pair": _lib.EFF_NODE_PAIR, "sum": _lib.EFF_NODE_SUM}
+
+    def __init__(self, up, site_len, down, base, sums, trees, link="identity"):
+        if link not in self.LINKS:
+            raise ValueError("link must be 'identity' or 'logistic'")
+        self.up, self.site_len, self.down, self.link_name = int(up), int(site_len), int(down), link
+        if any(not 0 <= v < 2 ** 32 for v in (self.up, self.site_len, self.down)):
+            raise ValueError("the shape's fields must fit 32 unsigned bits")
+        self.base = float(base)
+        self.sums = [(int(s), int(n), {str(k).upper().replace("U", "T"): int(w) for k, w in dict(wts).items()}) for s, n, wts in sums]
+        self.trees = [[tuple(node) for node in tree] for tree in trees]
+        self._h = None
+        i32 = lambda v, what: self._int(v, -2 ** 31, 2 ** 31 - 1, what)  # noqa: E731
+        u32 = lambda v, what: self._int(v, 0, 2 ** 32 - 1, what)        # noqa: E731
+        sum_arr = np.zeros(len(self.sums), dtype=_lib.EFF_SUM_DTYPE)
+        for i, (start, length, wts) in enumerate(self.sums):
+            sum_arr[i]["start"], sum_arr[i]["len"] = u32(start, "sum %d" % i), u32(length, "sum %d" % i)
+            for letters, w in wts.items():
+                what = "sum %d, weight %r" % (i, letters)
+                if len(letters) not in (1, 2):
+                    raise ValueError("%s: one letter or two" % what)
+                code = 0
+                for ch in letters:
+                    code = 4 * code + _base(ch, what)
+                sum_arr[i]["mono" if len(letters) == 1 else "di"][code] = i32(w, what)
+        first = np.zeros(len(self.trees) + 1, dtype=np.uint32)
+        first[1:] = np.cumsum([len(t) for t in self.trees])
+        nodes = np.zeros(int(first[-1]), dtype=_lib.EFF_NODE_DTYPE)
+        at = 0
+        for t, tree in enumerate(self.trees):
+            for k, node in enumerate(tree):
+                what = "tree %d, node %d" % (t, k)
+                n = nodes[at]
+                at += 1
+                kind = node[0] if len(node) else None
+                if kind not in self.KINDS or len(node) != {"leaf": 2, "base": 5, "pair": 6, "sum": 5}[kind]:
+                    raise ValueError("%s: %r is no node" % (what, node))
+                n["kind"] = self.KINDS[kind]
+                if kind == "leaf":
+                    n["value"] = float(node[1])
+                    continue
+                n["left"], n["right"] = u32(node[-2], what), u32(node[-1], what)
+                if kind == "base":
+                    n["a"], n["mask"] = u32(node[1], what), _letter_mask(node[2], 1, what)
+                elif kind == "pair":
+                    n["a"], n["b"], n["mask"] = u32(node[1], what), u32(node[2], what), _letter_mask(node[3], 2, what)
+                else:
+                    n["a"], n["t"] = u32(node[1], what), i32(node[2], what)
+        shape = _lib.EffShape(self.up, self.site_len, self.down, 0, 0, self.LINKS[link])
+        h = C.c_void_p()
+        check(lib().vsc_eff_trees_build(C.byref(shape), self.base, ptr(sum_arr) if len(sum_arr) else None, len(sum_arr),
+                                        ptr(nodes) if len(nodes) else None, ptr(first), len(self.trees), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _int(v, lo, hi, what):
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError("%s: %r is no integer in %d .. %d" % (what, v, lo, hi))
+        return int(v)
+
+    @property
+    def context_len(self):
+        return self.up + self.site_len + self.down
+
+    @classmethod
+    def from_sklearn(cls, estimator, features, up, site_len, down, sums=(), link="identity"):
+        """The model of a fitted scikit-learn GradientBoostingRegressor (squared error; its constant init or init="zero").
+        features[k] says what column k of the training matrix was: ("base", pos, "A") - 1 where the letter at pos is A, else 0 -,
+        ("pair", a, b, "AG") - 1 where the letters at a and b are A and G -, or ("sum", i) - S_i of `sums`.  A split x <= thr on
+        an indicator becomes the complement mask (a constant mask when thr lies outside [0, 1)), a split on a sum
+        S_i <= floor(thr); the leaves are learning_rate * value, the base is the init's constant: score_text then equals
+        estimator.predict to the bit.  Every other estimator is refused."""
+        name = type(estimator).__name__
+        if name != "GradientBoostingRegressor" or not type(estimator).__module__.startswith("sklearn."):
+            raise ValueError("from_sklearn takes a fitted sklearn GradientBoostingRegressor, not a %s" % name)
+        if not hasattr(estimator, "estimators_"):
+            raise ValueError("the estimator is not fitted")
+        if getattr(estimator, "loss", None) != "squared_error":
+            raise ValueError("from_sklearn takes the squared_error loss only, not %r" % (getattr(estimator, "loss", None),))
+        if isinstance(estimator.init, str) and estimator.init == "zero":
+            base = 0.0
+        elif estimator.init is None and type(estimator.init_).__name__ == "DummyRegressor":
+            base = float(np.asarray(estimator.init_.constant_, dtype=np.float64).reshape(-1)[0])
+        else:
+            raise ValueError("from_sklearn takes the estimator's constant init or init='zero'")
+        if len(features) != estimator.n_features_in_:
+            raise ValueError("the estimator has %d columns, features names %d" % (estimator.n_features_in_, len(features)))
+        rate = float(estimator.learning_rate)
+        trees = []
+        for stage in estimator.estimators_[:, 0]:
+            tr = stage.tree_
+            left, right, feat, thr, value = tr.children_left, tr.children_right, tr.feature, tr.threshold, tr.value
+            order, stack = [], [0]  # preorder: a child's new number is larger than its parent's
+            while stack:
+                k = stack.pop()
+                order.append(k)
+                if left[k] >= 0:
+                    stack += [int(right[k]), int(left[k])]
+            new = {k: i for i, k in enumerate(order)}
+            nodes = []
+            for k in order:
+                if left[k] < 0:
+                    nodes.append(("leaf", rate * float(value[k, 0, 0])))
+                    continue
+                f, x, lr = features[int(feat[k])], float(thr[k]), (new[int(left[k])], new[int(right[k])])
+                if f[0] == "sum" and len(f) == 2:
+                    nodes.append(("sum", int(f[1]), int(min(max(math.floor(x), -2 ** 31), 2 ** 31 - 1))) + lr)
+                elif f[0] in ("base", "pair") and len(f) == (3 if f[0] == "base" else 4):
+                    width = 1 if f[0] == "base" else 2
+                    full = 0xF if width == 1 else 0xFFFF
+                    one = _letter_mask([f[-1]], width, "feature %r" % (f,))
+                    mask = full if x >= 1.0 else 0 if x < 0.0 else full & ~one  # x_k <= thr, x_k 0 or 1
+                    text = _mask_letters(mask, width)
+                    nodes.append((f[0],) + tuple(int(p) for p in f[1:-1]) + (text if width == 1 else [] if text == "-" else text.split(","),) + lr)
+                else:
+                    raise ValueError("feature %r is none of ('base', pos, X), ('pair', a, b, XY), ('sum', i)" % (f,))
+            trees.append(nodes)
+        return cls(up, site_len, down, base, sums, trees, link=link)
+
+    @classmethod
+    def from_tsv(cls, path):
+        """A model from the text file to_tsv writes (tools/README.md): `shape up site_len down`, `link identity|logistic`,
+        `intercept x` (the base), `sum I START LENGTH`, `sumw I X|XY W`, `tree T`, `leaf K V`, `base_in K POS LETTERS L R`,
+        `pair_in K POSA POSB XY[,XY...] L R`, `sum_le K I T L R`; '-' is the empty set of letters, '#' starts a comment.  I, T
+        and K ascend from 0; a node belongs to the last `tree` line.  Anything that does not parse, a key given twice, an
+        index out of turn and a `mono` / `di` / `gc` line are refused with the line number."""
+        shape = None
+        base, link, sums, trees = 0.0, "identity", [], []
+        once = set()
+        with open(path) as fh:
+            for n, line in enumerate(fh, 1):
+                f = line.split("#", 1)[0].split()
+                if not f:
+                    continue
+                where = "%s:%d" % (path, n)
+                try:
+                    key, a = f[0], f[1:]
+                    if key in ("shape", "link", "intercept"):
+                        if key in once:
+                            raise ValueError("'%s' is given twice" % key)
+                        once.add(key)
+                    if key in ("mono", "di", "gc", "gc_range"):
+                        raise ValueError("'%s' belongs to a linear model; this file holds a tree model" % key)
+                    if key in ("leaf", "base_in", "pair_in", "sum_le"):
+                        if not trees:
+                            raise ValueError("'%s' before the first 'tree' line" % key)
+                        if len(a) < 1 or int(a[0]) != len(trees[-1]):
+                            raise ValueError("node %s out of turn: node %d of tree %d comes next" % (a[0] if a else "?", len(trees[-1]), len(trees) - 1))
+                    if key == "shape" and len(a) == 3:
+                        shape = tuple(int(v) for v in a)
+                    elif key == "link" and len(a) == 1:
+                        if a[0] not in cls.LINKS:
+                            raise ValueError("link must be 'identity' or 'logistic'")
+                        link = a[0]
+                    elif key == "intercept" and len(a) == 1:
+                        base = float(a[0])
+                    elif key == "sum" and len(a) == 3:
+                        if int(a[0]) != len(sums):
+                            raise ValueError("sum %s out of turn: sum %d comes next" % (a[0], len(sums)))
+                        sums.append((int(a[1]), int(a[2]), {}))
+                    elif key == "sumw" and len(a) == 3:
+                        if not 0 <= int(a[0]) < len(sums):
+                            raise ValueError("'sumw' before its 'sum %s' line" % a[0])
+                        letters = a[1].upper().replace("U", "T")
+                        if len(letters) not in (1, 2):
+                            raise ValueError("'sumw' takes one letter or two")
+                        for ch in letters:
+                            _base(ch, where)
+                        if letters in sums[int(a[0])][2]:
+                            raise ValueError("weight %s of sum %s is given twice" % (a[1], a[0]))
+                        sums[int(a[0])][2][letters] = int(a[2])
+                    elif key == "tree" and len(a) == 1:
+                        if int(a[0]) != len(trees):
+                            raise ValueError("tree %s out of turn: tree %d comes next" % (a[0], len(trees)))
+                        if trees and not trees[-1]:
+                            raise ValueError("tree %d has no node" % (len(trees) - 1))
+                        trees.append([])
+                    elif key == "leaf" and len(a) == 2:
+                        trees[-1].append(("leaf", float(a[1])))
+                    elif key == "base_in" and len(a) == 5:
+                        _letter_mask(a[2], 1, where)
+                        trees[-1].append(("base", int(a[1]), a[2], int(a[3]), int(a[4])))
+                    elif key == "pair_in" and len(a) == 6:
+                        _letter_mask(a[3], 2, where)
+                        trees[-1].append(("pair", int(a[1]), int(a[2]), a[3], int(a[4]), int(a[5])))
+                    elif key == "sum_le" and len(a) == 5:
+                        trees[-1].append(("sum", int(a[1]), int(a[2]), int(a[3]), int(a[4])))
+                    else:
+                        raise ValueError("unknown key or wrong number of fields: %r" % " ".join(f))
+                except ValueError as e:
+                    raise ValueError(str(e) if str(e).startswith(where) else "%s: %s" % (where, e)) from None
+        if shape is None:
+            raise ValueError("%s: no 'shape' line" % path)
+        if not trees:
+            raise ValueError("%s: no 'tree' line" % path)
+        return cls(shape[0], shape[1], shape[2], base, sums, trees, link=link)
+
+    def to_tsv(self, path):
+        """The model as a text file from_tsv reads back to the bit: doubles as repr() prints them."""
+        with open(path, "w") as fh:
+            fh.write("# on-target efficiency model (regression trees): context = %d upstream + %d site + %d downstream bases, read orientation\n"
+                     % (self.up, self.site_len, self.down))
+            fh.write("shape\t%d\t%d\t%d\nlink\t%s\nintercept\t%r\n" % (self.up, self.site_len, self.down, self.link_name, self.base))
+            for i, (start, length, wts) in enumerate(self.sums):
+                fh.write("sum\t%d\t%d\t%d\n" % (i, start, length))
+                for letters, w in wts.items():
+                    fh.write("sumw\t%d\t%s\t%d\n" % (i, letters, w))
+            for t, tree in enumerate(self.trees):
+                fh.write("tree\t%d\n" % t)
+                for k, node in enumerate(tree):
+                    if node[0] == "leaf":
+                        fh.write("leaf\t%d\t%r\n" % (k, float(node[1])))
+                    elif node[0] == "base":
+                        fh.write("base_in\t%d\t%d\t%s\t%d\t%d\n" % (k, node[1], _mask_letters(_letter_mask(node[2], 1, "node"), 1), node[3], node[4]))
+                    elif node[0] == "pair":
+                        fh.write("pair_in\t%d\t%d\t%d\t%s\t%d\t%d\n"
+                                 % (k, node[1], node[2], _mask_letters(_letter_mask(node[3], 2, "node"), 2), node[4], node[5]))
+                    else:
+                        fh.write("sum_le\t%d\t%d\t%d\t%d\t%d\n" % (k, node[1], node[2], node[3], node[4]))
+
+    def info(self):
+        st = _lib.EffTreesStats()
+        check(lib().vsc_eff_trees_info(self._h, C.byref(st)))
+        s = st.shape
+        return {"serial": int(st.serial), "up": int(s.up), "site_len": int(s.site_len), "down": int(s.down),
+                "link": {v: k for k, v in self.LINKS.items()}[int(s.link)], "n_sums": int(st.n_sums), "n_trees": int(st.n_trees),
+                "n_nodes": int(st.n_nodes), "leaves": int(st.leaves), "base_nodes": int(st.base_nodes), "pair_nodes": int(st.pair_nodes),
+                "sum_nodes": int(st.sum_nodes), "max_depth": int(st.max_depth)}
+
+    def score_text(self, context):
+        """vsc_eff_trees_score_text: the predictor of one context of C letters in read orientation, on the host by the
+        functions the kernels run; a letter outside ACGT gives the undefined NaN.  No device is needed."""
+        b = context if isinstance(context, bytes) else context.encode()
+        x = C.c_double()
+        check(lib().vsc_eff_trees_score_text(self._h, b, C.byref(x)))
+        return x.value
+
+    def link(self, x):
+        """vsc_eff_trees_link: a predictor (or an array of them) through the model's link, on the host."""
+        L = lib()
+        if np.ndim(x) == 0:
+            return L.vsc_eff_trees_link(self._h, float(x))
+        a = np.asarray(x, dtype=np.float64)
+        return np.array([L.vsc_eff_trees_link(self._h, float(v)) for v in a.reshape(-1)], dtype=np.float64).reshape(a.shape)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().vsc_eff_trees_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -2300,7 +2599,7 @@ class Genome:
         array, applied to the whole site under `rule` ("overlap" / "inside"); an empty list keeps nothing.  Returns a
         PatternGuides (.codes, .loci, .text()) in ascending (contig, pos), '+' before '-'.  More than max_guides (0: no cap)
         candidates raise VarscotError -34.  params: a PatternEnumParams to pass as it is (tests).
-        efficiency= an EfficiencyModel whose site_len is the pattern's length: returns (PatternGuides, linear float64[n]) - the
+        efficiency= an EfficiencyModel or a TreeEfficiencyModel whose site_len is the pattern's length: returns (PatternGuides, linear float64[n]) - the
         candidates' predictors, computed where the candidates lie on the device (vsc_pattern_guides_efficiency).
         min_efficiency=x (needs efficiency=): only the candidates whose predictor is defined and >= x, linear domain
         (vsc_pattern_guides_filter_efficiency).
@@ -2425,15 +2724,18 @@ class Genome:
             if floor is not None:
                 raise ValueError("min_efficiency needs efficiency=model")
             return
-        if not isinstance(model, EfficiencyModel):
-            raise ValueError("efficiency must be an EfficiencyModel")
+        if not isinstance(model, (EfficiencyModel, TreeEfficiencyModel)):
+            raise ValueError("efficiency must be an EfficiencyModel or a TreeEfficiencyModel")
         if model.site_len != site_len:
             raise ValueError("the model's site_len is %d; these candidates are %d bases long" % (model.site_len, site_len))
 
     def _eff_on_handle(self, held, model, floor, count_fn, score_fn, filter_fn, free_fn, score=True):
         """The predictors of the candidate handle held[0] under a model, computed where the candidates lie.  With a floor the
         handle is first replaced by the filter's result: the input is freed and held[0] is the result - the caller frees
-        held[0], whatever happens here.  score=False: the filter only."""
+        held[0], whatever happens here.  score=False: the filter only.  A TreeEfficiencyModel goes through the calls of the
+        same names that end in _trees."""
+        if isinstance(model, TreeEfficiencyModel):
+            score_fn, filter_fn = (getattr(lib(), fn.__name__ + "_trees") for fn in (score_fn, filter_fn))
         if floor is not None:
             out = C.c_void_p()
             check(filter_fn(self.ctx._h, self._h, held[0], model._h, float(floor), C.byref(out)), self.ctx._h)
@@ -2883,7 +3185,8 @@ class Genome:
         return picks, counts
 
     def efficiency(self, loci_or_found, model, allow_partial=False):
-        """vsc_loci_efficiency: the linear predictors of candidates under an EfficiencyModel, computed on the device from the
+        """vsc_loci_efficiency (vsc_loci_efficiency_trees for a TreeEfficiencyModel): the linear predictors of candidates under an
+        EfficiencyModel or a TreeEfficiencyModel, computed on the device from the
         resident planes: (linear float64[n], stats).  loci_or_found: what enumerate_guides returns (its loci are taken), a
         PatternGuides, or a LOCUS_DTYPE array / (contig, pos, strand) rows - a locus names the site's first base on the
         forward strand.  An undefined predictor is the NaN with bits EFF_UNDEFINED_BITS; stats counts the candidates by
@@ -2899,7 +3202,8 @@ class Genome:
         lo = _loci(loci, len(loci))
         linear = np.empty(len(lo), dtype=np.float64)
         st = _lib.EffStats()
-        check(lib().vsc_loci_efficiency(self.ctx._h, self._h, ptr(lo), len(lo), model._h, ptr(linear), C.byref(st)), self.ctx._h)
+        fn = lib().vsc_loci_efficiency_trees if isinstance(model, TreeEfficiencyModel) else lib().vsc_loci_efficiency
+        check(fn(self.ctx._h, self._h, ptr(lo), len(lo), model._h, ptr(linear), C.byref(st)), self.ctx._h)
         stats = st.as_dict()
         _eff_partial(stats, allow_partial)
         return linear, stats
@@ -3047,7 +3351,7 @@ class Genome:
         candidates raise VarscotError -34.  params: an EnumParams to pass as it is (tests).
         labels=True (needs regions; or labels=another Regions): returns (codes, loci, labels uint32[n]) - per candidate the
         index of the interval it lies in, REGION_NONE if none, as Regions.locate gives it (vsc_guides_locate, on the device).
-        efficiency= an EfficiencyModel with site_len 23: the candidates' linear predictors (float64[n], computed where the
+        efficiency= an EfficiencyModel or a TreeEfficiencyModel with site_len 23: the candidates' linear predictors (float64[n], computed where the
         candidates lie on the device: vsc_guides_efficiency) come last in the returned tuple.  min_efficiency=x (needs
         efficiency=): only the candidates whose predictor is defined and >= x, linear domain (vsc_guides_filter_efficiency).
         microhomology= a MicrohomologyShape with site_len 23: the candidates' (sum, oof) pairs (uint32[n, 2],

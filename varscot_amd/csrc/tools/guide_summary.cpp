@@ -104,7 +104,9 @@
 //   efficiencyLinear efficiency
 // = the linear predictor (%.17g; NA when the context leaves its sequence or holds an N) and the predictor through the model's
 // link.  -y MIN (needs -Y) keeps only the candidates whose predictor is defined and >= MIN, linear domain
-// (vsc_guides_filter_efficiency), BEFORE the off-target search: every output holds the survivors only.
+// (vsc_guides_filter_efficiency), BEFORE the off-target search: every output holds the survivors only.  A -Y file that holds
+// a `tree` line is an ensemble of regression trees instead (the form of Rule Set 2; varscot_amd.TreeEfficiencyModel.to_tsv,
+// tools/eff_trees_host.hpp; vsc_guides_efficiency_trees, vsc_guides_filter_efficiency_trees): the same columns, the same -y.
 // -H FLANK[,CUT] (needs -E, one device) scores every found guide's MICROHOMOLOGY around its cut site (vsc_guides_microhomology: the
 // score of Bae et al. 2014 over FLANK bases on either side of the break in front of read position CUT, default 17): the -L
 // listing gains the last columns mhScore oofScore (%.17g; NA when the window leaves its sequence or holds an N).  -m
@@ -134,6 +136,7 @@
 #include <sstream>
 
 #include "eff_model_host.hpp"
+#include "eff_trees_host.hpp"
 #include "mh_host.hpp"
 #include "edit_host.hpp"
 #include "effects_host.hpp"
@@ -637,7 +640,7 @@ int main(int argc, char **argv)
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
     vsc_sites *scored_sites = nullptr;
-    vsc_eff_model *eff_model = nullptr;
+    EffAnyModel eff_model;  // -Y: a linear model, or - a file with a `tree` line - a tree model
     vsc_genome *genome = nullptr;
     vsc_bulge_hits *bulge_hits = nullptr;
     vsc_hits *site_plain = nullptr;
@@ -654,7 +657,7 @@ int main(int argc, char **argv)
     try {
         if (efficient) {  // (read before the index and the device: a model that does not fit costs nothing)
             vsc_eff_shape eff_shape{};
-            eff_model = load_eff_model(opts[33].value, &eff_shape);
+            eff_model = load_eff_any(opts[33].value, &eff_shape);
             if (eff_shape.site_len != (uint32_t)VSC_READ_LEN)
                 throw std::runtime_error("-Y: the model's site_len is " + std::to_string(eff_shape.site_len) + "; the guides are 23 bases long");
         }
@@ -775,7 +778,7 @@ int main(int argc, char **argv)
             if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
                 if (opts[34].set) {
                     vsc_guides *kept = nullptr;
-                    if (vsc_guides_filter_efficiency(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                    if (eff_any_filter(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
                     vsc_guides_free(found);
                     found = kept;
                 }
@@ -817,7 +820,7 @@ int main(int argc, char **argv)
             }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
-                if (vsc_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
             mh_pairs.resize(mh.on ? 2 * vsc_guides_count(found) : 0);
             if (mh.on && vsc_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
@@ -867,7 +870,7 @@ int main(int argc, char **argv)
                 if (opts[20].set) {
                     const std::string line = chrom + '\t' + std::to_string(fl[i].pos) + '\t' + std::to_string(fl[i].pos + VSC_READ_LEN) + '\t' + ids.back() +
                             "\t0\t" + strand + (from.empty() ? "" : '\t' + (from[i] < target_desc.size() ? target_desc[from[i]] : "-")) +
-                            (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i])) : "") +
+                            (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(eff_any_link(eff_model, eff_linear[i])) : "") +
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
                     const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
                                              (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "");
@@ -1345,7 +1348,7 @@ int main(int argc, char **argv)
     vsc_score_table_free(table);
     vsc_bulge_table_free(bulge_table);
     vsc_sites_free(scored_sites);
-    vsc_eff_model_free(eff_model);
+    eff_any_free(eff_model);
     if (pair_hits) vsc_hits_free(pair_hits);
     vsc_bulge_hits_free(bulge_hits);
     vsc_sites_free(sites);

@@ -32,6 +32,8 @@
 // must be the pattern's length): the -E listing gains two last columns, efficiencyLinear (%.17g; NA when the context leaves
 // its sequence or holds an N) and efficiency (the predictor through the model's link).  -y MIN (needs -Y) keeps only the
 // candidates whose predictor is defined and >= MIN, linear domain, BEFORE the search.  Without -Y every output is what it was.
+// A -Y file that holds a `tree` line is an ensemble of regression trees instead (varscot_amd.TreeEfficiencyModel.to_tsv,
+// tools/eff_trees_host.hpp; vsc_pattern_guides_efficiency_trees): the same columns, the same -y.
 // -H FLANK[,CUT] (needs -E) scores every found guide's MICROHOMOLOGY around its cut site (vsc_pattern_guides_microhomology: the
 // score of Bae et al. 2014 over FLANK bases on either side of the break in front of read position CUT; default CUT: 3 bases
 // before the end of a protospacer that starts the pattern - SpCas9, SaCas9 - else 18 bases behind its start - Cas12a): the -E
@@ -70,6 +72,7 @@
 #include <sstream>
 
 #include "eff_model_host.hpp"
+#include "eff_trees_host.hpp"
 #include "mh_host.hpp"
 #include "edit_host.hpp"
 #include "effects_host.hpp"
@@ -594,7 +597,7 @@ int main(int argc, char **argv)
     vsc_bulge_hits *bulge_hits = nullptr;
     vsc_pattern_hits *site_plain = nullptr;
     vsc_sites *sites = nullptr;
-    vsc_eff_model *eff_model = nullptr;
+    EffAnyModel eff_model;  // -Y: a linear model, or - a file with a `tree` line - a tree model
     vsc_pattern_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
     vsc_sites *scored_sites = nullptr;
@@ -607,7 +610,7 @@ int main(int argc, char **argv)
         const uint32_t len = (uint32_t)pattern.size();
         if (efficient) {  // (read before the index and the device: a model that does not fit costs nothing)
             vsc_eff_shape eff_shape{};
-            eff_model = load_eff_model(opts[16].value, &eff_shape);
+            eff_model = load_eff_any(opts[16].value, &eff_shape);
             if (eff_shape.site_len != len)
                 throw std::runtime_error("-Y: the model's site_len is " + std::to_string(eff_shape.site_len) + "; the pattern has " + std::to_string(len) + " letters");
         }
@@ -662,7 +665,7 @@ int main(int argc, char **argv)
             if (efficient) {  // -y: the survivors replace the candidates; -Y: their predictors, where they lie
                 if (opts[17].set) {
                     vsc_pattern_guides *kept = nullptr;
-                    if (vsc_pattern_guides_filter_efficiency(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                    if (eff_any_filter(ctx, genome, found, eff_model, min_eff, &kept) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
                     vsc_pattern_guides_free(found);
                     found = kept;
                 }
@@ -704,7 +707,7 @@ int main(int argc, char **argv)
             }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
-                if (vsc_pattern_guides_efficiency(ctx, genome, found, eff_model, eff_linear.data(), nullptr) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
+                if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
             }
             mh_pairs.resize(mh.on ? 2 * vsc_pattern_guides_count(found) : 0);
             if (mh.on && vsc_pattern_guides_microhomology(ctx, genome, found, &mh.shape, mh_pairs.data(), nullptr) != VSC_OK)
@@ -758,7 +761,7 @@ int main(int argc, char **argv)
                 }
                 guides[i].id = first_word(ix.names[loci[i].contig]) + ':' + std::to_string(loci[i].pos) + ':' + (loci[i].strand ? '-' : '+');
                 std::string line = guides[i].seq + '\t' + first_word(ix.names[loci[i].contig]) + '\t' + std::to_string(loci[i].pos) + '\t' + (loci[i].strand ? '-' : '+');
-                if (efficient) line += '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(vsc_eff_link(eff_model, eff_linear[i]));
+                if (efficient) line += '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(eff_any_link(eff_model, eff_linear[i]));
                 if (mh.on) line += mh_columns(&mh_pairs[2 * i]);
                 std::string ecol;
                 if (edit.on) {
@@ -1048,7 +1051,7 @@ int main(int argc, char **argv)
     }
     vsc_pattern_hits_free(hits);
     vsc_pattern_guides_free(found);
-    vsc_eff_model_free(eff_model);
+    eff_any_free(eff_model);
     vsc_pattern_table_free(table);
     vsc_bulge_table_free(bulge_table);
     vsc_sites_free(scored_sites);

@@ -12,6 +12,7 @@
 //   vsc_pattern.hip        pattern search, pattern guide discovery
 //   vsc_pattern_bulge.hip  bulges under a pattern
 //   vsc_efficiency.hip     on-target efficiency of candidates
+//   vsc_eff_trees.hip      ... from regression-tree ensembles
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
 //   vsc_edit.hip           base-editor windows of candidates and their join with targets
 //   vsc_prime.hip          prime-editing extensions of candidates and their join with edits
@@ -248,13 +249,14 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->sel_masks, &ctx->sum_rows_in, &ctx->regions_buf, &ctx->enum_tabs, &ctx->locate_buf, &ctx->locate_out,
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
-                         &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_in,
+                         &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_trees_buf, &ctx->eff_in,
                          &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->cds_buf, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
     ctx->bulge_table_serial = 0;
     ctx->eff_serial = 0;
+    ctx->eff_trees_serial = 0;
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
     ctx->cds_serial = 0;
@@ -4393,6 +4395,264 @@ int vsc_pattern_guides_filter_efficiency(vsc_ctx *ctx, const vsc_genome *genome,
                                          double min_linear, vsc_pattern_guides **out)
 {
     return eff_filter(ctx, genome, in, model, false, min_linear, out, "vsc_pattern_guides_filter_efficiency");
+}
+
+}  // extern "C"
+
+// ---- on-target efficiency from regression-tree ensembles (the definition: vsc_eff_trees.h, the kernels:
+// vsc_eff_trees.hip).  The calls are the linear model's, one for one, with another model and another kernel.
+namespace {
+
+// The device copy of `model` on this context, kept beside the linear model's and keyed by its own serial number.
+int resident_eff_trees(vsc_ctx *ctx, const vsc_eff_trees *model, EffTreesView &view)
+{
+    if (!(ctx->eff_trees_serial == model->serial && ctx->eff_trees_buf.p)) {
+        ctx->eff_trees_serial = 0;
+        const size_t bytes = model->words.size() * sizeof(uint32_t);
+        VSC_HIP(ctx, ctx->eff_trees_buf.ensure(bytes));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_trees_buf.p, model->words.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the model as soon as its call returns)
+        ctx->eff_trees_serial = model->serial;
+    }
+    view = EffTreesView{(const uint32_t *)ctx->eff_trees_buf.p, (uint32_t)model->words.size(), model->n_nodes, model->n_sums, model->n_trees,
+                        model->base, model->shape};
+    return VSC_OK;
+}
+
+int eff_trees_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_trees *model, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !model) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    return VSC_OK;
+}
+
+// eff_score with the tree model: the model resident, eff_trees_score_kernel, one copy back of the scores and one of the counts
+int eff_trees_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_trees *model, const void *d_loci, const vsc_locus *h_loci,
+                    uint64_t n, double *linear, vsc_eff_stats *stats, const char *who)
+{
+    if (stats) *stats = vsc_eff_stats{};
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        return VSC_OK;
+    }
+    if (!linear) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EffTreesArgs a{};
+    const int mrc = resident_eff_trees(ctx, model, a.m);
+    if (mrc != VSC_OK) return mrc;
+    a.g = eff_planes(genome);
+    a.n = n;
+    const size_t head = 256;  // the class counts, in front of the scores
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(double)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.linear = (double *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_eff_trees_score(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kEffClasses] = {};
+    VSC_HIP(ctx, hipMemcpyAsync(linear, a.linear, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+    }
+    t.score_ms = t.total_ms = ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(double));
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+template <class Guides>
+int eff_trees_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_eff_trees *model, bool need_23, double *linear,
+                           vsc_eff_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const int rc = eff_trees_check(ctx, genome, model, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
+    const bool dev = guides->ctx != nullptr;
+    return eff_trees_score(ctx, genome, model, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
+                           dev ? nullptr : guides->loci.data(), guides->n, linear, stats, who);
+    });
+}
+
+template <class Guides>
+int eff_trees_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_eff_trees *model, bool need_23, double min_linear,
+                     Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    const int rc = eff_trees_check(ctx, genome, model, who);
+    if (rc != VSC_OK) return rc;
+    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
+    if (std::isnan(min_linear)) return fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN");
+    const uint64_t n = in->n;
+    const uint64_t tiles = (n + kEffTile - 1) / kEffTile;
+    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    EffTreesFilterArgs a{};
+    const int mrc = resident_eff_trees(ctx, model, a.m);
+    if (mrc != VSC_OK) return mrc;
+    a.g = eff_planes(genome);
+    a.n = n;
+    a.min_linear = min_linear;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_eff_trees_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_eff_trees_build(const vsc_eff_shape *shape, double base, const vsc_eff_sum *sums, uint32_t n_sums, const vsc_eff_node *nodes,
+                        const uint32_t *tree_first, uint32_t n_trees, vsc_eff_trees **out)
+{
+    if (!out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    if (!shape || !nodes || !tree_first) return VSC_ERR_INVALID;
+    if (shape->reserved[0] || shape->reserved[1] || shape->link > VSC_EFF_LOGISTIC) return VSC_ERR_INVALID;
+    const EffShape s{shape->up, shape->site_len, shape->down, shape->gc_start, shape->gc_len};
+    return guarded(nullptr, [&]() -> int {
+    static std::atomic<uint64_t> serial{0};
+    EffTreesBuilt built;
+    if (!eff_trees_pack(s, base, sums, n_sums, nodes, tree_first, n_trees, built)) return VSC_ERR_INVALID;
+    std::unique_ptr<vsc_eff_trees> m(new vsc_eff_trees());
+    m->shape = s;
+    m->link = shape->link;
+    m->base = built.base;
+    m->words = std::move(built.words);
+    m->n_sums = n_sums;
+    m->n_trees = n_trees;
+    m->n_nodes = built.n_nodes;
+    for (int k = 0; k < 4; ++k) m->by_kind[k] = built.by_kind[k];
+    m->max_depth = built.max_depth;
+    m->serial = serial.fetch_add(1, std::memory_order_relaxed) + 1;
+    *out = m.release();
+    return VSC_OK;
+    });
+}
+
+int vsc_eff_trees_free(vsc_eff_trees *model)
+{
+    delete model;
+    return VSC_OK;
+}
+
+int vsc_eff_trees_info(const vsc_eff_trees *model, vsc_eff_trees_stats *out)
+{
+    if (!model || !out) return VSC_ERR_INVALID;
+    const EffShape &s = model->shape;
+    *out = vsc_eff_trees_stats{model->serial, vsc_eff_shape{s.up, s.site_len, s.down, 0, 0, model->link, {0, 0}}, model->n_sums, model->n_trees,
+                               model->n_nodes, model->by_kind[VSC_EFF_NODE_LEAF], model->by_kind[VSC_EFF_NODE_BASE],
+                               model->by_kind[VSC_EFF_NODE_PAIR], model->by_kind[VSC_EFF_NODE_SUM], model->max_depth, {0, 0}};
+    return VSC_OK;
+}
+
+int vsc_eff_trees_score_text(const vsc_eff_trees *model, const char *context, double *linear)
+{
+    if (!model || !context || !linear) return VSC_ERR_INVALID;
+    const uint32_t C = eff_context_len(model->shape);
+    if (strnlen(context, C + 1) != C) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    *linear = eff_undefined();
+    for (uint32_t j = 0; j < C; ++j) {
+        const int b = base_code(context[j]);
+        if (b > 3) return VSC_OK;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+    }
+    const EffTreesPacked m{model->words.data(), model->n_nodes, model->n_sums, model->n_trees, model->base};
+    int32_t S[kEffTreesMaxSums] = {};
+    eff_trees_sums(m, C, ch, cl, S, 1);
+    *linear = eff_trees_predict(m, ch, cl, S, 1);
+    return VSC_OK;
+}
+
+double vsc_eff_trees_link(const vsc_eff_trees *model, double linear)
+{
+    if (!model || std::isnan(linear)) return eff_undefined();
+    return model->link == VSC_EFF_LOGISTIC ? 1.0 / (1.0 + std::exp(-linear)) : linear;
+}
+
+int vsc_loci_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_eff_trees *model,
+                              double *linear, vsc_eff_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_efficiency_trees";
+    const int rc = eff_trees_check(ctx, genome, model, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    return eff_trees_score(ctx, genome, model, nullptr, loci, n, linear, stats, fn);
+    });
+}
+
+int vsc_guides_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_eff_trees *model, double *linear,
+                                vsc_eff_stats *stats)
+{
+    return eff_trees_score_guides(ctx, genome, guides, model, true, linear, stats, "vsc_guides_efficiency_trees");
+}
+
+int vsc_pattern_guides_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_eff_trees *model,
+                                        double *linear, vsc_eff_stats *stats)
+{
+    return eff_trees_score_guides(ctx, genome, guides, model, false, linear, stats, "vsc_pattern_guides_efficiency_trees");
+}
+
+int vsc_guides_filter_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_eff_trees *model, double min_linear,
+                                       vsc_guides **out)
+{
+    return eff_trees_filter(ctx, genome, in, model, true, min_linear, out, "vsc_guides_filter_efficiency_trees");
+}
+
+int vsc_pattern_guides_filter_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_eff_trees *model,
+                                               double min_linear, vsc_pattern_guides **out)
+{
+    return eff_trees_filter(ctx, genome, in, model, false, min_linear, out, "vsc_pattern_guides_filter_efficiency_trees");
 }
 
 }  // extern "C"

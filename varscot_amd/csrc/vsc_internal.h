@@ -7,6 +7,7 @@
 
 #include "varscot_hip.h"
 #include "vsc_efficiency.h"
+#include "vsc_eff_trees.h"
 #include "vsc_mh.h"
 #include "vsc_edit.h"
 #include "vsc_prime.h"
@@ -572,6 +573,39 @@ struct EffFilterArgs {
 };
 hipError_t launch_eff_score(const EffArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_eff_filter(const EffFilterArgs &args, bool write, hipStream_t stream);
+// vsc_eff_trees.hip (the definition: vsc_eff_trees.h).  The model as the kernels read it: the packed words of
+// vsc_eff_trees.h (the context's device copy), which every workgroup copies into its LDS.
+struct EffTreesView {
+    const uint32_t *words;
+    uint32_t n_words, n_nodes, n_sums, n_trees;
+    double base;
+    EffShape shape;  // gc_len 0
+};
+struct EffTreesArgs {
+    EffPlanes g;
+    EffTreesView m;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    double *linear;               // [n] out: the predictor, kEffUndefinedBits where it is undefined
+    unsigned long long *stats;    // [kEffClasses], zeroed before the launch: the kernel adds its candidates per class
+};
+// the filter's two passes, driven by run_enumeration as EffFilterArgs is: tiles of kEffTile candidates
+struct EffTreesFilterArgs {
+    EffPlanes g;
+    EffTreesView m;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    double min_linear;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_eff_trees_score(const EffTreesArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_eff_trees_filter(const EffTreesFilterArgs &args, bool write, hipStream_t stream);
 // vsc_mh.hip (the definition: vsc_mh.h)
 struct MhArgs {
     EffPlanes g;

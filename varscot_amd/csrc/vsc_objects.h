@@ -133,6 +133,10 @@ struct vsc_ctx {
     // vsc_*_microhomology (no model) bring their candidates in eff_in and leave their pairs in eff_out as well.
     vsc::DeviceBuf eff_buf, eff_in, eff_out;
     uint64_t eff_serial = 0;  // 0: none resident
+    // vsc_*_efficiency_trees: the device copy of the tree model this context used last (its packed words,
+    // vsc_eff_trees.h), keyed by the model's serial number, beside the linear model's
+    vsc::DeviceBuf eff_trees_buf;
+    uint64_t eff_trees_serial = 0;  // 0: none resident
     // vsc_*_pick: what a call uploads (keys, then the targets or the groups, then the loci of a call that brings
     // them from the host), the call's tables (targets per candidate, per-target counts, segment offsets, cursors, stats, picks,
     // counts, ranks) and the records of the eligible candidates in their targets' segments
@@ -305,6 +309,19 @@ struct vsc_eff_model {
     std::vector<double> w;  // mono, the transposed di, gc (vsc_efficiency.h): what the device copy holds
     uint64_t serial = 0;    // process-wide, handed out by vsc_eff_model_build: what a context's device copy is keyed by
     uint32_t nonzero = 0;   // weights that are not 0
+};
+
+// A regression-tree efficiency model (include/varscot_hip.h "SUMS / TREES"; built and checked by vsc_eff_trees_build).
+// Host-only, immutable once built.
+struct vsc_eff_trees {
+    vsc::EffShape shape{};  // gc_len 0
+    uint32_t link = 0;
+    double base = 0;
+    std::vector<uint32_t> words;  // the packed model of vsc_eff_trees.h: what the device copy holds
+    uint32_t n_sums = 0, n_trees = 0, n_nodes = 0;
+    uint32_t by_kind[4] = {};     // nodes by VSC_EFF_NODE_*
+    uint32_t max_depth = 0;
+    uint64_t serial = 0;          // process-wide, handed out by vsc_eff_trees_build: what a context's device copy is keyed by
 };
 
 struct vsc_hits {
