@@ -212,6 +212,158 @@ def test_more_targets_than_waves(ctx):
         gen.close()
 
 
+# ---- segment sizes around every boundary of the select: 64 / 128 / 192 (a lane's register slots) and 256 (registers / memory) ----
+@pytest.fixture(scope="module")
+def boundary(ctx):
+    """n_contigs -> the fixture of pick_cases.boundary with its genome loaded."""
+    made = {}
+
+    def get(n_contigs):
+        if n_contigs not in made:
+            f = pk.boundary(n_contigs)
+            made[n_contigs] = dict(f, gen=ctx.load_genome(va.PackedGenome.from_sequences(list(f["contigs"]))))
+        return made[n_contigs]
+
+    yield get
+    for f in made.values():
+        f["gen"].close()
+
+
+def boundary_arrays(n_contigs, key_set, order):
+    loci, target, key = pk.boundary_inputs(n_contigs, key_set, order)
+    return pk.loci_array(loci, va.LOCUS_DTYPE), np.array(target, dtype=np.uint32), np.array(key, dtype=np.uint64)
+
+
+def test_boundary_fixture_floors():
+    assert pk.boundary_floors() == list(pk.SIZES) and pk.WAVE_CAP == WAVE_CAP
+
+
+@pytest.mark.parametrize("order", pk.ORDERS)
+@pytest.mark.parametrize("n_contigs", [1, 3])
+def test_loci_pick_at_the_segment_boundaries(boundary, n_contigs, order):
+    f = boundary(n_contigs)
+    for key_set in pk.BOUNDARY_KEYS:
+        arr, tg, ky = boundary_arrays(n_contigs, key_set, order)
+        for k in pk.KS:
+            for spacing in pk.SPACINGS:
+                got = f["gen"].pick(arr, ky, va.PickShape(k, spacing), target=tg, n_targets=f["n_targets"], rank=True)
+                same(got, pk.boundary_expected(n_contigs, key_set, order, k, spacing))
+        again = f["gen"].pick(arr, ky, va.PickShape(k, spacing), target=tg, n_targets=f["n_targets"], rank=True)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:3], again[:3]))
+
+
+@pytest.mark.parametrize("order", pk.ORDERS)
+def test_guides_pick_at_the_segment_boundaries_across_contigs(ctx, boundary, order):
+    f = boundary(3)
+    arr, tg, _ = boundary_arrays(3, "equal", order)
+    g = Guides.from_arrays(ctx, np.zeros(len(arr), dtype=np.uint64), arr)   # the loci lie on the device
+    try:
+        for key_set in pk.BOUNDARY_KEYS:
+            ky = boundary_arrays(3, key_set, order)[2]
+            for k in pk.KS:
+                for spacing in pk.SPACINGS:
+                    got = g.pick(f["gen"], ky, f["n_targets"], va.PickShape(k, spacing), target=tg)
+                    same(got, pk.boundary_expected(3, key_set, order, k, spacing))
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("order", pk.ORDERS)
+@pytest.mark.parametrize("n_contigs", [1, 3])
+def test_planted_spacing_triple_on_the_device(boundary, n_contigs, order):
+    """Cuts at x, x + 19 and x + 20 ('-'), and a '-' with its cut at x: at spacing 20 the first and the third are picked, the
+    second and the fourth are not - in every target of three or more, on both sides of 256 records."""
+    f = boundary(n_contigs)
+    planted = pk.boundary_planted(n_contigs, order)
+    assert sum(1 for t in planted if f["size_of"][t] > WAVE_CAP) >= 5 and sum(1 for t in planted if f["size_of"][t] <= WAVE_CAP) >= 5
+    for key_set in pk.BOUNDARY_KEYS:
+        arr, tg, ky = boundary_arrays(n_contigs, key_set, order)
+        for k in (4, 32):
+            got = f["gen"].pick(arr, ky, va.PickShape(k, pk.BOUNDARY_SPACING), target=tg, n_targets=f["n_targets"], rank=True)
+            same(got, pk.boundary_expected(n_contigs, key_set, order, k, pk.BOUNDARY_SPACING))
+            picks, counts, rank, _ = got
+            for t, p in planted.items():
+                assert picks[t, :2].tolist() == [p[0], p[2]] and counts[t] >= 2, (key_set, k, f["size_of"][t])
+                assert rank[p].tolist() == [0, pk.NONE, 1, pk.NONE][:len(p)], (key_set, k, f["size_of"][t])
+            got = f["gen"].pick(arr, ky, va.PickShape(k, pk.BOUNDARY_SPACING - 1), target=tg, n_targets=f["n_targets"], rank=True)
+            same(got, pk.boundary_expected(n_contigs, key_set, order, k, pk.BOUNDARY_SPACING - 1))
+            picks, _, rank, _ = got
+            for t, p in planted.items():   # one base less and the second no longer conflicts with the first; the fourth still does
+                assert picks[t, :2].tolist() == p[:2] and rank[p[3:]].tolist() == [pk.NONE] * len(p[3:]), (key_set, k, f["size_of"][t])
+            got = f["gen"].pick(arr, ky, va.PickShape(k, 1), target=tg, n_targets=f["n_targets"], rank=True)
+            same(got, pk.boundary_expected(n_contigs, key_set, order, k, 1))
+            for t, p in planted.items():   # spacing 1: only the '-' whose cut IS the first's conflicts (their positions are 11 apart)
+                assert got[0][t, :3].tolist() == p[:3] and got[2][p[3:]].tolist() == [pk.NONE] * len(p[3:]), (key_set, k, f["size_of"][t])
+
+
+# ---- one wave takes a large, a small and a large target in turn -------------------------------------------------------------
+def test_large_small_large_in_one_wave(ctx):
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n_waves = cus * wc.GROUPS_PER_CU * wc.WAVES_PER_GROUP
+    f = pk.same_wave(n_waves)
+    assert f["n_targets"] == 2 * n_waves + 3   # the launch is capped: wave w takes the targets w, w + n_waves, w + 2 n_waves
+    assert pk.same_wave_floors(n_waves) == [True, False, True, False, True, False]   # memory, register, memory; register, memory, register
+    want = pk.same_wave_expected(n_waves)
+    gen = ctx.load_genome(va.PackedGenome.from_sequences(["ACGT" * (f["lens"][0] // 4)]))
+    try:
+        got = gen.pick(pk.loci_array(f["loci"], va.LOCUS_DTYPE), np.array(f["key"], dtype=np.uint64), va.PickShape(pk.SAME_WAVE_K, pk.SAME_WAVE_SPACING),
+                       target=np.array(f["target"], dtype=np.uint32), n_targets=f["n_targets"], rank=True)
+        same(got, want)
+        assert got[3]["targets_picked"] == f["n_targets"]
+    finally:
+        gen.close()
+
+
+# ---- beyond one launch ------------------------------------------------------------------------------------------------------
+TILE = 1024  # candidates per tile of the `picked` passes (vsc_pick_device.h: kPickTile)
+
+
+def launch_waves():
+    return torch.cuda.get_device_properties(0).multi_processor_count * wc.GROUPS_PER_CU * wc.WAVES_PER_GROUP
+
+
+def same_arrays(got, want):
+    assert got[0].dtype == np.uint32 and got[0].shape == want[0].shape and np.array_equal(got[0], want[0])
+    assert np.array_equal(got[1], want[1]) and np.array_equal(got[2], want[2])
+    assert {k: got[3][k] for k in want[3]} == want[3]
+
+
+def test_more_candidates_than_a_launch_has_lanes_and_more_tiles_than_waves(ctx, small):
+    W, k = launch_waves(), 4
+    n = (W + 3) * TILE + 17
+    idx, target, key, n_targets, block = pk.replicas(n)
+    assert n > 64 * W and n_targets > 2 * W              # mark and scatter step twice; every wave of the select takes several targets
+    assert n_targets * k > 64 * W                        # rank steps twice
+    assert -(-n // TILE) > W and n % TILE                # more tiles than a launch has waves, the last one partial
+    want = pk.replicas_expected(n, k, 20, block)
+    loci = small["arr"][idx]
+    codes = np.arange(n, dtype=np.uint64) * np.uint64(3)
+    g = Guides.from_arrays(ctx, codes, loci)
+    try:
+        picks, counts, rank, stats, picked = g.pick(small["gen"], key, n_targets, va.PickShape(k, 20), target=target, picked=True)
+        same_arrays((picks, counts, rank, stats), want)
+        keep = np.flatnonzero(rank != pk.NONE)
+        assert len(keep) == stats["picks"] == len(picked) > TILE   # a work list longer than the scan's 1024 threads
+        pc, pl = picked.arrays()
+        assert pc.tobytes() == codes[keep].tobytes() and pl.tobytes() == loci[keep].tobytes()
+        picked.close()
+    finally:
+        g.close()
+
+
+def test_permuted_candidates_beyond_one_launch(small):
+    W, k = launch_waves(), 4
+    n = 2 * 64 * W + 77
+    idx, target, key, n_targets, block = pk.replicas(n, distinct=True)   # no target has two equal keys: no index decides
+    order = np.random.default_rng(23).permutation(n)
+    assert n > 64 * W and n_targets > 2 * W
+    t = target[order]
+    assert ((t[1:] == t[:-1]) & (t[1:] != pk.NONE)).mean() < 0.01         # hardly a run of equal targets is left
+    want = pk.permuted(pk.replicas_expected(n, k, 20, block), order)
+    got = small["gen"].pick(small["arr"][idx][order], key[order], va.PickShape(k, 20), target=target[order], n_targets=n_targets, rank=True)
+    same_arrays(got, want)
+
+
 # ---- pattern forms --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("pattern,cut", [("N" * 21 + "NNGRRT", 18), ("TTTV" + "N" * 23, 22)])
 def test_pattern_forms(ctx, small, pattern, cut):

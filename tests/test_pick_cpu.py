@@ -60,6 +60,48 @@ def test_host_on_shuffled_candidates():
             same(host(f["lens"], loci, target, key, f["n_targets"], k, spacing), want)
 
 
+def test_boundary_fixture_floors():
+    assert pk.boundary_floors() == list(pk.SIZES)
+
+
+@pytest.mark.parametrize("order", pk.ORDERS)
+@pytest.mark.parametrize("n_contigs", [1, 3])
+def test_host_equals_restatement_on_the_boundary_fixtures(n_contigs, order):
+    f = pk.boundary(n_contigs)
+    for key_set in pk.BOUNDARY_KEYS:
+        loci, target, key = pk.boundary_inputs(n_contigs, key_set, order)
+        for k in pk.KS:
+            for spacing in pk.SPACINGS:
+                same(host(f["lens"], loci, target, key, f["n_targets"], k, spacing), pk.boundary_expected(n_contigs, key_set, order, k, spacing))
+
+
+def test_host_equals_restatement_on_large_small_large():
+    assert pk.same_wave_floors(64) == [True, False, True, False, True, False]   # memory, register, memory; register, memory, register
+    f = pk.same_wave(64)
+    got = host(f["lens"], f["loci"], f["target"], f["key"], f["n_targets"], pk.SAME_WAVE_K, pk.SAME_WAVE_SPACING)
+    same(got, pk.same_wave_expected(64))
+
+
+def test_replicas_compose_and_permute_as_the_restatement_says():
+    """The expectation of the device's scale tests - composed from two restatement calls, then carried through a permutation -
+    against the restatement and the host on the whole input, at a size where that is quick."""
+    f = pk.small()
+    m = len(f["loci"])
+    for n, distinct in ((3 * m + 17, False), (2 * m, False), (4 * m + 400, True)):
+        idx, target, key, n_targets, block = pk.replicas(n, distinct)
+        assert n_targets == 14 * -(-n // m) and target.dtype == np.uint32 and key.dtype == np.uint64
+        loci = [f["loci"][i] for i in idx]
+        composed = pk.replicas_expected(n, 4, 20, block)
+        want = pk.pick(f["lens"], loci, [int(t) for t in target], [int(q) for q in key], n_targets, 4, 20)
+        same(composed, want)
+        same(host(f["lens"], loci, target, key, n_targets, 4, 20), want)
+        if distinct:
+            order = np.random.default_rng(17).permutation(n)
+            want = pk.pick(f["lens"], [loci[i] for i in order], [int(t) for t in target[order]], [int(q) for q in key[order]], n_targets, 4, 20)
+            same(pk.permuted(composed, order), want)
+            assert not np.array_equal(pk.permuted(composed, order)[0], composed[0])
+
+
 def test_all_keys_equal_picks_by_index():
     lens = [500]
     loci = [(0, 10 * i, i % 2) for i in range(40)]
