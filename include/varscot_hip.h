@@ -2381,6 +2381,135 @@ int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vs
                                       uint32_t to, const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid,
                                       vsc_pattern_guides **out);
 
+/* ---- known variation under candidate guides: population-robust and allele-specific design -------- */
+/*
+ * "Does this guide's own site carry known variation, where, and how common is it?" - the join of every candidate's site with a
+ * sorted list of variant intervals, on the device where the candidates lie.  Two uses: drop or down-rank guides whose
+ * protospacer or PAM overlaps common variants (population-robust design), and find the guides whose PAM or seed a heterozygous
+ * variant falls in, so that only one allele is cut (allele-specific design).  Integers only.
+ *
+ * SHAPE    site_len 16 .. 32;  zones: two bits per READ position j at bits 2 j, 2 j + 1 - the caller's label 0 .. 3 of the position
+ *          (the presets of the Python layer: 1 distal, 2 seed, 3 PAM, 0 a position of no interest such as the N of NGG); accept[2]:
+ *          four bits per read position (position j: nibble j & 15 of accept[j >> 4]), bit b = "read base b (A C G T) at j leaves
+ *          the site usable" (the R of NNGRRT accepts A and G; protospacer positions: 0).  No bit at a position from site_len on;
+ *          reserved fields 0.
+ * SITE     of a locus (c, p, strand) as in vsc_loci_edit: '+': c[p, p + site_len);  '-': its reverse complement.
+ * CLASS    as in vsc_loci_edit, tested in that order: invalid, not_resident, has_n, defined.  off_contig cannot occur.
+ * VARIANTS n_v records of 16 bytes { contig, pos, span_alt, weight }.  span = span_alt & 0xFFFF, 1 .. 65535: the variant touches
+ *          the forward bases [pos, pos + span), which lie inside the contig.  alt = span_alt >> 16 & 7: 0 .. 3 the forward-strand
+ *          alternative base of an SNV (span == 1), 4 any other change (indel, MNV); other bits 0.  weight <= 0xFFFFFFFE: the
+ *          caller's integer cost.  Ascending (contig, pos); TIES ARE ALLOWED (multi-allelic sites) and keep their order.  A
+ *          variant's index is its place in the array.  n_v <= 0xFFFFFFFE.
+ * OVERLAP  variant k overlaps a site on its contig iff pos_k < p + site_len and pos_k + span_k > p.  The touched forward positions f
+ *          are the intersection; the touched read position of f is j = f - p on '+', j = site_len - 1 - (f - p) on '-'.
+ * SILENT   an overlapping SNV is silent iff nibble j of accept has bit b set, b = alt on '+', b = 3 - alt on '-'.
+ * DISRUPTING every other overlapping variant.
+ * TOP      of an overlapping variant: the largest zone label among its touched read positions.
+ * ROW      four uint32 per candidate, all 0xFFFFFFFF (VSC_VARIATION_UNDEFINED) unless the class is defined:
+ *          by_zone: byte z = min(255, disrupting variants with top z);  silent: the silent variants;
+ *          cost = min(0xFFFFFFFE, sum of weight over the disrupting variants) - summed in 64 bits, then clamped: a clamped sum of
+ *          non-negatives does not depend on the order;  max_weight: the largest weight among them, 0 when there is none.
+ * PAIR     16 bytes { candidate, variant, info, weight } per overlapping variant, silent ones included;
+ *          info = smallest touched read position | touched positions << 8 | top << 16 | silent << 18.
+ *          Order: ascending (candidate, variant).
+ * COVERAGE optional, two uint32 per variant: its disrupting pairs and its silent pairs.
+ * FILTER   keep a candidate iff it is defined, cost <= max_cost, every byte z of by_zone <= byte z of max_by_zone (255: no bound),
+ *          and (require_zones == 0, or a zone z with bit z of require_zones set has a non-zero byte).  The last condition is the
+ *          allele-specific mode: "at least one disrupting variant in PAM or seed".  Survivors keep their input order.
+ *
+ * The output is a function of the inputs alone: it does not depend on launch shape or wave order, nor on the block of the lookup
+ * below.  The coverage counters use integer add atomics, which commute; nothing else depends on an atomic's order, and the pairs
+ * have no append cursor: count pass over the rows, scan, write pass over tiles of 1 024 candidates.
+ *
+ * The lookup.  A lower bound over positions finds points, not intervals: a long deletion that starts far to the left still
+ * overlaps.  At upload the device builds gpos[k] = contig offset + pos (32-bit, as everywhere) and reach[k] = max over i <= k of
+ * (gpos[i] + span[i]), which never decreases.  The first variant that can overlap a site at global g0 is the first k with
+ * reach[k] > g0; the walk runs from there while gpos[k] < g0 + site_len and tests OVERLAP per variant.  Variants stay inside
+ * contigs and contigs lie one base apart, so global overlap is overlap on the contig.  The first k is found through a block
+ * table, first[b] = the first k with reach[k] > b * 256: one table load, then a search confined to [first[b], first[b + 1]].
+ *
+ * vsc_variation_host is the definition on the host and needs no device: contigs gives the contig lengths (they lie one base
+ * apart, as vsc_pack_genome lays them), the other arrays are host arrays.  It has no planes, so its classes are invalid and
+ * defined only.  rows: 4 n words.  It goes through the functions the kernels call, the lookup included.
+ *
+ * vsc_loci_variation: loci are host entries in any order, duplicates allowed.  rows (optional): 4 n words.  The pairs follow
+ * vsc_loci_edit's contract: *n_pairs (optional) is always the full count; pairs == NULL only counts; a count above `capacity` is
+ * VSC_ERR_RANGE, and then nothing is written to `pairs`, while rows, coverage, stats and *n_pairs are valid.  coverage (optional):
+ * 2 n_v entries.  stats (optional): the candidates by class (the five counts add up to n), the candidates with a disrupting
+ * variant, the pairs, the variants with a pair, the rows kernel's time and the call's wall time in milliseconds.  n == 0: VSC_OK,
+ * nothing is launched, the coverage is 0.  vsc_guides_variation works over the candidates where they lie on the device and
+ * requires site_len == 23; the host-only object of vsc_multi_guides_enumerate goes the vsc_loci_variation way.
+ * vsc_pattern_guides_variation is the same for vsc_pattern_guides: the CALLER vouches for site_len, as in the edit calls.
+ *
+ * vsc_guides_filter_variation / vsc_pattern_guides_filter_variation: *out = the candidates of `in` that pass FILTER - codes and
+ * loci copied unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass, as vsc_guides_filter_edit.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a shape outside SHAPE or
+ * with a non-zero reserved field; a filter with require_zones > 15 or a non-zero reserved field; variants not ascending; on an
+ * unknown contig; a span of 0 or beyond its contig; alt 0 .. 3 with span != 1; alt > 4 or other bits of span_alt; a weight of
+ * 0xFFFFFFFF; NULL arguments; a genome or object of another context; site_len != 23 for vsc_guides.  VSC_ERR_RANGE: n or n_v above
+ * 0xFFFFFFFE; more than 0xFFFFFFFE pairs.  Uploads and results use context scratch; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: a vsc_multi_* entry; guides that exist only on the alternative allele (PAM-creating variants) - enumerate over
+ * the alternative-allele windows genome (vsc_windows_build) for those; genotype or phase handling: every variant stands alone.
+ */
+#define VSC_VARIATION_UNDEFINED 0xFFFFFFFFu
+#define VSC_VARIANT_OTHER 4u
+typedef struct {
+    uint32_t site_len;
+    uint32_t reserved0; /* 0 */
+    uint64_t zones;
+    uint64_t accept[2];
+    uint32_t reserved[4]; /* 0 */
+} vsc_variation_shape;
+typedef struct {
+    uint32_t contig, pos;
+    uint32_t span_alt; /* span | alt << 16 */
+    uint32_t weight;
+} vsc_variant;
+typedef struct {
+    uint32_t candidate, variant;
+    uint32_t info; /* first | touched << 8 | top << 16 | silent << 18 */
+    uint32_t weight;
+} vsc_variation_pair;
+typedef struct {
+    uint32_t max_cost;
+    uint32_t max_by_zone; /* byte z: the bound of zone z, 255 = none */
+    uint32_t require_zones; /* bit z: zone z; 0: nothing is required */
+    uint32_t reserved; /* 0 */
+} vsc_variation_filter;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t with_disrupting, pairs, variants_covered;
+    double kernel_ms, wall_ms;
+    uint64_t reserved[2]; /* 0 */
+} vsc_variation_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_variation_shape) == 48 && sizeof(vsc_variant) == 16 && sizeof(vsc_variation_pair) == 16 &&
+              sizeof(vsc_variation_filter) == 16 && sizeof(vsc_variation_stats) == 96, "vsc_variation_* layout");
+#else
+_Static_assert(sizeof(vsc_variation_shape) == 48 && sizeof(vsc_variant) == 16 && sizeof(vsc_variation_pair) == 16 &&
+               sizeof(vsc_variation_filter) == 16 && sizeof(vsc_variation_stats) == 96, "vsc_variation_* layout");
+#endif
+int vsc_variation_host(const vsc_contig *contigs, uint32_t n_contigs, const vsc_locus *loci, uint64_t n, const vsc_variation_shape *shape,
+                       const vsc_variant *variants, uint64_t n_v, uint32_t *rows /* 4 n, optional */, vsc_variation_pair *pairs /* optional */,
+                       uint64_t capacity, uint64_t *n_pairs /* optional */, uint32_t *coverage /* 2 n_v, optional */);
+int vsc_loci_variation(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                       const vsc_variation_shape *shape, const vsc_variant *variants /* host */, uint64_t n_v,
+                       uint32_t *rows /* host, 4 n, optional */, vsc_variation_pair *pairs /* host, optional */, uint64_t capacity,
+                       uint64_t *n_pairs /* optional */, uint32_t *coverage /* host, 2 n_v, optional */, vsc_variation_stats *stats /* optional */);
+int vsc_guides_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_variation_shape *shape,
+                         const vsc_variant *variants, uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity,
+                         uint64_t *n_pairs, uint32_t *coverage, vsc_variation_stats *stats);
+int vsc_pattern_guides_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_variation_shape *shape,
+                                 const vsc_variant *variants, uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity,
+                                 uint64_t *n_pairs, uint32_t *coverage, vsc_variation_stats *stats);
+int vsc_guides_filter_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_variation_shape *shape,
+                                const vsc_variant *variants, uint64_t n_v, const vsc_variation_filter *filter, vsc_guides **out);
+int vsc_pattern_guides_filter_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_variation_shape *shape,
+                                        const vsc_variant *variants, uint64_t n_v, const vsc_variation_filter *filter,
+                                        vsc_pattern_guides **out);
+
 /* ---- prime-editing guide design: pegRNA extensions per edit --------------------------------------- */
 /*
  * Prime editors write substitutions, insertions and deletions behind a nick.  "Which candidates nick close enough upstream of my

@@ -89,6 +89,11 @@ int vsc_debug_prime_bitmap(vsc_ctx *ctx, int on);
  * The kernel is grid-stride: no output bit depends on it (tools/prime_bench.py times several against each other). */
 int vsc_debug_prime_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
 
+/* The block of the variation lookup's table on this context: log2 of the global positions per entry, 4 .. 32, or 0 =
+ * the default (8).  At 32 the table has one block and the lookup is the plain lower bound over all variants.  No output bit
+ * depends on it; the tests compare the smallest and a large block, tools/variation_bench.py times them against each other. */
+int vsc_debug_variation_block_bits(vsc_ctx *ctx, uint32_t bits);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

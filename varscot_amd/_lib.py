@@ -391,6 +391,42 @@ class EditStats(C.Structure):
 assert C.sizeof(EditShapeStruct) == 32 and C.sizeof(EditStats) == 96 and EDIT_PAIR_DTYPE.itemsize == 16 and EDIT_TARGET_DTYPE.itemsize == 8
 
 
+VARIATION_UNDEFINED = 0xFFFFFFFF  # VSC_VARIATION_UNDEFINED
+VARIANT_OTHER = 4  # VSC_VARIANT_OTHER: the alt of a variant that is no SNV
+VARIANT_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("span_alt", "<u4"), ("weight", "<u4")])
+VARIATION_PAIR_DTYPE = np.dtype([("candidate", "<u4"), ("variant", "<u4"), ("info", "<u4"), ("weight", "<u4")])
+
+
+class VariationShapeStruct(C.Structure):
+    """vsc_variation_shape: the site's length, two bits of zone label and four bits of accepted read bases per read position."""
+    _fields_ = [("site_len", C.c_uint32), ("reserved0", C.c_uint32), ("zones", C.c_uint64), ("accept", C.c_uint64 * 2),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class VariationFilterStruct(C.Structure):
+    """vsc_variation_filter: the largest cost, the largest count per zone (a byte each, 255: none) and the mask of zones of which
+    one must hold a disrupting variant (0: nothing is required)."""
+    _fields_ = [("max_cost", C.c_uint32), ("max_by_zone", C.c_uint32), ("require_zones", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class VariationStats(C.Structure):
+    """vsc_variation_stats: the candidates of a call by class (the five counts add up to n), the candidates with a disrupting
+    variant, the pairs, the variants with a pair, the rows kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("with_disrupting", C.c_uint64), ("pairs", C.c_uint64), ("variants_covered", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n", "with_disrupting", "pairs",
+                                                "variants_covered")}
+        d.update(kernel_ms=float(self.kernel_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(VariationShapeStruct) == 48 and C.sizeof(VariationFilterStruct) == 16 and C.sizeof(VariationStats) == 96
+assert VARIANT_DTYPE.itemsize == 16 and VARIATION_PAIR_DTYPE.itemsize == 16
+
+
 PRIME_UNDEFINED = 0xFFFFFFFF  # VSC_PRIME_UNDEFINED
 PRIME_EDIT_DTYPE = np.dtype([("contig", "<u4"), ("pos", "<u4"), ("del_len", "<u2"), ("ins_len", "<u2"), ("ins", "<u4")])
 PRIME_PAIR_DTYPE = np.dtype([("candidate", "<u4"), ("edit", "<u4"), ("info", "<u4"), ("ext", "<u4")])
@@ -729,6 +765,18 @@ SYMBOLS = [
                                            C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
     ("vsc_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_variation_host", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp,
+                                     C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    ("vsc_loci_variation", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                     C.POINTER(C.c_uint64), _vp, C.POINTER(VariationStats)]),
+    ("vsc_guides_variation", C.c_int, [_vp, _vp, _vp, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                       C.POINTER(C.c_uint64), _vp, C.POINTER(VariationStats)]),
+    ("vsc_pattern_guides_variation", C.c_int, [_vp, _vp, _vp, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
+                                               C.POINTER(C.c_uint64), _vp, C.POINTER(VariationStats)]),
+    ("vsc_guides_filter_variation", C.c_int, [_vp, _vp, _vp, C.POINTER(VariationShapeStruct), _vp, C.c_uint64,
+                                              C.POINTER(VariationFilterStruct), C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_variation", C.c_int, [_vp, _vp, _vp, C.POINTER(VariationShapeStruct), _vp, C.c_uint64,
+                                                      C.POINTER(VariationFilterStruct), C.POINTER(_vp)]),
     ("vsc_sam_order", None, [_vp, C.c_uint64, _vp, _vp]),
 ]
 # include/varscot_hip_debug.h (test / experiment hooks, not part of the drop-in boundary)
@@ -747,6 +795,7 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_sites_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_prime_bitmap", C.c_int, [_vp, C.c_int]),
     ("vsc_debug_prime_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
 ]
 
 _lib = None

@@ -1476,6 +1476,260 @@ def edit_pick_inputs(pairs, loci, extra_columns=()):
     return lo[cand], pr["target"].astype(np.uint32), pick_key(cols, bits)
 
 
+# ---- known variation under candidate guides -----------------------------------------------------------------
+VARIATION_UNDEFINED = _lib.VARIATION_UNDEFINED  # the four words of the row of a candidate whose site is undefined
+VARIANT_OTHER = _lib.VARIANT_OTHER              # the alt of a variant that is no SNV
+VARIANT_DTYPE = _lib.VARIANT_DTYPE
+VARIATION_PAIR_DTYPE = _lib.VARIATION_PAIR_DTYPE
+VARIATION_ZONES = ("none", "distal", "seed", "pam")  # the labels the presets use
+VARIANT_WEIGHT_ONE = 1 << 20                    # variant_weight's scale: cost / 2^20 = -ln P(no disrupting variant)
+_IUPAC_BITS = {"A": 1, "C": 2, "G": 4, "T": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7,
+               "N": 15}
+
+
+class VariationShape:
+    """vsc_variation_shape: how known variants count against a site.  site_len 16..32 is the candidates' length; zones: one
+    label 0..3 per read position (a sequence of site_len numbers, or the packed integer: two bits per position) - the presets
+    use 1 distal, 2 seed, 3 PAM, 0 a position of no interest such as the N of NGG; accept: per read position the read bases
+    that leave the site usable, as a sequence of site_len IUPAC letters ("-" or "": none) or numbers 0..15 (bit b: base b of A
+    C G T), or the packed (low, high) pair of integers: four bits per position.  validate=False passes the numbers to the
+    library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, zones=0, accept=(0, 0), validate=True):
+        self.site_len = int(site_len)
+        if isinstance(zones, (int, np.integer)):
+            self.zones = int(zones)
+        else:
+            z = [int(v) for v in zones]
+            if len(z) != self.site_len or any(not 0 <= v <= 3 for v in z):
+                raise ValueError("zones holds one label 0..3 per read position")
+            self.zones = sum(v << (2 * j) for j, v in enumerate(z))
+        if isinstance(accept, tuple) and len(accept) == 2 and all(isinstance(v, (int, np.integer)) for v in accept):
+            self.accept = (int(accept[0]), int(accept[1]))
+        else:
+            a = [(_IUPAC_BITS[v.upper()] if v not in ("", "-") else 0) if isinstance(v, str) else int(v) for v in accept]
+            if len(a) != self.site_len or any(not 0 <= v <= 15 for v in a):
+                raise ValueError("accept holds one IUPAC letter or number 0..15 per read position")
+            self.accept = (sum(v << (4 * j) for j, v in enumerate(a[:16])), sum(v << (4 * j) for j, v in enumerate(a[16:])))
+        if validate and not (16 <= self.site_len <= 32 and 0 <= self.zones < 1 << (2 * self.site_len) and 0 <= self.accept[0] < 1 << 64
+                             and 0 <= self.accept[1] < 1 << (4 * (self.site_len - 16))):
+            raise ValueError("a variation shape has site_len 16..32 and no zone or accept bit at a position from site_len on")
+
+    def zone(self, j):
+        return self.zones >> (2 * j) & 3
+
+    def accepts(self, j):
+        return self.accept[j >> 4] >> (4 * (j & 15)) & 15
+
+    def _struct(self):
+        m = (1 << 64) - 1
+        return _lib.VariationShapeStruct(self.site_len & 0xFFFFFFFF, 0, self.zones & m, (C.c_uint64 * 2)(self.accept[0] & m, self.accept[1] & m),
+                                         (C.c_uint32 * 4)(0, 0, 0, 0))
+
+    def __repr__(self):
+        return "VariationShape(site_len=%d, zones=%r, accept=%r)" % (self.site_len, "".join(str(self.zone(j)) for j in range(self.site_len)),
+                                                                      [self.accepts(j) for j in range(self.site_len)])
+
+
+def variation_shape_from_pattern(pattern, protospacer, seed_len):
+    """The VariationShape of an IUPAC pattern of 16..32 letters with the protospacer (start, length) in read positions
+    (pattern_protospacer gives it for a preset): inside the protospacer the seed_len bases next to the PAM are seed (2), the
+    others distal (1), and no base is accepted there; outside it a position is PAM (3) and accepts the pattern's IUPAC set -
+    an N is of no interest (0) and accepts every base.  The PAM lies on one side of the protospacer: behind it (SpCas9: the
+    seed is the protospacer's end) or in front of it (Cas12a: its start)."""
+    p = pattern.decode() if isinstance(pattern, bytes) else pattern
+    start, length = int(protospacer[0]), int(protospacer[1])
+    n = len(p)
+    if not (0 <= start and 1 <= length and start + length <= n) or not 0 <= int(seed_len) <= length:
+        raise ValueError("the protospacer lies inside the pattern, and the seed inside the protospacer")
+    if start > 0 and start + length < n:
+        raise ValueError("the PAM lies on one side of the protospacer")
+    seed_first = start if start > 0 else start + length - int(seed_len)  # PAM in front: the first bases; behind: the last
+    zones, accept = [], []
+    for j, ch in enumerate(p.upper()):
+        if start <= j < start + length:
+            zones.append(2 if seed_first <= j < seed_first + int(seed_len) else 1)
+            accept.append(0)
+        else:
+            if ch not in _IUPAC_BITS:
+                raise ValueError("%r is no IUPAC letter" % ch)
+            zones.append(0 if ch == "N" else 3)
+            accept.append(_IUPAC_BITS[ch])
+    return VariationShape(n, zones, accept)
+
+
+# SpCas9 NGG with a 10-base seed (read positions 10..19; the N at 20 is of no interest, the GG accept G only), and the other
+# rows of PATTERNS by the same rule.  The seed's length is a convention (8 to 12 bases are in use); a caller who knows better
+# makes a shape.
+VARIATION_SHAPES = {"SpCas9": variation_shape_from_pattern("N" * 20 + "NGG", (0, 20), 10),
+                    "SaCas9": variation_shape_from_pattern("N" * 21 + "NNGRRT", (0, 21), 10),
+                    "Cas12a": variation_shape_from_pattern("TTTV" + "N" * 23, (4, 23), 8)}
+
+
+def _variation_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in VARIATION_SHAPES:
+            raise ValueError("%s names one of %s, or is a VariationShape" % (what, ", ".join(sorted(VARIATION_SHAPES))))
+        return VARIATION_SHAPES[shape]
+    if not isinstance(shape, VariationShape):
+        raise ValueError("%s must be a VariationShape or the name of a preset" % what)
+    return shape
+
+
+def variant_weight(af):
+    """The integer weight of a variant of allele frequency af (a number or an array): round(-log1p(-af) * 2^20), at most
+    0xFFFFFFFE (af >= 1 included).  Under independence the cost of a candidate - the sum over its disrupting variants - is then
+    -ln P(a haplotype carries none of them) in units of 2^-20; carrier_free turns it back."""
+    a = np.asarray(af, dtype=np.float64)
+    if (a < 0).any() or np.isnan(a).any():
+        raise ValueError("an allele frequency is a number in 0 .. 1")
+    with np.errstate(divide="ignore"):
+        x = np.where(a >= 1.0, np.inf, -np.log1p(-np.minimum(a, 1.0)) * float(VARIANT_WEIGHT_ONE))
+    w = np.minimum(np.floor(x + 0.5), float(0xFFFFFFFE)).astype(np.uint32)
+    return int(w) if w.ndim == 0 else w
+
+
+def carrier_free(cost):
+    """exp(-cost / 2^20): the probability that a haplotype carries no disrupting variant, from a row's cost made of
+    variant_weight weights (a clamped cost, 0xFFFFFFFE, gives practically 0)."""
+    c = np.asarray(cost, dtype=np.float64)
+    out = np.exp(-c / float(VARIANT_WEIGHT_ONE))
+    return float(out) if out.ndim == 0 else out
+
+
+def site_variants(rows, lengths=None):
+    """The variants of a variation call as the library takes them: (VARIANT_DTYPE array in ascending (contig, pos) - rows of
+    one position keep the caller's order -, order, inverse).  order[k] is the caller's index of sorted variant k, inverse[i]
+    the sorted index of the caller's row i.  rows: (contig, pos, ref, alt[, weight]) in any order - pos the 0-based position of
+    ref's first base on the contig, ref and alt VCF-style allele texts, weight an integer 0..0xFFFFFFFE (0 without one).
+    The alleles are normalised: the common prefix, then the common suffix is trimmed; what is left is an SNV (span 1 with its
+    alt), a deletion (its deleted bases), an insertion (the two bases that flank the insertion point; one at a contig's
+    first base - and at its end, for which lengths= gives the contig lengths), or anything else (alt 4 over the bases of ref:
+    an MNV its length).  Equal alleles, symbolic alleles and spans above 65535 are refused."""
+    rec, keys = [], []
+    for row in rows:
+        if len(row) not in (4, 5):
+            raise ValueError("a variant is (contig, pos, ref, alt[, weight])")
+        contig, pos = int(row[0]), int(row[1])
+        ref, alt = (x.decode() if isinstance(x, bytes) else str(x) for x in (row[2], row[3]))
+        ref, alt = ref.upper(), alt.upper()
+        weight = int(row[4]) if len(row) == 5 else 0
+        if not (0 <= contig <= 0xFFFFFFFF and 0 <= pos <= 0xFFFFFFFF and 0 <= weight <= 0xFFFFFFFE):
+            raise ValueError("contig and pos are unsigned 32-bit numbers, a weight is at most 0xFFFFFFFE")
+        if not ref or not alt or any(ch not in "ACGTN" for ch in ref + alt):
+            raise ValueError("alleles are texts over ACGTN (symbolic alleles are not taken): %r -> %r" % (ref, alt))
+        k = 0
+        while k < len(ref) and k < len(alt) and ref[k] == alt[k]:
+            k += 1
+        ref, alt, pos = ref[k:], alt[k:], pos + k
+        k = 0
+        while k < len(ref) and k < len(alt) and ref[-1 - k] == alt[-1 - k]:
+            k += 1
+        if k:
+            ref, alt = ref[:-k], alt[:-k]
+        if not ref and not alt:
+            raise ValueError("a variant's alleles are equal")
+        if len(ref) == 1 and len(alt) == 1:
+            span, code = 1, "ACGT".index(alt) if alt in "ACGT" else VARIANT_OTHER
+        elif not ref:  # an insertion in front of pos: the bases on either side of it
+            first = max(pos - 1, 0)
+            last = pos + 1
+            if lengths is not None and contig < len(lengths):
+                last = min(last, int(lengths[contig]))
+            pos, span, code = first, last - first, VARIANT_OTHER
+        else:
+            span, code = len(ref), VARIANT_OTHER
+        if not 1 <= span <= 65535 or pos > 0xFFFFFFFF:
+            raise ValueError("a variant spans 1 .. 65535 bases")
+        rec.append((contig, pos, span | code << 16, weight))
+        keys.append(contig << 32 | pos)
+    out = np.zeros(len(rec), dtype=_lib.VARIANT_DTYPE)
+    order = np.argsort(np.asarray(keys, dtype=np.uint64), kind="stable").astype(np.int64) if rec else np.zeros(0, dtype=np.int64)
+    for k, i in enumerate(order):
+        out[k] = rec[int(i)]
+    inverse = np.empty(len(rec), dtype=np.int64)
+    inverse[order] = np.arange(len(rec), dtype=np.int64)
+    return out, order, inverse
+
+
+def unpack_variation_row(rows):
+    """(by_zone uint8[n, 4], silent, cost, max_weight) of variation rows uint32[n, 4]: the disrupting variants by their top zone
+    (255: that many or more), the silent variants, the clamped sum and the largest of the disrupting variants' weights.  A row
+    of an undefined site is VARIATION_UNDEFINED four times: 255 in every zone."""
+    r = np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
+    by_zone = np.stack([(r[:, 0] >> np.uint32(8 * z)) & np.uint32(0xFF) for z in range(4)], axis=1).astype(np.uint8)
+    return by_zone, r[:, 1].copy(), r[:, 2].copy(), r[:, 3].copy()
+
+
+def unpack_variation_info(info):
+    """(first, touched, top, silent) of a variation pair's info word (or an array of them): the smallest touched read position,
+    the number of touched read positions, the largest zone label among them, and 1 for a silent SNV."""
+    i = np.asarray(info, dtype=np.uint32)
+    return i & np.uint32(0xFF), (i >> np.uint32(8)) & np.uint32(0xFF), (i >> np.uint32(16)) & np.uint32(3), (i >> np.uint32(18)) & np.uint32(1)
+
+
+def variation_pick_inputs(pairs, loci, zones=(2, 3), extra_columns=()):
+    """What Genome.pick takes for "of every variant the K guides that tell its alleles apart best": (loci[pairs.candidate],
+    pairs.variant, key, index) over the DISRUPTING pairs whose top zone is in `zones` (default: seed and PAM) - one pick
+    candidate per such pair, its target the pair's variant, its key made with pick_key: the first column is the top zone (2
+    bits: PAM before seed).  index holds the kept pairs' places in `pairs`.  extra_columns: (values per CANDIDATE of the
+    variation call, bits) in priority order behind it - unsigned integer arrays, larger is better (pick_column makes them)."""
+    pr = np.asarray(pairs, dtype=_lib.VARIATION_PAIR_DTYPE)
+    lo = _loci(loci, len(loci))
+    _, _, top, silent = unpack_variation_info(pr["info"])
+    index = np.flatnonzero((silent == 0) & np.isin(top, np.asarray(sorted({int(z) for z in zones}), dtype=np.uint32)))
+    cand = pr["candidate"][index].astype(np.int64)
+    cols, bits = [top[index].astype(np.uint64)], [2]
+    for values, b in extra_columns:
+        v = np.asarray(values)
+        if v.dtype.kind != "u" or v.ndim != 1 or len(v) != len(lo):
+            raise ValueError("an extra column is a one-dimensional unsigned integer array with one value per candidate")
+        cols.append(v[cand])
+        bits.append(int(b))
+    return lo[cand], pr["variant"][index].astype(np.uint32), pick_key(cols, bits), index
+
+
+def _variants_in(variants):
+    """(sorted VARIANT_DTYPE array, order, inverse) of what a variation call is given: a VARIANT_DTYPE array as the library takes
+    it (passed as it is: order and inverse None), or rows for site_variants."""
+    if isinstance(variants, np.ndarray) and variants.dtype == _lib.VARIANT_DTYPE:
+        return np.ascontiguousarray(variants), None, None
+    return site_variants(variants)
+
+
+def variation_host(contigs, loci, shape, variants, pairs=True, coverage=False):
+    """vsc_variation_host: the definition of the variation join as host code - no device.  contigs: a CONTIG_DTYPE array (a
+    PackedGenome's .contigs); loci, shape, variants: as Genome.variation takes them.  Without planes a site's class is invalid
+    or defined only.  Returns (rows uint32[n, 4], pairs or None, coverage uint32[n_v, 2] or None), as Genome.variation."""
+    shape = _variation_shape(shape)
+    ct = np.ascontiguousarray(contigs, dtype=CONTIG_DTYPE)
+    _, loci = _pick_loci(loci)
+    lo = _loci(loci, len(loci))
+    vr, order, inverse = _variants_in(variants)
+    n, n_v = len(lo), len(vr)
+    rows = np.empty((n, 4), dtype=np.uint32)
+    cov = np.empty((n_v, 2), dtype=np.uint32) if coverage else None
+    sh = shape._struct()
+    count = C.c_uint64()
+    L = lib()
+    check(L.vsc_variation_host(ptr(ct), len(ct), ptr(lo), n, C.byref(sh), ptr(vr) if n_v else None, n_v, ptr(rows), None, 0, C.byref(count),
+                               ptr(cov)))
+    pr = None
+    if pairs:
+        pr = np.empty(int(count.value), dtype=_lib.VARIATION_PAIR_DTYPE)
+        check(L.vsc_variation_host(ptr(ct), len(ct), ptr(lo), n, C.byref(sh), ptr(vr) if n_v else None, n_v, None, ptr(pr), len(pr),
+                                   C.byref(count), None))
+    return rows, _variation_pairs_out(pr, order), (cov[inverse] if cov is not None and inverse is not None else cov)
+
+
+def _variation_pairs_out(pr, order):
+    """The pairs with the variant's index in the caller's order, ascending (candidate, variant)."""
+    if pr is None or order is None:
+        return pr
+    pr["variant"] = order[pr["variant"].astype(np.int64)].astype(np.uint32)
+    return pr[np.lexsort((pr["variant"], pr["candidate"]))]
+
+
 # ---- prime-editing guide design (DESIGN 4.30) -----------------------------------------------------------------------------
 PRIME_UNDEFINED = _lib.PRIME_UNDEFINED  # both words of the row of a candidate whose context is undefined
 PRIME_EDIT_DTYPE = _lib.PRIME_EDIT_DTYPE
@@ -2591,7 +2845,8 @@ class Genome:
                           max_guides=0, params=None, efficiency=None, min_efficiency=None, microhomology=None,
                           min_out_of_frame=None, min_microhomology=None, edit=None, edit_targets=None, min_editable=None,
                           max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None,
-                          prime_edits=None, prime_allow_weak=None):
+                          prime_edits=None, prime_allow_weak=None, variation=None, variants=None, max_variant_cost=None,
+                          max_variants_by_zone=None, require_variant_zones=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2619,7 +2874,12 @@ class Genome:
         prime= a PrimeShape whose site_len is the pattern's length: the candidates' (pbs, n_pairs) rows (uint32[n, 2],
         vsc_pattern_guides_prime) come last of all.  prime_edits= (contig, pos, del_len, ins) rows / prime_allow_weak= (both need
         prime=): only the candidates whose context is defined, that - with edits - can write one of them, and - with
-        prime_allow_weak=False - whose PBS is not WEAK (vsc_pattern_guides_filter_prime), after the edit and effects filters."""
+        prime_allow_weak=False - whose PBS is not WEAK (vsc_pattern_guides_filter_prime), after the edit and effects filters.
+        variation= a VariationShape whose site_len is the pattern's length (or the name of a preset of VARIATION_SHAPES) with
+        variants= (as Genome.variation takes them): the candidates' variation rows (uint32[n, 4], vsc_pattern_guides_variation)
+        come last of all.  max_variant_cost= / max_variants_by_zone= four bounds (255: none) / require_variant_zones= zone
+        numbers or names of VARIATION_ZONES (all need variation=): only the candidates that pass the variation filter
+        (vsc_pattern_guides_filter_variation), after the other filters."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -2631,6 +2891,7 @@ class Genome:
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, len(p))
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, len(p))
+        vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -2642,7 +2903,8 @@ class Genome:
                                            L.vsc_pattern_guides_free, ed,
                                            (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit), fx,
                                            (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects), pe,
-                                           (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime))
+                                           (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime), vr,
+                                           (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -2673,7 +2935,9 @@ class Genome:
         "oof" and "mh".  (picks, counts) come last of all.  edit= (and its options), as enumerate_pattern takes them: only the
         survivors are searched; the edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= /
         require_effect= / forbid_effect=: as enumerate_pattern; the effect rows come after the edit rows.  prime= /
-        prime_edits= / prime_allow_weak=: as enumerate_pattern; the prime rows come after the effect rows."""
+        prime_edits= / prime_allow_weak=: as enumerate_pattern; the prime rows come after the effect rows.  variation= /
+        variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_pattern; only the survivors
+        are searched, and the variation rows come after the prime rows."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -2791,10 +3055,10 @@ class Genome:
         return pairs
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
-                          fx=None, fx_fns=None, pe=None, pe_fns=None):
+                          fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs before the edit rows before the effect rows before the prime rows.  held[0] is replaced as
-        _eff_on_handle replaces it."""
+        the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows.
+        held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
         if mh is not None:
@@ -2805,6 +3069,8 @@ class Genome:
             self._effects_on_handle(held, ed[0], fx, count_fn, fx_fns[0], fx_fns[1], free_fn, rows=False)
         if pe is not None:
             self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, rows=False)
+        if va is not None:
+            self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -2816,6 +3082,8 @@ class Genome:
             extra += (self._effects_on_handle(held, ed[0], fx[:2] + (0, 0) + fx[4:], count_fn, fx_fns[0], fx_fns[1], free_fn),)
         if pe is not None:
             extra += (self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, filt=False),)
+        if va is not None:
+            extra += (self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, filt=False),)
         return extra
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
@@ -3024,6 +3292,102 @@ class Genome:
             cov = cov[inverse]
         if order is not None:
             stats["target_order"] = order
+        return rows, pr, cov, stats
+
+    # ---- known variation under candidates (vsc_*_variation) --------------------------------------------------------------------
+    @staticmethod
+    def _variation_args(shape, variants, max_cost, max_by_zone, require_zones, site_len):
+        """(shape, sorted variants, order, inverse, VariationFilterStruct or None) - or None without a shape."""
+        if shape is None:
+            if variants is not None or max_cost is not None or max_by_zone is not None or require_zones is not None:
+                raise ValueError("variants / max_variant_cost / max_variants_by_zone / require_variant_zones need variation=shape")
+            return None
+        shape = _variation_shape(shape, "variation")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        if variants is None:
+            raise ValueError("variation= needs variants=")
+        vr, order, inverse = _variants_in(variants)
+        filt = None
+        if max_cost is not None or max_by_zone is not None or require_zones is not None:
+            cost = 0xFFFFFFFF if max_cost is None else int(max_cost)
+            by = [255, 255, 255, 255] if max_by_zone is None else [int(v) for v in max_by_zone]
+            req = 0
+            for z in (() if require_zones is None else require_zones):
+                z = VARIATION_ZONES.index(z) if isinstance(z, str) and z in VARIATION_ZONES else z
+                if isinstance(z, str) or not 0 <= int(z) <= 3:
+                    raise ValueError("a required zone is 0..3 or one of %s" % ", ".join(VARIATION_ZONES))
+                req |= 1 << int(z)
+            if not 0 <= cost <= 0xFFFFFFFF or len(by) != 4 or any(not 0 <= v <= 255 for v in by):
+                raise ValueError("max_variant_cost is an unsigned 32-bit number, max_variants_by_zone four numbers 0..255 (255: no bound)")
+            filt = _lib.VariationFilterStruct(cost, by[0] | by[1] << 8 | by[2] << 16 | by[3] << 24, req, 0)
+        return shape, vr, order, inverse, filt
+
+    def _variation_on_handle(self, held, va, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _edit_on_handle, for the variation rows: va = what _variation_args returned.  With a filter the handle is first
+        replaced by the filter's result (filt); the rows of the survivors come back as uint32[n, 4]."""
+        shape, vr, _, _, f = va
+        sh = shape._struct()
+        vp = ptr(vr) if len(vr) else None
+        if filt and f is not None:
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), vp, len(vr), C.byref(f), C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        r = np.empty((int(count_fn(held[0])), 4), dtype=np.uint32)
+        st = _lib.VariationStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), vp, len(vr), ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return r
+
+    def variation(self, loci_or_found, shape, variants, pairs=True, coverage=False, allow_partial=False):
+        """vsc_loci_variation: the known variants under candidates' own sites, on the device.  shape: a
+        VariationShape or the name of a preset of VARIATION_SHAPES.  variants: (contig, pos, ref, alt[, weight]) rows in any
+        order (site_variants sorts and normalises them), or a VARIANT_DTYPE array as the library takes it.  Returns (rows,
+        pairs, coverage, stats).  rows uint32[n, 4] (unpack_variation_row): by_zone, silent, cost, max_weight per candidate;
+        VARIATION_UNDEFINED four times where the site is undefined.  pairs (VARIATION_PAIR_DTYPE; None with pairs=False): one
+        per overlapping variant, silent ones included - candidate, variant (the index in the CALLER's rows), info
+        (unpack_variation_info: first, touched, top, silent), weight - in ascending (candidate, variant).  coverage
+        (uint32[len(variants), 2] in the caller's order with coverage=True, else None): the disrupting and the silent pairs of
+        every variant.  stats: the candidates by class, with_disrupting, pairs, variants_covered, kernel_ms, wall_ms and - for
+        rows - variant_order (the caller's index of every sorted variant).  loci_or_found: as Genome.efficiency takes it.
+        Raises when a site is not resident on this object (a shard) unless allow_partial=True."""
+        shape = _variation_shape(shape)
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        vr, order, inverse = _variants_in(variants)
+        n_v = len(vr)
+        vp = ptr(vr) if n_v else None
+        rows = np.empty((n, 4), dtype=np.uint32)
+        cov = np.empty((n_v, 2), dtype=np.uint32) if coverage else None
+        want_pairs = bool(pairs)
+        cap = min(max(n, 1024), 1 << 22) if want_pairs else 0
+        pr = np.empty(cap, dtype=_lib.VARIATION_PAIR_DTYPE) if want_pairs else None
+        st = _lib.VariationStats()
+        sh = shape._struct()
+        count = C.c_uint64()
+        L = lib()
+        rc = L.vsc_loci_variation(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), vp, n_v, ptr(rows), ptr(pr), cap, C.byref(count), ptr(cov),
+                                  C.byref(st))
+        if rc == _lib.VSC_ERR_RANGE and want_pairs and cap < int(count.value) <= 0xFFFFFFFE:
+            # (the rows, the coverage and the stats of the first call stand; the second brings the pairs alone)
+            cap = int(count.value)
+            pr = np.empty(cap, dtype=_lib.VARIATION_PAIR_DTYPE)
+            check(L.vsc_loci_variation(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), vp, n_v, None, ptr(pr), cap, C.byref(count), None, None),
+                  self.ctx._h)
+        else:
+            check(rc, self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        if want_pairs:
+            pr = _variation_pairs_out(pr[:int(count.value)].copy(), order)
+        if cov is not None and inverse is not None:
+            cov = cov[inverse]
+        if order is not None:
+            stats["variant_order"] = order
         return rows, pr, cov, stats
 
     # ---- prime-editing extensions (vsc_*_prime) ---------------------------------------------------------------------------
@@ -3342,7 +3706,8 @@ class Genome:
     def enumerate_guides(self, regions=None, pam="GG", strands="both", gc=(0, 0), max_t_run=0, max_guides=0, params=None,
                          labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
                          min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None, cds=None,
-                         edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None):
+                         edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
+                         variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -3370,7 +3735,12 @@ class Genome:
         (uint32[n, 2], vsc_guides_prime) come last of all.  prime_edits= (contig, pos, del_len, ins) rows in any order /
         prime_allow_weak= (both need prime=): only the candidates whose context is defined, that - with edits - can write one of
         them, and - with prime_allow_weak=False - whose PBS is not WEAK (vsc_guides_filter_prime), after the edit and effects
-        filters."""
+        filters.
+        variation= a VariationShape with site_len 23 or the name of a preset of VARIATION_SHAPES, with variants= (as
+        Genome.variation takes them): the candidates' variation rows (uint32[n, 4], vsc_guides_variation) come last of all.
+        max_variant_cost= / max_variants_by_zone= four bounds (255: none) / require_variant_zones= zone numbers or names of
+        VARIATION_ZONES (all need variation=): only the candidates that pass the variation filter
+        (vsc_guides_filter_variation), after the other filters."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
@@ -3378,11 +3748,12 @@ class Genome:
         ed = self._edit_args(edit, edit_targets, min_editable, max_editable, READ_LEN)
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, READ_LEN)
+        vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None and pe is None:
+        if efficiency is None and mh is None and ed is None and pe is None and vr is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -3391,7 +3762,8 @@ class Genome:
                                            (L.vsc_guides_microhomology, L.vsc_guides_filter_microhomology), L.vsc_guides_free,
                                            ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit), fx,
                                            (L.vsc_guides_effects, L.vsc_guides_filter_effects), pe,
-                                           (L.vsc_guides_prime, L.vsc_guides_filter_prime))
+                                           (L.vsc_guides_prime, L.vsc_guides_filter_prime), vr,
+                                           (L.vsc_guides_variation, L.vsc_guides_filter_variation))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -3425,6 +3797,7 @@ class Genome:
                efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None, min_microhomology=None,
                pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
                cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
+               variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
                **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
@@ -3442,7 +3815,9 @@ class Genome:
         edit= / edit_targets= / min_editable= / max_editable=: as enumerate_guides; only the survivors are searched, and the
         edit rows come after the microhomology pairs, before (picks, counts).  cds= / edit_to= / require_effect= /
         forbid_effect=: as enumerate_guides; the effect rows come after the edit rows.  prime= / prime_edits= /
-        prime_allow_weak=: as enumerate_guides; the prime rows come after the effect rows, before (picks, counts)."""
+        prime_allow_weak=: as enumerate_guides; the prime rows come after the effect rows, before (picks, counts).
+        variation= / variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_guides; only
+        the survivors are searched, and the variation rows come after the prime rows, before (picks, counts)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -3451,7 +3826,9 @@ class Genome:
                                       min_microhomology=min_microhomology, edit=edit, edit_targets=edit_targets,
                                       min_editable=min_editable, max_editable=max_editable, cds=cds, edit_to=edit_to,
                                       require_effect=require_effect, forbid_effect=forbid_effect, prime=prime,
-                                      prime_edits=prime_edits, prime_allow_weak=prime_allow_weak)
+                                      prime_edits=prime_edits, prime_allow_weak=prime_allow_weak, variation=variation,
+                                      variants=variants, max_variant_cost=max_variant_cost,
+                                      max_variants_by_zone=max_variants_by_zone, require_variant_zones=require_variant_zones)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])

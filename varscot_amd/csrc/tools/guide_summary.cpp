@@ -141,6 +141,7 @@
 #include "edit_host.hpp"
 #include "effects_host.hpp"
 #include "prime_host.hpp"
+#include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
 #include "merge_host.hpp"
@@ -228,6 +229,17 @@ int main(int argc, char **argv)
         {'5', "prime-allow-weak", "With --prime: keep the candidates whose primer binding site is WEAK", false, false},
         {'6', "prime-out", "With --prime-edits: path to the listing of the pairs: #chrom pos guideId pbsLen rttLen nickToEdit homology flags "
                            "extension", false},
+        {'7', "variants", "With -E: path to known variants (.vcf: POS 1-based, one variant per ALT allele; or a TSV: chrom pos ref alt [weight], pos "
+                          "0-based): the variants under every found guide's own site are joined with it on the device (one device)", false},
+        {'8', "variant-af", "With --variants (a VCF): the INFO key of the allele frequency; a variant's weight is round(-log1p(-AF) * 2^20)", false},
+        {'9', "variant-seed", "With --variants: the seed, the N protospacer bases next to the PAM (default 10)", false},
+        {'0', "max-variant-cost", "With --variants: keep only the candidates whose cost (the sum of their disrupting variants' weights) is at most this", false},
+        {'1', "max-variants-by-zone", "With --variants: a,b,c,d: keep only the candidates with at most a, b, c, d disrupting variants whose top zone is "
+                                      "none, distal, seed, pam (255: no bound)", false},
+        {'@', "require-variant-zones", "With --variants: zones out of none, distal, seed, pam: keep only the candidates with a disrupting variant "
+                                       "in one of them (allele-specific design)", false},
+        {'%', "variation-out", "With --variants: path to the TSV of the guides' rows (#guideId none distal seed pam silent cost maxWeight) and, "
+                               "behind a blank line, of the pairs (#chrom pos span alt guideId first touched top silent weight)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -636,6 +648,18 @@ int main(int argc, char **argv)
         }
     }
 
+    // --variants and its options: the known variants under the found guides' own sites
+    VariationOptions variation;
+    {
+        const std::string guide_pam = opts[16].set ? opts[16].value : "GG";
+        const std::string why = parse_variation_options(opts[54], opts[55], opts[56], opts[57], opts[58], opts[59], opts[60], discover, devices.size() != 1,
+                                                        std::string(21, 'N') + guide_pam, 0, 20, &variation);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     vsc_ctx *ctx = nullptr;
     vsc_score_table *table = nullptr;
     vsc_bulge_table *bulge_table = nullptr;
@@ -818,6 +842,16 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_variant> variants;
+            if (variation.on) variants = read_variants(variation, ix.names, ix.contigs);
+            if (variation.filtered) {  // the bounds and the required zones: the same for the variation FILTER, after all others
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_variation(ctx, genome, found, &variation.shape, variants.empty() ? nullptr : variants.data(), variants.size(),
+                                                &variation.filter, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -848,6 +882,14 @@ int main(int argc, char **argv)
                                          cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &prime_rows, &prime_pairs);
+            std::vector<uint32_t> variation_rows;  // --variation-out: the rows and the pairs
+            std::vector<vsc_variation_pair> variation_pairs;
+            if (variation.with_out)
+                variation_rows_and_pairs(vsc_guides_count(found), [&](uint32_t *r, vsc_variation_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_guides_variation(ctx, genome, found, &variation.shape, variants.empty() ? nullptr : variants.data(), variants.size(), r, pp,
+                                             cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &variation_rows, &variation_pairs);
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -888,6 +930,7 @@ int main(int argc, char **argv)
             if (edit.with_pairs) write_edit_pairs(edit.pairs_path, edit_pairs, edit_targets, ix.names, ids);
             if (fx.with_listing) write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
             if (prime.with_pairs) write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, loci, ix, ids);
+            if (variation.with_out) write_variation(variation.out_path, variation_rows, variation_pairs, variants, ix.names, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');

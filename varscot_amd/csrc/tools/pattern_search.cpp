@@ -77,6 +77,7 @@
 #include "edit_host.hpp"
 #include "effects_host.hpp"
 #include "prime_host.hpp"
+#include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
 
@@ -275,6 +276,17 @@ int main(int argc, char **argv)
         {'5', "prime-allow-weak", "With --prime: keep the candidates whose primer binding site is WEAK", false, false},
         {'6', "prime-out", "With --prime-edits: path to the listing of the pairs: #chrom pos guideId pbsLen rttLen nickToEdit homology flags "
                            "extension", false},
+        {'7', "variants", "With -E: path to known variants (.vcf: POS 1-based, one variant per ALT allele; or a TSV: chrom pos ref alt [weight], pos "
+                          "0-based): the variants under every found guide's own site are joined with it on the device (one device)", false},
+        {'8', "variant-af", "With --variants (a VCF): the INFO key of the allele frequency; a variant's weight is round(-log1p(-AF) * 2^20)", false},
+        {'9', "variant-seed", "With --variants: the seed, the N protospacer bases next to the PAM (default 10)", false},
+        {'0', "max-variant-cost", "With --variants: keep only the candidates whose cost (the sum of their disrupting variants' weights) is at most this", false},
+        {'1', "max-variants-by-zone", "With --variants: a,b,c,d: keep only the candidates with at most a, b, c, d disrupting variants whose top zone is "
+                                      "none, distal, seed, pam (255: no bound)", false},
+        {'@', "require-variant-zones", "With --variants: zones out of none, distal, seed, pam: keep only the candidates with a disrupting variant "
+                                       "in one of them (allele-specific design)", false},
+        {'%', "variation-out", "With --variants: path to the TSV of the guides' rows (#guideId none distal seed pam silent cost maxWeight) and, "
+                               "behind a blank line, of the pairs (#chrom pos span alt guideId first touched top silent weight)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -511,6 +523,16 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // --variants and its options: the known variants under the found guides' own sites
+    VariationOptions variation;
+    {
+        const std::string why = parse_variation_options(opts[42], opts[43], opts[44], opts[45], opts[46], opts[47], opts[48], enumerate,
+                                                        opts[4].value.find(',') != std::string::npos, pattern, ep.ps_start, ep.ps_len, &variation);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
     // -W / -K / -S: the table score of the hits
     const bool tabled = opts[18].set;
     // -k / -b / -c: the best guides of every -B target
@@ -705,6 +727,16 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_variant> variants;
+            if (variation.on) variants = read_variants(variation, ix.names, ix.contigs);
+            if (variation.filtered) {  // the bounds and the required zones: the same for the variation FILTER, after all others
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_variation(ctx, genome, found, &variation.shape, variants.empty() ? nullptr : variants.data(),
+                                                        variants.size(), &variation.filter, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -735,6 +767,14 @@ int main(int argc, char **argv)
                                                  prime_edits.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &prime_rows, &prime_pairs);
+            std::vector<uint32_t> variation_rows;  // --variation-out: the rows and the pairs
+            std::vector<vsc_variation_pair> variation_pairs;
+            if (variation.with_out)
+                variation_rows_and_pairs(vsc_pattern_guides_count(found), [&](uint32_t *r, vsc_variation_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_pattern_guides_variation(ctx, genome, found, &variation.shape, variants.empty() ? nullptr : variants.data(),
+                                                     variants.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &variation_rows, &variation_pairs);
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -788,6 +828,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, std::vector<vsc_locus>(loci, loci + n), ix, ids);
+            }
+            if (variation.with_out) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_variation(variation.out_path, variation_rows, variation_pairs, variants, ix.names, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

@@ -16,6 +16,7 @@
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
 //   vsc_edit.hip           base-editor windows of candidates and their join with targets
 //   vsc_prime.hip          prime-editing extensions of candidates and their join with edits
+//   vsc_variation.hip      known variation under candidates: the join of their sites with variant intervals
 //   vsc_pick.hip           the best K candidates per target, with spacing
 // No CPU implementation of the search exists in this library: without a HIP device every compute entry point fails with
 // VSC_ERR_NODEVICE / VSC_ERR_DEVICE.
@@ -5629,6 +5630,419 @@ int vsc_pattern_guides_filter_edit(vsc_ctx *ctx, const vsc_genome *genome, vsc_p
                                    vsc_pattern_guides **out)
 {
     return edit_filter(ctx, genome, in, shape, targets, n_t, false, min_editable, max_editable, out, "vsc_pattern_guides_filter_edit");
+}
+
+}  // extern "C"
+
+// ---- known variation under candidate guides (the definition: vsc_variation.h, the kernels: vsc_variation.hip) ----
+namespace {
+
+// The shape and the variants of a variation call against contigs [off[c], end[c]) in global positions; null: fine, else the reason.
+const char *var_check(const vsc_variation_shape *shape, const vsc_variant *variants, uint64_t n_v, const uint32_t *off, const uint32_t *end,
+                      size_t n_contigs, VarShape &s, int *code)
+{
+    *code = VSC_ERR_INVALID;
+    if (!shape) return "null argument";
+    s = VarShape{shape->site_len, shape->zones, {shape->accept[0], shape->accept[1]}};
+    if (shape->reserved0 || shape->reserved[0] || shape->reserved[1] || shape->reserved[2] || shape->reserved[3] || !var_shape_valid(s))
+        return "site_len 16 .. 32, no zone or accept bit at a position from site_len on, reserved fields 0";
+    if (n_v && !variants) return "variants are null with n_v > 0";
+    if (n_v > kVarMaxCount) {
+        *code = VSC_ERR_RANGE;
+        return "more than 0xFFFFFFFE variants";
+    }
+    for (uint64_t k = 0; k < n_v; ++k) {
+        const vsc_variant &v = variants[k];
+        if (v.contig >= n_contigs) return "a variant lies on an unknown contig";
+        const uint32_t len = end[v.contig] - off[v.contig], span = v.span_alt & 0xFFFFu, alt = v.span_alt >> 16;
+        if (span == 0) return "a variant's span is 0";
+        if (v.pos >= len || span > len - v.pos) return "a variant reaches beyond its contig";
+        if (alt > kVarOther) return "a variant's alt is above 4, or span_alt has other bits";
+        if (alt < kVarOther && span != 1) return "an SNV (alt 0 .. 3) has a span other than 1";
+        if (v.weight > kVarMaxCount) return "a variant's weight is 0xFFFFFFFF";
+        if (k && (variants[k - 1].contig > v.contig || (variants[k - 1].contig == v.contig && variants[k - 1].pos > v.pos)))
+            return "the variants are not ascending by (contig, pos)";
+    }
+    *code = VSC_OK;
+    return nullptr;
+}
+
+// var_check for a device call: the context and the genome first
+int var_check_ctx(vsc_ctx *ctx, const vsc_genome *genome, const vsc_variation_shape *shape, const vsc_variant *variants, uint64_t n_v, VarShape &s,
+                  const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    int code = VSC_OK;
+    const size_t n_contigs = std::min<size_t>(genome->n_contigs, genome->h_contig_off.size());
+    const char *why = var_check(shape, variants, n_v, genome->h_contig_off.data(), genome->h_contig_end.data(), n_contigs, s, &code);
+    return why ? fail_in(ctx, code, who, why) : VSC_OK;
+}
+
+// The variants at the front of edit_tabs, rewritten there as the walk's records, and the block table behind them; `more` bytes
+// behind those (256-byte aligned) for the caller.  The caller's array is read until the stream is synchronised.
+int var_upload(vsc_ctx *ctx, const vsc_genome *genome, const vsc_variant *variants, uint64_t n_v, size_t more, VarTable &t, char **behind)
+{
+    const uint32_t bits = ctx->variation_block_bits ? ctx->variation_block_bits : kVarBlockBits;
+    const uint64_t total = genome->h_contig_end.empty() ? 0 : genome->h_contig_end.back();
+    VarBuildArgs b{};
+    b.n = (uint32_t)n_v;
+    b.n_tiles = (uint32_t)((n_v + kEditTile - 1) / kEditTile);
+    b.bits = bits;
+    b.n_blocks = n_v ? var_block_count(total, bits) : 0u;
+    const size_t rec_bytes = round256((size_t)n_v * sizeof(VarRec) + 16), first_bytes = round256(((size_t)b.n_blocks + 1) * sizeof(uint32_t));
+    const size_t max_bytes = round256((size_t)b.n_tiles * sizeof(uint32_t) + 4);
+    VSC_HIP(ctx, ctx->edit_tabs.ensure(rec_bytes + first_bytes + max_bytes + more));
+    char *base = (char *)ctx->edit_tabs.p;
+    b.rec = (VarRec *)base;
+    b.first = (uint32_t *)(base + rec_bytes);
+    b.tile_max = (uint32_t *)(base + rec_bytes + first_bytes);
+    b.contig_off = genome->d_contig_off;
+    if (n_v) {
+        VSC_HIP(ctx, hipMemcpyAsync(b.rec, variants, (size_t)n_v * sizeof(vsc_variant), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, launch_var_build(b, ctx->n_cus, ctx->stream));
+    }
+    t = VarTable{b.rec, b.first, b.n, bits, b.n_blocks};
+    if (behind) *behind = base + rec_bytes + first_bytes + max_bytes;
+    return VSC_OK;
+}
+
+// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): the variants'
+// build, var_rows_kernel, then - with variants - the pairs' count pass over the rows, the scan, one 8-byte read-back (the
+// pairs) and the write pass.
+int var_run(vsc_ctx *ctx, const vsc_genome *genome, const VarShape &shape, const vsc_variant *variants, uint64_t n_v, const void *d_loci,
+            const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+            vsc_variation_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) *stats = vsc_variation_stats{};
+    if (n_pairs) *n_pairs = 0;
+    if (coverage) std::fill(coverage, coverage + 2 * n_v, 0u);
+    vsc_timing t{};
+    if (n == 0) {
+        ctx->timing = t;
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
+    // edit_tabs behind the variants and their table: [pairs per variant, two kinds][pairs per tile][offsets per tile]
+    const size_t cov_bytes = round256(2 * (size_t)n_v * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
+    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
+    VarArgs a{};
+    char *tabs = nullptr;
+    const int urc = var_upload(ctx, genome, variants, n_v, cov_bytes + count_bytes + off_bytes, a.table, &tabs);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n = n;
+    const size_t head = 256;  // the counters, in front of the rows
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint4)));
+    a.stats = (unsigned long long *)ctx->eff_out.p;
+    a.out = (uint4 *)((char *)ctx->eff_out.p + head);
+    if (h_loci) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.loci = (const uint4 *)ctx->eff_in.p;
+    } else {
+        a.loci = (const uint4 *)d_loci;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch_var_rows(a, ctx->n_cus, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    unsigned long long seen[kVarCounts] = {};
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    VarPairArgs p{};
+    unsigned long long total = 0;
+    float pass_ms = 0;
+    if (n_v) {
+        p.shape = shape;
+        p.table = a.table;
+        p.contig_off = genome->d_contig_off;
+        p.loci = a.loci;
+        p.rows = a.out;
+        p.n = n;
+        p.n_work = tiles;
+        p.tile_count = (uint32_t *)(tabs + cov_bytes);
+        unsigned long long *d_off = (unsigned long long *)(tabs + cov_bytes + count_bytes);
+        p.tile_off = d_off;
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_var_pairs(p, false, ctx->stream));
+        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    if (n_v) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+    if (n_pairs) *n_pairs = total;
+    // (a tile's count saturates at 0xFFFFFFFF, so a total within the bound is the exact one)
+    const bool too_many = total > kVarMaxCount, write = pairs && total && total <= capacity && !too_many;
+    const bool cover = total && !too_many && (coverage || stats);
+    uint64_t covered = 0;
+    if (write || cover) {
+        if (write) {
+            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_variation_pair)));
+            p.pairs = (uint4 *)ctx->edit_pairs.p;
+        }
+        if (cover) {
+            p.coverage = (uint32_t *)tabs;
+            VSC_HIP(ctx, hipMemsetAsync(p.coverage, 0, 2 * (size_t)n_v * sizeof(uint32_t), ctx->stream));
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch_var_pairs(p, true, ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        unsigned long long d_covered = 0;
+        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_variation_pair), hipMemcpyDeviceToHost, ctx->stream));
+        if (cover && !coverage) {  // the stats alone: the covered variants are counted where they lie, 8 bytes come back
+            unsigned long long *slot = a.stats + kVarCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
+            VSC_HIP(ctx, launch_var_covered(p.coverage, (uint32_t)n_v, slot, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+        } else if (cover) {
+            VSC_HIP(ctx, hipMemcpyAsync(coverage, p.coverage, 2 * (size_t)n_v * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float wms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        pass_ms += wms;
+        covered = d_covered;
+        for (uint64_t k = 0; coverage && k < n_v; ++k) covered += (coverage[2 * k] | coverage[2 * k + 1]) != 0;
+    }
+    if (stats) {
+        stats->defined = seen[kEffDefined];
+        stats->invalid = seen[kEffInvalid];
+        stats->off_contig = seen[kEffOffContig];
+        stats->not_resident = seen[kEffNotResident];
+        stats->has_n = seen[kEffHasN];
+        stats->with_disrupting = seen[kEffClasses];
+        stats->pairs = total;
+        stats->variants_covered = covered;
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    t.score_ms = ms;
+    t.scan_ms = pass_ms;
+    t.total_ms = t.score_ms + t.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint4));
+    ctx->timing = t;
+    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
+    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
+    return VSC_OK;
+}
+
+// vsc_guides_variation / vsc_pattern_guides_variation: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int var_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_variation_shape *shape, const vsc_variant *variants, uint64_t n_v,
+               bool need_23, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+               vsc_variation_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    VarShape s{};
+    const int rc = var_check_ctx(ctx, genome, shape, variants, n_v, s, who);
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (guides->n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const bool dev = guides->ctx != nullptr;
+    return var_run(ctx, genome, s, variants, n_v, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
+                   dev ? nullptr : guides->loci.data(), guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_variation / vsc_pattern_guides_filter_variation: run_enumeration's two passes over tiles of kEditTile
+// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+template <class Guides>
+int var_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_variation_shape *shape, const vsc_variant *variants, uint64_t n_v,
+               bool need_23, const vsc_variation_filter *filter, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    VarShape s{};
+    const int rc = var_check_ctx(ctx, genome, shape, variants, n_v, s, who);
+    if (rc != VSC_OK) return rc;
+    if (!in || !filter) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
+    if (filter->require_zones > 15u || filter->reserved) return fail_in(ctx, VSC_ERR_INVALID, who, "require_zones is a mask of four bits, the reserved field 0");
+    const uint64_t n = in->n;
+    if (n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
+    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    VarFilterArgs a{};
+    if (n) {
+        const int urc = var_upload(ctx, genome, variants, n_v, 0, a.table, nullptr);
+        if (urc != VSC_OK) return urc;
+    }
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.filter = VarFilter{filter->max_cost, filter->max_by_zone, filter->require_zones};
+    a.n = n;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch_var_filter(a, write, ctx->stream); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_variation_block_bits(vsc_ctx *ctx, uint32_t bits)
+{
+    if (!ctx || (bits && (bits < kVarMinBlockBits || bits > kVarMaxBlockBits))) return VSC_ERR_INVALID;
+    ctx->variation_block_bits = bits;
+    return VSC_OK;
+}
+
+int vsc_variation_host(const vsc_contig *contigs, uint32_t n_contigs, const vsc_locus *loci, uint64_t n, const vsc_variation_shape *shape,
+                       const vsc_variant *variants, uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                       uint32_t *coverage)
+{
+    return guarded(nullptr, [&]() -> int {
+    if ((n_contigs && !contigs) || (n && !loci)) return VSC_ERR_INVALID;
+    if (n > kVarMaxCount) return VSC_ERR_RANGE;
+    // the contigs one base apart, as the packed genome lays them
+    std::vector<uint32_t> off(n_contigs), end(n_contigs);
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        if (at + contigs[c].length > 0xFFFFFFFFull) return VSC_ERR_RANGE;
+        off[c] = (uint32_t)at;
+        end[c] = (uint32_t)(at + contigs[c].length);
+        at += (uint64_t)contigs[c].length + 1;
+    }
+    VarShape s{};
+    int code = VSC_OK;
+    if (var_check(shape, variants, n_v, off.data(), end.data(), n_contigs, s, &code)) return code;
+    if (n_pairs) *n_pairs = 0;
+    if (coverage) std::fill(coverage, coverage + 2 * n_v, 0u);
+    // the records and the block table, as the device builds them
+    std::vector<VarRec> rec((size_t)n_v);
+    uint32_t reach = 0;
+    for (uint64_t k = 0; k < n_v; ++k) {
+        const uint32_t gpos = off[variants[k].contig] + variants[k].pos;
+        reach = std::max(reach, gpos + (variants[k].span_alt & 0xFFFFu));
+        rec[k] = VarRec{gpos, variants[k].span_alt, variants[k].weight, reach};
+    }
+    const uint64_t total = n_contigs ? end[n_contigs - 1] : 0;
+    const uint32_t n_blocks = n_v ? var_block_count(total, kVarBlockBits) : 0u;
+    std::vector<uint32_t> first((size_t)n_blocks + 1);
+    for (uint64_t b = 0; b <= n_blocks; ++b) first[b] = var_first_reach(rec.data(), 0u, (uint32_t)n_v, b << kVarBlockBits);
+    const VarTable t{rec.data(), first.data(), (uint32_t)n_v, kVarBlockBits, n_blocks};
+    // no planes: every word of a site is "held" and none is read, so that the classes are invalid and defined only
+    const EffPlanes g{nullptr, nullptr, nullptr, 0, (total + 31) / 32 + 1, 0, off.data(), end.data(), n_contigs};
+    // the count first: a refusal for capacity writes no pair
+    uint64_t count = 0;
+    bool refused = false;
+    for (int pass = 0; pass < 2; ++pass) {
+        uint64_t o = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            const vsc_locus &l = loci[i];
+            const uint32_t cls = var_site(g, s, l.contig, l.pos, l.strand);
+            if (cls != kEffDefined) {
+                if (pass == 0 && rows) std::fill(rows + 4 * i, rows + 4 * i + 4, kVarUndefined);
+                continue;
+            }
+            const uint32_t g0 = off[l.contig] + l.pos;
+            if (pass == 0) {
+                uint64_t mine = 0;
+                const VarRow row = var_row(t, g0, l.strand, s, &mine);
+                count += mine;
+                if (rows) {
+                    rows[4 * i] = row.by_zone;
+                    rows[4 * i + 1] = row.silent;
+                    rows[4 * i + 2] = var_cost(row);
+                    rows[4 * i + 3] = row.max_weight;
+                }
+                continue;
+            }
+            for (uint32_t k = var_first(t, g0); k < t.n; ++k) {
+                if (rec[k].gpos >= g0 + s.site_len) break;
+                uint32_t info;
+                if (!var_touch(rec[k], g0, l.strand, s, &info)) continue;
+                if (pairs) pairs[o] = vsc_variation_pair{(uint32_t)i, k, info, rec[k].weight};
+                ++o;
+                if (coverage) ++coverage[2 * (uint64_t)k + (info >> 18 & 1u)];
+            }
+        }
+        if (pass == 0) {
+            if (n_pairs) *n_pairs = count;
+            if (count > kVarMaxCount) return VSC_ERR_RANGE;
+            refused = pairs && count > capacity;
+            if (refused) pairs = nullptr;  // (the coverage stays valid: counted without the pairs)
+            if (!pairs && !coverage) break;
+        }
+    }
+    return refused ? VSC_ERR_RANGE : VSC_OK;
+    });
+}
+
+int vsc_loci_variation(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_variation_shape *shape,
+                       const vsc_variant *variants, uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                       uint32_t *coverage, vsc_variation_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_variation";
+    VarShape s{};
+    const int rc = var_check_ctx(ctx, genome, shape, variants, n_v, s, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return var_run(ctx, genome, s, variants, n_v, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_variation_shape *shape, const vsc_variant *variants,
+                         uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+                         vsc_variation_stats *stats)
+{
+    return var_guides(ctx, genome, guides, shape, variants, n_v, true, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_guides_variation");
+}
+
+int vsc_pattern_guides_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_variation_shape *shape,
+                                 const vsc_variant *variants, uint64_t n_v, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity,
+                                 uint64_t *n_pairs, uint32_t *coverage, vsc_variation_stats *stats)
+{
+    return var_guides(ctx, genome, guides, shape, variants, n_v, false, rows, pairs, capacity, n_pairs, coverage, stats,
+                      "vsc_pattern_guides_variation");
+}
+
+int vsc_guides_filter_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_variation_shape *shape, const vsc_variant *variants,
+                                uint64_t n_v, const vsc_variation_filter *filter, vsc_guides **out)
+{
+    return var_filter(ctx, genome, in, shape, variants, n_v, true, filter, out, "vsc_guides_filter_variation");
+}
+
+int vsc_pattern_guides_filter_variation(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_variation_shape *shape,
+                                        const vsc_variant *variants, uint64_t n_v, const vsc_variation_filter *filter, vsc_pattern_guides **out)
+{
+    return var_filter(ctx, genome, in, shape, variants, n_v, false, filter, out, "vsc_pattern_guides_filter_variation");
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include "vsc_eff_trees.h"
 #include "vsc_mh.h"
 #include "vsc_edit.h"
+#include "vsc_variation.h"
 #include "vsc_prime.h"
 #include "vsc_effects.h"
 
@@ -679,6 +680,63 @@ hipError_t launch_edit_pairs(const EditPairArgs &args, bool write, hipStream_t s
 hipError_t launch_edit_filter(const EditFilterArgs &args, bool write, hipStream_t stream);
 // *out (zeroed) += the entries of cov_count that are not 0
 hipError_t launch_edit_covered(const uint32_t *cov_count, uint32_t n_t, unsigned long long *out, int n_cus, hipStream_t stream);
+// vsc_variation.hip (the definition: vsc_variation.h)
+constexpr uint32_t kVarCounts = kEffClasses + 1;  // the classes, then the candidates with a disrupting variant
+// The variants on the device.  They arrive as the caller's 16-byte records { contig, pos, span_alt, weight } in `rec` and are
+// rewritten in place as VarRec by three launches: the largest end per tile of kEditTile variants, the prefix maximum over the
+// tiles, the records; a fourth fills the block table.
+struct VarBuildArgs {
+    VarRec *rec;                  // [n] in: the caller's records; out: VarRec
+    const uint32_t *contig_off;   // (every contig was checked on the host)
+    uint32_t n, n_tiles;
+    uint32_t *tile_max;           // [n_tiles] the largest gpos + span of a tile, then of the tiles in front of it
+    uint32_t *first;              // [n_blocks + 1] out
+    uint32_t bits, n_blocks;
+};
+struct VarArgs {
+    EffPlanes g;
+    VarShape shape;
+    VarTable table;               // n == 0: no variants, every defined row is 0
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint4 *out;                   // [n] out: (by_zone, silent, cost, max_weight), kVarUndefined four times where the class is not defined
+    unsigned long long *stats;    // [kVarCounts], zeroed before the launch: the kernel adds its candidates per class
+};
+// the pairs' and the filter's two passes: tile i = candidates [i * kEditTile, ..)
+struct VarPairArgs {
+    VarShape shape;
+    VarTable table;
+    const uint32_t *contig_off;
+    const uint4 *loci;            // [n]
+    const uint4 *rows;            // [n] what var_rows_kernel left
+    unsigned long long n;
+    uint32_t n_work;              // tiles
+    uint32_t *tile_count;         // count pass out: pairs per tile, 0xFFFFFFFF: that many or more
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    uint4 *pairs;                 // write pass out (null: coverage only)
+    uint32_t *coverage;           // [2 table.n] write pass: disrupting and silent pairs per variant, 0 before the launch; null: none
+};
+struct VarFilterArgs {
+    EffPlanes g;
+    VarShape shape;
+    VarTable table;
+    VarFilter filter;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+hipError_t launch_var_build(const VarBuildArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_var_rows(const VarArgs &args, int n_cus, hipStream_t stream);
+hipError_t launch_var_pairs(const VarPairArgs &args, bool write, hipStream_t stream);
+hipError_t launch_var_filter(const VarFilterArgs &args, bool write, hipStream_t stream);
+// *out (zeroed) += the variants with a pair of either kind
+hipError_t launch_var_covered(const uint32_t *coverage, uint32_t n_v, unsigned long long *out, int n_cus, hipStream_t stream);
 // vsc_prime.hip (the definition: vsc_prime.h)
 // the rows kernel's counters: the classes, the candidates with a pair, the weak candidates
 constexpr uint32_t kPrimeCounts = kEffClasses + 2;
