@@ -427,6 +427,7 @@ def test_filter_bounds_and_input_order(ctx, small, which):
         assert kept[0, 16] == want["stats"]["with_hit"] and 0 < kept[1, 1] < kept[0, 16] and kept[0, 0] == 0  # no editable base, no hit
     t = ctx.timing()
     assert t["sites"] == n and t["score_ms"] == t["total_ms"] > 0
+    assert t["genome_bytes"] == 32 * n + 48 * kept[0, 0]  # (the last call's)
     host = Guides.from_arrays(ctx, codes, s["arr"], on_device=False)  # the host-only object: uploaded first, the same bytes
     keep = np.array([ed.keep(r, targets is not None, 2, 16) for r in zip(want["editable"], want["hit"])])
     h_out = host.filter(s["gen"], sh, targets, 2, 16)

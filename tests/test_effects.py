@@ -378,6 +378,7 @@ def test_filter_require_forbid_and_input_order(ctx, small):
     assert all(0 < kept[c] < want["stats"]["with_effect"] for c in cases[1:5] if c[0]) and 0 < kept[cases[2]] < kept[(), ()]
     t = ctx.timing()
     assert t["sites"] == n and t["score_ms"] == t["total_ms"] > 0
+    assert t["genome_bytes"] == 32 * n + 48 * kept[(), fx.EFFECTS]  # (the last call's)
     # a custom code moves the stops: another set of survivors
     mito = small["want"](shape, "mito")
     keep_m = np.array([fx.keep(c, ("stop_gained",), ()) for c in mito["classes"]])

@@ -457,6 +457,7 @@ def test_filter_rule_and_input_order(ctx, small, which):
     assert kept[True] == (want["stats"]["defined"] if edits is None else want["stats"]["with_pair"]) and 0 < kept[False] < kept[True]
     t = ctx.timing()
     assert t["sites"] == n and t["score_ms"] == t["total_ms"] > 0
+    assert t["genome_bytes"] == 32 * n + 48 * kept[False]  # (the last call's)
     host = Guides.from_arrays(ctx, codes, s["arr"], on_device=False)  # the host-only object: uploaded first, the same bytes
     keep = np.array([pc.keep(r, edits is not None, False) for r in want["rows"]])
     h_out = host.filter(s["gen"], sh, edits, False)

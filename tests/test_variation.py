@@ -311,6 +311,7 @@ def test_filter_bounds_and_input_order(ctx, world, which, shape_name):
         assert all(k <= kept[0] for k in kept) and len(set(kept)) >= 7 and sum(k > 0 for k in kept) >= 8
         t = ctx.timing()
         assert t["sites"] == n and t["score_ms"] == t["total_ms"] > 0
+        assert t["genome_bytes"] == 32 * n + 48 * kept[-1]  # (the last call's)
     if which == "none":
         assert kept[1:7] == [kept[0]] * 6 and kept[7:] == [0] * 4  # no variant: every bound holds, nothing is required in vain
     empty = g.filter(c["gen"], c["sh"], c["var"], max_cost=0, require=15)  # an empty result is a result

@@ -4128,6 +4128,312 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
 
 }  // extern "C"
 
+// ---- the host path of the candidate annotations ----------------------------------------------------------------
+// What the families that annotate candidate guides - linear and tree efficiency, microhomology, edit windows, coding effects,
+// prime editing, variation - do alike on the host: the checks in front of a call over candidates, the filter (staging,
+// run_enumeration, the timing restated), the rows pass, and the join of the rows with a family's table (count pass, scan,
+// write pass, coverage).  A family keeps its check, its table upload, the fields of its Args, its launchers and its stats;
+// what differs between families enters here as a value or a callable of the family's.
+namespace {
+
+double wall_ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// What a family tells candidate_front about itself.
+struct CandidateRule {
+    const char *need_23;   // the refusal of another site_len than 23 by a call over vsc_guides, with the family's noun
+    uint64_t max_n;        // more candidates than this are refused ...
+    const char *too_many;  // ... in these words
+};
+
+// Where the loci of a call's candidates lie: on the context's device already (dev), or on the host (host: uploaded first).
+struct CandidateLoci {
+    const void *dev;
+    const vsc_locus *host;
+    uint64_t n;
+};
+
+int no_refusal() { return VSC_OK; }
+
+// The checks in front of every call over a candidate list, in their order: check() is the family's own check of its other
+// arguments - the first, because it clears ctx->err -, after which *site_len is the site length the family works with;
+// refuse() holds the refusals of the call's own parameters (no_refusal: it has none).  at = where the loci lie.
+template <class Guides, class Check, class Refuse>
+int candidate_front(vsc_ctx *ctx, Guides *guides, bool need_23, const CandidateRule &rule, const char *who, CandidateLoci &at,
+                    const uint32_t *site_len, Check check, Refuse refuse)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    const int rc = check();
+    if (rc != VSC_OK) return rc;
+    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
+    if (need_23 && *site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, rule.need_23);
+    const int frc = refuse();
+    if (frc != VSC_OK) return frc;
+    if (guides->n > rule.max_n) return fail_in(ctx, VSC_ERR_RANGE, who, rule.too_many);
+    const bool dev = guides->ctx != nullptr;  // (a host-only object: from the host)
+    at = CandidateLoci{dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(), guides->n};
+    return VSC_OK;
+}
+
+// candidate_front for a filter, whose result is null until there is one; on VSC_OK the context's device is the current one
+template <class Guides, class Check, class Refuse>
+int filter_front(vsc_ctx *ctx, Guides *in, Guides **out, bool need_23, const CandidateRule &rule, const char *who, const uint32_t *site_len,
+                 Check check, Refuse refuse)
+{
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    *out = nullptr;
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, in, need_23, rule, who, at, site_len, check, refuse);
+    if (rc != VSC_OK) return rc;
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    return VSC_OK;
+}
+
+// The candidates of `in` that a family keeps, as a new object: run_enumeration's two passes over tiles of `tile` candidates
+// (a host-only object: uploaded first, into eff_in); its timing is then restated as the scoring calls report theirs.  The
+// family has filled the fields of `a` that are its own; launch(write) starts a pass.
+template <class Guides, class Args, class Launch>
+int filter_candidates(vsc_ctx *ctx, Guides *in, Args &a, uint32_t tile, Guides **out, const char *who, Launch launch)
+{
+    const uint64_t n = in->n;
+    a.n = n;
+    if (n && in->ctx) {
+        a.in_codes = (const unsigned long long *)in->storage.p;
+        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
+    } else if (n) {
+        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
+        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
+        char *base = (char *)ctx->eff_in.p;
+        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        a.in_codes = (const unsigned long long *)base;
+        a.in_loci = (const uint4 *)(base + loci_at);
+    }
+    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)((n + tile - 1) / tile), nullptr, 0, 0, out,
+                                    [&](const void *, unsigned long long, bool write) { return launch(write); });
+    if (erc != VSC_OK) return erc;
+    vsc_timing t{};
+    t.score_ms = t.total_ms = ctx->timing.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+// The rows pass of at.n > 0 candidates, enqueued on the context's stream: eff_out is laid out as a zeroed head of 256 bytes
+// (the family's counters; what lies behind them in the head is scratch of the call) and the rows of row_bytes each, the loci
+// are uploaded into eff_in where they lie on the host, launch(stats, rows, loci) starts the family's kernel between the stage
+// events, and the rows (rows == null: not asked for) and the first n_seen counters are copied back.  Nothing is synchronised.
+template <class Launch>
+int rows_pass(vsc_ctx *ctx, const CandidateLoci &at, size_t row_bytes, void *rows, unsigned long long *seen, uint32_t n_seen, Launch launch)
+{
+    const size_t head = 256;
+    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)at.n * row_bytes));
+    unsigned long long *d_stats = (unsigned long long *)ctx->eff_out.p;
+    void *d_rows = (char *)ctx->eff_out.p + head;
+    const void *d_loci = at.dev;
+    if (at.host) {
+        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)at.n * sizeof(vsc_locus)));
+        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, at.host, (size_t)at.n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
+        d_loci = ctx->eff_in.p;
+    }
+    VSC_HIP(ctx, hipMemsetAsync(d_stats, 0, head, ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
+    VSC_HIP(ctx, launch(d_stats, d_rows, (const uint4 *)d_loci));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, d_rows, (size_t)at.n * row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VSC_HIP(ctx, hipMemcpyAsync(seen, d_stats, n_seen * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    return VSC_OK;
+}
+
+// What a rows pass reports as the call's timing; the pass has ended.  A join adds its passes as scan_ms.
+int rows_timing(vsc_ctx *ctx, uint64_t n, size_t row_bytes, float pass_ms, float *rows_ms)
+{
+    VSC_HIP(ctx, hipEventElapsedTime(rows_ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    vsc_timing t{};
+    t.score_ms = *rows_ms;
+    t.scan_ms = pass_ms;
+    t.total_ms = t.score_ms + t.scan_ms;
+    t.sites = n;
+    t.genome_bytes = n * (sizeof(vsc_locus) + row_bytes);
+    ctx->timing = t;
+    return VSC_OK;
+}
+
+// A scoring call's whole device work: the rows pass alone, waited for.  at.n > 0; rows is the caller's array; prepare() makes
+// resident what the family's kernel reads beside the genome.
+template <class Prepare, class Launch>
+int score_rows(vsc_ctx *ctx, const CandidateLoci &at, size_t row_bytes, void *rows, unsigned long long *seen, uint32_t n_seen, float *rows_ms,
+               const char *who, Prepare prepare, Launch launch)
+{
+    if (!rows) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (at.n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    const int prc = prepare();
+    if (prc != VSC_OK) return prc;
+    const int rc = rows_pass(ctx, at, row_bytes, rows, seen, n_seen, launch);
+    if (rc != VSC_OK) return rc;
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return rows_timing(ctx, at.n, row_bytes, 0.0f, rows_ms);
+}
+
+// the classes of the candidates, which every family's rows kernel counts first, into the family's stats
+template <class Stats> void class_counts(Stats *stats, const unsigned long long *seen)
+{
+    stats->defined = seen[kEffDefined];
+    stats->invalid = seen[kEffInvalid];
+    stats->off_contig = seen[kEffOffContig];
+    stats->not_resident = seen[kEffNotResident];
+    stats->has_n = seen[kEffHasN];
+}
+
+// The part of edit_tabs that a join uses behind the family's own table: [coverage][pairs per tile][offsets per tile][extra],
+// 256-byte aligned parts.  The family needs its size before the table is uploaded, and its place from the upload.
+struct JoinTabs {
+    uint32_t tiles;
+    size_t cov_bytes, count_bytes, off_bytes, extra_bytes;
+    char *base = nullptr;
+    JoinTabs(uint64_t n, size_t cov, size_t extra)
+        : tiles((uint32_t)((n + kEditTile - 1) / kEditTile)), cov_bytes(cov), count_bytes(round256((size_t)tiles * sizeof(uint32_t))),
+          off_bytes(round256(((size_t)tiles + 1) * sizeof(unsigned long long))), extra_bytes(extra)
+    {
+    }
+    size_t bytes() const { return cov_bytes + count_bytes + off_bytes + extra_bytes; }
+    uint32_t *tile_count() const { return (uint32_t *)(base + cov_bytes); }
+    unsigned long long *tile_off() const { return (unsigned long long *)(base + cov_bytes + count_bytes); }
+    char *extra() const { return base + cov_bytes + count_bytes + off_bytes; }
+};
+
+// What a join is asked for, and what it found.
+struct Join {
+    uint64_t n;             // candidates (> 0)
+    size_t row_bytes;       // of the rows pass in front of it, for the timing
+    bool counted;           // false: the family's table is empty - no pass runs, there is no pair
+    void *pairs;            // the caller's array (null: not asked for) of `capacity` pairs of pair_bytes each
+    size_t pair_bytes;
+    uint64_t capacity;
+    uint64_t *n_pairs;      // the caller's (null: not asked for)
+    uint64_t max_pairs;     // more are refused
+    const char *too_many, *beyond_capacity;  // the two refusals, in the family's words
+    unsigned long long total = 0;  // out: the pairs
+    float rows_ms = 0;             // out: the rows pass
+};
+
+// The join of the rows with a family's table, behind a rows_pass that is still in flight: the count pass and the scan between
+// the second pair of stage events, one 8-byte read-back (the pairs) and the first synchronise; then - where pairs are written
+// or the coverage is counted - the write pass into edit_pairs, the pairs and the coverage copied back, the second synchronise;
+// last the call's timing.  The family has bound its pair args to tabs.tile_count() and tabs.tile_off(); its callables:
+// launch(pairs, write) starts a pass (pairs == null: the count pass, or a write pass for the coverage alone);
+// wants_cover(too_many) says after the first synchronise whether the coverage is to be counted; clear_cover() binds and
+// clears the family's coverage arrays; read_cover() enqueues what of them goes back.
+// VSC_OK also where the pairs are refused: the family fills its stats, then returns join_refusal().
+template <class Launch, class WantsCover, class ClearCover, class ReadCover>
+int join_passes(vsc_ctx *ctx, const JoinTabs &tabs, Join &j, Launch launch, WantsCover wants_cover, ClearCover clear_cover, ReadCover read_cover)
+{
+    float pass_ms = 0;
+    if (j.counted) {
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch((uint4 *)nullptr, false));
+        VSC_HIP(ctx, launch_enum_scan(tabs.tile_count(), tabs.tiles, tabs.tile_off(), ctx->stream));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync(&j.total, tabs.tile_off() + tabs.tiles, sizeof j.total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (j.counted) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+    if (j.n_pairs) *j.n_pairs = j.total;
+    const bool too_many = j.total > j.max_pairs, write = j.pairs && j.total && j.total <= j.capacity && !too_many;
+    const bool cover = j.total && wants_cover(too_many);
+    if (write || cover) {
+        uint4 *d_pairs = nullptr;
+        if (write) {
+            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)j.total * j.pair_bytes));
+            d_pairs = (uint4 *)ctx->edit_pairs.p;
+        }
+        if (cover) {
+            const int crc = clear_cover();
+            if (crc != VSC_OK) return crc;
+        }
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
+        VSC_HIP(ctx, launch(d_pairs, true));
+        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
+        if (write) VSC_HIP(ctx, hipMemcpyAsync(j.pairs, d_pairs, (size_t)j.total * j.pair_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (cover) {
+            const int rrc = read_cover();
+            if (rrc != VSC_OK) return rrc;
+        }
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        float wms = 0;
+        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
+        pass_ms += wms;
+    }
+    return rows_timing(ctx, j.n, j.row_bytes, pass_ms, &j.rows_ms);
+}
+
+// how a call with a join returns, its stats filled: the pairs it could not give are a refusal
+int join_refusal(vsc_ctx *ctx, const Join &j, const char *who)
+{
+    if (j.total > j.max_pairs) return fail_in(ctx, VSC_ERR_RANGE, who, j.too_many);
+    if (j.pairs && j.total > j.capacity) return fail_in(ctx, VSC_ERR_RANGE, who, j.beyond_capacity);
+    return VSC_OK;
+}
+
+// The coverage of the edit, prime and effects joins: per entry of the family's table (a target, an edit, a transcript) its
+// pairs and the smallest of a value over them, (0, undefined) without a pair; on the device two arrays at the front of the
+// join's part of edit_tabs, for the caller interleaved.
+struct PairCoverage {
+    size_t n;                          // entries
+    uint32_t *coverage;                // the caller's 2 n words (null: not asked for; the stats then want the covered entries alone)
+    uint32_t *count = nullptr, *min = nullptr;  // device
+    std::vector<uint32_t> host;        // both arrays as they come back
+    unsigned long long d_covered = 0;  // the covered entries as the device counted them
+    static size_t bytes(size_t entries) { return round256(entries * sizeof(uint32_t) + 4); }  // of one array
+
+    PairCoverage(size_t n_entries, uint32_t *out, uint32_t undefined) : n(n_entries), coverage(out)
+    {
+        for (size_t k = 0; coverage && k < n; ++k) {
+            coverage[2 * k] = 0;
+            coverage[2 * k + 1] = undefined;
+        }
+    }
+    int clear(vsc_ctx *ctx, const JoinTabs &tabs)
+    {
+        count = (uint32_t *)tabs.base;
+        min = (uint32_t *)(tabs.base + bytes(n));
+        VSC_HIP(ctx, hipMemsetAsync(count, 0, n * sizeof(uint32_t), ctx->stream));
+        VSC_HIP(ctx, hipMemsetAsync(min, 0xFF, n * sizeof(uint32_t), ctx->stream));
+        return VSC_OK;
+    }
+    // slot: 8 bytes inside the zeroed head of eff_out, behind the rows kernel's counters
+    int read(vsc_ctx *ctx, unsigned long long *slot)
+    {
+        if (!coverage) {  // the stats alone: the covered entries are counted where they lie, 8 bytes come back
+            VSC_HIP(ctx, launch_edit_covered(count, (uint32_t)n, slot, ctx->n_cus, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+        } else {
+            host.resize(2 * n);
+            VSC_HIP(ctx, hipMemcpyAsync(host.data(), count, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(host.data() + n, min, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        return VSC_OK;
+    }
+    // after the join: the caller's coverage filled, the covered entries
+    uint64_t take()
+    {
+        uint64_t covered = d_covered;
+        for (size_t k = 0; !host.empty() && k < n; ++k) {
+            covered += host[k] != 0;
+            coverage[2 * k] = host[k];
+            coverage[2 * k + 1] = host[n + k];
+        }
+        return covered;
+    }
+};
+
+}  // namespace
+
 // ---- on-target efficiency (the definition: vsc_efficiency.h, the kernels: vsc_efficiency.hip) -------------------
 namespace {
 
@@ -4163,58 +4469,35 @@ int eff_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_model *model
     return VSC_OK;
 }
 
-// The predictors of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first) - into host memory:
-// the model resident, eff_score_kernel, one copy back of the scores and one of the class counts.
-int eff_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_model *model, const void *d_loci, const vsc_locus *h_loci,
-              uint64_t n, double *linear, vsc_eff_stats *stats, const char *who)
+const CandidateRule kEffScoreRule{"the model's site_len must be 23", ~0ull, ""};  // (the scoring itself refuses above 2^40)
+const CandidateRule kEffFilterRule{"the model's site_len must be 23", 0xFFFFFFFFull * kEffTile, "more candidates than 2^32 tiles hold"};
+static_assert(kEffClasses * sizeof(unsigned long long) <= 256, "the class counts fit their part of eff_out");
+
+// The predictors of the loci `at` into host memory: the model resident, eff_score_kernel, one copy back of the scores and one
+// of the class counts.
+int eff_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_model *model, const CandidateLoci &at, double *linear, vsc_eff_stats *stats,
+              const char *who)
 {
     if (stats) *stats = vsc_eff_stats{};
-    vsc_timing t{};
-    if (n == 0) {
-        ctx->timing = t;
+    if (at.n == 0) {
+        ctx->timing = vsc_timing{};
         return VSC_OK;
     }
-    if (!linear) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     EffArgs a{};
-    const int mrc = resident_eff_model(ctx, model, a.m);
-    if (mrc != VSC_OK) return mrc;
     a.g = eff_planes(genome);
-    a.n = n;
-    const size_t head = 256;  // the class counts, in front of the scores
-    static_assert(kEffClasses * sizeof(unsigned long long) <= 256, "the class counts fit their part of eff_out");
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(double)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.linear = (double *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_eff_score(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    a.n = at.n;
     unsigned long long seen[kEffClasses] = {};
-    VSC_HIP(ctx, hipMemcpyAsync(linear, a.linear, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
-    }
-    t.score_ms = t.total_ms = ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(double));
-    ctx->timing = t;
+    const int rc = score_rows(
+        ctx, at, sizeof(double), linear, seen, kEffClasses, &ms, who, [&] { return resident_eff_model(ctx, model, a.m); },
+        [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+            a.stats = d_stats;
+            a.linear = (double *)d_rows;
+            a.loci = d_loci;
+            return launch_eff_score(a, ctx->n_cus, ctx->stream);
+        });
+    if (rc != VSC_OK) return rc;
+    if (stats) class_counts(stats, seen);
     return VSC_OK;
 }
 
@@ -4224,64 +4507,31 @@ int eff_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, con
                      vsc_eff_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
-    const int rc = eff_check(ctx, genome, model, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kEffScoreRule, who, at, model ? &model->shape.site_len : nullptr,
+                                   [&] { return eff_check(ctx, genome, model, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
-    const bool dev = guides->ctx != nullptr;
-    return eff_score(ctx, genome, model, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
-                     guides->n, linear, stats, who);
+    return eff_score(ctx, genome, model, at, linear, stats, who);
     });
 }
 
-// vsc_guides_filter_efficiency / vsc_pattern_guides_filter_efficiency: run_enumeration's two passes over tiles of kEffTile
-// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the efficiency calls report theirs.
+// vsc_guides_filter_efficiency / vsc_pattern_guides_filter_efficiency: the candidates whose predictor is at least min_linear
 template <class Guides>
 int eff_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_eff_model *model, bool need_23, double min_linear, Guides **out,
                const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
-    const int rc = eff_check(ctx, genome, model, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kEffFilterRule, who, model ? &model->shape.site_len : nullptr,
+        [&] { return eff_check(ctx, genome, model, who); },
+        [&] { return std::isnan(min_linear) ? fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN") : VSC_OK; });
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
-    if (std::isnan(min_linear)) return fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN");
-    const uint64_t n = in->n;
-    const uint64_t tiles = (n + kEffTile - 1) / kEffTile;
-    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     EffFilterArgs a{};
     const int mrc = resident_eff_model(ctx, model, a.m);
     if (mrc != VSC_OK) return mrc;
     a.g = eff_planes(genome);
-    a.n = n;
     a.min_linear = min_linear;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_eff_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEffTile, out, who, [&](bool write) { return launch_eff_filter(a, write, ctx->stream); });
     });
 }
 
@@ -4370,7 +4620,7 @@ int vsc_loci_efficiency(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus 
     const int rc = eff_check(ctx, genome, model, fn);
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
-    return eff_score(ctx, genome, model, nullptr, loci, n, linear, stats, fn);
+    return eff_score(ctx, genome, model, CandidateLoci{nullptr, loci, n}, linear, stats, fn);
     });
 }
 
@@ -4429,55 +4679,29 @@ int eff_trees_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_trees 
 }
 
 // eff_score with the tree model: the model resident, eff_trees_score_kernel, one copy back of the scores and one of the counts
-int eff_trees_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_trees *model, const void *d_loci, const vsc_locus *h_loci,
-                    uint64_t n, double *linear, vsc_eff_stats *stats, const char *who)
+int eff_trees_score(vsc_ctx *ctx, const vsc_genome *genome, const vsc_eff_trees *model, const CandidateLoci &at, double *linear,
+                    vsc_eff_stats *stats, const char *who)
 {
     if (stats) *stats = vsc_eff_stats{};
-    vsc_timing t{};
-    if (n == 0) {
-        ctx->timing = t;
+    if (at.n == 0) {
+        ctx->timing = vsc_timing{};
         return VSC_OK;
     }
-    if (!linear) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     EffTreesArgs a{};
-    const int mrc = resident_eff_trees(ctx, model, a.m);
-    if (mrc != VSC_OK) return mrc;
     a.g = eff_planes(genome);
-    a.n = n;
-    const size_t head = 256;  // the class counts, in front of the scores
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(double)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.linear = (double *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_eff_trees_score(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    a.n = at.n;
     unsigned long long seen[kEffClasses] = {};
-    VSC_HIP(ctx, hipMemcpyAsync(linear, a.linear, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
-    }
-    t.score_ms = t.total_ms = ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(double));
-    ctx->timing = t;
+    const int rc = score_rows(
+        ctx, at, sizeof(double), linear, seen, kEffClasses, &ms, who, [&] { return resident_eff_trees(ctx, model, a.m); },
+        [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+            a.stats = d_stats;
+            a.linear = (double *)d_rows;
+            a.loci = d_loci;
+            return launch_eff_trees_score(a, ctx->n_cus, ctx->stream);
+        });
+    if (rc != VSC_OK) return rc;
+    if (stats) class_counts(stats, seen);
     return VSC_OK;
 }
 
@@ -4486,15 +4710,11 @@ int eff_trees_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guide
                            vsc_eff_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
-    const int rc = eff_trees_check(ctx, genome, model, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kEffScoreRule, who, at, model ? &model->shape.site_len : nullptr,
+                                   [&] { return eff_trees_check(ctx, genome, model, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
-    const bool dev = guides->ctx != nullptr;
-    return eff_trees_score(ctx, genome, model, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
-                           dev ? nullptr : guides->loci.data(), guides->n, linear, stats, who);
+    return eff_trees_score(ctx, genome, model, at, linear, stats, who);
     });
 }
 
@@ -4503,45 +4723,17 @@ int eff_trees_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const v
                      Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
-    const int rc = eff_trees_check(ctx, genome, model, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kEffFilterRule, who, model ? &model->shape.site_len : nullptr,
+        [&] { return eff_trees_check(ctx, genome, model, who); },
+        [&] { return std::isnan(min_linear) ? fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN") : VSC_OK; });
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && model->shape.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the model's site_len must be 23");
-    if (std::isnan(min_linear)) return fail_in(ctx, VSC_ERR_INVALID, who, "min_linear is NaN");
-    const uint64_t n = in->n;
-    const uint64_t tiles = (n + kEffTile - 1) / kEffTile;
-    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     EffTreesFilterArgs a{};
     const int mrc = resident_eff_trees(ctx, model, a.m);
     if (mrc != VSC_OK) return mrc;
     a.g = eff_planes(genome);
-    a.n = n;
     a.min_linear = min_linear;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_eff_trees_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEffTile, out, who, [&](bool write) { return launch_eff_trees_filter(a, write, ctx->stream); });
     });
 }
 
@@ -4628,7 +4820,7 @@ int vsc_loci_efficiency_trees(vsc_ctx *ctx, const vsc_genome *genome, const vsc_
     const int rc = eff_trees_check(ctx, genome, model, fn);
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
-    return eff_trees_score(ctx, genome, model, nullptr, loci, n, linear, stats, fn);
+    return eff_trees_score(ctx, genome, model, CandidateLoci{nullptr, loci, n}, linear, stats, fn);
     });
 }
 
@@ -4661,11 +4853,6 @@ int vsc_pattern_guides_filter_efficiency_trees(vsc_ctx *ctx, const vsc_genome *g
 // ---- microhomology and out-of-frame scores (the definition: vsc_mh.h, the kernels: vsc_mh.hip) ------------------
 namespace {
 
-double wall_ms_since(std::chrono::steady_clock::time_point t0)
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int mh_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_mh_shape *shape, MhShape &s, const char *who)
 {
     ctx->err.clear();
@@ -4676,59 +4863,39 @@ int mh_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_mh_shape *shape, 
     return VSC_OK;
 }
 
-// The pairs of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first) - into host memory:
-// mh_score_kernel, one copy back of the pairs and one of the class counts.  The scratch is the efficiency calls'.
-int mh_score_loci(vsc_ctx *ctx, const vsc_genome *genome, const MhShape &shape, const void *d_loci, const vsc_locus *h_loci, uint64_t n,
-                  uint32_t *pairs, vsc_mh_stats *stats, const char *who)
+const CandidateRule kMhScoreRule{"the shape's site_len must be 23", ~0ull, ""};  // (the scoring itself refuses above 2^40)
+const CandidateRule kMhFilterRule{"the shape's site_len must be 23", 0xFFFFFFFFull * kMhTile, "more candidates than 2^32 tiles hold"};
+
+// The pairs of the loci `at` into host memory: mh_score_kernel, one copy back of the pairs and one of the class counts.
+int mh_score_loci(vsc_ctx *ctx, const vsc_genome *genome, const MhShape &shape, const CandidateLoci &at, uint32_t *pairs, vsc_mh_stats *stats,
+                  const char *who)
 {
     const auto t0 = std::chrono::steady_clock::now();
     if (stats) *stats = vsc_mh_stats{};
-    vsc_timing t{};
-    if (n == 0) {
-        ctx->timing = t;
+    if (at.n == 0) {
+        ctx->timing = vsc_timing{};
         return VSC_OK;
     }
-    if (!pairs) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (n > (1ull << 40)) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 2^40 candidates");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     MhArgs a{};
     a.g = eff_planes(genome);
     a.shape = shape;
-    a.n = n;
-    const size_t head = 256;  // the class counts, in front of the pairs
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_mh_score(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
+    a.n = at.n;
     unsigned long long seen[kEffClasses] = {};
-    VSC_HIP(ctx, hipMemcpyAsync(pairs, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
+    const int rc = score_rows(
+        ctx, at, sizeof(uint2), pairs, seen, kEffClasses, &ms, who, [] { return VSC_OK; },
+        [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+            a.stats = d_stats;
+            a.out = (uint2 *)d_rows;
+            a.loci = d_loci;
+            return launch_mh_score(a, ctx->n_cus, ctx->stream);
+        });
+    if (rc != VSC_OK) return rc;
     if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
+        class_counts(stats, seen);
         stats->kernel_ms = ms;
         stats->wall_ms = wall_ms_since(t0);
     }
-    t.score_ms = t.total_ms = ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
-    ctx->timing = t;
     return VSC_OK;
 }
 
@@ -4738,66 +4905,33 @@ int mh_score_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, cons
                     vsc_mh_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     MhShape s{};
-    const int rc = mh_check(ctx, genome, shape, s, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kMhScoreRule, who, at, &s.site_len,
+                                   [&] { return mh_check(ctx, genome, shape, s, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    const bool dev = guides->ctx != nullptr;
-    return mh_score_loci(ctx, genome, s, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
-                         guides->n, pairs, stats, who);
+    return mh_score_loci(ctx, genome, s, at, pairs, stats, who);
     });
 }
 
-// vsc_guides_filter_microhomology / vsc_pattern_guides_filter_microhomology: run_enumeration's two passes over tiles of kMhTile
-// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the scoring calls report theirs.
+// vsc_guides_filter_microhomology / vsc_pattern_guides_filter_microhomology: the candidates within the two bounds
 template <class Guides>
 int mh_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_mh_shape *shape, bool need_23, uint32_t min_sum,
               uint32_t min_oof_permille, Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
     MhShape s{};
-    const int rc = mh_check(ctx, genome, shape, s, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kMhFilterRule, who, &s.site_len,
+        [&] { return mh_check(ctx, genome, shape, s, who); },
+        [&] { return min_oof_permille > 1000u ? fail_in(ctx, VSC_ERR_INVALID, who, "min_oof_permille is more than 1000") : VSC_OK; });
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (min_oof_permille > 1000u) return fail_in(ctx, VSC_ERR_INVALID, who, "min_oof_permille is more than 1000");
-    const uint64_t n = in->n;
-    const uint64_t tiles = (n + kMhTile - 1) / kMhTile;
-    if (tiles > 0xFFFFFFFFull) return fail_in(ctx, VSC_ERR_RANGE, who, "more candidates than 2^32 tiles hold");
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     MhFilterArgs a{};
     a.g = eff_planes(genome);
     a.shape = s;
-    a.n = n;
     a.min_sum = min_sum;
     a.min_oof_permille = min_oof_permille;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_mh_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kMhTile, out, who, [&](bool write) { return launch_mh_filter(a, write, ctx->stream); });
     });
 }
 
@@ -4845,7 +4979,7 @@ int vsc_loci_microhomology(vsc_ctx *ctx, const vsc_genome *genome, const vsc_loc
     const int rc = mh_check(ctx, genome, shape, s, fn);
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
-    return mh_score_loci(ctx, genome, s, nullptr, loci, n, pairs, stats, fn);
+    return mh_score_loci(ctx, genome, s, CandidateLoci{nullptr, loci, n}, pairs, stats, fn);
     });
 }
 
@@ -5353,142 +5487,77 @@ int edit_upload_targets(vsc_ctx *ctx, const std::vector<uint32_t> &gpos, size_t 
     return VSC_OK;
 }
 
-// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): edit_rows_kernel,
-// then - with targets - the pairs' count pass over the rows, the scan, one 8-byte read-back (the pairs) and the write pass.
-int edit_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, const std::vector<uint32_t> &gpos, const void *d_loci,
-             const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
-             vsc_edit_stats *stats, const char *who)
+const CandidateRule kEditRule{"the shape's site_len must be 23", kEditMaxCount, "more than 0xFFFFFFFE candidates"};
+
+// Rows, pairs and coverage of the loci `at`: edit_rows_kernel, then - with targets - the join of the rows with them.
+int edit_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, const std::vector<uint32_t> &gpos, const CandidateLoci &at,
+             uint32_t *rows, vsc_edit_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_edit_stats *stats, const char *who)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_t = gpos.size();
+    const uint64_t n = at.n;
     if (stats) *stats = vsc_edit_stats{};
     if (n_pairs) *n_pairs = 0;
-    if (coverage)
-        for (size_t k = 0; k < n_t; ++k) {
-            coverage[2 * k] = 0;
-            coverage[2 * k + 1] = kEditUndefined;
-        }
-    vsc_timing t{};
+    PairCoverage cov(n_t, coverage, kEditUndefined);
     if (n == 0) {
-        ctx->timing = t;
+        ctx->timing = vsc_timing{};
         if (stats) stats->wall_ms = wall_ms_since(t0);
         return VSC_OK;
     }
     VSC_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
     // edit_tabs: [targets][pairs per target][fewest bystanders per target][pairs per tile][offsets per tile]
-    const size_t cov_bytes = round256(n_t * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
-    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
+    JoinTabs tabs(n, 2 * PairCoverage::bytes(n_t), 0);
     EditArgs a{};
-    char *tabs = nullptr;
-    const int urc = edit_upload_targets(ctx, gpos, 2 * cov_bytes + count_bytes + off_bytes, a.targets, &tabs);
+    const int urc = edit_upload_targets(ctx, gpos, tabs.bytes(), a.targets, &tabs.base);
     if (urc != VSC_OK) return urc;
     a.g = eff_planes(genome);
     a.shape = shape;
     a.n = n;
-    const size_t head = 256;  // the counters, in front of the rows
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_edit_rows(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     unsigned long long seen[kEditCounts] = {};
-    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    const int rrc = rows_pass(ctx, at, sizeof(uint2), rows, seen, kEditCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint2 *)d_rows;
+        a.loci = d_loci;
+        return launch_edit_rows(a, ctx->n_cus, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
     EditPairArgs p{};
-    unsigned long long total = 0;
-    float pass_ms = 0;
-    if (n_t) {
-        p.shape = shape;
-        p.targets = a.targets;
-        p.contig_off = genome->d_contig_off;
-        p.loci = a.loci;
-        p.rows = a.out;
-        p.n = n;
-        p.n_work = tiles;
-        p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
-        unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
-        p.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_edit_pairs(p, false, ctx->stream));
-        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    if (n_t) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-    if (n_pairs) *n_pairs = total;
-    const bool too_many = total > kEditMaxCount, write = pairs && total && total <= capacity && !too_many, cover = total && (coverage || stats);
-    uint64_t covered = 0;
-    if (write || cover) {
-        if (write) {
-            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_edit_pair)));
-            p.pairs = (uint4 *)ctx->edit_pairs.p;
-        }
-        if (cover) {
-            p.cov_count = (uint32_t *)tabs;
-            p.cov_min = (uint32_t *)(tabs + cov_bytes);
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_t * sizeof(uint32_t), ctx->stream));
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_t * sizeof(uint32_t), ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_edit_pairs(p, true, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        std::vector<uint32_t> cov;
-        unsigned long long d_covered = 0;
-        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_edit_pair), hipMemcpyDeviceToHost, ctx->stream));
-        if (cover && !coverage) {  // the stats alone: the covered targets are counted where they lie, 8 bytes come back
-            unsigned long long *slot = a.stats + kEditCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
-            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_t, slot, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (cover) {
-            cov.resize(2 * n_t);
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_t * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_t, p.cov_min, n_t * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float wms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-        pass_ms += wms;
-        covered = d_covered;
-        for (size_t k = 0; coverage && k < n_t; ++k) {
-            covered += cov[k] != 0;
-            coverage[2 * k] = cov[k];
-            coverage[2 * k + 1] = cov[n_t + k];
-        }
-    }
+    p.shape = shape;
+    p.targets = a.targets;
+    p.contig_off = genome->d_contig_off;
+    p.loci = a.loci;
+    p.rows = a.out;
+    p.n = n;
+    p.n_work = tabs.tiles;
+    p.tile_count = tabs.tile_count();
+    p.tile_off = tabs.tile_off();
+    Join j{n, sizeof(uint2), n_t != 0, pairs, sizeof(vsc_edit_pair), capacity, n_pairs, kEditMaxCount, "more than 0xFFFFFFFE pairs",
+           "more pairs than `capacity` holds; *n_pairs is their number"};
+    const int jrc = join_passes(
+        ctx, tabs, j,
+        [&](uint4 *d_pairs, bool write) {
+            p.pairs = d_pairs;
+            return launch_edit_pairs(p, write, ctx->stream);
+        },
+        [&](bool) { return coverage || stats; },
+        [&] {
+            const int crc = cov.clear(ctx, tabs);
+            p.cov_count = cov.count;
+            p.cov_min = cov.min;
+            return crc;
+        },
+        [&] { return cov.read(ctx, a.stats + kEditCounts + 1); });
+    if (jrc != VSC_OK) return jrc;
+    const uint64_t covered = cov.take();
     if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
+        class_counts(stats, seen);
         stats->with_hit = seen[kEffClasses];
-        stats->pairs = total;
+        stats->pairs = j.total;
         stats->targets_covered = covered;
-        stats->kernel_ms = ms;
+        stats->kernel_ms = j.rows_ms;
         stats->wall_ms = wall_ms_since(t0);
     }
-    t.score_ms = ms;
-    t.scan_ms = pass_ms;
-    t.total_ms = t.score_ms + t.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
-    ctx->timing = t;
-    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
-    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
-    return VSC_OK;
+    return join_refusal(ctx, j, who);
 }
 
 // vsc_guides_edit / vsc_pattern_guides_edit: over the candidates where they lie, a host-only object from the host
@@ -5498,72 +5567,38 @@ int edit_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vs
                 vsc_edit_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     EditShape s{};
     std::vector<uint32_t> gpos;
-    const int rc = edit_check(ctx, genome, shape, targets, n_t, s, gpos, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kEditRule, who, at, &s.site_len,
+                                   [&] { return edit_check(ctx, genome, shape, targets, n_t, s, gpos, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (guides->n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const bool dev = guides->ctx != nullptr;
-    return edit_run(ctx, genome, s, gpos, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
-                    guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    return edit_run(ctx, genome, s, gpos, at, rows, pairs, capacity, n_pairs, coverage, stats, who);
     });
 }
 
-// vsc_guides_filter_edit / vsc_pattern_guides_filter_edit: run_enumeration's two passes over tiles of kEditTile candidates of `in`
-// (a host-only object: uploaded first); its timing is then restated as the microhomology filter restates its own.
+// vsc_guides_filter_edit / vsc_pattern_guides_filter_edit: the candidates with a hit and an editable count within the bounds
 template <class Guides>
 int edit_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_edit_shape *shape, const vsc_edit_target *targets, uint64_t n_t,
                 bool need_23, uint32_t min_editable, uint32_t max_editable, Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
     EditShape s{};
     std::vector<uint32_t> gpos;
-    const int rc = edit_check(ctx, genome, shape, targets, n_t, s, gpos, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kEditRule, who, &s.site_len,
+        [&] { return edit_check(ctx, genome, shape, targets, n_t, s, gpos, who); },
+        [&] { return min_editable > max_editable ? fail_in(ctx, VSC_ERR_INVALID, who, "min_editable is more than max_editable") : VSC_OK; });
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (min_editable > max_editable) return fail_in(ctx, VSC_ERR_INVALID, who, "min_editable is more than max_editable");
-    const uint64_t n = in->n;
-    if (n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     EditFilterArgs a{};
     const int urc = edit_upload_targets(ctx, gpos, 0, a.targets, nullptr);
     if (urc != VSC_OK) return urc;
+    if (in->n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (gpos is this call's vector, and no pass will wait)
     a.g = eff_planes(genome);
     a.shape = s;
-    a.n = n;
     a.min_editable = min_editable;
     a.max_editable = max_editable;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    if (n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (gpos is this call's vector)
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_edit_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_edit_filter(a, write, ctx->stream); });
     });
 }
 
@@ -5601,7 +5636,7 @@ int vsc_loci_edit(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci,
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
     if (n > kEditMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
-    return edit_run(ctx, genome, s, gpos, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    return edit_run(ctx, genome, s, gpos, CandidateLoci{nullptr, loci, n}, rows, pairs, capacity, n_pairs, coverage, stats, fn);
     });
 }
 
@@ -5708,131 +5743,89 @@ int var_upload(vsc_ctx *ctx, const vsc_genome *genome, const vsc_variant *varian
     return VSC_OK;
 }
 
-// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): the variants'
-// build, var_rows_kernel, then - with variants - the pairs' count pass over the rows, the scan, one 8-byte read-back (the
-// pairs) and the write pass.
-int var_run(vsc_ctx *ctx, const vsc_genome *genome, const VarShape &shape, const vsc_variant *variants, uint64_t n_v, const void *d_loci,
-            const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
-            vsc_variation_stats *stats, const char *who)
+const CandidateRule kVarRule{"the shape's site_len must be 23", kVarMaxCount, "more than 0xFFFFFFFE candidates"};
+
+// Rows, pairs and coverage of the loci `at`: the variants' build, var_rows_kernel, then - with variants - the join of the rows
+// with them.  The coverage is one array of two words per variant, zeros without a pair, and comes back as it lies.
+int var_run(vsc_ctx *ctx, const vsc_genome *genome, const VarShape &shape, const vsc_variant *variants, uint64_t n_v, const CandidateLoci &at,
+            uint32_t *rows, vsc_variation_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_variation_stats *stats,
+            const char *who)
 {
     const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t n = at.n;
     if (stats) *stats = vsc_variation_stats{};
     if (n_pairs) *n_pairs = 0;
     if (coverage) std::fill(coverage, coverage + 2 * n_v, 0u);
-    vsc_timing t{};
     if (n == 0) {
-        ctx->timing = t;
+        ctx->timing = vsc_timing{};
         if (stats) stats->wall_ms = wall_ms_since(t0);
         return VSC_OK;
     }
     VSC_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
     // edit_tabs behind the variants and their table: [pairs per variant, two kinds][pairs per tile][offsets per tile]
-    const size_t cov_bytes = round256(2 * (size_t)n_v * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
-    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
+    JoinTabs tabs(n, round256(2 * (size_t)n_v * sizeof(uint32_t) + 4), 0);
     VarArgs a{};
-    char *tabs = nullptr;
-    const int urc = var_upload(ctx, genome, variants, n_v, cov_bytes + count_bytes + off_bytes, a.table, &tabs);
+    const int urc = var_upload(ctx, genome, variants, n_v, tabs.bytes(), a.table, &tabs.base);
     if (urc != VSC_OK) return urc;
     a.g = eff_planes(genome);
     a.shape = shape;
     a.n = n;
-    const size_t head = 256;  // the counters, in front of the rows
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint4)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.out = (uint4 *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_var_rows(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     unsigned long long seen[kVarCounts] = {};
-    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    const int rrc = rows_pass(ctx, at, sizeof(uint4), rows, seen, kVarCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint4 *)d_rows;
+        a.loci = d_loci;
+        return launch_var_rows(a, ctx->n_cus, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
     VarPairArgs p{};
-    unsigned long long total = 0;
-    float pass_ms = 0;
-    if (n_v) {
-        p.shape = shape;
-        p.table = a.table;
-        p.contig_off = genome->d_contig_off;
-        p.loci = a.loci;
-        p.rows = a.out;
-        p.n = n;
-        p.n_work = tiles;
-        p.tile_count = (uint32_t *)(tabs + cov_bytes);
-        unsigned long long *d_off = (unsigned long long *)(tabs + cov_bytes + count_bytes);
-        p.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_var_pairs(p, false, ctx->stream));
-        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    if (n_v) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-    if (n_pairs) *n_pairs = total;
-    // (a tile's count saturates at 0xFFFFFFFF, so a total within the bound is the exact one)
-    const bool too_many = total > kVarMaxCount, write = pairs && total && total <= capacity && !too_many;
-    const bool cover = total && !too_many && (coverage || stats);
-    uint64_t covered = 0;
-    if (write || cover) {
-        if (write) {
-            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_variation_pair)));
-            p.pairs = (uint4 *)ctx->edit_pairs.p;
-        }
-        if (cover) {
-            p.coverage = (uint32_t *)tabs;
+    p.shape = shape;
+    p.table = a.table;
+    p.contig_off = genome->d_contig_off;
+    p.loci = a.loci;
+    p.rows = a.out;
+    p.n = n;
+    p.n_work = tabs.tiles;
+    p.tile_count = tabs.tile_count();
+    p.tile_off = tabs.tile_off();
+    Join j{n, sizeof(uint4), n_v != 0, pairs, sizeof(vsc_variation_pair), capacity, n_pairs, kVarMaxCount, "more than 0xFFFFFFFE pairs",
+           "more pairs than `capacity` holds; *n_pairs is their number"};
+    unsigned long long d_covered = 0;
+    const int jrc = join_passes(
+        ctx, tabs, j,
+        [&](uint4 *d_pairs, bool write) {
+            p.pairs = d_pairs;
+            return launch_var_pairs(p, write, ctx->stream);
+        },
+        // (a tile's count saturates at 0xFFFFFFFF, so a total within the bound is the exact one - and only such a one is covered)
+        [&](bool too_many) { return !too_many && (coverage || stats); },
+        [&] {
+            p.coverage = (uint32_t *)tabs.base;
             VSC_HIP(ctx, hipMemsetAsync(p.coverage, 0, 2 * (size_t)n_v * sizeof(uint32_t), ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_var_pairs(p, true, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        unsigned long long d_covered = 0;
-        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_variation_pair), hipMemcpyDeviceToHost, ctx->stream));
-        if (cover && !coverage) {  // the stats alone: the covered variants are counted where they lie, 8 bytes come back
-            unsigned long long *slot = a.stats + kVarCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
-            VSC_HIP(ctx, launch_var_covered(p.coverage, (uint32_t)n_v, slot, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (cover) {
-            VSC_HIP(ctx, hipMemcpyAsync(coverage, p.coverage, 2 * (size_t)n_v * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float wms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-        pass_ms += wms;
-        covered = d_covered;
-        for (uint64_t k = 0; coverage && k < n_v; ++k) covered += (coverage[2 * k] | coverage[2 * k + 1]) != 0;
-    }
+            return VSC_OK;
+        },
+        [&] {
+            if (!coverage) {  // the stats alone: the covered variants are counted where they lie, 8 bytes come back
+                unsigned long long *slot = a.stats + kVarCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
+                VSC_HIP(ctx, launch_var_covered(p.coverage, (uint32_t)n_v, slot, ctx->n_cus, ctx->stream));
+                VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
+            } else {
+                VSC_HIP(ctx, hipMemcpyAsync(coverage, p.coverage, 2 * (size_t)n_v * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            }
+            return VSC_OK;
+        });
+    if (jrc != VSC_OK) return jrc;
+    uint64_t covered = d_covered;
+    for (uint64_t k = 0; coverage && p.coverage && k < n_v; ++k) covered += (coverage[2 * k] | coverage[2 * k + 1]) != 0;
     if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
+        class_counts(stats, seen);
         stats->with_disrupting = seen[kEffClasses];
-        stats->pairs = total;
+        stats->pairs = j.total;
         stats->variants_covered = covered;
-        stats->kernel_ms = ms;
+        stats->kernel_ms = j.rows_ms;
         stats->wall_ms = wall_ms_since(t0);
     }
-    t.score_ms = ms;
-    t.scan_ms = pass_ms;
-    t.total_ms = t.score_ms + t.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint4));
-    ctx->timing = t;
-    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
-    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
-    return VSC_OK;
+    return join_refusal(ctx, j, who);
 }
 
 // vsc_guides_variation / vsc_pattern_guides_variation: over the candidates where they lie, a host-only object from the host
@@ -5842,70 +5835,43 @@ int var_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc
                vsc_variation_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     VarShape s{};
-    const int rc = var_check_ctx(ctx, genome, shape, variants, n_v, s, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kVarRule, who, at, &s.site_len,
+                                   [&] { return var_check_ctx(ctx, genome, shape, variants, n_v, s, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (guides->n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const bool dev = guides->ctx != nullptr;
-    return var_run(ctx, genome, s, variants, n_v, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
-                   dev ? nullptr : guides->loci.data(), guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    return var_run(ctx, genome, s, variants, n_v, at, rows, pairs, capacity, n_pairs, coverage, stats, who);
     });
 }
 
-// vsc_guides_filter_variation / vsc_pattern_guides_filter_variation: run_enumeration's two passes over tiles of kEditTile
-// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+// vsc_guides_filter_variation / vsc_pattern_guides_filter_variation: the candidates within the bounds of `filter`
 template <class Guides>
 int var_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_variation_shape *shape, const vsc_variant *variants, uint64_t n_v,
                bool need_23, const vsc_variation_filter *filter, Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
     VarShape s{};
-    const int rc = var_check_ctx(ctx, genome, shape, variants, n_v, s, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kVarRule, who, &s.site_len,
+        [&] {
+            const int crc = var_check_ctx(ctx, genome, shape, variants, n_v, s, who);
+            return crc == VSC_OK && !filter ? fail_in(ctx, VSC_ERR_INVALID, who, "null argument") : crc;
+        },
+        [&] {
+            if (filter->require_zones > 15u || filter->reserved)
+                return fail_in(ctx, VSC_ERR_INVALID, who, "require_zones is a mask of four bits, the reserved field 0");
+            return VSC_OK;
+        });
     if (rc != VSC_OK) return rc;
-    if (!in || !filter) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (filter->require_zones > 15u || filter->reserved) return fail_in(ctx, VSC_ERR_INVALID, who, "require_zones is a mask of four bits, the reserved field 0");
-    const uint64_t n = in->n;
-    if (n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     VarFilterArgs a{};
-    if (n) {
+    if (in->n) {  // (no candidate: no pass reads the variants)
         const int urc = var_upload(ctx, genome, variants, n_v, 0, a.table, nullptr);
         if (urc != VSC_OK) return urc;
     }
     a.g = eff_planes(genome);
     a.shape = s;
     a.filter = VarFilter{filter->max_cost, filter->max_by_zone, filter->require_zones};
-    a.n = n;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_var_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_var_filter(a, write, ctx->stream); });
     });
 }
 
@@ -6014,7 +5980,7 @@ int vsc_loci_variation(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
     if (n > kVarMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
-    return var_run(ctx, genome, s, variants, n_v, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    return var_run(ctx, genome, s, variants, n_v, CandidateLoci{nullptr, loci, n}, rows, pairs, capacity, n_pairs, coverage, stats, fn);
     });
 }
 
@@ -6140,148 +6106,88 @@ int prime_upload_edits(vsc_ctx *ctx, const PrimeHostEdits &h, size_t more, Prime
     return VSC_OK;
 }
 
-// Rows, pairs and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first): prime_rows_kernel,
-// then - with edits - the pairs' count pass over the rows, the scan, one 8-byte read-back (the pairs) and the write pass.
-int prime_run(vsc_ctx *ctx, const vsc_genome *genome, const PrimeShape &shape, const PrimeHostEdits &h, const void *d_loci, const vsc_locus *h_loci,
-              uint64_t n, uint32_t *rows, vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats,
-              const char *who)
+const CandidateRule kPrimeRule{"the shape's site_len must be 23", kPrimeMaxCount, "more than 0xFFFFFFFE candidates"};
+
+// Rows, pairs and coverage of the loci `at`: prime_rows_kernel, then - with edits - the join of the rows with them, whose write
+// pass also counts the pairs by flag.
+int prime_run(vsc_ctx *ctx, const vsc_genome *genome, const PrimeShape &shape, const PrimeHostEdits &h, const CandidateLoci &at, uint32_t *rows,
+              vsc_prime_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_prime_stats *stats, const char *who)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_e = h.gpos.size();
+    const uint64_t n = at.n;
     if (stats) *stats = vsc_prime_stats{};
     if (n_pairs) *n_pairs = 0;
-    if (coverage)
-        for (size_t k = 0; k < n_e; ++k) {
-            coverage[2 * k] = 0;
-            coverage[2 * k + 1] = kPrimeUndefined;
-        }
-    vsc_timing t{};
+    PairCoverage cov(n_e, coverage, kPrimeUndefined);
     if (n == 0) {
-        ctx->timing = t;
+        ctx->timing = vsc_timing{};
         if (stats) stats->wall_ms = wall_ms_since(t0);
         return VSC_OK;
     }
     VSC_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
     // edit_tabs behind the edits: [pairs per edit][smallest t per edit][pairs per tile][offsets per tile][pairs by flag]
-    const size_t cov_bytes = round256(n_e * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
-    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long)), flag_bytes = 256;
+    const size_t flag_bytes = 256;
+    JoinTabs tabs(n, 2 * PairCoverage::bytes(n_e), flag_bytes);
     PrimeArgs a{};
-    char *tabs = nullptr;
-    const int urc = prime_upload_edits(ctx, h, 2 * cov_bytes + count_bytes + off_bytes + flag_bytes, a.edits, &tabs);
+    const int urc = prime_upload_edits(ctx, h, tabs.bytes(), a.edits, &tabs.base);
     if (urc != VSC_OK) return urc;
     a.g = eff_planes(genome);
     a.shape = shape;
     a.n = n;
-    const size_t head = 256;  // the counters, in front of the rows
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_prime_rows(a, ctx->n_cus, ctx->prime_groups_per_cu, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     unsigned long long seen[kPrimeCounts] = {};
-    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    const int rrc = rows_pass(ctx, at, sizeof(uint2), rows, seen, kPrimeCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint2 *)d_rows;
+        a.loci = d_loci;
+        return launch_prime_rows(a, ctx->n_cus, ctx->prime_groups_per_cu, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
     PrimePairArgs p{};
-    unsigned long long total = 0;
-    float pass_ms = 0;
-    if (n_e) {
-        p.g = a.g;
-        p.shape = shape;
-        p.edits = a.edits;
-        p.loci = a.loci;
-        p.rows = a.out;
-        p.n = n;
-        p.n_work = tiles;
-        p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
-        unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
-        p.tile_off = d_off;
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_prime_pairs(p, false, ctx->stream));
-        VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    if (n_e) VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-    if (n_pairs) *n_pairs = total;
-    const bool too_many = total > kPrimeMaxCount, write = pairs && total && total <= capacity && !too_many, cover = total && (coverage || stats);
-    uint64_t covered = 0;
+    p.g = a.g;
+    p.shape = shape;
+    p.edits = a.edits;
+    p.loci = a.loci;
+    p.rows = a.out;
+    p.n = n;
+    p.n_work = tabs.tiles;
+    p.tile_count = tabs.tile_count();
+    p.tile_off = tabs.tile_off();
+    Join j{n, sizeof(uint2), n_e != 0, pairs, sizeof(vsc_prime_pair), capacity, n_pairs, kPrimeMaxCount, "more than 0xFFFFFFFE pairs",
+           "more pairs than `capacity` holds; *n_pairs is their number"};
     unsigned long long by_flag[kPrimeFlags] = {};
-    if (write || cover) {
-        if (write) {
-            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_prime_pair)));
-            p.pairs = (uint4 *)ctx->edit_pairs.p;
-        }
-        if (cover) {
-            p.cov_count = (uint32_t *)tabs;
-            p.cov_min = (uint32_t *)(tabs + cov_bytes);
-            p.flag_count = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes + off_bytes);
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_e * sizeof(uint32_t), ctx->stream));
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_e * sizeof(uint32_t), ctx->stream));
+    const int jrc = join_passes(
+        ctx, tabs, j,
+        [&](uint4 *d_pairs, bool write) {
+            p.pairs = d_pairs;
+            return launch_prime_pairs(p, write, ctx->stream);
+        },
+        [&](bool) { return coverage || stats; },
+        [&] {
+            const int crc = cov.clear(ctx, tabs);
+            if (crc != VSC_OK) return crc;
+            p.cov_count = cov.count;
+            p.cov_min = cov.min;
+            p.flag_count = (unsigned long long *)tabs.extra();
             VSC_HIP(ctx, hipMemsetAsync(p.flag_count, 0, flag_bytes, ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_prime_pairs(p, true, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        std::vector<uint32_t> cov;
-        unsigned long long d_covered = 0;
-        if (write) VSC_HIP(ctx, hipMemcpyAsync(pairs, p.pairs, (size_t)total * sizeof(vsc_prime_pair), hipMemcpyDeviceToHost, ctx->stream));
-        if (cover) VSC_HIP(ctx, hipMemcpyAsync(by_flag, p.flag_count, sizeof by_flag, hipMemcpyDeviceToHost, ctx->stream));
-        if (cover && !coverage) {  // the stats alone: the covered edits are counted where they lie, 8 bytes come back
-            unsigned long long *slot = a.stats + kPrimeCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
-            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_e, slot, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (cover) {
-            cov.resize(2 * n_e);
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_e * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_e, p.cov_min, n_e * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float wms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-        pass_ms += wms;
-        covered = d_covered;
-        for (size_t k = 0; coverage && k < n_e; ++k) {
-            covered += cov[k] != 0;
-            coverage[2 * k] = cov[k];
-            coverage[2 * k + 1] = cov[n_e + k];
-        }
-    }
+            return VSC_OK;
+        },
+        [&] {
+            VSC_HIP(ctx, hipMemcpyAsync(by_flag, p.flag_count, sizeof by_flag, hipMemcpyDeviceToHost, ctx->stream));
+            return cov.read(ctx, a.stats + kPrimeCounts + 1);
+        });
+    if (jrc != VSC_OK) return jrc;
+    const uint64_t covered = cov.take();
     if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
+        class_counts(stats, seen);
         stats->with_pair = seen[kEffClasses];
         stats->weak = seen[kEffClasses + 1];
-        stats->pairs = total;
+        stats->pairs = j.total;
         for (uint32_t b = 0; b < kPrimeFlags; ++b) stats->pairs_by_flag[b] = by_flag[b];
         stats->edits_covered = covered;
-        stats->score_ms = ms;
+        stats->score_ms = j.rows_ms;
         stats->wall_ms = wall_ms_since(t0);
     }
-    t.score_ms = ms;
-    t.scan_ms = pass_ms;
-    t.total_ms = t.score_ms + t.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
-    ctx->timing = t;
-    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE pairs");
-    if (pairs && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more pairs than `capacity` holds; *n_pairs is their number");
-    return VSC_OK;
+    return join_refusal(ctx, j, who);
 }
 
 // vsc_guides_prime / vsc_pattern_guides_prime: over the candidates where they lie, a host-only object from the host
@@ -6291,70 +6197,35 @@ int prime_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const v
                  vsc_prime_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     PrimeShape s{};
     PrimeHostEdits h;
-    const int rc = prime_check(ctx, genome, shape, edits, n_e, s, h, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kPrimeRule, who, at, &s.site_len,
+                                   [&] { return prime_check(ctx, genome, shape, edits, n_e, s, h, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (guides->n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const bool dev = guides->ctx != nullptr;
-    return prime_run(ctx, genome, s, h, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr, dev ? nullptr : guides->loci.data(),
-                     guides->n, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    return prime_run(ctx, genome, s, h, at, rows, pairs, capacity, n_pairs, coverage, stats, who);
     });
 }
 
-// vsc_guides_filter_prime / vsc_pattern_guides_filter_prime: run_enumeration's two passes over tiles of kEditTile candidates of
-// `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+// vsc_guides_filter_prime / vsc_pattern_guides_filter_prime: the candidates with a pair, weak ones only where allowed
 template <class Guides>
 int prime_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
                  bool need_23, uint32_t allow_weak, Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
     PrimeShape s{};
     PrimeHostEdits h;
-    const int rc = prime_check(ctx, genome, shape, edits, n_e, s, h, who);
+    const int rc = filter_front(ctx, in, out, need_23, kPrimeRule, who, &s.site_len,
+                                [&] { return prime_check(ctx, genome, shape, edits, n_e, s, h, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    const uint64_t n = in->n;
-    if (n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     PrimeFilterArgs a{};
     const int urc = prime_upload_edits(ctx, h, 0, a.edits, nullptr);
     if (urc != VSC_OK) return urc;
+    if (in->n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the edits are this call's vectors, and no pass will wait)
     a.g = eff_planes(genome);
     a.shape = s;
-    a.n = n;
     a.allow_weak = allow_weak ? 1u : 0u;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    if (n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the edits are this call's vectors)
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_prime_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_prime_filter(a, write, ctx->stream); });
     });
 }
 
@@ -6436,7 +6307,7 @@ int vsc_loci_prime(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
     if (n > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
-    return prime_run(ctx, genome, s, h, nullptr, loci, n, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    return prime_run(ctx, genome, s, h, CandidateLoci{nullptr, loci, n}, rows, pairs, capacity, n_pairs, coverage, stats, fn);
     });
 }
 
@@ -6535,34 +6406,31 @@ int effects_upload_cds(vsc_ctx *ctx, const vsc_cds *cds, CdsView &v)
     return VSC_OK;
 }
 
-// Rows, records and coverage of n loci - on ctx's device already (d_loci), or the host's (h_loci: uploaded first):
-// effects_rows_kernel, then the records' count pass over the rows, the scan, one 8-byte read-back (the effects) and the write pass.
+const CandidateRule kEffectsRule{"the shape's site_len must be 23", kEffectsMaxCount, "more than 0xFFFFFFFE candidates"};
+static_assert((kEffectsCounts + 2) * sizeof(unsigned long long) <= 256, "the counters and the covered transcripts lie in the head");
+
+// Rows, records and coverage of the loci `at`: effects_rows_kernel, then the join of the rows with the transcripts - always,
+// the records do not depend on a table of the call's - whose coverage is the stop_gained effects per transcript.
 int effects_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, uint32_t to, const vsc_cds *cds, const EffectsCode &code,
-                const void *d_loci, const vsc_locus *h_loci, uint64_t n, uint32_t *rows, vsc_effect *effects, uint64_t capacity,
-                uint64_t *n_effects, uint32_t *coverage, vsc_effects_stats *stats, const char *who)
+                const CandidateLoci &at, uint32_t *rows, vsc_effect *effects, uint64_t capacity, uint64_t *n_effects, uint32_t *coverage,
+                vsc_effects_stats *stats, const char *who)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_tx = cds->n_tx;
+    const uint64_t n = at.n;
     if (stats) *stats = vsc_effects_stats{};
     if (n_effects) *n_effects = 0;
-    if (coverage)
-        for (size_t k = 0; k < n_tx; ++k) {
-            coverage[2 * k] = 0;
-            coverage[2 * k + 1] = kEffectsUndefined;
-        }
-    vsc_timing t{};
+    PairCoverage cov(n_tx, coverage, kEffectsUndefined);
     if (n == 0) {
-        ctx->timing = t;
+        ctx->timing = vsc_timing{};
         if (stats) stats->wall_ms = wall_ms_since(t0);
         return VSC_OK;
     }
     VSC_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t tiles = (uint32_t)((n + kEditTile - 1) / kEditTile);
     // edit_tabs: [stop_gained effects per transcript][their smallest codon][effects per tile][offsets per tile]
-    const size_t cov_bytes = round256(n_tx * sizeof(uint32_t) + 4), count_bytes = round256((size_t)tiles * sizeof(uint32_t));
-    const size_t off_bytes = round256(((size_t)tiles + 1) * sizeof(unsigned long long));
-    VSC_HIP(ctx, ctx->edit_tabs.ensure(2 * cov_bytes + count_bytes + off_bytes));
-    char *tabs = (char *)ctx->edit_tabs.p;
+    JoinTabs tabs(n, 2 * PairCoverage::bytes(n_tx), 0);
+    VSC_HIP(ctx, ctx->edit_tabs.ensure(tabs.bytes()));
+    tabs.base = (char *)ctx->edit_tabs.p;
     EffectsArgs a{};
     const int urc = effects_upload_cds(ctx, cds, a.cds);
     if (urc != VSC_OK) return urc;
@@ -6571,25 +6439,14 @@ int effects_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, 
     a.to = to;
     a.code = code;
     a.n = n;
-    const size_t head = 256;  // the counters, in front of the rows
-    static_assert((kEffectsCounts + 2) * sizeof(unsigned long long) <= 256, "the counters and the covered transcripts lie in the head");
-    VSC_HIP(ctx, ctx->eff_out.ensure(head + (size_t)n * sizeof(uint2)));
-    a.stats = (unsigned long long *)ctx->eff_out.p;
-    a.out = (uint2 *)((char *)ctx->eff_out.p + head);
-    if (h_loci) {
-        VSC_HIP(ctx, ctx->eff_in.ensure((size_t)n * sizeof(vsc_locus)));
-        VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_in.p, h_loci, (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.loci = (const uint4 *)ctx->eff_in.p;
-    } else {
-        a.loci = (const uint4 *)d_loci;
-    }
-    VSC_HIP(ctx, hipMemsetAsync(a.stats, 0, head, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageStart], ctx->stream));
-    VSC_HIP(ctx, launch_effects_rows(a, ctx->n_cus, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStageEnd], ctx->stream));
     unsigned long long seen[kEffectsCounts] = {};
-    if (rows) VSC_HIP(ctx, hipMemcpyAsync(rows, a.out, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(seen, a.stats, sizeof seen, hipMemcpyDeviceToHost, ctx->stream));
+    const int rrc = rows_pass(ctx, at, sizeof(uint2), rows, seen, kEffectsCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint2 *)d_rows;
+        a.loci = d_loci;
+        return launch_effects_rows(a, ctx->n_cus, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
     EffectsRecordArgs p{};
     p.g = a.g;
     p.shape = shape;
@@ -6599,85 +6456,38 @@ int effects_run(vsc_ctx *ctx, const vsc_genome *genome, const EditShape &shape, 
     p.loci = a.loci;
     p.rows = a.out;
     p.n = n;
-    p.n_work = tiles;
+    p.n_work = tabs.tiles;
     p.n_tx = (uint32_t)n_tx;
-    p.tile_count = (uint32_t *)(tabs + 2 * cov_bytes);
-    unsigned long long *d_off = (unsigned long long *)(tabs + 2 * cov_bytes + count_bytes);
-    p.tile_off = d_off;
-    unsigned long long total = 0;
-    float pass_ms = 0;
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-    VSC_HIP(ctx, launch_effects_records(p, false, ctx->stream));
-    VSC_HIP(ctx, launch_enum_scan(p.tile_count, tiles, d_off, ctx->stream));
-    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-    VSC_HIP(ctx, hipMemcpyAsync(&total, d_off + tiles, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    VSC_HIP(ctx, hipEventElapsedTime(&ms, ctx->ev[kEvStageStart], ctx->ev[kEvStageEnd]));
-    VSC_HIP(ctx, hipEventElapsedTime(&pass_ms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-    if (n_effects) *n_effects = total;
-    const bool too_many = total > kEffectsMaxCount, write = effects && total && total <= capacity && !too_many;
-    const bool cover = total && n_tx && seen[kEffClasses + 1 + kEffectStopGained] && (coverage || stats);
-    uint64_t covered = 0;
-    if (write || cover) {
-        if (write) {
-            VSC_HIP(ctx, ctx->edit_pairs.ensure((size_t)total * sizeof(vsc_effect)));
-            p.effects = (uint4 *)ctx->edit_pairs.p;
-        }
-        if (cover) {
-            p.cov_count = (uint32_t *)tabs;
-            p.cov_min = (uint32_t *)(tabs + cov_bytes);
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_count, 0, n_tx * sizeof(uint32_t), ctx->stream));
-            VSC_HIP(ctx, hipMemsetAsync(p.cov_min, 0xFF, n_tx * sizeof(uint32_t), ctx->stream));
-        }
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2Start], ctx->stream));
-        VSC_HIP(ctx, launch_effects_records(p, true, ctx->stream));
-        VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvStage2End], ctx->stream));
-        std::vector<uint32_t> cov;
-        unsigned long long d_covered = 0;
-        if (write) VSC_HIP(ctx, hipMemcpyAsync(effects, p.effects, (size_t)total * sizeof(vsc_effect), hipMemcpyDeviceToHost, ctx->stream));
-        if (cover && !coverage) {  // the stats alone: the covered transcripts are counted where they lie, 8 bytes come back
-            unsigned long long *slot = a.stats + kEffectsCounts + 1;  // (inside the zeroed head, behind the rows kernel's counters)
-            VSC_HIP(ctx, launch_edit_covered(p.cov_count, (uint32_t)n_tx, slot, ctx->n_cus, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(&d_covered, slot, sizeof d_covered, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (cover) {
-            cov.resize(2 * n_tx);
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data(), p.cov_count, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VSC_HIP(ctx, hipMemcpyAsync(cov.data() + n_tx, p.cov_min, n_tx * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float wms = 0;
-        VSC_HIP(ctx, hipEventElapsedTime(&wms, ctx->ev[kEvStage2Start], ctx->ev[kEvStage2End]));
-        pass_ms += wms;
-        covered = d_covered;
-        for (size_t k = 0; cover && coverage && k < n_tx; ++k) {
-            covered += cov[k] != 0;
-            coverage[2 * k] = cov[k];
-            coverage[2 * k + 1] = cov[n_tx + k];
-        }
-    }
+    p.tile_count = tabs.tile_count();
+    p.tile_off = tabs.tile_off();
+    Join j{n, sizeof(uint2), true, effects, sizeof(vsc_effect), capacity, n_effects, kEffectsMaxCount, "more than 0xFFFFFFFE effects",
+           "more effects than `capacity` holds; *n_effects is their number"};
+    const int jrc = join_passes(
+        ctx, tabs, j,
+        [&](uint4 *d_effects, bool write) {
+            p.effects = d_effects;
+            return launch_effects_records(p, write, ctx->stream);
+        },
+        [&](bool) { return n_tx && seen[kEffClasses + 1 + kEffectStopGained] && (coverage || stats); },
+        [&] {
+            const int crc = cov.clear(ctx, tabs);
+            p.cov_count = cov.count;
+            p.cov_min = cov.min;
+            return crc;
+        },
+        [&] { return cov.read(ctx, a.stats + kEffectsCounts + 1); });
+    if (jrc != VSC_OK) return jrc;
+    const uint64_t covered = cov.take();
     if (stats) {
-        stats->defined = seen[kEffDefined];
-        stats->invalid = seen[kEffInvalid];
-        stats->off_contig = seen[kEffOffContig];
-        stats->not_resident = seen[kEffNotResident];
-        stats->has_n = seen[kEffHasN];
+        class_counts(stats, seen);
         stats->with_effect = seen[kEffClasses];
-        stats->effects = total;
+        stats->effects = j.total;
         for (uint32_t k = 0; k < kEffectClasses; ++k) stats->by_class[k] = seen[kEffClasses + 1 + k];
         stats->transcripts_stopped = covered;
-        stats->kernel_ms = ms;
+        stats->kernel_ms = j.rows_ms;
         stats->wall_ms = wall_ms_since(t0);
     }
-    t.score_ms = ms;
-    t.scan_ms = pass_ms;
-    t.total_ms = t.score_ms + t.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * (sizeof(vsc_locus) + sizeof(uint2));
-    ctx->timing = t;
-    if (too_many) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE effects");
-    if (effects && total > capacity) return fail_in(ctx, VSC_ERR_RANGE, who, "more effects than `capacity` holds; *n_effects is their number");
-    return VSC_OK;
+    return join_refusal(ctx, j, who);
 }
 
 // vsc_guides_effects / vsc_pattern_guides_effects: over the candidates where they lie, a host-only object from the host
@@ -6687,71 +6497,37 @@ int effects_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const
                    uint32_t *coverage, vsc_effects_stats *stats, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx) return VSC_ERR_INVALID;
     EditShape s{};
     EffectsCode ec{};
-    const int rc = effects_check(ctx, genome, shape, to, cds, code, s, ec, who);
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kEffectsRule, who, at, &s.site_len,
+                                   [&] { return effects_check(ctx, genome, shape, to, cds, code, s, ec, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
-    if (!guides) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (guides->ctx && guides->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if (guides->n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const bool dev = guides->ctx != nullptr;
-    return effects_run(ctx, genome, s, to, cds, ec, dev ? (const char *)guides->storage.p + guides->loci_at : nullptr,
-                       dev ? nullptr : guides->loci.data(), guides->n, rows, effects, capacity, n_effects, coverage, stats, who);
+    return effects_run(ctx, genome, s, to, cds, ec, at, rows, effects, capacity, n_effects, coverage, stats, who);
     });
 }
 
-// vsc_guides_filter_effects / vsc_pattern_guides_filter_effects: run_enumeration's two passes over tiles of kEditTile
-// candidates of `in` (a host-only object: uploaded first); its timing is then restated as the edit filter restates its own.
+// vsc_guides_filter_effects / vsc_pattern_guides_filter_effects: the candidates with every required class and no forbidden one
 template <class Guides>
 int effects_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_edit_shape *shape, uint32_t to, const vsc_cds *cds,
                    const char *code, bool need_23, uint32_t require, uint32_t forbid, Guides **out, const char *who)
 {
     return guarded(ctx, [&]() -> int {
-    if (!ctx || !out) return VSC_ERR_INVALID;
-    *out = nullptr;
     EditShape s{};
     EffectsFilterArgs a{};
-    const int rc = effects_check(ctx, genome, shape, to, cds, code, s, a.code, who);
+    const int rc = filter_front(
+        ctx, in, out, need_23, kEffectsRule, who, &s.site_len,
+        [&] { return effects_check(ctx, genome, shape, to, cds, code, s, a.code, who); },
+        [&] { return (require | forbid) >> kEffectClasses ? fail_in(ctx, VSC_ERR_INVALID, who, "require / forbid are masks over bits 0 .. 5") : VSC_OK; });
     if (rc != VSC_OK) return rc;
-    if (!in) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (in->ctx && in->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "the candidates belong to another context");
-    if (need_23 && s.site_len != (uint32_t)VSC_READ_LEN) return fail_in(ctx, VSC_ERR_INVALID, who, "the shape's site_len must be 23");
-    if ((require | forbid) >> kEffectClasses) return fail_in(ctx, VSC_ERR_INVALID, who, "require / forbid are masks over bits 0 .. 5");
-    const uint64_t n = in->n;
-    if (n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE candidates");
-    const uint64_t tiles = (n + kEditTile - 1) / kEditTile;
-    VSC_HIP(ctx, hipSetDevice(ctx->device));
     const int urc = effects_upload_cds(ctx, cds, a.cds);
     if (urc != VSC_OK) return urc;
     a.g = eff_planes(genome);
     a.shape = s;
     a.to = to;
-    a.n = n;
     a.require = require;
     a.forbid = forbid;
-    if (n && in->ctx) {
-        a.in_codes = (const unsigned long long *)in->storage.p;
-        a.in_loci = (const uint4 *)((const char *)in->storage.p + in->loci_at);
-    } else if (n) {
-        const size_t loci_at = round256((size_t)n * sizeof(uint64_t));
-        VSC_HIP(ctx, ctx->eff_in.ensure(loci_at + (size_t)n * sizeof(vsc_locus)));
-        char *base = (char *)ctx->eff_in.p;
-        VSC_HIP(ctx, hipMemcpyAsync(base, in->codes.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        VSC_HIP(ctx, hipMemcpyAsync(base + loci_at, in->loci.data(), (size_t)n * sizeof(vsc_locus), hipMemcpyHostToDevice, ctx->stream));
-        a.in_codes = (const unsigned long long *)base;
-        a.in_loci = (const uint4 *)(base + loci_at);
-    }
-    const int erc = run_enumeration(ctx, who, a, nullptr, (uint32_t)tiles, nullptr, 0, 0, out,
-                                    [&](const void *, unsigned long long, bool write) { return launch_effects_filter(a, write, ctx->stream); });
-    if (erc != VSC_OK) return erc;
-    vsc_timing t{};
-    t.score_ms = t.total_ms = ctx->timing.scan_ms;
-    t.sites = n;
-    t.genome_bytes = n * 2 * sizeof(vsc_locus) + (*out)->n * 2 * (sizeof(uint64_t) + sizeof(vsc_locus));
-    ctx->timing = t;
-    return VSC_OK;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_effects_filter(a, write, ctx->stream); });
     });
 }
 
@@ -6941,7 +6717,7 @@ int vsc_loci_effects(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *lo
     if (rc != VSC_OK) return rc;
     if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
     if (n > kEffectsMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
-    return effects_run(ctx, genome, s, to, cds, ec, nullptr, loci, n, rows, effects, capacity, n_effects, coverage, stats, fn);
+    return effects_run(ctx, genome, s, to, cds, ec, CandidateLoci{nullptr, loci, n}, rows, effects, capacity, n_effects, coverage, stats, fn);
     });
 }
 
