@@ -2644,6 +2644,157 @@ int vsc_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *
 int vsc_pattern_guides_filter_prime(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_prime_shape *shape,
                                     const vsc_prime_edit *edits, uint64_t n_e, uint32_t allow_weak, vsc_pattern_guides **out);
 
+/* ---- HDR knock-in design: reach, re-cut block, silent changes ------------------------------------- */
+/*
+ * A nuclease cut repaired from a donor template (homology-directed repair, often with a single-stranded oligo donor): "which
+ * candidates cut close enough to my edit, does the edit itself keep the nuclease from cutting the repaired allele again, and if
+ * not, which single silent substitution in the donor would?" - answered on the resident genome, where the candidates lie.
+ * Everything is integer.  Letters are A C G T = 0 .. 3.
+ *
+ * SHAPE    site_len 16 .. 32; up 0 .. 32, down 0 .. 32; C = up + site_len + down <= 64. The site is context positions
+ *          [s0, s0 + site_len), s0 = up; "site position q" is context position s0 + q.
+ *          cut 1 .. site_len - 1: the break lies between site positions cut - 1 and cut; K = s0 + cut (SpCas9 23-mer: cut 17).
+ *          max_dist 0 .. 63.   anchor 0 | 1: the side of the site the PAM fixes (1: its last base, SpCas9; 0: its first, Cas12a).
+ *          pam_start, pam_len 0 .. 8, inside the site; pam_accept[8]: for j < pam_len a non-empty set of letters, bit b = letter
+ *          b (NGG: 15, 4, 4); 0 for j >= pam_len.
+ *          seed_start, seed_len 0 .. 16 and proto_start, proto_len 0 .. 32: two ranges of site positions inside the site.
+ *          min_seed_mm 0 .. seed_len, min_proto_mm 0 .. proto_len (0: that rule is off).
+ *          flags bit 0 SUBSTITUTE, bit 1 SUB_SEED, bit 2 SUB_NONCODING; every other bit and every reserved field 0.
+ * CONTEXT  eff_context with {up, site_len, down}: '+': R = c[p - up, p + site_len + down); '-': R = revcomp(c[p - down, p + site_len + up)).
+ *          F0 = the context's first forward position. CLASS as EffClass, in its order.
+ * EDITS    vsc_prime_edit entries under 4.30's rules (strictly ascending (contig, pos), del_len and ins_len 0 .. 16, not both 0,
+ *          inside the contig, n_e <= 0xFFFFFFFE). Every pair treats its edit alone.
+ * READ     e0 and I as in 4.30 ('+': e0 = pos - F0, I = ins; '-': e0 = C - (pos - F0) - del_len, I = revcomp(ins)); e1 = e0 + del_len.
+ *          dist = 0 when e0 <= K <= e1, K - e1 when e1 < K, e0 - K when e0 > K. side = 0 | 1 | 2 in that order.
+ *          The edit is IN REACH of a defined candidate on its contig iff [pos, pos + del_len) lies inside [F0, F0 + C)
+ *          (del_len 0: F0 <= pos <= F0 + C) and dist <= max_dist.
+ *          E = R[0, e0) + I + R[e1, C); delta = ins_len - del_len; |E| = C + delta.
+ * SEEN     what the nuclease finds on the repaired allele, held at the PAM side:
+ *          shift = delta when (anchor = 1 and e0 < s0 + site_len) or (anchor = 0 and e1 <= s0), otherwise 0.
+ *          S[q] = E[s0 + q + shift] for q in [0, site_len). An index outside [0, |E|) gives NO LETTER, which differs from every
+ *          letter and is in no pam_accept set.
+ * BLOCKED  pam_broken = some j < pam_len with S[pam_start + j] not in pam_accept[j].
+ *          seed_mm / proto_mm = the q of that range with S[q] != R[s0 + q].
+ *          flag bit 0 B_PAM = pam_broken; bit 1 B_SEED = min_seed_mm != 0 and seed_mm >= min_seed_mm; bit 2 B_PROTO likewise.
+ *          The pair is BLOCKED when one of them is set. (pam_broken speaks about S, not about a change: the caller vouches that the
+ *          candidates' own PAM is in pam_accept.)
+ * SUBSTITUTE  only under SUBSTITUTE and when the pair is not BLOCKED: ONE substitution of one base that the donor carries beside
+ *          the edit. A site position q is a SLOT when x = s0 + q + shift lies in [0, |E|) and not in [e0, e0 + ins_len) (an
+ *          inserted letter is not a slot); its reference context position is r = x (x < e0) or x - delta; its forward position
+ *          f = F0 + r ('+') or F0 + C - 1 - r ('-'); the forward letter of a read letter b is b ('+') or 3 - b ('-').
+ *          ALLOWED(r, b): without a CDS always. With one: f lies in no segment -> SUB_NONCODING. f lies in a segment -> all of:
+ *            its codon is not UNKNOWN (4.29)
+ *            none of the codon's three forward positions g has pos <= g + 1 and g <= pos + del_len
+ *              (the codon does not touch the edit, one base of margin for an insertion point)
+ *            CODE[ref] == CODE[alt], alt = the reference codon with that one base replaced
+ *              (transcript orientation; complemented when the strands differ)
+ *          Frameshifting edits do not move the frame the substitution is judged in (see "Not offered").
+ *          ORDER of the tries, the first that holds is taken:
+ *            1. j = 0 .. pam_len - 1 ascending, q = pam_start + j a slot, b = 0 .. 3 ascending with b not in pam_accept[j] and
+ *               ALLOWED(r, b)                                                                       -> flag bit 3 SUB_PAM
+ *            2. under SUB_SEED, when min_seed_mm != 0 and seed_mm + 1 >= min_seed_mm: the seed's q from the PAM side outward
+ *               (anchor 1: descending, anchor 0: ascending), q a slot with S[q] == R[s0 + q], b ascending with b != R[s0 + q] and
+ *               ALLOWED(r, b)                                                                       -> flag bit 4 SUB_SEED
+ *          none: flag bit 5 OPEN (the repaired allele can be cut again). A pair is USABLE when it is not OPEN.
+ *          Without SUBSTITUTE a pair that is not BLOCKED is OPEN.
+ * PAIR     16 bytes { candidate, edit, info, block }; info = dist | side << 6 | seed_mm << 8 | proto_mm << 13 | flags << 24;
+ *          block = 0xFFFFFFFF without a substitution, else q | b << 8 | coding << 10 | r << 16 (coding: f lies in a segment).
+ *          Order: ascending (candidate, edit). n <= 0xFFFFFFFE.
+ * ROW      two uint32 per candidate: n_pairs, n_usable. Both 0xFFFFFFFF unless defined. Without edits both 0.
+ * COVERAGE optional, two uint32 per edit: its USABLE pairs and the smallest dist among them (0xFFFFFFFF: none).
+ * FILTER   keep iff defined and (no edits given, or n_usable >= 1, or allow_open and n_pairs >= 1). Survivors keep their order.
+ *
+ * The output is a function of the inputs alone: it does not depend on launch shape or wave order.  The coverage and the pairs by
+ * flag use integer add / min atomics, which commute; the pairs have no append cursor.  The occupancy bitmap over the edits'
+ * positions (4.30) is asked before any search; it changes no output bit.  The CDS is read only for a pair that is in reach and
+ * not BLOCKED.
+ *
+ * vsc_hdr_site_text: one context of C letters (any case) in read orientation and one edit in READ coordinates (e0, del_len, the
+ * inserted letters as the read strand has them, "" for none) on the host, by the functions the kernels call.  allowed (optional):
+ * C bytes, byte r = the set of read letters ALLOWED at reference context position r (bit b = letter b); NULL: every letter
+ * everywhere.  pair[0] = info, pair[1] = block (coding is 0: there is no CDS); both 0xFFFFFFFF when the edit is not in reach.
+ * edited (optional, at least 81 bytes): E with the substitution applied, as letters.  A letter other than ACGT, a text of another
+ * length, a shape outside SHAPE, an edit outside [0, C] or longer than 16, a set above 15: VSC_ERR_INVALID.
+ *
+ * vsc_loci_hdr: vsc_loci_prime's arguments, with an optional CDS (NULL: ALLOWED always holds) and CODE (NULL: the standard code)
+ * as vsc_loci_effects takes them.  rows (optional): rows[2 i], rows[2 i + 1] = n_pairs, n_usable of loci[i].  The pairs follow
+ * vsc_loci_edit's contract: *n_pairs (optional) is always the full count; pairs == NULL only counts; a count above `capacity` is
+ * VSC_ERR_RANGE, and then nothing is written to `pairs`, while rows, coverage, stats and *n_pairs are valid.  stats (optional):
+ * the candidates by class, those with a pair and with a usable pair, the pairs, the pairs by flag (B_PAM, B_SEED, B_PROTO, SUB_PAM,
+ * SUB_SEED, OPEN), the edits with a usable pair, the rows kernel's time and the call's wall time in milliseconds.  n == 0: VSC_OK,
+ * nothing is launched.  vsc_guides_hdr works over the candidates where they lie on the device and requires site_len == 23; a
+ * host-only object goes the vsc_loci_hdr way.  vsc_pattern_guides_hdr is the same for vsc_pattern_guides: site_len is the
+ * pattern's length, which the CALLER vouches for.
+ *
+ * vsc_guides_filter_hdr / vsc_pattern_guides_filter_hdr: *out = the candidates of `in` that pass FILTER - codes and loci copied
+ * unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of 1 024 candidates.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a shape outside SHAPE or
+ * with a non-zero reserved field; NULL arguments; a genome or object of another context; a CDS built for another contig table; a
+ * code of fewer than 64 letters; site_len != 23 for vsc_guides; the refusals of EDITS as in 4.30.  VSC_ERR_RANGE: n or n_e above
+ * 0xFFFFFFFE.  Uploads and results use context scratch; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: several substitutions per pair; frame-aware judgement of a substitution behind a frameshifting edit; homology
+ * arms or the donor's strand on the device (va.hdr_donor cuts the arms on the host); a vsc_multi_* entry; trained HDR-efficiency
+ * models.
+ */
+#define VSC_HDR_UNDEFINED 0xFFFFFFFFu
+#define VSC_HDR_NO_BLOCK 0xFFFFFFFFu
+#define VSC_HDR_SUBSTITUTE 1u
+#define VSC_HDR_SUB_SEED 2u
+#define VSC_HDR_SUB_NONCODING 4u
+#define VSC_HDR_FLAG_B_PAM 1u
+#define VSC_HDR_FLAG_B_SEED 2u
+#define VSC_HDR_FLAG_B_PROTO 4u
+#define VSC_HDR_FLAG_SUB_PAM 8u
+#define VSC_HDR_FLAG_SUB_SEED 16u
+#define VSC_HDR_FLAG_OPEN 32u
+typedef struct {
+    uint32_t up, site_len, down, cut, max_dist, anchor;
+    uint32_t pam_start, pam_len, pam_accept[8];
+    uint32_t seed_start, seed_len, proto_start, proto_len, min_seed_mm, min_proto_mm;
+    uint32_t flags; /* VSC_HDR_SUBSTITUTE | VSC_HDR_SUB_SEED | VSC_HDR_SUB_NONCODING */
+    uint32_t reserved; /* 0 */
+} vsc_hdr_shape;
+typedef struct {
+    uint32_t candidate, edit;
+    uint32_t info;  /* dist | side << 6 | seed_mm << 8 | proto_mm << 13 | flags << 24 */
+    uint32_t block; /* VSC_HDR_NO_BLOCK, or q | b << 8 | coding << 10 | r << 16 */
+} vsc_hdr_pair;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t with_pair, with_usable, pairs;
+    uint64_t pairs_by_flag[6]; /* B_PAM, B_SEED, B_PROTO, SUB_PAM, SUB_SEED, OPEN */
+    uint64_t edits_covered;
+    double score_ms, wall_ms;
+    uint64_t reserved; /* 0 */
+} vsc_hdr_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_hdr_shape) == 96 && sizeof(vsc_hdr_pair) == 16 && sizeof(vsc_hdr_stats) == 144, "vsc_hdr_* layout");
+#else
+_Static_assert(sizeof(vsc_hdr_shape) == 96 && sizeof(vsc_hdr_pair) == 16 && sizeof(vsc_hdr_stats) == 144, "vsc_hdr_* layout");
+#endif
+int vsc_hdr_site_text(const char *context /* C letters, read orientation, any case */, const vsc_hdr_shape *shape, uint32_t e0,
+                      uint32_t del_len, const char *ins /* read orientation, "" for none */,
+                      const uint8_t *allowed /* C bytes of letter sets, or NULL */, uint32_t *pair /* 2: info, block */,
+                      char *edited /* >= 81 bytes, optional */);
+int vsc_loci_hdr(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                 const vsc_hdr_shape *shape, const vsc_prime_edit *edits /* host */, uint64_t n_e, const vsc_cds *cds /* optional */,
+                 const char *code /* 64 letters, or NULL */, uint32_t *rows /* host, 2 n, optional */,
+                 vsc_hdr_pair *pairs /* host, optional */, uint64_t capacity, uint64_t *n_pairs /* optional */,
+                 uint32_t *coverage /* host, 2 n_e, optional */, vsc_hdr_stats *stats /* optional */);
+int vsc_guides_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_hdr_shape *shape, const vsc_prime_edit *edits,
+                   uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t *rows, vsc_hdr_pair *pairs, uint64_t capacity,
+                   uint64_t *n_pairs, uint32_t *coverage, vsc_hdr_stats *stats);
+int vsc_pattern_guides_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_hdr_shape *shape,
+                           const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t *rows,
+                           vsc_hdr_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_hdr_stats *stats);
+int vsc_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_hdr_shape *shape, const vsc_prime_edit *edits,
+                          uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t allow_open, vsc_guides **out);
+int vsc_pattern_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_hdr_shape *shape,
+                                  const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t allow_open,
+                                  vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -88,6 +88,11 @@ int vsc_debug_prime_bitmap(vsc_ctx *ctx, int on);
 /* The workgroups (of 4 waves) per CU that prime_rows_kernel's grid is capped at on this context: 0 = the default, 1 .. 64.
  * The kernel is grid-stride: no output bit depends on it (tools/prime_bench.py times several against each other). */
 int vsc_debug_prime_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
+/* The same two hooks for vsc_*_hdr and vsc_*_filter_hdr: the occupancy bitmap in front of the edit search (1, the
+ * default: on), and the workgroups per CU that hdr_rows_kernel's grid is capped at (0 = the default, 1 .. 64).  No output bit
+ * depends on either. */
+int vsc_debug_hdr_bitmap(vsc_ctx *ctx, int on);
+int vsc_debug_hdr_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
 
 /* The block of the variation lookup's table on this context: log2 of the global positions per entry, 4 .. 32, or 0 =
  * the default (8).  At 32 the table has one block and the lookup is the plain lower bound over all variants.  No output bit

@@ -460,6 +460,39 @@ class PrimeStats(C.Structure):
 assert C.sizeof(PrimeShapeStruct) == 160 and C.sizeof(PrimeStats) == 128 and PRIME_PAIR_DTYPE.itemsize == 16 and PRIME_EDIT_DTYPE.itemsize == 16
 
 
+HDR_UNDEFINED = 0xFFFFFFFF  # VSC_HDR_UNDEFINED
+HDR_NO_BLOCK = 0xFFFFFFFF  # VSC_HDR_NO_BLOCK
+HDR_PAIR_DTYPE = np.dtype([("candidate", "<u4"), ("edit", "<u4"), ("info", "<u4"), ("block", "<u4")])
+
+
+class HdrShapeStruct(C.Structure):
+    """vsc_hdr_shape: the site with its context on both sides, the break, the reach, the side the PAM fixes, the PAM with the
+    letters it accepts, the seed and protospacer ranges with their mismatch thresholds, and the flags."""
+    _fields_ = [("up", C.c_uint32), ("site_len", C.c_uint32), ("down", C.c_uint32), ("cut", C.c_uint32), ("max_dist", C.c_uint32),
+                ("anchor", C.c_uint32), ("pam_start", C.c_uint32), ("pam_len", C.c_uint32), ("pam_accept", C.c_uint32 * 8),
+                ("seed_start", C.c_uint32), ("seed_len", C.c_uint32), ("proto_start", C.c_uint32), ("proto_len", C.c_uint32),
+                ("min_seed_mm", C.c_uint32), ("min_proto_mm", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class HdrStats(C.Structure):
+    """vsc_hdr_stats: the candidates of a call by class (the five counts add up to n), the candidates with a pair and with a
+    usable pair, the pairs, the pairs by flag (B_PAM, B_SEED, B_PROTO, SUB_PAM, SUB_SEED, OPEN), the edits with a usable pair, the
+    rows kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("with_pair", C.c_uint64), ("with_usable", C.c_uint64), ("pairs", C.c_uint64),
+                ("pairs_by_flag", C.c_uint64 * 6), ("edits_covered", C.c_uint64), ("score_ms", C.c_double), ("wall_ms", C.c_double),
+                ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "invalid", "off_contig", "not_resident", "has_n", "with_pair", "with_usable",
+                                                "pairs", "edits_covered")}
+        d.update(pairs_by_flag=[int(v) for v in self.pairs_by_flag], score_ms=float(self.score_ms), wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(HdrShapeStruct) == 96 and C.sizeof(HdrStats) == 144 and HDR_PAIR_DTYPE.itemsize == 16
+
+
 EFFECTS_UNDEFINED = 0xFFFFFFFF  # VSC_EFFECTS_UNDEFINED
 EFFECT_CLASS_NAMES = ("synonymous", "missense", "stop_gained", "stop_lost", "start_lost", "unknown")  # VSC_EFFECT_*
 CDS_SEGMENT_DTYPE = np.dtype([("contig", "<u4"), ("start", "<u4"), ("end", "<u4"), ("transcript", "<u4"), ("strand", "<u4"),
@@ -765,6 +798,17 @@ SYMBOLS = [
                                            C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
     ("vsc_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_prime", C.c_int, [_vp, _vp, _vp, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_hdr_site_text", C.c_int, [C.c_char_p, C.POINTER(HdrShapeStruct), C.c_uint32, C.c_uint32, C.c_char_p, _vp, _vp, _vp]),
+    ("vsc_loci_hdr", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, _vp, _vp, C.c_uint64,
+                               C.POINTER(C.c_uint64), _vp, C.POINTER(HdrStats)]),
+    ("vsc_guides_hdr", C.c_int, [_vp, _vp, _vp, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, _vp, _vp, C.c_uint64,
+                                 C.POINTER(C.c_uint64), _vp, C.POINTER(HdrStats)]),
+    ("vsc_pattern_guides_hdr", C.c_int, [_vp, _vp, _vp, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, _vp, _vp, C.c_uint64,
+                                         C.POINTER(C.c_uint64), _vp, C.POINTER(HdrStats)]),
+    ("vsc_guides_filter_hdr", C.c_int, [_vp, _vp, _vp, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, C.c_uint32,
+                                        C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_hdr", C.c_int, [_vp, _vp, _vp, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, C.c_uint32,
+                                                C.POINTER(_vp)]),
     ("vsc_variation_host", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp,
                                      C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     ("vsc_loci_variation", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
@@ -795,6 +839,8 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_sites_from_host", C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_prime_bitmap", C.c_int, [_vp, C.c_int]),
     ("vsc_debug_prime_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_hdr_bitmap", C.c_int, [_vp, C.c_int]),
+    ("vsc_debug_hdr_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
 ]
 

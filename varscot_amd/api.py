@@ -1942,6 +1942,195 @@ def prime_pick_inputs(pairs, loci, extra_columns=()):
     return lo[cand], pr["edit"].astype(np.uint32), pick_key(cols, bits)
 
 
+# ---- HDR knock-in design ----------------------------------------------------------------------------------------
+HDR_UNDEFINED = _lib.HDR_UNDEFINED  # both words of the row of a candidate whose context is undefined; "not in reach" of hdr_site_text
+HDR_NO_BLOCK = _lib.HDR_NO_BLOCK    # the block word of a pair without a substitution
+HDR_PAIR_DTYPE = _lib.HDR_PAIR_DTYPE
+HDR_FLAGS = ("B_PAM", "B_SEED", "B_PROTO", "SUB_PAM", "SUB_SEED", "OPEN")  # bit k of a pair's flags
+_IUPAC_SETS = {"A": 1, "C": 2, "G": 4, "T": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7, "N": 15}
+
+
+class HdrShape:
+    """vsc_hdr_shape: how a cutting nuclease sits on a candidate, for knock-ins by homology-directed repair.  site_len 16..32 is
+    the candidates' length, up / down (0..32 each) the bases of context in front of and behind the site in read orientation (C =
+    up + site_len + down <= 64).  cut: the break lies in front of site position cut (17 for the SpCas9 23-mer); max_dist
+    0..63: an edit further from the break is not in reach.  anchor: the side of the site the PAM fixes (1: its last base, 0: its
+    first).  pam = (start, accept): accept one letter set per PAM position - an IUPAC string ("NGG") or numbers 1..15 (bit b =
+    letter b of ACGT), at most 8.  seed / proto = (start, length) in site positions (at most 16 / 32 long); min_seed_mm /
+    min_proto_mm: that many changed letters there keep the nuclease from cutting the repaired allele again (0: the rule is
+    off).  substitute: look for one blocking substitution where the edit does not block; sub_seed: also in the seed;
+    sub_noncoding: with a CDS, also outside its segments.  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, up=20, down=21, cut=17, max_dist=30, anchor=1, pam=(20, "NGG"), seed=(10, 10), proto=(0, 20),
+                 min_seed_mm=2, min_proto_mm=4, substitute=True, sub_seed=True, sub_noncoding=True, flags=None, validate=True):
+        self.site_len, self.up, self.down, self.cut = int(site_len), int(up), int(down), int(cut)
+        self.max_dist, self.anchor = int(max_dist), int(anchor)
+        self.pam_start = int(pam[0])
+        acc = pam[1]
+        if isinstance(acc, (str, bytes)):
+            t = (acc.decode() if isinstance(acc, bytes) else acc).upper()
+            if any(c not in _IUPAC_SETS for c in t):
+                raise ValueError("a PAM is spelled in IUPAC letters")
+            acc = [_IUPAC_SETS[c] for c in t]
+        self.pam_accept = tuple(int(v) for v in acc)
+        self.pam_len = len(self.pam_accept)
+        self.seed_start, self.seed_len = int(seed[0]), int(seed[1])
+        self.proto_start, self.proto_len = int(proto[0]), int(proto[1])
+        self.min_seed_mm, self.min_proto_mm = int(min_seed_mm), int(min_proto_mm)
+        self.flags = (int(bool(substitute)) | int(bool(sub_seed)) << 1 | int(bool(sub_noncoding)) << 2) if flags is None else int(flags)
+        if validate and not self.valid():
+            raise ValueError("an HDR shape has site_len 16..32, up and down 0..32, up + site_len + down <= 64, 1 <= cut <= site_len - 1, "
+                             "max_dist 0..63, anchor 0 or 1, a PAM of at most 8 non-empty letter sets, a seed of at most 16 and a "
+                             "protospacer of at most 32 positions, all inside the site, and thresholds of at most the ranges' lengths")
+
+    def valid(self):
+        def inside(start, length, most):
+            return 0 <= length <= most and 0 <= start and start + length <= self.site_len
+        return (16 <= self.site_len <= 32 and 0 <= self.up <= 32 and 0 <= self.down <= 32 and self.context_len <= 64
+                and 1 <= self.cut <= self.site_len - 1 and 0 <= self.max_dist <= 63 and self.anchor in (0, 1)
+                and inside(self.pam_start, self.pam_len, 8) and all(1 <= v <= 15 for v in self.pam_accept)
+                and inside(self.seed_start, self.seed_len, 16) and inside(self.proto_start, self.proto_len, 32)
+                and 0 <= self.min_seed_mm <= self.seed_len and 0 <= self.min_proto_mm <= self.proto_len and 0 <= self.flags <= 7)
+
+    @property
+    def context_len(self):
+        return self.up + self.site_len + self.down
+
+    def _struct(self, reserved=0):
+        acc = (list(self.pam_accept) + [0] * 8)[:8]
+        return _lib.HdrShapeStruct(self.up & 0xFFFFFFFF, self.site_len & 0xFFFFFFFF, self.down & 0xFFFFFFFF, self.cut & 0xFFFFFFFF,
+                                   self.max_dist & 0xFFFFFFFF, self.anchor & 0xFFFFFFFF, self.pam_start & 0xFFFFFFFF,
+                                   self.pam_len & 0xFFFFFFFF, (C.c_uint32 * 8)(*[v & 0xFFFFFFFF for v in acc]),
+                                   self.seed_start & 0xFFFFFFFF, self.seed_len & 0xFFFFFFFF, self.proto_start & 0xFFFFFFFF,
+                                   self.proto_len & 0xFFFFFFFF, self.min_seed_mm & 0xFFFFFFFF, self.min_proto_mm & 0xFFFFFFFF,
+                                   self.flags & 0xFFFFFFFF, int(reserved))
+
+    def __repr__(self):
+        return "HdrShape(site_len=%d, up=%d, down=%d, cut=%d, max_dist=%d, anchor=%d, pam=(%d, %r), seed=(%d, %d), proto=(%d, %d), " \
+               "min_seed_mm=%d, min_proto_mm=%d, flags=%d)" % (self.site_len, self.up, self.down, self.cut, self.max_dist, self.anchor,
+                                                               self.pam_start, self.pam_accept, self.seed_start, self.seed_len,
+                                                               self.proto_start, self.proto_len, self.min_seed_mm, self.min_proto_mm,
+                                                               self.flags)
+
+
+# Two presets.  SpCas9 on its 23-mer (20 protospacer bases, then NGG; the blunt break lies three bases in front of the PAM): the
+# PAM-proximal 10 bases as the seed.  Cas12a on a 27-mer (TTTV, then 23 protospacer bases; the break is taken at the cut of the
+# non-target strand, 18 bases behind the PAM): the 6 PAM-proximal bases as the seed.  Two seed or four protospacer mismatches
+# count as a block, an edit up to 30 bases from the break as in reach.  Commonly used settings and nothing more.
+HDR_NUCLEASES = {
+    "SpCas9": HdrShape(READ_LEN, 20, 21, 17, 30, 1, (20, "NGG"), (10, 10), (0, 20), 2, 4),
+    "Cas12a": HdrShape(27, 18, 19, 22, 30, 0, (0, "TTTV"), (4, 6), (4, 23), 2, 4),
+}
+
+
+def _hdr_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in HDR_NUCLEASES:
+            raise ValueError("%s names one of %s, or is an HdrShape" % (what, ", ".join(sorted(HDR_NUCLEASES))))
+        shape = HDR_NUCLEASES[shape]
+    if not isinstance(shape, HdrShape):
+        raise ValueError("%s must be an HdrShape or the name of a preset" % what)
+    return shape
+
+
+def unpack_hdr_info(info):
+    """(dist, side, seed_mm, proto_mm, flags) of an HDR pair's info word (or an array of them): the bases between the break and
+    the edit, the side the edit lies on (0: it spans the break, 1: in front of it, 2: behind it, in read orientation), the changed
+    letters the nuclease finds in the seed and in the protospacer, and the flags (bit k: HDR_FLAGS[k])."""
+    i = np.asarray(info, dtype=np.uint32)
+    return (i & np.uint32(0x3F), (i >> np.uint32(6)) & np.uint32(3), (i >> np.uint32(8)) & np.uint32(0x1F),
+            (i >> np.uint32(13)) & np.uint32(0x3F), i >> np.uint32(24))
+
+
+def unpack_hdr_block(block):
+    """(q, letter, coding, r, has) of an HDR pair's block word (or an array of them): the site position of the blocking
+    substitution, the read letter 0..3 it writes, whether the base lies in a CDS segment, its reference context position - and
+    has = False (the other four 0) where the pair carries no substitution."""
+    b = np.asarray(block, dtype=np.uint32)
+    has = b != np.uint32(HDR_NO_BLOCK)
+    z = np.where(has, b, np.uint32(0))
+    return z & np.uint32(0xFF), (z >> np.uint32(8)) & np.uint32(3), (z >> np.uint32(10)) & np.uint32(1), (z >> np.uint32(16)) & np.uint32(0xFF), has
+
+
+def hdr_site_text(context, shape, e0, del_len=0, ins="", allowed=None):
+    """vsc_hdr_site_text: one context of shape.context_len letters (any case) in read orientation and one edit in READ
+    coordinates - read bases [e0, e0 + del_len) are replaced by the letters `ins` (as the read strand has them) - on the host, by
+    the functions the kernels call.  allowed: None, or one letter set 0..15 per context position (ALLOWED of a substitution
+    there).  Returns (in_reach, info, block, edited): in_reach False (info = block = HDR_UNDEFINED, edited = "") for an edit too
+    far from the break; edited is E with the substitution applied.  A letter other than ACGT or a text of another length
+    raises VarscotError."""
+    b = context if isinstance(context, bytes) else context.encode()
+    sh = _hdr_shape(shape)._struct()
+    it = ins if isinstance(ins, bytes) else ins.encode()
+    al = None
+    if allowed is not None:
+        al = np.ascontiguousarray(allowed, dtype=np.uint8)
+        if len(al) != len(b):
+            raise ValueError("one letter set per context position")
+    pair = (C.c_uint32 * 2)()
+    text = C.create_string_buffer(96)
+    check(lib().vsc_hdr_site_text(b, C.byref(sh), int(e0), int(del_len), it, ptr(al), pair, text))
+    reach = not (int(pair[0]) == HDR_UNDEFINED and int(pair[1]) == HDR_UNDEFINED)
+    return reach, int(pair[0]), int(pair[1]), text.value.decode()
+
+
+def hdr_pick_inputs(pairs, loci, extra_columns=()):
+    """What Genome.pick takes for "of every edit the K best cutting guides": (loci[pairs.candidate], pairs.edit, key) - one pick
+    candidate per HDR pair, its target the pair's edit, its key made with pick_key.  The first columns are: not OPEN (1 bit);
+    BLOCKED by the edit itself (1 bit: the donor needs no further change); the substitution breaks the PAM (1 bit, before one in
+    the seed); 63 - dist (6 bits: the nearer break).  extra_columns: (values per CANDIDATE of the HDR call, bits) in priority
+    order behind them - unsigned integer arrays, larger is better (pick_column makes them)."""
+    pr = np.asarray(pairs, dtype=_lib.HDR_PAIR_DTYPE)
+    lo = _loci(loci, len(loci))
+    cand = pr["candidate"].astype(np.int64)
+    dist, _, _, _, flags = unpack_hdr_info(pr["info"])
+    cols = [((flags & np.uint32(32)) == 0).astype(np.uint64), ((flags & np.uint32(7)) != 0).astype(np.uint64),
+            ((flags & np.uint32(8)) != 0).astype(np.uint64), np.uint64(63) - dist.astype(np.uint64)]
+    bits = [1, 1, 1, 6]
+    for values, b in extra_columns:
+        v = np.asarray(values)
+        if v.dtype.kind != "u" or v.ndim != 1 or len(v) != len(lo):
+            raise ValueError("an extra column is a one-dimensional unsigned integer array with one value per candidate")
+        cols.append(v[cand])
+        bits.append(int(b))
+    return lo[cand], pr["edit"].astype(np.uint32), pick_key(cols, bits)
+
+
+def hdr_donor(contig_text, locus, shape, edit, pair, arms=(40, 40)):
+    """The donor of one HDR pair as forward DNA letters, on the host: the contig's text with the edit = (contig, pos, del_len,
+    ins) and the pair's blocking substitution (if it has one) applied, cut to the span of the break, the edit and the
+    substitution plus arms = (left, right) reference bases on either side - clipped at the contig's ends, and as long as the
+    caller likes (they are not bound to the 64-base context).  locus = (contig, pos, strand) of the candidate; pair: an
+    HDR_PAIR_DTYPE record or (info, block).  A pair whose substitution does not fit the locus and the edit raises ValueError."""
+    shape = _hdr_shape(shape)
+    pos, strand = int(locus[1]), int(locus[2])
+    C_ = shape.context_len
+    f0 = pos - (shape.down if strand else shape.up)
+    K = shape.up + shape.cut
+    brk = f0 + (C_ - K if strand else K)  # the break lies in front of this forward position
+    e_pos, del_len = int(edit[1]), int(edit[2])
+    n, code = _prime_ins(edit[3])
+    letters = "".join("ACGT"[(code >> (2 * k)) & 3] for k in range(n))
+    block = int(pair["block"]) if isinstance(pair, (np.void, np.ndarray)) else int(pair[1])
+    text = contig_text.upper()
+    if int(edit[0]) != int(locus[0]) or f0 < 0 or f0 + C_ > len(text) or e_pos + del_len > len(text):
+        raise ValueError("the locus and the edit do not lie together on this contig")
+    lo, hi = min(brk, e_pos), max(brk, e_pos + del_len)
+    sub = None
+    if block != HDR_NO_BLOCK:
+        _, b, _, r, _ = (int(v) for v in unpack_hdr_block(block))
+        f = f0 + (C_ - 1 - r if strand else r)
+        if r >= C_ or e_pos <= f < e_pos + del_len:
+            raise ValueError("the pair's substitution does not fit the locus and the edit")
+        sub = (f, "ACGT"[3 - b if strand else b])
+        lo, hi = min(lo, f), max(hi, f + 1)
+    left, right = max(0, lo - int(arms[0])), min(len(text), hi + int(arms[1]))
+    ref = list(text[left:right])
+    if sub is not None:
+        ref[sub[0] - left] = sub[1]
+    return "".join(ref[:e_pos - left]) + letters + "".join(ref[e_pos + del_len - left:])
+
+
 # ---- coding consequences of base edits (DESIGN 4.29) --------------------------------------------------------------------
 # CODE: 64 amino-acid letters indexed 16 b0 + 4 b1 + b2 (A C G T = 0 .. 3), '*' = stop - the standard genetic code
 GENETIC_CODE = "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"
@@ -2846,7 +3035,8 @@ class Genome:
                           min_out_of_frame=None, min_microhomology=None, edit=None, edit_targets=None, min_editable=None,
                           max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None,
                           prime_edits=None, prime_allow_weak=None, variation=None, variants=None, max_variant_cost=None,
-                          max_variants_by_zone=None, require_variant_zones=None):
+                          max_variants_by_zone=None, require_variant_zones=None, hdr=None, hdr_edits=None, hdr_cds=None,
+                          hdr_allow_open=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -2879,7 +3069,12 @@ class Genome:
         variants= (as Genome.variation takes them): the candidates' variation rows (uint32[n, 4], vsc_pattern_guides_variation)
         come last of all.  max_variant_cost= / max_variants_by_zone= four bounds (255: none) / require_variant_zones= zone
         numbers or names of VARIATION_ZONES (all need variation=): only the candidates that pass the variation filter
-        (vsc_pattern_guides_filter_variation), after the other filters."""
+        (vsc_pattern_guides_filter_variation), after the other filters.
+        hdr= an HdrShape whose site_len is the pattern's length (or the name of a preset of HDR_NUCLEASES): the candidates'
+        (n_pairs, n_usable) rows (uint32[n, 2], vsc_pattern_guides_hdr) come last of all.  hdr_edits= (contig, pos, del_len, ins)
+        rows / hdr_cds= a Cds / hdr_allow_open= (all need hdr=): with edits or hdr_allow_open only the candidates whose context
+        is defined and that - with edits - have a usable pair, or with hdr_allow_open=True any pair
+        (vsc_pattern_guides_filter_hdr), after the other families' filters."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -2892,6 +3087,7 @@ class Genome:
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, len(p))
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, len(p))
+        hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -2904,7 +3100,8 @@ class Genome:
                                            (L.vsc_pattern_guides_edit, L.vsc_pattern_guides_filter_edit), fx,
                                            (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects), pe,
                                            (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime), vr,
-                                           (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation))
+                                           (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation), hd,
+                                           (L.vsc_pattern_guides_hdr, L.vsc_pattern_guides_filter_hdr))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -3055,9 +3252,9 @@ class Genome:
         return pairs
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
-                          fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None):
+                          fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None, hd=None, hd_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows.
+        the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows before the HDR rows.
         held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
@@ -3071,6 +3268,8 @@ class Genome:
             self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, rows=False)
         if va is not None:
             self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, rows=False)
+        if hd is not None:
+            self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -3084,6 +3283,8 @@ class Genome:
             extra += (self._prime_on_handle(held, pe, count_fn, pe_fns[0], pe_fns[1], free_fn, filt=False),)
         if va is not None:
             extra += (self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, filt=False),)
+        if hd is not None:
+            extra += (self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, filt=False),)
         return extra
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
@@ -3480,6 +3681,102 @@ class Genome:
             stats["edit_order"] = order
         return rows, pr, cov, stats
 
+    # ---- HDR knock-in design (vsc_*_hdr) ----------------------------------------------------------------------------------
+    @staticmethod
+    def _hdr_args(shape, edits, cds, allow_open, site_len, code=None):
+        """(shape, sorted edits or None, order, inverse, cds or None, code, allow_open or None) - or None without a shape."""
+        if shape is None:
+            if edits is not None or cds is not None or allow_open is not None:
+                raise ValueError("hdr_edits / hdr_cds / hdr_allow_open need hdr=shape")
+            return None
+        shape = _hdr_shape(shape, "hdr")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        if cds is not None and not isinstance(cds, Cds):
+            raise ValueError("hdr_cds must be a Cds")
+        ed = order = inverse = None
+        if edits is not None:
+            ed, order, inverse = prime_edits(edits)
+        return shape, ed, order, inverse, cds, _effect_code(code), None if allow_open is None else bool(allow_open)
+
+    def _hdr_on_handle(self, held, hd, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _prime_on_handle, for the HDR rows: hd = what _hdr_args returned.  With edits or hdr_allow_open the handle is
+        first replaced by the filter's result (filt); the rows of the survivors come back as uint32[n, 2]."""
+        shape, ed, _, _, cds, code, allow_open = hd
+        sh = shape._struct()
+        n_e = 0 if ed is None else len(ed)
+        ep = ptr(ed) if n_e else None
+        ch = cds._h if cds is not None else None
+        if filt and (ed is not None or allow_open is not None):
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), ep, n_e, ch, code, 1 if allow_open else 0, C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        r = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.HdrStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), ep, n_e, ch, code, ptr(r), None, 0, None, None, C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return r
+
+    def hdr(self, loci_or_found, shape, edits=None, cds=None, code=None, pairs=True, coverage=False, allow_partial=False):
+        """vsc_loci_hdr: knock-in design by homology-directed repair for candidates under an HdrShape (or the name of a preset of
+        HDR_NUCLEASES) and a list of wanted edits, on the device from the resident planes.  Returns (rows, pairs,
+        coverage, stats).  rows uint32[n, 2]: (n_pairs, n_usable) per candidate - the edits in reach of its break, and those
+        among them whose repaired allele the nuclease does not cut again; (HDR_UNDEFINED, HDR_UNDEFINED) where the context is
+        undefined.  edits: as Genome.prime takes them; None: no edits, both 0.  cds: a Cds - a blocking substitution inside
+        its segments is synonymous (under `code`, 64 letters, or GENETIC_CODE); None: any substitution is allowed.  pairs
+        (HDR_PAIR_DTYPE; None with pairs=False or without edits): candidate, edit (the index in the CALLER's array), info
+        (unpack_hdr_info: dist, side, seed_mm, proto_mm, flags), block (unpack_hdr_block: q, letter, coding, r) - in ascending
+        (candidate, edit).  coverage (uint32[len(edits), 2] in the caller's order with coverage=True, else None): usable pairs
+        of the edit, smallest dist among them (HDR_UNDEFINED: none).  stats: the candidates by class, with_pair, with_usable,
+        pairs, pairs_by_flag, edits_covered, score_ms, wall_ms and edit_order.  loci_or_found: as Genome.efficiency takes it.
+        Raises when a context is not resident on this object (a shard) unless allow_partial=True."""
+        shape = _hdr_shape(shape)
+        if cds is not None and not isinstance(cds, Cds):
+            raise ValueError("cds must be a Cds")
+        cd = _effect_code(code)
+        ch = cds._h if cds is not None else None
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        ed = order = inverse = None
+        if edits is not None:
+            ed, order, inverse = prime_edits(edits)
+        n_e = 0 if ed is None else len(ed)
+        ep = ptr(ed) if n_e else None
+        rows = np.empty((n, 2), dtype=np.uint32)
+        cov = np.empty((n_e, 2), dtype=np.uint32) if coverage and ed is not None else None
+        want_pairs = bool(pairs) and ed is not None
+        cap = min(max(n, 1024), 1 << 22) if want_pairs else 0
+        pr = np.empty(cap, dtype=_lib.HDR_PAIR_DTYPE) if want_pairs else None
+        st = _lib.HdrStats()
+        sh = shape._struct()
+        count = C.c_uint64()
+        L = lib()
+        rc = L.vsc_loci_hdr(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), ep, n_e, ch, cd, ptr(rows), ptr(pr), cap, C.byref(count), ptr(cov),
+                            C.byref(st))
+        if rc == _lib.VSC_ERR_RANGE and want_pairs and cap < int(count.value) <= 0xFFFFFFFE:
+            # (the rows, the coverage and the stats of the first call stand; the second brings the pairs alone)
+            cap = int(count.value)
+            pr = np.empty(cap, dtype=_lib.HDR_PAIR_DTYPE)
+            check(L.vsc_loci_hdr(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), ep, n_e, ch, cd, None, ptr(pr), cap, C.byref(count), None, None),
+                  self.ctx._h)
+        else:
+            check(rc, self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        if want_pairs:
+            pr = pr[:int(count.value)].copy()
+            pr["edit"] = order[pr["edit"].astype(np.int64)].astype(np.uint32)
+            pr = pr[np.lexsort((pr["edit"], pr["candidate"]))]
+        if cov is not None:
+            cov = cov[inverse]
+        if order is not None:
+            stats["edit_order"] = order
+        return rows, pr, cov, stats
+
     def pick(self, loci_or_found, key, shape, regions=None, groups=None, target=None, n_targets=None, rank=False):
         """The best shape.k candidates of every target under `key` (uint64 per candidate, larger is better), no two of one
         target closer than shape.spacing bases at their cut sites - picked on the device.  loci_or_found: as
@@ -3707,7 +4004,8 @@ class Genome:
                          labels=False, efficiency=None, min_efficiency=None, microhomology=None, min_out_of_frame=None,
                          min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None, cds=None,
                          edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
-                         variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None):
+                         variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
+                         hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -3740,7 +4038,12 @@ class Genome:
         Genome.variation takes them): the candidates' variation rows (uint32[n, 4], vsc_guides_variation) come last of all.
         max_variant_cost= / max_variants_by_zone= four bounds (255: none) / require_variant_zones= zone numbers or names of
         VARIATION_ZONES (all need variation=): only the candidates that pass the variation filter
-        (vsc_guides_filter_variation), after the other filters."""
+        (vsc_guides_filter_variation), after the other filters.
+        hdr= an HdrShape with site_len 23 or the name of a preset of HDR_NUCLEASES: the candidates' (n_pairs, n_usable) rows
+        (uint32[n, 2], vsc_guides_hdr) come last of all.  hdr_edits= (contig, pos, del_len, ins) rows in any order / hdr_cds= a
+        Cds / hdr_allow_open= (all need hdr=): with edits or hdr_allow_open only the candidates whose context is defined and
+        that - with edits - have a usable pair, or with hdr_allow_open=True any pair (vsc_guides_filter_hdr), after the other
+        families' filters."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
@@ -3749,11 +4052,12 @@ class Genome:
         fx = self._effects_args(ed, edit, cds, edit_to, require_effect, forbid_effect)
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, READ_LEN)
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, READ_LEN)
+        hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None and pe is None and vr is None:
+        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -3763,7 +4067,8 @@ class Genome:
                                            ed, (L.vsc_guides_edit, L.vsc_guides_filter_edit), fx,
                                            (L.vsc_guides_effects, L.vsc_guides_filter_effects), pe,
                                            (L.vsc_guides_prime, L.vsc_guides_filter_prime), vr,
-                                           (L.vsc_guides_variation, L.vsc_guides_filter_variation))
+                                           (L.vsc_guides_variation, L.vsc_guides_filter_variation), hd,
+                                           (L.vsc_guides_hdr, L.vsc_guides_filter_hdr))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -3798,7 +4103,7 @@ class Genome:
                pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
                cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
                variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
-               **search_options):
+               hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -3817,7 +4122,9 @@ class Genome:
         forbid_effect=: as enumerate_guides; the effect rows come after the edit rows.  prime= / prime_edits= /
         prime_allow_weak=: as enumerate_guides; the prime rows come after the effect rows, before (picks, counts).
         variation= / variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_guides; only
-        the survivors are searched, and the variation rows come after the prime rows, before (picks, counts)."""
+        the survivors are searched, and the variation rows come after the prime rows, before (picks, counts).
+        hdr= / hdr_edits= / hdr_cds= / hdr_allow_open=: as enumerate_guides; only the survivors are searched, and the HDR rows
+        come after the variation rows, before (picks, counts)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -3828,7 +4135,8 @@ class Genome:
                                       require_effect=require_effect, forbid_effect=forbid_effect, prime=prime,
                                       prime_edits=prime_edits, prime_allow_weak=prime_allow_weak, variation=variation,
                                       variants=variants, max_variant_cost=max_variant_cost,
-                                      max_variants_by_zone=max_variants_by_zone, require_variant_zones=require_variant_zones)
+                                      max_variants_by_zone=max_variants_by_zone, require_variant_zones=require_variant_zones,
+                                      hdr=hdr, hdr_edits=hdr_edits, hdr_cds=hdr_cds, hdr_allow_open=hdr_allow_open)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])

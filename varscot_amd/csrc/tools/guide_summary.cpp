@@ -126,6 +126,11 @@
 // sites at least SPACING bases apart (vsc_guides_pick; tools/pick_host.hpp makes the key from mit, table, eff, oof, mh
 // in the order of -b): the -L listing, written after the search whose rows rank the guides, gains the last columns pickTarget
 // pickRank (NA NA where a guide is not picked).  Without -k every output is byte for byte what it was.
+// --hdr SpCas9 | Cas12a | SPEC (needs -E, one device; tools/hdr_host.hpp) asks whether a cut at every found guide can be repaired
+// from a donor that carries a wanted edit: the candidates without a context are dropped BEFORE the off-target search,
+// with --hdr-edits edits.tsv those without a usable pair as well (--hdr-allow-open: without any pair); --hdr-cds cds.bed keeps the
+// blocking substitution synonymous; the -L listing gains the last columns hdrPairs hdrUsable; --hdr-out pairs.tsv (needs
+// --hdr-edits) lists the pairs with their substitutions.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -141,6 +146,7 @@
 #include "edit_host.hpp"
 #include "effects_host.hpp"
 #include "prime_host.hpp"
+#include "hdr_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
@@ -240,6 +246,14 @@ int main(int argc, char **argv)
                                        "in one of them (allele-specific design)", false},
         {'%', "variation-out", "With --variants: path to the TSV of the guides' rows (#guideId none distal seed pam silent cost maxWeight) and, "
                                "behind a blank line, of the pairs (#chrom pos span alt guideId first touched top silent weight)", false},
+        {'^', "hdr", "With -E: SpCas9 | Cas12a | UP,DOWN,CUT,MAXDIST,ANCHOR,PAMSTART,PAM,SEEDSTART,SEEDLEN,PROTOSTART,PROTOLEN,MINSEED,MINPROTO,FLAGS: "
+                     "the cutting nuclease's shape for knock-ins by homology-directed repair; only the candidates with a defined context are "
+                     "kept, and the guide listing gains the last columns hdrPairs hdrUsable (one device)", false},
+        {'&', "hdr-edits", "With --hdr: path to the wanted edits (.tsv/.txt: chrom pos ref-length alt-letters-or--): only the candidates with a "
+                           "usable pair are kept", false},
+        {'=', "hdr-out", "With --hdr-edits: path to the listing of the pairs: #chrom pos guideId dist seedMm protoMm flags subChrom subPos subBase", false},
+        {'+', "hdr-cds", "With --hdr: path to the coding segments (.bed, BED6 as --cds): a blocking substitution inside them is synonymous", false},
+        {'~', "hdr-allow-open", "With --hdr: keep the candidates with a pair whose repaired allele can be cut again", false, false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -648,6 +662,17 @@ int main(int argc, char **argv)
         }
     }
 
+    // --hdr / --hdr-edits / --hdr-out / --hdr-cds / --hdr-allow-open: knock-in design for the found guides
+    HdrOptions hdr;
+    {
+        const std::string why = parse_hdr_options(opts[61], opts[62], opts[63], opts[64], opts[65], discover, devices.size() != 1, (uint32_t)VSC_READ_LEN, &hdr);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+    CdsOfFile hdr_coding;
+
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
     {
@@ -852,6 +877,17 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_prime_edit> hdr_edits;
+            if (hdr.with_edits) hdr_edits = read_prime_edits(hdr.edits_path, ix.names);
+            if (hdr.with_cds) read_cds(hdr.cds_path, ix.names, ix.contigs, &hdr_coding);
+            if (hdr.on) {  // --hdr: the same for the knock-in FILTER, after all others
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_hdr(ctx, genome, found, &hdr.shape, hdr_edits.empty() ? nullptr : hdr_edits.data(), hdr_edits.size(), hdr_coding.cds,
+                        nullptr, hdr.allow_open, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -890,6 +926,14 @@ int main(int argc, char **argv)
                                              cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &variation_rows, &variation_pairs);
+            std::vector<uint32_t> hdr_rows;  // --hdr: the (n_pairs, n_usable) rows, and with --hdr-out the pairs
+            std::vector<vsc_hdr_pair> hdr_pairs;
+            if (hdr.on)
+                hdr_rows_and_pairs(hdr, vsc_guides_count(found), [&](uint32_t *r, vsc_hdr_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_guides_hdr(ctx, genome, found, &hdr.shape, hdr_edits.empty() ? nullptr : hdr_edits.data(), hdr_edits.size(), hdr_coding.cds, nullptr,
+                            r, pp, cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &hdr_rows, &hdr_pairs);
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -915,7 +959,8 @@ int main(int argc, char **argv)
                             (efficient ? '\t' + eff_text(eff_linear[i]) + '\t' + eff_text(eff_any_link(eff_model, eff_linear[i])) : "") +
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
                     const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
-                                             (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "");
+                                             (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "") +
+                                             (hdr.on ? hdr_columns(&hdr_rows[2 * i]) : "");
                     if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
                     else bed6 += line + ecol + '\n';
                 }
@@ -931,6 +976,7 @@ int main(int argc, char **argv)
             if (fx.with_listing) write_effects(fx.effects_path, fx_records, coding.transcripts, ids);
             if (prime.with_pairs) write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, loci, ix, ids);
             if (variation.with_out) write_variation(variation.out_path, variation_rows, variation_pairs, variants, ix.names, ids);
+            if (hdr.with_pairs) write_hdr_pairs(hdr.pairs_path, hdr.shape, hdr_pairs, hdr_edits, loci, ix.names, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');

@@ -63,6 +63,11 @@
 // -k K[,SPACING] -b COLS [-c interval|name] (needs -E and -B) picks the K best guides of every -B target, their cut sites at
 // least SPACING bases apart (vsc_pattern_guides_pick; tools/pick_host.hpp): ranked by table, eff, oof, mh in the order
 // of -b - pattern hits have no MIT score, so -b is required -; the -E listing gains the last columns pickTarget pickRank.
+// --hdr SpCas9 | Cas12a | SPEC (needs -E, one device; tools/hdr_host.hpp) asks whether a cut at every found guide can be repaired
+// from a donor that carries a wanted edit: the candidates without a context are dropped BEFORE the off-target search,
+// with --hdr-edits edits.tsv those without a usable pair as well (--hdr-allow-open: without any pair); --hdr-cds cds.bed keeps the
+// blocking substitution synonymous; the -E listing gains the last columns hdrPairs hdrUsable; --hdr-out pairs.tsv (needs
+// --hdr-edits) lists the pairs with their substitutions.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -77,6 +82,7 @@
 #include "edit_host.hpp"
 #include "effects_host.hpp"
 #include "prime_host.hpp"
+#include "hdr_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
@@ -287,6 +293,14 @@ int main(int argc, char **argv)
                                        "in one of them (allele-specific design)", false},
         {'%', "variation-out", "With --variants: path to the TSV of the guides' rows (#guideId none distal seed pam silent cost maxWeight) and, "
                                "behind a blank line, of the pairs (#chrom pos span alt guideId first touched top silent weight)", false},
+        {'^', "hdr", "With -E: SpCas9 | Cas12a | UP,DOWN,CUT,MAXDIST,ANCHOR,PAMSTART,PAM,SEEDSTART,SEEDLEN,PROTOSTART,PROTOLEN,MINSEED,MINPROTO,FLAGS: "
+                     "the cutting nuclease's shape for knock-ins by homology-directed repair; only the candidates with a defined context are "
+                     "kept, and the guide listing gains the last columns hdrPairs hdrUsable (one device)", false},
+        {'&', "hdr-edits", "With --hdr: path to the wanted edits (.tsv/.txt: chrom pos ref-length alt-letters-or--): only the candidates with a "
+                           "usable pair are kept", false},
+        {'=', "hdr-out", "With --hdr-edits: path to the listing of the pairs: #chrom pos guideId dist seedMm protoMm flags subChrom subPos subBase", false},
+        {'+', "hdr-cds", "With --hdr: path to the coding segments (.bed, BED6 as --cds): a blocking substitution inside them is synonymous", false},
+        {'~', "hdr-allow-open", "With --hdr: keep the candidates with a pair whose repaired allele can be cut again", false, false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -523,6 +537,17 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    // --hdr / --hdr-edits / --hdr-out / --hdr-cds / --hdr-allow-open: knock-in design for the found guides
+    HdrOptions hdr;
+    {
+        const std::string why = parse_hdr_options(opts[49], opts[50], opts[51], opts[52], opts[53], enumerate, opts[4].value.find(',') != std::string::npos, (uint32_t)pattern.size(), &hdr);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+    CdsOfFile hdr_coding;
+
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
     {
@@ -737,6 +762,17 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            std::vector<vsc_prime_edit> hdr_edits;
+            if (hdr.with_edits) hdr_edits = read_prime_edits(hdr.edits_path, ix.names);
+            if (hdr.with_cds) read_cds(hdr.cds_path, ix.names, ix.contigs, &hdr_coding);
+            if (hdr.on) {  // --hdr: the same for the knock-in FILTER, after all others
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_hdr(ctx, genome, found, &hdr.shape, hdr_edits.empty() ? nullptr : hdr_edits.data(), hdr_edits.size(), hdr_coding.cds,
+                        nullptr, hdr.allow_open, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -775,6 +811,14 @@ int main(int argc, char **argv)
                                                      variants.size(), r, pp, cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &variation_rows, &variation_pairs);
+            std::vector<uint32_t> hdr_rows;  // --hdr: the (n_pairs, n_usable) rows, and with --hdr-out the pairs
+            std::vector<vsc_hdr_pair> hdr_pairs;
+            if (hdr.on)
+                hdr_rows_and_pairs(hdr, vsc_pattern_guides_count(found), [&](uint32_t *r, vsc_hdr_pair *pp, uint64_t cap, uint64_t *np) {
+                    if (vsc_pattern_guides_hdr(ctx, genome, found, &hdr.shape, hdr_edits.empty() ? nullptr : hdr_edits.data(), hdr_edits.size(), hdr_coding.cds, nullptr,
+                            r, pp, cap, np, nullptr, nullptr) != VSC_OK)
+                        throw std::runtime_error(vsc_last_error(ctx));
+                }, &hdr_rows, &hdr_pairs);
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -784,7 +828,8 @@ int main(int argc, char **argv)
             if (!out.is_open()) throw std::runtime_error("Could not open output path.");
             out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
                 << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "")
-                << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << (prime.on ? "\tpbsLen\tpbsGC\tprimePairs" : "") << '\n';
+                << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << (prime.on ? "\tpbsLen\tpbsGC\tprimePairs" : "")
+                << (hdr.on ? "\thdrPairs\thdrUsable" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -811,6 +856,7 @@ int main(int argc, char **argv)
                 }
                 if (fx.on) ecol += effects_columns(&fx_rows[2 * i]);
                 if (prime.on) ecol += prime_columns(&prime_rows[2 * i]);
+                if (hdr.on) ecol += hdr_columns(&hdr_rows[2 * i]);
                 if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
                 else out << line << ecol << '\n';
             }
@@ -833,6 +879,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_variation(variation.out_path, variation_rows, variation_pairs, variants, ix.names, ids);
+            }
+            if (hdr.with_pairs) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_hdr_pairs(hdr.pairs_path, hdr.shape, hdr_pairs, hdr_edits, std::vector<vsc_locus>(loci, loci + n), ix.names, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

@@ -6052,14 +6052,10 @@ struct PrimeHostEdits {
     std::vector<uint32_t> bitmap;  // one bit per cell of 2^kPrimeCellShift global positions, over the whole genome
 };
 
-// The shape, the genome and the edits of a prime call, checked on the host.
-int prime_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e, PrimeShape &s,
-                PrimeHostEdits &h, const char *who)
+// EDITS of a call (the prime and the HDR family share the entry and its rules), checked on the host and laid out as the kernels
+// hold them
+int prime_edits_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_prime_edit *edits, uint64_t n_e, PrimeHostEdits &h, const char *who)
 {
-    ctx->err.clear();
-    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
-    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
-    if (!prime_shape_in(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kPrimeShapeRule);
     if (n_e && !edits) return fail_in(ctx, VSC_ERR_INVALID, who, "edits are null with n_e > 0");
     if (n_e > kPrimeMaxCount) return fail_in(ctx, VSC_ERR_RANGE, who, "more than 0xFFFFFFFE edits");
     h.gpos.resize((size_t)n_e);
@@ -6087,8 +6083,20 @@ int prime_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_prime_shape *s
     return VSC_OK;
 }
 
-// the edits at the front of edit_tabs: [global positions][entries][bitmap]; `more` bytes behind them (256-byte aligned) for the caller
-int prime_upload_edits(vsc_ctx *ctx, const PrimeHostEdits &h, size_t more, PrimeEdits &e, char **behind)
+// The shape, the genome and the edits of a prime call, checked on the host.
+int prime_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_prime_shape *shape, const vsc_prime_edit *edits, uint64_t n_e, PrimeShape &s,
+                PrimeHostEdits &h, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!prime_shape_in(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kPrimeShapeRule);
+    return prime_edits_check(ctx, genome, edits, n_e, h, who);
+}
+
+// the edits at the front of edit_tabs: [global positions][entries][bitmap]; `more` bytes behind them (256-byte aligned) for the
+// caller; bitmap: the kernels ask it (the family's debug switch)
+int prime_upload_edits(vsc_ctx *ctx, const PrimeHostEdits &h, size_t more, PrimeEdits &e, char **behind, bool bitmap)
 {
     const size_t n = h.gpos.size();
     const size_t g_bytes = round256(n * sizeof(uint32_t) + 4), r_bytes = round256(n * sizeof(PrimeEdit) + 4);
@@ -6101,7 +6109,7 @@ int prime_upload_edits(vsc_ctx *ctx, const PrimeHostEdits &h, size_t more, Prime
         VSC_HIP(ctx, hipMemcpyAsync(base + g_bytes + r_bytes, h.bitmap.data(), h.bitmap.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     }
     e = PrimeEdits{(const uint32_t *)base, (const PrimeEdit *)(base + g_bytes),
-                   n && ctx->prime_bitmap ? (const uint32_t *)(base + g_bytes + r_bytes) : nullptr, (uint32_t)n};
+                   n && bitmap ? (const uint32_t *)(base + g_bytes + r_bytes) : nullptr, (uint32_t)n};
     if (behind) *behind = base + g_bytes + r_bytes + b_bytes;
     return VSC_OK;
 }
@@ -6129,7 +6137,7 @@ int prime_run(vsc_ctx *ctx, const vsc_genome *genome, const PrimeShape &shape, c
     const size_t flag_bytes = 256;
     JoinTabs tabs(n, 2 * PairCoverage::bytes(n_e), flag_bytes);
     PrimeArgs a{};
-    const int urc = prime_upload_edits(ctx, h, tabs.bytes(), a.edits, &tabs.base);
+    const int urc = prime_upload_edits(ctx, h, tabs.bytes(), a.edits, &tabs.base, ctx->prime_bitmap);
     if (urc != VSC_OK) return urc;
     a.g = eff_planes(genome);
     a.shape = shape;
@@ -6219,7 +6227,7 @@ int prime_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_p
                                 [&] { return prime_check(ctx, genome, shape, edits, n_e, s, h, who); }, no_refusal);
     if (rc != VSC_OK) return rc;
     PrimeFilterArgs a{};
-    const int urc = prime_upload_edits(ctx, h, 0, a.edits, nullptr);
+    const int urc = prime_upload_edits(ctx, h, 0, a.edits, nullptr, ctx->prime_bitmap);
     if (urc != VSC_OK) return urc;
     if (in->n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the edits are this call's vectors, and no pass will wait)
     a.g = eff_planes(genome);
@@ -6748,6 +6756,308 @@ int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vs
                                       vsc_pattern_guides **out)
 {
     return effects_filter(ctx, genome, in, shape, to, cds, code, false, require, forbid, out, "vsc_pattern_guides_filter_effects");
+}
+
+}  // extern "C"
+
+// ---- HDR knock-in design (the definition: vsc_hdr.h, the kernels: vsc_hdr.hip) -----------------------------------
+namespace {
+
+const char *const kHdrShapeRule =
+    "site_len 16 .. 32, up and down <= 32, up + site_len + down <= 64, 1 <= cut <= site_len - 1, max_dist <= 63, anchor 0 or 1, the pam "
+    "(len <= 8), seed (len <= 16) and protospacer (len <= 32) ranges inside the site, pam_accept 1 .. 15 below pam_len and 0 from it on, "
+    "min_seed_mm <= seed_len, min_proto_mm <= proto_len, flags <= 7, reserved fields 0";
+
+bool hdr_shape_in(const vsc_hdr_shape *shape, HdrShape &s)
+{
+    s = HdrShape{};
+    s.up = shape->up;
+    s.site_len = shape->site_len;
+    s.down = shape->down;
+    s.cut = shape->cut;
+    s.max_dist = shape->max_dist;
+    s.anchor = shape->anchor;
+    s.pam_start = shape->pam_start;
+    s.pam_len = shape->pam_len;
+    for (uint32_t j = 0; j < kHdrMaxPam; ++j) s.pam_accept[j] = shape->pam_accept[j];
+    s.seed_start = shape->seed_start;
+    s.seed_len = shape->seed_len;
+    s.proto_start = shape->proto_start;
+    s.proto_len = shape->proto_len;
+    s.min_seed_mm = shape->min_seed_mm;
+    s.min_proto_mm = shape->min_proto_mm;
+    s.flags = shape->flags;
+    return shape->reserved == 0u && hdr_shape_valid(s);
+}
+
+// The shape, the genome, the edits, the CDS and CODE of an HDR call, checked on the host.
+int hdr_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_hdr_shape *shape, const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds,
+              const char *code, HdrShape &s, PrimeHostEdits &h, HdrTables &tabs, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!hdr_shape_in(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kHdrShapeRule);
+    EffectsCode ec{};
+    if (!effects_code(code, ec)) return fail_in(ctx, VSC_ERR_INVALID, who, "the code has fewer than 64 letters");
+    std::memcpy(tabs.aa, ec.aa, 64);
+    for (uint32_t j = 0; j < kHdrMaxPam; ++j) tabs.accept[j] = s.pam_accept[j];
+    if (cds) {
+        bool same = cds->contig_off.size() == genome->h_contig_off.size() && genome->h_contig_off.size() == genome->h_contig_end.size();
+        for (size_t c = 0; same && c < cds->contig_off.size(); ++c)
+            same = cds->contig_off[c] == genome->h_contig_off[c] && cds->contig_off[c] + cds->contig_len[c] == genome->h_contig_end[c];
+        if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the CDS was built with another contig table than the genome's");
+    }
+    return prime_edits_check(ctx, genome, edits, n_e, h, who);
+}
+
+const CandidateRule kHdrRule{"the shape's site_len must be 23", kHdrMaxCount, "more than 0xFFFFFFFE candidates"};
+
+// Rows, pairs and coverage of the loci `at`: hdr_rows_kernel, then - with edits - the join of the rows with them, whose write
+// pass also counts the pairs by flag.
+int hdr_run(vsc_ctx *ctx, const vsc_genome *genome, const HdrShape &shape, const PrimeHostEdits &h, const vsc_cds *cds, const HdrTables &tables,
+            const CandidateLoci &at, uint32_t *rows, vsc_hdr_pair *pairs, uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage,
+            vsc_hdr_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_e = h.gpos.size();
+    const uint64_t n = at.n;
+    if (stats) *stats = vsc_hdr_stats{};
+    if (n_pairs) *n_pairs = 0;
+    PairCoverage cov(n_e, coverage, kHdrUndefined);
+    if (n == 0) {
+        ctx->timing = vsc_timing{};
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    // edit_tabs behind the edits: [usable pairs per edit][their smallest dist][pairs per tile][offsets per tile][pairs by flag]
+    const size_t flag_bytes = 256;
+    JoinTabs tabs(n, 2 * PairCoverage::bytes(n_e), flag_bytes);
+    HdrArgs a{};
+    const int urc = prime_upload_edits(ctx, h, tabs.bytes(), a.edits, &tabs.base, ctx->hdr_bitmap);
+    if (urc != VSC_OK) return urc;
+    if (cds) {
+        const int crc = effects_upload_cds(ctx, cds, a.cds);
+        if (crc != VSC_OK) return crc;
+        a.have_cds = 1u;
+    }
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.tabs = tables;
+    a.n = n;
+    unsigned long long seen[kHdrCounts] = {};
+    const int rrc = rows_pass(ctx, at, sizeof(uint2), rows, seen, kHdrCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint2 *)d_rows;
+        a.loci = d_loci;
+        return launch_hdr_rows(a, ctx->n_cus, ctx->hdr_groups_per_cu, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
+    HdrPairArgs p{};
+    p.g = a.g;
+    p.shape = shape;
+    p.edits = a.edits;
+    p.cds = a.cds;
+    p.have_cds = a.have_cds;
+    p.tabs = tables;
+    p.loci = a.loci;
+    p.rows = a.out;
+    p.n = n;
+    p.n_work = tabs.tiles;
+    p.tile_count = tabs.tile_count();
+    p.tile_off = tabs.tile_off();
+    Join j{n, sizeof(uint2), n_e != 0, pairs, sizeof(vsc_hdr_pair), capacity, n_pairs, kHdrMaxCount, "more than 0xFFFFFFFE pairs",
+           "more pairs than `capacity` holds; *n_pairs is their number"};
+    unsigned long long by_flag[kHdrFlags] = {};
+    const int jrc = join_passes(
+        ctx, tabs, j,
+        [&](uint4 *d_pairs, bool write) {
+            p.pairs = d_pairs;
+            return launch_hdr_pairs(p, write, ctx->stream);
+        },
+        [&](bool) { return coverage || stats; },
+        [&] {
+            const int crc = cov.clear(ctx, tabs);
+            if (crc != VSC_OK) return crc;
+            p.cov_count = cov.count;
+            p.cov_min = cov.min;
+            p.flag_count = (unsigned long long *)tabs.extra();
+            VSC_HIP(ctx, hipMemsetAsync(p.flag_count, 0, flag_bytes, ctx->stream));
+            return VSC_OK;
+        },
+        [&] {
+            VSC_HIP(ctx, hipMemcpyAsync(by_flag, p.flag_count, sizeof by_flag, hipMemcpyDeviceToHost, ctx->stream));
+            return cov.read(ctx, a.stats + kHdrCounts + 1);
+        });
+    if (jrc != VSC_OK) return jrc;
+    const uint64_t covered = cov.take();
+    if (stats) {
+        class_counts(stats, seen);
+        stats->with_pair = seen[kEffClasses];
+        stats->with_usable = seen[kEffClasses + 1];
+        stats->pairs = j.total;
+        for (uint32_t b = 0; b < kHdrFlags; ++b) stats->pairs_by_flag[b] = by_flag[b];
+        stats->edits_covered = covered;
+        stats->score_ms = j.rows_ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    return join_refusal(ctx, j, who);
+}
+
+// vsc_guides_hdr / vsc_pattern_guides_hdr: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int hdr_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_hdr_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
+               const vsc_cds *cds, const char *code, bool need_23, uint32_t *rows, vsc_hdr_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+               uint32_t *coverage, vsc_hdr_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    HdrShape s{};
+    PrimeHostEdits h;
+    HdrTables tables{};
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kHdrRule, who, at, &s.site_len,
+                                   [&] { return hdr_check(ctx, genome, shape, edits, n_e, cds, code, s, h, tables, who); }, no_refusal);
+    if (rc != VSC_OK) return rc;
+    return hdr_run(ctx, genome, s, h, cds, tables, at, rows, pairs, capacity, n_pairs, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_hdr / vsc_pattern_guides_filter_hdr: the candidates with a usable pair, or - allow_open - with any pair
+template <class Guides>
+int hdr_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_hdr_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
+               const vsc_cds *cds, const char *code, bool need_23, uint32_t allow_open, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    HdrShape s{};
+    PrimeHostEdits h;
+    HdrFilterArgs a{};
+    const int rc = filter_front(ctx, in, out, need_23, kHdrRule, who, &s.site_len,
+                                [&] { return hdr_check(ctx, genome, shape, edits, n_e, cds, code, s, h, a.tabs, who); }, no_refusal);
+    if (rc != VSC_OK) return rc;
+    const int urc = prime_upload_edits(ctx, h, 0, a.edits, nullptr, ctx->hdr_bitmap);
+    if (urc != VSC_OK) return urc;
+    if (cds) {
+        const int crc = effects_upload_cds(ctx, cds, a.cds);
+        if (crc != VSC_OK) return crc;
+        a.have_cds = 1u;
+    }
+    if (in->n == 0) VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the edits are this call's vectors, and no pass will wait)
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.allow_open = allow_open ? 1u : 0u;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_hdr_filter(a, write, ctx->stream); });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_hdr_bitmap(vsc_ctx *ctx, int on)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    ctx->hdr_bitmap = on != 0;
+    return VSC_OK;
+}
+
+int vsc_debug_hdr_groups_per_cu(vsc_ctx *ctx, uint32_t groups)
+{
+    if (!ctx || groups > kHdrMaxGroupsPerCu) return VSC_ERR_INVALID;
+    ctx->hdr_groups_per_cu = groups;
+    return VSC_OK;
+}
+
+int vsc_hdr_site_text(const char *context, const vsc_hdr_shape *shape, uint32_t e0, uint32_t del_len, const char *ins, const uint8_t *allowed,
+                      uint32_t *pair, char *edited)
+{
+    if (!context || !shape || !ins || !pair) return VSC_ERR_INVALID;
+    HdrShape s{};
+    if (!hdr_shape_in(shape, s)) return VSC_ERR_INVALID;
+    const uint32_t C = hdr_context_len(s);
+    if (strnlen(context, C + 1) != C) return VSC_ERR_INVALID;
+    uint64_t ch = 0, cl = 0;
+    for (uint32_t j = 0; j < C; ++j) {
+        const int b = base_code(context[j]);
+        if (b > 3) return VSC_ERR_INVALID;
+        ch |= (uint64_t)(b >> 1) << j;
+        cl |= (uint64_t)(b & 1) << j;
+        if (allowed && allowed[j] > kHdrAnyLetter) return VSC_ERR_INVALID;
+    }
+    PrimeEdit e{0u, 0u, 0u, 0u};
+    const size_t ins_len = strnlen(ins, kPrimeMaxIndel + 1);
+    if (ins_len > kPrimeMaxIndel || del_len > kPrimeMaxIndel || del_len + ins_len < 1 || e0 > C || del_len > C - e0) return VSC_ERR_INVALID;
+    for (size_t k = 0; k < ins_len; ++k) {
+        const int b = base_code(ins[k]);
+        if (b > 3) return VSC_ERR_INVALID;
+        e.ins |= (uint32_t)b << (2 * k);
+    }
+    e.lens = del_len | (uint32_t)ins_len << 16;
+    pair[0] = pair[1] = kHdrUndefined;
+    if (edited) edited[0] = 0;
+    uint32_t info = 0, block = 0;
+    if (!hdr_pair(s, s.pam_accept, ch, cl, 0u, e0, e, [&](uint32_t r) -> uint32_t { return allowed ? allowed[r] : kHdrAnyLetter; }, &info, &block))
+        return VSC_OK;
+    pair[0] = info;
+    pair[1] = block;
+    if (edited) {
+        uint32_t o = 0;
+        for (uint32_t j = 0; j < e0; ++j) edited[o++] = (char)std::toupper((unsigned char)context[j]);
+        for (size_t k = 0; k < ins_len; ++k) edited[o++] = (char)std::toupper((unsigned char)ins[k]);
+        for (uint32_t j = e0 + del_len; j < C; ++j) edited[o++] = (char)std::toupper((unsigned char)context[j]);
+        edited[o] = 0;
+        if (block != kHdrNoBlock) {
+            const uint32_t r = block >> 16 & 0xFFu;
+            edited[r < e0 ? r : r + (uint32_t)ins_len - del_len] = "ACGT"[block >> 8 & 3u];
+        }
+    }
+    return VSC_OK;
+}
+
+int vsc_loci_hdr(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_hdr_shape *shape, const vsc_prime_edit *edits,
+                 uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t *rows, vsc_hdr_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                 uint32_t *coverage, vsc_hdr_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_hdr";
+    HdrShape s{};
+    PrimeHostEdits h;
+    HdrTables tables{};
+    const int rc = hdr_check(ctx, genome, shape, edits, n_e, cds, code, s, h, tables, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kHdrMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return hdr_run(ctx, genome, s, h, cds, tables, CandidateLoci{nullptr, loci, n}, rows, pairs, capacity, n_pairs, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_hdr_shape *shape, const vsc_prime_edit *edits, uint64_t n_e,
+                   const vsc_cds *cds, const char *code, uint32_t *rows, vsc_hdr_pair *pairs, uint64_t capacity, uint64_t *n_pairs,
+                   uint32_t *coverage, vsc_hdr_stats *stats)
+{
+    return hdr_guides(ctx, genome, guides, shape, edits, n_e, cds, code, true, rows, pairs, capacity, n_pairs, coverage, stats, "vsc_guides_hdr");
+}
+
+int vsc_pattern_guides_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_hdr_shape *shape,
+                           const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t *rows, vsc_hdr_pair *pairs,
+                           uint64_t capacity, uint64_t *n_pairs, uint32_t *coverage, vsc_hdr_stats *stats)
+{
+    return hdr_guides(ctx, genome, guides, shape, edits, n_e, cds, code, false, rows, pairs, capacity, n_pairs, coverage, stats,
+                      "vsc_pattern_guides_hdr");
+}
+
+int vsc_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_hdr_shape *shape, const vsc_prime_edit *edits,
+                          uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t allow_open, vsc_guides **out)
+{
+    return hdr_filter(ctx, genome, in, shape, edits, n_e, cds, code, true, allow_open, out, "vsc_guides_filter_hdr");
+}
+
+int vsc_pattern_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_hdr_shape *shape,
+                                  const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t allow_open,
+                                  vsc_pattern_guides **out)
+{
+    return hdr_filter(ctx, genome, in, shape, edits, n_e, cds, code, false, allow_open, out, "vsc_pattern_guides_filter_hdr");
 }
 
 }  // extern "C"

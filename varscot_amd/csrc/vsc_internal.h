@@ -12,6 +12,7 @@
 #include "vsc_edit.h"
 #include "vsc_variation.h"
 #include "vsc_prime.h"
+#include "vsc_hdr.h"
 #include "vsc_effects.h"
 
 namespace vsc {
@@ -784,6 +785,67 @@ hipError_t launch_prime_rows(const PrimeArgs &args, int n_cus, uint32_t groups_p
 hipError_t launch_prime_pairs(const PrimePairArgs &args, bool write, hipStream_t stream);
 hipError_t launch_prime_filter(const PrimeFilterArgs &args, bool write, hipStream_t stream);
 constexpr uint32_t kPrimeGroupsPerCu = 28, kPrimeMaxGroupsPerCu = 64;
+// vsc_hdr.hip (the definition: vsc_hdr.h)
+// the rows kernel's counters: the classes, the candidates with a pair, the candidates with a usable pair
+constexpr uint32_t kHdrCounts = kEffClasses + 2;
+// CODE and the PAM's letter sets, the tables a lane indexes: the kernels copy them to LDS once per workgroup
+struct HdrTables {
+    uint8_t aa[64];
+    uint32_t accept[kHdrMaxPam];
+};
+struct HdrArgs {
+    EffPlanes g;
+    HdrShape shape;
+    PrimeEdits edits;             // n == 0: no edits, both words of a defined row are 0
+    CdsView cds;                  // have_cds == 0: none, ALLOWED always holds
+    uint32_t have_cds;
+    HdrTables tabs;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: (n_pairs, n_usable), kHdrUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kHdrCounts], zeroed before the launch: the kernel adds its candidates per counter
+};
+// the pairs' and the filter's two passes: tile i = candidates [i * kEditTile, ..)
+struct HdrPairArgs {
+    EffPlanes g;
+    HdrShape shape;
+    PrimeEdits edits;
+    CdsView cds;
+    uint32_t have_cds;
+    HdrTables tabs;
+    const uint4 *loci;            // [n]
+    const uint2 *rows;            // [n] what hdr_rows_kernel left
+    unsigned long long n;
+    uint32_t n_work;              // tiles
+    uint32_t *tile_count;         // count pass out: pairs per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    uint4 *pairs;                 // write pass out (null: coverage and flag counts only)
+    uint32_t *cov_count, *cov_min;  // [edits.n] each, write pass: usable pairs and their smallest dist per edit, 0 / 0xFFFFFFFF before the launch; null: none
+    unsigned long long *flag_count;  // [kHdrFlags], zeroed before the launch: the write pass adds its pairs per flag; null: none
+};
+struct HdrFilterArgs {
+    EffPlanes g;
+    HdrShape shape;
+    PrimeEdits edits;
+    CdsView cds;
+    uint32_t have_cds;
+    HdrTables tabs;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    uint32_t allow_open;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+// groups_per_cu: workgroups per CU the rows kernel's grid is capped at (0: the default, kHdrGroupsPerCu)
+hipError_t launch_hdr_rows(const HdrArgs &args, int n_cus, uint32_t groups_per_cu, hipStream_t stream);
+hipError_t launch_hdr_pairs(const HdrPairArgs &args, bool write, hipStream_t stream);
+hipError_t launch_hdr_filter(const HdrFilterArgs &args, bool write, hipStream_t stream);
+constexpr uint32_t kHdrGroupsPerCu = 28, kHdrMaxGroupsPerCu = 64;
 // vsc_effects.hip (the definition: vsc_effects.h)
 constexpr uint32_t kEffectsCounts = kEffClasses + 1 + kEffectClasses;  // the candidates' classes, the candidates with an effect, the effects by class
 struct EffectsCode {
