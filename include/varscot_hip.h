@@ -2795,6 +2795,106 @@ int vsc_pattern_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pa
                                   const vsc_prime_edit *edits, uint64_t n_e, const vsc_cds *cds, const char *code, uint32_t allow_open,
                                   vsc_pattern_guides **out);
 
+/* ---- guide RNA self-complementarity: hairpin and scaffold stems --------------------------------- */
+/*
+ * "Will this guide RNA fold back on itself, or onto its own constant part?": the count of stems a spacer can form with
+ * itself and with the scaffold text the caller brings (the sgRNA scaffold, the Cas12a direct repeat, a pegRNA's scaffold with
+ * its extension) - the "self-complementarity" column of guide-design tools.  A relation between two positions of the same
+ * guide, which no model of the other families can express.  This text is normative; everything is integer.  Letters are
+ * A C G T = 0 .. 3, and U is read as T.
+ *
+ * SHAPE    site_len 16 .. 32.  proto_start, proto_len 12 .. 32 with proto_start + proto_len <= site_len: the site positions (read
+ *          orientation) that become the guide RNA's spacer; n = proto_len.  (SpCas9 23-mer: 0, 20; Cas12a 27-mer: 4, 23.)
+ *          stem k 3 .. 8;  gc_min 0 .. k;  min_loop 0 .. 16.
+ *          seed_start, seed_len 0 .. 16 in SPACER positions, seed_start + seed_len <= n (seed_len 0: no seed).
+ *          flags bit 0 WOBBLE; every other bit and every reserved field 0.
+ * SCAFFOLD m letters s[0, m), 5' to 3', m 0 .. 128, A C G T U in any case; any other letter is refused.  It is the launch's, not
+ *          the candidate's.  The library ships none.
+ * SPACER   g[0, n) = the site of locus (c, p, strand) in read orientation ('+': c[p, p + site_len), '-': its reverse complement),
+ *          positions [proto_start, proto_start + n).  CLASS as EffClass, in its order (off_contig cannot occur and stays 0).
+ * PAIR(a, b)   a + b == 3; under WOBBLE also {a, b} == {G, T}.
+ * SELF STEM (i, j, L)      0 <= i, i + L + min_loop <= j, j + L <= n, PAIR(g[i + t], g[j + L - 1 - t]) for t in [0, L).
+ * SCAFFOLD STEM (i, j, L)  i + L <= n, j + L <= m,                  PAIR(g[i + t], s[j + L - 1 - t]) for t in [0, L).
+ * QUAL(i)      the k-mer g[i, i + k), i in [0, n - k], holds at least gc_min letters G or C.
+ * SELF5(i)     a self stem (i, j, k) exists.        SCAF(i)   a scaffold stem (i, j, k) exists.
+ * self_starts  #{ i : QUAL(i) and SELF5(i) }
+ * scaf_starts  #{ i : QUAL(i) and SCAF(i) }
+ * starts       #{ i : QUAL(i) and (SELF5(i) or SCAF(i)) }   (the form of CHOPCHOP's count: k = 4, gc_min = 2)
+ * COVERED      the union of [i, i + k) and [j, j + k) over self stems (i, j, k) with QUAL(i), and of [i, i + k) over scaffold stems
+ *              (i, j, k) with QUAL(i).
+ * seed_paired  # of COVERED positions inside [seed_start, seed_start + seed_len)
+ * self_longest the largest L for which a self stem (i, j, L) exists (any G/C content), 0 when none
+ * scaf_longest the largest L for which a scaffold stem (i, j, L) exists, 0 when none (m == 0: 0)
+ * ROW      two uint32 per candidate: w0 = starts | self_starts << 8 | scaf_starts << 16 | seed_paired << 24,
+ *          w1 = self_longest | scaf_longest << 8.  Both 0xFFFFFFFF (VSC_FOLD_UNDEFINED) unless the class is defined.
+ * FILTER   limits max_starts, max_self_longest, max_scaf_longest, max_seed_paired, each 0 .. 32 or 0xFFFFFFFF (no limit):
+ *          keep iff defined and every value <= its limit.  Survivors keep their order.
+ *
+ * No bit parity with CHOPCHOP's script is claimed: its loop bounds carry quirks of their own.  Device, host (vsc_fold_text) and
+ * the definition restated on strings agree to the bit.
+ *
+ * vsc_fold_text gives the row of one spacer of n = shape->proto_len letters against a scaffold of m letters on the host, with
+ * the very function the kernels call - for users who hold a guide list and no genome.  A spacer letter other than A C G T U
+ * gives the undefined row (VSC_OK); a shape outside SHAPE, n != proto_len, a spacer shorter than n, m > 128 or a bad scaffold
+ * letter is VSC_ERR_INVALID.
+ *
+ * vsc_loci_fold: rows[2 i], rows[2 i + 1] = w0, w1 of loci[i] (host arrays, n entries).  One upload, one kernel, one copy back.
+ * stats is optional: the candidates by class (they add up to n), the kernel's time and the call's wall time in milliseconds.
+ * n == 0: VSC_OK, nothing is launched.  vsc_guides_fold takes the candidates where they lie on the device and requires
+ * site_len == 23 (else VSC_ERR_INVALID); the host-only object of vsc_multi_guides_enumerate goes the vsc_loci_fold way.
+ * vsc_pattern_guides_fold is the same for vsc_pattern_guides: site_len is the pattern's length, which the CALLER vouches for.
+ * VSC_ERR_INVALID, before anything is written: a shape outside SHAPE, a non-zero reserved field, m > 128, a bad scaffold letter,
+ * a genome or an object of another context, a NULL shape, NULL rows with n > 0, a NULL scaffold with m > 0.
+ *
+ * vsc_guides_filter_fold / vsc_pattern_guides_filter_fold: *out = the candidates of `in` that pass FILTER - codes and loci copied
+ * unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of 1 024 candidates: no append
+ * atomic, the bytes depend on the input, the shape, the scaffold and the limits only.  A limit in 33 .. 0xFFFFFFFE:
+ * VSC_ERR_INVALID.  The result is a normal object of its kind on ctx's device, as the efficiency filter's is.
+ *
+ * vsc_ctx_timing afterwards: as after the efficiency calls (8 bytes written per candidate).  The scratch is the efficiency
+ * calls'; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: minimum-free-energy folding (nearest-neighbour energies, bulges or internal loops inside a stem); a shipped
+ * scaffold; the pegRNA extension of each (candidate, edit) pair folded against its spacer, which belongs to the prime-editing
+ * pairs; a vsc_multi_* entry (for the reason given above for the efficiency calls).
+ */
+#define VSC_FOLD_UNDEFINED 0xFFFFFFFFu
+#define VSC_FOLD_NO_LIMIT 0xFFFFFFFFu
+#define VSC_FOLD_WOBBLE 1u
+typedef struct {
+    uint32_t site_len, proto_start, proto_len;
+    uint32_t stem, gc_min, min_loop;
+    uint32_t seed_start, seed_len;
+    uint32_t flags;
+    uint32_t reserved[3]; /* 0 */
+} vsc_fold_shape;
+typedef struct {
+    uint32_t max_starts, max_self_longest, max_scaf_longest, max_seed_paired;
+} vsc_fold_limits;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    double kernel_ms, wall_ms;
+    uint64_t reserved; /* 0 */
+} vsc_fold_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_fold_stats) == 64 && sizeof(vsc_fold_shape) == 48 && sizeof(vsc_fold_limits) == 16, "vsc_fold_* layout");
+#else
+_Static_assert(sizeof(vsc_fold_stats) == 64 && sizeof(vsc_fold_shape) == 48 && sizeof(vsc_fold_limits) == 16, "vsc_fold_* layout");
+#endif
+int vsc_fold_text(const char *spacer /* n letters */, uint32_t n, const char *scaffold /* m letters */, uint32_t m,
+                  const vsc_fold_shape *shape, uint32_t *row /* 2 */);
+int vsc_loci_fold(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n, const vsc_fold_shape *shape,
+                  const char *scaffold, uint32_t m, uint32_t *rows /* host, 2 n */, vsc_fold_stats *stats /* optional */);
+int vsc_guides_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_fold_shape *shape, const char *scaffold,
+                    uint32_t m, uint32_t *rows /* host, two per candidate */, vsc_fold_stats *stats /* optional */);
+int vsc_pattern_guides_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_fold_shape *shape,
+                            const char *scaffold, uint32_t m, uint32_t *rows /* host, two per candidate */,
+                            vsc_fold_stats *stats /* optional */);
+int vsc_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_fold_shape *shape, const char *scaffold,
+                           uint32_t m, const vsc_fold_limits *limits, vsc_guides **out);
+int vsc_pattern_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_fold_shape *shape,
+                                   const char *scaffold, uint32_t m, const vsc_fold_limits *limits, vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

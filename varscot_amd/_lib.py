@@ -336,6 +336,32 @@ class MhStats(C.Structure):
 
 assert C.sizeof(MhShape) == 16 and C.sizeof(MhStats) == 64
 
+FOLD_UNDEFINED = 0xFFFFFFFF  # VSC_FOLD_UNDEFINED: both words of a candidate whose class is not defined
+FOLD_NO_LIMIT = 0xFFFFFFFF  # VSC_FOLD_NO_LIMIT
+FOLD_WOBBLE = 1  # VSC_FOLD_WOBBLE
+
+
+class FoldShapeStruct(C.Structure):
+    """vsc_fold_shape: the site's length, the spacer inside it, the stem length k, the G/C floor of a k-mer, the shortest loop,
+    the seed in spacer positions and the flags (bit 0: G-U wobble pairs count)."""
+    _fields_ = [("site_len", C.c_uint32), ("proto_start", C.c_uint32), ("proto_len", C.c_uint32), ("stem", C.c_uint32),
+                ("gc_min", C.c_uint32), ("min_loop", C.c_uint32), ("seed_start", C.c_uint32), ("seed_len", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class FoldLimits(C.Structure):
+    """vsc_fold_limits: the largest starts, self_longest, scaf_longest and seed_paired a kept candidate may have (0 .. 32, or
+    FOLD_NO_LIMIT)."""
+    _fields_ = [("max_starts", C.c_uint32), ("max_self_longest", C.c_uint32), ("max_scaf_longest", C.c_uint32),
+                ("max_seed_paired", C.c_uint32)]
+
+
+class FoldStats(MhStats):
+    """vsc_fold_stats: the candidates of a call by class (the five counts add up to n), the kernel's and the call's time."""
+
+
+assert C.sizeof(FoldShapeStruct) == 48 and C.sizeof(FoldLimits) == 16 and C.sizeof(FoldStats) == 64
+
 PICK_NONE = 0xFFFFFFFF  # VSC_PICK_NONE: a picks entry beyond counts[t], the rank of a candidate that is not picked
 
 
@@ -809,6 +835,14 @@ SYMBOLS = [
                                         C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_hdr", C.c_int, [_vp, _vp, _vp, C.POINTER(HdrShapeStruct), _vp, C.c_uint64, _vp, C.c_char_p, C.c_uint32,
                                                 C.POINTER(_vp)]),
+    ("vsc_fold_text", C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(FoldShapeStruct), _vp]),
+    ("vsc_loci_fold", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, _vp, C.POINTER(FoldStats)]),
+    ("vsc_guides_fold", C.c_int, [_vp, _vp, _vp, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, _vp, C.POINTER(FoldStats)]),
+    ("vsc_pattern_guides_fold", C.c_int, [_vp, _vp, _vp, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, _vp, C.POINTER(FoldStats)]),
+    ("vsc_guides_filter_fold", C.c_int, [_vp, _vp, _vp, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, C.POINTER(FoldLimits),
+                                         C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_fold", C.c_int, [_vp, _vp, _vp, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, C.POINTER(FoldLimits),
+                                                 C.POINTER(_vp)]),
     ("vsc_variation_host", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp,
                                      C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     ("vsc_loci_variation", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
@@ -841,6 +875,7 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_prime_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_hdr_bitmap", C.c_int, [_vp, C.c_int]),
     ("vsc_debug_hdr_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_fold_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
 ]
 

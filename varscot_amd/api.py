@@ -1268,6 +1268,128 @@ def microhomology_scores(pairs):
     return mh, oof
 
 
+FOLD_UNDEFINED = _lib.FOLD_UNDEFINED  # both words of a candidate whose fold row is undefined
+FOLD_NO_LIMIT = _lib.FOLD_NO_LIMIT
+FOLD_WOBBLE = _lib.FOLD_WOBBLE
+_FOLD_RULE = ("a fold shape has site_len 16..32, a spacer of 12..32 bases inside the site, stem 3..8, gc_min 0..stem, min_loop 0..16, a seed "
+              "(start and length 0..16) inside the spacer and no flag but FOLD_WOBBLE")
+
+
+class FoldShape:
+    """vsc_fold_shape: how the self-complementarity of a guide RNA is counted.  site_len 16..32 is the candidates' length (23 for
+    enumerate_guides', the pattern's for enumerate_pattern's); spacer = (start, length) in read positions of the site, length
+    12..32: the bases that become the guide RNA's spacer; stem 3..8 is the length k of a counted stem, gc_min 0..k the G/C a
+    k-mer needs to count, min_loop 0..16 the unpaired bases between the arms of a hairpin; seed = (start, length), each 0..16, in
+    SPACER positions (length 0: none); wobble=True counts G-U pairs.  FOLD_SHAPES holds "SpCas9" and "Cas12a": shapes only, the
+    scaffold is the caller's.  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, spacer=(0, 20), stem=4, gc_min=2, min_loop=3, seed=(8, 12), wobble=False, flags=None,
+                 validate=True):
+        self.site_len, self.proto_start, self.proto_len = int(site_len), int(spacer[0]), int(spacer[1])
+        self.stem, self.gc_min, self.min_loop = int(stem), int(gc_min), int(min_loop)
+        self.seed_start, self.seed_len = int(seed[0]), int(seed[1])
+        self.flags = int(flags) if flags is not None else (FOLD_WOBBLE if wobble else 0)
+        self.reserved = (0, 0, 0)
+        if validate and not self.valid():
+            raise ValueError(_FOLD_RULE)
+
+    def valid(self):
+        return (16 <= self.site_len <= 32 and 12 <= self.proto_len <= 32 and 0 <= self.proto_start
+                and self.proto_start + self.proto_len <= self.site_len and 3 <= self.stem <= 8 and 0 <= self.gc_min <= self.stem
+                and 0 <= self.min_loop <= 16 and 0 <= self.seed_start <= 16 and 0 <= self.seed_len <= 16
+                and self.seed_start + self.seed_len <= self.proto_len and self.flags in (0, FOLD_WOBBLE)
+                and tuple(self.reserved) == (0, 0, 0))
+
+    def _struct(self):
+        s = _lib.FoldShapeStruct(self.site_len, self.proto_start, self.proto_len, self.stem, self.gc_min, self.min_loop,
+                                 self.seed_start, self.seed_len, self.flags)
+        for i, v in enumerate(self.reserved):
+            s.reserved[i] = int(v)
+        return s
+
+    def __repr__(self):
+        return "FoldShape(site_len=%d, spacer=(%d, %d), stem=%d, gc_min=%d, min_loop=%d, seed=(%d, %d), flags=%d)" % (
+            self.site_len, self.proto_start, self.proto_len, self.stem, self.gc_min, self.min_loop, self.seed_start, self.seed_len,
+            self.flags)
+
+
+FOLD_SHAPES = {"SpCas9": FoldShape(23, (0, 20), 4, 2, 3, (8, 12)), "Cas12a": FoldShape(27, (4, 23), 4, 2, 3, (0, 6))}
+
+
+def _fold_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in FOLD_SHAPES:
+            raise ValueError("%s names one of %s, or is a FoldShape" % (what, ", ".join(sorted(FOLD_SHAPES))))
+        shape = FOLD_SHAPES[shape]
+    if not isinstance(shape, FoldShape):
+        raise ValueError("%s must be a FoldShape or the name of a preset" % what)
+    return shape
+
+
+def _fold_scaffold(scaffold, validate=True):
+    """The scaffold text of a call as bytes (None: empty).  At most 128 letters of A C G T U, in any case."""
+    if scaffold is None:
+        return b""
+    b = scaffold if isinstance(scaffold, bytes) else str(scaffold).encode()
+    if validate and (len(b) > 128 or any(c not in b"ACGTUacgtu" for c in b)):
+        raise ValueError("a scaffold has at most 128 letters of A C G T U")
+    return b
+
+
+def _fold_limits(max_starts, max_self, max_scaffold, max_seed):
+    """The four limits as integers, once: None is FOLD_NO_LIMIT; a limit is a whole number 0..32."""
+    out = []
+    for name, v in (("max_fold_starts", max_starts), ("max_fold_self", max_self), ("max_fold_scaffold", max_scaffold),
+                    ("max_fold_seed", max_seed)):
+        if v is None:
+            out.append(FOLD_NO_LIMIT)
+            continue
+        i = int(v)
+        if i != v or not (0 <= i <= 32 or i == FOLD_NO_LIMIT):
+            raise ValueError("%s is a whole number 0 .. 32, or None for no limit" % name)
+        out.append(i)
+    return tuple(out)
+
+
+def fold_text(spacer, shape, scaffold=None):
+    """vsc_fold_text: the row (w0, w1) of one spacer of shape.proto_len letters (A C G T U, any case) against itself and a
+    scaffold text, on the host, by the function the kernels call - for a guide list without a genome.  A spacer letter other
+    than A C G T U gives (FOLD_UNDEFINED, FOLD_UNDEFINED); unpack_fold_row names the fields."""
+    shape = _fold_shape(shape)
+    b = spacer if isinstance(spacer, bytes) else spacer.encode()
+    sc = _fold_scaffold(scaffold)
+    if len(b) != shape.proto_len:
+        raise ValueError("the spacer has %d letters, the shape's spacer %d" % (len(b), shape.proto_len))
+    sh = shape._struct()
+    row = (C.c_uint32 * 2)()
+    check(lib().vsc_fold_text(b, len(b), sc, len(sc), C.byref(sh), row))
+    return int(row[0]), int(row[1])
+
+
+def unpack_fold_row(rows):
+    """The fields of fold rows (one (w0, w1) pair or an array of shape (n, 2)) as a dict of integer arrays: starts,
+    self_starts, scaf_starts, seed_paired, self_longest, scaf_longest, and defined (bool; the other fields of an undefined row
+    are 0)."""
+    a = np.asarray(rows, dtype=np.uint32)
+    flat = a.reshape(-1, 2)
+    w0, w1 = flat[:, 0], flat[:, 1]
+    defined = ~((w0 == FOLD_UNDEFINED) & (w1 == FOLD_UNDEFINED))
+    z = np.uint32(0)
+    out = {"starts": np.where(defined, w0 & 0xFF, z), "self_starts": np.where(defined, (w0 >> 8) & 0xFF, z),
+           "scaf_starts": np.where(defined, (w0 >> 16) & 0xFF, z), "seed_paired": np.where(defined, w0 >> 24, z),
+           "self_longest": np.where(defined, w1 & 0xFF, z), "scaf_longest": np.where(defined, (w1 >> 8) & 0xFF, z),
+           "defined": defined}
+    if a.ndim == 1:
+        return {k: (bool(v[0]) if k == "defined" else int(v[0])) for k, v in out.items()}
+    return out
+
+
+def pack_fold_row(starts, self_starts, scaf_starts, seed_paired, self_longest, scaf_longest):
+    """(w0, w1) of the six fields: the inverse of unpack_fold_row on a defined row."""
+    return (int(starts) | int(self_starts) << 8 | int(scaf_starts) << 16 | int(seed_paired) << 24,
+            int(self_longest) | int(scaf_longest) << 8)
+
+
 PICK_NONE = _lib.PICK_NONE  # a picks entry beyond counts[t]; the rank of a candidate that is not picked
 
 
@@ -1354,13 +1476,14 @@ def pick_host(contigs, loci, target, key, n_targets, shape, rank=False):
 
 
 # The fixed quantisation of the columns a design call (and the tools' -b) can rank by: (bits, what the column is made from)
-PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20}
+PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20, "fold": 6}
 
 
 def pick_column(name, values):
     """One key column in the tools' fixed quantisation (PICK_COLUMNS bits): mit / table: rint(100 x specificity) of float64
     specificities; eff: the top 20 bits of order_bits of the linear predictors; oof: floor(1000 oof / sum) of (sum, oof)
-    pairs, undefined -> 0; mh: min(sum, 2^20 - 1) of the pairs, undefined -> 0."""
+    pairs, undefined -> 0; mh: min(sum, 2^20 - 1) of the pairs, undefined -> 0; fold: 32 - starts of the fold rows (fewer stems
+    are better), undefined -> 0."""
     if name in ("mit", "table"):  # (NaN and negative values: 0, as the undefined values of the other columns)
         v = np.asarray(values, dtype=np.float64)
         return np.rint(100.0 * np.where(np.isnan(v) | (v <= 0), 0.0, np.minimum(v, 1e6))).astype(np.uint64)
@@ -1368,12 +1491,14 @@ def pick_column(name, values):
         return order_bits(values) >> np.uint64(44)
     pairs = np.asarray(values, dtype=np.uint32).reshape(-1, 2).astype(np.uint64)
     undefined = pairs[:, 0] == MH_UNDEFINED
+    if name == "fold":
+        return np.where(undefined, np.uint64(0), np.uint64(32) - np.minimum(pairs[:, 0] & np.uint64(0xFF), np.uint64(32))).astype(np.uint64)
     if name == "oof":
         q = np.uint64(1000) * pairs[:, 1] // np.maximum(pairs[:, 0], np.uint64(1))
         return np.where(undefined | (pairs[:, 0] == 0), np.uint64(0), q).astype(np.uint64)
     if name == "mh":
         return np.where(undefined, np.uint64(0), np.minimum(pairs[:, 0], np.uint64(2 ** 20 - 1))).astype(np.uint64)
-    raise ValueError("a pick column is one of mit, table, eff, oof, mh")
+    raise ValueError("a pick column is one of mit, table, eff, oof, mh, fold")
 
 
 EDIT_UNDEFINED = _lib.EDIT_UNDEFINED  # mask and hits of a candidate whose site is undefined
@@ -3036,7 +3161,8 @@ class Genome:
                           max_editable=None, cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None,
                           prime_edits=None, prime_allow_weak=None, variation=None, variants=None, max_variant_cost=None,
                           max_variants_by_zone=None, require_variant_zones=None, hdr=None, hdr_edits=None, hdr_cds=None,
-                          hdr_allow_open=None):
+                          hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None, max_fold_self=None,
+                          max_fold_scaffold=None, max_fold_seed=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -3074,7 +3200,12 @@ class Genome:
         (n_pairs, n_usable) rows (uint32[n, 2], vsc_pattern_guides_hdr) come last of all.  hdr_edits= (contig, pos, del_len, ins)
         rows / hdr_cds= a Cds / hdr_allow_open= (all need hdr=): with edits or hdr_allow_open only the candidates whose context
         is defined and that - with edits - have a usable pair, or with hdr_allow_open=True any pair
-        (vsc_pattern_guides_filter_hdr), after the other families' filters."""
+        (vsc_pattern_guides_filter_hdr), after the other families' filters.
+        fold= a FoldShape whose site_len is the pattern's length (or the name of a preset of FOLD_SHAPES): the candidates' fold
+        rows (uint32[n, 2], vsc_pattern_guides_fold; unpack_fold_row names the fields) come last of all, after the HDR rows.
+        fold_scaffold= the constant part of the guide RNA (at most 128 letters of A C G T U; default: none) / max_fold_starts= /
+        max_fold_self= / max_fold_scaffold= / max_fold_seed= whole numbers 0 .. 32 (all need fold=): with a limit only the
+        candidates whose row is defined and within every limit (vsc_pattern_guides_filter_fold), after the HDR filter."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -3088,6 +3219,7 @@ class Genome:
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, len(p))
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, len(p))
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, len(p))
+        fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -3101,7 +3233,8 @@ class Genome:
                                            (L.vsc_pattern_guides_effects, L.vsc_pattern_guides_filter_effects), pe,
                                            (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime), vr,
                                            (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation), hd,
-                                           (L.vsc_pattern_guides_hdr, L.vsc_pattern_guides_filter_hdr))
+                                           (L.vsc_pattern_guides_hdr, L.vsc_pattern_guides_filter_hdr), fo,
+                                           (L.vsc_pattern_guides_fold, L.vsc_pattern_guides_filter_fold))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -3134,7 +3267,8 @@ class Genome:
         require_effect= / forbid_effect=: as enumerate_pattern; the effect rows come after the edit rows.  prime= /
         prime_edits= / prime_allow_weak=: as enumerate_pattern; the prime rows come after the effect rows.  variation= /
         variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_pattern; only the survivors
-        are searched, and the variation rows come after the prime rows."""
+        are searched, and the variation rows come after the prime rows.  fold= (and its options): as enumerate_pattern; only the
+        survivors are searched, the fold rows come last of the rows, and pick_by= knows the column "fold"."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -3168,13 +3302,14 @@ class Genome:
         rest = list(extra)
         linear = rest.pop(0) if filters.get("efficiency") is not None else None
         pairs = rest.pop(0) if filters.get("microhomology") is not None else None
+        folds = rest[-1] if filters.get("fold") is not None else None
         spec = None
         if table is not None:
             spec = np.array([table_specificity(x) for x in out[2]["score_sum"]], dtype=np.float64)
         regions = Regions(self.packed, targets, rule=filters.get("rule", "overlap"))
         try:
             return tuple(out) + self._pick_found(pick, pick_by, pick_groups, regions, found,
-                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs})
+                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds})
         finally:
             regions.close()
 
@@ -3252,9 +3387,11 @@ class Genome:
         return pairs
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
-                          fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None, hd=None, hd_fns=None):
+                          fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None, hd=None, hd_fns=None, fo=None,
+                          fo_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
-        the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows before the HDR rows.
+        the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows before the HDR rows
+        before the fold rows.
         held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
@@ -3270,6 +3407,8 @@ class Genome:
             self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, rows=False)
         if hd is not None:
             self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, rows=False)
+        if fo is not None:
+            self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -3285,7 +3424,68 @@ class Genome:
             extra += (self._variation_on_handle(held, va, count_fn, va_fns[0], va_fns[1], free_fn, filt=False),)
         if hd is not None:
             extra += (self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, filt=False),)
+        if fo is not None:
+            extra += (self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, filt=False),)
         return extra
+
+    # ---- guide RNA self-complementarity (vsc_*_fold) -------------------------------------------------------------------
+    @staticmethod
+    def _fold_args(shape, scaffold, max_starts, max_self, max_scaffold, max_seed, site_len):
+        """(shape, scaffold bytes, the four limits as integers or None when none is given) - or None without a shape.  The
+        limits become integers here, once."""
+        given = [v is not None for v in (max_starts, max_self, max_scaffold, max_seed)]
+        if shape is None:
+            if scaffold is not None or any(given):
+                raise ValueError("fold_scaffold / max_fold_starts / max_fold_self / max_fold_scaffold / max_fold_seed need fold=shape")
+            return None
+        shape = _fold_shape(shape, "fold")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        limits = _fold_limits(max_starts, max_self, max_scaffold, max_seed) if any(given) else None
+        return shape, _fold_scaffold(scaffold), limits
+
+    def _fold_on_handle(self, held, fo, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _mh_on_handle, for the fold rows: fo = what _fold_args returned.  With limits the handle is first replaced by
+        the filter's result."""
+        shape, scaffold, limits = fo
+        sh = shape._struct()
+        if filt and limits is not None:
+            lim = _lib.FoldLimits(*limits)
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), scaffold, len(scaffold), C.byref(lim), C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        out_rows = np.empty((int(count_fn(held[0])), 2), dtype=np.uint32)
+        st = _lib.FoldStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), scaffold, len(scaffold), ptr(out_rows), C.byref(st)), self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return out_rows
+
+    def fold(self, loci_or_found, shape, scaffold=None, allow_partial=False):
+        """vsc_loci_fold: the fold rows of candidates under a FoldShape (or the name of a preset of FOLD_SHAPES) and a scaffold
+        text (None: empty), computed on the device from the resident planes: (uint32[n, 2], stats) - unpack_fold_row names the
+        fields of a row.  loci_or_found: as Genome.efficiency takes it.  An undefined row is (FOLD_UNDEFINED, FOLD_UNDEFINED);
+        stats counts the candidates by class - defined, invalid, off_contig, not_resident, has_n - and holds kernel_ms and
+        wall_ms.  Raises when a site is not resident on this object (a shard) unless allow_partial=True."""
+        shape = _fold_shape(shape)
+        sc = _fold_scaffold(scaffold)
+        if isinstance(loci_or_found, PatternGuides):
+            loci = loci_or_found.loci
+        elif isinstance(loci_or_found, tuple) and len(loci_or_found) >= 2 and isinstance(loci_or_found[1], np.ndarray) \
+                and loci_or_found[1].dtype == _lib.LOCUS_DTYPE:
+            loci = loci_or_found[1]
+        else:
+            loci = loci_or_found
+        lo = _loci(loci, len(loci))
+        rows = np.empty((len(lo), 2), dtype=np.uint32)
+        st = _lib.FoldStats()
+        sh = shape._struct()
+        check(lib().vsc_loci_fold(self.ctx._h, self._h, ptr(lo), len(lo), C.byref(sh), sc, len(sc), ptr(rows), C.byref(st)), self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        return rows, stats
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
         """vsc_loci_microhomology: the microhomology pairs of candidates under a MicrohomologyShape, computed on the device from
@@ -4005,7 +4205,8 @@ class Genome:
                          min_microhomology=None, edit=None, edit_targets=None, min_editable=None, max_editable=None, cds=None,
                          edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
                          variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
-                         hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None):
+                         hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None,
+                         max_fold_starts=None, max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -4043,7 +4244,12 @@ class Genome:
         (uint32[n, 2], vsc_guides_hdr) come last of all.  hdr_edits= (contig, pos, del_len, ins) rows in any order / hdr_cds= a
         Cds / hdr_allow_open= (all need hdr=): with edits or hdr_allow_open only the candidates whose context is defined and
         that - with edits - have a usable pair, or with hdr_allow_open=True any pair (vsc_guides_filter_hdr), after the other
-        families' filters."""
+        families' filters.
+        fold= a FoldShape with site_len 23 or the name of a preset of FOLD_SHAPES: the candidates' fold rows (uint32[n, 2],
+        vsc_guides_fold; unpack_fold_row names the fields) come last of all, after the HDR rows.  fold_scaffold= the constant part
+        of the guide RNA (at most 128 letters of A C G T U; default: none) / max_fold_starts= / max_fold_self= /
+        max_fold_scaffold= / max_fold_seed= whole numbers 0 .. 32 (all need fold=): with a limit only the candidates whose row is
+        defined and within every limit (vsc_guides_filter_fold), after the HDR filter."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
@@ -4053,11 +4259,12 @@ class Genome:
         pe = self._prime_args(prime, prime_edits, prime_allow_weak, READ_LEN)
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, READ_LEN)
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, READ_LEN)
+        fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None:
+        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None and fo is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -4068,7 +4275,8 @@ class Genome:
                                            (L.vsc_guides_effects, L.vsc_guides_filter_effects), pe,
                                            (L.vsc_guides_prime, L.vsc_guides_filter_prime), vr,
                                            (L.vsc_guides_variation, L.vsc_guides_filter_variation), hd,
-                                           (L.vsc_guides_hdr, L.vsc_guides_filter_hdr))
+                                           (L.vsc_guides_hdr, L.vsc_guides_filter_hdr), fo,
+                                           (L.vsc_guides_fold, L.vsc_guides_filter_fold))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -4103,7 +4311,8 @@ class Genome:
                pick=None, pick_by=None, pick_groups=None, edit=None, edit_targets=None, min_editable=None, max_editable=None,
                cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
                variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
-               hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, **search_options):
+               hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None,
+               max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -4124,7 +4333,10 @@ class Genome:
         variation= / variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_guides; only
         the survivors are searched, and the variation rows come after the prime rows, before (picks, counts).
         hdr= / hdr_edits= / hdr_cds= / hdr_allow_open=: as enumerate_guides; only the survivors are searched, and the HDR rows
-        come after the variation rows, before (picks, counts)."""
+        come after the variation rows, before (picks, counts).
+        fold= / fold_scaffold= / max_fold_starts= / max_fold_self= / max_fold_scaffold= / max_fold_seed=: as enumerate_guides; only
+        the survivors are searched, and the fold rows come after the HDR rows, before (picks, counts); pick_by= then knows the
+        column "fold" (32 - starts, 6 bits: fewer stems are better)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -4136,7 +4348,9 @@ class Genome:
                                       prime_edits=prime_edits, prime_allow_weak=prime_allow_weak, variation=variation,
                                       variants=variants, max_variant_cost=max_variant_cost,
                                       max_variants_by_zone=max_variants_by_zone, require_variant_zones=require_variant_zones,
-                                      hdr=hdr, hdr_edits=hdr_edits, hdr_cds=hdr_cds, hdr_allow_open=hdr_allow_open)
+                                      hdr=hdr, hdr_edits=hdr_edits, hdr_cds=hdr_cds, hdr_allow_open=hdr_allow_open, fold=fold,
+                                      fold_scaffold=fold_scaffold, max_fold_starts=max_fold_starts, max_fold_self=max_fold_self,
+                                      max_fold_scaffold=max_fold_scaffold, max_fold_seed=max_fold_seed)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])
@@ -4145,10 +4359,11 @@ class Genome:
         extra = list(found[3:] if len(found) > 2 and _label_regions(labels, regions) is not None else found[2:])
         linear = extra.pop(0) if efficiency is not None else None
         pairs = extra.pop(0) if microhomology is not None else None
+        folds = extra[-1] if fold is not None else None
         all_rows = rows[0] if isinstance(rows, tuple) else rows
         spec = np.array([mit_specificity(x) for x in all_rows["mit_sum"]], dtype=np.float64)
         return out + self._pick_found(pick, pick_by, pick_groups, regions, (codes, loci),
-                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs})
+                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds})
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)

@@ -131,6 +131,9 @@
 // with --hdr-edits edits.tsv those without a usable pair as well (--hdr-allow-open: without any pair); --hdr-cds cds.bed keeps the
 // blocking substitution synonymous; the -L listing gains the last columns hdrPairs hdrUsable; --hdr-out pairs.tsv (needs
 // --hdr-edits) lists the pairs with their substitutions.
+// --fold SpCas9 | Cas12a | SPEC (needs -E, one device; tools/fold_host.hpp) counts the stems the guide RNA of every found guide can
+// form with itself and with the --fold-scaffold text (at most 128 letters, or @FILE; default: none): the -L listing gains the last
+// columns foldStarts foldSelf foldScaffold foldSeed; --max-fold STARTS[,SELF[,SCAF[,SEED]]] keeps the candidates within the limits.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -147,6 +150,7 @@
 #include "effects_host.hpp"
 #include "prime_host.hpp"
 #include "hdr_host.hpp"
+#include "fold_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
@@ -254,6 +258,12 @@ int main(int argc, char **argv)
         {'=', "hdr-out", "With --hdr-edits: path to the listing of the pairs: #chrom pos guideId dist seedMm protoMm flags subChrom subPos subBase", false},
         {'+', "hdr-cds", "With --hdr: path to the coding segments (.bed, BED6 as --cds): a blocking substitution inside them is synonymous", false},
         {'~', "hdr-allow-open", "With --hdr: keep the candidates with a pair whose repaired allele can be cut again", false, false},
+        {'!', "fold", "With -E: SpCas9 | Cas12a | SITELEN,PROTOSTART,PROTOLEN,STEM,GCMIN,MINLOOP,SEEDSTART,SEEDLEN,FLAGS: how the guide RNA's "
+                      "self-complementarity is counted; the guide listing gains the last columns foldStarts foldSelf foldScaffold foldSeed "
+                      "(one device)", false},
+        {':', "fold-scaffold", "With --fold: the constant part of the guide RNA, 5' to 3', at most 128 letters of A C G T U, or @FILE", false},
+        {';', "max-fold", "With --fold: STARTS[,SELF[,SCAF[,SEED]]] - only the candidates with at most so many stem starts, so long a "
+                          "hairpin stem, so long a scaffold stem and so many paired seed bases (each 0 .. 32, - for no limit)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -672,6 +682,15 @@ int main(int argc, char **argv)
         }
     }
     CdsOfFile hdr_coding;
+    // --fold / --fold-scaffold / --max-fold: the self-complementarity of the found guides
+    FoldOptions fold;
+    {
+        const std::string why = parse_fold_options(opts[66], opts[67], opts[68], discover, devices.size() != 1, (uint32_t)VSC_READ_LEN, &fold);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
 
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
@@ -888,6 +907,13 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            if (fold.limited) {  // --max-fold: the same for the fold limits, after the knock-in FILTER
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_fold(ctx, genome, found, &fold.shape, fold.scaffold.c_str(), (uint32_t)fold.scaffold.size(), &fold.limits, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -934,6 +960,9 @@ int main(int argc, char **argv)
                             r, pp, cap, np, nullptr, nullptr) != VSC_OK)
                         throw std::runtime_error(vsc_last_error(ctx));
                 }, &hdr_rows, &hdr_pairs);
+            std::vector<uint32_t> fold_rows(fold.on ? 2 * vsc_guides_count(found) : 0);  // --fold: the rows
+            if (fold.on && vsc_guides_fold(ctx, genome, found, &fold.shape, fold.scaffold.c_str(), (uint32_t)fold.scaffold.size(), fold_rows.data(), nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -960,7 +989,7 @@ int main(int argc, char **argv)
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
                     const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
                                              (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "") +
-                                             (hdr.on ? hdr_columns(&hdr_rows[2 * i]) : "");
+                                             (hdr.on ? hdr_columns(&hdr_rows[2 * i]) : "") + (fold.on ? fold_columns(&fold_rows[2 * i]) : "");
                     if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
                     else bed6 += line + ecol + '\n';
                 }

@@ -14,6 +14,7 @@
 //   vsc_efficiency.hip     on-target efficiency of candidates
 //   vsc_eff_trees.hip      ... from regression-tree ensembles
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
+//   vsc_fold.hip           self-complementarity of the candidates' guide RNA: hairpin and scaffold stems
 //   vsc_edit.hip           base-editor windows of candidates and their join with targets
 //   vsc_prime.hip          prime-editing extensions of candidates and their join with edits
 //   vsc_variation.hip      known variation under candidates: the join of their sites with variant intervals
@@ -4130,8 +4131,8 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
 
 // ---- the host path of the candidate annotations ----------------------------------------------------------------
 // What the families that annotate candidate guides - linear and tree efficiency, microhomology, edit windows, coding effects,
-// prime editing, variation - do alike on the host: the checks in front of a call over candidates, the filter (staging,
-// run_enumeration, the timing restated), the rows pass, and the join of the rows with a family's table (count pass, scan,
+// prime editing, variation, HDR, the guide RNA's fold - do alike on the host: the checks in front of a call over candidates,
+// the filter (staging, run_enumeration, the timing restated), the rows pass, and the join of the rows with a family's table (count pass, scan,
 // write pass, coverage).  A family keeps its check, its table upload, the fields of its Args, its launchers and its stats;
 // what differs between families enters here as a value or a callable of the family's.
 namespace {
@@ -7058,6 +7059,213 @@ int vsc_pattern_guides_filter_hdr(vsc_ctx *ctx, const vsc_genome *genome, vsc_pa
                                   vsc_pattern_guides **out)
 {
     return hdr_filter(ctx, genome, in, shape, edits, n_e, cds, code, false, allow_open, out, "vsc_pattern_guides_filter_hdr");
+}
+
+}  // extern "C"
+
+// ---- guide RNA self-complementarity (the definition: vsc_fold.h, the kernels: vsc_fold.hip) -----------------------
+namespace {
+
+const char *const kFoldShapeRule =
+    "site_len 16 .. 32, proto_len 12 .. 32 inside the site, stem 3 .. 8, gc_min 0 .. stem, min_loop 0 .. 16, the seed (each 0 .. 16) inside "
+    "the spacer, flags bit 0 only, reserved fields 0";
+
+bool fold_shape_in(const vsc_fold_shape *shape, FoldShape &s)
+{
+    s = FoldShape{shape->site_len, shape->proto_start, shape->proto_len, shape->stem,  shape->gc_min,
+                  shape->min_loop, shape->seed_start,  shape->seed_len,  shape->flags};
+    return !shape->reserved[0] && !shape->reserved[1] && !shape->reserved[2] && fold_shape_valid(s);
+}
+
+// the scaffold text of a call as letters 0 .. 3; false: longer than 128 or another letter
+bool fold_scaffold_in(const char *scaffold, uint32_t m, std::vector<uint8_t> &letters)
+{
+    if (m > kFoldMaxScaffold || (m && !scaffold)) return false;
+    letters.resize(m);
+    for (uint32_t j = 0; j < m; ++j) {
+        const uint32_t b = fold_letter(scaffold[j]);
+        if (b > 3u) return false;
+        letters[j] = (uint8_t)b;
+    }
+    return true;
+}
+
+// The shape, the genome and the scaffold of a fold call, checked on the host; win = the scaffold's windows for the shape's spacer.
+int fold_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_fold_shape *shape, const char *scaffold, uint32_t m, FoldShape &s,
+               std::vector<FoldWindow> &win, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!fold_shape_in(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kFoldShapeRule);
+    std::vector<uint8_t> letters;
+    if (!fold_scaffold_in(scaffold, m, letters)) return fail_in(ctx, VSC_ERR_INVALID, who, "the scaffold: at most 128 letters of A C G T U");
+    win.resize(fold_diagonals(s.proto_len, m));
+    fold_scaffold_windows(letters.data(), m, s.proto_len, win.data());
+    return VSC_OK;
+}
+
+// The windows of a call onto the device, enqueued on the context's stream: into eff_buf, whose efficiency model is forgotten.
+// Every call uploads its own, so no call reads another's scaffold; `win` outlives the call's last synchronise.
+int fold_upload(vsc_ctx *ctx, const std::vector<FoldWindow> &win, const FoldWindow **d_win, uint32_t *n_diag)
+{
+    *d_win = nullptr;
+    *n_diag = (uint32_t)win.size();
+    if (win.empty()) return VSC_OK;
+    ctx->eff_serial = 0;
+    VSC_HIP(ctx, ctx->eff_buf.ensure(win.size() * sizeof(FoldWindow)));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_buf.p, win.data(), win.size() * sizeof(FoldWindow), hipMemcpyHostToDevice, ctx->stream));
+    *d_win = (const FoldWindow *)ctx->eff_buf.p;
+    return VSC_OK;
+}
+
+const CandidateRule kFoldRowsRule{"the shape's site_len must be 23", ~0ull, ""};  // (the scoring itself refuses above 2^40)
+const CandidateRule kFoldFilterRule{"the shape's site_len must be 23", 0xFFFFFFFFull * kFoldTile, "more candidates than 2^32 tiles hold"};
+
+// The rows of the loci `at` into host memory: fold_rows_kernel, one copy back of the rows and one of the class counts.
+int fold_rows_loci(vsc_ctx *ctx, const vsc_genome *genome, const FoldShape &shape, const std::vector<FoldWindow> &win, const CandidateLoci &at,
+                   uint32_t *rows, vsc_fold_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (stats) *stats = vsc_fold_stats{};
+    if (at.n == 0) {
+        ctx->timing = vsc_timing{};
+        return VSC_OK;
+    }
+    FoldArgs a{};
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n = at.n;
+    unsigned long long seen[kEffClasses] = {};
+    float ms = 0;
+    const int rc = score_rows(
+        ctx, at, sizeof(uint2), rows, seen, kEffClasses, &ms, who, [&] { return fold_upload(ctx, win, &a.win, &a.n_diag); },
+        [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+            a.stats = d_stats;
+            a.out = (uint2 *)d_rows;
+            a.loci = d_loci;
+            return launch_fold_rows(a, ctx->n_cus, ctx->fold_groups_per_cu, ctx->stream);
+        });
+    if (rc != VSC_OK) return rc;
+    if (stats) {
+        class_counts(stats, seen);
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    return VSC_OK;
+}
+
+// vsc_guides_fold / vsc_pattern_guides_fold: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int fold_rows_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_fold_shape *shape, const char *scaffold, uint32_t m,
+                     bool need_23, uint32_t *rows, vsc_fold_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    FoldShape s{};
+    std::vector<FoldWindow> win;
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kFoldRowsRule, who, at, &s.site_len,
+                                   [&] { return fold_check(ctx, genome, shape, scaffold, m, s, win, who); }, no_refusal);
+    if (rc != VSC_OK) return rc;
+    return fold_rows_loci(ctx, genome, s, win, at, rows, stats, who);
+    });
+}
+
+// vsc_guides_filter_fold / vsc_pattern_guides_filter_fold: the candidates within the limits
+template <class Guides>
+int fold_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_fold_shape *shape, const char *scaffold, uint32_t m, bool need_23,
+                const vsc_fold_limits *limits, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    FoldShape s{};
+    std::vector<FoldWindow> win;
+    FoldFilterArgs a{};
+    const int rc = filter_front(
+        ctx, in, out, need_23, kFoldFilterRule, who, &s.site_len, [&] { return fold_check(ctx, genome, shape, scaffold, m, s, win, who); },
+        [&]() -> int {
+            if (!limits) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+            a.limits = FoldLimits{limits->max_starts, limits->max_self_longest, limits->max_scaf_longest, limits->max_seed_paired};
+            return fold_limits_valid(a.limits) ? VSC_OK : fail_in(ctx, VSC_ERR_INVALID, who, "a limit is 0 .. 32 or VSC_FOLD_NO_LIMIT");
+        });
+    if (rc != VSC_OK) return rc;
+    const int urc = fold_upload(ctx, win, &a.win, &a.n_diag);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = s;
+    return filter_candidates(ctx, in, a, kFoldTile, out, who, [&](bool write) { return launch_fold_filter(a, write, ctx->stream); });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_fold_groups_per_cu(vsc_ctx *ctx, uint32_t groups)
+{
+    if (!ctx || groups > kFoldMaxGroupsPerCu) return VSC_ERR_INVALID;
+    ctx->fold_groups_per_cu = groups;
+    return VSC_OK;
+}
+
+int vsc_fold_text(const char *spacer, uint32_t n, const char *scaffold, uint32_t m, const vsc_fold_shape *shape, uint32_t *row)
+{
+    if (!spacer || !shape || !row) return VSC_ERR_INVALID;
+    FoldShape s{};
+    if (!fold_shape_in(shape, s) || n != s.proto_len) return VSC_ERR_INVALID;
+    std::vector<uint8_t> letters;
+    if (!fold_scaffold_in(scaffold, m, letters)) return VSC_ERR_INVALID;
+    if (strnlen(spacer, n) != n) return VSC_ERR_INVALID;
+    row[0] = row[1] = kFoldUndefined;
+    uint32_t gh = 0, gl = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t b = fold_letter(spacer[j]);
+        if (b > 3u) return VSC_OK;
+        gh |= (b >> 1) << j;
+        gl |= (b & 1u) << j;
+    }
+    std::vector<FoldWindow> win(fold_diagonals(n, m));
+    fold_scaffold_windows(letters.data(), m, n, win.data());
+    fold_row(gh, gl, FoldScaffold{win.data(), (uint32_t)win.size()}, s, &row[0], &row[1]);
+    return VSC_OK;
+}
+
+int vsc_loci_fold(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_fold_shape *shape, const char *scaffold,
+                  uint32_t m, uint32_t *rows, vsc_fold_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_fold";
+    FoldShape s{};
+    std::vector<FoldWindow> win;
+    const int rc = fold_check(ctx, genome, shape, scaffold, m, s, win, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    return fold_rows_loci(ctx, genome, s, win, CandidateLoci{nullptr, loci, n}, rows, stats, fn);
+    });
+}
+
+int vsc_guides_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_fold_shape *shape, const char *scaffold, uint32_t m,
+                    uint32_t *rows, vsc_fold_stats *stats)
+{
+    return fold_rows_guides(ctx, genome, guides, shape, scaffold, m, true, rows, stats, "vsc_guides_fold");
+}
+
+int vsc_pattern_guides_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_fold_shape *shape, const char *scaffold,
+                            uint32_t m, uint32_t *rows, vsc_fold_stats *stats)
+{
+    return fold_rows_guides(ctx, genome, guides, shape, scaffold, m, false, rows, stats, "vsc_pattern_guides_fold");
+}
+
+int vsc_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_fold_shape *shape, const char *scaffold, uint32_t m,
+                           const vsc_fold_limits *limits, vsc_guides **out)
+{
+    return fold_filter(ctx, genome, in, shape, scaffold, m, true, limits, out, "vsc_guides_filter_fold");
+}
+
+int vsc_pattern_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_fold_shape *shape,
+                                   const char *scaffold, uint32_t m, const vsc_fold_limits *limits, vsc_pattern_guides **out)
+{
+    return fold_filter(ctx, genome, in, shape, scaffold, m, false, limits, out, "vsc_pattern_guides_filter_fold");
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "vsc_efficiency.h"
 #include "vsc_eff_trees.h"
 #include "vsc_mh.h"
+#include "vsc_fold.h"
 #include "vsc_edit.h"
 #include "vsc_variation.h"
 #include "vsc_prime.h"
@@ -635,6 +636,39 @@ struct MhFilterArgs {
 };
 hipError_t launch_mh_score(const MhArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_mh_filter(const MhFilterArgs &args, bool write, hipStream_t stream);
+// vsc_fold.hip (the definition: vsc_fold.h)
+struct FoldArgs {
+    EffPlanes g;
+    FoldShape shape;
+    const FoldWindow *win;        // [n_diag] the scaffold's windows (fold_scaffold_windows), on the device
+    uint32_t n_diag;              // 0: no scaffold
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint2 *out;                   // [n] out: the row, kFoldUndefined twice where the class is not defined
+    unsigned long long *stats;    // [kEffClasses], zeroed before the launch: the kernel adds its candidates per class
+};
+// the filter's two passes, driven by run_enumeration (vsc_api.cpp): tile i of the work list = candidates [i * kFoldTile, ..)
+constexpr uint32_t kFoldTile = 1024;
+struct FoldFilterArgs {
+    EffPlanes g;
+    FoldShape shape;
+    FoldLimits limits;
+    const FoldWindow *win;
+    uint32_t n_diag;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+// groups_per_cu: workgroups per CU the rows kernel's grid is capped at (0: the default, kFoldGroupsPerCu)
+hipError_t launch_fold_rows(const FoldArgs &args, int n_cus, uint32_t groups_per_cu, hipStream_t stream);
+hipError_t launch_fold_filter(const FoldFilterArgs &args, bool write, hipStream_t stream);
+constexpr uint32_t kFoldGroupsPerCu = 8, kFoldMaxGroupsPerCu = 64;
 // vsc_edit.hip (the definition: vsc_edit.h)
 constexpr uint32_t kEditCounts = kEffClasses + 1;  // the classes, then the candidates with a hit
 struct EditArgs {
