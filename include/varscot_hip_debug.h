@@ -102,6 +102,69 @@ int vsc_debug_fold_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
  * depends on it; the tests compare the smallest and a large block, tools/variation_bench.py times them against each other. */
 int vsc_debug_variation_block_bits(vsc_ctx *ctx, uint32_t bits);
 
+/* ---- the bin sort on the caller's records ------------------------------------------------------------------
+ * vsc_debug_sort_records runs the record sink of a search pass (level 0 of the streaming scan, the result's storage, the
+ * "slots allowed" memory, the bin sort with its levels and the finalize kernel) on records the CALLER made, under the
+ * context's current vsc_debug_params: the tests choose the distribution the sort sees - bins of exact sizes, tiles and
+ * segments of chosen lengths, positions at the top of 32 bits, contig tables of any shape.  The product path is untouched. */
+
+/* A genome object that carries a contig table and nothing else (no planes: a sort without rows never reads them; no call
+ * but vsc_debug_sort_records and vsc_genome_free takes it).  contig_off: n_contigs (1 .. 2^24) ascending global start
+ * positions; span: one past the last position of the last contig, at most 2^32.  It also carries the sort's "slots allowed"
+ * memory, as every genome does. */
+int vsc_debug_genome_from_contigs(vsc_ctx *ctx, const uint32_t *contig_off, uint32_t n_contigs, uint64_t span, vsc_genome **out);
+
+typedef struct {
+    uint64_t first_slot; /* first 8-byte slot of the segment */
+    uint32_t n_slots;    /* slots of the segment: records, sentinels, holes */
+    uint32_t guide_base; /* read index of the segment's read 0 */
+} vsc_debug_sort_segment;
+
+typedef struct {
+    /* the position encoding: pos_bits 1 .. 32 meaningful bits of the records' 32-bit position field (they sit at its top:
+     * field = (global position - pos_base) << (32 - pos_bits)); pos_bits 0: as a search derives them from a genome that
+     * covers the table's span - ceil(log2(span)) bits, pos_base 0 */
+    uint32_t pos_bits, pos_base;
+    uint32_t read_bits;  /* SEED form: bits of the read index inside a segment, 0 .. 6 (the sort's key: pos_bits + 1 + read_bits) */
+    /* SEED form - record slots as the seed search leaves them: packed records, sentinels (all ones), and anything at all
+     * in the slots that the fill table leaves out */
+    const uint64_t *slots;
+    uint64_t n_slots;
+    const vsc_debug_sort_segment *segments; /* each ordered on its own; the result is their concatenation */
+    uint32_t n_segments;
+    uint32_t fill_shift;  /* with fill: log2 slots per block, 6 .. 13; every segment starts on a block boundary */
+    const uint32_t *fill; /* NULL, or per block of 1 << fill_shift slots (ceil(n_slots / block) entries) the slots it holds */
+    /* SCAN form (pair_keys != NULL; no segments then) - (key, value) pairs as scan_kernel leaves them: key = (read index
+     * in the pass) << 33 | strand << 32 | global position, value = NM << 23 | mask; they go through level 0 */
+    const uint64_t *pair_keys;
+    const uint32_t *pair_vals;
+    uint64_t n_pairs;
+    uint32_t n_regions;  /* regions of 64 reads the pass has, 1 .. 256: every key's read index is below 64 * n_regions */
+    uint32_t guide_base; /* read index of the pass's read 0 (a multiple of 64) */
+    /* the genome's "slots allowed" memory before the sort (SEED form; the scan form never asks): -1 as earlier calls left
+     * it, 0 forget the permission, 1 give it back - so that a fallback in one call need not change the path of the next */
+    int32_t slots_allowed;
+    uint32_t reserved;
+} vsc_debug_sort_input;
+
+typedef struct {
+    uint64_t n;              /* records of the result */
+    uint64_t bytes;          /* what the sort's kernels moved (vsc_timing.sort_bytes) */
+    uint32_t levels;         /* partition levels run, level 0 not counted (vsc_timing.sort_levels) */
+    uint32_t bin_bits;       /* key bits of the first of them */
+    uint32_t slot_fallbacks; /* slot partitions that overflowed and ran again with the histogram */
+    uint32_t slots_allowed;  /* the genome's memory after the call */
+} vsc_debug_sort_info;
+
+/* Sorts `in`'s records into a result like any search's (freed with vsc_hits_free).  The records themselves are not verified
+ * (a key may repeat, a position may lie behind its contig); what would make a kernel index outside its tables is refused
+ * with VSC_ERR_INVALID before anything is uploaded: a NULL argument, both forms at once, pos_bits > 32, read_bits > 6, a
+ * segment that ends behind n_slots, a fill_shift outside 6 .. 13 or a segment off the block boundaries with a fill table,
+ * n_regions outside 1 .. 256, a guide_base that is no multiple of 64 or that leaves no room for the regions' reads, a key
+ * whose read index is not below 64 * n_regions, 2^32 pairs or more.  Zero segments / zero pairs: an empty result.  `info`
+ * may be NULL; vsc_ctx_timing reports the same figures. */
+int vsc_debug_sort_records(vsc_ctx *ctx, vsc_genome *genome, const vsc_debug_sort_input *in, vsc_debug_sort_info *info, vsc_hits **out);
+
 typedef struct {
     int32_t rccl;             /* -1: RCCL when n > 1 distinct devices; 0: device copies; 1: insist on RCCL (also n = 1);
                                   2: try RCCL also for n = 1, device copies when it cannot be set up */

@@ -575,6 +575,28 @@ class MultiDebugParams(C.Structure):
     _fields_ = [("rccl", C.c_int32), ("rccl_library", C.c_char_p)]
 
 
+# vsc_debug_sort_segment / _input / _info (include/varscot_hip_debug.h): the bin sort on the caller's records
+SORT_SEGMENT_DTYPE = np.dtype([("first_slot", "<u8"), ("n_slots", "<u4"), ("guide_base", "<u4")])
+
+
+class DebugSortInput(C.Structure):
+    _fields_ = [("pos_bits", C.c_uint32), ("pos_base", C.c_uint32), ("read_bits", C.c_uint32), ("slots", C.c_void_p),
+                ("n_slots", C.c_uint64), ("segments", C.c_void_p), ("n_segments", C.c_uint32), ("fill_shift", C.c_uint32),
+                ("fill", C.c_void_p), ("pair_keys", C.c_void_p), ("pair_vals", C.c_void_p), ("n_pairs", C.c_uint64),
+                ("n_regions", C.c_uint32), ("guide_base", C.c_uint32), ("slots_allowed", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class DebugSortInfo(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("bytes", C.c_uint64), ("levels", C.c_uint32), ("bin_bits", C.c_uint32),
+                ("slot_fallbacks", C.c_uint32), ("slots_allowed", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert SORT_SEGMENT_DTYPE.itemsize == 16 and C.sizeof(DebugSortInput) == 96 and C.sizeof(DebugSortInfo) == 32
+
+
 BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32)  # vsc_batch_fn
 ROWS_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)  # vsc_rows_batch_fn
 MULTI_BATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)  # vsc_multi_batch_fn
@@ -877,6 +899,8 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_hdr_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_fold_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_genome_from_contigs", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
+    ("vsc_debug_sort_records", C.c_int, [_vp, _vp, C.POINTER(DebugSortInput), C.POINTER(DebugSortInfo), C.POINTER(_vp)]),
 ]
 
 _lib = None

@@ -4423,6 +4423,57 @@ class Genome:
         check(rc, self.ctx._h)
 
 
+class ContigTable:
+    """A genome object that carries a contig table alone (vsc_debug_genome_from_contigs, include/varscot_hip_debug.h) and
+    sorts the caller's records over it (vsc_debug_sort_records): the tests' way to the bin sort.  contig_off: ascending
+    global start positions; span: one past the last position, at most 2^32."""
+
+    def __init__(self, ctx, contig_off, span):
+        self.ctx = ctx
+        self.contig_off = np.ascontiguousarray(contig_off, dtype=np.uint32)
+        self.span = int(span)
+        self._h = C.c_void_p()
+        check(lib().vsc_debug_genome_from_contigs(ctx._h, ptr(self.contig_off), len(self.contig_off), self.span, C.byref(self._h)), ctx._h)
+        ctx._children.add(self)
+
+    def close(self):
+        if self._h:
+            lib().vsc_genome_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _sort(self, inp, keep):
+        info, h = _lib.DebugSortInfo(), C.c_void_p()
+        check(lib().vsc_debug_sort_records(self.ctx._h, self._h, C.byref(inp), C.byref(info), C.byref(h)), self.ctx._h)
+        del keep  # (the arrays `inp` points into lived until here)
+        return Hits(self, h, None), info.as_dict()
+
+    def sort_slots(self, slots, segments, read_bits, pos_bits=0, pos_base=0, fill=None, fill_shift=0, slots_allowed=-1):
+        """Seed form: `slots` (uint64: packed records, sentinels, anything in the holes of `fill`), `segments`
+        (_lib.SORT_SEGMENT_DTYPE).  Returns (Hits, info dict: n, bytes, levels, bin_bits, slot_fallbacks, slots_allowed)."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint64)
+        segments = np.ascontiguousarray(segments, dtype=_lib.SORT_SEGMENT_DTYPE)
+        fill = None if fill is None else np.ascontiguousarray(fill, dtype=np.uint32)
+        inp = _lib.DebugSortInput(pos_bits=pos_bits, pos_base=pos_base, read_bits=read_bits, slots=ptr(slots), n_slots=len(slots),
+                                  segments=ptr(segments), n_segments=len(segments), fill=ptr(fill), fill_shift=fill_shift,
+                                  slots_allowed=slots_allowed)
+        return self._sort(inp, (slots, segments, fill))
+
+    def sort_pairs(self, keys, vals, n_regions, guide_base=0, pos_bits=0, pos_base=0):
+        """Scan form: (key, value) pairs as the streaming scan leaves them, through level 0.  Returns as sort_slots."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        assert len(keys) == len(vals)
+        inp = _lib.DebugSortInput(pos_bits=pos_bits, pos_base=pos_base, pair_keys=ptr(keys), pair_vals=ptr(vals), n_pairs=len(keys),
+                                  n_regions=n_regions, guide_base=guide_base, slots_allowed=-1)
+        return self._sort(inp, (keys, vals))
+
+
 class Hits:
     """Result of one search (vsc_hits): records sorted by (guide, strand, contig, pos)."""
 

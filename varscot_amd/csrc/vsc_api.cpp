@@ -9203,4 +9203,129 @@ int vsc_debug_site_table_ms(const vsc_ctx *ctx, double *score_ms, double *select
     return VSC_OK;
 }
 
+int vsc_debug_genome_from_contigs(vsc_ctx *ctx, const uint32_t *contig_off, uint32_t n_contigs, uint64_t span, vsc_genome **out)
+{
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    *out = nullptr;
+    if (!contig_off || n_contigs == 0 || n_contigs > (1u << 24) || span > (1ull << 32) || contig_off[n_contigs - 1] > span)
+        return fail(ctx, VSC_ERR_INVALID, "vsc_debug_genome_from_contigs: bad contig table");
+    std::vector<vsc_contig> table(n_contigs);
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const uint64_t end = c + 1 < n_contigs ? contig_off[c + 1] : span;
+        if (end < contig_off[c]) return fail(ctx, VSC_ERR_INVALID, "vsc_debug_genome_from_contigs: contig starts must ascend");
+        table[c] = vsc_contig{contig_off[c], (uint32_t)std::min<uint64_t>(end - contig_off[c], 0xFFFFFFFFu), 0};
+    }
+    return genome_table_only(ctx, table.data(), n_contigs, out);
+    });
+}
+
+// The record sink of a pass (sort_pass) over a hand-made PassFound: the caller's slots or pairs uploaded into the buffers
+// the search would have left them in.
+int vsc_debug_sort_records(vsc_ctx *ctx, vsc_genome *genome, const vsc_debug_sort_input *in, vsc_debug_sort_info *info, vsc_hits **out)
+{
+    if (!ctx || !out) return VSC_ERR_INVALID;
+    return guarded(ctx, [&]() -> int {
+    const char *const who = "vsc_debug_sort_records";
+    *out = nullptr;
+    if (!genome || !in || genome->ctx != ctx || !genome->d_contig_off || genome->n_contigs == 0) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    const bool scan = in->pair_keys != nullptr || in->pair_vals != nullptr || in->n_pairs != 0;
+    if (scan && (in->slots || in->segments || in->n_slots || in->n_segments || in->fill)) return fail_in(ctx, VSC_ERR_INVALID, who, "both forms at once");
+    if (in->pos_bits > 32 || in->read_bits > (uint32_t)kRegionBits || in->reserved || in->slots_allowed < -1 || in->slots_allowed > 1)
+        return fail_in(ctx, VSC_ERR_INVALID, who, "bad position or read bits");
+    PassFound f;
+    f.max_mm = 0;  // (whose entry of the genome's "slots allowed" memory the call uses)
+    uint64_t span = genome->h_contig_end.back() ? genome->h_contig_end.back() : (1ull << 32);  // (an end of 2^32 wrapped)
+    span = std::max<uint64_t>(span, (uint64_t)genome->h_contig_off.back() + 1);
+    const unsigned pos_bits = in->pos_bits ? in->pos_bits : std::max(1u, ceil_log2(span));
+    f.pos_base = in->pos_bits ? in->pos_base : 0u;
+    f.pos_pad = 32 - pos_bits;
+    size_t fill_words = 0;
+    if (scan) {
+        if (!in->pair_keys || !in->pair_vals) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+        if (in->n_regions < 1 || in->n_regions > (uint32_t)kParts || in->n_pairs >= (1ull << 32) || in->guide_base % kRegionReads ||
+            (uint64_t)in->guide_base + (uint64_t)in->n_regions * kRegionReads > (1ull << 32))
+            return fail_in(ctx, VSC_ERR_INVALID, who, "bad regions");
+        for (uint64_t i = 0; i < in->n_pairs; ++i)
+            if ((in->pair_keys[i] >> kRecKeyBits) >= in->n_regions) return fail_in(ctx, VSC_ERR_INVALID, who, "a key's read lies outside the regions");
+        f.algo = VSC_ALGO_SCAN;
+        f.n_parts = (int)in->n_regions;
+        f.guide_base = in->guide_base;
+        f.cap = std::max<uint64_t>(in->n_pairs, 1);
+        f.n = in->n_pairs;
+        f.key_bits = pos_bits + 1 + kRegionBits;
+        if (f.n > 0) f.segs.push_back(SortSeg{0, 0, 0, (uint32_t)f.n, in->guide_base});
+    } else {
+        if ((in->n_slots && !in->slots) || (in->n_segments && !in->segments)) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+        if (in->fill && (in->fill_shift < 6 || in->fill_shift > 13)) return fail_in(ctx, VSC_ERR_INVALID, who, "bad block size");
+        const uint64_t block_mask = in->fill ? (1ull << in->fill_shift) - 1 : 0;
+        for (uint32_t s = 0; s < in->n_segments; ++s) {
+            const vsc_debug_sort_segment &g = in->segments[s];
+            if (g.first_slot > in->n_slots || g.n_slots > in->n_slots - g.first_slot) return fail_in(ctx, VSC_ERR_INVALID, who, "a segment ends behind the slots");
+            if (g.first_slot & block_mask) return fail_in(ctx, VSC_ERR_INVALID, who, "a segment off the block boundaries");
+        }
+        f.algo = VSC_ALGO_SEED;
+        f.n_parts = (int)in->n_segments;
+        f.cap = in->n_slots + kSortTile;
+        f.key_bits = pos_bits + 1 + in->read_bits;
+        for (uint32_t s = 0; s < in->n_segments; ++s) {
+            const vsc_debug_sort_segment &g = in->segments[s];
+            if (g.n_slots == 0) continue;
+            // the records the sort will find: slots the fill table does not leave out and that hold no sentinel
+            uint64_t real = 0;
+            for (uint64_t i = g.first_slot; i < g.first_slot + g.n_slots; ++i)
+                real += (!in->fill || (i & block_mask) < in->fill[i >> in->fill_shift]) && !(in->slots[i] >> 63);
+            f.segs.push_back(SortSeg{g.first_slot, g.first_slot, f.n, g.n_slots, g.guide_base, s, 0});
+            f.n += real;
+        }
+        if (in->fill) {
+            fill_words = (size_t)((in->n_slots + block_mask) >> in->fill_shift);
+            f.l1.fill_shift = in->fill_shift;
+            f.l1.n_real = f.n;
+        }
+        if (in->slots_allowed >= 0) genome->sort_slots_ok[f.max_mm] = in->slots_allowed != 0;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvPassStart], ctx->stream));
+    VSC_HIP(ctx, ctx->keys_a.ensure(f.cap * sizeof(uint64_t)));
+    if (scan) {
+        VSC_HIP(ctx, ctx->vals_a.ensure(f.cap * sizeof(uint32_t)));
+        if (f.n) {
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->keys_a.p, in->pair_keys, f.n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->vals_a.p, in->pair_vals, f.n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        }
+    } else {
+        if (in->n_slots) VSC_HIP(ctx, hipMemcpyAsync(ctx->keys_a.p, in->slots, in->n_slots * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        if (fill_words) {
+            VSC_HIP(ctx, ctx->seed_fill.ensure(fill_words * sizeof(uint32_t)));
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->seed_fill.p, in->fill, fill_words * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            f.l1.fill = (const uint32_t *)ctx->seed_fill.p;
+        }
+    }
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSearchStart], ctx->stream));
+    VSC_HIP(ctx, hipEventRecord(ctx->ev[kEvSearchEnd], ctx->stream));
+    std::unique_ptr<vsc_hits, int (*)(vsc_hits *)> hits(new (std::nothrow) vsc_hits(), vsc_hits_free);
+    if (!hits) return fail_in(ctx, VSC_ERR_NOMEM, who, "out of host memory");
+    hits->ctx = ctx;
+    vsc_timing t{};
+    t.algorithm = (uint32_t)f.algo;
+    t.hits = f.n;
+    const int rc = sort_pass(ctx, genome, f, hits.get(), 0, 0, t);
+    if (rc != VSC_OK) return rc;
+    hits->n = f.n;
+    if (f.n == 0) hits->host_valid = true;
+    ctx->timing = t;
+    if (info) {
+        info->n = f.n;
+        info->bytes = t.sort_bytes;
+        info->levels = t.sort_levels;
+        info->bin_bits = t.sort_bin_bits;
+        info->slot_fallbacks = t.sort_fallbacks;
+        info->slots_allowed = genome->sort_slots_ok[f.max_mm] ? 1u : 0u;
+    }
+    *out = hits.release();
+    return VSC_OK;
+    });
+}
+
 }  // extern "C"
