@@ -2895,6 +2895,123 @@ int vsc_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *i
 int vsc_pattern_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_fold_shape *shape,
                                    const char *scaffold, uint32_t m, const vsc_fold_limits *limits, vsc_pattern_guides **out);
 
+/* ---- restriction sites and IUPAC motifs in candidate guides ------------------------------------- */
+/*
+ * "Can this guide be cloned with this enzyme, and can its edit be seen in a digest?": the recognition sites of restriction
+ * enzymes - short IUPAC motifs in general - in the cloned construct of a candidate (the spacer between the vector's flanks)
+ * and in its genomic context, at the cut and elsewhere.  A word anywhere in a text, which no model of the other families can
+ * express.  This text is normative; everything is integer.  Letters are A C G T = 0 .. 3, and U is read as T.
+ *
+ * SHAPE     site_len 16 .. 32;  up, down 0 .. 16 with C = up + site_len + down <= 64 (the genomic context, as the efficiency
+ *           shape's);  proto_start, proto_len 12 .. 32 with proto_start + proto_len <= site_len (the spacer, n = proto_len, as the
+ *           fold shape's);  cut_start, cut_len 1 .. 16 in SITE positions with cut_start + cut_len <= site_len: the CUT ZONE, the
+ *           site positions an indel at the cut is expected to change (SpCas9 23-mer: 16, 2 - the two bases beside the bond 3 bp
+ *           from the PAM; Cas12a 27-mer TTTV + 23: 21, 6 - the staggered cuts);  every reserved field 0.
+ * FLANKS    left a letters, right b letters, a, b 0 .. 16, A C G T U in any case, anything else refused: the vector's text on
+ *           either side of the cloned spacer, 5' to 3' in the spacer's orientation.  The launch's, not the candidate's.  The
+ *           library ships none.
+ * MOTIFS    M 1 .. 63 motifs; motif m = IUPAC text of len 2 .. 16 (A C G T U R Y S W K M B D H V N, any case; not every letter
+ *           N) and flags bit 0 BOTH_STRANDS; every other bit 0.  PATTERNS(m) = { text } and, under BOTH_STRANDS, its reverse
+ *           complement (IUPAC complement letter by letter, reversed); a palindrome has one pattern.  The library ships none.
+ * GENOMIC   x[0, C) = the context of locus (c, p, strand) in read orientation - the efficiency CONTEXT under (up, site_len,
+ *           down); CLASS as EffClass, in its order (off_contig can occur when up or down > 0).
+ * CONSTRUCT y[0, a + n + b) = left + x[up + proto_start, up + proto_start + n) + right.
+ * OCC(t, P) the starts q with q + |P| <= |t| and t[q + k] in the letter set of P[k] for every k.  |P| > |t|: none.
+ * Z         [z0, z1) = [up + cut_start, up + cut_start + cut_len) in context positions.
+ * construct bit m  iff  OCC(y, P) is not empty for some P in PATTERNS(m)
+ * cut       bit m  iff  some q in OCC(x, P), P in PATTERNS(m), has q < z1 and q + |P| > z0   (the occurrence overlaps Z)
+ * elsewhere bit m  iff  some q in OCC(x, P), P in PATTERNS(m), has q >= z1 or q + |P| <= z0
+ * ROW       three uint64 per candidate: construct, cut, elsewhere; bits M .. 63 are 0.  All three 0xFFFFFFFFFFFFFFFF
+ *           (VSC_MOTIF_UNDEFINED) unless the class is defined - M <= 63 keeps that apart from every defined row.
+ * TOTALS    optional, 3 M uint64: totals[3 m], [3 m + 1], [3 m + 2] = the number of defined candidates with motif m's construct,
+ *           cut and cut-only (cut & ~elsewhere) bit.
+ * FILTER    limits forbid_construct, forbid_context, require_cut (uint64 masks; a bit >= M set: refused), flags bit 0 CUT_ONLY:
+ *           keep iff defined and construct & forbid_construct == 0 and (cut | elsewhere) & forbid_context == 0 and
+ *           (require_cut == 0 or X & require_cut != 0), X = cut, under CUT_ONLY cut & ~elsewhere.  Survivors keep their order.
+ *
+ * Device, host (vsc_motif_text) and the definition restated on strings agree to the bit.
+ *
+ * vsc_motif_text gives the row of one context text of c_len = C letters on the host, with the very function the kernels call -
+ * for users who hold a guide list and no genome (up = down = 0 and the site as the text).  A context letter other than
+ * A C G T U gives the undefined row (VSC_OK); a shape outside SHAPE, c_len != C, a text shorter than c_len, bad flanks or
+ * motifs are VSC_ERR_INVALID.
+ *
+ * vsc_loci_motifs: rows[3 i], [3 i + 1], [3 i + 2] = construct, cut, elsewhere of loci[i] (host arrays, n entries).  One upload,
+ * one kernel, one copy back.  totals is optional (host, 3 M entries, written whole).  stats is optional: the candidates by
+ * class (they add up to n), the candidates with any construct, any cut and any cut-only bit, the kernel's time and the call's
+ * wall time in milliseconds.  n == 0: VSC_OK, nothing is launched (totals and stats are zeroed).  vsc_guides_motifs takes the
+ * candidates where they lie on the device and requires site_len == 23 (else VSC_ERR_INVALID); the host-only object of
+ * vsc_multi_guides_enumerate goes the vsc_loci_motifs way.  vsc_pattern_guides_motifs is the same for vsc_pattern_guides:
+ * site_len is the pattern's length, which the CALLER vouches for.
+ * VSC_ERR_INVALID, before anything is written: a shape outside SHAPE, a non-zero reserved field, a flank longer than 16 or with
+ * a bad letter, M outside 1 .. 63, a motif's len outside 2 .. 16, a bad motif letter, an all-N motif, an unknown flag, a genome
+ * or an object of another context, a NULL where a count says there is something (shape, motifs, rows with n > 0, a flank with
+ * a letter count > 0).
+ *
+ * vsc_guides_filter_motifs / vsc_pattern_guides_filter_motifs: *out = the candidates of `in` that pass FILTER - codes and loci
+ * copied unchanged, in the input's order; `in` stays as it is.  Count pass, scan, write pass over tiles of 1 024 candidates: no
+ * append atomic, the bytes depend on the input, the shape, the flanks, the motifs and the limits only.  A limits bit at or
+ * above M, an unknown limits flag or a non-zero reserved field: VSC_ERR_INVALID.
+ *
+ * vsc_ctx_timing afterwards: as after the efficiency calls (24 bytes written per candidate).  The scratch is the efficiency
+ * calls'; vsc_ctx_release_scratch gives it back.
+ *
+ * Not offered: a shipped enzyme list or vector; motifs beyond 16 letters or more than 63 per call (call twice); uniqueness of a
+ * site over an amplicon wider than the 64-base context; sites made or destroyed by an HDR or prime edit, which belong to those
+ * pairs; a vsc_multi_* entry (for the reason given above for the efficiency calls).
+ */
+#define VSC_MOTIF_UNDEFINED 0xFFFFFFFFFFFFFFFFull
+#define VSC_MOTIF_BOTH_STRANDS 1u
+#define VSC_MOTIF_CUT_ONLY 1u
+typedef struct {
+    char text[16]; /* len letters; the rest is not read */
+    uint32_t len;
+    uint32_t flags;
+} vsc_motif;
+typedef struct {
+    uint32_t up, site_len, down;
+    uint32_t proto_start, proto_len;
+    uint32_t cut_start, cut_len;
+    uint32_t reserved[5]; /* 0 */
+} vsc_motif_shape;
+typedef struct {
+    uint64_t forbid_construct, forbid_context, require_cut;
+    uint32_t flags;
+    uint32_t reserved; /* 0 */
+} vsc_motif_limits;
+typedef struct {
+    uint64_t defined, invalid, off_contig, not_resident, has_n;
+    uint64_t any_construct, any_cut, any_cut_only;
+    double kernel_ms, wall_ms;
+    uint64_t reserved[2]; /* 0 */
+} vsc_motif_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_motif) == 24 && sizeof(vsc_motif_shape) == 48 && sizeof(vsc_motif_limits) == 32 && sizeof(vsc_motif_stats) == 96,
+              "vsc_motif_* layout");
+#else
+_Static_assert(sizeof(vsc_motif) == 24 && sizeof(vsc_motif_shape) == 48 && sizeof(vsc_motif_limits) == 32 && sizeof(vsc_motif_stats) == 96,
+               "vsc_motif_* layout");
+#endif
+int vsc_motif_text(const char *context /* c_len letters */, uint32_t c_len, const char *left /* a letters */, uint32_t a,
+                   const char *right /* b letters */, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, const vsc_motif_shape *shape,
+                   uint64_t *row /* 3 */);
+int vsc_loci_motifs(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host */, uint64_t n, const vsc_motif_shape *shape,
+                    const char *left, uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs,
+                    uint64_t *rows /* host, 3 n */, uint64_t *totals /* optional: host, 3 n_motifs */, vsc_motif_stats *stats /* optional */);
+int vsc_guides_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_motif_shape *shape, const char *left, uint32_t a,
+                      const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, uint64_t *rows /* host, three per candidate */,
+                      uint64_t *totals /* optional */, vsc_motif_stats *stats /* optional */);
+int vsc_pattern_guides_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_motif_shape *shape, const char *left,
+                              uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs,
+                              uint64_t *rows /* host, three per candidate */, uint64_t *totals /* optional */,
+                              vsc_motif_stats *stats /* optional */);
+int vsc_guides_filter_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_motif_shape *shape, const char *left, uint32_t a,
+                             const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, const vsc_motif_limits *limits,
+                             vsc_guides **out);
+int vsc_pattern_guides_filter_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_motif_shape *shape,
+                                     const char *left, uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs,
+                                     const vsc_motif_limits *limits, vsc_pattern_guides **out);
+
 /* ---- several devices, streamed + scored on the owning shard ------------------------------------------------ */
 /*
  * The streamed search of vsc_search_stream over the device set (BASELINE configuration 5: "100 000 guides streamed ... +

@@ -96,6 +96,9 @@ int vsc_debug_hdr_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
 /* The workgroups per CU that fold_rows_kernel's grid (vsc_*_fold) is capped at: 0 = the default (8), 1 .. 64.  The
  * kernel is grid-stride: no output bit depends on it. */
 int vsc_debug_fold_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
+/* The workgroups per CU that motif_rows_kernel's grid (vsc_*_motifs) is capped at: 0 = the default (8), 1 .. 64.  The
+ * kernel is grid-stride and its counts are sums of integers: no output bit depends on it. */
+int vsc_debug_motif_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
 
 /* The block of the variation lookup's table on this context: log2 of the global positions per entry, 4 .. 32, or 0 =
  * the default (8).  At 32 the table has one block and the lookup is the plain lower bound over all variants.  No output bit

@@ -362,6 +362,42 @@ class FoldStats(MhStats):
 
 assert C.sizeof(FoldShapeStruct) == 48 and C.sizeof(FoldLimits) == 16 and C.sizeof(FoldStats) == 64
 
+MOTIF_UNDEFINED = 0xFFFFFFFFFFFFFFFF  # VSC_MOTIF_UNDEFINED: all three words of a candidate whose class is not defined
+MOTIF_BOTH_STRANDS = 1  # VSC_MOTIF_BOTH_STRANDS
+MOTIF_CUT_ONLY = 1  # VSC_MOTIF_CUT_ONLY
+
+
+class MotifStruct(C.Structure):
+    """vsc_motif: an IUPAC text of len 2 .. 16 letters and the flags (bit 0: its reverse complement counts too)."""
+    _fields_ = [("text", C.c_char * 16), ("len", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MotifShapeStruct(C.Structure):
+    """vsc_motif_shape: the genomic context (up, site_len, down), the spacer and the cut zone in site positions."""
+    _fields_ = [("up", C.c_uint32), ("site_len", C.c_uint32), ("down", C.c_uint32), ("proto_start", C.c_uint32),
+                ("proto_len", C.c_uint32), ("cut_start", C.c_uint32), ("cut_len", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class MotifLimits(C.Structure):
+    """vsc_motif_limits: the motifs (bit masks) a kept candidate may not hold in its construct / in its genomic context, those of
+    which it must hold one at the cut, and the flags (bit 0: at the cut and nowhere else in the context)."""
+    _fields_ = [("forbid_construct", C.c_uint64), ("forbid_context", C.c_uint64), ("require_cut", C.c_uint64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class MotifStats(C.Structure):
+    """vsc_motif_stats: the candidates of a call by class (the five counts add up to n), those with any construct, any cut and
+    any cut-only bit, the kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("invalid", C.c_uint64), ("off_contig", C.c_uint64), ("not_resident", C.c_uint64),
+                ("has_n", C.c_uint64), ("any_construct", C.c_uint64), ("any_cut", C.c_uint64), ("any_cut_only", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+assert C.sizeof(MotifStruct) == 24 and C.sizeof(MotifShapeStruct) == 48 and C.sizeof(MotifLimits) == 32 and C.sizeof(MotifStats) == 96
+
 PICK_NONE = 0xFFFFFFFF  # VSC_PICK_NONE: a picks entry beyond counts[t], the rank of a candidate that is not picked
 
 
@@ -865,6 +901,18 @@ SYMBOLS = [
                                          C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_fold", C.c_int, [_vp, _vp, _vp, C.POINTER(FoldShapeStruct), C.c_char_p, C.c_uint32, C.POINTER(FoldLimits),
                                                  C.POINTER(_vp)]),
+    ("vsc_motif_text", C.c_int, [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32,
+                                 C.POINTER(MotifShapeStruct), _vp]),
+    ("vsc_loci_motifs", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(MotifShapeStruct), C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32, _vp, _vp,
+                                  C.POINTER(MotifStats)]),
+    ("vsc_guides_motifs", C.c_int, [_vp, _vp, _vp, C.POINTER(MotifShapeStruct), C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32, _vp, _vp,
+                                    C.POINTER(MotifStats)]),
+    ("vsc_pattern_guides_motifs", C.c_int, [_vp, _vp, _vp, C.POINTER(MotifShapeStruct), C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32, _vp, _vp,
+                                            C.POINTER(MotifStats)]),
+    ("vsc_guides_filter_motifs", C.c_int, [_vp, _vp, _vp, C.POINTER(MotifShapeStruct), C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32,
+                                           C.POINTER(MotifLimits), C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_motifs", C.c_int, [_vp, _vp, _vp, C.POINTER(MotifShapeStruct), C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.POINTER(MotifStruct), C.c_uint32,
+                                                   C.POINTER(MotifLimits), C.POINTER(_vp)]),
     ("vsc_variation_host", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp,
                                      C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     ("vsc_loci_variation", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(VariationShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
@@ -898,6 +946,7 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_hdr_bitmap", C.c_int, [_vp, C.c_int]),
     ("vsc_debug_hdr_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_fold_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_motif_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_genome_from_contigs", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_sort_records", C.c_int, [_vp, _vp, C.POINTER(DebugSortInput), C.POINTER(DebugSortInfo), C.POINTER(_vp)]),

@@ -1390,6 +1390,187 @@ def pack_fold_row(starts, self_starts, scaf_starts, seed_paired, self_longest, s
             int(self_longest) | int(scaf_longest) << 8)
 
 
+MOTIF_UNDEFINED = _lib.MOTIF_UNDEFINED  # all three words of a candidate whose motif row is undefined
+MOTIF_BOTH_STRANDS = _lib.MOTIF_BOTH_STRANDS
+MOTIF_CUT_ONLY = _lib.MOTIF_CUT_ONLY
+_MOTIF_RULE = ("a motif shape has site_len 16..32, up and down 0..16 with a context of at most 64 bases, a spacer of 12..32 bases inside the "
+               "site and a cut zone of 1..16 bases inside the site")
+_MOTIF_LETTERS = b"ACGTURYSWKMBDHVNacgturyswkmbdhvn"
+
+
+class MotifShape:
+    """vsc_motif_shape: where motifs are looked for.  site_len 16..32 is the candidates' length (23 for enumerate_guides', the
+    pattern's for enumerate_pattern's); up / down 0..16 are the bases of genomic context in front of and behind the site (read
+    orientation; the context has at most 64 bases); spacer = (start, length) in read positions of the site, length 12..32: the
+    bases that are cloned between the flanks; cut = (start, length) in SITE positions, length 1..16: the cut zone, the positions
+    an indel at the cut is expected to change.  MOTIF_SHAPES holds "SpCas9" and "Cas12a" with 16 bases of context a side: shapes
+    only, the motifs and the flanks are the caller's.  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, spacer=(0, 20), cut=(16, 2), up=0, down=0, validate=True):
+        self.site_len, self.up, self.down = int(site_len), int(up), int(down)
+        self.proto_start, self.proto_len = int(spacer[0]), int(spacer[1])
+        self.cut_start, self.cut_len = int(cut[0]), int(cut[1])
+        self.reserved = (0, 0, 0, 0, 0)
+        if validate and not self.valid():
+            raise ValueError(_MOTIF_RULE)
+
+    @property
+    def context_len(self):
+        return self.up + self.site_len + self.down
+
+    def valid(self):
+        return (16 <= self.site_len <= 32 and 0 <= self.up <= 16 and 0 <= self.down <= 16 and self.context_len <= 64
+                and 12 <= self.proto_len <= 32 and 0 <= self.proto_start and self.proto_start + self.proto_len <= self.site_len
+                and 1 <= self.cut_len <= 16 and 0 <= self.cut_start and self.cut_start + self.cut_len <= self.site_len
+                and tuple(self.reserved) == (0, 0, 0, 0, 0))
+
+    def _struct(self):
+        s = _lib.MotifShapeStruct(self.up, self.site_len, self.down, self.proto_start, self.proto_len, self.cut_start, self.cut_len)
+        for i, v in enumerate(self.reserved):
+            s.reserved[i] = int(v)
+        return s
+
+    def __repr__(self):
+        return "MotifShape(site_len=%d, spacer=(%d, %d), cut=(%d, %d), up=%d, down=%d)" % (
+            self.site_len, self.proto_start, self.proto_len, self.cut_start, self.cut_len, self.up, self.down)
+
+
+MOTIF_SHAPES = {"SpCas9": MotifShape(23, (0, 20), (16, 2), 16, 16), "Cas12a": MotifShape(27, (4, 23), (21, 6), 16, 16)}
+
+
+def _motif_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in MOTIF_SHAPES:
+            raise ValueError("%s names one of %s, or is a MotifShape" % (what, ", ".join(sorted(MOTIF_SHAPES))))
+        shape = MOTIF_SHAPES[shape]
+    if not isinstance(shape, MotifShape):
+        raise ValueError("%s must be a MotifShape or the name of a preset" % what)
+    return shape
+
+
+class MotifSet:
+    """A checked list of motifs that keeps their names: motif m is bit m of every mask.  names, texts (bytes) and both (bool)
+    are parallel lists; mask() turns names into a bit mask; made by motifs()."""
+
+    def __init__(self, names, texts, both, flags=None):
+        self.names, self.texts, self.both = list(names), list(texts), list(both)
+        self.flags = list(flags) if flags is not None else [MOTIF_BOTH_STRANDS if b else 0 for b in self.both]
+
+    def __len__(self):
+        return len(self.names)
+
+    def mask(self, which, what="a motif mask"):
+        """The bit mask of `which`: None -> 0, an integer below 2^len as it is, a name or a list of names."""
+        if which is None:
+            return 0
+        if isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+            m = int(which)
+            if m < 0 or m >> len(self):
+                raise ValueError("%s has a bit at or above the number of motifs (%d)" % (what, len(self)))
+            return m
+        m = 0
+        for name in ([which] if isinstance(which, str) else list(which)):
+            if name not in self.names:
+                raise ValueError("%s names %r, which is no motif of the set" % (what, name))
+            m |= 1 << self.names.index(name)
+        return m
+
+    def names_of(self, mask):
+        return [n for i, n in enumerate(self.names) if (int(mask) >> i) & 1]
+
+    def _array(self):
+        arr = (_lib.MotifStruct * max(len(self), 1))()
+        for i, (t, f) in enumerate(zip(self.texts, self.flags)):
+            arr[i].text = t[:16]
+            arr[i].len = len(t)
+            arr[i].flags = int(f)
+        return arr
+
+
+def motifs(entries, validate=True):
+    """A MotifSet out of (name, text[, both_strands]) entries: 1..63 motifs, a text of 2..16 IUPAC letters (A C G T U R Y S W
+    K M B D H V N, any case), not every letter N, names that differ; both_strands (default True) counts the reverse complement
+    too.  validate=False passes the entries to the library as they are (tests)."""
+    names, texts, both = [], [], []
+    for e in entries:
+        e = tuple(e)
+        if validate and len(e) not in (2, 3):
+            raise ValueError("a motif is (name, text) or (name, text, both_strands)")
+        t = e[1] if isinstance(e[1], bytes) else str(e[1]).encode()
+        if validate:
+            if not 2 <= len(t) <= 16:
+                raise ValueError("the motif %r has %d letters; a motif has 2..16" % (e[0], len(t)))
+            if any(c not in _MOTIF_LETTERS for c in t):
+                raise ValueError("the motif %r holds a letter that is no IUPAC letter" % (e[0],))
+            if all(c in b"Nn" for c in t):
+                raise ValueError("the motif %r is N alone" % (e[0],))
+            if str(e[0]) in names:
+                raise ValueError("the motif name %r occurs twice" % (e[0],))
+        names.append(str(e[0]))
+        texts.append(t)
+        both.append(bool(e[2]) if len(e) > 2 else True)
+    if validate and not 1 <= len(names) <= 63:
+        raise ValueError("a motif set has 1..63 motifs, not %d" % len(names))
+    return MotifSet(names, texts, both)
+
+
+def _motif_set(m, what="motif_set"):
+    if isinstance(m, MotifSet):
+        return m
+    if m is None:
+        raise ValueError("%s is a MotifSet (motifs(...)) or a list of (name, text[, both_strands])" % what)
+    return motifs(m)
+
+
+def _motif_flank(text, what, validate=True):
+    """A flank of a call as bytes (None: empty).  At most 16 letters of A C G T U, in any case."""
+    if text is None:
+        return b""
+    b = text if isinstance(text, bytes) else str(text).encode()
+    if validate and (len(b) > 16 or any(c not in b"ACGTUacgtu" for c in b)):
+        raise ValueError("%s has at most 16 letters of A C G T U" % what)
+    return b
+
+
+def motif_text(context, shape, motif_set, left=None, right=None):
+    """vsc_motif_text: the row (construct, cut, elsewhere) of one context of shape.context_len letters (A C G T U, any case; read
+    orientation) under a MotifSet and the flanks, on the host, by the function the kernels call - for a guide list without a
+    genome.  A context letter other than A C G T U gives (MOTIF_UNDEFINED,) * 3; unpack_motif_row names the bits."""
+    shape = _motif_shape(shape)
+    ms = _motif_set(motif_set)
+    b = context if isinstance(context, bytes) else context.encode()
+    if len(b) != shape.context_len:
+        raise ValueError("the context has %d letters, the shape's context %d" % (len(b), shape.context_len))
+    lf, rf = _motif_flank(left, "left"), _motif_flank(right, "right")
+    sh = shape._struct()
+    row = (C.c_uint64 * 3)()
+    check(lib().vsc_motif_text(b, len(b), lf, len(lf), rf, len(rf), ms._array(), len(ms), C.byref(sh), row))
+    return int(row[0]), int(row[1]), int(row[2])
+
+
+def unpack_motif_row(rows, motif_set=None):
+    """The masks of motif rows (one (construct, cut, elsewhere) triple or an array of shape (n, 3)) as a dict: construct, cut,
+    elsewhere, cut_only (cut & ~elsewhere) and defined (bool; the masks of an undefined row are 0).  With a MotifSet also
+    construct_names, cut_names, elsewhere_names and cut_only_names: the motifs' names per set bit (a list for one row, a list
+    of lists for an array)."""
+    a = np.asarray(rows, dtype=np.uint64)
+    flat = a.reshape(-1, 3)
+    und = np.uint64(MOTIF_UNDEFINED)
+    defined = ~((flat[:, 0] == und) & (flat[:, 1] == und) & (flat[:, 2] == und))
+    z = np.uint64(0)
+    out = {"construct": np.where(defined, flat[:, 0], z), "cut": np.where(defined, flat[:, 1], z),
+           "elsewhere": np.where(defined, flat[:, 2], z)}
+    out["cut_only"] = out["cut"] & ~out["elsewhere"]
+    keys = list(out)
+    out["defined"] = defined
+    if motif_set is not None:
+        for k in keys:
+            out[k + "_names"] = [motif_set.names_of(v) for v in out[k]]
+    if a.ndim == 1:
+        return {k: (bool(v[0]) if k == "defined" else v[0] if k.endswith("_names") else int(v[0])) for k, v in out.items()}
+    return out
+
+
 PICK_NONE = _lib.PICK_NONE  # a picks entry beyond counts[t]; the rank of a candidate that is not picked
 
 
@@ -1476,19 +1657,26 @@ def pick_host(contigs, loci, target, key, n_targets, shape, rank=False):
 
 
 # The fixed quantisation of the columns a design call (and the tools' -b) can rank by: (bits, what the column is made from)
-PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20, "fold": 6}
+PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20, "fold": 6, "rflp": 6}
 
 
 def pick_column(name, values):
     """One key column in the tools' fixed quantisation (PICK_COLUMNS bits): mit / table: rint(100 x specificity) of float64
     specificities; eff: the top 20 bits of order_bits of the linear predictors; oof: floor(1000 oof / sum) of (sum, oof)
     pairs, undefined -> 0; mh: min(sum, 2^20 - 1) of the pairs, undefined -> 0; fold: 32 - starts of the fold rows (fewer stems
-    are better), undefined -> 0."""
+    are better), undefined -> 0; rflp: min(popcount(cut & ~elsewhere), 63) of the motif rows (more motifs that lie over the
+    cut and nowhere else in the context are better), undefined -> 0."""
     if name in ("mit", "table"):  # (NaN and negative values: 0, as the undefined values of the other columns)
         v = np.asarray(values, dtype=np.float64)
         return np.rint(100.0 * np.where(np.isnan(v) | (v <= 0), 0.0, np.minimum(v, 1e6))).astype(np.uint64)
     if name == "eff":
         return order_bits(values) >> np.uint64(44)
+    if name == "rflp":
+        only = unpack_motif_row(np.asarray(values, dtype=np.uint64).reshape(-1, 3))["cut_only"]
+        count = np.zeros(len(only), dtype=np.uint64)
+        for m in range(63):
+            count += (only >> np.uint64(m)) & np.uint64(1)
+        return np.minimum(count, np.uint64(63))
     pairs = np.asarray(values, dtype=np.uint32).reshape(-1, 2).astype(np.uint64)
     undefined = pairs[:, 0] == MH_UNDEFINED
     if name == "fold":
@@ -1498,7 +1686,7 @@ def pick_column(name, values):
         return np.where(undefined | (pairs[:, 0] == 0), np.uint64(0), q).astype(np.uint64)
     if name == "mh":
         return np.where(undefined, np.uint64(0), np.minimum(pairs[:, 0], np.uint64(2 ** 20 - 1))).astype(np.uint64)
-    raise ValueError("a pick column is one of mit, table, eff, oof, mh, fold")
+    raise ValueError("a pick column is one of mit, table, eff, oof, mh, fold, rflp")
 
 
 EDIT_UNDEFINED = _lib.EDIT_UNDEFINED  # mask and hits of a candidate whose site is undefined
@@ -3162,7 +3350,8 @@ class Genome:
                           prime_edits=None, prime_allow_weak=None, variation=None, variants=None, max_variant_cost=None,
                           max_variants_by_zone=None, require_variant_zones=None, hdr=None, hdr_edits=None, hdr_cds=None,
                           hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None, max_fold_self=None,
-                          max_fold_scaffold=None, max_fold_seed=None):
+                          max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
+                          forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -3205,7 +3394,14 @@ class Genome:
         rows (uint32[n, 2], vsc_pattern_guides_fold; unpack_fold_row names the fields) come last of all, after the HDR rows.
         fold_scaffold= the constant part of the guide RNA (at most 128 letters of A C G T U; default: none) / max_fold_starts= /
         max_fold_self= / max_fold_scaffold= / max_fold_seed= whole numbers 0 .. 32 (all need fold=): with a limit only the
-        candidates whose row is defined and within every limit (vsc_pattern_guides_filter_fold), after the HDR filter."""
+        candidates whose row is defined and within every limit (vsc_pattern_guides_filter_fold), after the HDR filter.
+        motifs= a MotifShape whose site_len is the pattern's length (or the name of a preset of MOTIF_SHAPES) with motif_set= a
+        MotifSet (motifs(...)) or its entries: the candidates' motif rows (uint64[n, 3]: construct, cut, elsewhere;
+        vsc_pattern_guides_motifs; unpack_motif_row names the bits) come last of all, after the fold rows.  motif_left= /
+        motif_right= the vector's text on either side of the cloned spacer (at most 16 letters of A C G T U; default: none) /
+        forbid_motifs= / forbid_context_motifs= / require_cut_motifs= names or bit masks / cut_only= (all need motifs=): with one of
+        them only the candidates whose row is defined and passes FILTER (vsc_pattern_guides_filter_motifs), after the fold
+        filter."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
         iv = None if targets is None else _intervals(targets)
@@ -3220,6 +3416,7 @@ class Genome:
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, len(p))
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, len(p))
         fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, len(p))
+        mo = self._motif_args(motifs, motif_set, motif_left, motif_right, forbid_motifs, forbid_context_motifs, require_cut_motifs, cut_only, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -3234,7 +3431,8 @@ class Genome:
                                            (L.vsc_pattern_guides_prime, L.vsc_pattern_guides_filter_prime), vr,
                                            (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation), hd,
                                            (L.vsc_pattern_guides_hdr, L.vsc_pattern_guides_filter_hdr), fo,
-                                           (L.vsc_pattern_guides_fold, L.vsc_pattern_guides_filter_fold))
+                                           (L.vsc_pattern_guides_fold, L.vsc_pattern_guides_filter_fold), mo,
+                                           (L.vsc_pattern_guides_motifs, L.vsc_pattern_guides_filter_motifs))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -3268,7 +3466,9 @@ class Genome:
         prime_edits= / prime_allow_weak=: as enumerate_pattern; the prime rows come after the effect rows.  variation= /
         variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_pattern; only the survivors
         are searched, and the variation rows come after the prime rows.  fold= (and its options): as enumerate_pattern; only the
-        survivors are searched, the fold rows come last of the rows, and pick_by= knows the column "fold"."""
+        survivors are searched, the fold rows come last of the rows but the motif rows, and pick_by= knows the column "fold".
+        motifs= (and its options): as enumerate_pattern; only the survivors are searched, the motif rows come last of the rows, and
+        pick_by= knows the column "rflp"."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -3302,6 +3502,7 @@ class Genome:
         rest = list(extra)
         linear = rest.pop(0) if filters.get("efficiency") is not None else None
         pairs = rest.pop(0) if filters.get("microhomology") is not None else None
+        sites = rest.pop() if filters.get("motifs") is not None else None
         folds = rest[-1] if filters.get("fold") is not None else None
         spec = None
         if table is not None:
@@ -3309,7 +3510,7 @@ class Genome:
         regions = Regions(self.packed, targets, rule=filters.get("rule", "overlap"))
         try:
             return tuple(out) + self._pick_found(pick, pick_by, pick_groups, regions, found,
-                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds})
+                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites})
         finally:
             regions.close()
 
@@ -3388,10 +3589,10 @@ class Genome:
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
                           fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None, hd=None, hd_fns=None, fo=None,
-                          fo_fns=None):
+                          fo_fns=None, mo=None, mo_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
         the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows before the HDR rows
-        before the fold rows.
+        before the fold rows before the motif rows.
         held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
@@ -3409,6 +3610,8 @@ class Genome:
             self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, rows=False)
         if fo is not None:
             self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, rows=False)
+        if mo is not None:
+            self._motif_on_handle(held, mo, count_fn, mo_fns[0], mo_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -3426,6 +3629,8 @@ class Genome:
             extra += (self._hdr_on_handle(held, hd, count_fn, hd_fns[0], hd_fns[1], free_fn, filt=False),)
         if fo is not None:
             extra += (self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, filt=False),)
+        if mo is not None:
+            extra += (self._motif_on_handle(held, mo, count_fn, mo_fns[0], mo_fns[1], free_fn, filt=False),)
         return extra
 
     # ---- guide RNA self-complementarity (vsc_*_fold) -------------------------------------------------------------------
@@ -3486,6 +3691,80 @@ class Genome:
         stats = st.as_dict()
         _eff_partial(stats, allow_partial)
         return rows, stats
+
+    # ---- restriction sites and IUPAC motifs (vsc_*_motifs) -------------------------------------------------------------
+    @staticmethod
+    def _motif_args(shape, motif_set, left, right, forbid, forbid_context, require_cut, cut_only, site_len):
+        """(shape, MotifSet, left bytes, right bytes, the limits as (forbid_construct, forbid_context, require_cut, flags) or None
+        when none is given) - or None without a shape.  The names become masks here, once."""
+        given = [v is not None for v in (forbid, forbid_context, require_cut)]
+        if shape is None:
+            if motif_set is not None or left is not None or right is not None or any(given) or cut_only is not None:
+                raise ValueError("motif_set / motif_left / motif_right / forbid_motifs / forbid_context_motifs / require_cut_motifs / "
+                                 "cut_only need motifs=shape")
+            return None
+        shape = _motif_shape(shape, "motifs")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        ms = _motif_set(motif_set)
+        if cut_only and require_cut is None:
+            raise ValueError("cut_only= belongs to require_cut_motifs=")
+        limits = None
+        if any(given):
+            limits = (ms.mask(forbid, "forbid_motifs"), ms.mask(forbid_context, "forbid_context_motifs"),
+                      ms.mask(require_cut, "require_cut_motifs"), MOTIF_CUT_ONLY if cut_only else 0)
+        return shape, ms, _motif_flank(left, "motif_left"), _motif_flank(right, "motif_right"), limits
+
+    def _motif_on_handle(self, held, mo, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _fold_on_handle, for the motif rows: mo = what _motif_args returned.  With limits the handle is first replaced by
+        the filter's result."""
+        shape, ms, lf, rf, limits = mo
+        sh = shape._struct()
+        arr = ms._array()
+        if filt and limits is not None:
+            lim = _lib.MotifLimits(*limits)
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), lf, len(lf), rf, len(rf), arr, len(ms), C.byref(lim), C.byref(out)),
+                  self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        out_rows = np.empty((int(count_fn(held[0])), 3), dtype=np.uint64)
+        st = _lib.MotifStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), lf, len(lf), rf, len(rf), arr, len(ms), ptr(out_rows), None, C.byref(st)),
+              self.ctx._h)
+        _eff_partial(st.as_dict(), False)
+        return out_rows
+
+    def motifs(self, loci_or_found, shape, motif_set, left=None, right=None, totals=False, allow_partial=False):
+        """vsc_loci_motifs: the motif rows of candidates under a MotifShape (or the name of a preset of MOTIF_SHAPES), a MotifSet
+        (or its entries) and the flanks (None: empty), computed on the device from the resident planes: (uint64[n, 3], stats) -
+        columns construct, cut, elsewhere; unpack_motif_row names the bits.  totals=True: (rows, totals uint64[M, 3], stats) with
+        per motif the defined candidates that hold its construct, cut and cut-only bit.  loci_or_found: as Genome.efficiency
+        takes it.  An undefined row is (MOTIF_UNDEFINED,) * 3; stats counts the candidates by class - defined, invalid,
+        off_contig, not_resident, has_n -, those with any construct, any cut and any cut-only bit, and holds kernel_ms and
+        wall_ms.  Raises when a context is not resident on this object (a shard) unless allow_partial=True."""
+        shape = _motif_shape(shape)
+        ms = _motif_set(motif_set)
+        lf, rf = _motif_flank(left, "left"), _motif_flank(right, "right")
+        if isinstance(loci_or_found, PatternGuides):
+            loci = loci_or_found.loci
+        elif isinstance(loci_or_found, tuple) and len(loci_or_found) >= 2 and isinstance(loci_or_found[1], np.ndarray) \
+                and loci_or_found[1].dtype == _lib.LOCUS_DTYPE:
+            loci = loci_or_found[1]
+        else:
+            loci = loci_or_found
+        lo = _loci(loci, len(loci))
+        rows = np.empty((len(lo), 3), dtype=np.uint64)
+        tot = np.zeros((len(ms), 3), dtype=np.uint64) if totals else None
+        st = _lib.MotifStats()
+        sh = shape._struct()
+        check(lib().vsc_loci_motifs(self.ctx._h, self._h, ptr(lo), len(lo), C.byref(sh), lf, len(lf), rf, len(rf), ms._array(), len(ms),
+                                    ptr(rows), ptr(tot) if totals else None, C.byref(st)), self.ctx._h)
+        stats = st.as_dict()
+        _eff_partial(stats, allow_partial)
+        return (rows, tot, stats) if totals else (rows, stats)
 
     def microhomology(self, loci_or_found, shape, allow_partial=False):
         """vsc_loci_microhomology: the microhomology pairs of candidates under a MicrohomologyShape, computed on the device from
@@ -4206,7 +4485,8 @@ class Genome:
                          edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
                          variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
                          hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None,
-                         max_fold_starts=None, max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None):
+                         max_fold_starts=None, max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
+                         forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -4249,7 +4529,14 @@ class Genome:
         vsc_guides_fold; unpack_fold_row names the fields) come last of all, after the HDR rows.  fold_scaffold= the constant part
         of the guide RNA (at most 128 letters of A C G T U; default: none) / max_fold_starts= / max_fold_self= /
         max_fold_scaffold= / max_fold_seed= whole numbers 0 .. 32 (all need fold=): with a limit only the candidates whose row is
-        defined and within every limit (vsc_guides_filter_fold), after the HDR filter."""
+        defined and within every limit (vsc_guides_filter_fold), after the HDR filter.
+        motifs= a MotifShape with site_len 23 (or the name of a preset of MOTIF_SHAPES) with motif_set= a
+        MotifSet (motifs(...)) or its entries: the candidates' motif rows (uint64[n, 3]: construct, cut, elsewhere;
+        vsc_guides_motifs; unpack_motif_row names the bits) come last of all, after the fold rows.  motif_left= /
+        motif_right= the vector's text on either side of the cloned spacer (at most 16 letters of A C G T U; default: none) /
+        forbid_motifs= / forbid_context_motifs= / require_cut_motifs= names or bit masks / cut_only= (all need motifs=): with one of
+        them only the candidates whose row is defined and passes FILTER (vsc_guides_filter_motifs), after the fold
+        filter."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
         self._eff_args(efficiency, min_efficiency, READ_LEN)
@@ -4260,11 +4547,12 @@ class Genome:
         vr = self._variation_args(variation, variants, max_variant_cost, max_variants_by_zone, require_variant_zones, READ_LEN)
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, READ_LEN)
         fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, READ_LEN)
+        mo = self._motif_args(motifs, motif_set, motif_left, motif_right, forbid_motifs, forbid_context_motifs, require_cut_motifs, cut_only, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None and fo is None:
+        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None and fo is None and mo is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -4276,7 +4564,8 @@ class Genome:
                                            (L.vsc_guides_prime, L.vsc_guides_filter_prime), vr,
                                            (L.vsc_guides_variation, L.vsc_guides_filter_variation), hd,
                                            (L.vsc_guides_hdr, L.vsc_guides_filter_hdr), fo,
-                                           (L.vsc_guides_fold, L.vsc_guides_filter_fold))
+                                           (L.vsc_guides_fold, L.vsc_guides_filter_fold), mo,
+                                           (L.vsc_guides_motifs, L.vsc_guides_filter_motifs))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -4312,7 +4601,8 @@ class Genome:
                cds=None, edit_to=None, require_effect=None, forbid_effect=None, prime=None, prime_edits=None, prime_allow_weak=None,
                variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
                hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None,
-               max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, **search_options):
+               max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
+               forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -4336,7 +4626,10 @@ class Genome:
         come after the variation rows, before (picks, counts).
         fold= / fold_scaffold= / max_fold_starts= / max_fold_self= / max_fold_scaffold= / max_fold_seed=: as enumerate_guides; only
         the survivors are searched, and the fold rows come after the HDR rows, before (picks, counts); pick_by= then knows the
-        column "fold" (32 - starts, 6 bits: fewer stems are better)."""
+        column "fold" (32 - starts, 6 bits: fewer stems are better).
+        motifs= / motif_set= / motif_left= / motif_right= / forbid_motifs= / forbid_context_motifs= / require_cut_motifs= / cut_only=:
+        as enumerate_guides; only the survivors are searched, and the motif rows come after the fold rows, before (picks, counts);
+        pick_by= then knows the column "rflp" (the motifs over the cut and nowhere else in the context, 6 bits: more are better)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -4350,7 +4643,10 @@ class Genome:
                                       max_variants_by_zone=max_variants_by_zone, require_variant_zones=require_variant_zones,
                                       hdr=hdr, hdr_edits=hdr_edits, hdr_cds=hdr_cds, hdr_allow_open=hdr_allow_open, fold=fold,
                                       fold_scaffold=fold_scaffold, max_fold_starts=max_fold_starts, max_fold_self=max_fold_self,
-                                      max_fold_scaffold=max_fold_scaffold, max_fold_seed=max_fold_seed)
+                                      max_fold_scaffold=max_fold_scaffold, max_fold_seed=max_fold_seed, motifs=motifs,
+                                      motif_set=motif_set, motif_left=motif_left, motif_right=motif_right, forbid_motifs=forbid_motifs,
+                                      forbid_context_motifs=forbid_context_motifs, require_cut_motifs=require_cut_motifs,
+                                      cut_only=cut_only)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])
@@ -4359,11 +4655,12 @@ class Genome:
         extra = list(found[3:] if len(found) > 2 and _label_regions(labels, regions) is not None else found[2:])
         linear = extra.pop(0) if efficiency is not None else None
         pairs = extra.pop(0) if microhomology is not None else None
+        sites = extra.pop() if motifs is not None else None
         folds = extra[-1] if fold is not None else None
         all_rows = rows[0] if isinstance(rows, tuple) else rows
         spec = np.array([mit_specificity(x) for x in all_rows["mit_sum"]], dtype=np.float64)
         return out + self._pick_found(pick, pick_by, pick_groups, regions, (codes, loci),
-                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds})
+                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites})
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)

@@ -131,6 +131,10 @@
 // with --hdr-edits edits.tsv those without a usable pair as well (--hdr-allow-open: without any pair); --hdr-cds cds.bed keeps the
 // blocking substitution synonymous; the -L listing gains the last columns hdrPairs hdrUsable; --hdr-out pairs.tsv (needs
 // --hdr-edits) lists the pairs with their substitutions.
+// --motifs motifs.tsv (needs -E, one device; tools/motif_host.hpp) looks for restriction sites and IUPAC motifs in the cloned construct
+// (the spacer between --motif-left and --motif-right) and in the genomic context of every found guide: the listing gains the last
+// columns motifsConstruct motifsCut motifsElsewhere motifsCutOnly; --motif-forbid / --motif-forbid-context / --motif-require-cut NAMES
+// (--motif-cut-only) keep the candidates that pass; --motifs-out sites.tsv lists the names per candidate.
 // --fold SpCas9 | Cas12a | SPEC (needs -E, one device; tools/fold_host.hpp) counts the stems the guide RNA of every found guide can
 // form with itself and with the --fold-scaffold text (at most 128 letters, or @FILE; default: none): the -L listing gains the last
 // columns foldStarts foldSelf foldScaffold foldSeed; --max-fold STARTS[,SELF[,SCAF[,SEED]]] keeps the candidates within the limits.
@@ -151,6 +155,7 @@
 #include "prime_host.hpp"
 #include "hdr_host.hpp"
 #include "fold_host.hpp"
+#include "motif_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "forest_host.hpp"
@@ -264,6 +269,16 @@ int main(int argc, char **argv)
         {':', "fold-scaffold", "With --fold: the constant part of the guide RNA, 5' to 3', at most 128 letters of A C G T U, or @FILE", false},
         {';', "max-fold", "With --fold: STARTS[,SELF[,SCAF[,SEED]]] - only the candidates with at most so many stem starts, so long a "
                           "hairpin stem, so long a scaffold stem and so many paired seed bases (each 0 .. 32, - for no limit)", false},
+        {'[', "motifs", "With -E: path to the motifs (.tsv: name, IUPAC text of 2 .. 16 letters, 1 or 2 strands; at most 63): restriction sites "
+                        "in the cloned construct and the genomic context; the guide listing gains the last columns motifsConstruct motifsCut "
+                        "motifsElsewhere motifsCutOnly (one device)", false},
+        {']', "motif-left", "With --motifs: the vector's text in front of the cloned spacer, at most 16 letters of A C G T U", false},
+        {'{', "motif-right", "With --motifs: the vector's text behind the cloned spacer, at most 16 letters of A C G T U", false},
+        {'}', "motif-forbid", "With --motifs: NAMES - drop the candidates whose construct holds one of these motifs", false},
+        {'<', "motif-forbid-context", "With --motifs: NAMES - drop the candidates whose genomic context holds one of these motifs", false},
+        {'>', "motif-require-cut", "With --motifs: NAMES - keep the candidates with one of these motifs over the cut zone", false},
+        {'/', "motif-cut-only", "With --motif-require-cut: ... and nowhere else in the context", false, false},
+        {'?', "motifs-out", "With --motifs: path to the listing, one line per candidate: #guideId construct cut elsewhere cutOnly (names)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Guide summary",
                               "Per-guide off-target counts by mismatch number and MIT specificity score (CRISPOR's "
@@ -692,6 +707,16 @@ int main(int argc, char **argv)
         }
     }
 
+    // --motifs and its options: restriction sites and motifs in the found guides' construct and context
+    MotifOptions motif;
+    {
+        const std::string why = parse_motif_options(opts[69], opts[70], opts[71], opts[72], opts[73], opts[74], opts[75], opts[76], discover, devices.size() != 1, (uint32_t)VSC_READ_LEN, &motif);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
     {
@@ -914,6 +939,14 @@ int main(int argc, char **argv)
                 vsc_guides_free(found);
                 found = kept;
             }
+            if (motif.limited) {  // --motif-forbid / --motif-forbid-context / --motif-require-cut: the same, after the fold FILTER
+                vsc_guides *kept = nullptr;
+                if (vsc_guides_filter_motifs(ctx, genome, found, &motif.shape, motif.left.c_str(), (uint32_t)motif.left.size(), motif.right.c_str(),
+                                     (uint32_t)motif.right.size(), motif.motifs.data(), (uint32_t)motif.motifs.size(), &motif.limits, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -963,6 +996,11 @@ int main(int argc, char **argv)
             std::vector<uint32_t> fold_rows(fold.on ? 2 * vsc_guides_count(found) : 0);  // --fold: the rows
             if (fold.on && vsc_guides_fold(ctx, genome, found, &fold.shape, fold.scaffold.c_str(), (uint32_t)fold.scaffold.size(), fold_rows.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<uint64_t> motif_rows(motif.on ? 3 * vsc_guides_count(found) : 0);  // --motifs: the rows
+            if (motif.on && vsc_guides_motifs(ctx, genome, found, &motif.shape, motif.left.c_str(), (uint32_t)motif.left.size(), motif.right.c_str(),
+                                              (uint32_t)motif.right.size(), motif.motifs.data(), (uint32_t)motif.motifs.size(), motif_rows.data(),
+                                              nullptr, nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t *fc = nullptr;
             const vsc_locus *fl = nullptr;
             if (vsc_guides_data(found, &fc, &fl) != VSC_OK) throw std::runtime_error(multi ? "could not read the candidates" : vsc_last_error(ctx));
@@ -989,7 +1027,8 @@ int main(int argc, char **argv)
                             (mh.on ? mh_columns(&mh_pairs[2 * i]) : "");
                     const std::string ecol = (edit.on ? edit_columns(edit.shape, seq, &edit_rows[2 * i]) : "") +
                                              (fx.on ? effects_columns(&fx_rows[2 * i]) : "") + (prime.on ? prime_columns(&prime_rows[2 * i]) : "") +
-                                             (hdr.on ? hdr_columns(&hdr_rows[2 * i]) : "") + (fold.on ? fold_columns(&fold_rows[2 * i]) : "");
+                                             (hdr.on ? hdr_columns(&hdr_rows[2 * i]) : "") + (fold.on ? fold_columns(&fold_rows[2 * i]) : "") +
+                                             (motif.on ? motif_columns(motif, &motif_rows[3 * i]) : "");
                     if (pick.on) bed_lines.push_back(line), edit_cols.push_back(ecol);
                     else bed6 += line + ecol + '\n';
                 }
@@ -1006,6 +1045,7 @@ int main(int argc, char **argv)
             if (prime.with_pairs) write_prime_pairs(prime.pairs_path, prime.shape, prime_pairs, prime_edits, loci, ix, ids);
             if (variation.with_out) write_variation(variation.out_path, variation_rows, variation_pairs, variants, ix.names, ids);
             if (hdr.with_pairs) write_hdr_pairs(hdr.pairs_path, hdr.shape, hdr_pairs, hdr_edits, loci, ix.names, ids);
+            if (motif.on && !motif.out_path.empty()) write_motifs(motif, motif_rows, ids);
             std::fprintf(stderr, "Guides found (total: %zu).\n", seqs.size());
             // the guide's own locus is a hit only if the search allows its PAM
             const bool canonical = (ep.pam[0] == 'G' || ep.pam[0] == 'g') && (ep.pam[1] == 'G' || ep.pam[1] == 'g' || ep.pam[1] == 'A' || ep.pam[1] == 'a');

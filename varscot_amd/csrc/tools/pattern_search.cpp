@@ -68,6 +68,10 @@
 // with --hdr-edits edits.tsv those without a usable pair as well (--hdr-allow-open: without any pair); --hdr-cds cds.bed keeps the
 // blocking substitution synonymous; the -E listing gains the last columns hdrPairs hdrUsable; --hdr-out pairs.tsv (needs
 // --hdr-edits) lists the pairs with their substitutions.
+// --motifs motifs.tsv (needs -E, one device; tools/motif_host.hpp) looks for restriction sites and IUPAC motifs in the cloned construct
+// (the spacer between --motif-left and --motif-right) and in the genomic context of every found guide: the listing gains the last
+// columns motifsConstruct motifsCut motifsElsewhere motifsCutOnly; --motif-forbid / --motif-forbid-context / --motif-require-cut NAMES
+// (--motif-cut-only) keep the candidates that pass; --motifs-out sites.tsv lists the names per candidate.
 // --fold SpCas9 | Cas12a | SPEC (needs -E, one device; tools/fold_host.hpp) counts the stems the guide RNA of every found guide can
 // form with itself and with the --fold-scaffold text (at most 128 letters, or @FILE; default: none): the -E listing gains the last
 // columns foldStarts foldSelf foldScaffold foldSeed; --max-fold STARTS[,SELF[,SCAF[,SEED]]] keeps the candidates within the limits.
@@ -87,6 +91,7 @@
 #include "prime_host.hpp"
 #include "hdr_host.hpp"
 #include "fold_host.hpp"
+#include "motif_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
@@ -311,6 +316,16 @@ int main(int argc, char **argv)
         {':', "fold-scaffold", "With --fold: the constant part of the guide RNA, 5' to 3', at most 128 letters of A C G T U, or @FILE", false},
         {';', "max-fold", "With --fold: STARTS[,SELF[,SCAF[,SEED]]] - only the candidates with at most so many stem starts, so long a "
                           "hairpin stem, so long a scaffold stem and so many paired seed bases (each 0 .. 32, - for no limit)", false},
+        {'[', "motifs", "With -E: path to the motifs (.tsv: name, IUPAC text of 2 .. 16 letters, 1 or 2 strands; at most 63): restriction sites "
+                        "in the cloned construct and the genomic context; the guide listing gains the last columns motifsConstruct motifsCut "
+                        "motifsElsewhere motifsCutOnly (one device)", false},
+        {']', "motif-left", "With --motifs: the vector's text in front of the cloned spacer, at most 16 letters of A C G T U", false},
+        {'{', "motif-right", "With --motifs: the vector's text behind the cloned spacer, at most 16 letters of A C G T U", false},
+        {'}', "motif-forbid", "With --motifs: NAMES - drop the candidates whose construct holds one of these motifs", false},
+        {'<', "motif-forbid-context", "With --motifs: NAMES - drop the candidates whose genomic context holds one of these motifs", false},
+        {'>', "motif-require-cut", "With --motifs: NAMES - keep the candidates with one of these motifs over the cut zone", false},
+        {'/', "motif-cut-only", "With --motif-require-cut: ... and nowhere else in the context", false, false},
+        {'?', "motifs-out", "With --motifs: path to the listing, one line per candidate: #guideId construct cut elsewhere cutOnly (names)", false},
     };
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
@@ -567,6 +582,17 @@ int main(int argc, char **argv)
         }
     }
 
+    // --motifs and its options: restriction sites and motifs in the found guides' construct and context
+    MotifOptions motif;
+    {
+        const std::string why = parse_motif_options(opts[57], opts[58], opts[59], opts[60], opts[61], opts[62], opts[63], opts[64], enumerate,
+                                                    opts[4].value.find(',') != std::string::npos, (uint32_t)pattern.size(), &motif);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
     {
@@ -799,6 +825,14 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            if (motif.limited) {  // --motif-forbid / --motif-forbid-context / --motif-require-cut: the same, after the fold FILTER
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_motifs(ctx, genome, found, &motif.shape, motif.left.c_str(), (uint32_t)motif.left.size(), motif.right.c_str(),
+                                     (uint32_t)motif.right.size(), motif.motifs.data(), (uint32_t)motif.motifs.size(), &motif.limits, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -848,6 +882,11 @@ int main(int argc, char **argv)
             std::vector<uint32_t> fold_rows(fold.on ? 2 * vsc_pattern_guides_count(found) : 0);  // --fold: the rows
             if (fold.on && vsc_pattern_guides_fold(ctx, genome, found, &fold.shape, fold.scaffold.c_str(), (uint32_t)fold.scaffold.size(), fold_rows.data(), nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<uint64_t> motif_rows(motif.on ? 3 * vsc_pattern_guides_count(found) : 0);  // --motifs: the rows
+            if (motif.on && vsc_pattern_guides_motifs(ctx, genome, found, &motif.shape, motif.left.c_str(), (uint32_t)motif.left.size(),
+                                                      motif.right.c_str(), (uint32_t)motif.right.size(), motif.motifs.data(),
+                                                      (uint32_t)motif.motifs.size(), motif_rows.data(), nullptr, nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -858,7 +897,8 @@ int main(int argc, char **argv)
             out << "#guide\tchrom\tpos\tstrand" << (efficient ? "\tefficiencyLinear\tefficiency" : "") << (mh.on ? "\tmhScore\toofScore" : "")
                 << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "")
                 << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << (prime.on ? "\tpbsLen\tpbsGC\tprimePairs" : "")
-                << (hdr.on ? "\thdrPairs\thdrUsable" : "") << (fold.on ? "\tfoldStarts\tfoldSelf\tfoldScaffold\tfoldSeed" : "") << '\n';
+                << (hdr.on ? "\thdrPairs\thdrUsable" : "") << (fold.on ? "\tfoldStarts\tfoldSelf\tfoldScaffold\tfoldSeed" : "")
+                << (motif.on ? "\tmotifsConstruct\tmotifsCut\tmotifsElsewhere\tmotifsCutOnly" : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -887,6 +927,7 @@ int main(int argc, char **argv)
                 if (prime.on) ecol += prime_columns(&prime_rows[2 * i]);
                 if (hdr.on) ecol += hdr_columns(&hdr_rows[2 * i]);
                 if (fold.on) ecol += fold_columns(&fold_rows[2 * i]);
+                if (motif.on) ecol += motif_columns(motif, &motif_rows[3 * i]);
                 if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
                 else out << line << ecol << '\n';
             }
@@ -914,6 +955,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_hdr_pairs(hdr.pairs_path, hdr.shape, hdr_pairs, hdr_edits, std::vector<vsc_locus>(loci, loci + n), ix.names, ids);
+            }
+            if (motif.on && !motif.out_path.empty()) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_motifs(motif, motif_rows, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

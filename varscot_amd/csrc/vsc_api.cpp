@@ -15,6 +15,7 @@
 //   vsc_eff_trees.hip      ... from regression-tree ensembles
 //   vsc_mh.hip             microhomology and out-of-frame scores of candidates
 //   vsc_fold.hip           self-complementarity of the candidates' guide RNA: hairpin and scaffold stems
+//   vsc_motif.hip          restriction sites and IUPAC motifs in the candidates' construct and genomic context
 //   vsc_edit.hip           base-editor windows of candidates and their join with targets
 //   vsc_prime.hip          prime-editing extensions of candidates and their join with edits
 //   vsc_variation.hip      known variation under candidates: the join of their sites with variant intervals
@@ -4131,7 +4132,7 @@ int vsc_guides_locate(vsc_guides *guides, const vsc_regions *regions, uint32_t *
 
 // ---- the host path of the candidate annotations ----------------------------------------------------------------
 // What the families that annotate candidate guides - linear and tree efficiency, microhomology, edit windows, coding effects,
-// prime editing, variation, HDR, the guide RNA's fold - do alike on the host: the checks in front of a call over candidates,
+// prime editing, variation, HDR, the guide RNA's fold, motifs - do alike on the host: the checks in front of a call over candidates,
 // the filter (staging, run_enumeration, the timing restated), the rows pass, and the join of the rows with a family's table (count pass, scan,
 // write pass, coverage).  A family keeps its check, its table upload, the fields of its Args, its launchers and its stats;
 // what differs between families enters here as a value or a callable of the family's.
@@ -7266,6 +7267,270 @@ int vsc_pattern_guides_filter_fold(vsc_ctx *ctx, const vsc_genome *genome, vsc_p
                                    const char *scaffold, uint32_t m, const vsc_fold_limits *limits, vsc_pattern_guides **out)
 {
     return fold_filter(ctx, genome, in, shape, scaffold, m, false, limits, out, "vsc_pattern_guides_filter_fold");
+}
+
+}  // extern "C"
+
+// ---- restriction sites and IUPAC motifs (the definition: vsc_motif.h, the kernels: vsc_motif.hip) -----------------
+namespace {
+
+const char *const kMotifShapeRule =
+    "site_len 16 .. 32, up and down 0 .. 16 with a context of at most 64, proto_len 12 .. 32 inside the site, cut_len 1 .. 16 inside the "
+    "site, reserved fields 0";
+
+bool motif_shape_in(const vsc_motif_shape *shape, MotifShape &s)
+{
+    s = MotifShape{shape->up, shape->site_len, shape->down, shape->proto_start, shape->proto_len, shape->cut_start, shape->cut_len};
+    for (uint32_t r : shape->reserved)
+        if (r) return false;
+    return motif_shape_valid(s);
+}
+
+// a flank's text as letters 0 .. 3; false: longer than 16 or another letter
+bool motif_flank_in(const char *text, uint32_t n, uint8_t *letters)
+{
+    if (n > kMotifMaxFlank || (n && !text)) return false;
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t b = motif_letter(text[j]);
+        if (b > 3u) return false;
+        letters[j] = (uint8_t)b;
+    }
+    return true;
+}
+
+// What a call makes of its shape, flanks and motifs on the host: the table as the kernels read it (pat: host), and its image
+// for the device - the patterns, then 3 * 63 zeroed totals.
+struct MotifCall {
+    MotifShape s{};
+    MotifTable tab{};
+    std::vector<MotifPattern> pat;
+};
+constexpr size_t kMotifTotalsAt = (kMotifMaxPatterns * sizeof(MotifPattern) + 255) / 256 * 256;
+constexpr size_t kMotifImage = kMotifTotalsAt + 3 * kMotifMaxMotifs * sizeof(uint64_t);
+
+// nullptr: fine; else the words of the refusal
+const char *motif_call_in(const vsc_motif_shape *shape, const char *left, uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs,
+                          uint32_t n_motifs, MotifCall &c)
+{
+    if (!shape) return "null argument";
+    if (!motif_shape_in(shape, c.s)) return kMotifShapeRule;
+    uint8_t lf[kMotifMaxFlank], rf[kMotifMaxFlank];
+    if (!motif_flank_in(left, a, lf) || !motif_flank_in(right, b, rf)) return "a flank: at most 16 letters of A C G T U";
+    if (n_motifs < 1u || n_motifs > kMotifMaxMotifs) return "1 .. 63 motifs";
+    if (!motifs) return "null argument";
+    uint64_t accept[kMotifMaxMotifs];
+    uint32_t len[kMotifMaxMotifs], flags[kMotifMaxMotifs];
+    for (uint32_t m = 0; m < n_motifs; ++m) {
+        if (motifs[m].flags & ~kMotifBothStrands) return "a motif's flags: bit 0 only";
+        if (motifs[m].len < kMotifMinLen || motifs[m].len > kMotifMaxLen) return "a motif has 2 .. 16 letters";
+        if (!motif_accepts(motifs[m].text, motifs[m].len, &accept[m])) return "a motif: IUPAC letters, not every one N";
+        len[m] = motifs[m].len;
+        flags[m] = motifs[m].flags;
+    }
+    c.pat.resize(kMotifMaxPatterns);
+    c.pat.resize(motif_layout(accept, len, flags, n_motifs, c.s, a, b, c.pat.data()));
+    c.tab = MotifTable{c.pat.data(), (uint32_t)c.pat.size(), n_motifs, 0ull, 0ull, a, b};
+    motif_flank_planes(lf, a, rf, b, c.s.proto_len, &c.tab.flank_h, &c.tab.flank_l);
+    return nullptr;
+}
+
+// The shape, the genome, the flanks and the motifs of a call, checked on the host.
+int motif_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_motif_shape *shape, const char *left, uint32_t a, const char *right, uint32_t b,
+                const vsc_motif *motifs, uint32_t n_motifs, MotifCall &c, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    const char *why = motif_call_in(shape, left, a, right, b, motifs, n_motifs, c);
+    return why ? fail_in(ctx, VSC_ERR_INVALID, who, why) : VSC_OK;
+}
+
+// The patterns of a call onto the device, enqueued on the context's stream: into eff_buf, whose efficiency model is forgotten,
+// with the zeroed totals behind them.  Every call uploads its own, so no call reads another's motifs.  *d_tab = the table
+// with the device's patterns.
+int motif_upload(vsc_ctx *ctx, const MotifCall &c, MotifTable *d_tab, unsigned long long **d_totals)
+{
+    ctx->eff_serial = 0;
+    VSC_HIP(ctx, ctx->eff_buf.ensure(kMotifImage));
+    VSC_HIP(ctx, hipMemcpyAsync(ctx->eff_buf.p, c.pat.data(), c.pat.size() * sizeof(MotifPattern), hipMemcpyHostToDevice, ctx->stream));
+    VSC_HIP(ctx, hipMemsetAsync((char *)ctx->eff_buf.p + kMotifTotalsAt, 0, kMotifImage - kMotifTotalsAt, ctx->stream));
+    *d_tab = c.tab;
+    d_tab->pat = (const MotifPattern *)ctx->eff_buf.p;
+    if (d_totals) *d_totals = (unsigned long long *)((char *)ctx->eff_buf.p + kMotifTotalsAt);
+    return VSC_OK;
+}
+
+const CandidateRule kMotifRowsRule{"the shape's site_len must be 23", ~0ull, ""};  // (the scoring itself refuses above 2^40)
+const CandidateRule kMotifFilterRule{"the shape's site_len must be 23", 0xFFFFFFFFull * kMotifTile, "more candidates than 2^32 tiles hold"};
+
+// The rows of the loci `at` into host memory: motif_rows_kernel, one copy back of the rows, one of the counts and - where asked
+// for - one of the totals.
+int motif_rows_loci(vsc_ctx *ctx, const vsc_genome *genome, const MotifCall &c, const CandidateLoci &at, uint64_t *rows, uint64_t *totals,
+                    vsc_motif_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (at.n && !rows) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (stats) *stats = vsc_motif_stats{};
+    if (totals) std::fill(totals, totals + 3 * (size_t)c.tab.n_motifs, (uint64_t)0);
+    if (at.n == 0) {
+        ctx->timing = vsc_timing{};
+        return VSC_OK;
+    }
+    MotifArgs a{};
+    a.g = eff_planes(genome);
+    a.shape = c.s;
+    a.n = at.n;
+    unsigned long long seen[kMotifStats] = {};
+    float ms = 0;
+    const int rc = score_rows(
+        ctx, at, sizeof(MotifRow), rows, seen, kMotifStats, &ms, who,
+        [&] {
+            unsigned long long *d_totals = nullptr;
+            const int urc = motif_upload(ctx, c, &a.tab, &d_totals);
+            a.totals = totals ? d_totals : nullptr;
+            return urc;
+        },
+        [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+            a.stats = d_stats;
+            a.out = (MotifRow *)d_rows;
+            a.loci = d_loci;
+            return launch_motif_rows(a, ctx->n_cus, ctx->motif_groups_per_cu, ctx->stream);
+        });
+    if (rc != VSC_OK) return rc;
+    if (totals) {
+        VSC_HIP(ctx, hipMemcpyAsync(totals, a.totals, 3 * (size_t)c.tab.n_motifs * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (stats) {
+        class_counts(stats, seen);
+        stats->any_construct = seen[kEffClasses];
+        stats->any_cut = seen[kEffClasses + 1];
+        stats->any_cut_only = seen[kEffClasses + 2];
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    return VSC_OK;
+}
+
+// vsc_guides_motifs / vsc_pattern_guides_motifs: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int motif_rows_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_motif_shape *shape, const char *left, uint32_t fa,
+                      const char *right, uint32_t fb, const vsc_motif *motifs, uint32_t n_motifs, bool need_23, uint64_t *rows, uint64_t *totals,
+                      vsc_motif_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    MotifCall c;
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kMotifRowsRule, who, at, &c.s.site_len,
+                                   [&] { return motif_check(ctx, genome, shape, left, fa, right, fb, motifs, n_motifs, c, who); }, no_refusal);
+    if (rc != VSC_OK) return rc;
+    return motif_rows_loci(ctx, genome, c, at, rows, totals, stats, who);
+    });
+}
+
+// vsc_guides_filter_motifs / vsc_pattern_guides_filter_motifs: the candidates the limits keep
+template <class Guides>
+int motif_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_motif_shape *shape, const char *left, uint32_t fa, const char *right,
+                 uint32_t fb, const vsc_motif *motifs, uint32_t n_motifs, bool need_23, const vsc_motif_limits *limits, Guides **out,
+                 const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    MotifCall c;
+    MotifFilterArgs a{};
+    const int rc = filter_front(
+        ctx, in, out, need_23, kMotifFilterRule, who, &c.s.site_len,
+        [&] { return motif_check(ctx, genome, shape, left, fa, right, fb, motifs, n_motifs, c, who); },
+        [&]() -> int {
+            if (!limits) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+            a.limits = MotifLimits{limits->forbid_construct, limits->forbid_context, limits->require_cut, limits->flags};
+            return !limits->reserved && motif_limits_valid(a.limits, n_motifs)
+                       ? VSC_OK
+                       : fail_in(ctx, VSC_ERR_INVALID, who, "the limits: bits below the number of motifs, flags bit 0 only, reserved 0");
+        });
+    if (rc != VSC_OK) return rc;
+    const int urc = motif_upload(ctx, c, &a.tab, nullptr);
+    if (urc != VSC_OK) return urc;
+    a.g = eff_planes(genome);
+    a.shape = c.s;
+    return filter_candidates(ctx, in, a, kMotifTile, out, who, [&](bool write) { return launch_motif_filter(a, write, ctx->stream); });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_motif_groups_per_cu(vsc_ctx *ctx, uint32_t groups)
+{
+    if (!ctx || groups > kMotifMaxGroupsPerCu) return VSC_ERR_INVALID;
+    ctx->motif_groups_per_cu = groups;
+    return VSC_OK;
+}
+
+int vsc_motif_text(const char *context, uint32_t c_len, const char *left, uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs,
+                   uint32_t n_motifs, const vsc_motif_shape *shape, uint64_t *row)
+{
+    if (!context || !row) return VSC_ERR_INVALID;
+    MotifCall c;
+    if (motif_call_in(shape, left, a, right, b, motifs, n_motifs, c)) return VSC_ERR_INVALID;
+    if (c_len != motif_context_len(c.s) || strnlen(context, c_len) != c_len) return VSC_ERR_INVALID;
+    row[0] = row[1] = row[2] = kMotifUndefined;
+    uint64_t ch = 0, cl = 0;
+    for (uint32_t j = 0; j < c_len; ++j) {
+        const uint32_t l = motif_letter(context[j]);
+        if (l > 3u) return VSC_OK;
+        ch |= (uint64_t)(l >> 1) << j;
+        cl |= (uint64_t)(l & 1u) << j;
+    }
+    const MotifRow r = motif_row(ch, cl, c.s, c.tab);
+    row[0] = r.construct;
+    row[1] = r.cut;
+    row[2] = r.elsewhere;
+    return VSC_OK;
+}
+
+int vsc_loci_motifs(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_motif_shape *shape, const char *left,
+                    uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, uint64_t *rows, uint64_t *totals,
+                    vsc_motif_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_motifs";
+    MotifCall c;
+    const int rc = motif_check(ctx, genome, shape, left, a, right, b, motifs, n_motifs, c, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    return motif_rows_loci(ctx, genome, c, CandidateLoci{nullptr, loci, n}, rows, totals, stats, fn);
+    });
+}
+
+int vsc_guides_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_motif_shape *shape, const char *left, uint32_t a,
+                      const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, uint64_t *rows, uint64_t *totals,
+                      vsc_motif_stats *stats)
+{
+    return motif_rows_guides(ctx, genome, guides, shape, left, a, right, b, motifs, n_motifs, true, rows, totals, stats, "vsc_guides_motifs");
+}
+
+int vsc_pattern_guides_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_motif_shape *shape, const char *left,
+                              uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, uint64_t *rows,
+                              uint64_t *totals, vsc_motif_stats *stats)
+{
+    return motif_rows_guides(ctx, genome, guides, shape, left, a, right, b, motifs, n_motifs, false, rows, totals, stats,
+                             "vsc_pattern_guides_motifs");
+}
+
+int vsc_guides_filter_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_motif_shape *shape, const char *left, uint32_t a,
+                             const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs, const vsc_motif_limits *limits,
+                             vsc_guides **out)
+{
+    return motif_filter(ctx, genome, in, shape, left, a, right, b, motifs, n_motifs, true, limits, out, "vsc_guides_filter_motifs");
+}
+
+int vsc_pattern_guides_filter_motifs(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_motif_shape *shape,
+                                     const char *left, uint32_t a, const char *right, uint32_t b, const vsc_motif *motifs, uint32_t n_motifs,
+                                     const vsc_motif_limits *limits, vsc_pattern_guides **out)
+{
+    return motif_filter(ctx, genome, in, shape, left, a, right, b, motifs, n_motifs, false, limits, out, "vsc_pattern_guides_filter_motifs");
 }
 
 }  // extern "C"

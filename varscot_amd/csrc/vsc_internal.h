@@ -10,6 +10,7 @@
 #include "vsc_eff_trees.h"
 #include "vsc_mh.h"
 #include "vsc_fold.h"
+#include "vsc_motif.h"
 #include "vsc_edit.h"
 #include "vsc_variation.h"
 #include "vsc_prime.h"
@@ -669,6 +670,40 @@ struct FoldFilterArgs {
 hipError_t launch_fold_rows(const FoldArgs &args, int n_cus, uint32_t groups_per_cu, hipStream_t stream);
 hipError_t launch_fold_filter(const FoldFilterArgs &args, bool write, hipStream_t stream);
 constexpr uint32_t kFoldGroupsPerCu = 8, kFoldMaxGroupsPerCu = 64;
+// vsc_motif.hip (the definition: vsc_motif.h)
+struct MotifArgs {
+    EffPlanes g;
+    MotifShape shape;
+    MotifTable tab;               // pat: [n_pat] the launch's patterns (motif_layout), on the device
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    MotifRow *out;                // [n] out: the row, kMotifUndefined three times where the class is not defined
+    unsigned long long *stats;    // [kMotifStats], zeroed before the launch: the classes, then the candidates with any construct,
+                                  // any cut, any cut-only bit
+    unsigned long long *totals;   // null, or [3 n_motifs] zeroed before the launch: per motif the defined candidates with the
+                                  // construct, the cut and the cut-only bit
+};
+// the filter's two passes, driven by run_enumeration (vsc_api.cpp): tile i of the work list = candidates [i * kMotifTile, ..)
+constexpr uint32_t kMotifTile = 1024;
+struct MotifFilterArgs {
+    EffPlanes g;
+    MotifShape shape;
+    MotifLimits limits;
+    MotifTable tab;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+// groups_per_cu: workgroups per CU the rows kernel's grid is capped at (0: the default, kMotifGroupsPerCu)
+hipError_t launch_motif_rows(const MotifArgs &args, int n_cus, uint32_t groups_per_cu, hipStream_t stream);
+hipError_t launch_motif_filter(const MotifFilterArgs &args, bool write, hipStream_t stream);
+constexpr uint32_t kMotifGroupsPerCu = 8, kMotifMaxGroupsPerCu = 64;
 // vsc_edit.hip (the definition: vsc_edit.h)
 constexpr uint32_t kEditCounts = kEffClasses + 1;  // the classes, then the candidates with a hit
 struct EditArgs {

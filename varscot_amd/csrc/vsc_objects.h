@@ -152,6 +152,8 @@ struct vsc_ctx {
     uint32_t hdr_groups_per_cu = 0;  // vsc_debug_hdr_groups_per_cu: the cap of hdr_rows_kernel's grid (0: the default)
     // vsc_*_fold upload their scaffold's windows into eff_buf (the efficiency model's copy is forgotten: eff_serial 0)
     uint32_t fold_groups_per_cu = 0;  // vsc_debug_fold_groups_per_cu: the cap of fold_rows_kernel's grid (0: the default)
+    // vsc_*_motifs upload their patterns (and the zeroed totals behind them) into eff_buf, as the fold calls do
+    uint32_t motif_groups_per_cu = 0;  // vsc_debug_motif_groups_per_cu: the cap of motif_rows_kernel's grid (0: the default)
     uint32_t variation_block_bits = 0;  // vsc_debug_variation_block_bits: the block of the variation lookup (0: kVarBlockBits)
     // vsc_*_effects: the device copy of the CDS this context walked last - the segments' global starts, then the
     // segments, keyed by the object's serial number as locate_buf is; the call's tables and records lie in edit_tabs / edit_pairs
