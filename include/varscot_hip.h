@@ -2381,6 +2381,122 @@ int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vs
                                       uint32_t to, const vsc_cds *cds, const char *code, uint32_t require, uint32_t forbid,
                                       vsc_pattern_guides **out);
 
+/* ---- knock-out design: cut position, frameshift stops, nonsense-mediated decay ------------------- */
+/*
+ * The oldest use of a nuclease: cut inside a gene and let the repair's indel destroy the protein.  For every candidate: is its
+ * cut in coding sequence, in which transcript, codon and frame, how far along the protein, how close to the exon's edge; where is
+ * the first premature stop codon (PTC) when the frame shifts by +1 or +2, and does that stop lie far enough upstream of the last
+ * exon-exon junction for nonsense-mediated decay (NMD) - or does the cell make a truncated protein instead.  Answered on the
+ * resident genome against a CDS annotation (4.29's object), where the candidates lie.
+ *
+ * CODE, SEGMENT, CODING   4.29's, unchanged (one transcript set per call).
+ * SHAPE     { site_len 16 .. 32, cut 1 .. site_len - 1, nmd_window 0 .. 65535, start_window 0 .. 65535 (0: rule off),
+ *             max_codons 1 .. 4096, reserved 0 }.  Presets in Python only (SpCas9 23 / 17, nmd_window 50).
+ * CUT       x = p + cut on '+', p + site_len - cut on '-'  (4.27's CUT COORDINATE): the break lies between forward bases x - 1 and x.
+ * DEFINED   the locus is valid and the site lies inside its contig. Otherwise the row is 0xFFFFFFFF four times.
+ * CODING CUT  bases x - 1 and x lie in ONE segment S (start < x < end). Otherwise the row is NONCODING:
+ *             word 0 = 0xFFFFFFFF, word 1 = 0, word 2 = JUNCTION << 31, word 3 = 0, JUNCTION iff x - 1 or x lies in some segment.
+ * TRANSCRIPT  t = S.transcript; shift, ci as in CODING; B_t = the transcript's coding bases; E_t = shift + B_t;
+ *             J_t = ci of the first base of t's LAST segment in transcript order (t has one segment: no junction).
+ * K         the coding index of the first base 3' of the break in transcript orientation: ci(x) on a '+' transcript, ci(x - 1) on '-'.
+ *             codon = K / 3, frame = K % 3; frac = ((K - shift) << 16) / B_t  (0 .. 65535, 64-bit arithmetic);
+ *             edge = min(x - S.start, S.end - x, 255).
+ * SHIFTED   for s = 1, 2: the transcript with s bases removed behind the break. Its index j is the transcript's j for j < K, j + s otherwise.
+ * WALK(s)   c = codon, codon + 1, ... at most max_codons codons. The three bases of codon c of SHIFTED(s), in transcript orientation
+ *             (complemented on '-'), read across segments:
+ *               an index >= E_t        -> END      (no stop inside the coding sequence)       d_s = 0xFFFF
+ *               an index <  shift      -> the codon is skipped
+ *               a base N / not resident-> UNKNOWN                                              d_s = 0xFFFD
+ *               CODE[codon] == '*'     -> PTC at c                                             d_s = c - codon
+ *             max_codons codons without any of these -> CAP                                   d_s = 0xFFFE
+ * NMD(s)    PTC found, t has a junction, J_t - e >= nmd_window with e = 1 + the transcript index of the stop codon's third base,
+ *             and (start_window == 0 or the transcript index of its first base - shift >= start_window).
+ * ROW       four uint32:  t;  codon | frame << 30;  frac | edge << 16 | flags << 24;  d_1 | d_2 << 16.
+ *             flags: 0 FIRST (S has no previous segment), 1 LAST (no next), 2 PTC1, 3 PTC2, 4 NMD1, 5 NMD2, 6 UNKNOWN (either walk), 7 = 0.
+ * COVERAGE  optional, two uint32 per transcript: the candidates that cut it with NMD1 and NMD2, and the smallest codon among them
+ *             (0xFFFFFFFF: none) - 4.33's PairCoverage.
+ * FILTER    { min_frac, max_frac 0 .. 65535, min_edge 0 .. 255, require, forbid: masks over flag bits 0 .. 6 }: keep iff DEFINED, CODING CUT,
+ *             min_frac <= frac <= max_frac, edge >= min_edge, flags & require == require, flags & forbid == 0. Survivors keep their order.
+ *
+ * The tests of a codon are made in the order they are written; a skipped codon counts as one of the max_codons codons; the
+ * comparison J_t - e >= nmd_window is signed (a stop in the last segment has e > J_t and is never NMD).
+ * Integers only.  The output is a function of the inputs alone: it does not depend on launch shape or wave order.  Only the
+ * coverage uses atomics: integer add and min, which commute.
+ *
+ * vsc_knockout_site_text (host only): the ROW of the one site at (contig, pos, strand) from letters, as vsc_effects_site_text
+ * reads them: texts[c] holds the letters of contig c (any case, a letter other than ACGT is an N).  The same inline functions
+ * as the kernels', on planes packed from the letters on every call: a definition to test against, not a fast path.
+ *
+ * vsc_loci_knockout: loci are host entries in any order, duplicates allowed.  rows (optional): rows[4 i .. 4 i + 3] = the ROW of
+ * loci[i].  coverage (optional): 2 n_tx entries.  stats (optional): the defined and the undefined candidates (they add up to
+ * n), the coding cuts, the non-coding cuts at a JUNCTION, the rows with PTC1 / PTC2, with NMD1 / NMD2 and with UNKNOWN, the
+ * candidates the occupancy bitmap answered without a segment search, the drains of the kernel's queue and the entries they
+ * held, the transcripts with a covered candidate, the kernel's time and the call's wall time in milliseconds.  n == 0:
+ * VSC_OK, nothing is launched, the coverage says "none".  vsc_guides_knockout works over the candidates where they lie on the
+ * device and requires site_len == 23; vsc_pattern_guides_knockout is the same for vsc_pattern_guides: site_len is the
+ * pattern's length, which the CALLER vouches for.  vsc_guides_filter_knockout / vsc_pattern_guides_filter_knockout: *out = the
+ * candidates of `in` that pass FILTER, codes and loci copied unchanged in the input's order, as vsc_guides_filter_effects.
+ * vsc_ctx_timing reports the kernel as score_ms and genome_bytes = 32 n for the rows.
+ *
+ * VSC_ERR_INVALID, checked on the host before anything is written (vsc_last_error names the reason): a value outside SHAPE or
+ * a non-zero reserved field; a mask with bit 7 or above; min_frac > max_frac, max_frac > 65535, min_edge > 255; NULL arguments;
+ * a genome or object of another context; a CDS built with another contig table than the genome's; a code with fewer than 64
+ * letters; site_len != 23 for vsc_guides.  VSC_ERR_RANGE: n above 0xFFFFFFFE.  Uploads and results use context scratch;
+ * vsc_ctx_release_scratch gives it back, the device copies of the per-transcript table and the occupancy bitmap included.
+ *
+ * Not offered: introns in the 3' UTR (the last junction is the last CDS junction); overlapping isoforms in one call (call once
+ * per transcript set); in-frame indels (that is vsc_*_microhomology's out-of-frame share); trained indel-outcome models; a
+ * vsc_multi_* entry.
+ */
+#define VSC_KNOCKOUT_UNDEFINED 0xFFFFFFFFu
+#define VSC_KNOCKOUT_END 0xFFFFu
+#define VSC_KNOCKOUT_CAP 0xFFFEu
+#define VSC_KNOCKOUT_UNKNOWN 0xFFFDu
+#define VSC_KNOCKOUT_FIRST 1u
+#define VSC_KNOCKOUT_LAST 2u
+#define VSC_KNOCKOUT_PTC1 4u
+#define VSC_KNOCKOUT_PTC2 8u
+#define VSC_KNOCKOUT_NMD1 16u
+#define VSC_KNOCKOUT_NMD2 32u
+#define VSC_KNOCKOUT_UNKNOWN_WALK 64u
+typedef struct {
+    uint32_t site_len, cut, nmd_window, start_window, max_codons;
+    uint32_t reserved[3]; /* 0 */
+} vsc_knockout_shape;
+typedef struct {
+    uint32_t min_frac, max_frac, min_edge;
+    uint32_t require, forbid; /* masks over VSC_KNOCKOUT_FIRST .. VSC_KNOCKOUT_UNKNOWN_WALK */
+    uint32_t reserved[3];     /* 0 */
+} vsc_knockout_limits;
+typedef struct {
+    uint64_t defined, undefined;
+    uint64_t coding, junction;
+    uint64_t ptc[2], nmd[2]; /* frames +1, +2 */
+    uint64_t unknown;
+    uint64_t past_find, drains, drained;
+    uint64_t transcripts_covered;
+    uint64_t reserved; /* 0 */
+    double kernel_ms, wall_ms;
+} vsc_knockout_stats;
+#ifdef __cplusplus
+static_assert(sizeof(vsc_knockout_shape) == 32 && sizeof(vsc_knockout_limits) == 32 && sizeof(vsc_knockout_stats) == 128, "vsc_knockout layout");
+#else
+_Static_assert(sizeof(vsc_knockout_shape) == 32 && sizeof(vsc_knockout_limits) == 32 && sizeof(vsc_knockout_stats) == 128, "vsc_knockout layout");
+#endif
+int vsc_knockout_site_text(const vsc_cds *cds, const char *const *texts /* one per contig */, uint32_t contig, uint32_t pos, uint32_t strand,
+                           const vsc_knockout_shape *shape, const char *code /* 64 letters, or NULL */, uint32_t *row /* 4 */);
+int vsc_loci_knockout(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci /* host, any order, duplicates allowed */, uint64_t n,
+                      const vsc_knockout_shape *shape, const vsc_cds *cds, const char *code, uint32_t *rows /* host, 4 n, optional */,
+                      uint32_t *coverage /* host, 2 n_tx, optional */, vsc_knockout_stats *stats /* optional */);
+int vsc_guides_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_knockout_shape *shape, const vsc_cds *cds,
+                        const char *code, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats);
+int vsc_pattern_guides_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_knockout_shape *shape,
+                                const vsc_cds *cds, const char *code, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats);
+int vsc_guides_filter_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_knockout_shape *shape, const vsc_cds *cds,
+                               const char *code, const vsc_knockout_limits *limits, vsc_guides **out);
+int vsc_pattern_guides_filter_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_knockout_shape *shape,
+                                       const vsc_cds *cds, const char *code, const vsc_knockout_limits *limits, vsc_pattern_guides **out);
+
 /* ---- known variation under candidate guides: population-robust and allele-specific design -------- */
 /*
  * "Does this guide's own site carry known variation, where, and how common is it?" - the join of every candidate's site with a

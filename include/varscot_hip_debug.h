@@ -99,6 +99,18 @@ int vsc_debug_fold_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
 /* The workgroups per CU that motif_rows_kernel's grid (vsc_*_motifs) is capped at: 0 = the default (8), 1 .. 64.  The
  * kernel is grid-stride and its counts are sums of integers: no output bit depends on it. */
 int vsc_debug_motif_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
+/* The workgroups per CU that knockout_rows_kernel's grid (vsc_*_knockout) is capped at: 0 = the default (8), 1 .. 64.
+ * The kernel is grid-stride, its queue belongs to a workgroup and every row is a function of its candidate: no output bit depends
+ * on it.  With few workgroups a workgroup takes many steps, which is how the tests meet the queue's edges. */
+int vsc_debug_knockout_groups_per_cu(vsc_ctx *ctx, uint32_t groups);
+/* on != 0: knockout_rows_kernel runs without its queue - every coding lane walks where it lies, two lanes in 64 busy on a genome.
+ * The variant the queue is measured against (tools/knockout_bench.py); every row, the coverage and the counts but drains /
+ * drained are the same, which then count the wave steps with a coding lane and their coding lanes. */
+int vsc_debug_knockout_in_place(vsc_ctx *ctx, int on);
+/* What vsc_cds_build derived for the knock-out walk (host only): table (optional) = four uint32 per transcript - shift, E_t, J_t,
+ * segments (all 0 for a transcript without a segment); *n_blocks = the bits of the occupancy bitmap, one per 256 global positions;
+ * bitmap (optional) = its (*n_blocks + 31) / 32 words. */
+int vsc_debug_knockout_table(const vsc_cds *cds, uint32_t *table, uint32_t *bitmap, uint32_t *n_blocks);
 
 /* The block of the variation lookup's table on this context: log2 of the global positions per entry, 4 .. 32, or 0 =
  * the default (8).  At 32 the table has one block and the lookup is the plain lower bound over all variants.  No output bit

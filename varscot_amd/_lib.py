@@ -589,6 +589,44 @@ class EffectsStats(C.Structure):
 assert C.sizeof(CdsStats) == 64 and C.sizeof(EffectsStats) == 128 and CDS_SEGMENT_DTYPE.itemsize == 32 and EFFECT_DTYPE.itemsize == 16
 
 
+KNOCKOUT_UNDEFINED = 0xFFFFFFFF  # VSC_KNOCKOUT_UNDEFINED
+KNOCKOUT_END, KNOCKOUT_CAP, KNOCKOUT_UNKNOWN = 0xFFFF, 0xFFFE, 0xFFFD  # d_s of a walk that finds no stop
+KNOCKOUT_FLAG_NAMES = ("first", "last", "ptc1", "ptc2", "nmd1", "nmd2", "unknown")  # flag bit k of a row; VSC_KNOCKOUT_FIRST ..
+
+
+class KnockoutShapeStruct(C.Structure):
+    """vsc_knockout_shape"""
+    _fields_ = [("site_len", C.c_uint32), ("cut", C.c_uint32), ("nmd_window", C.c_uint32), ("start_window", C.c_uint32),
+                ("max_codons", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class KnockoutLimits(C.Structure):
+    """vsc_knockout_limits"""
+    _fields_ = [("min_frac", C.c_uint32), ("max_frac", C.c_uint32), ("min_edge", C.c_uint32), ("require", C.c_uint32),
+                ("forbid", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class KnockoutStats(C.Structure):
+    """vsc_knockout_stats: the defined and undefined candidates of a call (they add up to n), the coding cuts, the non-coding
+    cuts at a junction, the rows with a PTC and with NMD in frames +1 / +2, the rows with an unknown walk, the candidates the
+    occupancy bitmap answered, the drains of the kernel's queue and the entries they held, the transcripts with a candidate
+    that has NMD in both frames, the kernel's and the call's time."""
+    _fields_ = [("defined", C.c_uint64), ("undefined", C.c_uint64), ("coding", C.c_uint64), ("junction", C.c_uint64),
+                ("ptc", C.c_uint64 * 2), ("nmd", C.c_uint64 * 2), ("unknown", C.c_uint64), ("past_find", C.c_uint64),
+                ("drains", C.c_uint64), ("drained", C.c_uint64), ("transcripts_covered", C.c_uint64), ("reserved", C.c_uint64),
+                ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in ("defined", "undefined", "coding", "junction", "unknown", "past_find", "drains", "drained",
+                                                "transcripts_covered")}
+        d.update(ptc=[int(v) for v in self.ptc], nmd=[int(v) for v in self.nmd], kernel_ms=float(self.kernel_ms),
+                 wall_ms=float(self.wall_ms))
+        return d
+
+
+assert C.sizeof(KnockoutShapeStruct) == 32 and C.sizeof(KnockoutLimits) == 32 and C.sizeof(KnockoutStats) == 128
+
+
 class DebugParams(C.Structure):
     """vsc_debug_params (include/varscot_hip_debug.h): test / experiment hooks; 0 or -1 = the library's default."""
     _fields_ = [("seed_groups_per_cu", C.c_uint32), ("seed_reserve", C.c_uint32), ("sort_cap", C.c_uint32),
@@ -873,6 +911,17 @@ SYMBOLS = [
                                             C.c_uint32, C.POINTER(_vp)]),
     ("vsc_pattern_guides_filter_effects", C.c_int, [_vp, _vp, _vp, C.POINTER(EditShapeStruct), C.c_uint32, _vp, C.c_char_p, C.c_uint32,
                                                     C.c_uint32, C.POINTER(_vp)]),
+    ("vsc_knockout_site_text", C.c_int, [_vp, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(KnockoutShapeStruct),
+                                         C.c_char_p, _vp]),
+    ("vsc_loci_knockout", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(KnockoutShapeStruct), _vp, C.c_char_p, _vp, _vp,
+                                    C.POINTER(KnockoutStats)]),
+    ("vsc_guides_knockout", C.c_int, [_vp, _vp, _vp, C.POINTER(KnockoutShapeStruct), _vp, C.c_char_p, _vp, _vp, C.POINTER(KnockoutStats)]),
+    ("vsc_pattern_guides_knockout", C.c_int, [_vp, _vp, _vp, C.POINTER(KnockoutShapeStruct), _vp, C.c_char_p, _vp, _vp,
+                                              C.POINTER(KnockoutStats)]),
+    ("vsc_guides_filter_knockout", C.c_int, [_vp, _vp, _vp, C.POINTER(KnockoutShapeStruct), _vp, C.c_char_p, C.POINTER(KnockoutLimits),
+                                             C.POINTER(_vp)]),
+    ("vsc_pattern_guides_filter_knockout", C.c_int, [_vp, _vp, _vp, C.POINTER(KnockoutShapeStruct), _vp, C.c_char_p,
+                                                     C.POINTER(KnockoutLimits), C.POINTER(_vp)]),
     ("vsc_prime_site_text", C.c_int, [C.c_char_p, C.POINTER(PrimeShapeStruct), C.c_uint32, C.c_uint32, C.c_char_p, _vp, _vp, _vp]),
     ("vsc_loci_prime", C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(PrimeShapeStruct), _vp, C.c_uint64, _vp, _vp, C.c_uint64,
                                  C.POINTER(C.c_uint64), _vp, C.POINTER(PrimeStats)]),
@@ -947,6 +996,9 @@ DEBUG_SYMBOLS = [
     ("vsc_debug_hdr_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_fold_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_motif_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_knockout_groups_per_cu", C.c_int, [_vp, C.c_uint32]),
+    ("vsc_debug_knockout_in_place", C.c_int, [_vp, C.c_int]),
+    ("vsc_debug_knockout_table", C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint32)]),
     ("vsc_debug_variation_block_bits", C.c_int, [_vp, C.c_uint32]),
     ("vsc_debug_genome_from_contigs", C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(_vp)]),
     ("vsc_debug_sort_records", C.c_int, [_vp, _vp, C.POINTER(DebugSortInput), C.POINTER(DebugSortInfo), C.POINTER(_vp)]),

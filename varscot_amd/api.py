@@ -1657,7 +1657,7 @@ def pick_host(contigs, loci, target, key, n_targets, shape, rank=False):
 
 
 # The fixed quantisation of the columns a design call (and the tools' -b) can rank by: (bits, what the column is made from)
-PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20, "fold": 6, "rflp": 6}
+PICK_COLUMNS = {"mit": 14, "table": 14, "eff": 20, "oof": 10, "mh": 20, "fold": 6, "rflp": 6, "knockout": 17}
 
 
 def pick_column(name, values):
@@ -1665,7 +1665,13 @@ def pick_column(name, values):
     specificities; eff: the top 20 bits of order_bits of the linear predictors; oof: floor(1000 oof / sum) of (sum, oof)
     pairs, undefined -> 0; mh: min(sum, 2^20 - 1) of the pairs, undefined -> 0; fold: 32 - starts of the fold rows (fewer stems
     are better), undefined -> 0; rflp: min(popcount(cut & ~elsewhere), 63) of the motif rows (more motifs that lie over the
-    cut and nowhere else in the context are better), undefined -> 0."""
+    cut and nowhere else in the context are better), undefined -> 0; knockout: of the knock-out rows, bit 16 = NMD in both
+    frames, bits 0 .. 15 = 65535 - frac (an earlier cut is better); a row that is undefined or no coding cut -> 0."""
+    if name == "knockout":
+        r = unpack_knockout_row(values)
+        both = (r["flags"] & 0x30) == 0x30
+        key = (both.astype(np.uint64) << np.uint64(16)) | (np.uint64(65535) - r["frac"].astype(np.uint64))
+        return np.where(r["coding"], key, np.uint64(0)).astype(np.uint64)
     if name in ("mit", "table"):  # (NaN and negative values: 0, as the undefined values of the other columns)
         v = np.asarray(values, dtype=np.float64)
         return np.rint(100.0 * np.where(np.isnan(v) | (v <= 0), 0.0, np.minimum(v, 1e6))).astype(np.uint64)
@@ -1686,7 +1692,7 @@ def pick_column(name, values):
         return np.where(undefined | (pairs[:, 0] == 0), np.uint64(0), q).astype(np.uint64)
     if name == "mh":
         return np.where(undefined, np.uint64(0), np.minimum(pairs[:, 0], np.uint64(2 ** 20 - 1))).astype(np.uint64)
-    raise ValueError("a pick column is one of mit, table, eff, oof, mh, fold, rflp")
+    raise ValueError("a pick column is one of mit, table, eff, oof, mh, fold, rflp, knockout")
 
 
 EDIT_UNDEFINED = _lib.EDIT_UNDEFINED  # mask and hits of a candidate whose site is undefined
@@ -2620,6 +2626,113 @@ def effects_pick_inputs(effects, loci, classes=("stop_gained",), extra_columns=(
     return lo[cand], ef["transcript"].astype(np.uint32), pick_key(cols, bits)
 
 
+# ---- knock-out design: cut position, frameshift stops, NMD ----------------------------------------------------
+KNOCKOUT_UNDEFINED = _lib.KNOCKOUT_UNDEFINED  # all four words of the row of a candidate that is not defined
+KNOCKOUT_END, KNOCKOUT_CAP, KNOCKOUT_UNKNOWN = _lib.KNOCKOUT_END, _lib.KNOCKOUT_CAP, _lib.KNOCKOUT_UNKNOWN  # d1 / d2 without a stop
+KNOCKOUT_FLAGS = _lib.KNOCKOUT_FLAG_NAMES  # the name of flag bit k of a row; the bit of a require / forbid mask
+KNOCKOUT_ROW_DTYPE = np.dtype([("transcript", "<u4"), ("codon", "<u4"), ("frame", "u1"), ("frac", "<u2"), ("edge", "u1"), ("flags", "u1"),
+                               ("d1", "<u2"), ("d2", "<u2"), ("coding", "?"), ("defined", "?")])
+
+
+class KnockoutShape:
+    """vsc_knockout_shape: where a nuclease cuts and what counts as a knock-out.  site_len 16..32 is the candidates' length (23
+    for enumerate_guides', the pattern's for enumerate_pattern's); cut 1..site_len - 1: the break lies between read positions
+    cut - 1 and cut of the site (SpCas9: 17; Cas12a TTTV + 23: 22); nmd_window 0..65535: a premature stop triggers
+    nonsense-mediated decay when it ends at least that many coding bases in front of the last exon-exon junction (the 50-55 nt
+    rule); start_window 0..65535: and begins at least that many coding bases behind the transcript's first one (0: the rule is
+    off); max_codons 1..4096: how far a walk looks for a stop.  KNOCKOUT_SHAPES holds the preset "SpCas9" (23, 17, 50, 0,
+    4096).  validate=False passes the numbers to the library as they are (tests)."""
+
+    def __init__(self, site_len=READ_LEN, cut=17, nmd_window=50, start_window=0, max_codons=4096, validate=True):
+        self.site_len, self.cut, self.nmd_window = int(site_len), int(cut), int(nmd_window)
+        self.start_window, self.max_codons = int(start_window), int(max_codons)
+        if validate and not (16 <= self.site_len <= 32 and 1 <= self.cut < self.site_len and 0 <= self.nmd_window <= 65535
+                             and 0 <= self.start_window <= 65535 and 1 <= self.max_codons <= 4096):
+            raise ValueError("a knock-out shape has site_len 16..32, cut 1..site_len - 1, windows 0..65535 and max_codons 1..4096")
+
+    def _struct(self):
+        return _lib.KnockoutShapeStruct(self.site_len, self.cut, self.nmd_window, self.start_window, self.max_codons,
+                                        (C.c_uint32 * 3)(0, 0, 0))
+
+    def __repr__(self):
+        return "KnockoutShape(site_len=%d, cut=%d, nmd_window=%d, start_window=%d, max_codons=%d)" % (
+            self.site_len, self.cut, self.nmd_window, self.start_window, self.max_codons)
+
+
+KNOCKOUT_SHAPES = {"SpCas9": KnockoutShape(READ_LEN, 17, 50, 0, 4096)}
+
+
+def _knockout_shape(shape, what="shape"):
+    if isinstance(shape, str):
+        if shape not in KNOCKOUT_SHAPES:
+            raise ValueError("%s names one of %s, or is a KnockoutShape" % (what, ", ".join(sorted(KNOCKOUT_SHAPES))))
+        shape = KNOCKOUT_SHAPES[shape]
+    if not isinstance(shape, KnockoutShape):
+        raise ValueError("%s must be a KnockoutShape or the name of a preset" % what)
+    return shape
+
+
+def knockout_flag_mask(flags):
+    """The require / forbid mask of flag names (KNOCKOUT_FLAGS), one name, several joined by "+", or a list; None: 0; a number
+    passes as it is."""
+    if flags is None:
+        return 0
+    if isinstance(flags, (int, np.integer)):
+        return int(flags)
+    if isinstance(flags, str):
+        flags = [f for f in flags.split("+") if f]
+    m = 0
+    for f in flags:
+        if f not in KNOCKOUT_FLAGS:
+            raise ValueError("a knock-out flag is one of %s" % ", ".join(KNOCKOUT_FLAGS))
+        m |= 1 << KNOCKOUT_FLAGS.index(f)
+    return m
+
+
+def knockout_cut_frac(share, upper=False):
+    """A share of the protein (0 .. 1) in the units of a row's frac (0 .. 65535), the rule of min_cut_frac= / max_cut_frac=:
+    a lower bound becomes ceil(65536 x share), an upper bound floor(65536 x share), both capped at 65535 - so that the bounds
+    keep exactly the cuts K with share_min <= (K - shift) / B_t <= share_max up to frac's own rounding down."""
+    x = float(share)
+    if not 0.0 <= x <= 1.0:
+        raise ValueError("a share of the protein lies in 0 .. 1")
+    v = int(np.floor(65536.0 * x)) if upper else int(np.ceil(65536.0 * x))
+    return min(v, 65535)
+
+
+def knockout_site_text(cds, texts, contig, pos, strand, shape, code=None):
+    """vsc_knockout_site_text: the row (uint32[4]) of the one site at (contig, pos, strand) from letters, on the host, by the
+    functions the kernels call.  texts: the letters of every contig of the genome the Cds was built for."""
+    shape = _knockout_shape(shape)
+    raw = [t if isinstance(t, bytes) else t.encode() for t in texts]
+    arr = (C.c_char_p * max(len(raw), 1))(*raw)
+    row = np.zeros(4, dtype=np.uint32)
+    sh = shape._struct()
+    check(lib().vsc_knockout_site_text(cds._h, arr, int(contig), int(pos), int(strand), C.byref(sh), _effect_code(code), ptr(row)))
+    return row
+
+
+def unpack_knockout_row(rows):
+    """Knock-out rows uint32[n, 4] (or one row) as a KNOCKOUT_ROW_DTYPE array: transcript, codon, frame, frac (0..65535 along
+    the protein), edge (bases to the nearer end of the segment, capped at 255), flags (bit k: KNOCKOUT_FLAGS[k]), d1, d2 (codons
+    from the cut's codon to the first stop in frame +1 / +2; KNOCKOUT_END / KNOCKOUT_CAP / KNOCKOUT_UNKNOWN), coding, defined.
+    A row that is not defined, or not a coding cut, has zeros but for flags bit 7 = JUNCTION of a non-coding cut."""
+    r = np.asarray(rows, dtype=np.uint32).reshape(-1, 4)
+    out = np.zeros(len(r), dtype=KNOCKOUT_ROW_DTYPE)
+    defined = ~np.all(r == np.uint32(KNOCKOUT_UNDEFINED), axis=1)
+    coding = defined & (r[:, 0] != np.uint32(0xFFFFFFFF))
+    out["defined"], out["coding"] = defined, coding
+    out["transcript"] = np.where(coding, r[:, 0], 0)
+    out["codon"] = np.where(coding, r[:, 1] & np.uint32(0x3FFFFFFF), 0)
+    out["frame"] = np.where(coding, r[:, 1] >> np.uint32(30), 0)
+    out["frac"] = np.where(coding, r[:, 2] & np.uint32(0xFFFF), 0)
+    out["edge"] = np.where(coding, (r[:, 2] >> np.uint32(16)) & np.uint32(0xFF), 0)
+    out["flags"] = np.where(defined, r[:, 2] >> np.uint32(24), 0)
+    out["d1"] = np.where(coding, r[:, 3] & np.uint32(0xFFFF), 0)
+    out["d2"] = np.where(coding, r[:, 3] >> np.uint32(16), 0)
+    return out
+
+
 def _region_filter(regions, scope):
     """(vsc_region_filter or None) for search_select's regions / region_scope arguments."""
     if regions is None:
@@ -3351,7 +3464,8 @@ class Genome:
                           max_variants_by_zone=None, require_variant_zones=None, hdr=None, hdr_edits=None, hdr_cds=None,
                           hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None, max_fold_self=None,
                           max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
-                          forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None):
+                          forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None, knockout=None, knockout_cds=None,
+                          min_cut_frac=None, max_cut_frac=None, min_cut_edge=None, require_knockout=None, forbid_knockout=None):
         """vsc_guides_enumerate_pattern: the candidate guides of this genome (or shard) under an IUPAC pattern of 16..32
         letters - every N-free site that satisfies it, on either strand.  protospacer = (start, length) in read positions
         (pattern_protospacer gives it for a preset): gc[0] <= its G/C <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -3401,6 +3515,13 @@ class Genome:
         motif_right= the vector's text on either side of the cloned spacer (at most 16 letters of A C G T U; default: none) /
         forbid_motifs= / forbid_context_motifs= / require_cut_motifs= names or bit masks / cut_only= (all need motifs=): with one of
         them only the candidates whose row is defined and passes FILTER (vsc_pattern_guides_filter_motifs), after the fold
+        filter.
+        knockout= a KnockoutShape whose site_len is the pattern's length (or the name of a preset of KNOCKOUT_SHAPES) with
+        knockout_cds= a Cds: the candidates' knock-out rows (uint32[n, 4], vsc_pattern_guides_knockout; unpack_knockout_row names
+        the fields) come last of all, after the motif rows.  min_cut_frac= / max_cut_frac= shares of the protein, floats in 0 .. 1
+        (knockout_cut_frac states how they become 0 .. 65535) / min_cut_edge= 0 .. 255 bases to the nearer end of the exon /
+        require_knockout= / forbid_knockout= flag names of KNOCKOUT_FLAGS or masks (all need knockout=): with one of them only
+        the candidates whose cut is a coding cut and passes FILTER (vsc_pattern_guides_filter_knockout), after the motif
         filter."""
         p = pattern if isinstance(pattern, bytes) else pattern.encode()
         ep = params if params is not None else _pattern_enum_params(protospacer, rule, strands, gc, max_t_run, max_guides)
@@ -3417,6 +3538,7 @@ class Genome:
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, len(p))
         fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, len(p))
         mo = self._motif_args(motifs, motif_set, motif_left, motif_right, forbid_motifs, forbid_context_motifs, require_cut_motifs, cut_only, len(p))
+        ko = self._knockout_args(knockout, knockout_cds, min_cut_frac, max_cut_frac, min_cut_edge, require_knockout, forbid_knockout, len(p))
         h = C.c_void_p()
         check(L.vsc_guides_enumerate_pattern(self.ctx._h, self._h, p, len(p), C.byref(ep), iv_ptr, 0 if iv is None else len(iv),
                                              C.byref(h)), self.ctx._h)
@@ -3432,7 +3554,8 @@ class Genome:
                                            (L.vsc_pattern_guides_variation, L.vsc_pattern_guides_filter_variation), hd,
                                            (L.vsc_pattern_guides_hdr, L.vsc_pattern_guides_filter_hdr), fo,
                                            (L.vsc_pattern_guides_fold, L.vsc_pattern_guides_filter_fold), mo,
-                                           (L.vsc_pattern_guides_motifs, L.vsc_pattern_guides_filter_motifs))
+                                           (L.vsc_pattern_guides_motifs, L.vsc_pattern_guides_filter_motifs), ko,
+                                           (L.vsc_pattern_guides_knockout, L.vsc_pattern_guides_filter_knockout))
             h = held[0]
             n = int(L.vsc_pattern_guides_count(h))
             pc, pl = C.c_void_p(), C.c_void_p()
@@ -3467,8 +3590,9 @@ class Genome:
         variants= / max_variant_cost= / max_variants_by_zone= / require_variant_zones=: as enumerate_pattern; only the survivors
         are searched, and the variation rows come after the prime rows.  fold= (and its options): as enumerate_pattern; only the
         survivors are searched, the fold rows come last of the rows but the motif rows, and pick_by= knows the column "fold".
-        motifs= (and its options): as enumerate_pattern; only the survivors are searched, the motif rows come last of the rows, and
-        pick_by= knows the column "rflp"."""
+        motifs= (and its options): as enumerate_pattern; only the survivors are searched, the motif rows come last of the rows but
+        the knock-out rows, and pick_by= knows the column "rflp".  knockout= (and its options): as enumerate_pattern; only the
+        survivors are searched, the knock-out rows come last of the rows, and pick_by= knows the column "knockout"."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_pattern(pattern, protospacer, targets, **filters)
@@ -3502,6 +3626,7 @@ class Genome:
         rest = list(extra)
         linear = rest.pop(0) if filters.get("efficiency") is not None else None
         pairs = rest.pop(0) if filters.get("microhomology") is not None else None
+        kos = rest.pop() if filters.get("knockout") is not None else None
         sites = rest.pop() if filters.get("motifs") is not None else None
         folds = rest[-1] if filters.get("fold") is not None else None
         spec = None
@@ -3510,7 +3635,8 @@ class Genome:
         regions = Regions(self.packed, targets, rule=filters.get("rule", "overlap"))
         try:
             return tuple(out) + self._pick_found(pick, pick_by, pick_groups, regions, found,
-                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites})
+                                                 {"table": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites,
+                                                  "knockout": kos})
         finally:
             regions.close()
 
@@ -3589,10 +3715,10 @@ class Genome:
 
     def _scores_on_handle(self, held, efficiency, min_efficiency, mh, count_fn, eff_fns, mh_fns, free_fn, ed=None, ed_fns=None,
                           fx=None, fx_fns=None, pe=None, pe_fns=None, va=None, va_fns=None, hd=None, hd_fns=None, fo=None,
-                          fo_fns=None, mo=None, mo_fns=None):
+                          fo_fns=None, mo=None, mo_fns=None, ko=None, ko_fns=None):
         """The floors, then the scores over the survivors: the extras of an enumeration, the efficiency predictors before
         the microhomology pairs before the edit rows before the effect rows before the prime rows before the variation rows before the HDR rows
-        before the fold rows before the motif rows.
+        before the fold rows before the motif rows before the knock-out rows.
         held[0] is replaced as _eff_on_handle replaces it."""
         if efficiency is not None:
             self._eff_on_handle(held, efficiency, min_efficiency, count_fn, eff_fns[0], eff_fns[1], free_fn, score=False)
@@ -3612,6 +3738,8 @@ class Genome:
             self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, rows=False)
         if mo is not None:
             self._motif_on_handle(held, mo, count_fn, mo_fns[0], mo_fns[1], free_fn, rows=False)
+        if ko is not None:
+            self._knockout_on_handle(held, ko, count_fn, ko_fns[0], ko_fns[1], free_fn, rows=False)
         extra = ()
         if efficiency is not None:
             extra += (self._eff_on_handle(held, efficiency, None, count_fn, eff_fns[0], eff_fns[1], free_fn),)
@@ -3631,6 +3759,8 @@ class Genome:
             extra += (self._fold_on_handle(held, fo, count_fn, fo_fns[0], fo_fns[1], free_fn, filt=False),)
         if mo is not None:
             extra += (self._motif_on_handle(held, mo, count_fn, mo_fns[0], mo_fns[1], free_fn, filt=False),)
+        if ko is not None:
+            extra += (self._knockout_on_handle(held, ko, count_fn, ko_fns[0], ko_fns[1], free_fn, filt=False),)
         return extra
 
     # ---- guide RNA self-complementarity (vsc_*_fold) -------------------------------------------------------------------
@@ -3917,6 +4047,78 @@ class Genome:
         if want:
             ef = ef[:int(count.value)].copy()
         return rows, ef, cov, stats
+
+    # ---- knock-out design (vsc_*_knockout) ---------------------------------------------------------------------------------
+    @staticmethod
+    def _knockout_args(shape, cds, min_frac, max_frac, min_edge, require, forbid, site_len):
+        """(shape, cds, code, the limits as (min_frac, max_frac, min_edge, require, forbid) or None when none is given) - or None
+        without a shape.  The shares and the names become integers here, once (knockout_cut_frac, knockout_flag_mask)."""
+        given = [v is not None for v in (min_frac, max_frac, min_edge, require, forbid)]
+        if shape is None:
+            if cds is not None or any(given):
+                raise ValueError("knockout_cds / min_cut_frac / max_cut_frac / min_cut_edge / require_knockout / forbid_knockout need "
+                                 "knockout=shape")
+            return None
+        shape = _knockout_shape(shape, "knockout")
+        if shape.site_len != site_len:
+            raise ValueError("the shape's site_len is %d; these candidates are %d bases long" % (shape.site_len, site_len))
+        if not isinstance(cds, Cds):
+            raise ValueError("knockout= needs knockout_cds=, a Cds")
+        limits = None
+        if any(given):
+            limits = (0 if min_frac is None else knockout_cut_frac(min_frac), 65535 if max_frac is None else knockout_cut_frac(max_frac, True),
+                      0 if min_edge is None else int(min_edge), knockout_flag_mask(require), knockout_flag_mask(forbid))
+            if limits[0] > limits[1]:
+                raise ValueError("min_cut_frac is above max_cut_frac")
+            if not 0 <= limits[2] <= 255:
+                raise ValueError("min_cut_edge is 0 .. 255")
+            if (limits[3] | limits[4]) >> 7:
+                raise ValueError("require_knockout / forbid_knockout are masks over the 7 flags")
+        return shape, cds, None, limits
+
+    def _knockout_on_handle(self, held, ko, count_fn, rows_fn, filter_fn, free_fn, rows=True, filt=True):
+        """As _fold_on_handle, for the knock-out rows: ko = what _knockout_args returned.  With limits the handle is first
+        replaced by the filter's result."""
+        shape, cds, code, limits = ko
+        sh = shape._struct()
+        if filt and limits is not None:
+            lim = _lib.KnockoutLimits(*limits, (C.c_uint32 * 3)(0, 0, 0))
+            out = C.c_void_p()
+            check(filter_fn(self.ctx._h, self._h, held[0], C.byref(sh), cds._h, code, C.byref(lim), C.byref(out)), self.ctx._h)
+            free_fn(held[0])
+            held[0] = out
+        if not rows:
+            return None
+        out_rows = np.empty((int(count_fn(held[0])), 4), dtype=np.uint32)
+        st = _lib.KnockoutStats()
+        check(rows_fn(self.ctx._h, self._h, held[0], C.byref(sh), cds._h, code, ptr(out_rows), None, C.byref(st)), self.ctx._h)
+        return out_rows
+
+    def knockout(self, loci_or_found, shape, cds, coverage=False, code=None):
+        """vsc_loci_knockout: where the cut of every candidate falls in the coding sequence of a Cds and what a frameshift
+        there does, on the device from the resident planes.  shape: a KnockoutShape or the name of a preset of
+        KNOCKOUT_SHAPES.  Returns (rows, coverage, stats).  rows uint32[n, 4] (unpack_knockout_row names the fields):
+        transcript; codon | frame << 30; frac | edge << 16 | flags << 24; d1 | d2 << 16 - KNOCKOUT_UNDEFINED four times where
+        the locus is invalid or the site leaves its contig, (0xFFFFFFFF, 0, JUNCTION << 31, 0) where the cut is not inside one
+        segment.  coverage (uint32[cds.n_tx, 2] with coverage=True, else None): the candidates that cut the transcript with
+        NMD in both frames and the smallest codon among them (KNOCKOUT_UNDEFINED: none).  code: 64 letters instead of
+        GENETIC_CODE.  stats: defined, undefined, coding, junction, ptc, nmd (a pair each: frames +1, +2), unknown, past_find,
+        drains, drained, transcripts_covered, kernel_ms, wall_ms.  loci_or_found: as Genome.efficiency takes it.  A base
+        that is not resident on this object (a shard) makes the walk that reads it UNKNOWN."""
+        shape = _knockout_shape(shape)
+        if not isinstance(cds, Cds):
+            raise ValueError("cds must be a Cds")
+        cd = _effect_code(code)
+        _, loci = _pick_loci(loci_or_found)
+        lo = _loci(loci, len(loci))
+        n = len(lo)
+        rows = np.empty((n, 4), dtype=np.uint32)
+        cov = np.empty((cds.n_tx, 2), dtype=np.uint32) if coverage else None
+        st = _lib.KnockoutStats()
+        sh = shape._struct()
+        check(lib().vsc_loci_knockout(self.ctx._h, self._h, ptr(lo), n, C.byref(sh), cds._h, cd, ptr(rows), ptr(cov), C.byref(st)),
+              self.ctx._h)
+        return rows, cov, st.as_dict()
 
     def edit(self, loci_or_found, shape, targets=None, pairs=True, coverage=False, allow_partial=False):
         """vsc_loci_edit: the editing windows of candidates under an EditShape (or the name of a preset of EDITORS), and their
@@ -4486,7 +4688,8 @@ class Genome:
                          variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
                          hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None,
                          max_fold_starts=None, max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
-                         forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None):
+                         forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None, knockout=None, knockout_cds=None,
+                          min_cut_frac=None, max_cut_frac=None, min_cut_edge=None, require_knockout=None, forbid_knockout=None):
         """vsc_guides_enumerate: the candidate guides of this genome (or shard) - every N-free 23-base window that ends in
         `pam` on '+' or starts with its reverse complement on '-' - that lie in `regions` (a Regions, under its own rule; None:
         everywhere), with gc[0] <= G/C of the 20 protospacer bases <= gc[1] (gc[1] = 0: no upper bound) and no run of more
@@ -4536,6 +4739,13 @@ class Genome:
         motif_right= the vector's text on either side of the cloned spacer (at most 16 letters of A C G T U; default: none) /
         forbid_motifs= / forbid_context_motifs= / require_cut_motifs= names or bit masks / cut_only= (all need motifs=): with one of
         them only the candidates whose row is defined and passes FILTER (vsc_guides_filter_motifs), after the fold
+        filter.
+        knockout= a KnockoutShape with site_len 23 (or the name of a preset of KNOCKOUT_SHAPES) with
+        knockout_cds= a Cds: the candidates' knock-out rows (uint32[n, 4], vsc_guides_knockout; unpack_knockout_row names
+        the fields) come last of all, after the motif rows.  min_cut_frac= / max_cut_frac= shares of the protein, floats in 0 .. 1
+        (knockout_cut_frac states how they become 0 .. 65535) / min_cut_edge= 0 .. 255 bases to the nearer end of the exon /
+        require_knockout= / forbid_knockout= flag names of KNOCKOUT_FLAGS or masks (all need knockout=): with one of them only
+        the candidates whose cut is a coding cut and passes FILTER (vsc_guides_filter_knockout), after the motif
         filter."""
         lab = _label_regions(labels, regions)
         p = params if params is not None else _enum_params(pam, strands, gc, max_t_run, max_guides)
@@ -4548,11 +4758,12 @@ class Genome:
         hd = self._hdr_args(hdr, hdr_edits, hdr_cds, hdr_allow_open, READ_LEN)
         fo = self._fold_args(fold, fold_scaffold, max_fold_starts, max_fold_self, max_fold_scaffold, max_fold_seed, READ_LEN)
         mo = self._motif_args(motifs, motif_set, motif_left, motif_right, forbid_motifs, forbid_context_motifs, require_cut_motifs, cut_only, READ_LEN)
+        ko = self._knockout_args(knockout, knockout_cds, min_cut_frac, max_cut_frac, min_cut_edge, require_knockout, forbid_knockout, READ_LEN)
         L = lib()
         h = C.c_void_p()
         check(L.vsc_guides_enumerate(self.ctx._h, self._h, regions._h if regions is not None else None, C.byref(p), C.byref(h)),
               self.ctx._h)
-        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None and fo is None and mo is None:
+        if efficiency is None and mh is None and ed is None and pe is None and vr is None and hd is None and fo is None and mo is None and ko is None:
             return _guides_arrays(h, lambda code: check(code, self.ctx._h), lab)
         held = [h]
         try:
@@ -4565,7 +4776,8 @@ class Genome:
                                            (L.vsc_guides_variation, L.vsc_guides_filter_variation), hd,
                                            (L.vsc_guides_hdr, L.vsc_guides_filter_hdr), fo,
                                            (L.vsc_guides_fold, L.vsc_guides_filter_fold), mo,
-                                           (L.vsc_guides_motifs, L.vsc_guides_filter_motifs))
+                                           (L.vsc_guides_motifs, L.vsc_guides_filter_motifs), ko,
+                                           (L.vsc_guides_knockout, L.vsc_guides_filter_knockout))
         except BaseException:
             L.vsc_guides_free(held[0])
             raise
@@ -4602,7 +4814,8 @@ class Genome:
                variation=None, variants=None, max_variant_cost=None, max_variants_by_zone=None, require_variant_zones=None,
                hdr=None, hdr_edits=None, hdr_cds=None, hdr_allow_open=None, fold=None, fold_scaffold=None, max_fold_starts=None,
                max_fold_self=None, max_fold_scaffold=None, max_fold_seed=None, motifs=None, motif_set=None, motif_left=None, motif_right=None,
-               forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None, **search_options):
+               forbid_motifs=None, forbid_context_motifs=None, require_cut_motifs=None, cut_only=None, knockout=None, knockout_cds=None,
+                          min_cut_frac=None, max_cut_frac=None, min_cut_edge=None, require_knockout=None, forbid_knockout=None, **search_options):
         """Every guide of `regions`, with its specificity: enumerate_guides(regions, ...) followed by summarize(codes,
         max_mismatches, exclude=loci, **search_options) on the same resident genome.  Returns (codes, loci, rows) - or, with
         summarize's own regions= option among the search options, (codes, loci, (rows, rows over the hits in those regions)).
@@ -4629,7 +4842,11 @@ class Genome:
         column "fold" (32 - starts, 6 bits: fewer stems are better).
         motifs= / motif_set= / motif_left= / motif_right= / forbid_motifs= / forbid_context_motifs= / require_cut_motifs= / cut_only=:
         as enumerate_guides; only the survivors are searched, and the motif rows come after the fold rows, before (picks, counts);
-        pick_by= then knows the column "rflp" (the motifs over the cut and nowhere else in the context, 6 bits: more are better)."""
+        pick_by= then knows the column "rflp" (the motifs over the cut and nowhere else in the context, 6 bits: more are better).
+        knockout= / knockout_cds= / min_cut_frac= / max_cut_frac= / min_cut_edge= / require_knockout= / forbid_knockout=: as
+        enumerate_guides; only the survivors are searched, and the knock-out rows come after the motif rows, before (picks,
+        counts); pick_by= then knows the column "knockout" (17 bits: bit 16 = NMD in both frames, bits 0 .. 15 = 65535 - frac, so
+        that among equals the earlier cut wins; no coding cut: 0)."""
         if pick is None and (pick_by is not None or pick_groups is not None):
             raise ValueError("pick_by= / pick_groups= need pick=")
         found = self.enumerate_guides(regions, pam=pam, strands=strands, gc=gc, max_t_run=max_t_run, max_guides=max_guides,
@@ -4646,7 +4863,9 @@ class Genome:
                                       max_fold_scaffold=max_fold_scaffold, max_fold_seed=max_fold_seed, motifs=motifs,
                                       motif_set=motif_set, motif_left=motif_left, motif_right=motif_right, forbid_motifs=forbid_motifs,
                                       forbid_context_motifs=forbid_context_motifs, require_cut_motifs=require_cut_motifs,
-                                      cut_only=cut_only)
+                                      cut_only=cut_only, knockout=knockout, knockout_cds=knockout_cds, min_cut_frac=min_cut_frac,
+                                      max_cut_frac=max_cut_frac, min_cut_edge=min_cut_edge, require_knockout=require_knockout,
+                                      forbid_knockout=forbid_knockout)
         codes, loci = found[0], found[1]
         rows = self.summarize(codes, max_mismatches, exclude=loci, **search_options)
         out = (codes, loci, rows) + tuple(found[2:])
@@ -4655,12 +4874,14 @@ class Genome:
         extra = list(found[3:] if len(found) > 2 and _label_regions(labels, regions) is not None else found[2:])
         linear = extra.pop(0) if efficiency is not None else None
         pairs = extra.pop(0) if microhomology is not None else None
+        kos = extra.pop() if knockout is not None else None
         sites = extra.pop() if motifs is not None else None
         folds = extra[-1] if fold is not None else None
         all_rows = rows[0] if isinstance(rows, tuple) else rows
         spec = np.array([mit_specificity(x) for x in all_rows["mit_sum"]], dtype=np.float64)
         return out + self._pick_found(pick, pick_by, pick_groups, regions, (codes, loci),
-                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites})
+                                      {"mit": spec, "eff": linear, "oof": pairs, "mh": pairs, "fold": folds, "rflp": sites,
+                                       "knockout": kos})
 
     def search_streamed(self, guides, max_mismatches, on_batch, batch=0, extra_pam=None, algorithm="auto"):
         """vsc_search_stream: the reads are searched in batches of `batch` (0 = the library's maximum, 16 384)

@@ -72,6 +72,10 @@
 // (the spacer between --motif-left and --motif-right) and in the genomic context of every found guide: the listing gains the last
 // columns motifsConstruct motifsCut motifsElsewhere motifsCutOnly; --motif-forbid / --motif-forbid-context / --motif-require-cut NAMES
 // (--motif-cut-only) keep the candidates that pass; --motifs-out sites.tsv lists the names per candidate.
+// --knockout [CUT] --knockout-cds cds.bed (needs -E, one device; tools/knockout_host.hpp) says where the cut of every found guide falls in
+// the coding sequence and what a frameshift there does: the listing gains the last columns koTranscript koCodon koFrame koCutPct
+// koEdge koPtc1 koPtc2 koNmd; --knockout-nmd WINDOW[,START] sets the decay rule, --knockout-filter MINPCT,MAXPCT[,EDGE[,REQUIRE[/FORBID]]]
+// keeps the candidates that pass, --knockout-out rows.tsv lists the rows with their flags.
 // --fold SpCas9 | Cas12a | SPEC (needs -E, one device; tools/fold_host.hpp) counts the stems the guide RNA of every found guide can
 // form with itself and with the --fold-scaffold text (at most 128 letters, or @FILE; default: none): the -E listing gains the last
 // columns foldStarts foldSelf foldScaffold foldSeed; --max-fold STARTS[,SELF[,SCAF[,SEED]]] keeps the candidates within the limits.
@@ -92,6 +96,7 @@
 #include "hdr_host.hpp"
 #include "fold_host.hpp"
 #include "motif_host.hpp"
+#include "knockout_host.hpp"
 #include "variation_host.hpp"
 #include "pick_host.hpp"
 #include "vsc_host.hpp"
@@ -326,7 +331,20 @@ int main(int argc, char **argv)
         {'>', "motif-require-cut", "With --motifs: NAMES - keep the candidates with one of these motifs over the cut zone", false},
         {'/', "motif-cut-only", "With --motif-require-cut: ... and nowhere else in the context", false, false},
         {'?', "motifs-out", "With --motifs: path to the listing, one line per candidate: #guideId construct cut elsewhere cutOnly (names)", false},
+        {0, "knockout", "With -E: knock-out design - where the cut of every found guide falls in the coding sequence of --knockout-cds and what "
+                        "a frameshift there does; CUT = the break lies between read positions CUT - 1 and CUT (default: 17 for sites of 23 "
+                        "bases, 22 for sites of 27); the guide listing gains the last columns koTranscript koCodon koFrame koCutPct koEdge "
+                        "koPtc1 koPtc2 koNmd (one device)", false},
+        {0, "knockout-cds", "With --knockout: path to the coding segments (.bed, BED6: chrom start end transcript phase strand)", false},
+        {0, "knockout-nmd", "With --knockout: WINDOW[,START] - a premature stop triggers nonsense-mediated decay when it ends at least WINDOW "
+                            "coding bases in front of the last exon-exon junction (default 50) and begins at least START behind the first "
+                            "coding base (default 0: off)", false},
+        {0, "knockout-filter", "With --knockout: MINPCT,MAXPCT[,EDGE[,REQUIRE[/FORBID]]] - only the coding cuts between MINPCT and MAXPCT per cent "
+                               "of the protein, at least EDGE bases from the exon's ends, with every REQUIRE and no FORBID flag (names joined "
+                               "by + out of first last ptc1 ptc2 nmd1 nmd2 unknown)", false},
+        {0, "knockout-out", "With --knockout: path to the listing, one line per candidate: #guideId, the eight columns, koFlags", false},
     };
+    opts[65].optional_value = true;  // --knockout [CUT]
     const int pr = parse_args(argc, argv, opts, "Pattern search",
                               "Off-target search for any PAM and any guide of 16..32 bases: the sites of the genome that satisfy "
                               "the pattern and differ from a guide in at most -M compared positions. Give -O, -T or both. "
@@ -593,6 +611,17 @@ int main(int argc, char **argv)
         }
     }
 
+    // --knockout and its options: where the found guides cut the coding sequence, and what a frameshift there does
+    KnockoutOptions knockout;
+    {
+        const std::string why = parse_knockout_options(opts[65], opts[66], opts[67], opts[68], opts[69], enumerate, opts[4].value.find(',') != std::string::npos, (uint32_t)pattern.size(), &knockout);
+        if (!why.empty()) {
+            std::fprintf(stderr, "%s: %s\n", argv[0], why.c_str());
+            return 1;
+        }
+    }
+    CdsOfFile knockout_coding;
+
     // --variants and its options: the known variants under the found guides' own sites
     VariationOptions variation;
     {
@@ -833,6 +862,14 @@ int main(int argc, char **argv)
                 vsc_pattern_guides_free(found);
                 found = kept;
             }
+            if (knockout.on) read_cds(knockout.cds_path, ix.names, ix.contigs, &knockout_coding);
+            if (knockout.filtered) {  // --knockout-filter: the same, after the motif FILTER
+                vsc_pattern_guides *kept = nullptr;
+                if (vsc_pattern_guides_filter_knockout(ctx, genome, found, &knockout.shape, knockout_coding.cds, nullptr, &knockout.limits, &kept) != VSC_OK)
+                    throw std::runtime_error(vsc_last_error(ctx));
+                vsc_pattern_guides_free(found);
+                found = kept;
+            }
             if (efficient) {
                 eff_linear.resize(vsc_pattern_guides_count(found));
                 if (eff_any_score(ctx, genome, found, eff_model, eff_linear.data()) != VSC_OK) throw std::runtime_error(vsc_last_error(ctx));
@@ -887,6 +924,10 @@ int main(int argc, char **argv)
                                                       motif.right.c_str(), (uint32_t)motif.right.size(), motif.motifs.data(),
                                                       (uint32_t)motif.motifs.size(), motif_rows.data(), nullptr, nullptr) != VSC_OK)
                 throw std::runtime_error(vsc_last_error(ctx));
+            std::vector<uint32_t> knockout_rows(knockout.on ? 4 * vsc_pattern_guides_count(found) : 0);  // --knockout: the rows
+            if (knockout.on && vsc_pattern_guides_knockout(ctx, genome, found, &knockout.shape, knockout_coding.cds, nullptr, knockout_rows.data(),
+                                                           nullptr, nullptr) != VSC_OK)
+                throw std::runtime_error(vsc_last_error(ctx));
             const uint64_t n = vsc_pattern_guides_count(found);
             const uint64_t *codes = nullptr;
             st = vsc_pattern_guides_data(found, &codes, &loci);
@@ -898,7 +939,7 @@ int main(int argc, char **argv)
                 << (pick.on ? "\tpickTarget\tpickRank" : "") << (edit.on ? "\teditWindow\teditable\ttargetsHit" : "")
                 << (fx.on ? "\tcodingEdits\tstopGained\tmissense\tsynonymous" : "") << (prime.on ? "\tpbsLen\tpbsGC\tprimePairs" : "")
                 << (hdr.on ? "\thdrPairs\thdrUsable" : "") << (fold.on ? "\tfoldStarts\tfoldSelf\tfoldScaffold\tfoldSeed" : "")
-                << (motif.on ? "\tmotifsConstruct\tmotifsCut\tmotifsElsewhere\tmotifsCutOnly" : "") << '\n';
+                << (motif.on ? "\tmotifsConstruct\tmotifsCut\tmotifsElsewhere\tmotifsCutOnly" : "") << (knockout.on ? knockout_header() : "") << '\n';
             guides.resize(n);
             letters.resize(n * len);
             for (uint64_t i = 0; i < n; ++i) {
@@ -928,6 +969,7 @@ int main(int argc, char **argv)
                 if (hdr.on) ecol += hdr_columns(&hdr_rows[2 * i]);
                 if (fold.on) ecol += fold_columns(&fold_rows[2 * i]);
                 if (motif.on) ecol += motif_columns(motif, &motif_rows[3 * i]);
+                if (knockout.on) ecol += knockout_columns(&knockout_rows[4 * i], knockout_coding.transcripts);
                 if (pick.on) pick_lines.push_back(line), edit_cols.push_back(ecol);
                 else out << line << ecol << '\n';
             }
@@ -960,6 +1002,11 @@ int main(int argc, char **argv)
                 std::vector<std::string> ids;
                 for (const auto &g : guides) ids.push_back(g.id);
                 write_motifs(motif, motif_rows, ids);
+            }
+            if (knockout.on && !knockout.out_path.empty()) {
+                std::vector<std::string> ids;
+                for (const auto &g : guides) ids.push_back(g.id);
+                write_knockout(knockout.out_path, knockout_rows, knockout_coding.transcripts, ids);
             }
             if (!out) throw std::runtime_error("Write error on " + opts[7].value);
         }

@@ -418,6 +418,7 @@ struct Option {
     bool has_value = true;
     std::string value;
     bool set = false;
+    bool optional_value = false;  // the value may be left out: the next argument is taken unless it starts with '-'
 };
 
 // returns 0 = ok, 1 = parse error (message printed), 2 = help printed
@@ -425,7 +426,10 @@ inline int parse_args(int argc, char **argv, std::vector<Option> &opts, const ch
 {
     auto usage = [&]() {
         std::printf("%s\n\n%s\n\nOPTIONS\n", title, description);
-        for (auto &o : opts) std::printf("  -%c, --%s %s\n        %s\n", o.short_name, o.long_name, o.has_value ? "ARG" : "", o.help);
+        for (auto &o : opts) {
+            if (o.short_name) std::printf("  -%c, --%s %s\n        %s\n", o.short_name, o.long_name, o.has_value ? "ARG" : "", o.help);
+            else std::printf("  --%s %s\n        %s\n", o.long_name, o.optional_value ? "[ARG]" : o.has_value ? "ARG" : "", o.help);  // (long only)
+        }
         std::printf("  -h, --help\n        Display this help message.\n");
     };
     for (int i = 1; i < argc; ++i) {
@@ -438,7 +442,7 @@ inline int parse_args(int argc, char **argv, std::vector<Option> &opts, const ch
         std::string inline_value;
         bool has_inline = false;
         for (auto &o : opts) {
-            if ((a.size() == 2 && a[0] == '-' && a[1] == o.short_name) || a == std::string("--") + o.long_name) hit = &o;
+            if ((a.size() == 2 && a[0] == '-' && o.short_name && a[1] == o.short_name) || a == std::string("--") + o.long_name) hit = &o;
             const std::string pre = std::string("--") + o.long_name + "=";
             if (a.compare(0, pre.size(), pre) == 0) {
                 hit = &o;
@@ -453,6 +457,8 @@ inline int parse_args(int argc, char **argv, std::vector<Option> &opts, const ch
         if (hit->has_value) {
             if (has_inline) {
                 hit->value = inline_value;
+            } else if (hit->optional_value && (i + 1 >= argc || argv[i + 1][0] == '-')) {
+                hit->value.clear();
             } else {
                 if (i + 1 >= argc) {
                     std::fprintf(stderr, "%s: option requires an argument -- %s\n", argv[0], a.c_str());

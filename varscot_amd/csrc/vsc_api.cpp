@@ -253,7 +253,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
                          &ctx->varmap_buf, &ctx->var_state, &ctx->var_excl, &ctx->var_labels, &ctx->pairs_tabs, &ctx->pairs_items,
                          &ctx->pairs_out, &ctx->bulge_tabs, &ctx->sites_tabs, &ctx->bulge_table_buf, &ctx->site_table_tabs, &ctx->site_table_scores,
                          &ctx->pattern_tabs, &ctx->pattern_table_buf, &ctx->table_buf, &ctx->table_rows, &ctx->eff_buf, &ctx->eff_trees_buf, &ctx->eff_in,
-                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->cds_buf, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
+                         &ctx->eff_out, &ctx->pick_in, &ctx->pick_tabs, &ctx->pick_recs, &ctx->edit_tabs, &ctx->edit_pairs, &ctx->cds_buf, &ctx->ko_buf, &ctx->pv_shadow_buf, &ctx->pv_state, &ctx->pv_flags})
         b->release();
     ctx->table_serial = 0;
     ctx->pattern_table_serial = 0;
@@ -263,6 +263,7 @@ int vsc_ctx_release_scratch(vsc_ctx *ctx)
     ctx->regions_serial = 0;
     ctx->locate_serial = 0;
     ctx->cds_serial = 0;
+    ctx->ko_serial = 0;
     ctx->varmap_serial = 0;
     ctx->pv_shadow_serial = 0;
     for (auto &b : ctx->spare_records) b.release();
@@ -6416,6 +6417,32 @@ int effects_upload_cds(vsc_ctx *ctx, const vsc_cds *cds, CdsView &v)
     return VSC_OK;
 }
 
+// the planes of the letters of a CDS object's contigs, as the genome's are packed: what lies between the contigs is N
+// (vsc_effects_site_text, vsc_knockout_site_text); total = the end of the last contig
+struct TextPlanes {
+    std::vector<uint32_t> hi, lo, nm, ends;
+    uint64_t words;
+    TextPlanes(const vsc_cds *cds, const char *const *texts, uint64_t total)
+        : hi((size_t)((total + 31) / 32 + 1), 0u), lo(hi.size(), 0u), nm(hi.size(), 0xFFFFFFFFu), ends(cds->contig_off.size()), words(hi.size())
+    {
+        for (uint32_t c = 0; c < (uint32_t)ends.size(); ++c) {
+            ends[c] = cds->contig_off[c] + cds->contig_len[c];
+            for (uint32_t i = 0; i < cds->contig_len[c]; ++i) {
+                const int b = base_code(texts[c][i]);
+                if (b > 3) continue;
+                const uint64_t x = (uint64_t)cds->contig_off[c] + i;
+                nm[x >> 5] &= ~(1u << (x & 31));
+                hi[x >> 5] |= (uint32_t)(b >> 1) << (x & 31);
+                lo[x >> 5] |= (uint32_t)(b & 1) << (x & 31);
+            }
+        }
+    }
+    EffPlanes view(const vsc_cds *cds) const
+    {
+        return EffPlanes{hi.data(), lo.data(), nm.data(), 0, words, words, cds->contig_off.data(), ends.data(), (uint32_t)ends.size()};
+    }
+};
+
 const CandidateRule kEffectsRule{"the shape's site_len must be 23", kEffectsMaxCount, "more than 0xFFFFFFFE candidates"};
 static_assert((kEffectsCounts + 2) * sizeof(unsigned long long) <= 256, "the counters and the covered transcripts lie in the head");
 
@@ -6569,6 +6596,11 @@ int vsc_cds_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_cds_s
             c->contig_len.push_back(contigs[k].length);
         }
         c->n_tx = n_tx;
+        c->ko_tx.assign(n_tx, KoTx{0u, 0u, 0u, 0u});
+        uint64_t genome_end = 0;
+        for (uint32_t k = 0; k < n_contigs; ++k) genome_end = std::max<uint64_t>(genome_end, (uint64_t)c->contig_off[k] + c->contig_len[k]);
+        c->ko_blocks = (uint32_t)((genome_end + (1u << kKoBlockBits) - 1u) >> kKoBlockBits);
+        c->ko_bitmap.assign((size_t)c->ko_blocks / 32u + 1u, 0u);
         c->gstart.resize((size_t)n);
         c->seg.resize((size_t)n);
         // per transcript: its first segment in genome order, its last one, contig and strand, its bases
@@ -6621,7 +6653,10 @@ int vsc_cds_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_cds_s
             const uint32_t head = t.strand ? t.last : t.first;
             const uint32_t shift = (3u - segments[head].phase) % 3u;
             uint32_t ci = shift;
+            KoTx &ko = c->ko_tx[k];
             for (uint32_t i = head; i != kCdsNone; i = fwd[i]) {
+                ko.junction = ci;  // (the last one stays: the first base of the last segment in transcript order)
+                ++ko.n_seg;
                 if (i != head && segments[i].phase != (3u - ci % 3u) % 3u)
                     return cds_refuse(VSC_ERR_INVALID, "its phase does not continue its transcript's reading frame", i);
                 CdsSeg &sg = c->seg[i];
@@ -6631,7 +6666,11 @@ int vsc_cds_build(const vsc_contig *contigs, uint32_t n_contigs, const vsc_cds_s
                 sg.shift = shift;
                 ci += sg.gend - sg.gstart;
             }
+            ko.shift = shift;
+            ko.end = ci;
         }
+        for (const CdsSeg &sg : c->seg)
+            for (uint32_t b = sg.gstart >> kKoBlockBits; b <= (sg.gend - 1u) >> kKoBlockBits; ++b) c->ko_bitmap[b >> 5] |= 1u << (b & 31u);
         c->stats.segments = n;
         c->stats.transcripts = n_tx;
         c->stats.transcripts_used = used;
@@ -6680,21 +6719,8 @@ int vsc_effects_site_text(const vsc_cds *cds, const char *const *texts, uint32_t
             if (cds->contig_len[c] && !texts[c]) return VSC_ERR_INVALID;
             total = std::max<uint64_t>(total, (uint64_t)cds->contig_off[c] + cds->contig_len[c]);
         }
-        // the planes of the letters, as the genome's are packed: what lies between the contigs is N
-        const uint64_t words = (total + 31) / 32 + 1;
-        std::vector<uint32_t> hi((size_t)words, 0u), lo((size_t)words, 0u), nm((size_t)words, 0xFFFFFFFFu), ends(nc);
-        for (uint32_t c = 0; c < nc; ++c) {
-            ends[c] = cds->contig_off[c] + cds->contig_len[c];
-            for (uint32_t i = 0; i < cds->contig_len[c]; ++i) {
-                const int b = base_code(texts[c][i]);
-                if (b > 3) continue;
-                const uint64_t x = (uint64_t)cds->contig_off[c] + i;
-                nm[x >> 5] &= ~(1u << (x & 31));
-                hi[x >> 5] |= (uint32_t)(b >> 1) << (x & 31);
-                lo[x >> 5] |= (uint32_t)(b & 1) << (x & 31);
-            }
-        }
-        const EffPlanes g{hi.data(), lo.data(), nm.data(), 0, words, words, cds->contig_off.data(), ends.data(), nc};
+        const TextPlanes planes(cds, texts, total);
+        const EffPlanes g = planes.view(cds);
         *n_effects = 0;
         row[0] = row[1] = kEffectsUndefined;
         uint64_t ch = 0, cl = 0;
@@ -6758,6 +6784,274 @@ int vsc_pattern_guides_filter_effects(vsc_ctx *ctx, const vsc_genome *genome, vs
                                       vsc_pattern_guides **out)
 {
     return effects_filter(ctx, genome, in, shape, to, cds, code, false, require, forbid, out, "vsc_pattern_guides_filter_effects");
+}
+
+}  // extern "C"
+
+// ---- knock-out design (the definition: vsc_knockout.h, the kernels: vsc_knockout.hip) ----------------------------
+namespace {
+
+const char *const kKoShapeRule =
+    "site_len 16 .. 32, 1 <= cut <= site_len - 1, nmd_window and start_window <= 65535, 1 <= max_codons <= 4096, reserved fields 0";
+
+bool knockout_params(const vsc_knockout_shape *shape, KoShape &s)
+{
+    s = KoShape{shape->site_len, shape->cut, shape->nmd_window, shape->start_window, shape->max_codons};
+    return !(shape->reserved[0] || shape->reserved[1] || shape->reserved[2]) && knockout_shape_valid(s);
+}
+
+bool knockout_limits(const vsc_knockout_limits *limits, KoFilter &f)
+{
+    f = KoFilter{limits->min_frac, limits->max_frac, limits->min_edge, limits->require, limits->forbid};
+    return !(limits->reserved[0] || limits->reserved[1] || limits->reserved[2]) && knockout_filter_valid(f);
+}
+
+// The arguments every device entry shares, checked on the host.
+int knockout_check(vsc_ctx *ctx, const vsc_genome *genome, const vsc_knockout_shape *shape, const vsc_cds *cds, const char *code, KoShape &s,
+                   EffectsCode &ec, const char *who)
+{
+    ctx->err.clear();
+    if (!genome || !shape || !cds) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+    if (genome->ctx != ctx) return fail_in(ctx, VSC_ERR_INVALID, who, "genome belongs to another context");
+    if (!knockout_params(shape, s)) return fail_in(ctx, VSC_ERR_INVALID, who, kKoShapeRule);
+    if (!effects_code(code, ec)) return fail_in(ctx, VSC_ERR_INVALID, who, "the code has fewer than 64 letters");
+    bool same = cds->contig_off.size() == genome->h_contig_off.size() && genome->h_contig_off.size() == genome->h_contig_end.size();
+    for (size_t c = 0; same && c < cds->contig_off.size(); ++c)
+        same = cds->contig_off[c] == genome->h_contig_off[c] && cds->contig_off[c] + cds->contig_len[c] == genome->h_contig_end[c];
+    if (!same) return fail_in(ctx, VSC_ERR_INVALID, who, "the CDS was built with another contig table than the genome's");
+    return VSC_OK;
+}
+
+// the device copy of what the walk reads beside the segments: [per-transcript table][occupancy bitmap], keyed as cds_buf is
+int knockout_upload(vsc_ctx *ctx, const vsc_cds *cds, const KoTx **tx, const uint32_t **bitmap)
+{
+    const size_t tx_bytes = round256(cds->ko_tx.size() * sizeof(KoTx) + sizeof(KoTx)), map_bytes = cds->ko_bitmap.size() * sizeof(uint32_t);
+    if (ctx->ko_serial != cds->serial) {
+        ctx->ko_serial = 0;
+        VSC_HIP(ctx, ctx->ko_buf.ensure(tx_bytes + map_bytes));
+        if (!cds->ko_tx.empty())
+            VSC_HIP(ctx, hipMemcpyAsync(ctx->ko_buf.p, cds->ko_tx.data(), cds->ko_tx.size() * sizeof(KoTx), hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipMemcpyAsync((char *)ctx->ko_buf.p + tx_bytes, cds->ko_bitmap.data(), map_bytes, hipMemcpyHostToDevice, ctx->stream));
+        VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the caller may free the object as soon as its call returns)
+        ctx->ko_serial = cds->serial;
+    }
+    *tx = (const KoTx *)ctx->ko_buf.p;
+    *bitmap = (const uint32_t *)((const char *)ctx->ko_buf.p + tx_bytes);
+    return VSC_OK;
+}
+
+const CandidateRule kKoRule{"the shape's site_len must be 23", kKoMaxCount, "more than 0xFFFFFFFE candidates"};
+static_assert((kKoCounts + 1) * sizeof(unsigned long long) <= 256, "the counters and the covered transcripts lie in the head");
+
+// Rows, coverage and stats of the loci `at`: knockout_rows_kernel alone - the coverage is taken where a row is made.
+int knockout_run(vsc_ctx *ctx, const vsc_genome *genome, const KoShape &shape, const vsc_cds *cds, const EffectsCode &code, const CandidateLoci &at,
+                 uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats, const char *who)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_tx = cds->n_tx;
+    const uint64_t n = at.n;
+    if (stats) *stats = vsc_knockout_stats{};
+    PairCoverage cov(n_tx, coverage, kKoUndefined);
+    if (n == 0) {
+        ctx->timing = vsc_timing{};
+        if (stats) stats->wall_ms = wall_ms_since(t0);
+        return VSC_OK;
+    }
+    VSC_HIP(ctx, hipSetDevice(ctx->device));
+    KoArgs a{};
+    const int urc = effects_upload_cds(ctx, cds, a.cds);
+    if (urc != VSC_OK) return urc;
+    const int krc = knockout_upload(ctx, cds, &a.tx, &a.bitmap);
+    if (krc != VSC_OK) return krc;
+    a.g = eff_planes(genome);
+    a.shape = shape;
+    a.n_blocks = cds->ko_blocks;
+    a.n_tx = (uint32_t)n_tx;
+    a.code = code;
+    a.n = n;
+    const bool cover = n_tx && (coverage || stats);
+    if (cover) {  // edit_tabs: [candidates with NMD in both frames per transcript][their smallest codon]
+        JoinTabs tabs(0, 2 * PairCoverage::bytes(n_tx), 0);
+        VSC_HIP(ctx, ctx->edit_tabs.ensure(tabs.bytes()));
+        tabs.base = (char *)ctx->edit_tabs.p;
+        const int crc = cov.clear(ctx, tabs);
+        if (crc != VSC_OK) return crc;
+        a.cov_count = cov.count;
+        a.cov_min = cov.min;
+    }
+    unsigned long long seen[kKoCounts] = {};
+    const int rrc = rows_pass(ctx, at, sizeof(uint4), rows, seen, kKoCounts, [&](unsigned long long *d_stats, void *d_rows, const uint4 *d_loci) {
+        a.stats = d_stats;
+        a.out = (uint4 *)d_rows;
+        a.loci = d_loci;
+        return launch_knockout_rows(a, ctx->n_cus, ctx->knockout_groups_per_cu, ctx->knockout_in_place, ctx->stream);
+    });
+    if (rrc != VSC_OK) return rrc;
+    if (cover) {
+        const int crc = cov.read(ctx, a.stats + kKoCounts);
+        if (crc != VSC_OK) return crc;
+    }
+    VSC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    const int trc = rows_timing(ctx, n, sizeof(uint4), 0.0f, &ms);
+    if (trc != VSC_OK) return trc;
+    const uint64_t covered = cov.take();
+    if (stats) {
+        stats->defined = seen[0];
+        stats->undefined = seen[1];
+        stats->coding = seen[2];
+        stats->junction = seen[3];
+        stats->ptc[0] = seen[4];
+        stats->ptc[1] = seen[5];
+        stats->nmd[0] = seen[6];
+        stats->nmd[1] = seen[7];
+        stats->unknown = seen[8];
+        stats->past_find = seen[9];
+        stats->drains = seen[10];
+        stats->drained = seen[11];
+        stats->transcripts_covered = covered;
+        stats->kernel_ms = ms;
+        stats->wall_ms = wall_ms_since(t0);
+    }
+    return VSC_OK;
+}
+
+// vsc_guides_knockout / vsc_pattern_guides_knockout: over the candidates where they lie, a host-only object from the host
+template <class Guides>
+int knockout_guides(vsc_ctx *ctx, const vsc_genome *genome, Guides *guides, const vsc_knockout_shape *shape, const vsc_cds *cds, const char *code,
+                    bool need_23, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    KoShape s{};
+    EffectsCode ec{};
+    CandidateLoci at{};
+    const int rc = candidate_front(ctx, guides, need_23, kKoRule, who, at, &s.site_len,
+                                   [&] { return knockout_check(ctx, genome, shape, cds, code, s, ec, who); }, no_refusal);
+    if (rc != VSC_OK) return rc;
+    return knockout_run(ctx, genome, s, cds, ec, at, rows, coverage, stats, who);
+    });
+}
+
+// vsc_guides_filter_knockout / vsc_pattern_guides_filter_knockout: the candidates that pass FILTER, in the input's order
+template <class Guides>
+int knockout_filter(vsc_ctx *ctx, const vsc_genome *genome, Guides *in, const vsc_knockout_shape *shape, const vsc_cds *cds, const char *code,
+                    bool need_23, const vsc_knockout_limits *limits, Guides **out, const char *who)
+{
+    return guarded(ctx, [&]() -> int {
+    KoShape s{};
+    KoFilterArgs a{};
+    const int rc = filter_front(
+        ctx, in, out, need_23, kKoRule, who, &s.site_len, [&] { return knockout_check(ctx, genome, shape, cds, code, s, a.code, who); },
+        [&] {
+            if (!limits) return fail_in(ctx, VSC_ERR_INVALID, who, "null argument");
+            return knockout_limits(limits, a.filter)
+                       ? VSC_OK
+                       : fail_in(ctx, VSC_ERR_INVALID, who,
+                                 "min_frac <= max_frac <= 65535, min_edge <= 255, require / forbid are masks over bits 0 .. 6, reserved fields 0");
+        });
+    if (rc != VSC_OK) return rc;
+    const int urc = effects_upload_cds(ctx, cds, a.cds);
+    if (urc != VSC_OK) return urc;
+    const int krc = knockout_upload(ctx, cds, &a.tx, &a.bitmap);
+    if (krc != VSC_OK) return krc;
+    a.g = eff_planes(genome);
+    a.shape = s;
+    a.n_blocks = cds->ko_blocks;
+    a.n_tx = cds->n_tx;
+    return filter_candidates(ctx, in, a, kEditTile, out, who, [&](bool write) { return launch_knockout_filter(a, write, ctx->stream); });
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsc_debug_knockout_groups_per_cu(vsc_ctx *ctx, uint32_t groups)
+{
+    if (!ctx || groups > kKoMaxGroupsPerCu) return VSC_ERR_INVALID;
+    ctx->knockout_groups_per_cu = groups;
+    return VSC_OK;
+}
+
+int vsc_debug_knockout_in_place(vsc_ctx *ctx, int on)
+{
+    if (!ctx) return VSC_ERR_INVALID;
+    ctx->knockout_in_place = on != 0;
+    return VSC_OK;
+}
+
+int vsc_debug_knockout_table(const vsc_cds *cds, uint32_t *table, uint32_t *bitmap, uint32_t *n_blocks)
+{
+    if (!cds || !n_blocks) return VSC_ERR_INVALID;
+    *n_blocks = cds->ko_blocks;
+    if (table && !cds->ko_tx.empty()) std::memcpy(table, cds->ko_tx.data(), cds->ko_tx.size() * sizeof(KoTx));
+    if (bitmap) std::memcpy(bitmap, cds->ko_bitmap.data(), ((size_t)cds->ko_blocks + 31) / 32 * sizeof(uint32_t));
+    return VSC_OK;
+}
+
+int vsc_knockout_site_text(const vsc_cds *cds, const char *const *texts, uint32_t contig, uint32_t pos, uint32_t strand,
+                           const vsc_knockout_shape *shape, const char *code, uint32_t *row)
+{
+    if (!cds || !shape || !row) return VSC_ERR_INVALID;
+    try {
+        KoShape s{};
+        EffectsCode ec{};
+        if (!knockout_params(shape, s) || !effects_code(code, ec)) return VSC_ERR_INVALID;
+        const uint32_t nc = (uint32_t)cds->contig_off.size();
+        if (nc && !texts) return VSC_ERR_INVALID;
+        uint64_t total = 0;
+        for (uint32_t c = 0; c < nc; ++c) {
+            if (cds->contig_len[c] && !texts[c]) return VSC_ERR_INVALID;
+            total = std::max<uint64_t>(total, (uint64_t)cds->contig_off[c] + cds->contig_len[c]);
+        }
+        const TextPlanes planes(cds, texts, total);
+        knockout_row(planes.view(cds), cds->view(), cds->ko_tx.data(), s, ec.aa, contig, pos, strand, row);
+        return VSC_OK;
+    } catch (const std::bad_alloc &) {
+        return VSC_ERR_NOMEM;
+    } catch (...) {
+        return VSC_ERR_INVALID;
+    }
+}
+
+int vsc_loci_knockout(vsc_ctx *ctx, const vsc_genome *genome, const vsc_locus *loci, uint64_t n, const vsc_knockout_shape *shape,
+                      const vsc_cds *cds, const char *code, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats)
+{
+    return guarded(ctx, [&]() -> int {
+    if (!ctx) return VSC_ERR_INVALID;
+    const char *const fn = "vsc_loci_knockout";
+    KoShape s{};
+    EffectsCode ec{};
+    const int rc = knockout_check(ctx, genome, shape, cds, code, s, ec, fn);
+    if (rc != VSC_OK) return rc;
+    if (n && !loci) return fail_in(ctx, VSC_ERR_INVALID, fn, "null argument");
+    if (n > kKoMaxCount) return fail_in(ctx, VSC_ERR_RANGE, fn, "more than 0xFFFFFFFE candidates");
+    return knockout_run(ctx, genome, s, cds, ec, CandidateLoci{nullptr, loci, n}, rows, coverage, stats, fn);
+    });
+}
+
+int vsc_guides_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *guides, const vsc_knockout_shape *shape, const vsc_cds *cds,
+                        const char *code, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats)
+{
+    return knockout_guides(ctx, genome, guides, shape, cds, code, true, rows, coverage, stats, "vsc_guides_knockout");
+}
+
+int vsc_pattern_guides_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *guides, const vsc_knockout_shape *shape,
+                                const vsc_cds *cds, const char *code, uint32_t *rows, uint32_t *coverage, vsc_knockout_stats *stats)
+{
+    return knockout_guides(ctx, genome, guides, shape, cds, code, false, rows, coverage, stats, "vsc_pattern_guides_knockout");
+}
+
+int vsc_guides_filter_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_guides *in, const vsc_knockout_shape *shape, const vsc_cds *cds,
+                               const char *code, const vsc_knockout_limits *limits, vsc_guides **out)
+{
+    return knockout_filter(ctx, genome, in, shape, cds, code, true, limits, out, "vsc_guides_filter_knockout");
+}
+
+int vsc_pattern_guides_filter_knockout(vsc_ctx *ctx, const vsc_genome *genome, vsc_pattern_guides *in, const vsc_knockout_shape *shape,
+                                       const vsc_cds *cds, const char *code, const vsc_knockout_limits *limits, vsc_pattern_guides **out)
+{
+    return knockout_filter(ctx, genome, in, shape, cds, code, false, limits, out, "vsc_pattern_guides_filter_knockout");
 }
 
 }  // extern "C"

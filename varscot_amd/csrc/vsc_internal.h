@@ -16,6 +16,7 @@
 #include "vsc_prime.h"
 #include "vsc_hdr.h"
 #include "vsc_effects.h"
+#include "vsc_knockout.h"
 
 namespace vsc {
 
@@ -968,6 +969,48 @@ struct EffectsFilterArgs {
 hipError_t launch_effects_rows(const EffectsArgs &args, int n_cus, hipStream_t stream);
 hipError_t launch_effects_records(const EffectsRecordArgs &args, bool write, hipStream_t stream);
 hipError_t launch_effects_filter(const EffectsFilterArgs &args, bool write, hipStream_t stream);
+// vsc_knockout.hip (the definition: vsc_knockout.h)
+// the rows kernel's counters: defined and undefined candidates, coding cuts, junction cuts, PTC and NMD in both frames, rows
+// with an unknown walk, the candidates the bitmap sent past cds_find, the drains of the queue and the entries they held
+constexpr uint32_t kKoCounts = 12;
+struct KoArgs {
+    EffPlanes g;
+    KoShape shape;
+    CdsView cds;
+    const KoTx *tx;               // [n_tx]
+    const uint32_t *bitmap;       // one bit per block of 2^kKoBlockBits global positions, n_blocks of them
+    uint32_t n_blocks, n_tx;
+    EffectsCode code;
+    const uint4 *loci;            // vsc_locus
+    unsigned long long n;
+    uint4 *out;                   // [n] out: ROW
+    unsigned long long *stats;    // [kKoCounts], zeroed before the launch
+    uint32_t *cov_count, *cov_min;  // [n_tx] each: candidates with NMD1 and NMD2 and their smallest codon per transcript, 0 / 0xFFFFFFFF before the launch; null: none
+};
+struct KoFilterArgs {
+    EffPlanes g;
+    KoShape shape;
+    KoFilter filter;
+    CdsView cds;
+    const KoTx *tx;
+    const uint32_t *bitmap;
+    uint32_t n_blocks, n_tx;
+    EffectsCode code;
+    const unsigned long long *in_codes;  // [n] the input's codes and loci
+    const uint4 *in_loci;
+    unsigned long long n;
+    const uint32_t *work;          // null: tiles 0 .. n_work - 1
+    uint32_t n_work;
+    uint32_t *tile_count;          // count pass out: survivors per tile
+    const unsigned long long *tile_off;  // write pass in: their exclusive scan
+    unsigned long long *codes;     // write pass out
+    uint4 *loci;
+};
+// groups_per_cu: workgroups per CU the rows kernel's grid is capped at (0: the default, kKoGroupsPerCu)
+// in_place: the variant without the queue, every coding lane walking where it lies (vsc_debug_knockout_in_place)
+hipError_t launch_knockout_rows(const KoArgs &args, int n_cus, uint32_t groups_per_cu, bool in_place, hipStream_t stream);
+hipError_t launch_knockout_filter(const KoFilterArgs &args, bool write, hipStream_t stream);
+constexpr uint32_t kKoGroupsPerCu = 8, kKoMaxGroupsPerCu = 64;
 hipError_t launch_interleave(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint2 *hl, hipStream_t stream);
 hipError_t launch_score(const ScoreArgs &args, hipStream_t stream);
 hipError_t launch_score_packed(const ScoreArgs &args, uint4 *packed, hipStream_t stream);

@@ -159,6 +159,12 @@ struct vsc_ctx {
     // segments, keyed by the object's serial number as locate_buf is; the call's tables and records lie in edit_tabs / edit_pairs
     vsc::DeviceBuf cds_buf;
     uint64_t cds_serial = 0;  // 0: none resident
+    // vsc_*_knockout: the per-transcript table and the occupancy bitmap of the CDS this context walked last,
+    // beside cds_buf and keyed as it is
+    vsc::DeviceBuf ko_buf;
+    uint64_t ko_serial = 0;  // 0: none resident
+    bool knockout_in_place = false;       // vsc_debug_knockout_in_place: knockout_rows_kernel without its queue
+    uint32_t knockout_groups_per_cu = 0;  // vsc_debug_knockout_groups_per_cu: the cap of knockout_rows_kernel's grid (0: the default)
     // vsc_hits_locate / vsc_guides_locate: the device copy of the label structure of the regions this context located against
     // last - end[], index[], up[], contig offsets and lengths in one buffer, keyed as regions_buf is - and the labels on their
     // way to the host
@@ -277,6 +283,9 @@ struct vsc_cds {
     std::vector<uint32_t> contig_off, contig_len;  // the genome's table the segments were placed in
     std::vector<uint32_t> gstart;                  // vsc::CdsView's arrays
     std::vector<vsc::CdsSeg> seg;
+    std::vector<vsc::KoTx> ko_tx;                  // per transcript, what the knock-out walk reads (vsc_knockout.h); n_tx entries
+    std::vector<uint32_t> ko_bitmap;               // one bit per block of 2^kKoBlockBits global positions that overlaps a segment
+    uint32_t ko_blocks = 0;                        // its bits
     uint32_t n_tx = 0;
     uint64_t serial = 0;  // process-wide, handed out by vsc_cds_build: what a context's device copy is keyed by
     vsc_cds_stats stats{};
